@@ -7,7 +7,13 @@ Cholesky (K3), assemble c0 (K2), forward substitution + fused prediction / varia
 before the timed region; only the 141 KB of prediction coordinates and the 141 KB of results
 cross PCIe inside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n-obs 20000] [--params A|B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n-obs 20000] [--params A|B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else the
+benchmark measures or checks behind the timed region: the sequential reference passes and the bit-for-bit check of the
+timed steps against them (result_check), the roofline and stage figures, the resident-factor prediction, the cold
+PCIe-inclusive pass, one pass of BASELINE configs[3] and the CPU baseline.  --dump-outputs DIR writes what the last
+timed step returned to its caller (pred, pred_err: float64, one entry per grid point) as DIR/<name>.npy.
 
 N > 1 is launched by the driver under torch.distributed.run (one rank per GPU, RCCL): Sigma is
 partitioned 1-D block-column-cyclic, panels are broadcast over xGMI at each Cholesky step, the
@@ -156,6 +162,41 @@ def self_launch(args):
     raise SystemExit(subprocess.run(cmd).returncode)
 
 
+def headline(args, world, n, m, pv, ms_per_step):
+    """The fields every run prints: the metric, its value and the workload it was measured on."""
+    N = 2 * n
+    return {
+        "metric": "cokriging grid-points/s at n_obs=20k bivariate",
+        "value": m / (ms_per_step / 1e3),
+        "unit": "grid-points/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": (f"configs[1]: n_obs={n}/process (N={N}) uniform sites on the unit square, Euclidean, "
+                                f"full 2n x 2n solve, {m}-point grid, closed-form Matern set B (unit square)")
+                   if args.config == 1 else
+                               (f"configs[2]: n_obs={n}/process (N={N}) SIF+XCO2-like residuals on the 0.05-degree "
+                                f"CONUS lattice, haversine, full 2n x 2n solve, {m}-point 0.5-degree grid, "
+                                f"Matern set {args.params}"),
+                   "n_obs": n, "N": N, "m": m, "params": pv, "partition": f"block-column-cyclic x{world}"},
+    }
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: what the last timed step handed its caller, one DIR/<name>.npy per array (float64).  The inputs
+    are seeded (synth), so two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -166,9 +207,15 @@ def main():
                     help="index into BASELINE.json configs: 2 (default, the metric's config: CONUS lattice, haversine) "
                          "or 1 (unit square, Euclidean, n_obs = 5000, 100 x 100 grid -- a side measurement)")
     ap.add_argument("--params", default="A")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything else the benchmark measures or checks (sequential passes and "
+                         "result_check, roofline and stages, resident-factor prediction, cold pass, configs[3], CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned (pred, pred_err) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-config3", action="store_true",
-                    help="skip the secondary block: one pass of BASELINE configs[3] (n_obs = 50 000 per process, N = 100 000) on the same ranks")
+                    help="with --full: skip the secondary block: one pass of BASELINE configs[3] (n_obs = 50 000 per process, "
+                         "N = 100 000) on the same ranks")
     ap.add_argument("--sweeps", default="overlapped", choices=["overlapped", "sequential"],
                     help="single GPU: the timed step's factorisation and substitution as two overlapped sweeps (ck_factor_predict, "
                          "the product path, default) or one after the other (ck_factor, ck_predict: what the profiling scripts "
@@ -177,6 +224,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args)   # does not return
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -227,7 +276,7 @@ def main():
         name, value = kv.split("=")
         h.set_option(name.strip(), int(value))
     if world == 1:
-        h.set_option("time_gemm", 1)
+        h.set_option("time_gemm", 1)   # also in a plain run: the timed steps are the same with and without --full
 
         def step():
             # the product path (joint_prediction.Predictor.__call__ on a new model): assemble Sigma, assemble c0, then the
@@ -298,6 +347,16 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pred": pred, "pred_err": err})
+    if not args.full:
+        # a plain run ends here: everything below measures or checks something besides the headline figure (--full)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(headline(args, world, n, m, pv, ms_per_step)), flush=True)
+        return
     tim_fused = tim
     seq_ms = None
     result_check = None
@@ -433,27 +492,7 @@ def main():
         dist.destroy_process_group()
         dist = None
     if rank == 0:
-        out = {
-            "metric": "cokriging grid-points/s at n_obs=20k bivariate",
-            "value": m / (ms_per_step / 1e3),
-            "unit": "grid-points/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": (f"configs[1]: n_obs={n}/process (N={N}) uniform sites on the unit square, Euclidean, "
-                                    f"full 2n x 2n solve, {m}-point grid, closed-form Matern set B (unit square)")
-                       if args.config == 1 else
-                                   (f"configs[2]: n_obs={n}/process (N={N}) SIF+XCO2-like residuals on the 0.05-degree "
-                                    f"CONUS lattice, haversine, full 2n x 2n solve, {m}-point 0.5-degree grid, "
-                                    f"Matern set {args.params}"),
-                       "n_obs": n, "N": N, "m": m, "params": pv, "partition": f"block-column-cyclic x{world}"},
-        }
+        out = headline(args, world, n, m, pv, ms_per_step)
         nK = -(-N // 512)
         Npad = nK * 512
         cov_bytes = 8.0 * (N * (N + 1) / 2)

@@ -1,4 +1,4 @@
-"""Copy the summaries of scripts/profile_round.sh from gpurun_out/ into profiles/ (tracked) and derive
+"""Copy the summaries of scripts/profile_round.sh from $CK_PROFILE_OUT (default profile_out/) into profiles/ (tracked) and derive
 profiles/<tag>_traffic.json: HBM-side bytes per launch of the dominant kernel from the FETCH_SIZE / WRITE_SIZE passes,
 corrected as /opt/skills/guides/MI355X_MICROARCH.md prescribes, next to the algorithmic bytes of the same launches.
 usage: python scripts/collect_profiles.py [tag]"""
@@ -12,7 +12,7 @@ import pandas as pd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r04"
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.environ.get("CK_PROFILE_OUT") or os.path.join(ROOT, "profile_out"), os.path.join(ROOT, "profiles")
 
 
 def cp(src, dst):

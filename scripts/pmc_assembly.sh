@@ -1,7 +1,7 @@
 #!/bin/bash
 # LDS / VALU counters of the table-path assembly kernel (scripts/diag_assembly.py)
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-OUT=$ROOT/gpurun_out/pmc_assembly
+OUT=$(realpath -m "${CK_PROFILE_OUT:-$ROOT/profile_out}")/pmc_assembly
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU --kernel-trace --output-format csv -d $OUT -- python3 $ROOT/scripts/diag_assembly.py "$@" > $OUT/log.txt 2>&1

@@ -3,7 +3,7 @@
 # usage: scripts/pmc_kernel.sh <tag> <kernel-name-regex> <script.py> [args...]      (run from the repo root via gpurun)
 TAG=$1; PAT=$2; shift 2
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-OUT=$ROOT/gpurun_out/pmc_$TAG
+OUT=$(realpath -m "${CK_PROFILE_OUT:-$ROOT/profile_out}")/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA --kernel-trace --output-format csv -d $OUT/p1 -- python3 $ROOT/"$@" > $OUT/log1.txt 2>&1 || echo "pass 1 failed"

@@ -2,7 +2,7 @@
 # per-kernel times of the local predictor bench (rocprofv3 kernel trace); usage: scripts/prof_local.sh <tag> <bench_local args...>
 TAG=$1; shift
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-OUT=$ROOT/gpurun_out/prof_local_$TAG
+OUT=$(realpath -m "${CK_PROFILE_OUT:-$ROOT/profile_out}")/prof_local_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o lt -- python3 $ROOT/scripts/bench_local.py "$@" > $OUT/run.log 2>&1

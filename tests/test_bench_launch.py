@@ -35,7 +35,7 @@ def test_world_size_mismatch_fails():
 def test_self_launch_two_ranks_on_one_gpu_reports_breakdown():
     """The driver's N > 1 command without a launcher: bench.py spawns the ranks itself (gloo rehearsal of the
     multi-rank path on one GPU) and rank 0's line carries every rank's panel / update / broadcast-wait times."""
-    r = _run(["--gpus", "2", "--n-obs", "2200", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+    r = _run(["--gpus", "2", "--n-obs", "2200", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"],
              {"CK_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")][-1]
@@ -50,3 +50,25 @@ def test_self_launch_two_ranks_on_one_gpu_reports_breakdown():
     assert out["roofline"]["frac"] > 0 and out["roofline"]["traffic_source"]
     ca = out["stages"]["cov_assembly"]
     assert ca["K1_sigma_rank0"]["GBs"] > 0 and ca["K2_c0_rank0"]["GBs"] > 0 and out["stages"]["rank0"]["update_ms"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_headline_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) prints the headline fields only, and --dump-outputs writes what the last timed step
+    returned: pred and pred_err, float64, one entry per grid point -- the same bits from one run to the next."""
+    lines = []
+    for d in ("a", "b"):
+        r = _run(["--config", "1", "--n-obs", "1000", "--steps", "2", "--warmup", "1",
+                  "--dump-outputs", str(tmp_path / d)], {})
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1]))
+    out = lines[0]
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["dtype"] == "f64"
+    assert out["value"] == pytest.approx(out["config"]["m"] / (out["ms_per_step"] / 1e3))
+    for k in ("roofline", "stages", "result_check", "cpu_baseline", "config3", "pcie_inclusive"):
+        assert k not in out
+    import numpy as np
+    for name in ("pred", "pred_err"):
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float64 and a.shape == (out["config"]["m"],) and np.all(np.isfinite(a))
+        assert np.array_equal(a, b)
