@@ -142,6 +142,24 @@ int ck_factor_predict(ck_handle* h, int i, const double* pcoords_host, int64_t m
  * not be repeated after it).  Needs m (m + 512) / 2 more doubles of device memory. */
 int ck_verify_model(ck_handle* h, int64_t* info);
 
+/* Block (areal) cokriging of process i on the resident factor (needs ck_factor; single-process form).
+ * block[a] in [0, r) names the block of site a, every block non-empty; weight[a] finite.
+ * pred / pred_err: r values; cov: r x r row-major A S A^T, or NULL to skip it.
+ * A is the r x m matrix A[b, a] = weight[a] for the sites a of block b, S = C_pp - c0^T Sigma^-1 c0 the posterior covariance
+ * of the point predictions (nugget where h == 0, as ck_predict / ck_verify_model):  pred_b = sum_a w_a pred_a,
+ * pred_err_b = nan_to_num(sqrt((A S A^T)_bb)).  A block of one site with weight 1 is that site's ck_predict.
+ * The point right-hand sides (K2) are folded into r block rows, so the forward sweep runs over r + 1 rows instead of m + 1;
+ * the sites are assembled in chunks of option "block_chunk" sites (0, default: from the device memory the handle may use)
+ * and every block's members are summed in the caller's order whatever the chunking: repeated calls give the same bits.
+ * cov is refused for r > 65 536 blocks.  The prior covariance of the blocks costs sum_b n_b^2 exact covariance
+ * evaluations (with cov: m^2 / 2 + O(m)), spread over the chip in pieces of 512 pairs whatever the block sizes.
+ * Needs (roundup(r + 1, 256) N + O(m)) doubles of device memory besides the point rows of one chunk, and with cov the
+ * r (r + 512) / 2 doubles of ck_verify_model's Schur buffers plus r (r + 1) / 2 piece offsets (8 bytes each, on the host
+ * and the device).  Afterwards -- also after a call that failed once it had started -- ck_verify_model and ck_aux_finish
+ * fail until the next ck_predict / ck_aux_begin (the rows are block sums).  ck_timings [16 ..] describe the call (slots 0 .. 15 are left as they were). */
+int ck_predict_blocks(ck_handle* h, int i, const double* pcoords_host, int64_t m, const int32_t* block_host,
+                      const double* weight_host, int32_t r, double* pred_host, double* pred_err_host, double* cov_host);
+
 /* Leave-one-out cross-validation of process i at all its data sites from ONE factorisation
  * (Predictor.cross_validation, src/joint_prediction.py:207-257, which re-solves per datum):
  * pred_q = z_q - (Sigma^-1 z)_q / (Sigma^-1)_qq, pred_err_q = sqrt(1 / (Sigma^-1)_qq); n_i values
@@ -320,7 +338,11 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * (k_tall_group_d; launches of the two streams overlap each other, so the sum exceeds the span); [10] counts device work only
  * (counting pass + solve), [14] = host milliseconds the last ck_predict_local / ck_local_reserve spent growing the scratch slab
  * (hipMalloc; 0 when it did not grow); [15] after a tall sweep with "time_gemm": the union of the intervals of its update launches
- * -- the time during which k_tall_group_d is running at all (its launches on the two streams overlap each other). */
+ * -- the time during which k_tall_group_d is running at all (its launches on the two streams overlap each other).
+ * ck_predict_blocks (n up to 23): [16] K2 assembly of the point rows, summed over the chunks; [17] the fold into block rows
+ * (k_block_fold), summed; [18] the blocks' prior covariance (k_block_prior_part + _sum: diagonal, and the lower triangle with cov);
+ * [19] the forward sweep over the r + 1 block rows; [20] reductions, and with cov V^T V (k_schur_syrk_d) and its download;
+ * [21] host wall clock of the call; [22] number of chunks. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it
@@ -375,6 +397,8 @@ int ck_table_fallbacks(ck_handle* h, int reset, int64_t* count);
  * workgroups that take their 64 x 512 strips (or halves / quarters of them) from a work queue -- the 48 KB table is loaded once per
  * workgroup instead of once per strip; automatic: the right-hand-side assembly (K2) with 768 workgroups from 8 strips per workgroup
  * on (N = 40 000: 0.62 -> 0.56 ms), Sigma (K1) never (faster on one box, slower on another);
+ * "block_chunk" (default 0 = automatic: what the arena has left, or half of the free device memory, beside the point rows
+ * the handle holds): prediction sites per K2 assembly of ck_predict_blocks;
  * "local_slab_mb" = scratch budget of ck_predict_local in MiB (0, default: a quarter of the free memory, at most
  * 32 GiB; the points are processed in batches that fit; the scratch is kept until ck_destroy and reused);
  * "local_tile_min" (default 64 = the LDS kernel's limit): neighbourhoods with more sites than this are factored by

@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 #include <memory>
 #include <string>
@@ -31,6 +32,7 @@
 #include "ck_model.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+#define CK_N_TIMINGS 23
 
 static int fail(const std::string& msg) { return ck_fail(msg); }   // thread-local text: ck_host.cpp (ck_last_error)
 #define HIPCHK(expr)                                                                              \
@@ -131,6 +133,12 @@ struct ck_handle {
     char* mv_buf = nullptr;   // ck_model_variogram's device rows (i, j, lag, out), kept between the cost evaluations of a fit
     int64_t mv_cap = 0;
     int aux_state = 0;   // 0: nothing usable | 1: right-hand sides assembled | 2: solved by ck_predict (rows = V^T, row m = y)
+                         // | 3: the last call was ck_predict_blocks (its rows are block sums: the sites are gone)
+    // ck_predict_blocks: the block rows (the aux panel layout with bmpad = roundup(r + 1, CK_AUX_ALIGN) rows per panel), kept
+    // between calls like aux; option "block_chunk": prediction sites per K2 assembly (0: from the device memory the handle may use)
+    double* baux = nullptr;
+    int64_t baux_cap = 0;   // doubles
+    int64_t block_chunk = 0;
     // Schur complement of the prediction sites (ck_verify_model), kept between calls with the same padded order
     int64_t sch_M = 0;
     std::vector<double*> sch_sig;
@@ -161,7 +169,7 @@ struct ck_handle {
     int64_t vg_stats[4] = {0, 0, 0, 0};   // host-decided pairs of the extent pass | of the binning pass | pairs visited by
                                           // the binning pass | extra extent rounds
     // timings
-    double t_ms[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double t_ms[CK_N_TIMINGS] = {};   // ck_timings; [16 ..] ck_predict_blocks
     int time_gemm = 0;   // 1: bracket every trailing-update launch with events | 2: the Sigma updates only (step-wise form)
     std::vector<EvPair> gemm_ev;
     size_t gemm_ev_used = 0;
@@ -1705,6 +1713,7 @@ extern "C" int ck_aux_begin(ck_handle* h, int i, const double* pcoords, int64_t 
 extern "C" int ck_aux_finish(ck_handle* h, double* pred, double* pred_err) {
     CHKH(h);
     if (h->mpad <= 0) return fail("ck_aux_begin has not been called");
+    if (h->aux_state == 3) return fail("ck_aux_finish: the last call was ck_predict_blocks; call ck_aux_begin first");
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     const double c0 = h->blk[2 * h->i_pred].amp + h->blk[2 * h->i_pred].nugget;   // sigma_i^2 + nugget_i (model.py:194-196 at h = 0)
     ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, h->m, h->m, c0, h->d_pred, h->d_err);
@@ -1829,47 +1838,57 @@ struct SchurSwap {
     }
 };
 
+// the Schur complement's packed panels (Mp = roundup(sites, CK_NB) rows, a Sigma-like block-column layout) and the
+// assembly state that goes with them; kept between calls with the same padded order
+static int schur_ensure(ck_handle* h, int64_t Mp) {
+    if (h->sch_M == Mp) return 0;
+    const int nJ = (int)(Mp / CK_NB);
+    schur_free(h);
+    h->sch_sig.assign((size_t)nJ, nullptr);
+    std::vector<int> tile0, panel_of;
+    int acc = 0;
+    for (int J = 0; J < nJ; ++J) {
+        const int64_t rows = Mp - (int64_t)J * CK_NB;
+        HIPCHK(hipMalloc((void**)&h->sch_sig[(size_t)J], (size_t)(rows * CK_NB + CK_PANEL_TAIL) * 8));
+        tile0.push_back(acc);
+        panel_of.push_back(J);
+        acc += (int)(rows / 64);
+    }
+    tile0.push_back(acc);
+    h->sch_tiles = acc;
+    HIPCHK(hipMalloc((void**)&h->d_sch_ptr, (size_t)nJ * sizeof(double*)));
+    HIPCHK(hipMemcpy(h->d_sch_ptr, h->sch_sig.data(), (size_t)nJ * sizeof(double*), hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc((void**)&h->d_sch_tile0, tile0.size() * sizeof(int)));
+    HIPCHK(hipMalloc((void**)&h->d_sch_panel_of, (panel_of.size() + 1) * sizeof(int)));
+    HIPCHK(hipMemcpy(h->d_sch_tile0, tile0.data(), tile0.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_sch_panel_of, panel_of.data(), panel_of.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc((void**)&h->sch_pc, (size_t)(2 * Mp) * 8));
+    HIPCHK(hipMalloc((void**)&h->sch_c, (size_t)(3 * Mp) * 8));
+    HIPCHK(hipMalloc((void**)&h->sch_u, (size_t)(3 * Mp) * 8));
+    HIPCHK(hipMalloc((void**)&h->d_sch_blk, 3 * sizeof(CkMatern)));
+    HIPCHK(hipMalloc((void**)&h->d_sch_tabs, 3 * sizeof(CkTable)));
+    HIPCHK(hipMalloc((void**)&h->d_sch_coefptr, 3 * sizeof(double*)));
+    HIPCHK(hipMalloc((void**)&h->d_sch_info, sizeof(long long)));
+    h->sch_M = Mp;
+    return 0;
+}
+
 static int factor_sweep(ck_handle* h);
 
 extern "C" int ck_verify_model(ck_handle* h, int64_t* info) {
     CHKH(h);
     if (!info) return fail("null info");
     if (h->world != 1) return fail("ck_verify_model is the single-process form");
+    if (h->aux_state == 3)
+        return fail("ck_verify_model: the last call was ck_predict_blocks, whose right-hand sides are block sums; call ck_predict "
+                    "with the sites to check first");
     if (h->aux_state != 2) return fail("ck_verify_model needs the solved right-hand sides of a preceding ck_predict");
     const int64_t m = h->m, mpad = h->mpad;
     *info = 0;
     if (m <= 0) return 0;
     const int64_t Mp = roundup(m, CK_NB);
     const int nJ = (int)(Mp / CK_NB);
-    if (h->sch_M != Mp) {
-        schur_free(h);
-        h->sch_sig.assign((size_t)nJ, nullptr);
-        std::vector<int> tile0, panel_of;
-        int acc = 0;
-        for (int J = 0; J < nJ; ++J) {
-            const int64_t rows = Mp - (int64_t)J * CK_NB;
-            HIPCHK(hipMalloc((void**)&h->sch_sig[(size_t)J], (size_t)(rows * CK_NB + CK_PANEL_TAIL) * 8));
-            tile0.push_back(acc);
-            panel_of.push_back(J);
-            acc += (int)(rows / 64);
-        }
-        tile0.push_back(acc);
-        h->sch_tiles = acc;
-        HIPCHK(hipMalloc((void**)&h->d_sch_ptr, (size_t)nJ * sizeof(double*)));
-        HIPCHK(hipMemcpy(h->d_sch_ptr, h->sch_sig.data(), (size_t)nJ * sizeof(double*), hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc((void**)&h->d_sch_tile0, tile0.size() * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&h->d_sch_panel_of, (panel_of.size() + 1) * sizeof(int)));
-        HIPCHK(hipMemcpy(h->d_sch_tile0, tile0.data(), tile0.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_sch_panel_of, panel_of.data(), panel_of.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMalloc((void**)&h->sch_pc, (size_t)(2 * Mp) * 8));
-        HIPCHK(hipMalloc((void**)&h->sch_c, (size_t)(3 * Mp) * 8));
-        HIPCHK(hipMalloc((void**)&h->sch_u, (size_t)(3 * Mp) * 8));
-        HIPCHK(hipMalloc((void**)&h->d_sch_blk, 3 * sizeof(CkMatern)));
-        HIPCHK(hipMalloc((void**)&h->d_sch_tabs, 3 * sizeof(CkTable)));
-        HIPCHK(hipMalloc((void**)&h->d_sch_coefptr, 3 * sizeof(double*)));
-        HIPCHK(hipMalloc((void**)&h->d_sch_info, sizeof(long long)));
-        h->sch_M = Mp;
-    }
+    if (schur_ensure(h, Mp)) return -1;
     const auto t_begin = std::chrono::steady_clock::now();
     // the prediction sites as a one-process site set: every tile uses the auto-block (i, i), replicated into all
     // three slots of the block / table arrays
@@ -1922,6 +1941,267 @@ extern "C" int ck_verify_model(ck_handle* h, int64_t* info) {
     }
     *info = (int64_t)v;   // 1-based index among the prediction sites in the library's internal order, 0 = positive definite
     h->t_ms[11] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// block (areal) cokriging: weighted sums of the joint point predictor (ck_blocks.hip)
+// ---------------------------------------------------------------------------------------
+// Block b is the weighted sum of its sites, A[b, a] = w_a.  Its right-hand side is c0_b = sum_a w_a c0(s_a): the point
+// rows of K2 are folded into r block rows (k_block_fold), so that the O(N^2) forward sweep runs over r + 1 rows instead of
+// m + 1.  pred_b = V_b . y, cov = Cbar - V^T V with Cbar = A C_pp A^T (k_block_prior_part + _sum) -- A S A^T, S the posterior
+// covariance of the point predictions.  The sites go through K2 in chunks of option "block_chunk" sites (caller's order),
+// each folded into the same block rows: the device memory of the call is bounded by r, not m.
+
+// point the right-hand-side state at the block rows for the sweep (the point rows' buffer stays the handle's)
+struct AuxSwap {
+    ck_handle* h;
+    double* aux;
+    int64_t m, mpad;
+    bool p_sorted;
+    AuxSwap(ck_handle* hh, double* baux, int64_t r, int64_t bmpad) : h(hh), aux(hh->aux), m(hh->m), mpad(hh->mpad), p_sorted(hh->p_sorted) {
+        h->aux = baux;
+        h->m = r;
+        h->mpad = bmpad;
+        h->p_sorted = false;
+    }
+    ~AuxSwap() {
+        h->aux = aux;
+        h->m = m;
+        h->mpad = mpad;
+        h->p_sorted = p_sorted;
+    }
+};
+
+// every return of ck_predict_blocks once it has started: slots 0 .. 15 of ck_timings describe the last point-path calls and
+// are left as they were; the right-hand sides are block rows (or a chunk's unsolved point rows after a failure) -- state 3,
+// which ck_verify_model and ck_aux_finish refuse
+struct BlockCallGuard {
+    ck_handle* h;
+    double kept[16];
+    explicit BlockCallGuard(ck_handle* hh) : h(hh) {
+        memcpy(kept, h->t_ms, sizeof(kept));
+        h->aux_state = 3;
+    }
+    ~BlockCallGuard() {
+        memcpy(h->t_ms, kept, sizeof(kept));
+        h->aux_state = 3;
+    }
+};
+
+// piece offsets of the prior's elements (ck_blocks.hip): poff[e] .. poff[e + 1] = the pieces of CK_PRIOR_PIECE pairs of
+// element e (full == 0: e = b, n_b^2 pairs; full != 0: e = R (R + 1) / 2 + C, n_R n_C pairs); returns the number of pieces
+static int64_t prior_pieces(const std::vector<int>& off, int32_t r, int full, std::vector<long long>& poff) {
+    auto n = [&](int64_t b) { return (int64_t)(off[(size_t)b + 1] - off[(size_t)b]); };
+    auto pieces = [](int64_t pairs) { return (pairs + CK_PRIOR_PIECE - 1) / CK_PRIOR_PIECE; };
+    poff.assign(1, 0);
+    poff.reserve((size_t)(full ? (int64_t)r * (r + 1) / 2 : r) + 1);
+    for (int64_t R = 0; R < r; ++R) {
+        if (!full) {
+            poff.push_back(poff.back() + pieces(n(R) * n(R)));
+            continue;
+        }
+        for (int64_t C = 0; C <= R; ++C) poff.push_back(poff.back() + pieces(n(R) * n(C)));
+    }
+    return poff.back();
+}
+
+extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int64_t m, const int32_t* block,
+                                 const double* weight, int32_t r, double* pred, double* pred_err, double* cov) {
+    CHKH(h);
+    if (h->world != 1) return fail("ck_predict_blocks is the single-process form");
+    if (!h->factored) return fail("ck_factor has not been called");
+    if (i < 0 || i >= h->n_procs) return fail("process index out of range");
+    if (r < 1) return fail("ck_predict_blocks: r must be >= 1");
+    if (m < 1 || m > INT32_MAX) return fail("ck_predict_blocks: m must be in [1, 2^31)");
+    if (!pcoords || !block || !weight || !pred || !pred_err) return fail("ck_predict_blocks: null argument");
+    if (cov && r > 65536) return fail("ck_predict_blocks: the covariance is limited to 65 536 blocks");
+    // member lists: off[b] .. off[b + 1], the caller's order inside each block
+    std::vector<int> off((size_t)r + 1, 0);
+    for (int64_t a = 0; a < m; ++a) {
+        if (block[a] < 0 || block[a] >= r)
+            return fail("ck_predict_blocks: block label " + std::to_string(block[a]) + " of site " + std::to_string(a) +
+                        " is outside [0, r)");
+        if (!std::isfinite(weight[a])) return fail("ck_predict_blocks: weight of site " + std::to_string(a) + " is not finite");
+        ++off[(size_t)block[a] + 1];
+    }
+    for (int32_t b = 0; b < r; ++b) {
+        if (off[(size_t)b + 1] == 0) return fail("ck_predict_blocks: block " + std::to_string(b) + " has no site");
+        off[(size_t)b + 1] += off[(size_t)b];
+    }
+    const auto t_begin = std::chrono::steady_clock::now();
+    BlockCallGuard guard(h);
+    for (int k = 16; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    auto elapsed = [&](hipEvent_t a, hipEvent_t b) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, a, b);
+        return (double)ms;
+    };
+    DevTemps tmp;
+    // ---- prior of the blocks (diagonal): members in block order, exact-formula coordinates
+    std::vector<double> mc((size_t)(2 * m)), mw((size_t)m);
+    {
+        std::vector<int> pos(off.begin(), off.end() - 1);
+        for (int64_t a = 0; a < m; ++a) {
+            const int k = pos[(size_t)block[a]]++;
+            mc[2 * (size_t)k] = pcoords[2 * a];
+            mc[2 * (size_t)k + 1] = pcoords[2 * a + 1];
+            mw[(size_t)k] = weight[a];
+        }
+    }
+    double *d_mc = nullptr, *d_mx = nullptr, *d_mw = nullptr, *d_diag = nullptr, *d_red = nullptr;
+    int* d_off = nullptr;
+    HIPCHK(tmp.get(&d_mc, (size_t)(2 * m) * 8));
+    HIPCHK(tmp.get(&d_mx, (size_t)(3 * m) * 8));
+    HIPCHK(tmp.get(&d_mw, (size_t)m * 8));
+    HIPCHK(tmp.get(&d_off, ((size_t)r + 1) * sizeof(int)));
+    HIPCHK(tmp.get(&d_diag, (size_t)r * 8));
+    HIPCHK(tmp.get(&d_red, (size_t)(2 * r) * 8));
+    HIPCHK(hipMemcpyAsync(d_mc, mc.data(), (size_t)(2 * m) * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_mw, mw.data(), (size_t)m * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_off, off.data(), ((size_t)r + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    std::vector<long long> poff;
+    const int64_t n_pieces = prior_pieces(off, r, 0, poff);
+    long long* d_poff = nullptr;
+    double* d_part = nullptr;
+    HIPCHK(tmp.get(&d_poff, poff.size() * sizeof(long long)));
+    HIPCHK(tmp.get(&d_part, (size_t)n_pieces * 8));
+    HIPCHK(hipMemcpyAsync(d_poff, poff.data(), poff.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    ck_launch_prep_sites(h->stream, d_mc, m, h->metric, d_mx, d_mx + m, d_mx + 2 * m, nullptr);
+    ck_launch_block_prior(h->stream, h->d_blk + 2 * i, h->metric, d_mx, d_mx + m, d_mx + 2 * m, d_mw, d_off, r, 0, d_poff,
+                          n_pieces, d_part, d_diag, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipEventSynchronize(h->ev1));   // mc / mw / off are host memory
+    h->t_ms[18] = elapsed(h->ev0, h->ev1);
+    // ---- block rows
+    const int64_t bmpad = roundup((int64_t)r + 1, CK_AUX_ALIGN);
+    if (bmpad * h->Npad > h->baux_cap) {
+        dev_free_one(h, h->baux);
+        h->baux = nullptr;
+        h->baux_cap = 0;
+        if (dev_alloc(h, (void**)&h->baux, bmpad * h->Npad * 8)) return -1;
+        h->baux_cap = bmpad * h->Npad;
+    }
+    int64_t chunk = h->block_chunk;
+    if (chunk <= 0) {   // what the handle may still take (the arena's rest or half of the free memory) beside the point rows it holds
+        int64_t avail = 0;
+        if (h->arena) {
+            avail = h->arena_size - h->arena_used;
+        } else {
+            size_t fr = 0, tot = 0;
+            HIPCHK(hipMemGetInfo(&fr, &tot));
+            avail = (int64_t)(fr / 2);
+        }
+        // hipMalloc: aux_begin_impl frees the point rows' buffer before it allocates a larger one; an arena never takes
+        // memory back, so there the chunk fits either the buffer the handle holds or the arena's rest
+        avail = h->arena ? std::max<int64_t>(avail, h->aux_cap * 8) : avail + h->aux_cap * 8;
+        chunk = std::max<int64_t>(avail / (8 * h->Npad) - CK_AUX_ALIGN, CK_AUX_ALIGN);
+    }
+    chunk = std::min<int64_t>(chunk, m);
+    int *d_coff = nullptr, *d_crows = nullptr;
+    double* d_cw = nullptr;
+    HIPCHK(tmp.get(&d_coff, ((size_t)r + 1) * sizeof(int)));
+    HIPCHK(tmp.get(&d_crows, (size_t)chunk * sizeof(int)));
+    HIPCHK(tmp.get(&d_cw, (size_t)chunk * 8));
+    std::vector<int> coff((size_t)r + 1), crows((size_t)chunk), inv((size_t)chunk);
+    std::vector<double> cw((size_t)chunk);
+    int n_chunks = 0;
+    for (int64_t a0 = 0; a0 < m; a0 += chunk, ++n_chunks) {
+        const int64_t mc_ = std::min<int64_t>(chunk, m - a0);
+        if (aux_begin_impl(h, i, pcoords + 2 * a0, mc_, true)) return -1;   // K2 on this chunk's sites (synchronised)
+        h->aux_state = 3;
+        h->t_ms[16] += h->t_ms[2];
+        // this chunk's member lists, rows in the library's internal order (Hilbert order when p_sorted)
+        for (int64_t j = 0; j < mc_; ++j) inv[(size_t)(h->p_sorted ? h->pperm[(size_t)j] : j)] = (int)j;
+        std::fill(coff.begin(), coff.end(), 0);
+        for (int64_t q = 0; q < mc_; ++q) ++coff[(size_t)block[a0 + q] + 1];
+        for (int32_t b = 0; b < r; ++b) coff[(size_t)b + 1] += coff[(size_t)b];
+        {
+            std::vector<int> pos(coff.begin(), coff.end() - 1);
+            for (int64_t q = 0; q < mc_; ++q) {
+                const int k = pos[(size_t)block[a0 + q]]++;
+                crows[(size_t)k] = inv[(size_t)q];
+                cw[(size_t)k] = weight[a0 + q];
+            }
+        }
+        HIPCHK(hipMemcpyAsync(d_coff, coff.data(), ((size_t)r + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_crows, crows.data(), (size_t)mc_ * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_cw, cw.data(), (size_t)mc_ * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        ck_launch_block_fold(h->stream, h->aux, h->mpad, h->nK, h->baux, bmpad, d_coff, d_crows, d_cw, r, mc_, a0 == 0);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        HIPCHK(hipEventSynchronize(h->ev1));   // the lists are rewritten for the next chunk
+        h->t_ms[17] += elapsed(h->ev0, h->ev1);
+    }
+    h->t_ms[22] = n_chunks;
+    // ---- the forward sweep over the r + 1 block rows on the resident factor, raw reductions V_b . y and |V_b|^2
+    {
+        AuxSwap swap(h, h->baux, r, bmpad);
+        h->gemm_ev_used = 0;
+        HIPCHK(hipEventRecord(h->ev2, h->stream));
+        if (solve_sweep(h)) return -1;
+        HIPCHK(hipEventRecord(h->ev3, h->stream));
+        h->gemm_ev_used = 0;
+    }
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    ck_launch_reduce_pred(h->stream, h->baux, bmpad, h->nK, r, r, -1.0, d_red, d_red + r);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    std::vector<double> s1((size_t)r), s2((size_t)r), cbar((size_t)r);
+    HIPCHK(hipMemcpyAsync(s1.data(), d_red, (size_t)r * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(s2.data(), d_red + r, (size_t)r * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(cbar.data(), d_diag, (size_t)r * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->t_ms[19] = elapsed(h->ev2, h->ev3);
+    h->t_ms[20] = elapsed(h->ev0, h->ev1);
+    for (int32_t b = 0; b < r; ++b) {
+        pred[b] = s1[(size_t)b];
+        const double e = sqrt(cbar[(size_t)b] - s2[(size_t)b]);   // negative variance -> NaN -> 0.0 (np.nan_to_num)
+        pred_err[b] = (e == e) ? e : 0.0;
+    }
+    // ---- the full A S A^T: Cbar's lower triangle in the Schur buffers' packed panels, minus V^T V (k_schur_syrk_d)
+    if (cov) {
+        const int64_t Mp = roundup(r, CK_NB);
+        const int nJ = (int)(Mp / CK_NB);
+        if (schur_ensure(h, Mp)) return -1;
+        const int64_t n_pieces_full = prior_pieces(off, r, 1, poff);
+        long long* d_poff_full = nullptr;
+        double* d_part_full = nullptr;
+        HIPCHK(tmp.get(&d_poff_full, poff.size() * sizeof(long long)));
+        HIPCHK(tmp.get(&d_part_full, (size_t)n_pieces_full * 8));
+        HIPCHK(hipMemcpyAsync(d_poff_full, poff.data(), poff.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        for (int J = 0; J < nJ; ++J)
+            HIPCHK(hipMemsetAsync(h->sch_sig[(size_t)J], 0, (size_t)((Mp - (int64_t)J * CK_NB) * CK_NB) * 8, h->stream));
+        ck_launch_block_prior(h->stream, h->d_blk + 2 * i, h->metric, d_mx, d_mx + m, d_mx + 2 * m, d_mw, d_off, r, 1,
+                              d_poff_full, n_pieces_full, d_part_full, nullptr, h->d_sch_ptr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        ck_launch_schur_syrk(h->stream, h->d_sch_ptr, h->baux, bmpad, h->nK, nJ, Mp);
+        HIPCHK(hipGetLastError());
+        std::vector<double> panel;
+        for (int J = 0; J < nJ; ++J) {   // rows J NB .. r - 1 of block column J; only R >= C is meaningful
+            const int64_t R0 = (int64_t)J * CK_NB, rows = r - R0;
+            panel.resize((size_t)(rows * CK_NB));
+            HIPCHK(hipMemcpyAsync(panel.data(), h->sch_sig[(size_t)J], (size_t)(rows * CK_NB) * 8, hipMemcpyDeviceToHost,
+                                  h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            for (int64_t R = R0; R < r; ++R)
+                for (int64_t C = R0; C < std::min<int64_t>(R0 + CK_NB, R + 1); ++C) {
+                    const double v = panel[(size_t)((R - R0) * CK_NB + (C - R0))];
+                    cov[R * r + C] = v;
+                    cov[C * r + R] = v;
+                }
+        }
+        HIPCHK(hipEventRecord(h->ev2, h->stream));
+        HIPCHK(hipEventSynchronize(h->ev2));
+        h->t_ms[18] += elapsed(h->ev0, h->ev1);
+        h->t_ms[20] += elapsed(h->ev1, h->ev2);
+    }
+    h->t_ms[21] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return 0;
 }
 
@@ -3044,6 +3324,11 @@ extern "C" int ck_set_option(ck_handle* h, const char* name, int64_t value) {
         h->recv_slots = (int)value;
         return 0;
     }
+    if (!strcmp(name, "block_chunk")) {   // ck_predict_blocks: prediction sites per K2 assembly (0 = automatic)
+        if (value < 0) return fail("block_chunk must be >= 0 (0 = automatic)");
+        h->block_chunk = value;
+        return 0;
+    }
     if (!strcmp(name, "exact_cov")) {   // 1: per-entry Bessel evaluation instead of the tables
         h->exact_cov = value != 0;
         return 0;
@@ -3074,7 +3359,7 @@ extern "C" int ck_table_fallbacks(ck_handle* h, int reset, int64_t* count) {
 
 extern "C" int ck_timings(ck_handle* h, double* out, int n) {
     CHKH(h);
-    for (int k = 0; k < n && k < 16; ++k) out[k] = h->t_ms[k];
+    for (int k = 0; k < n && k < CK_N_TIMINGS; ++k) out[k] = h->t_ms[k];
     return 0;
 }
 

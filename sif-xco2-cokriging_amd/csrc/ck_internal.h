@@ -77,6 +77,21 @@ void ck_launch_model_variogram(hipStream_t s, const CkMatern* blk, double sill, 
 void ck_launch_cov_lags(hipStream_t s, const CkMatern* blk_ij, int add_nugget, const double* lags, int64_t n,
                         double* out);
 
+// ---- block cokriging (ck_blocks.hip) ------------------------------------------------------
+// block rows out[b] (+)= sum_k w_k aux[rows_k] over the member list off[b] .. off[b + 1] of every panel, in list order;
+// row r = the data row zrow of aux; first != 0: start from zero and zero the padding rows (r, mpad_r)
+void ck_launch_block_fold(hipStream_t s, const double* aux, int64_t mpad, int n_panels, double* out, int64_t mpad_r,
+                          const int* off, const int* rows, const double* w, int64_t r, int64_t zrow, int first);
+// Cbar[R][C] = sum_{a in R, c in C} w_a w_c C(h(a, c)) (nugget where h == 0) over members stored block by block
+// (c0 / c1 / c2: exact-formula coordinates, off: r + 1 offsets).  full == 0: diag[b] = Cbar[b][b];
+// full != 0: the lower triangle into packed panels (panel J = C / NB: rows J NB .., ld = NB).
+// The pairs of element e (e = b | R (R + 1) / 2 + C) are cut into pieces of CK_PRIOR_PIECE pairs: poff[e] .. poff[e + 1]
+// (n_elem + 1 words, host-built: ck_block_prior_pieces), part: n_pieces doubles of scratch
+#define CK_PRIOR_PIECE 512
+void ck_launch_block_prior(hipStream_t s, const CkMatern* blk, int metric, const double* c0, const double* c1,
+                           const double* c2, const double* w, const int* off, int64_t r, int full, const long long* poff,
+                           int64_t n_pieces, double* part, double* diag, double* const* panels);
+
 // ---- dense linear algebra (ck_la.hip) ----------------------------------------
 // C (M x N, ldc) -= A (M x K, lda) * B (N x K, ldb)^T on FP64 MFMA.
 // M % 256 == 0, N % 64 == 0, K % 16 == 0.  lower: skip tiles whose rows are all above the

@@ -284,6 +284,17 @@ class Predictor:
         out = df[["lon", "lat"]].copy()
         out["pred"] = df["pred"].values * at["scale_fact"] + at["spatial_mean"]
         out["pred_err"] = df["pred_err"].values * at["scale_fact"]
+        out["pred"] = out["pred"] + self._spatial_trend(df) + at["temporal_trend"]
+        out = out.set_index(["lon", "lat"])
+        if xr is None:
+            return out
+        ds = out.to_xarray()
+        return ds.assign_coords(coords={"time": np.datetime64(self.mf.fields[self.i].timestamp)})
+
+    def _spatial_trend(self, df: pd.DataFrame) -> np.ndarray:
+        """The OLS spatial trend of process ``self.i`` at the sites of ``df`` (columns lon, lat); NaN where a covariate is
+        missing (src/joint_prediction.py:170-200)."""
+        at = self.mf.fields[self.i].ds.attrs
         if self.covariates is None:
             cov = df[["lon", "lat"]].copy()
             keep = np.ones(len(df), dtype=bool)
@@ -299,12 +310,88 @@ class Predictor:
             cov[name] = (cov[name] - at["covariate_means"][k]) / at["covariate_scales"][k]
         trend = np.full(len(df), np.nan)
         trend[keep] = at["spatial_model"].predict(cov)
-        out["pred"] = out["pred"] + trend + at["temporal_trend"]
-        out = out.set_index(["lon", "lat"])
-        if xr is None:
-            return out
-        ds = out.to_xarray()
-        return ds.assign_coords(coords={"time": np.datetime64(self.mf.fields[self.i].timestamp)})
+        return trend
+
+    # -- regional means ---------------------------------------------------------------------------
+    @staticmethod
+    def _block_layout(pcoords, blocks, weights=None):
+        """Host side of ``predict_blocks``: validated coordinates of the sites that belong to a block, their compact
+        block codes (0 .. r - 1, in the order of the sorted labels), their weights (default 1 / n_b) and the labels.
+        Raises ValueError before any device work."""
+        pc = np.atleast_2d(np.asarray(pcoords.values if isinstance(pcoords, pd.DataFrame) else pcoords, dtype=np.float64))
+        if pc.ndim != 2 or pc.shape[1] < 2:
+            raise ValueError("pcoords must be [[lat, lon], ...]")
+        pc = np.ascontiguousarray(pc[:, :2])
+        m = len(pc)
+        if isinstance(blocks, (np.ndarray, pd.Series, pd.Index)):
+            lab = pd.Series(np.asarray(blocks))
+        else:
+            lab = pd.Series(list(blocks), dtype=object)
+        if len(lab) != m:
+            raise ValueError(f"blocks has {len(lab)} entries for {m} prediction sites")
+        codes, labels = pd.factorize(lab, sort=True)   # NaN / None -> -1: the site is in no block
+        labels = pd.Index(list(labels))
+        inside = codes >= 0
+        if not inside.any():
+            raise ValueError("no prediction site belongs to a block")
+        codes = codes[inside].astype(np.int32)
+        r = len(labels)
+        if weights is None:
+            n_b = np.bincount(codes, minlength=r)
+            w = 1.0 / n_b[codes]
+        else:
+            w = np.asarray(weights, dtype=np.float64).ravel()
+            if len(w) != m:
+                raise ValueError(f"weights has {len(w)} entries for {m} prediction sites")
+            w = w[inside]
+            if not np.all(np.isfinite(w)):
+                raise ValueError("weights must be finite for every site in a block")
+        return pc[inside], codes, np.ascontiguousarray(w, dtype=np.float64), labels, inside
+
+    def predict_blocks(self, i: int, pcoords, blocks, weights=None, postprocess: bool = True, return_cov: bool = False):
+        """Weighted regional means of process ``i`` and their joint uncertainty (block cokriging).
+
+        ``blocks[a]`` names the block of site ``pcoords[a]`` (any hashable; NaN / None leaves the site out), ``weights[a]``
+        its weight (default: 1 / n_b, the plain mean of the block).  A block's prediction is the weighted sum of the joint
+        point predictions of its sites, pred_b = sum_a w_a pred_a, and its standard error is sqrt(w^T S w) with S the
+        posterior covariance of the point predictions -- not a combination of the sites' ``pred_err``, which are strongly
+        correlated.  ``return_cov=True`` also returns the r x r covariance A S A^T of the blocks (``(df, cov)``, rows in
+        the frame's order).  Runs on the resident factor of ``__call__`` (include/cokrige.h: ck_predict_blocks); with
+        ``devices=[...]`` on ``devices[0]``, as ``cross_validation``.
+
+        Returns a DataFrame indexed by the sorted block labels with ``pred``, ``pred_err``, ``n_sites`` and the weighted
+        centroid ``lat`` / ``lon``.  ``postprocess=True`` is ``_postprocess_predictions`` applied to the weighted sum:
+        pred = scale_fact pred_b + sum_a w_a (spatial_mean + trend_a + temporal_trend), pred_err and cov scaled by
+        scale_fact (cov by its square); a block with a site whose trend is missing (covariate NaN) has pred NaN."""
+        pc, codes, w, labels, _ = self._block_layout(pcoords, blocks, weights)
+        r = len(labels)
+        h = self._factored_handle()
+        pred, err, cov = h.predict_blocks(i, pc, codes, w, r, want_cov=return_cov)
+        n_sites = np.bincount(codes, minlength=r)
+        sw = np.bincount(codes, weights=w, minlength=r)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            lat = np.bincount(codes, weights=w * pc[:, 0], minlength=r) / sw
+            lon = np.bincount(codes, weights=w * pc[:, 1], minlength=r) / sw
+        if postprocess:
+            self.i = i
+            pred, err, cov = self._postprocess_blocks(pc, codes, w, r, pred, err, cov)
+        index = labels.copy()
+        if index.nlevels == 1:
+            index.name = "block"
+        df = pd.DataFrame({"pred": pred, "pred_err": err, "n_sites": n_sites, "lat": lat, "lon": lon}, index=index)
+        return (df, cov) if return_cov else df
+
+    def _postprocess_blocks(self, pc, codes, w, r, pred, err, cov):
+        """``_postprocess_predictions`` of a weighted sum (process ``self.i``)."""
+        at = self.mf.fields[self.i].ds.attrs
+        sf = at["scale_fact"]
+        trend = self._spatial_trend(pd.DataFrame({"lon": pc[:, 1], "lat": pc[:, 0]}))
+        offset = at["spatial_mean"] + trend + at["temporal_trend"]
+        missing = np.bincount(codes, weights=np.isnan(offset).astype(np.float64), minlength=r) > 0
+        add = np.bincount(codes, weights=w * np.where(np.isnan(offset), 0.0, offset), minlength=r)
+        pred = pred * sf + add
+        pred[missing] = np.nan
+        return pred, err * sf, (cov * (sf * sf) if cov is not None else None)
 
     def cross_validation(self, i: int, postprocess: bool = True, refactor_each: bool = False) -> pd.DataFrame:
         """Leave-one-out cross-validation at each data location of process ``i``

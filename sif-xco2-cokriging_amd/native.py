@@ -48,6 +48,7 @@ _PROTOS = {
     "ck_predict": [c_void_p, c_int, _dp, c_int64, _dp, _dp],
     "ck_factor_predict": [c_void_p, c_int, _dp, c_int64, _dp, _dp, POINTER(c_int64)],
     "ck_verify_model": [c_void_p, POINTER(c_int64)],
+    "ck_predict_blocks": [c_void_p, c_int, _dp, c_int64, POINTER(c_int32), _dp, c_int32, _dp, _dp, _dp],
     "ck_loocv": [c_void_p, c_int, _dp, _dp],
     "ck_sample": [c_void_p, _dp, _dp, c_int64],
     "ck_num_panels": [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int64)],
@@ -355,6 +356,23 @@ class Handle:
         _chk(lib().ck_verify_model(self._h, byref(info)))
         return info.value
 
+    def predict_blocks(self, i, pcoords, block, weight, r, want_cov=False):
+        """Weighted regional means of process i on the resident factor (include/cokrige.h: ck_predict_blocks):
+        block[a] in [0, r) names the block of site a, weight[a] its weight.  Returns (pred, err, cov | None), r values
+        each and with ``want_cov`` the r x r covariance A S A^T of the block predictions."""
+        pc = _f64(pcoords, 2)
+        m = pc.shape[0]
+        b = np.ascontiguousarray(block, dtype=np.int32).ravel()
+        w = _f64(weight).ravel()
+        if b.size != m or w.size != m:
+            raise ValueError("pcoords, block and weight disagree in length")
+        r = int(r)
+        pred, err = np.empty(max(r, 0)), np.empty(max(r, 0))
+        cov = np.empty((r, r)) if want_cov and r > 0 else None
+        _chk(lib().ck_predict_blocks(self._h, int(i), _p(pc), m, b.ctypes.data_as(POINTER(c_int32)), _p(w), r, _p(pred),
+                                     _p(err), _p(cov) if cov is not None else None))
+        return pred, err, cov
+
     def loocv(self, i, n_i):
         pred, err = np.empty(n_i), np.empty(n_i)
         _chk(lib().ck_loocv(self._h, int(i), _p(pred), _p(err)))
@@ -546,11 +564,14 @@ class Handle:
         return out, grid
 
     def timings(self):
-        out = np.zeros(16)
-        _chk(lib().ck_timings(self._h, _p(out), 16))
+        out = np.zeros(23)
+        _chk(lib().ck_timings(self._h, _p(out), 23))
         keys = ["assemble_sigma_ms", "factor_ms", "assemble_aux_ms", "solve_ms", "reduce_ms", "syrk_ms",
                 "syrk_launches", "aux_gemm_ms", "aux_gemm_launches", "vario_bin_ms", "local_ms", "verify_ms",
-                "panel_coop_redone", "fused_sweeps_ms", "local_alloc_ms", "tall_union_ms"]
+                "panel_coop_redone", "fused_sweeps_ms", "local_alloc_ms", "tall_union_ms",
+                # ck_predict_blocks
+                "blocks_assemble_ms", "blocks_fold_ms", "blocks_prior_ms", "blocks_solve_ms", "blocks_reduce_ms",
+                "blocks_total_ms", "blocks_chunks"]
         return dict(zip(keys, out.tolist()))
 
     def dev_gemm_nt(self, C_ptr, ldc, A_ptr, lda, B_ptr, ldb, M, N, K, lower=False):
