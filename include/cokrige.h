@@ -166,6 +166,24 @@ int ck_predict_blocks(ck_handle* h, int i, const double* pcoords_host, int64_t m
  * each.  Needs ck_factor. */
 int ck_loocv(ck_handle* h, int i, double* pred_host, double* pred_err_host);
 
+/* Gaussian log-likelihood of the data of every process under the model (zero mean, as simple cokriging), with Sigma assembled
+ * exactly as ck_assemble_joint builds it (same metric, table path, nugget rule at h == 0):
+ *     l = -1/2 (N log 2 pi + log|Sigma| + z^T Sigma^-1 z),   out3 = (l, log|Sigma|, z^T Sigma^-1 z).
+ * want_grad != 0: grad[k] = dl/dtheta_k = 1/2 sum_pq G_pq (dSigma/dtheta_k)_pq, G = alpha alpha^T - Sigma^-1, alpha = Sigma^-1 z,
+ * in the flat parameter order sigma_11 sigma_22 nu_11 nu_12 nu_22 len_11 len_12 len_22 nugget_11 nugget_22 rho_12 (11 values;
+ * one process: sigma nu len nugget, 4 values).  dSigma comes from the exact Matern evaluator (derivative in len scale closed
+ * form, in nu a fourth-order difference of the evaluator at a fixed scaled lag); it is 0 where the correlation is 1, clamped
+ * or set to 0.  Reductions in a fixed order, no atomics: repeated calls give the same bits.
+ * Input: a handle after ck_assemble_joint; the call factors Sigma itself (or uses the factor of a preceding ck_factor).
+ * info = 0, or -- Sigma not positive definite -- the 1-based leading minor as ck_factor reports it; out3 / grad are then NaN
+ * and the handle needs ck_assemble_joint again.  Single-process form (a partitioned handle is refused).  The gradient needs
+ * (N + 1) rows of Npad doubles (roundup(Npad + 1, 256) x Npad for the unit right-hand sides of all data sites) and the lower
+ * triangle of G (the packed panels of ck_verify_model's Schur buffers) on the device; the call refuses, stating the amount,
+ * when they do not fit.  Costs N^3 / 3 flop for the unit-row sweep and N^3 / 3 for G on top of the factorisation.
+ * Afterwards the factor stays resident (ck_predict gives the same bits as without the call); ck_verify_model and ck_aux_finish
+ * fail until the next ck_predict / ck_aux_begin.  ck_timings [24 ..] describe the call. */
+int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad, int64_t* info);
+
 /* Simulation draw z = L eps in the caller's stacked order (process 0 sites, then process 1):
  * sim.BivariateRandomField._simulate (src/sim.py:52-54: cholesky(cmat, lower=True) @ noise).
  * n = number of observations; needs ck_factor. */
@@ -342,7 +360,11 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * ck_predict_blocks (n up to 23): [16] K2 assembly of the point rows, summed over the chunks; [17] the fold into block rows
  * (k_block_fold), summed; [18] the blocks' prior covariance (k_block_prior_part + _sum: diagonal, and the lower triangle with cov);
  * [19] the forward sweep over the r + 1 block rows; [20] reductions, and with cov V^T V (k_schur_syrk_d) and its download;
- * [21] host wall clock of the call; [22] number of chunks. */
+ * [21] host wall clock of the call; [22] number of chunks.
+ * ck_loglik (n up to 30): [24] the assembly of its Sigma (= [0] of that ck_assemble_joint); [25] its factorisation (0 when it
+ * used a resident factor); [26] the sweep of the right-hand sides (the data row, with the gradient also the unit rows of all
+ * data sites) with the reductions alpha, |y|^2 and log|Sigma|; [27] G = alpha alpha^T - Sigma^-1 (k_ginv_syrk_d);
+ * [28] the contraction (k_loglik_grad); [29] host wall clock of the call. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it

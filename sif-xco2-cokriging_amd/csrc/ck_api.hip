@@ -32,7 +32,7 @@
 #include "ck_model.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 23
+#define CK_N_TIMINGS 30
 
 static int fail(const std::string& msg) { return ck_fail(msg); }   // thread-local text: ck_host.cpp (ck_last_error)
 #define HIPCHK(expr)                                                                              \
@@ -106,6 +106,8 @@ struct ck_handle {
     CkTable* d_tabs = nullptr;
     double** d_coefptr = nullptr;
     bool tables_built = false;
+    bool tables_stale = false;   // ck_set_model changed the model after the tables were built: rebuild before the next use
+    double qbox = 0.0;           // squared bounding-box diagonal of the data sites (Euclidean table range)
     bool exact_cov = false;             // option "exact_cov": bypass the tables
     CkWorklist wl = {nullptr, nullptr, 0, nullptr};   // entries deferred by the table kernels
     unsigned* wl_counts = nullptr;           // its two counters (used alternately: next_worklist)
@@ -134,6 +136,9 @@ struct ck_handle {
     int64_t mv_cap = 0;
     int aux_state = 0;   // 0: nothing usable | 1: right-hand sides assembled | 2: solved by ck_predict (rows = V^T, row m = y)
                          // | 3: the last call was ck_predict_blocks (its rows are block sums: the sites are gone)
+                         // | 4: the last call was ck_loglik (its rows are y and the unit rows of the data sites)
+    double par_sigma[2] = {0.0, 0.0}, par_rho = 0.0;   // ck_set_model's sigma and rho12 (ck_loglik's derivatives in them)
+    CkMatern* d_lik_blk = nullptr;                      // ck_loglik: 3 blocks x (the block, nu - 2 d, nu - d, nu + d, nu + 2 d)
     // ck_predict_blocks: the block rows (the aux panel layout with bmpad = roundup(r + 1, CK_AUX_ALIGN) rows per panel), kept
     // between calls like aux; option "block_chunk": prediction sites per K2 assembly (0: from the device memory the handle may use)
     double* baux = nullptr;
@@ -313,6 +318,7 @@ extern "C" int ck_destroy(ck_handle* h) {
     schur_free(h);
     for (void* p : h->owned) (void)hipFree(p);
     (void)hipFree(h->d_blk);
+    if (h->d_lik_blk) (void)hipFree(h->d_lik_blk);
     if (h->d_tile0) (void)hipFree(h->d_tile0);
     if (h->local_slab) (void)hipFree(h->local_slab);
     if (h->d_panel_of) (void)hipFree(h->d_panel_of);
@@ -376,8 +382,15 @@ extern "C" int ck_set_model(ck_handle* h, int n_procs, const double* sigma, cons
     const int nb = n_procs == 1 ? 1 : 3;
     for (int k = 0; k < nb; ++k)
         if (!(nu[k] > 0.0) || !(len_scale[k] > 0.0)) return fail("nu and len_scale must be positive");
+    CkMatern prev[3];
+    memcpy(prev, h->blk, sizeof(prev));
+    const int prev_procs = h->n_procs;
     ck_model_prepare(n_procs, sigma, nu, len_scale, nugget, rho12, h->blk);
+    if (h->tables_built && (prev_procs != n_procs || memcmp(prev, h->blk, sizeof(prev)) != 0)) h->tables_stale = true;
     h->n_procs = n_procs;
+    h->par_sigma[0] = sigma[0];
+    h->par_sigma[1] = n_procs == 2 ? sigma[1] : 0.0;
+    h->par_rho = n_procs == 2 ? rho12 : 0.0;
     HIPCHK(hipMemcpyAsync(h->d_blk, h->blk, 3 * sizeof(CkMatern), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->model_set = true;
@@ -500,7 +513,12 @@ static int build_tables(ck_handle* h, double qbox_euclid) {
 // joint runner's arena); they are allocated by the first entry that needs them.
 static int ensure_panels(ck_handle* h);
 static int ensure_layout(ck_handle* h, bool need_panels = true) {
-    if (h->layout_ready) return need_panels ? ensure_panels(h) : 0;
+    if (h->layout_ready) {
+        // tables of a model set before the last ck_set_model (a handle kept across models, e.g. the likelihood's)
+        if (h->tables_stale && build_tables(h, h->qbox)) return -1;
+        h->tables_stale = false;
+        return need_panels ? ensure_panels(h) : 0;
+    }
     if (!h->model_set) return fail("ck_set_model has not been called");
     for (int k = 0; k < h->n_procs; ++k)
         if (!h->data_set[k]) return fail("ck_set_data missing for process " + std::to_string(k));
@@ -553,7 +571,9 @@ static int ensure_layout(ck_handle* h, bool need_panels = true) {
     HIPCHK(hipStreamSynchronize(h->stream));
     // squared bounding-box diagonal of the data sites (Euclidean table range)
     const double qbox = (bhi[0] - blo[0]) * (bhi[0] - blo[0]) + (bhi[1] - blo[1]) * (bhi[1] - blo[1]);
+    h->qbox = qbox;
     if (build_tables(h, qbox)) return -1;
+    h->tables_stale = false;
     h->layout_ready = true;
     return need_panels ? ensure_panels(h) : 0;
 }
@@ -1714,6 +1734,7 @@ extern "C" int ck_aux_finish(ck_handle* h, double* pred, double* pred_err) {
     CHKH(h);
     if (h->mpad <= 0) return fail("ck_aux_begin has not been called");
     if (h->aux_state == 3) return fail("ck_aux_finish: the last call was ck_predict_blocks; call ck_aux_begin first");
+    if (h->aux_state == 4) return fail("ck_aux_finish: the last call was ck_loglik; call ck_aux_begin first");
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     const double c0 = h->blk[2 * h->i_pred].amp + h->blk[2 * h->i_pred].nugget;   // sigma_i^2 + nugget_i (model.py:194-196 at h = 0)
     ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, h->m, h->m, c0, h->d_pred, h->d_err);
@@ -1882,6 +1903,9 @@ extern "C" int ck_verify_model(ck_handle* h, int64_t* info) {
     if (h->aux_state == 3)
         return fail("ck_verify_model: the last call was ck_predict_blocks, whose right-hand sides are block sums; call ck_predict "
                     "with the sites to check first");
+    if (h->aux_state == 4)
+        return fail("ck_verify_model: the last call was ck_loglik, whose right-hand sides are the data sites' unit rows; call "
+                    "ck_predict with the sites to check first");
     if (h->aux_state != 2) return fail("ck_verify_model needs the solved right-hand sides of a preceding ck_predict");
     const int64_t m = h->m, mpad = h->mpad;
     *info = 0;
@@ -2280,6 +2304,160 @@ extern "C" int ck_loocv(ck_handle* h, int i, double* pred, double* pred_err) {
         const double e = sqrt(1.0 / s2[q]);
         pred_err[x] = (e == e) ? e : 0.0;
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// Gaussian log-likelihood of the joint model and its gradient (ck_lik.hip)
+// ---------------------------------------------------------------------------------------
+// The predictor's computation read the other way round: with Sigma = L L^T resident,
+//   log|Sigma| = 2 sum log L_qq (k_lik_logdet), z^T Sigma^-1 z = |y|^2, y = L^-1 z: the data row of a one-row sweep.
+// The gradient needs G = alpha alpha^T - Sigma^-1.  The right-hand sides are the leave-one-out layout of ck_loocv extended to
+// the unit vectors of ALL Npad internal positions (row 0 = z, row 1 + p = e_p; padding positions solve to themselves), swept
+// through the factor on the growing prefix of live rows (aux_rows); then alpha_p = W_p . y (k_reduce_pred, raw mode),
+// G = alpha alpha^T - W^T W on the lower tiles with the structurally zero panels skipped (ck_la.hip: k_ginv_syrk_d, N^3 / 3
+// flop), and one pass of k_loglik_grad over G.  The handle's own state: the factor stays resident; the right-hand sides are
+// not prediction rows (aux_state 4: ck_verify_model / ck_aux_finish refuse until the next ck_predict / ck_aux_begin).
+struct LikCallGuard {
+    ck_handle* h;
+    explicit LikCallGuard(ck_handle* hh) : h(hh) { h->aux_state = 4; }
+    ~LikCallGuard() {
+        h->aux_state = 4;
+        h->loo_g0 = -1;
+    }
+};
+
+extern "C" int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad, int64_t* info) {
+    CHKH(h);
+    if (!out3 || !info || (want_grad && !grad)) return fail("ck_loglik: null argument");
+    if (h->world != 1)
+        return fail("ck_loglik is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) +
+                    "); the multi-GPU likelihood is not available");
+    if (!h->assembled) return fail("ck_loglik: ck_assemble_joint has not been called");
+    const auto t_begin = std::chrono::steady_clock::now();
+    const int64_t Np = h->Npad;
+    const int npar = h->n_procs == 1 ? 4 : CK_LIK_NPAR;
+    *info = 0;
+    out3[0] = out3[1] = out3[2] = NAN;
+    if (want_grad)
+        for (int k = 0; k < npar; ++k) grad[k] = NAN;
+    // device memory of the gradient: N + 1 unit / data rows of Npad doubles (the right-hand sides, mpad = Npad + 256 rows) and
+    // the lower triangle of G (packed block columns with their tails, as the Schur complement of ck_verify_model)
+    const int64_t mrows = want_grad ? Np : 0;
+    const int64_t mpad_need = roundup(mrows + 1, CK_AUX_ALIGN);
+    if (want_grad) {
+        int64_t g_bytes = 0;
+        for (int J = 0; J < h->nK; ++J) g_bytes += ((Np - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;
+        const int64_t aux_bytes = mpad_need * Np * 8;
+        const int64_t need = (aux_bytes > h->aux_cap * 8 ? aux_bytes : 0) + (h->sch_M == Np ? 0 : g_bytes);
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        int64_t avail = (int64_t)fr;
+        if (!h->arena) avail += h->aux_cap * 8;   // the right-hand sides' buffer is released before a larger one is taken
+        if (h->sch_M != Np)
+            for (int J = 0; J < (int)h->sch_sig.size(); ++J)
+                avail += ((h->sch_M - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;   // schur_ensure releases these first
+        if (h->arena && aux_bytes > h->aux_cap * 8 && aux_bytes > h->arena_size - h->arena_used)
+            return fail("ck_loglik: the gradient needs " + std::to_string(aux_bytes) + " bytes of the arena for its " +
+                        std::to_string(mrows + 1) + " right-hand-side rows of " + std::to_string(Np) + " doubles; " +
+                        std::to_string(h->arena_size - h->arena_used) + " bytes are left");
+        if (need > avail)
+            return fail("ck_loglik: the gradient needs " + std::to_string(aux_bytes + g_bytes) + " bytes of device memory (" +
+                        std::to_string(aux_bytes) + " for N + 1 rows of " + std::to_string(Np) + " doubles, " +
+                        std::to_string(g_bytes) + " for the lower triangle of G); " + std::to_string(avail) +
+                        " bytes are available");
+    }
+    LikCallGuard guard(h);
+    for (int k = 24; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    h->t_ms[24] = h->t_ms[0];   // the assembly of this Sigma (ck_assemble_joint)
+    auto elapsed = [&](hipEvent_t a, hipEvent_t b) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, a, b);
+        return (double)ms;
+    };
+    // ---- the factor: factor here, or the resident one of a preceding ck_factor
+    if (!h->factored) {
+        if (ck_factor(h, info)) return -1;
+        h->t_ms[25] = h->t_ms[1];
+    } else {
+        if (factor_info_raw(h, info)) return -1;
+    }
+    if (*info != 0) {   // not positive definite: the factor is unusable; assemble again before the next call
+        h->factored = false;
+        h->assembled = false;
+        h->t_ms[29] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        return 0;
+    }
+    const CkLayout L = layout_of(h);
+    DevTemps tmp;
+    // ---- right-hand sides: row 0 = z, rows 1 .. mrows = the unit vectors of every internal position; the sweep
+    if (aux_begin_impl(h, 0, nullptr, mrows, false)) return -1;
+    h->aux_state = 4;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    HIPCHK(hipMemsetAsync(h->aux, 0, (size_t)h->mpad * Np * 8, h->stream));
+    h->loo_g0 = 0;
+    ck_launch_loo_rows(h->stream, h->aux, h->mpad, mrows, 0, h->z, Np);
+    const int rc = solve_sweep(h);
+    h->loo_g0 = -1;
+    if (rc) return -1;
+    // alpha_p = W_p . y (d_pred[1 + p]) and |y|^2 (d_pred[0]); log L_qq per panel
+    ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, mrows + 1, 0, -1.0, h->d_pred, h->d_err);
+    double* d_ldp = nullptr;
+    HIPCHK(tmp.get(&d_ldp, (size_t)h->nK * 8));
+    ck_launch_lik_logdet(h->stream, h->d_sigptr, h->nK, L, d_ldp);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    std::vector<double> ldp((size_t)h->nK);
+    double quad = 0.0;
+    HIPCHK(hipMemcpyAsync(ldp.data(), d_ldp, (size_t)h->nK * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&quad, h->d_pred, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->t_ms[26] = elapsed(h->ev0, h->ev1);
+    double half_logdet = 0.0;
+    for (int K = 0; K < h->nK; ++K) half_logdet += ldp[(size_t)K];
+    const double logdet = 2.0 * half_logdet;
+    out3[1] = logdet;
+    out3[2] = quad;
+    out3[0] = -0.5 * ((double)h->N * log(2.0 * M_PI) + logdet + quad);
+    if (want_grad) {
+        // ---- G = alpha alpha^T - Sigma^-1, lower tiles of the first nend rows
+        if (schur_ensure(h, Np)) return -1;
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        ck_launch_ginv_syrk(h->stream, h->d_sch_ptr, h->aux, h->mpad, h->d_pred + 1, h->nK, h->nend);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        // ---- the contraction: the model's blocks and their nu +- dnu, nu +- 2 dnu neighbours
+        const int nblk = h->n_procs == 1 ? 1 : 3;
+        CkMatern hb[15];
+        double dnu3[3] = {0.0, 0.0, 0.0};
+        const double offs[4] = {-2.0, -1.0, 1.0, 2.0};
+        for (int b = 0; b < 3; ++b) {
+            const CkMatern& m = h->blk[b < nblk ? b : 0];
+            dnu3[b] = ck_matern_dnu_step(m.nu);
+            hb[5 * b] = m;
+            for (int k = 0; k < 4; ++k)
+                ck_matern_prepare(m.nu + offs[k] * dnu3[b], m.len_scale, m.amp, m.nugget, &hb[5 * b + 1 + k]);
+        }
+        if (!h->d_lik_blk) HIPCHK(hipMalloc((void**)&h->d_lik_blk, sizeof(hb)));
+        HIPCHK(hipMemcpyAsync(h->d_lik_blk, hb, sizeof(hb), hipMemcpyHostToDevice, h->stream));
+        const int64_t ngr = ck_lik_grad_groups(L);
+        double* d_part = nullptr;
+        HIPCHK(tmp.get(&d_part, (size_t)(ngr * CK_LIK_NPAR) * 8));
+        ck_launch_loglik_grad(h->stream, h->d_sch_ptr, L, h->n_procs, h->metric, h->s0, h->d_lik_blk, dnu3, h->par_sigma[0],
+                              h->par_sigma[1], h->par_rho, d_part);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev2, h->stream));
+        std::vector<double> part((size_t)(ngr * CK_LIK_NPAR));
+        HIPCHK(hipMemcpyAsync(part.data(), d_part, part.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));   // (hb is stack memory)
+        h->t_ms[27] = elapsed(h->ev0, h->ev1);
+        h->t_ms[28] = elapsed(h->ev1, h->ev2);
+        double g[CK_LIK_NPAR] = {};
+        for (int64_t w = 0; w < ngr; ++w)
+            for (int k = 0; k < CK_LIK_NPAR; ++k) g[k] += part[(size_t)(w * CK_LIK_NPAR + k)];
+        for (int k = 0; k < npar; ++k) grad[k] = g[k];
+    }
+    h->t_ms[29] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return 0;
 }
 

@@ -125,6 +125,11 @@ void ck_launch_aux_group(hipStream_t s, double* aux, int64_t mpad, double* const
 // complement (ck_verify_model); aux: np block columns of mpad x CK_NB solved right-hand-side rows
 void ck_launch_schur_syrk(hipStream_t s, double* const* schur_dev, const double* aux, int64_t mpad, int np, int nJ,
                           int64_t Mpad);
+// G = alpha alpha^T - W^T W over the unit right-hand-side rows of all data sites (ck_loglik; row 1 + p of aux = W_p, alpha[p]
+// = W_p . y): the lower tiles of the first nvalid rows of the Npad = nK NB order, packed block columns G_dev[J]; a tile skips
+// the panels in front of its first row, where its W rows are zero.  mpad >= Npad + 1 (the rows read are 1 .. Npad).
+void ck_launch_ginv_syrk(hipStream_t s, double* const* G_dev, const double* aux, int64_t mpad, const double* alpha, int nK,
+                         int64_t nvalid);
 // In-place Cholesky of the 64 x 64 diagonal block at A (ld); info_dev gets global_index0 + j + 1 of
 // the first non-positive pivot (only if still 0).
 void ck_launch_potrf64(hipStream_t s, double* A, int64_t ld, int64_t global_index0, long long* info_dev,
@@ -149,6 +154,18 @@ void ck_launch_loo_rows(hipStream_t s, double* aux, int64_t mpad, int64_t m, int
                         int64_t npad);
 void ck_launch_mfma_probe(hipStream_t s, int32_t* out);
 int ck_launch_mfma_peak(hipStream_t s, int blocks, int waves_per_simd, int iters, double* sink);
+
+// ---- Gaussian log-likelihood (ck_lik.hip) ----------------------------------------------------
+// part[K] = sum of log L_qq over the valid rows q of panel K (sigptr[K]: rows K NB .., ld = NB), nK panels
+void ck_launch_lik_logdet(hipStream_t s, double* const* sigptr_dev, int nK, CkLayout L, double* part);
+// The contraction 1/2 sum_pq G_pq dSigma_pq / dtheta_k over the lower triangle of G (packed block columns G_dev[J], the
+// off-diagonal entries counted twice) with the exact evaluator.  blk5[5 b .. 5 b + 4]: Matern block b = 0 (11), 1 (12), 2 (22)
+// and the same block at nu - 2 dnu_b, nu - dnu_b, nu + dnu_b, nu + 2 dnu_b.  c: 3 x npad exact-formula coordinates.
+// part: CK_LIK_NPAR doubles per workgroup (ck_lik_grad_groups of them), in the flat order of the parameters.
+#define CK_LIK_NPAR 11
+int64_t ck_lik_grad_groups(CkLayout L);
+void ck_launch_loglik_grad(hipStream_t s, double* const* G_dev, CkLayout L, int n_procs, int metric, const double* c,
+                           const CkMatern* blk5, const double* dnu3, double sig1, double sig2, double rho, double* part);
 
 // ---- empirical variogram (ck_vario.hip) ----------------------------------------------------
 #ifndef CK_VG_JSUB

@@ -401,9 +401,11 @@ struct CkSrcAux {
 // NI: 16-row blocks this WAVE computes (4: all of its 64 rows).  A right-hand-side tile row that holds only a few rows in front of
 // the padding (m + 1 = 8 834 rows: 69 tile rows and two rows) runs with NI = 1 in the waves of the upper half and NI = 0 -- staging
 // and barriers only -- in the others (k_tall_group_d): an eighth of a tile's MFMAs; a row's result does not depend on its neighbours.
-template <int WAVES, class SRC, int NI = 4>
+// RANK1 (k_ginv_syrk_d): the accumulators start from ar[row] ac[col] instead of the C tile (which is then written, not read)
+template <int WAVES, class SRC, int NI = 4, bool RANK1 = false>
 __device__ __forceinline__ void gemm_tile_d(double* __restrict__ C, long ldc, const SRC& src, int np, long r0, long c0,
-                                            char* lds) {
+                                            char* lds, const double* __restrict__ ar = nullptr,
+                                            const double* __restrict__ ac = nullptr) {
     static_assert(WAVES == 8, "8 waves of 64 x 32");
     constexpr int NA = NI > 0 ? NI : 1;
     constexpr int BOFF = 128 * 128;
@@ -461,14 +463,25 @@ __device__ __forceinline__ void gemm_tile_d(double* __restrict__ C, long ldc, co
     }
     CK_DMA_CHUNK(0, 0L);
     d4_t acc[NA][WJ];
+    if constexpr (RANK1) {
 #pragma unroll
-    for (int i = 0; i < NI; ++i)
+        for (int i = 0; i < NI; ++i)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const ck_gchar* rowp = reinterpret_cast<const ck_gchar*>(Cb + (long)(i * 16 + 4 * r) * ldc);   // wave-uniform
+            for (int r = 0; r < 4; ++r) {
+                const double a = ar[wm * 64 + g + i * 16 + 4 * r];
 #pragma unroll
-            for (int j = 0; j < WJ; ++j) acc[i][j][r] = -*reinterpret_cast<const ck_gdouble*>(rowp + j * 128 + c_off);
-        }
+                for (int j = 0; j < WJ; ++j) acc[i][j][r] = -(a * ac[wn * (WJ * 16) + j * 16 + li]);
+            }
+    } else {
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const ck_gchar* rowp = reinterpret_cast<const ck_gchar*>(Cb + (long)(i * 16 + 4 * r) * ldc);   // wave-uniform
+#pragma unroll
+                for (int j = 0; j < WJ; ++j) acc[i][j][r] = -*reinterpret_cast<const ck_gdouble*>(rowp + j * 128 + c_off);
+            }
+    }
     __builtin_amdgcn_s_waitcnt(0);   // C and the first chunk have landed
     __syncthreads();
 
@@ -720,6 +733,44 @@ void ck_launch_schur_syrk(hipStream_t s, double* const* schur_dev, const double*
     const CkTileMap map = ck_tilemap_make(std::min<int64_t>(mpad / 128 * 128, Mpad), 0, 1, nJ);
     if (map.total <= 0) return;
     k_schur_syrk_d<<<dim3((unsigned)map.total), dim3(512), 0, s>>>(schur_dev, aux, mpad, np, map);
+}
+
+// G = alpha alpha^T - Sigma^-1 of the log-likelihood's gradient (ck_loglik), lower triangle in packed block columns like the
+// Schur complement above.  W: the solved unit right-hand-side rows of ALL data sites, row 1 + p = (L^-1 e_p)^T (row 0 = y),
+// so (Sigma^-1)_pq = W_p . W_q; alpha_p = W_p . y.  W_p is zero in every column before p (L^-1 is lower triangular): a tile
+// whose first row is p0 needs the panels from p0 / NB on only (the rows are the larger index of a lower tile), so the launch
+// performs N^3 / 3 flop instead of N^3.  The accumulators start from the rank-1 term (gemm_tile_d, RANK1).
+struct CkSrcGinv {
+    const double* aux;
+    long mpad;
+    int K0;
+    long ra, rb;   // aux rows of the tile's first row / column (1 + index)
+    __device__ __forceinline__ void get(int p, const ck_gchar*& A, const ck_gchar*& B) const {
+        const double* base = aux + (long)(K0 + p) * mpad * CK_NB;
+        A = as_global(reinterpret_cast<const char*>(base + ra * CK_NB));
+        B = as_global(reinterpret_cast<const char*>(base + rb * CK_NB));
+    }
+};
+
+__global__ __launch_bounds__(512, 4) void k_ginv_syrk_d(double* const* __restrict__ G, const double* __restrict__ aux, long mpad,
+                                                         const double* __restrict__ alpha, int nK, const CkTileMap map) {
+    __shared__ __attribute__((aligned(16))) char lds[2 * 256 * 128];
+    int u, tm, tn;
+    ck_tilemap_get(map, xcd_remap(blockIdx.x, (int)map.total), u, tm, tn);
+    const int J = map.J0 + u * map.Jstep;
+    const long r0 = (long)tm * 128, c0 = (long)tn * 128;
+    const long p0 = (long)J * CK_NB + r0, q0 = (long)J * CK_NB + c0;
+    const int K0 = (int)(p0 / CK_NB);
+    const CkSrcGinv src{aux, mpad, K0, 1 + p0, 1 + q0};
+    gemm_tile_d<8, CkSrcGinv, 4, true>(G[J], CK_NB, src, nK - K0, r0, c0, lds, alpha + p0, alpha + q0);
+}
+
+void ck_launch_ginv_syrk(hipStream_t s, double* const* G_dev, const double* aux, int64_t mpad, const double* alpha, int nK,
+                         int64_t nvalid) {
+    if (nK <= 0) return;
+    const CkTileMap map = ck_tilemap_make(nvalid, 0, 1, nK);
+    if (map.total <= 0) return;
+    k_ginv_syrk_d<<<dim3((unsigned)map.total), dim3(512), 0, s>>>(G_dev, aux, mpad, alpha, nK, map);
 }
 
 // srcptr_dev: readable location of every panel (== sigptr_dev in a single-process run); Jstep > 1 is the

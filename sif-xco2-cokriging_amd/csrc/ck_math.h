@@ -281,3 +281,134 @@ CK_HD double ck_cov_entry(const CkMatern& m, double h, int add_nugget) {
     const double s = m.sqrt2nu * (h / m.len_scale);
     return m.amp * ck_matern_rho_scaled(m, s);
 }
+
+// --------------------------------------------------------------------------
+// Derivatives of the Matern correlation M (the Gaussian log-likelihood's gradient, ck_lik.hip)
+// --------------------------------------------------------------------------
+// With x = sqrt(2 nu) h / ell and M = 2^(1-nu) / Gamma(nu) x^nu K_nu(x), dK_nu/dx = -K_(nu-1) - (nu / x) K_nu gives
+//     dM/dx = -2^(1-nu) / Gamma(nu) x^nu K_(nu-1)(x),     dM/d ell = -(x / ell) dM/dx.
+// ck_matern_dlen_scaled returns D(x) = 2^(1-nu) / Gamma(nu) x^nu K_(nu-1)(x), so that dM/d ell = (x / ell) D(x).
+// Half-integer kinds: D = x e^-x (nu = 3/2), x (1 + x) / 3 e^-x (5/2), x (3 + 3x + x^2) / 15 e^-x (7/2), e^-x (1/2).
+// General kind: K_(nu-1) is the order before the last step of the upward recurrence of ck_matern_rho_scaled.  With
+// nl = round(nu) = 0 (nu < 1/2) it is K_(mu-1) = K_(1-mu): for x <= 2 the Temme series of K_(1-mu) (p and q swap roles
+// under mu -> -mu), for x > 2 the downward step K_(mu-1) = K_(mu+1) - (2 mu / x) K_mu (no cancellation there).
+// Non-finite results are 0, as for M itself.
+
+// Temme's series with the extra sum of K_(1-mu):  *k1m = K_(1-mu)(x), 0 < x <= 2
+CK_HD void ck_temme_km1(const CkMatern& m, double x, double* kmu, double* kmu1, double* k1m) {
+    const double x2 = 0.5 * x;
+    const double d = -log(x2);
+    const double e = m.mu * d;
+    double E = exp(e);
+    double Ei = 1.0 / E;
+    double ch = 0.5 * (E + Ei);
+    double shc;
+    if (fabs(e) < 0.5) {
+        const double e2 = e * e;
+        shc = 1.0 + e2 * (1.0 / 6 + e2 * (1.0 / 120 + e2 * (1.0 / 5040 + e2 * (1.0 / 362880 +
+              e2 * (1.0 / 39916800 + e2 * (1.0 / 6227020800.0 + e2 * (1.0 / 1307674368000.0)))))));
+    } else {
+        shc = 0.5 * (E - Ei) / e;
+    }
+    double ff = m.fact * (m.gam1 * ch + m.gam2 * shc * d);
+    double sum = ff;
+    double p = 0.5 * E / m.gampl;
+    double q = 0.5 * Ei / m.gammi;
+    double c = 1.0;
+    const double dd = x2 * x2;
+    double sum1 = p, sum2 = q;
+    for (int i = 1; i <= CK_TEMME_MAXIT; ++i) {
+        ff = (i * ff + p + q) * m.t_r[i];
+        c *= dd * m.t_i[i];
+        p *= m.t_p[i];
+        q *= m.t_q[i];
+        const double del = c * ff;
+        sum += del;
+        sum1 += c * (p - i * ff);
+        sum2 += c * (q - i * ff);
+        if (fabs(del) < fabs(sum) * 1e-17) break;
+    }
+    *kmu = sum;
+    *kmu1 = sum1 * (2.0 / x);
+    *k1m = sum2 * (2.0 / x);
+}
+
+CK_HD double ck_matern_dlen_scaled(const CkMatern& m, double s) {
+    double D;
+    switch (m.kind) {
+    case CK_KIND_HALF:
+        D = exp(-s);
+        break;
+    case CK_KIND_3HALF:
+        D = s * exp(-s);
+        break;
+    case CK_KIND_5HALF:
+        D = s * (1.0 + s) * (1.0 / 3.0) * exp(-s);
+        break;
+    case CK_KIND_7HALF:
+        D = s * (3.0 + s * (3.0 + s)) * (1.0 / 15.0) * exp(-s);
+        break;
+    default: {
+        double k0, k1, km = 0.0;
+        const double ls = log(s);
+        double ex;
+        if (s <= 2.0) {
+            ck_temme_km1(m, s, &k0, &k1, &km);
+            ex = m.lnpref + m.nu * ls;
+        } else {
+            ck_cf2(m, s, &k0, &k1);
+            km = k1 - 2.0 * m.mu / s * k0;   // K_(mu-1), scaled by e^s like k0 and k1
+            ex = m.lnpref + m.nu * ls - s;
+        }
+        const double xi2 = 2.0 / s;
+        double v = m.mu;
+        for (int i = 0; i < m.nl; ++i) {   // after the loop: k0 = K_nu, km = K_(nu-1)
+            v += 1.0;
+            const double kn = v * xi2 * k1 + k0;
+            km = k0;
+            k0 = k1;
+            k1 = kn;
+        }
+        D = exp(ex) * km;
+        break;
+    }
+    }
+    if (!(fabs(D) <= 1.79769313486231570815e308)) D = 0.0;
+    return D;
+}
+
+// M and its derivatives in ell and nu for one entry at lag h.  mv[0..3]: the same block prepared at nu - 2 dnu, nu - dnu,
+// nu + dnu, nu + 2 dnu (ck_matern_prepare on the host).  x depends on nu too (x = sqrt(2 nu) h / ell), so
+//     dM/dnu = dM/dnu|_x - D(x) x / (2 nu),
+// and only the first term, smooth in nu at a fixed x, is a difference of the evaluator: the fourth-order central one at
+// the SAME x (a difference at the same h would carry a truncation error that grows like x^2 in the tail).  Where M is 1
+// (h == 0) or 0 (clamped, non-finite, underflow) both derivatives are 0, as the value is constant there.
+#ifndef CK_DNU_REL
+#define CK_DNU_REL 2e-3
+#endif
+struct CkMaternGrad {
+    double M, dnu, dlen;
+};
+
+CK_HD CkMaternGrad ck_matern_grad(const CkMatern& m, const CkMatern* mv, double dnu, double h) {
+    CkMaternGrad g;
+    g.dnu = 0.0;
+    g.dlen = 0.0;
+    if (h == 0.0) {
+        g.M = 1.0;
+        return g;
+    }
+    const double s = m.sqrt2nu * (h / m.len_scale);
+    g.M = ck_matern_rho_scaled(m, s);
+    if (g.M == 0.0) return g;
+    const double D = ck_matern_dlen_scaled(m, s);
+    g.dlen = (s / m.len_scale) * D;
+    const double f0 = ck_matern_rho_scaled(mv[0], s), f1 = ck_matern_rho_scaled(mv[1], s);
+    const double f2 = ck_matern_rho_scaled(mv[2], s), f3 = ck_matern_rho_scaled(mv[3], s);
+    g.dnu = ((f0 - f3) + 8.0 * (f2 - f1)) / (12.0 * dnu) - D * s / (2.0 * m.nu);
+    return g;
+}
+
+// the step of the difference in nu: its truncation error (~ dnu^4) against the rounding of the evaluator (~ 1e-15 / dnu);
+// tests/test_host_matern_grad.py checks the result against finite differences of scipy
+CK_HD double ck_matern_dnu_step(double nu) { return CK_DNU_REL * nu; }

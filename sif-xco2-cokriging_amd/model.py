@@ -8,6 +8,10 @@ device K_nu; nothing is evaluated in numpy/scipy here.
 the reference's optimiser call -- scipy L-BFGS-B with its finite-difference gradient -- and
 evaluates the model variograms of every cost-function call in ONE device launch
 (``ck_model_variogram``).
+
+``log_likelihood`` / ``fit_likelihood`` (not in the reference) evaluate and maximise the Gaussian log-likelihood of the
+data the joint predictor uses, with its analytic gradient (``ck_loglik``): the factor, the unit-row sweep and the gradient
+contraction run on the device.
 """
 from __future__ import annotations
 
@@ -15,6 +19,7 @@ import warnings
 
 import numpy as np
 import pandas as pd
+from numpy.linalg import LinAlgError
 from scipy.optimize import minimize
 
 from . import native
@@ -141,6 +146,7 @@ class MultivariateMatern:
         self.fit_result = None
         self._device = device
         self._h = None
+        self._lik = None   # (key, handle): the data-loaded handle of log_likelihood
 
     def _handle(self):
         if self._h is None:
@@ -251,6 +257,140 @@ class MultivariateMatern:
         self.params.set_values(optim_result.x)
         self.fit_result = FittedVariogram(self, estimate, optim_result.fun)
         return self
+
+
+    # -- Gaussian log-likelihood -----------------------------------------------------------------
+    def _lik_handle(self, mf, dist_units, fast_dist):
+        """A handle with the data of ``mf`` loaded, kept on the model and keyed like Predictor._state_key (metric and
+        data arrays; the parameters are set again on every evaluation)."""
+        from .fields import metric_of
+        if mf.n_procs != self.n_procs:
+            raise ValueError("Number of theoretical processes different from empirical processes.")
+        metric = metric_of(dist_units, fast_dist)
+        cs, vs, key = [], [], [metric]
+        for k in range(self.n_procs):
+            c = np.ascontiguousarray(np.asarray(mf.fields[k].coords_main, dtype=np.float64)[:, :2])
+            v = np.ascontiguousarray(mf.fields[k].values_main, dtype=np.float64).ravel()
+            cs.append(c)
+            vs.append(v)
+            key += [c.shape, hash(c.tobytes()), hash(v.tobytes())]
+        key = tuple(key)
+        if self._lik is None or self._lik[0] != key:
+            if self._lik is not None:
+                self._lik[1].close()
+                self._lik = None
+            h = native.Handle(self._device)
+            h.set_metric(metric)
+            for k in range(self.n_procs):
+                h.set_data(k, cs[k], vs[k])
+            self._lik = (key, h)
+        h = self._lik[1]
+        configure_handle(h, self)
+        return h
+
+    def log_likelihood(self, mf, dist_units: str = "km", fast_dist: bool = True, gradient: bool = False):
+        """Gaussian log-likelihood of the data the joint predictor uses (every field's ``coords_main`` / ``values_main``,
+        zero mean as in simple cokriging) under the current parameters:
+            l = -1/2 (N log 2 pi + log|Sigma| + z^T Sigma^-1 z),
+        Sigma assembled as the predictor assembles it.  ``gradient=True``: (l, dl/dtheta) with the gradient in the flat
+        order of ``params.get_names()``.  A Sigma that is not positive definite raises LinAlgError with scipy's text."""
+        h = self._lik_handle(mf, dist_units, fast_dist)
+        h.assemble_joint()
+        info, out3, g = h.loglik(gradient)
+        if info != 0:
+            raise LinAlgError(f"{info}-th leading minor of the array is not positive definite")
+        return (out3[0], g) if gradient else out3[0]
+
+    def fit_likelihood(self, mf, guess: MaternParams = None, fixed=None, dist_units: str = "km", fast_dist: bool = True):
+        """Maximum-likelihood fit: L-BFGS-B on -l with the analytic gradient, within ``params.get_bounds()``.
+        ``guess`` as in ``fit``: None starts from the default parameters, else from the current ones with the bounds of
+        ``guess``.  ``fixed``: parameter names or flat indices held at their starting values.
+        The optimiser works on every free parameter mapped linearly onto [0, 1] over its bounds (the parameters differ by
+        three orders of magnitude in scale).  A step into a region where Sigma is not positive definite does not end the
+        fit: the cost there is the largest -l met so far plus 1e6 (1 + |that value|), finite and far above every positive
+        definite point, with the gradient of the last positive definite point, so that the line search backtracks; such
+        evaluations are counted in ``fit_result.n_not_pd``.  Sets the parameters and ``self.fit_result``
+        (FittedLikelihood)."""
+        if guess is None:
+            init = self.params.reset_values().get_values().astype(float)
+        else:
+            init = self.params.get_values().astype(float)
+            self.params.set_bounds(**{p.name: p.bounds for p in guess._params})
+        names = list(self.params.get_names())
+        bounds = np.array([tuple(b) for b in self.params.get_bounds()], dtype=float)
+        hold = set()
+        for f in ([] if fixed is None else ([fixed] if isinstance(fixed, (str, int, np.integer)) else fixed)):
+            if isinstance(f, str):
+                if f not in names:
+                    raise ValueError(f"`{f}` is not a parameter name ({names})")
+                hold.add(names.index(f))
+            else:
+                if not 0 <= int(f) < len(names):
+                    raise ValueError(f"parameter index {f} out of range")
+                hold.add(int(f))
+        free = np.array([k for k in range(len(names)) if k not in hold], dtype=int)
+        if free.size == 0:
+            raise ValueError("every parameter is fixed")
+        lo, width = bounds[free, 0], bounds[free, 1] - bounds[free, 0]
+        width = np.where(width > 0, width, 1.0)
+        init = init.copy()
+        init[free] = np.clip(init[free], bounds[free, 0], bounds[free, 1])
+        state = {"n_eval": 0, "n_not_pd": 0, "worst": None, "grad": np.zeros(free.size)}
+
+        def theta_of(u):
+            th = init.copy()
+            th[free] = lo + width * np.asarray(u, dtype=float)
+            return th
+
+        def cost(u):
+            state["n_eval"] += 1
+            self.params.set_values(theta_of(u))
+            try:
+                ll, g = self.log_likelihood(mf, dist_units, fast_dist, gradient=True)
+            except LinAlgError:
+                ll = None
+            if ll is None or not np.isfinite(ll) or not np.all(np.isfinite(g)):
+                state["n_not_pd"] += 1
+                worst = state["worst"]
+                if worst is None:
+                    raise LinAlgError("the starting point of fit_likelihood is not positive definite")
+                return worst + 1e6 * (1.0 + abs(worst)), state["grad"].copy()
+            f = -ll
+            gu = -np.asarray(g, dtype=float)[free] * width
+            state["worst"] = f if state["worst"] is None else max(state["worst"], f)
+            state["grad"] = gu
+            return f, gu
+
+        u0 = (init[free] - lo) / width
+        res = minimize(cost, u0, jac=True, method="L-BFGS-B", bounds=[(0.0, 1.0)] * free.size,
+                       options={"maxiter": 1000, "ftol": 1e-13, "gtol": 1e-9})
+        if res.success == False:   # noqa: E712  (as fit)
+            warnings.warn("ERROR: optimization did not converge.")
+        theta = theta_of(res.x)
+        self.params.set_values(theta)
+        ll, g = self.log_likelihood(mf, dist_units, fast_dist, gradient=True)
+        self.fit_result = FittedLikelihood(self, ll, g, free, state["n_eval"], state["n_not_pd"], res)
+        return self
+
+
+class FittedLikelihood:
+    """Result of ``MultivariateMatern.fit_likelihood``: the maximised log-likelihood, AIC = 2 k - 2 l over the k free
+    parameters, the gradient there, the numbers of evaluations and of evaluations at a Sigma that was not positive
+    definite, and the optimiser's message."""
+
+    def __init__(self, model: MultivariateMatern, loglik: float, gradient, free, n_eval: int, n_not_pd: int, optim) -> None:
+        self.params = model.params
+        self.names = list(model.params.get_names())
+        self.loglik = float(loglik)
+        self.gradient = np.asarray(gradient, dtype=float)
+        self.free = [self.names[k] for k in free]
+        self.n_free = len(free)
+        self.aic = 2.0 * self.n_free - 2.0 * self.loglik
+        self.n_eval = int(n_eval)
+        self.n_not_pd = int(n_not_pd)
+        self.success = bool(optim.success)
+        self.message = optim.message if isinstance(optim.message, str) else str(optim.message)
+        self.n_iter = int(getattr(optim, "nit", 0))
 
 
 class FittedVariogram:

@@ -50,6 +50,7 @@ _PROTOS = {
     "ck_verify_model": [c_void_p, POINTER(c_int64)],
     "ck_predict_blocks": [c_void_p, c_int, _dp, c_int64, POINTER(c_int32), _dp, c_int32, _dp, _dp, _dp],
     "ck_loocv": [c_void_p, c_int, _dp, _dp],
+    "ck_loglik": [c_void_p, c_int, _dp, _dp, POINTER(c_int64)],
     "ck_sample": [c_void_p, _dp, _dp, c_int64],
     "ck_num_panels": [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int64)],
     "ck_panel_owner": [c_void_p, c_int, POINTER(c_int)],
@@ -279,6 +280,7 @@ class Handle:
         if n_procs == 2 and (s.size != 2 or v.size != 3 or l.size != 3 or g.size != 2):
             raise ValueError("bivariate model needs sigma[2], nu[3], len_scale[3], nugget[2]")
         _chk(lib().ck_set_model(self._h, int(n_procs), _p(s), _p(v), _p(l), _p(g), float(rho12)))
+        self._n_procs = int(n_procs)
 
     def set_metric(self, metric: int):
         _chk(lib().ck_set_metric(self._h, int(metric)))
@@ -372,6 +374,25 @@ class Handle:
         _chk(lib().ck_predict_blocks(self._h, int(i), _p(pc), m, b.ctypes.data_as(POINTER(c_int32)), _p(w), r, _p(pred),
                                      _p(err), _p(cov) if cov is not None else None))
         return pred, err, cov
+
+    def loglik(self, want_grad=False):
+        """Gaussian log-likelihood of the loaded data under the model (include/cokrige.h: ck_loglik) on an assembled handle.
+        Returns (info, (l, log|Sigma|, z^T Sigma^-1 z), gradient | None); info != 0: Sigma is not positive definite (the
+        1-based leading minor) and the values are NaN.  The gradient is in MaternParams' flat order (11 or 4 values)."""
+        out3 = np.empty(3)
+        grad = np.empty(11) if want_grad else None
+        info = c_int64(0)
+        _chk(lib().ck_loglik(self._h, int(bool(want_grad)), _p(out3), _p(grad) if grad is not None else None, byref(info)))
+        if grad is not None and getattr(self, "_n_procs", 2) == 1:
+            grad = grad[:4].copy()
+        return info.value, tuple(out3.tolist()), grad
+
+    def loglik_timings(self):
+        """ck_timings [24 ..] of the last loglik() call, in milliseconds."""
+        out = np.zeros(30)
+        _chk(lib().ck_timings(self._h, _p(out), 30))
+        keys = ["assemble_ms", "factor_ms", "sweep_ms", "syrk_ms", "contract_ms", "total_ms"]
+        return dict(zip(keys, out[24:30].tolist()))
 
     def loocv(self, i, n_i):
         pred, err = np.empty(n_i), np.empty(n_i)
