@@ -189,6 +189,35 @@ int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad, int64_t* 
  * n = number of observations; needs ck_factor. */
 int ck_sample(ck_handle* h, const double* noise_host, double* out_host, int64_t n);
 
+/* Conditional simulation of process i at pcoords (m x 2) on the resident factor (needs ck_factor; single-process form):
+ * draws[d, k] = pred[k] + (L_S eps_d)[k],  S = C_pp - c0^T Sigma^-1 c0 (the S of ck_verify_model / ck_predict_blocks),
+ * L_S the Cholesky of S after deflation.  Outputs in the caller's site order.
+ *   1. pred / pred_err (m values each) are those of ck_predict on the same handle, bit for bit (the call runs it).
+ *   2. S is built in ck_verify_model's Schur buffers by the same code.
+ *   3. Deflation: site k with S_kk <= tol (sigma_i^2 + nugget_i) gets its row and column of S set to zero and S_kk = 1 -- a
+ *      site on a datum of process i has S_kk = 0, and for a positive semi-definite S its whole row is then zero, so removing
+ *      it is exact: its draws equal pred.  Every other S_kk gets jitter (sigma_i^2 + nugget_i) added.  deflated[k] (m bytes)
+ *      is 1 for a deflated site.
+ *   4. S is factored by the blocked Cholesky of the point path.  info = 0, or 1 + the caller's index of the site at whose
+ *      pivot the factorisation stopped; the call then returns 0 and leaves draws untouched (pred, pred_err, deflated are
+ *      valid).  Two sites with identical coordinates that are not deflated give identical rows of S: info names the later
+ *      of them (the library's internal order) without factoring.
+ *   5. noise (n_draws x m row-major, the caller's order) is used as given; NULL: normals from Philox4x32-10 with key = seed
+ *      and counter = (caller's site index k, d / 2, 0, 0), two 53-bit uniforms, FP64 Box-Muller (r cos t for even d,
+ *      r sin t for odd d).  Draw d therefore does not depend on n_draws, on the chunking or on the internal site order.
+ *      The noise of deflated sites is zeroed.
+ *   6. X = E L_S^T on the matrix cores over the lower tiles (m^2 n_draws flop), in chunks of option "draw_chunk" draws
+ *      (0, default: from the free device memory); every element sums in a fixed order: the same bits whatever the chunk.
+ * Refused (through ck_last_error): a partitioned handle, no factor, m outside 1 .. 65 536, n_draws < 1, tol or jitter
+ * negative or NaN, too little device memory (the message states the amount).  Needs m (m + 512) / 2 doubles of Schur
+ * buffers (as ck_verify_model) and (roundup(chunk, 128) roundup(m, 512) + 2 chunk m) doubles for a chunk.
+ * Afterwards the handle is as after ck_predict of these sites followed by ck_verify_model: the factor of Sigma stays
+ * resident, ck_predict gives the same bits as without the call, ck_verify_model the verdict it gives after ck_predict.
+ * ck_timings [30 ..] describe the call. */
+int ck_conditional_draws(ck_handle* h, int i, const double* pcoords_host, int64_t m, int64_t n_draws, uint64_t seed,
+                         const double* noise_host, double tol, double jitter, double* draws_host, double* pred_host,
+                         double* pred_err_host, uint8_t* deflated_host, int64_t* info);
+
 /* ---- step-wise form (multi-GPU, fused solve) ------------------------------ */
 int ck_num_panels(ck_handle* h, int* n_panels, int* panel_width, int64_t* n_padded);
 int ck_panel_owner(ck_handle* h, int K, int* owner_rank);
@@ -364,7 +393,11 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * ck_loglik (n up to 30): [24] the assembly of its Sigma (= [0] of that ck_assemble_joint); [25] its factorisation (0 when it
  * used a resident factor); [26] the sweep of the right-hand sides (the data row, with the gradient also the unit rows of all
  * data sites) with the reductions alpha, |y|^2 and log|Sigma|; [27] G = alpha alpha^T - Sigma^-1 (k_ginv_syrk_d);
- * [28] the contraction (k_loglik_grad); [29] host wall clock of the call. */
+ * [28] the contraction (k_loglik_grad); [29] host wall clock of the call.
+ * ck_conditional_draws (n up to 40): [30] the point prediction (host wall clock of its ck_predict); [31] the assembly of C_pp;
+ * [32] V^T V (k_schur_syrk_d); [33] deflation and jitter (k_draw_deflate, k_draw_zero); [34] the factor of S; [35] noise
+ * generation (k_draw_noise), summed over the chunks; [36] the draw product and its epilogue (k_draw_trmm), summed over the
+ * chunks; [37] host wall clock of the call; [38] number of deflated sites; [39] number of chunks. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it
@@ -419,6 +452,8 @@ int ck_table_fallbacks(ck_handle* h, int reset, int64_t* count);
  * workgroups that take their 64 x 512 strips (or halves / quarters of them) from a work queue -- the 48 KB table is loaded once per
  * workgroup instead of once per strip; automatic: the right-hand-side assembly (K2) with 768 workgroups from 8 strips per workgroup
  * on (N = 40 000: 0.62 -> 0.56 ms), Sigma (K1) never (faster on one box, slower on another);
+ * "draw_chunk" (default 0 = automatic: half of the free device memory, 128 .. 8192 draws): draws per product launch of
+ * ck_conditional_draws;
  * "block_chunk" (default 0 = automatic: what the arena has left, or half of the free device memory, beside the point rows
  * the handle holds): prediction sites per K2 assembly of ck_predict_blocks;
  * "local_slab_mb" = scratch budget of ck_predict_local in MiB (0, default: a quarter of the free memory, at most

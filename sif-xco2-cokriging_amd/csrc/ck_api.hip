@@ -32,7 +32,7 @@
 #include "ck_model.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 30
+#define CK_N_TIMINGS 40
 
 static int fail(const std::string& msg) { return ck_fail(msg); }   // thread-local text: ck_host.cpp (ck_last_error)
 #define HIPCHK(expr)                                                                              \
@@ -144,6 +144,7 @@ struct ck_handle {
     double* baux = nullptr;
     int64_t baux_cap = 0;   // doubles
     int64_t block_chunk = 0;
+    int64_t draw_chunk = 0;   // option "draw_chunk": draws per product launch of ck_conditional_draws (0: from the free device memory)
     // Schur complement of the prediction sites (ck_verify_model), kept between calls with the same padded order
     int64_t sch_M = 0;
     std::vector<double*> sch_sig;
@@ -174,7 +175,7 @@ struct ck_handle {
     int64_t vg_stats[4] = {0, 0, 0, 0};   // host-decided pairs of the extent pass | of the binning pass | pairs visited by
                                           // the binning pass | extra extent rounds
     // timings
-    double t_ms[CK_N_TIMINGS] = {};   // ck_timings; [16 ..] ck_predict_blocks
+    double t_ms[CK_N_TIMINGS] = {};   // ck_timings; [16 ..] ck_predict_blocks, [24 ..] ck_loglik, [30 ..] ck_conditional_draws
     int time_gemm = 0;   // 1: bracket every trailing-update launch with events | 2: the Sigma updates only (step-wise form)
     std::vector<EvPair> gemm_ev;
     size_t gemm_ev_used = 0;
@@ -1896,24 +1897,15 @@ static int schur_ensure(ck_handle* h, int64_t Mp) {
 
 static int factor_sweep(ck_handle* h);
 
-extern "C" int ck_verify_model(ck_handle* h, int64_t* info) {
-    CHKH(h);
-    if (!info) return fail("null info");
-    if (h->world != 1) return fail("ck_verify_model is the single-process form");
-    if (h->aux_state == 3)
-        return fail("ck_verify_model: the last call was ck_predict_blocks, whose right-hand sides are block sums; call ck_predict "
-                    "with the sites to check first");
-    if (h->aux_state == 4)
-        return fail("ck_verify_model: the last call was ck_loglik, whose right-hand sides are the data sites' unit rows; call "
-                    "ck_predict with the sites to check first");
-    if (h->aux_state != 2) return fail("ck_verify_model needs the solved right-hand sides of a preceding ck_predict");
+// S = C_pp - V^T V of the m prediction sites of the last ck_predict in the Schur buffers (schur_ensure(h, Mp) first): C_pp, the
+// auto-covariance of process i_pred at the sites (nugget where h == 0), assembled in the packed panel format of Sigma, minus
+// V^T V over the solved right-hand-side rows (k_schur_syrk_d).  Consumes the data row m of the right-hand sides.  ms_cpp /
+// ms_vtv (may be null): device milliseconds of the assembly and of V^T V.
+static int schur_build(ck_handle* h, double* ms_cpp = nullptr, double* ms_vtv = nullptr) {
     const int64_t m = h->m, mpad = h->mpad;
-    *info = 0;
-    if (m <= 0) return 0;
     const int64_t Mp = roundup(m, CK_NB);
     const int nJ = (int)(Mp / CK_NB);
-    if (schur_ensure(h, Mp)) return -1;
-    const auto t_begin = std::chrono::steady_clock::now();
+    const bool timed = ms_cpp || ms_vtv;
     // the prediction sites as a one-process site set: every tile uses the auto-block (i, i), replicated into all
     // three slots of the block / table arrays
     const int bi = 2 * h->i_pred;
@@ -1925,6 +1917,7 @@ extern "C" int ck_verify_model(ck_handle* h, int64_t* info) {
     HIPCHK(hipMemcpyAsync(h->d_sch_coefptr, hc, sizeof(hc), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->sch_pc, 0, (size_t)(2 * Mp) * 8, h->stream));
     HIPCHK(hipMemcpyAsync(h->sch_pc, h->d_pcoords, (size_t)(2 * m) * 8, hipMemcpyDeviceToDevice, h->stream));
+    if (timed) HIPCHK(hipEventRecord(h->ev0, h->stream));
     ck_launch_prep_sites(h->stream, h->sch_pc, Mp, h->metric, h->sch_c, h->sch_c + Mp, h->sch_c + 2 * Mp, h->sch_u);
     HIPCHK(hipStreamSynchronize(h->stream));   // hb / ht / hc are stack memory
     const CkLayout L{m, Mp, Mp, Mp};
@@ -1944,25 +1937,65 @@ extern "C" int ck_verify_model(ck_handle* h, int64_t* info) {
         if (cnt <= h->wl.cap) break;
     }
     HIPCHK(hipGetLastError());
+    if (timed) HIPCHK(hipEventRecord(h->ev1, h->stream));
     // row m of the right-hand sides is y = L^-1 z, not a prediction site (ck_aux_finish has consumed it)
     HIPCHK(hipMemset2DAsync(h->aux + m * CK_NB, (size_t)mpad * CK_NB * 8, 0, (size_t)CK_NB * 8, (size_t)h->nK, h->stream));
     ck_launch_schur_syrk(h->stream, h->d_sch_ptr, h->aux, mpad, h->nK, nJ, Mp);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(h->d_sch_info, 0, sizeof(long long), h->stream));
-    long long v = 0;
-    {
-        SchurSwap swap(h, nJ, Mp, m);
-        if (factor_sweep(h)) return -1;   // records ev1 at its end
-        HIPCHK(hipMemcpyAsync(&v, h->d_info, sizeof(v), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        unsigned werr = 0;
-        HIPCHK(hipMemcpy(&werr, h->d_coop + 16, sizeof(werr), hipMemcpyDeviceToHost));
-        if (werr != 0) {
-            HIPCHK(hipMemset(h->d_coop + 16, 0, sizeof(unsigned)));
-            h->panel_fused &= ~16;
-            return fail("cooperative panel step timed out (option panel_fused bit 4 now off): call ck_predict and ck_verify_model again");
-        }
+    if (timed) {
+        HIPCHK(hipEventRecord(h->ev2, h->stream));
+        HIPCHK(hipEventSynchronize(h->ev2));
+        float a = 0, b = 0;
+        HIPCHK(hipEventElapsedTime(&a, h->ev0, h->ev1));
+        HIPCHK(hipEventElapsedTime(&b, h->ev1, h->ev2));
+        if (ms_cpp) *ms_cpp = a;
+        if (ms_vtv) *ms_vtv = b;
     }
+    return 0;
+}
+
+// the blocked Cholesky of the Schur buffers (factor_sweep under SchurSwap); *v = 0 or the 1-based failing pivot among the m
+// sites in the library's internal order.  again: what the caller should repeat after a cooperative-step timeout.
+static int schur_factor(ck_handle* h, long long* v, const char* again) {
+    const int64_t m = h->m;
+    const int64_t Mp = roundup(m, CK_NB);
+    const int nJ = (int)(Mp / CK_NB);
+    HIPCHK(hipMemsetAsync(h->d_sch_info, 0, sizeof(long long), h->stream));
+    *v = 0;
+    SchurSwap swap(h, nJ, Mp, m);
+    if (factor_sweep(h)) return -1;   // records ev1 at its end
+    HIPCHK(hipMemcpyAsync(v, h->d_info, sizeof(*v), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    unsigned werr = 0;
+    HIPCHK(hipMemcpy(&werr, h->d_coop + 16, sizeof(werr), hipMemcpyDeviceToHost));
+    if (werr != 0) {
+        HIPCHK(hipMemset(h->d_coop + 16, 0, sizeof(unsigned)));
+        h->panel_fused &= ~16;
+        return fail(std::string("cooperative panel step timed out (option panel_fused bit 4 now off): ") + again);
+    }
+    return 0;
+}
+
+extern "C" int ck_verify_model(ck_handle* h, int64_t* info) {
+    CHKH(h);
+    if (!info) return fail("null info");
+    if (h->world != 1) return fail("ck_verify_model is the single-process form");
+    if (h->aux_state == 3)
+        return fail("ck_verify_model: the last call was ck_predict_blocks, whose right-hand sides are block sums; call ck_predict "
+                    "with the sites to check first");
+    if (h->aux_state == 4)
+        return fail("ck_verify_model: the last call was ck_loglik, whose right-hand sides are the data sites' unit rows; call "
+                    "ck_predict with the sites to check first");
+    if (h->aux_state != 2) return fail("ck_verify_model needs the solved right-hand sides of a preceding ck_predict");
+    const int64_t m = h->m;
+    *info = 0;
+    if (m <= 0) return 0;
+    const int64_t Mp = roundup(m, CK_NB);
+    if (schur_ensure(h, Mp)) return -1;
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (schur_build(h)) return -1;
+    long long v = 0;
+    if (schur_factor(h, &v, "call ck_predict and ck_verify_model again")) return -1;
     *info = (int64_t)v;   // 1-based index among the prediction sites in the library's internal order, 0 = positive definite
     h->t_ms[11] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return 0;
@@ -2254,6 +2287,177 @@ extern "C" int ck_sample(ck_handle* h, const double* noise, double* out, int64_t
     HIPCHK(hipStreamSynchronize(h->stream));
     memcpy(out, ho.data(), n0 * 8);
     if (n > n0) memcpy(out + n0, ho.data() + n0 + gap, (n - n0) * 8);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// conditional simulation: draws from the posterior of the joint predictor (ck_draws.hip, ck_la.hip: k_draw_trmm)
+// ---------------------------------------------------------------------------------------
+// draws[d] = pred + L_S eps_d with S = C_pp - V^T V the posterior covariance of the point predictions (ck_verify_model's
+// Schur complement, built by the same code) and L_S its Cholesky factor after deflation: a site whose S_kk is at most
+// tol (sigma_i^2 + nugget_i) -- in practice a site on a datum of process i, whose row and column of S vanish -- gets the row
+// and column e_k, so that its draw is pred; every other diagonal entry gets jitter (sigma_i^2 + nugget_i).  The noise comes
+// from the caller or from the Philox stream of ck_rng.h keyed on (seed, caller's site index, draw index), and the product
+// E L_S^T runs on the matrix cores over the lower tiles, in chunks of option "draw_chunk" draws.
+static int64_t schur_bytes(int64_t Mp) {
+    int64_t b = 0;
+    for (int64_t r = Mp; r > 0; r -= CK_NB) b += (r * CK_NB + CK_PANEL_TAIL) * 8;
+    return b + (2 * Mp + 6 * Mp) * 8;
+}
+
+extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, int64_t m, int64_t n_draws, uint64_t seed,
+                                    const double* noise, double tol, double jitter, double* draws, double* pred,
+                                    double* pred_err, uint8_t* deflated, int64_t* info) {
+    CHKH(h);
+    if (!pcoords || !draws || !pred || !pred_err || !deflated || !info) return fail("ck_conditional_draws: null argument");
+    if (h->world != 1)
+        return fail("ck_conditional_draws is the single-process form: this handle is partitioned (world = " +
+                    std::to_string(h->world) + ")");
+    if (!h->factored) return fail("ck_conditional_draws: ck_factor has not been called");
+    if (i < 0 || i >= h->n_procs) return fail("ck_conditional_draws: process index out of range");
+    if (m < 1 || m > 65536)
+        return fail("ck_conditional_draws: m = " + std::to_string(m) + " prediction sites; the posterior covariance is limited to "
+                    "1 .. 65 536 sites");
+    if (n_draws < 1) return fail("ck_conditional_draws: n_draws must be >= 1");
+    if (!(tol >= 0.0) || !(jitter >= 0.0)) return fail("ck_conditional_draws: tol and jitter must be >= 0");
+    const auto t_begin = std::chrono::steady_clock::now();
+    const int64_t Mp = roundup(m, CK_NB);
+    const int nJ = (int)(Mp / CK_NB);
+    // device memory: the Schur buffers, the right-hand sides of the point prediction, one chunk of 128 draws
+    {
+        const int64_t aux_bytes = roundup(m + 1, CK_AUX_ALIGN) * h->Npad * 8;
+        const int64_t s_bytes = h->sch_M == Mp ? 0 : schur_bytes(Mp);
+        const int64_t c_bytes = 128 * (Mp + (noise ? 2 : 1) * m) * 8 + (int64_t)m * 13 + Mp * 12 + 1024;
+        const int64_t need = (aux_bytes > h->aux_cap * 8 ? aux_bytes : 0) + s_bytes + c_bytes;
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        int64_t avail = (int64_t)fr;
+        if (!h->arena && aux_bytes > h->aux_cap * 8) avail += h->aux_cap * 8;   // released before a larger one is taken
+        if (s_bytes > 0 && h->sch_M > 0) avail += schur_bytes(h->sch_M);       // schur_ensure releases these first
+        if (need > avail)
+            return fail("ck_conditional_draws: needs " + std::to_string(need) + " bytes of device memory (" +
+                        std::to_string(s_bytes) + " for the posterior covariance of " + std::to_string(m) + " sites, " +
+                        std::to_string(c_bytes) + " for a chunk of 128 draws); " + std::to_string(avail) + " bytes are available");
+    }
+    for (int k = 30; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    *info = 0;
+    auto elapsed = [&](hipEvent_t a, hipEvent_t b) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, a, b);
+        return (double)ms;
+    };
+    auto wall_ms = [](std::chrono::steady_clock::time_point t0) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    };
+    // ---- 1. the point prediction (the same call, the same bits)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (ck_predict(h, i, pcoords, m, pred, pred_err)) return -1;
+        h->t_ms[30] = wall_ms(t0);
+    }
+    // ---- 2. S = C_pp - V^T V in the Schur buffers
+    if (schur_ensure(h, Mp)) return -1;
+    if (schur_build(h, &h->t_ms[31], &h->t_ms[32])) return -1;
+    // ---- 3. deflation and jitter
+    const double c0 = h->blk[2 * i].amp + h->blk[2 * i].nugget;   // sigma_i^2 + nugget_i
+    DevTemps tmp;
+    unsigned char* d_mask = nullptr;
+    int* d_cmap = nullptr;
+    double *d_pred = nullptr, *d_ones = nullptr;
+    HIPCHK(tmp.get(&d_mask, (size_t)m));
+    HIPCHK(tmp.get(&d_cmap, (size_t)Mp * sizeof(int)));
+    HIPCHK(tmp.get(&d_pred, (size_t)Mp * 8));
+    HIPCHK(tmp.get(&d_ones, 128 * 8));
+    std::vector<int> cmap((size_t)Mp, -1);
+    for (int64_t j = 0; j < m; ++j) cmap[(size_t)j] = (int)(h->p_sorted ? h->pperm[(size_t)j] : j);
+    const std::vector<double> ones(128, 1.0);
+    HIPCHK(hipMemcpyAsync(d_cmap, cmap.data(), (size_t)Mp * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_ones, ones.data(), 128 * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(d_pred, 0, (size_t)Mp * 8, h->stream));
+    HIPCHK(hipMemcpyAsync(d_pred, h->d_pred, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));   // internal order
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    ck_launch_draw_deflate(h->stream, h->d_sch_ptr, nJ, m, tol * c0, jitter * c0, d_mask);
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned char> mask((size_t)m);
+    HIPCHK(hipMemcpyAsync(mask.data(), d_mask, (size_t)m, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));   // (cmap / ones are host memory)
+    int64_t n_defl = 0;
+    for (int64_t j = 0; j < m; ++j) {
+        deflated[cmap[(size_t)j]] = mask[(size_t)j];
+        n_defl += mask[(size_t)j] != 0;
+    }
+    if (n_defl > 0) ck_launch_draw_zero(h->stream, h->d_sch_ptr, nJ, m, d_mask);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipEventSynchronize(h->ev1));
+    h->t_ms[33] = elapsed(h->ev0, h->ev1);
+    h->t_ms[38] = (double)n_defl;
+    // ---- 4. the factor of S.  Two sites at the same coordinates have identical rows of S: singular unless deflated.  The
+    // exact factorisation stops at the later of them (internal order); report that without leaving it to rounding.
+    {
+        std::vector<std::pair<std::pair<double, double>, int64_t>> key;
+        key.reserve((size_t)m);
+        for (int64_t j = 0; j < m; ++j)
+            if (!mask[(size_t)j]) key.push_back({{pcoords[2 * cmap[(size_t)j]], pcoords[2 * cmap[(size_t)j] + 1]}, j});
+        std::sort(key.begin(), key.end());
+        int64_t stop = -1;
+        for (size_t q = 1; q < key.size(); ++q)
+            if (key[q].first.first == key[q - 1].first.first && key[q].first.second == key[q - 1].first.second &&
+                (stop < 0 || key[q].second < stop))
+                stop = key[q].second;   // the larger internal index of the pair (equal keys are sorted by index)
+        if (stop >= 0) {
+            *info = 1 + cmap[(size_t)stop];
+            h->t_ms[37] = wall_ms(t_begin);
+            return 0;
+        }
+    }
+    {
+        long long v = 0;
+        HIPCHK(hipEventRecord(h->ev2, h->stream));
+        if (schur_factor(h, &v, "call ck_conditional_draws again")) return -1;
+        HIPCHK(hipEventRecord(h->ev3, h->stream));
+        HIPCHK(hipEventSynchronize(h->ev3));
+        h->t_ms[34] = elapsed(h->ev2, h->ev3);
+        if (v != 0) {
+            *info = 1 + (v - 1 < m ? cmap[(size_t)(v - 1)] : (int64_t)(v - 1));
+            h->t_ms[37] = wall_ms(t_begin);
+            return 0;
+        }
+    }
+    ck_launch_draw_upper(h->stream, h->d_sch_ptr, nJ);
+    HIPCHK(hipGetLastError());
+    // ---- 5 / 6. noise and the draw product, chunk by chunk
+    int64_t chunk = h->draw_chunk;
+    if (chunk <= 0) {
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        chunk = (int64_t)(fr / 2) / (8 * (Mp + (noise ? 2 : 1) * m)) / 128 * 128;
+        chunk = std::max<int64_t>(128, std::min<int64_t>(chunk, 8192));
+    }
+    chunk = std::min<int64_t>(chunk, n_draws);
+    const int64_t ldp = roundup(chunk, 128);
+    double *d_E = nullptr, *d_X = nullptr, *d_noise = nullptr;
+    HIPCHK(tmp.get(&d_E, (size_t)(ldp * Mp) * 8));
+    HIPCHK(tmp.get(&d_X, (size_t)(chunk * m) * 8));
+    if (noise) HIPCHK(tmp.get(&d_noise, (size_t)(chunk * m) * 8));
+    int n_chunks = 0;
+    for (int64_t d0 = 0; d0 < n_draws; d0 += chunk, ++n_chunks) {
+        const int64_t nd = std::min<int64_t>(chunk, n_draws - d0);
+        if (noise) HIPCHK(hipMemcpyAsync(d_noise, noise + d0 * m, (size_t)(nd * m) * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        ck_launch_draw_noise(h->stream, d_E, ldp, Mp, nd, m, d0, d_cmap, d_mask, d_noise, seed);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        ck_launch_draw_trmm(h->stream, d_X, m, d_E, ldp, nd, h->d_sch_ptr, d_pred, d_ones, d_cmap);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev2, h->stream));
+        HIPCHK(hipMemcpyAsync(draws + d0 * m, d_X, (size_t)(nd * m) * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->t_ms[35] += elapsed(h->ev0, h->ev1);
+        h->t_ms[36] += elapsed(h->ev1, h->ev2);
+    }
+    h->t_ms[39] = n_chunks;
+    h->t_ms[37] = wall_ms(t_begin);
     return 0;
 }
 
@@ -3505,6 +3709,11 @@ extern "C" int ck_set_option(ck_handle* h, const char* name, int64_t value) {
     if (!strcmp(name, "block_chunk")) {   // ck_predict_blocks: prediction sites per K2 assembly (0 = automatic)
         if (value < 0) return fail("block_chunk must be >= 0 (0 = automatic)");
         h->block_chunk = value;
+        return 0;
+    }
+    if (!strcmp(name, "draw_chunk")) {   // ck_conditional_draws: draws per product launch (0 = automatic)
+        if (value < 0) return fail("draw_chunk must be >= 0 (0 = automatic)");
+        h->draw_chunk = value;
         return 0;
     }
     if (!strcmp(name, "exact_cov")) {   // 1: per-entry Bessel evaluation instead of the tables

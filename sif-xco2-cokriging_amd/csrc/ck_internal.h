@@ -130,6 +130,12 @@ void ck_launch_schur_syrk(hipStream_t s, double* const* schur_dev, const double*
 // the panels in front of its first row, where its W rows are zero.  mpad >= Npad + 1 (the rows read are 1 .. Npad).
 void ck_launch_ginv_syrk(hipStream_t s, double* const* G_dev, const double* aux, int64_t mpad, const double* alpha, int nK,
                          int64_t nvalid);
+// Conditional simulation (ck_conditional_draws): X (nd x m, ld m, the caller's site order) = pred + eps L_S^T on the lower
+// tiles of the factor L_S in the Schur buffers (L_dev[J]: packed block columns, upper triangles of the diagonal blocks zero).
+// E: -eps in block columns of ldp >= roundup(nd, 128) rows (ck_launch_draw_noise); pred, cmap: Mp entries in the internal order
+// (cmap[j]: the caller's index of internal site j, -1 beyond m); ones: 128 doubles equal to 1.
+void ck_launch_draw_trmm(hipStream_t s, double* X, int64_t m, const double* E, int64_t ldp, int64_t nd, double* const* L_dev,
+                         const double* pred, const double* ones, const int* cmap);
 // In-place Cholesky of the 64 x 64 diagonal block at A (ld); info_dev gets global_index0 + j + 1 of
 // the first non-positive pivot (only if still 0).
 void ck_launch_potrf64(hipStream_t s, double* A, int64_t ld, int64_t global_index0, long long* info_dev,
@@ -166,6 +172,19 @@ void ck_launch_lik_logdet(hipStream_t s, double* const* sigptr_dev, int nK, CkLa
 int64_t ck_lik_grad_groups(CkLayout L);
 void ck_launch_loglik_grad(hipStream_t s, double* const* G_dev, CkLayout L, int n_procs, int metric, const double* c,
                            const CkMatern* blk5, const double* dnu3, double sig1, double sig2, double rho, double* part);
+
+// ---- conditional simulation (ck_draws.hip) ---------------------------------------------------
+// on the Schur buffers sch[J] (packed block columns of S, nJ of them), sites k < m:
+// mask[k] = S_kk <= thr; S_kk = 1 where deflated, else S_kk + jit
+void ck_launch_draw_deflate(hipStream_t s, double* const* sch, int nJ, int64_t m, double thr, double jit, unsigned char* mask);
+// the strictly lower entries of the deflated sites' rows and columns -> 0
+void ck_launch_draw_zero(hipStream_t s, double* const* sch, int nJ, int64_t m, const unsigned char* mask);
+// above the diagonal of the nJ diagonal blocks -> 0 (after the factorisation, in front of ck_launch_draw_trmm)
+void ck_launch_draw_upper(hipStream_t s, double* const* sch, int nJ);
+// E = -eps of draws d0 .. d0 + nd - 1 (ldp x Mp, block columns of ld NB; 0 beyond nd, beyond m and at deflated sites):
+// noise (nd x m, the caller's order) if given, else the Philox normals of ck_rng.h keyed on seed, counter (cmap[j], d / 2)
+void ck_launch_draw_noise(hipStream_t s, double* E, int64_t ldp, int64_t Mp, int64_t nd, int64_t m, int64_t d0, const int* cmap,
+                          const unsigned char* mask, const double* noise, uint64_t seed);
 
 // ---- empirical variogram (ck_vario.hip) ----------------------------------------------------
 #ifndef CK_VG_JSUB

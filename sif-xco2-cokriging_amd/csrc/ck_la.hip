@@ -402,10 +402,13 @@ struct CkSrcAux {
 // the padding (m + 1 = 8 834 rows: 69 tile rows and two rows) runs with NI = 1 in the waves of the upper half and NI = 0 -- staging
 // and barriers only -- in the others (k_tall_group_d): an eighth of a tile's MFMAs; a row's result does not depend on its neighbours.
 // RANK1 (k_ginv_syrk_d): the accumulators start from ar[row] ac[col] instead of the C tile (which is then written, not read)
-template <int WAVES, class SRC, int NI = 4, bool RANK1 = false>
+// SCATTER (k_draw_trmm): the tile's column c is stored to column cmap[c] of C (none where cmap[c] < 0), its rows only in front
+// of row_lim; C is then the output's base (c0 plays no part in the store)
+template <int WAVES, class SRC, int NI = 4, bool RANK1 = false, bool SCATTER = false>
 __device__ __forceinline__ void gemm_tile_d(double* __restrict__ C, long ldc, const SRC& src, int np, long r0, long c0,
                                             char* lds, const double* __restrict__ ar = nullptr,
-                                            const double* __restrict__ ac = nullptr) {
+                                            const double* __restrict__ ac = nullptr, const int* __restrict__ cmap = nullptr,
+                                            long row_lim = 0) {
     static_assert(WAVES == 8, "8 waves of 64 x 32");
     constexpr int NA = NI > 0 ? NI : 1;
     constexpr int BOFF = 128 * 128;
@@ -558,6 +561,22 @@ __device__ __forceinline__ void gemm_tile_d(double* __restrict__ C, long ldc, co
     }
 #undef CK_DMA_NEXT
 #undef CK_DMA_CHUNK
+    if constexpr (SCATTER) {
+        int col[WJ];
+#pragma unroll
+        for (int j = 0; j < WJ; ++j) col[j] = cmap[wn * (WJ * 16) + j * 16 + li];
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long row = r0 + wm * 64 + g + i * 16 + 4 * r;
+                if (row >= row_lim) continue;
+#pragma unroll
+                for (int j = 0; j < WJ; ++j)
+                    if (col[j] >= 0) C[row * ldc + col[j]] = -acc[i][j][r];
+            }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -771,6 +790,46 @@ void ck_launch_ginv_syrk(hipStream_t s, double* const* G_dev, const double* aux,
     const CkTileMap map = ck_tilemap_make(nvalid, 0, 1, nK);
     if (map.total <= 0) return;
     k_ginv_syrk_d<<<dim3((unsigned)map.total), dim3(512), 0, s>>>(G_dev, aux, mpad, alpha, nK, map);
+}
+
+// Conditional simulation (ck_conditional_draws): X = pred + eps L_S^T for a chunk of draws, L_S the factor of the
+// deflated posterior covariance in the Schur buffers (packed block columns, upper triangles of the diagonal blocks zeroed:
+// ck_draws.hip k_draw_upper).  Output tile (draw rows r0.., sites k0..): X = sum over the block columns p <= k0 / NB of
+// E_p L_S[k0.., p]^T -- the lower tiles only, K = NB (k0 / NB + 1), m^2 n_draws flop in all.  E holds -eps (ck_draws.hip:
+// k_draw_noise) in the same block-column layout (ld NB, ldp rows per block column); the accumulators start from -pred
+// (RANK1 with ar = ones) and are stored negated, so the tile is pred + eps L_S^T.  Every output element sums its K in the
+// same order whatever the chunk of draws it lands in: the draws' bits do not depend on the chunking.
+struct CkSrcDraw {
+    const double* E;
+    long ldp;
+    double* const* L;
+    long r0, k0;
+    __device__ __forceinline__ void get(int p, const ck_gchar*& A, const ck_gchar*& B) const {
+        A = as_global(reinterpret_cast<const char*>(E + (long)p * ldp * CK_NB + r0 * CK_NB));
+        B = as_global(reinterpret_cast<const char*>(L[p] + (k0 - (long)p * CK_NB) * CK_NB));
+    }
+};
+
+// one workgroup per 128 x 128 tile, the site tiles with the longest K first (blockIdx.x = tc_rev * tiles_r + tr)
+__global__ __launch_bounds__(512, 4) void k_draw_trmm(double* __restrict__ X, long ldx, const double* __restrict__ E, long ldp,
+                                                       double* const* __restrict__ L, const double* __restrict__ pred,
+                                                       const double* __restrict__ ones, const int* __restrict__ cmap,
+                                                       int tiles_r, int tiles_c, long nd) {
+    __shared__ __attribute__((aligned(16))) char lds[2 * 256 * 128];
+    const int tc = tiles_c - 1 - (int)(blockIdx.x / (unsigned)tiles_r);
+    const int tr = (int)(blockIdx.x % (unsigned)tiles_r);
+    const long r0 = (long)tr * 128, k0 = (long)tc * 128;
+    const CkSrcDraw src{E, ldp, L, r0, k0};
+    gemm_tile_d<8, CkSrcDraw, 4, true, true>(X, ldx, src, (int)(k0 / CK_NB) + 1, r0, 0, lds, ones, pred + k0, cmap + k0, nd);
+}
+
+// X: nd x m (the caller's site order, ld m); E: ldp x Mp in block columns; pred / cmap: Mp entries (cmap -1 beyond m)
+void ck_launch_draw_trmm(hipStream_t s, double* X, int64_t m, const double* E, int64_t ldp, int64_t nd, double* const* L_dev,
+                         const double* pred, const double* ones, const int* cmap) {
+    if (nd <= 0 || m <= 0) return;
+    const int tiles_r = (int)((nd + 127) / 128), tiles_c = (int)((m + 127) / 128);
+    k_draw_trmm<<<dim3((unsigned)(tiles_r * tiles_c)), dim3(512), 0, s>>>(X, (long)m, E, (long)ldp, L_dev, pred, ones, cmap,
+                                                                          tiles_r, tiles_c, (long)nd);
 }
 
 // srcptr_dev: readable location of every panel (== sigptr_dev in a single-process run); Jstep > 1 is the

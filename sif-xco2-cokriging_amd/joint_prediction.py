@@ -393,6 +393,115 @@ class Predictor:
         pred[missing] = np.nan
         return pred, err * sf, (cov * (sf * sf) if cov is not None else None)
 
+    # -- conditional simulation -------------------------------------------------------------------
+    MAX_DRAW_SITES = 65536   # include/cokrige.h: ck_conditional_draws
+
+    def conditional_draws_arrays(self, i: int, pcoords, n_draws: int, seed=None, noise=None, tol: float = 1e-10,
+                                 jitter: float = 0.0):
+        """Draws from the posterior of process ``i`` at ``pcoords`` -- the numeric body of ``conditional_simulation``.
+
+        draws[d] = pred + L_S eps_d, S = C_pp - c0^T Sigma^-1 c0 the posterior covariance of the point predictions
+        (include/cokrige.h: ck_conditional_draws).  A site on a datum of process ``i`` has zero posterior variance; it is
+        deflated (its draws equal pred).  Rows of ``pcoords`` that repeat a site are one random variable: they are removed
+        before the device call and get the draws of their first occurrence.  ``noise`` (n_draws, m) in the caller's sites
+        replaces the device's Philox stream (a duplicated site uses the column of its first occurrence); that stream is
+        keyed on ``seed`` and on the index in the de-duplicated sites.  ``seed=None`` takes 64 bits from
+        ``numpy.random.SeedSequence()``.  Runs on the resident factor of ``__call__``; with ``devices=[...]`` on
+        ``devices[0]``.
+
+        Returns (draws (n_draws, m), pred, pred_err, deflated (bool, m), seed).  Raises ValueError on bad arguments
+        before any device work, and numpy.linalg.LinAlgError when S cannot be factored."""
+        if isinstance(i, bool) or not (isinstance(i, (int, np.integer)) and 0 <= int(i) < self.n_procs):
+            raise ValueError(f"process index {i!r} out of range for {self.n_procs} processes")
+        pc = np.atleast_2d(np.asarray(pcoords.values if isinstance(pcoords, pd.DataFrame) else pcoords, dtype=np.float64))
+        if pc.ndim != 2 or pc.shape[1] < 2 or len(pc) < 1:
+            raise ValueError("pcoords must be [[lat, lon], ...] with at least one site")
+        pc = np.ascontiguousarray(pc[:, :2])
+        m = len(pc)
+        if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or n_draws < 1:
+            raise ValueError(f"n_draws must be an integer >= 1, not {n_draws!r}")
+        n_draws = int(n_draws)
+        if not (np.isfinite(tol) and tol >= 0.0) or not (np.isfinite(jitter) and jitter >= 0.0):
+            raise ValueError(f"tol and jitter must be finite and >= 0 (tol={tol!r}, jitter={jitter!r})")
+        if noise is not None:
+            noise = np.asarray(noise, dtype=np.float64)
+            if noise.shape != (n_draws, m):
+                raise ValueError(f"noise has shape {noise.shape}, expected (n_draws, m) = {(n_draws, m)}")
+        rows = pc.view([("a", np.float64), ("b", np.float64)]).ravel()
+        _, first, inv = np.unique(rows, return_index=True, return_inverse=True)
+        order = np.argsort(first)
+        keep = first[order]                       # the first occurrences, in the caller's order
+        rank = np.empty_like(order)
+        rank[order] = np.arange(len(order))
+        where = rank[np.asarray(inv).ravel()]     # caller's site -> its index among the kept sites
+        if len(keep) > self.MAX_DRAW_SITES:
+            raise ValueError(f"{len(keep)} distinct prediction sites; conditional draws are limited to {self.MAX_DRAW_SITES}")
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2^64)")
+        e = None if noise is None else np.ascontiguousarray(noise[:, keep])
+        h = self._factored_handle()
+        draws, pred, err, defl, info = h.conditional_draws(int(i), pc[keep], n_draws, seed=seed, noise=e, tol=tol,
+                                                           jitter=jitter)
+        if info != 0:
+            site = int(keep[info - 1])
+            raise LinAlgError(f"the posterior covariance of the prediction sites is not positive definite at site {site} "
+                              f"{tuple(pc[site])}; a small jitter (e.g. jitter=1e-10) regularises nearly coincident sites")
+        self.timings = h.draws_timings()
+        return draws[:, where], pred[where], err[where], defl[where], seed
+
+    def conditional_simulation(self, i: int, pcoords, n_draws: int = 100, seed=None, postprocess: bool = True, noise=None,
+                               tol: float = 1e-10, jitter: float = 0.0):
+        """Ensembles of maps drawn from the posterior of process ``i`` at ``pcoords`` (conditional simulation).
+
+        Nonlinear quantities -- exceedance probabilities, areas above a threshold, maxima, ratios, inputs to downstream
+        models -- need joint draws: neighbouring prediction errors are strongly correlated, so ``pred +- pred_err`` per site
+        cannot give them.  Returns an object shaped like ``__call__``'s output: an xarray Dataset with ``pred``,
+        ``pred_err`` and ``draws`` (a leading ``draw`` dimension), ``attrs`` holding ``seed``, ``n_deflated`` and
+        ``jitter``.  ``postprocess=True`` applies ``_postprocess_predictions``' transform to every draw (scale, spatial
+        mean, OLS trend, temporal trend).  Without xarray: ``(DataFrame, draws)`` -- the frame as ``__call__`` returns it
+        (with the attrs in ``DataFrame.attrs``) and the (n_draws, m) array in its row order.  See
+        ``conditional_draws_arrays`` for the arguments."""
+        if not isinstance(pcoords, pd.DataFrame):
+            a = np.atleast_2d(np.asarray(pcoords, dtype=np.float64))
+            if a.ndim != 2 or a.shape[1] < 2:
+                raise ValueError("pcoords must be [[lat, lon], ...]")
+            pcoords = pd.DataFrame({"d1": a[:, 0], "d2": a[:, 1]})
+        draws, pred, err, defl, seed = self.conditional_draws_arrays(i, pcoords.values[:, :2], n_draws, seed=seed,
+                                                                     noise=noise, tol=tol, jitter=jitter)
+        self.i = i
+        attrs = {"seed": seed, "n_deflated": int(defl.sum()), "jitter": float(jitter)}
+        df = pcoords.copy()
+        df["pred"], df["pred_err"] = pred, err
+        if postprocess:
+            df = df.rename(columns={"d1": "lat", "d2": "lon"})
+            at = self.mf.fields[i].ds.attrs
+            offset = at["spatial_mean"] + self._spatial_trend(df) + at["temporal_trend"]
+            draws = draws * at["scale_fact"] + offset
+            out = df[["lon", "lat"]].copy()
+            out["pred"] = pred * at["scale_fact"] + offset
+            out["pred_err"] = err * at["scale_fact"]
+            out = out.set_index(["lon", "lat"])
+        else:
+            out = df.set_index(pcoords.columns.values.tolist())
+        out.attrs.update(attrs)
+        if xr is None:
+            return out, draws
+        ds = out.to_xarray()
+        st = pd.DataFrame(draws.T, index=out.index, columns=pd.RangeIndex(draws.shape[0], name="draw")).stack()
+        ds["draws"] = st.to_xarray().transpose("draw", *ds["pred"].dims)
+        ds.attrs.update(attrs)
+        if postprocess:
+            return ds.assign_coords(coords={"time": np.datetime64(self.mf.fields[i].timestamp)})
+        ts = self.mf.fields[i].timestamp
+        try:
+            np.isnan(ts)
+            return ds
+        except TypeError:
+            return ds.assign_coords(coords={"time": np.datetime64(ts)})
+
     def cross_validation(self, i: int, postprocess: bool = True, refactor_each: bool = False) -> pd.DataFrame:
         """Leave-one-out cross-validation at each data location of process ``i``
         (src/joint_prediction.py:207-257).  The reference withholds one datum and re-assembles

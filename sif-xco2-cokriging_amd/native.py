@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_int32, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, byref, c_char_p, c_double, c_int, c_int32, c_int64, c_uint8, c_uint32, c_uint64, c_void_p
 
 import numpy as np
 
@@ -52,6 +52,8 @@ _PROTOS = {
     "ck_loocv": [c_void_p, c_int, _dp, _dp],
     "ck_loglik": [c_void_p, c_int, _dp, _dp, POINTER(c_int64)],
     "ck_sample": [c_void_p, _dp, _dp, c_int64],
+    "ck_conditional_draws": [c_void_p, c_int, _dp, c_int64, c_int64, c_uint64, _dp, c_double, c_double, _dp, _dp, _dp,
+                             POINTER(c_uint8), POINTER(c_int64)],
     "ck_num_panels": [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int64)],
     "ck_panel_owner": [c_void_p, c_int, POINTER(c_int)],
     "ck_aux_begin": [c_void_p, c_int, _dp, c_int64],
@@ -393,6 +395,36 @@ class Handle:
         _chk(lib().ck_timings(self._h, _p(out), 30))
         keys = ["assemble_ms", "factor_ms", "sweep_ms", "syrk_ms", "contract_ms", "total_ms"]
         return dict(zip(keys, out[24:30].tolist()))
+
+    def conditional_draws(self, i, pcoords, n_draws, seed=0, noise=None, tol=1e-10, jitter=0.0):
+        """Draws from the posterior of process i at pcoords on the resident factor (include/cokrige.h: ck_conditional_draws).
+        Returns (draws (n_draws, m), pred, pred_err, deflated (bool, m), info); info != 0: S could not be factored at the
+        caller's site info - 1 and ``draws`` holds zeros.  ``noise``: (n_draws, m) normals in the caller's order, else the
+        device's Philox stream keyed on ``seed``."""
+        pc = _f64(pcoords, 2)
+        m = pc.shape[0]
+        n_draws = int(n_draws)
+        e = None
+        if noise is not None:
+            e = _f64(noise)
+            if e.shape != (n_draws, m):
+                raise ValueError(f"noise has shape {e.shape}, expected {(n_draws, m)}")
+        draws = np.zeros((max(n_draws, 0), m))
+        pred, err = np.empty(m), np.empty(m)
+        defl = np.zeros(m, dtype=np.uint8)
+        info = c_int64(0)
+        _chk(lib().ck_conditional_draws(self._h, int(i), _p(pc), m, n_draws, c_uint64(int(seed) & (2 ** 64 - 1)),
+                                        _p(e) if e is not None else None, float(tol), float(jitter), _p(draws), _p(pred),
+                                        _p(err), defl.ctypes.data_as(POINTER(c_uint8)), byref(info)))
+        return draws, pred, err, defl.astype(bool), info.value
+
+    def draws_timings(self):
+        """ck_timings [30 ..] of the last conditional_draws() call (milliseconds; the last two are counts)."""
+        out = np.zeros(40)
+        _chk(lib().ck_timings(self._h, _p(out), 40))
+        keys = ["predict_ms", "cpp_ms", "vtv_ms", "deflate_ms", "factor_ms", "noise_ms", "product_ms", "total_ms",
+                "n_deflated", "n_chunks"]
+        return dict(zip(keys, out[30:40].tolist()))
 
     def loocv(self, i, n_i):
         pred, err = np.empty(n_i), np.empty(n_i)
