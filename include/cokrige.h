@@ -184,6 +184,44 @@ int ck_loocv(ck_handle* h, int i, double* pred_host, double* pred_err_host);
  * fail until the next ck_predict / ck_aux_begin.  ck_timings [24 ..] describe the call. */
 int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad, int64_t* info);
 
+/* ---- universal cokriging: an unknown trend estimated by GLS jointly with the kriging ------------------------------
+ * Regressors of process k at its data sites: F_k (n_k x p_k).  X (N x p, p = p_0 + p_1) is block diagonal: the rows of process
+ * k carry F_k in the columns of block k (process 0's columns first) and zeros elsewhere; z the data, Sigma = L L^T.
+ *   y = L^-1 z,  U = L^-1 X,  V_s = L^-1 c0_s,  A = U^T U = X^T Sigma^-1 X,  b = U^T y,  beta = A^-1 b,  Cov(beta) = A^-1,
+ *   x0_s = the regressors of process i at site s in the columns of block i (zeros elsewhere),  r_s = x0_s - U^T V_s,
+ *   pred_s = V_s . y + r_s^T beta,   pred_err_s = nan_to_num(sqrt(sigma_i^2 + nugget_i - |V_s|^2 + r_s^T A^-1 r_s)).
+ * This is the bordered (Lagrange) universal-kriging system [[Sigma, X], [X^T, 0]] (Cressie 1993, section 3.4.5); one constant
+ * column per process is ordinary cokriging (the weights on process i sum to 1, those on the other process to 0).
+ *
+ * ck_set_trend: F (n_k x p_k, row-major) in the caller's order of ck_set_data of process k; p_k = 0 clears the trend of
+ * process k, and so does ck_set_data of process k.  Refused: p_k > CK_TREND_PMAX, n_k != that process's data count, n_k < p_k,
+ * a non-finite entry.  The library keeps F on the host and lays it out along its site order whenever the sites are laid out
+ * (also again: ck_factor's retry in the caller's order, option "site_order", ck_set_metric); a new trend needs no new
+ * factorisation. */
+#define CK_TREND_PMAX 8
+int ck_set_trend(ck_handle* h, int k, const double* F_host, int64_t n_k, int p_k);
+/* Universal cokriging of process i at pcoords (m x 2) on the resident factor (needs ck_factor; single-process form).
+ * f0: m x p_i regressors of process i at the prediction sites (the caller's order; NULL when p_i = 0), finite.  pred / pred_err:
+ * m values in the caller's order; beta: p values, beta_cov: p x p (either may be NULL).  The right-hand sides are ck_predict's
+ * with the p rows X^T behind the data row (roundup(m + 1 + p, 256) rows of Npad doubles); one pass (k_reduce_univ) dots every
+ * solved row with [y; U] in a fixed order: repeated calls and any chunking of the sites give the same bits.  A is factored on
+ * the host with a relative pivot threshold of 1e-10: a rank-deficient design (a repeated column, a constant column twice for
+ * one process, fewer distinct sites than regressors) is refused with a message naming the process and the regressor.
+ * With no trend set (p = 0) the call is ck_predict (the same bits; beta / beta_cov untouched).  Afterwards the factor stays
+ * resident (ck_predict gives the same bits as without the call); ck_verify_model and ck_aux_finish fail until the next
+ * ck_predict / ck_aux_begin (the simple-kriging verdict does not apply).  ck_timings [40 ..] describe the call. */
+int ck_predict_universal(ck_handle* h, int i, const double* pcoords_host, int64_t m, const double* f0_host, double* pred_host,
+                         double* pred_err_host, double* beta_host, double* beta_cov_host);
+/* Restricted (REML) log-likelihood for the trend of ck_set_trend:
+ *     l_R = -1/2 [(N - p) log 2 pi + log|Sigma| + log|X^T Sigma^-1 X| + z^T P z],  P = Sigma^-1 - Sigma^-1 X A^-1 X^T Sigma^-1,
+ *     out4 = (l_R, log|Sigma|, log|X^T Sigma^-1 X|, z^T P z).
+ * Convention: no log|X^T X| term (it does not depend on the parameters).  want_grad: grad[k] = 1/2 sum_pq (G_R)_pq
+ * (dSigma/dtheta_k)_pq with G_R = alpha_R alpha_R^T + C C^T - Sigma^-1, alpha_R = Sigma^-1 (z - X beta), C = Sigma^-1 X R^-T
+ * (A = R R^T), in ck_loglik's parameter order.  Inputs, memory (p more right-hand-side rows), refusals, info and the handle's
+ * state afterwards as ck_loglik; a rank-deficient design is refused as in ck_predict_universal.  With p = 0 the call is
+ * ck_loglik, bit for bit (out4[2] = 0). */
+int ck_loglik_reml(ck_handle* h, int want_grad, double* out4, double* grad, int64_t* info);
+
 /* Simulation draw z = L eps in the caller's stacked order (process 0 sites, then process 1):
  * sim.BivariateRandomField._simulate (src/sim.py:52-54: cholesky(cmat, lower=True) @ noise).
  * n = number of observations; needs ck_factor. */
@@ -397,7 +435,9 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * ck_conditional_draws (n up to 40): [30] the point prediction (host wall clock of its ck_predict); [31] the assembly of C_pp;
  * [32] V^T V (k_schur_syrk_d); [33] deflation and jitter (k_draw_deflate, k_draw_zero); [34] the factor of S; [35] noise
  * generation (k_draw_noise), summed over the chunks; [36] the draw product and its epilogue (k_draw_trmm), summed over the
- * chunks; [37] host wall clock of the call; [38] number of deflated sites; [39] number of chunks. */
+ * chunks; [37] host wall clock of the call; [38] number of deflated sites; [39] number of chunks.
+ * ck_predict_universal (n up to 48): [40] K2 assembly of its right-hand sides; [41] the forward sweep; [42] the universal
+ * reduction (k_reduce_univ); [43] the host GLS step; [44] the host epilogue; [45] host wall clock of the call. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it

@@ -32,7 +32,9 @@
 #include "ck_model.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 40
+#define CK_N_TIMINGS 48
+// ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
+#define CK_TREND_TOL 1e-10
 
 static int fail(const std::string& msg) { return ck_fail(msg); }   // thread-local text: ck_host.cpp (ck_last_error)
 #define HIPCHK(expr)                                                                              \
@@ -237,9 +239,21 @@ struct ck_handle {
     unsigned coop_seq = 0;
     unsigned coop_spins = 2000000;    // option "coop_spins": polls a workgroup of k_panel_coop spends on one flag before it gives up (~2 s)
     int coop_inject_panel = -1;       // option "coop_inject_panel" (tests): the cooperative step of this panel loses one flag store
+    // universal cokriging (ck_set_trend): regressors of process k, n_k x trend_p[k] row-major in the caller's order, kept on the
+    // host; d_trendX: their p = sum_k trend_p[k] columns of X as p rows of Npad doubles in the internal order (zero at padding
+    // positions and in the other process's rows), uploaded when the layout is known
+    std::vector<double> trend_F[2];
+    int trend_p[2] = {0, 0};
+    bool trend_dirty = false;
+    double* d_trendX = nullptr;
+    int64_t trend_cap = 0;          // doubles
+    double* d_univ = nullptr;       // the universal reduction's output (rows x (q + 1) doubles)
+    int64_t univ_cap = 0;
+    int aux_trend = 0;   // trend rows behind the data row of the right-hand sides being assembled (rows m + 1 .. m + aux_trend)
+    int loo_dense = 1;   // rows in front of the unit rows in the leave-one-out / likelihood layout (ck_loglik_reml: 1 + p)
 };
 
-extern "C" int ck_version(void) { return 100; }
+extern "C" int ck_version(void) { return 101; }
 extern "C" int ck_device_count(int* n) {
     HIPCHK(hipGetDeviceCount(n));
     return 0;
@@ -345,6 +359,8 @@ extern "C" int ck_destroy(ck_handle* h) {
     if (h->side_lo) (void)hipStreamDestroy(h->side_lo);
     if (h->d_coop) (void)hipFree(h->d_coop);
     if (h->d_stamps) (void)hipFree(h->d_stamps);
+    if (h->d_trendX) (void)hipFree(h->d_trendX);
+    if (h->d_univ) (void)hipFree(h->d_univ);
     (void)hipStreamDestroy(h->own_stream);
     delete h;
     return 0;
@@ -431,6 +447,35 @@ extern "C" int ck_set_data(ck_handle* h, int k, const double* coords, const doub
     h->h_values[k].assign(values, values + n_k);
     h->n[k] = n_k;
     h->data_set[k] = true;
+    h->trend_F[k].clear();   // new data: the regressors of the old sites no longer apply
+    h->trend_p[k] = 0;
+    return 0;
+}
+
+extern "C" int ck_set_trend(ck_handle* h, int k, const double* F, int64_t n_k, int p_k) {
+    CHKH(h);
+    if (k < 0 || k > 1) return fail("ck_set_trend: process index must be 0 or 1");
+    if (p_k < 0 || p_k > CK_TREND_PMAX)
+        return fail("ck_set_trend: " + std::to_string(p_k) + " regressors for process " + std::to_string(k) + "; at most " +
+                    std::to_string(CK_TREND_PMAX) + " per process");
+    if (!h->data_set[k]) return fail("ck_set_trend: ck_set_data has not been called for process " + std::to_string(k));
+    if (n_k != h->n[k])
+        return fail("ck_set_trend: " + std::to_string(n_k) + " rows for process " + std::to_string(k) + ", which has " +
+                    std::to_string(h->n[k]) + " data sites");
+    if (p_k > 0 && n_k < p_k)
+        return fail("ck_set_trend: process " + std::to_string(k) + " has " + std::to_string(n_k) + " data sites for " +
+                    std::to_string(p_k) + " regressors");
+    if (p_k > 0 && !F) return fail("ck_set_trend: null regressors");
+    for (int64_t e = 0; e < n_k * p_k; ++e)
+        if (!std::isfinite(F[e]))
+            return fail("ck_set_trend: regressor " + std::to_string(e % p_k) + " of process " + std::to_string(k) +
+                        " is not finite at data site " + std::to_string(e / p_k));
+    if (p_k == 0)
+        h->trend_F[k].clear();
+    else
+        h->trend_F[k].assign(F, F + n_k * p_k);
+    h->trend_p[k] = p_k;
+    h->trend_dirty = true;
     return 0;
 }
 
@@ -551,6 +596,7 @@ static int ensure_layout(ck_handle* h, bool need_panels = true) {
             h->perm[k].resize((size_t)nk);
             for (int64_t j = 0; j < nk; ++j) h->perm[k][(size_t)j] = j;
         }
+        h->trend_dirty = true;   // a new site order (also a re-layout: ck_factor's retry, option "site_order"): X follows it
         for (int64_t j = 0; j < nk; ++j) {
             const int64_t e = h->perm[k][(size_t)j];
             hc[2 * (off + j)] = h->h_coords[k][2 * e];
@@ -1002,12 +1048,13 @@ static void apply_sigma_on(ck_handle* h, int K, const double* P, int Jlo, int Jh
 // process 1: 8 %).
 static int64_t aux_rows(const ck_handle* h, int K) {
     if (h->loo_g0 < 0) return h->mpad;
-    const int64_t live = (int64_t)(K + 1) * CK_NB - h->loo_g0 + 1;   // rows 0 .. live - 1
+    const int64_t live = (int64_t)(K + 1) * CK_NB - h->loo_g0 + h->loo_dense;   // rows 0 .. live - 1
     return std::min(h->mpad, roundup(std::max<int64_t>(live, 1), CK_AUX_ALIGN));
 }
 
-// rows of the right-hand-side block in front of its padding, for the thin last tile row (0: treat every row as live)
-static int64_t aux_live(const ck_handle* h) { return h->loo_g0 < 0 && h->tall_thin ? h->m + 1 : 0; }
+// rows of the right-hand-side block in front of its padding, for the thin last tile row (0: treat every row as live): the
+// prediction rows, the data row and the trend rows of a universal call
+static int64_t aux_live(const ck_handle* h) { return h->loo_g0 < 0 && h->tall_thin ? h->m + 1 + h->aux_trend : 0; }
 
 static void aux_inner_on(ck_handle* h, int K, const double* P, hipStream_t st) {
     double* X = h->aux + (int64_t)K * h->mpad * CK_NB;
@@ -1476,7 +1523,7 @@ static int tall_sweeps(ck_handle* h) {
     auto update = [&](hipStream_t st, int K0, int np, int J0, int nJ) {
         if (nJ <= 0) return;
         gemm_timed_begin(h, st);
-        ck_launch_tall_group(st, h->d_sigptr, h->aux, h->mpad, K0, np, J0, nJ, h->nend, h->tall_thin ? h->m + 1 : 0);
+        ck_launch_tall_group(st, h->d_sigptr, h->aux, h->mpad, K0, np, J0, nJ, h->nend, aux_live(h));
         gemm_timed_end(h, st);
     };
     // option "tall_b2_stream": B2(g) on the handle's own stream instead of behind B1(g) on T -- the two only need group g's panels,
@@ -1636,11 +1683,74 @@ extern "C" int ck_factor(ck_handle* h, int64_t* info) {
 }
 
 // pcoords == nullptr: storage only (ck_loocv fills the right-hand-side rows itself)
+// ---------------------------------------------------------------------------------------
+// universal cokriging: the regressors in the internal order (ck_set_trend)
+// ---------------------------------------------------------------------------------------
+static int trend_total(const ck_handle* h) {
+    int p = 0;
+    for (int k = 0; k < h->n_procs && k < 2; ++k) p += h->trend_p[k];
+    return p;
+}
+
+// d_trendX <- the columns of X as rows in the internal order; needs the layout
+static int ensure_trend(ck_handle* h) {
+    const int p = trend_total(h);
+    if (!h->trend_dirty || p == 0) return 0;
+    const int64_t Np = h->Npad;
+    if ((int64_t)p * Np > h->trend_cap) {
+        if (h->d_trendX) HIPCHK(hipFree(h->d_trendX));
+        h->d_trendX = nullptr;
+        h->trend_cap = 0;
+        HIPCHK(hipMalloc((void**)&h->d_trendX, (size_t)p * Np * 8));   // outside the arena, as d_chunkb: p <= 16 rows
+        h->trend_cap = (int64_t)p * Np;
+    }
+    std::vector<double> xt((size_t)p * Np, 0.0);
+    int col = 0;
+    for (int k = 0; k < h->n_procs; ++k) {
+        const int pk = h->trend_p[k];
+        const int64_t nk = h->n[k], off = k == 0 ? 0 : h->n0p;
+        for (int64_t j = 0; j < nk; ++j) {
+            const int64_t e = h->perm[k][(size_t)j];
+            for (int c = 0; c < pk; ++c) xt[(size_t)(col + c) * Np + off + j] = h->trend_F[k][(size_t)(e * pk + c)];
+        }
+        col += pk;
+    }
+    HIPCHK(hipMemcpyAsync(h->d_trendX, xt.data(), (size_t)p * Np * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->trend_dirty = false;
+    return 0;
+}
+
+// rows row0 .. row0 + p - 1 of every right-hand-side panel <- the rows of d_trendX
+static int put_trend_rows(ck_handle* h, int64_t row0) {
+    const int p = trend_total(h);
+    for (int j = 0; j < p; ++j)
+        HIPCHK(hipMemcpy2DAsync(h->aux + (row0 + j) * CK_NB, (size_t)h->mpad * CK_NB * 8, h->d_trendX + (int64_t)j * h->Npad,
+                                CK_NB * 8, CK_NB * 8, (size_t)h->nK, hipMemcpyDeviceToDevice, h->stream));
+    return 0;
+}
+
+static int ensure_univ(ck_handle* h, int64_t doubles) {
+    if (doubles <= h->univ_cap) return 0;
+    if (h->d_univ) HIPCHK(hipFree(h->d_univ));
+    h->d_univ = nullptr;
+    h->univ_cap = 0;
+    HIPCHK(hipMalloc((void**)&h->d_univ, (size_t)doubles * 8));
+    h->univ_cap = doubles;
+    return 0;
+}
+
+// the process and its regressor behind column c of X
+static std::string trend_column_name(const ck_handle* h, int c) {
+    const int k = c < h->trend_p[0] ? 0 : 1;
+    return "regressor " + std::to_string(k == 0 ? c : c - h->trend_p[0]) + " of process " + std::to_string(k);
+}
+
 static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m, bool may_sort) {
     if (ensure_layout(h)) return -1;
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
     if (m < 0) return fail("bad pcoords");
-    const int64_t mpad = roundup(m + 1, CK_AUX_ALIGN);
+    const int64_t mpad = roundup(m + 1 + h->aux_trend, CK_AUX_ALIGN);
     const int64_t need = mpad * h->Npad;
     if (need > h->aux_cap) {
         dev_free_one(h, h->aux);
@@ -1722,6 +1832,7 @@ static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m,
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
     h->t_ms[2] = ms;
+    if (h->aux_trend > 0 && put_trend_rows(h, m + 1)) return -1;   // universal cokriging: X^T behind the data row
     return 0;
 }
 
@@ -1736,6 +1847,7 @@ extern "C" int ck_aux_finish(ck_handle* h, double* pred, double* pred_err) {
     if (h->mpad <= 0) return fail("ck_aux_begin has not been called");
     if (h->aux_state == 3) return fail("ck_aux_finish: the last call was ck_predict_blocks; call ck_aux_begin first");
     if (h->aux_state == 4) return fail("ck_aux_finish: the last call was ck_loglik; call ck_aux_begin first");
+    if (h->aux_state == 5) return fail("ck_aux_finish: the last call was ck_predict_universal; call ck_aux_begin first");
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     const double c0 = h->blk[2 * h->i_pred].amp + h->blk[2 * h->i_pred].nugget;   // sigma_i^2 + nugget_i (model.py:194-196 at h = 0)
     ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, h->m, h->m, c0, h->d_pred, h->d_err);
@@ -1778,6 +1890,111 @@ extern "C" int ck_predict(ck_handle* h, int i, const double* pcoords, int64_t m,
     h->t_ms[3] = ms;
     gemm_timed_collect(h, 7);
     h->aux_state = 2;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// universal cokriging (ck_predict_universal): GLS trend jointly with the kriging
+// ---------------------------------------------------------------------------------------
+// The right-hand sides are ck_predict's [c0^T; z^T] with the p trend rows X^T behind the data row; the same sweep carries them
+// (a row's result does not depend on its neighbours), so V = L^-1 c0 and y = L^-1 z keep ck_predict's bits.  One pass of
+// k_reduce_univ dots every solved row with [y; U]: |V_s|^2, V_s . y, U^T V_s for the sites and, over the trend rows themselves,
+// A = U^T U and b = U^T y.  The p x p GLS step runs on the host (ck_host_gls), and so does the O(m p^2) epilogue
+// pred_s = V_s . y + r_s^T beta, pred_err_s^2 = c0 - |V_s|^2 + r_s^T A^-1 r_s, r_s = x0_s - U^T V_s.
+struct UnivCallGuard {
+    ck_handle* h;
+    explicit UnivCallGuard(ck_handle* hh) : h(hh) {}
+    ~UnivCallGuard() {
+        h->aux_trend = 0;
+        h->aux_state = 5;
+    }
+};
+
+extern "C" int ck_predict_universal(ck_handle* h, int i, const double* pcoords, int64_t m, const double* f0, double* pred,
+                                    double* pred_err, double* beta, double* beta_cov) {
+    CHKH(h);
+    if (h->world != 1)
+        return fail("ck_predict_universal is the single-process form: this handle is partitioned (world = " +
+                    std::to_string(h->world) + ")");
+    if (!h->factored) return fail("ck_predict_universal: ck_factor has not been called");
+    if (i < 0 || i >= h->n_procs) return fail("process index out of range");
+    if (m < 0 || (m > 0 && (!pcoords || !pred || !pred_err))) return fail("ck_predict_universal: bad prediction arrays");
+    const int p = trend_total(h);
+    if (p == 0) return ck_predict(h, i, pcoords, m, pred, pred_err);   // no trend: simple cokriging, ck_predict's bits
+    const int pi = h->trend_p[i], offi = i == 0 ? 0 : h->trend_p[0];
+    if (m > 0 && pi > 0 && !f0) return fail("ck_predict_universal: null regressors of the prediction sites");
+    for (int64_t e = 0; e < m * pi; ++e)
+        if (!std::isfinite(f0[e]))
+            return fail("ck_predict_universal: regressor " + std::to_string(e % pi) + " is not finite at prediction site " +
+                        std::to_string(e / pi));
+    const auto t_begin = std::chrono::steady_clock::now();
+    for (int k = 40; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    if (ensure_trend(h)) return -1;
+    UnivCallGuard guard(h);
+    h->aux_trend = p;
+    static const double no_site[2] = {0.0, 0.0};
+    if (aux_begin_impl(h, i, m > 0 ? pcoords : no_site, m, true)) return -1;
+    h->t_ms[40] = h->t_ms[2];
+    h->gemm_ev_used = 0;
+    HIPCHK(hipEventRecord(h->ev2, h->stream));
+    if (solve_sweep(h)) return -1;
+    HIPCHK(hipEventRecord(h->ev3, h->stream));
+    const int q = 1 + p;
+    const int64_t nrows = m + 1 + p;
+    if (ensure_univ(h, nrows * (q + 1))) return -1;
+    ck_launch_reduce_univ(h->stream, h->aux, h->mpad, h->nK, nrows, m, q, h->d_univ);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    std::vector<double> W((size_t)(nrows * (q + 1)));
+    HIPCHK(hipMemcpyAsync(W.data(), h->d_univ, W.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, h->ev2, h->ev3));
+        h->t_ms[41] = ms;
+        HIPCHK(hipEventElapsedTime(&ms, h->ev3, h->ev1));
+        h->t_ms[42] = ms;
+    }
+    gemm_timed_collect(h, 7);
+    // ---- the GLS step
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<double> A((size_t)p * p), b((size_t)p), bh((size_t)p), Ai((size_t)p * p);
+    for (int j = 0; j < p; ++j) {
+        const double* wr = &W[(size_t)((m + 1 + j) * (q + 1))];
+        b[(size_t)j] = wr[1];
+        for (int l = 0; l < p; ++l) A[(size_t)(j * p + l)] = wr[2 + l];
+    }
+    const int bad = ck_host_gls(p, A.data(), b.data(), CK_TREND_TOL, nullptr, bh.data(), Ai.data(), nullptr, nullptr);
+    if (bad)
+        return fail("ck_predict_universal: the trend design is rank deficient: " + trend_column_name(h, bad - 1) +
+                    " is, to rounding, a combination of the regressors in front of it (X^T Sigma^-1 X is singular)");
+    auto t1 = std::chrono::steady_clock::now();
+    h->t_ms[43] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    // ---- the epilogue, in the caller's order
+    const double c0 = h->blk[2 * i].amp + h->blk[2 * i].nugget;   // sigma_i^2 + nugget_i, as ck_aux_finish
+    ck_host_parallel(m, [&](int, int64_t a, int64_t e) {
+        double r[CK_UNIV_QMAX];
+        for (int64_t s = a; s < e; ++s) {
+            const int64_t c = h->p_sorted ? h->pperm[(size_t)s] : s;
+            const double* wr = &W[(size_t)(s * (q + 1))];
+            for (int j = 0; j < p; ++j) r[j] = -wr[2 + j];
+            for (int j = 0; j < pi; ++j) r[offi + j] += f0[c * pi + j];
+            double pr = wr[1], var = c0 - wr[0];
+            for (int j = 0; j < p; ++j) {
+                pr += r[j] * bh[(size_t)j];
+                double t = 0.0;
+                for (int l = 0; l < p; ++l) t += Ai[(size_t)(j * p + l)] * r[l];
+                var += r[j] * t;
+            }
+            const double er = sqrt(var);   // negative variance -> NaN -> 0.0 (np.nan_to_num, as ck_aux_finish)
+            pred[c] = pr;
+            pred_err[c] = (er == er) ? er : 0.0;
+        }
+    });
+    if (beta) memcpy(beta, bh.data(), (size_t)p * 8);
+    if (beta_cov) memcpy(beta_cov, Ai.data(), (size_t)p * p * 8);
+    h->t_ms[44] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    h->t_ms[45] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return 0;
 }
 
@@ -1986,6 +2203,9 @@ extern "C" int ck_verify_model(ck_handle* h, int64_t* info) {
     if (h->aux_state == 4)
         return fail("ck_verify_model: the last call was ck_loglik, whose right-hand sides are the data sites' unit rows; call "
                     "ck_predict with the sites to check first");
+    if (h->aux_state == 5)
+        return fail("ck_verify_model: the last call was ck_predict_universal, for which the simple-kriging verdict does not apply; "
+                    "call ck_predict with the sites to check first");
     if (h->aux_state != 2) return fail("ck_verify_model needs the solved right-hand sides of a preceding ck_predict");
     const int64_t m = h->m;
     *info = 0;
@@ -2522,33 +2742,44 @@ extern "C" int ck_loocv(ck_handle* h, int i, double* pred, double* pred_err) {
 // G = alpha alpha^T - W^T W on the lower tiles with the structurally zero panels skipped (ck_la.hip: k_ginv_syrk_d, N^3 / 3
 // flop), and one pass of k_loglik_grad over G.  The handle's own state: the factor stays resident; the right-hand sides are
 // not prediction rows (aux_state 4: ck_verify_model / ck_aux_finish refuse until the next ck_predict / ck_aux_begin).
+//
+// REML (ck_loglik_reml, p = the trend columns of ck_set_trend): the right-hand sides are [z^T; X^T; unit rows], the unit rows
+// behind the p trend rows (loo_dense = 1 + p).  k_reduce_univ dots every row with [y; U]: |y|^2, b = U^T y and A = U^T U over
+// the first 1 + p rows, alpha_q = W_q . y and B_q = U^T W_q (= (Sigma^-1 X)_q) over the unit rows.  The host forms beta, log|A|,
+// b^T A^-1 b, alpha_R = alpha - B beta and C = B R^-T (A = R R^T); k_ginv_syrk_d starts from the rank-(1 + p) term
+// alpha_R alpha_R^T + C C^T.  p = 0 is ck_loglik's path, bit for bit.
 struct LikCallGuard {
     ck_handle* h;
     explicit LikCallGuard(ck_handle* hh) : h(hh) { h->aux_state = 4; }
     ~LikCallGuard() {
         h->aux_state = 4;
         h->loo_g0 = -1;
+        h->loo_dense = 1;
     }
 };
 
-extern "C" int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad, int64_t* info) {
-    CHKH(h);
-    if (!out3 || !info || (want_grad && !grad)) return fail("ck_loglik: null argument");
+static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, double* grad, int64_t* info) {
+    const char* name = reml ? "ck_loglik_reml" : "ck_loglik";
+    if (!out || !info || (want_grad && !grad)) return fail(std::string(name) + ": null argument");
     if (h->world != 1)
-        return fail("ck_loglik is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) +
+        return fail(std::string(name) + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) +
                     "); the multi-GPU likelihood is not available");
-    if (!h->assembled) return fail("ck_loglik: ck_assemble_joint has not been called");
+    if (!h->assembled) return fail(std::string(name) + ": ck_assemble_joint has not been called");
     const auto t_begin = std::chrono::steady_clock::now();
     const int64_t Np = h->Npad;
     const int npar = h->n_procs == 1 ? 4 : CK_LIK_NPAR;
+    const int p = reml ? trend_total(h) : 0;   // trend columns (0: the zero-mean likelihood)
+    const int q = 1 + p;
     *info = 0;
-    out3[0] = out3[1] = out3[2] = NAN;
+    const int nout = reml ? 4 : 3;
+    for (int k = 0; k < nout; ++k) out[k] = NAN;
+    double* out3 = out;
     if (want_grad)
         for (int k = 0; k < npar; ++k) grad[k] = NAN;
     // device memory of the gradient: N + 1 unit / data rows of Npad doubles (the right-hand sides, mpad = Npad + 256 rows) and
     // the lower triangle of G (packed block columns with their tails, as the Schur complement of ck_verify_model)
     const int64_t mrows = want_grad ? Np : 0;
-    const int64_t mpad_need = roundup(mrows + 1, CK_AUX_ALIGN);
+    const int64_t mpad_need = roundup(mrows + 1 + p, CK_AUX_ALIGN);
     if (want_grad) {
         int64_t g_bytes = 0;
         for (int J = 0; J < h->nK; ++J) g_bytes += ((Np - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;
@@ -2562,12 +2793,12 @@ extern "C" int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad
             for (int J = 0; J < (int)h->sch_sig.size(); ++J)
                 avail += ((h->sch_M - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;   // schur_ensure releases these first
         if (h->arena && aux_bytes > h->aux_cap * 8 && aux_bytes > h->arena_size - h->arena_used)
-            return fail("ck_loglik: the gradient needs " + std::to_string(aux_bytes) + " bytes of the arena for its " +
-                        std::to_string(mrows + 1) + " right-hand-side rows of " + std::to_string(Np) + " doubles; " +
+            return fail(std::string(name) + ": the gradient needs " + std::to_string(aux_bytes) + " bytes of the arena for its " +
+                        std::to_string(mrows + 1 + p) + " right-hand-side rows of " + std::to_string(Np) + " doubles; " +
                         std::to_string(h->arena_size - h->arena_used) + " bytes are left");
         if (need > avail)
-            return fail("ck_loglik: the gradient needs " + std::to_string(aux_bytes + g_bytes) + " bytes of device memory (" +
-                        std::to_string(aux_bytes) + " for N + 1 rows of " + std::to_string(Np) + " doubles, " +
+            return fail(std::string(name) + ": the gradient needs " + std::to_string(aux_bytes + g_bytes) + " bytes of device memory (" +
+                        std::to_string(aux_bytes) + " for " + std::to_string(mrows + 1 + p) + " rows of " + std::to_string(Np) + " doubles, " +
                         std::to_string(g_bytes) + " for the lower triangle of G); " + std::to_string(avail) +
                         " bytes are available");
     }
@@ -2594,18 +2825,29 @@ extern "C" int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad
     }
     const CkLayout L = layout_of(h);
     DevTemps tmp;
-    // ---- right-hand sides: row 0 = z, rows 1 .. mrows = the unit vectors of every internal position; the sweep
-    if (aux_begin_impl(h, 0, nullptr, mrows, false)) return -1;
+    if (p > 0 && ensure_trend(h)) return -1;
+    // ---- right-hand sides: row 0 = z, rows 1 .. p = X^T (REML), rows 1 + p .. p + mrows = the unit vectors of every internal
+    // position; the sweep
+    if (aux_begin_impl(h, 0, nullptr, mrows + p, false)) return -1;
     h->aux_state = 4;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     HIPCHK(hipMemsetAsync(h->aux, 0, (size_t)h->mpad * Np * 8, h->stream));
     h->loo_g0 = 0;
-    ck_launch_loo_rows(h->stream, h->aux, h->mpad, mrows, 0, h->z, Np);
+    h->loo_dense = q;
+    ck_launch_loo_rows(h->stream, h->aux, h->mpad, mrows, 0, h->z, Np, q);
+    if (p > 0 && put_trend_rows(h, 1)) return -1;
     const int rc = solve_sweep(h);
     h->loo_g0 = -1;
+    h->loo_dense = 1;
     if (rc) return -1;
-    // alpha_p = W_p . y (d_pred[1 + p]) and |y|^2 (d_pred[0]); log L_qq per panel
-    ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, mrows + 1, 0, -1.0, h->d_pred, h->d_err);
+    // alpha_p = W_p . y (d_pred[1 + p]) and |y|^2 (d_pred[0]); with a trend every row's dots with [y; U]; log L_qq per panel
+    const int64_t nrows = mrows + 1 + p;
+    if (p == 0) {
+        ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, mrows + 1, 0, -1.0, h->d_pred, h->d_err);
+    } else {
+        if (ensure_univ(h, nrows * (q + 1))) return -1;
+        ck_launch_reduce_univ(h->stream, h->aux, h->mpad, h->nK, nrows, 0, q, h->d_univ);
+    }
     double* d_ldp = nullptr;
     HIPCHK(tmp.get(&d_ldp, (size_t)h->nK * 8));
     ck_launch_lik_logdet(h->stream, h->d_sigptr, h->nK, L, d_ldp);
@@ -2614,20 +2856,67 @@ extern "C" int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad
     std::vector<double> ldp((size_t)h->nK);
     double quad = 0.0;
     HIPCHK(hipMemcpyAsync(ldp.data(), d_ldp, (size_t)h->nK * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(&quad, h->d_pred, 8, hipMemcpyDeviceToHost, h->stream));
+    std::vector<double> W;
+    if (p == 0) {
+        HIPCHK(hipMemcpyAsync(&quad, h->d_pred, 8, hipMemcpyDeviceToHost, h->stream));
+    } else {
+        W.resize((size_t)(nrows * (q + 1)));
+        HIPCHK(hipMemcpyAsync(W.data(), h->d_univ, W.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    }
     HIPCHK(hipStreamSynchronize(h->stream));
     h->t_ms[26] = elapsed(h->ev0, h->ev1);
     double half_logdet = 0.0;
     for (int K = 0; K < h->nK; ++K) half_logdet += ldp[(size_t)K];
     const double logdet = 2.0 * half_logdet;
+    double logdetA = 0.0;
+    std::vector<double> R((size_t)p * p), bh((size_t)p);
+    if (p > 0) {   // the GLS step: A = U^T U, b = U^T y from rows 1 .. p
+        std::vector<double> A((size_t)p * p), b((size_t)p);
+        for (int j = 0; j < p; ++j) {
+            const double* wr = &W[(size_t)((1 + j) * (q + 1))];
+            b[(size_t)j] = wr[1];
+            for (int l = 0; l < p; ++l) A[(size_t)(j * p + l)] = wr[2 + l];
+        }
+        double bAb = 0.0;
+        const int bad = ck_host_gls(p, A.data(), b.data(), CK_TREND_TOL, R.data(), bh.data(), nullptr, &logdetA, &bAb);
+        if (bad)
+            return fail(std::string(name) + ": the trend design is rank deficient: " + trend_column_name(h, bad - 1) +
+                        " is, to rounding, a combination of the regressors in front of it (X^T Sigma^-1 X is singular)");
+        quad = W[1] - bAb;   // z^T P z = |y|^2 - b^T A^-1 b
+    }
     out3[1] = logdet;
-    out3[2] = quad;
-    out3[0] = -0.5 * ((double)h->N * log(2.0 * M_PI) + logdet + quad);
+    if (reml) {
+        out[2] = logdetA;
+        out[3] = quad;
+        out[0] = -0.5 * ((double)(h->N - p) * log(2.0 * M_PI) + logdet + logdetA + quad);
+    } else {
+        out3[2] = quad;
+        out3[0] = -0.5 * ((double)h->N * log(2.0 * M_PI) + logdet + quad);
+    }
     if (want_grad) {
-        // ---- G = alpha alpha^T - Sigma^-1, lower tiles of the first nend rows
+        // ---- G = alpha alpha^T - Sigma^-1 (REML: alpha_R alpha_R^T + C C^T - Sigma^-1), lower tiles of the first nend rows
+        const double* avec = h->d_pred + 1;
+        if (p > 0) {
+            std::vector<double> av((size_t)q * Np, 0.0);
+            for (int64_t r = 0; r < Np; ++r) {
+                const double* wr = &W[(size_t)((q + r) * (q + 1))];   // unit row of internal position r
+                double a = wr[1];
+                for (int j = 0; j < p; ++j) a -= wr[2 + j] * bh[(size_t)j];
+                av[(size_t)r] = a;
+                for (int j = 0; j < p; ++j) {   // C_r = R^-1 B_r (forward substitution)
+                    double c = wr[2 + j];
+                    for (int l = 0; l < j; ++l) c -= R[(size_t)(j * p + l)] * av[(size_t)(1 + l) * Np + r];
+                    av[(size_t)(1 + j) * Np + r] = c / R[(size_t)(j * p + j)];
+                }
+            }
+            double* d_av = nullptr;
+            HIPCHK(tmp.get(&d_av, av.size() * 8));
+            HIPCHK(hipMemcpyAsync(d_av, av.data(), av.size() * 8, hipMemcpyHostToDevice, h->stream));
+            avec = d_av;
+        }
         if (schur_ensure(h, Np)) return -1;
         HIPCHK(hipEventRecord(h->ev0, h->stream));
-        ck_launch_ginv_syrk(h->stream, h->d_sch_ptr, h->aux, h->mpad, h->d_pred + 1, h->nK, h->nend);
+        ck_launch_ginv_syrk(h->stream, h->d_sch_ptr, h->aux, h->mpad, avec, h->nK, h->nend, q, Np, q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev1, h->stream));
         // ---- the contraction: the model's blocks and their nu +- dnu, nu +- 2 dnu neighbours
@@ -2663,6 +2952,16 @@ extern "C" int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad
     }
     h->t_ms[29] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return 0;
+}
+
+extern "C" int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad, int64_t* info) {
+    CHKH(h);
+    return loglik_impl(h, want_grad, false, out3, grad, info);
+}
+
+extern "C" int ck_loglik_reml(ck_handle* h, int want_grad, double* out4, double* grad, int64_t* info) {
+    CHKH(h);
+    return loglik_impl(h, want_grad, true, out4, grad, info);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 #include "ck_tilemap.h"
 
 #include <math.h>
+#include <cmath>
 #include <string.h>
 
 #include <atomic>
@@ -402,4 +403,68 @@ void ck_host_vario_fix(int metric, const double* ci, const double* cj, const dou
             sm[b] += dsum[(size_t)t * NB1 + b];
             cnt[b] += dcnt[(size_t)t * NB1 + b];
         }
+}
+
+// ---------------------------------------------------------------------------------------
+// universal cokriging: the p x p GLS step (p <= 16; plain loops in a fixed order)
+// ---------------------------------------------------------------------------------------
+int ck_host_gls(int p, const double* A, const double* b, double tol, double* R_out, double* beta, double* Ainv,
+                double* logdet, double* bAb) {
+    if (p <= 0) {
+        if (logdet) *logdet = 0.0;
+        if (bAb) *bAb = 0.0;
+        return 0;
+    }
+    std::vector<double> R((size_t)p * p, 0.0), Ri((size_t)p * p, 0.0), w((size_t)p, 0.0);
+    double ld = 0.0;
+    for (int j = 0; j < p; ++j) {
+        const double ajj = A[(size_t)j * p + j];
+        double d = ajj;
+        for (int k = 0; k < j; ++k) d -= R[(size_t)j * p + k] * R[(size_t)j * p + k];
+        if (!(ajj > 0.0) || !(d > tol * ajj) || !std::isfinite(d)) return j + 1;
+        const double rjj = sqrt(d);
+        R[(size_t)j * p + j] = rjj;
+        ld += log(rjj);
+        for (int i = j + 1; i < p; ++i) {
+            double s = A[(size_t)i * p + j];
+            for (int k = 0; k < j; ++k) s -= R[(size_t)i * p + k] * R[(size_t)j * p + k];
+            R[(size_t)i * p + j] = s / rjj;
+        }
+    }
+    // Ri = R^-1 (lower), w = R^-1 b
+    for (int j = 0; j < p; ++j) {
+        Ri[(size_t)j * p + j] = 1.0 / R[(size_t)j * p + j];
+        for (int i = j + 1; i < p; ++i) {
+            double s = 0.0;
+            for (int k = j; k < i; ++k) s += R[(size_t)i * p + k] * Ri[(size_t)k * p + j];
+            Ri[(size_t)i * p + j] = -s / R[(size_t)i * p + i];
+        }
+    }
+    double q = 0.0;
+    for (int i = 0; i < p; ++i) {
+        double s = 0.0;
+        for (int k = 0; k <= i; ++k) s += Ri[(size_t)i * p + k] * b[k];
+        w[(size_t)i] = s;
+        q += s * s;
+    }
+    if (R_out) memcpy(R_out, R.data(), (size_t)p * p * 8);
+    if (Ainv || beta) {
+        std::vector<double> Ai((size_t)p * p);
+        for (int i = 0; i < p; ++i)   // A^-1 = R^-T R^-1: (A^-1)_il = sum_{k >= max(i, l)} Ri_ki Ri_kl
+            for (int l = 0; l <= i; ++l) {
+                double s = 0.0;
+                for (int k = i; k < p; ++k) s += Ri[(size_t)k * p + i] * Ri[(size_t)k * p + l];
+                Ai[(size_t)i * p + l] = Ai[(size_t)l * p + i] = s;
+            }
+        if (Ainv) memcpy(Ainv, Ai.data(), (size_t)p * p * 8);
+        if (beta)   // beta = R^-T w
+            for (int i = 0; i < p; ++i) {
+                double s = 0.0;
+                for (int k = i; k < p; ++k) s += Ri[(size_t)k * p + i] * w[(size_t)k];
+                beta[i] = s;
+            }
+    }
+    if (logdet) *logdet = 2.0 * ld;
+    if (bAb) *bAb = q;
+    return 0;
 }

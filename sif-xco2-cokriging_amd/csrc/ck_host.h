@@ -78,3 +78,11 @@ CK_HIDDEN void ck_host_vario_decide_extent(int metric, const double* ci, const d
 CK_HIDDEN void ck_host_vario_fix(int metric, const double* ci, const double* cj, const double* vi, const double* vj,
                                  const CkVarioPair* fix, int64_t nf, const CkVarioLevels& lv, int covariogram,
                                  double* sm, long long* cnt);
+
+// ---- universal cokriging: the p x p GLS step (ck_api.hip: ck_predict_universal / ck_loglik_reml) -------------------
+// A = X^T Sigma^-1 X (p x p row-major; the lower triangle is read), b = X^T Sigma^-1 z.  Cholesky A = R R^T with a relative
+// pivot threshold: column j is refused when its pivot is not above tol A_jj (a column that is, to rounding, a combination of
+// the columns in front of it).  Returns 0, or 1 + the first refused column.  Outputs (any may be null): R (p x p, lower,
+// zeros above), beta = A^-1 b, Ainv = A^-1 (p x p, symmetric), logdet = log|A|, bAb = b^T A^-1 b.
+CK_HIDDEN int ck_host_gls(int p, const double* A, const double* b, double tol, double* R, double* beta, double* Ainv,
+                          double* logdet, double* bAb);

@@ -127,9 +127,11 @@ void ck_launch_schur_syrk(hipStream_t s, double* const* schur_dev, const double*
                           int64_t Mpad);
 // G = alpha alpha^T - W^T W over the unit right-hand-side rows of all data sites (ck_loglik; row 1 + p of aux = W_p, alpha[p]
 // = W_p . y): the lower tiles of the first nvalid rows of the Npad = nK NB order, packed block columns G_dev[J]; a tile skips
-// the panels in front of its first row, where its W rows are zero.  mpad >= Npad + 1 (the rows read are 1 .. Npad).
-void ck_launch_ginv_syrk(hipStream_t s, double* const* G_dev, const double* aux, int64_t mpad, const double* alpha, int nK,
-                         int64_t nvalid);
+// the panels in front of its first row, where its W rows are zero.  mpad >= Npad + dense (the rows read are dense ..
+// dense + Npad - 1).  Rank-q start (ck_loglik_reml): the accumulators start from sum_j a_j[p] a_j[q] over the q vectors
+// a_j = avec + j ald (q = 1, avec = alpha: ck_loglik's alpha alpha^T, the same bits); dense: the rows in front of the unit rows.
+void ck_launch_ginv_syrk(hipStream_t s, double* const* G_dev, const double* aux, int64_t mpad, const double* avec, int nK,
+                         int64_t nvalid, int q = 1, int64_t ald = 0, int dense = 1);
 // Conditional simulation (ck_conditional_draws): X (nd x m, ld m, the caller's site order) = pred + eps L_S^T on the lower
 // tiles of the factor L_S in the Schur buffers (L_dev[J]: packed block columns, upper triangles of the diagonal blocks zero).
 // E: -eps in block columns of ldp >= roundup(nd, 128) rows (ck_launch_draw_noise); pred, cmap: Mp entries in the internal order
@@ -156,8 +158,16 @@ void ck_launch_trsm64(hipStream_t s, double* A, int64_t ld, int64_t nrows, const
 void ck_launch_reduce_pred(hipStream_t s, const double* aux, int64_t mpad, int n_panels, int64_t m, int64_t zrow,
                            double c0, double* pred, double* err);
 void ck_launch_tri_matvec(hipStream_t s, double* const* sigptr_dev, int64_t npad, const double* v, double* out);
+// dense: the row of the unit vector of datum 0 (1: row 0 = z only; ck_loglik_reml: 1 + p, the trend rows in between)
 void ck_launch_loo_rows(hipStream_t s, double* aux, int64_t mpad, int64_t m, int64_t g0, const double* z,
-                        int64_t npad);
+                        int64_t npad, int64_t dense = 1);
+// Universal cokriging (ck_predict_universal / ck_loglik_reml): every row r < nrows of the right-hand sides dotted with the q
+// basis rows brow0 .. brow0 + q - 1 ([y; U] = the data row and the trend rows) in one pass over the panels:
+// out[r (q + 1)] = |X_r|^2, out[r (q + 1) + 1 + j] = X_r . X_{brow0 + j}.  q <= CK_UNIV_QMAX, brow0 + q <= mpad, nrows <= mpad.
+// Every row sums in a fixed order that does not depend on nrows or on its neighbours.
+#define CK_UNIV_QMAX 17
+void ck_launch_reduce_univ(hipStream_t s, const double* aux, int64_t mpad, int n_panels, int64_t nrows, int64_t brow0, int q,
+                           double* out);
 void ck_launch_mfma_probe(hipStream_t s, int32_t* out);
 int ck_launch_mfma_peak(hipStream_t s, int blocks, int waves_per_simd, int iters, double* sink);
 

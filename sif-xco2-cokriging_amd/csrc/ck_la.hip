@@ -401,14 +401,15 @@ struct CkSrcAux {
 // NI: 16-row blocks this WAVE computes (4: all of its 64 rows).  A right-hand-side tile row that holds only a few rows in front of
 // the padding (m + 1 = 8 834 rows: 69 tile rows and two rows) runs with NI = 1 in the waves of the upper half and NI = 0 -- staging
 // and barriers only -- in the others (k_tall_group_d): an eighth of a tile's MFMAs; a row's result does not depend on its neighbours.
-// RANK1 (k_ginv_syrk_d): the accumulators start from ar[row] ac[col] instead of the C tile (which is then written, not read)
+// RANK1 (k_ginv_syrk_d): the accumulators start from ar[row] ac[col] instead of the C tile (which is then written, not read);
+// rq > 1 (ck_loglik_reml): from sum_j ar[j rld + row] ac[j rld + col] over rq vector pairs, the first product as for rq = 1
 // SCATTER (k_draw_trmm): the tile's column c is stored to column cmap[c] of C (none where cmap[c] < 0), its rows only in front
 // of row_lim; C is then the output's base (c0 plays no part in the store)
 template <int WAVES, class SRC, int NI = 4, bool RANK1 = false, bool SCATTER = false>
 __device__ __forceinline__ void gemm_tile_d(double* __restrict__ C, long ldc, const SRC& src, int np, long r0, long c0,
                                             char* lds, const double* __restrict__ ar = nullptr,
                                             const double* __restrict__ ac = nullptr, const int* __restrict__ cmap = nullptr,
-                                            long row_lim = 0) {
+                                            long row_lim = 0, int rq = 1, long rld = 0) {
     static_assert(WAVES == 8, "8 waves of 64 x 32");
     constexpr int NA = NI > 0 ? NI : 1;
     constexpr int BOFF = 128 * 128;
@@ -473,7 +474,16 @@ __device__ __forceinline__ void gemm_tile_d(double* __restrict__ C, long ldc, co
             for (int r = 0; r < 4; ++r) {
                 const double a = ar[wm * 64 + g + i * 16 + 4 * r];
 #pragma unroll
-                for (int j = 0; j < WJ; ++j) acc[i][j][r] = -(a * ac[wn * (WJ * 16) + j * 16 + li]);
+                for (int j = 0; j < WJ; ++j) {
+                    if (rq == 1) {   // (a compile-time 1 everywhere but k_ginv_syrk_d<true>: the rank-1 code as it was)
+                        acc[i][j][r] = -(a * ac[wn * (WJ * 16) + j * 16 + li]);
+                        continue;
+                    }
+                    double s = a * ac[wn * (WJ * 16) + j * 16 + li];
+                    for (int v = 1; v < rq; ++v)
+                        s += ar[v * rld + wm * 64 + g + i * 16 + 4 * r] * ac[v * rld + wn * (WJ * 16) + j * 16 + li];
+                    acc[i][j][r] = -s;
+                }
             }
     } else {
 #pragma unroll
@@ -771,8 +781,12 @@ struct CkSrcGinv {
     }
 };
 
+// RQ = false (ck_loglik, and ck_loglik_reml without a trend): the rank-1 start with rq a compile-time 1 -- the code of the ML path
+// is the rank-1 kernel's; RQ = true: the rank-q start of ck_loglik_reml (q = 1 + p at run time)
+template <bool RQ>
 __global__ __launch_bounds__(512, 4) void k_ginv_syrk_d(double* const* __restrict__ G, const double* __restrict__ aux, long mpad,
-                                                         const double* __restrict__ alpha, int nK, const CkTileMap map) {
+                                                         const double* __restrict__ alpha, int nK, const CkTileMap map, int q,
+                                                         long ald, int dense) {
     __shared__ __attribute__((aligned(16))) char lds[2 * 256 * 128];
     int u, tm, tn;
     ck_tilemap_get(map, xcd_remap(blockIdx.x, (int)map.total), u, tm, tn);
@@ -780,16 +794,21 @@ __global__ __launch_bounds__(512, 4) void k_ginv_syrk_d(double* const* __restric
     const long r0 = (long)tm * 128, c0 = (long)tn * 128;
     const long p0 = (long)J * CK_NB + r0, q0 = (long)J * CK_NB + c0;
     const int K0 = (int)(p0 / CK_NB);
-    const CkSrcGinv src{aux, mpad, K0, 1 + p0, 1 + q0};
-    gemm_tile_d<8, CkSrcGinv, 4, true>(G[J], CK_NB, src, nK - K0, r0, c0, lds, alpha + p0, alpha + q0);
+    const long dn = RQ ? dense : 1;   // (ck_loglik: one dense row, the data row)
+    const CkSrcGinv src{aux, mpad, K0, dn + p0, dn + q0};
+    gemm_tile_d<8, CkSrcGinv, 4, true>(G[J], CK_NB, src, nK - K0, r0, c0, lds, alpha + p0, alpha + q0, nullptr, 0, RQ ? q : 1,
+                                       ald);
 }
 
-void ck_launch_ginv_syrk(hipStream_t s, double* const* G_dev, const double* aux, int64_t mpad, const double* alpha, int nK,
-                         int64_t nvalid) {
+void ck_launch_ginv_syrk(hipStream_t s, double* const* G_dev, const double* aux, int64_t mpad, const double* avec, int nK,
+                         int64_t nvalid, int q, int64_t ald, int dense) {
     if (nK <= 0) return;
     const CkTileMap map = ck_tilemap_make(nvalid, 0, 1, nK);
     if (map.total <= 0) return;
-    k_ginv_syrk_d<<<dim3((unsigned)map.total), dim3(512), 0, s>>>(G_dev, aux, mpad, alpha, nK, map);
+    if (q == 1)
+        k_ginv_syrk_d<false><<<dim3((unsigned)map.total), dim3(512), 0, s>>>(G_dev, aux, mpad, avec, nK, map, 1, (long)ald, dense);
+    else
+        k_ginv_syrk_d<true><<<dim3((unsigned)map.total), dim3(512), 0, s>>>(G_dev, aux, mpad, avec, nK, map, q, (long)ald, dense);
 }
 
 // Conditional simulation (ck_conditional_draws): X = pred + eps L_S^T for a chunk of draws, L_S the factor of the
@@ -1942,11 +1961,11 @@ __global__ __launch_bounds__(256) void k_reduce_pred(const double* __restrict__ 
 // the withheld process (internal index g0 + p).  Row 1 + p is zero in every column before g0 + p, so the sweep
 // only needs the first rows up to the current panel (ck_api.hip: aux_rows).
 __global__ void k_loo_rows(double* __restrict__ aux, long mpad, long m, long g0, const double* __restrict__ z,
-                           long npad) {
+                           long npad, long dense) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) {   // row 1 + i: unit vector of datum i (site g0 + i)
+    if (i < m) {   // row dense + i: unit vector of datum i (site g0 + i)
         const long g = g0 + i;
-        aux[(g / CK_NB) * mpad * CK_NB + (i + 1) * CK_NB + (g % CK_NB)] = 1.0;
+        aux[(g / CK_NB) * mpad * CK_NB + (i + dense) * CK_NB + (g % CK_NB)] = 1.0;
     }
     if (i < npad) aux[(i / CK_NB) * mpad * CK_NB + (i % CK_NB)] = z[i];   // row 0: the data values
 }
@@ -1975,15 +1994,102 @@ void ck_launch_tri_matvec(hipStream_t s, double* const* sigptr_dev, int64_t npad
 }
 
 void ck_launch_loo_rows(hipStream_t s, double* aux, int64_t mpad, int64_t m, int64_t g0, const double* z,
-                        int64_t npad) {
+                        int64_t npad, int64_t dense) {
     const int64_t n = m > npad ? m : npad;
-    k_loo_rows<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(aux, mpad, m, g0, z, npad);
+    k_loo_rows<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(aux, mpad, m, g0, z, npad, (long)dense);
 }
 
 void ck_launch_reduce_pred(hipStream_t s, const double* aux, int64_t mpad, int n_panels, int64_t m, int64_t zrow,
                            double c0, double* pred, double* err) {
     if (m <= 0) return;
     k_reduce_pred<<<dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s>>>(aux, mpad, n_panels, m, zrow, c0, pred, err);
+}
+
+// Universal cokriging: each solved row dotted with the q = 1 + p basis rows [y; U] (the data row and the trend rows) in ONE
+// pass.  A wave owns CK_UNIV_RW rows and keeps their q + 1 sums per lane in registers; the basis rows of a panel are staged
+// through LDS half a panel (256 columns) at a time, so every workgroup reads them once per panel for its 4 CK_UNIV_RW rows
+// instead of once per row (k_reduce_pred reads y per row).  The loads of a panel's rows are issued before the staging barrier.
+// The loops over the basis rows are unrolled to CK_UNIV_QMAX with a uniform guard: the sums stay in registers.
+#define CK_UNIV_RW 2
+__global__ __launch_bounds__(256) void k_reduce_univ(const double* __restrict__ aux, long mpad, int n_panels, long nrows,
+                                                      long brow0, int q, double* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) double ub[CK_UNIV_QMAX * 256];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long row0 = (long)blockIdx.x * (4 * CK_UNIV_RW) + (long)w * CK_UNIV_RW;
+    double acc[CK_UNIV_RW][CK_UNIV_QMAX + 1];
+#pragma unroll
+    for (int r = 0; r < CK_UNIV_RW; ++r)
+#pragma unroll
+        for (int j = 0; j <= CK_UNIV_QMAX; ++j) acc[r][j] = 0.0;
+    for (int K = 0; K < n_panels; ++K) {
+        const double* pb = aux + (long)K * mpad * CK_NB;
+        d2_t x[CK_UNIV_RW][4];
+#pragma unroll
+        for (int r = 0; r < CK_UNIV_RW; ++r) {
+            const bool live = row0 + r < nrows;
+            const double* xr = pb + (live ? row0 + r : 0) * CK_NB;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                x[r][t] = *reinterpret_cast<const d2_t*>(xr + t * 128 + lane * 2);
+                if (!live) x[r][t] = d2_t{0.0, 0.0};
+            }
+        }
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+            __syncthreads();   // the previous half's basis has been read
+            for (int e = threadIdx.x; e < q * 128; e += 256) {   // q rows x 256 columns, two doubles per thread and step
+                const int j = e >> 7, c = (e & 127) * 2;
+                *reinterpret_cast<d2_t*>(ub + j * 256 + c) =
+                    *reinterpret_cast<const d2_t*>(pb + (brow0 + j) * CK_NB + hf * 256 + c);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {
+#pragma unroll
+                for (int r = 0; r < CK_UNIV_RW; ++r) {
+                    const d2_t xv = x[r][2 * hf + tt];
+                    acc[r][0] += xv[0] * xv[0] + xv[1] * xv[1];
+                }
+#pragma unroll
+                for (int j = 0; j < CK_UNIV_QMAX; ++j) {
+                    if (j < q) {
+                        const d2_t bj = *reinterpret_cast<const d2_t*>(ub + j * 256 + tt * 128 + lane * 2);
+#pragma unroll
+                        for (int r = 0; r < CK_UNIV_RW; ++r) {
+                            const d2_t xv = x[r][2 * hf + tt];
+                            acc[r][1 + j] += xv[0] * bj[0] + xv[1] * bj[1];
+                        }
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < CK_UNIV_RW; ++r)
+#pragma unroll
+        for (int j = 0; j <= CK_UNIV_QMAX; ++j) {
+            if (j <= q) {
+                double v = acc[r][j];
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+                acc[r][j] = v;
+            }
+        }
+    if (lane == 0)
+#pragma unroll
+        for (int r = 0; r < CK_UNIV_RW; ++r) {
+#pragma unroll
+            for (int j = 0; j <= CK_UNIV_QMAX; ++j)
+                if (j <= q && row0 + r < nrows) out[(row0 + r) * (q + 1) + j] = acc[r][j];
+        }
+}
+
+void ck_launch_reduce_univ(hipStream_t s, const double* aux, int64_t mpad, int n_panels, int64_t nrows, int64_t brow0, int q,
+                           double* out) {
+    if (nrows <= 0 || n_panels <= 0 || q < 1 || q > CK_UNIV_QMAX || brow0 < 0 || brow0 + q > mpad || nrows > mpad) return;
+    const int64_t rows_per = 4 * CK_UNIV_RW;
+    k_reduce_univ<<<dim3((unsigned)((nrows + rows_per - 1) / rows_per)), dim3(256), 0, s>>>(aux, (long)mpad, n_panels, (long)nrows,
+                                                                                           (long)brow0, q, out);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -37,6 +37,7 @@ from numpy.linalg import LinAlgError
 from . import native
 from .fields import metric_of
 from .model import configure_handle
+from .trend import TrendDesign, check_trend
 
 try:  # the reference returns xarray objects; keep that when xarray exists
     import xarray as xr
@@ -48,15 +49,28 @@ class Predictor:
     """Multivariate prediction framework (src/joint_prediction.py:13-33)."""
 
     def __init__(self, mod, mf, covariates=None, dist_units: str = "km", fast_dist: bool = True,
-                 device: int = 0, devices=None) -> None:
+                 device: int = 0, devices=None, trend=None) -> None:
         """``devices=[0, 1, ...]``: the multi-GPU form (BASELINE configs[3]) -- one worker process per entry, Sigma
         block-column-cyclic over them, panels exchanged over RCCL/xGMI at each Cholesky step, prediction points sharded
         (workers.RankPool + distributed.DistributedJoint; the same ordinal twice rehearses it on one GPU over gloo).
         The reference's parallel entry is likewise a keyword on the predictor (src/point_prediction.py:45-52,69-81).
         Same results as ``device=`` to rounding; ``cross_validation`` and the exact ``_verify_model`` check are
-        single-device paths and run on ``devices[0]``."""
+        single-device paths and run on ``devices[0]``.
+
+        ``trend``: None (simple cokriging, the data have a known zero mean), ``"constant"`` (ordinary cokriging),
+        ``"linear"`` ([1, c1, c2] per process, coordinates centred and scaled by that process's data sites) or a callable
+        ``f(k, coords) -> (n, p_k)``: universal cokriging, the trend estimated by GLS jointly with the kriging and its
+        uncertainty added to ``pred_err`` (include/cokrige.h: ck_predict_universal).  After a call ``trend_coef`` holds
+        the GLS coefficients and ``trend_cov`` their covariance.  A prediction site whose regressors are not finite gets
+        NaN.  The universal forms of ``predict_blocks``, ``conditional_simulation``, ``cross_validation`` and the
+        multi-GPU path are not available."""
         if mod.n_procs != mf.n_procs:
             raise ValueError("Number of theoretical processes different from empirical processes.")
+        self.trend = check_trend(trend)
+        if self.trend is not None and devices is not None and len(devices) > 1:
+            raise NotImplementedError("universal cokriging (trend=...) runs on one device; the multi-GPU path is simple "
+                                      "cokriging only")
+        self.trend_coef, self.trend_cov = None, None
         self.n_procs = mod.n_procs
         self.mod = mod
         self.mf = mf
@@ -179,6 +193,8 @@ class Predictor:
         """(pred, pred_err) as arrays -- the numeric body of ``__call__``
         (src/joint_prediction.py:49-78)."""
         pc = np.ascontiguousarray(np.atleast_2d(np.asarray(pcoords, dtype=np.float64)))
+        if self.trend is not None:
+            return self._predict_universal(i, pc, cv_ix)
         if cv_ix is None and self.devices is not None and len(self.devices) > 1:
             self._verdict = None     # the exact _verify_model check is a single-device path: the variance test stands in
             return self._predict_on_ranks(i, pc)
@@ -218,6 +234,56 @@ class Predictor:
             finally:
                 h.close()
         return pred, err
+
+    def _trend_design(self):
+        return TrendDesign(self.trend, [np.asarray(self.mf.fields[k].coords_main, dtype=np.float64)[:, :2]
+                                        for k in range(self.n_procs)])
+
+    def _predict_universal(self, i, pc, cv_ix=None):
+        """Universal cokriging (``trend``): the regressors are validated on the host before any device work, then the
+        trend is set on the resident factor's handle (the factor does not depend on it) and the sites with finite
+        regressors go through ``ck_predict_universal`` in chunks of ``rhs_budget_bytes``."""
+        if not 0 <= int(i) < self.n_procs:
+            raise ValueError(f"process index {i!r} out of range for {self.n_procs} processes")
+        design = self._trend_design()
+        F = [design.data(k, np.asarray(self.mf.fields[k].coords_main, dtype=np.float64)[:, :2]) for k in range(self.n_procs)]
+        if cv_ix is not None:
+            F[i] = np.delete(F[i], cv_ix, axis=0)
+        pc = np.ascontiguousarray(pc[:, :2])
+        F0 = design(i, pc)
+        ok = np.all(np.isfinite(F0), axis=1)
+        self._verdict = None   # the exact _verify_model check is the simple-kriging one: the variance test stands in
+        if cv_ix is None:
+            h = self._factored_handle()
+        else:
+            h = self._new_handle(drop=(i, cv_ix))
+        try:
+            if cv_ix is not None:
+                self._factor(h)
+            for k in range(self.n_procs):
+                h.set_trend(k, F[k])
+            m = len(pc)
+            pred, err = np.full(m, np.nan), np.full(m, np.nan)
+            idx = np.flatnonzero(ok)
+            n_pad = h.num_panels()[2]
+            chunk = max(1024, int(self.rhs_budget_bytes // (8 * max(n_pad, 1))))
+            beta, cov = None, None
+            for a in range(0, max(len(idx), 1), chunk):
+                sub = idx[a:a + chunk]
+                p_, e_, beta, cov = h.predict_universal(i, pc[sub], F0[sub])
+                pred[sub], err[sub] = p_, e_
+            self.trend_coef, self.trend_cov = beta, cov
+            if cv_ix is None:
+                self.timings = h.universal_timings()
+        finally:
+            if cv_ix is not None:
+                h.close()
+        return pred, err
+
+    def _no_trend(self, what):
+        if self.trend is not None:
+            raise NotImplementedError(f"{what} is simple cokriging only; it has no universal form (this predictor has "
+                                      f"trend={self.trend!r})")
 
     def _verify(self, h, i, pc, pred_err):
         """True: the joint covariance of the data and these prediction sites is NOT positive definite
@@ -363,6 +429,7 @@ class Predictor:
         centroid ``lat`` / ``lon``.  ``postprocess=True`` is ``_postprocess_predictions`` applied to the weighted sum:
         pred = scale_fact pred_b + sum_a w_a (spatial_mean + trend_a + temporal_trend), pred_err and cov scaled by
         scale_fact (cov by its square); a block with a site whose trend is missing (covariate NaN) has pred NaN."""
+        self._no_trend("predict_blocks")
         pc, codes, w, labels, _ = self._block_layout(pcoords, blocks, weights)
         r = len(labels)
         h = self._factored_handle()
@@ -411,6 +478,7 @@ class Predictor:
 
         Returns (draws (n_draws, m), pred, pred_err, deflated (bool, m), seed).  Raises ValueError on bad arguments
         before any device work, and numpy.linalg.LinAlgError when S cannot be factored."""
+        self._no_trend("conditional simulation")
         if isinstance(i, bool) or not (isinstance(i, (int, np.integer)) and 0 <= int(i) < self.n_procs):
             raise ValueError(f"process index {i!r} out of range for {self.n_procs} processes")
         pc = np.atleast_2d(np.asarray(pcoords.values if isinstance(pcoords, pd.DataFrame) else pcoords, dtype=np.float64))
@@ -509,6 +577,7 @@ class Predictor:
         ONE factorisation (``ck_loocv``: the Gaussian conditional of z_q given the rest,
         pred_q = z_q - (Sigma^-1 z)_q / (Sigma^-1)_qq, var_q = 1 / (Sigma^-1)_qq -- the same
         numbers).  ``refactor_each=True`` runs the reference's n-solve loop instead."""
+        self._no_trend("cross_validation")
         names = ["lat", "lon"] if postprocess else ["d1", "d2"]
         f = self.mf.fields[i]
         data = pd.DataFrame(np.hstack((f.coords_main, np.atleast_2d(f.values_main).T)), columns=names + ["data"])

@@ -288,20 +288,37 @@ class MultivariateMatern:
         configure_handle(h, self)
         return h
 
-    def log_likelihood(self, mf, dist_units: str = "km", fast_dist: bool = True, gradient: bool = False):
+    def log_likelihood(self, mf, dist_units: str = "km", fast_dist: bool = True, gradient: bool = False, trend=None):
         """Gaussian log-likelihood of the data the joint predictor uses (every field's ``coords_main`` / ``values_main``,
         zero mean as in simple cokriging) under the current parameters:
             l = -1/2 (N log 2 pi + log|Sigma| + z^T Sigma^-1 z),
         Sigma assembled as the predictor assembles it.  ``gradient=True``: (l, dl/dtheta) with the gradient in the flat
-        order of ``params.get_names()``.  A Sigma that is not positive definite raises LinAlgError with scipy's text."""
+        order of ``params.get_names()``.  A Sigma that is not positive definite raises LinAlgError with scipy's text.
+
+        ``trend`` (as ``Predictor(trend=...)``: "constant", "linear" or a callable): the restricted likelihood (REML) for an
+        unknown trend X beta, ``ck_loglik_reml``:
+            l_R = -1/2 ((N - p) log 2 pi + log|Sigma| + log|X^T Sigma^-1 X| + z^T P z),
+        without a log|X^T X| term."""
+        from .trend import TrendDesign, check_trend
+        check_trend(trend)
         h = self._lik_handle(mf, dist_units, fast_dist)
+        if trend is not None:
+            cs = [np.asarray(mf.fields[k].coords_main, dtype=np.float64)[:, :2] for k in range(self.n_procs)]
+            design = TrendDesign(trend, cs)
+            F = [design.data(k, cs[k]) for k in range(self.n_procs)]
+            for k in range(self.n_procs):
+                h.set_trend(k, F[k])
+        else:
+            for k in range(self.n_procs):
+                h.set_trend(k, None)
         h.assemble_joint()
-        info, out3, g = h.loglik(gradient)
+        info, out3, g = h.loglik_reml(gradient) if trend is not None else h.loglik(gradient)
         if info != 0:
             raise LinAlgError(f"{info}-th leading minor of the array is not positive definite")
         return (out3[0], g) if gradient else out3[0]
 
-    def fit_likelihood(self, mf, guess: MaternParams = None, fixed=None, dist_units: str = "km", fast_dist: bool = True):
+    def fit_likelihood(self, mf, guess: MaternParams = None, fixed=None, dist_units: str = "km", fast_dist: bool = True,
+                       trend=None):
         """Maximum-likelihood fit: L-BFGS-B on -l with the analytic gradient, within ``params.get_bounds()``.
         ``guess`` as in ``fit``: None starts from the default parameters, else from the current ones with the bounds of
         ``guess``.  ``fixed``: parameter names or flat indices held at their starting values.
@@ -310,7 +327,10 @@ class MultivariateMatern:
         fit: the cost there is the largest -l met so far plus 1e6 (1 + |that value|), finite and far above every positive
         definite point, with the gradient of the last positive definite point, so that the line search backtracks; such
         evaluations are counted in ``fit_result.n_not_pd``.  Sets the parameters and ``self.fit_result``
-        (FittedLikelihood)."""
+        (FittedLikelihood).  ``trend``: maximise the restricted likelihood (REML) for that trend instead
+        (``log_likelihood(trend=...)``); ``fit_result.method`` is then "REML"."""
+        from .trend import check_trend
+        check_trend(trend)
         if guess is None:
             init = self.params.reset_values().get_values().astype(float)
         else:
@@ -346,7 +366,7 @@ class MultivariateMatern:
             state["n_eval"] += 1
             self.params.set_values(theta_of(u))
             try:
-                ll, g = self.log_likelihood(mf, dist_units, fast_dist, gradient=True)
+                ll, g = self.log_likelihood(mf, dist_units, fast_dist, gradient=True, trend=trend)
             except LinAlgError:
                 ll = None
             if ll is None or not np.isfinite(ll) or not np.all(np.isfinite(g)):
@@ -368,17 +388,20 @@ class MultivariateMatern:
             warnings.warn("ERROR: optimization did not converge.")
         theta = theta_of(res.x)
         self.params.set_values(theta)
-        ll, g = self.log_likelihood(mf, dist_units, fast_dist, gradient=True)
-        self.fit_result = FittedLikelihood(self, ll, g, free, state["n_eval"], state["n_not_pd"], res)
+        ll, g = self.log_likelihood(mf, dist_units, fast_dist, gradient=True, trend=trend)
+        self.fit_result = FittedLikelihood(self, ll, g, free, state["n_eval"], state["n_not_pd"], res,
+                                           method="ML" if trend is None else "REML")
         return self
 
 
 class FittedLikelihood:
     """Result of ``MultivariateMatern.fit_likelihood``: the maximised log-likelihood, AIC = 2 k - 2 l over the k free
     parameters, the gradient there, the numbers of evaluations and of evaluations at a Sigma that was not positive
-    definite, and the optimiser's message."""
+    definite, and the optimiser's message.  ``method``: "ML", or "REML" for a fit with a trend (``loglik`` is then l_R)."""
 
-    def __init__(self, model: MultivariateMatern, loglik: float, gradient, free, n_eval: int, n_not_pd: int, optim) -> None:
+    def __init__(self, model: MultivariateMatern, loglik: float, gradient, free, n_eval: int, n_not_pd: int, optim,
+                 method: str = "ML") -> None:
+        self.method = method
         self.params = model.params
         self.names = list(model.params.get_names())
         self.loglik = float(loglik)

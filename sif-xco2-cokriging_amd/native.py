@@ -51,6 +51,9 @@ _PROTOS = {
     "ck_predict_blocks": [c_void_p, c_int, _dp, c_int64, POINTER(c_int32), _dp, c_int32, _dp, _dp, _dp],
     "ck_loocv": [c_void_p, c_int, _dp, _dp],
     "ck_loglik": [c_void_p, c_int, _dp, _dp, POINTER(c_int64)],
+    "ck_set_trend": [c_void_p, c_int, _dp, c_int64, c_int],
+    "ck_predict_universal": [c_void_p, c_int, _dp, c_int64, _dp, _dp, _dp, _dp, _dp],
+    "ck_loglik_reml": [c_void_p, c_int, _dp, _dp, POINTER(c_int64)],
     "ck_sample": [c_void_p, _dp, _dp, c_int64],
     "ck_conditional_draws": [c_void_p, c_int, _dp, c_int64, c_int64, c_uint64, _dp, c_double, c_double, _dp, _dp, _dp,
                              POINTER(c_uint8), POINTER(c_int64)],
@@ -239,6 +242,7 @@ class Handle:
         entry of `devices`), already partitioned (rank, len(devices)) -- include/cokrige.h: ck_create_partitioned."""
         self._h = c_void_p()
         self._keep = []
+        self._trend_p, self._n_data = {}, {}
         if devices is None:
             _chk(lib().ck_create(int(device), byref(self._h)))
         else:
@@ -296,6 +300,8 @@ class Handle:
         if c.shape[0] != v.size:
             raise ValueError("coords and values disagree in length")
         _chk(lib().ck_set_data(self._h, int(k), _p(c), _p(v), c.shape[0]))
+        self._n_data[int(k)] = c.shape[0]
+        self._trend_p[int(k)] = 0   # ck_set_data clears the trend of process k
 
     # -- element-wise surface -------------------------------------------------------------
     def distance_dense(self, A, B):
@@ -388,6 +394,58 @@ class Handle:
         if grad is not None and getattr(self, "_n_procs", 2) == 1:
             grad = grad[:4].copy()
         return info.value, tuple(out3.tolist()), grad
+
+    def set_trend(self, k, F):
+        """Regressors of process k at its data sites, (n_k, p_k) in the order of set_data (include/cokrige.h: ck_set_trend);
+        None or p_k = 0 clears the trend of process k."""
+        if F is None:
+            n = int(getattr(self, "_n_data", {}).get(int(k), 0))
+            _chk(lib().ck_set_trend(self._h, int(k), None, n, 0))
+            self._trend_p[int(k)] = 0
+            return
+        F = _f64(F)
+        if F.ndim != 2:
+            raise ValueError("the regressors must be a 2-D array (n_k, p_k)")
+        _chk(lib().ck_set_trend(self._h, int(k), _p(F) if F.size else None, F.shape[0], F.shape[1]))
+        self._trend_p[int(k)] = F.shape[1]
+
+    def predict_universal(self, i, pcoords, f0=None):
+        """Universal cokriging of process i on the resident factor (include/cokrige.h: ck_predict_universal).  f0: (m, p_i)
+        regressors of process i at pcoords.  Returns (pred, err, beta, beta_cov) with beta (p,) and beta_cov (p, p) over the
+        trend columns of both processes; without a trend (p = 0) the predict() result and empty beta / beta_cov."""
+        pc = _f64(pcoords, 2)
+        m = pc.shape[0]
+        p = sum(self._trend_p.values())
+        pi = self._trend_p.get(int(i), 0)
+        F0 = None
+        if pi > 0:
+            F0 = _f64(np.zeros((m, 0)) if f0 is None else f0)
+            if F0.shape != (m, pi):
+                raise ValueError(f"f0 has shape {F0.shape}, expected {(m, pi)}")
+        pred, err = np.empty(m), np.empty(m)
+        beta, cov = np.empty(p), np.empty((p, p))
+        _chk(lib().ck_predict_universal(self._h, int(i), _p(pc), m, _p(F0) if F0 is not None else None, _p(pred), _p(err),
+                                        _p(beta) if p else None, _p(cov) if p else None))
+        return pred, err, beta, cov
+
+    def universal_timings(self):
+        """ck_timings [40 ..] of the last predict_universal() call, in milliseconds."""
+        out = np.zeros(46)
+        _chk(lib().ck_timings(self._h, _p(out), 46))
+        keys = ["k2_ms", "sweep_ms", "reduce_ms", "gls_ms", "finish_ms", "total_ms"]
+        return dict(zip(keys, out[40:46].tolist()))
+
+    def loglik_reml(self, want_grad=False):
+        """Restricted log-likelihood for the trend of set_trend (include/cokrige.h: ck_loglik_reml) on an assembled handle.
+        Returns (info, (l_R, log|Sigma|, log|X^T Sigma^-1 X|, z^T P z), gradient | None), as loglik()."""
+        out4 = np.empty(4)
+        grad = np.empty(11) if want_grad else None
+        info = c_int64(0)
+        _chk(lib().ck_loglik_reml(self._h, int(bool(want_grad)), _p(out4), _p(grad) if grad is not None else None,
+                                  byref(info)))
+        if grad is not None and getattr(self, "_n_procs", 2) == 1:
+            grad = grad[:4].copy()
+        return info.value, tuple(out4.tolist()), grad
 
     def loglik_timings(self):
         """ck_timings [24 ..] of the last loglik() call, in milliseconds."""
