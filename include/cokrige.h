@@ -309,6 +309,34 @@ int ck_predict_local(ck_handle* h, int i, const double* pcoords_host, int64_t m,
  * 32 GiB; option "local_slab_mb" if set).  Afterwards no ck_predict_local whose batches fit pays a hipMalloc (tens of GiB
  * right after smaller buffers were freed: up to seconds -- ck_timings [14] shows what a call spent growing the slab). */
 int ck_local_reserve(ck_handle* h, int64_t nbytes);
+/* Universal cokriging in the moving neighbourhood: ck_predict_local with the trend of ck_set_trend estimated by GLS in every
+ * neighbourhood (one constant column per process: ordinary cokriging in a moving window).  The formulation is that of
+ * ck_predict_universal applied to one point's k neighbours, Sigma_loc = L L^T, c and z as in ck_predict_local:
+ *   X_loc (k x p, p = p_0 + p_1 <= 2 CK_TREND_PMAX): the columns of process q carry F_q at that process's neighbours,
+ *   v = L^-1 c,  y = L^-1 z,  U = L^-1 X_loc,  A = U^T U,  b = U^T y,  r = x0 - U^T v,  beta = A^-1 b,
+ *   pred = v . y + r^T beta,  pred_err = nan_to_num(sqrt(sigma_i^2 + nugget_i - v . v + r^T A^-1 r)), clamped at 0,
+ * x0 = the regressors of process i at the point in the columns of block i, zeros elsewhere.  The p trend rows ride along the
+ * local factorisation as c and z do; every sum has a fixed order (no atomics): repeated calls give the same bits.
+ * f0: m x p_i regressors of process i at pcoords (NULL when p_i = 0).  beta (m x p, or NULL): every point's local GLS
+ * coefficients, NaN in dropped columns (rule 3) and in the whole row where the prediction is NaN.
+ * Degenerate cases, per point:
+ *   1. empty neighbourhood: NaN, counted in n_empty;
+ *   2. local Sigma not positive definite: NaN, counted in n_not_pd;
+ *   3. a process with regressors but no neighbour in range has identically zero columns of X_loc.  If it is not process i its
+ *      columns are dropped and the result is the universal prediction from the remaining columns; if it is process i
+ *      (p_i > 0) the unbiasedness constraint cannot be met: NaN, counted in n_rank_def;
+ *   4. A is then factored with the relative pivot threshold of the joint path (1e-10): a rank-deficient design (fewer
+ *      neighbours of a process than it has regressors, collinear columns) gives NaN, counted in n_rank_def -- it never fails
+ *      the call, being a property of single points;
+ *   5. a non-finite regressor in a row of f0: both outputs NaN, the point is in none of the three counters;
+ *   6. no trend set (p = 0): the call is ck_predict_local, bit for bit (n_rank_def = 0, beta untouched).
+ * Needs ck_set_model / ck_set_data / ck_set_trend only (no Sigma panels).  Refused through ck_last_error: a partitioned
+ * handle, f0 == NULL with p_i > 0.  Neighbourhoods of up to 64 sites are solved in LDS ((64 + 2 + p) x 64 doubles), larger
+ * ones on the tiled path with roundup(k + 2 + p, 64) rows; the scratch slab (ck_local_reserve) is shared with ck_predict_local
+ * and batches are sized with the p extra rows.  ck_timings [48 ..] describe the call. */
+int ck_predict_local_universal(ck_handle* h, int i, const double* pcoords_host, int64_t m, const double* f0_host,
+                               double max_dist, int cv, double* pred_host, double* pred_err_host, double* beta_host,
+                               int64_t* n_empty, int64_t* n_not_pd, int64_t* n_rank_def, int64_t* k_max);
 
 /* ---- empirical (cross-)semivariogram / covariogram: src/fields.py:192-232, 378-403 ----- */
 /* Fields i and j: coords (n x 2), residuals = values minus their mean (src/fields.py:380).
@@ -437,7 +465,11 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * generation (k_draw_noise), summed over the chunks; [36] the draw product and its epilogue (k_draw_trmm), summed over the
  * chunks; [37] host wall clock of the call; [38] number of deflated sites; [39] number of chunks.
  * ck_predict_universal (n up to 48): [40] K2 assembly of its right-hand sides; [41] the forward sweep; [42] the universal
- * reduction (k_reduce_univ); [43] the host GLS step; [44] the host epilogue; [45] host wall clock of the call. */
+ * reduction (k_reduce_univ); [43] the host GLS step; [44] the host epilogue; [45] host wall clock of the call.
+ * ck_predict_local_universal (n up to 54): [48] the counting pass; [49] assembly and factorisation of both size classes (the
+ * LDS class's kernel whole, its reduction included); [50] the tiled class's universal reduction (Gram matrix of the solved
+ * rows and the GLS step), summed over the batches; [51] host wall clock of the call; [52] / [53] number of points in the LDS
+ * class (empty neighbourhoods included) / in the tiled class. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it
@@ -500,7 +532,8 @@ int ck_table_fallbacks(ck_handle* h, int reset, int64_t* count);
  * 32 GiB; the points are processed in batches that fit; the scratch is kept until ck_destroy and reused);
  * "local_tile_min" (default 64 = the LDS kernel's limit): neighbourhoods with more sites than this are factored by
  * the tiled path of ck_predict_local (batched 64-column steps on the matrix cores) instead of one workgroup per
- * point (in LDS up to 64 sites, on a global slab above);
+ * point (in LDS up to 64 sites, on a global slab above); ck_predict_local_universal with a trend set has no slab kernel:
+ * there every neighbourhood beyond min(local_tile_min, 64) sites takes the tiled path;
  * "local_group" (1..8, default 4) = 64-column blocks per group of that path; "local_left" (0/1, default 1): a group's columns receive
  * everything from their left in one pass (K = the group's first column) before the group is factored, instead of a K = 64 x
  * local_group update of everything behind every group (same bits: the accumulation order per element is the same);

@@ -32,9 +32,10 @@
 #include "ck_model.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 48
+#define CK_N_TIMINGS 56
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
+static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
 
 static int fail(const std::string& msg) { return ck_fail(msg); }   // thread-local text: ck_host.cpp (ck_last_error)
 #define HIPCHK(expr)                                                                              \
@@ -2967,10 +2968,15 @@ extern "C" int ck_loglik_reml(ck_handle* h, int want_grad, double* out4, double*
 // ---------------------------------------------------------------------------------------
 // local-neighbourhood cokriging: src/point_prediction.py:45-249
 // ---------------------------------------------------------------------------------------
-extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int64_t m, double max_dist, int cv,
-                                double* pred, double* pred_err, int64_t* n_empty, int64_t* n_not_pd,
-                                int64_t* k_max) {
-    CHKH(h);
+// The universal form's extras (ck_predict_local_universal); null: simple cokriging, ck_predict_local as it always was
+struct LocalUniv {
+    const double* f0;      // m x p_i, the caller's (may hold non-finite entries: rule 5)
+    double* beta;          // m x p or null
+    int64_t* n_rank_def;
+};
+
+static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_t m, double max_dist, int cv, double* pred,
+                              double* pred_err, int64_t* n_empty, int64_t* n_not_pd, int64_t* k_max, const LocalUniv* u) {
     if (ensure_layout(h, false)) return -1;   // sites, tables, chunk bounds -- no Sigma panels
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
     if (m < 0 || (m > 0 && !pcoords)) return fail("bad pcoords");
@@ -2978,6 +2984,10 @@ extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int6
     if (n_not_pd) *n_not_pd = 0;
     if (k_max) *k_max = 0;
     if (m == 0) return 0;
+    const auto t_begin = std::chrono::steady_clock::now();
+    const int up = u ? trend_total(h) : 0;   // trend rows of every local system
+    const int upi = u ? h->trend_p[i] : 0;
+    if (u && ensure_trend(h)) return -1;
     const int64_t mp = roundup(m, 64);
     DevTemps tmp;
     double *d_pc = nullptr, *d_p3 = nullptr, *d_pu = nullptr, *d_out = nullptr, *d_slab = nullptr;
@@ -2991,6 +3001,25 @@ extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int6
     HIPCHK(tmp.get(&d_out, (size_t)(2 * mp * 8)));
     HIPCHK(tmp.get(&d_cnt, (size_t)(mp * sizeof(int))));
     HIPCHK(tmp.get(&d_off, (size_t)(mp * sizeof(long long))));
+    // universal form: the regressors of the prediction points (a point with a non-finite one is settled on the host at the
+    // end and computes with zeros meanwhile), the status of every point, the local coefficients
+    double *d_f0 = nullptr, *d_beta = nullptr;
+    int* d_stat = nullptr;
+    std::vector<char> f0_bad;
+    if (u) {
+        std::vector<double> f0s((size_t)(m * upi));
+        f0_bad.assign((size_t)m, 0);
+        for (int64_t e = 0; e < m * upi; ++e) {
+            const bool ok = std::isfinite(u->f0[e]);
+            f0s[(size_t)e] = ok ? u->f0[e] : 0.0;
+            if (!ok) f0_bad[(size_t)(e / upi)] = 1;
+        }
+        HIPCHK(tmp.get(&d_f0, (size_t)(m * upi * 8)));
+        HIPCHK(tmp.get(&d_stat, (size_t)(mp * sizeof(int))));
+        if (u->beta) HIPCHK(tmp.get(&d_beta, (size_t)(m * up * 8)));
+        if (upi > 0) HIPCHK(hipMemcpy(d_f0, f0s.data(), (size_t)(m * upi * 8), hipMemcpyHostToDevice));
+    }
+    const CkLocalTrend Tr{h->d_trendX, d_f0, u ? h->trend_p[0] : 0, u && h->n_procs == 2 ? h->trend_p[1] : 0, CK_TREND_TOL};
     HIPCHK(hipMemsetAsync(d_pc, 0, 2 * mp * 8, h->stream));
     HIPCHK(hipMemcpyAsync(d_pc, pcoords, 2 * m * 8, hipMemcpyHostToDevice, h->stream));
     ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, d_p3, d_p3 + mp, d_p3 + 2 * mp, d_pu);
@@ -3019,7 +3048,9 @@ extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int6
     // Both slab users work in batches that fit a budget (a quarter of the free device memory, at most 32 GiB),
     // so that large radii over many points do not need sum_p k_p^2 doubles at once.
     const int kl = ck_local_lds_limit();
-    const int k_hi = h->local_tile_min;   // may lie below the LDS limit: then the LDS kernel only sees k <= k_hi
+    // may lie below the LDS limit: then the LDS kernel only sees k <= k_hi.  The universal form has no slab kernel: every
+    // neighbourhood beyond the LDS limit takes the tiled path
+    const int k_hi = u ? std::min(h->local_tile_min, kl) : h->local_tile_min;
     std::vector<long long> off(m, 0), need(m, 0);
     std::vector<int64_t> tiled;   // points of the third class
     int64_t kmx = 0, nempty = 0;
@@ -3031,7 +3062,7 @@ extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int6
         long long nd = 0;
         if (k > k_hi) {
             tiled.push_back(p);
-            nd = ck_local_tiled_doubles(k);
+            nd = ck_local_tiled_doubles(k, up);
         } else if (k > kl) {
             nd = need[p] = ((k + 2) * k + (k + 1) / 2 + 2 + 1) & ~1LL;   // matrix + index list (ints), kept 16-byte aligned
         }
@@ -3043,7 +3074,7 @@ extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int6
     long long budget = (long long)std::min<size_t>(mem_free / 4, (size_t)32 << 30) / 8;   // doubles
     if (h->local_slab_mb > 0) budget = (long long)h->local_slab_mb * (1 << 20) / 8;      // option "local_slab_mb" (tests)
     if (budget < need_max) budget = need_max;
-    if ((size_t)need_max * 8 > mem_free) return fail("ck_predict_local: a neighbourhood of " + std::to_string(kmx) + " sites does not fit the device memory");
+    if ((size_t)need_max * 8 > mem_free) return fail(std::string(u ? "ck_predict_local_universal" : "ck_predict_local") + ": a neighbourhood of " + std::to_string(kmx) + " sites does not fit the device memory");
     std::vector<std::pair<int64_t, int64_t>> batches;   // [begin, end)
     long long slab_doubles = 0;
     {
@@ -3070,14 +3101,14 @@ extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int6
         size_t b0 = 0;
         long long acc = 0;
         for (size_t t = 0; t < tiled.size(); ++t) {
-            const long long k = cnt[tiled[t]], nd = ck_local_tiled_doubles(k);
+            const long long k = cnt[tiled[t]], nd = ck_local_tiled_doubles(k, up);
             if (acc + nd > budget && t > b0) {
                 tbatches.push_back({b0, t});
                 slab_doubles = acc > slab_doubles ? acc : slab_doubles;
                 b0 = t;
                 acc = 0;
             }
-            const int kq = (int)ck_local_tiled_kq(k);
+            const int kq = (int)ck_local_tiled_kq(k, up);
             sysv[t] = CkLocalSys{acc, (int)k, kq, kq + 128, (int)tiled[t]};
             acc += nd;
         }
@@ -3115,11 +3146,23 @@ extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int6
     HIPCHK(hipMemcpyAsync(d_off, off.data(), m * sizeof(long long), hipMemcpyHostToDevice, h->stream));
     const double c0var = h->blk[2 * i].amp + h->blk[2 * i].nugget;   // covariance(i, 0)[0], point_prediction.py:66
     const int use_tab = tables_usable(h) ? 1 : 0;
-    for (const auto& bt : batches)
-        ck_launch_local_solve(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, bt.first, bt.second - bt.first,
-                              mp, h->s0, h->z, layout_of(h), d_cnt, d_off, d_slab, c0var, d_out, d_out + mp, h->d_tabs,
-                              h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb, cmax);
+    if (u)
+        ck_launch_local_solve_u(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, h->z, layout_of(h),
+                                d_cnt, c0var, d_out, d_out + mp, h->d_tabs, h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb,
+                                cmax, Tr, d_beta, d_stat);
+    else
+        for (const auto& bt : batches)
+            ck_launch_local_solve(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, bt.first, bt.second - bt.first,
+                                  mp, h->s0, h->z, layout_of(h), d_cnt, d_off, d_slab, c0var, d_out, d_out + mp, h->d_tabs,
+                                  h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb, cmax);
     HIPCHK(hipGetLastError());
+    std::vector<hipEvent_t> ev_red;   // universal form: an event pair around every batch's reduction (ck_timings [50])
+    struct EvFree {
+        std::vector<hipEvent_t>& v;
+        ~EvFree() {
+            for (hipEvent_t e : v) (void)hipEventDestroy(e);
+        }
+    } ev_free{ev_red};
     if (!tiled.empty()) {
         HIPCHK(tmp.get(&d_sys, (size_t)(sysv.size() * sizeof(CkLocalSys))));
         HIPCHK(tmp.get(&d_linfo, (size_t)(sysv.size() * sizeof(long long))));
@@ -3132,6 +3175,7 @@ extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int6
             ck_launch_local_assemble_t(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, mp, h->s0, h->z,
                                        layout_of(h), bsys, nb, d_slab, h->d_tabs, h->d_coefptr, use_tab, h->su, d_pu,
                                        h->d_chunkb, cmax, d_k0 + tb.first);
+            if (u) ck_launch_local_trend_rows_t(h->stream, bsys, nb, d_slab, layout_of(h), Tr);
             const int kq_max = sysv[tb.first].kq;
             std::vector<int> kqv(nb);
             for (int y = 0; y < nb; ++y) kqv[y] = sysv[tb.first + y].kq;
@@ -3155,7 +3199,19 @@ extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int6
                 ck_launch_local_tiled_rows_all(h->stream, bsys, d_slab, na, g0, G, kqv.data());
                 if (!left) ck_launch_local_tiled_trailing(h->stream, bsys, d_slab, na, g0, 64 * G, kqv.data());
             }
-            ck_launch_local_reduce_t(h->stream, bsys, nb, d_slab, d_linfo + tb.first, c0var, d_out, d_out + mp);
+            if (u) {
+                hipEvent_t e0 = nullptr, e1 = nullptr;
+                HIPCHK(hipEventCreate(&e0));
+                ev_red.push_back(e0);
+                HIPCHK(hipEventCreate(&e1));
+                ev_red.push_back(e1);
+                HIPCHK(hipEventRecord(e0, h->stream));
+                ck_launch_local_reduce_ut(h->stream, bsys, nb, d_slab, d_linfo + tb.first, d_k0 + tb.first, i, c0var, d_out,
+                                          d_out + mp, Tr, d_beta, d_stat);
+                HIPCHK(hipEventRecord(e1, h->stream));
+            } else {
+                ck_launch_local_reduce_t(h->stream, bsys, nb, d_slab, d_linfo + tb.first, c0var, d_out, d_out + mp);
+            }
             HIPCHK(hipGetLastError());
         }
     }
@@ -3169,12 +3225,71 @@ extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int6
     HIPCHK(hipEventElapsedTime(&ms2, h->ev2, h->ev3));
     h->t_ms[10] = (double)ms + (double)ms2;   // device work: counting pass + assembly / factorisations / reductions
     int64_t npd = 0;
-    for (int64_t p = 0; p < m; ++p)
-        if (cnt[p] > 0 && pred[p] != pred[p]) ++npd;
+    if (u) {
+        std::vector<int> stat((size_t)m);
+        HIPCHK(hipMemcpy(stat.data(), d_stat, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
+        if (u->beta) HIPCHK(hipMemcpy(u->beta, d_beta, (size_t)(m * up * 8), hipMemcpyDeviceToHost));
+        int64_t nrd = 0;
+        nempty = 0;
+        for (int64_t p = 0; p < m; ++p) {
+            if (f0_bad[(size_t)p]) {   // rule 5: NaN, in none of the counters
+                pred[p] = pred_err[p] = NAN;
+                if (u->beta)
+                    for (int j = 0; j < up; ++j) u->beta[p * up + j] = NAN;
+                continue;
+            }
+            nempty += stat[(size_t)p] == CK_LU_EMPTY;
+            npd += stat[(size_t)p] == CK_LU_NOT_PD;
+            nrd += stat[(size_t)p] == CK_LU_RANK_DEF;
+        }
+        if (u->n_rank_def) *u->n_rank_def = nrd;
+        double red_ms = 0.0;
+        for (size_t e = 0; e + 1 < ev_red.size(); e += 2) {
+            float t = 0;
+            HIPCHK(hipEventElapsedTime(&t, ev_red[e], ev_red[e + 1]));
+            red_ms += t;
+        }
+        h->t_ms[48] = ms;                      // the counting pass
+        h->t_ms[49] = (double)ms2 - red_ms;    // assembly and factorisation (the LDS class's kernel whole)
+        h->t_ms[50] = red_ms;                  // the tiled class's universal reduction (Gram matrix + GLS step)
+        h->t_ms[51] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        h->t_ms[52] = (double)(m - (int64_t)tiled.size());   // points of the LDS class (the empty ones among them)
+        h->t_ms[53] = (double)tiled.size();                  // points of the tiled class
+    } else {
+        for (int64_t p = 0; p < m; ++p)
+            if (cnt[p] > 0 && pred[p] != pred[p]) ++npd;
+    }
     if (n_empty) *n_empty = nempty;
     if (n_not_pd) *n_not_pd = npd;
     if (k_max) *k_max = kmx;
     return 0;
+}
+
+extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int64_t m, double max_dist, int cv,
+                                double* pred, double* pred_err, int64_t* n_empty, int64_t* n_not_pd,
+                                int64_t* k_max) {
+    CHKH(h);
+    return predict_local_impl(h, i, pcoords, m, max_dist, cv, pred, pred_err, n_empty, n_not_pd, k_max, nullptr);
+}
+
+// Universal cokriging in the moving neighbourhood: include/cokrige.h has the arithmetic and the rules for degenerate cases;
+// ck_local.hip the kernels.  No trend set: ck_predict_local itself.
+extern "C" int ck_predict_local_universal(ck_handle* h, int i, const double* pcoords, int64_t m, const double* f0, double max_dist,
+                                          int cv, double* pred, double* pred_err, double* beta, int64_t* n_empty,
+                                          int64_t* n_not_pd, int64_t* n_rank_def, int64_t* k_max) {
+    CHKH(h);
+    if (h->world != 1)
+        return fail("ck_predict_local_universal is the single-process form: this handle is partitioned (world = " +
+                    std::to_string(h->world) + ")");
+    if (n_rank_def) *n_rank_def = 0;
+    if (i < 0 || i >= h->n_procs) return fail("process index out of range");
+    if (m > 0 && (!pred || !pred_err)) return fail("ck_predict_local_universal: bad prediction arrays");
+    for (int k = 48; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    if (trend_total(h) == 0)
+        return predict_local_impl(h, i, pcoords, m, max_dist, cv, pred, pred_err, n_empty, n_not_pd, k_max, nullptr);
+    if (m > 0 && h->trend_p[i] > 0 && !f0) return fail("ck_predict_local_universal: null regressors of the prediction sites");
+    const LocalUniv u{f0, beta, n_rank_def};
+    return predict_local_impl(h, i, pcoords, m, max_dist, cv, pred, pred_err, n_empty, n_not_pd, k_max, &u);
 }
 
 // The reference builds the local predictor's state once, in its constructor (src/point_prediction.py:24-43: the full Sigma

@@ -275,9 +275,10 @@ struct CkLocalSys {
 #define CK_LT_BIG 1e200
 #define CK_LT_ROWS(kq) ((kq) + 128)
 #define CK_LT_NINV 8   // inverses of the diagonal blocks of one column group kept side by side (option local_group <= 8)
-static inline long long ck_local_tiled_kq(long long k) { return (k + 2 + 63) / 64 * 64; }
-static inline long long ck_local_tiled_doubles(long long k) {
-    const long long kq = ck_local_tiled_kq(k);
+// p: trend rows of the universal form (below), in [kq - 2 - p, kq - 2) between the identity padding and the c / z rows
+static inline long long ck_local_tiled_kq(long long k, int p = 0) { return (k + 2 + p + 63) / 64 * 64; }
+static inline long long ck_local_tiled_doubles(long long k, int p = 0) {
+    const long long kq = ck_local_tiled_kq(k, p);
     return (CK_LT_ROWS(kq) * (kq + 128) + CK_LT_NINV * 64 * 64 + (k + 1) / 2 + 1) & ~1LL;
 }
 void ck_launch_local_assemble_t(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
@@ -305,3 +306,32 @@ void ck_launch_local_tiled_left(hipStream_t s, const CkLocalSys* sys, double* sl
                                 const int* kq_host);
 void ck_launch_local_reduce_t(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab,
                               const long long* info, double c0var, double* pred, double* err);
+
+// Universal cokriging in the neighbourhood (ck_predict_local_universal): the p = p0 + p1 trend rows X_loc^T ride along each
+// local factorisation like c and z, and a GLS step per point (ck_local_gls.h) follows the reduction.
+//   LDS class (k <= 64): k_local_solve_u, a (k + 2 + p) x k matrix -- rows k (c), k + 1 (z), k + 2 .. (trend) -- in dynamic
+//   LDS sized by p;  tiled class: kq = roundup(k + 2 + p, 64), the trend rows in [kq - 2 - p, kq - 2), each with its own
+//   CK_LT_BIG diagonal entry; the batched factorisation steps are those of the simple form.
+#define CK_LU_PMAX 16   // 2 CK_TREND_PMAX (include/cokrige.h)
+struct CkLocalTrend {
+    const double* X;    // p rows of npad doubles in the internal site order (ck_api.hip: d_trendX)
+    const double* f0;   // m x p_i regressors of the predicted process at the prediction points, finite
+    int p0, p1;         // trend columns of process 0 / process 1
+    double tol;         // relative pivot threshold of the GLS step
+};
+// status[p] of a point (beta: m x p, NaN rows unless CK_LU_OK; dropped columns NaN)
+#define CK_LU_OK 0
+#define CK_LU_EMPTY 1
+#define CK_LU_NOT_PD 2
+#define CK_LU_RANK_DEF 3
+void ck_launch_local_solve_u(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
+                             const double* pc, int64_t m, int64_t mpad, const double* sc, const double* z, CkLayout L,
+                             const int* counts, double c0var, double* pred, double* err, const CkTable* tabs,
+                             const double* const* coefs, int use_tab, const double* su, const double* pu, int k_hi,
+                             const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status);
+// behind ck_launch_local_assemble_t: the trend rows of the batch's systems
+void ck_launch_local_trend_rows_t(hipStream_t s, const CkLocalSys* sys, int n_sys, double* slab, CkLayout L, CkLocalTrend Tr);
+// k0buf: the process-0 neighbour counts ck_launch_local_assemble_t left
+void ck_launch_local_reduce_ut(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab, const long long* info,
+                               const int* k0buf, int i_pred, double c0var, double* pred, double* err, CkLocalTrend Tr,
+                               double* beta, int* status);

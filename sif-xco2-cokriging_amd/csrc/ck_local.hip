@@ -13,6 +13,7 @@
 // Systems with k <= 64 neighbours live in LDS (k_local_solve); larger ones go through the tiled path (batched
 // 64-column steps on the matrix cores, see below) or, if option "local_tile_min" says so, a global scratch slab
 // per point with a blocked factorisation in one workgroup (k_local_solve_big).
+// Universal cokriging in the neighbourhood (a GLS trend per point, ck_predict_local_universal): at the end of this file.
 #include "ck_internal.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
@@ -804,3 +805,256 @@ void ck_launch_local_reduce_t(hipStream_t s, const CkLocalSys* sys, int n_sys, c
 }
 
 int ck_local_lds_limit() { return LP_KL; }
+
+// ---------------------------------------------------------------------------------------
+// universal cokriging in the neighbourhood (ck_predict_local_universal; include/cokrige.h has the rules)
+// ---------------------------------------------------------------------------------------
+// The p trend rows X_loc^T ride along the factorisation as c and z do: behind it they hold U^T = (L^-1 X_loc)^T.  Every
+// kernel then forms the Gram matrix G of the nx = 2 + p solved rows [v; y; U_0 .. U_{p-1}] -- one thread per entry, each a
+// sequential sum over the neighbours: a fixed order, no atomics -- and one thread runs the GLS step (ck_local_gls.h) on it:
+//   G[0][0] = v.v, G[1][0] = v.y, G[2 + j][0] = (U^T v)_j, G[2 + j][1] = b_j, G[2 + j][2 + l] = A_jl.
+// Work area E (LDS): G nx nx | W p p + 2 p | bb p | rr p | bl p doubles.
+#include "ck_local_gls.h"
+
+#define LU_EXTRA(p) (((p) + 2) * ((p) + 2) + (p) * (p) + 5 * (p))
+#define LU_NPAIR(nx) ((nx) * ((nx) + 1) / 2)
+
+__device__ __forceinline__ void lu_fill_nan(long p, int np, double* __restrict__ pred, double* __restrict__ err,
+                                            double* __restrict__ beta, int* __restrict__ status, int code) {
+    pred[p] = NAN;
+    err[p] = NAN;
+    status[p] = code;
+    if (beta)
+        for (int j = 0; j < np; ++j) beta[p * np + j] = NAN;
+}
+
+// entry e of the lower triangle -> (r, c), r >= c (e < 171: exact in the few steps below)
+__device__ __forceinline__ void lu_pair(int e, int* r, int* c) {
+    int a = 0;
+    while ((a + 1) * (a + 2) / 2 <= e) ++a;
+    *r = a;
+    *c = e - a * (a + 1) / 2;
+}
+
+// one thread: r = x0 - U^T v, the GLS step, the outputs of point p
+__device__ __forceinline__ void lu_finish(double* E, CkLocalTrend Tr, int i_pred, int k0, int k1, long p, double c0var,
+                                          double* __restrict__ pred, double* __restrict__ err, double* __restrict__ beta,
+                                          int* __restrict__ status) {
+    const int np = Tr.p0 + Tr.p1, nx = np + 2;
+    double *G = E, *W = G + nx * nx, *bb = W + np * np + 2 * np, *rr = bb + np, *bl = rr + np;
+    const int pi = i_pred == 0 ? Tr.p0 : Tr.p1, offi = i_pred == 0 ? 0 : Tr.p0;
+    for (int j = 0; j < np; ++j) {
+        bb[j] = G[(2 + j) * nx + 1];
+        const double x0 = (j >= offi && j < offi + pi) ? Tr.f0[p * pi + (j - offi)] : 0.0;
+        rr[j] = x0 - G[(2 + j) * nx];
+    }
+    double rb, rar;
+    if (ck_local_gls(Tr.p0, Tr.p1, k0, k1, i_pred, G + 2 * nx + 2, nx, bb, rr, Tr.tol, W, bl, &rb, &rar) != CK_LG_OK) {
+        lu_fill_nan(p, np, pred, err, beta, status, CK_LU_RANK_DEF);
+        return;
+    }
+    pred[p] = G[nx] + rb;
+    const double sd = sqrt(c0var - G[0] + rar);
+    err[p] = (sd == sd) ? fmax(sd, 0.0) : 0.0;
+    status[p] = CK_LU_OK;
+    if (beta)
+        for (int j = 0; j < np; ++j) beta[p * np + j] = bl[j];
+}
+
+// LDS class: k_local_solve with k + 2 + p rows (c, z, then the trend rows); dynamic LDS sized by p
+__global__ __launch_bounds__(LP_TPB) void k_local_solve_u(const CkMatern* __restrict__ blk, int metric, int i_pred, int cv,
+                                                           double max_dist, const double* __restrict__ pc, long mpad,
+                                                           const double* __restrict__ sc, const double* __restrict__ z,
+                                                           CkLayout L, const int* __restrict__ counts, double c0var,
+                                                           double* __restrict__ pred, double* __restrict__ err, LpTab T,
+                                                           const double* __restrict__ su, const double* __restrict__ pu,
+                                                           LpSearch R, int k_hi, CkLocalTrend Tr, double* __restrict__ beta,
+                                                           int* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) double lu_lds[];   // (LP_KL + nx) x LP_KL matrix | LU_EXTRA(p)
+    __shared__ int lidx[LP_KL];
+    __shared__ int wsum[LP_TPB / 64], wsum0[LP_TPB / 64];
+    __shared__ int fail;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int np = Tr.p0 + Tr.p1, nx = np + 2;
+    const long p = blockIdx.x;
+    const int k = counts[p];
+    if (k == 0) {
+        if (tid == 0) lu_fill_nan(p, np, pred, err, beta, status, CK_LU_EMPTY);
+        return;
+    }
+    if (k > LP_KL || k > k_hi) return;   // the tiled path
+    const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
+    const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
+    const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;
+    const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
+    double* S = lu_lds;
+    double* E = lu_lds + (LP_KL + nx) * LP_KL;
+    int* idx = lidx;
+    const long ld = LP_KL;
+    // ---- 1. neighbour list, in site order; k0 = neighbours of process 0 ----
+    if (tid == 0) fail = 0;
+    int base = 0, k0 = 0;
+    for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
+        if (lp_chunk_far(R, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
+        const long g = g0 + tid;
+        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, max_dist, L, g, p0, p1, p2, s0, s1, s2);
+        const unsigned long long bal = __ballot(f), bal0 = __ballot(f && g < L.n0p);
+        const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
+        if (lane == 0) {
+            wsum[wv] = __popcll(bal);
+            wsum0[wv] = __popcll(bal0);
+        }
+        __syncthreads();
+        int off = base;
+        for (int w2 = 0; w2 < wv; ++w2) off += wsum[w2];
+        if (f) idx[off + below] = (int)g;
+        for (int w2 = 0; w2 < LP_TPB / 64; ++w2) {
+            base += wsum[w2];
+            k0 += wsum0[w2];
+        }
+        __syncthreads();
+    }
+    // ---- 2. local covariance (lower triangle), c row, z row, trend rows ----
+    const long npair = (long)k * (k + 1) / 2;
+    for (long e = tid; e < npair; e += LP_TPB) {
+        long a = (long)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
+        while (a * (a + 1) / 2 > e) --a;
+        while ((a + 1) * (a + 2) / 2 <= e) ++a;
+        const long b = e - a * (a + 1) / 2;
+        const long ga = idx[a], gb = idx[b];
+        const int pa = ga >= L.n0p, pb = gb >= L.n0p;
+        S[a * ld + b] = lp_cov(blk, T, pa + pb, pa == pb, metric, s0[ga], s1[ga], s2[ga], u0[ga], u1[ga], u2[ga], s0[gb],
+                               s1[gb], s2[gb], u0[gb], u1[gb], u2[gb]);
+    }
+    for (int a = tid; a < k; a += LP_TPB) {
+        const long ga = idx[a];
+        const int pa = ga >= L.n0p;
+        S[(long)k * ld + a] = lp_cov(blk, T, i_pred + pa, pa == i_pred, metric, p0, p1, p2, q0, q1, q2, s0[ga], s1[ga],
+                                     s2[ga], u0[ga], u1[ga], u2[ga]);
+        S[(long)(k + 1) * ld + a] = z[ga];
+    }
+    for (int e = tid; e < np * k; e += LP_TPB) {
+        const int j = e / k, a = e - j * k;
+        S[(long)(k + 2 + j) * ld + a] = Tr.X[(long)j * L.npad + idx[a]];
+    }
+    __syncthreads();
+    // ---- 3. Cholesky of the k x k block, the nx extra rows ride along (forward substitution) ----
+    for (int j = 0; j < k; ++j) {
+        const double piv = S[(long)j * ld + j];
+        if (!(piv > 0.0)) {
+            if (tid == 0) fail = 1;
+            break;   // uniform: every thread reads the same pivot
+        }
+        const double rd = 1.0 / sqrt(piv);
+        __syncthreads();
+        for (int a = j + 1 + tid; a < k + nx; a += LP_TPB) S[(long)a * ld + j] *= rd;
+        if (tid == 0) S[(long)j * ld + j] = sqrt(piv);
+        __syncthreads();
+        const int nb = k - 1 - j;            // columns b = j + 1 .. k - 1
+        const int na = k + nx - 1 - j;       // rows    a = j + 1 .. k + nx - 1
+        const long tot = (long)na * nb;
+        for (long e = tid; e < tot; e += LP_TPB) {
+            const int a = j + 1 + (int)(e / nb), b = j + 1 + (int)(e % nb);
+            if (b <= a) S[(long)a * ld + b] -= S[(long)a * ld + j] * S[(long)b * ld + j];
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    if (fail) {
+        if (tid == 0) lu_fill_nan(p, np, pred, err, beta, status, CK_LU_NOT_PD);
+        return;
+    }
+    // ---- 4. Gram matrix of the solved rows, then the GLS step ----
+    if (tid < LU_NPAIR(nx)) {
+        int r, c;
+        lu_pair(tid, &r, &c);
+        const double *xr = S + (long)(k + r) * ld, *xc = S + (long)(k + c) * ld;
+        double acc = 0.0;
+        for (int a = 0; a < k; ++a) acc += xr[a] * xc[a];
+        E[r * nx + c] = acc;
+    }
+    __syncthreads();
+    if (tid == 0) lu_finish(E, Tr, i_pred, k0, k - k0, p, c0var, pred, err, beta, status);
+}
+
+void ck_launch_local_solve_u(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
+                             const double* pc, int64_t m, int64_t mpad, const double* sc, const double* z, CkLayout L,
+                             const int* counts, double c0var, double* pred, double* err, const CkTable* tabs,
+                             const double* const* coefs, int use_tab, const double* su, const double* pu, int k_hi,
+                             const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status) {
+    if (m <= 0) return;
+    const LpTab T{tabs, coefs, use_tab};
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax};
+    const int np = Tr.p0 + Tr.p1;
+    const size_t lds = (size_t)((LP_KL + 2 + np) * LP_KL + LU_EXTRA(np)) * sizeof(double);   // 34.9 KB (p = 2) .. 47.2 KB (p = 16)
+    k_local_solve_u<<<dim3((unsigned)m), dim3(LP_TPB), lds, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L, counts,
+                                                                 c0var, pred, err, T, su, pu, R, k_hi, Tr, beta, status);
+}
+
+// Tiled class: behind k_local_search_t (which has written identity rows up to kq - 2) the p rows [kq - 2 - p, kq - 2)
+// become the trend rows -- X_loc^T in the columns [0, k), CK_LT_BIG on the diagonal, the zeros in between stay
+__global__ __launch_bounds__(LP_TPB) void k_local_trend_rows_t(const CkLocalSys* __restrict__ sys, double* __restrict__ slab,
+                                                                CkLayout L, CkLocalTrend Tr) {
+    const CkLocalSys q = sys[blockIdx.x];
+    const int np = Tr.p0 + Tr.p1, t0 = q.kq - 2 - np;
+    double* S = slab + q.off;
+    const int* idx = reinterpret_cast<const int*>(S + (long)CK_LT_ROWS(q.kq) * q.ld + CK_LT_NINV * 64 * 64);
+    for (int j = 0; j < np; ++j) {
+        double* row = S + (long)(t0 + j) * q.ld;
+        for (int a = threadIdx.x; a < q.k; a += LP_TPB) row[a] = Tr.X[(long)j * L.npad + idx[a]];
+        if (threadIdx.x == 0) row[t0 + j] = CK_LT_BIG;
+    }
+}
+
+// the solved rows dotted with [y; U] (64 columns at a time through LDS), then the GLS step
+__global__ __launch_bounds__(LP_TPB) void k_local_reduce_ut(const CkLocalSys* __restrict__ sys, const double* __restrict__ slab,
+                                                             const long long* __restrict__ info, const int* __restrict__ k0in,
+                                                             int i_pred, double c0var, double* __restrict__ pred,
+                                                             double* __restrict__ err, CkLocalTrend Tr, double* __restrict__ beta,
+                                                             int* __restrict__ status) {
+    __shared__ double tile[2 + CK_LU_PMAX][65];
+    __shared__ double E[LU_EXTRA(CK_LU_PMAX)];
+    const int tid = threadIdx.x;
+    const int np = Tr.p0 + Tr.p1, nx = np + 2;
+    const CkLocalSys q = sys[blockIdx.x];
+    if (info[blockIdx.x] != 0) {
+        if (tid == 0) lu_fill_nan(q.p, np, pred, err, beta, status, CK_LU_NOT_PD);
+        return;
+    }
+    const double* S = slab + q.off;
+    int r = 0, c = 0;
+    if (tid < LU_NPAIR(nx)) lu_pair(tid, &r, &c);
+    double acc = 0.0;
+    for (int a0 = 0; a0 < q.k; a0 += 64) {
+        const int na = min(64, q.k - a0);
+        __syncthreads();
+        for (int e = tid; e < nx * 64; e += LP_TPB) {
+            const int rr = e >> 6, a = e & 63;
+            // row 0: v (kq - 2), row 1: y (kq - 1), rows 2 ..: the trend rows
+            const int row = rr < 2 ? q.kq - 2 + rr : q.kq - 2 - np + (rr - 2);
+            tile[rr][a] = a < na ? S[(long)row * q.ld + a0 + a] : 0.0;
+        }
+        __syncthreads();
+        if (tid < LU_NPAIR(nx))
+            for (int a = 0; a < na; ++a) acc += tile[r][a] * tile[c][a];
+    }
+    if (tid < LU_NPAIR(nx)) E[r * nx + c] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        const int k0 = k0in[blockIdx.x];
+        lu_finish(E, Tr, i_pred, k0, q.k - k0, q.p, c0var, pred, err, beta, status);
+    }
+}
+
+void ck_launch_local_trend_rows_t(hipStream_t s, const CkLocalSys* sys, int n_sys, double* slab, CkLayout L, CkLocalTrend Tr) {
+    if (n_sys <= 0) return;
+    k_local_trend_rows_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(sys, slab, L, Tr);
+}
+
+void ck_launch_local_reduce_ut(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab, const long long* info,
+                               const int* k0buf, int i_pred, double c0var, double* pred, double* err, CkLocalTrend Tr, double* beta,
+                               int* status) {
+    if (n_sys <= 0) return;
+    k_local_reduce_ut<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(sys, slab, info, k0buf, i_pred, c0var, pred, err, Tr, beta,
+                                                                     status);
+}

@@ -71,6 +71,8 @@ _PROTOS = {
     "ck_predict_local": [c_void_p, c_int, _dp, c_int64, c_double, c_int, _dp, _dp, POINTER(c_int64), POINTER(c_int64),
                          POINTER(c_int64)],
     "ck_local_reserve": [c_void_p, c_int64],
+    "ck_predict_local_universal": [c_void_p, c_int, _dp, c_int64, _dp, c_double, c_int, _dp, _dp, _dp, POINTER(c_int64),
+                                   POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
     "ck_vario_begin": [c_void_p, _dp, _dp, c_int64, _dp, _dp, c_int64, c_int],
     "ck_vario_extent": [c_void_p, c_double, _dp, _dp, POINTER(c_int64)],
     "ck_vario_bin": [c_void_p, c_double, _dp, c_int, c_int, _dp, POINTER(c_int64)],
@@ -550,6 +552,38 @@ class Handle:
         _chk(lib().ck_predict_local(self._h, int(i), _p(pc), m, float(max_dist), int(bool(cv)), _p(pred), _p(err),
                                     byref(ne), byref(npd), byref(km)))
         return pred, err, dict(n_empty=ne.value, n_not_pd=npd.value, k_max=km.value)
+
+    def predict_local_universal(self, i, pcoords, f0=None, max_dist=1e3, cv=False, want_beta=False):
+        """Universal cokriging of process i in the moving neighbourhood, with the trend of set_trend (include/cokrige.h:
+        ck_predict_local_universal).  f0: (m, p_i) regressors of process i at pcoords; a row with a non-finite entry gives
+        NaN.  Returns (pred, err, info) with n_empty, n_not_pd, n_rank_def, k_max and, with ``want_beta``, beta (m, p): every
+        site's local GLS coefficients.  Without a trend (p = 0) the predict_local result."""
+        pc = _f64(pcoords, 2)
+        m = pc.shape[0]
+        p = sum(self._trend_p.values())
+        pi = self._trend_p.get(int(i), 0)
+        F0 = None
+        if pi > 0:
+            F0 = _f64(np.zeros((m, 0)) if f0 is None else f0)
+            if F0.shape != (m, pi):
+                raise ValueError(f"f0 has shape {F0.shape}, expected {(m, pi)}")
+        pred, err = np.empty(m), np.empty(m)
+        beta = np.full((m, p), np.nan) if want_beta else None
+        ne, npd, nrd, km = c_int64(0), c_int64(0), c_int64(0), c_int64(0)
+        _chk(lib().ck_predict_local_universal(self._h, int(i), _p(pc), m, _p(F0) if F0 is not None else None, float(max_dist),
+                                              int(bool(cv)), _p(pred), _p(err), _p(beta) if want_beta and p else None,
+                                              byref(ne), byref(npd), byref(nrd), byref(km)))
+        info = dict(n_empty=ne.value, n_not_pd=npd.value, n_rank_def=nrd.value, k_max=km.value)
+        if want_beta:
+            info["beta"] = beta
+        return pred, err, info
+
+    def local_universal_timings(self):
+        """ck_timings [48 ..] of the last predict_local_universal() call (milliseconds; the last two are counts)."""
+        out = np.zeros(54)
+        _chk(lib().ck_timings(self._h, _p(out), 54))
+        keys = ["count_ms", "factor_ms", "reduce_ms", "total_ms", "n_lds", "n_tiled"]
+        return dict(zip(keys, out[48:54].tolist()))
 
     def local_reserve(self, nbytes: int = 0):
         """Pre-size the scratch slab of predict_local (0: the automatic budget) -- include/cokrige.h: ck_local_reserve."""

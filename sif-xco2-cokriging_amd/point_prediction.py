@@ -11,7 +11,9 @@ Differences from the reference, none in the arithmetic:
   * ``partitions`` (a ``multiprocessing.Pool`` in the reference, :69-81) is accepted and ignored:
     the prediction points are already processed in parallel;
   * the reference warns once per affected point (:219-221, 230-232); here one warning per
-    call and kind, carrying the number of points.
+    call and kind, carrying the number of points;
+  * ``trend=`` (not in the reference): ordinary / universal cokriging in the moving neighbourhood -- the unknown mean is
+    estimated by GLS in every neighbourhood and its uncertainty is part of ``pred_err``.
 """
 from __future__ import annotations
 
@@ -25,18 +27,30 @@ from .fields import metric_of
 from .joint_prediction import Predictor as _JointPredictor
 from .joint_prediction import prediction_coords, xr  # noqa: F401  (same helper, same signature)
 from .model import configure_handle
+from .trend import TrendDesign, check_trend
 
 
 class Predictor:
     """Multivariate prediction framework (src/point_prediction.py:21-43)."""
 
     def __init__(self, mod, mf, covariates=None, dist_units: str = "km", fast_dist: bool = True, device: int = 0,
-                 devices=None, reserve_scratch=None):
+                 devices=None, reserve_scratch=None, trend=None):
         """``devices=[0, 1, ...]``: the prediction points are sharded over one worker process per GPU (observations
         replicated, no exchange inside the computation) -- what ``partitions`` is to the reference's CPU pool
-        (src/point_prediction.py:45-52, 69-81)."""
+        (src/point_prediction.py:45-52, 69-81).
+
+        ``trend``: None (simple cokriging: a known zero mean in every neighbourhood), ``"constant"`` (ordinary cokriging in
+        the moving window), ``"linear"`` or a callable ``f(k, coords) -> (n, p_k)``, as for the joint predictor.  The trend
+        is estimated by GLS in every neighbourhood (include/cokrige.h: ck_predict_local_universal); a site whose
+        neighbourhood cannot carry it (rank deficient), or whose regressors are not finite, gets NaN.  After a call
+        ``trend_coef`` holds the (m, p) local coefficients."""
         if mod.n_procs != mf.n_procs:
             raise ValueError("Number of theoretical processes different from empirical processes.")
+        self.trend = check_trend(trend)
+        if self.trend is not None and devices is not None and len(devices) > 1:
+            raise NotImplementedError("universal cokriging (trend=...) runs on one device; the multi-GPU path is simple "
+                                      "cokriging only")
+        self.trend_coef = None
         self.n_procs = mod.n_procs
         self.mod, self.mf, self.covariates = mod, mf, covariates
         self.dist_units, self.fast_dist = dist_units, fast_dist
@@ -99,8 +113,27 @@ class Predictor:
             self._pool_key = key
         return self._pool.predict_local(i, pcoords, max_dist=max_dist, cv=self.cv)
 
+    def _predict_universal(self, i, pcoords, max_dist):
+        """The regressors of the data and the prediction sites are validated on the host, then set on the handle (a new
+        trend needs no new device state)."""
+        if not 0 <= int(i) < self.n_procs:
+            raise ValueError(f"process index {i!r} out of range for {self.n_procs} processes")
+        coords = [np.asarray(self.mf.fields[k].coords_main, dtype=np.float64)[:, :2] for k in range(self.n_procs)]
+        design = TrendDesign(self.trend, coords)
+        F = [design.data(k, coords[k]) for k in range(self.n_procs)]
+        pc = np.ascontiguousarray(np.atleast_2d(np.asarray(pcoords, dtype=np.float64))[:, :2])
+        F0 = design(i, pc)
+        h = self._handle()
+        for k in range(self.n_procs):
+            h.set_trend(k, F[k])
+        pred, err, info = h.predict_local_universal(i, pc, F0, max_dist=max_dist, cv=self.cv, want_beta=True)
+        self.trend_coef = info.pop("beta")
+        return pred, err, info
+
     def predict_arrays(self, i: int, pcoords, max_dist: float = 1e3):
-        if self.devices is not None and len(self.devices) > 1:
+        if self.trend is not None:
+            pred, err, info = self._predict_universal(i, pcoords, max_dist)
+        elif self.devices is not None and len(self.devices) > 1:
             pred, err, info = self._predict_on_ranks(i, pcoords, max_dist)
         else:
             pred, err, info = self._handle().predict_local(i, pcoords, max_dist=max_dist, cv=self.cv)
@@ -110,6 +143,9 @@ class Predictor:
         if info["n_not_pd"]:
             warnings.warn(f"Local covariance matrix not positive definte at {info['n_not_pd']} location(s);"
                           " returning NaN.")
+        if info.get("n_rank_def"):
+            warnings.warn(f"Trend not estimable from the data within maximum distance {max_dist} at {info['n_rank_def']}"
+                          " location(s); returning NaN. Use a larger max_dist or a smaller trend.")
         return pred, err
 
     def __call__(self, i: int, pcoords: pd.DataFrame, max_dist: float = 1e3, partitions: int = None,
