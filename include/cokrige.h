@@ -166,6 +166,36 @@ int ck_predict_blocks(ck_handle* h, int i, const double* pcoords_host, int64_t m
  * each.  Needs ck_factor. */
 int ck_loocv(ck_handle* h, int i, double* pred_host, double* pred_err_host);
 
+/* Leave-group-out cross-validation of process i from ONE factorisation: fold f withholds every datum of EITHER process
+ * labelled f -- a track, a spatial block, a random tenth (K-fold), a datum together with its co-located partner -- and the
+ * withheld data of process i are predicted from all the rest.  With S the withheld positions, Q = Sigma^-1, alpha = Sigma^-1 z:
+ *     E[z_S | z_rest] = z_S - Q_SS^-1 alpha_S,      Cov[z_S | z_rest] = Q_SS^-1
+ * (ck_loocv is the case of singleton folds).  With W = the solved unit right-hand-side rows (row of site a = (L^-1 e_a)^T) and
+ * y = L^-1 z:  Q_SS = W_S W_S^T, alpha_S = W_S y -- one sweep of the unit rows, the Gram matrices of the folds' rows, one small
+ * dense solve per fold.
+ * Inputs: fold_k[a], in the caller's order of ck_set_data of process k, is the fold of datum a; -1: never withheld.
+ * fold1_host may be NULL (nothing of the other process is withheld); the array of the predicted process must not be.  With
+ * one process the other array is ignored.  Every fold in [0, n_folds) must hold at least one datum of process i.
+ * Outputs: pred / pred_err: n_i values in the caller's order, pred_q = z_q - (Q_SS^-1 alpha_S)_q, pred_err_q =
+ * nan_to_num(sqrt((Q_SS^-1)_qq)); NaN for a datum labelled -1.  fold_stats: n_folds x 3 row-major, or NULL: [0] the fold's
+ * size (both processes counted), [1] log|Q_SS|, [2] alpha_S^T Q_SS^-1 alpha_S -- the joint negative log predictive density of
+ * the withheld values is 1/2 (s log 2 pi - [1] + [2]).  info: 0, or 1 + the index of the first fold whose Q_SS failed to factor;
+ * that fold's outputs are NaN, the other folds are valid, and the call returns 0.
+ * Device path: right-hand sides in ck_loocv's layout (row 0 = z, unit rows in the internal site order) from the first withheld
+ * internal position to the last (fold1_host NULL: ck_loocv's rows of process i), swept on the growing prefix of live rows;
+ * every fold's lower triangle of Q_SS in ONE launch on the matrix cores, the rows gathered by index (a tile map over the
+ * within-fold tiles only, each tile starting at the panel of its first position: sum_f s_f^2 N work); folds of up to 64
+ * members solved in LDS, one workgroup each; larger ones batched, 64 columns per step, with the updates on the matrix cores.
+ * Every reduction has a fixed order and there are no atomics: repeated calls give the same bits.
+ * Single-process form, needs ck_factor.  Refused through ck_last_error, with the amounts and the fold: a label outside
+ * [-1, n_folds), an empty fold, a fold of more than CK_FOLD_MAX data, too little device memory ((pmax - pmin + 2 rounded up to
+ * 256) rows of Npad doubles, 128 x 128 doubles per tile of small folds and (2 s + 192)^2 doubles per larger fold of s data).
+ * Afterwards the handle is as after ck_loocv: the factor stays resident, ck_predict gives the same bits as without the call;
+ * ck_verify_model / ck_aux_finish refuse until the next ck_predict / ck_aux_begin.  ck_timings [56 ..] describe the call. */
+#define CK_FOLD_MAX 4096
+int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0_host, const int32_t* fold1_host, int32_t n_folds, double* pred_host,
+                double* pred_err_host, double* fold_stats_host, int64_t* info);
+
 /* Gaussian log-likelihood of the data of every process under the model (zero mean, as simple cokriging), with Sigma assembled
  * exactly as ck_assemble_joint builds it (same metric, table path, nugget rule at h == 0):
  *     l = -1/2 (N log 2 pi + log|Sigma| + z^T Sigma^-1 z),   out3 = (l, log|Sigma|, z^T Sigma^-1 z).
@@ -469,7 +499,9 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * ck_predict_local_universal (n up to 54): [48] the counting pass; [49] assembly and factorisation of both size classes (the
  * LDS class's kernel whole, its reduction included); [50] the tiled class's universal reduction (Gram matrix of the solved
  * rows and the GLS step), summed over the batches; [51] host wall clock of the call; [52] / [53] number of points in the LDS
- * class (empty neighbourhoods included) / in the tiled class. */
+ * class (empty neighbourhoods included) / in the tiled class.
+ * ck_cv_folds (n up to 60): [56] the unit rows and their sweep; [57] alpha = W y and the folds' Gram matrices (k_fold_gram);
+ * [58] the fold solves of both size classes; [59] host wall clock of the call. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it

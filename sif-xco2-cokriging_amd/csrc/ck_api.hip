@@ -32,7 +32,7 @@
 #include "ck_model.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 56
+#define CK_N_TIMINGS 60
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -1849,6 +1849,7 @@ extern "C" int ck_aux_finish(ck_handle* h, double* pred, double* pred_err) {
     if (h->aux_state == 3) return fail("ck_aux_finish: the last call was ck_predict_blocks; call ck_aux_begin first");
     if (h->aux_state == 4) return fail("ck_aux_finish: the last call was ck_loglik; call ck_aux_begin first");
     if (h->aux_state == 5) return fail("ck_aux_finish: the last call was ck_predict_universal; call ck_aux_begin first");
+    if (h->aux_state == 6) return fail("ck_aux_finish: the last call was ck_cv_folds; call ck_aux_begin first");
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     const double c0 = h->blk[2 * h->i_pred].amp + h->blk[2 * h->i_pred].nugget;   // sigma_i^2 + nugget_i (model.py:194-196 at h = 0)
     ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, h->m, h->m, c0, h->d_pred, h->d_err);
@@ -2207,6 +2208,9 @@ extern "C" int ck_verify_model(ck_handle* h, int64_t* info) {
     if (h->aux_state == 5)
         return fail("ck_verify_model: the last call was ck_predict_universal, for which the simple-kriging verdict does not apply; "
                     "call ck_predict with the sites to check first");
+    if (h->aux_state == 6)
+        return fail("ck_verify_model: the last call was ck_cv_folds, whose right-hand sides are the withheld data's unit rows; call "
+                    "ck_predict with the sites to check first");
     if (h->aux_state != 2) return fail("ck_verify_model needs the solved right-hand sides of a preceding ck_predict");
     const int64_t m = h->m;
     *info = 0;
@@ -2729,6 +2733,197 @@ extern "C" int ck_loocv(ck_handle* h, int i, double* pred, double* pred_err) {
         const double e = sqrt(1.0 / s2[q]);
         pred_err[x] = (e == e) ? e : 0.0;
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// leave-group-out cross-validation from ONE factorisation
+// ---------------------------------------------------------------------------------------
+// ck_loocv's identity for a set S of withheld positions (any mix of both processes): with Q = Sigma^-1 and alpha = Sigma^-1 z
+//     E[z_S | z_rest] = z_S - Q_SS^-1 alpha_S,      Cov[z_S | z_rest] = Q_SS^-1,
+// and with W = the solved unit rows (row of site a = (L^-1 e_a)^T), y = L^-1 z:  Q_SS = W_S W_S^T, alpha_S = W_S y.
+//   1. right-hand sides in ck_loocv's layout for the internal positions pmin .. pmax of the withheld data (row 0 = z, row
+//      1 + p = unit vector of position pmin + p), swept on the growing prefix of live rows;
+//   2. alpha = W y for every row (k_reduce_pred, raw mode) and the folds' Gram matrices on the matrix cores (k_fold_gram: one
+//      launch over the tile map of ck_host_fold_plan);
+//   3. the fold solves: k_fold_small in LDS for folds of up to 64 members; larger folds as systems of the local predictor's
+//      batched Cholesky steps, left-looking, stopped behind the largest fold's last column (ck_folds.hip).
+static_assert(CK_FOLD_MAX == CK_HOST_FOLD_MAX, "include/cokrige.h and ck_host.h disagree about the largest fold");
+static_assert(CK_LT_NINV * 64 * 64 == 8 * 64 * 64 && CK_LT_ROWS(64) == 64 + 128, "ck_host_fold_plan sizes the big folds' systems");
+extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int32_t* fold1, int32_t n_folds, double* pred,
+                           double* pred_err, double* fold_stats, int64_t* info) {
+    CHKH(h);
+    if (h->world != 1) return fail("ck_cv_folds is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) + ")");
+    if (!h->factored) return fail("ck_cv_folds: ck_factor has not been called");
+    if (i < 0 || i >= h->n_procs) return fail("ck_cv_folds: process index out of range");
+    if (!pred || !pred_err || !info) return fail("ck_cv_folds: null argument");
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!(i == 0 ? fold0 : fold1))
+        return fail("ck_cv_folds: the fold labels of the predicted process " + std::to_string(i) + " are null");
+    CkFoldPlan plan;
+    if (ck_host_fold_plan(i, h->n_procs, h->n, h->n0p, h->perm[0].data(), h->n_procs == 2 ? h->perm[1].data() : nullptr, fold0, fold1,
+                          n_folds, CK_FOLD_MAX, &plan))
+        return -1;
+    const int64_t ni = h->n[i];
+    const int64_t Np = h->Npad;
+    const int64_t m = plan.pmax - plan.pmin + 1;   // unit rows: every internal position from the first withheld one to the last
+    const int64_t mpad_need = roundup(m + 1 + h->aux_trend, CK_AUX_ALIGN);
+    if (mpad_need * CK_NB * 8 >= (1LL << 31))
+        return fail("ck_cv_folds: " + std::to_string(m) + " unit rows are too many for the Gram kernel's 32-bit row offsets (at most " +
+                    std::to_string((1LL << 31) / (CK_NB * 8) - CK_AUX_ALIGN) + ")");
+    const int64_t ng = (int64_t)plan.gpos.size();
+    const int nbig = (int)plan.big.size();
+    // Everything of the call besides the right-hand sides is carved from the handle's scratch slab (the one ck_predict_local
+    // keeps between calls): the folds' Gram matrices and systems first, then the outputs and the index tables.
+    int64_t slab_bytes = 0;
+    auto carve = [&](size_t bytes) {
+        const int64_t at = slab_bytes;
+        slab_bytes += (int64_t)((bytes + 255) / 256 * 256);
+        return at;
+    };
+    const int64_t buf_bytes = plan.buffer_doubles * 8;
+    const int64_t o_buf = carve((size_t)buf_bytes), o_x = carve((size_t)ng * 8), o_d = carve((size_t)ng * 8),
+                  o_stat = carve((size_t)n_folds * 16), o_linfo = carve((size_t)nbig * sizeof(long long)),
+                  o_tiles = carve(plan.tiles.size() * sizeof(CkFoldTile)), o_small = carve(plan.small.size() * sizeof(CkFoldSmall)),
+                  o_big = carve((size_t)nbig * sizeof(CkFoldBig)), o_sys = carve((size_t)nbig * sizeof(CkLocalSys)),
+                  o_grow = carve((size_t)ng * sizeof(int)), o_fail = carve((size_t)n_folds * sizeof(int));
+    const long long slab_doubles = slab_bytes / 8;
+    {   // device memory: the right-hand sides and the slab, as far as they have to grow
+        const int64_t aux_bytes = mpad_need * Np * 8;
+        const bool grow = aux_bytes > h->aux_cap * 8, grow_slab = slab_doubles > h->local_slab_doubles;
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        int64_t avail = (int64_t)fr;
+        if (!h->arena && grow) avail += h->aux_cap * 8;       // released before the larger one is taken
+        if (grow_slab) avail += h->local_slab_doubles * 8;   // likewise
+        if (h->arena && grow && aux_bytes > h->arena_size - h->arena_used)
+            return fail("ck_cv_folds needs " + std::to_string(aux_bytes) + " bytes of the arena for its " + std::to_string(m + 1) +
+                        " right-hand-side rows of " + std::to_string(Np) + " doubles; " + std::to_string(h->arena_size - h->arena_used) +
+                        " bytes are left");
+        const int64_t need = (grow && !h->arena ? aux_bytes : 0) + (grow_slab ? slab_bytes : 0);
+        if (need > avail)
+            return fail("ck_cv_folds needs " + std::to_string(need) + " bytes of device memory (" + std::to_string(grow ? aux_bytes : 0) +
+                        " for " + std::to_string(m + 1) + " right-hand-side rows of " + std::to_string(Np) + " doubles, " +
+                        std::to_string(buf_bytes) + " for the Gram matrices and systems of " + std::to_string(n_folds) + " folds, " +
+                        std::to_string(slab_bytes - buf_bytes) + " for their outputs and index tables); " + std::to_string(avail) +
+                        " bytes are available");
+    }
+    *info = 0;
+    for (int64_t a = 0; a < ni; ++a) pred[a] = pred_err[a] = NAN;
+    for (int k = 56; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    auto elapsed = [&](hipEvent_t a, hipEvent_t b) {
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, a, b);
+        return (double)ms;
+    };
+    struct Guard {
+        ck_handle* h;
+        ~Guard() {
+            h->aux_state = 6;
+            h->loo_g0 = -1;
+        }
+    } guard{h};
+    // ---- 1. rows and sweep
+    if (aux_begin_impl(h, i, nullptr, m, false)) return -1;
+    h->aux_state = 6;
+    if (slab_doubles > h->local_slab_doubles) {   // outside the timed stages: only the first call of a layout allocates
+        if (h->local_slab) (void)hipFree(h->local_slab);
+        h->local_slab = nullptr;
+        h->local_slab_doubles = 0;
+        HIPCHK(hipMalloc((void**)&h->local_slab, (size_t)slab_bytes));
+        h->local_slab_doubles = slab_doubles;
+    }
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    HIPCHK(hipMemsetAsync(h->aux, 0, (size_t)h->mpad * Np * 8, h->stream));
+    h->loo_g0 = plan.pmin;
+    ck_launch_loo_rows(h->stream, h->aux, h->mpad, m, h->loo_g0, h->z, Np);
+    const int rc = solve_sweep(h);
+    h->loo_g0 = -1;
+    if (rc) return -1;
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    // ---- 2. alpha and the Gram matrices
+    std::vector<int> grow((size_t)ng);
+    for (int64_t g = 0; g < ng; ++g) grow[(size_t)g] = (int)(1 + plan.gpos[(size_t)g] - plan.pmin);
+    std::vector<CkLocalSys> sysv((size_t)nbig);
+    std::vector<int> kqv((size_t)nbig);
+    for (int y = 0; y < nbig; ++y) {
+        const CkFoldBig& b = plan.big[(size_t)y];
+        sysv[(size_t)y] = CkLocalSys{b.off, b.s, b.kq, b.ld, b.gbase};
+        kqv[(size_t)y] = b.kq;
+    }
+    char* const slab = (char*)h->local_slab;
+    double *d_buf = (double*)(slab + o_buf), *d_x = (double*)(slab + o_x), *d_d = (double*)(slab + o_d),
+           *d_stat = (double*)(slab + o_stat);
+    long long* d_linfo = (long long*)(slab + o_linfo);
+    CkFoldTile* d_tiles = (CkFoldTile*)(slab + o_tiles);
+    CkFoldSmall* d_small = (CkFoldSmall*)(slab + o_small);
+    CkFoldBig* d_big = (CkFoldBig*)(slab + o_big);
+    CkLocalSys* d_sys = (CkLocalSys*)(slab + o_sys);
+    int *d_grow = (int*)(slab + o_grow), *d_fail = (int*)(slab + o_fail);
+    HIPCHK(hipMemcpyAsync(d_grow, grow.data(), (size_t)ng * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_tiles, plan.tiles.data(), plan.tiles.size() * sizeof(CkFoldTile), hipMemcpyHostToDevice, h->stream));
+    if (!plan.small.empty())
+        HIPCHK(hipMemcpyAsync(d_small, plan.small.data(), plan.small.size() * sizeof(CkFoldSmall), hipMemcpyHostToDevice, h->stream));
+    if (nbig > 0) {
+        HIPCHK(hipMemcpyAsync(d_big, plan.big.data(), (size_t)nbig * sizeof(CkFoldBig), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_sys, sysv.data(), (size_t)nbig * sizeof(CkLocalSys), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemsetAsync(d_linfo, 0, (size_t)nbig * sizeof(long long), h->stream));
+    }
+    ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, m + 1, 0, -1.0, h->d_pred, h->d_err);
+    ck_launch_fold_gram(h->stream, h->aux, h->mpad, h->nK, d_tiles, (int64_t)plan.tiles.size(), d_grow, d_buf);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev2, h->stream));
+    // ---- 3. the fold solves
+    ck_launch_fold_small(h->stream, d_small, (int64_t)plan.small.size(), d_buf, d_grow, h->d_pred, d_x, d_d, d_stat, d_fail);
+    if (nbig > 0) {
+        const int kq_max = plan.big[0].kq, s_max = plan.big[0].s;
+        ck_launch_fold_big_fill(h->stream, d_big, nbig, kq_max, d_buf, d_grow, h->d_pred);
+        const int G = 4;   // 64-column blocks per group; the group's columns receive everything from their left in one pass
+        int na = nbig;
+        for (int g0 = 0; g0 < s_max; g0 += 64 * G) {
+            if (g0 > 0) ck_launch_local_tiled_left(h->stream, d_sys, d_buf, na, g0, 64 * G, kqv.data());
+            for (int b = 0; b < G && g0 + 64 * b < kq_max; ++b) {
+                while (na > 0 && kqv[(size_t)na - 1] <= g0 + 64 * b) --na;
+                ck_launch_local_tiled_block(h->stream, d_sys, d_buf, na, g0, b, kqv.data(), d_linfo, G);
+            }
+            while (na > 0 && kqv[(size_t)na - 1] <= g0 + 64 * G) --na;
+            ck_launch_local_tiled_rows_all(h->stream, d_sys, d_buf, na, g0, G, kqv.data());
+        }
+        ck_launch_fold_big_reduce(h->stream, d_big, nbig, s_max, d_buf, d_linfo, d_x, d_d, d_stat, d_fail);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev3, h->stream));
+    std::vector<double> xs((size_t)ng), ds((size_t)ng), st((size_t)n_folds * 2);
+    std::vector<int> fl((size_t)n_folds);
+    HIPCHK(hipMemcpyAsync(xs.data(), d_x, (size_t)ng * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ds.data(), d_d, (size_t)ng * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(st.data(), d_stat, (size_t)n_folds * 16, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(fl.data(), d_fail, (size_t)n_folds * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->t_ms[56] = elapsed(h->ev0, h->ev1);
+    h->t_ms[57] = elapsed(h->ev1, h->ev2);
+    h->t_ms[58] = elapsed(h->ev2, h->ev3);
+    const double* zi = h->h_values[i].data();
+    for (int32_t f = 0; f < n_folds; ++f) {
+        const int s = plan.off[(size_t)f + 1] - plan.off[(size_t)f];
+        const bool bad = fl[(size_t)f] != 0;
+        if (bad && *info == 0) *info = 1 + f;
+        if (fold_stats) {
+            fold_stats[3 * f] = (double)s;
+            fold_stats[3 * f + 1] = bad ? NAN : st[(size_t)2 * f];
+            fold_stats[3 * f + 2] = bad ? NAN : st[(size_t)2 * f + 1];
+        }
+        if (bad) continue;
+        for (int q = 0; q < s; ++q) {
+            const int64_t x = plan.cidx[(size_t)(plan.off[(size_t)f] + q)];
+            if (x < 0) continue;   // a datum of the other process: withheld, not predicted
+            const int64_t g = plan.gbase[(size_t)f] + q;
+            pred[x] = zi[x] - xs[(size_t)g];
+            const double e = sqrt(ds[(size_t)g]);
+            pred_err[x] = (e == e) ? e : 0.0;
+        }
+    }
+    h->t_ms[59] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return 0;
 }
 

@@ -468,3 +468,99 @@ int ck_host_gls(int p, const double* A, const double* b, double tol, double* R_o
     if (bAb) *bAb = q;
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------
+// leave-group-out cross-validation: members, gather list, tile map and system offsets of the folds
+// ---------------------------------------------------------------------------------------
+int ck_host_fold_plan(int i, int n_procs, const int64_t n[2], int64_t n0p, const int64_t* perm0, const int64_t* perm1,
+                      const int32_t* fold0, const int32_t* fold1, int32_t n_folds, int fold_max, CkFoldPlan* out) {
+    if (!out) return ck_fail("ck_cv_folds: null plan");
+    if (n_procs < 1 || n_procs > 2 || i < 0 || i >= n_procs) return ck_fail("ck_cv_folds: process index out of range");
+    if (n_folds < 1) return ck_fail("ck_cv_folds: n_folds = " + std::to_string(n_folds) + "; at least one fold is needed");
+    const int32_t* fold[2] = {fold0, n_procs == 2 ? fold1 : nullptr};
+    const int64_t* perm[2] = {perm0, perm1};
+    if (!fold[i]) return ck_fail("ck_cv_folds: the fold labels of the predicted process " + std::to_string(i) + " are null");
+    *out = CkFoldPlan();
+    std::vector<int32_t> cnt((size_t)n_folds, 0), cnt_i((size_t)n_folds, 0);
+    for (int k = 0; k < n_procs; ++k) {
+        if (!fold[k]) continue;
+        for (int64_t a = 0; a < n[k]; ++a) {
+            const int32_t f = fold[k][a];
+            if (f < -1 || f >= n_folds)
+                return ck_fail("ck_cv_folds: label " + std::to_string(f) + " of datum " + std::to_string(a) + " of process " +
+                               std::to_string(k) + " is outside [-1, n_folds = " + std::to_string(n_folds) + ")");
+            if (f < 0) continue;
+            ++cnt[(size_t)f];
+            if (k == i) ++cnt_i[(size_t)f];
+        }
+    }
+    out->off.assign((size_t)n_folds + 1, 0);
+    for (int32_t f = 0; f < n_folds; ++f) {
+        if (cnt_i[(size_t)f] == 0)
+            return ck_fail("ck_cv_folds: fold " + std::to_string(f) + " is empty: it holds no datum of process " + std::to_string(i) +
+                           " (and " + std::to_string(cnt[(size_t)f]) + " of the other process)");
+        if (cnt[(size_t)f] > fold_max)
+            return ck_fail("ck_cv_folds: fold " + std::to_string(f) + " holds " + std::to_string(cnt[(size_t)f]) +
+                           " data; a fold may hold at most CK_FOLD_MAX = " + std::to_string(fold_max));
+        out->off[(size_t)f + 1] = out->off[(size_t)f] + cnt[(size_t)f];
+    }
+    const int64_t total = out->off[(size_t)n_folds];
+    out->pos.assign((size_t)total, 0);
+    out->cidx.assign((size_t)total, -1);
+    std::vector<int32_t> fill(out->off.begin(), out->off.end() - 1);
+    out->pmin = INT64_MAX;
+    for (int k = 0; k < n_procs; ++k) {   // ascending internal position: every fold's members come out sorted
+        if (!fold[k]) continue;
+        for (int64_t j = 0; j < n[k]; ++j) {
+            const int64_t a = perm[k] ? perm[k][j] : j;
+            const int32_t f = fold[k][a];
+            if (f < 0) continue;
+            const int64_t p = (k == 0 ? 0 : n0p) + j;
+            const int32_t w = fill[(size_t)f]++;
+            out->pos[(size_t)w] = (int32_t)p;
+            out->cidx[(size_t)w] = k == i ? (int32_t)a : -1;
+            out->pmin = std::min(out->pmin, p);
+            out->pmax = std::max(out->pmax, p);
+        }
+    }
+    // ---- gather list: small folds packed into tiles, sorted by their first position
+    const int T = CK_HOST_FOLD_TILE;
+    out->gbase.assign((size_t)n_folds, 0);
+    std::vector<int32_t> sm, bg;
+    for (int32_t f = 0; f < n_folds; ++f) (cnt[(size_t)f] <= CK_HOST_FOLD_LDS ? sm : bg).push_back(f);
+    std::stable_sort(sm.begin(), sm.end(), [&](int32_t a, int32_t b) { return out->pos[(size_t)out->off[(size_t)a]] < out->pos[(size_t)out->off[(size_t)b]]; });
+    std::stable_sort(bg.begin(), bg.end(), [&](int32_t a, int32_t b) { return cnt[(size_t)a] > cnt[(size_t)b]; });
+    auto pad_tile = [&]() {
+        while (out->gpos.size() % (size_t)T) out->gpos.push_back(out->gpos[out->gpos.size() / T * T]);
+    };
+    for (int32_t f : sm) {
+        const int s = cnt[(size_t)f];
+        if ((int)(out->gpos.size() % (size_t)T) + s > T) pad_tile();
+        out->gbase[(size_t)f] = (int32_t)out->gpos.size();
+        out->small.push_back({(int)out->gpos.size(), s, f, 0});
+        for (int q = 0; q < s; ++q) out->gpos.push_back(out->pos[(size_t)(out->off[(size_t)f] + q)]);
+    }
+    pad_tile();
+    out->n_small_tiles = (int64_t)out->gpos.size() / T;
+    for (int64_t t = 0; t < out->n_small_tiles; ++t)
+        out->tiles.push_back({t * T * T, (int)(t * T), (int)(t * T), T, out->gpos[(size_t)(t * T)]});
+    // ---- big folds: their own runs of tiles, written straight into their systems
+    long long at = out->n_small_tiles * T * T;
+    for (int32_t f : bg) {
+        const int s = cnt[(size_t)f];
+        const int kq = (2 * s + 1 + 63) / 64 * 64, ld = kq + 128;
+        const int g0 = (int)out->gpos.size();
+        out->gbase[(size_t)f] = g0;
+        out->big.push_back({at, s, kq, ld, g0, f, 0});
+        for (int q = 0; q < s; ++q) out->gpos.push_back(out->pos[(size_t)(out->off[(size_t)f] + q)]);
+        while (out->gpos.size() % (size_t)T) out->gpos.push_back(out->gpos.back());
+        const int nt = (s + T - 1) / T;
+        for (int tm = 0; tm < nt; ++tm)
+            for (int tn = 0; tn <= tm; ++tn)
+                out->tiles.push_back({at + (long long)tm * T * ld + (long long)tn * T, g0 + tm * T, g0 + tn * T, ld, out->gpos[(size_t)(g0 + tm * T)]});
+        at += (long long)(kq + 128) * ld + 8 * 64 * 64;
+    }
+    out->buffer_doubles = at;
+    std::stable_sort(out->tiles.begin(), out->tiles.end(), [](const CkFoldTile& a, const CkFoldTile& b) { return a.pos0 < b.pos0; });
+    return 0;
+}

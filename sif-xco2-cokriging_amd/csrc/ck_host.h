@@ -86,3 +86,47 @@ CK_HIDDEN void ck_host_vario_fix(int metric, const double* ci, const double* cj,
 // zeros above), beta = A^-1 b, Ainv = A^-1 (p x p, symmetric), logdet = log|A|, bAb = b^T A^-1 b.
 CK_HIDDEN int ck_host_gls(int p, const double* A, const double* b, double tol, double* R, double* beta, double* Ainv,
                           double* logdet, double* bAb);
+
+// ---- leave-group-out cross-validation: the fold layout (ck_api.hip: ck_cv_folds) ---------------------------------------
+// Pure index work, no device.  Fold f withholds every datum of either process labelled f (fold_k[a]: the caller's order of
+// process k; -1: never withheld; fold1 may be null).  perm_k[j] = caller's index of the site at internal position j of
+// process k (ck_handle::perm); internal position of that site: j for process 0, n0p + j for process 1.
+//   members     off (n_folds + 1), pos (internal positions, ascending inside a fold), cidx (caller's index within process
+//               i, -1 for a datum of the other process)
+//   gather list gpos: the internal positions whose unit rows the Gram kernel reads, 128 per tile.  Folds of up to
+//               CK_HOST_FOLD_LDS members ("small") are packed several to a tile, sorted by their first position, none across
+//               a tile edge; a larger fold ("big") starts its own run of tiles.  Padding entries repeat a position of the
+//               same tile (their products are never read).  gbase[f]: where fold f starts in gpos.
+//   tiles       one 128 x 128 product each: rows gpos[a0 ..], columns gpos[b0 ..], written at buffer + c_off with leading
+//               dimension ld; pos0 = the smallest position among its rows AND columns' later operand, i.e. every panel in
+//               front of pos0 / 512 is structurally zero in the product.  Sorted by pos0 (longest contraction first).
+//   buffer      [n_small_tiles x 128 x 128 | the big folds' systems].  A big fold of s members is the symmetric system of
+//               order kq = roundup(2 s + 1, 64) that the local predictor's batched Cholesky steps factor (ck_la.hip: k_lt_*):
+//               rows [0, s) Q_SS, rows s + q the unit rows (they become row q of R^-T), row 2 s alpha_S (becomes R^-1 alpha),
+//               ld = kq + 128, kq + 128 rows, then 8 x 64 x 64 doubles for the diagonal blocks' inverses.  big: largest first.
+#define CK_HOST_FOLD_MAX 4096   // == CK_FOLD_MAX (include/cokrige.h)
+#define CK_HOST_FOLD_LDS 64     // folds up to this size are solved in LDS
+#define CK_HOST_FOLD_TILE 128
+struct CkFoldTile {
+    long long c_off;
+    int a0, b0, ld, pos0;
+};
+struct CkFoldBig {
+    long long off;
+    int s, kq, ld, gbase, fold, pad;
+};
+struct CkFoldSmall {
+    int gbase, s, fold, pad;
+};
+struct CkFoldPlan {
+    int64_t pmin = 0, pmax = -1;
+    std::vector<int32_t> off, pos, cidx, gbase, gpos;
+    std::vector<CkFoldTile> tiles;
+    std::vector<CkFoldSmall> small;
+    std::vector<CkFoldBig> big;
+    int64_t n_small_tiles = 0, buffer_doubles = 0;
+};
+// 0, or -1 with the error text set: a label outside [-1, n_folds), a fold without a datum of process i, a fold of more than
+// fold_max members (the messages state the amounts and name the fold)
+CK_HIDDEN int ck_host_fold_plan(int i, int n_procs, const int64_t n[2], int64_t n0p, const int64_t* perm0, const int64_t* perm1,
+                                const int32_t* fold0, const int32_t* fold1, int32_t n_folds, int fold_max, CkFoldPlan* out);

@@ -196,6 +196,21 @@ void ck_launch_draw_upper(hipStream_t s, double* const* sch, int nJ);
 void ck_launch_draw_noise(hipStream_t s, double* E, int64_t ldp, int64_t Mp, int64_t nd, int64_t m, int64_t d0, const int* cmap,
                           const unsigned char* mask, const double* noise, uint64_t seed);
 
+// ---- leave-group-out cross-validation (ck_la.hip: the Gram kernel; ck_folds.hip: the fold solves) ------------------
+// Q_SS = W_S W_S^T of every fold, one workgroup per tile of the host's tile map (ck_host.h: CkFoldPlan): rows grow[a0 ..] and
+// grow[b0 ..] of the solved right-hand sides (grow: the gather list as ROW indices of aux, all >= 1), product at out + c_off
+// (ld), panels pos0 / CK_NB .. nK - 1.  mpad CK_NB 8 < 2^31 (a row's byte offset inside a panel is a 32-bit register).
+void ck_launch_fold_gram(hipStream_t s, const double* aux, int64_t mpad, int nK, const CkFoldTile* tiles, int64_t n_tiles,
+                         const int* grow, double* out);
+// dots[row] = W_row . y (k_reduce_pred, raw mode).  Outputs indexed like the gather list: x = Q_SS^-1 alpha_S, d = diag(Q_SS^-1);
+// stat2[2 f], stat2[2 f + 1] = log|Q_SS|, alpha_S^T Q_SS^-1 alpha_S; fail[f] = 1 where Q_SS did not factor (outputs NaN)
+void ck_launch_fold_small(hipStream_t s, const CkFoldSmall* folds, int64_t n, const double* buf, const int* grow,
+                          const double* dots, double* x_out, double* d_out, double* stat2, int* fail);
+void ck_launch_fold_big_fill(hipStream_t s, const CkFoldBig* sys, int n_sys, int kq_max, double* buf, const int* grow,
+                             const double* dots);
+void ck_launch_fold_big_reduce(hipStream_t s, const CkFoldBig* sys, int n_sys, int s_max, const double* buf, const long long* info,
+                               double* x_out, double* d_out, double* stat2, int* fail);
+
 // ---- empirical variogram (ck_vario.hip) ----------------------------------------------------
 #ifndef CK_VG_JSUB
 #define CK_VG_JSUB 128   // "j" points of a sub-chunk: the unit of the level-window decision (and of the third set of bounding

@@ -405,7 +405,11 @@ struct CkSrcAux {
 // rq > 1 (ck_loglik_reml): from sum_j ar[j rld + row] ac[j rld + col] over rq vector pairs, the first product as for rq = 1
 // SCATTER (k_draw_trmm): the tile's column c is stored to column cmap[c] of C (none where cmap[c] < 0), its rows only in front
 // of row_lim; C is then the output's base (c0 plays no part in the store)
-template <int WAVES, class SRC, int NI = 4, bool RANK1 = false, bool SCATTER = false>
+// GRAM (k_fold_gram): the 128 A rows and the 128 B rows are GATHERED -- image row r of the tile is row src.ga[r] / src.gb[r] of the
+// source panel, so SRC::get returns the panel's row 0 and a transfer's per-lane offset register carries the row (one panel row is
+// CK_NB contiguous doubles: every transfer still fetches whole 128-byte lines); the accumulators start from zero and C = + A B^T
+// is written, not read
+template <int WAVES, class SRC, int NI = 4, bool RANK1 = false, bool SCATTER = false, bool GRAM = false>
 __device__ __forceinline__ void gemm_tile_d(double* __restrict__ C, long ldc, const SRC& src, int np, long r0, long c0,
                                             char* lds, const double* __restrict__ ar = nullptr,
                                             const double* __restrict__ ac = nullptr, const int* __restrict__ cmap = nullptr,
@@ -454,7 +458,15 @@ __device__ __forceinline__ void gemm_tile_d(double* __restrict__ C, long ldc, co
 #pragma unroll
     // (the four transfers of a chunk share one LDS base in M0: the instruction's immediate offset, 0 / 1024 / 2048 / 3072, counts
     // on the LDS side AND on the memory side, so the per-lane offset registers carry the difference)
-    for (int t = 0; t < NDMA; ++t) vo4[t] = ((t & 1) ? d_odd : d_even) + (unsigned)(8 * t * CK_NB) * 8u - (unsigned)(t * 1024);
+    for (int t = 0; t < NDMA; ++t) {
+        if constexpr (GRAM) {   // (a gathered row is at least row 1 of the panel: the offset stays positive behind the - t * 1024)
+            const int ir = RPW * (w % (WAVES / 2)) + 8 * t + r8;
+            const unsigned grow = (unsigned)(stage_a ? src.ga[ir] : src.gb[ir]);
+            vo4[t] = grow * (unsigned)(CK_NB * 8) + 16u * (unsigned)(sj ^ (r8 >> 1) ^ ((t & 1) ? 4 : 0)) - (unsigned)(t * 1024);
+        } else {
+            vo4[t] = ((t & 1) ? d_odd : d_even) + (unsigned)(8 * t * CK_NB) * 8u - (unsigned)(t * 1024);
+        }
+    }
 #define CK_DMA_CHUNK(stage_, kbyte_)                                                                            \
     {                                                                                                           \
         const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc(                                   \
@@ -467,7 +479,12 @@ __device__ __forceinline__ void gemm_tile_d(double* __restrict__ C, long ldc, co
     }
     CK_DMA_CHUNK(0, 0L);
     d4_t acc[NA][WJ];
-    if constexpr (RANK1) {
+    if constexpr (GRAM) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+            for (int j = 0; j < WJ; ++j) acc[i][j] = d4_t{0.0, 0.0, 0.0, 0.0};
+    } else if constexpr (RANK1) {
 #pragma unroll
         for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -593,7 +610,7 @@ __device__ __forceinline__ void gemm_tile_d(double* __restrict__ C, long ldc, co
         for (int r = 0; r < 4; ++r) {
             ck_gchar* rowp = reinterpret_cast<ck_gchar*>(Cb + (long)(i * 16 + 4 * r) * ldc);
 #pragma unroll
-            for (int j = 0; j < WJ; ++j) *reinterpret_cast<ck_gdouble*>(rowp + j * 128 + c_off) = -acc[i][j][r];
+            for (int j = 0; j < WJ; ++j) *reinterpret_cast<ck_gdouble*>(rowp + j * 128 + c_off) = GRAM ? acc[i][j][r] : -acc[i][j][r];
         }
 }
 
@@ -809,6 +826,42 @@ void ck_launch_ginv_syrk(hipStream_t s, double* const* G_dev, const double* aux,
         k_ginv_syrk_d<false><<<dim3((unsigned)map.total), dim3(512), 0, s>>>(G_dev, aux, mpad, avec, nK, map, 1, (long)ald, dense);
     else
         k_ginv_syrk_d<true><<<dim3((unsigned)map.total), dim3(512), 0, s>>>(G_dev, aux, mpad, avec, nK, map, q, (long)ald, dense);
+}
+
+// ---------------------------------------------------------------------------------------
+// Leave-group-out cross-validation (ck_cv_folds): the Gram matrices Q_SS = W_S W_S^T of all folds in ONE launch
+// ---------------------------------------------------------------------------------------
+// W: the solved unit right-hand-side rows of the leave-one-out layout.  A fold's rows are scattered over the buffer, but a row's
+// slice of a panel is CK_NB contiguous doubles, so the tile's operand loader takes the row from an index list (gemm_tile_d,
+// GRAM) and everything behind the loader is the trailing updates' tile.  One workgroup per tile of the host's tile map
+// (ck_host.cpp: ck_host_fold_plan): only within-fold tiles exist, and a tile starts at the panel of its first position -- in
+// front of it its later operand is structurally zero.
+struct CkSrcGram {
+    const double* aux;
+    long mpad;
+    int K0;
+    const int* ga;
+    const int* gb;
+    __device__ __forceinline__ void get(int p, const ck_gchar*& A, const ck_gchar*& B) const {
+        A = as_global(reinterpret_cast<const char*>(aux + (long)(K0 + p) * mpad * CK_NB));
+        B = A;
+    }
+};
+
+__global__ __launch_bounds__(512, 4) void k_fold_gram(const double* __restrict__ aux, long mpad, int nK,
+                                                       const CkFoldTile* __restrict__ tiles, const int* __restrict__ grow,
+                                                       double* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) char lds[2 * 256 * 128];
+    const CkFoldTile t = tiles[blockIdx.x];
+    const int K0 = t.pos0 / CK_NB;
+    const CkSrcGram src{aux, mpad, K0, grow + t.a0, grow + t.b0};
+    gemm_tile_d<8, CkSrcGram, 4, false, false, true>(out + t.c_off, (long)t.ld, src, nK - K0, 0, 0, lds);
+}
+
+void ck_launch_fold_gram(hipStream_t s, const double* aux, int64_t mpad, int nK, const CkFoldTile* tiles, int64_t n_tiles,
+                         const int* grow, double* out) {
+    if (n_tiles <= 0) return;
+    k_fold_gram<<<dim3((unsigned)n_tiles), dim3(512), 0, s>>>(aux, (long)mpad, nK, tiles, grow, out);
 }
 
 // Conditional simulation (ck_conditional_draws): X = pred + eps L_S^T for a chunk of draws, L_S the factor of the

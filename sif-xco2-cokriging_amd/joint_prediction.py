@@ -570,14 +570,26 @@ class Predictor:
         except TypeError:
             return ds.assign_coords(coords={"time": np.datetime64(ts)})
 
-    def cross_validation(self, i: int, postprocess: bool = True, refactor_each: bool = False) -> pd.DataFrame:
+    def cross_validation(self, i: int, postprocess: bool = True, refactor_each: bool = False, folds=None,
+                         also_withhold=None, seed: int = 0) -> pd.DataFrame:
         """Leave-one-out cross-validation at each data location of process ``i``
         (src/joint_prediction.py:207-257).  The reference withholds one datum and re-assembles
         and re-factorises everything, n times; here all n leave-one-out predictions come from
         ONE factorisation (``ck_loocv``: the Gaussian conditional of z_q given the rest,
         pred_q = z_q - (Sigma^-1 z)_q / (Sigma^-1)_qq, var_q = 1 / (Sigma^-1)_qq -- the same
-        numbers).  ``refactor_each=True`` runs the reference's n-solve loop instead."""
+        numbers).  ``refactor_each=True`` runs the reference's n-solve loop instead.
+
+        ``folds``: leave-GROUP-out cross-validation, still from the one resident factor (``ck_cv_folds``).  An array of n_i
+        labels -- any hashable values, numbered in order of first appearance; ``None`` / NaN / -1 mean "never withheld" -- or
+        an int K: a random K-fold drawn from ``seed``.  Every datum is predicted from the data outside its fold.
+        ``also_withhold``: n_other labels from the same label set: the other process's data that leave together with a fold
+        (the co-located partner, the same track).  The frame gains a ``fold`` column and loses the rows of never-withheld
+        data; ``cv_folds_`` holds one row per fold: label, n_withheld, nlpd (the joint negative log predictive density of
+        the withheld values) and failed.  ``refactor_each=True`` with folds runs the slow truth: a fresh factorisation per
+        fold with that fold's data removed."""
         self._no_trend("cross_validation")
+        if folds is not None or also_withhold is not None:
+            return self._cv_folds(i, postprocess, refactor_each, folds, also_withhold, seed)
         names = ["lat", "lon"] if postprocess else ["d1", "d2"]
         f = self.mf.fields[i]
         data = pd.DataFrame(np.hstack((f.coords_main, np.atleast_2d(f.values_main).T)), columns=names + ["data"])
@@ -589,8 +601,11 @@ class Predictor:
                 pred[ix], err[ix] = p[0], e[0]
         else:
             pred, err = self._factored_handle().loocv(i, len(data))
+        return self._cv_frame(i, postprocess, data, names, pred, err)
+
+    def _cv_frame(self, i, postprocess, data, names, pred, err, fold=None):
+        f = self.mf.fields[i]
         if postprocess:
-            at = f.ds.attrs
             tmp = pd.DataFrame({"lat": data["lat"], "lon": data["lon"], "pred": pred, "pred_err": err})
             self.i = i
             pp = self._postprocess_predictions(tmp)
@@ -602,7 +617,131 @@ class Predictor:
         # the reference's xr.merge(...).to_dataframe() + outer merge hands the rows back sorted by the coordinates
         # (src/joint_prediction.py:248-254)
         data = data.sort_values(names, kind="stable").reset_index(drop=True)
-        return data[names + ["data", "pred", "residual", "pred_err"]]
+        cols = names + ["data", "pred", "residual", "pred_err"]
+        return data[cols] if fold is None else data[cols + ["fold"]]
+
+    def _cv_folds(self, i, postprocess, refactor_each, folds, also_withhold, seed):
+        """The ``folds=`` form of ``cross_validation``: everything is validated on the host before any device work."""
+        if self.devices is not None and len(self.devices) > 1:
+            raise ValueError(f"cross_validation(folds=...) runs on a single device; this predictor has devices={self.devices}")
+        if not 0 <= int(i) < self.n_procs:
+            raise ValueError(f"process index {i!r} out of range for {self.n_procs} processes")
+        f = self.mf.fields[i]
+        n_i = len(np.asarray(f.values_main))
+        n_o = len(np.asarray(self.mf.fields[1 - i].values_main)) if self.n_procs == 2 else 0
+        codes, codes_o, labels = fold_codes(folds, also_withhold, n_i, n_o if self.n_procs == 2 else None, seed)
+        names = ["lat", "lon"] if postprocess else ["d1", "d2"]
+        data = pd.DataFrame(np.hstack((f.coords_main, np.atleast_2d(f.values_main).T)), columns=names + ["data"])
+        K = len(labels)
+        sizes = np.bincount(codes[codes >= 0], minlength=K) + (0 if codes_o is None else np.bincount(codes_o[codes_o >= 0], minlength=K))
+        if refactor_each:
+            pred, err = np.full(n_i, np.nan), np.full(n_i, np.nan)
+            nlpd, failed = np.full(K, np.nan), np.zeros(K, dtype=bool)
+            for k in range(K):
+                sel = np.flatnonzero(codes == k)
+                drop = [sel if q == i else (np.flatnonzero(codes_o == k) if codes_o is not None else np.empty(0, dtype=int))
+                        for q in range(self.n_procs)]
+                h = native.Handle(self.device)
+                try:
+                    configure_handle(h, self.mod)
+                    h.set_metric(metric_of(self.dist_units, self.fast_dist))
+                    for q in range(self.n_procs):
+                        c = np.asarray(self.mf.fields[q].coords_main, dtype=np.float64)
+                        v = np.asarray(self.mf.fields[q].values_main, dtype=np.float64)
+                        h.set_data(q, np.delete(c, drop[q], axis=0), np.delete(v, drop[q], axis=0))
+                    pred[sel], err[sel] = self._factor_predict(h, i, np.ascontiguousarray(np.asarray(f.coords_main, dtype=np.float64)[sel]))
+                finally:
+                    h.close()
+        else:
+            h = self._factored_handle()
+            info, pred, err, stats = h.cv_folds(i, codes, codes_o, n_folds=K, want_stats=True)
+            self.timings = h.cv_folds_timings()
+            failed = np.isnan(stats[:, 1])
+            nlpd = 0.5 * (stats[:, 0] * np.log(2.0 * np.pi) - stats[:, 1] + stats[:, 2])
+            if info != 0:
+                bad = [labels[k] for k in np.flatnonzero(failed)]
+                warnings.warn(f"cross_validation: the withheld data of {len(bad)} fold(s) have no positive definite conditional "
+                              f"precision (first: fold {labels[info - 1]!r}); their rows are NaN")
+        self.cv_folds_ = pd.DataFrame({"label": pd.Series(labels, dtype=object), "n_withheld": sizes.astype(int), "nlpd": nlpd,
+                                       "failed": failed})
+        data["fold"] = pd.Series([labels[c] if c >= 0 else None for c in codes], dtype=object)
+        keep = codes >= 0
+        if postprocess:
+            out = self._cv_frame(i, True, data, names, pred, err, fold=True)
+            return out[out["fold"].notna()].reset_index(drop=True)
+        data = data[keep].reset_index(drop=True)
+        return self._cv_frame(i, False, data, names, pred[keep], err[keep], fold=True)
+
+
+CK_FOLD_MAX = 4096   # include/cokrige.h
+
+
+def _is_missing(x):
+    if x is None:
+        return True
+    try:
+        if x != x:   # NaN
+            return True
+        return bool(x == -1) and not isinstance(x, (str, bytes))
+    except Exception:
+        return False
+
+
+def fold_codes(folds, also_withhold, n_i, n_other, seed=0):
+    """(codes_i, codes_other or None, labels): the fold labels of ``cross_validation(folds=...)`` as the int32 codes of
+    ``ck_cv_folds``.  Labels are numbered in order of first appearance in ``folds``; None / NaN / -1 -> -1 (never withheld).
+    An int K draws a random K-fold from ``seed``: a permutation of the data cut into K nearly equal parts.  Raises
+    ValueError for wrong lengths, ``also_withhold`` labels that are no label of ``folds``, an empty fold set and folds of
+    more than CK_FOLD_MAX data.  Host only."""
+    if folds is None:
+        raise ValueError("also_withhold needs folds")
+    if isinstance(folds, (int, np.integer)) and not isinstance(folds, bool):
+        K = int(folds)
+        if not 1 <= K <= n_i:
+            raise ValueError(f"folds={K}: a K-fold of {n_i} data needs 1 <= K <= {n_i}")
+        perm = np.random.default_rng(seed).permutation(n_i)
+        codes = np.empty(n_i, dtype=np.int32)
+        codes[perm] = (np.arange(n_i) * K // n_i).astype(np.int32)
+        labels = list(range(K))
+    else:
+        raw = list(folds) if not isinstance(folds, np.ndarray) else folds.tolist()
+        if len(raw) != n_i:
+            raise ValueError(f"folds has {len(raw)} labels, the predicted process has {n_i} data")
+        index, labels = {}, []
+        codes = np.empty(n_i, dtype=np.int32)
+        for a, x in enumerate(raw):
+            if _is_missing(x):
+                codes[a] = -1
+                continue
+            if x not in index:
+                index[x] = len(labels)
+                labels.append(x)
+            codes[a] = index[x]
+    if not labels:
+        raise ValueError("folds withholds nothing: every label is None / NaN / -1")
+    codes_o = None
+    if also_withhold is not None:
+        if n_other is None:
+            raise ValueError("also_withhold needs a second process")
+        raw = list(also_withhold) if not isinstance(also_withhold, np.ndarray) else also_withhold.tolist()
+        if len(raw) != n_other:
+            raise ValueError(f"also_withhold has {len(raw)} labels, the other process has {n_other} data")
+        index = {x: k for k, x in enumerate(labels)}
+        codes_o = np.empty(n_other, dtype=np.int32)
+        for a, x in enumerate(raw):
+            if _is_missing(x):
+                codes_o[a] = -1
+            elif x in index:
+                codes_o[a] = index[x]
+            else:
+                raise ValueError(f"also_withhold label {x!r} (datum {a}) is no label of folds")
+    sizes = np.bincount(codes[codes >= 0], minlength=len(labels))
+    if codes_o is not None:
+        sizes = sizes + np.bincount(codes_o[codes_o >= 0], minlength=len(labels))
+    big = np.flatnonzero(sizes > CK_FOLD_MAX)
+    if len(big):
+        raise ValueError(f"fold {labels[big[0]]!r} withholds {int(sizes[big[0]])} data; the cap is CK_FOLD_MAX = {CK_FOLD_MAX} per fold")
+    return codes, codes_o, labels
 
 
 def prediction_coords(extents: tuple = (-125, -65, 22, 58), lon_res: float = 0.5, lat_res: float = 0.5,

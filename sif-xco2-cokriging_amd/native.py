@@ -50,6 +50,7 @@ _PROTOS = {
     "ck_verify_model": [c_void_p, POINTER(c_int64)],
     "ck_predict_blocks": [c_void_p, c_int, _dp, c_int64, POINTER(c_int32), _dp, c_int32, _dp, _dp, _dp],
     "ck_loocv": [c_void_p, c_int, _dp, _dp],
+    "ck_cv_folds": [c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), c_int32, _dp, _dp, _dp, POINTER(c_int64)],
     "ck_loglik": [c_void_p, c_int, _dp, _dp, POINTER(c_int64)],
     "ck_set_trend": [c_void_p, c_int, _dp, c_int64, c_int],
     "ck_predict_universal": [c_void_p, c_int, _dp, c_int64, _dp, _dp, _dp, _dp, _dp],
@@ -490,6 +491,32 @@ class Handle:
         pred, err = np.empty(n_i), np.empty(n_i)
         _chk(lib().ck_loocv(self._h, int(i), _p(pred), _p(err)))
         return pred, err
+
+    def cv_folds(self, i, folds_i, folds_other=None, n_folds=None, want_stats=False):
+        """Leave-group-out cross-validation of process ``i`` from the resident factor (include/cokrige.h: ck_cv_folds).
+        ``folds_i`` / ``folds_other``: int labels in [-1, n_folds) of the data of process i / of the other process (the caller's
+        order of set_data; -1 = never withheld; ``folds_other=None``: nothing of the other process is withheld).
+        Returns (info, pred, pred_err[, fold_stats (n_folds x 3)])."""
+        fi = np.ascontiguousarray(folds_i, dtype=np.int32).ravel()
+        fo = None if folds_other is None else np.ascontiguousarray(folds_other, dtype=np.int32).ravel()
+        if n_folds is None:
+            n_folds = int(max(fi.max(initial=-1), -1 if fo is None else fo.max(initial=-1))) + 1
+        n_folds = int(n_folds)
+        pred, err = np.empty(fi.size), np.empty(fi.size)
+        stats = np.empty((max(n_folds, 0), 3)) if want_stats else None
+        info = c_int64(0)
+        ip = POINTER(c_int32)
+        pi = fi.ctypes.data_as(ip)
+        po = None if fo is None else fo.ctypes.data_as(ip)
+        f0, f1 = (pi, po) if int(i) == 0 else (po, pi)
+        _chk(lib().ck_cv_folds(self._h, int(i), f0, f1, n_folds, _p(pred), _p(err), _p(stats) if want_stats else None, byref(info)))
+        return (info.value, pred, err, stats) if want_stats else (info.value, pred, err)
+
+    def cv_folds_timings(self):
+        """ck_timings [56 ..] of the last cv_folds() call (milliseconds)."""
+        out = np.zeros(60)
+        _chk(lib().ck_timings(self._h, _p(out), 60))
+        return dict(zip(["sweep_ms", "gram_ms", "solve_ms", "total_ms"], out[56:60].tolist()))
 
     def sample(self, noise):
         e = _f64(noise).ravel()
