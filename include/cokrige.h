@@ -163,14 +163,15 @@ int ck_predict_blocks(ck_handle* h, int i, const double* pcoords_host, int64_t m
 /* Leave-one-out cross-validation of process i at all its data sites from ONE factorisation
  * (Predictor.cross_validation, src/joint_prediction.py:207-257, which re-solves per datum):
  * pred_q = z_q - (Sigma^-1 z)_q / (Sigma^-1)_qq, pred_err_q = sqrt(1 / (Sigma^-1)_qq); n_i values
- * each.  Needs ck_factor. */
+ * each.  Needs ck_factor.  With ck_set_noise the withheld OBSERVATION is predicted: 1 / (Sigma^-1)_qq contains s d_q. */
 int ck_loocv(ck_handle* h, int i, double* pred_host, double* pred_err_host);
 
 /* Leave-group-out cross-validation of process i from ONE factorisation: fold f withholds every datum of EITHER process
  * labelled f -- a track, a spatial block, a random tenth (K-fold), a datum together with its co-located partner -- and the
  * withheld data of process i are predicted from all the rest.  With S the withheld positions, Q = Sigma^-1, alpha = Sigma^-1 z:
  *     E[z_S | z_rest] = z_S - Q_SS^-1 alpha_S,      Cov[z_S | z_rest] = Q_SS^-1
- * (ck_loocv is the case of singleton folds).  With W = the solved unit right-hand-side rows (row of site a = (L^-1 e_a)^T) and
+ * (ck_loocv is the case of singleton folds; with ck_set_noise Sigma carries s d on its diagonal, so Q_SS^-1 is the covariance of
+ * the withheld OBSERVATIONS and contains their s d_q).  With W = the solved unit right-hand-side rows (row of site a = (L^-1 e_a)^T) and
  * y = L^-1 z:  Q_SS = W_S W_S^T, alpha_S = W_S y -- one sweep of the unit rows, the Gram matrices of the folds' rows, one small
  * dense solve per fold.
  * Inputs: fold_k[a], in the caller's order of ck_set_data of process k, is the fold of datum a; -1: never withheld.
@@ -251,6 +252,38 @@ int ck_predict_universal(ck_handle* h, int i, const double* pcoords_host, int64_
  * state afterwards as ck_loglik; a rank-deficient design is refused as in ck_predict_universal.  With p = 0 the call is
  * ck_loglik, bit for bit (out4[2] = 0). */
 int ck_loglik_reml(ck_handle* h, int want_grad, double* out4, double* grad, int64_t* info);
+
+/* ---- per-observation measurement-error variances ---------------------------------------------------------------------
+ * The reference's loaders carry a variance for every datum (xco2_var, sif_var: src/data_utils.py:28-87, "the variance of the
+ * measurement error which will be added to the diagonals of the covariance matrix"; Field.variance_estimate, src/fields.py:88;
+ * the line that would use it is commented out at src/point_prediction.py:109-110).  With d_a >= 0 the variance of datum a of
+ * process k and s_k >= 0 a scale per process:
+ *     Sigma_noise = Sigma + diag(s_k(a) d_a)
+ * on the TRUE diagonal, by datum index -- not "where h == 0": two data at identical coordinates keep the nugget on their
+ * off-diagonal entry and get no measurement error there.  Nothing else changes: c0, the prior variance sigma_i^2 + nugget_i of
+ * pred_err and C_pp of the Schur complement are the field's, so the predictors filter the measurement error out.  Everything
+ * that works on the factor follows: ck_predict, ck_factor_predict, ck_predict_universal, ck_predict_blocks, ck_verify_model,
+ * ck_conditional_draws (a site on a datum with s d > 0 has S_kk > 0 and is not deflated), ck_sample (draws noisy observations),
+ * ck_loglik / ck_loglik_reml (their gradients keep formulas and order: dSigma/dtheta does not involve d), and ck_loocv /
+ * ck_cv_folds -- these predict the withheld OBSERVATION, so their variance 1 / Q_qq (Q_SS^-1) contains s d_q.  ck_predict_local
+ * and ck_predict_local_universal add the neighbour's s d to the diagonal of every local system, in every size class; the cv
+ * rule, the NaN rules and the counters are unchanged.
+ *
+ * ck_set_noise: var (n_k values) in the caller's order of ck_set_data of process k; var == NULL or n_k == 0 clears the noise
+ * of process k, and so does ck_set_data of process k.  Allowed after the sites are laid out: the library keeps the vector on
+ * the host and lays it along its site order whenever the sites are laid out (also again: ck_factor's retry in the caller's
+ * order, option "site_order", ck_set_metric).  Invalidates the assembled Sigma, the factor and the solved right-hand sides, as
+ * ck_set_model does (ck_predict_local needs neither).  Refused through ck_last_error, naming the process and the datum: a
+ * count other than that process's data count, a negative or non-finite variance, a negative or non-finite scale, a
+ * partitioned handle.  A vector of zeros, a scale of 0 and a cleared vector behave bit for bit like a handle that never saw
+ * the call (no kernel is then launched or handed the vector). */
+int ck_set_noise(ck_handle* h, int k, const double* var_host, int64_t n_k, double scale);
+/* out2 = (dl/ds_0, dl/ds_1) of the last ck_loglik / ck_loglik_reml called with want_grad != 0 on this handle:
+ *     dl/ds_k = 1/2 sum_{a in k} G_aa d_a,   G (G_R for REML) the matrix those calls contract,
+ * reduced over the packed G tiles in a fixed order (no atomics: repeated calls give the same bits) inside that call.  A process
+ * without noise gives 0 (a scale of 0 does not: d is still there).  Refused when no such call has succeeded since the last
+ * ck_assemble_joint. */
+int ck_loglik_noise_grad(ck_handle* h, double* out2);
 
 /* Simulation draw z = L eps in the caller's stacked order (process 0 sites, then process 1):
  * sim.BivariateRandomField._simulate (src/sim.py:52-54: cholesky(cmat, lower=True) @ noise).

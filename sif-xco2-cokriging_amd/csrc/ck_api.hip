@@ -250,6 +250,16 @@ struct ck_handle {
     int64_t trend_cap = 0;          // doubles
     double* d_univ = nullptr;       // the universal reduction's output (rows x (q + 1) doubles)
     int64_t univ_cap = 0;
+    // measurement-error variances (ck_set_noise): d_a of process k in the caller's order, kept on the host, and the scale s_k;
+    // d_noise: [s_k d_a | d_a], two rows of Npad doubles in the internal order (zero at padding positions and where a process
+    // has none), uploaded when the layout is known.  noise_on: some s_k d_a > 0 -- otherwise no kernel sees the vector
+    std::vector<double> noise_var[2];
+    double noise_scale[2] = {1.0, 1.0};
+    bool noise_dirty = false, noise_on = false;
+    double* d_noise = nullptr;
+    int64_t noise_cap = 0;          // doubles
+    double lik_noise_grad[2] = {0.0, 0.0};   // dl/ds_k of the last ck_loglik / ck_loglik_reml with a gradient
+    bool lik_noise_valid = false;            // ... since the last ck_assemble_joint
     int aux_trend = 0;   // trend rows behind the data row of the right-hand sides being assembled (rows m + 1 .. m + aux_trend)
     int loo_dense = 1;   // rows in front of the unit rows in the leave-one-out / likelihood layout (ck_loglik_reml: 1 + p)
 };
@@ -361,6 +371,7 @@ extern "C" int ck_destroy(ck_handle* h) {
     if (h->d_coop) (void)hipFree(h->d_coop);
     if (h->d_stamps) (void)hipFree(h->d_stamps);
     if (h->d_trendX) (void)hipFree(h->d_trendX);
+    if (h->d_noise) (void)hipFree(h->d_noise);
     if (h->d_univ) (void)hipFree(h->d_univ);
     (void)hipStreamDestroy(h->own_stream);
     delete h;
@@ -450,6 +461,9 @@ extern "C" int ck_set_data(ck_handle* h, int k, const double* coords, const doub
     h->data_set[k] = true;
     h->trend_F[k].clear();   // new data: the regressors of the old sites no longer apply
     h->trend_p[k] = 0;
+    h->noise_var[k].clear();   // ... and neither do their measurement-error variances
+    h->noise_scale[k] = 1.0;
+    h->noise_dirty = true;
     return 0;
 }
 
@@ -477,6 +491,40 @@ extern "C" int ck_set_trend(ck_handle* h, int k, const double* F, int64_t n_k, i
         h->trend_F[k].assign(F, F + n_k * p_k);
     h->trend_p[k] = p_k;
     h->trend_dirty = true;
+    return 0;
+}
+
+extern "C" int ck_set_noise(ck_handle* h, int k, const double* var, int64_t n_k, double scale) {
+    CHKH(h);
+    if (k < 0 || k > 1) return fail("ck_set_noise: process index must be 0 or 1");
+    if (h->world != 1)
+        return fail("ck_set_noise is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) +
+                    "); process " + std::to_string(k) + " keeps no measurement-error variances");
+    if (!h->data_set[k]) return fail("ck_set_noise: ck_set_data has not been called for process " + std::to_string(k));
+    const bool clear = !var || n_k == 0;
+    if (!clear && n_k != h->n[k])
+        return fail("ck_set_noise: " + std::to_string(n_k) + " variances for process " + std::to_string(k) + ", which has " +
+                    std::to_string(h->n[k]) + " data sites");
+    if (!clear) {
+        if (!(std::isfinite(scale) && scale >= 0.0))
+            return fail("ck_set_noise: the scale of process " + std::to_string(k) + " is " + std::to_string(scale) +
+                        "; it must be finite and >= 0");
+        for (int64_t a = 0; a < n_k; ++a)
+            if (!(std::isfinite(var[a]) && var[a] >= 0.0))
+                return fail("ck_set_noise: the variance of datum " + std::to_string(a) + " of process " + std::to_string(k) + " is " +
+                            std::to_string(var[a]) + "; it must be finite and >= 0");
+    }
+    if (clear) {
+        h->noise_var[k].clear();
+        h->noise_scale[k] = 1.0;
+    } else {
+        h->noise_var[k].assign(var, var + n_k);
+        h->noise_scale[k] = scale;
+    }
+    h->noise_dirty = true;
+    h->assembled = h->factored = false;   // as ck_set_model: Sigma, its factor and the solved right-hand sides are stale
+    h->aux_state = 0;
+    h->lik_noise_valid = false;
     return 0;
 }
 
@@ -598,6 +646,7 @@ static int ensure_layout(ck_handle* h, bool need_panels = true) {
             for (int64_t j = 0; j < nk; ++j) h->perm[k][(size_t)j] = j;
         }
         h->trend_dirty = true;   // a new site order (also a re-layout: ck_factor's retry, option "site_order"): X follows it
+        h->noise_dirty = true;   // ... and so do the measurement-error variances
         for (int64_t j = 0; j < nk; ++j) {
             const int64_t e = h->perm[k][(size_t)j];
             hc[2 * (off + j)] = h->h_coords[k][2 * e];
@@ -813,9 +862,46 @@ static void next_worklist(ck_handle* h) {
 // internal (padded-order) 1-based index -> index in the caller's stacked order
 static int64_t external_index(const ck_handle* h, int64_t g) { return g > h->n0p ? g - (h->n0p - h->n[0]) : g; }
 
+// d_noise <- [s d | d] in the internal order (ck_set_noise); needs the layout.  noise_on: some s d > 0
+static int ensure_noise(ck_handle* h) {
+    if (!h->noise_dirty) return 0;
+    h->noise_on = false;
+    if (h->noise_var[0].empty() && (h->n_procs < 2 || h->noise_var[1].empty())) {
+        h->noise_dirty = false;
+        return 0;
+    }
+    const int64_t Np = h->Npad;
+    if (2 * Np > h->noise_cap) {
+        if (h->d_noise) HIPCHK(hipFree(h->d_noise));
+        h->d_noise = nullptr;
+        h->noise_cap = 0;
+        HIPCHK(hipMalloc((void**)&h->d_noise, (size_t)(2 * Np) * 8));   // outside the arena, as d_trendX: two rows
+        h->noise_cap = 2 * Np;
+    }
+    std::vector<double> nv((size_t)(2 * Np), 0.0);
+    for (int k = 0; k < h->n_procs && k < 2; ++k) {
+        if (h->noise_var[k].empty()) continue;
+        const int64_t off = k == 0 ? 0 : h->n0p;
+        for (int64_t j = 0; j < h->n[k]; ++j) {
+            const double d = h->noise_var[k][(size_t)h->perm[k][(size_t)j]];
+            nv[(size_t)(off + j)] = h->noise_scale[k] * d;
+            nv[(size_t)(Np + off + j)] = d;
+            if (h->noise_scale[k] * d > 0.0) h->noise_on = true;
+        }
+    }
+    HIPCHK(hipMemcpyAsync(h->d_noise, nv.data(), (size_t)(2 * Np) * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->noise_dirty = false;
+    return 0;
+}
+// s d per site for the kernels, or null: no noise set, or all of it zero (the bits of a handle that never saw ck_set_noise)
+static const double* noise_sd(const ck_handle* h) { return h->noise_on ? h->d_noise : nullptr; }
+
 extern "C" int ck_assemble_joint(ck_handle* h) {
     CHKH(h);
     if (ensure_layout(h)) return -1;
+    if (ensure_noise(h)) return -1;
+    h->lik_noise_valid = false;
 
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     bool fast_done = false;
@@ -827,9 +913,14 @@ extern "C" int ck_assemble_joint(ck_handle* h) {
             ck_launch_assemble_sigma(h->stream, fast, h->d_blk, h->d_tabs, h->d_coefptr, h->metric, h->s0, h->su,
                                      layout_of(h), pm, h->total_tiles, h->wl, fast ? h->assemble_queue : 0);
         }
-        if (!fast) break;
+        if (!fast) {
+            ck_launch_assemble_noise(h->stream, h->d_sigptr, noise_sd(h), layout_of(h));
+            break;
+        }
         ck_launch_assemble_fix(h->stream, false, h->d_blk, h->metric, 0, nullptr, 0, h->s0, layout_of(h), h->wl,
                                h->d_sigptr, nullptr);
+        // measurement-error variances on the diagonal, once per assembled Sigma (a second attempt writes every entry anew)
+        ck_launch_assemble_noise(h->stream, h->d_sigptr, noise_sd(h), layout_of(h));
         HIPCHK(hipEventRecord(h->ev1, h->stream));   // table kernel + exact pass; the count check below is host latency
         unsigned cnt = 0;
         HIPCHK(hipMemcpyAsync(&cnt, h->wl.count, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
@@ -3145,6 +3236,22 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
         for (int64_t w = 0; w < ngr; ++w)
             for (int k = 0; k < CK_LIK_NPAR; ++k) g[k] += part[(size_t)(w * CK_LIK_NPAR + k)];
         for (int k = 0; k < npar; ++k) grad[k] = g[k];
+        // ---- dl/ds_k = 1/2 sum_{a in k} G_aa d_a while G is in the Schur buffers (ck_loglik_noise_grad)
+        h->lik_noise_grad[0] = h->lik_noise_grad[1] = 0.0;
+        if (ensure_noise(h)) return -1;
+        if (!h->noise_var[0].empty() || (h->n_procs == 2 && !h->noise_var[1].empty())) {
+            double* d_np = nullptr;
+            HIPCHK(tmp.get(&d_np, (size_t)(2 * h->nK) * 8));
+            ck_launch_lik_noise_grad(h->stream, h->d_sch_ptr, h->nK, L, h->d_noise + Np, d_np);
+            HIPCHK(hipGetLastError());
+            std::vector<double> np2((size_t)(2 * h->nK));
+            HIPCHK(hipMemcpyAsync(np2.data(), d_np, np2.size() * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            for (int K = 0; K < h->nK; ++K)
+                for (int k = 0; k < 2; ++k) h->lik_noise_grad[k] += np2[(size_t)(2 * K + k)];
+            for (int k = 0; k < 2; ++k) h->lik_noise_grad[k] *= 0.5;
+        }
+        h->lik_noise_valid = true;
     }
     h->t_ms[29] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     return 0;
@@ -3158,6 +3265,17 @@ extern "C" int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad
 extern "C" int ck_loglik_reml(ck_handle* h, int want_grad, double* out4, double* grad, int64_t* info) {
     CHKH(h);
     return loglik_impl(h, want_grad, true, out4, grad, info);
+}
+
+extern "C" int ck_loglik_noise_grad(ck_handle* h, double* out2) {
+    CHKH(h);
+    if (!out2) return fail("ck_loglik_noise_grad: null argument");
+    if (!h->lik_noise_valid)
+        return fail("ck_loglik_noise_grad: no ck_loglik / ck_loglik_reml with want_grad != 0 has succeeded on this handle since the "
+                    "last ck_assemble_joint");
+    out2[0] = h->lik_noise_grad[0];
+    out2[1] = h->lik_noise_grad[1];
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -3183,6 +3301,8 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     const int up = u ? trend_total(h) : 0;   // trend rows of every local system
     const int upi = u ? h->trend_p[i] : 0;
     if (u && ensure_trend(h)) return -1;
+    if (ensure_noise(h)) return -1;
+    const double* nz = noise_sd(h);   // measurement-error variances on the diagonal of every local system (null: off)
     const int64_t mp = roundup(m, 64);
     DevTemps tmp;
     double *d_pc = nullptr, *d_p3 = nullptr, *d_pu = nullptr, *d_out = nullptr, *d_slab = nullptr;
@@ -3344,12 +3464,12 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     if (u)
         ck_launch_local_solve_u(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, h->z, layout_of(h),
                                 d_cnt, c0var, d_out, d_out + mp, h->d_tabs, h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb,
-                                cmax, Tr, d_beta, d_stat);
+                                cmax, Tr, d_beta, d_stat, nz);
     else
         for (const auto& bt : batches)
             ck_launch_local_solve(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, bt.first, bt.second - bt.first,
                                   mp, h->s0, h->z, layout_of(h), d_cnt, d_off, d_slab, c0var, d_out, d_out + mp, h->d_tabs,
-                                  h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb, cmax);
+                                  h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb, cmax, nz);
     HIPCHK(hipGetLastError());
     std::vector<hipEvent_t> ev_red;   // universal form: an event pair around every batch's reduction (ck_timings [50])
     struct EvFree {
@@ -3369,7 +3489,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
             const int nb = (int)(tb.second - tb.first);
             ck_launch_local_assemble_t(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, mp, h->s0, h->z,
                                        layout_of(h), bsys, nb, d_slab, h->d_tabs, h->d_coefptr, use_tab, h->su, d_pu,
-                                       h->d_chunkb, cmax, d_k0 + tb.first);
+                                       h->d_chunkb, cmax, d_k0 + tb.first, nz);
             if (u) ck_launch_local_trend_rows_t(h->stream, bsys, nb, d_slab, layout_of(h), Tr);
             const int kq_max = sysv[tb.first].kq;
             std::vector<int> kqv(nb);

@@ -480,6 +480,24 @@ void ck_launch_assemble_fix(hipStream_t s, bool aux_rows, const CkMatern* blk, i
     }
 }
 
+// Measurement-error variances (ck_set_noise), behind the table pass and k_assemble_fix: Sigma_gg += nz[g] for every data site
+// g -- the true diagonal by datum index, not "where h == 0" (two data at one place keep their nugget between them and get
+// no measurement error there).  nz: s_k d_a in the internal site order, npad values.  One thread per site; a zero adds nothing.
+__global__ __launch_bounds__(256) void k_assemble_noise(double* const* __restrict__ sigptr, const double* __restrict__ nz,
+                                                         CkLayout L) {
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    if (!(g < L.n0 || (g >= L.n0p && g < L.nend))) return;
+    const double v = nz[g];
+    if (v == 0.0) return;
+    const long K = g / CK_NB, r = g - K * CK_NB;
+    sigptr[K][r * CK_NB + r] += v;
+}
+
+void ck_launch_assemble_noise(hipStream_t s, double* const* sigptr, const double* nz, CkLayout L) {
+    if (!nz || L.nend <= 0) return;
+    k_assemble_noise<<<dim3((unsigned)((L.nend + 255) / 256)), dim3(256), 0, s>>>(sigptr, nz, L);
+}
+
 // dense a x b block (element-wise parity surface) ------------------------------------------
 __global__ __launch_bounds__(256) void k_cov_dense(const CkMatern* __restrict__ m, int metric, int add_nugget,
                                                     int mode, const double* __restrict__ a0,

@@ -68,6 +68,9 @@ void ck_launch_assemble_aux(hipStream_t s, bool fast, const CkMatern* blk, const
 void ck_launch_assemble_fix(hipStream_t s, bool aux_rows, const CkMatern* blk, int metric, int i_pred,
                             const double* pc, int64_t mpad, const double* c, CkLayout L, CkWorklist wl,
                             double* const* sigptr, double* aux);
+// measurement-error variances (ck_set_noise): Sigma_gg += nz[g] at every data site g (nz: npad values in the internal order,
+// zero where there is none); behind ck_launch_assemble_fix, once per assembled Sigma.  nz == null: no launch.
+void ck_launch_assemble_noise(hipStream_t s, double* const* sigptr, const double* nz, CkLayout L);
 // dense a x b block for one (i, j) Matern block; mode 0 = covariance, 1 = distance only
 void ck_launch_cov_dense(hipStream_t s, const CkMatern* blk_ij, int metric, int add_nugget, int mode,
                          const double* a0, const double* a1, const double* a2, int64_t a, const double* b0,
@@ -183,6 +186,10 @@ int64_t ck_lik_grad_groups(CkLayout L);
 void ck_launch_loglik_grad(hipStream_t s, double* const* G_dev, CkLayout L, int n_procs, int metric, const double* c,
                            const CkMatern* blk5, const double* dnu3, double sig1, double sig2, double rho, double* part);
 
+// part[2 K + k] = sum of G_aa d_a over the sites a of process k in block column K (d: npad variances in the internal order);
+// dl/ds_k = 1/2 sum_K part[2 K + k] (ck_loglik_noise_grad)
+void ck_launch_lik_noise_grad(hipStream_t s, double* const* G_dev, int nK, CkLayout L, const double* d, double* part);
+
 // ---- conditional simulation (ck_draws.hip) ---------------------------------------------------
 // on the Schur buffers sch[J] (packed block columns of S, nJ of them), sites k < m:
 // mask[k] = S_kk <= thr; S_kk = 1 where deflated, else S_kk + jit
@@ -267,7 +274,9 @@ void ck_launch_local_solve(hipStream_t s, const CkMatern* blk, int metric, int i
                            const double* pc, int64_t p_base, int64_t m, int64_t mpad, const double* sc, const double* z,
                            CkLayout L, const int* counts, const long long* slab_off, double* slab, double c0var,
                            double* pred, double* err, const CkTable* tabs, const double* const* coefs, int use_tab,
-                           const double* su, const double* pu, int k_hi, const double* cb, double cmax);
+                           const double* su, const double* pu, int k_hi, const double* cb, double cmax,
+                           const double* nz = nullptr /* ck_set_noise: s d per site in the internal order, added to the diagonal
+                           of every local system next to z[ga]; null: off (the same for the other local launches) */);
 int ck_local_lds_limit();
 
 // Large neighbourhoods (k > k_hi above): the "tiled" path.  The systems of a batch are factored TOGETHER,
@@ -300,7 +309,8 @@ void ck_launch_local_assemble_t(hipStream_t s, const CkMatern* blk, int metric, 
                                 const double* pc, int64_t mpad, const double* sc, const double* z, CkLayout L,
                                 const CkLocalSys* sys, int n_sys, double* slab, const CkTable* tabs,
                                 const double* const* coefs, int use_tab, const double* su, const double* pu,
-                                const double* cb, double cmax, int* k0buf /* n_sys ints of scratch */);
+                                const double* cb, double cmax, int* k0buf /* n_sys ints of scratch */,
+                                const double* nz = nullptr);
 // Columns are processed in groups of g 64-column blocks [g0, g0 + 64 g): block i of a group first receives the
 // updates of the group's earlier blocks (one pass, K = 64 i), then its diagonal block is factored and inverted and
 // the rows below are solved; the trailing matrix behind the group is updated once with K = 64 g (a g-th of the
@@ -343,7 +353,8 @@ void ck_launch_local_solve_u(hipStream_t s, const CkMatern* blk, int metric, int
                              const double* pc, int64_t m, int64_t mpad, const double* sc, const double* z, CkLayout L,
                              const int* counts, double c0var, double* pred, double* err, const CkTable* tabs,
                              const double* const* coefs, int use_tab, const double* su, const double* pu, int k_hi,
-                             const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status);
+                             const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status,
+                             const double* nz = nullptr);
 // behind ck_launch_local_assemble_t: the trend rows of the batch's systems
 void ck_launch_local_trend_rows_t(hipStream_t s, const CkLocalSys* sys, int n_sys, double* slab, CkLayout L, CkLocalTrend Tr);
 // k0buf: the process-0 neighbour counts ck_launch_local_assemble_t left

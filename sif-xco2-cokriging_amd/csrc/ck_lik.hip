@@ -113,6 +113,45 @@ __global__ __launch_bounds__(256) void k_loglik_grad(double* const* __restrict__
     }
 }
 
+// Derivative in the noise scales (ck_loglik_noise_grad): dl/ds_k = 1/2 sum_{a in k} G_aa d_a over the diagonal of the packed
+// G tiles.  One workgroup per block column; part[2 K], part[2 K + 1] = that column's sums of G_aa d_a for process 0 / 1 (the
+// host adds the columns in order and halves).  d: npad variances in the internal site order.  Fixed order, no atomics.
+__global__ __launch_bounds__(256) void k_lik_noise_grad(double* const* __restrict__ G, CkLayout L, const double* __restrict__ d,
+                                                         double* __restrict__ part) {
+    __shared__ double red[4][2];
+    const int K = blockIdx.x;
+    const double* Gk = G[K];
+    double s0 = 0.0, s1 = 0.0;
+    for (int j = threadIdx.x; j < CK_NB; j += 256) {
+        const long g = (long)K * CK_NB + j;
+        if (!lik_valid(L, g)) continue;
+        const double v = Gk[(long)j * CK_NB + j] * d[g];
+        if (g >= L.n0p)
+            s1 += v;
+        else
+            s0 += v;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s0 += __shfl_xor(s0, off);
+        s1 += __shfl_xor(s1, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6][0] = s0;
+        red[threadIdx.x >> 6][1] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const int k = threadIdx.x;
+        part[2 * K + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    }
+}
+
+void ck_launch_lik_noise_grad(hipStream_t s, double* const* G_dev, int nK, CkLayout L, const double* d, double* part) {
+    if (nK <= 0) return;
+    k_lik_noise_grad<<<dim3((unsigned)nK), dim3(256), 0, s>>>(G_dev, L, d, part);
+}
+
 int64_t ck_lik_grad_groups(CkLayout L) { return (L.npad / CK_NB) * CK_LIK_STRIPS(L.npad); }
 
 void ck_launch_loglik_grad(hipStream_t s, double* const* G_dev, CkLayout L, int n_procs, int metric, const double* c,

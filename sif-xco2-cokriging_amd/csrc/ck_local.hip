@@ -163,7 +163,8 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve(const CkMatern* __restri
                                                          double* __restrict__ slab, double c0var,
                                                          double* __restrict__ pred, double* __restrict__ err,
                                                          long p_base, LpTab T, const double* __restrict__ su,
-                                                         const double* __restrict__ pu, LpSearch R, int k_hi) {
+                                                         const double* __restrict__ pu, LpSearch R, int k_hi,
+                                                         const double* __restrict__ nz) {
     __shared__ double lS[(LP_KL + 2) * LP_KL];
     __shared__ int lidx[LP_KL];
     __shared__ int wsum[LP_TPB / 64];
@@ -228,6 +229,10 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve(const CkMatern* __restri
         S[(long)(k + 1) * ld + a] = z[ga];
     }
     __syncthreads();
+    if (nz) {   // measurement-error variances (ck_set_noise): the neighbour's s d on the true diagonal
+        for (int a = tid; a < k; a += LP_TPB) S[(long)a * ld + a] += nz[idx[a]];
+        __syncthreads();
+    }
     // ---- 3. Cholesky of the k x k block, the two extra rows ride along (forward substitution) ----
     for (int j = 0; j < k; ++j) {
         const double piv = S[(long)j * ld + j];
@@ -304,7 +309,8 @@ __global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(const CkMatern* _
                                                              double* __restrict__ slab, double c0var,
                                                              double* __restrict__ pred, double* __restrict__ err,
                                                              long p_base, LpTab T, const double* __restrict__ su,
-                                                             const double* __restrict__ pu, int k_hi, LpSearch R) {
+                                                             const double* __restrict__ pu, int k_hi, LpSearch R,
+                                                             const double* __restrict__ nz) {
     __shared__ __attribute__((aligned(16))) double lbuf[2 * LB_IB * (64 + 4)];
     double (*At)[64 + 4] = reinterpret_cast<double (*)[64 + 4]>(lbuf);                 // At[c][r] = strip of the tile's rows
     double (*Bt)[64 + 4] = reinterpret_cast<double (*)[64 + 4]>(lbuf + LB_IB * (64 + 4));   // Bt[c][r] = ... columns
@@ -364,6 +370,10 @@ __global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(const CkMatern* _
         S[(long)(k + 1) * ld + a] = z[ga];
     }
     __syncthreads();
+    if (nz) {   // measurement-error variances (ck_set_noise): the neighbour's s d on the true diagonal
+        for (int a = tid; a < k; a += LP_TPB) S[(long)a * ld + a] += nz[idx[a]];
+        __syncthreads();
+    }
     // ---- 3. blocked Cholesky; rows k, k + 1 ride along (forward substitution) ----
     const int ty = tid >> 4, tx = tid & 15;
     bool bad = false;
@@ -516,16 +526,17 @@ void ck_launch_local_solve(hipStream_t s, const CkMatern* blk, int metric, int i
                            const double* pc, int64_t p_base, int64_t m, int64_t mpad, const double* sc, const double* z,
                            CkLayout L, const int* counts, const long long* slab_off, double* slab, double c0var,
                            double* pred, double* err, const CkTable* tabs, const double* const* coefs, int use_tab,
-                           const double* su, const double* pu, int k_hi, const double* cb, double cmax) {
+                           const double* su, const double* pu, int k_hi, const double* cb, double cmax, const double* nz) {
     if (m <= 0) return;
     const LpTab T{tabs, coefs, use_tab};
     const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax};
     k_local_solve<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L,
-                                                             counts, slab_off, slab, c0var, pred, err, p_base, T, su, pu, R, k_hi);
+                                                             counts, slab_off, slab, c0var, pred, err, p_base, T, su, pu, R, k_hi,
+                                                             nz);
     if (slab && k_hi > LP_KL)   // some neighbourhood is larger than the LDS limit
         k_local_solve_big<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z,
                                                                      L, counts, slab_off, slab, c0var, pred, err,
-                                                                     p_base, T, su, pu, k_hi, R);
+                                                                     p_base, T, su, pu, k_hi, R, nz);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -620,7 +631,8 @@ __global__ __launch_bounds__(LT_TPB, 4) void k_local_assemble_t(const CkMatern* 
                                                                  const CkLocalSys* __restrict__ sys, int n_sys,
                                                                  double* __restrict__ slab, LpTab T,
                                                                  const double* __restrict__ su,
-                                                                 const int* __restrict__ k0in) {
+                                                                 const int* __restrict__ k0in,
+                                                                 const double* __restrict__ nz) {
     __shared__ double tab[(CK_TAB_DEG + 1) * CK_TAB_STRIDE];
     __shared__ double bu[3][LT_BC];
     __shared__ double au[3][LT_AC];
@@ -741,6 +753,10 @@ __global__ __launch_bounds__(LT_TPB, 4) void k_local_assemble_t(const CkMatern* 
             const int a = wl[e].x, b = wl[e].y;
             S[(long)a * ld + b] = lp_exact_pair(&blk[reg], metric, nug, s0, s1, s2, idx[a], idx[b]);
         }
+        if (nz && reg != 1) {   // measurement-error variances (ck_set_noise) on the diagonal of this launch's region
+            __syncthreads();
+            for (int a = alo + tid; a < ahi; a += LT_TPB) S[(long)a * ld + a] += nz[idx[a]];
+        }
     }
 }
 
@@ -786,7 +802,7 @@ void ck_launch_local_assemble_t(hipStream_t s, const CkMatern* blk, int metric, 
                                 const double* pc, int64_t mpad, const double* sc, const double* z, CkLayout L,
                                 const CkLocalSys* sys, int n_sys, double* slab, const CkTable* tabs,
                                 const double* const* coefs, int use_tab, const double* su, const double* pu,
-                                const double* cb, double cmax, int* k0buf) {
+                                const double* cb, double cmax, int* k0buf, const double* nz) {
     if (n_sys <= 0) return;
     const LpTab T{tabs, coefs, use_tab};
     const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax};
@@ -795,7 +811,8 @@ void ck_launch_local_assemble_t(hipStream_t s, const CkMatern* blk, int metric, 
     const int nreg = L.nend > L.n0p ? 3 : 1;               // a second process?
     const int grid = n_sys < 512 ? n_sys : 512;            // two workgroups per CU; they walk over the systems
     for (int reg = 0; reg < nreg; ++reg)
-        k_local_assemble_t<<<dim3((unsigned)grid), dim3(LT_TPB), 0, s>>>(blk, metric, reg, sc, L, sys, n_sys, slab, T, su, k0buf);
+        k_local_assemble_t<<<dim3((unsigned)grid), dim3(LT_TPB), 0, s>>>(blk, metric, reg, sc, L, sys, n_sys, slab, T, su, k0buf,
+                                                                         nz);
 }
 
 void ck_launch_local_reduce_t(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab,
@@ -869,7 +886,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve_u(const CkMatern* __rest
                                                            double* __restrict__ pred, double* __restrict__ err, LpTab T,
                                                            const double* __restrict__ su, const double* __restrict__ pu,
                                                            LpSearch R, int k_hi, CkLocalTrend Tr, double* __restrict__ beta,
-                                                           int* __restrict__ status) {
+                                                           int* __restrict__ status, const double* __restrict__ nz) {
     extern __shared__ __attribute__((aligned(16))) double lu_lds[];   // (LP_KL + nx) x LP_KL matrix | LU_EXTRA(p)
     __shared__ int lidx[LP_KL];
     __shared__ int wsum[LP_TPB / 64], wsum0[LP_TPB / 64];
@@ -938,6 +955,10 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve_u(const CkMatern* __rest
         S[(long)(k + 2 + j) * ld + a] = Tr.X[(long)j * L.npad + idx[a]];
     }
     __syncthreads();
+    if (nz) {   // measurement-error variances (ck_set_noise): the neighbour's s d on the true diagonal
+        for (int a = tid; a < k; a += LP_TPB) S[(long)a * ld + a] += nz[idx[a]];
+        __syncthreads();
+    }
     // ---- 3. Cholesky of the k x k block, the nx extra rows ride along (forward substitution) ----
     for (int j = 0; j < k; ++j) {
         const double piv = S[(long)j * ld + j];
@@ -981,14 +1002,14 @@ void ck_launch_local_solve_u(hipStream_t s, const CkMatern* blk, int metric, int
                              const double* pc, int64_t m, int64_t mpad, const double* sc, const double* z, CkLayout L,
                              const int* counts, double c0var, double* pred, double* err, const CkTable* tabs,
                              const double* const* coefs, int use_tab, const double* su, const double* pu, int k_hi,
-                             const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status) {
+                             const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status, const double* nz) {
     if (m <= 0) return;
     const LpTab T{tabs, coefs, use_tab};
     const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax};
     const int np = Tr.p0 + Tr.p1;
     const size_t lds = (size_t)((LP_KL + 2 + np) * LP_KL + LU_EXTRA(np)) * sizeof(double);   // 34.9 KB (p = 2) .. 47.2 KB (p = 16)
     k_local_solve_u<<<dim3((unsigned)m), dim3(LP_TPB), lds, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L, counts,
-                                                                 c0var, pred, err, T, su, pu, R, k_hi, Tr, beta, status);
+                                                                 c0var, pred, err, T, su, pu, R, k_hi, Tr, beta, status, nz);
 }
 
 // Tiled class: behind k_local_search_t (which has written identity rows up to kq - 2) the p rows [kq - 2 - p, kq - 2)

@@ -68,13 +68,26 @@ class Field:
     """Values and coordinates of one process at one time (the attributes of
     src/fields.py:59-95 that the predictors and variograms read)."""
 
-    def __init__(self, coords, values, coords_main=None, values_main=None, timestamp=np.nan, attrs=None):
+    def __init__(self, coords, values, coords_main=None, values_main=None, timestamp=np.nan, attrs=None,
+                 variance_estimate=None, variance_estimate_main=None):
         self.coords = np.ascontiguousarray(coords, dtype=np.float64).reshape(-1, 2)
         self.values = np.ascontiguousarray(values, dtype=np.float64).ravel()
         self.coords_main = self.coords if coords_main is None else np.ascontiguousarray(coords_main, dtype=np.float64).reshape(-1, 2)
         self.values_main = self.values if values_main is None else np.ascontiguousarray(values_main, dtype=np.float64).ravel()
         self.timestamp = timestamp
         self.size = len(self.values)
+        # the variance of the measurement error of every datum (src/fields.py:88), what measurement_error=True reads;
+        # the _main twin follows values_main
+        self.variance_estimate = None if variance_estimate is None else np.ascontiguousarray(variance_estimate, dtype=np.float64).ravel()
+        if self.variance_estimate is not None and len(self.variance_estimate) != len(self.values):
+            raise ValueError(f"variance_estimate has {len(self.variance_estimate)} values for {len(self.values)} data")
+        if variance_estimate_main is None:
+            self.variance_estimate_main = self.variance_estimate if values_main is None else None
+        else:
+            self.variance_estimate_main = np.ascontiguousarray(variance_estimate_main, dtype=np.float64).ravel()
+            if len(self.variance_estimate_main) != len(self.values_main):
+                raise ValueError(f"variance_estimate_main has {len(self.variance_estimate_main)} values for "
+                                 f"{len(self.values_main)} main data")
         # post-processing attributes of src/fields.py:345-375 (scale_fact, spatial_mean, ...)
         self.ds = _Attrs(attrs or {})
 

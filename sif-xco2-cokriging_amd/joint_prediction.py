@@ -37,6 +37,7 @@ from numpy.linalg import LinAlgError
 from . import native
 from .fields import metric_of
 from .model import configure_handle
+from .noise import apply_noise, noise_key, resolve_measurement_error
 from .trend import TrendDesign, check_trend
 
 try:  # the reference returns xarray objects; keep that when xarray exists
@@ -49,7 +50,7 @@ class Predictor:
     """Multivariate prediction framework (src/joint_prediction.py:13-33)."""
 
     def __init__(self, mod, mf, covariates=None, dist_units: str = "km", fast_dist: bool = True,
-                 device: int = 0, devices=None, trend=None) -> None:
+                 device: int = 0, devices=None, trend=None, measurement_error=None, noise_scale=(1.0, 1.0)) -> None:
         """``devices=[0, 1, ...]``: the multi-GPU form (BASELINE configs[3]) -- one worker process per entry, Sigma
         block-column-cyclic over them, panels exchanged over RCCL/xGMI at each Cholesky step, prediction points sharded
         (workers.RankPool + distributed.DistributedJoint; the same ordinal twice rehearses it on one GPU over gloo).
@@ -63,9 +64,17 @@ class Predictor:
         uncertainty added to ``pred_err`` (include/cokrige.h: ck_predict_universal).  After a call ``trend_coef`` holds
         the GLS coefficients and ``trend_cov`` their covariance.  A prediction site whose regressors are not finite gets
         NaN.  The universal forms of ``predict_blocks``, ``conditional_simulation``, ``cross_validation`` and the
-        multi-GPU path are not available."""
+        multi-GPU path are not available.
+
+        ``measurement_error``: per-observation measurement-error variances d_a, added to the true diagonal of Sigma as
+        ``noise_scale[k] * d_a`` (include/cokrige.h: ck_set_noise).  None: none, today's behaviour; True: every field's
+        ``variance_estimate``; a list with an array or None per process.  The predictions filter the measurement error out
+        (c0 and the prior variance are the field's); ``cross_validation`` predicts the withheld OBSERVATION, so its
+        ``pred_err`` contains the datum's own noise.  Single-device only."""
         if mod.n_procs != mf.n_procs:
             raise ValueError("Number of theoretical processes different from empirical processes.")
+        self.measurement_error, self.noise_scale = measurement_error, noise_scale
+        resolve_measurement_error(measurement_error, noise_scale, mf.fields, devices)   # refusals before any device work
         self.trend = check_trend(trend)
         if self.trend is not None and devices is not None and len(devices) > 1:
             raise NotImplementedError("universal cokriging (trend=...) runs on one device; the multi-GPU path is simple "
@@ -105,7 +114,17 @@ class Predictor:
                 c = np.delete(c, drop[1], axis=0)
                 v = np.delete(v, drop[1], axis=0)
             h.set_data(k, c, v)
+        self._set_noise(h, None if drop is None else [drop[1] if k == drop[0] else None for k in range(self.n_procs)])
         return h
+
+    def _noise(self):
+        return resolve_measurement_error(getattr(self, "measurement_error", None), getattr(self, "noise_scale", None),
+                                         self.mf.fields, self.devices)
+
+    def _set_noise(self, h, drop=None):
+        """``measurement_error`` on a handle whose data are loaded; ``drop[k]``: the data of process k that were left out."""
+        var, scales = self._noise()
+        apply_noise(h, var, scales, drop)
 
     @staticmethod
     def _factor(h):
@@ -138,6 +157,9 @@ class Predictor:
             c = np.ascontiguousarray(f.coords_main, dtype=np.float64)
             v = np.ascontiguousarray(f.values_main, dtype=np.float64)
             key += [c.shape, hash(c.tobytes()), hash(v.tobytes())]
+        if getattr(self, "measurement_error", None) is not None:
+            key.append(noise_key(*resolve_measurement_error(self.measurement_error, getattr(self, "noise_scale", None),
+                                                           self.mf.fields, self.devices)))
         return tuple(key)
 
     def invalidate(self):
@@ -649,6 +671,7 @@ class Predictor:
                         c = np.asarray(self.mf.fields[q].coords_main, dtype=np.float64)
                         v = np.asarray(self.mf.fields[q].values_main, dtype=np.float64)
                         h.set_data(q, np.delete(c, drop[q], axis=0), np.delete(v, drop[q], axis=0))
+                    self._set_noise(h, drop)
                     pred[sel], err[sel] = self._factor_predict(h, i, np.ascontiguousarray(np.asarray(f.coords_main, dtype=np.float64)[sel]))
                 finally:
                     h.close()

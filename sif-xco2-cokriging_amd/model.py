@@ -288,7 +288,8 @@ class MultivariateMatern:
         configure_handle(h, self)
         return h
 
-    def log_likelihood(self, mf, dist_units: str = "km", fast_dist: bool = True, gradient: bool = False, trend=None):
+    def log_likelihood(self, mf, dist_units: str = "km", fast_dist: bool = True, gradient: bool = False, trend=None,
+                       measurement_error=None, noise_scale=None):
         """Gaussian log-likelihood of the data the joint predictor uses (every field's ``coords_main`` / ``values_main``,
         zero mean as in simple cokriging) under the current parameters:
             l = -1/2 (N log 2 pi + log|Sigma| + z^T Sigma^-1 z),
@@ -298,10 +299,26 @@ class MultivariateMatern:
         ``trend`` (as ``Predictor(trend=...)``: "constant", "linear" or a callable): the restricted likelihood (REML) for an
         unknown trend X beta, ``ck_loglik_reml``:
             l_R = -1/2 ((N - p) log 2 pi + log|Sigma| + log|X^T Sigma^-1 X| + z^T P z),
-        without a log|X^T X| term."""
+        without a log|X^T X| term.
+
+        ``measurement_error`` (as ``Predictor(measurement_error=...)``: True or a list with an array or None per process)
+        and ``noise_scale`` (one scale per process, default 1): Sigma carries ``noise_scale[k] * d_a`` on its true diagonal
+        (``ck_set_noise``).  With ``gradient=True`` the call then returns (l, dl/dtheta, dl/ds): the derivatives in the
+        noise scales, one per process (0 for a process without noise), as a third value; without ``measurement_error``
+        the result has the shape it always had."""
+        from .noise import apply_noise, resolve_measurement_error
         from .trend import TrendDesign, check_trend
         check_trend(trend)
+        var, scales = resolve_measurement_error(measurement_error, noise_scale, mf.fields)
         h = self._lik_handle(mf, dist_units, fast_dist)
+        if var is None:
+            for k in range(self.n_procs):
+                h.set_noise(k, None)
+        else:
+            apply_noise(h, [d if d is not None else None for d in var], scales)
+            for k in range(self.n_procs):
+                if var[k] is None:
+                    h.set_noise(k, None)
         if trend is not None:
             cs = [np.asarray(mf.fields[k].coords_main, dtype=np.float64)[:, :2] for k in range(self.n_procs)]
             design = TrendDesign(trend, cs)
@@ -315,10 +332,12 @@ class MultivariateMatern:
         info, out3, g = h.loglik_reml(gradient) if trend is not None else h.loglik(gradient)
         if info != 0:
             raise LinAlgError(f"{info}-th leading minor of the array is not positive definite")
+        if gradient and var is not None:
+            return out3[0], g, h.loglik_noise_grad()[:self.n_procs]
         return (out3[0], g) if gradient else out3[0]
 
     def fit_likelihood(self, mf, guess: MaternParams = None, fixed=None, dist_units: str = "km", fast_dist: bool = True,
-                       trend=None):
+                       trend=None, measurement_error=None, noise_scale=None, fit_noise_scale: bool = False):
         """Maximum-likelihood fit: L-BFGS-B on -l with the analytic gradient, within ``params.get_bounds()``.
         ``guess`` as in ``fit``: None starts from the default parameters, else from the current ones with the bounds of
         ``guess``.  ``fixed``: parameter names or flat indices held at their starting values.
@@ -328,9 +347,22 @@ class MultivariateMatern:
         definite point, with the gradient of the last positive definite point, so that the line search backtracks; such
         evaluations are counted in ``fit_result.n_not_pd``.  Sets the parameters and ``self.fit_result``
         (FittedLikelihood).  ``trend``: maximise the restricted likelihood (REML) for that trend instead
-        (``log_likelihood(trend=...)``); ``fit_result.method`` is then "REML"."""
+        (``log_likelihood(trend=...)``); ``fit_result.method`` is then "REML".
+
+        ``measurement_error`` / ``noise_scale``: as ``log_likelihood``.  ``fit_noise_scale=True``: the scales of the processes
+        that have noise are estimated too (the reported retrieval uncertainties are known to be too small by a factor):
+        they join the optimiser's vector as log s over [log 1e-3, log 1e3], mapped onto [0, 1] like the other parameters,
+        starting at ``noise_scale``.  ``fit_result.noise_scale`` holds the scales used or found, and the AIC counts the
+        estimated ones."""
+        from .noise import resolve_measurement_error
         from .trend import check_trend
         check_trend(trend)
+        var, scales = resolve_measurement_error(measurement_error, noise_scale, mf.fields)
+        if fit_noise_scale and var is None:
+            raise ValueError("fit_noise_scale=True needs measurement_error")
+        s_free = [k for k in range(self.n_procs) if var is not None and var[k] is not None] if fit_noise_scale else []
+        s_lo, s_width = np.log(1e-3), np.log(1e3) - np.log(1e-3)
+        s_cur = None if scales is None else np.array(scales, dtype=float)
         if guess is None:
             init = self.params.reset_values().get_values().astype(float)
         else:
@@ -349,24 +381,44 @@ class MultivariateMatern:
                     raise ValueError(f"parameter index {f} out of range")
                 hold.add(int(f))
         free = np.array([k for k in range(len(names)) if k not in hold], dtype=int)
-        if free.size == 0:
+        if free.size == 0 and not s_free:
             raise ValueError("every parameter is fixed")
         lo, width = bounds[free, 0], bounds[free, 1] - bounds[free, 0]
         width = np.where(width > 0, width, 1.0)
         init = init.copy()
         init[free] = np.clip(init[free], bounds[free, 0], bounds[free, 1])
-        state = {"n_eval": 0, "n_not_pd": 0, "worst": None, "grad": np.zeros(free.size)}
+        state = {"n_eval": 0, "n_not_pd": 0, "worst": None, "grad": np.zeros(free.size + len(s_free))}
+        nf = free.size
 
         def theta_of(u):
             th = init.copy()
-            th[free] = lo + width * np.asarray(u, dtype=float)
+            th[free] = lo + width * np.asarray(u, dtype=float)[:nf]
             return th
+
+        def scales_of(u):
+            if s_cur is None:
+                return None
+            s = s_cur.copy()
+            for j, k in enumerate(s_free):
+                s[k] = np.exp(s_lo + s_width * float(np.asarray(u, dtype=float)[nf + j]))
+            return tuple(s.tolist())
+
+        def loglik(u):
+            out = self.log_likelihood(mf, dist_units, fast_dist, gradient=True, trend=trend, measurement_error=measurement_error,
+                                      noise_scale=scales_of(u))
+            return out if len(out) == 3 else (out[0], out[1], np.zeros(self.n_procs))
 
         def cost(u):
             state["n_eval"] += 1
             self.params.set_values(theta_of(u))
             try:
-                ll, g = self.log_likelihood(mf, dist_units, fast_dist, gradient=True, trend=trend)
+                ll, g, gs = loglik(u)
+                if s_free:   # dl/du = dl/ds * ds/du, s = exp(s_lo + s_width u)
+                    sc = np.array(scales_of(u))
+                    g = np.concatenate([np.asarray(g, dtype=float)[free] * width,
+                                        [gs[k] * sc[k] * s_width for k in s_free]])
+                else:
+                    g = np.asarray(g, dtype=float)[free] * width
             except LinAlgError:
                 ll = None
             if ll is None or not np.isfinite(ll) or not np.all(np.isfinite(g)):
@@ -376,21 +428,24 @@ class MultivariateMatern:
                     raise LinAlgError("the starting point of fit_likelihood is not positive definite")
                 return worst + 1e6 * (1.0 + abs(worst)), state["grad"].copy()
             f = -ll
-            gu = -np.asarray(g, dtype=float)[free] * width
+            gu = -g
             state["worst"] = f if state["worst"] is None else max(state["worst"], f)
             state["grad"] = gu
             return f, gu
 
         u0 = (init[free] - lo) / width
-        res = minimize(cost, u0, jac=True, method="L-BFGS-B", bounds=[(0.0, 1.0)] * free.size,
+        if s_free:
+            u0 = np.concatenate([u0, [(np.log(np.clip(s_cur[k], 1e-3, 1e3)) - s_lo) / s_width for k in s_free]])
+        res = minimize(cost, u0, jac=True, method="L-BFGS-B", bounds=[(0.0, 1.0)] * len(u0),
                        options={"maxiter": 1000, "ftol": 1e-13, "gtol": 1e-9})
         if res.success == False:   # noqa: E712  (as fit)
             warnings.warn("ERROR: optimization did not converge.")
         theta = theta_of(res.x)
         self.params.set_values(theta)
-        ll, g = self.log_likelihood(mf, dist_units, fast_dist, gradient=True, trend=trend)
+        ll, g, gs = loglik(res.x)
         self.fit_result = FittedLikelihood(self, ll, g, free, state["n_eval"], state["n_not_pd"], res,
-                                           method="ML" if trend is None else "REML")
+                                           method="ML" if trend is None else "REML", noise_scale=scales_of(res.x),
+                                           noise_gradient=None if var is None else gs, noise_free=s_free)
         return self
 
 
@@ -400,14 +455,18 @@ class FittedLikelihood:
     definite, and the optimiser's message.  ``method``: "ML", or "REML" for a fit with a trend (``loglik`` is then l_R)."""
 
     def __init__(self, model: MultivariateMatern, loglik: float, gradient, free, n_eval: int, n_not_pd: int, optim,
-                 method: str = "ML") -> None:
+                 method: str = "ML", noise_scale=None, noise_gradient=None, noise_free=()) -> None:
         self.method = method
         self.params = model.params
         self.names = list(model.params.get_names())
         self.loglik = float(loglik)
         self.gradient = np.asarray(gradient, dtype=float)
         self.free = [self.names[k] for k in free]
-        self.n_free = len(free)
+        self.n_free = len(free) + len(noise_free)
+        # measurement_error: the noise scales used (fit_noise_scale: found), dl/ds there, the processes whose scale was free
+        self.noise_scale = noise_scale
+        self.noise_gradient = None if noise_gradient is None else np.asarray(noise_gradient, dtype=float)
+        self.noise_free = list(noise_free)
         self.aic = 2.0 * self.n_free - 2.0 * self.loglik
         self.n_eval = int(n_eval)
         self.n_not_pd = int(n_not_pd)

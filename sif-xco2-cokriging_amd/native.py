@@ -53,6 +53,8 @@ _PROTOS = {
     "ck_cv_folds": [c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), c_int32, _dp, _dp, _dp, POINTER(c_int64)],
     "ck_loglik": [c_void_p, c_int, _dp, _dp, POINTER(c_int64)],
     "ck_set_trend": [c_void_p, c_int, _dp, c_int64, c_int],
+    "ck_set_noise": [c_void_p, c_int, _dp, c_int64, c_double],
+    "ck_loglik_noise_grad": [c_void_p, _dp],
     "ck_predict_universal": [c_void_p, c_int, _dp, c_int64, _dp, _dp, _dp, _dp, _dp],
     "ck_loglik_reml": [c_void_p, c_int, _dp, _dp, POINTER(c_int64)],
     "ck_sample": [c_void_p, _dp, _dp, c_int64],
@@ -411,6 +413,23 @@ class Handle:
             raise ValueError("the regressors must be a 2-D array (n_k, p_k)")
         _chk(lib().ck_set_trend(self._h, int(k), _p(F) if F.size else None, F.shape[0], F.shape[1]))
         self._trend_p[int(k)] = F.shape[1]
+
+    def set_noise(self, k, var, scale=1.0):
+        """Measurement-error variances of the data of process k, (n_k,) in the order of set_data, and their scale: Sigma gets
+        scale * var on its true diagonal (include/cokrige.h: ck_set_noise).  None clears them.  Sigma must be assembled
+        again afterwards."""
+        if var is None:
+            _chk(lib().ck_set_noise(self._h, int(k), None, 0, 1.0))
+            return
+        v = _f64(var).ravel()
+        _chk(lib().ck_set_noise(self._h, int(k), _p(v) if v.size else None, v.size, float(scale)))
+
+    def loglik_noise_grad(self):
+        """(dl/ds_0, dl/ds_1): the derivatives of the last loglik() / loglik_reml() with a gradient in the noise scales
+        (include/cokrige.h: ck_loglik_noise_grad); 0 for a process without noise."""
+        out = np.empty(2)
+        _chk(lib().ck_loglik_noise_grad(self._h, _p(out)))
+        return out
 
     def predict_universal(self, i, pcoords, f0=None):
         """Universal cokriging of process i on the resident factor (include/cokrige.h: ck_predict_universal).  f0: (m, p_i)

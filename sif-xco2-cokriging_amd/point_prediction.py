@@ -27,6 +27,7 @@ from .fields import metric_of
 from .joint_prediction import Predictor as _JointPredictor
 from .joint_prediction import prediction_coords, xr  # noqa: F401  (same helper, same signature)
 from .model import configure_handle
+from .noise import apply_noise, resolve_measurement_error
 from .trend import TrendDesign, check_trend
 
 
@@ -34,7 +35,7 @@ class Predictor:
     """Multivariate prediction framework (src/point_prediction.py:21-43)."""
 
     def __init__(self, mod, mf, covariates=None, dist_units: str = "km", fast_dist: bool = True, device: int = 0,
-                 devices=None, reserve_scratch=None, trend=None):
+                 devices=None, reserve_scratch=None, trend=None, measurement_error=None, noise_scale=(1.0, 1.0)):
         """``devices=[0, 1, ...]``: the prediction points are sharded over one worker process per GPU (observations
         replicated, no exchange inside the computation) -- what ``partitions`` is to the reference's CPU pool
         (src/point_prediction.py:45-52, 69-81).
@@ -43,9 +44,14 @@ class Predictor:
         the moving window), ``"linear"`` or a callable ``f(k, coords) -> (n, p_k)``, as for the joint predictor.  The trend
         is estimated by GLS in every neighbourhood (include/cokrige.h: ck_predict_local_universal); a site whose
         neighbourhood cannot carry it (rank deficient), or whose regressors are not finite, gets NaN.  After a call
-        ``trend_coef`` holds the (m, p) local coefficients."""
+        ``trend_coef`` holds the (m, p) local coefficients.
+
+        ``measurement_error`` / ``noise_scale``: as for the joint predictor -- every neighbour's ``noise_scale[k] * d_a``
+        goes on the diagonal of its local system (include/cokrige.h: ck_set_noise).  Single-device only."""
         if mod.n_procs != mf.n_procs:
             raise ValueError("Number of theoretical processes different from empirical processes.")
+        self.measurement_error, self.noise_scale = measurement_error, noise_scale
+        resolve_measurement_error(measurement_error, noise_scale, mf.fields, devices)   # refusals before any device work
         self.trend = check_trend(trend)
         if self.trend is not None and devices is not None and len(devices) > 1:
             raise NotImplementedError("universal cokriging (trend=...) runs on one device; the multi-GPU path is simple "
@@ -81,6 +87,7 @@ class Predictor:
             h.set_metric(metric_of(self.dist_units, self.fast_dist))
             for k in range(self.n_procs):
                 h.set_data(k, self.mf.fields[k].coords_main, self.mf.fields[k].values_main)
+            apply_noise(h, *resolve_measurement_error(self.measurement_error, self.noise_scale, self.mf.fields, self.devices))
             if self.reserve_scratch is not None:
                 h.local_reserve(0 if self.reserve_scratch == "auto" else int(self.reserve_scratch))
             self._h = h

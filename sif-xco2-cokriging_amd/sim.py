@@ -80,6 +80,7 @@ class BivariateRandomField:
         samples = [pd.merge(self.fields[i], coords[i]) for i in range(2)]
         for i, df in enumerate(samples):
             df["value"] += self.rng.normal(scale=epsilon[i], size=size)
+            df.attrs["epsilon"] = float(epsilon[i])   # to_fields: the variance of the noise added here
             df.rename(columns={"value": f"Z{i}"}, inplace=True)
         return samples
 
@@ -89,5 +90,9 @@ class BivariateRandomField:
         fl = []
         for j in ([0, 1] if i is None else [i]):
             s = samples[j].sort_values(["x", "y"])
-            fl.append(Field(s[["x", "y"]].values, s[f"Z{j}"].values))
+            eps = float(samples[j].attrs.get("epsilon", 0.0))
+            # where sample(epsilon=...) added noise, its variance: a simulated experiment can close the loop with
+            # Predictor(..., measurement_error=True)
+            var = np.full(len(s), eps * eps) if eps > 0.0 else None
+            fl.append(Field(s[["x", "y"]].values, s[f"Z{j}"].values, variance_estimate=var))
         return MultiField(fl)
