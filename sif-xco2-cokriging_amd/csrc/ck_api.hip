@@ -207,8 +207,8 @@ struct ck_handle {
     std::vector<hipEvent_t> ev_col, ev_pan;   // [K]: column K fully updated | panel K done
     // option "panel_group": G panels are factored (left-looking inside the group) before the trailing
     // matrix is updated ONCE with K = 512 G (ck_la.hip: gemm_tile_m); 1 = update after every panel
-    int panel_group = 0;   // 0 = automatic: 3 for 40 or more panels, else 1 (measured: the one-column in-group
-                           // launches cost more than the saved C traffic on small matrices)
+    int panel_group = 0;   // 0 = automatic (eff_group): 4 from 40 panels, 2 from 14, else 1 (measured: the one-column
+                           // in-group launches cost more than the saved C traffic on small matrices)
     int64_t local_slab_mb = 0;   // option "local_slab_mb": scratch budget of ck_predict_local (0 = automatic)
     int local_tile_min = 64;     // option "local_tile_min": neighbourhoods larger than this take the tiled path
     int local_group = 4;         // option "local_group": 64-column blocks per trailing update of the tiled path
@@ -1030,8 +1030,9 @@ static void gemm_timed_collect(ck_handle* h, int slot, hipEvent_t ref = nullptr)
 }
 
 // ---- the building blocks, on an explicit stream --------------------------------------------------
-// two-level panel step on block column K: 8 x (64 x 64 Cholesky, row solves, K = 64 update)
-static void syrk_update(ck_handle* h, hipStream_t st, int K0, int np, int J0, int Jstep, int nJ) {
+// Sigma update of the block columns J0, J0 + Jstep, ... (nJ of them) by the panels K0 .. K0 + np - 1: the only place this launch
+// is written
+static void sigma_update_on(ck_handle* h, hipStream_t st, int K0, int np, int J0, int Jstep, int nJ, bool timed) {
     unsigned long long* stamps = nullptr;
     if (h->d_stamps) {   // diagnostic: only launches that fit the stamp buffer are stamped
         const size_t wgs = (size_t)((h->Npad - (int64_t)J0 * CK_NB) / 128) * (CK_NB / 128) * (size_t)nJ;
@@ -1043,9 +1044,12 @@ static void syrk_update(ck_handle* h, hipStream_t st, int K0, int np, int J0, in
             h->stamp_grid[3] = np;
         }
     }
+    if (timed) gemm_timed_begin(h, st);
     ck_launch_syrk_group(st, h->d_sigptr, h->d_panelptr, K0, np, J0, Jstep, nJ, h->Npad, h->nend, stamps);
+    if (timed) gemm_timed_end(h, st);
 }
 
+// two-level panel step on block column K: 8 x (64 x 64 Cholesky, row solves, K = 64 update)
 // with_aux (the tall sweep, cooperative panel step only): the right-hand-side rows of block column K walk through the panel as
 // further workgroups of the same launch
 // split (with_aux only): the cooperative launch on the 512 x 512 head alone, then every row below it and every right-hand-side row
@@ -1128,9 +1132,7 @@ static void apply_sigma_on(ck_handle* h, int K, const double* P, int Jlo, int Jh
     if (J0 > Jhi) return;
     const int nJ = (Jhi - J0) / h->world + 1;
     (void)P;   // the group kernel reads panel K through d_panelptr[K] (own storage or receive buffer)
-    if (timed) gemm_timed_begin(h, st);
-    syrk_update(h, st, K, 1, J0, h->world, nJ);
-    if (timed) gemm_timed_end(h, st);
+    sigma_update_on(h, st, K, 1, J0, h->world, nJ, timed);
 }
 
 // forward substitution of the right-hand-side rows with the diagonal block of panel K
@@ -1147,6 +1149,15 @@ static int64_t aux_rows(const ck_handle* h, int K) {
 // rows of the right-hand-side block in front of its padding, for the thin last tile row (0: treat every row as live): the
 // prediction rows, the data row and the trend rows of a universal call
 static int64_t aux_live(const ck_handle* h) { return h->loo_g0 < 0 && h->tall_thin ? h->m + 1 + h->aux_trend : 0; }
+
+// right-hand-side update of the block columns J0 .. J0 + nJ - 1 by the panels K0 .. K0 + np - 1: the only place this launch is
+// written
+static void aux_group_on(ck_handle* h, hipStream_t st, int K0, int np, int J0, int nJ, bool timed) {
+    if (nJ <= 0) return;
+    if (timed) gemm_timed_begin(h, st);
+    ck_launch_aux_group(st, h->aux, h->mpad, h->d_panelptr, K0, np, J0, nJ, aux_rows(h, K0 + np - 1), h->nend, aux_live(h));
+    if (timed) gemm_timed_end(h, st);
+}
 
 static void aux_inner_on(ck_handle* h, int K, const double* P, hipStream_t st) {
     double* X = h->aux + (int64_t)K * h->mpad * CK_NB;
@@ -1168,14 +1179,9 @@ static void aux_inner_on(ck_handle* h, int K, const double* P, hipStream_t st) {
 
 // aux[J] -= aux[K] * P[(J-K)*NB .., :]^T for J in [Jlo, Jhi], batched over J
 static void aux_update_on(ck_handle* h, int K, const double* P, int Jlo, int Jhi, hipStream_t st, bool timed) {
-    const int nJ = Jhi - Jlo + 1;
-    if (nJ <= 0) return;
-    const int64_t rows = aux_rows(h, K);
-    timed = timed && h->time_gemm == 1;   // 2: only the Sigma updates are timed (one event list per sweep)
     (void)P;
-    if (timed) gemm_timed_begin(h, st);
-    ck_launch_aux_group(st, h->aux, h->mpad, h->d_panelptr, K, 1, Jlo, nJ, rows, h->nend, aux_live(h));
-    if (timed) gemm_timed_end(h, st);
+    // time_gemm 2: only the Sigma updates are timed (one event list per sweep)
+    aux_group_on(h, st, K, 1, Jlo, Jhi - Jlo + 1, timed && h->time_gemm == 1);
 }
 
 static int ensure_events(ck_handle* h) {
@@ -1246,21 +1252,14 @@ extern "C" int ck_panel_apply_group(ck_handle* h, int K0, int np, int what, int 
         if (J0 <= J_hi) {
             const int step = h->world * n_phase;
             const int nJ = (J_hi - J0) / step + 1;
-            gemm_timed_begin(h);
-            syrk_update(h, h->stream, K0, np, J0, step, nJ);
-            gemm_timed_end(h);
+            sigma_update_on(h, h->stream, K0, np, J0, step, nJ, true);
         }
     }
     if ((what & CK_APPLY_AUX) && h->mpad > 0) {
         // right-hand-side block columns: piece `phase` of n_phase contiguous pieces of [J_lo, J_hi]
         const int tot = J_hi - J_lo + 1, per = (tot + n_phase - 1) / n_phase;
         const int a = J_lo + phase * per, b = std::min(J_hi, a + per - 1);
-        if (a <= b) {
-            const bool timed = h->time_gemm == 1;
-            if (timed) gemm_timed_begin(h);
-            ck_launch_aux_group(h->stream, h->aux, h->mpad, h->d_panelptr, K0, np, a, b - a + 1, aux_rows(h, K0 + np - 1), h->nend, aux_live(h));
-            if (timed) gemm_timed_end(h);
-        }
+        aux_group_on(h, h->stream, K0, np, a, b - a + 1, h->time_gemm == 1);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -1273,6 +1272,21 @@ extern "C" int ck_panel_aux_solve(ck_handle* h, int K) {
     if (!P) return fail("panel " + std::to_string(K) + " is not readable on this rank");
     if (h->mpad > 0) aux_inner_on(h, K, P, h->stream);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// The cooperative panel step's error word (d_coop[16]): nonzero when a workgroup of k_panel_coop gave up waiting for a pivot block
+// (bounded spin, option "coop_spins": ~2 s; never observed outside the test hook "coop_inject_panel"), which leaves a factor --
+// and an info word -- that are not to be trusted.  Read behind a synchronised stream.
+static int coop_error(ck_handle* h, unsigned* werr) {
+    *werr = 0;
+    HIPCHK(hipMemcpy(werr, h->d_coop + 16, sizeof(*werr), hipMemcpyDeviceToHost));
+    return 0;
+}
+// after a timed-out step: clear the word and switch the cooperative step off for this handle; redoing or failing is the caller's
+static int coop_switch_off(ck_handle* h) {
+    HIPCHK(hipMemset(h->d_coop + 16, 0, sizeof(unsigned)));
+    h->panel_fused &= ~16;
     return 0;
 }
 
@@ -1292,10 +1306,9 @@ extern "C" int ck_factor_info(ck_handle* h, int64_t* info) {
     HIPCHK(hipStreamSynchronize(h->stream));
     if (h->panel_fused & 16) {                     // step-wise form: a timed-out cooperative panel step is an error here
         unsigned werr = 0;                         // (ck_factor repeats the factorisation instead)
-        HIPCHK(hipMemcpy(&werr, h->d_coop + 16, sizeof(werr), hipMemcpyDeviceToHost));
+        if (coop_error(h, &werr)) return -1;
         if (werr != 0) {
-            HIPCHK(hipMemset(h->d_coop + 16, 0, sizeof(unsigned)));
-            h->panel_fused &= ~16;
+            if (coop_switch_off(h)) return -1;
             return fail("cooperative panel step timed out waiting for a pivot block (option panel_fused bit 4 now off): sweep again");
         }
     }
@@ -1303,10 +1316,9 @@ extern "C" int ck_factor_info(ck_handle* h, int64_t* info) {
     return 0;
 }
 
-// automatic: 4 from 40 panels on (round 4; 3 in rounds 1-3: interleaved A/B at N = 40 000, G = 3 / 4 / 5 / 6 with their best first
-// groups: 491.0 / 488.2 / 489.5 / 489.2 ms), 1 below
-// automatic group size (measured with scripts/ab_tall.py, round 4: groups of two pay from 14 panels -- N = 10 000: 23.2 -> 22.4 ms --,
-// groups of four from 40)
+// automatic group size (round 4): groups of two pay from 14 panels (scripts/ab_tall.py, N = 10 000: 23.2 -> 22.4 ms), groups of
+// four from 40 (3 in rounds 1-3: interleaved A/B at N = 40 000, G = 3 / 4 / 5 / 6 with their best first groups: 491.0 / 488.2 /
+// 489.5 / 489.2 ms), 1 below
 static int eff_group(const ck_handle* h) { return h->panel_group > 0 ? h->panel_group : (h->nK >= 40 ? 4 : h->nK >= 14 ? 2 : 1); }
 
 // Group boundaries of the single-process sweeps (every form -- ck_factor / ck_predict, the two overlapped sweeps, the tall
@@ -1341,89 +1353,91 @@ static bool factor_lookahead(const ck_handle* h) {
     return (h->panel_fused & 16) && h->panel_group == 0 && h->world == 1 && h->nK >= 12 && h->nK < 64;
 }
 
-static int factor_sweep(ck_handle* h) {
-    h->gemm_ev_used = 0;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    if (factor_lookahead(h)) {
-        // Look-ahead: as soon as panel K has updated block column K + 1, the panel step of K + 1
-        // starts on the side stream and runs under the update of the columns K + 2.. by panel K.
-        if (ensure_events(h)) return -1;
-        hipStream_t M = h->stream, S = h->side;
-        panel_factor_on(h, 0, M);
-        for (int K = 0; K < h->nK; ++K) {
-            if (K > 0) HIPCHK(hipStreamWaitEvent(M, h->ev_pan[K], 0));
-            if (K + 1 < h->nK) {
-                apply_sigma_on(h, K, h->sig[K], K + 1, K + 1, M, false);
-                HIPCHK(hipEventRecord(h->ev_col[K + 1], M));
-                HIPCHK(hipStreamWaitEvent(S, h->ev_col[K + 1], 0));
-                panel_factor_on(h, K + 1, S);
-                HIPCHK(hipEventRecord(h->ev_pan[K + 1], S));
-                apply_sigma_on(h, K, h->sig[K], K + 2, h->nK - 1, M, true);
-            }
-        }
-        HIPCHK(hipGetLastError());
-    } else if (eff_group(h) <= 1) {
-        for (int K = 0; K < h->nK; ++K) {
-            if (ck_panel_factor(h, K)) return -1;
-            if (ck_panel_apply(h, K, CK_APPLY_SIGMA)) return -1;
-        }
-    } else {
-        // Groups of G panels: inside a group block column K first receives the updates of the group's
-        // earlier panels in one pass (K dimension 512 g), then its panel step; the trailing matrix
-        // beyond the group is updated once with K = 512 G -- a quarter of the C traffic of G = 1.
-        const std::vector<int> gs = group_plan(h, eff_group(h));
-        for (size_t gi = 0; gi + 1 < gs.size(); ++gi) {
-            const int K0 = gs[gi], Gc = gs[gi + 1] - gs[gi];
-            for (int g = 0; g < Gc; ++g) {
-                if (g > 0) {
-                    gemm_timed_begin(h);
-                    syrk_update(h, h->stream, K0, g, K0 + g, 1, 1);
-                    gemm_timed_end(h);
-                }
-                panel_factor_on(h, K0 + g, h->stream);
-            }
-            if (K0 + Gc < h->nK) {
-                gemm_timed_begin(h);
-                syrk_update(h, h->stream, K0, Gc, K0 + Gc, 1, h->nK - K0 - Gc);
-                gemm_timed_end(h);
-            }
-        }
-        HIPCHK(hipGetLastError());
+// ---- the schedules of the single-process sweeps, each written once ------------------------------------
+// A sweep is a STEP per panel -- Sigma's panel step, the right-hand-side rows' walk through the panel, or both in one launch --
+// and an UPDATE of later block columns by a run of panels, both on an explicit stream: step(st, K) and update(st, K0, np, J0, nJ),
+// the block columns J0 .. J0 + nJ - 1 by the panels K0 .. K0 + np - 1.  The four that every form but the tall sweep is made of:
+static auto sigma_step(ck_handle* h) {
+    return [h](hipStream_t st, int K) { panel_factor_on(h, K, st); };
+}
+static auto aux_step(ck_handle* h) {
+    return [h](hipStream_t st, int K) { aux_inner_on(h, K, h->sig[K], st); };
+}
+static auto sigma_update(ck_handle* h, bool timed) {
+    return [h, timed](hipStream_t st, int K0, int np, int J0, int nJ) { sigma_update_on(h, st, K0, np, J0, 1, nJ, timed); };
+}
+static auto aux_update(ck_handle* h, bool timed) {
+    return [h, timed](hipStream_t st, int K0, int np, int J0, int nJ) { aux_group_on(h, st, K0, np, J0, nJ, timed); };
+}
+
+// The chain of one panel group: block column K0 + q first receives the updates of the group's earlier panels in one pass
+// (K dimension 512 q), then its step.
+template <class Step, class Update>
+static void group_chain(hipStream_t st, int K0, int Gc, Step step, Update update) {
+    for (int q = 0; q < Gc; ++q) {
+        if (q > 0) update(st, K0, q, K0 + q, 1);
+        step(st, K0 + q);
     }
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
+}
+
+// One group of the grouped pass on one stream: its chain, then the trailing matrix beyond the group is updated once with
+// K = 512 G -- a quarter of the C traffic of G = 1.  chain_done (may be null) is recorded between the two: the group's panels
+// are final.
+template <class Step, class Update>
+static int grouped_pass(ck_handle* h, hipStream_t st, int K0, int Gc, Step step, Update update, hipEvent_t chain_done = nullptr) {
+    group_chain(st, K0, Gc, step, update);
+    if (chain_done) HIPCHK(hipEventRecord(chain_done, st));
+    if (K0 + Gc < h->nK) update(st, K0, Gc, K0 + Gc, h->nK - K0 - Gc);
     return 0;
 }
 
-// The same sweep with the look-ahead of tall_sweeps (round 4; ck_predict on a resident factor -- the second field of a
-// Predictor, the sites of a new grid): stream C (high priority) carries the chain of group g -- the one-column in-group updates
-// (280 tiles: they fill 55 % of the chip) and the rows' walk through each panel -- and A(g), the update of the NEXT group's block
-// columns; stream T carries B1(g) / B2(g), the update of everything beyond.  The chain of group g + 1 runs under the bulk of group g
-// instead of in front of it.  Same launches on the same operands in the same order per block column: same bits.
-static int solve_sweep_la(ck_handle* h) {
+// Look-ahead per panel: as soon as panel K has updated block column K + 1, the step of K + 1 starts on the side stream and runs
+// under the update of the columns K + 2.. by panel K.  update(K, Jlo, Jhi, timed): the block columns Jlo .. Jhi by panel K, on
+// the handle's own stream.
+template <class Step, class Update>
+static int panel_lookahead(ck_handle* h, Step step, Update update) {
     if (ensure_events(h)) return -1;
-    if (!h->side_lo) HIPCHK(hipStreamCreateWithFlags(&h->side_lo, hipStreamNonBlocking));
+    hipStream_t M = h->stream, S = h->side;
+    step(M, 0);
+    for (int K = 0; K < h->nK; ++K) {
+        if (K > 0) HIPCHK(hipStreamWaitEvent(M, h->ev_pan[K], 0));
+        if (K + 1 < h->nK) {
+            update(K, K + 1, K + 1, false);
+            HIPCHK(hipEventRecord(h->ev_col[K + 1], M));
+            HIPCHK(hipStreamWaitEvent(S, h->ev_col[K + 1], 0));
+            step(S, K + 1);
+            HIPCHK(hipEventRecord(h->ev_pan[K + 1], S));
+            update(K, K + 2, h->nK - 1, true);
+        }
+    }
+    return 0;
+}
+
+// Look-ahead over panel groups (solve_sweep_la, fused_sweeps_la, tall_sweeps), three streams.  C (the side stream, high priority)
+// carries the critical path -- per panel group g its chain and then A(g), the update of the NEXT group's block columns by group g,
+// which is all the next chain waits for; T (side_lo) carries the bulk of the trailing updates, B1(g) = group g -> block columns of
+// group g + 2 and B2(g) = group g -> everything beyond.  Every block column still receives its updates in the order of the
+// sequential sweep (group 0, 1, 2, ... each in one launch with K = 512 G), so the result has the same bits; what changes is that
+// the latency-bound chain of group g + 1 runs UNDER the bulk of group g instead of in front of it.
+//   C:  chain(g) -> [ev_pan g] -> wait ev_col g - 1 -> A(g) -> chain(g + 1) ...
+//   T:  wait ev_pan g -> B1(g) -> [ev_col g] -> B2(g) -> wait ev_pan g + 1 ...
+//   M:  wait ev_pan g -> follow(g, K0, Gc), which enqueues that wait itself (fused_sweeps_la: the substitution of group g)
+// b2m (option "tall_b2_stream"; never with a follower, whose work M carries): B2(g) on the handle's own stream M instead of behind
+// B1(g) on T -- the two only need group g's panels, so the partly filled last round of B1(g) runs beside B2(g)'s tiles instead of
+// in front of them.  B1(g) then waits for B2(g - 1), the last writer of its block columns [ev_b2 g - 1]; B2(g) follows B2(g - 1)
+// in stream order.
+// The callers open the sweep (ev0 on M, C and T wait for it) and close it, each with its own events.
+// (an event is always recorded, in host order, before the wait on it is enqueued: a wait on a never-recorded event is a no-op)
+template <class Step, class Update, class Follow>
+static int group_lookahead(ck_handle* h, const std::vector<int>& gs, bool b2m, Step step, Update update, Follow follow) {
     hipStream_t C = h->side, T = h->side_lo, M = h->stream;
-    const std::vector<int> gs = group_plan(h, eff_group(h));
     const int ng = (int)gs.size() - 1;
     auto first = [&](int g) { return gs[(size_t)g]; };
     auto count = [&](int g) { return gs[(size_t)g + 1] - gs[(size_t)g]; };
-    auto update = [&](hipStream_t st, int K0, int np, int J0, int nJ) {
-        if (nJ <= 0) return;
-        gemm_timed_begin(h, st);
-        ck_launch_aux_group(st, h->aux, h->mpad, h->d_panelptr, K0, np, J0, nJ, aux_rows(h, K0 + np - 1), h->nend, aux_live(h));
-        gemm_timed_end(h, st);
-    };
-    const bool b2m = h->tall_b2_stream != 0;
-    HIPCHK(hipEventRecord(h->ev0, M));   // (ev0 / ev1 are free between ck_aux_begin and ck_aux_finish)
-    HIPCHK(hipStreamWaitEvent(C, h->ev0, 0));
-    HIPCHK(hipStreamWaitEvent(T, h->ev0, 0));
     for (int g = 0; g < ng; ++g) {
         const int K0 = first(g), Gc = count(g);
-        for (int q = 0; q < Gc; ++q) {
-            if (q > 0) update(C, K0, q, K0 + q, 1);
-            aux_inner_on(h, K0 + q, h->sig[K0 + q], C);
-        }
-        HIPCHK(hipEventRecord(h->ev_pan[g], C));   // group g's right-hand-side block columns are final
+        group_chain(C, K0, Gc, step, update);
+        HIPCHK(hipEventRecord(h->ev_pan[g], C));   // group g's block columns are final
         if (g + 1 < ng) {
             if (g >= 1) HIPCHK(hipStreamWaitEvent(C, h->ev_col[g - 1], 0));   // B1(g - 1) wrote the same block columns
             update(C, K0, Gc, first(g + 1), count(g + 1));                    // A(g)
@@ -1436,10 +1450,52 @@ static int solve_sweep_la(ck_handle* h) {
         }
         if (g + 3 < ng) {
             if (b2m) HIPCHK(hipStreamWaitEvent(M, h->ev_pan[g], 0));
-            update(b2m ? M : T, K0, Gc, first(g + 3), h->nK - first(g + 3));   // B2(g): beside B1(g) on the handle's own stream
+            update(b2m ? M : T, K0, Gc, first(g + 3), h->nK - first(g + 3));   // B2(g)
         }
         if (b2m) HIPCHK(hipEventRecord(h->ev_b2[g], M));
+        if (follow(g, K0, Gc)) return -1;
     }
+    return 0;
+}
+static int no_follower(int, int, int) { return 0; }
+
+static int factor_sweep(ck_handle* h) {
+    h->gemm_ev_used = 0;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    if (factor_lookahead(h)) {
+        if (panel_lookahead(h, sigma_step(h), [h](int K, int Jlo, int Jhi, bool timed) {
+                apply_sigma_on(h, K, h->sig[K], Jlo, Jhi, h->stream, timed);
+            }))
+            return -1;
+        HIPCHK(hipGetLastError());
+    } else if (eff_group(h) <= 1) {
+        for (int K = 0; K < h->nK; ++K) {
+            if (ck_panel_factor(h, K)) return -1;
+            if (ck_panel_apply(h, K, CK_APPLY_SIGMA)) return -1;
+        }
+    } else {
+        const std::vector<int> gs = group_plan(h, eff_group(h));
+        for (size_t gi = 0; gi + 1 < gs.size(); ++gi)
+            if (grouped_pass(h, h->stream, gs[gi], gs[gi + 1] - gs[gi], sigma_step(h), sigma_update(h, true))) return -1;
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    return 0;
+}
+
+// The grouped forward sweep with the look-ahead over groups (round 4; ck_predict on a resident factor -- the second field of a
+// Predictor, the sites of a new grid): the chain of group g is the one-column in-group updates (280 tiles: they fill 55 % of
+// the chip) and the rows' walk through each panel.  Same launches on the same operands in the same order per block column: same bits.
+static int solve_sweep_la(ck_handle* h) {
+    if (ensure_events(h)) return -1;
+    if (!h->side_lo) HIPCHK(hipStreamCreateWithFlags(&h->side_lo, hipStreamNonBlocking));
+    hipStream_t C = h->side, T = h->side_lo, M = h->stream;
+    const std::vector<int> gs = group_plan(h, eff_group(h));
+    HIPCHK(hipEventRecord(h->ev0, M));   // (ev0 / ev1 are free between ck_aux_begin and ck_aux_finish)
+    HIPCHK(hipStreamWaitEvent(C, h->ev0, 0));
+    HIPCHK(hipStreamWaitEvent(T, h->ev0, 0));
+    if (group_lookahead(h, gs, h->tall_b2_stream != 0, aux_step(h), aux_update(h, true), no_follower)) return -1;
+    // (ev2 / ev3 are not free: ck_predict_universal and others bracket solve_sweep with them)
     HIPCHK(hipEventRecord(h->ev1, C));
     HIPCHK(hipEventRecord(h->ev_col[(size_t)h->nK], T));   // (ensure_events: nK + 1 entries, the groups use at most nK)
     HIPCHK(hipStreamWaitEvent(M, h->ev1, 0));
@@ -1453,42 +1509,17 @@ static int solve_sweep(ck_handle* h) {
     const bool la = h->solve_la >= 0 ? h->solve_la != 0 : h->nK >= 40;
     if (la && h->world == 1 && h->loo_g0 < 0 && (h->panel_fused & 2) && eff_group(h) > 1 && h->side) return solve_sweep_la(h);
     if (h->lookahead > 0) {
-        if (ensure_events(h)) return -1;
-        hipStream_t M = h->stream, S = h->side;
-        aux_inner_on(h, 0, h->sig[0], M);
-        for (int K = 0; K < h->nK; ++K) {
-            if (K > 0) HIPCHK(hipStreamWaitEvent(M, h->ev_pan[K], 0));
-            if (K + 1 < h->nK) {
-                aux_update_on(h, K, h->sig[K], K + 1, K + 1, M, false);
-                HIPCHK(hipEventRecord(h->ev_col[K + 1], M));
-                HIPCHK(hipStreamWaitEvent(S, h->ev_col[K + 1], 0));
-                aux_inner_on(h, K + 1, h->sig[K + 1], S);
-                HIPCHK(hipEventRecord(h->ev_pan[K + 1], S));
-                aux_update_on(h, K, h->sig[K], K + 2, h->nK - 1, M, true);
-            }
-        }
+        if (panel_lookahead(h, aux_step(h), [h](int K, int Jlo, int Jhi, bool timed) {
+                aux_update_on(h, K, h->sig[K], Jlo, Jhi, h->stream, timed);
+            }))
+            return -1;
     } else if (eff_group(h) <= 1) {
         for (int K = 0; K < h->nK; ++K)
             if (ck_panel_apply(h, K, CK_APPLY_AUX)) return -1;
     } else {
         const std::vector<int> gs = group_plan(h, eff_group(h));
-        for (size_t gi = 0; gi + 1 < gs.size(); ++gi) {
-            const int K0 = gs[gi], Gc = gs[gi + 1] - gs[gi];
-            for (int g = 0; g < Gc; ++g) {
-                if (g > 0) {
-                    gemm_timed_begin(h);
-                    ck_launch_aux_group(h->stream, h->aux, h->mpad, h->d_panelptr, K0, g, K0 + g, 1, aux_rows(h, K0 + g - 1), h->nend, aux_live(h));
-                    gemm_timed_end(h);
-                }
-                aux_inner_on(h, K0 + g, h->sig[K0 + g], h->stream);
-            }
-            if (K0 + Gc < h->nK) {
-                gemm_timed_begin(h);
-                ck_launch_aux_group(h->stream, h->aux, h->mpad, h->d_panelptr, K0, Gc, K0 + Gc, h->nK - K0 - Gc,
-                                    aux_rows(h, K0 + Gc - 1), h->nend, aux_live(h));
-                gemm_timed_end(h);
-            }
-        }
+        for (size_t gi = 0; gi + 1 < gs.size(); ++gi)
+            if (grouped_pass(h, h->stream, gs[gi], gs[gi + 1] - gs[gi], aux_step(h), aux_update(h, true))) return -1;
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -1514,19 +1545,9 @@ static int fused_sweeps(ck_handle* h) {
     if (M != h->stream) HIPCHK(hipStreamWaitEvent(M, h->ev0, 0));
     for (int ge = 0; ge + 1 < (int)gs.size(); ++ge) {
         const int K0 = gs[ge], Gc = gs[ge + 1] - gs[ge];
-        for (int g = 0; g < Gc; ++g) {
-            if (g > 0) syrk_update(h, F, K0, g, K0 + g, 1, 1);
-            panel_factor_on(h, K0 + g, F);
-        }
-        HIPCHK(hipEventRecord(h->ev_pan[ge], F));   // the group's panels are final
-        if (K0 + Gc < h->nK) syrk_update(h, F, K0, Gc, K0 + Gc, 1, h->nK - K0 - Gc);
+        if (grouped_pass(h, F, K0, Gc, sigma_step(h), sigma_update(h, false), h->ev_pan[ge])) return -1;
         HIPCHK(hipStreamWaitEvent(M, h->ev_pan[ge], 0));
-        for (int g = 0; g < Gc; ++g) {
-            if (g > 0) ck_launch_aux_group(M, h->aux, h->mpad, h->d_panelptr, K0, g, K0 + g, 1, aux_rows(h, K0 + g - 1), h->nend, aux_live(h));
-            aux_inner_on(h, K0 + g, h->sig[K0 + g], M);
-        }
-        if (K0 + Gc < h->nK)
-            ck_launch_aux_group(M, h->aux, h->mpad, h->d_panelptr, K0, Gc, K0 + Gc, h->nK - K0 - Gc, aux_rows(h, K0 + Gc - 1), h->nend, aux_live(h));
+        if (grouped_pass(h, M, K0, Gc, aux_step(h), aux_update(h, false))) return -1;
     }
     HIPCHK(hipEventRecord(h->ev1, F));               // end of the factorisation
     HIPCHK(hipEventRecord(h->ev2, M));               // end of the substitution
@@ -1537,53 +1558,21 @@ static int fused_sweeps(ck_handle* h) {
     return 0;
 }
 
-// The same with a LOOK-AHEAD inside the factorisation (option "fused_la"): three streams.  C (high priority) carries the
-// critical path -- per panel group g its chain (panel steps and in-group updates) and then A(g), the update of the NEXT
-// group's block columns by group g, which is all the next chain waits for; T carries the bulk of the trailing updates,
-// B1(g) = group g -> block columns of group g + 2 and B2(g) = group g -> everything beyond; the main stream carries the
-// substitution as before.  Every block column still receives its updates in the order of the sequential sweep (group 0,
-// 1, 2, ... each in one launch with K = 512 G), so the factor has the same bits; what changes is that the latency-bound
-// chain of group g + 1 runs UNDER the bulk of group g instead of in front of it.
-//   C:  chain(g) -> [ev_chain g] -> wait B1(g - 1) -> A(g) -> chain(g + 1) ...
-//   T:  wait ev_chain g -> B1(g) -> [ev_B1 g] -> B2(g) -> wait ev_chain g + 1 ...
-//   M:  wait ev_chain g -> substitution of group g
-// (an event is always recorded, in host order, before the wait on it is enqueued: a wait on a never-recorded event is a no-op)
+// The same with a LOOK-AHEAD inside the factorisation (option "fused_la"): group_lookahead on Sigma, and the main stream
+// carries the substitution as before, one panel group behind the chain.
 static int fused_sweeps_la(ck_handle* h) {
     if (ensure_events(h)) return -1;
     if (!h->side_lo) HIPCHK(hipStreamCreateWithFlags(&h->side_lo, hipStreamNonBlocking));
     hipStream_t C = h->side, T = h->side_lo, M = h->stream;
     const std::vector<int> gs = group_plan(h, h->fused_group > 0 ? h->fused_group : eff_group(h));
-    const int ng = (int)gs.size() - 1;
-    auto first = [&](int g) { return gs[(size_t)g]; };
-    auto count = [&](int g) { return gs[(size_t)g + 1] - gs[(size_t)g]; };
     HIPCHK(hipEventRecord(h->ev0, M));
     HIPCHK(hipStreamWaitEvent(C, h->ev0, 0));
     HIPCHK(hipStreamWaitEvent(T, h->ev0, 0));
-    for (int g = 0; g < ng; ++g) {
-        const int K0 = first(g), Gc = count(g);
-        for (int q = 0; q < Gc; ++q) {
-            if (q > 0) syrk_update(h, C, K0, q, K0 + q, 1, 1);
-            panel_factor_on(h, K0 + q, C);
-        }
-        HIPCHK(hipEventRecord(h->ev_pan[g], C));   // group g's panels are final
-        if (g + 1 < ng) {
-            if (g >= 1) HIPCHK(hipStreamWaitEvent(C, h->ev_col[g - 1], 0));   // B1(g - 1) wrote the same block columns
-            syrk_update(h, C, K0, Gc, first(g + 1), 1, count(g + 1));         // A(g)
-        }
-        HIPCHK(hipStreamWaitEvent(T, h->ev_pan[g], 0));
-        if (g + 2 < ng) {
-            syrk_update(h, T, K0, Gc, first(g + 2), 1, count(g + 2));         // B1(g)
-            HIPCHK(hipEventRecord(h->ev_col[g], T));
-        }
-        if (g + 3 < ng) syrk_update(h, T, K0, Gc, first(g + 3), 1, h->nK - first(g + 3));   // B2(g)
+    auto substitution = [h, M](int g, int K0, int Gc) {
         HIPCHK(hipStreamWaitEvent(M, h->ev_pan[g], 0));
-        for (int q = 0; q < Gc; ++q) {
-            if (q > 0) ck_launch_aux_group(M, h->aux, h->mpad, h->d_panelptr, K0, q, K0 + q, 1, aux_rows(h, K0 + q - 1), h->nend, aux_live(h));
-            aux_inner_on(h, K0 + q, h->sig[K0 + q], M);
-        }
-        if (K0 + Gc < h->nK)
-            ck_launch_aux_group(M, h->aux, h->mpad, h->d_panelptr, K0, Gc, K0 + Gc, h->nK - K0 - Gc, aux_rows(h, K0 + Gc - 1), h->nend, aux_live(h));
-    }
+        return grouped_pass(h, M, K0, Gc, aux_step(h), aux_update(h, false));
+    };
+    if (group_lookahead(h, gs, false, sigma_step(h), sigma_update(h, false), substitution)) return -1;
     HIPCHK(hipEventRecord(h->ev1, C));               // end of the factorisation's chain: the last panel is final
     HIPCHK(hipEventRecord(h->ev2, T));
     HIPCHK(hipStreamWaitEvent(M, h->ev1, 0));
@@ -1597,62 +1586,32 @@ static int fused_sweeps_la(ck_handle* h) {
 // step applied to more rows, so every launch of the factorisation takes the right-hand-side rows along --
 // the cooperative panel step as further workgroups (k_panel_coop), the updates as further tiles of the same grid
 // (k_tall_group_d) -- instead of a second sweep that shares the chip with the first (fused_sweeps_la: 156 big launches per
-// pass on two streams, the substitution's one-column launches filling 280 of 512 slots).  The look-ahead is kept: stream C
-// (high priority) carries the chain of group g and A(g), the update of the NEXT group's block columns by group g; stream T
-// carries B1(g) = group g -> block columns of group g + 2 and B2(g) = group g -> everything beyond.  Every block column --
-// of Sigma and of the right-hand-side rows -- receives its updates in the order of the sequential sweeps, each in one launch
-// with K = 512 G, and every tile computes what it computed there: same bits as ck_factor + ck_predict.
-//   C:  chain(g) -> [ev_pan g] -> wait B1(g - 1) -> A(g) -> chain(g + 1) ...
-//   T:  wait ev_pan g -> B1(g) -> [ev_col g] -> B2(g) -> wait ev_pan g + 1 ...
+// pass on two streams, the substitution's one-column launches filling 280 of 512 slots).  The look-ahead is kept
+// (group_lookahead).  Every block column -- of Sigma and of the right-hand-side rows -- receives its updates in the order of
+// the sequential sweeps, each in one launch with K = 512 G, and every tile computes what it computed there: same bits as
+// ck_factor + ck_predict.
 static int tall_sweeps(ck_handle* h) {
     if (ensure_events(h)) return -1;
     if (!h->side_lo) HIPCHK(hipStreamCreateWithFlags(&h->side_lo, hipStreamNonBlocking));
     hipStream_t C = h->side, T = h->side_lo, M = h->stream;
     const std::vector<int> gs = group_plan(h, h->fused_group > 0 ? h->fused_group : eff_group(h));
-    const int ng = (int)gs.size() - 1;
-    auto first = [&](int g) { return gs[(size_t)g]; };
-    auto count = [&](int g) { return gs[(size_t)g + 1] - gs[(size_t)g]; };
-    auto update = [&](hipStream_t st, int K0, int np, int J0, int nJ) {
+    HIPCHK(hipEventRecord(h->ev0, M));
+    HIPCHK(hipStreamWaitEvent(C, h->ev0, 0));
+    HIPCHK(hipStreamWaitEvent(T, h->ev0, 0));
+    auto step = [&](hipStream_t st, int K) {
+        const int64_t R = h->Npad - (int64_t)K * CK_NB;
+        // panel steps that run under a bulk update (behind the first group) and have many chunks: the head cooperatively, the
+        // rows on their own
+        const bool split = h->tall_split == 1 || (h->tall_split == 2 && K >= gs[1] && R >= h->tall_split_rows);
+        panel_factor_on(h, K, st, true, split);
+    };
+    auto update = [h](hipStream_t st, int K0, int np, int J0, int nJ) {
         if (nJ <= 0) return;
         gemm_timed_begin(h, st);
         ck_launch_tall_group(st, h->d_sigptr, h->aux, h->mpad, K0, np, J0, nJ, h->nend, aux_live(h));
         gemm_timed_end(h, st);
     };
-    // option "tall_b2_stream": B2(g) on the handle's own stream instead of behind B1(g) on T -- the two only need group g's panels,
-    // so the partly filled last round of B1(g) runs beside B2(g)'s tiles instead of in front of them
-    const bool b2m = h->tall_b2_stream != 0;
-    HIPCHK(hipEventRecord(h->ev0, M));
-    HIPCHK(hipStreamWaitEvent(C, h->ev0, 0));
-    HIPCHK(hipStreamWaitEvent(T, h->ev0, 0));
-    for (int g = 0; g < ng; ++g) {
-        const int K0 = first(g), Gc = count(g);
-        for (int q = 0; q < Gc; ++q) {
-            if (q > 0) update(C, K0, q, K0 + q, 1);
-            const int K = K0 + q;
-            const int64_t R = h->Npad - (int64_t)K * CK_NB;
-            // panel steps that run under a bulk update and have many chunks: the head cooperatively, the rows on their own
-            const bool split = h->tall_split == 1 || (h->tall_split == 2 && g >= 1 && R >= h->tall_split_rows);
-            panel_factor_on(h, K, C, true, split);
-        }
-        HIPCHK(hipEventRecord(h->ev_pan[g], C));   // group g's panels and right-hand-side block columns are final
-        if (g + 1 < ng) {
-            if (g >= 1) HIPCHK(hipStreamWaitEvent(C, h->ev_col[g - 1], 0));   // B1(g - 1) wrote the same block columns
-            update(C, K0, Gc, first(g + 1), count(g + 1));                    // A(g)
-        }
-        HIPCHK(hipStreamWaitEvent(T, h->ev_pan[g], 0));
-        if (g + 2 < ng) {
-            // (B2 on its own stream: B2(g - 1) was the last writer of the block columns B1(g) updates)
-            if (b2m && g >= 1 && g + 2 < ng) HIPCHK(hipStreamWaitEvent(T, h->ev_b2[g - 1], 0));
-            update(T, K0, Gc, first(g + 2), count(g + 2));                    // B1(g)
-            HIPCHK(hipEventRecord(h->ev_col[g], T));
-        }
-        if (g + 3 < ng) {
-            hipStream_t B = b2m ? M : T;
-            if (b2m) HIPCHK(hipStreamWaitEvent(M, h->ev_pan[g], 0));
-            update(B, K0, Gc, first(g + 3), h->nK - first(g + 3));            // B2(g)
-        }
-        if (b2m) HIPCHK(hipEventRecord(h->ev_b2[g], M));
-    }
+    if (group_lookahead(h, gs, h->tall_b2_stream != 0, step, update, no_follower)) return -1;
     HIPCHK(hipEventRecord(h->ev1, C));               // end of the chain: the last panel is final
     HIPCHK(hipEventRecord(h->ev2, T));
     HIPCHK(hipStreamWaitEvent(M, h->ev1, 0));
@@ -1696,10 +1655,7 @@ extern "C" int ck_factor_predict(ck_handle* h, int i, const double* pcoords, int
         // order for numpy's minor index / without the cooperative step), then the substitution on the finished factor.
         // A timed-out step: clear its error word and switch the cooperative step off HERE, so that ck_factor runs the
         // factorisation once, the plain way, instead of repeating a cooperative one and discarding it for the stale flag.
-        if (werr != 0) {
-            HIPCHK(hipMemset(h->d_coop + 16, 0, sizeof(unsigned)));
-            h->panel_fused &= ~16;
-        }
+        if (werr != 0 && coop_switch_off(h)) return -1;
         h->gemm_ev_used = 0;
         h->assembled = false;
         h->aux_state = 0;
@@ -1738,16 +1694,13 @@ extern "C" int ck_factor(ck_handle* h, int64_t* info) {
     h->t_ms[12] = 0.0;
     if (factor_sweep(h)) return -1;
     {
-        // FIRST the cooperative panel step's error word: a workgroup of k_panel_coop that gave up waiting for a pivot block
-        // (bounded spin, option "coop_spins": ~2 s; never observed outside the test hook "coop_inject_panel") leaves a factor --
-        // and an info word -- that are not to be trusted.  The cooperative step is switched off for this handle and the
-        // factorisation repeated with one launch per dependency.
+        // FIRST the cooperative panel step's error word (coop_error): after a timeout the cooperative step is switched off for
+        // this handle and the factorisation repeated with one launch per dependency.
         HIPCHK(hipStreamSynchronize(h->stream));
         unsigned werr = 0;
-        HIPCHK(hipMemcpy(&werr, h->d_coop + 16, sizeof(werr), hipMemcpyDeviceToHost));
+        if (coop_error(h, &werr)) return -1;
         if (werr != 0) {
-            HIPCHK(hipMemset(h->d_coop + 16, 0, sizeof(unsigned)));
-            h->panel_fused &= ~16;
+            if (coop_switch_off(h)) return -1;
             h->assembled = false;
             if (ck_assemble_joint(h)) return -1;
             if (factor_sweep(h)) return -1;
@@ -2277,10 +2230,9 @@ static int schur_factor(ck_handle* h, long long* v, const char* again) {
     HIPCHK(hipMemcpyAsync(v, h->d_info, sizeof(*v), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     unsigned werr = 0;
-    HIPCHK(hipMemcpy(&werr, h->d_coop + 16, sizeof(werr), hipMemcpyDeviceToHost));
+    if (coop_error(h, &werr)) return -1;
     if (werr != 0) {
-        HIPCHK(hipMemset(h->d_coop + 16, 0, sizeof(unsigned)));
-        h->panel_fused &= ~16;
+        if (coop_switch_off(h)) return -1;
         return fail(std::string("cooperative panel step timed out (option panel_fused bit 4 now off): ") + again);
     }
     return 0;
@@ -4151,7 +4103,7 @@ extern "C" int ck_debug_stream_overlap(ck_handle* h, int mode, int64_t rows, int
             HIPCHK(hipEventRecord(ev[2 + i], S));
         }
     }
-    if (mode != 1) syrk_update(h, M, 0, 3, 3, 1, h->nK - 3);
+    if (mode != 1) sigma_update_on(h, M, 0, 3, 3, 1, h->nK - 3, false);
     HIPCHK(hipEventRecord(ev[1], M));
     HIPCHK(hipStreamSynchronize(M));
     HIPCHK(hipStreamSynchronize(S));
