@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../include/cokrige.h"
+#include "ck_devbuf.h"
 #include "ck_host.h"
 #include "ck_internal.h"
 #include "ck_tilemap.h"
@@ -49,21 +50,21 @@ static int fail(const std::string& msg) { return ck_fail(msg); }   // thread-loc
     if (!(h)) return fail("null handle"); \
     HIPCHK(hipSetDevice((h)->device))
 
-// device temporaries of one call: released on every return path
-struct DevTemps {
-    std::vector<void*> p;
-    ~DevTemps() {
-        for (void* x : p)
-            if (x) (void)hipFree(x);
-    }
-    template <class T>
-    hipError_t get(T** out, size_t bytes) {
-        *out = nullptr;
-        const hipError_t e = hipMalloc((void**)out, bytes ? bytes : 8);
-        if (e == hipSuccess) p.push_back((void*)*out);
-        return e;
-    }
-};
+// milliseconds between two recorded events: the form for HIPCHK, and the form of the sites that ignore the status
+static hipError_t elapsed_ms(hipEvent_t a, hipEvent_t b, double* out) {
+    float ms = 0;
+    const hipError_t e = hipEventElapsedTime(&ms, a, b);
+    *out = ms;
+    return e;
+}
+static double elapsed_ms(hipEvent_t a, hipEvent_t b) {
+    double ms = 0;
+    (void)elapsed_ms(a, b, &ms);
+    return ms;
+}
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 struct EvPair {
     hipEvent_t a, b;
@@ -76,12 +77,11 @@ struct ck_handle {
     // arena
     char* arena = nullptr;
     int64_t arena_size = 0, arena_used = 0;
-    std::vector<void*> owned;   // hipMalloc'ed blocks (no arena)
     // model
     int n_procs = 0;
     int metric = CK_METRIC_HAVERSINE;
     CkMatern blk[3];
-    CkMatern* d_blk = nullptr;
+    DevBuf<CkMatern> d_blk;
     bool model_set = false;
     // partition
     int rank = 0, world = 1;
@@ -100,81 +100,90 @@ struct ck_handle {
     int site_order = 1;
     std::vector<int64_t> perm[2], pperm;
     bool p_sorted = false;
-    double *s0 = nullptr, *s1 = nullptr, *s2 = nullptr, *z = nullptr;   // stacked sites / values (Npad)
-    double* su = nullptr;               // chord vectors of the stacked sites (3 x Npad)
-    double* pu = nullptr;               // chord vectors of the prediction sites (3 x mpad)
+    DevBuf<double> s0, z;               // stacked sites (3 x Npad) / values (Npad)
+    double *s1 = nullptr, *s2 = nullptr;   // rows 1 and 2 of s0
+    DevBuf<double> su;                  // chord vectors of the stacked sites (3 x Npad)
+    DevBuf<double> pu;                  // chord vectors of the prediction sites (3 x mpad)
     // tabulated correlation (fast assembly)
     CkTable tab[3];
-    double* d_coef[3] = {nullptr, nullptr, nullptr};
-    CkTable* d_tabs = nullptr;
-    double** d_coefptr = nullptr;
+    DevBuf<double> d_coef[3];
+    DevBuf<CkTable> d_tabs;
+    DevBuf<double*> d_coefptr;
     bool tables_built = false;
     bool tables_stale = false;   // ck_set_model changed the model after the tables were built: rebuild before the next use
     double qbox = 0.0;           // squared bounding-box diagonal of the data sites (Euclidean table range)
     bool exact_cov = false;             // option "exact_cov": bypass the tables
     CkWorklist wl = {nullptr, nullptr, 0, nullptr};   // entries deferred by the table kernels
-    unsigned* wl_counts = nullptr;           // its two counters (used alternately: next_worklist)
+    DevBuf<int2> wl_items;                   // its list
+    DevBuf<unsigned> wl_counts;              // its two counters (used alternately: next_worklist)
     int64_t fallback_total = 0;
+    // sig, d_sigptr, d_panelptr, d_info, aux are views (SchurSwap / AuxSwap re-point them); what they look at is owned by
+    // sig_slab, sigptr_own, panelptr_own, d_coop, aux_own
     std::vector<double*> sig;    // per panel; nullptr if not owned
+    DevBuf<char> sig_slab;       // the owned panels, one allocation
     double** d_sigptr = nullptr;
     double** d_panelptr = nullptr;   // where panel K can be read on this rank: own storage or receive buffer K & 1
-    int *d_tile0 = nullptr, *d_panel_of = nullptr;   // assembly launch map of the owned panels
-    int* d_strip_order = nullptr;                    // the same strips sorted by Matern block (work-queue form of the assembly)
+    DevBuf<double*> sigptr_own, panelptr_own;
+    DevBuf<int> d_tile0, d_panel_of;   // assembly launch map of the owned panels
+    DevBuf<int> d_strip_order;         // the same strips sorted by Matern block (work-queue form of the assembly)
     int n_owned = 0, total_tiles = 0;
     // receive slots for remote panels (world > 1): panel K lands in slot K % recv_slots.  Two slots carry the per-panel
     // look-ahead schedule; 2 G slots the grouped one (the G panels of the group being applied + the G being received)
     int recv_slots = 2;
-    std::vector<double*> recv;
+    std::vector<DevBuf<double>> recv;
     long long* d_info = nullptr;
     bool assembled = false, factored = false;
     // aux
     int i_pred = 0;
-    int64_t m = 0, mpad = 0, aux_cap = 0;   // aux_cap in doubles
+    int64_t m = 0, mpad = 0;
     double* aux = nullptr;
-    double *p0 = nullptr, *p1 = nullptr, *p2 = nullptr;
-    int64_t p_cap = 0;
-    double *d_pred = nullptr, *d_err = nullptr;
-    double* d_pcoords = nullptr;
-    char* mv_buf = nullptr;   // ck_model_variogram's device rows (i, j, lag, out), kept between the cost evaluations of a fit
-    int64_t mv_cap = 0;
+    DevBuf<double> aux_own;
+    DevBuf<double> p0, d_pred, d_pcoords;   // p0: 3 x mpad, d_pred: pred | err, d_pcoords: 2 x mpad
+    double *p1 = nullptr, *p2 = nullptr, *d_err = nullptr;
+    int64_t p_cap = 0;        // the mpad that p0, pu, d_pcoords and d_pred hold
+    DevBuf<char[24]> mv_buf;   // ck_model_variogram's device arrays (lag | out | i | j, 24 bytes per row), kept between the cost
+                               // evaluations of a fit
     int aux_state = 0;   // 0: nothing usable | 1: right-hand sides assembled | 2: solved by ck_predict (rows = V^T, row m = y)
                          // | 3: the last call was ck_predict_blocks (its rows are block sums: the sites are gone)
                          // | 4: the last call was ck_loglik (its rows are y and the unit rows of the data sites)
     double par_sigma[2] = {0.0, 0.0}, par_rho = 0.0;   // ck_set_model's sigma and rho12 (ck_loglik's derivatives in them)
-    CkMatern* d_lik_blk = nullptr;                      // ck_loglik: 3 blocks x (the block, nu - 2 d, nu - d, nu + d, nu + 2 d)
+    DevBuf<CkMatern> d_lik_blk;                         // ck_loglik: 3 blocks x (the block, nu - 2 d, nu - d, nu + d, nu + 2 d)
     // ck_predict_blocks: the block rows (the aux panel layout with bmpad = roundup(r + 1, CK_AUX_ALIGN) rows per panel), kept
     // between calls like aux; option "block_chunk": prediction sites per K2 assembly (0: from the device memory the handle may use)
-    double* baux = nullptr;
-    int64_t baux_cap = 0;   // doubles
+    DevBuf<double> baux;
     int64_t block_chunk = 0;
     int64_t draw_chunk = 0;   // option "draw_chunk": draws per product launch of ck_conditional_draws (0: from the free device memory)
     // Schur complement of the prediction sites (ck_verify_model), kept between calls with the same padded order
-    int64_t sch_M = 0;
-    std::vector<double*> sch_sig;
-    double** d_sch_ptr = nullptr;
-    int *d_sch_tile0 = nullptr, *d_sch_panel_of = nullptr;
-    int sch_tiles = 0;
-    double *sch_pc = nullptr, *sch_c = nullptr, *sch_u = nullptr;
-    CkMatern* d_sch_blk = nullptr;
-    CkTable* d_sch_tabs = nullptr;
-    double** d_sch_coefptr = nullptr;
-    long long* d_sch_info = nullptr;
+    struct Schur {
+        int64_t M = 0;
+        int tiles = 0;
+        std::vector<DevBuf<double>> panels;
+        std::vector<double*> sig;   // the panels as SchurSwap hands them to the sweeps
+        DevBuf<double*> d_ptr, d_coefptr;
+        DevBuf<int> d_tile0, d_panel_of;
+        DevBuf<double> pc, c, u;
+        DevBuf<CkMatern> d_blk;
+        DevBuf<CkTable> d_tabs;
+        DevBuf<long long> d_info;
+    } sch;
     // empirical variogram state (ck_vario_*)
     std::vector<double> vg_ci, vg_cj, vg_vi, vg_vj;   // host copies of coordinates / residuals in the device's point order
                                                       // (the pairs the kernels leave to the host are decided on these)
-    double *vg_iu = nullptr, *vg_iv = nullptr, *vg_ju = nullptr, *vg_jv = nullptr;
-    unsigned long long* vg_best = nullptr;       // extreme-pair hints of the extent pass (ck_vario.hip)
-    double *vg_jb = nullptr, *vg_ib64 = nullptr, *vg_jbsub = nullptr;   // bounding balls: 1024-point "j" chunks, 64-point
-                                                                        // "i" blocks (wave tiles), 128-point sub-chunks
+    struct Vario {   // the device side, ck_vario_begin .. ck_vario_end
+        DevBuf<double> iu, iv, ju_own, jv_own;
+        double *ju = nullptr, *jv = nullptr;   // field j: ju_own / jv_own, or iu / iv when vg_same
+        DevBuf<unsigned long long> best;       // extreme-pair hints of the extent pass (ck_vario.hip)
+        DevBuf<double> jb, ib64, jbsub;        // bounding balls: 1024-point "j" chunks, 64-point "i" blocks (wave tiles),
+                                               // 128-point sub-chunks
+        DevBuf<CkVarioExt> part;
+        DevBuf<double> psum;
+        DevBuf<unsigned long long> pcnt;
+        DevBuf<double> out;          // xa[38] | xb[38] | dthr[38] | sums[36] | counts[37] (8-byte words) | kernel arguments
+        DevBuf<CkVarioPair> list;    // pairs left to the host; its capacity is what the kernels may fill
+        DevBuf<unsigned> count;
+    } vg;
     int64_t vg_ni = 0, vg_nj = 0;
     int vg_same = 0, vg_bgrid = 0;
-    void* vg_part = nullptr;
-    double* vg_psum = nullptr;
-    unsigned long long* vg_pcnt = nullptr;
-    double* vg_out = nullptr;          // xa[38] | xb[38] | dthr[38] | sums[36] | counts[37] (8-byte words) | kernel arguments
-    CkVarioPair* vg_list = nullptr;    // pairs left to the host
-    unsigned* vg_count = nullptr;
-    unsigned vg_list_cap = 0;
     int64_t vg_stats[4] = {0, 0, 0, 0};   // host-decided pairs of the extent pass | of the binning pass | pairs visited by
                                           // the binning pass | extra extent rounds
     // timings
@@ -220,9 +229,9 @@ struct ck_handle {
                                       // bit 4: the whole panel step of the factorisation in one launch of cooperating
                                       // workgroups (k_panel_coop: 360.4 -> 350.0 ms; N = 10 000: 14.4 -> 12.8 ms)
     int64_t loo_g0 = -1;              // >= 0 during ck_loocv: right-hand-side row 1 + p is the unit vector of site loo_g0 + p
-    double* d_chunkb = nullptr;       // chunk bounds of the sites for the radius search (ck_local.hip: LpSearch)
-    double* local_slab = nullptr;     // scratch of ck_predict_local, kept between calls (allocating tens of GiB
-    long long local_slab_doubles = 0; // costs up to seconds, erratically); grows when a call needs more
+    DevBuf<double> d_chunkb;          // chunk bounds of the sites for the radius search (ck_local.hip: LpSearch)
+    DevBuf<double> local_slab;        // scratch of ck_predict_local, kept between calls (allocating tens of GiB
+                                      // costs up to seconds, erratically); grows when a call needs more
     // option "lookahead": the panel step of column K + 1 on a second stream under the trailing update of the columns beyond
     // it (per-panel updates, no grouping).  With 24 launches per panel step it gained nothing (the side queue's launches
     // starve behind the resident update kernel); with the ONE-launch cooperative panel step, submitted in front of
@@ -232,8 +241,8 @@ struct ck_handle {
     // forced; 0 / 1 = off / on (1 also switches the solve sweep's variant on)
     int lookahead = -1;
     // the cooperative panel step (ck_la.hip: k_panel_coop, option "panel_fused" bit 4): [0..15] its flags, [16] its error word
-    unsigned* d_coop = nullptr;
-    unsigned long long* d_stamps = nullptr;   // option "gemm_stamps": lifetime stamps of the trailing-update workgroups
+    DevBuf<unsigned> d_coop;
+    DevBuf<unsigned long long> d_stamps;      // option "gemm_stamps": lifetime stamps of the trailing-update workgroups
     size_t n_stamps = 0;                      // (ck_debug_gemm_clock), 4 words per workgroup of the largest launch
     int64_t stamp_grid[4] = {0, 0, 0, 0};     // grid x, y, J0, panels of the last stamped launch
     int stamp_sel = 0;                        // 1: every launch | >= 2: only the trailing launch behind panel group K0 = stamp_sel - 2
@@ -246,23 +255,35 @@ struct ck_handle {
     std::vector<double> trend_F[2];
     int trend_p[2] = {0, 0};
     bool trend_dirty = false;
-    double* d_trendX = nullptr;
-    int64_t trend_cap = 0;          // doubles
-    double* d_univ = nullptr;       // the universal reduction's output (rows x (q + 1) doubles)
-    int64_t univ_cap = 0;
+    DevBuf<double> d_trendX;
+    DevBuf<double> d_univ;          // the universal reduction's output (rows x (q + 1) doubles)
     // measurement-error variances (ck_set_noise): d_a of process k in the caller's order, kept on the host, and the scale s_k;
     // d_noise: [s_k d_a | d_a], two rows of Npad doubles in the internal order (zero at padding positions and where a process
     // has none), uploaded when the layout is known.  noise_on: some s_k d_a > 0 -- otherwise no kernel sees the vector
     std::vector<double> noise_var[2];
     double noise_scale[2] = {1.0, 1.0};
     bool noise_dirty = false, noise_on = false;
-    double* d_noise = nullptr;
-    int64_t noise_cap = 0;          // doubles
+    DevBuf<double> d_noise;
     double lik_noise_grad[2] = {0.0, 0.0};   // dl/ds_k of the last ck_loglik / ck_loglik_reml with a gradient
     bool lik_noise_valid = false;            // ... since the last ck_assemble_joint
     int aux_trend = 0;   // trend rows behind the data row of the right-hand sides being assembled (rows m + 1 .. m + aux_trend)
     int loo_dense = 1;   // rows in front of the unit rows in the leave-one-out / likelihood layout (ck_loglik_reml: 1 + p)
+
+    ~ck_handle() {   // events and streams; the buffers release themselves
+        for (auto& e : gemm_ev) {
+            (void)hipEventDestroy(e.a);
+            (void)hipEventDestroy(e.b);
+        }
+        for (hipEvent_t e : {ev0, ev1, ev2, ev3})
+            if (e) (void)hipEventDestroy(e);
+        for (const auto* v : {&ev_b2, &ev_col, &ev_pan})
+            for (hipEvent_t e : *v) (void)hipEventDestroy(e);
+        for (hipStream_t st : {side, side_lo, own_stream})
+            if (st) (void)hipStreamDestroy(st);
+    }
 };
+static int64_t aux_cap(const ck_handle* h) { return (int64_t)h->aux_own.cap(); }               // doubles
+static long long local_slab_doubles(const ck_handle* h) { return (long long)h->local_slab.cap(); }
 
 extern "C" int ck_version(void) { return 101; }
 extern "C" int ck_device_count(int* n) {
@@ -273,28 +294,34 @@ extern "C" int ck_device_count(int* n) {
 // ---------------------------------------------------------------------------------------
 // memory
 // ---------------------------------------------------------------------------------------
-static int dev_alloc(ck_handle* h, void** out, int64_t bytes) {
-    bytes = (bytes + 255) & ~(int64_t)255;
+static int64_t align256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
+// What the handle allocates in the caller's arena if there is one (ck_estimate_bytes is the sum of exactly these sizes):
+// a panel's rows with the diagonal blocks' inverses behind them (ck_panel_buffer) ...
+static int64_t panel_payload(int64_t Np, int K) { return ((Np - (int64_t)K * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8; }
+static int64_t panel_bytes(int64_t Np, int K) { return align256(panel_payload(Np, K) + CK_PANEL_SLACK_BYTES); }   // in the slab
+static int64_t recv_bytes(int64_t Np) { return panel_payload(Np, 0) + CK_PANEL_SLACK_BYTES; }   // a receive slot: any panel
+static int64_t site_bytes(int64_t Np) { return 3 * Np * 8; }              // s0, su (p0, pu with mpad)
+static int64_t value_bytes(int64_t Np) { return Np * 8; }                 // z
+static int64_t ptr_bytes(int nK) { return (int64_t)nK * sizeof(double*); }   // d_sigptr, d_panelptr
+static int64_t rhs_bytes(int64_t mpad, int64_t Np) { return mpad * Np * 8; }   // aux
+static int64_t pair_bytes(int64_t mpad) { return 2 * mpad * 8; }          // d_pcoords, d_pred
+
+// b <- `bytes` (rounded up to 256) of the arena as a view, or of device memory as its owner; b is empty if that fails.  An
+// arena never takes a carve back: a buffer that grows under it abandons the old one
+template <class T>
+static int dev_alloc(ck_handle* h, DevBuf<T>& b, int64_t bytes) {
+    bytes = align256(bytes);
+    b.reset();
     if (h->arena) {
         if (h->arena_used + bytes > h->arena_size)
             return fail("arena too small: need " + std::to_string(h->arena_used + bytes) + " bytes, have " +
                         std::to_string(h->arena_size));
-        *out = h->arena + h->arena_used;
+        b.view((T*)(h->arena + h->arena_used), (size_t)bytes / sizeof(T));
         h->arena_used += bytes;
         return 0;
     }
-    HIPCHK(hipMalloc(out, (size_t)bytes));
-    h->owned.push_back(*out);
+    HIPCHK(b.reserve((size_t)bytes / sizeof(T)));
     return 0;
-}
-static void dev_free_one(ck_handle* h, void* p) {
-    if (!p || h->arena) return;
-    for (size_t i = 0; i < h->owned.size(); ++i)
-        if (h->owned[i] == p) {
-            (void)hipFree(p);
-            h->owned.erase(h->owned.begin() + i);
-            return;
-        }
 }
 
 extern "C" int ck_create(int device_id, ck_handle** out) {
@@ -304,7 +331,7 @@ extern "C" int ck_create(int device_id, ck_handle** out) {
     if (nd <= 0) return fail("no HIP device visible: libcokrige_hip needs an MI355X (gfx950)");
     if (device_id < 0 || device_id >= nd) return fail("bad device id");
     HIPCHK(hipSetDevice(device_id));
-    ck_handle* h = new ck_handle();
+    std::unique_ptr<ck_handle> h(new ck_handle());   // the handle cleans up after itself if a step below fails
     h->device = device_id;
     HIPCHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
     h->stream = h->own_stream;
@@ -317,11 +344,11 @@ extern "C" int ck_create(int device_id, ck_handle** out) {
         HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
         HIPCHK(hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, hi));
     }
-    HIPCHK(hipMalloc((void**)&h->d_coop, 32 * sizeof(unsigned)));
+    HIPCHK(h->d_coop.reserve(32));
     HIPCHK(hipMemset(h->d_coop, 0, 32 * sizeof(unsigned)));
-    HIPCHK(hipMalloc((void**)&h->d_blk, 3 * sizeof(CkMatern)));
+    HIPCHK(h->d_blk.reserve(3));
     h->d_info = (long long*)(h->d_coop + 18);   // behind the cooperative step's error word: one 16-byte read-back for both
-    *out = h;
+    *out = h.release();
     return 0;
 }
 
@@ -333,47 +360,12 @@ extern "C" int ck_create_partitioned(const int* device_ids, int n_dev, int rank,
     return 0;
 }
 
-static void vario_free(ck_handle* h);
-static void schur_free(ck_handle* h);
-
 extern "C" int ck_destroy(ck_handle* h) {
     if (!h) return 0;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
-    vario_free(h);
-    schur_free(h);
-    for (void* p : h->owned) (void)hipFree(p);
-    (void)hipFree(h->d_blk);
-    if (h->d_lik_blk) (void)hipFree(h->d_lik_blk);
-    if (h->d_tile0) (void)hipFree(h->d_tile0);
-    if (h->local_slab) (void)hipFree(h->local_slab);
-    if (h->d_panel_of) (void)hipFree(h->d_panel_of);
-    if (h->wl.items) (void)hipFree(h->wl.items);
-    if (h->wl_counts) (void)hipFree(h->wl_counts);
-    if (h->d_tabs) (void)hipFree(h->d_tabs);
-    if (h->d_coefptr) (void)hipFree(h->d_coefptr);
-    for (int b = 0; b < 3; ++b)
-        if (h->d_coef[b]) (void)hipFree(h->d_coef[b]);
-    for (auto& e : h->gemm_ev) {
-        (void)hipEventDestroy(e.a);
-        (void)hipEventDestroy(e.b);
-    }
-    (void)hipEventDestroy(h->ev0);
-    (void)hipEventDestroy(h->ev1);
-    (void)hipEventDestroy(h->ev2);
-    (void)hipEventDestroy(h->ev3);
-    if (h->mv_buf) (void)hipFree(h->mv_buf);
-    for (auto e : h->ev_b2) (void)hipEventDestroy(e);
-    for (auto e : h->ev_col) (void)hipEventDestroy(e);
-    for (auto e : h->ev_pan) (void)hipEventDestroy(e);
-    if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->side_lo) (void)hipStreamDestroy(h->side_lo);
-    if (h->d_coop) (void)hipFree(h->d_coop);
-    if (h->d_stamps) (void)hipFree(h->d_stamps);
-    if (h->d_trendX) (void)hipFree(h->d_trendX);
-    if (h->d_noise) (void)hipFree(h->d_noise);
-    if (h->d_univ) (void)hipFree(h->d_univ);
-    (void)hipStreamDestroy(h->own_stream);
+    if (h->side) (void)hipStreamSynchronize(h->side);
+    if (h->side_lo) (void)hipStreamSynchronize(h->side_lo);
     delete h;
     return 0;
 }
@@ -386,7 +378,8 @@ extern "C" int ck_set_stream(ck_handle* h, void* hip_stream, int external) {
 
 extern "C" int ck_set_arena(ck_handle* h, void* dev_base, int64_t nbytes) {
     CHKH(h);
-    if (h->layout_ready || !h->owned.empty()) return fail("ck_set_arena must precede any allocation");
+    // the first allocation an arena could serve is ensure_layout's s0, which is never released (ck_set_data's condition)
+    if (h->layout_ready || h->s0) return fail("ck_set_arena must precede any allocation");
     if (((uintptr_t)dev_base & 255) != 0) return fail("arena base must be 256-byte aligned");
     h->arena = (char*)dev_base;
     h->arena_size = nbytes;
@@ -538,19 +531,16 @@ extern "C" int ck_set_noise(ck_handle* h, int k, const double* var, int64_t n_k,
 static int build_tables(ck_handle* h, double qbox_euclid) {
     const int nblk = h->n_procs == 1 ? 1 : 3;
     if (!h->wl.items) {
-        h->wl.cap = 1u << 22;   // 4 M deferred entries (32 MB); beyond that the assembly re-runs exactly
-        HIPCHK(hipMalloc((void**)&h->wl.items, (size_t)h->wl.cap * sizeof(int2)));
-        HIPCHK(hipMalloc((void**)&h->wl_counts, 4 * sizeof(unsigned)));   // two pairs (count, work queue), used alternately: see CkWorklist
+        const unsigned cap = 1u << 22;   // 4 M deferred entries (32 MB); beyond that the assembly re-runs exactly
+        HIPCHK(h->wl_items.reserve(cap));
+        HIPCHK(h->wl_counts.reserve(4));   // two pairs (count, work queue), used alternately: see CkWorklist
         HIPCHK(hipMemset(h->wl_counts, 0, 4 * sizeof(unsigned)));
-        h->wl.count = h->wl_counts;
-        h->wl.reset = h->wl_counts + 2;
+        h->wl = CkWorklist{h->wl_items, h->wl_counts, cap, h->wl_counts + 2};
     }
     const int ND = CK_TAB_DEG + 1;
-    if (!h->d_tabs) {
-        HIPCHK(hipMalloc((void**)&h->d_tabs, 3 * sizeof(CkTable)));
-        HIPCHK(hipMalloc((void**)&h->d_coefptr, 3 * sizeof(double*)));
-        for (int b = 0; b < 3; ++b) HIPCHK(hipMalloc((void**)&h->d_coef[b], (size_t)ND * CK_TAB_STRIDE * 8));
-    }
+    HIPCHK(h->d_tabs.reserve(3));   // allocated by the first call
+    HIPCHK(h->d_coefptr.reserve(3));
+    for (int b = 0; b < 3; ++b) HIPCHK(h->d_coef[b].reserve((size_t)ND * CK_TAB_STRIDE));
     DevTemps tmp;
     unsigned long long* d_err = nullptr;
     double *d_q = nullptr, *d_f = nullptr;
@@ -594,7 +584,8 @@ static int build_tables(ck_handle* h, double qbox_euclid) {
         T.enabled = (T.max_rel_err < 2e-13) ? 1 : 0;
     }
     HIPCHK(hipMemcpyAsync(h->d_tabs, h->tab, 3 * sizeof(CkTable), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_coefptr, h->d_coef, 3 * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    double* const coefs[3] = {h->d_coef[0], h->d_coef[1], h->d_coef[2]};
+    HIPCHK(hipMemcpyAsync(h->d_coefptr, coefs, sizeof(coefs), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->tables_built = true;
     return 0;
@@ -626,9 +617,8 @@ static int ensure_layout(ck_handle* h, bool need_panels = true) {
     h->Npad = roundup(h->nend, CK_NB);
     h->nK = (int)(h->Npad / CK_NB);
     const int64_t Np = h->Npad;
-    if (!h->s0) {
-        if (dev_alloc(h, (void**)&h->s0, 3 * Np * 8) || dev_alloc(h, (void**)&h->su, 3 * Np * 8) ||
-            dev_alloc(h, (void**)&h->z, Np * 8))
+    if (!h->s0 || !h->su || !h->z) {
+        if (dev_alloc(h, h->s0, site_bytes(Np)) || dev_alloc(h, h->su, site_bytes(Np)) || dev_alloc(h, h->z, value_bytes(Np)))
             return -1;
         h->s1 = h->s0 + Np;
         h->s2 = h->s0 + 2 * Np;
@@ -660,10 +650,7 @@ static int ensure_layout(ck_handle* h, bool need_panels = true) {
     HIPCHK(hipMemcpyAsync(d_tmp, hc.data(), 2 * Np * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->z, hz.data(), Np * 8, hipMemcpyHostToDevice, h->stream));
     ck_launch_prep_sites(h->stream, d_tmp, Np, h->metric, h->s0, h->s1, h->s2, h->su);
-    if (!h->d_chunkb) {   // outside the arena: not part of ck_estimate_bytes
-        HIPCHK(hipMalloc((void**)&h->d_chunkb, (size_t)(4 * ((h->nend + 255) / 256 + 1) * 8)));
-        h->owned.push_back(h->d_chunkb);
-    }
+    HIPCHK(h->d_chunkb.reserve((size_t)(4 * ((h->nend + 255) / 256 + 1))));   // outside the arena: not part of ck_estimate_bytes
     ck_launch_local_chunk_bounds(h->stream, h->su, CkLayout{h->n[0], h->n0p, h->nend, h->Npad}, h->d_chunkb);
     HIPCHK(hipStreamSynchronize(h->stream));
     // squared bounding-box diagonal of the data sites (Euclidean table range)
@@ -675,70 +662,94 @@ static int ensure_layout(ck_handle* h, bool need_panels = true) {
     return need_panels ? ensure_panels(h) : 0;
 }
 
-static int ensure_panels(ck_handle* h) {
+// Everything is built into locals and handed to the handle at the end: a failed allocation or copy leaves no panel pointers
+// behind (sig stays empty, so the next call starts over) and gives the arena back what this call had carved
+struct PanelSet {
+    std::vector<double*> sig;
+    DevBuf<char> slab;
+    DevBuf<double*> sigptr, panelptr;
+    DevBuf<int> tile0, panel_of, strip_order;
+    std::vector<DevBuf<double>> recv;
+    int n_owned = 0, total_tiles = 0;
+};
+static int build_panels(ck_handle* h, PanelSet& s) {
     const int64_t Np = h->Npad;
-    if (h->sig.empty()) {
-        h->sig.assign(h->nK, nullptr);
-        // the owned panels from ONE allocation (outside a caller's arena, where dev_alloc carves anyway): 79 hipMalloc /
-        // hipFree calls of tens of MB each were most of what a cold pass spent in its first assemble and in ck_destroy
-        // beyond the kernels (scripts/diag_cold_phases.py)
-        auto panel_bytes = [&](int K) {
-            return (((Np - (int64_t)K * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8 + CK_PANEL_SLACK_BYTES + 255) & ~(int64_t)255;
-        };
-        int64_t slab_bytes = 0;
-        for (int K = h->rank; K < h->nK; K += h->world) slab_bytes += panel_bytes(K);
-        char* slab = nullptr;
-        if (dev_alloc(h, (void**)&slab, slab_bytes)) return -1;
-        for (int K = h->rank; K < h->nK; K += h->world) {
-            h->sig[K] = (double*)slab;
-            slab += panel_bytes(K);
-        }
-        if (dev_alloc(h, (void**)&h->d_sigptr, (int64_t)h->nK * sizeof(double*))) return -1;
-        HIPCHK(hipMemcpy(h->d_sigptr, h->sig.data(), h->nK * sizeof(double*), hipMemcpyHostToDevice));
-        std::vector<int> tile0, panel_of;
-        int acc = 0;
-        for (int K = h->rank; K < h->nK; K += h->world) {
-            tile0.push_back(acc);
-            panel_of.push_back(K);
-            acc += (int)((Np - (int64_t)K * CK_NB) / 64);
-        }
-        tile0.push_back(acc);
-        h->n_owned = (int)panel_of.size();
-        h->total_tiles = acc;
-        HIPCHK(hipMalloc((void**)&h->d_tile0, tile0.size() * sizeof(int)));
-        HIPCHK(hipMalloc((void**)&h->d_panel_of, (panel_of.size() + 1) * sizeof(int)));
-        HIPCHK(hipMemcpy(h->d_tile0, tile0.data(), tile0.size() * sizeof(int), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_panel_of, panel_of.data(), panel_of.size() * sizeof(int), hipMemcpyHostToDevice));
-        {
-            // work-queue form of the assembly: the 64-row strips of all owned panels sorted by Matern block (block 22 first, then
-            // 12, then 11; inside a block back to front as before), so that a resident workgroup reloads its table twice per launch
-            std::vector<int> order;
-            order.reserve((size_t)acc);
-            for (int cls = 2; cls >= 0; --cls)
-                for (int j = (int)panel_of.size() - 1; j >= 0; --j) {
-                    const int64_t K = panel_of[(size_t)j];
-                    const int pc = K * CK_NB >= h->n0p ? 1 : 0;
-                    for (int tile = tile0[(size_t)j + 1] - tile0[(size_t)j] - 1; tile >= 0; --tile) {
-                        const int64_t rt = K * CK_NB + (int64_t)tile * 64;
-                        if ((rt >= h->n0p ? 1 : 0) + pc == cls) order.push_back(tile0[(size_t)j] + tile);
-                    }
-                }
-            HIPCHK(hipMalloc((void**)&h->d_strip_order, std::max<size_t>(order.size(), 1) * sizeof(int)));
-            h->owned.push_back(h->d_strip_order);
-            HIPCHK(hipMemcpy(h->d_strip_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
-        }
-        if (h->world > 1) {
-            h->recv.assign((size_t)h->recv_slots, nullptr);
-            for (int b = 0; b < h->recv_slots; ++b)
-                if (dev_alloc(h, (void**)&h->recv[(size_t)b], (Np * CK_NB + CK_PANEL_TAIL) * 8 + CK_PANEL_SLACK_BYTES)) return -1;
-        }
-        {
-            std::vector<double*> pp(h->nK);
-            for (int K = 0; K < h->nK; ++K) pp[K] = h->sig[K] ? h->sig[K] : (h->world > 1 ? h->recv[(size_t)(K % h->recv_slots)] : nullptr);
-            if (dev_alloc(h, (void**)&h->d_panelptr, (int64_t)h->nK * sizeof(double*))) return -1;
-            HIPCHK(hipMemcpy(h->d_panelptr, pp.data(), h->nK * sizeof(double*), hipMemcpyHostToDevice));
-        }
+    s.sig.assign(h->nK, nullptr);
+    // the owned panels from ONE allocation (outside a caller's arena, where dev_alloc carves anyway): 79 hipMalloc /
+    // hipFree calls of tens of MB each were most of what a cold pass spent in its first assemble and in ck_destroy
+    // beyond the kernels (scripts/diag_cold_phases.py)
+    int64_t slab_bytes = 0;
+    for (int K = h->rank; K < h->nK; K += h->world) slab_bytes += panel_bytes(Np, K);
+    if (dev_alloc(h, s.slab, slab_bytes)) return -1;
+    char* slab = s.slab;
+    for (int K = h->rank; K < h->nK; K += h->world) {
+        s.sig[K] = (double*)slab;
+        slab += panel_bytes(Np, K);
     }
+    if (dev_alloc(h, s.sigptr, ptr_bytes(h->nK))) return -1;
+    HIPCHK(hipMemcpy(s.sigptr, s.sig.data(), h->nK * sizeof(double*), hipMemcpyHostToDevice));
+    std::vector<int> tile0, panel_of;
+    int acc = 0;
+    for (int K = h->rank; K < h->nK; K += h->world) {
+        tile0.push_back(acc);
+        panel_of.push_back(K);
+        acc += (int)((Np - (int64_t)K * CK_NB) / 64);
+    }
+    tile0.push_back(acc);
+    s.n_owned = (int)panel_of.size();
+    s.total_tiles = acc;
+    HIPCHK(s.tile0.reserve(tile0.size()));
+    HIPCHK(s.panel_of.reserve(panel_of.size() + 1));
+    HIPCHK(hipMemcpy(s.tile0, tile0.data(), tile0.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s.panel_of, panel_of.data(), panel_of.size() * sizeof(int), hipMemcpyHostToDevice));
+    {
+        // work-queue form of the assembly: the 64-row strips of all owned panels sorted by Matern block (block 22 first, then
+        // 12, then 11; inside a block back to front as before), so that a resident workgroup reloads its table twice per launch
+        std::vector<int> order;
+        order.reserve((size_t)acc);
+        for (int cls = 2; cls >= 0; --cls)
+            for (int j = (int)panel_of.size() - 1; j >= 0; --j) {
+                const int64_t K = panel_of[(size_t)j];
+                const int pc = K * CK_NB >= h->n0p ? 1 : 0;
+                for (int tile = tile0[(size_t)j + 1] - tile0[(size_t)j] - 1; tile >= 0; --tile) {
+                    const int64_t rt = K * CK_NB + (int64_t)tile * 64;
+                    if ((rt >= h->n0p ? 1 : 0) + pc == cls) order.push_back(tile0[(size_t)j] + tile);
+                }
+            }
+        HIPCHK(s.strip_order.reserve(std::max<size_t>(order.size(), 1)));
+        HIPCHK(hipMemcpy(s.strip_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    if (h->world > 1) {
+        s.recv.resize((size_t)h->recv_slots);
+        for (auto& r : s.recv)
+            if (dev_alloc(h, r, recv_bytes(Np))) return -1;
+    }
+    std::vector<double*> pp(h->nK);
+    for (int K = 0; K < h->nK; ++K) pp[K] = s.sig[K] ? s.sig[K] : (h->world > 1 ? s.recv[(size_t)(K % h->recv_slots)].get() : nullptr);
+    if (dev_alloc(h, s.panelptr, ptr_bytes(h->nK))) return -1;
+    HIPCHK(hipMemcpy(s.panelptr, pp.data(), h->nK * sizeof(double*), hipMemcpyHostToDevice));
+    return 0;
+}
+static int ensure_panels(ck_handle* h) {
+    if (!h->sig.empty()) return 0;
+    const int64_t used0 = h->arena_used;
+    PanelSet s;
+    if (build_panels(h, s)) {
+        h->arena_used = used0;
+        return -1;
+    }
+    h->sig = std::move(s.sig);
+    h->sig_slab = std::move(s.slab);
+    h->sigptr_own = std::move(s.sigptr);
+    h->panelptr_own = std::move(s.panelptr);
+    h->d_sigptr = h->sigptr_own;
+    h->d_panelptr = h->panelptr_own;
+    h->d_tile0 = std::move(s.tile0);
+    h->d_panel_of = std::move(s.panel_of);
+    h->d_strip_order = std::move(s.strip_order);
+    h->recv = std::move(s.recv);
+    h->n_owned = s.n_owned;
+    h->total_tiles = s.total_tiles;
     return 0;
 }
 
@@ -818,18 +829,13 @@ extern "C" int ck_model_variogram(ck_handle* h, const int32_t* pi, const int32_t
     double sill = h->blk[0].amp + h->blk[0].nugget;
     if (h->n_procs == 2) sill = 0.5 * (sill + (h->blk[2].amp + h->blk[2].nugget));
     else sill = 0.5 * sill;
-    if (n > h->mv_cap) {   // one allocation for all four arrays; a fit calls this hundreds of times with the same n
-        if (h->mv_buf) (void)hipFree(h->mv_buf);
-        h->mv_buf = nullptr;
-        h->mv_cap = 0;
-        const int64_t cap = roundup(n, 256);
-        HIPCHK(hipMalloc((void**)&h->mv_buf, (size_t)cap * 24));
-        h->mv_cap = cap;
-    }
-    double* dl = reinterpret_cast<double*>(h->mv_buf);
-    double* dO = dl + h->mv_cap;
-    int* di = reinterpret_cast<int*>(dO + h->mv_cap);
-    int* dj = di + h->mv_cap;
+    // one allocation for all four arrays; a fit calls this hundreds of times with the same n
+    if ((size_t)n > h->mv_buf.cap()) HIPCHK(h->mv_buf.reserve((size_t)roundup(n, 256)));
+    const size_t mv_cap = h->mv_buf.cap();
+    double* dl = reinterpret_cast<double*>(h->mv_buf.get());
+    double* dO = dl + mv_cap;
+    int* di = reinterpret_cast<int*>(dO + mv_cap);
+    int* dj = di + mv_cap;
     HIPCHK(hipMemcpyAsync(di, pi, n * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(dj, pj, n * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(dl, lags, n * 8, hipMemcpyHostToDevice, h->stream));
@@ -871,13 +877,7 @@ static int ensure_noise(ck_handle* h) {
         return 0;
     }
     const int64_t Np = h->Npad;
-    if (2 * Np > h->noise_cap) {
-        if (h->d_noise) HIPCHK(hipFree(h->d_noise));
-        h->d_noise = nullptr;
-        h->noise_cap = 0;
-        HIPCHK(hipMalloc((void**)&h->d_noise, (size_t)(2 * Np) * 8));   // outside the arena, as d_trendX: two rows
-        h->noise_cap = 2 * Np;
-    }
+    HIPCHK(h->d_noise.reserve((size_t)(2 * Np)));   // outside the arena, as d_trendX: two rows
     std::vector<double> nv((size_t)(2 * Np), 0.0);
     for (int k = 0; k < h->n_procs && k < 2; ++k) {
         if (h->noise_var[k].empty()) continue;
@@ -935,9 +935,7 @@ extern "C" int ck_assemble_joint(ck_handle* h) {
     HIPCHK(hipMemsetAsync(h->d_info, 0, sizeof(long long), h->stream));
     if (!fast_done) HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->t_ms[0] = ms;
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &h->t_ms[0]));
     h->assembled = true;
     h->factored = false;
     h->aux_state = 0;   // right-hand sides solved with the previous factor are stale from here on
@@ -969,7 +967,7 @@ extern "C" int ck_panel_buffer(ck_handle* h, int K, void** dev_ptr, int64_t* nby
     if (ensure_layout(h)) return -1;
     if (K < 0 || K >= h->nK) return fail("bad panel index");
     *dev_ptr = (void*)panel_src(h, K);
-    *nbytes = ((h->Npad - (int64_t)K * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;   // rows + the diagonal blocks' inverses
+    *nbytes = panel_payload(h->Npad, K);
     return 0;
 }
 
@@ -999,15 +997,8 @@ static void gemm_timed_collect(ck_handle* h, int slot, hipEvent_t ref = nullptr)
     double tot = 0;
     std::vector<std::pair<float, float>> iv;
     for (size_t e = 0; e < h->gemm_ev_used; ++e) {
-        float t = 0;
-        (void)hipEventElapsedTime(&t, h->gemm_ev[e].a, h->gemm_ev[e].b);
-        tot += t;
-        if (ref) {
-            float a = 0, b = 0;
-            (void)hipEventElapsedTime(&a, ref, h->gemm_ev[e].a);
-            (void)hipEventElapsedTime(&b, ref, h->gemm_ev[e].b);
-            iv.push_back({a, b});
-        }
+        tot += elapsed_ms(h->gemm_ev[e].a, h->gemm_ev[e].b);
+        if (ref) iv.push_back({(float)elapsed_ms(ref, h->gemm_ev[e].a), (float)elapsed_ms(ref, h->gemm_ev[e].b)});
     }
     h->t_ms[slot] = tot;
     h->t_ms[slot + 1] = (double)h->gemm_ev_used;
@@ -1669,11 +1660,8 @@ extern "C" int ck_factor_predict(ck_handle* h, int i, const double* pcoords, int
         return 0;
     }
     h->factored = true;
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->t_ms[1] = ms;    // the factorisation's span (it shares the chip with the substitution)
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev3));
-    h->t_ms[13] = ms;   // both sweeps
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &h->t_ms[1]));    // the factorisation's span (it shares the chip with the substitution)
+    HIPCHK(elapsed_ms(h->ev0, h->ev3, &h->t_ms[13]));   // both sweeps
     h->t_ms[3] = h->t_ms[13] - h->t_ms[1];   // what the substitution adds behind the factorisation
     h->t_ms[12] = 0.0;
     h->t_ms[5] = h->t_ms[6] = h->t_ms[7] = h->t_ms[8] = 0.0;
@@ -1719,9 +1707,7 @@ extern "C" int ck_factor(ck_handle* h, int64_t* info) {
         if (factor_sweep(h)) return -1;
         if (factor_info_raw(h, info)) return -1;
     }
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->t_ms[1] = ms;
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &h->t_ms[1]));
     gemm_timed_collect(h, 5);
     h->factored = true;
     return 0;
@@ -1742,13 +1728,7 @@ static int ensure_trend(ck_handle* h) {
     const int p = trend_total(h);
     if (!h->trend_dirty || p == 0) return 0;
     const int64_t Np = h->Npad;
-    if ((int64_t)p * Np > h->trend_cap) {
-        if (h->d_trendX) HIPCHK(hipFree(h->d_trendX));
-        h->d_trendX = nullptr;
-        h->trend_cap = 0;
-        HIPCHK(hipMalloc((void**)&h->d_trendX, (size_t)p * Np * 8));   // outside the arena, as d_chunkb: p <= 16 rows
-        h->trend_cap = (int64_t)p * Np;
-    }
+    HIPCHK(h->d_trendX.reserve((size_t)p * Np));   // outside the arena, as d_chunkb: p <= 16 rows
     std::vector<double> xt((size_t)p * Np, 0.0);
     int col = 0;
     for (int k = 0; k < h->n_procs; ++k) {
@@ -1776,12 +1756,7 @@ static int put_trend_rows(ck_handle* h, int64_t row0) {
 }
 
 static int ensure_univ(ck_handle* h, int64_t doubles) {
-    if (doubles <= h->univ_cap) return 0;
-    if (h->d_univ) HIPCHK(hipFree(h->d_univ));
-    h->d_univ = nullptr;
-    h->univ_cap = 0;
-    HIPCHK(hipMalloc((void**)&h->d_univ, (size_t)doubles * 8));
-    h->univ_cap = doubles;
+    HIPCHK(h->d_univ.reserve((size_t)doubles));
     return 0;
 }
 
@@ -1797,21 +1772,17 @@ static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m,
     if (m < 0) return fail("bad pcoords");
     const int64_t mpad = roundup(m + 1 + h->aux_trend, CK_AUX_ALIGN);
     const int64_t need = mpad * h->Npad;
-    if (need > h->aux_cap) {
-        dev_free_one(h, h->aux);
+    if (need > aux_cap(h)) {
         h->aux = nullptr;
-        if (dev_alloc(h, (void**)&h->aux, need * 8)) return -1;
-        h->aux_cap = need;
+        if (dev_alloc(h, h->aux_own, rhs_bytes(mpad, h->Npad))) return -1;
+        h->aux = h->aux_own;
     }
     if (mpad > h->p_cap) {
-        dev_free_one(h, h->p0);
-        dev_free_one(h, h->d_pcoords);
-        dev_free_one(h, h->d_pred);
-        dev_free_one(h, h->pu);
-        if (dev_alloc(h, (void**)&h->p0, 3 * mpad * 8)) return -1;
-        if (dev_alloc(h, (void**)&h->pu, 3 * mpad * 8)) return -1;
-        if (dev_alloc(h, (void**)&h->d_pcoords, 2 * mpad * 8)) return -1;
-        if (dev_alloc(h, (void**)&h->d_pred, 2 * mpad * 8)) return -1;
+        h->p_cap = 0;   // all four are taken again if one of them fails
+        for (auto* b : {&h->p0, &h->d_pcoords, &h->d_pred, &h->pu}) b->reset();
+        if (dev_alloc(h, h->p0, site_bytes(mpad)) || dev_alloc(h, h->pu, site_bytes(mpad)) ||
+            dev_alloc(h, h->d_pcoords, pair_bytes(mpad)) || dev_alloc(h, h->d_pred, pair_bytes(mpad)))
+            return -1;
         h->p_cap = mpad;
     }
     h->p1 = h->p0 + mpad;
@@ -1874,9 +1845,7 @@ static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m,
     HIPCHK(hipGetLastError());
     if (!fast_done) HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipEventSynchronize(h->ev1));   // pcoords is caller memory: do not return before the copy is done
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->t_ms[2] = ms;
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &h->t_ms[2]));
     if (h->aux_trend > 0 && put_trend_rows(h, m + 1)) return -1;   // universal cokriging: X^T behind the data row
     return 0;
 }
@@ -1915,9 +1884,7 @@ extern "C" int ck_aux_finish(ck_handle* h, double* pred, double* pred_err) {
             pred_err[h->pperm[(size_t)j]] = te[(size_t)j];
         }
     }
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->t_ms[4] = ms;
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &h->t_ms[4]));
     return 0;
 }
 
@@ -1931,9 +1898,7 @@ extern "C" int ck_predict(ck_handle* h, int i, const double* pcoords, int64_t m,
     if (solve_sweep(h)) return -1;
     HIPCHK(hipEventRecord(h->ev3, h->stream));
     if (ck_aux_finish(h, pred, pred_err)) return -1;
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev2, h->ev3));
-    h->t_ms[3] = ms;
+    HIPCHK(elapsed_ms(h->ev2, h->ev3, &h->t_ms[3]));
     gemm_timed_collect(h, 7);
     h->aux_state = 2;
     return 0;
@@ -1994,13 +1959,8 @@ extern "C" int ck_predict_universal(ck_handle* h, int i, const double* pcoords, 
     std::vector<double> W((size_t)(nrows * (q + 1)));
     HIPCHK(hipMemcpyAsync(W.data(), h->d_univ, W.size() * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev2, h->ev3));
-        h->t_ms[41] = ms;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev3, h->ev1));
-        h->t_ms[42] = ms;
-    }
+    HIPCHK(elapsed_ms(h->ev2, h->ev3, &h->t_ms[41]));
+    HIPCHK(elapsed_ms(h->ev3, h->ev1, &h->t_ms[42]));
     gemm_timed_collect(h, 7);
     // ---- the GLS step
     auto t0 = std::chrono::steady_clock::now();
@@ -2014,8 +1974,8 @@ extern "C" int ck_predict_universal(ck_handle* h, int i, const double* pcoords, 
     if (bad)
         return fail("ck_predict_universal: the trend design is rank deficient: " + trend_column_name(h, bad - 1) +
                     " is, to rounding, a combination of the regressors in front of it (X^T Sigma^-1 X is singular)");
-    auto t1 = std::chrono::steady_clock::now();
-    h->t_ms[43] = std::chrono::duration<double, std::milli>(t1 - t0).count();
+    h->t_ms[43] = ms_since(t0);
+    const auto t1 = std::chrono::steady_clock::now();
     // ---- the epilogue, in the caller's order
     const double c0 = h->blk[2 * i].amp + h->blk[2 * i].nugget;   // sigma_i^2 + nugget_i, as ck_aux_finish
     ck_host_parallel(m, [&](int, int64_t a, int64_t e) {
@@ -2039,8 +1999,8 @@ extern "C" int ck_predict_universal(ck_handle* h, int i, const double* pcoords, 
     });
     if (beta) memcpy(beta, bh.data(), (size_t)p * 8);
     if (beta_cov) memcpy(beta_cov, Ai.data(), (size_t)p * p * 8);
-    h->t_ms[44] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    h->t_ms[45] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    h->t_ms[44] = ms_since(t1);
+    h->t_ms[45] = ms_since(t_begin);
     return 0;
 }
 
@@ -2054,24 +2014,6 @@ extern "C" int ck_predict_universal(ck_handle* h, int i, const double* pcoords, 
 // process i at the prediction sites, nugget where h == 0, :94-102) in the packed panel format of Sigma, subtract
 // V^T V in one pass over the rows (ck_la.hip: k_schur_syrk_d), and run the same blocked Cholesky on it --
 // 2 N m^2 / 2 + m^3 / 3 flop instead of (m + N)^3 / 3.
-static void schur_free(ck_handle* h) {
-    for (double* p : h->sch_sig)
-        if (p) (void)hipFree(p);
-    h->sch_sig.clear();
-    void* ps[] = {h->d_sch_ptr, h->d_sch_tile0, h->d_sch_panel_of, h->sch_pc, h->sch_c, h->sch_u,
-                  h->d_sch_blk, h->d_sch_tabs, h->d_sch_coefptr, h->d_sch_info};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-    h->d_sch_ptr = nullptr;
-    h->d_sch_tile0 = h->d_sch_panel_of = nullptr;
-    h->sch_pc = h->sch_c = h->sch_u = nullptr;
-    h->d_sch_blk = nullptr;
-    h->d_sch_tabs = nullptr;
-    h->d_sch_coefptr = nullptr;
-    h->d_sch_info = nullptr;
-    h->sch_M = 0;
-}
-
 // the factorisation drivers work on the handle's matrix: point them at the Schur complement for one sweep
 struct SchurSwap {
     ck_handle* h;
@@ -2095,12 +2037,12 @@ struct SchurSwap {
         assembled = h->assembled;
         world = h->world;
         rank = h->rank;
-        h->sig = h->sch_sig;
-        h->d_sigptr = h->d_panelptr = h->d_sch_ptr;
+        h->sig = h->sch.sig;
+        h->d_sigptr = h->d_panelptr = h->sch.d_ptr;
         h->nK = nJ;
         h->Npad = Mp;
         h->nend = m_valid;
-        h->d_info = h->d_sch_info;
+        h->d_info = h->sch.d_info;
         h->time_gemm = 0;
         h->lookahead = 0;
         h->assembled = true;
@@ -2126,35 +2068,36 @@ struct SchurSwap {
 // the Schur complement's packed panels (Mp = roundup(sites, CK_NB) rows, a Sigma-like block-column layout) and the
 // assembly state that goes with them; kept between calls with the same padded order
 static int schur_ensure(ck_handle* h, int64_t Mp) {
-    if (h->sch_M == Mp) return 0;
+    if (h->sch.M == Mp) return 0;
     const int nJ = (int)(Mp / CK_NB);
-    schur_free(h);
-    h->sch_sig.assign((size_t)nJ, nullptr);
+    h->sch = {};   // M = 0: a failure below leaves no Schur complement, and the next call starts over
+    h->sch.panels.resize((size_t)nJ);
     std::vector<int> tile0, panel_of;
     int acc = 0;
     for (int J = 0; J < nJ; ++J) {
         const int64_t rows = Mp - (int64_t)J * CK_NB;
-        HIPCHK(hipMalloc((void**)&h->sch_sig[(size_t)J], (size_t)(rows * CK_NB + CK_PANEL_TAIL) * 8));
+        HIPCHK(h->sch.panels[(size_t)J].reserve((size_t)(rows * CK_NB + CK_PANEL_TAIL)));
+        h->sch.sig.push_back(h->sch.panels[(size_t)J]);
         tile0.push_back(acc);
         panel_of.push_back(J);
         acc += (int)(rows / 64);
     }
     tile0.push_back(acc);
-    h->sch_tiles = acc;
-    HIPCHK(hipMalloc((void**)&h->d_sch_ptr, (size_t)nJ * sizeof(double*)));
-    HIPCHK(hipMemcpy(h->d_sch_ptr, h->sch_sig.data(), (size_t)nJ * sizeof(double*), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void**)&h->d_sch_tile0, tile0.size() * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&h->d_sch_panel_of, (panel_of.size() + 1) * sizeof(int)));
-    HIPCHK(hipMemcpy(h->d_sch_tile0, tile0.data(), tile0.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_sch_panel_of, panel_of.data(), panel_of.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void**)&h->sch_pc, (size_t)(2 * Mp) * 8));
-    HIPCHK(hipMalloc((void**)&h->sch_c, (size_t)(3 * Mp) * 8));
-    HIPCHK(hipMalloc((void**)&h->sch_u, (size_t)(3 * Mp) * 8));
-    HIPCHK(hipMalloc((void**)&h->d_sch_blk, 3 * sizeof(CkMatern)));
-    HIPCHK(hipMalloc((void**)&h->d_sch_tabs, 3 * sizeof(CkTable)));
-    HIPCHK(hipMalloc((void**)&h->d_sch_coefptr, 3 * sizeof(double*)));
-    HIPCHK(hipMalloc((void**)&h->d_sch_info, sizeof(long long)));
-    h->sch_M = Mp;
+    h->sch.tiles = acc;
+    HIPCHK(h->sch.d_ptr.reserve((size_t)nJ));
+    HIPCHK(hipMemcpy(h->sch.d_ptr, h->sch.sig.data(), (size_t)nJ * sizeof(double*), hipMemcpyHostToDevice));
+    HIPCHK(h->sch.d_tile0.reserve(tile0.size()));
+    HIPCHK(h->sch.d_panel_of.reserve(panel_of.size() + 1));
+    HIPCHK(hipMemcpy(h->sch.d_tile0, tile0.data(), tile0.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->sch.d_panel_of, panel_of.data(), panel_of.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h->sch.pc.reserve((size_t)(2 * Mp)));
+    HIPCHK(h->sch.c.reserve((size_t)(3 * Mp)));
+    HIPCHK(h->sch.u.reserve((size_t)(3 * Mp)));
+    HIPCHK(h->sch.d_blk.reserve(3));
+    HIPCHK(h->sch.d_tabs.reserve(3));
+    HIPCHK(h->sch.d_coefptr.reserve(3));
+    HIPCHK(h->sch.d_info.reserve(1));
+    h->sch.M = Mp;
     return 0;
 }
 
@@ -2175,23 +2118,23 @@ static int schur_build(ck_handle* h, double* ms_cpp = nullptr, double* ms_vtv = 
     CkMatern hb[3] = {h->blk[bi], h->blk[bi], h->blk[bi]};
     CkTable ht[3] = {h->tab[bi], h->tab[bi], h->tab[bi]};
     double* hc[3] = {h->d_coef[bi], h->d_coef[bi], h->d_coef[bi]};
-    HIPCHK(hipMemcpyAsync(h->d_sch_blk, hb, sizeof(hb), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_sch_tabs, ht, sizeof(ht), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->d_sch_coefptr, hc, sizeof(hc), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->sch_pc, 0, (size_t)(2 * Mp) * 8, h->stream));
-    HIPCHK(hipMemcpyAsync(h->sch_pc, h->d_pcoords, (size_t)(2 * m) * 8, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->sch.d_blk, hb, sizeof(hb), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->sch.d_tabs, ht, sizeof(ht), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->sch.d_coefptr, hc, sizeof(hc), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->sch.pc, 0, (size_t)(2 * Mp) * 8, h->stream));
+    HIPCHK(hipMemcpyAsync(h->sch.pc, h->d_pcoords, (size_t)(2 * m) * 8, hipMemcpyDeviceToDevice, h->stream));
     if (timed) HIPCHK(hipEventRecord(h->ev0, h->stream));
-    ck_launch_prep_sites(h->stream, h->sch_pc, Mp, h->metric, h->sch_c, h->sch_c + Mp, h->sch_c + 2 * Mp, h->sch_u);
+    ck_launch_prep_sites(h->stream, h->sch.pc, Mp, h->metric, h->sch.c, h->sch.c + Mp, h->sch.c + 2 * Mp, h->sch.u);
     HIPCHK(hipStreamSynchronize(h->stream));   // hb / ht / hc are stack memory
     const CkLayout L{m, Mp, Mp, Mp};
     for (int attempt = 0; attempt < 2; ++attempt) {
         const bool fast = tables_usable(h) && attempt == 0;
         if (fast) next_worklist(h);
-        CkPanelMap pm{h->d_sch_tile0, h->d_sch_panel_of, h->d_sch_ptr, nJ, nullptr, 0, nullptr};
-        ck_launch_assemble_sigma(h->stream, fast, h->d_sch_blk, h->d_sch_tabs, h->d_sch_coefptr, h->metric, h->sch_c,
-                                 h->sch_u, L, pm, h->sch_tiles, h->wl, fast ? h->assemble_queue : 0);
+        CkPanelMap pm{h->sch.d_tile0, h->sch.d_panel_of, h->sch.d_ptr, nJ, nullptr, 0, nullptr};
+        ck_launch_assemble_sigma(h->stream, fast, h->sch.d_blk, h->sch.d_tabs, h->sch.d_coefptr, h->metric, h->sch.c,
+                                 h->sch.u, L, pm, h->sch.tiles, h->wl, fast ? h->assemble_queue : 0);
         if (!fast) break;
-        ck_launch_assemble_fix(h->stream, false, h->d_sch_blk, h->metric, 0, nullptr, 0, h->sch_c, L, h->wl, h->d_sch_ptr,
+        ck_launch_assemble_fix(h->stream, false, h->sch.d_blk, h->metric, 0, nullptr, 0, h->sch.c, L, h->wl, h->sch.d_ptr,
                                nullptr);
         unsigned cnt = 0;
         HIPCHK(hipMemcpyAsync(&cnt, h->wl.count, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
@@ -2203,14 +2146,14 @@ static int schur_build(ck_handle* h, double* ms_cpp = nullptr, double* ms_vtv = 
     if (timed) HIPCHK(hipEventRecord(h->ev1, h->stream));
     // row m of the right-hand sides is y = L^-1 z, not a prediction site (ck_aux_finish has consumed it)
     HIPCHK(hipMemset2DAsync(h->aux + m * CK_NB, (size_t)mpad * CK_NB * 8, 0, (size_t)CK_NB * 8, (size_t)h->nK, h->stream));
-    ck_launch_schur_syrk(h->stream, h->d_sch_ptr, h->aux, mpad, h->nK, nJ, Mp);
+    ck_launch_schur_syrk(h->stream, h->sch.d_ptr, h->aux, mpad, h->nK, nJ, Mp);
     HIPCHK(hipGetLastError());
     if (timed) {
         HIPCHK(hipEventRecord(h->ev2, h->stream));
         HIPCHK(hipEventSynchronize(h->ev2));
-        float a = 0, b = 0;
-        HIPCHK(hipEventElapsedTime(&a, h->ev0, h->ev1));
-        HIPCHK(hipEventElapsedTime(&b, h->ev1, h->ev2));
+        double a = 0, b = 0;
+        HIPCHK(elapsed_ms(h->ev0, h->ev1, &a));
+        HIPCHK(elapsed_ms(h->ev1, h->ev2, &b));
         if (ms_cpp) *ms_cpp = a;
         if (ms_vtv) *ms_vtv = b;
     }
@@ -2223,7 +2166,7 @@ static int schur_factor(ck_handle* h, long long* v, const char* again) {
     const int64_t m = h->m;
     const int64_t Mp = roundup(m, CK_NB);
     const int nJ = (int)(Mp / CK_NB);
-    HIPCHK(hipMemsetAsync(h->d_sch_info, 0, sizeof(long long), h->stream));
+    HIPCHK(hipMemsetAsync(h->sch.d_info, 0, sizeof(long long), h->stream));
     *v = 0;
     SchurSwap swap(h, nJ, Mp, m);
     if (factor_sweep(h)) return -1;   // records ev1 at its end
@@ -2265,7 +2208,7 @@ extern "C" int ck_verify_model(ck_handle* h, int64_t* info) {
     long long v = 0;
     if (schur_factor(h, &v, "call ck_predict and ck_verify_model again")) return -1;
     *info = (int64_t)v;   // 1-based index among the prediction sites in the library's internal order, 0 = positive definite
-    h->t_ms[11] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    h->t_ms[11] = ms_since(t_begin);
     return 0;
 }
 
@@ -2357,11 +2300,6 @@ extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int
     const auto t_begin = std::chrono::steady_clock::now();
     BlockCallGuard guard(h);
     for (int k = 16; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
-    auto elapsed = [&](hipEvent_t a, hipEvent_t b) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, a, b);
-        return (double)ms;
-    };
     DevTemps tmp;
     // ---- prior of the blocks (diagonal): members in block order, exact-formula coordinates
     std::vector<double> mc((size_t)(2 * m)), mw((size_t)m);
@@ -2399,16 +2337,10 @@ extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipEventSynchronize(h->ev1));   // mc / mw / off are host memory
-    h->t_ms[18] = elapsed(h->ev0, h->ev1);
+    h->t_ms[18] = elapsed_ms(h->ev0, h->ev1);
     // ---- block rows
     const int64_t bmpad = roundup((int64_t)r + 1, CK_AUX_ALIGN);
-    if (bmpad * h->Npad > h->baux_cap) {
-        dev_free_one(h, h->baux);
-        h->baux = nullptr;
-        h->baux_cap = 0;
-        if (dev_alloc(h, (void**)&h->baux, bmpad * h->Npad * 8)) return -1;
-        h->baux_cap = bmpad * h->Npad;
-    }
+    if (bmpad * h->Npad > (int64_t)h->baux.cap() && dev_alloc(h, h->baux, rhs_bytes(bmpad, h->Npad))) return -1;
     int64_t chunk = h->block_chunk;
     if (chunk <= 0) {   // what the handle may still take (the arena's rest or half of the free memory) beside the point rows it holds
         int64_t avail = 0;
@@ -2421,7 +2353,7 @@ extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int
         }
         // hipMalloc: aux_begin_impl frees the point rows' buffer before it allocates a larger one; an arena never takes
         // memory back, so there the chunk fits either the buffer the handle holds or the arena's rest
-        avail = h->arena ? std::max<int64_t>(avail, h->aux_cap * 8) : avail + h->aux_cap * 8;
+        avail = h->arena ? std::max<int64_t>(avail, aux_cap(h) * 8) : avail + aux_cap(h) * 8;
         chunk = std::max<int64_t>(avail / (8 * h->Npad) - CK_AUX_ALIGN, CK_AUX_ALIGN);
     }
     chunk = std::min<int64_t>(chunk, m);
@@ -2459,7 +2391,7 @@ extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev1, h->stream));
         HIPCHK(hipEventSynchronize(h->ev1));   // the lists are rewritten for the next chunk
-        h->t_ms[17] += elapsed(h->ev0, h->ev1);
+        h->t_ms[17] += elapsed_ms(h->ev0, h->ev1);
     }
     h->t_ms[22] = n_chunks;
     // ---- the forward sweep over the r + 1 block rows on the resident factor, raw reductions V_b . y and |V_b|^2
@@ -2480,8 +2412,8 @@ extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int
     HIPCHK(hipMemcpyAsync(s2.data(), d_red + r, (size_t)r * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(cbar.data(), d_diag, (size_t)r * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->t_ms[19] = elapsed(h->ev2, h->ev3);
-    h->t_ms[20] = elapsed(h->ev0, h->ev1);
+    h->t_ms[19] = elapsed_ms(h->ev2, h->ev3);
+    h->t_ms[20] = elapsed_ms(h->ev0, h->ev1);
     for (int32_t b = 0; b < r; ++b) {
         pred[b] = s1[(size_t)b];
         const double e = sqrt(cbar[(size_t)b] - s2[(size_t)b]);   // negative variance -> NaN -> 0.0 (np.nan_to_num)
@@ -2500,18 +2432,18 @@ extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int
         HIPCHK(hipMemcpyAsync(d_poff_full, poff.data(), poff.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipEventRecord(h->ev0, h->stream));
         for (int J = 0; J < nJ; ++J)
-            HIPCHK(hipMemsetAsync(h->sch_sig[(size_t)J], 0, (size_t)((Mp - (int64_t)J * CK_NB) * CK_NB) * 8, h->stream));
+            HIPCHK(hipMemsetAsync(h->sch.sig[(size_t)J], 0, (size_t)((Mp - (int64_t)J * CK_NB) * CK_NB) * 8, h->stream));
         ck_launch_block_prior(h->stream, h->d_blk + 2 * i, h->metric, d_mx, d_mx + m, d_mx + 2 * m, d_mw, d_off, r, 1,
-                              d_poff_full, n_pieces_full, d_part_full, nullptr, h->d_sch_ptr);
+                              d_poff_full, n_pieces_full, d_part_full, nullptr, h->sch.d_ptr);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev1, h->stream));
-        ck_launch_schur_syrk(h->stream, h->d_sch_ptr, h->baux, bmpad, h->nK, nJ, Mp);
+        ck_launch_schur_syrk(h->stream, h->sch.d_ptr, h->baux, bmpad, h->nK, nJ, Mp);
         HIPCHK(hipGetLastError());
         std::vector<double> panel;
         for (int J = 0; J < nJ; ++J) {   // rows J NB .. r - 1 of block column J; only R >= C is meaningful
             const int64_t R0 = (int64_t)J * CK_NB, rows = r - R0;
             panel.resize((size_t)(rows * CK_NB));
-            HIPCHK(hipMemcpyAsync(panel.data(), h->sch_sig[(size_t)J], (size_t)(rows * CK_NB) * 8, hipMemcpyDeviceToHost,
+            HIPCHK(hipMemcpyAsync(panel.data(), h->sch.sig[(size_t)J], (size_t)(rows * CK_NB) * 8, hipMemcpyDeviceToHost,
                                   h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
             for (int64_t R = R0; R < r; ++R)
@@ -2523,10 +2455,10 @@ extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int
         }
         HIPCHK(hipEventRecord(h->ev2, h->stream));
         HIPCHK(hipEventSynchronize(h->ev2));
-        h->t_ms[18] += elapsed(h->ev0, h->ev1);
-        h->t_ms[20] += elapsed(h->ev1, h->ev2);
+        h->t_ms[18] += elapsed_ms(h->ev0, h->ev1);
+        h->t_ms[20] += elapsed_ms(h->ev1, h->ev2);
     }
-    h->t_ms[21] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    h->t_ms[21] = ms_since(t_begin);
     return 0;
 }
 
@@ -2594,14 +2526,14 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
     // device memory: the Schur buffers, the right-hand sides of the point prediction, one chunk of 128 draws
     {
         const int64_t aux_bytes = roundup(m + 1, CK_AUX_ALIGN) * h->Npad * 8;
-        const int64_t s_bytes = h->sch_M == Mp ? 0 : schur_bytes(Mp);
+        const int64_t s_bytes = h->sch.M == Mp ? 0 : schur_bytes(Mp);
         const int64_t c_bytes = 128 * (Mp + (noise ? 2 : 1) * m) * 8 + (int64_t)m * 13 + Mp * 12 + 1024;
-        const int64_t need = (aux_bytes > h->aux_cap * 8 ? aux_bytes : 0) + s_bytes + c_bytes;
+        const int64_t need = (aux_bytes > aux_cap(h) * 8 ? aux_bytes : 0) + s_bytes + c_bytes;
         size_t fr = 0, tot = 0;
         HIPCHK(hipMemGetInfo(&fr, &tot));
         int64_t avail = (int64_t)fr;
-        if (!h->arena && aux_bytes > h->aux_cap * 8) avail += h->aux_cap * 8;   // released before a larger one is taken
-        if (s_bytes > 0 && h->sch_M > 0) avail += schur_bytes(h->sch_M);       // schur_ensure releases these first
+        if (!h->arena && aux_bytes > aux_cap(h) * 8) avail += aux_cap(h) * 8;   // released before a larger one is taken
+        if (s_bytes > 0 && h->sch.M > 0) avail += schur_bytes(h->sch.M);       // schur_ensure releases these first
         if (need > avail)
             return fail("ck_conditional_draws: needs " + std::to_string(need) + " bytes of device memory (" +
                         std::to_string(s_bytes) + " for the posterior covariance of " + std::to_string(m) + " sites, " +
@@ -2609,19 +2541,11 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
     }
     for (int k = 30; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
     *info = 0;
-    auto elapsed = [&](hipEvent_t a, hipEvent_t b) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, a, b);
-        return (double)ms;
-    };
-    auto wall_ms = [](std::chrono::steady_clock::time_point t0) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    };
     // ---- 1. the point prediction (the same call, the same bits)
     {
         const auto t0 = std::chrono::steady_clock::now();
         if (ck_predict(h, i, pcoords, m, pred, pred_err)) return -1;
-        h->t_ms[30] = wall_ms(t0);
+        h->t_ms[30] = ms_since(t0);
     }
     // ---- 2. S = C_pp - V^T V in the Schur buffers
     if (schur_ensure(h, Mp)) return -1;
@@ -2644,7 +2568,7 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
     HIPCHK(hipMemsetAsync(d_pred, 0, (size_t)Mp * 8, h->stream));
     HIPCHK(hipMemcpyAsync(d_pred, h->d_pred, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));   // internal order
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    ck_launch_draw_deflate(h->stream, h->d_sch_ptr, nJ, m, tol * c0, jitter * c0, d_mask);
+    ck_launch_draw_deflate(h->stream, h->sch.d_ptr, nJ, m, tol * c0, jitter * c0, d_mask);
     HIPCHK(hipGetLastError());
     std::vector<unsigned char> mask((size_t)m);
     HIPCHK(hipMemcpyAsync(mask.data(), d_mask, (size_t)m, hipMemcpyDeviceToHost, h->stream));
@@ -2654,11 +2578,11 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
         deflated[cmap[(size_t)j]] = mask[(size_t)j];
         n_defl += mask[(size_t)j] != 0;
     }
-    if (n_defl > 0) ck_launch_draw_zero(h->stream, h->d_sch_ptr, nJ, m, d_mask);
+    if (n_defl > 0) ck_launch_draw_zero(h->stream, h->sch.d_ptr, nJ, m, d_mask);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipEventSynchronize(h->ev1));
-    h->t_ms[33] = elapsed(h->ev0, h->ev1);
+    h->t_ms[33] = elapsed_ms(h->ev0, h->ev1);
     h->t_ms[38] = (double)n_defl;
     // ---- 4. the factor of S.  Two sites at the same coordinates have identical rows of S: singular unless deflated.  The
     // exact factorisation stops at the later of them (internal order); report that without leaving it to rounding.
@@ -2675,7 +2599,7 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
                 stop = key[q].second;   // the larger internal index of the pair (equal keys are sorted by index)
         if (stop >= 0) {
             *info = 1 + cmap[(size_t)stop];
-            h->t_ms[37] = wall_ms(t_begin);
+            h->t_ms[37] = ms_since(t_begin);
             return 0;
         }
     }
@@ -2685,14 +2609,14 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
         if (schur_factor(h, &v, "call ck_conditional_draws again")) return -1;
         HIPCHK(hipEventRecord(h->ev3, h->stream));
         HIPCHK(hipEventSynchronize(h->ev3));
-        h->t_ms[34] = elapsed(h->ev2, h->ev3);
+        h->t_ms[34] = elapsed_ms(h->ev2, h->ev3);
         if (v != 0) {
             *info = 1 + (v - 1 < m ? cmap[(size_t)(v - 1)] : (int64_t)(v - 1));
-            h->t_ms[37] = wall_ms(t_begin);
+            h->t_ms[37] = ms_since(t_begin);
             return 0;
         }
     }
-    ck_launch_draw_upper(h->stream, h->d_sch_ptr, nJ);
+    ck_launch_draw_upper(h->stream, h->sch.d_ptr, nJ);
     HIPCHK(hipGetLastError());
     // ---- 5 / 6. noise and the draw product, chunk by chunk
     int64_t chunk = h->draw_chunk;
@@ -2716,16 +2640,16 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
         ck_launch_draw_noise(h->stream, d_E, ldp, Mp, nd, m, d0, d_cmap, d_mask, d_noise, seed);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev1, h->stream));
-        ck_launch_draw_trmm(h->stream, d_X, m, d_E, ldp, nd, h->d_sch_ptr, d_pred, d_ones, d_cmap);
+        ck_launch_draw_trmm(h->stream, d_X, m, d_E, ldp, nd, h->sch.d_ptr, d_pred, d_ones, d_cmap);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev2, h->stream));
         HIPCHK(hipMemcpyAsync(draws + d0 * m, d_X, (size_t)(nd * m) * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        h->t_ms[35] += elapsed(h->ev0, h->ev1);
-        h->t_ms[36] += elapsed(h->ev1, h->ev2);
+        h->t_ms[35] += elapsed_ms(h->ev0, h->ev1);
+        h->t_ms[36] += elapsed_ms(h->ev1, h->ev2);
     }
     h->t_ms[39] = n_chunks;
-    h->t_ms[37] = wall_ms(t_begin);
+    h->t_ms[37] = ms_since(t_begin);
     return 0;
 }
 
@@ -2764,11 +2688,7 @@ extern "C" int ck_loocv(ck_handle* h, int i, double* pred, double* pred_err) {
     HIPCHK(hipMemcpyAsync(s1.data(), h->d_pred + 1, m * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(s2.data(), h->d_err + 1, m * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    {
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        h->t_ms[3] = ms;
-    }
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &h->t_ms[3]));
     const double* zi = h->h_values[i].data();
     for (int64_t q = 0; q < m; ++q) {   // q: internal position; results go to the caller's index
         const int64_t x = h->perm[i][(size_t)q];
@@ -2833,12 +2753,12 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
     const long long slab_doubles = slab_bytes / 8;
     {   // device memory: the right-hand sides and the slab, as far as they have to grow
         const int64_t aux_bytes = mpad_need * Np * 8;
-        const bool grow = aux_bytes > h->aux_cap * 8, grow_slab = slab_doubles > h->local_slab_doubles;
+        const bool grow = aux_bytes > aux_cap(h) * 8, grow_slab = slab_doubles > local_slab_doubles(h);
         size_t fr = 0, tot = 0;
         HIPCHK(hipMemGetInfo(&fr, &tot));
         int64_t avail = (int64_t)fr;
-        if (!h->arena && grow) avail += h->aux_cap * 8;       // released before the larger one is taken
-        if (grow_slab) avail += h->local_slab_doubles * 8;   // likewise
+        if (!h->arena && grow) avail += aux_cap(h) * 8;       // released before the larger one is taken
+        if (grow_slab) avail += local_slab_doubles(h) * 8;   // likewise
         if (h->arena && grow && aux_bytes > h->arena_size - h->arena_used)
             return fail("ck_cv_folds needs " + std::to_string(aux_bytes) + " bytes of the arena for its " + std::to_string(m + 1) +
                         " right-hand-side rows of " + std::to_string(Np) + " doubles; " + std::to_string(h->arena_size - h->arena_used) +
@@ -2854,11 +2774,6 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
     *info = 0;
     for (int64_t a = 0; a < ni; ++a) pred[a] = pred_err[a] = NAN;
     for (int k = 56; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
-    auto elapsed = [&](hipEvent_t a, hipEvent_t b) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, a, b);
-        return (double)ms;
-    };
     struct Guard {
         ck_handle* h;
         ~Guard() {
@@ -2869,13 +2784,8 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
     // ---- 1. rows and sweep
     if (aux_begin_impl(h, i, nullptr, m, false)) return -1;
     h->aux_state = 6;
-    if (slab_doubles > h->local_slab_doubles) {   // outside the timed stages: only the first call of a layout allocates
-        if (h->local_slab) (void)hipFree(h->local_slab);
-        h->local_slab = nullptr;
-        h->local_slab_doubles = 0;
-        HIPCHK(hipMalloc((void**)&h->local_slab, (size_t)slab_bytes));
-        h->local_slab_doubles = slab_doubles;
-    }
+    // outside the timed stages: only the first call of a layout allocates
+    if (slab_doubles > local_slab_doubles(h)) HIPCHK(h->local_slab.reserve((size_t)slab_doubles));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     HIPCHK(hipMemsetAsync(h->aux, 0, (size_t)h->mpad * Np * 8, h->stream));
     h->loo_g0 = plan.pmin;
@@ -2894,7 +2804,7 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
         sysv[(size_t)y] = CkLocalSys{b.off, b.s, b.kq, b.ld, b.gbase};
         kqv[(size_t)y] = b.kq;
     }
-    char* const slab = (char*)h->local_slab;
+    char* const slab = (char*)h->local_slab.get();
     double *d_buf = (double*)(slab + o_buf), *d_x = (double*)(slab + o_x), *d_d = (double*)(slab + o_d),
            *d_stat = (double*)(slab + o_stat);
     long long* d_linfo = (long long*)(slab + o_linfo);
@@ -2943,9 +2853,9 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
     HIPCHK(hipMemcpyAsync(st.data(), d_stat, (size_t)n_folds * 16, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(fl.data(), d_fail, (size_t)n_folds * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->t_ms[56] = elapsed(h->ev0, h->ev1);
-    h->t_ms[57] = elapsed(h->ev1, h->ev2);
-    h->t_ms[58] = elapsed(h->ev2, h->ev3);
+    h->t_ms[56] = elapsed_ms(h->ev0, h->ev1);
+    h->t_ms[57] = elapsed_ms(h->ev1, h->ev2);
+    h->t_ms[58] = elapsed_ms(h->ev2, h->ev3);
     const double* zi = h->h_values[i].data();
     for (int32_t f = 0; f < n_folds; ++f) {
         const int s = plan.off[(size_t)f + 1] - plan.off[(size_t)f];
@@ -2966,7 +2876,7 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
             pred_err[x] = (e == e) ? e : 0.0;
         }
     }
-    h->t_ms[59] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    h->t_ms[59] = ms_since(t_begin);
     return 0;
 }
 
@@ -3023,15 +2933,15 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
         int64_t g_bytes = 0;
         for (int J = 0; J < h->nK; ++J) g_bytes += ((Np - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;
         const int64_t aux_bytes = mpad_need * Np * 8;
-        const int64_t need = (aux_bytes > h->aux_cap * 8 ? aux_bytes : 0) + (h->sch_M == Np ? 0 : g_bytes);
+        const int64_t need = (aux_bytes > aux_cap(h) * 8 ? aux_bytes : 0) + (h->sch.M == Np ? 0 : g_bytes);
         size_t fr = 0, tot = 0;
         HIPCHK(hipMemGetInfo(&fr, &tot));
         int64_t avail = (int64_t)fr;
-        if (!h->arena) avail += h->aux_cap * 8;   // the right-hand sides' buffer is released before a larger one is taken
-        if (h->sch_M != Np)
-            for (int J = 0; J < (int)h->sch_sig.size(); ++J)
-                avail += ((h->sch_M - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;   // schur_ensure releases these first
-        if (h->arena && aux_bytes > h->aux_cap * 8 && aux_bytes > h->arena_size - h->arena_used)
+        if (!h->arena) avail += aux_cap(h) * 8;   // the right-hand sides' buffer is released before a larger one is taken
+        if (h->sch.M != Np)
+            for (int J = 0; J < (int)h->sch.sig.size(); ++J)
+                avail += ((h->sch.M - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;   // schur_ensure releases these first
+        if (h->arena && aux_bytes > aux_cap(h) * 8 && aux_bytes > h->arena_size - h->arena_used)
             return fail(std::string(name) + ": the gradient needs " + std::to_string(aux_bytes) + " bytes of the arena for its " +
                         std::to_string(mrows + 1 + p) + " right-hand-side rows of " + std::to_string(Np) + " doubles; " +
                         std::to_string(h->arena_size - h->arena_used) + " bytes are left");
@@ -3044,11 +2954,6 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
     LikCallGuard guard(h);
     for (int k = 24; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
     h->t_ms[24] = h->t_ms[0];   // the assembly of this Sigma (ck_assemble_joint)
-    auto elapsed = [&](hipEvent_t a, hipEvent_t b) {
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, a, b);
-        return (double)ms;
-    };
     // ---- the factor: factor here, or the resident one of a preceding ck_factor
     if (!h->factored) {
         if (ck_factor(h, info)) return -1;
@@ -3059,7 +2964,7 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
     if (*info != 0) {   // not positive definite: the factor is unusable; assemble again before the next call
         h->factored = false;
         h->assembled = false;
-        h->t_ms[29] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        h->t_ms[29] = ms_since(t_begin);
         return 0;
     }
     const CkLayout L = layout_of(h);
@@ -3103,7 +3008,7 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
         HIPCHK(hipMemcpyAsync(W.data(), h->d_univ, W.size() * 8, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->t_ms[26] = elapsed(h->ev0, h->ev1);
+    h->t_ms[26] = elapsed_ms(h->ev0, h->ev1);
     double half_logdet = 0.0;
     for (int K = 0; K < h->nK; ++K) half_logdet += ldp[(size_t)K];
     const double logdet = 2.0 * half_logdet;
@@ -3155,7 +3060,7 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
         }
         if (schur_ensure(h, Np)) return -1;
         HIPCHK(hipEventRecord(h->ev0, h->stream));
-        ck_launch_ginv_syrk(h->stream, h->d_sch_ptr, h->aux, h->mpad, avec, h->nK, h->nend, q, Np, q);
+        ck_launch_ginv_syrk(h->stream, h->sch.d_ptr, h->aux, h->mpad, avec, h->nK, h->nend, q, Np, q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev1, h->stream));
         // ---- the contraction: the model's blocks and their nu +- dnu, nu +- 2 dnu neighbours
@@ -3170,20 +3075,20 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
             for (int k = 0; k < 4; ++k)
                 ck_matern_prepare(m.nu + offs[k] * dnu3[b], m.len_scale, m.amp, m.nugget, &hb[5 * b + 1 + k]);
         }
-        if (!h->d_lik_blk) HIPCHK(hipMalloc((void**)&h->d_lik_blk, sizeof(hb)));
+        HIPCHK(h->d_lik_blk.reserve(sizeof(hb) / sizeof(CkMatern)));
         HIPCHK(hipMemcpyAsync(h->d_lik_blk, hb, sizeof(hb), hipMemcpyHostToDevice, h->stream));
         const int64_t ngr = ck_lik_grad_groups(L);
         double* d_part = nullptr;
         HIPCHK(tmp.get(&d_part, (size_t)(ngr * CK_LIK_NPAR) * 8));
-        ck_launch_loglik_grad(h->stream, h->d_sch_ptr, L, h->n_procs, h->metric, h->s0, h->d_lik_blk, dnu3, h->par_sigma[0],
+        ck_launch_loglik_grad(h->stream, h->sch.d_ptr, L, h->n_procs, h->metric, h->s0, h->d_lik_blk, dnu3, h->par_sigma[0],
                               h->par_sigma[1], h->par_rho, d_part);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev2, h->stream));
         std::vector<double> part((size_t)(ngr * CK_LIK_NPAR));
         HIPCHK(hipMemcpyAsync(part.data(), d_part, part.size() * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));   // (hb is stack memory)
-        h->t_ms[27] = elapsed(h->ev0, h->ev1);
-        h->t_ms[28] = elapsed(h->ev1, h->ev2);
+        h->t_ms[27] = elapsed_ms(h->ev0, h->ev1);
+        h->t_ms[28] = elapsed_ms(h->ev1, h->ev2);
         double g[CK_LIK_NPAR] = {};
         for (int64_t w = 0; w < ngr; ++w)
             for (int k = 0; k < CK_LIK_NPAR; ++k) g[k] += part[(size_t)(w * CK_LIK_NPAR + k)];
@@ -3194,7 +3099,7 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
         if (!h->noise_var[0].empty() || (h->n_procs == 2 && !h->noise_var[1].empty())) {
             double* d_np = nullptr;
             HIPCHK(tmp.get(&d_np, (size_t)(2 * h->nK) * 8));
-            ck_launch_lik_noise_grad(h->stream, h->d_sch_ptr, h->nK, L, h->d_noise + Np, d_np);
+            ck_launch_lik_noise_grad(h->stream, h->sch.d_ptr, h->nK, L, h->d_noise + Np, d_np);
             HIPCHK(hipGetLastError());
             std::vector<double> np2((size_t)(2 * h->nK));
             HIPCHK(hipMemcpyAsync(np2.data(), d_np, np2.size() * 8, hipMemcpyDeviceToHost, h->stream));
@@ -3205,7 +3110,7 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
         }
         h->lik_noise_valid = true;
     }
-    h->t_ms[29] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    h->t_ms[29] = ms_since(t_begin);
     return 0;
 }
 
@@ -3337,7 +3242,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     }
     size_t mem_free = 0, mem_total = 0;
     HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
-    mem_free += (size_t)h->local_slab_doubles * 8;   // the slab kept from an earlier call is ours to reuse
+    mem_free += (size_t)local_slab_doubles(h) * 8;   // the slab kept from an earlier call is ours to reuse
     long long budget = (long long)std::min<size_t>(mem_free / 4, (size_t)32 << 30) / 8;   // doubles
     if (h->local_slab_mb > 0) budget = (long long)h->local_slab_mb * (1 << 20) / 8;      // option "local_slab_mb" (tests)
     if (budget < need_max) budget = need_max;
@@ -3386,27 +3291,21 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     }
     h->t_ms[14] = 0.0;
     const auto t_grow = std::chrono::steady_clock::now();
-    if (slab_doubles > h->local_slab_doubles) {
+    if (slab_doubles > local_slab_doubles(h)) {
         // Growing is what stalls: hipMalloc of tens of GiB right after a hipFree of a few GiB that were written
         // took 1-4 s every time (scripts/diag_malloc.py).  So: beyond 1 GiB take the whole budget at once (the
         // slab then never grows again), and allocate the new slab before releasing the old one.
         const long long want = slab_doubles * 8 > (1LL << 30) ? std::max(slab_doubles, budget) : slab_doubles;
-        double* fresh = nullptr;
-        if (hipMalloc((void**)&fresh, (size_t)want * 8) != hipSuccess) {
+        DevBuf<double> fresh;
+        if (fresh.reserve((size_t)want) != hipSuccess) {
             (void)hipGetLastError();
-            if (h->local_slab) (void)hipFree(h->local_slab);   // not enough room for both
-            h->local_slab = nullptr;
-            h->local_slab_doubles = 0;
-            HIPCHK(hipMalloc((void**)&fresh, (size_t)slab_doubles * 8));
-            h->local_slab_doubles = slab_doubles;
-        } else {
-            if (h->local_slab) (void)hipFree(h->local_slab);
-            h->local_slab_doubles = want;
+            h->local_slab.reset();   // not enough room for both
+            HIPCHK(fresh.reserve((size_t)slab_doubles));
         }
-        h->local_slab = fresh;
+        h->local_slab = std::move(fresh);   // releases the old slab
         // visible in ck_timings [14]; profiles/r03c_local_predictor.json's 100 km row (1 262 ms for a 3 ms call) was this
         // allocation inside the one event window of round 3
-        h->t_ms[14] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_grow).count();
+        h->t_ms[14] = ms_since(t_grow);
     }
     if (slab_doubles > 0) d_slab = h->local_slab;
     HIPCHK(hipEventRecord(h->ev2, h->stream));
@@ -3487,10 +3386,10 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     HIPCHK(hipMemcpyAsync(pred, d_out, m * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(pred_err, d_out + mp, m * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    float ms = 0, ms2 = 0;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    HIPCHK(hipEventElapsedTime(&ms2, h->ev2, h->ev3));
-    h->t_ms[10] = (double)ms + (double)ms2;   // device work: counting pass + assembly / factorisations / reductions
+    double ms = 0, ms2 = 0;
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms));
+    HIPCHK(elapsed_ms(h->ev2, h->ev3, &ms2));
+    h->t_ms[10] = ms + ms2;   // device work: counting pass + assembly / factorisations / reductions
     int64_t npd = 0;
     if (u) {
         std::vector<int> stat((size_t)m);
@@ -3512,14 +3411,14 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
         if (u->n_rank_def) *u->n_rank_def = nrd;
         double red_ms = 0.0;
         for (size_t e = 0; e + 1 < ev_red.size(); e += 2) {
-            float t = 0;
-            HIPCHK(hipEventElapsedTime(&t, ev_red[e], ev_red[e + 1]));
+            double t = 0;
+            HIPCHK(elapsed_ms(ev_red[e], ev_red[e + 1], &t));
             red_ms += t;
         }
         h->t_ms[48] = ms;                      // the counting pass
         h->t_ms[49] = (double)ms2 - red_ms;    // assembly and factorisation (the LDS class's kernel whole)
         h->t_ms[50] = red_ms;                  // the tiled class's universal reduction (Gram matrix + GLS step)
-        h->t_ms[51] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        h->t_ms[51] = ms_since(t_begin);
         h->t_ms[52] = (double)(m - (int64_t)tiled.size());   // points of the LDS class (the empty ones among them)
         h->t_ms[53] = (double)tiled.size();                  // points of the tiled class
     } else {
@@ -3570,48 +3469,26 @@ extern "C" int ck_local_reserve(ck_handle* h, int64_t nbytes) {
     if (nbytes == 0) {
         size_t mem_free = 0, mem_total = 0;
         HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
-        mem_free += (size_t)h->local_slab_doubles * 8;
+        mem_free += (size_t)local_slab_doubles(h) * 8;
         want = (long long)std::min<size_t>(mem_free / 4, (size_t)32 << 30) / 8;
         if (h->local_slab_mb > 0) want = (long long)h->local_slab_mb * (1 << 20) / 8;
     }
-    if (want <= h->local_slab_doubles) return 0;
+    if (want <= local_slab_doubles(h)) return 0;
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->local_slab) (void)hipFree(h->local_slab);
-    h->local_slab = nullptr;
-    h->local_slab_doubles = 0;
-    HIPCHK(hipMalloc((void**)&h->local_slab, (size_t)want * 8));
-    h->local_slab_doubles = want;
-    h->t_ms[14] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    HIPCHK(h->local_slab.reserve((size_t)want));
+    h->t_ms[14] = ms_since(t0);
     return 0;
 }
 
 // ---------------------------------------------------------------------------------------
 // empirical (cross-)variogram: src/fields.py:192-232
 // ---------------------------------------------------------------------------------------
-static void vario_free(ck_handle* h) {
-    void* ps[] = {h->vg_iu, h->vg_iv, h->vg_same ? nullptr : h->vg_ju, h->vg_same ? nullptr : h->vg_jv,
-                  h->vg_part, h->vg_psum, h->vg_pcnt, h->vg_out, h->vg_jb, h->vg_ib64, h->vg_jbsub,
-                  h->vg_best, h->vg_list, h->vg_count};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-    h->vg_iu = h->vg_iv = h->vg_ju = h->vg_jv = nullptr;
-    h->vg_jb = h->vg_ib64 = h->vg_jbsub = nullptr;
-    h->vg_best = nullptr;
-    h->vg_part = nullptr;
-    h->vg_psum = nullptr;
-    h->vg_pcnt = nullptr;
-    h->vg_out = nullptr;
-    h->vg_list = nullptr;
-    h->vg_count = nullptr;
-    h->vg_list_cap = 0;
-}
-
 // Upload one field's points.  From 2 048 points on (and unless site_order = 0) they are first laid out along a
 // Hilbert curve: bins sums and counts do not depend on the order of the points (up to rounding of the sums), and
 // compact blocks of points are what lets the kernels skip whole pair tiles (ck_vario.hip, "tile culling").
 // host_coords / host_vals receive the points in the order the device sees them (pairs come back as indices).
-static int vario_upload(ck_handle* h, const double* coords, const double* vals, int64_t n, double** u, double** v,
+static int vario_upload(ck_handle* h, const double* coords, const double* vals, int64_t n, DevBuf<double>& u, DevBuf<double>& v,
                         std::vector<double>& host_coords, std::vector<double>& host_vals) {
     host_coords.assign(coords, coords + 2 * n);
     host_vals.assign(vals, vals + n);
@@ -3631,12 +3508,12 @@ static int vario_upload(ck_handle* h, const double* coords, const double* vals, 
     }
     DevTemps tmp;
     double* stage = nullptr;
-    HIPCHK(hipMalloc((void**)u, 3 * n * 8));
-    HIPCHK(hipMalloc((void**)v, n * 8));
+    HIPCHK(u.reserve((size_t)(3 * n)));
+    HIPCHK(v.reserve((size_t)n));
     HIPCHK(tmp.get(&stage, (size_t)(2 * n * 8)));
     HIPCHK(hipMemcpyAsync(stage, host_coords.data(), 2 * n * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(*v, host_vals.data(), n * 8, hipMemcpyHostToDevice, h->stream));
-    ck_launch_vario_prep(h->stream, stage, n, h->metric, *u, *u + n, *u + 2 * n);
+    HIPCHK(hipMemcpyAsync(v, host_vals.data(), n * 8, hipMemcpyHostToDevice, h->stream));
+    ck_launch_vario_prep(h->stream, stage, n, h->metric, u, u + n, u + 2 * n);
     HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -3648,36 +3525,38 @@ extern "C" int ck_vario_begin(ck_handle* h, const double* coords_i, const double
     if (!same && (n_j <= 0 || !coords_j || !resid_j)) return fail("bad field j");
     // the binning kernel addresses the "j" arrays with 32-bit byte offsets (8 n_j < 2^32) and lists pairs as int indices
     if (n_i >= (1LL << 28) || n_j >= (1LL << 28)) return fail("at most 2^28 - 1 points per field");
-    vario_free(h);
+    h->vg = {};
     h->vg_same = same ? 1 : 0;
     h->vg_ni = n_i;
-    if (vario_upload(h, coords_i, resid_i, n_i, &h->vg_iu, &h->vg_iv, h->vg_ci, h->vg_vi)) return -1;
+    if (vario_upload(h, coords_i, resid_i, n_i, h->vg.iu, h->vg.iv, h->vg_ci, h->vg_vi)) return -1;
     if (same) {
         h->vg_nj = n_i;
         h->vg_cj = h->vg_ci;
         h->vg_vj = h->vg_vi;
-        h->vg_ju = h->vg_iu;
-        h->vg_jv = h->vg_iv;
+        h->vg.ju = h->vg.iu;
+        h->vg.jv = h->vg.iv;
     } else {
         h->vg_nj = n_j;
-        if (vario_upload(h, coords_j, resid_j, n_j, &h->vg_ju, &h->vg_jv, h->vg_cj, h->vg_vj)) return -1;
+        if (vario_upload(h, coords_j, resid_j, n_j, h->vg.ju_own, h->vg.jv_own, h->vg_cj, h->vg_vj)) return -1;
+        h->vg.ju = h->vg.ju_own;
+        h->vg.jv = h->vg.jv_own;
     }
-    HIPCHK(hipMalloc((void**)&h->vg_ib64, (size_t)(4 * ck_vario_nblocks(h->vg_ni, 64) * 8)));
-    HIPCHK(hipMalloc((void**)&h->vg_jb, (size_t)(4 * ck_vario_nblocks(h->vg_nj, CK_VG_JCHUNK) * 8)));
-    HIPCHK(hipMalloc((void**)&h->vg_jbsub, (size_t)(4 * ck_vario_nblocks(h->vg_nj, CK_VG_JSUB) * 8)));
-    HIPCHK(hipMalloc((void**)&h->vg_best, 16));
-    ck_launch_vario_bounds(h->stream, h->vg_iu, h->vg_ni, 64, h->vg_ib64);
-    ck_launch_vario_bounds(h->stream, h->vg_ju, h->vg_nj, CK_VG_JCHUNK, h->vg_jb);
-    ck_launch_vario_bounds(h->stream, h->vg_ju, h->vg_nj, CK_VG_JSUB, h->vg_jbsub);
+    HIPCHK(h->vg.ib64.reserve((size_t)(4 * ck_vario_nblocks(h->vg_ni, 64))));
+    HIPCHK(h->vg.jb.reserve((size_t)(4 * ck_vario_nblocks(h->vg_nj, CK_VG_JCHUNK))));
+    HIPCHK(h->vg.jbsub.reserve((size_t)(4 * ck_vario_nblocks(h->vg_nj, CK_VG_JSUB))));
+    HIPCHK(h->vg.best.reserve(2));
+    ck_launch_vario_bounds(h->stream, h->vg.iu, h->vg_ni, 64, h->vg.ib64);
+    ck_launch_vario_bounds(h->stream, h->vg.ju, h->vg_nj, CK_VG_JCHUNK, h->vg.jb);
+    ck_launch_vario_bounds(h->stream, h->vg.ju, h->vg_nj, CK_VG_JSUB, h->vg.jbsub);
     HIPCHK(hipGetLastError());
     h->vg_bgrid = ck_vario_bin_grid(h->vg_ni, h->vg_nj);
-    HIPCHK(hipMalloc(&h->vg_part, h->vg_bgrid * sizeof(CkVarioExt)));
-    HIPCHK(hipMalloc((void**)&h->vg_psum, (size_t)h->vg_bgrid * CK_VG_MAXBINS * 8));
-    HIPCHK(hipMalloc((void**)&h->vg_pcnt, (size_t)h->vg_bgrid * (CK_VG_MAXBINS + 1) * 8));
-    HIPCHK(hipMalloc((void**)&h->vg_out, (3 * (CK_VG_MAXBINS + 2) + CK_VG_MAXBINS + CK_VG_MAXBINS + 1) * 8 + CK_VG_ARGS_BYTES));
-    HIPCHK(hipMalloc((void**)&h->vg_count, sizeof(unsigned)));
-    h->vg_list_cap = 1u << 20;
-    HIPCHK(hipMalloc((void**)&h->vg_list, (size_t)h->vg_list_cap * sizeof(CkVarioPair)));
+    HIPCHK(h->vg.part.reserve((size_t)h->vg_bgrid));
+    HIPCHK(h->vg.psum.reserve((size_t)h->vg_bgrid * CK_VG_MAXBINS));
+    HIPCHK(h->vg.pcnt.reserve((size_t)h->vg_bgrid * (CK_VG_MAXBINS + 1)));
+    static_assert(CK_VG_ARGS_BYTES % 8 == 0, "vg.out is counted in 8-byte words");
+    HIPCHK(h->vg.out.reserve(3 * (CK_VG_MAXBINS + 2) + CK_VG_MAXBINS + CK_VG_MAXBINS + 1 + CK_VG_ARGS_BYTES / 8));
+    HIPCHK(h->vg.count.reserve(1));
+    HIPCHK(h->vg.list.reserve((size_t)1 << 20));
     for (int k = 0; k < 4; ++k) h->vg_stats[k] = 0;
     return 0;
 }
@@ -3686,26 +3565,24 @@ extern "C" int ck_vario_begin(ck_handle* h, const double* coords_i, const double
 // the list is then re-allocated and the caller runs the kernel again
 static int vario_fetch_list(ck_handle* h, std::vector<CkVarioPair>& out, bool* overflow) {
     unsigned cnt = 0;
-    HIPCHK(hipMemcpyAsync(&cnt, h->vg_count, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&cnt, h->vg.count, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    *overflow = cnt > h->vg_list_cap;
+    *overflow = cnt > (unsigned)h->vg.list.cap();
     if (*overflow) {
-        (void)hipFree(h->vg_list);
-        h->vg_list = nullptr;
+        h->vg.list.reset();
         const uint64_t want = (uint64_t)cnt + cnt / 4 + 1024;
         if (want > 0xfffffff0ull) return fail("variogram: too many pairs on a bin edge for the host list");
-        h->vg_list_cap = (unsigned)want;
-        HIPCHK(hipMalloc((void**)&h->vg_list, (size_t)h->vg_list_cap * sizeof(CkVarioPair)));
+        HIPCHK(h->vg.list.reserve((size_t)want));
         return 0;
     }
     out.resize(cnt);
-    if (cnt) HIPCHK(hipMemcpy(out.data(), h->vg_list, (size_t)cnt * sizeof(CkVarioPair), hipMemcpyDeviceToHost));
+    if (cnt) HIPCHK(hipMemcpy(out.data(), h->vg.list, (size_t)cnt * sizeof(CkVarioPair), hipMemcpyDeviceToHost));
     return 0;
 }
 
 extern "C" int ck_vario_extent(ck_handle* h, double max_dist, double* lo, double* hi, int64_t* n_positive) {
     CHKH(h);
-    if (!h->vg_iu) return fail("ck_vario_begin has not been called");
+    if (!h->vg.iu) return fail("ck_vario_begin has not been called");
     if (!(max_dist >= 0.0)) return fail("max_dist must be >= 0");
     *lo = *hi = NAN;
     *n_positive = 0;
@@ -3728,13 +3605,13 @@ extern "C" int ck_vario_extent(ck_handle* h, double max_dist, double* lo, double
         // lies inside it, and the candidates for the largest distance are then complete without a second pass.
         const double win = fmax(1e-9 * cap, 8.0 * ck_host_vario_band(metric, cap));
         const double qwin_lo = cap - win;
-        HIPCHK(hipMemsetAsync(h->vg_count, 0, sizeof(unsigned), h->stream));
-        ck_launch_vario_extent(h->stream, h->vg_bgrid, h->vg_same, h->vg_iu, h->vg_ni, h->vg_ju, h->vg_nj, cap, h->vg_part,
-                               h->rank, h->world, h->vg_ib64, h->vg_jb, h->vg_jbsub, ck_host_vario_cmax(cap), h->vg_best, qwin_lo,
-                               h->vg_list, h->vg_count, h->vg_list_cap);
+        HIPCHK(hipMemsetAsync(h->vg.count, 0, sizeof(unsigned), h->stream));
+        ck_launch_vario_extent(h->stream, h->vg_bgrid, h->vg_same, h->vg.iu, h->vg_ni, h->vg.ju, h->vg_nj, cap, h->vg.part,
+                               h->rank, h->world, h->vg.ib64, h->vg.jb, h->vg.jbsub, ck_host_vario_cmax(cap), h->vg.best, qwin_lo,
+                               h->vg.list, h->vg.count, (unsigned)h->vg.list.cap());
         HIPCHK(hipGetLastError());
         std::vector<CkVarioExt> part(h->vg_bgrid);
-        HIPCHK(hipMemcpyAsync(part.data(), h->vg_part, h->vg_bgrid * sizeof(CkVarioExt), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(part.data(), h->vg.part, h->vg_bgrid * sizeof(CkVarioExt), hipMemcpyDeviceToHost, h->stream));
         std::vector<CkVarioPair> wcand;
         bool woverflow = false;
         if (vario_fetch_list(h, wcand, &woverflow)) return -1;   // synchronises the stream
@@ -3763,10 +3640,10 @@ extern "C" int ck_vario_extent(ck_handle* h, double max_dist, double* lo, double
             std::vector<CkVarioPair> cand;
             const double top_from = top_done ? INFINITY : qtop_lo;   // top candidates already decided: the bottom ones only
             for (int pass = 0; pass < 3; ++pass) {
-                HIPCHK(hipMemsetAsync(h->vg_count, 0, sizeof(unsigned), h->stream));
-                ck_launch_vario_collect(h->stream, h->vg_bgrid, h->vg_same, h->vg_iu, h->vg_ni, h->vg_ju, h->vg_nj, top_from, cap,
-                                        qbot_hi, h->vg_list, h->vg_count, h->vg_list_cap, h->rank, h->world, h->vg_ib64, h->vg_jb,
-                                        h->vg_jbsub);
+                HIPCHK(hipMemsetAsync(h->vg.count, 0, sizeof(unsigned), h->stream));
+                ck_launch_vario_collect(h->stream, h->vg_bgrid, h->vg_same, h->vg.iu, h->vg_ni, h->vg.ju, h->vg_nj, top_from, cap,
+                                        qbot_hi, h->vg.list, h->vg.count, (unsigned)h->vg.list.cap(), h->rank, h->world, h->vg.ib64, h->vg.jb,
+                                        h->vg.jbsub);
                 HIPCHK(hipGetLastError());
                 bool overflow = false;
                 if (vario_fetch_list(h, cand, &overflow)) return -1;
@@ -3791,7 +3668,7 @@ extern "C" int ck_vario_extent(ck_handle* h, double max_dist, double* lo, double
 extern "C" int ck_vario_bin(ck_handle* h, double max_dist, const double* edges, int n_edges, int covariogram,
                             double* sums, int64_t* counts) {
     CHKH(h);
-    if (!h->vg_iu) return fail("ck_vario_begin has not been called");
+    if (!h->vg.iu) return fail("ck_vario_begin has not been called");
     const int nb = n_edges - 1;
     if (nb < 1 || nb > CK_VG_MAXBINS) return fail("n_bins must be between 1 and " + std::to_string(CK_VG_MAXBINS));
     for (int b = 0; b < nb; ++b)
@@ -3806,10 +3683,10 @@ extern "C" int ck_vario_bin(ck_handle* h, double max_dist, const double* edges, 
     const double *cxa = lv.cxa, *cxb = lv.cxb, *cthr = lv.cthr;
     const int* clast = lv.clast;
     const double q_reach = lv.q_reach;
-    double* d_xa = h->vg_out;
-    double* d_xb = h->vg_out + (CK_VG_MAXBINS + 2);
-    double* d_dthr = h->vg_out + 2 * (CK_VG_MAXBINS + 2);
-    double* d_sums = h->vg_out + 3 * (CK_VG_MAXBINS + 2);
+    double* d_xa = h->vg.out;
+    double* d_xb = h->vg.out + (CK_VG_MAXBINS + 2);
+    double* d_dthr = h->vg.out + 2 * (CK_VG_MAXBINS + 2);
+    double* d_sums = h->vg.out + 3 * (CK_VG_MAXBINS + 2);
     long long* d_cnt = (long long*)(d_sums + CK_VG_MAXBINS);
     void* d_args = (void*)(d_cnt + CK_VG_MAXBINS + 1);
     HIPCHK(hipMemcpyAsync(d_xa, cxa, (EC + 1) * 8, hipMemcpyHostToDevice, h->stream));
@@ -3818,11 +3695,11 @@ extern "C" int ck_vario_bin(ck_handle* h, double max_dist, const double* edges, 
     HIPCHK(hipStreamSynchronize(h->stream));   // the arrays are on the stack
     std::vector<CkVarioPair> fix;
     for (int pass = 0; pass < 3; ++pass) {
-        HIPCHK(hipMemsetAsync(h->vg_count, 0, sizeof(unsigned), h->stream));
+        HIPCHK(hipMemsetAsync(h->vg.count, 0, sizeof(unsigned), h->stream));
         HIPCHK(hipEventRecord(h->ev0, h->stream));
-        ck_launch_vario_bin(h->stream, metric, h->vg_same, covariogram ? 1 : 0, h->vg_iu, h->vg_iv, h->vg_ni, h->vg_ju,
-                            h->vg_jv, h->vg_nj, EC, d_xa, d_xb, d_dthr, ck_host_vario_cmax(q_reach), h->vg_ib64, h->vg_jb, h->vg_jbsub,
-                            h->vg_bgrid, h->vg_psum, h->vg_pcnt, h->vg_list, h->vg_count, h->vg_list_cap, h->rank, h->world,
+        ck_launch_vario_bin(h->stream, metric, h->vg_same, covariogram ? 1 : 0, h->vg.iu, h->vg.iv, h->vg_ni, h->vg.ju,
+                            h->vg.jv, h->vg_nj, EC, d_xa, d_xb, d_dthr, ck_host_vario_cmax(q_reach), h->vg.ib64, h->vg.jb, h->vg.jbsub,
+                            h->vg_bgrid, h->vg.psum, h->vg.pcnt, h->vg.list, h->vg.count, (unsigned)h->vg.list.cap(), h->rank, h->world,
                             EC, d_sums, d_cnt, d_args);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev1, h->stream));
@@ -3854,9 +3731,7 @@ extern "C" int ck_vario_bin(ck_handle* h, double max_dist, const double* edges, 
     }
     h->vg_stats[1] = (int64_t)fix.size();
     h->vg_stats[2] = dcn[CK_VG_MAXBINS];
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->t_ms[9] = ms;
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &h->t_ms[9]));
     return 0;
 }
 
@@ -3868,7 +3743,7 @@ extern "C" int ck_vario_stats(ck_handle* h, int64_t* out, int n) {
 
 extern "C" int ck_vario_end(ck_handle* h) {
     CHKH(h);
-    vario_free(h);
+    h->vg = {};
     return 0;
 }
 
@@ -4004,9 +3879,9 @@ extern "C" int ck_debug_potrf_profile(ck_handle* h, int iters, double* out8) {
         }
         HIPCHK(hipEventRecord(h->ev1, h->stream));
         HIPCHK(hipEventSynchronize(h->ev1));
-        float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        out8[6 + which] = (double)ms * 1e3 / iters;
+        double ms = 0;
+        HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms));
+        out8[6 + which] = ms * 1e3 / iters;
     }
     {   // s_memtime ticks at the shader clock: scale the phases so that they add up to the instrumented launch's duration
         double sum = 0;
@@ -4035,7 +3910,7 @@ extern "C" int ck_debug_coop_profile(ck_handle* h, int64_t rows, double* out64) 
     for (int64_t i = 0; i < rows; ++i)
         for (int j = 0; j < CK_NB; ++j) A[(size_t)i * CK_NB + j] = (i == j ? 600.0 : 0.0) + 1.0 / (1.0 + (double)(i % 977) + j);
     long long hp[64];
-    float ms = 0;
+    double ms = 0;
     for (int it = 0; it < 3; ++it) {
         HIPCHK(hipMemcpyAsync(dP, A.data(), A.size() * 8, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemsetAsync(dinfo, 0, 8, h->stream));
@@ -4046,7 +3921,7 @@ extern "C" int ck_debug_coop_profile(ck_handle* h, int64_t rows, double* out64) 
         HIPCHK(hipEventRecord(h->ev1, h->stream));
         HIPCHK(hipMemcpyAsync(hp, dprof, sizeof(hp), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms));
     }
     HIPCHK(hipGetLastError());
     // the chain from link 1's first stamp to link 7's last takes (launch - head - tail); the stamps tick at the shader clock:
@@ -4056,7 +3931,7 @@ extern "C" int ck_debug_coop_profile(ck_handle* h, int64_t rows, double* out64) 
     for (int b = 1; b <= 7; ++b)
         for (int k = 1; k < 8; ++k) out64[8 * b + k] = (double)(hp[8 * b + k] - hp[8 * b]) / mhz;
     for (int b = 2; b <= 7; ++b) out64[8 * b] = (double)(hp[8 * b] - hp[8 * (b - 1)]) / mhz;   // link-to-link period
-    out64[0] = (double)ms * 1e3;
+    out64[0] = ms * 1e3;
     out64[1] = mhz;
     return 0;
 }
@@ -4108,13 +3983,13 @@ extern "C" int ck_debug_stream_overlap(ck_handle* h, int mode, int64_t rows, int
     HIPCHK(hipStreamSynchronize(M));
     HIPCHK(hipStreamSynchronize(S));
     HIPCHK(hipGetLastError());
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    double ms = 0;
+    HIPCHK(elapsed_ms(ev[0], ev[1], &ms));
     out[0] = mode != 1 ? ms : 0.0;
     for (int i = 0; i < n_side; ++i) {
         out[1 + i] = 0.0;
         if (mode >= 1) {
-            HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[2 + i]));
+            HIPCHK(elapsed_ms(ev[0], ev[2 + i], &ms));
             out[1 + i] = ms;
         }
     }
@@ -4124,13 +3999,12 @@ extern "C" int ck_debug_stream_overlap(ck_handle* h, int mode, int64_t rows, int
 
 extern "C" int ck_debug_mfma_probe(ck_handle* h, int32_t* out) {
     CHKH(h);
-    int32_t* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, 64 * 4 * 3 * sizeof(int32_t)));
+    DevBuf<int32_t> d;
+    HIPCHK(d.reserve(64 * 4 * 3));
     ck_launch_mfma_probe(h->stream, d);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d, 64 * 4 * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    (void)hipFree(d);
     return 0;
 }
 
@@ -4141,13 +4015,14 @@ extern "C" int ck_estimate_bytes(ck_handle* h, int64_t m, int64_t* out) {
     const int64_t n1 = h->n_procs == 2 ? h->n[1] : 0;
     const int64_t Np = roundup((n1 > 0 ? roundup(h->n[0], 64) : h->n[0]) + n1, CK_NB);
     const int nK = (int)(Np / CK_NB);
-    auto al = [](int64_t b) { return (b + 255) & ~(int64_t)255; };
-    int64_t tot = 2 * al(3 * Np * 8) + al(Np * 8);
-    for (int K = h->rank; K < nK; K += h->world) tot += al(((Np - (int64_t)K * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8 + CK_PANEL_SLACK_BYTES);
-    tot += 2 * al((int64_t)nK * sizeof(double*));   // d_sigptr, d_panelptr
-    if (h->world > 1) tot += (int64_t)h->recv_slots * al((Np * CK_NB + CK_PANEL_TAIL) * 8 + CK_PANEL_SLACK_BYTES);
+    // what dev_alloc is asked for by ensure_layout, build_panels and aux_begin_impl, each request rounded as it rounds
+    auto al = align256;
+    int64_t tot = 2 * al(site_bytes(Np)) + al(value_bytes(Np));
+    for (int K = h->rank; K < nK; K += h->world) tot += panel_bytes(Np, K);
+    tot += 2 * al(ptr_bytes(nK));
+    if (h->world > 1) tot += (int64_t)h->recv_slots * al(recv_bytes(Np));
     const int64_t mpad = roundup(m + 1, CK_AUX_ALIGN);
-    tot += al(mpad * Np * 8) + 2 * al(3 * mpad * 8) + 2 * al(2 * mpad * 8);
+    tot += al(rhs_bytes(mpad, Np)) + 2 * al(site_bytes(mpad)) + 2 * al(pair_bytes(mpad));
     *out = tot + 4096;
     return 0;
 }
@@ -4160,14 +4035,13 @@ extern "C" int ck_debug_cu_probe(ck_handle* h, const uint32_t* cu_mask8, int n_w
         HIPCHK(hipExtStreamCreateWithCUMask(&st, 8, cu_mask8));
     else
         HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    unsigned* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, (size_t)n_wg * 4));
+    DevBuf<unsigned> d;
+    HIPCHK(d.reserve((size_t)n_wg));
     HIPCHK(hipMemsetAsync(d, 0xff, (size_t)n_wg * 4, st));
     ck_launch_cu_probe(st, d, n_wg, 4);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, d, (size_t)n_wg * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    (void)hipFree(d);
     (void)hipStreamDestroy(st);
     return 0;
 }
@@ -4178,8 +4052,8 @@ extern "C" int ck_debug_mfma_peak(ck_handle* h, int waves_per_simd, int iters, d
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, h->device));
     const int cus = prop.multiProcessorCount;
-    double* sink = nullptr;
-    HIPCHK(hipMalloc((void**)&sink, 32));
+    DevBuf<double> sink;
+    HIPCHK(sink.reserve(4));
     const int threads = 256, blocks = cus * waves_per_simd;   // 4 waves per block = one per SIMD
     ck_launch_mfma_peak(h->stream, blocks, waves_per_simd, 10, sink);   // warm-up
     HIPCHK(hipEventRecord(h->ev0, h->stream));
@@ -4187,15 +4061,14 @@ extern "C" int ck_debug_mfma_peak(ck_handle* h, int waves_per_simd, int iters, d
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipEventSynchronize(h->ev1));
     HIPCHK(hipGetLastError());
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, h->ev0, h->ev1));
+    double ms = 0;
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms));
     const double flops = (double)blocks * (threads / 64) * (double)iters * nacc * 2048.0;
     double hs[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpy(hs, sink, 32, hipMemcpyDeviceToHost));
     out3[0] = flops / (ms * 1e-3) / 1e12;                           // TFLOP/s
     out3[1] = hs[2] > 0 ? hs[1] / hs[2] * 100.0 : 0.0;              // in-kernel shader clock, MHz
     out3[2] = hs[1] / ((double)iters * nacc);   // cycles per MFMA of one wave
-    (void)hipFree(sink);
     return 0;
 }
 
@@ -4246,16 +4119,14 @@ extern "C" int ck_set_option(ck_handle* h, const char* name, int64_t value) {
     CHKH(h);
     if (!name) return fail("null option name");
     if (!strcmp(name, "gemm_stamps")) {   // diagnostic, see ck_debug_gemm_clock; after the first assemble
-        if (h->d_stamps) {
-            (void)hipFree(h->d_stamps);
-            h->d_stamps = nullptr;
-            h->n_stamps = 0;
-        }
+        h->d_stamps.reset();
+        h->n_stamps = 0;
         if (value != 0) {
             if (!h->layout_ready) return fail("gemm_stamps: assemble first");
             HIPCHK(hipSetDevice(h->device));
-            h->n_stamps = (size_t)(h->Npad / 128) * (CK_NB / 128) * (size_t)(h->Npad / CK_NB);
-            HIPCHK(hipMalloc((void**)&h->d_stamps, 4 * h->n_stamps * sizeof(unsigned long long)));
+            const size_t n = (size_t)(h->Npad / 128) * (CK_NB / 128) * (size_t)(h->Npad / CK_NB);
+            HIPCHK(h->d_stamps.reserve(4 * n));
+            h->n_stamps = n;
             HIPCHK(hipMemset(h->d_stamps, 0, 4 * h->n_stamps * sizeof(unsigned long long)));
         }
         h->stamp_sel = (int)value;

@@ -364,3 +364,113 @@ def test_handles_of_other_sizes_after_a_large_one(native, data):
     info, v, g = h.loglik(True)
     assert info == 0 and all(abs(a - b) <= 1e-8 * abs(b) for a, b in zip(v, ref))
     h.close()
+
+
+def growing_steps(ds):
+    rng = np.random.default_rng(66)
+    sites = {m: dc.pred_sites(rng, ds.metric, m) for m in (5, 300, 700)}
+    lab2, lab300 = dc.block_labels(rng, 2, 300), dc.block_labels(rng, 300, 300)
+    w300 = rng.uniform(0.2, 2.0, 300)
+    noise = [rng.uniform(0.01, 0.05, len(c)) for c in ds.coords]
+    lags10, lags5000 = rng.uniform(0.0, 2000.0, 10), rng.uniform(0.0, 2000.0, 5000)
+    v300 = (dc.pred_sites(rng, ds.metric, 300), rng.standard_normal(300))
+    vi, vj = ((dc.pred_sites(rng, ds.metric, n), rng.standard_normal(n)) for n in (3000, 2500))
+    folds = rng.integers(0, 10, len(ds.coords[0]))
+    d129, _ = dc.draw_sites(ds, 0, 129, 20, 61)
+    eps = rng.standard_normal((3, 129))
+    from sif_xco2_cokriging_amd.variogram import variogram_arrays
+
+    def predict(m):
+        return lambda h: (h.predict(0, sites[m]), h.verify_model())
+
+    def universal(kind):
+        def step(h):
+            for k in range(2):
+                h.set_trend(k, dc.design(kind, ds.coords[k], ds.coords[k]) if kind else None)
+            return h.predict_universal(1, sites[300], dc.design(kind, ds.coords[1], sites[300]) if kind else None)
+        return step
+
+    def noisy(on):
+        def step(h):
+            for k in range(2):
+                h.set_noise(k, noise[k] if on else None)
+            h.assemble_joint()
+            return h.factor(), h.predict(1, sites[300])
+        return step
+
+    def vario(a, b=None):
+        same = b is None
+        return lambda h: variogram_arrays(h, a[0], a[1], None if same else b[0], None if same else b[1], same, 1500.0, 20)
+
+    def local(m, max_dist, reserve=0):
+        def step(h):
+            if reserve:
+                h.local_reserve(reserve)
+            pred, e, info = h.predict_local(0, sites[m], max_dist=max_dist)
+            return pred.view(np.uint64), e.view(np.uint64), sorted(info.items())   # the bits: sites without a neighbour give NaN
+        return step
+
+    return [("predict m=5", predict(5)), ("predict m=300", predict(300)), ("predict m=700", predict(700)),
+            ("predict m=5 again", predict(5)),
+            ("predict_blocks r=2", lambda h: h.predict_blocks(1, sites[300], lab2, w300, 2, want_cov=True)),
+            ("predict_blocks r=300", lambda h: h.predict_blocks(1, sites[300], lab300, w300, 300, want_cov=True)),
+            ("trend constant", universal("constant")), ("trend linear", universal("linear")), ("trend cleared", universal(None)),
+            ("noise on", noisy(True)), ("noise cleared", noisy(False)),
+            ("model_variogram 10", lambda h: h.model_variogram(0, 1, lags10)),
+            ("model_variogram 5000", lambda h: h.model_variogram(0, 1, lags5000)),
+            ("variogram 300", vario(v300)), ("variogram 3000 x 2500", vario(vi, vj)), ("variogram 300 again", vario(v300)),
+            # five sites at 2000 km: neighbourhoods of most of the data (the tiled path) in a slab of tens of MB -- from 1 GiB on
+            # the slab takes its whole budget, a quarter of the card's free memory, which is also what local_reserve(0) does
+            ("predict_local 150 km", local(300, 150.0)), ("predict_local 2000 km", local(5, 2000.0)),
+            ("local_reserve", local(5, 2000.0, reserve=64 << 20)),
+            ("cv_folds", lambda h: h.cv_folds(0, folds, want_stats=True)),
+            ("conditional_draws", lambda h: h.conditional_draws(0, d129, 3, noise=eps))], sites, v300
+
+
+def test_growing_sequence_and_handle_life_cycle(native):
+    """as test_sequence_on_one_handle, with every buffer of the handle growing on the way: right-hand sides over two mpad
+    steps (Schur panels 512 -> 1024 -> 512), block rows, trend, noise, variogram rows and lists, the local slab -- each call
+    gives the bits of the same call on a fresh handle.  Then handles closed at every stage of their life, and an arena"""
+    import torch
+    ds = dc.data_set(dc.REFIT)
+    steps, sites, v300 = growing_steps(ds)
+    h = handle(native, ds)
+    for name, step in steps:
+        got = step(h)
+        f = handle(native, ds)
+        want = step(f)
+        f.close()
+        assert same(got, want), name
+    # ---- closing a handle at every stage
+    for _ in range(20):
+        native.Handle(0).close()
+    f = native.Handle(0)
+    p = ds.p
+    f.set_model(2, p.sigma, [p.nu[0, 0], p.nu[0, 1], p.nu[1, 1]], [p.len_scale[0, 0], p.len_scale[0, 1], p.len_scale[1, 1]],
+                p.nugget, p.rho)
+    for k in range(2):
+        f.set_data(k, ds.coords[k], ds.values[k])
+    f.close()
+    f = native.Handle(0)
+    f.vario_begin(*v300)   # no vario_end
+    f.close()
+    f = handle(native, ds)
+    f.set_option("gemm_stamps", 1)
+    f.close()
+    # ---- an arena of estimate_bytes(700): the largest m first.  The arena never takes a carve back, so under it only
+    # non-growing orders fit the estimate (m = 5 first and 700 after it would need both right-hand-side buffers)
+    want = [h.predict(0, sites[m]) for m in (700, 5, 700)]
+    h.close()
+    a = native.Handle(0)
+    a.set_model(2, p.sigma, [p.nu[0, 0], p.nu[0, 1], p.nu[1, 1]], [p.len_scale[0, 0], p.len_scale[0, 1], p.len_scale[1, 1]],
+                p.nugget, p.rho)
+    a.set_metric(ds.metric)
+    for k in range(2):
+        a.set_data(k, ds.coords[k], ds.values[k])
+    nbytes = a.estimate_bytes(700)
+    arena = torch.empty(nbytes, dtype=torch.uint8, device="cuda:0")
+    a.set_arena(arena.data_ptr(), nbytes, keepalive=arena)
+    a.assemble_joint()
+    assert a.factor() == 0
+    assert same([a.predict(0, sites[m]) for m in (700, 5, 700)], want)
+    a.close()
