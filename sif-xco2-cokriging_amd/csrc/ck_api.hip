@@ -70,6 +70,31 @@ struct EvPair {
     hipEvent_t a, b;
 };
 
+// What the last call left in the right-hand sides (ck_handle::aux_state).  Only AUX_PREDICT feeds ck_verify_model; the states
+// with a name in aux_state_text are refused by ck_aux_finish and ck_verify_model until the next ck_predict / ck_aux_begin.
+enum AuxState {
+    AUX_NONE,        // nothing usable
+    AUX_ASSEMBLED,   // right-hand sides assembled (ck_aux_begin), not solved
+    AUX_PREDICT,     // solved by ck_predict: rows = V^T, row m = y
+    AUX_BLOCKS,      // block sums (or a chunk's unsolved point rows after a failure): the sites are gone
+    AUX_LOGLIK,      // y, the trend rows (REML) and the unit rows of every internal position
+    AUX_UNIVERSAL,   // ck_predict's rows with the trend rows behind the data row
+    AUX_FOLDS,       // y and the unit rows of the withheld positions
+    AUX_N_STATES
+};
+// per state: the entry point that left it (null: none to name) and the clause ck_verify_model adds to the name
+static const struct {
+    const char *call, *clause;
+} aux_state_text[AUX_N_STATES] = {
+    {nullptr, nullptr},
+    {nullptr, nullptr},
+    {nullptr, nullptr},
+    {"ck_predict_blocks", "whose right-hand sides are block sums"},
+    {"ck_loglik", "whose right-hand sides are the data sites' unit rows"},
+    {"ck_predict_universal", "for which the simple-kriging verdict does not apply"},
+    {"ck_cv_folds", "whose right-hand sides are the withheld data's unit rows"},
+};
+
 struct ck_handle {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -143,9 +168,7 @@ struct ck_handle {
     int64_t p_cap = 0;        // the mpad that p0, pu, d_pcoords and d_pred hold
     DevBuf<char[24]> mv_buf;   // ck_model_variogram's device arrays (lag | out | i | j, 24 bytes per row), kept between the cost
                                // evaluations of a fit
-    int aux_state = 0;   // 0: nothing usable | 1: right-hand sides assembled | 2: solved by ck_predict (rows = V^T, row m = y)
-                         // | 3: the last call was ck_predict_blocks (its rows are block sums: the sites are gone)
-                         // | 4: the last call was ck_loglik (its rows are y and the unit rows of the data sites)
+    AuxState aux_state = AUX_NONE;
     double par_sigma[2] = {0.0, 0.0}, par_rho = 0.0;   // ck_set_model's sigma and rho12 (ck_loglik's derivatives in them)
     DevBuf<CkMatern> d_lik_blk;                         // ck_loglik: 3 blocks x (the block, nu - 2 d, nu - d, nu + d, nu + 2 d)
     // ck_predict_blocks: the block rows (the aux panel layout with bmpad = roundup(r + 1, CK_AUX_ALIGN) rows per panel), kept
@@ -280,6 +303,22 @@ struct ck_handle {
             for (hipEvent_t e : *v) (void)hipEventDestroy(e);
         for (hipStream_t st : {side, side_lo, own_stream})
             if (st) (void)hipStreamDestroy(st);
+    }
+};
+// An entry point that leaves other rows than ck_predict's in the right-hand sides: on every return the layout fields are idle
+// again and aux_state names the call.  on_entry: the state also holds while the call runs (it goes through aux_begin_impl more
+// than once, or may fail in front of it)
+struct CallGuard {
+    ck_handle* h;
+    AuxState exit_state;
+    CallGuard(ck_handle* hh, AuxState st, bool on_entry) : h(hh), exit_state(st) {
+        if (on_entry) h->aux_state = st;
+    }
+    ~CallGuard() {
+        h->aux_trend = 0;
+        h->loo_g0 = -1;
+        h->loo_dense = 1;
+        h->aux_state = exit_state;
     }
 };
 static int64_t aux_cap(const ck_handle* h) { return (int64_t)h->aux_own.cap(); }               // doubles
@@ -417,7 +456,7 @@ extern "C" int ck_set_model(ck_handle* h, int n_procs, const double* sigma, cons
     HIPCHK(hipStreamSynchronize(h->stream));
     h->model_set = true;
     h->assembled = h->factored = false;
-    h->aux_state = 0;   // solved right-hand sides of the old model must not feed ck_verify_model
+    h->aux_state = AUX_NONE;   // solved right-hand sides of the old model must not feed ck_verify_model
     return 0;
 }
 
@@ -428,7 +467,7 @@ extern "C" int ck_set_metric(ck_handle* h, int metric) {
         h->metric = metric;
         h->layout_ready = false;   // site transforms depend on the metric
         h->assembled = h->factored = false;
-        h->aux_state = 0;
+        h->aux_state = AUX_NONE;
     }
     return 0;
 }
@@ -516,7 +555,7 @@ extern "C" int ck_set_noise(ck_handle* h, int k, const double* var, int64_t n_k,
     }
     h->noise_dirty = true;
     h->assembled = h->factored = false;   // as ck_set_model: Sigma, its factor and the solved right-hand sides are stale
-    h->aux_state = 0;
+    h->aux_state = AUX_NONE;
     h->lik_noise_valid = false;
     return 0;
 }
@@ -865,6 +904,30 @@ static void next_worklist(ck_handle* h) {
     h->wl.count = cur;
 }
 
+// One assembly, by the tables where they are usable: assemble(fast) launches the assembly kernel; on the table path fix()
+// launches the exact pass over the worklist, `fixed` (may be null) is recorded behind it -- the count check that follows is
+// host latency -- and a list that overflowed sends the assembly through the exact kernels once more.  Returns 1 where the
+// table path finished, 0 where the exact kernels assembled, -1 on an error.
+template <class Assemble, class Fix>
+static int table_or_exact(ck_handle* h, Assemble assemble, Fix fix, hipEvent_t fixed = nullptr) {
+    int table_done = 0;
+    for (int attempt = 0; attempt < 2 && !table_done; ++attempt) {
+        const bool fast = tables_usable(h) && attempt == 0;
+        if (fast) next_worklist(h);   // a zeroed counter, without a memset launch in front of the assembly
+        assemble(fast);
+        if (!fast) break;
+        fix();
+        if (fixed) HIPCHK(hipEventRecord(fixed, h->stream));
+        unsigned cnt = 0;
+        HIPCHK(hipMemcpyAsync(&cnt, h->wl.count, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->fallback_total += cnt;
+        table_done = cnt <= h->wl.cap;   // else: too many out-of-table pairs for the list -> exact kernels
+    }
+    HIPCHK(hipGetLastError());
+    return table_done;
+}
+
 // internal (padded-order) 1-based index -> index in the caller's stacked order
 static int64_t external_index(const ck_handle* h, int64_t g) { return g > h->n0p ? g - (h->n0p - h->n[0]) : g; }
 
@@ -904,41 +967,26 @@ extern "C" int ck_assemble_joint(ck_handle* h) {
     h->lik_noise_valid = false;
 
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    bool fast_done = false;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        const bool fast = tables_usable(h) && attempt == 0;
-        if (fast) next_worklist(h);   // a zeroed counter, without a memset launch in front of the assembly
-        {
-            CkPanelMap pm{h->d_tile0, h->d_panel_of, h->d_sigptr, h->n_owned, nullptr, 0, h->d_strip_order};
-            ck_launch_assemble_sigma(h->stream, fast, h->d_blk, h->d_tabs, h->d_coefptr, h->metric, h->s0, h->su,
-                                     layout_of(h), pm, h->total_tiles, h->wl, fast ? h->assemble_queue : 0);
-        }
-        if (!fast) {
-            ck_launch_assemble_noise(h->stream, h->d_sigptr, noise_sd(h), layout_of(h));
-            break;
-        }
-        ck_launch_assemble_fix(h->stream, false, h->d_blk, h->metric, 0, nullptr, 0, h->s0, layout_of(h), h->wl,
-                               h->d_sigptr, nullptr);
-        // measurement-error variances on the diagonal, once per assembled Sigma (a second attempt writes every entry anew)
+    // measurement-error variances on the diagonal, once per assembled Sigma (a second attempt writes every entry anew)
+    auto assemble = [&](bool fast) {
+        CkPanelMap pm{h->d_tile0, h->d_panel_of, h->d_sigptr, h->n_owned, nullptr, 0, h->d_strip_order};
+        ck_launch_assemble_sigma(h->stream, fast, h->d_blk, h->d_tabs, h->d_coefptr, h->metric, h->s0, h->su, layout_of(h), pm,
+                                 h->total_tiles, h->wl, fast ? h->assemble_queue : 0);
+        if (!fast) ck_launch_assemble_noise(h->stream, h->d_sigptr, noise_sd(h), layout_of(h));
+    };
+    auto fix = [&] {
+        ck_launch_assemble_fix(h->stream, false, h->d_blk, h->metric, 0, nullptr, 0, h->s0, layout_of(h), h->wl, h->d_sigptr, nullptr);
         ck_launch_assemble_noise(h->stream, h->d_sigptr, noise_sd(h), layout_of(h));
-        HIPCHK(hipEventRecord(h->ev1, h->stream));   // table kernel + exact pass; the count check below is host latency
-        unsigned cnt = 0;
-        HIPCHK(hipMemcpyAsync(&cnt, h->wl.count, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->fallback_total += cnt;
-        if (cnt <= h->wl.cap) {
-            fast_done = true;
-            break;
-        }   // else: too many out-of-table pairs for the list -> exact kernels
-    }
-    HIPCHK(hipGetLastError());
+    };
+    const int fast_done = table_or_exact(h, assemble, fix, h->ev1);   // ev1: table kernel + exact pass
+    if (fast_done < 0) return -1;
     HIPCHK(hipMemsetAsync(h->d_info, 0, sizeof(long long), h->stream));
     if (!fast_done) HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(elapsed_ms(h->ev0, h->ev1, &h->t_ms[0]));
     h->assembled = true;
     h->factored = false;
-    h->aux_state = 0;   // right-hand sides solved with the previous factor are stale from here on
+    h->aux_state = AUX_NONE;   // right-hand sides solved with the previous factor are stale from here on
     return 0;
 }
 
@@ -1649,7 +1697,7 @@ extern "C" int ck_factor_predict(ck_handle* h, int i, const double* pcoords, int
         if (werr != 0 && coop_switch_off(h)) return -1;
         h->gemm_ev_used = 0;
         h->assembled = false;
-        h->aux_state = 0;
+        h->aux_state = AUX_NONE;
         if (ck_assemble_joint(h)) return -1;
         if (ck_factor(h, info)) return -1;
         if (werr != 0) h->t_ms[12] = 1.0;   // visible in ck_timings: the factorisation was redone
@@ -1669,7 +1717,7 @@ extern "C" int ck_factor_predict(ck_handle* h, int i, const double* pcoords, int
     if (tall) gemm_timed_collect(h, 5, h->ev0);   // the tall sweep's update launches: sum of their durations and union of their intervals
     else h->gemm_ev_used = 0;
     if (ck_aux_finish(h, pred, pred_err)) return -1;
-    h->aux_state = 2;
+    h->aux_state = AUX_PREDICT;
     return 0;
 }
 
@@ -1678,7 +1726,7 @@ extern "C" int ck_factor(ck_handle* h, int64_t* info) {
     if (h->world != 1) return fail("ck_factor is the single-process form; drive ck_panel_* for world > 1");
     if (!h->assembled) return fail("ck_assemble_joint has not been called");
     if (h->factored) return fail("Sigma is already factored; call ck_assemble_joint again");
-    h->aux_state = 0;
+    h->aux_state = AUX_NONE;
     h->t_ms[12] = 0.0;
     if (factor_sweep(h)) return -1;
     {
@@ -1791,7 +1839,7 @@ static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m,
     h->i_pred = i;
     h->m = m;
     h->mpad = mpad;
-    h->aux_state = pcoords ? 1 : 0;
+    h->aux_state = pcoords ? AUX_ASSEMBLED : AUX_NONE;
     // large sets of prediction points are laid out along the Hilbert curve like the data sites
     // (site_order above); ck_aux_finish hands the results back in the caller's order
     std::vector<double> sorted;
@@ -1799,7 +1847,6 @@ static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m,
         h->p_sorted = false;
         return 0;
     }
-    bool fast_done = false;
     h->p_sorted = may_sort && h->site_order && m >= 256;
     if (h->p_sorted) {
         double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
@@ -1823,26 +1870,16 @@ static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m,
     // the stage.  The exact path (no tables) keeps the separate transform.
     const bool fold = tables_usable(h);
     if (!fold) ck_launch_prep_sites(h->stream, h->d_pcoords, mpad, h->metric, h->p0, h->p1, h->p2, h->pu);
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        const bool fast = tables_usable(h) && attempt == 0;
-        if (fast) next_worklist(h);
-        ck_launch_assemble_aux(h->stream, fast, h->d_blk, h->d_tabs, h->d_coefptr, h->metric, i, h->p0, h->pu, m,
-                               mpad, h->s0, h->su, h->z, layout_of(h), h->nK, h->aux, h->wl, fast && fold ? h->d_pcoords : nullptr,
+    auto assemble = [&](bool fast) {
+        ck_launch_assemble_aux(h->stream, fast, h->d_blk, h->d_tabs, h->d_coefptr, h->metric, i, h->p0, h->pu, m, mpad, h->s0, h->su,
+                               h->z, layout_of(h), h->nK, h->aux, h->wl, fast && fold ? h->d_pcoords : nullptr,
                                fast ? h->assemble_queue : 0);
-        if (!fast) break;
-        ck_launch_assemble_fix(h->stream, true, h->d_blk, h->metric, i, h->p0, mpad, h->s0, layout_of(h), h->wl,
-                               h->d_sigptr, h->aux);
-        HIPCHK(hipEventRecord(h->ev1, h->stream));
-        unsigned cnt = 0;
-        HIPCHK(hipMemcpyAsync(&cnt, h->wl.count, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->fallback_total += cnt;
-        if (cnt <= h->wl.cap) {
-            fast_done = true;
-            break;
-        }
-    }
-    HIPCHK(hipGetLastError());
+    };
+    auto fix = [&] {
+        ck_launch_assemble_fix(h->stream, true, h->d_blk, h->metric, i, h->p0, mpad, h->s0, layout_of(h), h->wl, h->d_sigptr, h->aux);
+    };
+    const int fast_done = table_or_exact(h, assemble, fix, h->ev1);
+    if (fast_done < 0) return -1;
     if (!fast_done) HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipEventSynchronize(h->ev1));   // pcoords is caller memory: do not return before the copy is done
     HIPCHK(elapsed_ms(h->ev0, h->ev1, &h->t_ms[2]));
@@ -1859,10 +1896,8 @@ extern "C" int ck_aux_begin(ck_handle* h, int i, const double* pcoords, int64_t 
 extern "C" int ck_aux_finish(ck_handle* h, double* pred, double* pred_err) {
     CHKH(h);
     if (h->mpad <= 0) return fail("ck_aux_begin has not been called");
-    if (h->aux_state == 3) return fail("ck_aux_finish: the last call was ck_predict_blocks; call ck_aux_begin first");
-    if (h->aux_state == 4) return fail("ck_aux_finish: the last call was ck_loglik; call ck_aux_begin first");
-    if (h->aux_state == 5) return fail("ck_aux_finish: the last call was ck_predict_universal; call ck_aux_begin first");
-    if (h->aux_state == 6) return fail("ck_aux_finish: the last call was ck_cv_folds; call ck_aux_begin first");
+    if (const char* call = aux_state_text[h->aux_state].call)
+        return fail(std::string("ck_aux_finish: the last call was ") + call + "; call ck_aux_begin first");
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     const double c0 = h->blk[2 * h->i_pred].amp + h->blk[2 * h->i_pred].nugget;   // sigma_i^2 + nugget_i (model.py:194-196 at h = 0)
     ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, h->m, h->m, c0, h->d_pred, h->d_err);
@@ -1900,7 +1935,7 @@ extern "C" int ck_predict(ck_handle* h, int i, const double* pcoords, int64_t m,
     if (ck_aux_finish(h, pred, pred_err)) return -1;
     HIPCHK(elapsed_ms(h->ev2, h->ev3, &h->t_ms[3]));
     gemm_timed_collect(h, 7);
-    h->aux_state = 2;
+    h->aux_state = AUX_PREDICT;
     return 0;
 }
 
@@ -1912,15 +1947,6 @@ extern "C" int ck_predict(ck_handle* h, int i, const double* pcoords, int64_t m,
 // k_reduce_univ dots every solved row with [y; U]: |V_s|^2, V_s . y, U^T V_s for the sites and, over the trend rows themselves,
 // A = U^T U and b = U^T y.  The p x p GLS step runs on the host (ck_host_gls), and so does the O(m p^2) epilogue
 // pred_s = V_s . y + r_s^T beta, pred_err_s^2 = c0 - |V_s|^2 + r_s^T A^-1 r_s, r_s = x0_s - U^T V_s.
-struct UnivCallGuard {
-    ck_handle* h;
-    explicit UnivCallGuard(ck_handle* hh) : h(hh) {}
-    ~UnivCallGuard() {
-        h->aux_trend = 0;
-        h->aux_state = 5;
-    }
-};
-
 extern "C" int ck_predict_universal(ck_handle* h, int i, const double* pcoords, int64_t m, const double* f0, double* pred,
                                     double* pred_err, double* beta, double* beta_cov) {
     CHKH(h);
@@ -1941,7 +1967,7 @@ extern "C" int ck_predict_universal(ck_handle* h, int i, const double* pcoords, 
     const auto t_begin = std::chrono::steady_clock::now();
     for (int k = 40; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
     if (ensure_trend(h)) return -1;
-    UnivCallGuard guard(h);
+    CallGuard guard(h, AUX_UNIVERSAL, false);
     h->aux_trend = p;
     static const double no_site[2] = {0.0, 0.0};
     if (aux_begin_impl(h, i, m > 0 ? pcoords : no_site, m, true)) return -1;
@@ -2127,22 +2153,15 @@ static int schur_build(ck_handle* h, double* ms_cpp = nullptr, double* ms_vtv = 
     ck_launch_prep_sites(h->stream, h->sch.pc, Mp, h->metric, h->sch.c, h->sch.c + Mp, h->sch.c + 2 * Mp, h->sch.u);
     HIPCHK(hipStreamSynchronize(h->stream));   // hb / ht / hc are stack memory
     const CkLayout L{m, Mp, Mp, Mp};
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        const bool fast = tables_usable(h) && attempt == 0;
-        if (fast) next_worklist(h);
+    auto assemble = [&](bool fast) {
         CkPanelMap pm{h->sch.d_tile0, h->sch.d_panel_of, h->sch.d_ptr, nJ, nullptr, 0, nullptr};
-        ck_launch_assemble_sigma(h->stream, fast, h->sch.d_blk, h->sch.d_tabs, h->sch.d_coefptr, h->metric, h->sch.c,
-                                 h->sch.u, L, pm, h->sch.tiles, h->wl, fast ? h->assemble_queue : 0);
-        if (!fast) break;
-        ck_launch_assemble_fix(h->stream, false, h->sch.d_blk, h->metric, 0, nullptr, 0, h->sch.c, L, h->wl, h->sch.d_ptr,
-                               nullptr);
-        unsigned cnt = 0;
-        HIPCHK(hipMemcpyAsync(&cnt, h->wl.count, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->fallback_total += cnt;
-        if (cnt <= h->wl.cap) break;
-    }
-    HIPCHK(hipGetLastError());
+        ck_launch_assemble_sigma(h->stream, fast, h->sch.d_blk, h->sch.d_tabs, h->sch.d_coefptr, h->metric, h->sch.c, h->sch.u, L, pm,
+                                 h->sch.tiles, h->wl, fast ? h->assemble_queue : 0);
+    };
+    auto fix = [&] {
+        ck_launch_assemble_fix(h->stream, false, h->sch.d_blk, h->metric, 0, nullptr, 0, h->sch.c, L, h->wl, h->sch.d_ptr, nullptr);
+    };
+    if (table_or_exact(h, assemble, fix) < 0) return -1;
     if (timed) HIPCHK(hipEventRecord(h->ev1, h->stream));
     // row m of the right-hand sides is y = L^-1 z, not a prediction site (ck_aux_finish has consumed it)
     HIPCHK(hipMemset2DAsync(h->aux + m * CK_NB, (size_t)mpad * CK_NB * 8, 0, (size_t)CK_NB * 8, (size_t)h->nK, h->stream));
@@ -2185,19 +2204,10 @@ extern "C" int ck_verify_model(ck_handle* h, int64_t* info) {
     CHKH(h);
     if (!info) return fail("null info");
     if (h->world != 1) return fail("ck_verify_model is the single-process form");
-    if (h->aux_state == 3)
-        return fail("ck_verify_model: the last call was ck_predict_blocks, whose right-hand sides are block sums; call ck_predict "
-                    "with the sites to check first");
-    if (h->aux_state == 4)
-        return fail("ck_verify_model: the last call was ck_loglik, whose right-hand sides are the data sites' unit rows; call "
-                    "ck_predict with the sites to check first");
-    if (h->aux_state == 5)
-        return fail("ck_verify_model: the last call was ck_predict_universal, for which the simple-kriging verdict does not apply; "
-                    "call ck_predict with the sites to check first");
-    if (h->aux_state == 6)
-        return fail("ck_verify_model: the last call was ck_cv_folds, whose right-hand sides are the withheld data's unit rows; call "
-                    "ck_predict with the sites to check first");
-    if (h->aux_state != 2) return fail("ck_verify_model needs the solved right-hand sides of a preceding ck_predict");
+    if (const char* call = aux_state_text[h->aux_state].call)
+        return fail(std::string("ck_verify_model: the last call was ") + call + ", " + aux_state_text[h->aux_state].clause +
+                    "; call ck_predict with the sites to check first");
+    if (h->aux_state != AUX_PREDICT) return fail("ck_verify_model needs the solved right-hand sides of a preceding ck_predict");
     const int64_t m = h->m;
     *info = 0;
     if (m <= 0) return 0;
@@ -2241,22 +2251,6 @@ struct AuxSwap {
     }
 };
 
-// every return of ck_predict_blocks once it has started: slots 0 .. 15 of ck_timings describe the last point-path calls and
-// are left as they were; the right-hand sides are block rows (or a chunk's unsolved point rows after a failure) -- state 3,
-// which ck_verify_model and ck_aux_finish refuse
-struct BlockCallGuard {
-    ck_handle* h;
-    double kept[16];
-    explicit BlockCallGuard(ck_handle* hh) : h(hh) {
-        memcpy(kept, h->t_ms, sizeof(kept));
-        h->aux_state = 3;
-    }
-    ~BlockCallGuard() {
-        memcpy(h->t_ms, kept, sizeof(kept));
-        h->aux_state = 3;
-    }
-};
-
 // piece offsets of the prior's elements (ck_blocks.hip): poff[e] .. poff[e + 1] = the pieces of CK_PRIOR_PIECE pairs of
 // element e (full == 0: e = b, n_b^2 pairs; full != 0: e = R (R + 1) / 2 + C, n_R n_C pairs); returns the number of pieces
 static int64_t prior_pieces(const std::vector<int>& off, int32_t r, int full, std::vector<long long>& poff) {
@@ -2274,9 +2268,8 @@ static int64_t prior_pieces(const std::vector<int>& off, int32_t r, int full, st
     return poff.back();
 }
 
-extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int64_t m, const int32_t* block,
-                                 const double* weight, int32_t r, double* pred, double* pred_err, double* cov) {
-    CHKH(h);
+static int predict_blocks_impl(ck_handle* h, int i, const double* pcoords, int64_t m, const int32_t* block, const double* weight,
+                               int32_t r, double* pred, double* pred_err, double* cov) {
     if (h->world != 1) return fail("ck_predict_blocks is the single-process form");
     if (!h->factored) return fail("ck_factor has not been called");
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
@@ -2298,7 +2291,8 @@ extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int
         off[(size_t)b + 1] += off[(size_t)b];
     }
     const auto t_begin = std::chrono::steady_clock::now();
-    BlockCallGuard guard(h);
+    // from here on the right-hand sides are block rows (or a chunk's unsolved point rows after a failure)
+    CallGuard guard(h, AUX_BLOCKS, true);
     for (int k = 16; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
     DevTemps tmp;
     // ---- prior of the blocks (diagonal): members in block order, exact-formula coordinates
@@ -2368,7 +2362,7 @@ extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int
     for (int64_t a0 = 0; a0 < m; a0 += chunk, ++n_chunks) {
         const int64_t mc_ = std::min<int64_t>(chunk, m - a0);
         if (aux_begin_impl(h, i, pcoords + 2 * a0, mc_, true)) return -1;   // K2 on this chunk's sites (synchronised)
-        h->aux_state = 3;
+        h->aux_state = AUX_BLOCKS;
         h->t_ms[16] += h->t_ms[2];
         // this chunk's member lists, rows in the library's internal order (Hilbert order when p_sorted)
         for (int64_t j = 0; j < mc_; ++j) inv[(size_t)(h->p_sorted ? h->pperm[(size_t)j] : j)] = (int)j;
@@ -2460,6 +2454,17 @@ extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int
     }
     h->t_ms[21] = ms_since(t_begin);
     return 0;
+}
+
+// slots 0 .. 15 of ck_timings describe the last point-path calls: every return leaves them as they were
+extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int64_t m, const int32_t* block,
+                                 const double* weight, int32_t r, double* pred, double* pred_err, double* cov) {
+    CHKH(h);
+    double kept[16];
+    memcpy(kept, h->t_ms, sizeof(kept));
+    const int rc = predict_blocks_impl(h, i, pcoords, m, block, weight, r, pred, pred_err, cov);
+    memcpy(h->t_ms, kept, sizeof(kept));
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2654,6 +2659,52 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
 }
 
 // ---------------------------------------------------------------------------------------
+// batched Cholesky of tiled systems (ck_predict_local's tiled class, ck_cv_folds' big folds)
+// ---------------------------------------------------------------------------------------
+// The columns [0, cols) of n systems (sys / slab on the device; kq: their padded sizes on the host, largest first, kq_max =
+// kq[0]) in groups of G 64-column blocks.  left: the group first receives everything from its left in one pass (K = g0) --
+// every tile of a system is read and written once instead of once per earlier group with K = 64 G; else the trailing matrix
+// is updated behind every group.  Finished systems drop off the end of the active prefix.
+static void factor_tiled_batch(hipStream_t st, const CkLocalSys* sys, double* slab, int n, const int* kq, int cols, int kq_max,
+                               int G, bool left, long long* info) {
+    int na = n;
+    for (int g0 = 0; g0 < cols; g0 += 64 * G) {
+        if (left && g0 > 0) ck_launch_local_tiled_left(st, sys, slab, na, g0, 64 * G, kq);
+        // the group's diagonal region block by block (diagonal block, then the few chunks of rows inside the region) ...
+        for (int b = 0; b < G && g0 + 64 * b < kq_max; ++b) {
+            while (na > 0 && kq[na - 1] <= g0 + 64 * b) --na;
+            ck_launch_local_tiled_block(st, sys, slab, na, g0, b, kq, info, G);
+        }
+        // ... then every row below it through all of the group's blocks in one launch
+        while (na > 0 && kq[na - 1] <= g0 + 64 * G) --na;
+        ck_launch_local_tiled_rows_all(st, sys, slab, na, g0, G, kq);
+        if (!left) ck_launch_local_tiled_trailing(st, sys, slab, na, g0, 64 * G, kq);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// unit rows as right-hand sides (ck_loocv, ck_cv_folds, ck_loglik / ck_loglik_reml)
+// ---------------------------------------------------------------------------------------
+// Behind aux_begin_impl(.., nullptr, ..): the right-hand sides become row 0 = z, rows 1 .. dense - 1 = the trend rows X^T (REML),
+// row dense + p = the unit vector of internal position g0 + p (p < m), and are swept through the factor on the growing prefix
+// of live rows (aux_rows: loo_g0 / loo_dense, idle again on every return).  before_sweep (may be null) is recorded between the
+// row fill and the sweep.
+static int unit_row_sweep(ck_handle* h, int64_t m, int64_t g0, int dense, hipEvent_t before_sweep = nullptr) {
+    HIPCHK(hipMemsetAsync(h->aux, 0, (size_t)h->mpad * h->Npad * 8, h->stream));
+    h->loo_g0 = g0;
+    h->loo_dense = dense;
+    ck_launch_loo_rows(h->stream, h->aux, h->mpad, m, g0, h->z, h->Npad, dense);
+    const int rc = [&]() -> int {
+        if (dense > 1 && put_trend_rows(h, 1)) return -1;
+        if (before_sweep) HIPCHK(hipEventRecord(before_sweep, h->stream));
+        return solve_sweep(h);
+    }();
+    h->loo_g0 = -1;
+    h->loo_dense = 1;
+    return rc;
+}
+
+// ---------------------------------------------------------------------------------------
 // leave-one-out cross-validation from ONE factorisation
 // ---------------------------------------------------------------------------------------
 // The reference re-assembles and re-factorises everything once per withheld datum
@@ -2674,13 +2725,7 @@ extern "C" int ck_loocv(ck_handle* h, int i, double* pred, double* pred_err) {
     // reuse the aux machinery: storage as for m prediction points; m + 1 rows:
     // row 0 = z, row 1 + q = unit vector of datum q
     if (aux_begin_impl(h, i, nullptr, m, false)) return -1;
-    HIPCHK(hipMemsetAsync(h->aux, 0, (size_t)h->mpad * h->Npad * 8, h->stream));
-    h->loo_g0 = i == 0 ? 0 : h->n0p;
-    ck_launch_loo_rows(h->stream, h->aux, h->mpad, m, h->loo_g0, h->z, h->Npad);
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    const int rc = solve_sweep(h);
-    h->loo_g0 = -1;
-    if (rc) return -1;
+    if (unit_row_sweep(h, m, i == 0 ? 0 : h->n0p, 1, h->ev0)) return -1;
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, m + 1, 0, -1.0, h->d_pred, h->d_err);
     HIPCHK(hipGetLastError());
@@ -2712,7 +2757,6 @@ extern "C" int ck_loocv(ck_handle* h, int i, double* pred, double* pred_err) {
 //   3. the fold solves: k_fold_small in LDS for folds of up to 64 members; larger folds as systems of the local predictor's
 //      batched Cholesky steps, left-looking, stopped behind the largest fold's last column (ck_folds.hip).
 static_assert(CK_FOLD_MAX == CK_HOST_FOLD_MAX, "include/cokrige.h and ck_host.h disagree about the largest fold");
-static_assert(CK_LT_NINV * 64 * 64 == 8 * 64 * 64 && CK_LT_ROWS(64) == 64 + 128, "ck_host_fold_plan sizes the big folds' systems");
 extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int32_t* fold1, int32_t n_folds, double* pred,
                            double* pred_err, double* fold_stats, int64_t* info) {
     CHKH(h);
@@ -2774,25 +2818,14 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
     *info = 0;
     for (int64_t a = 0; a < ni; ++a) pred[a] = pred_err[a] = NAN;
     for (int k = 56; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
-    struct Guard {
-        ck_handle* h;
-        ~Guard() {
-            h->aux_state = 6;
-            h->loo_g0 = -1;
-        }
-    } guard{h};
+    CallGuard guard(h, AUX_FOLDS, false);
     // ---- 1. rows and sweep
     if (aux_begin_impl(h, i, nullptr, m, false)) return -1;
-    h->aux_state = 6;
+    h->aux_state = AUX_FOLDS;
     // outside the timed stages: only the first call of a layout allocates
     if (slab_doubles > local_slab_doubles(h)) HIPCHK(h->local_slab.reserve((size_t)slab_doubles));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    HIPCHK(hipMemsetAsync(h->aux, 0, (size_t)h->mpad * Np * 8, h->stream));
-    h->loo_g0 = plan.pmin;
-    ck_launch_loo_rows(h->stream, h->aux, h->mpad, m, h->loo_g0, h->z, Np);
-    const int rc = solve_sweep(h);
-    h->loo_g0 = -1;
-    if (rc) return -1;
+    if (unit_row_sweep(h, m, plan.pmin, 1)) return -1;
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     // ---- 2. alpha and the Gram matrices
     std::vector<int> grow((size_t)ng);
@@ -2831,17 +2864,8 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
     if (nbig > 0) {
         const int kq_max = plan.big[0].kq, s_max = plan.big[0].s;
         ck_launch_fold_big_fill(h->stream, d_big, nbig, kq_max, d_buf, d_grow, h->d_pred);
-        const int G = 4;   // 64-column blocks per group; the group's columns receive everything from their left in one pass
-        int na = nbig;
-        for (int g0 = 0; g0 < s_max; g0 += 64 * G) {
-            if (g0 > 0) ck_launch_local_tiled_left(h->stream, d_sys, d_buf, na, g0, 64 * G, kqv.data());
-            for (int b = 0; b < G && g0 + 64 * b < kq_max; ++b) {
-                while (na > 0 && kqv[(size_t)na - 1] <= g0 + 64 * b) --na;
-                ck_launch_local_tiled_block(h->stream, d_sys, d_buf, na, g0, b, kqv.data(), d_linfo, G);
-            }
-            while (na > 0 && kqv[(size_t)na - 1] <= g0 + 64 * G) --na;
-            ck_launch_local_tiled_rows_all(h->stream, d_sys, d_buf, na, g0, G, kqv.data());
-        }
+        // left-looking in groups of 4 blocks, stopped behind the largest fold's last column
+        factor_tiled_batch(h->stream, d_sys, d_buf, nbig, kqv.data(), s_max, kq_max, 4, true, d_linfo);
         ck_launch_fold_big_reduce(h->stream, d_big, nbig, s_max, d_buf, d_linfo, d_x, d_d, d_stat, d_fail);
     }
     HIPCHK(hipGetLastError());
@@ -2890,23 +2914,13 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
 // through the factor on the growing prefix of live rows (aux_rows); then alpha_p = W_p . y (k_reduce_pred, raw mode),
 // G = alpha alpha^T - W^T W on the lower tiles with the structurally zero panels skipped (ck_la.hip: k_ginv_syrk_d, N^3 / 3
 // flop), and one pass of k_loglik_grad over G.  The handle's own state: the factor stays resident; the right-hand sides are
-// not prediction rows (aux_state 4: ck_verify_model / ck_aux_finish refuse until the next ck_predict / ck_aux_begin).
+// not prediction rows (AUX_LOGLIK: ck_verify_model / ck_aux_finish refuse until the next ck_predict / ck_aux_begin).
 //
 // REML (ck_loglik_reml, p = the trend columns of ck_set_trend): the right-hand sides are [z^T; X^T; unit rows], the unit rows
 // behind the p trend rows (loo_dense = 1 + p).  k_reduce_univ dots every row with [y; U]: |y|^2, b = U^T y and A = U^T U over
 // the first 1 + p rows, alpha_q = W_q . y and B_q = U^T W_q (= (Sigma^-1 X)_q) over the unit rows.  The host forms beta, log|A|,
 // b^T A^-1 b, alpha_R = alpha - B beta and C = B R^-T (A = R R^T); k_ginv_syrk_d starts from the rank-(1 + p) term
 // alpha_R alpha_R^T + C C^T.  p = 0 is ck_loglik's path, bit for bit.
-struct LikCallGuard {
-    ck_handle* h;
-    explicit LikCallGuard(ck_handle* hh) : h(hh) { h->aux_state = 4; }
-    ~LikCallGuard() {
-        h->aux_state = 4;
-        h->loo_g0 = -1;
-        h->loo_dense = 1;
-    }
-};
-
 static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, double* grad, int64_t* info) {
     const char* name = reml ? "ck_loglik_reml" : "ck_loglik";
     if (!out || !info || (want_grad && !grad)) return fail(std::string(name) + ": null argument");
@@ -2951,7 +2965,7 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
                         std::to_string(g_bytes) + " for the lower triangle of G); " + std::to_string(avail) +
                         " bytes are available");
     }
-    LikCallGuard guard(h);
+    CallGuard guard(h, AUX_LOGLIK, true);
     for (int k = 24; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
     h->t_ms[24] = h->t_ms[0];   // the assembly of this Sigma (ck_assemble_joint)
     // ---- the factor: factor here, or the resident one of a preceding ck_factor
@@ -2973,17 +2987,9 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
     // ---- right-hand sides: row 0 = z, rows 1 .. p = X^T (REML), rows 1 + p .. p + mrows = the unit vectors of every internal
     // position; the sweep
     if (aux_begin_impl(h, 0, nullptr, mrows + p, false)) return -1;
-    h->aux_state = 4;
+    h->aux_state = AUX_LOGLIK;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    HIPCHK(hipMemsetAsync(h->aux, 0, (size_t)h->mpad * Np * 8, h->stream));
-    h->loo_g0 = 0;
-    h->loo_dense = q;
-    ck_launch_loo_rows(h->stream, h->aux, h->mpad, mrows, 0, h->z, Np, q);
-    if (p > 0 && put_trend_rows(h, 1)) return -1;
-    const int rc = solve_sweep(h);
-    h->loo_g0 = -1;
-    h->loo_dense = 1;
-    if (rc) return -1;
+    if (unit_row_sweep(h, mrows, 0, q)) return -1;
     // alpha_p = W_p . y (d_pred[1 + p]) and |y|^2 (d_pred[0]); with a trend every row's dots with [y; U]; log L_qq per panel
     const int64_t nrows = mrows + 1 + p;
     if (p == 0) {
@@ -3223,72 +3229,19 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     // may lie below the LDS limit: then the LDS kernel only sees k <= k_hi.  The universal form has no slab kernel: every
     // neighbourhood beyond the LDS limit takes the tiled path
     const int k_hi = u ? std::min(h->local_tile_min, kl) : h->local_tile_min;
-    std::vector<long long> off(m, 0), need(m, 0);
-    std::vector<int64_t> tiled;   // points of the third class
-    int64_t kmx = 0, nempty = 0;
-    long long need_max = 0;
-    for (int64_t p = 0; p < m; ++p) {
-        const long long k = cnt[p];
-        kmx = k > kmx ? k : kmx;
-        if (k == 0) ++nempty;
-        long long nd = 0;
-        if (k > k_hi) {
-            tiled.push_back(p);
-            nd = ck_local_tiled_doubles(k, up);
-        } else if (k > kl) {
-            nd = need[p] = ((k + 2) * k + (k + 1) / 2 + 2 + 1) & ~1LL;   // matrix + index list (ints), kept 16-byte aligned
-        }
-        need_max = nd > need_max ? nd : need_max;
-    }
+    CkLocalNeeds nd;   // ck_host.cpp: the slab need of every point, the tiled class largest first
+    ck_host_local_needs(cnt.data(), m, kl, k_hi, up, &nd);
+    int64_t nempty = nd.n_empty;
     size_t mem_free = 0, mem_total = 0;
     HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
     mem_free += (size_t)local_slab_doubles(h) * 8;   // the slab kept from an earlier call is ours to reuse
     long long budget = (long long)std::min<size_t>(mem_free / 4, (size_t)32 << 30) / 8;   // doubles
     if (h->local_slab_mb > 0) budget = (long long)h->local_slab_mb * (1 << 20) / 8;      // option "local_slab_mb" (tests)
-    if (budget < need_max) budget = need_max;
-    if ((size_t)need_max * 8 > mem_free) return fail(std::string(u ? "ck_predict_local_universal" : "ck_predict_local") + ": a neighbourhood of " + std::to_string(kmx) + " sites does not fit the device memory");
-    std::vector<std::pair<int64_t, int64_t>> batches;   // [begin, end)
-    long long slab_doubles = 0;
-    {
-        int64_t b0 = 0;
-        long long acc = 0;
-        for (int64_t p = 0; p < m; ++p) {
-            if (acc + need[p] > budget && p > b0) {
-                batches.push_back({b0, p});
-                slab_doubles = acc > slab_doubles ? acc : slab_doubles;
-                b0 = p;
-                acc = 0;
-            }
-            off[p] = acc;
-            acc += need[p];
-        }
-        batches.push_back({b0, m});
-        slab_doubles = acc > slab_doubles ? acc : slab_doubles;
-    }
-    // tiled class: largest neighbourhoods first, so that the systems still active at a column are a prefix
-    std::sort(tiled.begin(), tiled.end(), [&](int64_t a, int64_t b) { return cnt[a] != cnt[b] ? cnt[a] > cnt[b] : a < b; });
-    std::vector<CkLocalSys> sysv(tiled.size());
-    std::vector<std::pair<size_t, size_t>> tbatches;
-    {
-        size_t b0 = 0;
-        long long acc = 0;
-        for (size_t t = 0; t < tiled.size(); ++t) {
-            const long long k = cnt[tiled[t]], nd = ck_local_tiled_doubles(k, up);
-            if (acc + nd > budget && t > b0) {
-                tbatches.push_back({b0, t});
-                slab_doubles = acc > slab_doubles ? acc : slab_doubles;
-                b0 = t;
-                acc = 0;
-            }
-            const int kq = (int)ck_local_tiled_kq(k, up);
-            sysv[t] = CkLocalSys{acc, (int)k, kq, kq + 128, (int)tiled[t]};
-            acc += nd;
-        }
-        if (!tiled.empty()) {
-            tbatches.push_back({b0, tiled.size()});
-            slab_doubles = acc > slab_doubles ? acc : slab_doubles;
-        }
-    }
+    if (budget < nd.need_max) budget = nd.need_max;
+    if ((size_t)nd.need_max * 8 > mem_free) return fail(std::string(u ? "ck_predict_local_universal" : "ck_predict_local") + ": a neighbourhood of " + std::to_string(nd.k_max) + " sites does not fit the device memory");
+    CkLocalPlan plan;   // slab offsets, the batches of both classes under the budget, the tiled systems
+    ck_host_local_plan(cnt.data(), nd, budget, up, &plan);
+    const long long slab_doubles = plan.slab_doubles;
     h->t_ms[14] = 0.0;
     const auto t_grow = std::chrono::steady_clock::now();
     if (slab_doubles > local_slab_doubles(h)) {
@@ -3309,7 +3262,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     }
     if (slab_doubles > 0) d_slab = h->local_slab;
     HIPCHK(hipEventRecord(h->ev2, h->stream));
-    HIPCHK(hipMemcpyAsync(d_off, off.data(), m * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_off, plan.off.data(), m * sizeof(long long), hipMemcpyHostToDevice, h->stream));
     const double c0var = h->blk[2 * i].amp + h->blk[2 * i].nugget;   // covariance(i, 0)[0], point_prediction.py:66
     const int use_tab = tables_usable(h) ? 1 : 0;
     if (u)
@@ -3317,7 +3270,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
                                 d_cnt, c0var, d_out, d_out + mp, h->d_tabs, h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb,
                                 cmax, Tr, d_beta, d_stat, nz);
     else
-        for (const auto& bt : batches)
+        for (const auto& bt : plan.batches)
             ck_launch_local_solve(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, bt.first, bt.second - bt.first,
                                   mp, h->s0, h->z, layout_of(h), d_cnt, d_off, d_slab, c0var, d_out, d_out + mp, h->d_tabs,
                                   h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb, cmax, nz);
@@ -3329,42 +3282,24 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
             for (hipEvent_t e : v) (void)hipEventDestroy(e);
         }
     } ev_free{ev_red};
-    if (!tiled.empty()) {
-        HIPCHK(tmp.get(&d_sys, (size_t)(sysv.size() * sizeof(CkLocalSys))));
-        HIPCHK(tmp.get(&d_linfo, (size_t)(sysv.size() * sizeof(long long))));
-        HIPCHK(tmp.get(&d_k0, (size_t)(sysv.size() * sizeof(int))));
-        HIPCHK(hipMemcpyAsync(d_sys, sysv.data(), sysv.size() * sizeof(CkLocalSys), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemsetAsync(d_linfo, 0, sysv.size() * sizeof(long long), h->stream));
-        for (const auto& tb : tbatches) {
+    if (!nd.tiled.empty()) {
+        HIPCHK(tmp.get(&d_sys, (size_t)(plan.sys.size() * sizeof(CkLocalSys))));
+        HIPCHK(tmp.get(&d_linfo, (size_t)(plan.sys.size() * sizeof(long long))));
+        HIPCHK(tmp.get(&d_k0, (size_t)(plan.sys.size() * sizeof(int))));
+        HIPCHK(hipMemcpyAsync(d_sys, plan.sys.data(), plan.sys.size() * sizeof(CkLocalSys), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemsetAsync(d_linfo, 0, plan.sys.size() * sizeof(long long), h->stream));
+        for (const auto& tb : plan.tbatches) {
             const CkLocalSys* bsys = d_sys + tb.first;
             const int nb = (int)(tb.second - tb.first);
             ck_launch_local_assemble_t(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, mp, h->s0, h->z,
                                        layout_of(h), bsys, nb, d_slab, h->d_tabs, h->d_coefptr, use_tab, h->su, d_pu,
                                        h->d_chunkb, cmax, d_k0 + tb.first, nz);
             if (u) ck_launch_local_trend_rows_t(h->stream, bsys, nb, d_slab, layout_of(h), Tr);
-            const int kq_max = sysv[tb.first].kq;
+            const int kq_max = plan.sys[tb.first].kq;
             std::vector<int> kqv(nb);
-            for (int y = 0; y < nb; ++y) kqv[y] = sysv[tb.first + y].kq;
-            int na = nb;
-            const int G = h->local_group;
-            const bool left = h->local_left != 0 && 64 * G <= 256;
-            for (int g0 = 0; g0 < kq_max; g0 += 64 * G) {
-                // left-looking (round 4): the group's columns first receive everything from their left in one pass (K = g0) --
-                // every tile of a system is read and written once instead of once per earlier group with K = 64 G
-                if (left && g0 > 0) {
-                    while (na > 0 && sysv[tb.first + na - 1].kq <= g0) --na;
-                    ck_launch_local_tiled_left(h->stream, bsys, d_slab, na, g0, 64 * G, kqv.data());
-                }
-                // the group's diagonal region block by block (diagonal block, then the few chunks of rows inside the region) ...
-                for (int b = 0; b < G && g0 + 64 * b < kq_max; ++b) {
-                    while (na > 0 && sysv[tb.first + na - 1].kq <= g0 + 64 * b) --na;   // finished systems drop off the end
-                    ck_launch_local_tiled_block(h->stream, bsys, d_slab, na, g0, b, kqv.data(), d_linfo + tb.first, G);
-                }
-                // ... then every row below it through all of the group's blocks in one launch, then the trailing update
-                while (na > 0 && sysv[tb.first + na - 1].kq <= g0 + 64 * G) --na;
-                ck_launch_local_tiled_rows_all(h->stream, bsys, d_slab, na, g0, G, kqv.data());
-                if (!left) ck_launch_local_tiled_trailing(h->stream, bsys, d_slab, na, g0, 64 * G, kqv.data());
-            }
+            for (int y = 0; y < nb; ++y) kqv[y] = plan.sys[tb.first + y].kq;
+            factor_tiled_batch(h->stream, bsys, d_slab, nb, kqv.data(), kq_max, kq_max, h->local_group,
+                               h->local_left != 0 && 64 * h->local_group <= 256, d_linfo + tb.first);
             if (u) {
                 hipEvent_t e0 = nullptr, e1 = nullptr;
                 HIPCHK(hipEventCreate(&e0));
@@ -3419,15 +3354,15 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
         h->t_ms[49] = (double)ms2 - red_ms;    // assembly and factorisation (the LDS class's kernel whole)
         h->t_ms[50] = red_ms;                  // the tiled class's universal reduction (Gram matrix + GLS step)
         h->t_ms[51] = ms_since(t_begin);
-        h->t_ms[52] = (double)(m - (int64_t)tiled.size());   // points of the LDS class (the empty ones among them)
-        h->t_ms[53] = (double)tiled.size();                  // points of the tiled class
+        h->t_ms[52] = (double)(m - (int64_t)nd.tiled.size());   // points of the LDS class (the empty ones among them)
+        h->t_ms[53] = (double)nd.tiled.size();                  // points of the tiled class
     } else {
         for (int64_t p = 0; p < m; ++p)
             if (cnt[p] > 0 && pred[p] != pred[p]) ++npd;
     }
     if (n_empty) *n_empty = nempty;
     if (n_not_pd) *n_not_pd = npd;
-    if (k_max) *k_max = kmx;
+    if (k_max) *k_max = nd.k_max;
     return 0;
 }
 
@@ -4247,7 +4182,7 @@ extern "C" int ck_set_option(ck_handle* h, const char* name, int64_t value) {
             // to report a failing minor in the caller's numbering; the step-wise driver does it through this option)
             h->layout_ready = false;
             h->assembled = h->factored = false;
-            h->aux_state = 0;
+            h->aux_state = AUX_NONE;
         }
         h->site_order = value != 0;
         return 0;

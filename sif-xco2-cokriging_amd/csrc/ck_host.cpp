@@ -548,7 +548,7 @@ int ck_host_fold_plan(int i, int n_procs, const int64_t n[2], int64_t n0p, const
     long long at = out->n_small_tiles * T * T;
     for (int32_t f : bg) {
         const int s = cnt[(size_t)f];
-        const int kq = (2 * s + 1 + 63) / 64 * 64, ld = kq + 128;
+        const int kq = (int)ck_local_tiled_kq(s, s - 1), ld = (int)ck_local_tiled_ld(kq);   // s + 2 + (s - 1) = 2 s + 1 rows
         const int g0 = (int)out->gpos.size();
         out->gbase[(size_t)f] = g0;
         out->big.push_back({at, s, kq, ld, g0, f, 0});
@@ -558,9 +558,68 @@ int ck_host_fold_plan(int i, int n_procs, const int64_t n[2], int64_t n0p, const
         for (int tm = 0; tm < nt; ++tm)
             for (int tn = 0; tn <= tm; ++tn)
                 out->tiles.push_back({at + (long long)tm * T * ld + (long long)tn * T, g0 + tm * T, g0 + tn * T, ld, out->gpos[(size_t)(g0 + tm * T)]});
-        at += (long long)(kq + 128) * ld + 8 * 64 * 64;
+        at += ck_local_tiled_matrix(kq);
     }
     out->buffer_doubles = at;
     std::stable_sort(out->tiles.begin(), out->tiles.end(), [](const CkFoldTile& a, const CkFoldTile& b) { return a.pos0 < b.pos0; });
     return 0;
+}
+
+// ---- ck_predict_local: size classes, slab offsets and batches (ck_host.h) -----------------------------------------------
+void ck_host_local_needs(const int* cnt, int64_t m, int lds_limit, int k_hi, int trend, CkLocalNeeds* out) {
+    *out = CkLocalNeeds();
+    out->need.assign((size_t)m, 0);
+    for (int64_t p = 0; p < m; ++p) {
+        const long long k = cnt[p];
+        out->k_max = std::max<int64_t>(out->k_max, k);
+        if (k == 0) ++out->n_empty;
+        long long nd = 0;
+        if (k > k_hi) {
+            out->tiled.push_back(p);
+            nd = ck_local_tiled_doubles(k, trend);
+        } else if (k > lds_limit) {
+            nd = out->need[(size_t)p] = ((k + 2) * k + (k + 1) / 2 + 2 + 1) & ~1LL;
+        }
+        out->need_max = std::max(out->need_max, nd);
+    }
+    std::sort(out->tiled.begin(), out->tiled.end(), [&](int64_t a, int64_t b) { return cnt[a] != cnt[b] ? cnt[a] > cnt[b] : a < b; });
+}
+
+// elements 0 .. n - 1 in order into batches under the budget: place(e, offset inside its batch); *largest is raised to the
+// largest batch sum
+template <class Need, class Place>
+static void cut_batches(int64_t n, long long budget, Need need, Place place, std::vector<std::pair<int64_t, int64_t>>* batches,
+                        long long* largest) {
+    int64_t b0 = 0;
+    long long acc = 0;
+    for (int64_t e = 0; e < n; ++e) {
+        if (acc + need(e) > budget && e > b0) {
+            batches->push_back({b0, e});
+            *largest = std::max(*largest, acc);
+            b0 = e;
+            acc = 0;
+        }
+        place(e, acc);
+        acc += need(e);
+    }
+    batches->push_back({b0, n});
+    *largest = std::max(*largest, acc);
+}
+
+void ck_host_local_plan(const int* cnt, const CkLocalNeeds& nd, long long budget, int trend, CkLocalPlan* out) {
+    *out = CkLocalPlan();
+    const int64_t m = (int64_t)nd.need.size(), nt = (int64_t)nd.tiled.size();
+    out->off.assign((size_t)m, 0);
+    cut_batches(
+        m, budget, [&](int64_t p) { return nd.need[(size_t)p]; }, [&](int64_t p, long long at) { out->off[(size_t)p] = at; },
+        &out->batches, &out->slab_doubles);
+    out->sys.resize((size_t)nt);
+    if (nt == 0) return;
+    cut_batches(
+        nt, budget, [&](int64_t t) { return ck_local_tiled_doubles(cnt[nd.tiled[(size_t)t]], trend); },
+        [&](int64_t t, long long at) {
+            const int k = cnt[nd.tiled[(size_t)t]], kq = (int)ck_local_tiled_kq(k, trend);
+            out->sys[(size_t)t] = CkLocalSys{at, k, kq, (int)ck_local_tiled_ld(kq), (int)nd.tiled[(size_t)t]};
+        },
+        &out->tbatches, &out->slab_doubles);
 }

@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 // symbols of this file that are not part of include/cokrige.h stay inside the shared object
@@ -87,6 +88,44 @@ CK_HIDDEN void ck_host_vario_fix(int metric, const double* ci, const double* cj,
 CK_HIDDEN int ck_host_gls(int p, const double* A, const double* b, double tol, double* R, double* beta, double* Ainv,
                           double* logdet, double* bAb);
 
+// ---- tiled local systems: their geometry (ck_internal.h has the layout) and ck_predict_local's plan -----------------------
+struct CkLocalSys {
+    long long off;      // doubles into the slab
+    int k, kq, ld, p;   // neighbours, padded size, leading dimension, prediction point index
+};
+#define CK_LT_ROWS(kq) ((kq) + 128)
+#define CK_LT_NINV 8   // inverses of the diagonal blocks of one column group kept side by side (option local_group <= 8)
+// p: trend rows of the universal form, in [kq - 2 - p, kq - 2) between the identity padding and the c / z rows
+static inline long long ck_local_tiled_kq(long long k, int p = 0) { return (k + 2 + p + 63) / 64 * 64; }
+static inline long long ck_local_tiled_ld(long long kq) { return kq + 128; }
+// the padded matrix and the inverses behind it
+static inline long long ck_local_tiled_matrix(long long kq) { return CK_LT_ROWS(kq) * ck_local_tiled_ld(kq) + CK_LT_NINV * 64 * 64; }
+static inline long long ck_local_tiled_doubles(long long k, int p = 0) {
+    return (ck_local_tiled_matrix(ck_local_tiled_kq(k, p)) + (k + 1) / 2 + 1) & ~1LL;
+}
+
+// Pure index work between ck_predict_local's counting pass and its first solve launch, in two steps around the device query
+// for the budget.  Step (a), from the neighbour counts cnt[0 .. m): need[p], the doubles of point p's scratch slab where
+// lds_limit < k <= k_hi (matrix + index list, kept 16-byte aligned; 0 elsewhere); tiled, the points with k > k_hi (k_hi may
+// lie below lds_limit: the universal form) sorted by k descending, ties by index -- the systems still active at a column are
+// a prefix; need_max, the largest need of a single point of either class (trend: the p trend rows of every tiled system).
+struct CkLocalNeeds {
+    std::vector<long long> need;
+    std::vector<int64_t> tiled;
+    int64_t k_max = 0, n_empty = 0;
+    long long need_max = 0;
+};
+CK_HIDDEN void ck_host_local_needs(const int* cnt, int64_t m, int lds_limit, int k_hi, int trend, CkLocalNeeds* out);
+// Step (b): both classes cut in order into batches [begin, end) whose needs sum to at most `budget` doubles (a batch holds at
+// least one element, whatever it needs); off[p] / sys[t].off: the prefix sums inside a batch; slab_doubles: the largest batch.
+struct CkLocalPlan {
+    std::vector<long long> off;
+    std::vector<std::pair<int64_t, int64_t>> batches, tbatches;   // points | indices into sys (empty without a tiled point)
+    std::vector<CkLocalSys> sys;
+    long long slab_doubles = 0;
+};
+CK_HIDDEN void ck_host_local_plan(const int* cnt, const CkLocalNeeds& nd, long long budget, int trend, CkLocalPlan* out);
+
 // ---- leave-group-out cross-validation: the fold layout (ck_api.hip: ck_cv_folds) ---------------------------------------
 // Pure index work, no device.  Fold f withholds every datum of either process labelled f (fold_k[a]: the caller's order of
 // process k; -1: never withheld; fold1 may be null).  perm_k[j] = caller's index of the site at internal position j of
@@ -103,7 +142,8 @@ CK_HIDDEN int ck_host_gls(int p, const double* A, const double* b, double tol, d
 //   buffer      [n_small_tiles x 128 x 128 | the big folds' systems].  A big fold of s members is the symmetric system of
 //               order kq = roundup(2 s + 1, 64) that the local predictor's batched Cholesky steps factor (ck_la.hip: k_lt_*):
 //               rows [0, s) Q_SS, rows s + q the unit rows (they become row q of R^-T), row 2 s alpha_S (becomes R^-1 alpha),
-//               ld = kq + 128, kq + 128 rows, then 8 x 64 x 64 doubles for the diagonal blocks' inverses.  big: largest first.
+//               ld = kq + 128, kq + 128 rows, then 8 x 64 x 64 doubles for the diagonal blocks' inverses (ck_local_tiled_matrix).  big:
+//               largest first.
 #define CK_HOST_FOLD_MAX 4096   // == CK_FOLD_MAX (include/cokrige.h)
 #define CK_HOST_FOLD_LDS 64     // folds up to this size are solved in LDS
 #define CK_HOST_FOLD_TILE 128

@@ -292,19 +292,8 @@ int ck_local_lds_limit();
 //         bounds checks; nothing valid depends on them.
 //   Linv  CK_LT_NINV x 64 x 64 doubles (inverses of the diagonal blocks of the current column group)
 //   idx   k ints (neighbour list)
-struct CkLocalSys {
-    long long off;      // doubles into the slab
-    int k, kq, ld, p;   // neighbours, padded size, leading dimension, prediction point index
-};
+// CkLocalSys, CK_LT_ROWS, CK_LT_NINV and the sizes ck_local_tiled_kq / ck_local_tiled_doubles: ck_host.h (the host plans with them)
 #define CK_LT_BIG 1e200
-#define CK_LT_ROWS(kq) ((kq) + 128)
-#define CK_LT_NINV 8   // inverses of the diagonal blocks of one column group kept side by side (option local_group <= 8)
-// p: trend rows of the universal form (below), in [kq - 2 - p, kq - 2) between the identity padding and the c / z rows
-static inline long long ck_local_tiled_kq(long long k, int p = 0) { return (k + 2 + p + 63) / 64 * 64; }
-static inline long long ck_local_tiled_doubles(long long k, int p = 0) {
-    const long long kq = ck_local_tiled_kq(k, p);
-    return (CK_LT_ROWS(kq) * (kq + 128) + CK_LT_NINV * 64 * 64 + (k + 1) / 2 + 1) & ~1LL;
-}
 void ck_launch_local_assemble_t(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
                                 const double* pc, int64_t mpad, const double* sc, const double* z, CkLayout L,
                                 const CkLocalSys* sys, int n_sys, double* slab, const CkTable* tabs,
