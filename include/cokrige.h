@@ -372,6 +372,32 @@ int ck_predict_local(ck_handle* h, int i, const double* pcoords_host, int64_t m,
  * 32 GiB; option "local_slab_mb" if set).  Afterwards no ck_predict_local whose batches fit pays a hipMalloc (tens of GiB
  * right after smaller buffers were freed: up to seconds -- ck_timings [14] shows what a call spent growing the slab). */
 int ck_local_reserve(ck_handle* h, int64_t nbytes);
+/* A nearest-neighbour cap per process for ck_predict_local / ck_predict_local_universal (gstat's nmax, per variable).  The rule,
+ * for prediction point p and process q:
+ *   - the candidates C_pq are the sites of process q that pass the radius predicate: d <= max_dist, and with cv != 0 and
+ *     q == i also d > 0; d is the distance the local kernels compute on the device;
+ *   - with nmax_q > 0 and |C_pq| > nmax_q, r_pq = the nmax_q-th smallest d over C_pq; otherwise r_pq = max_dist;
+ *   - the neighbours of p are the candidates with d <= r_pq.
+ * Every candidate at exactly the cut distance is kept, so a neighbourhood may hold more than nmax_q sites of process q: the
+ * neighbour set is a function of the distances alone -- not of the internal site order (option "site_order"), of chunking or
+ * of the order of ck_set_data.  Size classes, batches and k_max follow the final counts; nothing assumes k <= nmax0 + nmax1.
+ * Everything behind the neighbour list (its order, the local system, trend rows, noise, the NaN rules and counters) is as
+ * without a cap.  The cap is per process because a joint nearest-k list on data of unequal density often holds no datum of
+ * the sparser process at all.
+ * Handle state: 0 = no cap for that process, the default is (0, 0); a negative value is refused through ck_last_error; with
+ * one process nmax1 is ignored.  It invalidates nothing (no Sigma, factor or layout) and, like ck_set_trend, acts on the next
+ * local call; a partitioned handle accepts it.  With (0, 0) the local calls take exactly the uncapped path (no further kernel,
+ * the same bits).  With a cap set, a select pass (k_local_select, one workgroup per point: an 8-round radix select over the
+ * distances' bit patterns, integer histograms in LDS, no floating-point sums -- repeated calls give the same bits) replaces
+ * the counting pass and leaves every point its cut distances and the chord of max(r_p0, r_p1), against which the later
+ * kernels cull chunks of sites; a cap that binds nowhere (>= the data counts) gives the bits of the uncapped call.
+ * ck_timings [60 ..] describe the pass. */
+int ck_set_local_neighbours(ck_handle* h, int64_t nmax0, int64_t nmax1);
+/* The select pass alone, with the handle's caps: count (m x 2) the final number of neighbours of process 0 / 1 of every point,
+ * rcut (m x 2) r_pq, both in the caller's point order.  With (0, 0): the candidate counts and max_dist.  Answers "how far did
+ * the cap reach here"; the test surface of the selection kernel.  Sets ck_timings [60 ..]. */
+int ck_debug_local_neighbours(ck_handle* h, int i, const double* pcoords_host, int64_t m, double max_dist, int cv,
+                              int32_t* count_host /* m x 2 */, double* rcut_host /* m x 2 */);
 /* Universal cokriging in the moving neighbourhood: ck_predict_local with the trend of ck_set_trend estimated by GLS in every
  * neighbourhood (one constant column per process: ordinary cokriging in a moving window).  The formulation is that of
  * ck_predict_universal applied to one point's k neighbours, Sigma_loc = L L^T, c and z as in ck_predict_local:
@@ -534,7 +560,12 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * rows and the GLS step), summed over the batches; [51] host wall clock of the call; [52] / [53] number of points in the LDS
  * class (empty neighbourhoods included) / in the tiled class.
  * ck_cv_folds (n up to 60): [56] the unit rows and their sweep; [57] alpha = W y and the folds' Gram matrices (k_fold_gram);
- * [58] the fold solves of both size classes; [59] host wall clock of the call. */
+ * [58] the fold solves of both size classes; [59] host wall clock of the call.
+ * The neighbour cap (ck_set_local_neighbours; n up to 64), after a local call or ck_debug_local_neighbours: [60] the select
+ * pass (device; it is the counting pass of a capped call and part of [10]); [61] points with at least one capped process;
+ * [62] the largest candidate count of a point (both processes together) before the cap; [63] points where a process had more
+ * candidates than the LDS lists hold (option "local_select_cap") and re-scanned its chunks every round.  All 0 after an
+ * uncapped local call. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it
@@ -599,6 +630,9 @@ int ck_table_fallbacks(ck_handle* h, int reset, int64_t* count);
  * the tiled path of ck_predict_local (batched 64-column steps on the matrix cores) instead of one workgroup per
  * point (in LDS up to 64 sites, on a global slab above); ck_predict_local_universal with a trend set has no slab kernel:
  * there every neighbourhood beyond min(local_tile_min, 64) sites takes the tiled path;
+ * "local_select_cap" (1..2048, default 2048 = the compiled capacity): candidates per process the select pass of the neighbour
+ * cap keeps in LDS; a point with more re-scans its chunks every round (slower, the same result) -- lowered by tests to reach
+ * that path at small sizes;
  * "local_group" (1..8, default 4) = 64-column blocks per group of that path; "local_left" (0/1, default 1): a group's columns receive
  * everything from their left in one pass (K = the group's first column) before the group is factored, instead of a K = 64 x
  * local_group update of everything behind every group (same bits: the accumulation order per element is the same);

@@ -33,7 +33,7 @@
 #include "ck_model.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 60
+#define CK_N_TIMINGS 64
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -243,6 +243,8 @@ struct ck_handle {
                            // in-group launches cost more than the saved C traffic on small matrices)
     int64_t local_slab_mb = 0;   // option "local_slab_mb": scratch budget of ck_predict_local (0 = automatic)
     int local_tile_min = 64;     // option "local_tile_min": neighbourhoods larger than this take the tiled path
+    int64_t local_nmax[2] = {0, 0};   // ck_set_local_neighbours: nearest-neighbour cap per process of the local predictor (0: none)
+    int local_select_cap = 0;    // option "local_select_cap": candidates per process the select pass keeps in LDS (0: the compiled capacity)
     int local_group = 4;         // option "local_group": 64-column blocks per trailing update of the tiled path
     int local_left = 1;          // option "local_left": the tiled path's groups are updated left-looking (one pass with K = g0 in front
                                  // of each group) instead of right-looking (a K = 64 G update of everything behind each group)
@@ -324,7 +326,7 @@ struct CallGuard {
 static int64_t aux_cap(const ck_handle* h) { return (int64_t)h->aux_own.cap(); }               // doubles
 static long long local_slab_doubles(const ck_handle* h) { return (long long)h->local_slab.cap(); }
 
-extern "C" int ck_version(void) { return 101; }
+extern "C" int ck_version(void) { return 102; }
 extern "C" int ck_device_count(int* n) {
     HIPCHK(hipGetDeviceCount(n));
     return 0;
@@ -3144,6 +3146,93 @@ extern "C" int ck_loglik_noise_grad(ck_handle* h, double* out2) {
 // ---------------------------------------------------------------------------------------
 // local-neighbourhood cokriging: src/point_prediction.py:45-249
 // ---------------------------------------------------------------------------------------
+// largest chord (in the space of su / pu) a neighbour can have, with a margin (ck_local.hip: LpSearch)
+static double local_cmax(const ck_handle* h, double max_dist) {
+    double cmax = max_dist;
+    if (h->metric == CK_METRIC_HAVERSINE) {
+        const double half = max_dist / (2.0 * CK_EARTH_RADIUS_KM);
+        cmax = half >= 1.5 ? 4.0 : 2.0 * sin(half);   // beyond ~ a quarter of the globe: no culling
+    }
+    cmax = cmax * (1.0 + 1e-9) + 1e-12;
+    return cmax == cmax ? cmax : INFINITY;
+}
+
+// the neighbour cap of process q as the kernels take it (a cap beyond INT_MAX binds nowhere; one process: no second cap)
+static int local_nmax_of(const ck_handle* h, int q) {
+    if (q >= h->n_procs) return 0;
+    return (int)std::min<int64_t>(h->local_nmax[q], INT32_MAX);
+}
+static int local_key_cap(const ck_handle* h) {
+    return h->local_select_cap > 0 ? h->local_select_cap : ck_local_select_capacity();
+}
+// ck_timings [61] points with a capped process, [62] largest candidate count (both processes) before the cap, [63] points
+// that re-scanned; sel: the select pass's m x 4 ints (m = 0: an uncapped call)
+static void local_select_stats(ck_handle* h, const int* sel, int64_t m) {
+    int64_t n_capped = 0, n_rescan = 0, cand_max = 0;
+    for (int64_t p = 0; p < m; ++p) {
+        n_capped += (sel[4 * p + 3] & CK_LS_CAPPED) != 0;
+        n_rescan += (sel[4 * p + 3] & CK_LS_RESCAN) != 0;
+        cand_max = std::max<int64_t>(cand_max, sel[4 * p + 2]);
+    }
+    h->t_ms[61] = (double)n_capped;
+    h->t_ms[62] = (double)cand_max;
+    h->t_ms[63] = (double)n_rescan;
+}
+
+extern "C" int ck_set_local_neighbours(ck_handle* h, int64_t nmax0, int64_t nmax1) {
+    CHKH(h);
+    if (nmax0 < 0 || nmax1 < 0)
+        return fail("ck_set_local_neighbours: a cap must be >= 0 (0 = none), got (" + std::to_string(nmax0) + ", " +
+                    std::to_string(nmax1) + ")");
+    h->local_nmax[0] = nmax0;
+    h->local_nmax[1] = nmax1;
+    return 0;
+}
+
+// the select pass alone, with the handle's caps (none: the candidate counts and max_dist)
+extern "C" int ck_debug_local_neighbours(ck_handle* h, int i, const double* pcoords, int64_t m, double max_dist, int cv,
+                                         int32_t* count, double* rcut) {
+    CHKH(h);
+    if (ensure_layout(h, false)) return -1;
+    if (i < 0 || i >= h->n_procs) return fail("process index out of range");
+    if (m < 0 || (m > 0 && (!pcoords || !count || !rcut))) return fail("ck_debug_local_neighbours: bad arguments");
+    for (int k = 60; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    if (m == 0) return 0;
+    const int64_t mp = roundup(m, 64);
+    DevTemps tmp;
+    double *d_pc = nullptr, *d_p3 = nullptr, *d_pu = nullptr, *d_rq = nullptr, *d_cp = nullptr;
+    int *d_cnt = nullptr, *d_sel = nullptr;
+    HIPCHK(tmp.get(&d_pc, (size_t)(2 * mp * 8)));
+    HIPCHK(tmp.get(&d_p3, (size_t)(3 * mp * 8)));
+    HIPCHK(tmp.get(&d_pu, (size_t)(3 * mp * 8)));
+    HIPCHK(tmp.get(&d_rq, (size_t)(2 * mp * 8)));
+    HIPCHK(tmp.get(&d_cp, (size_t)(mp * 8)));
+    HIPCHK(tmp.get(&d_cnt, (size_t)(mp * sizeof(int))));
+    HIPCHK(tmp.get(&d_sel, (size_t)(4 * mp * sizeof(int))));
+    HIPCHK(hipMemsetAsync(d_pc, 0, 2 * mp * 8, h->stream));
+    HIPCHK(hipMemcpyAsync(d_pc, pcoords, 2 * m * 8, hipMemcpyHostToDevice, h->stream));
+    ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, d_p3, d_p3 + mp, d_p3 + 2 * mp, d_pu);
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    ck_launch_local_select(h->stream, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, layout_of(h), h->d_chunkb,
+                           local_cmax(h, max_dist), d_pu, local_nmax_of(h, 0), local_nmax_of(h, 1), local_key_cap(h), d_cnt, d_sel,
+                           d_rq, d_cp);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    std::vector<int> sel((size_t)(4 * m));
+    HIPCHK(hipMemcpyAsync(sel.data(), d_sel, sel.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(rcut, d_rq, (size_t)(2 * m * 8), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int64_t p = 0; p < m; ++p) {
+        count[2 * p] = sel[(size_t)(4 * p)];
+        count[2 * p + 1] = sel[(size_t)(4 * p + 1)];
+    }
+    double ms = 0;
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms));
+    h->t_ms[60] = ms;
+    local_select_stats(h, sel.data(), m);
+    return 0;
+}
+
 // The universal form's extras (ck_predict_local_universal); null: simple cokriging, ck_predict_local as it always was
 struct LocalUniv {
     const double* f0;      // m x p_i, the caller's (may hold non-finite entries: rule 5)
@@ -3179,6 +3268,18 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     HIPCHK(tmp.get(&d_out, (size_t)(2 * mp * 8)));
     HIPCHK(tmp.get(&d_cnt, (size_t)(mp * sizeof(int))));
     HIPCHK(tmp.get(&d_off, (size_t)(mp * sizeof(long long))));
+    // the neighbour cap (ck_set_local_neighbours): the select pass replaces the counting pass and leaves every point's cut
+    // distances and culling chord for the later launches; no cap: none of this exists and no kernel sees a new pointer
+    const int nmax0 = local_nmax_of(h, 0), nmax1 = local_nmax_of(h, 1);
+    const bool capped = nmax0 > 0 || nmax1 > 0;
+    int* d_sel = nullptr;
+    double *d_rq = nullptr, *d_cp = nullptr;
+    if (capped) {
+        HIPCHK(tmp.get(&d_sel, (size_t)(4 * mp * sizeof(int))));
+        HIPCHK(tmp.get(&d_rq, (size_t)(2 * mp * 8)));
+        HIPCHK(tmp.get(&d_cp, (size_t)(mp * 8)));
+    }
+    const CkLocalCap cap{d_rq, d_cp};
     // universal form: the regressors of the prediction points (a point with a non-finite one is settled on the host at the
     // end and computes with zeros meanwhile), the status of every point, the local coefficients
     double *d_f0 = nullptr, *d_beta = nullptr;
@@ -3202,22 +3303,22 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     HIPCHK(hipMemcpyAsync(d_pc, pcoords, 2 * m * 8, hipMemcpyHostToDevice, h->stream));
     ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, d_p3, d_p3 + mp, d_p3 + 2 * mp, d_pu);
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    // largest chord (in the space of su / pu) a neighbour can have, with a margin (ck_local.hip: LpSearch)
-    double cmax = max_dist;
-    if (h->metric == CK_METRIC_HAVERSINE) {
-        const double half = max_dist / (2.0 * CK_EARTH_RADIUS_KM);
-        cmax = half >= 1.5 ? 4.0 : 2.0 * sin(half);   // beyond ~ a quarter of the globe: no culling
-    }
-    cmax = cmax * (1.0 + 1e-9) + 1e-12;
-    if (!(cmax == cmax)) cmax = INFINITY;
-    ck_launch_local_count(h->stream, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, layout_of(h), d_cnt,
-                          h->d_chunkb, cmax, d_pu);
+    const double cmax = local_cmax(h, max_dist);
+    if (capped)
+        ck_launch_local_select(h->stream, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, layout_of(h), h->d_chunkb, cmax,
+                               d_pu, nmax0, nmax1, local_key_cap(h), d_cnt, d_sel, d_rq, d_cp);
+    else
+        ck_launch_local_count(h->stream, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, layout_of(h), d_cnt,
+                              h->d_chunkb, cmax, d_pu);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev1, h->stream));   // [ev0, ev1]: the counting pass; the host-side planning and a growth of the
                                                  // scratch slab (hipMalloc: up to seconds) lie between the two device windows
     std::vector<int> cnt(m);
     HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, m * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    std::vector<int> sel(capped ? (size_t)(4 * m) : 0);
+    if (capped) HIPCHK(hipMemcpyAsync(sel.data(), d_sel, sel.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    local_select_stats(h, sel.data(), capped ? m : 0);   // ck_timings [61] .. [63]
     // Scratch slabs for neighbourhoods beyond the LDS limit.  Three size classes:
     //   k <= LDS limit               k_local_solve, system in LDS
     //   k <= local_tile_min          k_local_solve_big, one workgroup per point on a slab in global memory
@@ -3268,12 +3369,12 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     if (u)
         ck_launch_local_solve_u(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, h->z, layout_of(h),
                                 d_cnt, c0var, d_out, d_out + mp, h->d_tabs, h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb,
-                                cmax, Tr, d_beta, d_stat, nz);
+                                cmax, Tr, d_beta, d_stat, nz, cap);
     else
         for (const auto& bt : plan.batches)
             ck_launch_local_solve(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, bt.first, bt.second - bt.first,
                                   mp, h->s0, h->z, layout_of(h), d_cnt, d_off, d_slab, c0var, d_out, d_out + mp, h->d_tabs,
-                                  h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb, cmax, nz);
+                                  h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb, cmax, nz, cap);
     HIPCHK(hipGetLastError());
     std::vector<hipEvent_t> ev_red;   // universal form: an event pair around every batch's reduction (ck_timings [50])
     struct EvFree {
@@ -3293,7 +3394,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
             const int nb = (int)(tb.second - tb.first);
             ck_launch_local_assemble_t(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, mp, h->s0, h->z,
                                        layout_of(h), bsys, nb, d_slab, h->d_tabs, h->d_coefptr, use_tab, h->su, d_pu,
-                                       h->d_chunkb, cmax, d_k0 + tb.first, nz);
+                                       h->d_chunkb, cmax, d_k0 + tb.first, nz, cap);
             if (u) ck_launch_local_trend_rows_t(h->stream, bsys, nb, d_slab, layout_of(h), Tr);
             const int kq_max = plan.sys[tb.first].kq;
             std::vector<int> kqv(nb);
@@ -3325,6 +3426,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms));
     HIPCHK(elapsed_ms(h->ev2, h->ev3, &ms2));
     h->t_ms[10] = ms + ms2;   // device work: counting pass + assembly / factorisations / reductions
+    h->t_ms[60] = capped ? ms : 0.0;   // the select pass (it is the counting pass of a capped call)
     int64_t npd = 0;
     if (u) {
         std::vector<int> stat((size_t)m);
@@ -4164,6 +4266,12 @@ extern "C" int ck_set_option(ck_handle* h, const char* name, int64_t value) {
     if (!strcmp(name, "local_group")) {
         if (value < 1 || value > CK_LT_NINV) return fail("local_group must be in [1, 8]");
         h->local_group = (int)value;
+        return 0;
+    }
+    if (!strcmp(name, "local_select_cap")) {   // see ck_handle::local_select_cap (tests: the re-scan path at small sizes)
+        if (value < 1 || value > ck_local_select_capacity())
+            return fail("local_select_cap must be in [1, " + std::to_string(ck_local_select_capacity()) + "]");
+        h->local_select_cap = (int)value;
         return 0;
     }
     if (!strcmp(name, "local_tile_min")) {   // see ck_handle::local_tile_min

@@ -268,6 +268,22 @@ void ck_launch_local_chunk_bounds(hipStream_t s, const double* su, CkLayout L, d
 void ck_launch_local_count(hipStream_t s, int metric, int i_pred, int cv, double max_dist, const double* pc,
                            int64_t m, int64_t mpad, const double* sc, CkLayout L, int* counts, const double* cb,
                            double cmax, const double* pu);
+// The neighbour cap (ck_set_local_neighbours; include/cokrige.h has the rule).  ck_launch_local_select is the counting pass
+// of a capped call: per point and process the cut distance r_pq (rq: m x 2; max_dist where the cap does not bind) and the
+// final counts (sel: m x 4 ints -- neighbours of process 0, of process 1, candidates before the cap, flags), their sum in
+// counts, and the point's culling chord cp (the chord of max(r_p0, r_p1) with cmax's margin; cmax itself where that is
+// max_dist).  key_cap: candidates per process kept in LDS (option "local_select_cap"); a process with more runs the same
+// rounds re-scanning its chunks.  The later launches take (rq, cp) as CkLocalCap; null pointers: no cap, today's expressions.
+#define CK_LS_CAPPED 1   // sel flags: the cap binds for some process of the point
+#define CK_LS_RESCAN 2   //            some process had more candidates than key_cap
+struct CkLocalCap {
+    const double* rq = nullptr;
+    const double* cp = nullptr;
+};
+int ck_local_select_capacity();
+void ck_launch_local_select(hipStream_t s, int metric, int i_pred, int cv, double max_dist, const double* pc, int64_t m,
+                            int64_t mpad, const double* sc, CkLayout L, const double* cb, double cmax, const double* pu,
+                            int nmax0, int nmax1, int key_cap, int* counts, int* sel, double* rq, double* cp);
 // slab_off[p]: offset (doubles) of point p's scratch slab ((k + 2) k doubles + k ints) when its
 // neighbourhood exceeds the LDS limit
 void ck_launch_local_solve(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
@@ -276,7 +292,8 @@ void ck_launch_local_solve(hipStream_t s, const CkMatern* blk, int metric, int i
                            double* pred, double* err, const CkTable* tabs, const double* const* coefs, int use_tab,
                            const double* su, const double* pu, int k_hi, const double* cb, double cmax,
                            const double* nz = nullptr /* ck_set_noise: s d per site in the internal order, added to the diagonal
-                           of every local system next to z[ga]; null: off (the same for the other local launches) */);
+                           of every local system next to z[ga]; null: off (the same for the other local launches) */,
+                           CkLocalCap cap = {});
 int ck_local_lds_limit();
 
 // Large neighbourhoods (k > k_hi above): the "tiled" path.  The systems of a batch are factored TOGETHER,
@@ -299,7 +316,7 @@ void ck_launch_local_assemble_t(hipStream_t s, const CkMatern* blk, int metric, 
                                 const CkLocalSys* sys, int n_sys, double* slab, const CkTable* tabs,
                                 const double* const* coefs, int use_tab, const double* su, const double* pu,
                                 const double* cb, double cmax, int* k0buf /* n_sys ints of scratch */,
-                                const double* nz = nullptr);
+                                const double* nz = nullptr, CkLocalCap cap = {});
 // Columns are processed in groups of g 64-column blocks [g0, g0 + 64 g): block i of a group first receives the
 // updates of the group's earlier blocks (one pass, K = 64 i), then its diagonal block is factored and inverted and
 // the rows below are solved; the trailing matrix behind the group is updated once with K = 64 g (a g-th of the
@@ -343,7 +360,7 @@ void ck_launch_local_solve_u(hipStream_t s, const CkMatern* blk, int metric, int
                              const int* counts, double c0var, double* pred, double* err, const CkTable* tabs,
                              const double* const* coefs, int use_tab, const double* su, const double* pu, int k_hi,
                              const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status,
-                             const double* nz = nullptr);
+                             const double* nz = nullptr, CkLocalCap cap = {});
 // behind ck_launch_local_assemble_t: the trend rows of the batch's systems
 void ck_launch_local_trend_rows_t(hipStream_t s, const CkLocalSys* sys, int n_sys, double* slab, CkLayout L, CkLocalTrend Tr);
 // k0buf: the process-0 neighbour counts ck_launch_local_assemble_t left

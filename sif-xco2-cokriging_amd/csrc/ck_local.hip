@@ -15,6 +15,7 @@
 // per point with a blocked factorisation in one workgroup (k_local_solve_big).
 // Universal cokriging in the neighbourhood (a GLS trend per point, ck_predict_local_universal): at the end of this file.
 #include "ck_internal.h"
+#include "ck_select.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 
@@ -27,14 +28,32 @@ __device__ __forceinline__ double lp_dist(int metric, double a0, double a1, doub
     return metric == CK_METRIC_HAVERSINE ? ck_haversine_km(a0, a1, a2, b0, b1, b2) : ck_euclid(a0, a1, b0, b1);
 }
 
-__device__ __forceinline__ bool lp_is_neighbour(int metric, int cv, int i_pred, double max_dist, const CkLayout& L,
-                                                long g, double p0, double p1, double p2, const double* s0,
-                                                const double* s1, const double* s2) {
+// What a point's search compares against: the cut distance of either process and the culling chord.  Without a neighbour cap
+// (LpSearch::rq null) these are max_dist and the host's cmax; with one, the point's own values from k_local_select.
+struct LpReach {
+    double r0, r1, cmax;
+};
+
+// today's predicate (the candidates of the neighbour cap): *d is the device distance, *proc the site's process
+__device__ __forceinline__ bool lp_candidate(int metric, int cv, int i_pred, double max_dist, const CkLayout& L, long g,
+                                             double p0, double p1, double p2, const double* s0, const double* s1,
+                                             const double* s2, double* d, int* proc) {
+    if (!(g < L.n0 || (g >= L.n0p && g < L.nend))) return false;
+    *d = lp_dist(metric, p0, p1, p2, s0[g], s1[g], s2[g]);
+    *proc = g >= L.n0p;
+    if (cv && *proc == i_pred) return *d > 0.0 && *d <= max_dist;
+    return *d <= max_dist;
+}
+
+__device__ __forceinline__ bool lp_is_neighbour(int metric, int cv, int i_pred, const LpReach& Q, const CkLayout& L, long g,
+                                                double p0, double p1, double p2, const double* s0, const double* s1,
+                                                const double* s2) {
     if (!(g < L.n0 || (g >= L.n0p && g < L.nend))) return false;
     const double d = lp_dist(metric, p0, p1, p2, s0[g], s1[g], s2[g]);
     const int proc = g >= L.n0p;
-    if (cv && proc == i_pred) return d > 0.0 && d <= max_dist;
-    return d <= max_dist;
+    const double lim = proc ? Q.r1 : Q.r0;
+    if (cv && proc == i_pred) return d > 0.0 && d <= lim;
+    return d <= lim;
 }
 
 // Covariance of a pair: through the block's table (ck_math.h "Tabulated covariance"; coefficients read from
@@ -77,14 +96,21 @@ struct LpSearch {
     const double* cb;   // 4 x nchunk: centre x, y, z, rad (rad < 0: no valid site in the chunk)
     long nchunk;
     double cmax;
+    const double* rq;   // neighbour cap: m x 2 cut distances and
+    const double* cp;   // m culling chords of the points (both null: no cap)
 };
 
-__device__ __forceinline__ bool lp_chunk_far(const LpSearch& R, long chunk, double q0, double q1, double q2) {
+__device__ __forceinline__ LpReach lp_reach(const LpSearch& R, long p, double max_dist) {
+    if (R.rq) return LpReach{R.rq[2 * p], R.rq[2 * p + 1], R.cp[p]};
+    return LpReach{max_dist, max_dist, R.cmax};
+}
+
+__device__ __forceinline__ bool lp_chunk_far(const LpSearch& R, const LpReach& Q, long chunk, double q0, double q1, double q2) {
     if (chunk >= R.nchunk) return true;
     const double rad = R.cb[3 * R.nchunk + chunk];
     if (rad < 0.0) return true;
     const double dx = R.cb[chunk] - q0, dy = R.cb[R.nchunk + chunk] - q1, dz = R.cb[2 * R.nchunk + chunk] - q2;
-    return sqrt(dx * dx + dy * dy + dz * dz) - rad > R.cmax;
+    return sqrt(dx * dx + dy * dy + dz * dz) - rad > Q.cmax;
 }
 
 __global__ __launch_bounds__(LP_TPB) void k_local_chunk_bounds(const double* __restrict__ su, CkLayout L, long nchunk,
@@ -138,12 +164,13 @@ __global__ __launch_bounds__(LP_TPB) void k_local_count(int metric, int i_pred, 
     const long p = blockIdx.x;
     const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
     const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
+    const LpReach Q = lp_reach(R, p, max_dist);
     const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
     int c = 0;
     for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
-        if (lp_chunk_far(R, g0 / LP_TPB, q0, q1, q2)) continue;
+        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;
         const long g = g0 + threadIdx.x;
-        c += (g < L.nend && lp_is_neighbour(metric, cv, i_pred, max_dist, L, g, p0, p1, p2, s0, s1, s2)) ? 1 : 0;
+        c += (g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2)) ? 1 : 0;
     }
     red[threadIdx.x] = c;
     __syncthreads();
@@ -152,6 +179,108 @@ __global__ __launch_bounds__(LP_TPB) void k_local_count(int metric, int i_pred, 
         __syncthreads();
     }
     if (threadIdx.x == 0) counts[p] = red[0];
+}
+
+// ---------------------------------------------------------------------------------------
+// The neighbour cap (ck_set_local_neighbours): the counting pass of a capped call
+// ---------------------------------------------------------------------------------------
+// One workgroup per point.  The candidates of process q -- the sites today's predicate lets through -- are cut at
+// r_pq = the nmax_q-th smallest distance when there are more than nmax_q of them, and every candidate with d <= r_pq stays (ties
+// at the cut included: the set is a function of the distances alone).  The order statistic comes from the radix select of
+// ck_select.h over the distances' bit patterns: per round a 256-bin histogram filled with integer LDS atomics (the same
+// histogram whatever the arrival order), then one thread per process narrows.  Up to key_cap candidates per process are kept
+// in LDS by the first scan; a process with more re-scans its chunks and recomputes the distances every round (same keys,
+// same result).  No floating-point sum anywhere: repeated calls give the same bits.
+#define LS_CAP 2048   // keys per process in LDS: 2 x 16 KB
+
+// calls f(process, key) for every candidate this thread meets, chunk by chunk as the counting pass walks them
+template <class F>
+__device__ __forceinline__ void ls_scan(int metric, int i_pred, int cv, double max_dist, const CkLayout& L, const LpSearch& R,
+                                        const LpReach& Q, double p0, double p1, double p2, double q0, double q1, double q2,
+                                        const double* s0, const double* s1, const double* s2, F f) {
+    for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
+        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;
+        const long g = g0 + threadIdx.x;
+        double d;
+        int proc;
+        if (g < L.nend && lp_candidate(metric, cv, i_pred, max_dist, L, g, p0, p1, p2, s0, s1, s2, &d, &proc)) f(proc, ck_sel_key(d));
+    }
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_local_select(int metric, int i_pred, int cv, double max_dist,
+                                                          const double* __restrict__ pc, long mpad,
+                                                          const double* __restrict__ sc, CkLayout L, LpSearch R,
+                                                          const double* __restrict__ pu, int nmax0, int nmax1, int key_cap,
+                                                          int* __restrict__ counts, int* __restrict__ sel,
+                                                          double* __restrict__ rq, double* __restrict__ cp) {
+    __shared__ unsigned long long keys[2][LS_CAP];
+    __shared__ unsigned hist[2][CK_SEL_BINS];
+    __shared__ unsigned ncand[2];
+    __shared__ CkSelState st[2];
+    const int tid = threadIdx.x;
+    const long p = blockIdx.x;
+    const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
+    const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
+    const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
+    const LpReach Q{max_dist, max_dist, R.cmax};   // the candidates are searched within max_dist
+    if (tid < 2) ncand[tid] = 0;
+    __syncthreads();
+    ls_scan(metric, i_pred, cv, max_dist, L, R, Q, p0, p1, p2, q0, q1, q2, s0, s1, s2, [&](int q, unsigned long long key) {
+        const unsigned slot = atomicAdd(&ncand[q], 1u);
+        if (slot < (unsigned)key_cap) keys[q][slot] = key;
+    });
+    __syncthreads();
+    // everything below is uniform (scalar branches around the barriers); bit q of a mask speaks of process q (no array is
+    // indexed at run time)
+    const int nc0 = __builtin_amdgcn_readfirstlane((int)ncand[0]), nc1 = __builtin_amdgcn_readfirstlane((int)ncand[1]);
+    const unsigned capped = (nmax0 > 0 && nc0 > nmax0 ? 1u : 0u) | (nmax1 > 0 && nc1 > nmax1 ? 2u : 0u);
+    const unsigned rescan = capped & ((nc0 > key_cap ? 1u : 0u) | (nc1 > key_cap ? 2u : 0u));
+    if (capped) {
+        if (tid < 2 && (capped >> tid & 1u)) ck_sel_begin(&st[tid], tid ? nmax1 : nmax0);
+        for (int round = 0; round < CK_SEL_ROUNDS; ++round) {
+            for (int e = tid; e < 2 * CK_SEL_BINS; e += LP_TPB) hist[e / CK_SEL_BINS][e % CK_SEL_BINS] = 0;
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                if (!((capped & ~rescan) >> q & 1u)) continue;
+                const int n = q ? nc1 : nc0;
+                for (int e = tid; e < n; e += LP_TPB) {
+                    const unsigned long long key = keys[q][e];
+                    if (ck_sel_match(&st[q], key)) atomicAdd(&hist[q][ck_sel_digit(&st[q], key)], 1u);
+                }
+            }
+            if (rescan)
+                ls_scan(metric, i_pred, cv, max_dist, L, R, Q, p0, p1, p2, q0, q1, q2, s0, s1, s2, [&](int q, unsigned long long key) {
+                    if ((rescan >> q & 1u) && ck_sel_match(&st[q], key)) atomicAdd(&hist[q][ck_sel_digit(&st[q], key)], 1u);
+                });
+            __syncthreads();
+            if ((tid == 0 || tid == 64) && (capped >> (tid >> 6) & 1u)) ck_sel_narrow(&st[tid >> 6], hist[tid >> 6]);   // a wave per process
+            __syncthreads();
+        }
+    }
+    if (tid == 0) {
+        const double r0 = (capped & 1u) ? ck_sel_dist(st[0].prefix) : max_dist, r1 = (capped & 2u) ? ck_sel_dist(st[1].prefix) : max_dist;
+        const int k0 = (capped & 1u) ? (int)(st[0].less + st[0].ties) : nc0, k1 = (capped & 2u) ? (int)(st[1].less + st[1].ties) : nc1;
+        rq[2 * p] = r0;
+        rq[2 * p + 1] = r1;
+        sel[4 * p] = k0;
+        sel[4 * p + 1] = k1;
+        sel[4 * p + 2] = nc0 + nc1;
+        sel[4 * p + 3] = (capped ? CK_LS_CAPPED : 0) | (rescan ? CK_LS_RESCAN : 0);
+        counts[p] = k0 + k1;
+        // the chord of the point's reach, with the margin of cmax; a process without sites does not widen it
+        const double reach = L.nend > L.n0p ? fmax(r0, r1) : r0;
+        double c = R.cmax;
+        if (reach < max_dist) {
+            c = reach;
+            if (metric == CK_METRIC_HAVERSINE) {
+                const double half = reach / (2.0 * CK_EARTH_RADIUS_KM);
+                c = half >= 1.5 ? 4.0 : 2.0 * sin(half);
+            }
+            c = fmin(c * (1.0 + 1e-9) + 1e-12, R.cmax);
+        }
+        cp[p] = c;
+    }
 }
 
 __global__ __launch_bounds__(LP_TPB) void k_local_solve(const CkMatern* __restrict__ blk, int metric, int i_pred,
@@ -185,6 +314,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve(const CkMatern* __restri
     const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
     const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;        // chord vectors (table path)
     const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
+    const LpReach Q = lp_reach(R, p, max_dist);
     // storage: (k + 2) x k matrix (rows k, k + 1 carry c and z) and the neighbour index list
     double* S = lS;
     int* idx = lidx;
@@ -193,9 +323,9 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve(const CkMatern* __restri
     if (tid == 0) fail = 0;
     int base = 0;
     for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
-        if (lp_chunk_far(R, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
+        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
         const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, max_dist, L, g, p0, p1, p2, s0, s1, s2);
+        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2);
         const unsigned long long bal = __ballot(f);
         const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
         if (lane == 0) wsum[wv] = __popcll(bal);
@@ -328,6 +458,7 @@ __global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(const CkMatern* _
     const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
     const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;        // chord vectors (table path)
     const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
+    const LpReach Q = lp_reach(R, p, max_dist);
     double* S = slab + slab_off[p];   // (k + 2) x k, rows k and k + 1 carry c and z
     int* idx = reinterpret_cast<int*>(S + (long)(k + 2) * k);
     const long ld = k;
@@ -335,9 +466,9 @@ __global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(const CkMatern* _
     if (tid == 0) fail = 0;
     int base = 0;
     for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
-        if (lp_chunk_far(R, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
+        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
         const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, max_dist, L, g, p0, p1, p2, s0, s1, s2);
+        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2);
         const unsigned long long bal = __ballot(f);
         const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
         if (lane == 0) wsum[wv] = __popcll(bal);
@@ -517,8 +648,20 @@ void ck_launch_local_count(hipStream_t s, int metric, int i_pred, int cv, double
                            int64_t m, int64_t mpad, const double* sc, CkLayout L, int* counts, const double* cb,
                            double cmax, const double* pu) {
     if (m <= 0) return;
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax};
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, nullptr, nullptr};
     k_local_count<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(metric, i_pred, cv, max_dist, pc, mpad, sc, L, counts, R, pu);
+}
+
+int ck_local_select_capacity() { return LS_CAP; }
+
+void ck_launch_local_select(hipStream_t s, int metric, int i_pred, int cv, double max_dist, const double* pc, int64_t m,
+                            int64_t mpad, const double* sc, CkLayout L, const double* cb, double cmax, const double* pu,
+                            int nmax0, int nmax1, int key_cap, int* counts, int* sel, double* rq, double* cp) {
+    if (m <= 0) return;
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, nullptr, nullptr};
+    key_cap = key_cap < 1 ? 1 : (key_cap > LS_CAP ? LS_CAP : key_cap);   // never beyond the LDS lists
+    k_local_select<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(metric, i_pred, cv, max_dist, pc, mpad, sc, L, R, pu, nmax0, nmax1,
+                                                              key_cap, counts, sel, rq, cp);
 }
 
 // points [p_base, p_base + m): slab_off is relative to `slab` within this batch (ck_predict_local)
@@ -526,10 +669,10 @@ void ck_launch_local_solve(hipStream_t s, const CkMatern* blk, int metric, int i
                            const double* pc, int64_t p_base, int64_t m, int64_t mpad, const double* sc, const double* z,
                            CkLayout L, const int* counts, const long long* slab_off, double* slab, double c0var,
                            double* pred, double* err, const CkTable* tabs, const double* const* coefs, int use_tab,
-                           const double* su, const double* pu, int k_hi, const double* cb, double cmax, const double* nz) {
+                           const double* su, const double* pu, int k_hi, const double* cb, double cmax, const double* nz, CkLocalCap cap) {
     if (m <= 0) return;
     const LpTab T{tabs, coefs, use_tab};
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax};
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp};
     k_local_solve<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L,
                                                              counts, slab_off, slab, c0var, pred, err, p_base, T, su, pu, R, k_hi,
                                                              nz);
@@ -581,13 +724,14 @@ __global__ __launch_bounds__(LP_TPB) void k_local_search_t(const CkMatern* __res
     const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
     const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;
     const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
+    const LpReach Q = lp_reach(R, p, max_dist);
     double* S = slab + q.off;
     int* idx = reinterpret_cast<int*>(S + (long)CK_LT_ROWS(kq) * ld + CK_LT_NINV * 64 * 64);
     int base = 0, k0 = 0;   // k0: neighbours of process 0
     for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {   // ordered compaction, as in k_local_solve
-        if (lp_chunk_far(R, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
+        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
         const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, max_dist, L, g, p0, p1, p2, s0, s1, s2);
+        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2);
         const unsigned long long bal = __ballot(f), bal0 = __ballot(f && g < L.n0p);
         const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
         if (lane == 0) {
@@ -802,10 +946,10 @@ void ck_launch_local_assemble_t(hipStream_t s, const CkMatern* blk, int metric, 
                                 const double* pc, int64_t mpad, const double* sc, const double* z, CkLayout L,
                                 const CkLocalSys* sys, int n_sys, double* slab, const CkTable* tabs,
                                 const double* const* coefs, int use_tab, const double* su, const double* pu,
-                                const double* cb, double cmax, int* k0buf, const double* nz) {
+                                const double* cb, double cmax, int* k0buf, const double* nz, CkLocalCap cap) {
     if (n_sys <= 0) return;
     const LpTab T{tabs, coefs, use_tab};
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax};
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp};
     k_local_search_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L, sys,
                                                                     slab, T, su, pu, R, k0buf);
     const int nreg = L.nend > L.n0p ? 3 : 1;               // a second process?
@@ -904,6 +1048,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve_u(const CkMatern* __rest
     const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
     const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;
     const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
+    const LpReach Q = lp_reach(R, p, max_dist);
     double* S = lu_lds;
     double* E = lu_lds + (LP_KL + nx) * LP_KL;
     int* idx = lidx;
@@ -912,9 +1057,9 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve_u(const CkMatern* __rest
     if (tid == 0) fail = 0;
     int base = 0, k0 = 0;
     for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
-        if (lp_chunk_far(R, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
+        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
         const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, max_dist, L, g, p0, p1, p2, s0, s1, s2);
+        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2);
         const unsigned long long bal = __ballot(f), bal0 = __ballot(f && g < L.n0p);
         const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
         if (lane == 0) {
@@ -1002,10 +1147,10 @@ void ck_launch_local_solve_u(hipStream_t s, const CkMatern* blk, int metric, int
                              const double* pc, int64_t m, int64_t mpad, const double* sc, const double* z, CkLayout L,
                              const int* counts, double c0var, double* pred, double* err, const CkTable* tabs,
                              const double* const* coefs, int use_tab, const double* su, const double* pu, int k_hi,
-                             const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status, const double* nz) {
+                             const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status, const double* nz, CkLocalCap cap) {
     if (m <= 0) return;
     const LpTab T{tabs, coefs, use_tab};
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax};
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp};
     const int np = Tr.p0 + Tr.p1;
     const size_t lds = (size_t)((LP_KL + 2 + np) * LP_KL + LU_EXTRA(np)) * sizeof(double);   // 34.9 KB (p = 2) .. 47.2 KB (p = 16)
     k_local_solve_u<<<dim3((unsigned)m), dim3(LP_TPB), lds, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L, counts,

@@ -74,6 +74,8 @@ _PROTOS = {
     "ck_predict_local": [c_void_p, c_int, _dp, c_int64, c_double, c_int, _dp, _dp, POINTER(c_int64), POINTER(c_int64),
                          POINTER(c_int64)],
     "ck_local_reserve": [c_void_p, c_int64],
+    "ck_set_local_neighbours": [c_void_p, c_int64, c_int64],
+    "ck_debug_local_neighbours": [c_void_p, c_int, _dp, c_int64, c_double, c_int, POINTER(c_int32), _dp],
     "ck_predict_local_universal": [c_void_p, c_int, _dp, c_int64, _dp, c_double, c_int, _dp, _dp, _dp, POINTER(c_int64),
                                    POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
     "ck_vario_begin": [c_void_p, _dp, _dp, c_int64, _dp, _dp, c_int64, c_int],
@@ -631,6 +633,20 @@ class Handle:
         keys = ["count_ms", "factor_ms", "reduce_ms", "total_ms", "n_lds", "n_tiled"]
         return dict(zip(keys, out[48:54].tolist()))
 
+    def set_local_neighbours(self, n0: int, n1: int = 0):
+        """Nearest-neighbour cap per process of the local predictor (include/cokrige.h: ck_set_local_neighbours); 0 = none."""
+        _chk(lib().ck_set_local_neighbours(self._h, int(n0), int(n1)))
+
+    def local_neighbours(self, i, pcoords, max_dist=1e3, cv=False):
+        """(count, rcut), both (m, 2): per point and process the number of neighbours under the handle's caps and the cut
+        distance r_pq (include/cokrige.h: ck_debug_local_neighbours)."""
+        pc = _f64(pcoords, 2)
+        m = pc.shape[0]
+        count, rcut = np.zeros((m, 2), dtype=np.int32), np.zeros((m, 2))
+        _chk(lib().ck_debug_local_neighbours(self._h, int(i), _p(pc), m, float(max_dist), int(bool(cv)),
+                                             count.ctypes.data_as(POINTER(c_int32)), _p(rcut)))
+        return count, rcut
+
     def local_reserve(self, nbytes: int = 0):
         """Pre-size the scratch slab of predict_local (0: the automatic budget) -- include/cokrige.h: ck_local_reserve."""
         _chk(lib().ck_local_reserve(self._h, int(nbytes)))
@@ -755,14 +771,17 @@ class Handle:
         return out, grid
 
     def timings(self):
-        out = np.zeros(23)
-        _chk(lib().ck_timings(self._h, _p(out), 23))
+        out = np.zeros(64)
+        _chk(lib().ck_timings(self._h, _p(out), 64))
+        # the neighbour cap of the local predictor (ck_set_local_neighbours): slots [60 ..]
+        out = np.concatenate([out[:23], out[60:64]])
         keys = ["assemble_sigma_ms", "factor_ms", "assemble_aux_ms", "solve_ms", "reduce_ms", "syrk_ms",
                 "syrk_launches", "aux_gemm_ms", "aux_gemm_launches", "vario_bin_ms", "local_ms", "verify_ms",
                 "panel_coop_redone", "fused_sweeps_ms", "local_alloc_ms", "tall_union_ms",
                 # ck_predict_blocks
                 "blocks_assemble_ms", "blocks_fold_ms", "blocks_prior_ms", "blocks_solve_ms", "blocks_reduce_ms",
-                "blocks_total_ms", "blocks_chunks"]
+                "blocks_total_ms", "blocks_chunks",
+                "local_select_ms", "local_n_capped", "local_cand_max", "local_n_rescan"]
         return dict(zip(keys, out.tolist()))
 
     def dev_gemm_nt(self, C_ptr, ldc, A_ptr, lda, B_ptr, ldb, M, N, K, lower=False):

@@ -13,7 +13,9 @@ Differences from the reference, none in the arithmetic:
   * the reference warns once per affected point (:219-221, 230-232); here one warning per
     call and kind, carrying the number of points;
   * ``trend=`` (not in the reference): ordinary / universal cokriging in the moving neighbourhood -- the unknown mean is
-    estimated by GLS in every neighbourhood and its uncertainty is part of ``pred_err``.
+    estimated by GLS in every neighbourhood and its uncertainty is part of ``pred_err``;
+  * ``max_neighbours=`` (not in the reference): a nearest-neighbour cap per process inside ``max_dist``, so that the radius
+    can be chosen for coverage of sparse regions instead of for cost.
 """
 from __future__ import annotations
 
@@ -31,11 +33,27 @@ from .noise import apply_noise, resolve_measurement_error
 from .trend import TrendDesign, check_trend
 
 
+def check_max_neighbours(max_neighbours, n_procs):
+    """None, an int (every process) or one int per process -> a pair of caps (0 = none), or None."""
+    if max_neighbours is None:
+        return None
+    vals = [max_neighbours] * n_procs if np.isscalar(max_neighbours) else list(max_neighbours)
+    if len(vals) != n_procs:
+        raise ValueError(f"max_neighbours needs one value per process ({n_procs}), got {len(vals)}")
+    for v in vals:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"max_neighbours must be integers, got {v!r}")
+        if v < 0:
+            raise ValueError(f"max_neighbours must be >= 0 (0 = no cap), got {v!r}")
+    return tuple(int(v) for v in vals) + (0,) * (2 - n_procs)
+
+
 class Predictor:
     """Multivariate prediction framework (src/point_prediction.py:21-43)."""
 
     def __init__(self, mod, mf, covariates=None, dist_units: str = "km", fast_dist: bool = True, device: int = 0,
-                 devices=None, reserve_scratch=None, trend=None, measurement_error=None, noise_scale=(1.0, 1.0)):
+                 devices=None, reserve_scratch=None, trend=None, measurement_error=None, noise_scale=(1.0, 1.0),
+                 max_neighbours=None):
         """``devices=[0, 1, ...]``: the prediction points are sharded over one worker process per GPU (observations
         replicated, no exchange inside the computation) -- what ``partitions`` is to the reference's CPU pool
         (src/point_prediction.py:45-52, 69-81).
@@ -47,7 +65,13 @@ class Predictor:
         ``trend_coef`` holds the (m, p) local coefficients.
 
         ``measurement_error`` / ``noise_scale``: as for the joint predictor -- every neighbour's ``noise_scale[k] * d_a``
-        goes on the diagonal of its local system (include/cokrige.h: ck_set_noise).  Single-device only."""
+        goes on the diagonal of its local system (include/cokrige.h: ck_set_noise).  Single-device only.
+
+        ``max_neighbours``: None, an int (applies to every process) or one int per process: of the sites of a process within
+        ``max_dist`` only the nearest so many are used -- with every site tied at the cut distance, so a neighbourhood may hold
+        a few more (include/cokrige.h: ck_set_local_neighbours); 0 = no cap for that process.  The cap is per process because
+        the denser process would otherwise crowd the other out of the list.  After a call ``info["n_capped"]`` is the number
+        of points where a cap was binding.  Single-device only."""
         if mod.n_procs != mf.n_procs:
             raise ValueError("Number of theoretical processes different from empirical processes.")
         self.measurement_error, self.noise_scale = measurement_error, noise_scale
@@ -56,6 +80,9 @@ class Predictor:
         if self.trend is not None and devices is not None and len(devices) > 1:
             raise NotImplementedError("universal cokriging (trend=...) runs on one device; the multi-GPU path is simple "
                                       "cokriging only")
+        self.max_neighbours = check_max_neighbours(max_neighbours, mod.n_procs)
+        if self.max_neighbours is not None and devices is not None and len(devices) > 1:
+            raise NotImplementedError("the neighbour cap (max_neighbours=...) runs on one device; the multi-GPU path has none")
         self.trend_coef = None
         self.n_procs = mod.n_procs
         self.mod, self.mf, self.covariates = mod, mf, covariates
@@ -120,6 +147,12 @@ class Predictor:
             self._pool_key = key
         return self._pool.predict_local(i, pcoords, max_dist=max_dist, cv=self.cv)
 
+    def _capped_handle(self):
+        """The handle with this predictor's neighbour cap on it (set before every local call: it is handle state)."""
+        h = self._handle()
+        h.set_local_neighbours(*(self.max_neighbours or (0, 0)))
+        return h
+
     def _predict_universal(self, i, pcoords, max_dist):
         """The regressors of the data and the prediction sites are validated on the host, then set on the handle (a new
         trend needs no new device state)."""
@@ -130,7 +163,7 @@ class Predictor:
         F = [design.data(k, coords[k]) for k in range(self.n_procs)]
         pc = np.ascontiguousarray(np.atleast_2d(np.asarray(pcoords, dtype=np.float64))[:, :2])
         F0 = design(i, pc)
-        h = self._handle()
+        h = self._capped_handle()
         for k in range(self.n_procs):
             h.set_trend(k, F[k])
         pred, err, info = h.predict_local_universal(i, pc, F0, max_dist=max_dist, cv=self.cv, want_beta=True)
@@ -143,7 +176,8 @@ class Predictor:
         elif self.devices is not None and len(self.devices) > 1:
             pred, err, info = self._predict_on_ranks(i, pcoords, max_dist)
         else:
-            pred, err, info = self._handle().predict_local(i, pcoords, max_dist=max_dist, cv=self.cv)
+            pred, err, info = self._capped_handle().predict_local(i, pcoords, max_dist=max_dist, cv=self.cv)
+        info["n_capped"] = int(self._h.timings()["local_n_capped"]) if self.max_neighbours is not None else 0
         self.info = info
         if info["n_empty"]:
             warnings.warn(f"No data within maximum distance {max_dist} at {info['n_empty']} location(s).")
