@@ -285,6 +285,26 @@ int ck_set_noise(ck_handle* h, int k, const double* var_host, int64_t n_k, doubl
  * ck_assemble_joint. */
 int ck_loglik_noise_grad(ck_handle* h, double* out2);
 
+/* Expected (Fisher) information of the likelihood at the model's parameters:
+ *     I_jk = 1/2 tr(Sigma^-1 D_j Sigma^-1 D_k),   D_k = dSigma / dtheta_k      (reml != 0: P = Sigma^-1 - H A^-1 H^T in place of
+ *     Sigma^-1, H = Sigma^-1 X, A = X^T Sigma^-1 X, with the trend of ck_set_trend),
+ * exact (no trace estimation) and positive semi-definite.  Slots: the 11 model parameters in ck_loglik's flat order (one process:
+ * the first 4), then the measurement-noise scales s_0, s_1 of ck_set_noise (D = diag(d_a) on that process): CK_FISHER_NPAR = 13.
+ * A slot is live when the parameter exists (s_k: process k has variances) and free13[slot] != 0 (NULL: all); fisher_host (13 x
+ * 13, row-major) is 0 in the rows and columns of the others and symmetric to the bit.  D_k is, entry for entry, the matrix
+ * whose contraction with G gives ck_loglik's gradient (the same evaluator, distance and h == 0 test).  Fixed-order reductions,
+ * no atomics: repeated calls give the same bits.
+ * Preconditions and refusals as ck_loglik (assembled, single-process form).  The call factors if no factor is resident; info
+ * != 0 (Sigma not positive definite): fisher_host is NaN and the handle needs ck_assemble_joint again.  On the device it needs
+ * what ck_loglik's gradient needs, Sigma^-1 in full (Npad^2 doubles), the derivative operands (about 3.5 Npad^2 doubles for
+ * two processes) and their products with Sigma^-1 (about 7 Npad^2); when the products do not fit at once they are formed in
+ * groups, and the call refuses, stating the bytes needed and available, when two of them do not fit.  About 7 N^3 flop on the
+ * FP64 matrix pipe for two processes of equal size with every parameter live.  Afterwards the factor stays resident (ck_predict
+ * gives the same bits as without the call) and the handle is in ck_loglik's state.  ck_timings [64 ..]: derivative assembly,
+ * products, contraction, total (ms), the flop of the products, the number of groups. */
+#define CK_FISHER_NPAR 13
+int ck_loglik_fisher(ck_handle* h, int reml, const int32_t* free13, double* fisher_host, int64_t* info);
+
 /* Simulation draw z = L eps in the caller's stacked order (process 0 sites, then process 1):
  * sim.BivariateRandomField._simulate (src/sim.py:52-54: cholesky(cmat, lower=True) @ noise).
  * n = number of observations; needs ck_factor. */
@@ -622,6 +642,8 @@ int ck_table_fallbacks(ck_handle* h, int reset, int64_t* count);
  * on (N = 40 000: 0.62 -> 0.56 ms), Sigma (K1) never (faster on one box, slower on another);
  * "draw_chunk" (default 0 = automatic: half of the free device memory, 128 .. 8192 draws): draws per product launch of
  * ck_conditional_draws;
+ * "fisher_product_mb" (default 0 = automatic: what is free beside everything else the call holds): MiB the stored products of
+ * ck_loglik_fisher may take -- less than all of them and they are formed in groups (the same bits);
  * "block_chunk" (default 0 = automatic: what the arena has left, or half of the free device memory, beside the point rows
  * the handle holds): prediction sites per K2 assembly of ck_predict_blocks;
  * "local_slab_mb" = scratch budget of ck_predict_local in MiB (0, default: a quarter of the free memory, at most

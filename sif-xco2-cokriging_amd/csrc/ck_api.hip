@@ -33,7 +33,7 @@
 #include "ck_model.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 64
+#define CK_N_TIMINGS 72
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -293,6 +293,8 @@ struct ck_handle {
     bool lik_noise_valid = false;            // ... since the last ck_assemble_joint
     int aux_trend = 0;   // trend rows behind the data row of the right-hand sides being assembled (rows m + 1 .. m + aux_trend)
     int loo_dense = 1;   // rows in front of the unit rows in the leave-one-out / likelihood layout (ck_loglik_reml: 1 + p)
+    int64_t fisher_product_mb = 0;    // option "fisher_product_mb": room of ck_loglik_fisher's stored products (0: what is free)
+    std::vector<double> fi_A, fi_H;   // ck_loglik_fisher (REML): A = X^T Sigma^-1 X (p x p) and H = Sigma^-1 X (Npad x p) of its sweep
 
     ~ck_handle() {   // events and streams; the buffers release themselves
         for (auto& e : gemm_ev) {
@@ -2923,8 +2925,10 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
 // the first 1 + p rows, alpha_q = W_q . y and B_q = U^T W_q (= (Sigma^-1 X)_q) over the unit rows.  The host forms beta, log|A|,
 // b^T A^-1 b, alpha_R = alpha - B beta and C = B R^-T (A = R R^T); k_ginv_syrk_d starts from the rank-(1 + p) term
 // alpha_R alpha_R^T + C C^T.  p = 0 is ck_loglik's path, bit for bit.
-static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, double* grad, int64_t* info) {
-    const char* name = reml ? "ck_loglik_reml" : "ck_loglik";
+// fisher (ck_loglik_fisher): the same sweep and reductions, but G starts from zero (G = -Sigma^-1), no contraction follows, and
+// A and H = Sigma^-1 X of the REML reduction are kept on the handle.
+static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, double* grad, int64_t* info, bool fisher = false) {
+    const char* name = fisher ? "ck_loglik_fisher" : reml ? "ck_loglik_reml" : "ck_loglik";
     if (!out || !info || (want_grad && !grad)) return fail(std::string(name) + ": null argument");
     if (h->world != 1)
         return fail(std::string(name) + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) +
@@ -3035,6 +3039,12 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
             return fail(std::string(name) + ": the trend design is rank deficient: " + trend_column_name(h, bad - 1) +
                         " is, to rounding, a combination of the regressors in front of it (X^T Sigma^-1 X is singular)");
         quad = W[1] - bAb;   // z^T P z = |y|^2 - b^T A^-1 b
+        if (fisher) {
+            h->fi_A = A;
+            h->fi_H.assign((size_t)(Np * p), 0.0);
+            for (int64_t r = 0; r < Np && want_grad; ++r)
+                for (int j = 0; j < p; ++j) h->fi_H[(size_t)(r * p + j)] = W[(size_t)((q + r) * (q + 1) + 2 + j)];
+        }
     }
     out3[1] = logdet;
     if (reml) {
@@ -3048,7 +3058,14 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
     if (want_grad) {
         // ---- G = alpha alpha^T - Sigma^-1 (REML: alpha_R alpha_R^T + C C^T - Sigma^-1), lower tiles of the first nend rows
         const double* avec = h->d_pred + 1;
-        if (p > 0) {
+        int q_syrk = q;
+        if (fisher) {   // zero start; with trend rows in front of the unit rows the rank-q kernel (it reads `dense`)
+            q_syrk = p > 0 ? 2 : 1;
+            double* d_zero = nullptr;
+            HIPCHK(tmp.get(&d_zero, (size_t)(q_syrk * Np) * 8));
+            HIPCHK(hipMemsetAsync(d_zero, 0, (size_t)(q_syrk * Np) * 8, h->stream));
+            avec = d_zero;
+        } else if (p > 0) {
             std::vector<double> av((size_t)q * Np, 0.0);
             for (int64_t r = 0; r < Np; ++r) {
                 const double* wr = &W[(size_t)((q + r) * (q + 1))];   // unit row of internal position r
@@ -3068,9 +3085,15 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
         }
         if (schur_ensure(h, Np)) return -1;
         HIPCHK(hipEventRecord(h->ev0, h->stream));
-        ck_launch_ginv_syrk(h->stream, h->sch.d_ptr, h->aux, h->mpad, avec, h->nK, h->nend, q, Np, q);
+        ck_launch_ginv_syrk(h->stream, h->sch.d_ptr, h->aux, h->mpad, avec, h->nK, h->nend, q_syrk, Np, q);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev1, h->stream));
+        if (fisher) {
+            HIPCHK(hipStreamSynchronize(h->stream));
+            h->t_ms[27] = elapsed_ms(h->ev0, h->ev1);
+            h->t_ms[29] = ms_since(t_begin);
+            return 0;
+        }
         // ---- the contraction: the model's blocks and their nu +- dnu, nu +- 2 dnu neighbours
         const int nblk = h->n_procs == 1 ? 1 : 3;
         CkMatern hb[15];
@@ -3140,6 +3163,288 @@ extern "C" int ck_loglik_noise_grad(ck_handle* h, double* out2) {
                     "last ck_assemble_joint");
     out2[0] = h->lik_noise_grad[0];
     out2[1] = h->lik_noise_grad[1];
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// Fisher information of the likelihood fit (ck_fisher.hip)
+// ---------------------------------------------------------------------------------------
+// I_jk = 1/2 tr(Sigma^-1 D_j Sigma^-1 D_k) in the plain form.  loglik_impl's sweep leaves -Sigma^-1 in the Schur buffers (zero
+// start); it is expanded to full K-panels, the derivative operands (ck_internal.h: CK_FOP_*) are assembled as the product
+// kernel's second operand, B_a = -Sigma^-1 D_a runs on the trailing updates' tile restricted to the operand's block (N^3 / 2
+// flop for an operand inside one process of a half-and-half model, N^3 for a cross operand), and one contraction kernel takes
+// all wanted pairs to per-workgroup partial sums.  The products of all operands are kept when they fit; otherwise the operands
+// are cut into groups of at most half the free memory, and the pairs across two groups are contracted with the later group's
+// products formed again (memory first: the need is computed in front of the first allocation).
+struct FisherUnit {
+    int op, r, kp;   // operand, process of its columns, process of its K-panels
+    int64_t d_doubles;
+};
+extern "C" int ck_loglik_fisher(ck_handle* h, int reml, const int32_t* free13, double* fisher, int64_t* info) {
+    CHKH(h);
+    const char* name = "ck_loglik_fisher";
+    if (!fisher || !info) return fail(std::string(name) + ": null argument");
+    if (h->world != 1)
+        return fail(std::string(name) + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) +
+                    "); the multi-GPU likelihood is not available");
+    if (!h->assembled) return fail(std::string(name) + ": ck_assemble_joint has not been called");
+    const auto t_begin = std::chrono::steady_clock::now();
+    const int NP = CK_FISHER_NPAR, NO = CK_FISHER_NOPS;
+    *info = 0;
+    for (int k = 0; k < NP * NP; ++k) fisher[k] = NAN;
+    const int64_t Np = h->Npad;
+    const int nK = h->nK;
+    const int p = reml ? trend_total(h) : 0;
+    // ---- live slots and the operands they need
+    unsigned char live[CK_FISHER_NPAR] = {};
+    const int npar = h->n_procs == 1 ? 4 : CK_LIK_NPAR;
+    for (int k = 0; k < npar; ++k) live[k] = 1;
+    if (!h->noise_var[0].empty()) live[11] = 1;
+    if (h->n_procs == 2 && !h->noise_var[1].empty()) live[12] = 1;
+    if (free13)
+        for (int k = 0; k < NP; ++k) live[k] = live[k] && free13[k] != 0;
+    double coef[CK_FISHER_NPAR * CK_FISHER_NOPS];
+    ck_host_fisher_coef(h->n_procs, h->par_sigma[0], h->par_sigma[1], h->par_rho, coef);
+    bool op_live[CK_FISHER_NOPS] = {};
+    for (int k = 0; k < NP; ++k)
+        for (int a = 0; a < NO; ++a)
+            if (live[k] && coef[k * NO + a] != 0.0) op_live[a] = true;
+    // ---- geometry of the units: columns (c0, wpad, nlo, nhi) and K-panels (pK0, npan) of process 0 / 1
+    int64_t c0[2] = {0, 0}, wpad[2] = {Np, 0}, nlo[2] = {0, 0}, nhi[2] = {Np, 0};
+    int pK0[2] = {0, 0}, npan[2] = {nK, 0};
+    if (h->n_procs == 2) {
+        wpad[0] = roundup(h->n0p, 128), nhi[0] = h->n0p, npan[0] = (int)((h->n0p + CK_NB - 1) / CK_NB);
+        c0[1] = h->n0p / 128 * 128, wpad[1] = Np - c0[1], nlo[1] = h->n0p, nhi[1] = Np;
+        pK0[1] = (int)(h->n0p / CK_NB), npan[1] = nK - pK0[1];
+    }
+    std::vector<FisherUnit> units;
+    int64_t b_doubles[CK_FISHER_NOPS] = {};
+    int64_t d_total = 0, b_total = 0, b_max = 0;
+    for (int a = 0; a < CK_FOP_DIAG0; ++a) {
+        if (!op_live[a]) continue;
+        if (a < CK_FOP_R01) {
+            const int r = a < CK_FOP_R11 ? 0 : 1;
+            units.push_back({a, r, r, (int64_t)npan[r] * wpad[r] * CK_NB});
+            b_doubles[a] = Np * wpad[r];
+        } else {
+            units.push_back({a, 0, 1, (int64_t)npan[1] * wpad[0] * CK_NB});
+            units.push_back({a, 1, 0, (int64_t)npan[0] * wpad[1] * CK_NB});
+            b_doubles[a] = Np * Np;
+        }
+        b_total += b_doubles[a];
+        b_max = std::max(b_max, b_doubles[a]);
+    }
+    for (const auto& u : units) d_total += u.d_doubles;
+    // ---- memory, in front of the first allocation: what loglik_impl's gradient path takes (as it computes it), Sigma^-1, the
+    // operands, the thin REML terms and the partial sums are needed whole; the products in as many groups as fit
+    const int64_t ngr = ck_fisher_contract_groups(Np);
+    const int64_t thin = p > 0 ? ((int64_t)nK * CK_FISHER_YROWS * CK_NB + Np * CK_FISHER_YROWS + Np * p + CK_FISHER_YROWS * (CK_FISHER_YROWS + p)) : 0;
+    const int64_t fixed_bytes = (Np * Np + d_total + thin + ngr * CK_FISHER_NPAIR + 2 * Np) * 8 + (1 << 20);
+    int64_t lik_bytes = 0;
+    {
+        int64_t g_bytes = 0;
+        for (int J = 0; J < nK; ++J) g_bytes += ((Np - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;
+        const int64_t aux_bytes = roundup(Np + 1 + p, CK_AUX_ALIGN) * Np * 8;
+        lik_bytes = (aux_bytes > aux_cap(h) * 8 ? aux_bytes : 0) + (h->sch.M == Np ? 0 : g_bytes);
+    }
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    int64_t avail = (int64_t)fr;
+    if (!h->arena && roundup(Np + 1 + p, CK_AUX_ALIGN) * Np > aux_cap(h)) avail += aux_cap(h) * 8;
+    if (h->sch.M != Np)
+        for (int J = 0; J < (int)h->sch.sig.size(); ++J) avail += ((h->sch.M - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;
+    int64_t room = avail - lik_bytes - fixed_bytes;
+    if (h->fisher_product_mb > 0 && room > 0) room = std::min(room, h->fisher_product_mb << 20);
+    std::vector<std::vector<int>> groups(1);
+    int64_t region = b_total;
+    if (b_total * 8 > room) {
+        region = room / 16;   // two regions of products, doubles each
+        if (room < 0 || b_max > region)
+            return fail(std::string(name) + ": needs " + std::to_string(lik_bytes + fixed_bytes + 2 * b_max * 8) +
+                        " bytes of device memory (" + std::to_string(lik_bytes) + " for the unit-row sweep and Sigma^-1's triangle, " +
+                        std::to_string(Np * Np * 8) + " for Sigma^-1 in full, " + std::to_string(d_total * 8) + " for " +
+                        std::to_string(units.size()) + " derivative operands, " + std::to_string(2 * b_max * 8) +
+                        " for two of their products); " + std::to_string(avail) + " bytes are available");
+        int64_t used = 0, big = 0;
+        for (int a = 0; a < CK_FOP_DIAG0; ++a) {
+            if (!op_live[a]) continue;
+            if (used + b_doubles[a] > region && !groups.back().empty()) {
+                groups.emplace_back();
+                used = 0;
+            }
+            groups.back().push_back(a);
+            used += b_doubles[a];
+            big = std::max(big, used);
+        }
+        region = big;
+    } else {
+        for (int a = 0; a < CK_FOP_DIAG0; ++a)
+            if (op_live[a]) groups.back().push_back(a);
+    }
+    // ---- the sweep: factor, unit rows, -Sigma^-1 in the Schur buffers (and A, H of REML)
+    double out4[4], gdummy[CK_LIK_NPAR];
+    if (loglik_impl(h, 1, reml != 0, out4, gdummy, info, true)) return -1;
+    for (int k = 64; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    if (*info != 0) {
+        h->t_ms[67] = ms_since(t_begin);
+        return 0;
+    }
+    CallGuard guard(h, AUX_LOGLIK, true);
+    const CkLayout L = layout_of(h);
+    DevTemps tmp;
+    if (ensure_noise(h)) return -1;
+    double *d_Sp = nullptr, *d_part = nullptr, *d_reg[2] = {nullptr, nullptr};
+    HIPCHK(tmp.get(&d_Sp, (size_t)(Np * Np) * 8));
+    HIPCHK(tmp.get(&d_part, (size_t)(ngr * CK_FISHER_NPAIR) * 8));
+    std::vector<double*> d_D(units.size(), nullptr);
+    for (size_t u = 0; u < units.size(); ++u) {
+        HIPCHK(tmp.get(&d_D[u], (size_t)units[u].d_doubles * 8));
+        HIPCHK(hipMemsetAsync(d_D[u], 0, (size_t)units[u].d_doubles * 8, h->stream));
+    }
+    if (region > 0) HIPCHK(tmp.get(&d_reg[0], (size_t)region * 8));
+    if (groups.size() > 1) HIPCHK(tmp.get(&d_reg[1], (size_t)region * 8));
+    // ---- Sigma^-1 in full; the operands
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    ck_launch_fisher_expand(h->stream, h->sch.d_ptr, L, d_Sp);
+    HIPCHK(hipGetLastError());
+    CkFisherAsm A = {};
+    for (int r = 0; r < 2; ++r) A.c0[r] = c0[r], A.wpad[r] = wpad[r], A.pK0[r] = pK0[r];
+    for (size_t u = 0; u < units.size(); ++u) A.D[units[u].op][units[u].r] = d_D[u];
+    if (!units.empty()) {
+        const int nblk = h->n_procs == 1 ? 1 : 3;
+        CkMatern hb[15];
+        double dnu3[3] = {0.0, 0.0, 0.0};
+        const double offs[4] = {-2.0, -1.0, 1.0, 2.0};
+        for (int b = 0; b < 3; ++b) {   // the blocks and their nu +- dnu, nu +- 2 dnu neighbours, as loglik_impl prepares them
+            const CkMatern& m = h->blk[b < nblk ? b : 0];
+            dnu3[b] = ck_matern_dnu_step(m.nu);
+            hb[5 * b] = m;
+            for (int k = 0; k < 4; ++k) ck_matern_prepare(m.nu + offs[k] * dnu3[b], m.len_scale, m.amp, m.nugget, &hb[5 * b + 1 + k]);
+        }
+        HIPCHK(h->d_lik_blk.reserve(sizeof(hb) / sizeof(CkMatern)));
+        HIPCHK(hipMemcpyAsync(h->d_lik_blk, hb, sizeof(hb), hipMemcpyHostToDevice, h->stream));
+        ck_launch_fisher_assemble(h->stream, A, L, h->n_procs, h->metric, h->s0, h->d_lik_blk, dnu3);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(h->stream));   // (hb is stack memory)
+    }
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->t_ms[64] = elapsed_ms(h->ev0, h->ev1);
+    // ---- products and contraction, group by group
+    const CkFisherCtx X{d_Sp, h->d_noise ? h->d_noise + Np : nullptr, Np, h->n_procs == 2 ? h->n0p : Np, h->n_procs};
+    double T[CK_FISHER_NOPS * CK_FISHER_NOPS] = {};
+    double flop = 0.0;
+    CkFisherOp desc[CK_FISHER_NOPS] = {};
+    for (int k = 0; k < 2; ++k)
+        if (op_live[CK_FOP_DIAG0 + k]) desc[CK_FOP_DIAG0 + k] = CkFisherOp{nullptr, 0, 0, 0, CK_FOPK_DIAG0 + k};
+    auto form = [&](const std::vector<int>& g, double* reg) -> int {   // the products of a group into a region
+        int64_t off = 0;
+        for (int a : g) {
+            double* B = reg + off;
+            off += b_doubles[a];
+            HIPCHK(hipMemsetAsync(B, 0, (size_t)b_doubles[a] * 8, h->stream));
+            const bool cross = a >= CK_FOP_R01;
+            const int r0 = a < CK_FOP_R11 ? 0 : 1;
+            desc[a] = cross ? CkFisherOp{B, Np, 0, Np, CK_FOPK_DENSE} : CkFisherOp{B, wpad[r0], c0[r0], wpad[r0], CK_FOPK_DENSE};
+            for (size_t u = 0; u < units.size(); ++u) {
+                if (units[u].op != a) continue;
+                const int r = units[u].r, kp = units[u].kp;
+                ck_launch_fisher_prod(h->stream, cross ? B + c0[r] : B, cross ? Np : wpad[r], d_Sp, Np, d_D[u], wpad[r], pK0[kp],
+                                      npan[kp]);
+                flop += 2.0 * (double)Np * (double)wpad[r] * (double)npan[kp] * CK_NB;
+            }
+        }
+        HIPCHK(hipGetLastError());
+        return 0;
+    };
+    std::vector<double> part((size_t)(ngr * CK_FISHER_NPAIR));
+    auto group_of = [&](int a) -> int {
+        for (size_t g = 0; g < groups.size(); ++g)
+            for (int x : groups[g])
+                if (x == a) return (int)g;
+        return 0;   // the diagonal operands ride with the first group
+    };
+    auto contract = [&](int ga, int gb) -> int {   // the pairs with one operand in group ga and the other in gb
+        CkFisherOps O = {};
+        bool any = false;
+        for (int a = 0; a < NO; ++a) {
+            O.op[a] = desc[a];
+            if (!op_live[a]) continue;
+            for (int b = a; b < NO; ++b) {
+                if (!op_live[b]) continue;
+                const int x = group_of(a), y = group_of(b);
+                if ((x == ga && y == gb) || (x == gb && y == ga)) O.mask[a] |= 1u << b, any = true;
+            }
+        }
+        if (!any) return 0;
+        ck_launch_fisher_contract(h->stream, O, X, d_part);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(part.data(), d_part, part.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (int a = 0; a < NO; ++a)
+            for (int b = a; b < NO; ++b) {
+                if (!((O.mask[a] >> b) & 1u)) continue;
+                double s = 0.0;
+                for (int64_t w = 0; w < ngr; ++w) s += part[(size_t)(w * CK_FISHER_NPAIR + b * (b + 1) / 2 + a)];
+                T[a * NO + b] = T[b * NO + a] = 0.5 * s;
+            }
+        return 0;
+    };
+    auto timed = [&](int slot, auto fn) -> int {
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        if (fn()) return -1;
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->t_ms[slot] += elapsed_ms(h->ev0, h->ev1);
+        return 0;
+    };
+    for (int ga = 0; ga < (int)groups.size(); ++ga) {
+        if (timed(65, [&]() { return form(groups[(size_t)ga], d_reg[0]); })) return -1;
+        if (timed(66, [&]() { return contract(ga, ga); })) return -1;
+        for (int gb = ga + 1; gb < (int)groups.size(); ++gb) {
+            if (timed(65, [&]() { return form(groups[(size_t)gb], d_reg[1]); })) return -1;
+            if (timed(66, [&]() { return contract(ga, gb); })) return -1;
+        }
+    }
+    // ---- REML: the thin terms Y_a = D_a H, V = Sigma^-1 Y, K = Y^T V, Gm = Y^T H and the p x p algebra on the host
+    if (p > 0) {
+        double *d_H = nullptr, *d_Yp = nullptr, *d_V = nullptr, *d_K = nullptr;
+        const int64_t yp_doubles = (int64_t)nK * CK_FISHER_YROWS * CK_NB;
+        HIPCHK(tmp.get(&d_H, (size_t)(Np * p) * 8));
+        HIPCHK(tmp.get(&d_Yp, (size_t)yp_doubles * 8));
+        HIPCHK(tmp.get(&d_V, (size_t)(Np * CK_FISHER_YROWS) * 8));
+        HIPCHK(tmp.get(&d_K, (size_t)(CK_FISHER_YROWS * (CK_FISHER_YROWS + p)) * 8));
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        HIPCHK(hipMemcpyAsync(d_H, h->fi_H.data(), (size_t)(Np * p) * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemsetAsync(d_Yp, 0, (size_t)yp_doubles * 8, h->stream));
+        HIPCHK(hipMemsetAsync(d_V, 0, (size_t)(Np * CK_FISHER_YROWS) * 8, h->stream));
+        for (size_t u = 0; u < units.size(); ++u) {
+            const int r = units[u].r, kp = units[u].kp;
+            const CkFisherUnit U{d_D[u], c0[r], wpad[r], nlo[r], nhi[r], pK0[kp], npan[kp]};
+            ck_launch_fisher_dh(h->stream, U, d_H, p, units[u].op * p, d_Yp);
+        }
+        for (int k = 0; k < 2; ++k)
+            if (op_live[CK_FOP_DIAG0 + k])
+                ck_launch_fisher_dh_diag(h->stream, L, h->n_procs, k, X.d, d_H, p, (CK_FOP_DIAG0 + k) * p, d_Yp);
+        ck_launch_fisher_prod(h->stream, d_V, CK_FISHER_YROWS, d_Sp, Np, d_Yp, CK_FISHER_YROWS, 0, nK);
+        flop += 2.0 * (double)Np * CK_FISHER_YROWS * (double)Np;
+        ck_launch_fisher_ytv(h->stream, d_Yp, Np, d_V, CK_FISHER_YROWS, CK_FISHER_YROWS, d_K, CK_FISHER_YROWS);
+        double* d_Gm = d_K + CK_FISHER_YROWS * CK_FISHER_YROWS;
+        ck_launch_fisher_ytv(h->stream, d_Yp, Np, d_H, p, p, d_Gm, p);
+        HIPCHK(hipGetLastError());
+        std::vector<double> Kh((size_t)(CK_FISHER_YROWS * (CK_FISHER_YROWS + p)));
+        HIPCHK(hipMemcpyAsync(Kh.data(), d_K, Kh.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->t_ms[65] += elapsed_ms(h->ev0, h->ev1);
+        for (size_t k = 0; k < (size_t)(CK_FISHER_YROWS * CK_FISHER_YROWS); ++k) Kh[k] = -Kh[k];   // V holds -Sigma^-1 Y
+        if (ck_host_fisher_reml(p, NO, h->fi_A.data(), Kh.data(), CK_FISHER_YROWS, Kh.data() + CK_FISHER_YROWS * CK_FISHER_YROWS, T))
+            return fail(std::string(name) + ": X^T Sigma^-1 X did not factor");
+    }
+    ck_host_fisher_combine(coef, T, live, fisher);
+    h->t_ms[68] = flop;
+    h->t_ms[69] = (double)groups.size();
+    h->t_ms[67] = ms_since(t_begin);
     return 0;
 }
 
@@ -4304,6 +4609,11 @@ extern "C" int ck_set_option(ck_handle* h, const char* name, int64_t value) {
     if (!strcmp(name, "block_chunk")) {   // ck_predict_blocks: prediction sites per K2 assembly (0 = automatic)
         if (value < 0) return fail("block_chunk must be >= 0 (0 = automatic)");
         h->block_chunk = value;
+        return 0;
+    }
+    if (!strcmp(name, "fisher_product_mb")) {   // ck_loglik_fisher: MiB the stored products may take (0 = automatic)
+        if (value < 0) return fail("fisher_product_mb must be >= 0 (0 = automatic)");
+        h->fisher_product_mb = value;
         return 0;
     }
     if (!strcmp(name, "draw_chunk")) {   // ck_conditional_draws: draws per product launch (0 = automatic)

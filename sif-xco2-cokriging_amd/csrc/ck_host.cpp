@@ -470,6 +470,75 @@ int ck_host_gls(int p, const double* A, const double* b, double tol, double* R_o
 }
 
 // ---------------------------------------------------------------------------------------
+// Fisher information (ck_loglik_fisher): the operands' information -> the parameters'; the REML correction
+// ---------------------------------------------------------------------------------------
+void ck_host_fisher_coef(int n_procs, double sig1, double sig2, double rho, double* C) {
+    const int NP = CK_HOST_FISHER_NPAR, NO = CK_HOST_FISHER_NOPS;
+    for (int k = 0; k < NP * NO; ++k) C[k] = 0.0;
+    auto c = [&](int par, int op) -> double& { return C[par * NO + op]; };
+    if (n_procs == 1) {   // sigma nu len nugget | s_0
+        c(0, 0) = 2.0 * sig1;
+        c(1, 1) = 1.0;
+        c(2, 2) = 1.0;
+        c(3, 3) = 1.0;
+        c(11, 11) = 1.0;
+        return;
+    }
+    // sigma_11 sigma_22 nu_11 nu_12 nu_22 len_11 len_12 len_22 nugget_11 nugget_22 rho_12 | s_0 s_1
+    c(0, 0) = 2.0 * sig1, c(0, 8) = rho * sig2;
+    c(1, 4) = 2.0 * sig2, c(1, 8) = rho * sig1;
+    c(2, 1) = 1.0, c(3, 9) = 1.0, c(4, 5) = 1.0;
+    c(5, 2) = 1.0, c(6, 10) = 1.0, c(7, 6) = 1.0;
+    c(8, 3) = 1.0, c(9, 7) = 1.0;
+    c(10, 8) = sig1 * sig2;
+    c(11, 11) = 1.0, c(12, 12) = 1.0;
+}
+
+void ck_host_fisher_combine(const double* C, const double* T, const unsigned char* live, double* I) {
+    const int NP = CK_HOST_FISHER_NPAR, NO = CK_HOST_FISHER_NOPS;
+    for (int k = 0; k < NP * NP; ++k) I[k] = 0.0;
+    for (int j = 0; j < NP; ++j) {
+        if (!live[j]) continue;
+        for (int k = j; k < NP; ++k) {
+            if (!live[k]) continue;
+            double s = 0.0;
+            for (int a = 0; a < NO; ++a) {
+                if (C[j * NO + a] == 0.0) continue;
+                for (int b = 0; b < NO; ++b)
+                    if (C[k * NO + b] != 0.0) s += C[j * NO + a] * C[k * NO + b] * T[(a <= b ? a * NO + b : b * NO + a)];
+            }
+            I[j * NP + k] = I[k * NP + j] = s;
+        }
+    }
+}
+
+int ck_host_fisher_reml(int p, int nops, const double* A, const double* K, int64_t ldk, const double* Gm, double* T) {
+    if (p <= 0) return 0;
+    std::vector<double> Ai((size_t)p * p), zero((size_t)p, 0.0), W((size_t)nops * p * p);
+    const int bad = ck_host_gls(p, A, zero.data(), 0.0, nullptr, nullptr, Ai.data(), nullptr, nullptr);
+    if (bad) return bad;
+    for (int a = 0; a < nops; ++a)   // W_a = A^-1 (Y_a^T H)
+        for (int i = 0; i < p; ++i)
+            for (int j = 0; j < p; ++j) {
+                double s = 0.0;
+                for (int l = 0; l < p; ++l) s += Ai[(size_t)i * p + l] * Gm[((size_t)a * p + l) * p + j];
+                W[((size_t)a * p + i) * p + j] = s;
+            }
+    for (int a = 0; a < nops; ++a)
+        for (int b = a; b < nops; ++b) {
+            double t1 = 0.0, t2 = 0.0;
+            for (int i = 0; i < p; ++i)
+                for (int j = 0; j < p; ++j) {
+                    t1 += Ai[(size_t)i * p + j] * (K[((size_t)b * p + j) * ldk + (size_t)a * p + i] + K[((size_t)a * p + j) * ldk + (size_t)b * p + i]);
+                    t2 += W[((size_t)a * p + i) * p + j] * W[((size_t)b * p + j) * p + i];
+                }
+            const double v = T[a * nops + b] - 0.5 * t1 + 0.5 * t2;
+            T[a * nops + b] = T[b * nops + a] = v;
+        }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // leave-group-out cross-validation: members, gather list, tile map and system offsets of the folds
 // ---------------------------------------------------------------------------------------
 int ck_host_fold_plan(int i, int n_procs, const int64_t n[2], int64_t n0p, const int64_t* perm0, const int64_t* perm1,

@@ -88,6 +88,23 @@ CK_HIDDEN void ck_host_vario_fix(int metric, const double* ci, const double* cj,
 CK_HIDDEN int ck_host_gls(int p, const double* A, const double* b, double tol, double* R, double* beta, double* Ainv,
                           double* logdet, double* bAb);
 
+// ---- Fisher information (ck_api.hip: ck_loglik_fisher) -----------------------------------------------------------------
+// Parameter slots: the 11 model parameters in the flat order (one process: the first 4), then the noise scales s_0, s_1.
+// Operands (ck_internal.h: CK_FOP_*): 0 .. 3 = R, amp dR/dnu, amp dR/dlen, Z of block (0, 0); 4 .. 7 of block (1, 1); 8 .. 10 =
+// R, amp dR/dnu, amp dR/dlen of the cross block with its transpose; 11, 12 = diag(d_a) on process 0 / 1.
+#define CK_HOST_FISHER_NPAR 13
+#define CK_HOST_FISHER_NOPS 13
+// C[par NOPS + op]: dSigma/dtheta_par = sum_op C D_op  (D_sigma1 = 2 sigma1 R00 + rho sigma2 (R01 + R01^T), ...)
+CK_HIDDEN void ck_host_fisher_coef(int n_procs, double sig1, double sig2, double rho, double* C);
+// I = C T C^T over the live slots (T: NOPS x NOPS, the upper triangle is read), rows / columns of the others 0; symmetric to
+// the bit (I_kj is written from I_jk)
+CK_HIDDEN void ck_host_fisher_combine(const double* C, const double* T, const unsigned char* live, double* I);
+// REML: T_ab = 1/2 tr(P D_a P D_b) from the ML value 1/2 tr(Sigma^-1 D_a Sigma^-1 D_b) already in T (nops x nops, both
+// triangles written), P = Sigma^-1 - H A^-1 H^T:  T_ab -= 1/2 (tr(A^-1 K_ab) + tr(A^-1 K_ba)) - 1/2 tr(A^-1 G_a A^-1 G_b) with
+// K_ab = Y_a^T Sigma^-1 Y_b = K[(a p + i) ldk + b p + j], G_a = Y_a^T H = Gm[(a p + i) p + j], Y_a = D_a H.  A: p x p (lower
+// triangle read).  Returns 0, or 1 + the column at which A failed to factor.
+CK_HIDDEN int ck_host_fisher_reml(int p, int nops, const double* A, const double* K, int64_t ldk, const double* Gm, double* T);
+
 // ---- tiled local systems: their geometry (ck_internal.h has the layout) and ck_predict_local's plan -----------------------
 struct CkLocalSys {
     long long off;      // doubles into the slab

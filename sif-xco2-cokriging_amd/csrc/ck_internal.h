@@ -190,6 +190,72 @@ void ck_launch_loglik_grad(hipStream_t s, double* const* G_dev, CkLayout L, int 
 // dl/ds_k = 1/2 sum_K part[2 K + k] (ck_loglik_noise_grad)
 void ck_launch_lik_noise_grad(hipStream_t s, double* const* G_dev, int nK, CkLayout L, const double* d, double* part);
 
+// ---- Fisher information of the likelihood fit (ck_fisher.hip; the product kernel: ck_la.hip) --------------------------
+// Parameter slots: the CK_LIK_NPAR model parameters in the flat order, then the noise scales s_0, s_1.  Every dSigma/dtheta is a
+// combination of the OPERANDS below (ck_host.h: ck_host_fisher_coef has the coefficients): per Matern block the correlation
+// R, amp dR/dnu, amp dR/dlen and -- inside a process -- Z, the 0 / 1 pattern of h == 0; per process diag(d_a).
+#define CK_FISHER_NPAR 13   // == CK_LIK_NPAR + 2 (include/cokrige.h has the same definition)
+static_assert(CK_FISHER_NPAR == CK_LIK_NPAR + 2, "the model parameters and the two noise scales");
+#define CK_FISHER_NOPS 13
+#define CK_FISHER_NPAIR (CK_FISHER_NOPS * (CK_FISHER_NOPS + 1) / 2)
+#define CK_FOP_R00 0     // R, dnu, dlen, Z of block (0, 0): operands 0 .. 3
+#define CK_FOP_R11 4     // ... of block (1, 1): 4 .. 7
+#define CK_FOP_R01 8     // R, dnu, dlen of the cross block and its transpose: 8 .. 10
+#define CK_FOP_DIAG0 11  // diag(d_a) on process 0 / 1: 11, 12
+#define CK_FISHER_YROWS 256   // rows of the thin REML operand Y^T (>= CK_FISHER_NOPS CK_LU_PMAX)
+// One UNIT of a dense operand D: the columns n in [c0, c0 + wpad) of the product Sigma^-1 D with the rows k of D in the K-panels
+// pK0 .. pK0 + npan - 1, stored as the product kernel's second operand: D[(pp wpad + n) NB + k'] = D[(pK0 + pp) NB + k', c0 + n]
+// (zero outside the block: the kernel runs over whole panels and 128-column tiles).  nlo / nhi: the columns that belong to
+// the unit's process.  A block-diagonal operand is one unit, a cross operand two (its columns in process 0 / in process 1).
+struct CkFisherUnit {
+    double* D;
+    long c0, wpad, nlo, nhi;
+    int pK0, npan;
+};
+// the assembly's view: D[op][r] = the unit of dense operand op whose columns lie in process r (null: not wanted)
+struct CkFisherAsm {
+    double* D[CK_FOP_DIAG0][2];
+    long c0[2], wpad[2];
+    int pK0[2];
+};
+#define CK_FOPK_NONE 0
+#define CK_FOPK_DENSE 1
+#define CK_FOPK_DIAG0 2   // + process
+// the contraction's view of a product: B[r ld + (c - c0)] for c in [c0, c0 + w), zero elsewhere; a diagonal operand is read
+// from Sigma^-1 itself
+struct CkFisherOp {
+    const double* B;
+    long ld, c0, w;
+    int kind;
+};
+struct CkFisherOps {
+    CkFisherOp op[CK_FISHER_NOPS];
+    unsigned mask[CK_FISHER_NOPS];   // mask[a] bit b (a <= b): the pair (a, b) is wanted
+};
+struct CkFisherCtx {
+    const double* Sp;   // Sigma^-1 as full K-panels (ck_launch_fisher_expand)
+    const double* d;    // npad measurement-error variances in the internal order (may be null without a diagonal operand)
+    long npad, n0p;
+    int n_procs;
+};
+// G_dev: the packed lower block columns of -Sigma^-1 (ck_launch_ginv_syrk with a zero start) -> Sp, npad x npad doubles
+void ck_launch_fisher_expand(hipStream_t s, double* const* G_dev, CkLayout L, double* Sp);
+// the units' buffers must be zero; blk5 / dnu3 / c as ck_launch_loglik_grad
+void ck_launch_fisher_assemble(hipStream_t s, const CkFisherAsm& A, CkLayout L, int n_procs, int metric, const double* c,
+                               const CkMatern* blk5, const double* dnu3);
+// C (npad rows, ldc; its columns [0, U.wpad)) -= Sigma^-1[:, panels of U] D_U on the trailing updates' MFMA tile (ck_la.hip)
+void ck_launch_fisher_prod(hipStream_t s, double* C, int64_t ldc, const double* Sp, int64_t npad, const double* D, int64_t wpad,
+                           int pK0, int npan);
+// part: CK_FISHER_NPAIR doubles per workgroup (ck_fisher_contract_groups of them), pair (a <= b) at b (b + 1) / 2 + a
+int64_t ck_fisher_contract_groups(int64_t npad);
+void ck_launch_fisher_contract(hipStream_t s, const CkFisherOps& O, const CkFisherCtx& X, double* part);
+// REML: Y = D H into the K-panel operand Yp (rows row0 .. row0 + p - 1), and the sums over the sites out = Y^T R
+void ck_launch_fisher_dh(hipStream_t s, const CkFisherUnit& U, const double* H, int p, int row0, double* Yp);
+void ck_launch_fisher_dh_diag(hipStream_t s, CkLayout L, int n_procs, int proc, const double* d, const double* H, int p, int row0,
+                              double* Yp);
+void ck_launch_fisher_ytv(hipStream_t s, const double* Yp, int64_t npad, const double* R, int64_t ldr, int ncols, double* out,
+                          int64_t ldo);
+
 // ---- conditional simulation (ck_draws.hip) ---------------------------------------------------
 // on the Schur buffers sch[J] (packed block columns of S, nJ of them), sites k < m:
 // mask[k] = S_kk <= thr; S_kk = 1 where deflated, else S_kk + jit

@@ -828,6 +828,40 @@ void ck_launch_ginv_syrk(hipStream_t s, double* const* G_dev, const double* aux,
         k_ginv_syrk_d<true><<<dim3((unsigned)map.total), dim3(512), 0, s>>>(G_dev, aux, mpad, avec, nK, map, q, (long)ald, dense);
 }
 
+// The products B = Sigma^-1 D of the Fisher information (ck_loglik_fisher, ck_fisher.hip): Sigma^-1 as full K-panels (Sp: panel
+// P = npad rows of its 512 columns) against one unit of a derivative operand (ck_internal.h: CkFisherUnit), restricted to the
+// panels and columns the unit lives in.  C starts at zero and receives -Sigma^-1 D (the tile's sign).
+struct CkSrcFisher {
+    const double* Sp;
+    long npad;
+    const double* D;
+    long wpad;
+    int pK0;
+    long r0, c0;
+    __device__ __forceinline__ void get(int p, const ck_gchar*& A, const ck_gchar*& B) const {
+        A = as_global(reinterpret_cast<const char*>(Sp + ((long)(pK0 + p) * npad + r0) * CK_NB));
+        B = as_global(reinterpret_cast<const char*>(D + ((long)p * wpad + c0) * CK_NB));
+    }
+};
+
+__global__ __launch_bounds__(512, 4) void k_fisher_prod(double* __restrict__ C, long ldc, const double* __restrict__ Sp, long npad,
+                                                         const double* __restrict__ D, long wpad, int pK0, int npan, int tiles_n) {
+    __shared__ __attribute__((aligned(16))) char lds[2 * 256 * 128];
+    const int t = xcd_remap(blockIdx.x, (int)gridDim.x);
+    const int tm = t / tiles_n, tn = t - tm * tiles_n;
+    const long r0 = (long)tm * 128, c0 = (long)tn * 128;
+    const CkSrcFisher src{Sp, npad, D, wpad, pK0, r0, c0};
+    gemm_tile_d<8>(C, ldc, src, npan, r0, c0, lds);
+}
+
+void ck_launch_fisher_prod(hipStream_t s, double* C, int64_t ldc, const double* Sp, int64_t npad, const double* D, int64_t wpad,
+                           int pK0, int npan) {
+    if (npad <= 0 || wpad <= 0 || npan <= 0) return;
+    const int tiles_m = (int)(npad / 128), tiles_n = (int)(wpad / 128);
+    k_fisher_prod<<<dim3((unsigned)(tiles_m * tiles_n)), dim3(512), 0, s>>>(C, (long)ldc, Sp, (long)npad, D, (long)wpad, pK0, npan,
+                                                                          tiles_n);
+}
+
 // ---------------------------------------------------------------------------------------
 // Leave-group-out cross-validation (ck_cv_folds): the Gram matrices Q_SS = W_S W_S^T of all folds in ONE launch
 // ---------------------------------------------------------------------------------------

@@ -306,6 +306,17 @@ class MultivariateMatern:
         (``ck_set_noise``).  With ``gradient=True`` the call then returns (l, dl/dtheta, dl/ds): the derivatives in the
         noise scales, one per process (0 for a process without noise), as a third value; without ``measurement_error``
         the result has the shape it always had."""
+        h, var = self._lik_assembled(mf, dist_units, fast_dist, trend, measurement_error, noise_scale)
+        info, out3, g = h.loglik_reml(gradient) if trend is not None else h.loglik(gradient)
+        if info != 0:
+            raise LinAlgError(f"{info}-th leading minor of the array is not positive definite")
+        if gradient and var is not None:
+            return out3[0], g, h.loglik_noise_grad()[:self.n_procs]
+        return (out3[0], g) if gradient else out3[0]
+
+    def _lik_assembled(self, mf, dist_units, fast_dist, trend, measurement_error, noise_scale):
+        """(handle, variances): the likelihood's handle with the current parameters, the noise and the trend set and Sigma
+        assembled -- what ``log_likelihood`` and ``information`` evaluate."""
         from .noise import apply_noise, resolve_measurement_error
         from .trend import TrendDesign, check_trend
         check_trend(trend)
@@ -329,15 +340,50 @@ class MultivariateMatern:
             for k in range(self.n_procs):
                 h.set_trend(k, None)
         h.assemble_joint()
-        info, out3, g = h.loglik_reml(gradient) if trend is not None else h.loglik(gradient)
+        return h, var
+
+    def information(self, mf, dist_units: str = "km", fast_dist: bool = True, trend=None, measurement_error=None,
+                    noise_scale=None, fixed=None, _at_bound=None):
+        """Expected (Fisher) information of the likelihood at the current parameters and what follows from it
+        (``ParameterInformation``): I_jk = 1/2 tr(Sigma^-1 D_j Sigma^-1 D_k) with D_k = dSigma/dtheta_k, computed on the
+        device (``ck_loglik_fisher``); with ``trend`` the information of the restricted likelihood.  The arguments are those
+        of ``log_likelihood``.  The noise scales of the processes that have ``measurement_error`` are parameters too
+        (``noise_scale_0`` / ``noise_scale_1``).  ``fixed``: names (or flat indices of the model parameters) conditioned on:
+        they are left out, and the standard errors are those of the others given them."""
+        h, var = self._lik_assembled(mf, dist_units, fast_dist, trend, measurement_error, noise_scale)
+        names13 = information_slot_names(self.n_procs)
+        model_names = list(self.params.get_names())
+        live = np.zeros(13, dtype=bool)
+        live[:len(model_names)] = True
+        for k in range(self.n_procs):
+            live[11 + k] = var is not None and var[k] is not None
+        for f in ([] if fixed is None else ([fixed] if isinstance(fixed, (str, int, np.integer)) else fixed)):
+            if isinstance(f, str):
+                if f not in names13 or f == "":
+                    raise ValueError(f"`{f}` is not a parameter name ({[n for n in names13 if n]})")
+                live[names13.index(f)] = False
+            else:
+                if not 0 <= int(f) < len(model_names):
+                    raise ValueError(f"parameter index {f} out of range")
+                live[int(f)] = False
+        bound = np.zeros(13, dtype=bool)
+        for f in ([] if _at_bound is None else _at_bound):
+            bound[names13.index(f)] = live[names13.index(f)]
+        info, fisher = h.fisher(reml=trend is not None, free=live & ~bound)
         if info != 0:
             raise LinAlgError(f"{info}-th leading minor of the array is not positive definite")
-        if gradient and var is not None:
-            return out3[0], g, h.loglik_noise_grad()[:self.n_procs]
-        return (out3[0], g) if gradient else out3[0]
+        est = np.full(13, np.nan)
+        est[:len(model_names)] = self.params.get_values().astype(float)
+        if var is not None:
+            from .noise import resolve_measurement_error
+            scales = resolve_measurement_error(measurement_error, noise_scale, mf.fields)[1]
+            for k in range(self.n_procs):
+                est[11 + k] = scales[k]
+        return summarize_information(fisher, self.n_procs, live, est, at_bound=bound)
 
     def fit_likelihood(self, mf, guess: MaternParams = None, fixed=None, dist_units: str = "km", fast_dist: bool = True,
-                       trend=None, measurement_error=None, noise_scale=None, fit_noise_scale: bool = False):
+                       trend=None, measurement_error=None, noise_scale=None, fit_noise_scale: bool = False,
+                       std_errors: bool = False):
         """Maximum-likelihood fit: L-BFGS-B on -l with the analytic gradient, within ``params.get_bounds()``.
         ``guess`` as in ``fit``: None starts from the default parameters, else from the current ones with the bounds of
         ``guess``.  ``fixed``: parameter names or flat indices held at their starting values.
@@ -353,7 +399,13 @@ class MultivariateMatern:
         that have noise are estimated too (the reported retrieval uncertainties are known to be too small by a factor):
         they join the optimiser's vector as log s over [log 1e-3, log 1e3], mapped onto [0, 1] like the other parameters,
         starting at ``noise_scale``.  ``fit_result.noise_scale`` holds the scales used or found, and the AIC counts the
-        estimated ones."""
+        estimated ones.
+
+        ``std_errors=True``: ``fit_result.information`` is the ``ParameterInformation`` at the optimum (``information``: ML
+        or REML as fitted, the noise scales included when they were fitted), with the shortcuts ``fit_result.std_error`` and
+        ``fit_result.conf_int()``.  Parameters held by ``fixed`` are conditioned on; so is a parameter that ends within 1e-8
+        of its bound width from a bound: it is listed in ``fit_result.at_bound`` with a NaN standard error, and one warning
+        says so.  With the default False these attributes are None."""
         from .noise import resolve_measurement_error
         from .trend import check_trend
         check_trend(trend)
@@ -446,6 +498,20 @@ class MultivariateMatern:
         self.fit_result = FittedLikelihood(self, ll, g, free, state["n_eval"], state["n_not_pd"], res,
                                            method="ML" if trend is None else "REML", noise_scale=scales_of(res.x),
                                            noise_gradient=None if var is None else gs, noise_free=s_free)
+        if std_errors:
+            # a parameter within 1e-8 of its bound width from a bound: conditioned on (no normal approximation on a boundary)
+            u = np.asarray(res.x, dtype=float)
+            at_bound = [names[k] for j, k in enumerate(free) if min(u[j], 1.0 - u[j]) <= 1e-8]
+            at_bound += [f"noise_scale_{k}" for j, k in enumerate(s_free) if min(u[nf + j], 1.0 - u[nf + j]) <= 1e-8]
+            held = [names[k] for k in sorted(hold)] + [f"noise_scale_{k}" for k in range(self.n_procs) if k not in s_free]
+            if at_bound:
+                warnings.warn(f"fit_likelihood: {', '.join(at_bound)} ended on a bound; the standard errors are conditional on "
+                              "them and their own are NaN")
+            inf = self.information(mf, dist_units, fast_dist, trend=trend, measurement_error=measurement_error,
+                                   noise_scale=scales_of(res.x), fixed=held, _at_bound=at_bound)
+            self.fit_result.information = inf
+            self.fit_result.at_bound = at_bound
+            self.fit_result.std_error = inf.std_error
         return self
 
 
@@ -473,6 +539,108 @@ class FittedLikelihood:
         self.success = bool(optim.success)
         self.message = optim.message if isinstance(optim.message, str) else str(optim.message)
         self.n_iter = int(getattr(optim, "nit", 0))
+        # fit_likelihood(std_errors=True): the ParameterInformation at the optimum, its standard errors, the parameters that
+        # ended on a bound
+        self.information = None
+        self.std_error = None
+        self.at_bound = None
+
+    def conf_int(self, level: float = 0.95):
+        """``information.conf_int(level)``; None without ``std_errors=True``."""
+        return None if self.information is None else self.information.conf_int(level)
+
+
+INFORMATION_SLOTS = 13
+
+
+def information_slot_names(n_procs: int):
+    """Names of the 13 slots of ``ck_loglik_fisher``: the model parameters in the flat order (one process: 4 of them, the
+    other slots ""), then the noise scales."""
+    names = list(MaternParams(n_procs=n_procs).get_names())
+    names += [""] * (11 - len(names)) + ["noise_scale_0", "noise_scale_1" if n_procs == 2 else ""]
+    return names
+
+
+def summarize_information(fisher, n_procs: int, live=None, estimates=None, at_bound=None):
+    """Pure numpy: the 13 x 13 information array of ``ck_loglik_fisher`` -> ``ParameterInformation``.  ``live``: 13 flags,
+    the slots that are parameters here (None: every slot that has a name); ``estimates``: 13 values (for ``conf_int``);
+    ``at_bound``: 13 flags, live parameters that are conditioned on and reported with NaN.
+    The inversion works on the matrix scaled to unit diagonal.  A live parameter with I_kk == 0 is not identified: NaN
+    everywhere, named in ``not_identified``, one warning.  If the rest is not positive definite every standard error is
+    NaN, with one warning."""
+    fisher = np.asarray(fisher, dtype=float)
+    if fisher.shape != (INFORMATION_SLOTS, INFORMATION_SLOTS):
+        raise ValueError("fisher: the 13 x 13 array of ck_loglik_fisher")
+    names13 = information_slot_names(n_procs)
+    named = np.array([n != "" for n in names13])
+    live = named.copy() if live is None else (np.asarray(live, dtype=bool) & named)
+    bound = np.zeros(INFORMATION_SLOTS, dtype=bool) if at_bound is None else (np.asarray(at_bound, dtype=bool) & live)
+    idx = np.flatnonzero(live)
+    names = [names13[k] for k in idx]
+    n = idx.size
+    sub = fisher[np.ix_(idx, idx)]
+    cov = np.full((n, n), np.nan)
+    corr = np.full((n, n), np.nan)
+    diag = np.diag(sub)
+    is_bound = bound[idx]
+    dead = ~is_bound & (diag == 0.0)
+    not_identified = [names[j] for j in np.flatnonzero(dead)]
+    if not_identified:
+        warnings.warn(f"information: {', '.join(not_identified)} not identified at these parameters (zero information); "
+                      "reported as NaN")
+    keep = np.flatnonzero(~is_bound & ~dead)
+    positive_definite = True
+    if keep.size:
+        d = diag[keep]
+        ok = np.all(np.isfinite(sub[np.ix_(keep, keep)])) and np.all(d > 0.0)
+        if ok:
+            s = 1.0 / np.sqrt(d)
+            c = sub[np.ix_(keep, keep)] * np.outer(s, s)
+            try:
+                lc = np.linalg.cholesky(c)
+                li = np.linalg.solve(lc, np.eye(keep.size))
+                ci = li.T @ li
+                cov[np.ix_(keep, keep)] = ci * np.outer(s, s)
+                sd = np.sqrt(np.diag(ci))
+                corr[np.ix_(keep, keep)] = ci / np.outer(sd, sd)
+            except LinAlgError:
+                ok = False
+        if not ok:
+            positive_definite = False
+            warnings.warn("information: the information matrix of the identified parameters is not positive definite; every "
+                          "standard error is NaN")
+    est = None if estimates is None else np.asarray(estimates, dtype=float)[idx]
+    return ParameterInformation(names, sub, cov, corr, est, not_identified, [names[j] for j in np.flatnonzero(is_bound)],
+                                positive_definite)
+
+
+class ParameterInformation:
+    """Fisher information of the likelihood and the asymptotic covariance of the estimates: ``names`` (the live parameters;
+    noise scales as ``noise_scale_0/1``), ``fisher``, ``cov`` = its inverse over the identified parameters (NaN rows and
+    columns for the others), ``std_error`` (a ``pd.Series`` by name), ``correlation``, ``not_identified``, ``at_bound``,
+    ``positive_definite`` and ``conf_int(level)`` (normal quantiles)."""
+
+    def __init__(self, names, fisher, cov, correlation, estimates, not_identified, at_bound, positive_definite) -> None:
+        self.names = list(names)
+        self.fisher = fisher
+        self.cov = cov
+        self.correlation = correlation
+        self.estimates = None if estimates is None else pd.Series(estimates, index=self.names)
+        self.std_error = pd.Series(np.sqrt(np.diag(cov)) if len(self.names) else np.zeros(0), index=self.names)
+        self.not_identified = list(not_identified)
+        self.at_bound = list(at_bound)
+        self.positive_definite = bool(positive_definite)
+
+    def conf_int(self, level: float = 0.95):
+        """estimate -+ z std_error with z the normal quantile of (1 + level) / 2: a DataFrame (lower, upper) by name."""
+        from scipy.special import ndtri
+        if not 0.0 < level < 1.0:
+            raise ValueError("level: a probability inside (0, 1)")
+        if self.estimates is None:
+            raise ValueError("conf_int needs the estimates")
+        z = float(ndtri(0.5 * (1.0 + level)))
+        return pd.DataFrame({"lower": self.estimates - z * self.std_error, "upper": self.estimates + z * self.std_error},
+                            index=self.names)
 
 
 class FittedVariogram:

@@ -57,6 +57,7 @@ _PROTOS = {
     "ck_loglik_noise_grad": [c_void_p, _dp],
     "ck_predict_universal": [c_void_p, c_int, _dp, c_int64, _dp, _dp, _dp, _dp, _dp],
     "ck_loglik_reml": [c_void_p, c_int, _dp, _dp, POINTER(c_int64)],
+    "ck_loglik_fisher": [c_void_p, c_int, POINTER(c_int32), _dp, POINTER(c_int64)],
     "ck_sample": [c_void_p, _dp, _dp, c_int64],
     "ck_conditional_draws": [c_void_p, c_int, _dp, c_int64, c_int64, c_uint64, _dp, c_double, c_double, _dp, _dp, _dp,
                              POINTER(c_uint8), POINTER(c_int64)],
@@ -470,6 +471,29 @@ class Handle:
         if grad is not None and getattr(self, "_n_procs", 2) == 1:
             grad = grad[:4].copy()
         return info.value, tuple(out4.tolist()), grad
+
+    def fisher(self, reml=False, free=None):
+        """Expected (Fisher) information of the likelihood at the model's parameters (include/cokrige.h: ck_loglik_fisher) on
+        an assembled handle.  ``free``: 13 flags over the slots (11 model parameters in the flat order -- one process: the
+        first 4 -- then the noise scales s_0, s_1), None = all.  Returns (info, I) with I the 13 x 13 array: rows and columns of
+        slots that are not live are 0; info != 0: Sigma is not positive definite and I is NaN."""
+        out = np.empty((13, 13))
+        info = c_int64(0)
+        fr = None
+        if free is not None:
+            fr = np.ascontiguousarray(np.asarray(free).astype(bool), dtype=np.int32)
+            if fr.shape != (13,):
+                raise ValueError("free: 13 flags, one per slot")
+        _chk(lib().ck_loglik_fisher(self._h, int(bool(reml)), fr.ctypes.data_as(POINTER(c_int32)) if fr is not None else None,
+                                    _p(out), byref(info)))
+        return info.value, out
+
+    def fisher_timings(self):
+        """ck_timings [64 ..] of the last fisher() call: milliseconds, the flop of the products and the number of groups."""
+        out = np.zeros(70)
+        _chk(lib().ck_timings(self._h, _p(out), 70))
+        keys = ["assemble_ms", "product_ms", "contract_ms", "total_ms", "flop", "groups"]
+        return dict(zip(keys, out[64:70].tolist()))
 
     def loglik_timings(self):
         """ck_timings [24 ..] of the last loglik() call, in milliseconds."""
