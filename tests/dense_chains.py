@@ -1,5 +1,6 @@
-"""Dense float64 reference chains for the likelihood, REML, universal, block and conditional-draw entry points, and the
-list of data sets tests/test_gpu_entry_edge_sizes.py runs them on.  Plain numpy / scipy on the oracle's covariances
+"""Dense float64 reference chains for the likelihood, REML, universal, block, conditional-draw, Fisher-information and
+leave-group-out entry points, and the list of data sets tests/test_gpu_entry_edge_sizes.py and
+tests/test_gpu_newer_entry_edge_sizes.py run them on.  Plain numpy / scipy on the oracle's covariances
 (oracle/cokrige_oracle.py: joint_cov, pred_cross_cov, pred_cov) in the caller's site order; no GPU, no library call except
 where a function takes the library's site order as an argument.  tests/test_dense_chains.py checks these references
 themselves, and the conditioning of every data set below, on the host."""
@@ -29,8 +30,23 @@ FIVE_RUNGS = [(5, 3, 40, "BIV", HAV), (63, 65, 40, "BIV", HAV), (448, 64, 40, "B
               (65, 0, 40, "UNI", HAV)]
 SMALL, LARGE = (63, 65, 40, "BIV", HAV), (513, 511, 40, "BIV", HAV)
 REFIT = (700, 650, 40, "BIV", HAV)   # the size the older tests use: the last set_data step of the sequence test
-# every data set the GPU module uses: the host test checks that Sigma factors and cond(Sigma) < 1e8 for each of them
-DATA_CASES = list(dict.fromkeys(LIK_CASES + FIVE_RUNGS + [(64, 64, 40, "BIV", HAV), SMALL, LARGE, REFIT]))
+REFIT_UNI = (700, 0, 40, "UNI", HAV)   # the univariate half of REFIT's sizes
+# Fisher information: every rung, n0p = 576 (the boundary mid-tile in the second panel), three panels with the other metric
+# and with rho = 0 (nu_12 and len_12 dead), one process down to N = 1
+FISHER_CASES = ([(n0, n1, 40, "BIV", HAV) for n0, n1 in LADDER_BIV] + [(576, 100, 40, "BIV", HAV)]
+                + [(513, 511, 40, "BIV_EUC", EUC), (513, 511, 40, "BIV_HALF", HAV)] + [(n0, 0, 40, "UNI", HAV) for n0 in LADDER_UNI])
+FISHER_WIDE = [LARGE, SMALL]   # REML with eight columns per process, p = 16
+FISHER_NOISE_CASES = [SMALL, (449, 63, 40, "BIV", HAV), (512, 512, 40, "BIV", HAV), LARGE, (64, 1, 40, "BIV", HAV),
+                      (1, 600, 40, "BIV", HAV), (65, 0, 40, "UNI", HAV)]
+NOISE_SCALES = (1.7, 0.6)
+NOISE_CASES = [SMALL, (449, 63, 40, "BIV", HAV), (512, 512, 40, "BIV", HAV), (64, 1, 40, "BIV", HAV), (1, 600, 40, "BIV", HAV)]
+# leave-group-out folds: (data set, predicted process) for every process that has data
+FOLD_CASES = ([((n0, n1, 40, "BIV", HAV), i) for n0, n1 in LADDER_BIV for i in (0, 1)]
+              + [((n0, 0, 40, "UNI", HAV), 0) for n0 in (1, 64, 65, 513)])
+FOLD_VARIANTS = [(False, False), (True, False), (True, True)]   # (labels on the other process, some data labelled -1)
+# every data set the GPU modules use: the host test checks that Sigma factors and cond(Sigma) < 1e8 for each of them
+DATA_CASES = list(dict.fromkeys(LIK_CASES + FIVE_RUNGS + [(64, 64, 40, "BIV", HAV), SMALL, LARGE, REFIT] + FISHER_CASES
+                                + FISHER_NOISE_CASES + NOISE_CASES + [c for c, _ in FOLD_CASES] + [REFIT_UNI]))
 
 # conditional draws: (data set, predicted process, m, sites on data of that process, seed of the sites)
 DRAW_M = [1, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1025]
@@ -379,3 +395,288 @@ def chain_draws(pred, S, defl, perm, eps, jitter_abs=0.0):
     x = np.zeros_like(eps)
     x[:, kept] = eps[:, kept] @ L.T
     return pred + x
+
+
+# ---- Fisher information -------------------------------------------------------------------------------------------------------
+# The 13 slots of ck_loglik_fisher by the kind of their derivative: exact block expressions (sigma, nugget, rho, noise
+# scales), the length scales (closed form in the library, differenced here) and nu (differenced on both sides).
+SLOTS = {11: {"exact": [0, 1, 8, 9, 10, 11, 12], "len": [5, 6, 7], "nu": [2, 3, 4]},
+         4: {"exact": [0, 3, 11], "len": [2], "nu": [1]}}
+
+
+def _corr(nu, ls, d):
+    return orc.matern_correlation(nu, ls, d).reshape(d.shape)
+
+
+def _d4(f, x, scale=1.0):
+    """4th-order central difference of f at x with fd_grad's step (times scale)"""
+    e = scale * (1e-3 * max(abs(x), 1.0))
+    return (f(x - 2 * e) - 8 * f(x - e) + 8 * f(x + e) - f(x + 2 * e)) / (12 * e)
+
+
+def derivative_matrices(params, coords, metric, noise=None, scale=1.0):
+    """{slot: D_slot} (N x N each) over the 13 slots of ck_loglik_fisher; noise: per process the variances d_a or None"""
+    p = orc.Params.from_flat(params)
+    n = [len(c) for c in coords]
+    N = sum(n)
+    off = [0, n[0]]
+    D = {}
+
+    def put(i, j, blk):
+        M = np.zeros((N, N))
+        M[off[i]:off[i] + n[i], off[j]:off[j] + n[j]] = blk
+        if i != j:
+            M[off[j]:off[j] + n[j], off[i]:off[i] + n[i]] = blk.T
+        return M
+
+    d00 = orc.distance_matrix(coords[0], coords[0], metric)
+    if p.n_procs == 1:
+        s, nu, ls = p.sigma[0], p.nu[0, 0], p.len_scale[0, 0]
+        D[0] = put(0, 0, 2 * s * _corr(nu, ls, d00))
+        D[1] = put(0, 0, s * s * _d4(lambda x: _corr(x, ls, d00), nu, scale))
+        D[2] = put(0, 0, s * s * _d4(lambda x: _corr(nu, x, d00), ls, scale))
+        D[3] = put(0, 0, (d00 == 0).astype(float))
+    else:
+        d01 = orc.distance_matrix(coords[0], coords[1], metric)
+        d11 = orc.distance_matrix(coords[1], coords[1], metric)
+        s1, s2, rho = p.sigma[0], p.sigma[1], p.rho
+        R00 = _corr(p.nu[0, 0], p.len_scale[0, 0], d00)
+        R01 = _corr(p.nu[0, 1], p.len_scale[0, 1], d01)
+        R11 = _corr(p.nu[1, 1], p.len_scale[1, 1], d11)
+        D[0] = put(0, 0, 2 * s1 * R00) + put(0, 1, rho * s2 * R01)
+        D[1] = put(1, 1, 2 * s2 * R11) + put(0, 1, rho * s1 * R01)
+        D[2] = put(0, 0, s1 * s1 * _d4(lambda x: _corr(x, p.len_scale[0, 0], d00), p.nu[0, 0], scale))
+        D[3] = put(0, 1, rho * s1 * s2 * _d4(lambda x: _corr(x, p.len_scale[0, 1], d01), p.nu[0, 1], scale))
+        D[4] = put(1, 1, s2 * s2 * _d4(lambda x: _corr(x, p.len_scale[1, 1], d11), p.nu[1, 1], scale))
+        D[5] = put(0, 0, s1 * s1 * _d4(lambda x: _corr(p.nu[0, 0], x, d00), p.len_scale[0, 0], scale))
+        D[6] = put(0, 1, rho * s1 * s2 * _d4(lambda x: _corr(p.nu[0, 1], x, d01), p.len_scale[0, 1], scale))
+        D[7] = put(1, 1, s2 * s2 * _d4(lambda x: _corr(p.nu[1, 1], x, d11), p.len_scale[1, 1], scale))
+        D[8] = put(0, 0, (d00 == 0).astype(float))
+        D[9] = put(1, 1, (d11 == 0).astype(float))
+        D[10] = put(0, 1, s1 * s2 * R01)
+    for k in range(p.n_procs):
+        if noise is not None and noise[k] is not None:
+            D[11 + k] = put(k, k, np.diag(np.asarray(noise[k], dtype=float)))
+    return D
+
+
+def dense_sigma(params, coords, metric, noise=None, scales=(1.0, 1.0)):
+    S = orc.joint_cov(orc.Params.from_flat(params), coords, metric)
+    if noise is not None:
+        dv = np.concatenate([scales[k] * np.asarray(noise[k], dtype=float) if noise[k] is not None else np.zeros(len(coords[k]))
+                             for k in range(len(coords))])
+        S = S + np.diag(dv)
+    return S
+
+
+def fisher_of(S, D, X=None):
+    """I_jk = 1/2 tr(S^-1 D_j S^-1 D_k) over the slots of D through cho_solve (X: P formed densely in place of S^-1)"""
+    cf = cho_factor(S, lower=True)
+    if X is None:
+        B = {k: cho_solve(cf, Dk) for k, Dk in D.items()}
+    else:
+        H = cho_solve(cf, X)
+        P = cho_solve(cf, np.eye(S.shape[0])) - H @ np.linalg.solve(X.T @ H, H.T)
+        B = {k: P @ Dk for k, Dk in D.items()}
+    ref = np.zeros((13, 13))
+    for j in B:
+        for k in B:
+            if k >= j:
+                ref[j, k] = ref[k, j] = 0.5 * np.sum(B[j] * B[k].T)
+    return ref
+
+
+def dense_fisher(params, coords, metric, noise=None, scales=(1.0, 1.0), X=None, scale=1.0):
+    """the 13 x 13 information of the dense chain (rows / columns of slots that do not exist are 0); scale multiplies the
+    step of the differenced nu and length-scale derivatives, as fd_of's does"""
+    return fisher_of(dense_sigma(params, coords, metric, noise, scales), derivative_matrices(params, coords, metric, noise, scale), X)
+
+
+def normalised(I, ref):
+    """|I - ref| / sqrt(ref_jj ref_kk) over the entries whose scale is positive; the others must be equal"""
+    d = np.sqrt(np.outer(np.diag(ref), np.diag(ref)))
+    pos = d > 0
+    assert np.array_equal(I[~pos], ref[~pos]), (I[~pos], ref[~pos])
+    e = np.zeros_like(I)
+    e[pos] = np.abs(I - ref)[pos] / d[pos]
+    return e
+
+
+def class_errors(e, npar):
+    """the largest entry of a normalised() error per class of pairs: exact x exact; a length-scale slot with an exact or a
+    length-scale slot; every pair with a nu slot"""
+    s = SLOTS[npar]
+    el = s["exact"] + s["len"]
+    ln = np.zeros_like(e)
+    ln[np.ix_(s["len"], el)] = e[np.ix_(s["len"], el)]
+    ln[np.ix_(el, s["len"])] = e[np.ix_(el, s["len"])]
+    nu = max(e[s["nu"], :].max(), e[:, s["nu"]].max())
+    return {"exact": e[np.ix_(s["exact"], s["exact"])].max(), "len": ln.max(), "nu": nu}
+
+
+# The reference's own floor in the length-scale class -- what halving _d4's step changes, in normalised()'s measure
+# (tests/test_dense_chains.py: test_fisher_reference_floor measures and prints it for every rung of FISHER_CASES).  The bound
+# of the length-scale class is max(1e-9, 10 x the rung's floor); a rung is listed here only when its floor exceeds 1e-10.
+FISHER_LEN_FLOOR = {}
+FISHER_TOL = {"exact": 1e-9, "nu": 1e-6}
+
+
+def fisher_tol(case):
+    return dict(FISHER_TOL, len=max(1e-9, 10.0 * FISHER_LEN_FLOOR.get(case, 0.0)))
+
+
+def noise_of(ds, which=(0, 1), seed=5):
+    """measurement-error variances uniform(0.01, 0.1) per process in `which`, None for the others"""
+    rng = np.random.default_rng(seed)
+    return [rng.uniform(0.01, 0.1, len(ds.coords[k])) if k in which else None for k in range(ds.p.n_procs)]
+
+
+def trend_kinds(ds, kind):
+    """`kind` per process; a process with fewer data than the design has columns (ck_set_trend refuses it) gets "constant" """
+    return [kind if len(c) >= TREND_COLUMNS[kind] else "constant" for c in ds.coords]
+
+
+TREND_COLUMNS = {"constant": 1, "linear": 3, "wide": 8}
+
+
+def annihilated_slots(n, kinds):
+    """REML with as many trend columns on a process as it has sites (one site with the constant design, three with the
+    linear one): the unit vectors of its sites lie in the span of X, so P e_a = 0 there and every D_k supported on its rows
+    and columns alone has P D_k P = 0 -- sigma, nu, len, nugget and noise scale of that process and everything of the cross
+    block.  Their information is 0 in exact arithmetic and rounding noise (1e-16 of the slot's scale) in any computation, the
+    dense chain included, so normalised() has no scale for them: they are compared with 0 in the scale of the ML
+    information (ml_scaled) and taken out of both matrices (drop_slots)"""
+    if len(n) != 2 or kinds is None:
+        return []
+    out = []
+    for k, own in ((0, [0, 2, 5, 8, 11]), (1, [1, 4, 7, 9, 12])):
+        if kinds[k] is not None and n[k] == TREND_COLUMNS[kinds[k]]:
+            out += own + [3, 6, 10]
+    return sorted(set(out))
+
+
+def ml_scaled(I, ml, slots):
+    """the largest |I_jk| over the rows `slots` in the scale sqrt(ml_jj ml_kk) of the ML information (1 where that is 0)"""
+    d = np.where(np.diag(ml) > 0, np.diag(ml), 1.0)
+    return float(np.max(np.abs(I[slots, :]) / np.sqrt(np.outer(d[slots], d)))) if len(slots) else 0.0
+
+
+def drop_slots(I, slots):
+    J = I.copy()
+    J[slots, :] = 0.0
+    J[:, slots] = 0.0
+    return J
+
+
+# ---- leave-group-out cross-validation -------------------------------------------------------------------------------------------
+def dense_folds(S, z, members):
+    """include/cokrige.h ck_cv_folds in dense form for a Sigma that already includes the noise: Q = S^-1 through cho_solve,
+    alpha = Q z; per fold (index arrays in the caller's stacked order) pred_S = z_S - Q_SS^-1 alpha_S, var_S = diag(Q_SS^-1),
+    log|Q_SS| and alpha_S^T Q_SS^-1 alpha_S: a list of (pred, var, logdet, quad)"""
+    cf = cho_factor(S, lower=True)
+    Q = cho_solve(cf, np.eye(len(z)))
+    Q = 0.5 * (Q + Q.T)
+    alpha = cho_solve(cf, z)
+    out = []
+    for ix in members:
+        ix = np.asarray(ix, dtype=np.int64)
+        cq = cho_factor(Q[np.ix_(ix, ix)], lower=True)
+        C = cho_solve(cq, np.eye(len(ix)))
+        w = cho_solve(cq, alpha[ix])
+        out.append((z[ix] - w, np.diag(C).copy(), 2.0 * np.sum(np.log(np.diag(cq[0]))), float(alpha[ix] @ w)))
+    return out
+
+
+def oracle_folds(p, coords, values, metric, i, fi, fo):
+    """the slow truth: per fold, the data without the fold -> joint_predict at the fold's sites of process i"""
+    pred, err = np.full(len(fi), np.nan), np.full(len(fi), np.nan)
+    for f in range(int(fi.max()) + 1):
+        sel = np.flatnonzero(fi == f)
+        keep_i = fi != f
+        keep_o = np.ones(len(coords[1 - i]), dtype=bool) if fo is None else fo != f
+        c, v = [None, None], [None, None]
+        c[i], v[i] = coords[i][keep_i], values[i][keep_i]
+        c[1 - i], v[1 - i] = coords[1 - i][keep_o], values[1 - i][keep_o]
+        pred[sel], err[sel] = orc.joint_predict(p, c, v, coords[i][sel], i, metric)
+    return pred, err
+
+
+def labels_from_sizes(rng, n, i, sizes, other=True):
+    """(fi, fo, sizes): fold f holds sizes[f] data scattered by a permutation, its first a datum of process i, the others
+    from both processes (other: else process i alone; fo is then None); the data left over are labelled -1"""
+    n_o = n[1 - i] if len(n) == 2 and other else 0
+    own = rng.permutation(n[i])
+    assert len(sizes) <= n[i] and sum(sizes) <= n[i] + n_o
+    lab = [np.full(n[i], -1, dtype=np.int32), np.full(n_o, -1, dtype=np.int32)]
+    for f in range(len(sizes)):
+        lab[0][own[f]] = f
+    pool = np.concatenate([own[len(sizes):], n[i] + np.arange(n_o)])
+    pool = pool[rng.permutation(len(pool))]
+    at = 0
+    for f, s in enumerate(sizes):
+        rest = pool[at:at + s - 1]
+        lab[0][rest[rest < n[i]]] = f
+        lab[1][rest[rest >= n[i]] - n[i]] = f
+        at += s - 1
+    return lab[0], (lab[1] if n_o else None), list(sizes)
+
+
+def fold_sizes(n_i, total):
+    """two singleton folds, a fold of 2, one of min(64, what is left) and the rest as one fold, as far as the `total` data
+    (n_i of them of the predicted process, one per fold at least) go; a process of one datum is one fold"""
+    if n_i == 1:
+        return [min(64, max(1, total - 1))]
+    sizes, left = [], total
+    for w in (1, 1, 2, 64, total):
+        w = min(w, left)
+        if w > 0 and len(sizes) < n_i:
+            sizes.append(w)
+            left -= w
+    return sizes
+
+
+def fold_labels(case, i, other, minus, seed=0):
+    """the labels of a FOLD_CASES entry: (fi, fo, sizes).  other: the folds take data of the other process too; minus: about
+    a tenth of the data (one at least) is never withheld"""
+    n = [k for k in case[:2] if k > 0]
+    rng = np.random.default_rng(1000 * seed + 100 * i + 10 * other + minus + case[0])
+    total = n[i] + (n[1 - i] if len(n) == 2 and other else 0)
+    if minus and total >= 3:
+        total -= max(1, total // 10)
+    return labels_from_sizes(rng, n, i, fold_sizes(n[i], total), other)
+
+
+def fold_members(n, i, fi, fo):
+    """the folds' index arrays in the caller's stacked order (process 0 first), and per fold the positions inside it of
+    the data of process i with their indices in process i"""
+    off = [0, n[0]]
+    mem, mine = [], []
+    for f in range(int(fi.max()) + 1):
+        a = np.flatnonzero(fi == f)
+        b = np.flatnonzero(fo == f) if fo is not None else np.zeros(0, dtype=np.int64)
+        ix = np.concatenate([off[i] + a, off[1 - i] + b]) if len(n) == 2 else a
+        mem.append(ix)
+        mine.append((np.arange(len(a)), a))
+    return mem, mine
+
+
+def folds_references(S, z, n, calls):
+    """per call (i, fi, fo): (pred, var) over the data of process i (NaN where fi == -1) and the n_folds x 3 statistics,
+    from ONE dense_folds over the folds of all calls (Sigma^-1 is formed once)"""
+    plans = [fold_members(n, i, fi, fo) for i, fi, fo in calls]
+    res = iter(dense_folds(S, z, [ix for mem, _ in plans for ix in mem]))
+    out = []
+    for (i, fi, fo), (mem, mine) in zip(calls, plans):
+        pred, var = np.full(len(fi), np.nan), np.full(len(fi), np.nan)
+        stats = np.zeros((len(mem), 3))
+        for f in range(len(mem)):
+            pr, vr, ld, qf = next(res)
+            at, a = mine[f]
+            pred[a], var[a] = pr[at], vr[at]
+            stats[f] = len(mem[f]), ld, qf
+        out.append((pred, var, stats))
+    return out
+
+
+def folds_reference(S, z, n, i, fi, fo):
+    return folds_references(S, z, n, [(i, fi, fo)])[0]

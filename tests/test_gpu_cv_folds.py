@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from oracle import cokrige_oracle as orc
+from tests.dense_chains import oracle_folds   # the slow truth: one refit per fold through the oracle's joint_predict
 
 pytestmark = pytest.mark.gpu
 
@@ -72,20 +73,6 @@ def handle(native, p, coords, values, metric):
     h.assemble_joint()
     assert h.factor() == 0
     return h
-
-
-def oracle_folds(p, coords, values, metric, i, fi, fo):
-    """the slow truth: per fold, the data without the fold -> joint_predict at the fold's sites of process i"""
-    pred, err = np.full(len(fi), np.nan), np.full(len(fi), np.nan)
-    for f in range(int(fi.max()) + 1):
-        sel = np.flatnonzero(fi == f)
-        keep_i = fi != f
-        keep_o = np.ones(len(coords[1 - i]), dtype=bool) if fo is None else fo != f
-        c, v = [None, None], [None, None]
-        c[i], v[i] = coords[i][keep_i], values[i][keep_i]
-        c[1 - i], v[1 - i] = coords[1 - i][keep_o], values[1 - i][keep_o]
-        pred[sel], err[sel] = orc.joint_predict(p, c, v, coords[i][sel], i, metric)
-    return pred, err
 
 
 def check(pred, err, rp, re, what):

@@ -1,16 +1,16 @@
 """GPU tests of the Fisher information of the likelihood fit: include/cokrige.h ck_loglik_fisher, native.Handle.fisher and
 model.MultivariateMatern.information / fit_likelihood(std_errors=True) against a dense numpy chain on the oracle's
-covariances: D_k = dSigma/dtheta_k (nu and len by 4th-order central differences of the block they enter, with the steps of
-tests/test_gpu_likelihood.py's fd_grad; sigma, rho, nugget and noise-scale derivatives as exact block expressions) and
-I = 1/2 tr(S^-1 D_j S^-1 D_k) through cho_solve (REML: P formed densely).  One reference per data set and module."""
+covariances (tests/dense_chains.py: dense_fisher): D_k = dSigma/dtheta_k (nu and len by 4th-order central differences of
+the block they enter, with the steps of tests/test_gpu_likelihood.py's fd_grad; sigma, rho, nugget and noise-scale derivatives
+as exact block expressions) and I = 1/2 tr(S^-1 D_j S^-1 D_k) through cho_solve (REML: P formed densely).  One reference per
+data set and module.  tests/test_gpu_newer_entry_edge_sizes.py runs the same reference over the size ladder."""
 import warnings
 from ctypes import byref, c_int64
 
 import numpy as np
 import pytest
-from scipy.linalg import cho_factor, cho_solve
 
-from oracle import cokrige_oracle as orc
+from tests.dense_chains import dense_fisher as reference, normalised
 from tests.test_gpu_likelihood import BIV, BIV_EUC, BIV_HALF, EUC, HAV, UNI, handle, make_data
 
 pytestmark = pytest.mark.gpu
@@ -26,90 +26,6 @@ def native():
     return nat
 
 
-def _corr(nu, ls, d):
-    return orc.matern_correlation(nu, ls, d).reshape(d.shape)
-
-
-def _d4(f, x):
-    """4th-order central difference of f at x with fd_grad's step"""
-    e = 1e-3 * max(abs(x), 1.0)
-    return (f(x - 2 * e) - 8 * f(x - e) + 8 * f(x + e) - f(x + 2 * e)) / (12 * e)
-
-
-def derivative_matrices(params, coords, metric, noise=None):
-    """{slot: D_slot} (N x N each) over the 13 slots of ck_loglik_fisher; noise: per process the variances d_a or None"""
-    p = orc.Params.from_flat(params)
-    n = [len(c) for c in coords]
-    N = sum(n)
-    off = [0, n[0]]
-    D = {}
-
-    def put(i, j, blk):
-        M = np.zeros((N, N))
-        M[off[i]:off[i] + n[i], off[j]:off[j] + n[j]] = blk
-        if i != j:
-            M[off[j]:off[j] + n[j], off[i]:off[i] + n[i]] = blk.T
-        return M
-
-    d00 = orc.distance_matrix(coords[0], coords[0], metric)
-    if p.n_procs == 1:
-        s, nu, ls = p.sigma[0], p.nu[0, 0], p.len_scale[0, 0]
-        D[0] = put(0, 0, 2 * s * _corr(nu, ls, d00))
-        D[1] = put(0, 0, s * s * _d4(lambda x: _corr(x, ls, d00), nu))
-        D[2] = put(0, 0, s * s * _d4(lambda x: _corr(nu, x, d00), ls))
-        D[3] = put(0, 0, (d00 == 0).astype(float))
-    else:
-        d01 = orc.distance_matrix(coords[0], coords[1], metric)
-        d11 = orc.distance_matrix(coords[1], coords[1], metric)
-        s1, s2, rho = p.sigma[0], p.sigma[1], p.rho
-        R00 = _corr(p.nu[0, 0], p.len_scale[0, 0], d00)
-        R01 = _corr(p.nu[0, 1], p.len_scale[0, 1], d01)
-        R11 = _corr(p.nu[1, 1], p.len_scale[1, 1], d11)
-        D[0] = put(0, 0, 2 * s1 * R00) + put(0, 1, rho * s2 * R01)
-        D[1] = put(1, 1, 2 * s2 * R11) + put(0, 1, rho * s1 * R01)
-        D[2] = put(0, 0, s1 * s1 * _d4(lambda x: _corr(x, p.len_scale[0, 0], d00), p.nu[0, 0]))
-        D[3] = put(0, 1, rho * s1 * s2 * _d4(lambda x: _corr(x, p.len_scale[0, 1], d01), p.nu[0, 1]))
-        D[4] = put(1, 1, s2 * s2 * _d4(lambda x: _corr(x, p.len_scale[1, 1], d11), p.nu[1, 1]))
-        D[5] = put(0, 0, s1 * s1 * _d4(lambda x: _corr(p.nu[0, 0], x, d00), p.len_scale[0, 0]))
-        D[6] = put(0, 1, rho * s1 * s2 * _d4(lambda x: _corr(p.nu[0, 1], x, d01), p.len_scale[0, 1]))
-        D[7] = put(1, 1, s2 * s2 * _d4(lambda x: _corr(p.nu[1, 1], x, d11), p.len_scale[1, 1]))
-        D[8] = put(0, 0, (d00 == 0).astype(float))
-        D[9] = put(1, 1, (d11 == 0).astype(float))
-        D[10] = put(0, 1, s1 * s2 * R01)
-    for k in range(p.n_procs):
-        if noise is not None and noise[k] is not None:
-            D[11 + k] = put(k, k, np.diag(np.asarray(noise[k], dtype=float)))
-    return D
-
-
-def dense_sigma(params, coords, metric, noise=None, scales=(1.0, 1.0)):
-    S = orc.joint_cov(orc.Params.from_flat(params), coords, metric)
-    if noise is not None:
-        dv = np.concatenate([scales[k] * np.asarray(noise[k], dtype=float) if noise[k] is not None else np.zeros(len(coords[k]))
-                             for k in range(len(coords))])
-        S = S + np.diag(dv)
-    return S
-
-
-def reference(params, coords, metric, noise=None, scales=(1.0, 1.0), X=None):
-    """the 13 x 13 information of the dense chain (rows / columns of slots that do not exist are 0)"""
-    S = dense_sigma(params, coords, metric, noise, scales)
-    D = derivative_matrices(params, coords, metric, noise)
-    cf = cho_factor(S, lower=True)
-    if X is None:
-        B = {k: cho_solve(cf, Dk) for k, Dk in D.items()}
-    else:
-        H = cho_solve(cf, X)
-        P = cho_solve(cf, np.eye(S.shape[0])) - H @ np.linalg.solve(X.T @ H, H.T)
-        B = {k: P @ Dk for k, Dk in D.items()}
-    ref = np.zeros((13, 13))
-    for j in B:
-        for k in B:
-            if k >= j:
-                ref[j, k] = ref[k, j] = 0.5 * np.sum(B[j] * B[k].T)
-    return ref
-
-
 _CASES = {}
 
 
@@ -119,16 +35,6 @@ def case(name, seed, params, metric, n0, n1):
         coords, values = make_data(seed, params, metric, n0=n0, n1=n1)
         _CASES[name] = (coords, values, reference(params, coords, metric))
     return _CASES[name]
-
-
-def normalised(I, ref):
-    """|I - ref| / sqrt(ref_jj ref_kk) over the entries whose scale is positive; the others must be equal"""
-    d = np.sqrt(np.outer(np.diag(ref), np.diag(ref)))
-    pos = d > 0
-    assert np.array_equal(I[~pos], ref[~pos]), (I[~pos], ref[~pos])
-    e = np.zeros_like(I)
-    e[pos] = np.abs(I - ref)[pos] / d[pos]
-    return e
 
 
 def check_against(I, ref, exact):
