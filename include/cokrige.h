@@ -305,6 +305,45 @@ int ck_loglik_noise_grad(ck_handle* h, double* out2);
 #define CK_FISHER_NPAR 13
 int ck_loglik_fisher(ck_handle* h, int reml, const int32_t* free13, double* fisher_host, int64_t* info);
 
+/* Vecchia's approximation of the log-likelihood on the local solver: the joint density as a product of conditionals, every
+ * datum conditioned on a small set of data that come earlier in a fixed ordering -- a likelihood where Sigma does not fit.
+ * The N data of all processes carry distinct integer ranks (rank_host, stacked: process 0 then 1; any distinct integers).  For
+ * datum t (process i_t, value z_t, rank rho_t) and process q:
+ *   - the candidates C_tq are the sites s of process q with rho_s < rho_t and d(s, t) <= max_dist, d the distance the local
+ *     kernels compute on the device.  d = 0 is allowed: a co-located partner of the other process, or an earlier duplicate of
+ *     the same process, is a legitimate conditioning datum;
+ *   - the cap is the handle's ck_set_local_neighbours(nmax0, nmax1), its rule unchanged: with nmax_q > 0 and |C_tq| > nmax_q,
+ *     r_tq = the nmax_q-th smallest d over C_tq and the set is {s in C_tq : d <= r_tq} (ties kept); otherwise all of C_tq.
+ *     (0, 0): every earlier datum within max_dist;
+ *   - with c(t) the union over q, the local system of ck_predict_local for prediction process i_t at the datum's own
+ *     coordinates: Sigma_loc = L L^T (ck_set_noise's s d on its diagonal when noise is on), v = L^-1 c, y = L^-1 z_c;
+ *   - mu_t = v . y,  s_t^2 = sigma_i^2 + nugget_i + (s_i d_t if noise is on) - v . v: the variance of the OBSERVATION, raw (not
+ *     ck_predict_local's clamped square root).  An empty set gives mu_t = 0 and s_t^2 = the prior observation variance; it is
+ *     counted (stats3[0]) and is not an error.
+ * out3 = (l, sum_t log s_t^2, sum_t (z_t - mu_t)^2 / s_t^2),  l = -1/2 (N log 2 pi + out3[1] + out3[2]): ck_loglik's three slots
+ * on purpose -- when every earlier datum is in every set the three numbers equal the dense ones whatever the ordering
+ * (sum_t log s_t^2 = log|Sigma|, and the quadratic forms agree).
+ * A datum whose local system is not positive definite, or whose s_t^2 is not > 0, makes out3 NaN and *info = 1 + that datum's
+ * index in the caller's stacked order (the first such datum); the call still returns 0 and the per-datum outputs stay valid
+ * for every other datum.  *info = 0 otherwise.
+ * mean_host, var_host (N, or NULL): mu_t and s_t^2;  count_host (N x 2, or NULL): the set's sizes per process;  stats3 (or NULL):
+ * data with an empty set, the largest set, data where a cap bound.  All in the caller's stacked order.
+ * The result depends on the ranks, the distances and the caps -- not on option "site_order", on chunking or on the order of
+ * ck_set_data, beyond rounding.  Every sum has a fixed order: the N terms are reduced in the caller's stacked order by a fixed
+ * tree (256 consecutive terms per workgroup, then the workgroups' sums), no atomics; repeated calls give the same bits.
+ * Needs ck_set_model / ck_set_data only, plus ck_set_noise and the caps if wanted.  It never allocates Sigma panels and
+ * invalidates nothing: a resident factor, the solved right-hand sides and ck_predict's bits are as before the call.  The ranks
+ * are permuted to the internal site order inside the call and kept nowhere.  The data of process i are the points of one pass
+ * of the local solver with i_pred = i (select pass, then both size classes as in ck_predict_local), one pass per process.
+ * Refused through ck_last_error: a partitioned handle; a trend set on the handle (REML is not defined here); two equal ranks
+ * (both data are named); a non-finite or negative max_dist; NULL rank_host or out3.
+ * ck_timings [72 ..]: the select pass, the solves of both size classes, the term reduction, host wall clock (ms), the number of
+ * data whose set fits the LDS class (<= 64, the empty ones among them) and the number beyond it; [60 ..] hold the select
+ * pass's counters summed over both passes. */
+int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host /* N, stacked: process 0 then 1 */, double max_dist,
+                      double* out3, double* mean_host /* N or NULL */, double* var_host /* N or NULL */,
+                      int32_t* count_host /* N x 2 or NULL */, int64_t* stats3 /* n_empty, k_max, n_capped */, int64_t* info);
+
 /* Simulation draw z = L eps in the caller's stacked order (process 0 sites, then process 1):
  * sim.BivariateRandomField._simulate (src/sim.py:52-54: cholesky(cmat, lower=True) @ noise).
  * n = number of observations; needs ck_factor. */
@@ -585,7 +624,10 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * pass (device; it is the counting pass of a capped call and part of [10]); [61] points with at least one capped process;
  * [62] the largest candidate count of a point (both processes together) before the cap; [63] points where a process had more
  * candidates than the LDS lists hold (option "local_select_cap") and re-scanned its chunks every round.  All 0 after an
- * uncapped local call. */
+ * uncapped local call.
+ * ck_loglik_vecchia (n up to 78): [72] the select passes of both processes; [73] the solves of both size classes; [74] the
+ * terms and their reduction (k_vecchia_terms, k_vecchia_sum); [75] host wall clock of the call; [76] / [77] number of data in
+ * the LDS class (empty sets included) / beyond it.  [10], [14] and [60 ..] then hold the sums over its two passes. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it

@@ -31,9 +31,10 @@
 #include "ck_internal.h"
 #include "ck_tilemap.h"
 #include "ck_model.h"
+#include "ck_vecchia.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 72
+#define CK_N_TIMINGS 80
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -328,7 +329,7 @@ struct CallGuard {
 static int64_t aux_cap(const ck_handle* h) { return (int64_t)h->aux_own.cap(); }               // doubles
 static long long local_slab_doubles(const ck_handle* h) { return (long long)h->local_slab.cap(); }
 
-extern "C" int ck_version(void) { return 102; }
+extern "C" int ck_version(void) { return 103; }
 extern "C" int ck_device_count(int* n) {
     HIPCHK(hipGetDeviceCount(n));
     return 0;
@@ -3545,8 +3546,19 @@ struct LocalUniv {
     int64_t* n_rank_def;
 };
 
+// The Vecchia likelihood's extras (ck_loglik_vecchia); null: a prediction.  The points are the data of process i in the caller's
+// order; a site is a neighbour only if it comes earlier in the ordering than the point.  The select pass always runs (it is
+// what counts per process), with the handle's caps or none.
+struct LocalVecchia {
+    const int* d_rs;      // device: position in the ordering of every site, internal site order (Npad ints)
+    const int* rp;        // host: the m points' positions
+    double* vv;           // host, m: the raw v . v of every solved point (0 where the set is empty)
+    int32_t* cnt2;        // host, m x 2: conditioning data of process 0 / 1
+};
+
 static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_t m, double max_dist, int cv, double* pred,
-                              double* pred_err, int64_t* n_empty, int64_t* n_not_pd, int64_t* k_max, const LocalUniv* u) {
+                              double* pred_err, int64_t* n_empty, int64_t* n_not_pd, int64_t* k_max, const LocalUniv* u,
+                              const LocalVecchia* vc = nullptr) {
     if (ensure_layout(h, false)) return -1;   // sites, tables, chunk bounds -- no Sigma panels
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
     if (m < 0 || (m > 0 && !pcoords)) return fail("bad pcoords");
@@ -3576,7 +3588,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     // the neighbour cap (ck_set_local_neighbours): the select pass replaces the counting pass and leaves every point's cut
     // distances and culling chord for the later launches; no cap: none of this exists and no kernel sees a new pointer
     const int nmax0 = local_nmax_of(h, 0), nmax1 = local_nmax_of(h, 1);
-    const bool capped = nmax0 > 0 || nmax1 > 0;
+    const bool capped = nmax0 > 0 || nmax1 > 0 || vc;
     int* d_sel = nullptr;
     double *d_rq = nullptr, *d_cp = nullptr;
     if (capped) {
@@ -3584,7 +3596,15 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
         HIPCHK(tmp.get(&d_rq, (size_t)(2 * mp * 8)));
         HIPCHK(tmp.get(&d_cp, (size_t)(mp * 8)));
     }
-    const CkLocalCap cap{d_rq, d_cp};
+    int* d_rp = nullptr;
+    double* d_vv = nullptr;
+    if (vc) {
+        HIPCHK(tmp.get(&d_rp, (size_t)(mp * sizeof(int))));
+        HIPCHK(tmp.get(&d_vv, (size_t)(mp * 8)));
+        HIPCHK(hipMemsetAsync(d_vv, 0, (size_t)(mp * 8), h->stream));
+        HIPCHK(hipMemcpyAsync(d_rp, vc->rp, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    }
+    const CkLocalCap cap{d_rq, d_cp, vc ? vc->d_rs : nullptr, d_rp};
     // universal form: the regressors of the prediction points (a point with a non-finite one is settled on the host at the
     // end and computes with zeros meanwhile), the status of every point, the local coefficients
     double *d_f0 = nullptr, *d_beta = nullptr;
@@ -3611,7 +3631,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     const double cmax = local_cmax(h, max_dist);
     if (capped)
         ck_launch_local_select(h->stream, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, layout_of(h), h->d_chunkb, cmax,
-                               d_pu, nmax0, nmax1, local_key_cap(h), d_cnt, d_sel, d_rq, d_cp);
+                               d_pu, nmax0, nmax1, local_key_cap(h), d_cnt, d_sel, d_rq, d_cp, cap);
     else
         ck_launch_local_count(h->stream, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, layout_of(h), d_cnt,
                               h->d_chunkb, cmax, d_pu);
@@ -3679,7 +3699,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
         for (const auto& bt : plan.batches)
             ck_launch_local_solve(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, bt.first, bt.second - bt.first,
                                   mp, h->s0, h->z, layout_of(h), d_cnt, d_off, d_slab, c0var, d_out, d_out + mp, h->d_tabs,
-                                  h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb, cmax, nz, cap);
+                                  h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb, cmax, nz, cap, d_vv);
     HIPCHK(hipGetLastError());
     std::vector<hipEvent_t> ev_red;   // universal form: an event pair around every batch's reduction (ck_timings [50])
     struct EvFree {
@@ -3717,7 +3737,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
                                           d_out + mp, Tr, d_beta, d_stat);
                 HIPCHK(hipEventRecord(e1, h->stream));
             } else {
-                ck_launch_local_reduce_t(h->stream, bsys, nb, d_slab, d_linfo + tb.first, c0var, d_out, d_out + mp);
+                ck_launch_local_reduce_t(h->stream, bsys, nb, d_slab, d_linfo + tb.first, c0var, d_out, d_out + mp, d_vv);
             }
             HIPCHK(hipGetLastError());
         }
@@ -3726,6 +3746,13 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     HIPCHK(hipEventRecord(h->ev3, h->stream));
     HIPCHK(hipMemcpyAsync(pred, d_out, m * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(pred_err, d_out + mp, m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (vc) {
+        HIPCHK(hipMemcpyAsync(vc->vv, d_vv, m * 8, hipMemcpyDeviceToHost, h->stream));
+        for (int64_t p = 0; p < m; ++p) {
+            vc->cnt2[2 * p] = sel[(size_t)(4 * p)];
+            vc->cnt2[2 * p + 1] = sel[(size_t)(4 * p + 1)];
+        }
+    }
     HIPCHK(hipStreamSynchronize(h->stream));
     double ms = 0, ms2 = 0;
     HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms));
@@ -3798,6 +3825,163 @@ extern "C" int ck_predict_local_universal(ck_handle* h, int i, const double* pco
     if (m > 0 && h->trend_p[i] > 0 && !f0) return fail("ck_predict_local_universal: null regressors of the prediction sites");
     const LocalUniv u{f0, beta, n_rank_def};
     return predict_local_impl(h, i, pcoords, m, max_dist, cv, pred, pred_err, n_empty, n_not_pd, k_max, &u);
+}
+
+// ---------------------------------------------------------------------------------------
+// the Vecchia likelihood (include/cokrige.h has the definition)
+// ---------------------------------------------------------------------------------------
+// ranks (distinct integers, the caller's stacked order) -> positions 0 .. N - 1 in the ordering; two equal ranks: -1 and both
+// data in dup.  Ranks that already are a permutation of 0 .. N - 1 (what vecchia.ordering_ranks hands over) cost one pass
+static int vecchia_positions(const int64_t* rank, int64_t N, std::vector<int>& pos, int64_t dup[2]) {
+    pos.resize((size_t)N);
+    std::vector<char> seen((size_t)N, 0);
+    bool direct = true;
+    for (int64_t t = 0; t < N && direct; ++t) {
+        const int64_t r = rank[t];
+        if (r < 0 || r >= N || seen[(size_t)r]) {
+            direct = false;
+        } else {
+            seen[(size_t)r] = 1;
+            pos[(size_t)t] = (int)r;
+        }
+    }
+    if (direct) return 0;
+    std::vector<int64_t> ix((size_t)N);
+    for (int64_t t = 0; t < N; ++t) ix[(size_t)t] = t;
+    std::sort(ix.begin(), ix.end(), [&](int64_t a, int64_t b) { return rank[a] != rank[b] ? rank[a] < rank[b] : a < b; });
+    for (int64_t j = 0; j < N; ++j) {
+        if (j > 0 && rank[ix[(size_t)j]] == rank[ix[(size_t)(j - 1)]]) {
+            dup[0] = ix[(size_t)(j - 1)];
+            dup[1] = ix[(size_t)j];
+            return -1;
+        }
+        pos[(size_t)ix[(size_t)j]] = (int)j;
+    }
+    return 0;
+}
+
+extern "C" int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host, double max_dist, double* out3, double* mean_host,
+                                 double* var_host, int32_t* count_host, int64_t* stats3, int64_t* info) {
+    CHKH(h);
+    if (h->world != 1)
+        return fail("ck_loglik_vecchia is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) +
+                    ")");
+    if (!rank_host || !out3) return fail("ck_loglik_vecchia: null rank_host / out3");
+    if (!(max_dist >= 0.0) || !std::isfinite(max_dist))
+        return fail("ck_loglik_vecchia: max_dist must be finite and >= 0, got " + std::to_string(max_dist));
+    if (trend_total(h) > 0)
+        return fail("ck_loglik_vecchia: a trend of " + std::to_string(trend_total(h)) +
+                    " columns is set on the handle; the Vecchia likelihood has no REML form (clear it with ck_set_trend)");
+    if (ensure_layout(h, false)) return -1;   // sites, tables, chunk bounds -- no Sigma panels, nothing invalidated
+    if (ensure_noise(h)) return -1;
+    const auto t_begin = std::chrono::steady_clock::now();
+    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    const int64_t N = h->N, n0 = h->n[0];
+    if (N > INT32_MAX) return fail("ck_loglik_vecchia: more than 2^31 - 1 data");
+    std::vector<int> pos;
+    int64_t dup[2] = {0, 0};
+    if (vecchia_positions(rank_host, N, pos, dup))
+        return fail("ck_loglik_vecchia: data " + std::to_string(dup[0]) + " and " + std::to_string(dup[1]) +
+                    " (stacked order) have the same rank " + std::to_string((long long)rank_host[dup[0]]));
+    // the sites' positions in the internal order (padding: never searched)
+    std::vector<int> rs((size_t)h->Npad, INT32_MAX);
+    for (int k = 0; k < h->n_procs; ++k) {
+        const int64_t off = k == 0 ? 0 : h->n0p, soff = k == 0 ? 0 : n0;
+        for (int64_t j = 0; j < h->n[k]; ++j) rs[(size_t)(off + j)] = pos[(size_t)(soff + h->perm[k][(size_t)j])];
+    }
+    DevTemps tmp;
+    int* d_rs = nullptr;
+    HIPCHK(tmp.get(&d_rs, (size_t)h->Npad * sizeof(int)));
+    HIPCHK(hipMemcpyAsync(d_rs, rs.data(), (size_t)h->Npad * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    // one pass of the local solver per process: its data are the points, i_pred = the process
+    std::vector<double> mu((size_t)N), vv((size_t)N, 0.0), sd((size_t)N), prior((size_t)N), own((size_t)N, 0.0), zs((size_t)N);
+    std::vector<int32_t> cnt2((size_t)(2 * N), 0);
+    int64_t n_empty = 0, k_max = 0, n_capped = 0, n_rescan = 0, cand_max = 0;
+    double ms_select = 0.0, ms_solve = 0.0, ms_grow = 0.0;
+    for (int k = 0; k < h->n_procs; ++k) {
+        const int64_t nk = h->n[k], soff = k == 0 ? 0 : n0;
+        if (nk == 0) continue;
+        const LocalVecchia vc{d_rs, pos.data() + soff, vv.data() + soff, cnt2.data() + 2 * soff};
+        int64_t ne = 0, npd = 0, km = 0;
+        if (predict_local_impl(h, k, h->h_coords[k].data(), nk, max_dist, 0, mu.data() + soff, sd.data() + soff, &ne, &npd, &km,
+                               nullptr, &vc))
+            return -1;
+        n_empty += ne;
+        k_max = std::max(k_max, km);
+        ms_select += h->t_ms[60];
+        ms_solve += h->t_ms[10] - h->t_ms[60];
+        ms_grow += h->t_ms[14];
+        n_capped += (int64_t)h->t_ms[61];
+        cand_max = std::max(cand_max, (int64_t)h->t_ms[62]);
+        n_rescan += (int64_t)h->t_ms[63];
+        const double c0 = h->blk[2 * k].amp + h->blk[2 * k].nugget;
+        const bool nz = h->noise_on && !h->noise_var[k].empty();
+        for (int64_t t = 0; t < nk; ++t) {
+            prior[(size_t)(soff + t)] = c0;
+            zs[(size_t)(soff + t)] = h->h_values[k][(size_t)t];
+            if (nz) own[(size_t)(soff + t)] = h->noise_scale[k] * h->noise_var[k][(size_t)t];
+        }
+    }
+    const int kl = ck_local_lds_limit();
+    int64_t n_lds = 0;
+    for (int64_t t = 0; t < N; ++t) {
+        const int kt = cnt2[(size_t)(2 * t)] + cnt2[(size_t)(2 * t + 1)];
+        n_lds += kt <= kl;
+        if (kt > 0 && mu[(size_t)t] != mu[(size_t)t]) vv[(size_t)t] = NAN;   // not positive definite: no variance either
+    }
+    // the terms and their sums, in the caller's stacked order
+    const int64_t nblk = (N + 255) / 256;
+    double *d_z = nullptr, *d_mu = nullptr, *d_vv = nullptr, *d_prior = nullptr, *d_own = nullptr, *d_mean = nullptr, *d_var = nullptr,
+           *d_part = nullptr, *d_out = nullptr;
+    int* d_cnt2 = nullptr;
+    long long* d_bad = nullptr;
+    for (double** b : {&d_z, &d_mu, &d_vv, &d_prior, &d_own, &d_mean, &d_var}) HIPCHK(tmp.get(b, (size_t)(N * 8)));
+    HIPCHK(tmp.get(&d_part, (size_t)(2 * nblk * 8)));
+    HIPCHK(tmp.get(&d_out, (size_t)(2 * 8)));
+    HIPCHK(tmp.get(&d_cnt2, (size_t)(2 * N) * sizeof(int)));
+    HIPCHK(tmp.get(&d_bad, (size_t)(nblk + 1) * sizeof(long long)));
+    const std::pair<double*, const double*> up[] = {{d_z, zs.data()}, {d_mu, mu.data()}, {d_vv, vv.data()}, {d_prior, prior.data()},
+                                                    {d_own, own.data()}};
+    for (const auto& c : up) HIPCHK(hipMemcpyAsync(c.first, c.second, (size_t)(N * 8), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_cnt2, cnt2.data(), (size_t)(2 * N) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    ck_launch_vecchia_terms(h->stream, N, d_z, d_mu, d_vv, d_prior, h->noise_on ? d_own : nullptr, d_cnt2, d_mean, d_var, d_part,
+                            d_bad, d_out, d_bad + nblk);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    double sums[2] = {0.0, 0.0};
+    long long first_bad = 0;
+    HIPCHK(hipMemcpyAsync(sums, d_out, 2 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&first_bad, d_bad + nblk, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    if (mean_host) HIPCHK(hipMemcpyAsync(mean_host, d_mean, (size_t)(N * 8), hipMemcpyDeviceToHost, h->stream));
+    if (var_host) HIPCHK(hipMemcpyAsync(var_host, d_var, (size_t)(N * 8), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (count_host) memcpy(count_host, cnt2.data(), (size_t)(2 * N) * sizeof(int32_t));
+    out3[1] = sums[0];
+    out3[2] = sums[1];
+    out3[0] = first_bad ? NAN : ck_vecchia_total(N, sums[0], sums[1]);
+    if (first_bad) out3[1] = out3[2] = NAN;
+    if (info) *info = first_bad;
+    if (stats3) {
+        stats3[0] = n_empty;
+        stats3[1] = k_max;
+        stats3[2] = n_capped;
+    }
+    double ms_terms = 0;
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms_terms));
+    h->t_ms[10] = ms_select + ms_solve;
+    h->t_ms[14] = ms_grow;
+    h->t_ms[60] = ms_select;   // [60 ..]: over both passes
+    h->t_ms[61] = (double)n_capped;
+    h->t_ms[62] = (double)cand_max;
+    h->t_ms[63] = (double)n_rescan;
+    h->t_ms[72] = ms_select;
+    h->t_ms[73] = ms_solve;
+    h->t_ms[74] = ms_terms;
+    h->t_ms[75] = ms_since(t_begin);
+    h->t_ms[76] = (double)n_lds;
+    h->t_ms[77] = (double)(N - n_lds);
+    return 0;
 }
 
 // The reference builds the local predictor's state once, in its constructor (src/point_prediction.py:24-43: the full Sigma

@@ -331,9 +331,18 @@ void ck_launch_vario_bin(hipStream_t s, int metric, int same, int covariogram, c
 // cb: chunk bounds of the sites (ck_launch_local_chunk_bounds: 4 x ceil(nend / 256) doubles), cmax: largest chord
 // (distance in the space of the chord vectors su / pu) a neighbour can have, with its safety margin
 void ck_launch_local_chunk_bounds(hipStream_t s, const double* su, CkLayout L, double* cb);
+// The cut distances and culling chords a capped call's select pass leaves (ck_launch_local_select below), and the precedence
+// pointers (ck_loglik_vecchia): rs = every site's position in the caller's ordering (npad ints, internal site order),
+// rp = the points' (mpad ints); a site is searched only if rs[site] < rp[point].  Null: no such condition.
+struct CkLocalCap {
+    const double* rq = nullptr;
+    const double* cp = nullptr;
+    const int* rs = nullptr;
+    const int* rp = nullptr;
+};
 void ck_launch_local_count(hipStream_t s, int metric, int i_pred, int cv, double max_dist, const double* pc,
                            int64_t m, int64_t mpad, const double* sc, CkLayout L, int* counts, const double* cb,
-                           double cmax, const double* pu);
+                           double cmax, const double* pu, CkLocalCap cap = {} /* its precedence pointers only */);
 // The neighbour cap (ck_set_local_neighbours; include/cokrige.h has the rule).  ck_launch_local_select is the counting pass
 // of a capped call: per point and process the cut distance r_pq (rq: m x 2; max_dist where the cap does not bind) and the
 // final counts (sel: m x 4 ints -- neighbours of process 0, of process 1, candidates before the cap, flags), their sum in
@@ -342,14 +351,11 @@ void ck_launch_local_count(hipStream_t s, int metric, int i_pred, int cv, double
 // rounds re-scanning its chunks.  The later launches take (rq, cp) as CkLocalCap; null pointers: no cap, today's expressions.
 #define CK_LS_CAPPED 1   // sel flags: the cap binds for some process of the point
 #define CK_LS_RESCAN 2   //            some process had more candidates than key_cap
-struct CkLocalCap {
-    const double* rq = nullptr;
-    const double* cp = nullptr;
-};
 int ck_local_select_capacity();
 void ck_launch_local_select(hipStream_t s, int metric, int i_pred, int cv, double max_dist, const double* pc, int64_t m,
                             int64_t mpad, const double* sc, CkLayout L, const double* cb, double cmax, const double* pu,
-                            int nmax0, int nmax1, int key_cap, int* counts, int* sel, double* rq, double* cp);
+                            int nmax0, int nmax1, int key_cap, int* counts, int* sel, double* rq, double* cp,
+                            CkLocalCap cap = {} /* its precedence pointers only */);
 // slab_off[p]: offset (doubles) of point p's scratch slab ((k + 2) k doubles + k ints) when its
 // neighbourhood exceeds the LDS limit
 void ck_launch_local_solve(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
@@ -359,8 +365,14 @@ void ck_launch_local_solve(hipStream_t s, const CkMatern* blk, int metric, int i
                            const double* su, const double* pu, int k_hi, const double* cb, double cmax,
                            const double* nz = nullptr /* ck_set_noise: s d per site in the internal order, added to the diagonal
                            of every local system next to z[ga]; null: off (the same for the other local launches) */,
-                           CkLocalCap cap = {});
+                           CkLocalCap cap = {}, double* vv = nullptr /* the raw v . v of every solved point, or null */);
 int ck_local_lds_limit();
+// The Vecchia likelihood's terms (ck_loglik_vecchia), n data in the caller's stacked order: from (z, mu, v . v, prior variance,
+// own noise -- null: none --, the two counts) to mean / var per datum and, by a fixed tree over part (2 x ceil(n / 256) doubles)
+// and bad (ceil(n / 256) words), out2 = (sum log var, sum e^2 / var) and *info = 1 + the first datum without a term (0: none)
+void ck_launch_vecchia_terms(hipStream_t s, int64_t n, const double* z, const double* mu, const double* vv, const double* prior,
+                             const double* noise, const int* cnt2, double* mean, double* var, double* part, long long* bad,
+                             double* out2, long long* info);
 
 // Large neighbourhoods (k > k_hi above): the "tiled" path.  The systems of a batch are factored TOGETHER,
 // 64 columns per step, by launches over all systems that still have columns left (diagonal block + its
@@ -402,7 +414,7 @@ void ck_launch_local_tiled_trailing(hipStream_t s, const CkLocalSys* sys, double
 void ck_launch_local_tiled_left(hipStream_t s, const CkLocalSys* sys, double* slab, int n_active, int g0, int W,
                                 const int* kq_host);
 void ck_launch_local_reduce_t(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab,
-                              const long long* info, double c0var, double* pred, double* err);
+                              const long long* info, double c0var, double* pred, double* err, double* vv = nullptr);
 
 // Universal cokriging in the neighbourhood (ck_predict_local_universal): the p = p0 + p1 trend rows X_loc^T ride along each
 // local factorisation like c and z, and a GLS step per point (ck_local_gls.h) follows the reduction.

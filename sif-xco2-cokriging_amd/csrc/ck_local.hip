@@ -13,7 +13,9 @@
 // Systems with k <= 64 neighbours live in LDS (k_local_solve); larger ones go through the tiled path (batched
 // 64-column steps on the matrix cores, see below) or, if option "local_tile_min" says so, a global scratch slab
 // per point with a blocked factorisation in one workgroup (k_local_solve_big).
-// Universal cokriging in the neighbourhood (a GLS trend per point, ck_predict_local_universal): at the end of this file.
+// Universal cokriging in the neighbourhood (a GLS trend per point, ck_predict_local_universal): behind the tiled path.
+// The Vecchia likelihood (ck_loglik_vecchia) runs the same kernels with the data as the points and one more predicate in the
+// search -- only sites that come earlier in the caller's ordering (lp_later) -- and sums its terms at the end of this file.
 #include "ck_internal.h"
 #include "ck_select.h"
 
@@ -34,11 +36,16 @@ struct LpReach {
     double r0, r1, cmax;
 };
 
-// today's predicate (the candidates of the neighbour cap): *d is the device distance, *proc the site's process
+// Precedence (ck_loglik_vecchia): a site takes part only if it comes earlier in the ordering than the point -- rs holds the
+// sites' positions in the ordering (internal site order), rp is the point's.  rs null: no such condition, today's predicate.
+__device__ __forceinline__ bool lp_later(const int* rs, int rp, long g) { return rs && !(rs[g] < rp); }
+
+// the radius predicate (the candidates of the neighbour cap): *d is the device distance, *proc the site's process
 __device__ __forceinline__ bool lp_candidate(int metric, int cv, int i_pred, double max_dist, const CkLayout& L, long g,
                                              double p0, double p1, double p2, const double* s0, const double* s1,
-                                             const double* s2, double* d, int* proc) {
+                                             const double* s2, const int* rs, int rp, double* d, int* proc) {
     if (!(g < L.n0 || (g >= L.n0p && g < L.nend))) return false;
+    if (lp_later(rs, rp, g)) return false;
     *d = lp_dist(metric, p0, p1, p2, s0[g], s1[g], s2[g]);
     *proc = g >= L.n0p;
     if (cv && *proc == i_pred) return *d > 0.0 && *d <= max_dist;
@@ -47,8 +54,9 @@ __device__ __forceinline__ bool lp_candidate(int metric, int cv, int i_pred, dou
 
 __device__ __forceinline__ bool lp_is_neighbour(int metric, int cv, int i_pred, const LpReach& Q, const CkLayout& L, long g,
                                                 double p0, double p1, double p2, const double* s0, const double* s1,
-                                                const double* s2) {
+                                                const double* s2, const int* rs, int rp) {
     if (!(g < L.n0 || (g >= L.n0p && g < L.nend))) return false;
+    if (lp_later(rs, rp, g)) return false;
     const double d = lp_dist(metric, p0, p1, p2, s0[g], s1[g], s2[g]);
     const int proc = g >= L.n0p;
     const double lim = proc ? Q.r1 : Q.r0;
@@ -98,7 +106,11 @@ struct LpSearch {
     double cmax;
     const double* rq;   // neighbour cap: m x 2 cut distances and
     const double* cp;   // m culling chords of the points (both null: no cap)
+    const int* rs;      // precedence (ck_loglik_vecchia): the sites' positions in the ordering, internal site order, and
+    const int* rp;      // the m points' (both null: none)
 };
+
+__device__ __forceinline__ int lp_rank(const LpSearch& R, long p) { return R.rs ? R.rp[p] : 0; }
 
 __device__ __forceinline__ LpReach lp_reach(const LpSearch& R, long p, double max_dist) {
     if (R.rq) return LpReach{R.rq[2 * p], R.rq[2 * p + 1], R.cp[p]};
@@ -165,12 +177,13 @@ __global__ __launch_bounds__(LP_TPB) void k_local_count(int metric, int i_pred, 
     const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
     const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
     const LpReach Q = lp_reach(R, p, max_dist);
+    const int rp = lp_rank(R, p);
     const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
     int c = 0;
     for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
         if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;
         const long g = g0 + threadIdx.x;
-        c += (g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2)) ? 1 : 0;
+        c += (g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp)) ? 1 : 0;
     }
     red[threadIdx.x] = c;
     __syncthreads();
@@ -197,13 +210,13 @@ __global__ __launch_bounds__(LP_TPB) void k_local_count(int metric, int i_pred, 
 template <class F>
 __device__ __forceinline__ void ls_scan(int metric, int i_pred, int cv, double max_dist, const CkLayout& L, const LpSearch& R,
                                         const LpReach& Q, double p0, double p1, double p2, double q0, double q1, double q2,
-                                        const double* s0, const double* s1, const double* s2, F f) {
+                                        const double* s0, const double* s1, const double* s2, int rp, F f) {
     for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
         if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;
         const long g = g0 + threadIdx.x;
         double d;
         int proc;
-        if (g < L.nend && lp_candidate(metric, cv, i_pred, max_dist, L, g, p0, p1, p2, s0, s1, s2, &d, &proc)) f(proc, ck_sel_key(d));
+        if (g < L.nend && lp_candidate(metric, cv, i_pred, max_dist, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp, &d, &proc)) f(proc, ck_sel_key(d));
     }
 }
 
@@ -223,9 +236,10 @@ __global__ __launch_bounds__(LP_TPB) void k_local_select(int metric, int i_pred,
     const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
     const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
     const LpReach Q{max_dist, max_dist, R.cmax};   // the candidates are searched within max_dist
+    const int rp = lp_rank(R, p);
     if (tid < 2) ncand[tid] = 0;
     __syncthreads();
-    ls_scan(metric, i_pred, cv, max_dist, L, R, Q, p0, p1, p2, q0, q1, q2, s0, s1, s2, [&](int q, unsigned long long key) {
+    ls_scan(metric, i_pred, cv, max_dist, L, R, Q, p0, p1, p2, q0, q1, q2, s0, s1, s2, rp, [&](int q, unsigned long long key) {
         const unsigned slot = atomicAdd(&ncand[q], 1u);
         if (slot < (unsigned)key_cap) keys[q][slot] = key;
     });
@@ -250,7 +264,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_select(int metric, int i_pred,
                 }
             }
             if (rescan)
-                ls_scan(metric, i_pred, cv, max_dist, L, R, Q, p0, p1, p2, q0, q1, q2, s0, s1, s2, [&](int q, unsigned long long key) {
+                ls_scan(metric, i_pred, cv, max_dist, L, R, Q, p0, p1, p2, q0, q1, q2, s0, s1, s2, rp, [&](int q, unsigned long long key) {
                     if ((rescan >> q & 1u) && ck_sel_match(&st[q], key)) atomicAdd(&hist[q][ck_sel_digit(&st[q], key)], 1u);
                 });
             __syncthreads();
@@ -293,7 +307,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve(const CkMatern* __restri
                                                          double* __restrict__ pred, double* __restrict__ err,
                                                          long p_base, LpTab T, const double* __restrict__ su,
                                                          const double* __restrict__ pu, LpSearch R, int k_hi,
-                                                         const double* __restrict__ nz) {
+                                                         const double* __restrict__ nz, double* __restrict__ vv) {
     __shared__ double lS[(LP_KL + 2) * LP_KL];
     __shared__ int lidx[LP_KL];
     __shared__ int wsum[LP_TPB / 64];
@@ -315,6 +329,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve(const CkMatern* __restri
     const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;        // chord vectors (table path)
     const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
     const LpReach Q = lp_reach(R, p, max_dist);
+    const int rp = lp_rank(R, p);
     // storage: (k + 2) x k matrix (rows k, k + 1 carry c and z) and the neighbour index list
     double* S = lS;
     int* idx = lidx;
@@ -325,7 +340,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve(const CkMatern* __restri
     for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
         if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
         const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2);
+        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp);
         const unsigned long long bal = __ballot(f);
         const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
         if (lane == 0) wsum[wv] = __popcll(bal);
@@ -412,6 +427,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve(const CkMatern* __restri
     }
     if (tid == 0) {
         pred[p] = red[0][0];
+        if (vv) vv[p] = red[1][0];   // the raw v . v (ck_loglik_vecchia: the unclamped variance is the caller's)
         const double sd = sqrt(c0var - red[1][0]);
         err[p] = (sd == sd) ? fmax(sd, 0.0) : 0.0;   // np.nanmax([std, 0.0]), point_prediction.py:217
     }
@@ -440,7 +456,7 @@ __global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(const CkMatern* _
                                                              double* __restrict__ pred, double* __restrict__ err,
                                                              long p_base, LpTab T, const double* __restrict__ su,
                                                              const double* __restrict__ pu, int k_hi, LpSearch R,
-                                                             const double* __restrict__ nz) {
+                                                             const double* __restrict__ nz, double* __restrict__ vv) {
     __shared__ __attribute__((aligned(16))) double lbuf[2 * LB_IB * (64 + 4)];
     double (*At)[64 + 4] = reinterpret_cast<double (*)[64 + 4]>(lbuf);                 // At[c][r] = strip of the tile's rows
     double (*Bt)[64 + 4] = reinterpret_cast<double (*)[64 + 4]>(lbuf + LB_IB * (64 + 4));   // Bt[c][r] = ... columns
@@ -459,6 +475,7 @@ __global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(const CkMatern* _
     const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;        // chord vectors (table path)
     const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
     const LpReach Q = lp_reach(R, p, max_dist);
+    const int rp = lp_rank(R, p);
     double* S = slab + slab_off[p];   // (k + 2) x k, rows k and k + 1 carry c and z
     int* idx = reinterpret_cast<int*>(S + (long)(k + 2) * k);
     const long ld = k;
@@ -468,7 +485,7 @@ __global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(const CkMatern* _
     for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
         if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
         const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2);
+        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp);
         const unsigned long long bal = __ballot(f);
         const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
         if (lane == 0) wsum[wv] = __popcll(bal);
@@ -639,6 +656,7 @@ __global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(const CkMatern* _
     }
     if (tid == 0) {
         pred[p] = red[0][0];
+        if (vv) vv[p] = red[1][0];   // the raw v . v (ck_loglik_vecchia: the unclamped variance is the caller's)
         const double sd = sqrt(c0var - red[1][0]);
         err[p] = (sd == sd) ? fmax(sd, 0.0) : 0.0;   // np.nanmax([std, 0.0]), point_prediction.py:217
     }
@@ -646,9 +664,9 @@ __global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(const CkMatern* _
 
 void ck_launch_local_count(hipStream_t s, int metric, int i_pred, int cv, double max_dist, const double* pc,
                            int64_t m, int64_t mpad, const double* sc, CkLayout L, int* counts, const double* cb,
-                           double cmax, const double* pu) {
+                           double cmax, const double* pu, CkLocalCap cap) {
     if (m <= 0) return;
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, nullptr, nullptr};
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, nullptr, nullptr, cap.rs, cap.rp};
     k_local_count<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(metric, i_pred, cv, max_dist, pc, mpad, sc, L, counts, R, pu);
 }
 
@@ -656,9 +674,9 @@ int ck_local_select_capacity() { return LS_CAP; }
 
 void ck_launch_local_select(hipStream_t s, int metric, int i_pred, int cv, double max_dist, const double* pc, int64_t m,
                             int64_t mpad, const double* sc, CkLayout L, const double* cb, double cmax, const double* pu,
-                            int nmax0, int nmax1, int key_cap, int* counts, int* sel, double* rq, double* cp) {
+                            int nmax0, int nmax1, int key_cap, int* counts, int* sel, double* rq, double* cp, CkLocalCap cap) {
     if (m <= 0) return;
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, nullptr, nullptr};
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, nullptr, nullptr, cap.rs, cap.rp};
     key_cap = key_cap < 1 ? 1 : (key_cap > LS_CAP ? LS_CAP : key_cap);   // never beyond the LDS lists
     k_local_select<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(metric, i_pred, cv, max_dist, pc, mpad, sc, L, R, pu, nmax0, nmax1,
                                                               key_cap, counts, sel, rq, cp);
@@ -669,17 +687,18 @@ void ck_launch_local_solve(hipStream_t s, const CkMatern* blk, int metric, int i
                            const double* pc, int64_t p_base, int64_t m, int64_t mpad, const double* sc, const double* z,
                            CkLayout L, const int* counts, const long long* slab_off, double* slab, double c0var,
                            double* pred, double* err, const CkTable* tabs, const double* const* coefs, int use_tab,
-                           const double* su, const double* pu, int k_hi, const double* cb, double cmax, const double* nz, CkLocalCap cap) {
+                           const double* su, const double* pu, int k_hi, const double* cb, double cmax, const double* nz, CkLocalCap cap,
+                           double* vv) {
     if (m <= 0) return;
     const LpTab T{tabs, coefs, use_tab};
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp};
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp, cap.rs, cap.rp};
     k_local_solve<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L,
                                                              counts, slab_off, slab, c0var, pred, err, p_base, T, su, pu, R, k_hi,
-                                                             nz);
+                                                             nz, vv);
     if (slab && k_hi > LP_KL)   // some neighbourhood is larger than the LDS limit
         k_local_solve_big<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z,
                                                                      L, counts, slab_off, slab, c0var, pred, err,
-                                                                     p_base, T, su, pu, k_hi, R, nz);
+                                                                     p_base, T, su, pu, k_hi, R, nz, vv);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -725,13 +744,14 @@ __global__ __launch_bounds__(LP_TPB) void k_local_search_t(const CkMatern* __res
     const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;
     const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
     const LpReach Q = lp_reach(R, p, max_dist);
+    const int rp = lp_rank(R, p);
     double* S = slab + q.off;
     int* idx = reinterpret_cast<int*>(S + (long)CK_LT_ROWS(kq) * ld + CK_LT_NINV * 64 * 64);
     int base = 0, k0 = 0;   // k0: neighbours of process 0
     for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {   // ordered compaction, as in k_local_solve
         if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
         const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2);
+        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp);
         const unsigned long long bal = __ballot(f), bal0 = __ballot(f && g < L.n0p);
         const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
         if (lane == 0) {
@@ -907,7 +927,8 @@ __global__ __launch_bounds__(LT_TPB, 4) void k_local_assemble_t(const CkMatern* 
 // pred = v . y, var = c0 - v . v from the two solved rows
 __global__ __launch_bounds__(LP_TPB) void k_local_reduce_t(const CkLocalSys* __restrict__ sys, const double* __restrict__ slab,
                                                             const long long* __restrict__ info, double c0var,
-                                                            double* __restrict__ pred, double* __restrict__ err) {
+                                                            double* __restrict__ pred, double* __restrict__ err,
+                                                            double* __restrict__ vv) {
     __shared__ double red[2][LP_TPB];
     const int tid = threadIdx.x;
     const CkLocalSys q = sys[blockIdx.x];
@@ -937,6 +958,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_reduce_t(const CkLocalSys* __r
     }
     if (tid == 0) {
         pred[q.p] = red[0][0];
+        if (vv) vv[q.p] = red[1][0];
         const double sd = sqrt(c0var - red[1][0]);
         err[q.p] = (sd == sd) ? fmax(sd, 0.0) : 0.0;   // np.nanmax([std, 0.0]), point_prediction.py:217
     }
@@ -949,7 +971,7 @@ void ck_launch_local_assemble_t(hipStream_t s, const CkMatern* blk, int metric, 
                                 const double* cb, double cmax, int* k0buf, const double* nz, CkLocalCap cap) {
     if (n_sys <= 0) return;
     const LpTab T{tabs, coefs, use_tab};
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp};
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp, cap.rs, cap.rp};
     k_local_search_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L, sys,
                                                                     slab, T, su, pu, R, k0buf);
     const int nreg = L.nend > L.n0p ? 3 : 1;               // a second process?
@@ -960,9 +982,9 @@ void ck_launch_local_assemble_t(hipStream_t s, const CkMatern* blk, int metric, 
 }
 
 void ck_launch_local_reduce_t(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab,
-                              const long long* info, double c0var, double* pred, double* err) {
+                              const long long* info, double c0var, double* pred, double* err, double* vv) {
     if (n_sys <= 0) return;
-    k_local_reduce_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(sys, slab, info, c0var, pred, err);
+    k_local_reduce_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(sys, slab, info, c0var, pred, err, vv);
 }
 
 int ck_local_lds_limit() { return LP_KL; }
@@ -1049,6 +1071,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve_u(const CkMatern* __rest
     const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;
     const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
     const LpReach Q = lp_reach(R, p, max_dist);
+    const int rp = lp_rank(R, p);
     double* S = lu_lds;
     double* E = lu_lds + (LP_KL + nx) * LP_KL;
     int* idx = lidx;
@@ -1059,7 +1082,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve_u(const CkMatern* __rest
     for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
         if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
         const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2);
+        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp);
         const unsigned long long bal = __ballot(f), bal0 = __ballot(f && g < L.n0p);
         const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
         if (lane == 0) {
@@ -1150,7 +1173,7 @@ void ck_launch_local_solve_u(hipStream_t s, const CkMatern* blk, int metric, int
                              const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status, const double* nz, CkLocalCap cap) {
     if (m <= 0) return;
     const LpTab T{tabs, coefs, use_tab};
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp};
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp, cap.rs, cap.rp};
     const int np = Tr.p0 + Tr.p1;
     const size_t lds = (size_t)((LP_KL + 2 + np) * LP_KL + LU_EXTRA(np)) * sizeof(double);   // 34.9 KB (p = 2) .. 47.2 KB (p = 16)
     k_local_solve_u<<<dim3((unsigned)m), dim3(LP_TPB), lds, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L, counts,
@@ -1223,4 +1246,92 @@ void ck_launch_local_reduce_ut(hipStream_t s, const CkLocalSys* sys, int n_sys, 
     if (n_sys <= 0) return;
     k_local_reduce_ut<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(sys, slab, info, k0buf, i_pred, c0var, pred, err, Tr, beta,
                                                                      status);
+}
+
+// ---------------------------------------------------------------------------------------
+// the Vecchia likelihood's terms (ck_loglik_vecchia; include/cokrige.h has the definition, ck_vecchia.h a term's arithmetic)
+// ---------------------------------------------------------------------------------------
+// k_vecchia_terms: one thread per datum, in the caller's stacked order; a workgroup's LP_TPB terms are summed by a fixed tree
+// in LDS into part[2 b], part[2 b + 1], and bad[b] = 1 + the smallest index of a datum without a term (0: none).
+// k_vecchia_sum (one workgroup): thread t adds the partial sums t, t + LP_TPB, .. in that order, the same tree finishes.
+// No atomics, no dependence on the launch: repeated calls give the same bits.
+#include "ck_vecchia.h"
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_terms(long n, const double* __restrict__ z, const double* __restrict__ mu,
+                                                           const double* __restrict__ vv, const double* __restrict__ prior,
+                                                           const double* __restrict__ noise, const int* __restrict__ cnt2,
+                                                           double* __restrict__ mean, double* __restrict__ var,
+                                                           double* __restrict__ part, long long* __restrict__ bad) {
+    __shared__ double red[2][LP_TPB];
+    __shared__ long long first[LP_TPB];
+    const int tid = threadIdx.x;
+    const long t = (long)blockIdx.x * LP_TPB + tid;
+    double lv = 0.0, qd = 0.0;
+    long long b = 0;
+    if (t < n) {
+        double m, s2;
+        if (ck_vecchia_term(z[t], mu[t], vv[t], prior[t], noise ? noise[t] : 0.0, cnt2[2 * t] + cnt2[2 * t + 1], &m, &s2, &lv, &qd))
+            b = t + 1;
+        mean[t] = m;
+        var[t] = s2;
+    }
+    red[0][tid] = lv;
+    red[1][tid] = qd;
+    first[tid] = b;
+    __syncthreads();
+    for (int s = LP_TPB / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            red[0][tid] += red[0][tid + s];
+            red[1][tid] += red[1][tid + s];
+            const long long o = first[tid + s];
+            if (o != 0 && (first[tid] == 0 || o < first[tid])) first[tid] = o;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        part[2 * blockIdx.x] = red[0][0];
+        part[2 * blockIdx.x + 1] = red[1][0];
+        bad[blockIdx.x] = first[0];
+    }
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_sum(long nblk, const double* __restrict__ part, const long long* __restrict__ bad,
+                                                         double* __restrict__ out2, long long* __restrict__ info) {
+    __shared__ double red[2][LP_TPB];
+    __shared__ long long first[LP_TPB];
+    const int tid = threadIdx.x;
+    double lv = 0.0, qd = 0.0;
+    long long b = 0;
+    for (long e = tid; e < nblk; e += LP_TPB) {
+        lv += part[2 * e];
+        qd += part[2 * e + 1];
+        if (b == 0) b = bad[e];   // the blocks come in ascending order of their data
+    }
+    red[0][tid] = lv;
+    red[1][tid] = qd;
+    first[tid] = b;
+    __syncthreads();
+    for (int s = LP_TPB / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            red[0][tid] += red[0][tid + s];
+            red[1][tid] += red[1][tid + s];
+            const long long o = first[tid + s];
+            if (o != 0 && (first[tid] == 0 || o < first[tid])) first[tid] = o;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        out2[0] = red[0][0];
+        out2[1] = red[1][0];
+        *info = first[0];
+    }
+}
+
+void ck_launch_vecchia_terms(hipStream_t s, int64_t n, const double* z, const double* mu, const double* vv, const double* prior,
+                             const double* noise, const int* cnt2, double* mean, double* var, double* part, long long* bad,
+                             double* out2, long long* info) {
+    if (n <= 0) return;
+    const long nblk = (long)((n + LP_TPB - 1) / LP_TPB);
+    k_vecchia_terms<<<dim3((unsigned)nblk), dim3(LP_TPB), 0, s>>>((long)n, z, mu, vv, prior, noise, cnt2, mean, var, part, bad);
+    k_vecchia_sum<<<dim3(1), dim3(LP_TPB), 0, s>>>(nblk, part, bad, out2, info);
 }

@@ -24,6 +24,13 @@ from scipy.optimize import minimize
 
 from . import native
 
+# fit_likelihood(vecchia=...): the step of the central differences in the [0, 1] coordinates (DESIGN 5d-3 has the table it was
+# chosen from: at N = 400 the difference gradient is within 6e-8 of the analytic one, relative to its largest entry)
+FD_STEP_DEFAULT = 1e-5
+# ... and the optimiser's stopping rules there: differences carry the rounding of two values, so the tolerances of the analytic
+# gradient (ftol 1e-13, gtol 1e-9) are below what they can resolve (with a step of 1e-4 the line search gave up under them)
+VECCHIA_FIT_OPTIONS = {"maxiter": 1000, "ftol": 1e-10, "gtol": 1e-5}
+
 
 class _Param:
     """An n_procs x n_procs parameter array, NaN where the parameter does not exist
@@ -289,7 +296,7 @@ class MultivariateMatern:
         return h
 
     def log_likelihood(self, mf, dist_units: str = "km", fast_dist: bool = True, gradient: bool = False, trend=None,
-                       measurement_error=None, noise_scale=None):
+                       measurement_error=None, noise_scale=None, vecchia=None, _ranks=None):
         """Gaussian log-likelihood of the data the joint predictor uses (every field's ``coords_main`` / ``values_main``,
         zero mean as in simple cokriging) under the current parameters:
             l = -1/2 (N log 2 pi + log|Sigma| + z^T Sigma^-1 z),
@@ -305,7 +312,24 @@ class MultivariateMatern:
         and ``noise_scale`` (one scale per process, default 1): Sigma carries ``noise_scale[k] * d_a`` on its true diagonal
         (``ck_set_noise``).  With ``gradient=True`` the call then returns (l, dl/dtheta, dl/ds): the derivatives in the
         noise scales, one per process (0 for a process without noise), as a third value; without ``measurement_error``
-        the result has the shape it always had."""
+        the result has the shape it always had.
+
+        ``vecchia`` (a ``vecchia.Vecchia``): Vecchia's approximation instead (``ck_loglik_vecchia``) -- every datum
+        conditioned on the earlier data of its ordering within ``vecchia.max_dist`` and under its caps; no Sigma is
+        assembled, so it reaches data sizes the exact form cannot.  ``measurement_error`` / ``noise_scale`` are honoured;
+        ``trend`` and ``gradient=True`` are refused (no REML form, no analytic gradient yet).  A datum whose local system is
+        not positive definite raises LinAlgError naming it."""
+        if vecchia is not None:
+            if trend is not None:
+                raise ValueError("log_likelihood(vecchia=...) has no restricted (REML) form: trend must be None")
+            if gradient:
+                raise NotImplementedError("the Vecchia likelihood has no analytic gradient yet: call it with gradient=False "
+                                          "(fit_likelihood(vecchia=...) differentiates it numerically)")
+            out3, info, _ = self._vecchia_eval(mf, vecchia, dist_units, fast_dist, measurement_error, noise_scale, _ranks)
+            if info != 0:
+                raise LinAlgError(f"the local system of datum {info - 1} (stacked order) is not positive definite, or its "
+                                  "conditional variance is not positive")
+            return out3[0]
         h, var = self._lik_assembled(mf, dist_units, fast_dist, trend, measurement_error, noise_scale)
         info, out3, g = h.loglik_reml(gradient) if trend is not None else h.loglik(gradient)
         if info != 0:
@@ -314,9 +338,27 @@ class MultivariateMatern:
             return out3[0], g, h.loglik_noise_grad()[:self.n_procs]
         return (out3[0], g) if gradient else out3[0]
 
-    def _lik_assembled(self, mf, dist_units, fast_dist, trend, measurement_error, noise_scale):
+    def _vecchia_eval(self, mf, vecchia, dist_units, fast_dist, measurement_error, noise_scale, ranks=None, terms=False):
+        """(out3, info, stats) of ``ck_loglik_vecchia`` on the likelihood's handle -- noise set, no trend, nothing assembled."""
+        from .vecchia import Vecchia
+        if not isinstance(vecchia, Vecchia):
+            raise ValueError(f"vecchia must be a vecchia.Vecchia, got {type(vecchia).__name__}")
+        caps = vecchia.caps(self.n_procs)
+        h, _ = self._lik_assembled(mf, dist_units, fast_dist, None, measurement_error, noise_scale, assemble=False)
+        if ranks is None:
+            ranks = vecchia.ranks([np.asarray(mf.fields[k].coords_main, dtype=np.float64)[:, :2] for k in range(self.n_procs)])
+        h.set_local_neighbours(*caps)
+        return h.loglik_vecchia(ranks, vecchia.max_dist, terms=terms)
+
+    def vecchia_terms(self, mf, vecchia, dist_units: str = "km", fast_dist: bool = True, measurement_error=None,
+                      noise_scale=None):
+        """One row per datum of the Vecchia likelihood (``vecchia.vecchia_terms``): process, index, mean, variance, n0, n1."""
+        from .vecchia import vecchia_terms
+        return vecchia_terms(self, mf, vecchia, dist_units, fast_dist, measurement_error, noise_scale)
+
+    def _lik_assembled(self, mf, dist_units, fast_dist, trend, measurement_error, noise_scale, assemble=True):
         """(handle, variances): the likelihood's handle with the current parameters, the noise and the trend set and Sigma
-        assembled -- what ``log_likelihood`` and ``information`` evaluate."""
+        assembled -- what ``log_likelihood`` and ``information`` evaluate.  ``assemble=False``: everything but Sigma."""
         from .noise import apply_noise, resolve_measurement_error
         from .trend import TrendDesign, check_trend
         check_trend(trend)
@@ -339,7 +381,8 @@ class MultivariateMatern:
         else:
             for k in range(self.n_procs):
                 h.set_trend(k, None)
-        h.assemble_joint()
+        if assemble:
+            h.assemble_joint()
         return h, var
 
     def information(self, mf, dist_units: str = "km", fast_dist: bool = True, trend=None, measurement_error=None,
@@ -383,7 +426,7 @@ class MultivariateMatern:
 
     def fit_likelihood(self, mf, guess: MaternParams = None, fixed=None, dist_units: str = "km", fast_dist: bool = True,
                        trend=None, measurement_error=None, noise_scale=None, fit_noise_scale: bool = False,
-                       std_errors: bool = False):
+                       std_errors: bool = False, vecchia=None, fd_step: float = FD_STEP_DEFAULT):
         """Maximum-likelihood fit: L-BFGS-B on -l with the analytic gradient, within ``params.get_bounds()``.
         ``guess`` as in ``fit``: None starts from the default parameters, else from the current ones with the bounds of
         ``guess``.  ``fixed``: parameter names or flat indices held at their starting values.
@@ -405,10 +448,27 @@ class MultivariateMatern:
         or REML as fitted, the noise scales included when they were fitted), with the shortcuts ``fit_result.std_error`` and
         ``fit_result.conf_int()``.  Parameters held by ``fixed`` are conditioned on; so is a parameter that ends within 1e-8
         of its bound width from a bound: it is listed in ``fit_result.at_bound`` with a NaN standard error, and one warning
-        says so.  With the default False these attributes are None."""
+        says so.  With the default False these attributes are None.
+
+        ``vecchia`` (a ``vecchia.Vecchia``): maximise the Vecchia likelihood instead (``log_likelihood(vecchia=...)``), for
+        data whose Sigma does not fit; bounds, ``fixed``, the [0, 1] mapping, the noise scales and the not-positive-definite
+        penalty are as above.  There is no analytic gradient yet: it comes from central differences of the value with the
+        step ``fd_step`` in the mapped coordinates, one-sided where a step would leave [0, 1] (2 k evaluations per gradient
+        for k free parameters).  The ordering's ranks are computed once per fit.  ``fit_result.method`` is "Vecchia-ML";
+        ``trend`` and ``std_errors=True`` are refused (the Fisher information is the dense one)."""
         from .noise import resolve_measurement_error
         from .trend import check_trend
         check_trend(trend)
+        if vecchia is not None:
+            if trend is not None:
+                raise ValueError("fit_likelihood(vecchia=...) has no restricted (REML) form: trend must be None")
+            if std_errors:
+                raise NotImplementedError("std_errors=True needs the Fisher information, which is the dense likelihood's: fit "
+                                          "with vecchia, then call information() where Sigma fits")
+            if not (isinstance(fd_step, (float, np.floating)) and 0.0 < fd_step < 0.5):
+                raise ValueError(f"fd_step must be a float in (0, 0.5), got {fd_step!r}")
+            v_ranks = vecchia.ranks([np.asarray(mf.fields[k].coords_main, dtype=np.float64)[:, :2]
+                                     for k in range(self.n_procs)])
         var, scales = resolve_measurement_error(measurement_error, noise_scale, mf.fields)
         if fit_noise_scale and var is None:
             raise ValueError("fit_noise_scale=True needs measurement_error")
@@ -455,7 +515,36 @@ class MultivariateMatern:
                 s[k] = np.exp(s_lo + s_width * float(np.asarray(u, dtype=float)[nf + j]))
             return tuple(s.tolist())
 
+        def value_v(u):
+            self.params.set_values(theta_of(u))
+            return self.log_likelihood(mf, dist_units, fast_dist, measurement_error=measurement_error, noise_scale=scales_of(u),
+                                       vecchia=vecchia, _ranks=v_ranks)
+
+        def loglik_v(u):
+            """(l, dl/dtheta over all parameters, dl/ds per process) by differences in the mapped coordinates"""
+            u = np.asarray(u, dtype=float)
+            ll = value_v(u)
+            gu = np.zeros(u.size)
+            for j in range(u.size):
+                up, dn = u.copy(), u.copy()
+                up[j] = min(u[j] + fd_step, 1.0)
+                dn[j] = max(u[j] - fd_step, 0.0)
+                f_up = ll if up[j] == u[j] else value_v(up)
+                f_dn = ll if dn[j] == u[j] else value_v(dn)
+                gu[j] = (f_up - f_dn) / (up[j] - dn[j])
+            self.params.set_values(theta_of(u))
+            g = np.zeros(len(names))
+            g[free] = gu[:nf] / width            # cost() maps back with the same widths
+            gs = np.zeros(self.n_procs)
+            if s_free:
+                sc = np.array(scales_of(u))
+                for j, k in enumerate(s_free):
+                    gs[k] = gu[nf + j] / (sc[k] * s_width)
+            return ll, g, gs
+
         def loglik(u):
+            if vecchia is not None:
+                return loglik_v(u)
             out = self.log_likelihood(mf, dist_units, fast_dist, gradient=True, trend=trend, measurement_error=measurement_error,
                                       noise_scale=scales_of(u))
             return out if len(out) == 3 else (out[0], out[1], np.zeros(self.n_procs))
@@ -489,14 +578,15 @@ class MultivariateMatern:
         if s_free:
             u0 = np.concatenate([u0, [(np.log(np.clip(s_cur[k], 1e-3, 1e3)) - s_lo) / s_width for k in s_free]])
         res = minimize(cost, u0, jac=True, method="L-BFGS-B", bounds=[(0.0, 1.0)] * len(u0),
-                       options={"maxiter": 1000, "ftol": 1e-13, "gtol": 1e-9})
+                       options=dict(VECCHIA_FIT_OPTIONS) if vecchia is not None else {"maxiter": 1000, "ftol": 1e-13, "gtol": 1e-9})
         if res.success == False:   # noqa: E712  (as fit)
             warnings.warn("ERROR: optimization did not converge.")
         theta = theta_of(res.x)
         self.params.set_values(theta)
         ll, g, gs = loglik(res.x)
         self.fit_result = FittedLikelihood(self, ll, g, free, state["n_eval"], state["n_not_pd"], res,
-                                           method="ML" if trend is None else "REML", noise_scale=scales_of(res.x),
+                                           method="Vecchia-ML" if vecchia is not None else "ML" if trend is None else "REML",
+                                           noise_scale=scales_of(res.x),
                                            noise_gradient=None if var is None else gs, noise_free=s_free)
         if std_errors:
             # a parameter within 1e-8 of its bound width from a bound: conditioned on (no normal approximation on a boundary)

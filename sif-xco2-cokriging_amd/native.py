@@ -77,6 +77,8 @@ _PROTOS = {
     "ck_local_reserve": [c_void_p, c_int64],
     "ck_set_local_neighbours": [c_void_p, c_int64, c_int64],
     "ck_debug_local_neighbours": [c_void_p, c_int, _dp, c_int64, c_double, c_int, POINTER(c_int32), _dp],
+    "ck_loglik_vecchia": [c_void_p, POINTER(c_int64), c_double, _dp, _dp, _dp, POINTER(c_int32), POINTER(c_int64),
+                          POINTER(c_int64)],
     "ck_predict_local_universal": [c_void_p, c_int, _dp, c_int64, _dp, c_double, c_int, _dp, _dp, _dp, POINTER(c_int64),
                                    POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
     "ck_vario_begin": [c_void_p, _dp, _dp, c_int64, _dp, _dp, c_int64, c_int],
@@ -670,6 +672,36 @@ class Handle:
         _chk(lib().ck_debug_local_neighbours(self._h, int(i), _p(pc), m, float(max_dist), int(bool(cv)),
                                              count.ctypes.data_as(POINTER(c_int32)), _p(rcut)))
         return count, rcut
+
+    def loglik_vecchia(self, rank, max_dist, terms=False):
+        """Vecchia log-likelihood of the data under the model (include/cokrige.h: ck_loglik_vecchia): every datum conditioned on
+        the data of smaller ``rank`` (N distinct integers, stacked: process 0 then 1) within ``max_dist``, under the caps of
+        set_local_neighbours.  Returns (out3, info, stats) -- out3 = (l, sum log s_t^2, sum e_t^2 / s_t^2), NaN with info =
+        1 + the first datum without a term; stats: n_empty, k_max, n_capped -- and with ``terms`` also mean, var (N) and
+        count (N, 2) in stats."""
+        r = np.ascontiguousarray(rank, dtype=np.int64).reshape(-1)
+        n = int(sum(self._n_data.values()))
+        if r.size != n:
+            raise ValueError(f"rank has {r.size} entries, the handle {n} data")
+        out3, st, info = np.zeros(3), np.zeros(3, dtype=np.int64), c_int64(0)
+        mean = np.empty(n) if terms else None
+        var = np.empty(n) if terms else None
+        count = np.zeros((n, 2), dtype=np.int32) if terms else None
+        _chk(lib().ck_loglik_vecchia(self._h, r.ctypes.data_as(POINTER(c_int64)), float(max_dist), _p(out3),
+                                     _p(mean) if terms else None, _p(var) if terms else None,
+                                     count.ctypes.data_as(POINTER(c_int32)) if terms else None,
+                                     st.ctypes.data_as(POINTER(c_int64)), byref(info)))
+        stats = dict(n_empty=int(st[0]), k_max=int(st[1]), n_capped=int(st[2]))
+        if terms:
+            stats.update(mean=mean, var=var, count=count)
+        return out3, info.value, stats
+
+    def vecchia_timings(self):
+        """ck_timings [72 ..] of the last loglik_vecchia() call (milliseconds; the last two are counts of data)."""
+        out = np.zeros(78)
+        _chk(lib().ck_timings(self._h, _p(out), 78))
+        keys = ["select_ms", "solve_ms", "terms_ms", "total_ms", "n_lds", "n_tiled"]
+        return dict(zip(keys, out[72:78].tolist()))
 
     def local_reserve(self, nbytes: int = 0):
         """Pre-size the scratch slab of predict_local (0: the automatic budget) -- include/cokrige.h: ck_local_reserve."""
