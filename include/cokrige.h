@@ -344,6 +344,34 @@ int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host /* N, stacked: proc
                       double* out3, double* mean_host /* N or NULL */, double* var_host /* N or NULL */,
                       int32_t* count_host /* N x 2 or NULL */, int64_t* stats3 /* n_empty, k_max, n_capped */, int64_t* info);
 
+/* The Vecchia likelihood with its analytic gradient, for conditioning sets of at most 64 data (the LDS class of the local
+ * solver).  For datum t with set c: w = Sigma_loc^-1 c, alpha = Sigma_loc^-1 z_c, b = (-w, 1) and a = (alpha, 0) over the set plus
+ * the datum, e = z_t - mu_t, and
+ *   dl/dtheta = 1/2 sum_t sum_pq M_t[p, q] dC_t[p, q]/dtheta,   M_t = (e^2 / s_t^4 - 1 / s_t^2) b b^T + (e / s_t^2) (b a^T + a b^T),
+ * C_t the (k + 1) x (k + 1) covariance of the set and the OBSERVATION (ck_set_noise's s d on its diagonal, the datum's own
+ * included), its derivatives those of ck_loglik's gradient (exact evaluator, the distance of the exact path).  The sets are held
+ * fixed: this is the derivative of the value ck_loglik_vecchia returns for these ranks, max_dist and caps wherever no cap's cut
+ * changes with theta -- it never does: the sets depend on the distances alone.  An empty set is the one-entry system b = (1),
+ * a = (0), e = z_t: it contributes the derivative of the prior observation variance (slots sigma_i, nugget_i, s_i).
+ * out3, stats3, info: as ck_loglik_vecchia; out3 has the bits that call gives on the same handle and inputs.
+ * grad13: the slots of ck_loglik_fisher (CK_FISHER_NPAR: the 11 model parameters in ck_loglik's flat order -- one process: the
+ * first 4 -- then s_0, s_1).  free13 (or NULL: all): a slot is live when its flag is set and its parameter exists; slots that
+ * are not live are exact 0, and masking a slot does not change a bit of the live ones.  When no nu slot of a block is live the
+ * four shifted evaluations of its nu difference are skipped.
+ * score_host (N x 13 or NULL): the per-datum contributions in the caller's stacked order (the kernel's output before the
+ * reduction; asking for them costs their download).  A datum whose local system is not positive definite or whose s_t^2 is not
+ * > 0 has NaN in its live slots; then *info names the first such datum, grad13 is NaN and every other datum's score is valid.
+ * The N scores are summed column by column by the fixed tree of the terms; no atomics; repeated calls give the same bits.
+ * State: as ck_loglik_vecchia -- no Sigma panels, nothing invalidated.
+ * Refused through ck_last_error: what ck_loglik_vecchia refuses, NULL grad13, and -- after the select passes of both processes,
+ * before any solve -- any conditioning set of more than 64 data (the message names how many data have one and the largest
+ * set): the tiled path of larger systems has no back substitution.  Use the caps, or difference ck_loglik_vecchia.
+ * ck_timings [80 ..]: the select passes, solve + back substitution + contraction (k_vecchia_grad), the reductions (terms and
+ * scores), host wall clock (ms), the data solved and the pairs contracted; [72 ..] hold what ck_loglik_vecchia would report. */
+int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, double max_dist, const int32_t* free13 /* or NULL: all */,
+                           double* out3, double* grad13, double* score_host /* N x 13 or NULL */,
+                           int64_t* stats3 /* n_empty, k_max, n_capped */, int64_t* info);
+
 /* Simulation draw z = L eps in the caller's stacked order (process 0 sites, then process 1):
  * sim.BivariateRandomField._simulate (src/sim.py:52-54: cholesky(cmat, lower=True) @ noise).
  * n = number of observations; needs ck_factor. */
@@ -627,7 +655,10 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * uncapped local call.
  * ck_loglik_vecchia (n up to 78): [72] the select passes of both processes; [73] the solves of both size classes; [74] the
  * terms and their reduction (k_vecchia_terms, k_vecchia_sum); [75] host wall clock of the call; [76] / [77] number of data in
- * the LDS class (empty sets included) / beyond it.  [10], [14] and [60 ..] then hold the sums over its two passes. */
+ * the LDS class (empty sets included) / beyond it.  [10], [14] and [60 ..] then hold the sums over its two passes.
+ * ck_loglik_vecchia_grad (n up to 86): [80] the select passes of both processes; [81] solve, back substitution and contraction
+ * (k_vecchia_grad, both processes); [82] the reductions (the terms' and the scores'); [83] host wall clock of the call; [84] data
+ * solved; [85] pairs contracted (sum over the data of (k + 1)(k + 2) / 2).  [72 ..] and [60 ..] are filled as by ck_loglik_vecchia. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it

@@ -34,7 +34,7 @@
 #include "ck_vecchia.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 80
+#define CK_N_TIMINGS 88
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -3860,6 +3860,56 @@ static int vecchia_positions(const int64_t* rank, int64_t N, std::vector<int>& p
     return 0;
 }
 
+// The terms and their sums in the caller's stacked order, from what the passes of the local solver left on the host: the tail of
+// both Vecchia entry points -- the same uploads and launches, so the same bits in out3.  [ev0, ev1]: the two term kernels.
+static int vecchia_terms_tail(ck_handle* h, DevTemps& tmp, int64_t N, const std::vector<double>& mu, std::vector<double>& vv,
+                              const std::vector<double>& prior, const std::vector<double>& own, const std::vector<double>& zs,
+                              const std::vector<int32_t>& cnt2, double* out3, double* mean_host, double* var_host,
+                              int32_t* count_host, int64_t* info, int64_t* n_lds_out) {
+    const int kl = ck_local_lds_limit();
+    int64_t n_lds = 0;
+    for (int64_t t = 0; t < N; ++t) {
+        const int kt = cnt2[(size_t)(2 * t)] + cnt2[(size_t)(2 * t + 1)];
+        n_lds += kt <= kl;
+        if (kt > 0 && mu[(size_t)t] != mu[(size_t)t]) vv[(size_t)t] = NAN;   // not positive definite: no variance either
+    }
+    // the terms and their sums, in the caller's stacked order
+    const int64_t nblk = (N + 255) / 256;
+    double *d_z = nullptr, *d_mu = nullptr, *d_vv = nullptr, *d_prior = nullptr, *d_own = nullptr, *d_mean = nullptr, *d_var = nullptr,
+           *d_part = nullptr, *d_out = nullptr;
+    int* d_cnt2 = nullptr;
+    long long* d_bad = nullptr;
+    for (double** b : {&d_z, &d_mu, &d_vv, &d_prior, &d_own, &d_mean, &d_var}) HIPCHK(tmp.get(b, (size_t)(N * 8)));
+    HIPCHK(tmp.get(&d_part, (size_t)(2 * nblk * 8)));
+    HIPCHK(tmp.get(&d_out, (size_t)(2 * 8)));
+    HIPCHK(tmp.get(&d_cnt2, (size_t)(2 * N) * sizeof(int)));
+    HIPCHK(tmp.get(&d_bad, (size_t)(nblk + 1) * sizeof(long long)));
+    const std::pair<double*, const double*> up[] = {{d_z, zs.data()}, {d_mu, mu.data()}, {d_vv, vv.data()}, {d_prior, prior.data()},
+                                                    {d_own, own.data()}};
+    for (const auto& c : up) HIPCHK(hipMemcpyAsync(c.first, c.second, (size_t)(N * 8), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_cnt2, cnt2.data(), (size_t)(2 * N) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    ck_launch_vecchia_terms(h->stream, N, d_z, d_mu, d_vv, d_prior, h->noise_on ? d_own : nullptr, d_cnt2, d_mean, d_var, d_part,
+                            d_bad, d_out, d_bad + nblk);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    double sums[2] = {0.0, 0.0};
+    long long first_bad = 0;
+    HIPCHK(hipMemcpyAsync(sums, d_out, 2 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&first_bad, d_bad + nblk, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    if (mean_host) HIPCHK(hipMemcpyAsync(mean_host, d_mean, (size_t)(N * 8), hipMemcpyDeviceToHost, h->stream));
+    if (var_host) HIPCHK(hipMemcpyAsync(var_host, d_var, (size_t)(N * 8), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (count_host) memcpy(count_host, cnt2.data(), (size_t)(2 * N) * sizeof(int32_t));
+    out3[1] = sums[0];
+    out3[2] = sums[1];
+    out3[0] = first_bad ? NAN : ck_vecchia_total(N, sums[0], sums[1]);
+    if (first_bad) out3[1] = out3[2] = NAN;
+    if (info) *info = first_bad;
+    *n_lds_out = n_lds;
+    return 0;
+}
+
 extern "C" int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host, double max_dist, double* out3, double* mean_host,
                                  double* var_host, int32_t* count_host, int64_t* stats3, int64_t* info) {
     CHKH(h);
@@ -3922,46 +3972,8 @@ extern "C" int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host, double 
             if (nz) own[(size_t)(soff + t)] = h->noise_scale[k] * h->noise_var[k][(size_t)t];
         }
     }
-    const int kl = ck_local_lds_limit();
     int64_t n_lds = 0;
-    for (int64_t t = 0; t < N; ++t) {
-        const int kt = cnt2[(size_t)(2 * t)] + cnt2[(size_t)(2 * t + 1)];
-        n_lds += kt <= kl;
-        if (kt > 0 && mu[(size_t)t] != mu[(size_t)t]) vv[(size_t)t] = NAN;   // not positive definite: no variance either
-    }
-    // the terms and their sums, in the caller's stacked order
-    const int64_t nblk = (N + 255) / 256;
-    double *d_z = nullptr, *d_mu = nullptr, *d_vv = nullptr, *d_prior = nullptr, *d_own = nullptr, *d_mean = nullptr, *d_var = nullptr,
-           *d_part = nullptr, *d_out = nullptr;
-    int* d_cnt2 = nullptr;
-    long long* d_bad = nullptr;
-    for (double** b : {&d_z, &d_mu, &d_vv, &d_prior, &d_own, &d_mean, &d_var}) HIPCHK(tmp.get(b, (size_t)(N * 8)));
-    HIPCHK(tmp.get(&d_part, (size_t)(2 * nblk * 8)));
-    HIPCHK(tmp.get(&d_out, (size_t)(2 * 8)));
-    HIPCHK(tmp.get(&d_cnt2, (size_t)(2 * N) * sizeof(int)));
-    HIPCHK(tmp.get(&d_bad, (size_t)(nblk + 1) * sizeof(long long)));
-    const std::pair<double*, const double*> up[] = {{d_z, zs.data()}, {d_mu, mu.data()}, {d_vv, vv.data()}, {d_prior, prior.data()},
-                                                    {d_own, own.data()}};
-    for (const auto& c : up) HIPCHK(hipMemcpyAsync(c.first, c.second, (size_t)(N * 8), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_cnt2, cnt2.data(), (size_t)(2 * N) * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    ck_launch_vecchia_terms(h->stream, N, d_z, d_mu, d_vv, d_prior, h->noise_on ? d_own : nullptr, d_cnt2, d_mean, d_var, d_part,
-                            d_bad, d_out, d_bad + nblk);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    double sums[2] = {0.0, 0.0};
-    long long first_bad = 0;
-    HIPCHK(hipMemcpyAsync(sums, d_out, 2 * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(&first_bad, d_bad + nblk, sizeof(long long), hipMemcpyDeviceToHost, h->stream));
-    if (mean_host) HIPCHK(hipMemcpyAsync(mean_host, d_mean, (size_t)(N * 8), hipMemcpyDeviceToHost, h->stream));
-    if (var_host) HIPCHK(hipMemcpyAsync(var_host, d_var, (size_t)(N * 8), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (count_host) memcpy(count_host, cnt2.data(), (size_t)(2 * N) * sizeof(int32_t));
-    out3[1] = sums[0];
-    out3[2] = sums[1];
-    out3[0] = first_bad ? NAN : ck_vecchia_total(N, sums[0], sums[1]);
-    if (first_bad) out3[1] = out3[2] = NAN;
-    if (info) *info = first_bad;
+    if (vecchia_terms_tail(h, tmp, N, mu, vv, prior, own, zs, cnt2, out3, mean_host, var_host, count_host, info, &n_lds)) return -1;
     if (stats3) {
         stats3[0] = n_empty;
         stats3[1] = k_max;
@@ -3981,6 +3993,227 @@ extern "C" int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host, double 
     h->t_ms[75] = ms_since(t_begin);
     h->t_ms[76] = (double)n_lds;
     h->t_ms[77] = (double)(N - n_lds);
+    return 0;
+}
+
+// The gradient of the Vecchia likelihood (include/cokrige.h has the definition, ck_vecchia_grad.h the formula).  Its own two
+// phases instead of predict_local_impl's one: the select passes of BOTH processes first -- a set beyond the LDS limit is
+// refused before any solve -- then one launch of k_vecchia_grad per process on the cut distances those passes left on the
+// device, then the terms (vecchia_terms_tail: ck_loglik_vecchia's bits) and the column sums of the scores.
+extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, double max_dist, const int32_t* free13, double* out3,
+                                      double* grad13, double* score_host, int64_t* stats3, int64_t* info) {
+    CHKH(h);
+    if (h->world != 1)
+        return fail("ck_loglik_vecchia_grad is the single-process form: this handle is partitioned (world = " +
+                    std::to_string(h->world) + ")");
+    if (!rank_host || !out3 || !grad13) return fail("ck_loglik_vecchia_grad: null rank_host / out3 / grad13");
+    if (!(max_dist >= 0.0) || !std::isfinite(max_dist))
+        return fail("ck_loglik_vecchia_grad: max_dist must be finite and >= 0, got " + std::to_string(max_dist));
+    if (trend_total(h) > 0)
+        return fail("ck_loglik_vecchia_grad: a trend of " + std::to_string(trend_total(h)) +
+                    " columns is set on the handle; the Vecchia likelihood has no REML form (clear it with ck_set_trend)");
+    if (ensure_layout(h, false)) return -1;   // sites, tables, chunk bounds -- no Sigma panels, nothing invalidated
+    if (ensure_noise(h)) return -1;
+    const auto t_begin = std::chrono::steady_clock::now();
+    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    const int NP = CK_FISHER_NPAR;
+    static_assert(CK_FISHER_NPAR == CK_VG_NPAR, "the score has the slots of ck_loglik_fisher");
+    for (int k = 0; k < NP; ++k) grad13[k] = NAN;
+    const int64_t N = h->N, n0 = h->n[0], Np = h->Npad;
+    if (N > INT32_MAX) return fail("ck_loglik_vecchia_grad: more than 2^31 - 1 data");
+    std::vector<int> pos;
+    int64_t dup[2] = {0, 0};
+    if (vecchia_positions(rank_host, N, pos, dup))
+        return fail("ck_loglik_vecchia_grad: data " + std::to_string(dup[0]) + " and " + std::to_string(dup[1]) +
+                    " (stacked order) have the same rank " + std::to_string((long long)rank_host[dup[0]]));
+    // the sites' positions in the internal order (padding: never searched), and every datum's own internal index
+    std::vector<int> rs((size_t)Np, INT32_MAX), gself((size_t)N);
+    for (int k = 0; k < h->n_procs; ++k) {
+        const int64_t off = k == 0 ? 0 : h->n0p, soff = k == 0 ? 0 : n0;
+        for (int64_t j = 0; j < h->n[k]; ++j) {
+            rs[(size_t)(off + j)] = pos[(size_t)(soff + h->perm[k][(size_t)j])];
+            gself[(size_t)(soff + h->perm[k][(size_t)j])] = (int)(off + j);
+        }
+    }
+    // live slots (ck_loglik_fisher's rule) and the operands of the contraction (ck_loglik's)
+    CkVecchiaGradArgs A{};
+    CkVecchiaModel& V = A.V;
+    const int npar = h->n_procs == 1 ? 4 : CK_LIK_NPAR;
+    for (int k = 0; k < npar; ++k) V.live |= 1u << k;
+    if (!h->noise_var[0].empty()) V.live |= 1u << 11;
+    if (h->n_procs == 2 && !h->noise_var[1].empty()) V.live |= 1u << 12;
+    if (free13)
+        for (int k = 0; k < NP; ++k)
+            if (free13[k] == 0) V.live &= ~(1u << k);
+    const int nblk3 = h->n_procs == 1 ? 1 : 3;
+    CkMatern hb[15];
+    const double offs[4] = {-2.0, -1.0, 1.0, 2.0};
+    for (int b = 0; b < 3; ++b) {
+        const CkMatern& m = h->blk[b < nblk3 ? b : 0];
+        V.dnu[b] = ck_matern_dnu_step(m.nu);
+        hb[5 * b] = m;
+        for (int k = 0; k < 4; ++k) ck_matern_prepare(m.nu + offs[k] * V.dnu[b], m.len_scale, m.amp, m.nugget, &hb[5 * b + 1 + k]);
+        if (b < nblk3 && (V.live >> ck_vg_nu_slot(h->n_procs, b) & 1u)) V.nu_live |= 1u << b;
+    }
+    HIPCHK(h->d_lik_blk.reserve(sizeof(hb) / sizeof(CkMatern)));
+    HIPCHK(hipMemcpyAsync(h->d_lik_blk, hb, sizeof(hb), hipMemcpyHostToDevice, h->stream));
+    V.blk5 = h->d_lik_blk;
+    V.sig1 = h->par_sigma[0];
+    V.sig2 = h->par_sigma[1];
+    V.rho = h->par_rho;
+    V.n_procs = h->n_procs;
+    const double* nz = noise_sd(h);
+    A.dvar = (V.live >> 11 & 3u) ? h->d_noise + Np : nullptr;
+    DevTemps tmp;
+    int *d_rs = nullptr, *d_gself = nullptr;
+    double* d_score = nullptr;
+    HIPCHK(tmp.get(&d_rs, (size_t)Np * sizeof(int)));
+    HIPCHK(tmp.get(&d_gself, (size_t)N * sizeof(int)));
+    HIPCHK(tmp.get(&d_score, (size_t)(N * NP) * 8));
+    HIPCHK(hipMemcpyAsync(d_rs, rs.data(), (size_t)Np * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_gself, gself.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    // ---- phase 1: the select pass of every process (its points: the process's data in the caller's order)
+    struct Pass {
+        int64_t m = 0, mp = 0;
+        double *d_p3 = nullptr, *d_pu = nullptr, *d_out = nullptr, *d_rq = nullptr, *d_cp = nullptr, *d_vv = nullptr;
+        int *d_cnt = nullptr, *d_rp = nullptr;
+    } pass[2];
+    const int nmax0 = local_nmax_of(h, 0), nmax1 = local_nmax_of(h, 1);
+    const double cmax = local_cmax(h, max_dist);
+    const int kl = ck_local_lds_limit();
+    std::vector<int32_t> cnt2((size_t)(2 * N), 0);
+    int64_t n_empty = 0, k_max = 0, n_capped = 0, n_rescan = 0, cand_max = 0, n_over = 0, n_pairs = 0;
+    double ms_select = 0.0;
+    for (int k = 0; k < h->n_procs; ++k) {
+        Pass& P = pass[k];
+        P.m = h->n[k];
+        if (P.m == 0) continue;
+        const int64_t m = P.m, mp = P.mp = roundup(m, 64), soff = k == 0 ? 0 : n0;
+        double* d_pc = nullptr;
+        int* d_sel = nullptr;
+        HIPCHK(tmp.get(&d_pc, (size_t)(2 * mp * 8)));
+        HIPCHK(tmp.get(&P.d_p3, (size_t)(3 * mp * 8)));
+        HIPCHK(tmp.get(&P.d_pu, (size_t)(3 * mp * 8)));
+        HIPCHK(tmp.get(&P.d_out, (size_t)(2 * mp * 8)));
+        HIPCHK(tmp.get(&P.d_cnt, (size_t)(mp * sizeof(int))));
+        HIPCHK(tmp.get(&d_sel, (size_t)(4 * mp * sizeof(int))));
+        HIPCHK(tmp.get(&P.d_rq, (size_t)(2 * mp * 8)));
+        HIPCHK(tmp.get(&P.d_cp, (size_t)(mp * 8)));
+        HIPCHK(tmp.get(&P.d_rp, (size_t)(mp * sizeof(int))));
+        HIPCHK(tmp.get(&P.d_vv, (size_t)(mp * 8)));
+        HIPCHK(hipMemsetAsync(P.d_vv, 0, (size_t)(mp * 8), h->stream));
+        HIPCHK(hipMemcpyAsync(P.d_rp, pos.data() + soff, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemsetAsync(d_pc, 0, 2 * mp * 8, h->stream));
+        HIPCHK(hipMemcpyAsync(d_pc, h->h_coords[k].data(), 2 * m * 8, hipMemcpyHostToDevice, h->stream));
+        ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, P.d_p3, P.d_p3 + mp, P.d_p3 + 2 * mp, P.d_pu);
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        const CkLocalCap pre{nullptr, nullptr, d_rs, P.d_rp};
+        ck_launch_local_select(h->stream, h->metric, k, 0, max_dist, P.d_p3, m, mp, h->s0, layout_of(h), h->d_chunkb, cmax, P.d_pu,
+                               nmax0, nmax1, local_key_cap(h), P.d_cnt, d_sel, P.d_rq, P.d_cp, pre);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        std::vector<int> sel((size_t)(4 * m));
+        HIPCHK(hipMemcpyAsync(sel.data(), d_sel, sel.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        double ms = 0;
+        HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms));
+        ms_select += ms;
+        local_select_stats(h, sel.data(), m);
+        n_capped += (int64_t)h->t_ms[61];
+        cand_max = std::max(cand_max, (int64_t)h->t_ms[62]);
+        n_rescan += (int64_t)h->t_ms[63];
+        for (int64_t p = 0; p < m; ++p) {
+            const int k0 = sel[(size_t)(4 * p)], k1 = sel[(size_t)(4 * p + 1)], kt = k0 + k1;
+            cnt2[(size_t)(2 * (soff + p))] = k0;
+            cnt2[(size_t)(2 * (soff + p) + 1)] = k1;
+            n_empty += kt == 0;
+            n_over += kt > kl;
+            k_max = std::max<int64_t>(k_max, kt);
+            n_pairs += (int64_t)(kt + 1) * (kt + 2) / 2;
+        }
+    }
+    h->t_ms[60] = ms_select;
+    h->t_ms[61] = (double)n_capped;
+    h->t_ms[62] = (double)cand_max;
+    h->t_ms[63] = (double)n_rescan;
+    if (n_over > 0)
+        return fail("ck_loglik_vecchia_grad: " + std::to_string(n_over) + " data have a conditioning set of more than " +
+                    std::to_string(kl) + " data (the largest: " + std::to_string(k_max) +
+                    "); the gradient is for sets the LDS solver takes: lower the caps or the radius, or difference ck_loglik_vecchia");
+    // ---- phase 2: solve, back substitution and contraction, one workgroup per datum
+    std::vector<double> mu((size_t)N), vv((size_t)N, 0.0), prior((size_t)N), own((size_t)N, 0.0), zs((size_t)N);
+    const int use_tab = tables_usable(h) ? 1 : 0;
+    HIPCHK(hipEventRecord(h->ev2, h->stream));
+    for (int k = 0; k < h->n_procs; ++k) {
+        const Pass& P = pass[k];
+        if (P.m == 0) continue;
+        const int64_t soff = k == 0 ? 0 : n0;
+        const double c0 = h->blk[2 * k].amp + h->blk[2 * k].nugget;
+        const CkLocalCap cap{P.d_rq, P.d_cp, d_rs, P.d_rp};
+        CkVecchiaGradArgs Ak = A;
+        Ak.gself = d_gself + soff;
+        Ak.score = d_score + soff * NP;
+        ck_launch_vecchia_grad(h->stream, h->d_blk, h->metric, k, max_dist, P.d_p3, P.m, P.mp, h->s0, h->z, layout_of(h), P.d_cnt, c0,
+                               P.d_out, P.d_out + P.mp, h->d_tabs, h->d_coefptr, use_tab, h->su, P.d_pu, h->d_chunkb, cmax, nz, cap,
+                               P.d_vv, Ak);
+        HIPCHK(hipGetLastError());
+        const bool nzk = h->noise_on && !h->noise_var[k].empty();
+        for (int64_t t = 0; t < P.m; ++t) {
+            prior[(size_t)(soff + t)] = c0;
+            zs[(size_t)(soff + t)] = h->h_values[k][(size_t)t];
+            if (nzk) own[(size_t)(soff + t)] = h->noise_scale[k] * h->noise_var[k][(size_t)t];
+        }
+    }
+    HIPCHK(hipEventRecord(h->ev3, h->stream));
+    for (int k = 0; k < h->n_procs; ++k) {
+        const Pass& P = pass[k];
+        if (P.m == 0) continue;
+        const int64_t soff = k == 0 ? 0 : n0;
+        HIPCHK(hipMemcpyAsync(mu.data() + soff, P.d_out, P.m * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(vv.data() + soff, P.d_vv, P.m * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));   // (hb is stack memory)
+    double ms_solve = 0;
+    HIPCHK(elapsed_ms(h->ev2, h->ev3, &ms_solve));
+    int64_t n_lds = 0, first_bad = 0;
+    if (vecchia_terms_tail(h, tmp, N, mu, vv, prior, own, zs, cnt2, out3, nullptr, nullptr, nullptr, &first_bad, &n_lds)) return -1;
+    // ---- the column sums of the scores, in the caller's stacked order
+    const int64_t nblk = (N + 255) / 256;
+    double *d_part = nullptr, *d_g = nullptr;
+    HIPCHK(tmp.get(&d_part, (size_t)(nblk * NP) * 8));
+    HIPCHK(tmp.get(&d_g, (size_t)NP * 8));
+    HIPCHK(hipEventRecord(h->ev2, h->stream));
+    ck_launch_vecchia_grad_sum(h->stream, N, d_score, d_part, d_g);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev3, h->stream));
+    HIPCHK(hipMemcpyAsync(grad13, d_g, (size_t)NP * 8, hipMemcpyDeviceToHost, h->stream));
+    if (score_host) HIPCHK(hipMemcpyAsync(score_host, d_score, (size_t)(N * NP) * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (first_bad)
+        for (int k = 0; k < NP; ++k) grad13[k] = NAN;
+    if (info) *info = first_bad;
+    if (stats3) {
+        stats3[0] = n_empty;
+        stats3[1] = k_max;
+        stats3[2] = n_capped;
+    }
+    double ms_terms = 0, ms_sum = 0;
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms_terms));
+    HIPCHK(elapsed_ms(h->ev2, h->ev3, &ms_sum));
+    h->t_ms[10] = ms_select + ms_solve;
+    h->t_ms[14] = 0.0;
+    h->t_ms[72] = ms_select;
+    h->t_ms[73] = ms_solve;
+    h->t_ms[74] = ms_terms;
+    h->t_ms[75] = ms_since(t_begin);
+    h->t_ms[76] = (double)n_lds;
+    h->t_ms[77] = 0.0;
+    h->t_ms[80] = ms_select;
+    h->t_ms[81] = ms_solve;
+    h->t_ms[82] = ms_terms + ms_sum;
+    h->t_ms[83] = h->t_ms[75];
+    h->t_ms[84] = (double)N;
+    h->t_ms[85] = (double)n_pairs;
     return 0;
 }
 

@@ -6,6 +6,7 @@
 
 #include "ck_host.h"
 #include "ck_math.h"
+#include "ck_vecchia_grad.h"
 
 #define CK_NB 512   // outer block column width (panel width)
 #define CK_IB 64    // inner block (diagonal factor / row solves)
@@ -373,6 +374,23 @@ int ck_local_lds_limit();
 void ck_launch_vecchia_terms(hipStream_t s, int64_t n, const double* z, const double* mu, const double* vv, const double* prior,
                              const double* noise, const int* cnt2, double* mean, double* var, double* part, long long* bad,
                              double* out2, long long* info);
+// The gradient of the Vecchia likelihood (ck_loglik_vecchia_grad; ck_vecchia_grad.h): k_vecchia_grad is k_local_solve for sets
+// of at most ck_local_lds_limit() data (same pred / err / vv bits; an empty set writes NaN, NaN as there) followed by the back
+// substitution and the contraction.  gself: the m points' own internal site indices; dvar: the raw measurement-error variances
+// d in the internal order (npad) or null; score: m x CK_VG_NPAR, the points' order.  ck_launch_vecchia_grad_sum: column sums of
+// n scores by the fixed tree of the terms (part: CK_VG_NPAR x ceil(n / 256) doubles).
+struct CkVecchiaGradArgs {
+    CkVecchiaModel V;
+    const int* gself;
+    const double* dvar;
+    double* score;
+};
+void ck_launch_vecchia_grad(hipStream_t s, const CkMatern* blk, int metric, int i_pred, double max_dist, const double* pc, int64_t m,
+                            int64_t mpad, const double* sc, const double* z, CkLayout L, const int* counts, double c0var,
+                            double* pred, double* err, const CkTable* tabs, const double* const* coefs, int use_tab,
+                            const double* su, const double* pu, const double* cb, double cmax, const double* nz, CkLocalCap cap,
+                            double* vv, CkVecchiaGradArgs A);
+void ck_launch_vecchia_grad_sum(hipStream_t s, int64_t n, const double* score, double* part, double* out13);
 
 // Large neighbourhoods (k > k_hi above): the "tiled" path.  The systems of a batch are factored TOGETHER,
 // 64 columns per step, by launches over all systems that still have columns left (diagonal block + its

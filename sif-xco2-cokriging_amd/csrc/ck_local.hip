@@ -15,7 +15,8 @@
 // per point with a blocked factorisation in one workgroup (k_local_solve_big).
 // Universal cokriging in the neighbourhood (a GLS trend per point, ck_predict_local_universal): behind the tiled path.
 // The Vecchia likelihood (ck_loglik_vecchia) runs the same kernels with the data as the points and one more predicate in the
-// search -- only sites that come earlier in the caller's ordering (lp_later) -- and sums its terms at the end of this file.
+// search -- only sites that come earlier in the caller's ordering (lp_later) -- and sums its terms at the end of this file; its
+// gradient (ck_loglik_vecchia_grad) has a kernel of its own behind them, k_vecchia_grad.
 #include "ck_internal.h"
 #include "ck_select.h"
 
@@ -1334,4 +1335,264 @@ void ck_launch_vecchia_terms(hipStream_t s, int64_t n, const double* z, const do
     const long nblk = (long)((n + LP_TPB - 1) / LP_TPB);
     k_vecchia_terms<<<dim3((unsigned)nblk), dim3(LP_TPB), 0, s>>>((long)n, z, mu, vv, prior, noise, cnt2, mean, var, part, bad);
     k_vecchia_sum<<<dim3(1), dim3(LP_TPB), 0, s>>>(nblk, part, bad, out2, info);
+}
+
+// ---------------------------------------------------------------------------------------
+// the gradient of the Vecchia likelihood (ck_loglik_vecchia_grad; ck_vecchia_grad.h has the formula and the pair rule)
+// ---------------------------------------------------------------------------------------
+// k_vecchia_grad: one workgroup per datum, sets of at most LP_KL data.  Steps 1 - 4 are k_local_solve's, expression by
+// expression (mu and v . v come out with the same bits); then
+//   5. back substitution in place on rows k and k + 1: v -> w = L^-T v, y -> alpha = L^-T y.  ONE wave, lane a holding x_a of
+//      both rows: step j broadcasts x_j / L_jj from lane j and every lane a < j subtracts L[j][a] x_j -- row j of L is
+//      contiguous in LDS, and with k <= 64 the whole vector lives in one wave, so the k dependent steps need no barrier
+//      (a barrier per step across four waves would cost more than the three waves add: a step has at most 64 updates);
+//   6. the contraction over the lower triangle of the set plus the datum, (k + 1)(k + 2) / 2 pairs over the 256 threads,
+//      ck_vecchia_pair per pair with the exact evaluator's derivatives; 13 sums per thread, reduced by wave shuffles and a
+//      fixed four-wave order (k_loglik_grad's), one 13-vector per datum.
+// An empty set is the one-entry system (b = 1, a = 0): it runs step 6 alone.  A system that is not positive definite or a
+// variance that is not > 0: NaN in the live slots.  k_vecchia_grad_part / _sum: the column sums of the scores by the fixed
+// tree of k_vecchia_terms / k_vecchia_sum.  No atomics: repeated calls give the same bits.
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_grad(const CkMatern* __restrict__ blk, int metric, int i_pred, double max_dist,
+                                                          const double* __restrict__ pc, long mpad, const double* __restrict__ sc,
+                                                          const double* __restrict__ z, CkLayout L, const int* __restrict__ counts,
+                                                          double c0var, double* __restrict__ pred, double* __restrict__ err,
+                                                          LpTab T, const double* __restrict__ su, const double* __restrict__ pu,
+                                                          LpSearch R, const double* __restrict__ nz, double* __restrict__ vv,
+                                                          CkVecchiaGradArgs A) {
+    __shared__ double lS[(LP_KL + 2) * LP_KL];
+    __shared__ int lidx[LP_KL];
+    __shared__ int wsum[LP_TPB / 64];
+    __shared__ int fail;
+    __shared__ double red[2][LP_TPB];
+    __shared__ double sred[LP_TPB / 64][CK_VG_NPAR];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const long p = blockIdx.x;
+    const int k = counts[p];
+    if (k > LP_KL) return;   // refused by the host before any launch
+    const CkVecchiaModel& V = A.V;
+    double* score = A.score + p * CK_VG_NPAR;
+    const int cv = 0;
+    const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
+    const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
+    const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;        // chord vectors (table path)
+    const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
+    const LpReach Q = lp_reach(R, p, max_dist);
+    const int rp = lp_rank(R, p);
+    double* S = lS;
+    int* idx = lidx;
+    const long ld = LP_KL;
+    if (tid == 0) fail = 0;
+    double mu = 0.0, vvs = 0.0;
+    if (k > 0) {
+        // ---- 1. neighbour list, in site order (block-wide ordered compaction) ----
+        int base = 0;
+        for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
+            if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
+            const long g = g0 + tid;
+            const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp);
+            const unsigned long long bal = __ballot(f);
+            const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
+            if (lane == 0) wsum[wv] = __popcll(bal);
+            __syncthreads();
+            int off = base;
+            for (int w2 = 0; w2 < wv; ++w2) off += wsum[w2];
+            if (f && off + below < LP_KL) idx[off + below] = (int)g;   // (the count is the select pass's: never beyond k)
+            int tot = 0;
+            for (int w2 = 0; w2 < LP_TPB / 64; ++w2) tot += wsum[w2];
+            base += tot;
+            __syncthreads();
+        }
+        // ---- 2. local covariance (lower triangle), c row, z row ----
+        const long npair = (long)k * (k + 1) / 2;
+        for (long e = tid; e < npair; e += LP_TPB) {
+            long a = (long)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
+            while (a * (a + 1) / 2 > e) --a;
+            while ((a + 1) * (a + 2) / 2 <= e) ++a;
+            const long b = e - a * (a + 1) / 2;
+            const long ga = idx[a], gb = idx[b];
+            const int pa = ga >= L.n0p, pb = gb >= L.n0p;
+            S[a * ld + b] = lp_cov(blk, T, pa + pb, pa == pb, metric, s0[ga], s1[ga], s2[ga], u0[ga], u1[ga], u2[ga], s0[gb],
+                                   s1[gb], s2[gb], u0[gb], u1[gb], u2[gb]);
+        }
+        for (int a = tid; a < k; a += LP_TPB) {
+            const long ga = idx[a];
+            const int pa = ga >= L.n0p;
+            S[(long)k * ld + a] = lp_cov(blk, T, i_pred + pa, pa == i_pred, metric, p0, p1, p2, q0, q1, q2, s0[ga], s1[ga],
+                                         s2[ga], u0[ga], u1[ga], u2[ga]);
+            S[(long)(k + 1) * ld + a] = z[ga];
+        }
+        __syncthreads();
+        if (nz) {   // measurement-error variances (ck_set_noise): the neighbour's s d on the true diagonal
+            for (int a = tid; a < k; a += LP_TPB) S[(long)a * ld + a] += nz[idx[a]];
+            __syncthreads();
+        }
+        // ---- 3. Cholesky of the k x k block, the two extra rows ride along (forward substitution) ----
+        for (int j = 0; j < k; ++j) {
+            const double piv = S[(long)j * ld + j];
+            if (!(piv > 0.0)) {
+                if (tid == 0) fail = 1;
+                break;   // uniform: every thread reads the same pivot
+            }
+            const double rd = 1.0 / sqrt(piv);
+            __syncthreads();
+            for (int a = j + 1 + tid; a < k + 2; a += LP_TPB) S[(long)a * ld + j] *= rd;
+            if (tid == 0) S[(long)j * ld + j] = sqrt(piv);
+            __syncthreads();
+            const int nb = k - 1 - j;            // columns b = j + 1 .. k - 1
+            const int na = k + 1 - j;            // rows    a = j + 1 .. k + 1
+            const long tot = (long)na * nb;
+            for (long e = tid; e < tot; e += LP_TPB) {
+                const int a = j + 1 + (int)(e / nb), b = j + 1 + (int)(e % nb);
+                if (b <= a) S[(long)a * ld + b] -= S[(long)a * ld + j] * S[(long)b * ld + j];
+            }
+            __syncthreads();
+        }
+    }
+    __syncthreads();
+    if (fail || k == 0) {   // no solve: k_local_solve's outputs for these points
+        if (tid == 0) {
+            pred[p] = NAN;
+            err[p] = NAN;
+        }
+        if (fail) {
+            if (tid < CK_VG_NPAR) score[tid] = ck_vecchia_slot_out(V, tid, 0.0, 1);
+            return;
+        }
+    } else {
+        // ---- 4. pred = v . y, var = c0 - v . v ----
+        double s1v = 0.0, s2v = 0.0;
+        for (int a = tid; a < k; a += LP_TPB) {
+            const double v = S[(long)k * ld + a], y = S[(long)(k + 1) * ld + a];
+            s1v += v * y;
+            s2v += v * v;
+        }
+        red[0][tid] = s1v;
+        red[1][tid] = s2v;
+        __syncthreads();
+        for (int s = LP_TPB / 2; s > 0; s >>= 1) {
+            if (tid < s) {
+                red[0][tid] += red[0][tid + s];
+                red[1][tid] += red[1][tid + s];
+            }
+            __syncthreads();
+        }
+        mu = red[0][0];
+        vvs = red[1][0];
+        if (tid == 0) {
+            pred[p] = mu;
+            vv[p] = vvs;
+            const double sd = sqrt(c0var - vvs);
+            err[p] = (sd == sd) ? fmax(sd, 0.0) : 0.0;
+        }
+    }
+    // ---- the two weights of M ----
+    const long gs = A.gself[p];
+    double w_bb, w_ab;
+    const int bad = ck_vecchia_weights(z[gs], mu, vvs, c0var, nz ? nz[gs] : 0.0, k, &w_bb, &w_ab);
+    if (bad) {   // uniform
+        if (tid < CK_VG_NPAR) score[tid] = ck_vecchia_slot_out(V, tid, 0.0, 1);
+        return;
+    }
+    // ---- 5. back substitution: rows k, k + 1 become b = -w and a = alpha ----
+    if (wv == 0 && k > 0) {
+        double xv = lane < k ? S[(long)k * ld + lane] : 0.0, xy = lane < k ? S[(long)(k + 1) * ld + lane] : 0.0;
+        for (int j = k - 1; j >= 0; --j) {
+            const double dj = S[(long)j * ld + j];
+            const double lj = lane < j ? S[(long)j * ld + lane] : 0.0;
+            const double vj = __shfl(xv, j) / dj, yj = __shfl(xy, j) / dj;
+            if (lane == j) {
+                xv = vj;
+                xy = yj;
+            } else if (lane < j) {
+                xv -= lj * vj;
+                xy -= lj * yj;
+            }
+        }
+        if (lane < k) {
+            S[(long)k * ld + lane] = -xv;
+            S[(long)(k + 1) * ld + lane] = xy;
+        }
+    }
+    __syncthreads();
+    // ---- 6. the contraction over the lower triangle of the set plus the datum ----
+    double acc[CK_VG_NPAR];
+#pragma unroll
+    for (int c = 0; c < CK_VG_NPAR; ++c) acc[c] = 0.0;
+    const long npair1 = (long)(k + 1) * (k + 2) / 2;
+    for (long e = tid; e < npair1; e += LP_TPB) {
+        int a, b;
+        ck_vg_pair_of(e, &a, &b);
+        const long ga = a < k ? idx[a] : gs, gb = b < k ? idx[b] : gs;
+        const int pa = a < k ? (V.n_procs == 2 && ga >= L.n0p ? 1 : 0) : i_pred;
+        const int pb = b < k ? (V.n_procs == 2 && gb >= L.n0p ? 1 : 0) : i_pred;
+        const double a0 = a < k ? s0[ga] : p0, a1 = a < k ? s1[ga] : p1, a2 = a < k ? s2[ga] : p2;
+        const double b0 = b < k ? s0[gb] : p0, b1 = b < k ? s1[gb] : p1, b2 = b < k ? s2[gb] : p2;
+        const double ba = a < k ? S[(long)k * ld + a] : 1.0, aa = a < k ? S[(long)(k + 1) * ld + a] : 0.0;
+        const double bb = b < k ? S[(long)k * ld + b] : 1.0, ab = b < k ? S[(long)(k + 1) * ld + b] : 0.0;
+        const double h = a == b ? 0.0 : lp_dist(metric, a0, a1, a2, b0, b1, b2);
+        const double d_p = (a == b && A.dvar) ? A.dvar[ga] : 0.0;
+        ck_vecchia_pair(acc, V, pa, pb, a == b, h, ck_vecchia_m(w_bb, w_ab, ba, aa, bb, ab), d_p);
+    }
+#pragma unroll
+    for (int c = 0; c < CK_VG_NPAR; ++c) {
+        double v = acc[c];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        acc[c] = v;
+    }
+    if (lane == 0)
+#pragma unroll
+        for (int c = 0; c < CK_VG_NPAR; ++c) sred[wv][c] = acc[c];
+    __syncthreads();
+    if (tid < CK_VG_NPAR) score[tid] = ck_vecchia_slot_out(V, tid, ((sred[0][tid] + sred[1][tid]) + sred[2][tid]) + sred[3][tid], 0);
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_grad_part(long n, const double* __restrict__ score, double* __restrict__ part) {
+    __shared__ double red[CK_VG_NPAR][LP_TPB];
+    const int tid = threadIdx.x;
+    const long t = (long)blockIdx.x * LP_TPB + tid;
+    for (int c = 0; c < CK_VG_NPAR; ++c) red[c][tid] = t < n ? score[t * CK_VG_NPAR + c] : 0.0;
+    __syncthreads();
+    for (int s = LP_TPB / 2; s > 0; s >>= 1) {
+        if (tid < s)
+            for (int c = 0; c < CK_VG_NPAR; ++c) red[c][tid] += red[c][tid + s];
+        __syncthreads();
+    }
+    if (tid < CK_VG_NPAR) part[(long)blockIdx.x * CK_VG_NPAR + tid] = red[tid][0];
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_grad_sum(long nblk, const double* __restrict__ part, double* __restrict__ out13) {
+    __shared__ double red[CK_VG_NPAR][LP_TPB];
+    const int tid = threadIdx.x;
+    for (int c = 0; c < CK_VG_NPAR; ++c) {
+        double v = 0.0;
+        for (long e = tid; e < nblk; e += LP_TPB) v += part[e * CK_VG_NPAR + c];
+        red[c][tid] = v;
+    }
+    __syncthreads();
+    for (int s = LP_TPB / 2; s > 0; s >>= 1) {
+        if (tid < s)
+            for (int c = 0; c < CK_VG_NPAR; ++c) red[c][tid] += red[c][tid + s];
+        __syncthreads();
+    }
+    if (tid < CK_VG_NPAR) out13[tid] = red[tid][0];
+}
+
+void ck_launch_vecchia_grad(hipStream_t s, const CkMatern* blk, int metric, int i_pred, double max_dist, const double* pc, int64_t m,
+                            int64_t mpad, const double* sc, const double* z, CkLayout L, const int* counts, double c0var,
+                            double* pred, double* err, const CkTable* tabs, const double* const* coefs, int use_tab,
+                            const double* su, const double* pu, const double* cb, double cmax, const double* nz, CkLocalCap cap,
+                            double* vv, CkVecchiaGradArgs A) {
+    if (m <= 0) return;
+    const LpTab T{tabs, coefs, use_tab};
+    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp, cap.rs, cap.rp};
+    k_vecchia_grad<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, max_dist, pc, mpad, sc, z, L, counts, c0var, pred,
+                                                              err, T, su, pu, R, nz, vv, A);
+}
+
+void ck_launch_vecchia_grad_sum(hipStream_t s, int64_t n, const double* score, double* part, double* out13) {
+    if (n <= 0) return;
+    const long nblk = (long)((n + LP_TPB - 1) / LP_TPB);
+    k_vecchia_grad_part<<<dim3((unsigned)nblk), dim3(LP_TPB), 0, s>>>((long)n, score, part);
+    k_vecchia_grad_sum<<<dim3(1), dim3(LP_TPB), 0, s>>>(nblk, part, out13);
 }

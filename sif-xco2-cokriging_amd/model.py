@@ -296,7 +296,7 @@ class MultivariateMatern:
         return h
 
     def log_likelihood(self, mf, dist_units: str = "km", fast_dist: bool = True, gradient: bool = False, trend=None,
-                       measurement_error=None, noise_scale=None, vecchia=None, _ranks=None):
+                       measurement_error=None, noise_scale=None, vecchia=None, _ranks=None, _free13=None):
         """Gaussian log-likelihood of the data the joint predictor uses (every field's ``coords_main`` / ``values_main``,
         zero mean as in simple cokriging) under the current parameters:
             l = -1/2 (N log 2 pi + log|Sigma| + z^T Sigma^-1 z),
@@ -317,19 +317,29 @@ class MultivariateMatern:
         ``vecchia`` (a ``vecchia.Vecchia``): Vecchia's approximation instead (``ck_loglik_vecchia``) -- every datum
         conditioned on the earlier data of its ordering within ``vecchia.max_dist`` and under its caps; no Sigma is
         assembled, so it reaches data sizes the exact form cannot.  ``measurement_error`` / ``noise_scale`` are honoured;
-        ``trend`` and ``gradient=True`` are refused (no REML form, no analytic gradient yet).  A datum whose local system is
-        not positive definite raises LinAlgError naming it."""
+        ``trend`` is refused (no REML form), and so is ``gradient=True`` unless the configuration says
+        ``Vecchia(..., gradient="analytic")``: then the call returns (l, dl/dtheta) -- with ``measurement_error``
+        (l, dl/dtheta, dl/ds) -- in the shapes of the dense call, from ``ck_loglik_vecchia_grad`` (conditioning sets of at most
+        64 data; a larger one raises the native error).  A datum whose local system is not positive definite raises
+        LinAlgError naming it."""
         if vecchia is not None:
             if trend is not None:
                 raise ValueError("log_likelihood(vecchia=...) has no restricted (REML) form: trend must be None")
-            if gradient:
+            if gradient and getattr(vecchia, "gradient", "numeric") != "analytic":
                 raise NotImplementedError("the Vecchia likelihood has no analytic gradient yet: call it with gradient=False "
                                           "(fit_likelihood(vecchia=...) differentiates it numerically)")
-            out3, info, _ = self._vecchia_eval(mf, vecchia, dist_units, fast_dist, measurement_error, noise_scale, _ranks)
+            if gradient:
+                out3, g13, info, var = self._vecchia_grad_eval(mf, vecchia, dist_units, fast_dist, measurement_error, noise_scale,
+                                                               _ranks, _free13)
+            else:
+                out3, info, _ = self._vecchia_eval(mf, vecchia, dist_units, fast_dist, measurement_error, noise_scale, _ranks)
             if info != 0:
                 raise LinAlgError(f"the local system of datum {info - 1} (stacked order) is not positive definite, or its "
                                   "conditional variance is not positive")
-            return out3[0]
+            if not gradient:
+                return out3[0]
+            g = g13[:len(self.params.get_names())].copy()
+            return (out3[0], g, g13[11:11 + self.n_procs].copy()) if var is not None else (out3[0], g)
         h, var = self._lik_assembled(mf, dist_units, fast_dist, trend, measurement_error, noise_scale)
         info, out3, g = h.loglik_reml(gradient) if trend is not None else h.loglik(gradient)
         if info != 0:
@@ -349,6 +359,25 @@ class MultivariateMatern:
             ranks = vecchia.ranks([np.asarray(mf.fields[k].coords_main, dtype=np.float64)[:, :2] for k in range(self.n_procs)])
         h.set_local_neighbours(*caps)
         return h.loglik_vecchia(ranks, vecchia.max_dist, terms=terms)
+
+    def _vecchia_grad_eval(self, mf, vecchia, dist_units, fast_dist, measurement_error, noise_scale, ranks=None, free13=None):
+        """(out3, grad13, info, variances) of ``ck_loglik_vecchia_grad`` on the likelihood's handle, set up as ``_vecchia_eval``."""
+        from .vecchia import Vecchia
+        if not isinstance(vecchia, Vecchia):
+            raise ValueError(f"vecchia must be a vecchia.Vecchia, got {type(vecchia).__name__}")
+        caps = vecchia.caps(self.n_procs)
+        h, var = self._lik_assembled(mf, dist_units, fast_dist, None, measurement_error, noise_scale, assemble=False)
+        if ranks is None:
+            ranks = vecchia.ranks([np.asarray(mf.fields[k].coords_main, dtype=np.float64)[:, :2] for k in range(self.n_procs)])
+        h.set_local_neighbours(*caps)
+        try:
+            out3, g13, info, _ = h.loglik_vecchia_grad(ranks, vecchia.max_dist, free=free13)
+        except native.NativeError as exc:
+            if "conditioning set of more than" in str(exc):
+                raise native.NativeError(f"{exc}.  The analytic gradient is for sets of at most 64 data: use "
+                                         "Vecchia(..., gradient=\"numeric\") or smaller max_neighbours") from None
+            raise
+        return out3, g13, info, var
 
     def vecchia_terms(self, mf, vecchia, dist_units: str = "km", fast_dist: bool = True, measurement_error=None,
                       noise_scale=None):
@@ -452,9 +481,12 @@ class MultivariateMatern:
 
         ``vecchia`` (a ``vecchia.Vecchia``): maximise the Vecchia likelihood instead (``log_likelihood(vecchia=...)``), for
         data whose Sigma does not fit; bounds, ``fixed``, the [0, 1] mapping, the noise scales and the not-positive-definite
-        penalty are as above.  There is no analytic gradient yet: it comes from central differences of the value with the
+        penalty are as above.  By default the gradient comes from central differences of the value with the
         step ``fd_step`` in the mapped coordinates, one-sided where a step would leave [0, 1] (2 k evaluations per gradient
-        for k free parameters).  The ordering's ranks are computed once per fit.  ``fit_result.method`` is "Vecchia-ML";
+        for k free parameters).  With ``Vecchia(..., gradient="analytic")`` value and gradient come from one native call per
+        evaluation (``ck_loglik_vecchia_grad``, the slots held fixed masked out), under the dense path's optimiser options;
+        ``fd_step`` is then validated and otherwise unused, and a conditioning set beyond 64 data raises the native error.
+        The ordering's ranks are computed once per fit.  ``fit_result.method`` is "Vecchia-ML";
         ``trend`` and ``std_errors=True`` are refused (the Fisher information is the dense one)."""
         from .noise import resolve_measurement_error
         from .trend import check_trend
@@ -542,7 +574,17 @@ class MultivariateMatern:
                     gs[k] = gu[nf + j] / (sc[k] * s_width)
             return ll, g, gs
 
+        analytic_v = vecchia is not None and getattr(vecchia, "gradient", "numeric") == "analytic"
+        free13 = np.zeros(13, dtype=bool)   # the live slots of ck_loglik_vecchia_grad: the free parameters, the fitted scales
+        free13[free] = True
+        for k in s_free:
+            free13[11 + k] = True
+
         def loglik(u):
+            if analytic_v:   # value and gradient from one native call; the slots held fixed are not computed (exact zeros)
+                out = self.log_likelihood(mf, dist_units, fast_dist, gradient=True, measurement_error=measurement_error,
+                                          noise_scale=scales_of(u), vecchia=vecchia, _ranks=v_ranks, _free13=free13)
+                return out if len(out) == 3 else (out[0], out[1], np.zeros(self.n_procs))
             if vecchia is not None:
                 return loglik_v(u)
             out = self.log_likelihood(mf, dist_units, fast_dist, gradient=True, trend=trend, measurement_error=measurement_error,
@@ -578,7 +620,8 @@ class MultivariateMatern:
         if s_free:
             u0 = np.concatenate([u0, [(np.log(np.clip(s_cur[k], 1e-3, 1e3)) - s_lo) / s_width for k in s_free]])
         res = minimize(cost, u0, jac=True, method="L-BFGS-B", bounds=[(0.0, 1.0)] * len(u0),
-                       options=dict(VECCHIA_FIT_OPTIONS) if vecchia is not None else {"maxiter": 1000, "ftol": 1e-13, "gtol": 1e-9})
+                       options=dict(VECCHIA_FIT_OPTIONS) if vecchia is not None and not analytic_v
+                       else {"maxiter": 1000, "ftol": 1e-13, "gtol": 1e-9})
         if res.success == False:   # noqa: E712  (as fit)
             warnings.warn("ERROR: optimization did not converge.")
         theta = theta_of(res.x)

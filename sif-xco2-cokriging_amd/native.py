@@ -79,6 +79,8 @@ _PROTOS = {
     "ck_debug_local_neighbours": [c_void_p, c_int, _dp, c_int64, c_double, c_int, POINTER(c_int32), _dp],
     "ck_loglik_vecchia": [c_void_p, POINTER(c_int64), c_double, _dp, _dp, _dp, POINTER(c_int32), POINTER(c_int64),
                           POINTER(c_int64)],
+    "ck_loglik_vecchia_grad": [c_void_p, POINTER(c_int64), c_double, POINTER(c_int32), _dp, _dp, _dp, POINTER(c_int64),
+                               POINTER(c_int64)],
     "ck_predict_local_universal": [c_void_p, c_int, _dp, c_int64, _dp, c_double, c_int, _dp, _dp, _dp, POINTER(c_int64),
                                    POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
     "ck_vario_begin": [c_void_p, _dp, _dp, c_int64, _dp, _dp, c_int64, c_int],
@@ -702,6 +704,37 @@ class Handle:
         _chk(lib().ck_timings(self._h, _p(out), 78))
         keys = ["select_ms", "solve_ms", "terms_ms", "total_ms", "n_lds", "n_tiled"]
         return dict(zip(keys, out[72:78].tolist()))
+
+    def loglik_vecchia_grad(self, rank, max_dist, free=None, scores=False):
+        """Vecchia log-likelihood with its analytic gradient (include/cokrige.h: ck_loglik_vecchia_grad), for conditioning sets
+        of at most 64 data.  ``free``: 13 flags over the slots of fisher() (None: all).  Returns (out3, grad13, info, stats):
+        out3 has loglik_vecchia's bits; grad13 holds exact zeros in the slots that are not live and is NaN when info != 0;
+        with ``scores`` stats["score"] is the (N, 13) array of the per-datum contributions in the stacked order."""
+        r = np.ascontiguousarray(rank, dtype=np.int64).reshape(-1)
+        n = int(sum(self._n_data.values()))
+        if r.size != n:
+            raise ValueError(f"rank has {r.size} entries, the handle {n} data")
+        fr = None
+        if free is not None:
+            fr = np.ascontiguousarray(np.asarray(free).astype(bool), dtype=np.int32)
+            if fr.shape != (13,):
+                raise ValueError("free: 13 flags, one per slot")
+        out3, grad, st, info = np.zeros(3), np.zeros(13), np.zeros(3, dtype=np.int64), c_int64(0)
+        score = np.empty((n, 13)) if scores else None
+        _chk(lib().ck_loglik_vecchia_grad(self._h, r.ctypes.data_as(POINTER(c_int64)), float(max_dist),
+                                          fr.ctypes.data_as(POINTER(c_int32)) if fr is not None else None, _p(out3), _p(grad),
+                                          _p(score) if scores else None, st.ctypes.data_as(POINTER(c_int64)), byref(info)))
+        stats = dict(n_empty=int(st[0]), k_max=int(st[1]), n_capped=int(st[2]))
+        if scores:
+            stats["score"] = score
+        return out3, grad, info.value, stats
+
+    def vecchia_grad_timings(self):
+        """ck_timings [80 ..] of the last loglik_vecchia_grad() call (milliseconds; the last two are counts)."""
+        out = np.zeros(86)
+        _chk(lib().ck_timings(self._h, _p(out), 86))
+        keys = ["select_ms", "solve_ms", "reduce_ms", "total_ms", "n_data", "n_pairs"]
+        return dict(zip(keys, out[80:86].tolist()))
 
     def local_reserve(self, nbytes: int = 0):
         """Pre-size the scratch slab of predict_local (0: the automatic budget) -- include/cokrige.h: ck_local_reserve."""

@@ -9,6 +9,7 @@ from . import native
 from .point_prediction import check_max_neighbours
 
 ORDERINGS = ("random", "hilbert")
+GRADIENTS = ("numeric", "analytic")
 
 
 def check_ordering(ordering):
@@ -55,9 +56,11 @@ def ordering_ranks(coords_per_process, ordering="random", seed=0):
 class Vecchia:
     """Configuration of the Vecchia likelihood: ``max_dist`` (in the distance units of the call), ``max_neighbours`` (None,
     an int for every process or one int per process; 0 = no cap), ``ordering`` ("random", "hilbert" or an array of ranks) and
-    the ``seed`` of the random ordering.  Validated here, before any device work."""
+    the ``seed`` of the random ordering.  ``gradient``: "numeric" (the default: ``fit_likelihood`` differences the value) or
+    "analytic" (``ck_loglik_vecchia_grad``: value and gradient from one native call, for conditioning sets of at most 64 data --
+    ``log_likelihood(..., gradient=True)`` then works and the fit uses it).  Validated here, before any device work."""
 
-    def __init__(self, max_dist, max_neighbours=None, ordering="random", seed=0):
+    def __init__(self, max_dist, max_neighbours=None, ordering="random", seed=0, gradient="numeric"):
         if isinstance(max_dist, (bool, np.bool_)) or not isinstance(max_dist, (int, float, np.integer, np.floating)):
             raise ValueError(f"max_dist must be a number, got {max_dist!r}")
         if not np.isfinite(max_dist) or max_dist < 0:
@@ -72,6 +75,9 @@ class Vecchia:
             check_max_neighbours(max_neighbours, 1 if np.isscalar(max_neighbours) else len(max_neighbours))
         self.ordering = check_ordering(ordering)
         self.seed = check_seed(seed)
+        if not isinstance(gradient, str) or gradient not in GRADIENTS:
+            raise ValueError(f"gradient must be one of {GRADIENTS}, got {gradient!r}")
+        self.gradient = gradient
 
     def caps(self, n_procs):
         """The pair of caps for a model of ``n_procs`` processes ((0, 0): none)."""
