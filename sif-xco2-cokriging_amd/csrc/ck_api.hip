@@ -255,7 +255,7 @@ struct ck_handle {
                                       // bit 4: the whole panel step of the factorisation in one launch of cooperating
                                       // workgroups (k_panel_coop: 360.4 -> 350.0 ms; N = 10 000: 14.4 -> 12.8 ms)
     int64_t loo_g0 = -1;              // >= 0 during ck_loocv: right-hand-side row 1 + p is the unit vector of site loo_g0 + p
-    DevBuf<double> d_chunkb;          // chunk bounds of the sites for the radius search (ck_local.hip: LpSearch)
+    DevBuf<double> d_chunkb;          // chunk bounds of the sites for the radius search (ck_local.hip: lp_chunk_far)
     DevBuf<double> local_slab;        // scratch of ck_predict_local, kept between calls (allocating tens of GiB
                                       // costs up to seconds, erratically); grows when a call needs more
     // option "lookahead": the panel step of column K + 1 on a second stream under the trailing update of the columns beyond
@@ -3452,7 +3452,7 @@ extern "C" int ck_loglik_fisher(ck_handle* h, int reml, const int32_t* free13, d
 // ---------------------------------------------------------------------------------------
 // local-neighbourhood cokriging: src/point_prediction.py:45-249
 // ---------------------------------------------------------------------------------------
-// largest chord (in the space of su / pu) a neighbour can have, with a margin (ck_local.hip: LpSearch)
+// largest chord (in the space of su / pu) a neighbour can have, with a margin (ck_local.hip: lp_chunk_far)
 static double local_cmax(const ck_handle* h, double max_dist) {
     double cmax = max_dist;
     if (h->metric == CK_METRIC_HAVERSINE) {
@@ -3461,6 +3461,28 @@ static double local_cmax(const ck_handle* h, double max_dist) {
     }
     cmax = cmax * (1.0 + 1e-9) + 1e-12;
     return cmax == cmax ? cmax : INFINITY;
+}
+// What the handle knows of a local call (ck_internal.h: CkLocalProblem); the caller adds its points and the search's cap /
+// precedence pointers.  Behind ensure_layout and ensure_noise.
+static CkLocalProblem local_problem(const ck_handle* h, int i, int cv, double max_dist) {
+    CkLocalProblem P;
+    P.blk = h->d_blk;
+    P.tabs = h->d_tabs;
+    P.coefs = h->d_coefptr;
+    P.use_tab = tables_usable(h) ? 1 : 0;
+    P.metric = h->metric;
+    P.i_pred = i;
+    P.cv = cv ? 1 : 0;
+    P.max_dist = max_dist;
+    P.c0var = h->blk[2 * i].amp + h->blk[2 * i].nugget;   // covariance(i, 0)[0], point_prediction.py:66
+    P.sc = h->s0;
+    P.su = h->su;
+    P.z = h->z;
+    P.L = layout_of(h);
+    P.nz = noise_sd(h);   // measurement-error variances on the diagonal of every local system (null: off)
+    P.cb = h->d_chunkb;
+    P.cmax = local_cmax(h, max_dist);
+    return P;
 }
 
 // the neighbour cap of process q as the kernels take it (a cap beyond INT_MAX binds nowhere; one process: no second cap)
@@ -3519,9 +3541,11 @@ extern "C" int ck_debug_local_neighbours(ck_handle* h, int i, const double* pcoo
     HIPCHK(hipMemcpyAsync(d_pc, pcoords, 2 * m * 8, hipMemcpyHostToDevice, h->stream));
     ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, d_p3, d_p3 + mp, d_p3 + 2 * mp, d_pu);
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    ck_launch_local_select(h->stream, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, layout_of(h), h->d_chunkb,
-                           local_cmax(h, max_dist), d_pu, local_nmax_of(h, 0), local_nmax_of(h, 1), local_key_cap(h), d_cnt, d_sel,
-                           d_rq, d_cp);
+    CkLocalProblem P = local_problem(h, i, cv, max_dist);   // (the select pass reads neither the values nor the noise)
+    P.pc = d_p3;
+    P.pu = d_pu;
+    P.mpad = mp;
+    ck_launch_local_select(h->stream, P, m, local_nmax_of(h, 0), local_nmax_of(h, 1), local_key_cap(h), d_cnt, d_sel, d_rq, d_cp);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     std::vector<int> sel((size_t)(4 * m));
@@ -3571,7 +3595,6 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     const int upi = u ? h->trend_p[i] : 0;
     if (u && ensure_trend(h)) return -1;
     if (ensure_noise(h)) return -1;
-    const double* nz = noise_sd(h);   // measurement-error variances on the diagonal of every local system (null: off)
     const int64_t mp = roundup(m, 64);
     DevTemps tmp;
     double *d_pc = nullptr, *d_p3 = nullptr, *d_pu = nullptr, *d_out = nullptr, *d_slab = nullptr;
@@ -3604,7 +3627,15 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
         HIPCHK(hipMemsetAsync(d_vv, 0, (size_t)(mp * 8), h->stream));
         HIPCHK(hipMemcpyAsync(d_rp, vc->rp, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
     }
-    const CkLocalCap cap{d_rq, d_cp, vc ? vc->d_rs : nullptr, d_rp};
+    CkLocalProblem P = local_problem(h, i, cv, max_dist);   // what every launch below is told about the call
+    P.pc = d_p3;
+    P.pu = d_pu;
+    P.mpad = mp;
+    P.rq = d_rq;
+    P.cp = d_cp;
+    P.rs = vc ? vc->d_rs : nullptr;
+    P.rp = d_rp;
+    const double c0var = P.c0var;
     // universal form: the regressors of the prediction points (a point with a non-finite one is settled on the host at the
     // end and computes with zeros meanwhile), the status of every point, the local coefficients
     double *d_f0 = nullptr, *d_beta = nullptr;
@@ -3628,13 +3659,10 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     HIPCHK(hipMemcpyAsync(d_pc, pcoords, 2 * m * 8, hipMemcpyHostToDevice, h->stream));
     ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, d_p3, d_p3 + mp, d_p3 + 2 * mp, d_pu);
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    const double cmax = local_cmax(h, max_dist);
     if (capped)
-        ck_launch_local_select(h->stream, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, layout_of(h), h->d_chunkb, cmax,
-                               d_pu, nmax0, nmax1, local_key_cap(h), d_cnt, d_sel, d_rq, d_cp, cap);
+        ck_launch_local_select(h->stream, P, m, nmax0, nmax1, local_key_cap(h), d_cnt, d_sel, d_rq, d_cp);
     else
-        ck_launch_local_count(h->stream, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, layout_of(h), d_cnt,
-                              h->d_chunkb, cmax, d_pu);
+        ck_launch_local_count(h->stream, P, m, d_cnt);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev1, h->stream));   // [ev0, ev1]: the counting pass; the host-side planning and a growth of the
                                                  // scratch slab (hipMalloc: up to seconds) lie between the two device windows
@@ -3689,17 +3717,12 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     if (slab_doubles > 0) d_slab = h->local_slab;
     HIPCHK(hipEventRecord(h->ev2, h->stream));
     HIPCHK(hipMemcpyAsync(d_off, plan.off.data(), m * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    const double c0var = h->blk[2 * i].amp + h->blk[2 * i].nugget;   // covariance(i, 0)[0], point_prediction.py:66
-    const int use_tab = tables_usable(h) ? 1 : 0;
     if (u)
-        ck_launch_local_solve_u(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, m, mp, h->s0, h->z, layout_of(h),
-                                d_cnt, c0var, d_out, d_out + mp, h->d_tabs, h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb,
-                                cmax, Tr, d_beta, d_stat, nz, cap);
+        ck_launch_local_solve_u(h->stream, P, m, d_cnt, k_hi, Tr, d_out, d_out + mp, d_beta, d_stat);
     else
         for (const auto& bt : plan.batches)
-            ck_launch_local_solve(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, bt.first, bt.second - bt.first,
-                                  mp, h->s0, h->z, layout_of(h), d_cnt, d_off, d_slab, c0var, d_out, d_out + mp, h->d_tabs,
-                                  h->d_coefptr, use_tab, h->su, d_pu, k_hi, h->d_chunkb, cmax, nz, cap, d_vv);
+            ck_launch_local_solve(h->stream, P, bt.first, bt.second - bt.first, d_cnt, d_off, d_slab, k_hi, d_out, d_out + mp,
+                                  d_vv);
     HIPCHK(hipGetLastError());
     std::vector<hipEvent_t> ev_red;   // universal form: an event pair around every batch's reduction (ck_timings [50])
     struct EvFree {
@@ -3717,9 +3740,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
         for (const auto& tb : plan.tbatches) {
             const CkLocalSys* bsys = d_sys + tb.first;
             const int nb = (int)(tb.second - tb.first);
-            ck_launch_local_assemble_t(h->stream, h->d_blk, h->metric, i, cv ? 1 : 0, max_dist, d_p3, mp, h->s0, h->z,
-                                       layout_of(h), bsys, nb, d_slab, h->d_tabs, h->d_coefptr, use_tab, h->su, d_pu,
-                                       h->d_chunkb, cmax, d_k0 + tb.first, nz, cap);
+            ck_launch_local_assemble_t(h->stream, P, bsys, nb, d_slab, d_k0 + tb.first);
             if (u) ck_launch_local_trend_rows_t(h->stream, bsys, nb, d_slab, layout_of(h), Tr);
             const int kq_max = plan.sys[tb.first].kq;
             std::vector<int> kqv(nb);
@@ -4062,7 +4083,6 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
     V.sig2 = h->par_sigma[1];
     V.rho = h->par_rho;
     V.n_procs = h->n_procs;
-    const double* nz = noise_sd(h);
     A.dvar = (V.live >> 11 & 3u) ? h->d_noise + Np : nullptr;
     DevTemps tmp;
     int *d_rs = nullptr, *d_gself = nullptr;
@@ -4077,9 +4097,9 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
         int64_t m = 0, mp = 0;
         double *d_p3 = nullptr, *d_pu = nullptr, *d_out = nullptr, *d_rq = nullptr, *d_cp = nullptr, *d_vv = nullptr;
         int *d_cnt = nullptr, *d_rp = nullptr;
+        CkLocalProblem prob;
     } pass[2];
     const int nmax0 = local_nmax_of(h, 0), nmax1 = local_nmax_of(h, 1);
-    const double cmax = local_cmax(h, max_dist);
     const int kl = ck_local_lds_limit();
     std::vector<int32_t> cnt2((size_t)(2 * N), 0);
     int64_t n_empty = 0, k_max = 0, n_capped = 0, n_rescan = 0, cand_max = 0, n_over = 0, n_pairs = 0;
@@ -4107,9 +4127,15 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
         HIPCHK(hipMemcpyAsync(d_pc, h->h_coords[k].data(), 2 * m * 8, hipMemcpyHostToDevice, h->stream));
         ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, P.d_p3, P.d_p3 + mp, P.d_p3 + 2 * mp, P.d_pu);
         HIPCHK(hipEventRecord(h->ev0, h->stream));
-        const CkLocalCap pre{nullptr, nullptr, d_rs, P.d_rp};
-        ck_launch_local_select(h->stream, h->metric, k, 0, max_dist, P.d_p3, m, mp, h->s0, layout_of(h), h->d_chunkb, cmax, P.d_pu,
-                               nmax0, nmax1, local_key_cap(h), P.d_cnt, d_sel, P.d_rq, P.d_cp, pre);
+        P.prob = local_problem(h, k, 0, max_dist);   // this process's pass: the select here, the solve in phase 2
+        P.prob.pc = P.d_p3;
+        P.prob.pu = P.d_pu;
+        P.prob.mpad = mp;
+        P.prob.rq = P.d_rq;
+        P.prob.cp = P.d_cp;
+        P.prob.rs = d_rs;
+        P.prob.rp = P.d_rp;
+        ck_launch_local_select(h->stream, P.prob, m, nmax0, nmax1, local_key_cap(h), P.d_cnt, d_sel, P.d_rq, P.d_cp);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(h->ev1, h->stream));
         std::vector<int> sel((size_t)(4 * m));
@@ -4142,20 +4168,16 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
                     "); the gradient is for sets the LDS solver takes: lower the caps or the radius, or difference ck_loglik_vecchia");
     // ---- phase 2: solve, back substitution and contraction, one workgroup per datum
     std::vector<double> mu((size_t)N), vv((size_t)N, 0.0), prior((size_t)N), own((size_t)N, 0.0), zs((size_t)N);
-    const int use_tab = tables_usable(h) ? 1 : 0;
     HIPCHK(hipEventRecord(h->ev2, h->stream));
     for (int k = 0; k < h->n_procs; ++k) {
         const Pass& P = pass[k];
         if (P.m == 0) continue;
         const int64_t soff = k == 0 ? 0 : n0;
-        const double c0 = h->blk[2 * k].amp + h->blk[2 * k].nugget;
-        const CkLocalCap cap{P.d_rq, P.d_cp, d_rs, P.d_rp};
+        const double c0 = P.prob.c0var;
         CkVecchiaGradArgs Ak = A;
         Ak.gself = d_gself + soff;
         Ak.score = d_score + soff * NP;
-        ck_launch_vecchia_grad(h->stream, h->d_blk, h->metric, k, max_dist, P.d_p3, P.m, P.mp, h->s0, h->z, layout_of(h), P.d_cnt, c0,
-                               P.d_out, P.d_out + P.mp, h->d_tabs, h->d_coefptr, use_tab, h->su, P.d_pu, h->d_chunkb, cmax, nz, cap,
-                               P.d_vv, Ak);
+        ck_launch_vecchia_grad(h->stream, P.prob, P.m, P.d_cnt, P.d_out, P.d_out + P.mp, P.d_vv, Ak);
         HIPCHK(hipGetLastError());
         const bool nzk = h->noise_on && !h->noise_var[k].empty();
         for (int64_t t = 0; t < P.m; ++t) {

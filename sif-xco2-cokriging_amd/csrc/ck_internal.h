@@ -328,45 +328,56 @@ void ck_launch_vario_bin(hipStream_t s, int metric, int same, int covariogram, c
                          void* args_dev);
 
 // ---- local-neighbourhood cokriging (ck_local.hip) -------------------------------------------
-// pc: 3 x mpad prediction-site coordinates, sc: 3 x npad site coordinates (exact-formula form)
-// cb: chunk bounds of the sites (ck_launch_local_chunk_bounds: 4 x ceil(nend / 256) doubles), cmax: largest chord
-// (distance in the space of the chord vectors su / pu) a neighbour can have, with its safety margin
+// One workgroup per point (or per tiled system).  Every launch that searches, assembles or solves is told about the call by
+// ONE descriptor, filled once per call by ck_api.hip and passed to the kernels by value; a launcher's other arguments are
+// what differs between launches (the point range, outputs, scratch).  ck_local.hip's header lists the steps and which kernel
+// composes which.
 void ck_launch_local_chunk_bounds(hipStream_t s, const double* su, CkLayout L, double* cb);
-// The cut distances and culling chords a capped call's select pass leaves (ck_launch_local_select below), and the precedence
-// pointers (ck_loglik_vecchia): rs = every site's position in the caller's ordering (npad ints, internal site order),
-// rp = the points' (mpad ints); a site is searched only if rs[site] < rp[point].  Null: no such condition.
-struct CkLocalCap {
-    const double* rq = nullptr;
-    const double* cp = nullptr;
-    const int* rs = nullptr;
-    const int* rp = nullptr;
+struct CkLocalProblem {
+    // the model: the Matern blocks and their tables (ck_math.h "Tabulated covariance"; use_tab 0: exact formulas only)
+    const CkMatern* blk = nullptr;
+    const CkTable* tabs = nullptr;          // [3]
+    const double* const* coefs = nullptr;   // [3]
+    int use_tab = 0;
+    int metric = 0, i_pred = 0, cv = 0;     // cv: sites of process i_pred at distance 0 are no neighbours
+    double max_dist = 0.0;
+    double c0var = 0.0;                     // the prior variance of process i_pred
+    // the sites, internal order: sc = 3 x npad coordinates (exact-formula form), su = their chord vectors, z = the values,
+    // nz = ck_set_noise's s d, added to the diagonal of every local system (null: off)
+    const double *sc = nullptr, *su = nullptr, *z = nullptr;
+    CkLayout L{};
+    const double* nz = nullptr;
+    // the points: pc = 3 x mpad coordinates, pu = their chord vectors
+    const double *pc = nullptr, *pu = nullptr;
+    int64_t mpad = 0;
+    // the search: cb = chunk bounds of the sites (ck_launch_local_chunk_bounds: 4 x ceil(nend / 256) doubles), cmax = largest
+    // chord (distance in the space of su / pu) a neighbour can have, with its safety margin.
+    // Neighbour cap: rq = m x 2 cut distances, cp = m culling chords, as the select pass left them (both null: no cap, every
+    // point reaches max_dist / cmax).  Precedence (ck_loglik_vecchia): rs = every site's position in the caller's ordering
+    // (npad ints), rp = the points' (mpad ints); a site is searched only if rs[site] < rp[point] (both null: no condition).
+    const double* cb = nullptr;
+    double cmax = 0.0;
+    const double *rq = nullptr, *cp = nullptr;
+    const int *rs = nullptr, *rp = nullptr;
 };
-void ck_launch_local_count(hipStream_t s, int metric, int i_pred, int cv, double max_dist, const double* pc,
-                           int64_t m, int64_t mpad, const double* sc, CkLayout L, int* counts, const double* cb,
-                           double cmax, const double* pu, CkLocalCap cap = {} /* its precedence pointers only */);
+// neighbour count of the points [0, m) (an uncapped call's counting pass)
+void ck_launch_local_count(hipStream_t s, const CkLocalProblem& P, int64_t m, int* counts);
 // The neighbour cap (ck_set_local_neighbours; include/cokrige.h has the rule).  ck_launch_local_select is the counting pass
 // of a capped call: per point and process the cut distance r_pq (rq: m x 2; max_dist where the cap does not bind) and the
 // final counts (sel: m x 4 ints -- neighbours of process 0, of process 1, candidates before the cap, flags), their sum in
 // counts, and the point's culling chord cp (the chord of max(r_p0, r_p1) with cmax's margin; cmax itself where that is
 // max_dist).  key_cap: candidates per process kept in LDS (option "local_select_cap"); a process with more runs the same
-// rounds re-scanning its chunks.  The later launches take (rq, cp) as CkLocalCap; null pointers: no cap, today's expressions.
+// rounds re-scanning its chunks.  The pass itself searches within max_dist / cmax whatever P.rq / P.cp hold (they are
+// usually the very buffers it fills); it honours the precedence pointers.
 #define CK_LS_CAPPED 1   // sel flags: the cap binds for some process of the point
 #define CK_LS_RESCAN 2   //            some process had more candidates than key_cap
 int ck_local_select_capacity();
-void ck_launch_local_select(hipStream_t s, int metric, int i_pred, int cv, double max_dist, const double* pc, int64_t m,
-                            int64_t mpad, const double* sc, CkLayout L, const double* cb, double cmax, const double* pu,
-                            int nmax0, int nmax1, int key_cap, int* counts, int* sel, double* rq, double* cp,
-                            CkLocalCap cap = {} /* its precedence pointers only */);
-// slab_off[p]: offset (doubles) of point p's scratch slab ((k + 2) k doubles + k ints) when its
-// neighbourhood exceeds the LDS limit
-void ck_launch_local_solve(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
-                           const double* pc, int64_t p_base, int64_t m, int64_t mpad, const double* sc, const double* z,
-                           CkLayout L, const int* counts, const long long* slab_off, double* slab, double c0var,
-                           double* pred, double* err, const CkTable* tabs, const double* const* coefs, int use_tab,
-                           const double* su, const double* pu, int k_hi, const double* cb, double cmax,
-                           const double* nz = nullptr /* ck_set_noise: s d per site in the internal order, added to the diagonal
-                           of every local system next to z[ga]; null: off (the same for the other local launches) */,
-                           CkLocalCap cap = {}, double* vv = nullptr /* the raw v . v of every solved point, or null */);
+void ck_launch_local_select(hipStream_t s, const CkLocalProblem& P, int64_t m, int nmax0, int nmax1, int key_cap, int* counts,
+                            int* sel, double* rq, double* cp);
+// points [p_base, p_base + m).  slab_off[p]: offset (doubles) of point p's scratch slab ((k + 2) k doubles + k ints) when its
+// neighbourhood exceeds the LDS limit, relative to `slab` within this batch; vv: the raw v . v of every solved point, or null
+void ck_launch_local_solve(hipStream_t s, const CkLocalProblem& P, int64_t p_base, int64_t m, const int* counts,
+                           const long long* slab_off, double* slab, int k_hi, double* pred, double* err, double* vv);
 int ck_local_lds_limit();
 // The Vecchia likelihood's terms (ck_loglik_vecchia), n data in the caller's stacked order: from (z, mu, v . v, prior variance,
 // own noise -- null: none --, the two counts) to mean / var per datum and, by a fixed tree over part (2 x ceil(n / 256) doubles)
@@ -374,9 +385,10 @@ int ck_local_lds_limit();
 void ck_launch_vecchia_terms(hipStream_t s, int64_t n, const double* z, const double* mu, const double* vv, const double* prior,
                              const double* noise, const int* cnt2, double* mean, double* var, double* part, long long* bad,
                              double* out2, long long* info);
-// The gradient of the Vecchia likelihood (ck_loglik_vecchia_grad; ck_vecchia_grad.h): k_vecchia_grad is k_local_solve for sets
-// of at most ck_local_lds_limit() data (same pred / err / vv bits; an empty set writes NaN, NaN as there) followed by the back
-// substitution and the contraction.  gself: the m points' own internal site indices; dvar: the raw measurement-error variances
+// The gradient of the Vecchia likelihood (ck_loglik_vecchia_grad; ck_vecchia_grad.h): k_vecchia_grad runs k_local_solve's steps
+// (the same device functions: same pred / err / vv bits; an empty set writes NaN, NaN as there) on sets of at most
+// ck_local_lds_limit() data, points [0, m), followed by the back substitution and the contraction.
+// gself: the m points' own internal site indices; dvar: the raw measurement-error variances
 // d in the internal order (npad) or null; score: m x CK_VG_NPAR, the points' order.  ck_launch_vecchia_grad_sum: column sums of
 // n scores by the fixed tree of the terms (part: CK_VG_NPAR x ceil(n / 256) doubles).
 struct CkVecchiaGradArgs {
@@ -385,10 +397,7 @@ struct CkVecchiaGradArgs {
     const double* dvar;
     double* score;
 };
-void ck_launch_vecchia_grad(hipStream_t s, const CkMatern* blk, int metric, int i_pred, double max_dist, const double* pc, int64_t m,
-                            int64_t mpad, const double* sc, const double* z, CkLayout L, const int* counts, double c0var,
-                            double* pred, double* err, const CkTable* tabs, const double* const* coefs, int use_tab,
-                            const double* su, const double* pu, const double* cb, double cmax, const double* nz, CkLocalCap cap,
+void ck_launch_vecchia_grad(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, double* pred, double* err,
                             double* vv, CkVecchiaGradArgs A);
 void ck_launch_vecchia_grad_sum(hipStream_t s, int64_t n, const double* score, double* part, double* out13);
 
@@ -407,12 +416,8 @@ void ck_launch_vecchia_grad_sum(hipStream_t s, int64_t n, const double* score, d
 //   idx   k ints (neighbour list)
 // CkLocalSys, CK_LT_ROWS, CK_LT_NINV and the sizes ck_local_tiled_kq / ck_local_tiled_doubles: ck_host.h (the host plans with them)
 #define CK_LT_BIG 1e200
-void ck_launch_local_assemble_t(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
-                                const double* pc, int64_t mpad, const double* sc, const double* z, CkLayout L,
-                                const CkLocalSys* sys, int n_sys, double* slab, const CkTable* tabs,
-                                const double* const* coefs, int use_tab, const double* su, const double* pu,
-                                const double* cb, double cmax, int* k0buf /* n_sys ints of scratch */,
-                                const double* nz = nullptr, CkLocalCap cap = {});
+void ck_launch_local_assemble_t(hipStream_t s, const CkLocalProblem& P, const CkLocalSys* sys, int n_sys, double* slab,
+                                int* k0buf /* n_sys ints: the process-0 neighbour counts */);
 // Columns are processed in groups of g 64-column blocks [g0, g0 + 64 g): block i of a group first receives the
 // updates of the group's earlier blocks (one pass, K = 64 i), then its diagonal block is factored and inverted and
 // the rows below are solved; the trailing matrix behind the group is updated once with K = 64 g (a g-th of the
@@ -432,7 +437,7 @@ void ck_launch_local_tiled_trailing(hipStream_t s, const CkLocalSys* sys, double
 void ck_launch_local_tiled_left(hipStream_t s, const CkLocalSys* sys, double* slab, int n_active, int g0, int W,
                                 const int* kq_host);
 void ck_launch_local_reduce_t(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab,
-                              const long long* info, double c0var, double* pred, double* err, double* vv = nullptr);
+                              const long long* info, double c0var, double* pred, double* err, double* vv /* or null */);
 
 // Universal cokriging in the neighbourhood (ck_predict_local_universal): the p = p0 + p1 trend rows X_loc^T ride along each
 // local factorisation like c and z, and a GLS step per point (ck_local_gls.h) follows the reduction.
@@ -451,12 +456,8 @@ struct CkLocalTrend {
 #define CK_LU_EMPTY 1
 #define CK_LU_NOT_PD 2
 #define CK_LU_RANK_DEF 3
-void ck_launch_local_solve_u(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
-                             const double* pc, int64_t m, int64_t mpad, const double* sc, const double* z, CkLayout L,
-                             const int* counts, double c0var, double* pred, double* err, const CkTable* tabs,
-                             const double* const* coefs, int use_tab, const double* su, const double* pu, int k_hi,
-                             const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status,
-                             const double* nz = nullptr, CkLocalCap cap = {});
+void ck_launch_local_solve_u(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, int k_hi, CkLocalTrend Tr,
+                             double* pred, double* err, double* beta, int* status);
 // behind ck_launch_local_assemble_t: the trend rows of the batch's systems
 void ck_launch_local_trend_rows_t(hipStream_t s, const CkLocalSys* sys, int n_sys, double* slab, CkLayout L, CkLocalTrend Tr);
 // k0buf: the process-0 neighbour counts ck_launch_local_assemble_t left

@@ -1,22 +1,41 @@
 // ck_local.hip -- local-neighbourhood cokriging: one workgroup per prediction point.
 //
 // Replaces the per-row Python of point_prediction.Predictor (src/point_prediction.py:127-249):
-//   _local_dist_ix   radius search d <= max_dist per process (cross-validation: process i also
-//                    d > 0, :141-143)
-//   _local_values    gather of the precomputed Sigma blocks  -> here the k x k local covariance is
-//                    assembled on the fly from the k neighbours (no global Sigma is ever stored)
-//   _pred_calc       cho_factor / cho_solve, pred = w.z, std = sqrt(c0 - w.c), nanmax([std, 0])
-//                    -> one Cholesky of the local system carrying c and z as two extra rows
-//                    (forward substitution only: pred = v.y, var = c0 - v.v)
-// Empty neighbourhood -> (NaN, NaN) (:229-233); local Sigma not positive definite -> (NaN, NaN)
-// (:218-222).  Neighbours keep the reference's order: process 0 sites ascending, then process 1.
-// Systems with k <= 64 neighbours live in LDS (k_local_solve); larger ones go through the tiled path (batched
-// 64-column steps on the matrix cores, see below) or, if option "local_tile_min" says so, a global scratch slab
-// per point with a blocked factorisation in one workgroup (k_local_solve_big).
-// Universal cokriging in the neighbourhood (a GLS trend per point, ck_predict_local_universal): behind the tiled path.
-// The Vecchia likelihood (ck_loglik_vecchia) runs the same kernels with the data as the points and one more predicate in the
-// search -- only sites that come earlier in the caller's ordering (lp_later) -- and sums its terms at the end of this file; its
-// gradient (ck_loglik_vecchia_grad) has a kernel of its own behind them, k_vecchia_grad.
+//   _local_dist_ix   radius search d <= max_dist per process (cross-validation: process i also d > 0, :141-143)
+//   _local_values    gather of the precomputed Sigma blocks -> here the k x k local covariance is assembled on the fly
+//                    from the k neighbours (no global Sigma is ever stored)
+//   _pred_calc       cho_factor / cho_solve, pred = w.z, std = sqrt(c0 - w.c), nanmax([std, 0]) -> one Cholesky of the
+//                    local system carrying c and z as two extra rows (forward substitution only)
+// Empty neighbourhood -> (NaN, NaN) (:229-233); local Sigma not positive definite -> (NaN, NaN) (:218-222).
+//
+// Every kernel is told about the call by one CkLocalProblem (ck_internal.h), passed by value.  The steps, each written once:
+//   lp_point      what a workgroup loads for its point: exact and chord coordinates, its reach (LpReach: max_dist / cmax, or
+//                 the neighbour cap's own cut distances and culling chord), its rank in the Vecchia ordering, the site rows
+//   lp_compact    the neighbour list in site order (process 0 sites ascending, then process 1 -- the reference's order):
+//                 chunk culling, the predicate, block-wide ordered compaction; optionally k0 = neighbours of process 0
+//   lp_triangle   lower triangle of the local covariance, one entry per thread through the triangular index
+//   lp_cz_rows    the c row (covariances with the point, lp_c_entry) and the z row behind the triangle
+//   lp_noise      measurement-error variances on the diagonal
+//   lp_chol       unblocked Cholesky in LDS, nx extra rows riding along: behind it they hold L^-1 c, L^-1 z, ..
+//   lp_dots       v . y and v . v by a 256-wide LDS tree;  lp_write / lp_write_nan: pred, v . v, err = nanmax(sqrt(c0 - v.v), 0)
+//   vt_tree / vg_tree   the fixed trees of the Vecchia terms (sum, sum, first bad) and of the 13 score columns
+// and the kernels that compose them:
+//   k_local_count       lp_point, the predicate, a count                        (uncapped call)
+//   k_local_select      lp_point within max_dist, radix select (ck_select.h)    (capped call: counts, cut distances)
+//   k_local_solve       k <= LP_KL: lp_point lp_compact lp_triangle lp_cz_rows lp_noise lp_chol(2) lp_dots lp_write
+//   k_local_solve_big   k <= "local_tile_min": lp_point lp_compact, its own row-by-row triangle, lp_cz_rows lp_noise, a blocked
+//                       Cholesky on a slab in global memory, lp_dots lp_write
+//   k_local_search_t    the tiled path (batched 64-column steps on the matrix cores, ck_la.hip): lp_point lp_compact (with k0),
+//                       padding, lp_c_entry;  k_local_assemble_t: the triangle from a table in LDS;  k_local_reduce_t:
+//                       lp_dots lp_write
+//   k_local_solve_u     universal cokriging, k <= LP_KL: lp_point lp_compact (with k0) lp_triangle lp_cz_rows, trend rows,
+//                       lp_noise lp_chol(2 + p), Gram matrix, GLS step (ck_local_gls.h);  tiled: k_local_trend_rows_t /
+//                       k_local_reduce_ut behind the tiled path
+//   k_vecchia_terms / k_vecchia_sum            vt_tree
+//   k_vecchia_grad      k_local_solve's calls, then back substitution and the contraction (ck_vecchia_grad.h)
+//   k_vecchia_grad_part / k_vecchia_grad_sum   vg_tree
+// The Vecchia likelihood (ck_loglik_vecchia) runs the prediction kernels with the data as the points and one more predicate
+// in the search: only sites that come earlier in the caller's ordering (lp_later).
 #include "ck_internal.h"
 #include "ck_select.h"
 
@@ -31,99 +50,244 @@ __device__ __forceinline__ double lp_dist(int metric, double a0, double a1, doub
     return metric == CK_METRIC_HAVERSINE ? ck_haversine_km(a0, a1, a2, b0, b1, b2) : ck_euclid(a0, a1, b0, b1);
 }
 
-// What a point's search compares against: the cut distance of either process and the culling chord.  Without a neighbour cap
-// (LpSearch::rq null) these are max_dist and the host's cmax; with one, the point's own values from k_local_select.
+// ---- the point ----
+// What a point's search compares against: the cut distance of either process and the culling chord.
 struct LpReach {
     double r0, r1, cmax;
 };
-
-// Precedence (ck_loglik_vecchia): a site takes part only if it comes earlier in the ordering than the point -- rs holds the
-// sites' positions in the ordering (internal site order), rp is the point's.  rs null: no such condition, today's predicate.
-__device__ __forceinline__ bool lp_later(const int* rs, int rp, long g) { return rs && !(rs[g] < rp); }
-
-// the radius predicate (the candidates of the neighbour cap): *d is the device distance, *proc the site's process
-__device__ __forceinline__ bool lp_candidate(int metric, int cv, int i_pred, double max_dist, const CkLayout& L, long g,
-                                             double p0, double p1, double p2, const double* s0, const double* s1,
-                                             const double* s2, const int* rs, int rp, double* d, int* proc) {
-    if (!(g < L.n0 || (g >= L.n0p && g < L.nend))) return false;
-    if (lp_later(rs, rp, g)) return false;
-    *d = lp_dist(metric, p0, p1, p2, s0[g], s1[g], s2[g]);
-    *proc = g >= L.n0p;
-    if (cv && *proc == i_pred) return *d > 0.0 && *d <= max_dist;
-    return *d <= max_dist;
+struct LpPoint {
+    double p0, p1, p2;                 // exact-formula coordinates
+    double q0, q1, q2;                 // chord vector
+    LpReach Q;
+    int rp;                            // position in the ordering (precedence), 0 without one
+    const double *s0, *s1, *s2;        // the sites' coordinate rows
+    const double *u0, *u1, *u2;        // and chord-vector rows (table path)
+};
+// own_reach: the point's cut distances and culling chord from the select pass where the call has a neighbour cap (P.rq);
+// false: max_dist and the host's cmax whatever P.rq holds -- the select pass itself, which searches the candidates
+__device__ __forceinline__ LpPoint lp_point(const CkLocalProblem& P, long p, bool own_reach = true) {
+    LpPoint X;
+    X.p0 = P.pc[p], X.p1 = P.pc[P.mpad + p], X.p2 = P.pc[2 * P.mpad + p];
+    X.q0 = P.pu[p], X.q1 = P.pu[P.mpad + p], X.q2 = P.pu[2 * P.mpad + p];
+    X.Q = (own_reach && P.rq) ? LpReach{P.rq[2 * p], P.rq[2 * p + 1], P.cp[p]} : LpReach{P.max_dist, P.max_dist, P.cmax};
+    X.rp = P.rs ? P.rp[p] : 0;
+    X.s0 = P.sc, X.s1 = P.sc + P.L.npad, X.s2 = P.sc + 2 * P.L.npad;
+    X.u0 = P.su, X.u1 = P.su + P.L.npad, X.u2 = P.su + 2 * P.L.npad;
+    return X;
 }
 
-__device__ __forceinline__ bool lp_is_neighbour(int metric, int cv, int i_pred, const LpReach& Q, const CkLayout& L, long g,
-                                                double p0, double p1, double p2, const double* s0, const double* s1,
-                                                const double* s2, const int* rs, int rp) {
+// ---- the search ----
+// Precedence (ck_loglik_vecchia): a site takes part only if it comes earlier in the ordering than the point.
+__device__ __forceinline__ bool lp_later(const CkLocalProblem& P, const LpPoint& X, long g) { return P.rs && !(P.rs[g] < X.rp); }
+
+// the radius predicate within max_dist (the candidates of the neighbour cap): *d is the device distance, *proc the site's process
+__device__ __forceinline__ bool lp_candidate(const CkLocalProblem& P, const LpPoint& X, long g, double* d, int* proc) {
+    const CkLayout& L = P.L;
     if (!(g < L.n0 || (g >= L.n0p && g < L.nend))) return false;
-    if (lp_later(rs, rp, g)) return false;
-    const double d = lp_dist(metric, p0, p1, p2, s0[g], s1[g], s2[g]);
+    if (lp_later(P, X, g)) return false;
+    *d = lp_dist(P.metric, X.p0, X.p1, X.p2, X.s0[g], X.s1[g], X.s2[g]);
+    *proc = g >= L.n0p;
+    if (P.cv && *proc == P.i_pred) return *d > 0.0 && *d <= P.max_dist;
+    return *d <= P.max_dist;
+}
+
+// the same within the point's reach
+__device__ __forceinline__ bool lp_is_neighbour(const CkLocalProblem& P, const LpPoint& X, long g) {
+    const CkLayout& L = P.L;
+    if (!(g < L.n0 || (g >= L.n0p && g < L.nend))) return false;
+    if (lp_later(P, X, g)) return false;
+    const double d = lp_dist(P.metric, X.p0, X.p1, X.p2, X.s0[g], X.s1[g], X.s2[g]);
     const int proc = g >= L.n0p;
-    const double lim = proc ? Q.r1 : Q.r0;
-    if (cv && proc == i_pred) return d > 0.0 && d <= lim;
+    const double lim = proc ? X.Q.r1 : X.Q.r0;
+    if (P.cv && proc == P.i_pred) return d > 0.0 && d <= lim;
     return d <= lim;
 }
 
+// Radius search with chunk culling: the sites are laid out along a Hilbert curve (ck_api.hip: site_order), so
+// 256 consecutive sites are a compact patch.  Per chunk: the mean c of its chord vectors and rad = max |u - c|
+// (P.cb: 4 x nchunk -- centre x, y, z, rad; rad < 0: no valid site in the chunk).
+// A site can only be within max_dist of a point with chord vector q if its chord to q is <= cmax (haversine:
+// 2 sin(max_dist / 2R), monotone; Euclid: max_dist), and |u - q| >= |c - q| - rad, so a chunk with
+// |c - q| - rad > cmax holds no neighbour and is skipped by the whole workgroup.  cmax carries a relative
+// margin of 1e-9 (host), far above the rounding of either formula; which sites pass is still decided by the
+// reference's distance formula, so the neighbour lists do not change.
+__host__ __device__ __forceinline__ long lp_nchunk(const CkLayout& L) { return (long)((L.nend + LP_TPB - 1) / LP_TPB); }
+
+__device__ __forceinline__ bool lp_chunk_far(const CkLocalProblem& P, const LpPoint& X, long chunk) {
+    const long nchunk = lp_nchunk(P.L);
+    if (chunk >= nchunk) return true;
+    const double rad = P.cb[3 * nchunk + chunk];
+    if (rad < 0.0) return true;
+    const double dx = P.cb[chunk] - X.q0, dy = P.cb[nchunk + chunk] - X.q1, dz = P.cb[2 * nchunk + chunk] - X.q2;
+    return sqrt(dx * dx + dy * dy + dz * dz) - rad > X.Q.cmax;
+}
+
+// The neighbour list, in site order: block-wide ordered compaction into idx.  K0: *k0 = the neighbours of process 0 (a
+// second ballot and counter, paid only here).  CAP > 0: the capacity of idx, entries beyond it are dropped.  Uniform path:
+// every thread reaches both barriers of every chunk that is not culled.
+template <bool K0, int CAP>
+__device__ __forceinline__ void lp_compact(const CkLocalProblem& P, const LpPoint& X, int* idx, int* k0 = nullptr) {
+    __shared__ int wsum[K0 ? 2 : 1][LP_TPB / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int base = 0, n0 = 0;
+    for (long g0 = 0; g0 < P.L.nend; g0 += LP_TPB) {
+        if (lp_chunk_far(P, X, g0 / LP_TPB)) continue;   // uniform
+        const long g = g0 + tid;
+        const bool f = g < P.L.nend && lp_is_neighbour(P, X, g);
+        const unsigned long long bal = __ballot(f);
+        const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
+        if (lane == 0) wsum[0][wv] = __popcll(bal);
+        if (K0) {
+            const unsigned long long bal0 = __ballot(f && g < P.L.n0p);
+            if (lane == 0) wsum[K0 ? 1 : 0][wv] = __popcll(bal0);
+        }
+        __syncthreads();
+        int off = base;
+        for (int w2 = 0; w2 < wv; ++w2) off += wsum[0][w2];
+        if (f && (CAP <= 0 || off + below < CAP)) idx[off + below] = (int)g;
+        for (int w2 = 0; w2 < LP_TPB / 64; ++w2) {
+            base += wsum[0][w2];
+            if (K0) n0 += wsum[K0 ? 1 : 0][w2];
+        }
+        __syncthreads();
+    }
+    if (K0) *k0 = n0;
+}
+
+// ---- the local system ----
 // Covariance of a pair: through the block's table (ck_math.h "Tabulated covariance"; coefficients read from
 // global memory / L2 here -- three 48 KB tables do not fit next to the local system in LDS) when the pair's
 // squared chord is inside the table, else the exact evaluator (closer than the table's lower end incl.
 // h == 0 and the nugget, beyond its upper end, or tables disabled).
-struct LpTab {
-    const CkTable* tabs;             // [3]
-    const double* const* coefs;      // [3]
-    int use;
-};
-
 // the exact formulas out of line: rare beside the table, and inlined they cost the callers their registers
 __device__ __noinline__ double lp_exact_xyz(const CkMatern* m, int metric, int nug, double a0, double a1, double a2,
                                             double b0, double b1, double b2) {
     return ck_cov_entry(*m, lp_dist(metric, a0, a1, a2, b0, b1, b2), nug);
 }
 
-__device__ __forceinline__ double lp_cov(const CkMatern* blk, const LpTab& T, int bidx, int nug, int metric, double a0,
-                                         double a1, double a2, double au0, double au1, double au2, double b0, double b1,
-                                         double b2, double bu0, double bu1, double bu2) {
-    if (T.use) {
+__device__ __forceinline__ double lp_cov(const CkLocalProblem& P, int bidx, int nug, double a0, double a1, double a2,
+                                         double au0, double au1, double au2, double b0, double b1, double b2, double bu0,
+                                         double bu1, double bu2) {
+    if (P.use_tab) {
         const double dx = au0 - bu0, dy = au1 - bu1, dz = au2 - bu2;
         const double q = dx * dx + dy * dy + dz * dz;
         int iv;
-        const double y = ck_table_y(q, &iv, T.tabs[bidx].base);
-        if ((unsigned)iv < (unsigned)T.tabs[bidx].n_int) return ck_table_poly(T.coefs[bidx], iv, y);
+        const double y = ck_table_y(q, &iv, P.tabs[bidx].base);
+        if ((unsigned)iv < (unsigned)P.tabs[bidx].n_int) return ck_table_poly(P.coefs[bidx], iv, y);
     }
-    return lp_exact_xyz(&blk[bidx], metric, nug, a0, a1, a2, b0, b1, b2);
+    return lp_exact_xyz(&P.blk[bidx], P.metric, nug, a0, a1, a2, b0, b1, b2);
 }
 
-// Radius search with chunk culling: the sites are laid out along a Hilbert curve (ck_api.hip: site_order), so
-// 256 consecutive sites are a compact patch.  Per chunk: the mean c of its chord vectors and rad = max |u - c|.
-// A site can only be within max_dist of a point with chord vector q if its chord to q is <= cmax (haversine:
-// 2 sin(max_dist / 2R), monotone; Euclid: max_dist), and |u - q| >= |c - q| - rad, so a chunk with
-// |c - q| - rad > cmax holds no neighbour and is skipped by the whole workgroup.  cmax carries a relative
-// margin of 1e-9 (host), far above the rounding of either formula; which sites pass is still decided by the
-// reference's distance formula, so the neighbour lists do not change.
-struct LpSearch {
-    const double* cb;   // 4 x nchunk: centre x, y, z, rad (rad < 0: no valid site in the chunk)
-    long nchunk;
-    double cmax;
-    const double* rq;   // neighbour cap: m x 2 cut distances and
-    const double* cp;   // m culling chords of the points (both null: no cap)
-    const int* rs;      // precedence (ck_loglik_vecchia): the sites' positions in the ordering, internal site order, and
-    const int* rp;      // the m points' (both null: none)
-};
-
-__device__ __forceinline__ int lp_rank(const LpSearch& R, long p) { return R.rs ? R.rp[p] : 0; }
-
-__device__ __forceinline__ LpReach lp_reach(const LpSearch& R, long p, double max_dist) {
-    if (R.rq) return LpReach{R.rq[2 * p], R.rq[2 * p + 1], R.cp[p]};
-    return LpReach{max_dist, max_dist, R.cmax};
+// the point's covariance with site ga (point_prediction.py:115-125)
+__device__ __forceinline__ double lp_c_entry(const CkLocalProblem& P, const LpPoint& X, long ga) {
+    const int pa = ga >= P.L.n0p;
+    return lp_cov(P, P.i_pred + pa, pa == P.i_pred, X.p0, X.p1, X.p2, X.q0, X.q1, X.q2, X.s0[ga], X.s1[ga], X.s2[ga], X.u0[ga],
+                  X.u1[ga], X.u2[ga]);
 }
 
-__device__ __forceinline__ bool lp_chunk_far(const LpSearch& R, const LpReach& Q, long chunk, double q0, double q1, double q2) {
-    if (chunk >= R.nchunk) return true;
-    const double rad = R.cb[3 * R.nchunk + chunk];
-    if (rad < 0.0) return true;
-    const double dx = R.cb[chunk] - q0, dy = R.cb[R.nchunk + chunk] - q1, dz = R.cb[2 * R.nchunk + chunk] - q2;
-    return sqrt(dx * dx + dy * dy + dz * dz) - rad > Q.cmax;
+// lower triangle of the k x k local covariance into S (leading dimension ld), one entry per thread and pass
+__device__ __forceinline__ void lp_triangle(const CkLocalProblem& P, const LpPoint& X, const int* idx, double* S, long ld, int k) {
+    const long npair = (long)k * (k + 1) / 2;
+    for (long e = threadIdx.x; e < npair; e += LP_TPB) {
+        // e -> (a, b), a >= b:  a = floor((sqrt(8e + 1) - 1) / 2)
+        long a = (long)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
+        while (a * (a + 1) / 2 > e) --a;
+        while ((a + 1) * (a + 2) / 2 <= e) ++a;
+        const long b = e - a * (a + 1) / 2;
+        const long ga = idx[a], gb = idx[b];
+        const int pa = ga >= P.L.n0p, pb = gb >= P.L.n0p;
+        S[a * ld + b] = lp_cov(P, pa + pb, pa == pb, X.s0[ga], X.s1[ga], X.s2[ga], X.u0[ga], X.u1[ga], X.u2[ga], X.s0[gb],
+                               X.s1[gb], X.s2[gb], X.u0[gb], X.u1[gb], X.u2[gb]);
+    }
+}
+
+// rows k (c) and k + 1 (z) of S
+__device__ __forceinline__ void lp_cz_rows(const CkLocalProblem& P, const LpPoint& X, const int* idx, double* S, long ld, int k) {
+    for (int a = threadIdx.x; a < k; a += LP_TPB) {
+        const long ga = idx[a];
+        S[(long)k * ld + a] = lp_c_entry(P, X, ga);
+        S[(long)(k + 1) * ld + a] = P.z[ga];
+    }
+}
+
+// closes the assembly (barrier), then the measurement-error variances (ck_set_noise): the neighbour's s d on the true diagonal
+__device__ __forceinline__ void lp_noise(const CkLocalProblem& P, const int* idx, double* S, long ld, int k) {
+    __syncthreads();
+    if (P.nz) {
+        for (int a = threadIdx.x; a < k; a += LP_TPB) S[(long)a * ld + a] += P.nz[idx[a]];
+        __syncthreads();
+    }
+}
+
+// Cholesky of the k x k block of S in LDS; the nx rows below it ride along (forward substitution).  False: a pivot was not
+// > 0 (src/point_prediction.py:218-222).  Every thread takes the same path: the pivot is read by all, the break is uniform.
+__device__ __forceinline__ bool lp_chol(double* S, long ld, int k, int nx) {
+    __shared__ int fail;
+    const int tid = threadIdx.x;
+    if (tid == 0) fail = 0;
+    for (int j = 0; j < k; ++j) {
+        const double piv = S[(long)j * ld + j];
+        if (!(piv > 0.0)) {
+            if (tid == 0) fail = 1;
+            break;   // uniform: every thread reads the same pivot
+        }
+        const double rd = 1.0 / sqrt(piv);
+        __syncthreads();
+        for (int a = j + 1 + tid; a < k + nx; a += LP_TPB) S[(long)a * ld + j] *= rd;
+        if (tid == 0) S[(long)j * ld + j] = sqrt(piv);
+        __syncthreads();
+        // S[a][b] -= S[a][j] S[b][j] for j < b <= min(a, k - 1), a in (j, k + nx)
+        const int nb = k - 1 - j;            // columns b = j + 1 .. k - 1
+        const int na = k + nx - 1 - j;       // rows    a = j + 1 .. k + nx - 1
+        const long tot = (long)na * nb;
+        for (long e = tid; e < tot; e += LP_TPB) {
+            const int a = j + 1 + (int)(e / nb), b = j + 1 + (int)(e % nb);
+            if (b <= a) S[(long)a * ld + b] -= S[(long)a * ld + j] * S[(long)b * ld + j];
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+    return fail == 0;
+}
+
+// ---- the outputs ----
+// v . y and v . v over k entries of the two solved rows: a strided partial sum per thread, then the 256-wide tree in LDS.
+// Every thread returns with both sums.
+__device__ __forceinline__ void lp_dots(const double* v, const double* y, int k, double* vy, double* vv) {
+    __shared__ double red[2][LP_TPB];
+    const int tid = threadIdx.x;
+    double s1v = 0.0, s2v = 0.0;
+    for (int a = tid; a < k; a += LP_TPB) {
+        s1v += v[a] * y[a];
+        s2v += v[a] * v[a];
+    }
+    red[0][tid] = s1v;
+    red[1][tid] = s2v;
+    __syncthreads();
+    for (int s = LP_TPB / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            red[0][tid] += red[0][tid + s];
+            red[1][tid] += red[1][tid + s];
+        }
+        __syncthreads();
+    }
+    *vy = red[0][0];
+    *vv = red[1][0];
+}
+
+// one thread: pred = v . y, the raw v . v where asked for (ck_loglik_vecchia: the unclamped variance is the caller's),
+// err = np.nanmax([sqrt(c0 - v . v), 0.0]) (point_prediction.py:217)
+__device__ __forceinline__ void lp_write(long p, double vy, double vv, double c0var, double* pred, double* err, double* vvout) {
+    pred[p] = vy;
+    if (vvout) vvout[p] = vv;
+    const double sd = sqrt(c0var - vv);
+    err[p] = (sd == sd) ? fmax(sd, 0.0) : 0.0;
+}
+
+// one thread: an empty neighbourhood (src/point_prediction.py:229-233) or a system that is not positive definite (:218-222)
+__device__ __forceinline__ void lp_write_nan(long p, double* pred, double* err) {
+    pred[p] = NAN;
+    err[p] = NAN;
 }
 
 __global__ __launch_bounds__(LP_TPB) void k_local_chunk_bounds(const double* __restrict__ su, CkLayout L, long nchunk,
@@ -168,23 +332,15 @@ void ck_launch_local_chunk_bounds(hipStream_t s, const double* su, CkLayout L, d
 }
 
 // neighbour count per prediction point
-__global__ __launch_bounds__(LP_TPB) void k_local_count(int metric, int i_pred, int cv, double max_dist,
-                                                         const double* __restrict__ pc, long mpad,
-                                                         const double* __restrict__ sc, CkLayout L,
-                                                         int* __restrict__ counts, LpSearch R,
-                                                         const double* __restrict__ pu) {
+__global__ __launch_bounds__(LP_TPB) void k_local_count(CkLocalProblem P, int* __restrict__ counts) {
     __shared__ int red[LP_TPB];
     const long p = blockIdx.x;
-    const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
-    const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
-    const LpReach Q = lp_reach(R, p, max_dist);
-    const int rp = lp_rank(R, p);
-    const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
+    const LpPoint X = lp_point(P, p);
     int c = 0;
-    for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
-        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;
+    for (long g0 = 0; g0 < P.L.nend; g0 += LP_TPB) {
+        if (lp_chunk_far(P, X, g0 / LP_TPB)) continue;
         const long g = g0 + threadIdx.x;
-        c += (g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp)) ? 1 : 0;
+        c += (g < P.L.nend && lp_is_neighbour(P, X, g)) ? 1 : 0;
     }
     red[threadIdx.x] = c;
     __syncthreads();
@@ -209,22 +365,17 @@ __global__ __launch_bounds__(LP_TPB) void k_local_count(int metric, int i_pred, 
 
 // calls f(process, key) for every candidate this thread meets, chunk by chunk as the counting pass walks them
 template <class F>
-__device__ __forceinline__ void ls_scan(int metric, int i_pred, int cv, double max_dist, const CkLayout& L, const LpSearch& R,
-                                        const LpReach& Q, double p0, double p1, double p2, double q0, double q1, double q2,
-                                        const double* s0, const double* s1, const double* s2, int rp, F f) {
-    for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
-        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;
+__device__ __forceinline__ void ls_scan(const CkLocalProblem& P, const LpPoint& X, F f) {
+    for (long g0 = 0; g0 < P.L.nend; g0 += LP_TPB) {
+        if (lp_chunk_far(P, X, g0 / LP_TPB)) continue;
         const long g = g0 + threadIdx.x;
         double d;
         int proc;
-        if (g < L.nend && lp_candidate(metric, cv, i_pred, max_dist, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp, &d, &proc)) f(proc, ck_sel_key(d));
+        if (g < P.L.nend && lp_candidate(P, X, g, &d, &proc)) f(proc, ck_sel_key(d));
     }
 }
 
-__global__ __launch_bounds__(LP_TPB) void k_local_select(int metric, int i_pred, int cv, double max_dist,
-                                                          const double* __restrict__ pc, long mpad,
-                                                          const double* __restrict__ sc, CkLayout L, LpSearch R,
-                                                          const double* __restrict__ pu, int nmax0, int nmax1, int key_cap,
+__global__ __launch_bounds__(LP_TPB) void k_local_select(CkLocalProblem P, int nmax0, int nmax1, int key_cap,
                                                           int* __restrict__ counts, int* __restrict__ sel,
                                                           double* __restrict__ rq, double* __restrict__ cp) {
     __shared__ unsigned long long keys[2][LS_CAP];
@@ -233,14 +384,13 @@ __global__ __launch_bounds__(LP_TPB) void k_local_select(int metric, int i_pred,
     __shared__ CkSelState st[2];
     const int tid = threadIdx.x;
     const long p = blockIdx.x;
-    const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
-    const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
-    const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
-    const LpReach Q{max_dist, max_dist, R.cmax};   // the candidates are searched within max_dist
-    const int rp = lp_rank(R, p);
+    const int metric = P.metric;
+    const double max_dist = P.max_dist;
+    const CkLayout& L = P.L;
+    const LpPoint X = lp_point(P, p, /*own_reach=*/false);   // the candidates are searched within max_dist
     if (tid < 2) ncand[tid] = 0;
     __syncthreads();
-    ls_scan(metric, i_pred, cv, max_dist, L, R, Q, p0, p1, p2, q0, q1, q2, s0, s1, s2, rp, [&](int q, unsigned long long key) {
+    ls_scan(P, X, [&](int q, unsigned long long key) {
         const unsigned slot = atomicAdd(&ncand[q], 1u);
         if (slot < (unsigned)key_cap) keys[q][slot] = key;
     });
@@ -265,7 +415,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_select(int metric, int i_pred,
                 }
             }
             if (rescan)
-                ls_scan(metric, i_pred, cv, max_dist, L, R, Q, p0, p1, p2, q0, q1, q2, s0, s1, s2, rp, [&](int q, unsigned long long key) {
+                ls_scan(P, X, [&](int q, unsigned long long key) {
                     if ((rescan >> q & 1u) && ck_sel_match(&st[q], key)) atomicAdd(&hist[q][ck_sel_digit(&st[q], key)], 1u);
                 });
             __syncthreads();
@@ -285,153 +435,46 @@ __global__ __launch_bounds__(LP_TPB) void k_local_select(int metric, int i_pred,
         counts[p] = k0 + k1;
         // the chord of the point's reach, with the margin of cmax; a process without sites does not widen it
         const double reach = L.nend > L.n0p ? fmax(r0, r1) : r0;
-        double c = R.cmax;
+        double c = P.cmax;
         if (reach < max_dist) {
             c = reach;
             if (metric == CK_METRIC_HAVERSINE) {
                 const double half = reach / (2.0 * CK_EARTH_RADIUS_KM);
                 c = half >= 1.5 ? 4.0 : 2.0 * sin(half);
             }
-            c = fmin(c * (1.0 + 1e-9) + 1e-12, R.cmax);
+            c = fmin(c * (1.0 + 1e-9) + 1e-12, P.cmax);
         }
         cp[p] = c;
     }
 }
 
-__global__ __launch_bounds__(LP_TPB) void k_local_solve(const CkMatern* __restrict__ blk, int metric, int i_pred,
-                                                         int cv, double max_dist, const double* __restrict__ pc,
-                                                         long mpad, const double* __restrict__ sc,
-                                                         const double* __restrict__ z, CkLayout L,
-                                                         const int* __restrict__ counts,
-                                                         const long long* __restrict__ slab_off,
-                                                         double* __restrict__ slab, double c0var,
+// Systems of k <= LP_KL neighbours, in LDS: a (k + 2) x k matrix (rows k, k + 1 carry c and z) and the neighbour list
+__global__ __launch_bounds__(LP_TPB) void k_local_solve(CkLocalProblem P, const int* __restrict__ counts, long p_base, int k_hi,
                                                          double* __restrict__ pred, double* __restrict__ err,
-                                                         long p_base, LpTab T, const double* __restrict__ su,
-                                                         const double* __restrict__ pu, LpSearch R, int k_hi,
-                                                         const double* __restrict__ nz, double* __restrict__ vv) {
-    __shared__ double lS[(LP_KL + 2) * LP_KL];
-    __shared__ int lidx[LP_KL];
-    __shared__ int wsum[LP_TPB / 64];
-    __shared__ int fail;
-    __shared__ double red[2][LP_TPB];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+                                                         double* __restrict__ vv) {
+    __shared__ double S[(LP_KL + 2) * LP_KL];
+    __shared__ int idx[LP_KL];
+    const int tid = threadIdx.x;
     const long p = p_base + blockIdx.x;
     const int k = counts[p];
-    if (k == 0) {   // src/point_prediction.py:229-233
-        if (tid == 0) {
-            pred[p] = NAN;
-            err[p] = NAN;
-        }
+    if (k == 0) {
+        if (tid == 0) lp_write_nan(p, pred, err);
         return;
     }
     if (k > LP_KL || k > k_hi) return;   // larger systems: k_local_solve_big / the tiled path
-    const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
-    const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
-    const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;        // chord vectors (table path)
-    const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
-    const LpReach Q = lp_reach(R, p, max_dist);
-    const int rp = lp_rank(R, p);
-    // storage: (k + 2) x k matrix (rows k, k + 1 carry c and z) and the neighbour index list
-    double* S = lS;
-    int* idx = lidx;
     const long ld = LP_KL;
-    // ---- 1. neighbour list, in site order (block-wide ordered compaction) ----
-    if (tid == 0) fail = 0;
-    int base = 0;
-    for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
-        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
-        const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp);
-        const unsigned long long bal = __ballot(f);
-        const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
-        if (lane == 0) wsum[wv] = __popcll(bal);
-        __syncthreads();
-        int off = base;
-        for (int w2 = 0; w2 < wv; ++w2) off += wsum[w2];
-        if (f) idx[off + below] = (int)g;
-        int tot = 0;
-        for (int w2 = 0; w2 < LP_TPB / 64; ++w2) tot += wsum[w2];
-        base += tot;
-        __syncthreads();
-    }
-    // ---- 2. local covariance (lower triangle), c row, z row ----
-    const long npair = (long)k * (k + 1) / 2;
-    for (long e = tid; e < npair; e += LP_TPB) {
-        // e -> (a, b), a >= b:  a = floor((sqrt(8e + 1) - 1) / 2)
-        long a = (long)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
-        while (a * (a + 1) / 2 > e) --a;
-        while ((a + 1) * (a + 2) / 2 <= e) ++a;
-        const long b = e - a * (a + 1) / 2;
-        const long ga = idx[a], gb = idx[b];
-        const int pa = ga >= L.n0p, pb = gb >= L.n0p;
-        S[a * ld + b] = lp_cov(blk, T, pa + pb, pa == pb, metric, s0[ga], s1[ga], s2[ga], u0[ga], u1[ga], u2[ga], s0[gb],
-                               s1[gb], s2[gb], u0[gb], u1[gb], u2[gb]);
-    }
-    for (int a = tid; a < k; a += LP_TPB) {
-        const long ga = idx[a];
-        const int pa = ga >= L.n0p;
-        S[(long)k * ld + a] = lp_cov(blk, T, i_pred + pa, pa == i_pred, metric, p0, p1, p2, q0, q1, q2, s0[ga], s1[ga],
-                                     s2[ga], u0[ga], u1[ga], u2[ga]);   // point_prediction.py:115-125
-        S[(long)(k + 1) * ld + a] = z[ga];
-    }
-    __syncthreads();
-    if (nz) {   // measurement-error variances (ck_set_noise): the neighbour's s d on the true diagonal
-        for (int a = tid; a < k; a += LP_TPB) S[(long)a * ld + a] += nz[idx[a]];
-        __syncthreads();
-    }
-    // ---- 3. Cholesky of the k x k block, the two extra rows ride along (forward substitution) ----
-    for (int j = 0; j < k; ++j) {
-        const double piv = S[(long)j * ld + j];
-        if (!(piv > 0.0)) {
-            if (tid == 0) fail = 1;
-            break;   // uniform: every thread reads the same pivot
-        }
-        const double rd = 1.0 / sqrt(piv);
-        __syncthreads();
-        for (int a = j + 1 + tid; a < k + 2; a += LP_TPB) S[(long)a * ld + j] *= rd;
-        if (tid == 0) S[(long)j * ld + j] = sqrt(piv);
-        __syncthreads();
-        // S[a][b] -= S[a][j] S[b][j] for j < b <= min(a, k - 1), a in (j, k + 2)
-        const int nb = k - 1 - j;            // columns b = j + 1 .. k - 1
-        const int na = k + 1 - j;            // rows    a = j + 1 .. k + 1
-        const long tot = (long)na * nb;
-        for (long e = tid; e < tot; e += LP_TPB) {
-            const int a = j + 1 + (int)(e / nb), b = j + 1 + (int)(e % nb);
-            if (b <= a) S[(long)a * ld + b] -= S[(long)a * ld + j] * S[(long)b * ld + j];
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    if (fail) {   // src/point_prediction.py:218-222
-        if (tid == 0) {
-            pred[p] = NAN;
-            err[p] = NAN;
-        }
+    const LpPoint X = lp_point(P, p);
+    lp_compact<false, 0>(P, X, idx);           // 1. neighbour list
+    lp_triangle(P, X, idx, S, ld, k);          // 2. local covariance, c row, z row, noise
+    lp_cz_rows(P, X, idx, S, ld, k);
+    lp_noise(P, idx, S, ld, k);
+    if (!lp_chol(S, ld, k, 2)) {               // 3. Cholesky, the two extra rows ride along
+        if (tid == 0) lp_write_nan(p, pred, err);
         return;
     }
-    // ---- 4. pred = v . y, var = c0 - v . v ----
-    double s1v = 0.0, s2v = 0.0;
-    for (int a = tid; a < k; a += LP_TPB) {
-        const double v = S[(long)k * ld + a], y = S[(long)(k + 1) * ld + a];
-        s1v += v * y;
-        s2v += v * v;
-    }
-    red[0][tid] = s1v;
-    red[1][tid] = s2v;
-    __syncthreads();
-    for (int s = LP_TPB / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[0][tid] += red[0][tid + s];
-            red[1][tid] += red[1][tid + s];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        pred[p] = red[0][0];
-        if (vv) vv[p] = red[1][0];   // the raw v . v (ck_loglik_vecchia: the unclamped variance is the caller's)
-        const double sd = sqrt(c0var - red[1][0]);
-        err[p] = (sd == sd) ? fmax(sd, 0.0) : 0.0;   // np.nanmax([std, 0.0]), point_prediction.py:217
-    }
+    double vy, v2;                             // 4. pred = v . y, var = c0 - v . v
+    lp_dots(S + (long)k * ld, S + (long)(k + 1) * ld, k, &vy, &v2);
+    if (tid == 0) lp_write(p, vy, v2, P.c0var, pred, err, vv);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -446,83 +489,42 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve(const CkMatern* __restri
 // 0.4 TFLOP/s at k = 1 359).
 #define LB_IB 32
 #define LB_PR 128   // panel rows per pass; LB_IB * (LB_PR + 1) <= 2 * LB_IB * 68 doubles of LDS
-__global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(const CkMatern* __restrict__ blk, int metric, int i_pred,
-                                                             int cv, double max_dist,
-                                                             const double* __restrict__ pc, long mpad,
-                                                             const double* __restrict__ sc,
-                                                             const double* __restrict__ z, CkLayout L,
-                                                             const int* __restrict__ counts,
+__global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(CkLocalProblem P, const int* __restrict__ counts,
                                                              const long long* __restrict__ slab_off,
-                                                             double* __restrict__ slab, double c0var,
+                                                             double* __restrict__ slab, long p_base, int k_hi,
                                                              double* __restrict__ pred, double* __restrict__ err,
-                                                             long p_base, LpTab T, const double* __restrict__ su,
-                                                             const double* __restrict__ pu, int k_hi, LpSearch R,
-                                                             const double* __restrict__ nz, double* __restrict__ vv) {
+                                                             double* __restrict__ vv) {
     __shared__ __attribute__((aligned(16))) double lbuf[2 * LB_IB * (64 + 4)];
     double (*At)[64 + 4] = reinterpret_cast<double (*)[64 + 4]>(lbuf);                 // At[c][r] = strip of the tile's rows
     double (*Bt)[64 + 4] = reinterpret_cast<double (*)[64 + 4]>(lbuf + LB_IB * (64 + 4));   // Bt[c][r] = ... columns
     double (*Pt)[LB_PR + 1] = reinterpret_cast<double (*)[LB_PR + 1]>(lbuf);           // panel rows (3a), same storage
     __shared__ double Ld[LB_IB][LB_IB + 1];   // diagonal block of the column panel
     __shared__ double rdiag[LB_IB], Ldiag[LB_IB];
-    __shared__ int wsum[LP_TPB / 64];
     __shared__ int fail;
-    __shared__ double red[2][LP_TPB];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const long p = p_base + blockIdx.x;
     const int k = counts[p];
     if (k <= LP_KL || k > k_hi) return;   // k_local_solve (also the empty neighbourhoods) / the tiled path
-    const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
-    const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
-    const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;        // chord vectors (table path)
-    const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
-    const LpReach Q = lp_reach(R, p, max_dist);
-    const int rp = lp_rank(R, p);
+    const LpPoint X = lp_point(P, p);
     double* S = slab + slab_off[p];   // (k + 2) x k, rows k and k + 1 carry c and z
     int* idx = reinterpret_cast<int*>(S + (long)(k + 2) * k);
     const long ld = k;
-    // ---- 1. neighbour list, in site order (block-wide ordered compaction) ----
     if (tid == 0) fail = 0;
-    int base = 0;
-    for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
-        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
-        const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp);
-        const unsigned long long bal = __ballot(f);
-        const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
-        if (lane == 0) wsum[wv] = __popcll(bal);
-        __syncthreads();
-        int off = base;
-        for (int w2 = 0; w2 < wv; ++w2) off += wsum[w2];
-        if (f) idx[off + below] = (int)g;
-        int tot = 0;
-        for (int w2 = 0; w2 < LP_TPB / 64; ++w2) tot += wsum[w2];
-        base += tot;
-        __syncthreads();
-    }
-    // ---- 2. local covariance (lower triangle), c row, z row ----
+    lp_compact<false, 0>(P, X, idx);   // 1. neighbour list
+    // ---- 2. local covariance (lower triangle), c row, z row, noise ----
     for (int a = 0; a < k; ++a) {   // row by row: coalesced writes, no sqrt to invert the triangular index
         const long ga = idx[a];
-        const int pa = ga >= L.n0p;
-        const double a0 = s0[ga], a1 = s1[ga], a2 = s2[ga], au0 = u0[ga], au1 = u1[ga], au2 = u2[ga];
+        const int pa = ga >= P.L.n0p;
+        const double a0 = X.s0[ga], a1 = X.s1[ga], a2 = X.s2[ga], au0 = X.u0[ga], au1 = X.u1[ga], au2 = X.u2[ga];
         for (int b = tid; b <= a; b += LP_TPB) {
             const long gb = idx[b];
-            const int pb = gb >= L.n0p;
-            S[(long)a * ld + b] = lp_cov(blk, T, pa + pb, pa == pb, metric, a0, a1, a2, au0, au1, au2, s0[gb], s1[gb], s2[gb],
-                                         u0[gb], u1[gb], u2[gb]);
+            const int pb = gb >= P.L.n0p;
+            S[(long)a * ld + b] = lp_cov(P, pa + pb, pa == pb, a0, a1, a2, au0, au1, au2, X.s0[gb], X.s1[gb], X.s2[gb], X.u0[gb],
+                                         X.u1[gb], X.u2[gb]);
         }
     }
-    for (int a = tid; a < k; a += LP_TPB) {
-        const long ga = idx[a];
-        const int pa = ga >= L.n0p;
-        S[(long)k * ld + a] = lp_cov(blk, T, i_pred + pa, pa == i_pred, metric, p0, p1, p2, q0, q1, q2, s0[ga], s1[ga],
-                                     s2[ga], u0[ga], u1[ga], u2[ga]);   // point_prediction.py:115-125
-        S[(long)(k + 1) * ld + a] = z[ga];
-    }
-    __syncthreads();
-    if (nz) {   // measurement-error variances (ck_set_noise): the neighbour's s d on the true diagonal
-        for (int a = tid; a < k; a += LP_TPB) S[(long)a * ld + a] += nz[idx[a]];
-        __syncthreads();
-    }
+    lp_cz_rows(P, X, idx, S, ld, k);
+    lp_noise(P, idx, S, ld, k);
     // ---- 3. blocked Cholesky; rows k, k + 1 ride along (forward substitution) ----
     const int ty = tid >> 4, tx = tid & 15;
     bool bad = false;
@@ -631,75 +633,35 @@ __global__ __launch_bounds__(LP_TPB, 3) void k_local_solve_big(const CkMatern* _
         }
     }
     __syncthreads();
-    if (fail) {   // src/point_prediction.py:218-222
-        if (tid == 0) {
-            pred[p] = NAN;
-            err[p] = NAN;
-        }
+    if (fail) {
+        if (tid == 0) lp_write_nan(p, pred, err);
         return;
     }
-    // ---- 4. pred = v . y, var = c0 - v . v ----
-    double s1v = 0.0, s2v = 0.0;
-    for (int a = tid; a < k; a += LP_TPB) {
-        const double v = S[(long)k * ld + a], y = S[(long)(k + 1) * ld + a];
-        s1v += v * y;
-        s2v += v * v;
-    }
-    red[0][tid] = s1v;
-    red[1][tid] = s2v;
-    __syncthreads();
-    for (int s = LP_TPB / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[0][tid] += red[0][tid + s];
-            red[1][tid] += red[1][tid + s];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        pred[p] = red[0][0];
-        if (vv) vv[p] = red[1][0];   // the raw v . v (ck_loglik_vecchia: the unclamped variance is the caller's)
-        const double sd = sqrt(c0var - red[1][0]);
-        err[p] = (sd == sd) ? fmax(sd, 0.0) : 0.0;   // np.nanmax([std, 0.0]), point_prediction.py:217
-    }
+    double vy, v2;   // ---- 4. pred = v . y, var = c0 - v . v ----
+    lp_dots(S + (long)k * ld, S + (long)(k + 1) * ld, k, &vy, &v2);
+    if (tid == 0) lp_write(p, vy, v2, P.c0var, pred, err, vv);
 }
 
-void ck_launch_local_count(hipStream_t s, int metric, int i_pred, int cv, double max_dist, const double* pc,
-                           int64_t m, int64_t mpad, const double* sc, CkLayout L, int* counts, const double* cb,
-                           double cmax, const double* pu, CkLocalCap cap) {
+void ck_launch_local_count(hipStream_t s, const CkLocalProblem& P, int64_t m, int* counts) {
     if (m <= 0) return;
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, nullptr, nullptr, cap.rs, cap.rp};
-    k_local_count<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(metric, i_pred, cv, max_dist, pc, mpad, sc, L, counts, R, pu);
+    k_local_count<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(P, counts);
 }
 
 int ck_local_select_capacity() { return LS_CAP; }
 
-void ck_launch_local_select(hipStream_t s, int metric, int i_pred, int cv, double max_dist, const double* pc, int64_t m,
-                            int64_t mpad, const double* sc, CkLayout L, const double* cb, double cmax, const double* pu,
-                            int nmax0, int nmax1, int key_cap, int* counts, int* sel, double* rq, double* cp, CkLocalCap cap) {
+void ck_launch_local_select(hipStream_t s, const CkLocalProblem& P, int64_t m, int nmax0, int nmax1, int key_cap, int* counts,
+                            int* sel, double* rq, double* cp) {
     if (m <= 0) return;
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, nullptr, nullptr, cap.rs, cap.rp};
     key_cap = key_cap < 1 ? 1 : (key_cap > LS_CAP ? LS_CAP : key_cap);   // never beyond the LDS lists
-    k_local_select<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(metric, i_pred, cv, max_dist, pc, mpad, sc, L, R, pu, nmax0, nmax1,
-                                                              key_cap, counts, sel, rq, cp);
+    k_local_select<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(P, nmax0, nmax1, key_cap, counts, sel, rq, cp);
 }
 
-// points [p_base, p_base + m): slab_off is relative to `slab` within this batch (ck_predict_local)
-void ck_launch_local_solve(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
-                           const double* pc, int64_t p_base, int64_t m, int64_t mpad, const double* sc, const double* z,
-                           CkLayout L, const int* counts, const long long* slab_off, double* slab, double c0var,
-                           double* pred, double* err, const CkTable* tabs, const double* const* coefs, int use_tab,
-                           const double* su, const double* pu, int k_hi, const double* cb, double cmax, const double* nz, CkLocalCap cap,
-                           double* vv) {
+void ck_launch_local_solve(hipStream_t s, const CkLocalProblem& P, int64_t p_base, int64_t m, const int* counts,
+                           const long long* slab_off, double* slab, int k_hi, double* pred, double* err, double* vv) {
     if (m <= 0) return;
-    const LpTab T{tabs, coefs, use_tab};
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp, cap.rs, cap.rp};
-    k_local_solve<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L,
-                                                             counts, slab_off, slab, c0var, pred, err, p_base, T, su, pu, R, k_hi,
-                                                             nz, vv);
+    k_local_solve<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(P, counts, p_base, k_hi, pred, err, vv);
     if (slab && k_hi > LP_KL)   // some neighbourhood is larger than the LDS limit
-        k_local_solve_big<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z,
-                                                                     L, counts, slab_off, slab, c0var, pred, err,
-                                                                     p_base, T, su, pu, k_hi, R, nz, vv);
+        k_local_solve_big<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(P, counts, slab_off, slab, p_base, k_hi, pred, err, vv);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -726,49 +688,17 @@ __device__ __noinline__ double lp_exact_pair(const CkMatern* m, int metric, int 
 #define LT_WL 1024   // deferred exact pairs per system and block (LDS list; beyond that they are evaluated in place)
 #define LT_AC 256
 #define LT_TPB 512   // 8 waves: with two workgroups per CU (LDS) four waves per SIMD hide the table-read latency
-__global__ __launch_bounds__(LP_TPB) void k_local_search_t(const CkMatern* __restrict__ blk, int metric, int i_pred, int cv,
-                                                            double max_dist, const double* __restrict__ pc, long mpad,
-                                                            const double* __restrict__ sc, const double* __restrict__ z,
-                                                            CkLayout L, const CkLocalSys* __restrict__ sys,
-                                                            double* __restrict__ slab, LpTab T,
-                                                            const double* __restrict__ su,
-                                                            const double* __restrict__ pu, LpSearch R,
-                                                            int* __restrict__ k0out) {
-    __shared__ int wsum[LP_TPB / 64], wsum0[LP_TPB / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+__global__ __launch_bounds__(LP_TPB) void k_local_search_t(CkLocalProblem P, const CkLocalSys* __restrict__ sys,
+                                                            double* __restrict__ slab, int* __restrict__ k0out) {
+    const int tid = threadIdx.x;
     const CkLocalSys q = sys[blockIdx.x];
-    const long p = q.p;
     const int k = q.k, kq = q.kq;
     const long ld = q.ld;
-    const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
-    const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
-    const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;
-    const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
-    const LpReach Q = lp_reach(R, p, max_dist);
-    const int rp = lp_rank(R, p);
+    const LpPoint X = lp_point(P, q.p);
     double* S = slab + q.off;
     int* idx = reinterpret_cast<int*>(S + (long)CK_LT_ROWS(kq) * ld + CK_LT_NINV * 64 * 64);
-    int base = 0, k0 = 0;   // k0: neighbours of process 0
-    for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {   // ordered compaction, as in k_local_solve
-        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
-        const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp);
-        const unsigned long long bal = __ballot(f), bal0 = __ballot(f && g < L.n0p);
-        const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
-        if (lane == 0) {
-            wsum[wv] = __popcll(bal);
-            wsum0[wv] = __popcll(bal0);
-        }
-        __syncthreads();
-        int off = base;
-        for (int w2 = 0; w2 < wv; ++w2) off += wsum[w2];
-        if (f) idx[off + below] = (int)g;
-        for (int w2 = 0; w2 < LP_TPB / 64; ++w2) {
-            base += wsum[w2];
-            k0 += wsum0[w2];
-        }
-        __syncthreads();
-    }
+    int k0;   // neighbours of process 0
+    lp_compact<true, 0>(P, X, idx, &k0);
     if (tid == 0) k0out[blockIdx.x] = k0;
     // zeros up to the end of each row's 4-column diagonal block (the 64 x 64 factorisation loads whole 4 x 4
     // register blocks); rows [k, kq - 2): identity padding
@@ -781,15 +711,19 @@ __global__ __launch_bounds__(LP_TPB) void k_local_search_t(const CkMatern* __res
         double cv0 = 0.0, zv = 0.0;
         if (a < k) {
             const long ga = idx[a];
-            const int pa = ga >= L.n0p;
-            cv0 = lp_cov(blk, T, i_pred + pa, pa == i_pred, metric, p0, p1, p2, q0, q1, q2, s0[ga], s1[ga], s2[ga], u0[ga],
-                         u1[ga], u2[ga]);   // point_prediction.py:115-125
-            zv = z[ga];
+            cv0 = lp_c_entry(P, X, ga);
+            zv = P.z[ga];
         }
         S[(long)(kq - 2) * ld + a] = a == kq - 2 ? CK_LT_BIG : cv0;
         S[(long)(kq - 1) * ld + a] = a == kq - 1 ? CK_LT_BIG : zv;
     }
 }
+
+struct LpTab {   // the tables as k_local_assemble_t takes them (its other arguments: the descriptor's members one by one)
+    const CkTable* tabs;             // [3]
+    const double* const* coefs;      // [3]
+    int use;
+};
 
 __global__ __launch_bounds__(LT_TPB, 4) void k_local_assemble_t(const CkMatern* __restrict__ blk, int metric, int reg,
                                                                  const double* __restrict__ sc, CkLayout L,
@@ -930,56 +864,28 @@ __global__ __launch_bounds__(LP_TPB) void k_local_reduce_t(const CkLocalSys* __r
                                                             const long long* __restrict__ info, double c0var,
                                                             double* __restrict__ pred, double* __restrict__ err,
                                                             double* __restrict__ vv) {
-    __shared__ double red[2][LP_TPB];
     const int tid = threadIdx.x;
     const CkLocalSys q = sys[blockIdx.x];
-    if (info[blockIdx.x] != 0) {   // src/point_prediction.py:218-222
-        if (tid == 0) {
-            pred[q.p] = NAN;
-            err[q.p] = NAN;
-        }
+    if (info[blockIdx.x] != 0) {
+        if (tid == 0) lp_write_nan(q.p, pred, err);
         return;
     }
     const double* v = slab + q.off + (long)(q.kq - 2) * q.ld;
-    const double* y = v + q.ld;
-    double s1v = 0.0, s2v = 0.0;
-    for (int a = tid; a < q.k; a += LP_TPB) {
-        s1v += v[a] * y[a];
-        s2v += v[a] * v[a];
-    }
-    red[0][tid] = s1v;
-    red[1][tid] = s2v;
-    __syncthreads();
-    for (int s = LP_TPB / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[0][tid] += red[0][tid + s];
-            red[1][tid] += red[1][tid + s];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        pred[q.p] = red[0][0];
-        if (vv) vv[q.p] = red[1][0];
-        const double sd = sqrt(c0var - red[1][0]);
-        err[q.p] = (sd == sd) ? fmax(sd, 0.0) : 0.0;   // np.nanmax([std, 0.0]), point_prediction.py:217
-    }
+    double vy, v2;
+    lp_dots(v, v + q.ld, q.k, &vy, &v2);
+    if (tid == 0) lp_write(q.p, vy, v2, c0var, pred, err, vv);
 }
 
-void ck_launch_local_assemble_t(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
-                                const double* pc, int64_t mpad, const double* sc, const double* z, CkLayout L,
-                                const CkLocalSys* sys, int n_sys, double* slab, const CkTable* tabs,
-                                const double* const* coefs, int use_tab, const double* su, const double* pu,
-                                const double* cb, double cmax, int* k0buf, const double* nz, CkLocalCap cap) {
+void ck_launch_local_assemble_t(hipStream_t s, const CkLocalProblem& P, const CkLocalSys* sys, int n_sys, double* slab,
+                                int* k0buf) {
     if (n_sys <= 0) return;
-    const LpTab T{tabs, coefs, use_tab};
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp, cap.rs, cap.rp};
-    k_local_search_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L, sys,
-                                                                    slab, T, su, pu, R, k0buf);
-    const int nreg = L.nend > L.n0p ? 3 : 1;               // a second process?
+    k_local_search_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(P, sys, slab, k0buf);
+    const LpTab T{P.tabs, P.coefs, P.use_tab};
+    const int nreg = P.L.nend > P.L.n0p ? 3 : 1;           // a second process?
     const int grid = n_sys < 512 ? n_sys : 512;            // two workgroups per CU; they walk over the systems
     for (int reg = 0; reg < nreg; ++reg)
-        k_local_assemble_t<<<dim3((unsigned)grid), dim3(LT_TPB), 0, s>>>(blk, metric, reg, sc, L, sys, n_sys, slab, T, su, k0buf,
-                                                                         nz);
+        k_local_assemble_t<<<dim3((unsigned)grid), dim3(LT_TPB), 0, s>>>(P.blk, P.metric, reg, P.sc, P.L, sys, n_sys, slab, T, P.su,
+                                                                         k0buf, P.nz);
 }
 
 void ck_launch_local_reduce_t(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab,
@@ -1046,19 +952,12 @@ __device__ __forceinline__ void lu_finish(double* E, CkLocalTrend Tr, int i_pred
 }
 
 // LDS class: k_local_solve with k + 2 + p rows (c, z, then the trend rows); dynamic LDS sized by p
-__global__ __launch_bounds__(LP_TPB) void k_local_solve_u(const CkMatern* __restrict__ blk, int metric, int i_pred, int cv,
-                                                           double max_dist, const double* __restrict__ pc, long mpad,
-                                                           const double* __restrict__ sc, const double* __restrict__ z,
-                                                           CkLayout L, const int* __restrict__ counts, double c0var,
-                                                           double* __restrict__ pred, double* __restrict__ err, LpTab T,
-                                                           const double* __restrict__ su, const double* __restrict__ pu,
-                                                           LpSearch R, int k_hi, CkLocalTrend Tr, double* __restrict__ beta,
-                                                           int* __restrict__ status, const double* __restrict__ nz) {
+__global__ __launch_bounds__(LP_TPB) void k_local_solve_u(CkLocalProblem P, const int* __restrict__ counts, int k_hi,
+                                                           CkLocalTrend Tr, double* __restrict__ pred, double* __restrict__ err,
+                                                           double* __restrict__ beta, int* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) double lu_lds[];   // (LP_KL + nx) x LP_KL matrix | LU_EXTRA(p)
-    __shared__ int lidx[LP_KL];
-    __shared__ int wsum[LP_TPB / 64], wsum0[LP_TPB / 64];
-    __shared__ int fail;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ int idx[LP_KL];
+    const int tid = threadIdx.x;
     const int np = Tr.p0 + Tr.p1, nx = np + 2;
     const long p = blockIdx.x;
     const int k = counts[p];
@@ -1067,90 +966,20 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve_u(const CkMatern* __rest
         return;
     }
     if (k > LP_KL || k > k_hi) return;   // the tiled path
-    const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
-    const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
-    const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;
-    const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
-    const LpReach Q = lp_reach(R, p, max_dist);
-    const int rp = lp_rank(R, p);
     double* S = lu_lds;
     double* E = lu_lds + (LP_KL + nx) * LP_KL;
-    int* idx = lidx;
     const long ld = LP_KL;
-    // ---- 1. neighbour list, in site order; k0 = neighbours of process 0 ----
-    if (tid == 0) fail = 0;
-    int base = 0, k0 = 0;
-    for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
-        if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
-        const long g = g0 + tid;
-        const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp);
-        const unsigned long long bal = __ballot(f), bal0 = __ballot(f && g < L.n0p);
-        const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
-        if (lane == 0) {
-            wsum[wv] = __popcll(bal);
-            wsum0[wv] = __popcll(bal0);
-        }
-        __syncthreads();
-        int off = base;
-        for (int w2 = 0; w2 < wv; ++w2) off += wsum[w2];
-        if (f) idx[off + below] = (int)g;
-        for (int w2 = 0; w2 < LP_TPB / 64; ++w2) {
-            base += wsum[w2];
-            k0 += wsum0[w2];
-        }
-        __syncthreads();
-    }
-    // ---- 2. local covariance (lower triangle), c row, z row, trend rows ----
-    const long npair = (long)k * (k + 1) / 2;
-    for (long e = tid; e < npair; e += LP_TPB) {
-        long a = (long)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
-        while (a * (a + 1) / 2 > e) --a;
-        while ((a + 1) * (a + 2) / 2 <= e) ++a;
-        const long b = e - a * (a + 1) / 2;
-        const long ga = idx[a], gb = idx[b];
-        const int pa = ga >= L.n0p, pb = gb >= L.n0p;
-        S[a * ld + b] = lp_cov(blk, T, pa + pb, pa == pb, metric, s0[ga], s1[ga], s2[ga], u0[ga], u1[ga], u2[ga], s0[gb],
-                               s1[gb], s2[gb], u0[gb], u1[gb], u2[gb]);
-    }
-    for (int a = tid; a < k; a += LP_TPB) {
-        const long ga = idx[a];
-        const int pa = ga >= L.n0p;
-        S[(long)k * ld + a] = lp_cov(blk, T, i_pred + pa, pa == i_pred, metric, p0, p1, p2, q0, q1, q2, s0[ga], s1[ga],
-                                     s2[ga], u0[ga], u1[ga], u2[ga]);
-        S[(long)(k + 1) * ld + a] = z[ga];
-    }
+    const LpPoint X = lp_point(P, p);
+    int k0;                                    // 1. neighbour list; k0 = neighbours of process 0
+    lp_compact<true, 0>(P, X, idx, &k0);
+    lp_triangle(P, X, idx, S, ld, k);          // 2. local covariance, c row, z row, trend rows, noise
+    lp_cz_rows(P, X, idx, S, ld, k);
     for (int e = tid; e < np * k; e += LP_TPB) {
         const int j = e / k, a = e - j * k;
-        S[(long)(k + 2 + j) * ld + a] = Tr.X[(long)j * L.npad + idx[a]];
+        S[(long)(k + 2 + j) * ld + a] = Tr.X[(long)j * P.L.npad + idx[a]];
     }
-    __syncthreads();
-    if (nz) {   // measurement-error variances (ck_set_noise): the neighbour's s d on the true diagonal
-        for (int a = tid; a < k; a += LP_TPB) S[(long)a * ld + a] += nz[idx[a]];
-        __syncthreads();
-    }
-    // ---- 3. Cholesky of the k x k block, the nx extra rows ride along (forward substitution) ----
-    for (int j = 0; j < k; ++j) {
-        const double piv = S[(long)j * ld + j];
-        if (!(piv > 0.0)) {
-            if (tid == 0) fail = 1;
-            break;   // uniform: every thread reads the same pivot
-        }
-        const double rd = 1.0 / sqrt(piv);
-        __syncthreads();
-        for (int a = j + 1 + tid; a < k + nx; a += LP_TPB) S[(long)a * ld + j] *= rd;
-        if (tid == 0) S[(long)j * ld + j] = sqrt(piv);
-        __syncthreads();
-        const int nb = k - 1 - j;            // columns b = j + 1 .. k - 1
-        const int na = k + nx - 1 - j;       // rows    a = j + 1 .. k + nx - 1
-        const long tot = (long)na * nb;
-        for (long e = tid; e < tot; e += LP_TPB) {
-            const int a = j + 1 + (int)(e / nb), b = j + 1 + (int)(e % nb);
-            if (b <= a) S[(long)a * ld + b] -= S[(long)a * ld + j] * S[(long)b * ld + j];
-        }
-        __syncthreads();
-    }
-    __syncthreads();
-    if (fail) {
+    lp_noise(P, idx, S, ld, k);
+    if (!lp_chol(S, ld, k, nx)) {              // 3. Cholesky, the nx extra rows ride along
         if (tid == 0) lu_fill_nan(p, np, pred, err, beta, status, CK_LU_NOT_PD);
         return;
     }
@@ -1164,21 +993,15 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve_u(const CkMatern* __rest
         E[r * nx + c] = acc;
     }
     __syncthreads();
-    if (tid == 0) lu_finish(E, Tr, i_pred, k0, k - k0, p, c0var, pred, err, beta, status);
+    if (tid == 0) lu_finish(E, Tr, P.i_pred, k0, k - k0, p, P.c0var, pred, err, beta, status);
 }
 
-void ck_launch_local_solve_u(hipStream_t s, const CkMatern* blk, int metric, int i_pred, int cv, double max_dist,
-                             const double* pc, int64_t m, int64_t mpad, const double* sc, const double* z, CkLayout L,
-                             const int* counts, double c0var, double* pred, double* err, const CkTable* tabs,
-                             const double* const* coefs, int use_tab, const double* su, const double* pu, int k_hi,
-                             const double* cb, double cmax, CkLocalTrend Tr, double* beta, int* status, const double* nz, CkLocalCap cap) {
+void ck_launch_local_solve_u(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, int k_hi, CkLocalTrend Tr,
+                             double* pred, double* err, double* beta, int* status) {
     if (m <= 0) return;
-    const LpTab T{tabs, coefs, use_tab};
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp, cap.rs, cap.rp};
     const int np = Tr.p0 + Tr.p1;
     const size_t lds = (size_t)((LP_KL + 2 + np) * LP_KL + LU_EXTRA(np)) * sizeof(double);   // 34.9 KB (p = 2) .. 47.2 KB (p = 16)
-    k_local_solve_u<<<dim3((unsigned)m), dim3(LP_TPB), lds, s>>>(blk, metric, i_pred, cv, max_dist, pc, mpad, sc, z, L, counts,
-                                                                 c0var, pred, err, T, su, pu, R, k_hi, Tr, beta, status, nz);
+    k_local_solve_u<<<dim3((unsigned)m), dim3(LP_TPB), lds, s>>>(P, counts, k_hi, Tr, pred, err, beta, status);
 }
 
 // Tiled class: behind k_local_search_t (which has written identity rows up to kq - 2) the p rows [kq - 2 - p, kq - 2)
@@ -1258,56 +1081,11 @@ void ck_launch_local_reduce_ut(hipStream_t s, const CkLocalSys* sys, int n_sys, 
 // No atomics, no dependence on the launch: repeated calls give the same bits.
 #include "ck_vecchia.h"
 
-__global__ __launch_bounds__(LP_TPB) void k_vecchia_terms(long n, const double* __restrict__ z, const double* __restrict__ mu,
-                                                           const double* __restrict__ vv, const double* __restrict__ prior,
-                                                           const double* __restrict__ noise, const int* __restrict__ cnt2,
-                                                           double* __restrict__ mean, double* __restrict__ var,
-                                                           double* __restrict__ part, long long* __restrict__ bad) {
+// the tree of both kernels: (lv, qd) summed, b = the smallest non-zero; thread 0 writes out2[0], out2[1], *outb
+__device__ __forceinline__ void vt_tree(double lv, double qd, long long b, double* out2, long long* outb) {
     __shared__ double red[2][LP_TPB];
     __shared__ long long first[LP_TPB];
     const int tid = threadIdx.x;
-    const long t = (long)blockIdx.x * LP_TPB + tid;
-    double lv = 0.0, qd = 0.0;
-    long long b = 0;
-    if (t < n) {
-        double m, s2;
-        if (ck_vecchia_term(z[t], mu[t], vv[t], prior[t], noise ? noise[t] : 0.0, cnt2[2 * t] + cnt2[2 * t + 1], &m, &s2, &lv, &qd))
-            b = t + 1;
-        mean[t] = m;
-        var[t] = s2;
-    }
-    red[0][tid] = lv;
-    red[1][tid] = qd;
-    first[tid] = b;
-    __syncthreads();
-    for (int s = LP_TPB / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[0][tid] += red[0][tid + s];
-            red[1][tid] += red[1][tid + s];
-            const long long o = first[tid + s];
-            if (o != 0 && (first[tid] == 0 || o < first[tid])) first[tid] = o;
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        part[2 * blockIdx.x] = red[0][0];
-        part[2 * blockIdx.x + 1] = red[1][0];
-        bad[blockIdx.x] = first[0];
-    }
-}
-
-__global__ __launch_bounds__(LP_TPB) void k_vecchia_sum(long nblk, const double* __restrict__ part, const long long* __restrict__ bad,
-                                                         double* __restrict__ out2, long long* __restrict__ info) {
-    __shared__ double red[2][LP_TPB];
-    __shared__ long long first[LP_TPB];
-    const int tid = threadIdx.x;
-    double lv = 0.0, qd = 0.0;
-    long long b = 0;
-    for (long e = tid; e < nblk; e += LP_TPB) {
-        lv += part[2 * e];
-        qd += part[2 * e + 1];
-        if (b == 0) b = bad[e];   // the blocks come in ascending order of their data
-    }
     red[0][tid] = lv;
     red[1][tid] = qd;
     first[tid] = b;
@@ -1324,8 +1102,38 @@ __global__ __launch_bounds__(LP_TPB) void k_vecchia_sum(long nblk, const double*
     if (tid == 0) {
         out2[0] = red[0][0];
         out2[1] = red[1][0];
-        *info = first[0];
+        *outb = first[0];
     }
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_terms(long n, const double* __restrict__ z, const double* __restrict__ mu,
+                                                           const double* __restrict__ vv, const double* __restrict__ prior,
+                                                           const double* __restrict__ noise, const int* __restrict__ cnt2,
+                                                           double* __restrict__ mean, double* __restrict__ var,
+                                                           double* __restrict__ part, long long* __restrict__ bad) {
+    const long t = (long)blockIdx.x * LP_TPB + threadIdx.x;
+    double lv = 0.0, qd = 0.0;
+    long long b = 0;
+    if (t < n) {
+        double m, s2;
+        if (ck_vecchia_term(z[t], mu[t], vv[t], prior[t], noise ? noise[t] : 0.0, cnt2[2 * t] + cnt2[2 * t + 1], &m, &s2, &lv, &qd))
+            b = t + 1;
+        mean[t] = m;
+        var[t] = s2;
+    }
+    vt_tree(lv, qd, b, part + 2 * blockIdx.x, bad + blockIdx.x);
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_sum(long nblk, const double* __restrict__ part, const long long* __restrict__ bad,
+                                                         double* __restrict__ out2, long long* __restrict__ info) {
+    double lv = 0.0, qd = 0.0;
+    long long b = 0;
+    for (long e = threadIdx.x; e < nblk; e += LP_TPB) {
+        lv += part[2 * e];
+        qd += part[2 * e + 1];
+        if (b == 0) b = bad[e];   // the blocks come in ascending order of their data
+    }
+    vt_tree(lv, qd, b, out2, info);
 }
 
 void ck_launch_vecchia_terms(hipStream_t s, int64_t n, const double* z, const double* mu, const double* vv, const double* prior,
@@ -1340,8 +1148,9 @@ void ck_launch_vecchia_terms(hipStream_t s, int64_t n, const double* z, const do
 // ---------------------------------------------------------------------------------------
 // the gradient of the Vecchia likelihood (ck_loglik_vecchia_grad; ck_vecchia_grad.h has the formula and the pair rule)
 // ---------------------------------------------------------------------------------------
-// k_vecchia_grad: one workgroup per datum, sets of at most LP_KL data.  Steps 1 - 4 are k_local_solve's, expression by
-// expression (mu and v . v come out with the same bits); then
+// k_vecchia_grad: one workgroup per datum, sets of at most LP_KL data.  Steps 1 - 4 are k_local_solve's: the same
+// calls of the same device functions with the same arguments, so mu and v . v come out with the same bits (the one difference:
+// the neighbour list is written under the capacity guard of lp_compact, which never drops an entry here); then
 //   5. back substitution in place on rows k and k + 1: v -> w = L^-T v, y -> alpha = L^-T y.  ONE wave, lane a holding x_a of
 //      both rows: step j broadcasts x_j / L_jj from lane j and every lane a < j subtracts L[j][a] x_j -- row j of L is
 //      contiguous in LDS, and with k <= 64 the whole vector lives in one wave, so the k dependent steps need no barrier
@@ -1350,20 +1159,13 @@ void ck_launch_vecchia_terms(hipStream_t s, int64_t n, const double* z, const do
 //      ck_vecchia_pair per pair with the exact evaluator's derivatives; 13 sums per thread, reduced by wave shuffles and a
 //      fixed four-wave order (k_loglik_grad's), one 13-vector per datum.
 // An empty set is the one-entry system (b = 1, a = 0): it runs step 6 alone.  A system that is not positive definite or a
-// variance that is not > 0: NaN in the live slots.  k_vecchia_grad_part / _sum: the column sums of the scores by the fixed
-// tree of k_vecchia_terms / k_vecchia_sum.  No atomics: repeated calls give the same bits.
-__global__ __launch_bounds__(LP_TPB) void k_vecchia_grad(const CkMatern* __restrict__ blk, int metric, int i_pred, double max_dist,
-                                                          const double* __restrict__ pc, long mpad, const double* __restrict__ sc,
-                                                          const double* __restrict__ z, CkLayout L, const int* __restrict__ counts,
-                                                          double c0var, double* __restrict__ pred, double* __restrict__ err,
-                                                          LpTab T, const double* __restrict__ su, const double* __restrict__ pu,
-                                                          LpSearch R, const double* __restrict__ nz, double* __restrict__ vv,
-                                                          CkVecchiaGradArgs A) {
-    __shared__ double lS[(LP_KL + 2) * LP_KL];
-    __shared__ int lidx[LP_KL];
-    __shared__ int wsum[LP_TPB / 64];
-    __shared__ int fail;
-    __shared__ double red[2][LP_TPB];
+// variance that is not > 0: NaN in the live slots.  k_vecchia_grad_part / _sum: the column sums of the scores by vg_tree,
+// the 13-column form of the terms' tree and partial-sum order.  No atomics: repeated calls give the same bits.
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_grad(CkLocalProblem P, const int* __restrict__ counts,
+                                                          double* __restrict__ pred, double* __restrict__ err,
+                                                          double* __restrict__ vv, CkVecchiaGradArgs A) {
+    __shared__ double S[(LP_KL + 2) * LP_KL];
+    __shared__ int idx[LP_KL];
     __shared__ double sred[LP_TPB / 64][CK_VG_NPAR];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const long p = blockIdx.x;
@@ -1371,124 +1173,31 @@ __global__ __launch_bounds__(LP_TPB) void k_vecchia_grad(const CkMatern* __restr
     if (k > LP_KL) return;   // refused by the host before any launch
     const CkVecchiaModel& V = A.V;
     double* score = A.score + p * CK_VG_NPAR;
-    const int cv = 0;
-    const double p0 = pc[p], p1 = pc[mpad + p], p2 = pc[2 * mpad + p];
-    const double *s0 = sc, *s1 = sc + L.npad, *s2 = sc + 2 * L.npad;
-    const double *u0 = su, *u1 = su + L.npad, *u2 = su + 2 * L.npad;        // chord vectors (table path)
-    const double q0 = pu[p], q1 = pu[mpad + p], q2 = pu[2 * mpad + p];
-    const LpReach Q = lp_reach(R, p, max_dist);
-    const int rp = lp_rank(R, p);
-    double* S = lS;
-    int* idx = lidx;
     const long ld = LP_KL;
-    if (tid == 0) fail = 0;
-    double mu = 0.0, vvs = 0.0;
+    const LpPoint X = lp_point(P, p);
+    bool ok = true;
     if (k > 0) {
-        // ---- 1. neighbour list, in site order (block-wide ordered compaction) ----
-        int base = 0;
-        for (long g0 = 0; g0 < L.nend; g0 += LP_TPB) {
-            if (lp_chunk_far(R, Q, g0 / LP_TPB, q0, q1, q2)) continue;   // uniform
-            const long g = g0 + tid;
-            const bool f = g < L.nend && lp_is_neighbour(metric, cv, i_pred, Q, L, g, p0, p1, p2, s0, s1, s2, R.rs, rp);
-            const unsigned long long bal = __ballot(f);
-            const int below = __popcll(bal & ((1ULL << lane) - 1ULL));
-            if (lane == 0) wsum[wv] = __popcll(bal);
-            __syncthreads();
-            int off = base;
-            for (int w2 = 0; w2 < wv; ++w2) off += wsum[w2];
-            if (f && off + below < LP_KL) idx[off + below] = (int)g;   // (the count is the select pass's: never beyond k)
-            int tot = 0;
-            for (int w2 = 0; w2 < LP_TPB / 64; ++w2) tot += wsum[w2];
-            base += tot;
-            __syncthreads();
-        }
-        // ---- 2. local covariance (lower triangle), c row, z row ----
-        const long npair = (long)k * (k + 1) / 2;
-        for (long e = tid; e < npair; e += LP_TPB) {
-            long a = (long)((sqrt(8.0 * (double)e + 1.0) - 1.0) * 0.5);
-            while (a * (a + 1) / 2 > e) --a;
-            while ((a + 1) * (a + 2) / 2 <= e) ++a;
-            const long b = e - a * (a + 1) / 2;
-            const long ga = idx[a], gb = idx[b];
-            const int pa = ga >= L.n0p, pb = gb >= L.n0p;
-            S[a * ld + b] = lp_cov(blk, T, pa + pb, pa == pb, metric, s0[ga], s1[ga], s2[ga], u0[ga], u1[ga], u2[ga], s0[gb],
-                                   s1[gb], s2[gb], u0[gb], u1[gb], u2[gb]);
-        }
-        for (int a = tid; a < k; a += LP_TPB) {
-            const long ga = idx[a];
-            const int pa = ga >= L.n0p;
-            S[(long)k * ld + a] = lp_cov(blk, T, i_pred + pa, pa == i_pred, metric, p0, p1, p2, q0, q1, q2, s0[ga], s1[ga],
-                                         s2[ga], u0[ga], u1[ga], u2[ga]);
-            S[(long)(k + 1) * ld + a] = z[ga];
-        }
-        __syncthreads();
-        if (nz) {   // measurement-error variances (ck_set_noise): the neighbour's s d on the true diagonal
-            for (int a = tid; a < k; a += LP_TPB) S[(long)a * ld + a] += nz[idx[a]];
-            __syncthreads();
-        }
-        // ---- 3. Cholesky of the k x k block, the two extra rows ride along (forward substitution) ----
-        for (int j = 0; j < k; ++j) {
-            const double piv = S[(long)j * ld + j];
-            if (!(piv > 0.0)) {
-                if (tid == 0) fail = 1;
-                break;   // uniform: every thread reads the same pivot
-            }
-            const double rd = 1.0 / sqrt(piv);
-            __syncthreads();
-            for (int a = j + 1 + tid; a < k + 2; a += LP_TPB) S[(long)a * ld + j] *= rd;
-            if (tid == 0) S[(long)j * ld + j] = sqrt(piv);
-            __syncthreads();
-            const int nb = k - 1 - j;            // columns b = j + 1 .. k - 1
-            const int na = k + 1 - j;            // rows    a = j + 1 .. k + 1
-            const long tot = (long)na * nb;
-            for (long e = tid; e < tot; e += LP_TPB) {
-                const int a = j + 1 + (int)(e / nb), b = j + 1 + (int)(e % nb);
-                if (b <= a) S[(long)a * ld + b] -= S[(long)a * ld + j] * S[(long)b * ld + j];
-            }
-            __syncthreads();
-        }
+        lp_compact<false, LP_KL>(P, X, idx);       // 1. neighbour list (the count is the select pass's: never beyond k)
+        lp_triangle(P, X, idx, S, ld, k);          // 2. local covariance, c row, z row, noise
+        lp_cz_rows(P, X, idx, S, ld, k);
+        lp_noise(P, idx, S, ld, k);
+        ok = lp_chol(S, ld, k, 2);                 // 3. Cholesky, the two extra rows ride along
     }
-    __syncthreads();
-    if (fail || k == 0) {   // no solve: k_local_solve's outputs for these points
-        if (tid == 0) {
-            pred[p] = NAN;
-            err[p] = NAN;
-        }
-        if (fail) {
+    double mu = 0.0, vvs = 0.0;
+    if (!ok || k == 0) {   // no solve: k_local_solve's outputs for these points
+        if (tid == 0) lp_write_nan(p, pred, err);
+        if (!ok) {
             if (tid < CK_VG_NPAR) score[tid] = ck_vecchia_slot_out(V, tid, 0.0, 1);
             return;
         }
     } else {
-        // ---- 4. pred = v . y, var = c0 - v . v ----
-        double s1v = 0.0, s2v = 0.0;
-        for (int a = tid; a < k; a += LP_TPB) {
-            const double v = S[(long)k * ld + a], y = S[(long)(k + 1) * ld + a];
-            s1v += v * y;
-            s2v += v * v;
-        }
-        red[0][tid] = s1v;
-        red[1][tid] = s2v;
-        __syncthreads();
-        for (int s = LP_TPB / 2; s > 0; s >>= 1) {
-            if (tid < s) {
-                red[0][tid] += red[0][tid + s];
-                red[1][tid] += red[1][tid + s];
-            }
-            __syncthreads();
-        }
-        mu = red[0][0];
-        vvs = red[1][0];
-        if (tid == 0) {
-            pred[p] = mu;
-            vv[p] = vvs;
-            const double sd = sqrt(c0var - vvs);
-            err[p] = (sd == sd) ? fmax(sd, 0.0) : 0.0;
-        }
+        lp_dots(S + (long)k * ld, S + (long)(k + 1) * ld, k, &mu, &vvs);   // 4. pred = v . y, var = c0 - v . v
+        if (tid == 0) lp_write(p, mu, vvs, P.c0var, pred, err, vv);
     }
     // ---- the two weights of M ----
     const long gs = A.gself[p];
     double w_bb, w_ab;
-    const int bad = ck_vecchia_weights(z[gs], mu, vvs, c0var, nz ? nz[gs] : 0.0, k, &w_bb, &w_ab);
+    const int bad = ck_vecchia_weights(P.z[gs], mu, vvs, P.c0var, P.nz ? P.nz[gs] : 0.0, k, &w_bb, &w_ab);
     if (bad) {   // uniform
         if (tid < CK_VG_NPAR) score[tid] = ck_vecchia_slot_out(V, tid, 0.0, 1);
         return;
@@ -1523,13 +1232,13 @@ __global__ __launch_bounds__(LP_TPB) void k_vecchia_grad(const CkMatern* __restr
         int a, b;
         ck_vg_pair_of(e, &a, &b);
         const long ga = a < k ? idx[a] : gs, gb = b < k ? idx[b] : gs;
-        const int pa = a < k ? (V.n_procs == 2 && ga >= L.n0p ? 1 : 0) : i_pred;
-        const int pb = b < k ? (V.n_procs == 2 && gb >= L.n0p ? 1 : 0) : i_pred;
-        const double a0 = a < k ? s0[ga] : p0, a1 = a < k ? s1[ga] : p1, a2 = a < k ? s2[ga] : p2;
-        const double b0 = b < k ? s0[gb] : p0, b1 = b < k ? s1[gb] : p1, b2 = b < k ? s2[gb] : p2;
+        const int pa = a < k ? (V.n_procs == 2 && ga >= P.L.n0p ? 1 : 0) : P.i_pred;
+        const int pb = b < k ? (V.n_procs == 2 && gb >= P.L.n0p ? 1 : 0) : P.i_pred;
+        const double a0 = a < k ? X.s0[ga] : X.p0, a1 = a < k ? X.s1[ga] : X.p1, a2 = a < k ? X.s2[ga] : X.p2;
+        const double b0 = b < k ? X.s0[gb] : X.p0, b1 = b < k ? X.s1[gb] : X.p1, b2 = b < k ? X.s2[gb] : X.p2;
         const double ba = a < k ? S[(long)k * ld + a] : 1.0, aa = a < k ? S[(long)(k + 1) * ld + a] : 0.0;
         const double bb = b < k ? S[(long)k * ld + b] : 1.0, ab = b < k ? S[(long)(k + 1) * ld + b] : 0.0;
-        const double h = a == b ? 0.0 : lp_dist(metric, a0, a1, a2, b0, b1, b2);
+        const double h = a == b ? 0.0 : lp_dist(P.metric, a0, a1, a2, b0, b1, b2);
         const double d_p = (a == b && A.dvar) ? A.dvar[ga] : 0.0;
         ck_vecchia_pair(acc, V, pa, pb, a == b, h, ck_vecchia_m(w_bb, w_ab, ba, aa, bb, ab), d_p);
     }
@@ -1547,47 +1256,40 @@ __global__ __launch_bounds__(LP_TPB) void k_vecchia_grad(const CkMatern* __restr
     if (tid < CK_VG_NPAR) score[tid] = ck_vecchia_slot_out(V, tid, ((sred[0][tid] + sred[1][tid]) + sred[2][tid]) + sred[3][tid], 0);
 }
 
-__global__ __launch_bounds__(LP_TPB) void k_vecchia_grad_part(long n, const double* __restrict__ score, double* __restrict__ part) {
+// the tree of both kernels: column(c) is this thread's entry of column c; threads 0 .. 12 write the column sums to out
+template <class F>
+__device__ __forceinline__ void vg_tree(F column, double* out) {
     __shared__ double red[CK_VG_NPAR][LP_TPB];
     const int tid = threadIdx.x;
-    const long t = (long)blockIdx.x * LP_TPB + tid;
-    for (int c = 0; c < CK_VG_NPAR; ++c) red[c][tid] = t < n ? score[t * CK_VG_NPAR + c] : 0.0;
+    for (int c = 0; c < CK_VG_NPAR; ++c) red[c][tid] = column(c);
     __syncthreads();
     for (int s = LP_TPB / 2; s > 0; s >>= 1) {
         if (tid < s)
             for (int c = 0; c < CK_VG_NPAR; ++c) red[c][tid] += red[c][tid + s];
         __syncthreads();
     }
-    if (tid < CK_VG_NPAR) part[(long)blockIdx.x * CK_VG_NPAR + tid] = red[tid][0];
+    if (tid < CK_VG_NPAR) out[tid] = red[tid][0];
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_grad_part(long n, const double* __restrict__ score, double* __restrict__ part) {
+    const long t = (long)blockIdx.x * LP_TPB + threadIdx.x;
+    vg_tree([&](int c) { return t < n ? score[t * CK_VG_NPAR + c] : 0.0; }, part + (long)blockIdx.x * CK_VG_NPAR);
 }
 
 __global__ __launch_bounds__(LP_TPB) void k_vecchia_grad_sum(long nblk, const double* __restrict__ part, double* __restrict__ out13) {
-    __shared__ double red[CK_VG_NPAR][LP_TPB];
-    const int tid = threadIdx.x;
-    for (int c = 0; c < CK_VG_NPAR; ++c) {
-        double v = 0.0;
-        for (long e = tid; e < nblk; e += LP_TPB) v += part[e * CK_VG_NPAR + c];
-        red[c][tid] = v;
-    }
-    __syncthreads();
-    for (int s = LP_TPB / 2; s > 0; s >>= 1) {
-        if (tid < s)
-            for (int c = 0; c < CK_VG_NPAR; ++c) red[c][tid] += red[c][tid + s];
-        __syncthreads();
-    }
-    if (tid < CK_VG_NPAR) out13[tid] = red[tid][0];
+    vg_tree(
+        [&](int c) {
+            double v = 0.0;
+            for (long e = threadIdx.x; e < nblk; e += LP_TPB) v += part[e * CK_VG_NPAR + c];
+            return v;
+        },
+        out13);
 }
 
-void ck_launch_vecchia_grad(hipStream_t s, const CkMatern* blk, int metric, int i_pred, double max_dist, const double* pc, int64_t m,
-                            int64_t mpad, const double* sc, const double* z, CkLayout L, const int* counts, double c0var,
-                            double* pred, double* err, const CkTable* tabs, const double* const* coefs, int use_tab,
-                            const double* su, const double* pu, const double* cb, double cmax, const double* nz, CkLocalCap cap,
+void ck_launch_vecchia_grad(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, double* pred, double* err,
                             double* vv, CkVecchiaGradArgs A) {
     if (m <= 0) return;
-    const LpTab T{tabs, coefs, use_tab};
-    const LpSearch R{cb, (long)((L.nend + LP_TPB - 1) / LP_TPB), cmax, cap.rq, cap.cp, cap.rs, cap.rp};
-    k_vecchia_grad<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(blk, metric, i_pred, max_dist, pc, mpad, sc, z, L, counts, c0var, pred,
-                                                              err, T, su, pu, R, nz, vv, A);
+    k_vecchia_grad<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(P, counts, pred, err, vv, A);
 }
 
 void ck_launch_vecchia_grad_sum(hipStream_t s, int64_t n, const double* score, double* part, double* out13) {
