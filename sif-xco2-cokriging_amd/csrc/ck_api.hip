@@ -3493,18 +3493,130 @@ static int local_nmax_of(const ck_handle* h, int q) {
 static int local_key_cap(const ck_handle* h) {
     return h->local_select_cap > 0 ? h->local_select_cap : ck_local_select_capacity();
 }
-// ck_timings [61] points with a capped process, [62] largest candidate count (both processes) before the cap, [63] points
-// that re-scanned; sel: the select pass's m x 4 ints (m = 0: an uncapped call)
-static void local_select_stats(ck_handle* h, const int* sel, int64_t m) {
-    int64_t n_capped = 0, n_rescan = 0, cand_max = 0;
-    for (int64_t p = 0; p < m; ++p) {
-        n_capped += (sel[4 * p + 3] & CK_LS_CAPPED) != 0;
-        n_rescan += (sel[4 * p + 3] & CK_LS_RESCAN) != 0;
-        cand_max = std::max<int64_t>(cand_max, sel[4 * p + 2]);
+// What the select pass reports (all zero: an uncapped call, whose counting pass is no select pass); ck_timings [60 .. 63]
+struct LocalSelectStats {
+    double ms = 0.0;                                    // the pass's device window
+    int64_t n_capped = 0, cand_max = 0, n_rescan = 0;   // points with a capped process | largest candidate count (both
+                                                        // processes) before the cap | points that re-scanned
+    void add(const LocalSelectStats& o) {               // over several passes (the Vecchia entry points: one per process)
+        ms += o.ms;
+        n_capped += o.n_capped;
+        cand_max = std::max(cand_max, o.cand_max);
+        n_rescan += o.n_rescan;
     }
-    h->t_ms[61] = (double)n_capped;
-    h->t_ms[62] = (double)cand_max;
-    h->t_ms[63] = (double)n_rescan;
+};
+static void write_select_timings(ck_handle* h, const LocalSelectStats& st) {
+    h->t_ms[60] = st.ms;
+    h->t_ms[61] = (double)st.n_capped;
+    h->t_ms[62] = (double)st.cand_max;
+    h->t_ms[63] = (double)st.n_rescan;
+}
+
+// The first stage of every local call: the points on the device and their counting or select pass.  What it leaves behind is
+// what the later launches of the call are told (prob) and what the host plans with (cnt; sel: m x 4 ints of a select pass).
+struct LocalPass {
+    int64_t m = 0, mp = 0;
+    double *d_p3 = nullptr, *d_pu = nullptr, *d_rq = nullptr, *d_cp = nullptr;   // d_rq, d_cp: select pass only
+    int *d_cnt = nullptr, *d_sel = nullptr, *d_rp = nullptr;                     // d_sel: select pass only; d_rp: with rp_host
+    CkLocalProblem prob;
+    std::vector<int> cnt, sel;
+    double pass_ms = 0.0;   // the pass's device window, whichever pass it was
+    LocalSelectStats st;
+};
+// select: the select pass with the handle's caps (the counting pass of a capped call); else the counting pass, and no kernel
+// sees a cap pointer.  d_rs / rp_host: the precedence condition of the Vecchia likelihood (device: every site's position in the
+// ordering; host: the m points'), both null without one.  rcut_host: m x 2, receives the cut distances of a select pass.  One
+// synchronisation, after the downloads; pass_ms is read here, so [ev0, ev1] are free again when the stage returns.
+static int local_pass(ck_handle* h, DevTemps& tmp, int i, const double* pcoords, int64_t m, double max_dist, int cv, bool select,
+                      const int* d_rs, const int* rp_host, double* rcut_host, LocalPass* out) {
+    LocalPass& S = *out;
+    const int64_t mp = S.mp = roundup(S.m = m, 64);
+    double* d_pc = nullptr;
+    HIPCHK(tmp.get(&d_pc, (size_t)(2 * mp * 8)));
+    HIPCHK(tmp.get(&S.d_p3, (size_t)(3 * mp * 8)));
+    HIPCHK(tmp.get(&S.d_pu, (size_t)(3 * mp * 8)));
+    HIPCHK(tmp.get(&S.d_cnt, (size_t)(mp * sizeof(int))));
+    if (select) {
+        HIPCHK(tmp.get(&S.d_sel, (size_t)(4 * mp * sizeof(int))));
+        HIPCHK(tmp.get(&S.d_rq, (size_t)(2 * mp * 8)));
+        HIPCHK(tmp.get(&S.d_cp, (size_t)(mp * 8)));
+    }
+    if (rp_host) {
+        HIPCHK(tmp.get(&S.d_rp, (size_t)(mp * sizeof(int))));
+        HIPCHK(hipMemcpyAsync(S.d_rp, rp_host, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(hipMemsetAsync(d_pc, 0, 2 * mp * 8, h->stream));
+    HIPCHK(hipMemcpyAsync(d_pc, pcoords, 2 * m * 8, hipMemcpyHostToDevice, h->stream));
+    ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, S.d_p3, S.d_p3 + mp, S.d_p3 + 2 * mp, S.d_pu);
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    S.prob = local_problem(h, i, cv, max_dist);
+    S.prob.pc = S.d_p3;
+    S.prob.pu = S.d_pu;
+    S.prob.mpad = mp;
+    S.prob.rq = S.d_rq;
+    S.prob.cp = S.d_cp;
+    S.prob.rs = d_rs;
+    S.prob.rp = S.d_rp;
+    if (select)
+        ck_launch_local_select(h->stream, S.prob, m, local_nmax_of(h, 0), local_nmax_of(h, 1), local_key_cap(h), S.d_cnt, S.d_sel,
+                               S.d_rq, S.d_cp);
+    else
+        ck_launch_local_count(h->stream, S.prob, m, S.d_cnt);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    S.cnt.resize((size_t)m);
+    if (select) {   // the counts are the sum of its first two columns (ck_internal.h): one download
+        S.sel.resize((size_t)(4 * m));
+        HIPCHK(hipMemcpyAsync(S.sel.data(), S.d_sel, S.sel.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        if (rcut_host) HIPCHK(hipMemcpyAsync(rcut_host, S.d_rq, (size_t)(2 * m * 8), hipMemcpyDeviceToHost, h->stream));
+    } else {
+        HIPCHK(hipMemcpyAsync(S.cnt.data(), S.d_cnt, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &S.pass_ms));
+    if (select) {
+        S.st.ms = S.pass_ms;
+        for (int64_t p = 0; p < m; ++p) {
+            const int* s = &S.sel[(size_t)(4 * p)];
+            S.cnt[(size_t)p] = s[0] + s[1];
+            S.st.n_capped += (s[3] & CK_LS_CAPPED) != 0;
+            S.st.n_rescan += (s[3] & CK_LS_RESCAN) != 0;
+            S.st.cand_max = std::max<int64_t>(S.st.cand_max, s[2]);
+        }
+    }
+    return 0;
+}
+
+// The slab budget of the large-neighbourhood paths in doubles: a quarter of the free device memory, the kept slab counted as
+// free (it is ours to reuse), at most 32 GiB; option "local_slab_mb" if set (tests).  *avail: the bytes that count as free.
+static int local_budget_doubles(const ck_handle* h, long long* budget, size_t* avail = nullptr) {
+    size_t mem_free = 0, mem_total = 0;
+    HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
+    mem_free += (size_t)local_slab_doubles(h) * 8;
+    *budget = (long long)std::min<size_t>(mem_free / 4, (size_t)32 << 30) / 8;
+    if (h->local_slab_mb > 0) *budget = (long long)h->local_slab_mb * (1 << 20) / 8;
+    if (avail) *avail = mem_free;
+    return 0;
+}
+// The kept slab grown to at least `need` doubles (no-op when it is that large); *grow_ms: what that cost (ck_timings [14]).
+// Growing is what stalls: hipMalloc of tens of GiB right after a hipFree of a few GiB that were written took 1-4 s every time
+// (scripts/diag_malloc.py; profiles/r03c_local_predictor.json's 100 km row, 1 262 ms for a 3 ms call, was this allocation).
+// So: beyond 1 GiB take the whole budget at once (the slab then never grows again), and allocate the new slab before
+// releasing the old one; without room for both, release first and take what is needed.
+static int local_slab_grow(ck_handle* h, long long need, long long budget, double* grow_ms) {
+    *grow_ms = 0.0;
+    if (need <= local_slab_doubles(h)) return 0;
+    const auto t_grow = std::chrono::steady_clock::now();
+    const long long want = need * 8 > (1LL << 30) ? std::max(need, budget) : need;
+    DevBuf<double> fresh;
+    if (fresh.reserve((size_t)want) != hipSuccess) {
+        (void)hipGetLastError();
+        h->local_slab.reset();
+        HIPCHK(fresh.reserve((size_t)need));
+    }
+    h->local_slab = std::move(fresh);   // releases the old slab
+    *grow_ms = ms_since(t_grow);
+    return 0;
 }
 
 extern "C" int ck_set_local_neighbours(ck_handle* h, int64_t nmax0, int64_t nmax1) {
@@ -3524,42 +3636,15 @@ extern "C" int ck_debug_local_neighbours(ck_handle* h, int i, const double* pcoo
     if (ensure_layout(h, false)) return -1;
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
     if (m < 0 || (m > 0 && (!pcoords || !count || !rcut))) return fail("ck_debug_local_neighbours: bad arguments");
-    for (int k = 60; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
-    if (m == 0) return 0;
-    const int64_t mp = roundup(m, 64);
+    for (int k = 60; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
     DevTemps tmp;
-    double *d_pc = nullptr, *d_p3 = nullptr, *d_pu = nullptr, *d_rq = nullptr, *d_cp = nullptr;
-    int *d_cnt = nullptr, *d_sel = nullptr;
-    HIPCHK(tmp.get(&d_pc, (size_t)(2 * mp * 8)));
-    HIPCHK(tmp.get(&d_p3, (size_t)(3 * mp * 8)));
-    HIPCHK(tmp.get(&d_pu, (size_t)(3 * mp * 8)));
-    HIPCHK(tmp.get(&d_rq, (size_t)(2 * mp * 8)));
-    HIPCHK(tmp.get(&d_cp, (size_t)(mp * 8)));
-    HIPCHK(tmp.get(&d_cnt, (size_t)(mp * sizeof(int))));
-    HIPCHK(tmp.get(&d_sel, (size_t)(4 * mp * sizeof(int))));
-    HIPCHK(hipMemsetAsync(d_pc, 0, 2 * mp * 8, h->stream));
-    HIPCHK(hipMemcpyAsync(d_pc, pcoords, 2 * m * 8, hipMemcpyHostToDevice, h->stream));
-    ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, d_p3, d_p3 + mp, d_p3 + 2 * mp, d_pu);
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    CkLocalProblem P = local_problem(h, i, cv, max_dist);   // (the select pass reads neither the values nor the noise)
-    P.pc = d_p3;
-    P.pu = d_pu;
-    P.mpad = mp;
-    ck_launch_local_select(h->stream, P, m, local_nmax_of(h, 0), local_nmax_of(h, 1), local_key_cap(h), d_cnt, d_sel, d_rq, d_cp);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    std::vector<int> sel((size_t)(4 * m));
-    HIPCHK(hipMemcpyAsync(sel.data(), d_sel, sel.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(rcut, d_rq, (size_t)(2 * m * 8), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    LocalPass S;   // (the select pass reads neither the values nor the noise)
+    if (m > 0 && local_pass(h, tmp, i, pcoords, m, max_dist, cv, true, nullptr, nullptr, rcut, &S)) return -1;
     for (int64_t p = 0; p < m; ++p) {
-        count[2 * p] = sel[(size_t)(4 * p)];
-        count[2 * p + 1] = sel[(size_t)(4 * p + 1)];
+        count[2 * p] = S.sel[(size_t)(4 * p)];
+        count[2 * p + 1] = S.sel[(size_t)(4 * p + 1)];
     }
-    double ms = 0;
-    HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms));
-    h->t_ms[60] = ms;
-    local_select_stats(h, sel.data(), m);
+    write_select_timings(h, S.st);
     return 0;
 }
 
@@ -3580,15 +3665,30 @@ struct LocalVecchia {
     int32_t* cnt2;        // host, m x 2: conditioning data of process 0 / 1
 };
 
+// What a call of predict_local_impl reports: to the caller, and to ck_timings through the exported entry points
+struct LocalResult {
+    int64_t n_empty = 0, n_not_pd = 0, k_max = 0;
+    int64_t n_tiled = 0;        // points of the tiled class
+    double pass_ms = 0.0;       // device windows: the counting pass (a capped call's select pass),
+    double solve_ms = 0.0;      // assembly / factorisations / reductions,
+    double reduce_ms = 0.0;     // of which the tiled class's universal reductions (universal form)
+    double grow_ms = 0.0;       // host: a growth of the scratch slab, between the two device windows
+    double total_ms = 0.0;      // host: the call (universal form)
+    LocalSelectStats st;
+};
+// ck_timings [10] device work, [14] slab growth, [60 .. 63] the select pass (zeros after an uncapped call)
+static void write_local_timings(ck_handle* h, const LocalResult& R) {
+    h->t_ms[10] = R.pass_ms + R.solve_ms;
+    h->t_ms[14] = R.grow_ms;
+    write_select_timings(h, R.st);
+}
+
 static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_t m, double max_dist, int cv, double* pred,
-                              double* pred_err, int64_t* n_empty, int64_t* n_not_pd, int64_t* k_max, const LocalUniv* u,
-                              const LocalVecchia* vc = nullptr) {
+                              double* pred_err, LocalResult* res, const LocalUniv* u, const LocalVecchia* vc = nullptr) {
+    LocalResult& R = *res = LocalResult();
     if (ensure_layout(h, false)) return -1;   // sites, tables, chunk bounds -- no Sigma panels
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
     if (m < 0 || (m > 0 && !pcoords)) return fail("bad pcoords");
-    if (n_empty) *n_empty = 0;
-    if (n_not_pd) *n_not_pd = 0;
-    if (k_max) *k_max = 0;
     if (m == 0) return 0;
     const auto t_begin = std::chrono::steady_clock::now();
     const int up = u ? trend_total(h) : 0;   // trend rows of every local system
@@ -3597,45 +3697,16 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     if (ensure_noise(h)) return -1;
     const int64_t mp = roundup(m, 64);
     DevTemps tmp;
-    double *d_pc = nullptr, *d_p3 = nullptr, *d_pu = nullptr, *d_out = nullptr, *d_slab = nullptr;
-    int* d_cnt = nullptr;
+    double *d_out = nullptr, *d_slab = nullptr, *d_vv = nullptr;
     long long *d_off = nullptr, *d_linfo = nullptr;
     int* d_k0 = nullptr;
     CkLocalSys* d_sys = nullptr;
-    HIPCHK(tmp.get(&d_pc, (size_t)(2 * mp * 8)));
-    HIPCHK(tmp.get(&d_p3, (size_t)(3 * mp * 8)));
-    HIPCHK(tmp.get(&d_pu, (size_t)(3 * mp * 8)));
     HIPCHK(tmp.get(&d_out, (size_t)(2 * mp * 8)));
-    HIPCHK(tmp.get(&d_cnt, (size_t)(mp * sizeof(int))));
     HIPCHK(tmp.get(&d_off, (size_t)(mp * sizeof(long long))));
-    // the neighbour cap (ck_set_local_neighbours): the select pass replaces the counting pass and leaves every point's cut
-    // distances and culling chord for the later launches; no cap: none of this exists and no kernel sees a new pointer
-    const int nmax0 = local_nmax_of(h, 0), nmax1 = local_nmax_of(h, 1);
-    const bool capped = nmax0 > 0 || nmax1 > 0 || vc;
-    int* d_sel = nullptr;
-    double *d_rq = nullptr, *d_cp = nullptr;
-    if (capped) {
-        HIPCHK(tmp.get(&d_sel, (size_t)(4 * mp * sizeof(int))));
-        HIPCHK(tmp.get(&d_rq, (size_t)(2 * mp * 8)));
-        HIPCHK(tmp.get(&d_cp, (size_t)(mp * 8)));
-    }
-    int* d_rp = nullptr;
-    double* d_vv = nullptr;
     if (vc) {
-        HIPCHK(tmp.get(&d_rp, (size_t)(mp * sizeof(int))));
         HIPCHK(tmp.get(&d_vv, (size_t)(mp * 8)));
         HIPCHK(hipMemsetAsync(d_vv, 0, (size_t)(mp * 8), h->stream));
-        HIPCHK(hipMemcpyAsync(d_rp, vc->rp, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
     }
-    CkLocalProblem P = local_problem(h, i, cv, max_dist);   // what every launch below is told about the call
-    P.pc = d_p3;
-    P.pu = d_pu;
-    P.mpad = mp;
-    P.rq = d_rq;
-    P.cp = d_cp;
-    P.rs = vc ? vc->d_rs : nullptr;
-    P.rp = d_rp;
-    const double c0var = P.c0var;
     // universal form: the regressors of the prediction points (a point with a non-finite one is settled on the host at the
     // end and computes with zeros meanwhile), the status of every point, the local coefficients
     double *d_f0 = nullptr, *d_beta = nullptr;
@@ -3655,23 +3726,18 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
         if (upi > 0) HIPCHK(hipMemcpy(d_f0, f0s.data(), (size_t)(m * upi * 8), hipMemcpyHostToDevice));
     }
     const CkLocalTrend Tr{h->d_trendX, d_f0, u ? h->trend_p[0] : 0, u && h->n_procs == 2 ? h->trend_p[1] : 0, CK_TREND_TOL};
-    HIPCHK(hipMemsetAsync(d_pc, 0, 2 * mp * 8, h->stream));
-    HIPCHK(hipMemcpyAsync(d_pc, pcoords, 2 * m * 8, hipMemcpyHostToDevice, h->stream));
-    ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, d_p3, d_p3 + mp, d_p3 + 2 * mp, d_pu);
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    if (capped)
-        ck_launch_local_select(h->stream, P, m, nmax0, nmax1, local_key_cap(h), d_cnt, d_sel, d_rq, d_cp);
-    else
-        ck_launch_local_count(h->stream, P, m, d_cnt);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));   // [ev0, ev1]: the counting pass; the host-side planning and a growth of the
-                                                 // scratch slab (hipMalloc: up to seconds) lie between the two device windows
-    std::vector<int> cnt(m);
-    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, m * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    std::vector<int> sel(capped ? (size_t)(4 * m) : 0);
-    if (capped) HIPCHK(hipMemcpyAsync(sel.data(), d_sel, sel.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    local_select_stats(h, sel.data(), capped ? m : 0);   // ck_timings [61] .. [63]
+    // the neighbour cap (ck_set_local_neighbours): the select pass replaces the counting pass and leaves every point's cut
+    // distances and culling chord for the later launches; no cap: none of this exists and no kernel sees a new pointer.  The
+    // host-side planning and a growth of the scratch slab (hipMalloc: up to seconds) lie between the pass and the solve window
+    const bool select = local_nmax_of(h, 0) > 0 || local_nmax_of(h, 1) > 0 || vc;
+    LocalPass S;
+    if (local_pass(h, tmp, i, pcoords, m, max_dist, cv, select, vc ? vc->d_rs : nullptr, vc ? vc->rp : nullptr, nullptr, &S)) return -1;
+    const CkLocalProblem& P = S.prob;   // what every launch below is told about the call
+    const int* d_cnt = S.d_cnt;
+    const std::vector<int>& cnt = S.cnt;
+    const double c0var = P.c0var;
+    R.pass_ms = S.pass_ms;
+    R.st = S.st;
     // Scratch slabs for neighbourhoods beyond the LDS limit.  Three size classes:
     //   k <= LDS limit               k_local_solve, system in LDS
     //   k <= local_tile_min          k_local_solve_big, one workgroup per point on a slab in global memory
@@ -3685,36 +3751,15 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     const int k_hi = u ? std::min(h->local_tile_min, kl) : h->local_tile_min;
     CkLocalNeeds nd;   // ck_host.cpp: the slab need of every point, the tiled class largest first
     ck_host_local_needs(cnt.data(), m, kl, k_hi, up, &nd);
-    int64_t nempty = nd.n_empty;
-    size_t mem_free = 0, mem_total = 0;
-    HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
-    mem_free += (size_t)local_slab_doubles(h) * 8;   // the slab kept from an earlier call is ours to reuse
-    long long budget = (long long)std::min<size_t>(mem_free / 4, (size_t)32 << 30) / 8;   // doubles
-    if (h->local_slab_mb > 0) budget = (long long)h->local_slab_mb * (1 << 20) / 8;      // option "local_slab_mb" (tests)
+    long long budget = 0;
+    size_t mem_free = 0;
+    if (local_budget_doubles(h, &budget, &mem_free)) return -1;
     if (budget < nd.need_max) budget = nd.need_max;
     if ((size_t)nd.need_max * 8 > mem_free) return fail(std::string(u ? "ck_predict_local_universal" : "ck_predict_local") + ": a neighbourhood of " + std::to_string(nd.k_max) + " sites does not fit the device memory");
     CkLocalPlan plan;   // slab offsets, the batches of both classes under the budget, the tiled systems
     ck_host_local_plan(cnt.data(), nd, budget, up, &plan);
-    const long long slab_doubles = plan.slab_doubles;
-    h->t_ms[14] = 0.0;
-    const auto t_grow = std::chrono::steady_clock::now();
-    if (slab_doubles > local_slab_doubles(h)) {
-        // Growing is what stalls: hipMalloc of tens of GiB right after a hipFree of a few GiB that were written
-        // took 1-4 s every time (scripts/diag_malloc.py).  So: beyond 1 GiB take the whole budget at once (the
-        // slab then never grows again), and allocate the new slab before releasing the old one.
-        const long long want = slab_doubles * 8 > (1LL << 30) ? std::max(slab_doubles, budget) : slab_doubles;
-        DevBuf<double> fresh;
-        if (fresh.reserve((size_t)want) != hipSuccess) {
-            (void)hipGetLastError();
-            h->local_slab.reset();   // not enough room for both
-            HIPCHK(fresh.reserve((size_t)slab_doubles));
-        }
-        h->local_slab = std::move(fresh);   // releases the old slab
-        // visible in ck_timings [14]; profiles/r03c_local_predictor.json's 100 km row (1 262 ms for a 3 ms call) was this
-        // allocation inside the one event window of round 3
-        h->t_ms[14] = ms_since(t_grow);
-    }
-    if (slab_doubles > 0) d_slab = h->local_slab;
+    if (local_slab_grow(h, plan.slab_doubles, budget, &R.grow_ms)) return -1;
+    if (plan.slab_doubles > 0) d_slab = h->local_slab;
     HIPCHK(hipEventRecord(h->ev2, h->stream));
     HIPCHK(hipMemcpyAsync(d_off, plan.off.data(), m * sizeof(long long), hipMemcpyHostToDevice, h->stream));
     if (u)
@@ -3770,23 +3815,21 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     if (vc) {
         HIPCHK(hipMemcpyAsync(vc->vv, d_vv, m * 8, hipMemcpyDeviceToHost, h->stream));
         for (int64_t p = 0; p < m; ++p) {
-            vc->cnt2[2 * p] = sel[(size_t)(4 * p)];
-            vc->cnt2[2 * p + 1] = sel[(size_t)(4 * p + 1)];
+            vc->cnt2[2 * p] = S.sel[(size_t)(4 * p)];
+            vc->cnt2[2 * p + 1] = S.sel[(size_t)(4 * p + 1)];
         }
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    double ms = 0, ms2 = 0;
-    HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms));
-    HIPCHK(elapsed_ms(h->ev2, h->ev3, &ms2));
-    h->t_ms[10] = ms + ms2;   // device work: counting pass + assembly / factorisations / reductions
-    h->t_ms[60] = capped ? ms : 0.0;   // the select pass (it is the counting pass of a capped call)
-    int64_t npd = 0;
+    HIPCHK(elapsed_ms(h->ev2, h->ev3, &R.solve_ms));
+    R.k_max = nd.k_max;
+    R.n_tiled = (int64_t)nd.tiled.size();
+    R.n_empty = nd.n_empty;
     if (u) {
         std::vector<int> stat((size_t)m);
         HIPCHK(hipMemcpy(stat.data(), d_stat, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
         if (u->beta) HIPCHK(hipMemcpy(u->beta, d_beta, (size_t)(m * up * 8), hipMemcpyDeviceToHost));
         int64_t nrd = 0;
-        nempty = 0;
+        R.n_empty = 0;
         for (int64_t p = 0; p < m; ++p) {
             if (f0_bad[(size_t)p]) {   // rule 5: NaN, in none of the counters
                 pred[p] = pred_err[p] = NAN;
@@ -3794,38 +3837,41 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
                     for (int j = 0; j < up; ++j) u->beta[p * up + j] = NAN;
                 continue;
             }
-            nempty += stat[(size_t)p] == CK_LU_EMPTY;
-            npd += stat[(size_t)p] == CK_LU_NOT_PD;
+            R.n_empty += stat[(size_t)p] == CK_LU_EMPTY;
+            R.n_not_pd += stat[(size_t)p] == CK_LU_NOT_PD;
             nrd += stat[(size_t)p] == CK_LU_RANK_DEF;
         }
         if (u->n_rank_def) *u->n_rank_def = nrd;
-        double red_ms = 0.0;
         for (size_t e = 0; e + 1 < ev_red.size(); e += 2) {
             double t = 0;
             HIPCHK(elapsed_ms(ev_red[e], ev_red[e + 1], &t));
-            red_ms += t;
+            R.reduce_ms += t;
         }
-        h->t_ms[48] = ms;                      // the counting pass
-        h->t_ms[49] = (double)ms2 - red_ms;    // assembly and factorisation (the LDS class's kernel whole)
-        h->t_ms[50] = red_ms;                  // the tiled class's universal reduction (Gram matrix + GLS step)
-        h->t_ms[51] = ms_since(t_begin);
-        h->t_ms[52] = (double)(m - (int64_t)nd.tiled.size());   // points of the LDS class (the empty ones among them)
-        h->t_ms[53] = (double)nd.tiled.size();                  // points of the tiled class
+        R.total_ms = ms_since(t_begin);
     } else {
         for (int64_t p = 0; p < m; ++p)
-            if (cnt[p] > 0 && pred[p] != pred[p]) ++npd;
+            if (cnt[(size_t)p] > 0 && pred[p] != pred[p]) ++R.n_not_pd;
     }
-    if (n_empty) *n_empty = nempty;
-    if (n_not_pd) *n_not_pd = npd;
-    if (k_max) *k_max = nd.k_max;
     return 0;
+}
+
+// The exported predictions: the counts to the caller (any may be null), then the call's ck_timings slots, once.  m = 0: no
+// call ran and the slots of ck_predict_local keep what they held.
+static void local_counts_out(const LocalResult& R, int64_t* n_empty, int64_t* n_not_pd, int64_t* k_max) {
+    if (n_empty) *n_empty = R.n_empty;
+    if (n_not_pd) *n_not_pd = R.n_not_pd;
+    if (k_max) *k_max = R.k_max;
 }
 
 extern "C" int ck_predict_local(ck_handle* h, int i, const double* pcoords, int64_t m, double max_dist, int cv,
                                 double* pred, double* pred_err, int64_t* n_empty, int64_t* n_not_pd,
                                 int64_t* k_max) {
     CHKH(h);
-    return predict_local_impl(h, i, pcoords, m, max_dist, cv, pred, pred_err, n_empty, n_not_pd, k_max, nullptr);
+    LocalResult R;
+    if (predict_local_impl(h, i, pcoords, m, max_dist, cv, pred, pred_err, &R, nullptr)) return -1;
+    local_counts_out(R, n_empty, n_not_pd, k_max);
+    if (m > 0) write_local_timings(h, R);
+    return 0;
 }
 
 // Universal cokriging in the moving neighbourhood: include/cokrige.h has the arithmetic and the rules for degenerate cases;
@@ -3840,53 +3886,109 @@ extern "C" int ck_predict_local_universal(ck_handle* h, int i, const double* pco
     if (n_rank_def) *n_rank_def = 0;
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
     if (m > 0 && (!pred || !pred_err)) return fail("ck_predict_local_universal: bad prediction arrays");
-    for (int k = 48; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
-    if (trend_total(h) == 0)
-        return predict_local_impl(h, i, pcoords, m, max_dist, cv, pred, pred_err, n_empty, n_not_pd, k_max, nullptr);
-    if (m > 0 && h->trend_p[i] > 0 && !f0) return fail("ck_predict_local_universal: null regressors of the prediction sites");
+    for (int k = 48; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    const bool trend = trend_total(h) > 0;
+    if (trend && m > 0 && h->trend_p[i] > 0 && !f0) return fail("ck_predict_local_universal: null regressors of the prediction sites");
     const LocalUniv u{f0, beta, n_rank_def};
-    return predict_local_impl(h, i, pcoords, m, max_dist, cv, pred, pred_err, n_empty, n_not_pd, k_max, &u);
+    LocalResult R;
+    if (predict_local_impl(h, i, pcoords, m, max_dist, cv, pred, pred_err, &R, trend ? &u : nullptr)) return -1;
+    local_counts_out(R, n_empty, n_not_pd, k_max);
+    if (m > 0) write_local_timings(h, R);
+    if (m > 0 && trend) {
+        h->t_ms[48] = R.pass_ms;                      // the counting pass
+        h->t_ms[49] = R.solve_ms - R.reduce_ms;       // assembly and factorisation (the LDS class's kernel whole)
+        h->t_ms[50] = R.reduce_ms;                    // the tiled class's universal reduction (Gram matrix + GLS step)
+        h->t_ms[51] = R.total_ms;
+        h->t_ms[52] = (double)(m - R.n_tiled);        // points of the LDS class (the empty ones among them)
+        h->t_ms[53] = (double)R.n_tiled;              // points of the tiled class
+    }
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------
 // the Vecchia likelihood (include/cokrige.h has the definition)
 // ---------------------------------------------------------------------------------------
-// ranks (distinct integers, the caller's stacked order) -> positions 0 .. N - 1 in the ordering; two equal ranks: -1 and both
-// data in dup.  Ranks that already are a permutation of 0 .. N - 1 (what vecchia.ordering_ranks hands over) cost one pass
-static int vecchia_positions(const int64_t* rank, int64_t N, std::vector<int>& pos, int64_t dup[2]) {
-    pos.resize((size_t)N);
-    std::vector<char> seen((size_t)N, 0);
-    bool direct = true;
-    for (int64_t t = 0; t < N && direct; ++t) {
-        const int64_t r = rank[t];
-        if (r < 0 || r >= N || seen[(size_t)r]) {
-            direct = false;
-        } else {
-            seen[(size_t)r] = 1;
-            pos[(size_t)t] = (int)r;
-        }
-    }
-    if (direct) return 0;
-    std::vector<int64_t> ix((size_t)N);
-    for (int64_t t = 0; t < N; ++t) ix[(size_t)t] = t;
-    std::sort(ix.begin(), ix.end(), [&](int64_t a, int64_t b) { return rank[a] != rank[b] ? rank[a] < rank[b] : a < b; });
-    for (int64_t j = 0; j < N; ++j) {
-        if (j > 0 && rank[ix[(size_t)j]] == rank[ix[(size_t)(j - 1)]]) {
-            dup[0] = ix[(size_t)(j - 1)];
-            dup[1] = ix[(size_t)j];
-            return -1;
-        }
-        pos[(size_t)ix[(size_t)j]] = (int)j;
-    }
+// What both Vecchia entry points (name) refuse, in this order, before they touch the device; null_args: the arguments the
+// entry point cannot do without, named when one of them is null.  Then the layout: sites, tables, chunk bounds -- no Sigma
+// panels, nothing invalidated.
+static int vecchia_admit(ck_handle* h, const std::string& name, const char* null_args, double max_dist) {
+    if (h->world != 1)
+        return fail(name + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) + ")");
+    if (null_args) return fail(name + ": null " + null_args);
+    if (!(max_dist >= 0.0) || !std::isfinite(max_dist))
+        return fail(name + ": max_dist must be finite and >= 0, got " + std::to_string(max_dist));
+    if (trend_total(h) > 0)
+        return fail(name + ": a trend of " + std::to_string(trend_total(h)) +
+                    " columns is set on the handle; the Vecchia likelihood has no REML form (clear it with ck_set_trend)");
+    if (ensure_layout(h, false)) return -1;
+    if (ensure_noise(h)) return -1;
+    if (h->N > INT32_MAX) return fail(name + ": more than 2^31 - 1 data");
+    return 0;
+}
+// The ordering: positions of the data and of the sites (ck_host.cpp), the sites' on the device for the precedence condition
+static int vecchia_order(ck_handle* h, const std::string& name, const int64_t* rank_host, DevTemps& tmp, CkVecchiaOrder* ord,
+                         int** d_rs) {
+    if (ck_host_vecchia_order(rank_host, h->n_procs, h->n, h->n0p, h->Npad, h->perm[0].data(),
+                              h->n_procs == 2 ? h->perm[1].data() : nullptr, ord))
+        return fail(name + ": data " + std::to_string(ord->dup[0]) + " and " + std::to_string(ord->dup[1]) +
+                    " (stacked order) have the same rank " + std::to_string((long long)rank_host[ord->dup[0]]));
+    HIPCHK(tmp.get(d_rs, (size_t)h->Npad * sizeof(int)));
+    HIPCHK(hipMemcpyAsync(*d_rs, ord->rs.data(), (size_t)h->Npad * sizeof(int), hipMemcpyHostToDevice, h->stream));
     return 0;
 }
 
+// The data as the terms need them, in the caller's stacked order: every datum's value, prior variance and own measurement-error
+// variance s d (0 without noise)
+struct VecchiaData {
+    std::vector<double> zs, prior, own;
+};
+static void vecchia_data(const ck_handle* h, VecchiaData* D) {
+    D->zs.resize((size_t)h->N);
+    D->prior.resize((size_t)h->N);
+    D->own.assign((size_t)h->N, 0.0);
+    for (int k = 0; k < h->n_procs; ++k) {
+        const int64_t soff = k == 0 ? 0 : h->n[0];
+        const double c0 = h->blk[2 * k].amp + h->blk[2 * k].nugget;
+        const bool nz = h->noise_on && !h->noise_var[k].empty();
+        for (int64_t t = 0; t < h->n[k]; ++t) {
+            D->prior[(size_t)(soff + t)] = c0;
+            D->zs[(size_t)(soff + t)] = h->h_values[k][(size_t)t];
+            if (nz) D->own[(size_t)(soff + t)] = h->noise_scale[k] * h->noise_var[k][(size_t)t];
+        }
+    }
+}
+
+// What a Vecchia call reports: stats3 to the caller, ck_timings [10], [14], [60 .. 63] and [72 .. 77] (the gradient then writes
+// [80 .. 85])
+struct VecchiaReport {
+    int64_t n_empty = 0, k_max = 0, n_lds = 0, n_tiled = 0;
+    LocalSelectStats st;   // over the passes of both processes
+    double solve_ms = 0.0, grow_ms = 0.0, terms_ms = 0.0, total_ms = 0.0;
+};
+static void vecchia_report(ck_handle* h, const VecchiaReport& V, int64_t* stats3) {
+    if (stats3) {
+        stats3[0] = V.n_empty;
+        stats3[1] = V.k_max;
+        stats3[2] = V.st.n_capped;
+    }
+    h->t_ms[10] = V.st.ms + V.solve_ms;
+    h->t_ms[14] = V.grow_ms;
+    write_select_timings(h, V.st);
+    h->t_ms[72] = V.st.ms;
+    h->t_ms[73] = V.solve_ms;
+    h->t_ms[74] = V.terms_ms;
+    h->t_ms[75] = V.total_ms;
+    h->t_ms[76] = (double)V.n_lds;
+    h->t_ms[77] = (double)V.n_tiled;
+}
+
 // The terms and their sums in the caller's stacked order, from what the passes of the local solver left on the host: the tail of
-// both Vecchia entry points -- the same uploads and launches, so the same bits in out3.  [ev0, ev1]: the two term kernels.
-static int vecchia_terms_tail(ck_handle* h, DevTemps& tmp, int64_t N, const std::vector<double>& mu, std::vector<double>& vv,
-                              const std::vector<double>& prior, const std::vector<double>& own, const std::vector<double>& zs,
+// both Vecchia entry points -- the same uploads and launches, so the same bits in out3.  *terms_ms: the two term kernels
+// ([ev0, ev1], read here).
+static int vecchia_terms_tail(ck_handle* h, DevTemps& tmp, const VecchiaData& D, const std::vector<double>& mu, std::vector<double>& vv,
                               const std::vector<int32_t>& cnt2, double* out3, double* mean_host, double* var_host,
-                              int32_t* count_host, int64_t* info, int64_t* n_lds_out) {
+                              int32_t* count_host, int64_t* info, int64_t* n_lds_out, double* terms_ms) {
+    const int64_t N = h->N;
     const int kl = ck_local_lds_limit();
     int64_t n_lds = 0;
     for (int64_t t = 0; t < N; ++t) {
@@ -3905,8 +4007,8 @@ static int vecchia_terms_tail(ck_handle* h, DevTemps& tmp, int64_t N, const std:
     HIPCHK(tmp.get(&d_out, (size_t)(2 * 8)));
     HIPCHK(tmp.get(&d_cnt2, (size_t)(2 * N) * sizeof(int)));
     HIPCHK(tmp.get(&d_bad, (size_t)(nblk + 1) * sizeof(long long)));
-    const std::pair<double*, const double*> up[] = {{d_z, zs.data()}, {d_mu, mu.data()}, {d_vv, vv.data()}, {d_prior, prior.data()},
-                                                    {d_own, own.data()}};
+    const std::pair<double*, const double*> up[] = {{d_z, D.zs.data()}, {d_mu, mu.data()}, {d_vv, vv.data()}, {d_prior, D.prior.data()},
+                                                    {d_own, D.own.data()}};
     for (const auto& c : up) HIPCHK(hipMemcpyAsync(c.first, c.second, (size_t)(N * 8), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(d_cnt2, cnt2.data(), (size_t)(2 * N) * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
@@ -3921,6 +4023,7 @@ static int vecchia_terms_tail(ck_handle* h, DevTemps& tmp, int64_t N, const std:
     if (mean_host) HIPCHK(hipMemcpyAsync(mean_host, d_mean, (size_t)(N * 8), hipMemcpyDeviceToHost, h->stream));
     if (var_host) HIPCHK(hipMemcpyAsync(var_host, d_var, (size_t)(N * 8), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, terms_ms));
     if (count_host) memcpy(count_host, cnt2.data(), (size_t)(2 * N) * sizeof(int32_t));
     out3[1] = sums[0];
     out3[2] = sums[1];
@@ -3934,86 +4037,37 @@ static int vecchia_terms_tail(ck_handle* h, DevTemps& tmp, int64_t N, const std:
 extern "C" int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host, double max_dist, double* out3, double* mean_host,
                                  double* var_host, int32_t* count_host, int64_t* stats3, int64_t* info) {
     CHKH(h);
-    if (h->world != 1)
-        return fail("ck_loglik_vecchia is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) +
-                    ")");
-    if (!rank_host || !out3) return fail("ck_loglik_vecchia: null rank_host / out3");
-    if (!(max_dist >= 0.0) || !std::isfinite(max_dist))
-        return fail("ck_loglik_vecchia: max_dist must be finite and >= 0, got " + std::to_string(max_dist));
-    if (trend_total(h) > 0)
-        return fail("ck_loglik_vecchia: a trend of " + std::to_string(trend_total(h)) +
-                    " columns is set on the handle; the Vecchia likelihood has no REML form (clear it with ck_set_trend)");
-    if (ensure_layout(h, false)) return -1;   // sites, tables, chunk bounds -- no Sigma panels, nothing invalidated
-    if (ensure_noise(h)) return -1;
+    if (vecchia_admit(h, "ck_loglik_vecchia", rank_host && out3 ? nullptr : "rank_host / out3", max_dist)) return -1;
     const auto t_begin = std::chrono::steady_clock::now();
-    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
-    const int64_t N = h->N, n0 = h->n[0];
-    if (N > INT32_MAX) return fail("ck_loglik_vecchia: more than 2^31 - 1 data");
-    std::vector<int> pos;
-    int64_t dup[2] = {0, 0};
-    if (vecchia_positions(rank_host, N, pos, dup))
-        return fail("ck_loglik_vecchia: data " + std::to_string(dup[0]) + " and " + std::to_string(dup[1]) +
-                    " (stacked order) have the same rank " + std::to_string((long long)rank_host[dup[0]]));
-    // the sites' positions in the internal order (padding: never searched)
-    std::vector<int> rs((size_t)h->Npad, INT32_MAX);
-    for (int k = 0; k < h->n_procs; ++k) {
-        const int64_t off = k == 0 ? 0 : h->n0p, soff = k == 0 ? 0 : n0;
-        for (int64_t j = 0; j < h->n[k]; ++j) rs[(size_t)(off + j)] = pos[(size_t)(soff + h->perm[k][(size_t)j])];
-    }
+    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    const int64_t N = h->N;
     DevTemps tmp;
+    CkVecchiaOrder ord;
     int* d_rs = nullptr;
-    HIPCHK(tmp.get(&d_rs, (size_t)h->Npad * sizeof(int)));
-    HIPCHK(hipMemcpyAsync(d_rs, rs.data(), (size_t)h->Npad * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (vecchia_order(h, "ck_loglik_vecchia", rank_host, tmp, &ord, &d_rs)) return -1;
     // one pass of the local solver per process: its data are the points, i_pred = the process
-    std::vector<double> mu((size_t)N), vv((size_t)N, 0.0), sd((size_t)N), prior((size_t)N), own((size_t)N, 0.0), zs((size_t)N);
+    std::vector<double> mu((size_t)N), vv((size_t)N, 0.0), sd((size_t)N);
     std::vector<int32_t> cnt2((size_t)(2 * N), 0);
-    int64_t n_empty = 0, k_max = 0, n_capped = 0, n_rescan = 0, cand_max = 0;
-    double ms_select = 0.0, ms_solve = 0.0, ms_grow = 0.0;
+    VecchiaReport V;
     for (int k = 0; k < h->n_procs; ++k) {
-        const int64_t nk = h->n[k], soff = k == 0 ? 0 : n0;
+        const int64_t nk = h->n[k], soff = k == 0 ? 0 : h->n[0];
         if (nk == 0) continue;
-        const LocalVecchia vc{d_rs, pos.data() + soff, vv.data() + soff, cnt2.data() + 2 * soff};
-        int64_t ne = 0, npd = 0, km = 0;
-        if (predict_local_impl(h, k, h->h_coords[k].data(), nk, max_dist, 0, mu.data() + soff, sd.data() + soff, &ne, &npd, &km,
-                               nullptr, &vc))
+        const LocalVecchia vc{d_rs, ord.pos.data() + soff, vv.data() + soff, cnt2.data() + 2 * soff};
+        LocalResult R;
+        if (predict_local_impl(h, k, h->h_coords[k].data(), nk, max_dist, 0, mu.data() + soff, sd.data() + soff, &R, nullptr, &vc))
             return -1;
-        n_empty += ne;
-        k_max = std::max(k_max, km);
-        ms_select += h->t_ms[60];
-        ms_solve += h->t_ms[10] - h->t_ms[60];
-        ms_grow += h->t_ms[14];
-        n_capped += (int64_t)h->t_ms[61];
-        cand_max = std::max(cand_max, (int64_t)h->t_ms[62]);
-        n_rescan += (int64_t)h->t_ms[63];
-        const double c0 = h->blk[2 * k].amp + h->blk[2 * k].nugget;
-        const bool nz = h->noise_on && !h->noise_var[k].empty();
-        for (int64_t t = 0; t < nk; ++t) {
-            prior[(size_t)(soff + t)] = c0;
-            zs[(size_t)(soff + t)] = h->h_values[k][(size_t)t];
-            if (nz) own[(size_t)(soff + t)] = h->noise_scale[k] * h->noise_var[k][(size_t)t];
-        }
+        V.n_empty += R.n_empty;
+        V.k_max = std::max(V.k_max, R.k_max);
+        V.st.add(R.st);
+        V.solve_ms += R.solve_ms;
+        V.grow_ms += R.grow_ms;
     }
-    int64_t n_lds = 0;
-    if (vecchia_terms_tail(h, tmp, N, mu, vv, prior, own, zs, cnt2, out3, mean_host, var_host, count_host, info, &n_lds)) return -1;
-    if (stats3) {
-        stats3[0] = n_empty;
-        stats3[1] = k_max;
-        stats3[2] = n_capped;
-    }
-    double ms_terms = 0;
-    HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms_terms));
-    h->t_ms[10] = ms_select + ms_solve;
-    h->t_ms[14] = ms_grow;
-    h->t_ms[60] = ms_select;   // [60 ..]: over both passes
-    h->t_ms[61] = (double)n_capped;
-    h->t_ms[62] = (double)cand_max;
-    h->t_ms[63] = (double)n_rescan;
-    h->t_ms[72] = ms_select;
-    h->t_ms[73] = ms_solve;
-    h->t_ms[74] = ms_terms;
-    h->t_ms[75] = ms_since(t_begin);
-    h->t_ms[76] = (double)n_lds;
-    h->t_ms[77] = (double)(N - n_lds);
+    VecchiaData D;
+    vecchia_data(h, &D);
+    if (vecchia_terms_tail(h, tmp, D, mu, vv, cnt2, out3, mean_host, var_host, count_host, info, &V.n_lds, &V.terms_ms)) return -1;
+    V.n_tiled = N - V.n_lds;
+    V.total_ms = ms_since(t_begin);
+    vecchia_report(h, V, stats3);
     return 0;
 }
 
@@ -4024,38 +4078,18 @@ extern "C" int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host, double 
 extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, double max_dist, const int32_t* free13, double* out3,
                                       double* grad13, double* score_host, int64_t* stats3, int64_t* info) {
     CHKH(h);
-    if (h->world != 1)
-        return fail("ck_loglik_vecchia_grad is the single-process form: this handle is partitioned (world = " +
-                    std::to_string(h->world) + ")");
-    if (!rank_host || !out3 || !grad13) return fail("ck_loglik_vecchia_grad: null rank_host / out3 / grad13");
-    if (!(max_dist >= 0.0) || !std::isfinite(max_dist))
-        return fail("ck_loglik_vecchia_grad: max_dist must be finite and >= 0, got " + std::to_string(max_dist));
-    if (trend_total(h) > 0)
-        return fail("ck_loglik_vecchia_grad: a trend of " + std::to_string(trend_total(h)) +
-                    " columns is set on the handle; the Vecchia likelihood has no REML form (clear it with ck_set_trend)");
-    if (ensure_layout(h, false)) return -1;   // sites, tables, chunk bounds -- no Sigma panels, nothing invalidated
-    if (ensure_noise(h)) return -1;
+    if (vecchia_admit(h, "ck_loglik_vecchia_grad", rank_host && out3 && grad13 ? nullptr : "rank_host / out3 / grad13", max_dist))
+        return -1;
     const auto t_begin = std::chrono::steady_clock::now();
-    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
     const int NP = CK_FISHER_NPAR;
     static_assert(CK_FISHER_NPAR == CK_VG_NPAR, "the score has the slots of ck_loglik_fisher");
     for (int k = 0; k < NP; ++k) grad13[k] = NAN;
     const int64_t N = h->N, n0 = h->n[0], Np = h->Npad;
-    if (N > INT32_MAX) return fail("ck_loglik_vecchia_grad: more than 2^31 - 1 data");
-    std::vector<int> pos;
-    int64_t dup[2] = {0, 0};
-    if (vecchia_positions(rank_host, N, pos, dup))
-        return fail("ck_loglik_vecchia_grad: data " + std::to_string(dup[0]) + " and " + std::to_string(dup[1]) +
-                    " (stacked order) have the same rank " + std::to_string((long long)rank_host[dup[0]]));
-    // the sites' positions in the internal order (padding: never searched), and every datum's own internal index
-    std::vector<int> rs((size_t)Np, INT32_MAX), gself((size_t)N);
-    for (int k = 0; k < h->n_procs; ++k) {
-        const int64_t off = k == 0 ? 0 : h->n0p, soff = k == 0 ? 0 : n0;
-        for (int64_t j = 0; j < h->n[k]; ++j) {
-            rs[(size_t)(off + j)] = pos[(size_t)(soff + h->perm[k][(size_t)j])];
-            gself[(size_t)(soff + h->perm[k][(size_t)j])] = (int)(off + j);
-        }
-    }
+    DevTemps tmp;
+    CkVecchiaOrder ord;   // with every datum's own internal index (gself)
+    int* d_rs = nullptr;
+    if (vecchia_order(h, "ck_loglik_vecchia_grad", rank_host, tmp, &ord, &d_rs)) return -1;
     // live slots (ck_loglik_fisher's rule) and the operands of the contraction (ck_loglik's)
     CkVecchiaGradArgs A{};
     CkVecchiaModel& V = A.V;
@@ -4084,121 +4118,69 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
     V.rho = h->par_rho;
     V.n_procs = h->n_procs;
     A.dvar = (V.live >> 11 & 3u) ? h->d_noise + Np : nullptr;
-    DevTemps tmp;
-    int *d_rs = nullptr, *d_gself = nullptr;
+    int* d_gself = nullptr;
     double* d_score = nullptr;
-    HIPCHK(tmp.get(&d_rs, (size_t)Np * sizeof(int)));
     HIPCHK(tmp.get(&d_gself, (size_t)N * sizeof(int)));
     HIPCHK(tmp.get(&d_score, (size_t)(N * NP) * 8));
-    HIPCHK(hipMemcpyAsync(d_rs, rs.data(), (size_t)Np * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_gself, gself.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_gself, ord.gself.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
     // ---- phase 1: the select pass of every process (its points: the process's data in the caller's order)
-    struct Pass {
-        int64_t m = 0, mp = 0;
-        double *d_p3 = nullptr, *d_pu = nullptr, *d_out = nullptr, *d_rq = nullptr, *d_cp = nullptr, *d_vv = nullptr;
-        int *d_cnt = nullptr, *d_rp = nullptr;
-        CkLocalProblem prob;
-    } pass[2];
-    const int nmax0 = local_nmax_of(h, 0), nmax1 = local_nmax_of(h, 1);
+    LocalPass pass[2];
+    double *d_out[2] = {nullptr, nullptr}, *d_vv[2] = {nullptr, nullptr};
     const int kl = ck_local_lds_limit();
     std::vector<int32_t> cnt2((size_t)(2 * N), 0);
-    int64_t n_empty = 0, k_max = 0, n_capped = 0, n_rescan = 0, cand_max = 0, n_over = 0, n_pairs = 0;
-    double ms_select = 0.0;
+    VecchiaReport rep;
+    int64_t n_over = 0, n_pairs = 0;
     for (int k = 0; k < h->n_procs; ++k) {
-        Pass& P = pass[k];
-        P.m = h->n[k];
-        if (P.m == 0) continue;
-        const int64_t m = P.m, mp = P.mp = roundup(m, 64), soff = k == 0 ? 0 : n0;
-        double* d_pc = nullptr;
-        int* d_sel = nullptr;
-        HIPCHK(tmp.get(&d_pc, (size_t)(2 * mp * 8)));
-        HIPCHK(tmp.get(&P.d_p3, (size_t)(3 * mp * 8)));
-        HIPCHK(tmp.get(&P.d_pu, (size_t)(3 * mp * 8)));
-        HIPCHK(tmp.get(&P.d_out, (size_t)(2 * mp * 8)));
-        HIPCHK(tmp.get(&P.d_cnt, (size_t)(mp * sizeof(int))));
-        HIPCHK(tmp.get(&d_sel, (size_t)(4 * mp * sizeof(int))));
-        HIPCHK(tmp.get(&P.d_rq, (size_t)(2 * mp * 8)));
-        HIPCHK(tmp.get(&P.d_cp, (size_t)(mp * 8)));
-        HIPCHK(tmp.get(&P.d_rp, (size_t)(mp * sizeof(int))));
-        HIPCHK(tmp.get(&P.d_vv, (size_t)(mp * 8)));
-        HIPCHK(hipMemsetAsync(P.d_vv, 0, (size_t)(mp * 8), h->stream));
-        HIPCHK(hipMemcpyAsync(P.d_rp, pos.data() + soff, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemsetAsync(d_pc, 0, 2 * mp * 8, h->stream));
-        HIPCHK(hipMemcpyAsync(d_pc, h->h_coords[k].data(), 2 * m * 8, hipMemcpyHostToDevice, h->stream));
-        ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, P.d_p3, P.d_p3 + mp, P.d_p3 + 2 * mp, P.d_pu);
-        HIPCHK(hipEventRecord(h->ev0, h->stream));
-        P.prob = local_problem(h, k, 0, max_dist);   // this process's pass: the select here, the solve in phase 2
-        P.prob.pc = P.d_p3;
-        P.prob.pu = P.d_pu;
-        P.prob.mpad = mp;
-        P.prob.rq = P.d_rq;
-        P.prob.cp = P.d_cp;
-        P.prob.rs = d_rs;
-        P.prob.rp = P.d_rp;
-        ck_launch_local_select(h->stream, P.prob, m, nmax0, nmax1, local_key_cap(h), P.d_cnt, d_sel, P.d_rq, P.d_cp);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(h->ev1, h->stream));
-        std::vector<int> sel((size_t)(4 * m));
-        HIPCHK(hipMemcpyAsync(sel.data(), d_sel, sel.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        double ms = 0;
-        HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms));
-        ms_select += ms;
-        local_select_stats(h, sel.data(), m);
-        n_capped += (int64_t)h->t_ms[61];
-        cand_max = std::max(cand_max, (int64_t)h->t_ms[62]);
-        n_rescan += (int64_t)h->t_ms[63];
+        const int64_t m = h->n[k], mp = roundup(m, 64), soff = k == 0 ? 0 : n0;
+        if (m == 0) continue;
+        HIPCHK(tmp.get(&d_out[k], (size_t)(2 * mp * 8)));
+        HIPCHK(tmp.get(&d_vv[k], (size_t)(mp * 8)));
+        HIPCHK(hipMemsetAsync(d_vv[k], 0, (size_t)(mp * 8), h->stream));
+        LocalPass& S = pass[k];   // this process's pass: the select here, the solve in phase 2
+        if (local_pass(h, tmp, k, h->h_coords[k].data(), m, max_dist, 0, true, d_rs, ord.pos.data() + soff, nullptr, &S)) return -1;
+        rep.st.add(S.st);
         for (int64_t p = 0; p < m; ++p) {
-            const int k0 = sel[(size_t)(4 * p)], k1 = sel[(size_t)(4 * p + 1)], kt = k0 + k1;
+            const int k0 = S.sel[(size_t)(4 * p)], k1 = S.sel[(size_t)(4 * p + 1)], kt = k0 + k1;
             cnt2[(size_t)(2 * (soff + p))] = k0;
             cnt2[(size_t)(2 * (soff + p) + 1)] = k1;
-            n_empty += kt == 0;
+            rep.n_empty += kt == 0;
             n_over += kt > kl;
-            k_max = std::max<int64_t>(k_max, kt);
+            rep.k_max = std::max<int64_t>(rep.k_max, kt);
             n_pairs += (int64_t)(kt + 1) * (kt + 2) / 2;
         }
     }
-    h->t_ms[60] = ms_select;
-    h->t_ms[61] = (double)n_capped;
-    h->t_ms[62] = (double)cand_max;
-    h->t_ms[63] = (double)n_rescan;
-    if (n_over > 0)
+    if (n_over > 0) {
+        write_select_timings(h, rep.st);   // the refused call's passes did run
         return fail("ck_loglik_vecchia_grad: " + std::to_string(n_over) + " data have a conditioning set of more than " +
-                    std::to_string(kl) + " data (the largest: " + std::to_string(k_max) +
+                    std::to_string(kl) + " data (the largest: " + std::to_string(rep.k_max) +
                     "); the gradient is for sets the LDS solver takes: lower the caps or the radius, or difference ck_loglik_vecchia");
+    }
     // ---- phase 2: solve, back substitution and contraction, one workgroup per datum
-    std::vector<double> mu((size_t)N), vv((size_t)N, 0.0), prior((size_t)N), own((size_t)N, 0.0), zs((size_t)N);
+    std::vector<double> mu((size_t)N), vv((size_t)N, 0.0);
     HIPCHK(hipEventRecord(h->ev2, h->stream));
     for (int k = 0; k < h->n_procs; ++k) {
-        const Pass& P = pass[k];
-        if (P.m == 0) continue;
+        const LocalPass& S = pass[k];
+        if (S.m == 0) continue;
         const int64_t soff = k == 0 ? 0 : n0;
-        const double c0 = P.prob.c0var;
         CkVecchiaGradArgs Ak = A;
         Ak.gself = d_gself + soff;
         Ak.score = d_score + soff * NP;
-        ck_launch_vecchia_grad(h->stream, P.prob, P.m, P.d_cnt, P.d_out, P.d_out + P.mp, P.d_vv, Ak);
+        ck_launch_vecchia_grad(h->stream, S.prob, S.m, S.d_cnt, d_out[k], d_out[k] + S.mp, d_vv[k], Ak);
         HIPCHK(hipGetLastError());
-        const bool nzk = h->noise_on && !h->noise_var[k].empty();
-        for (int64_t t = 0; t < P.m; ++t) {
-            prior[(size_t)(soff + t)] = c0;
-            zs[(size_t)(soff + t)] = h->h_values[k][(size_t)t];
-            if (nzk) own[(size_t)(soff + t)] = h->noise_scale[k] * h->noise_var[k][(size_t)t];
-        }
     }
     HIPCHK(hipEventRecord(h->ev3, h->stream));
+    VecchiaData D;
+    vecchia_data(h, &D);   // on the host while the device solves: before the downloads, which wait for it
     for (int k = 0; k < h->n_procs; ++k) {
-        const Pass& P = pass[k];
-        if (P.m == 0) continue;
-        const int64_t soff = k == 0 ? 0 : n0;
-        HIPCHK(hipMemcpyAsync(mu.data() + soff, P.d_out, P.m * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(vv.data() + soff, P.d_vv, P.m * 8, hipMemcpyDeviceToHost, h->stream));
+        const int64_t m = pass[k].m, soff = k == 0 ? 0 : n0;
+        if (m == 0) continue;
+        HIPCHK(hipMemcpyAsync(mu.data() + soff, d_out[k], m * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(vv.data() + soff, d_vv[k], m * 8, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));   // (hb is stack memory)
-    double ms_solve = 0;
-    HIPCHK(elapsed_ms(h->ev2, h->ev3, &ms_solve));
-    int64_t n_lds = 0, first_bad = 0;
-    if (vecchia_terms_tail(h, tmp, N, mu, vv, prior, own, zs, cnt2, out3, nullptr, nullptr, nullptr, &first_bad, &n_lds)) return -1;
+    HIPCHK(elapsed_ms(h->ev2, h->ev3, &rep.solve_ms));
+    int64_t first_bad = 0;
+    if (vecchia_terms_tail(h, tmp, D, mu, vv, cnt2, out3, nullptr, nullptr, nullptr, &first_bad, &rep.n_lds, &rep.terms_ms)) return -1;
     // ---- the column sums of the scores, in the caller's stacked order
     const int64_t nblk = (N + 255) / 256;
     double *d_part = nullptr, *d_g = nullptr;
@@ -4214,26 +4196,14 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
     if (first_bad)
         for (int k = 0; k < NP; ++k) grad13[k] = NAN;
     if (info) *info = first_bad;
-    if (stats3) {
-        stats3[0] = n_empty;
-        stats3[1] = k_max;
-        stats3[2] = n_capped;
-    }
-    double ms_terms = 0, ms_sum = 0;
-    HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms_terms));
+    double ms_sum = 0;
     HIPCHK(elapsed_ms(h->ev2, h->ev3, &ms_sum));
-    h->t_ms[10] = ms_select + ms_solve;
-    h->t_ms[14] = 0.0;
-    h->t_ms[72] = ms_select;
-    h->t_ms[73] = ms_solve;
-    h->t_ms[74] = ms_terms;
-    h->t_ms[75] = ms_since(t_begin);
-    h->t_ms[76] = (double)n_lds;
-    h->t_ms[77] = 0.0;
-    h->t_ms[80] = ms_select;
-    h->t_ms[81] = ms_solve;
-    h->t_ms[82] = ms_terms + ms_sum;
-    h->t_ms[83] = h->t_ms[75];
+    rep.total_ms = ms_since(t_begin);
+    vecchia_report(h, rep, stats3);   // (n_tiled, grow_ms: 0 -- every set is of the LDS class)
+    h->t_ms[80] = rep.st.ms;
+    h->t_ms[81] = rep.solve_ms;
+    h->t_ms[82] = rep.terms_ms + ms_sum;
+    h->t_ms[83] = rep.total_ms;
     h->t_ms[84] = (double)N;
     h->t_ms[85] = (double)n_pairs;
     return 0;
@@ -4247,13 +4217,7 @@ extern "C" int ck_local_reserve(ck_handle* h, int64_t nbytes) {
     CHKH(h);
     if (nbytes < 0) return fail("ck_local_reserve: negative size");
     long long want = nbytes / 8;
-    if (nbytes == 0) {
-        size_t mem_free = 0, mem_total = 0;
-        HIPCHK(hipMemGetInfo(&mem_free, &mem_total));
-        mem_free += (size_t)local_slab_doubles(h) * 8;
-        want = (long long)std::min<size_t>(mem_free / 4, (size_t)32 << 30) / 8;
-        if (h->local_slab_mb > 0) want = (long long)h->local_slab_mb * (1 << 20) / 8;
-    }
+    if (nbytes == 0 && local_budget_doubles(h, &want)) return -1;
     if (want <= local_slab_doubles(h)) return 0;
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(hipStreamSynchronize(h->stream));

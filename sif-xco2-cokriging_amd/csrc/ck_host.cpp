@@ -692,3 +692,51 @@ void ck_host_local_plan(const int* cnt, const CkLocalNeeds& nd, long long budget
         },
         &out->tbatches, &out->slab_doubles);
 }
+
+// ---- the Vecchia likelihood: ranks -> positions, of the data and of the sites (ck_host.h) ---------------------------------
+// ranks (distinct integers) -> positions 0 .. N - 1; two equal ranks: -1 and both data in dup
+static int vecchia_positions(const int64_t* rank, int64_t N, std::vector<int>& pos, int64_t dup[2]) {
+    pos.resize((size_t)N);
+    std::vector<char> seen((size_t)N, 0);
+    bool direct = true;
+    for (int64_t t = 0; t < N && direct; ++t) {
+        const int64_t r = rank[t];
+        if (r < 0 || r >= N || seen[(size_t)r]) {
+            direct = false;
+        } else {
+            seen[(size_t)r] = 1;
+            pos[(size_t)t] = (int)r;
+        }
+    }
+    if (direct) return 0;
+    std::vector<int64_t> ix((size_t)N);
+    for (int64_t t = 0; t < N; ++t) ix[(size_t)t] = t;
+    std::sort(ix.begin(), ix.end(), [&](int64_t a, int64_t b) { return rank[a] != rank[b] ? rank[a] < rank[b] : a < b; });
+    for (int64_t j = 0; j < N; ++j) {
+        if (j > 0 && rank[ix[(size_t)j]] == rank[ix[(size_t)(j - 1)]]) {
+            dup[0] = ix[(size_t)(j - 1)];
+            dup[1] = ix[(size_t)j];
+            return -1;
+        }
+        pos[(size_t)ix[(size_t)j]] = (int)j;
+    }
+    return 0;
+}
+
+int ck_host_vecchia_order(const int64_t* rank, int n_procs, const int64_t n[2], int64_t n0p, int64_t npad, const int64_t* perm0,
+                          const int64_t* perm1, CkVecchiaOrder* out) {
+    *out = CkVecchiaOrder();
+    const int64_t N = n[0] + (n_procs == 2 ? n[1] : 0);
+    if (vecchia_positions(rank, N, out->pos, out->dup)) return -1;
+    out->rs.assign((size_t)npad, INT32_MAX);
+    out->gself.resize((size_t)N);
+    for (int k = 0; k < n_procs; ++k) {
+        const int64_t off = k == 0 ? 0 : n0p, soff = k == 0 ? 0 : n[0];
+        const int64_t* perm = k == 0 ? perm0 : perm1;
+        for (int64_t j = 0; j < n[k]; ++j) {
+            out->rs[(size_t)(off + j)] = out->pos[(size_t)(soff + perm[j])];
+            out->gself[(size_t)(soff + perm[j])] = (int)(off + j);
+        }
+    }
+    return 0;
+}

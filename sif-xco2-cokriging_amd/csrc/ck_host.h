@@ -143,6 +143,23 @@ struct CkLocalPlan {
 };
 CK_HIDDEN void ck_host_local_plan(const int* cnt, const CkLocalNeeds& nd, long long budget, int trend, CkLocalPlan* out);
 
+// ---- the Vecchia likelihood: the ordering's index work (ck_api.hip: ck_loglik_vecchia, ck_loglik_vecchia_grad) --------------
+// Pure index work, no device.  rank: N = n[0] + n[1] distinct integers in the caller's stacked order (process 0, then 1); only
+// their order counts.  perm_k as in the fold plan below (ck_handle::perm); internal position of the site at position j of
+// process k: j for process 0, n0p + j for process 1.
+//   pos    N: every datum's position 0 .. N - 1 in the ordering, stacked order.  Ranks that already are a permutation of
+//          0 .. N - 1 (what vecchia.ordering_ranks hands over) cost one pass, any others a sort
+//   rs     npad: every site's position in the ordering, internal order; padding (between the processes, behind the last) keeps
+//          INT32_MAX and is never earlier than a point
+//   gself  N: every datum's own internal position, stacked order
+struct CkVecchiaOrder {
+    std::vector<int> pos, rs, gself;
+    int64_t dup[2] = {0, 0};
+};
+// 0, or -1 with two data of equal rank in out->dup (stacked order, the earlier first; the caller words the refusal)
+CK_HIDDEN int ck_host_vecchia_order(const int64_t* rank, int n_procs, const int64_t n[2], int64_t n0p, int64_t npad,
+                                    const int64_t* perm0, const int64_t* perm1, CkVecchiaOrder* out);
+
 // ---- leave-group-out cross-validation: the fold layout (ck_api.hip: ck_cv_folds) ---------------------------------------
 // Pure index work, no device.  Fold f withholds every datum of either process labelled f (fold_k[a]: the caller's order of
 // process k; -1: never withheld; fold1 may be null).  perm_k[j] = caller's index of the site at internal position j of

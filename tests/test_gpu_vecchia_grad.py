@@ -298,6 +298,44 @@ def test_repeated_calls_give_the_same_bits_and_leave_the_state(native):
     h.close()
 
 
+def test_value_and_gradient_report_the_same_select_statistics(native):
+    """The lattice of tests/test_gpu_vecchia.py (576 + 144 sites: more than two 256-site chunks) on a handle that keeps 16
+    candidates per process in LDS, caps (4, 4) at radius 1.0, so that the re-scan path runs.  The counts in timings() and stats3
+    are those of the numpy reference over the passes of both processes, after the value and after the gradient alike; an uncapped
+    prediction on the same handle then reports no select pass."""
+    from sif_xco2_cokriging_amd import synth
+    from tests.test_gpu_vecchia import lattice
+    coords, values, ranks, D, proc = lattice()
+    caps, max_dist, key_cap = (4, 4), 1.0, 16
+    keep, _, capped = vr.conditioning_sets(D, proc, ranks, max_dist, caps)
+    ktot = np.count_nonzero(keep, axis=1)
+    cand = np.column_stack([np.count_nonzero((proc == q)[None, :] & (ranks[None, :] < ranks[:, None]) & (D <= max_dist), axis=1)
+                            for q in range(2)])
+    want = dict(local_n_capped=np.count_nonzero(capped), local_cand_max=cand.sum(axis=1).max(),
+                local_n_rescan=np.count_nonzero(np.any(cand > max(key_cap, caps[0]), axis=1)))
+    want_stats = dict(n_empty=np.count_nonzero(ktot == 0), k_max=ktot.max(), n_capped=np.count_nonzero(capped))
+    assert np.array_equal(capped, np.any(cand > np.array(caps), axis=1)) and ktot.max() <= 64
+    assert 0 < want["local_n_rescan"] < want["local_n_capped"] < len(ranks)   # every path of the pass is taken
+    h = make_handle(native, synth.SET_B_UNIT, EUC, coords, values, local_select_cap=key_cap)
+    h.set_local_neighbours(*caps)
+    seen = {}
+    for entry in ("value", "gradient"):
+        out = h.loglik_vecchia(ranks, max_dist) if entry == "value" else h.loglik_vecchia_grad(ranks, max_dist)
+        t = h.timings()
+        print(f"{entry}: stats3 {out[-1]}, timings [60 ..] {[t[k] for k in ('local_select_ms', *want)]}")
+        assert out[-2] == 0, entry
+        assert t["local_select_ms"] > 0, entry
+        seen[entry] = ({k: t[k] for k in want}, {k: out[-1][k] for k in want_stats})
+        assert seen[entry] == (want, want_stats), entry
+    assert seen["value"] == seen["gradient"]
+    h.set_local_neighbours(0, 0)
+    _, _, info = h.predict_local(0, coords[1][:40] + 0.05, 0.3)
+    t = h.timings()
+    assert info["k_max"] > 0 and t["local_ms"] > 0
+    assert t["local_select_ms"] == 0 and t["local_n_capped"] == 0 and t["local_cand_max"] == 0 and t["local_n_rescan"] == 0
+    h.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 8. refusals, 9. a datum without a term
 # ---------------------------------------------------------------------------------------------------------------------
