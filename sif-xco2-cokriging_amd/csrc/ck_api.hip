@@ -171,7 +171,8 @@ struct ck_handle {
                                // evaluations of a fit
     AuxState aux_state = AUX_NONE;
     double par_sigma[2] = {0.0, 0.0}, par_rho = 0.0;   // ck_set_model's sigma and rho12 (ck_loglik's derivatives in them)
-    DevBuf<CkMatern> d_lik_blk;                         // ck_loglik: 3 blocks x (the block, nu - 2 d, nu - d, nu + d, nu + 2 d)
+    DevBuf<CkMatern> d_lik_blk;                         // lik_blocks: 3 blocks x (the block, nu - 2 d, nu - d, nu + d, nu + 2 d)
+    CkMatern lik_hb[15];                                // ... and what its upload reads
     // ck_predict_blocks: the block rows (the aux panel layout with bmpad = roundup(r + 1, CK_AUX_ALIGN) rows per panel), kept
     // between calls like aux; option "block_chunk": prediction sites per K2 assembly (0: from the device memory the handle may use)
     DevBuf<double> baux;
@@ -295,7 +296,6 @@ struct ck_handle {
     int aux_trend = 0;   // trend rows behind the data row of the right-hand sides being assembled (rows m + 1 .. m + aux_trend)
     int loo_dense = 1;   // rows in front of the unit rows in the leave-one-out / likelihood layout (ck_loglik_reml: 1 + p)
     int64_t fisher_product_mb = 0;    // option "fisher_product_mb": room of ck_loglik_fisher's stored products (0: what is free)
-    std::vector<double> fi_A, fi_H;   // ck_loglik_fisher (REML): A = X^T Sigma^-1 X (p x p) and H = Sigma^-1 X (Npad x p) of its sweep
 
     ~ck_handle() {   // events and streams; the buffers release themselves
         for (auto& e : gemm_ev) {
@@ -341,7 +341,8 @@ extern "C" int ck_device_count(int* n) {
 static int64_t align256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
 // What the handle allocates in the caller's arena if there is one (ck_estimate_bytes is the sum of exactly these sizes):
 // a panel's rows with the diagonal blocks' inverses behind them (ck_panel_buffer) ...
-static int64_t panel_payload(int64_t Np, int K) { return ((Np - (int64_t)K * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8; }
+static_assert(CK_HOST_NB == CK_NB && CK_HOST_PANEL_TAIL == CK_PANEL_TAIL, "ck_host.h and ck_internal.h disagree about a panel");
+static int64_t panel_payload(int64_t Np, int K) { return ck_host_panel_payload(Np, K); }
 static int64_t panel_bytes(int64_t Np, int K) { return align256(panel_payload(Np, K) + CK_PANEL_SLACK_BYTES); }   // in the slab
 static int64_t recv_bytes(int64_t Np) { return panel_payload(Np, 0) + CK_PANEL_SLACK_BYTES; }   // a receive slot: any panel
 static int64_t site_bytes(int64_t Np) { return 3 * Np * 8; }              // s0, su (p0, pu with mpad)
@@ -349,6 +350,19 @@ static int64_t value_bytes(int64_t Np) { return Np * 8; }                 // z
 static int64_t ptr_bytes(int nK) { return (int64_t)nK * sizeof(double*); }   // d_sigptr, d_panelptr
 static int64_t rhs_bytes(int64_t mpad, int64_t Np) { return mpad * Np * 8; }   // aux
 static int64_t pair_bytes(int64_t mpad) { return 2 * mpad * 8; }          // d_pcoords, d_pred
+static int64_t schur_bytes(int64_t Mp) { return ck_host_schur_bytes(Mp); }   // what schur_ensure(h, Mp) allocates
+
+// The admission of a call that grows the handle's buffers, in front of its first allocation: what the handle holds and the
+// free device memory against the call's right-hand sides, Schur order (0: none), scratch slab and temporaries
+// (ck_host_mem_admit has the rule).  The caller words its refusal from the amounts.
+static int mem_admit(const ck_handle* h, const CkMemAsk& ask, CkMemAdmit* out) {
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    const CkMemState st = {(int64_t)fr, h->arena != nullptr, h->arena_size, h->arena_used,
+                           aux_cap(h) * 8, h->sch.M, local_slab_doubles(h) * 8};
+    *out = ck_host_mem_admit(st, ask);
+    return 0;
+}
 
 // b <- `bytes` (rounded up to 256) of the arena as a view, or of device memory as its owner; b is empty if that fails.  An
 // arena never takes a carve back: a buffer that grows under it abandons the old one
@@ -1819,6 +1833,24 @@ static std::string trend_column_name(const ck_handle* h, int c) {
     return "regressor " + std::to_string(k == 0 ? c : c - h->trend_p[0]) + " of process " + std::to_string(k);
 }
 
+// The GLS step behind k_reduce_univ: A = U^T U and b = U^T y from the p trend rows of the reduced rows W (p + 2 doubles each,
+// the first trend row at row0), then ck_host_gls; a rank-deficient design is refused in the caller's name.  A: p x p, kept
+// for the caller; the other outputs as ck_host_gls's (any may be null).
+static int trend_gls(const ck_handle* h, const char* name, const std::vector<double>& W, int64_t row0, int p, double* A, double* R,
+                     double* beta, double* Ainv, double* logdet, double* bAb) {
+    std::vector<double> b((size_t)p);
+    for (int j = 0; j < p; ++j) {
+        const double* wr = &W[(size_t)((row0 + j) * (p + 2))];
+        b[(size_t)j] = wr[1];
+        for (int l = 0; l < p; ++l) A[(size_t)(j * p + l)] = wr[2 + l];
+    }
+    const int bad = ck_host_gls(p, A, b.data(), CK_TREND_TOL, R, beta, Ainv, logdet, bAb);
+    if (bad)
+        return fail(std::string(name) + ": the trend design is rank deficient: " + trend_column_name(h, bad - 1) +
+                    " is, to rounding, a combination of the regressors in front of it (X^T Sigma^-1 X is singular)");
+    return 0;
+}
+
 static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m, bool may_sort) {
     if (ensure_layout(h)) return -1;
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
@@ -1995,16 +2027,8 @@ extern "C" int ck_predict_universal(ck_handle* h, int i, const double* pcoords, 
     gemm_timed_collect(h, 7);
     // ---- the GLS step
     auto t0 = std::chrono::steady_clock::now();
-    std::vector<double> A((size_t)p * p), b((size_t)p), bh((size_t)p), Ai((size_t)p * p);
-    for (int j = 0; j < p; ++j) {
-        const double* wr = &W[(size_t)((m + 1 + j) * (q + 1))];
-        b[(size_t)j] = wr[1];
-        for (int l = 0; l < p; ++l) A[(size_t)(j * p + l)] = wr[2 + l];
-    }
-    const int bad = ck_host_gls(p, A.data(), b.data(), CK_TREND_TOL, nullptr, bh.data(), Ai.data(), nullptr, nullptr);
-    if (bad)
-        return fail("ck_predict_universal: the trend design is rank deficient: " + trend_column_name(h, bad - 1) +
-                    " is, to rounding, a combination of the regressors in front of it (X^T Sigma^-1 X is singular)");
+    std::vector<double> A((size_t)p * p), bh((size_t)p), Ai((size_t)p * p);
+    if (trend_gls(h, "ck_predict_universal", W, m + 1, p, A.data(), nullptr, bh.data(), Ai.data(), nullptr, nullptr)) return -1;
     h->t_ms[43] = ms_since(t0);
     const auto t1 = std::chrono::steady_clock::now();
     // ---- the epilogue, in the caller's order
@@ -2509,12 +2533,6 @@ extern "C" int ck_sample(ck_handle* h, const double* noise, double* out, int64_t
 // and column e_k, so that its draw is pred; every other diagonal entry gets jitter (sigma_i^2 + nugget_i).  The noise comes
 // from the caller or from the Philox stream of ck_rng.h keyed on (seed, caller's site index, draw index), and the product
 // E L_S^T runs on the matrix cores over the lower tiles, in chunks of option "draw_chunk" draws.
-static int64_t schur_bytes(int64_t Mp) {
-    int64_t b = 0;
-    for (int64_t r = Mp; r > 0; r -= CK_NB) b += (r * CK_NB + CK_PANEL_TAIL) * 8;
-    return b + (2 * Mp + 6 * Mp) * 8;
-}
-
 extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, int64_t m, int64_t n_draws, uint64_t seed,
                                     const double* noise, double tol, double jitter, double* draws, double* pred,
                                     double* pred_err, uint8_t* deflated, int64_t* info) {
@@ -2535,19 +2553,14 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
     const int nJ = (int)(Mp / CK_NB);
     // device memory: the Schur buffers, the right-hand sides of the point prediction, one chunk of 128 draws
     {
-        const int64_t aux_bytes = roundup(m + 1, CK_AUX_ALIGN) * h->Npad * 8;
         const int64_t s_bytes = h->sch.M == Mp ? 0 : schur_bytes(Mp);
         const int64_t c_bytes = 128 * (Mp + (noise ? 2 : 1) * m) * 8 + (int64_t)m * 13 + Mp * 12 + 1024;
-        const int64_t need = (aux_bytes > aux_cap(h) * 8 ? aux_bytes : 0) + s_bytes + c_bytes;
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        int64_t avail = (int64_t)fr;
-        if (!h->arena && aux_bytes > aux_cap(h) * 8) avail += aux_cap(h) * 8;   // released before a larger one is taken
-        if (s_bytes > 0 && h->sch.M > 0) avail += schur_bytes(h->sch.M);       // schur_ensure releases these first
-        if (need > avail)
-            return fail("ck_conditional_draws: needs " + std::to_string(need) + " bytes of device memory (" +
+        CkMemAdmit a;
+        if (mem_admit(h, {rhs_bytes(roundup(m + 1, CK_AUX_ALIGN), h->Npad), Mp, 0, c_bytes}, &a)) return -1;
+        if (a.need > a.avail)   // (an arena too small for the point rows is ck_predict's to refuse)
+            return fail("ck_conditional_draws: needs " + std::to_string(a.need) + " bytes of device memory (" +
                         std::to_string(s_bytes) + " for the posterior covariance of " + std::to_string(m) + " sites, " +
-                        std::to_string(c_bytes) + " for a chunk of 128 draws); " + std::to_string(avail) + " bytes are available");
+                        std::to_string(c_bytes) + " for a chunk of 128 draws); " + std::to_string(a.avail) + " bytes are available");
     }
     for (int k = 30; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
     *info = 0;
@@ -2801,23 +2814,19 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
                   o_grow = carve((size_t)ng * sizeof(int)), o_fail = carve((size_t)n_folds * sizeof(int));
     const long long slab_doubles = slab_bytes / 8;
     {   // device memory: the right-hand sides and the slab, as far as they have to grow
-        const int64_t aux_bytes = mpad_need * Np * 8;
-        const bool grow = aux_bytes > aux_cap(h) * 8, grow_slab = slab_doubles > local_slab_doubles(h);
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        int64_t avail = (int64_t)fr;
-        if (!h->arena && grow) avail += aux_cap(h) * 8;       // released before the larger one is taken
-        if (grow_slab) avail += local_slab_doubles(h) * 8;   // likewise
-        if (h->arena && grow && aux_bytes > h->arena_size - h->arena_used)
+        const int64_t aux_bytes = rhs_bytes(mpad_need, Np);
+        const bool grow = aux_bytes > aux_cap(h) * 8;
+        CkMemAdmit a;
+        if (mem_admit(h, {aux_bytes, 0, slab_bytes, 0}, &a)) return -1;
+        if (a.arena_short)
             return fail("ck_cv_folds needs " + std::to_string(aux_bytes) + " bytes of the arena for its " + std::to_string(m + 1) +
                         " right-hand-side rows of " + std::to_string(Np) + " doubles; " + std::to_string(h->arena_size - h->arena_used) +
                         " bytes are left");
-        const int64_t need = (grow && !h->arena ? aux_bytes : 0) + (grow_slab ? slab_bytes : 0);
-        if (need > avail)
-            return fail("ck_cv_folds needs " + std::to_string(need) + " bytes of device memory (" + std::to_string(grow ? aux_bytes : 0) +
+        if (a.need > a.avail)
+            return fail("ck_cv_folds needs " + std::to_string(a.need) + " bytes of device memory (" + std::to_string(grow ? aux_bytes : 0) +
                         " for " + std::to_string(m + 1) + " right-hand-side rows of " + std::to_string(Np) + " doubles, " +
                         std::to_string(buf_bytes) + " for the Gram matrices and systems of " + std::to_string(n_folds) + " folds, " +
-                        std::to_string(slab_bytes - buf_bytes) + " for their outputs and index tables); " + std::to_string(avail) +
+                        std::to_string(slab_bytes - buf_bytes) + " for their outputs and index tables); " + std::to_string(a.avail) +
                         " bytes are available");
     }
     *info = 0;
@@ -2926,73 +2935,59 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
 // the first 1 + p rows, alpha_q = W_q . y and B_q = U^T W_q (= (Sigma^-1 X)_q) over the unit rows.  The host forms beta, log|A|,
 // b^T A^-1 b, alpha_R = alpha - B beta and C = B R^-T (A = R R^T); k_ginv_syrk_d starts from the rank-(1 + p) term
 // alpha_R alpha_R^T + C C^T.  p = 0 is ck_loglik's path, bit for bit.
-// fisher (ck_loglik_fisher): the same sweep and reductions, but G starts from zero (G = -Sigma^-1), no contraction follows, and
-// A and H = Sigma^-1 X of the REML reduction are kept on the handle.
-static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, double* grad, int64_t* info, bool fisher = false) {
-    const char* name = fisher ? "ck_loglik_fisher" : reml ? "ck_loglik_reml" : "ck_loglik";
-    if (!out || !info || (want_grad && !grad)) return fail(std::string(name) + ": null argument");
+// ck_loglik_fisher: the same sweep and reductions, but G starts from zero (G = -Sigma^-1) and no contraction follows.
+//
+// Every stage below is written once and hands what it found to its caller; nothing of a sweep stays on the handle.  The three
+// entry points chain the stages and are the only writers of ck_timings [24 .. 29] and [64 .. 69].
+static int lik_admit(const ck_handle* h, const char* name, bool null_argument) {
+    if (null_argument) return fail(std::string(name) + ": null argument");
     if (h->world != 1)
         return fail(std::string(name) + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) +
                     "); the multi-GPU likelihood is not available");
     if (!h->assembled) return fail(std::string(name) + ": ck_assemble_joint has not been called");
-    const auto t_begin = std::chrono::steady_clock::now();
-    const int64_t Np = h->Npad;
-    const int npar = h->n_procs == 1 ? 4 : CK_LIK_NPAR;
-    const int p = reml ? trend_total(h) : 0;   // trend columns (0: the zero-mean likelihood)
-    const int q = 1 + p;
-    *info = 0;
-    const int nout = reml ? 4 : 3;
-    for (int k = 0; k < nout; ++k) out[k] = NAN;
-    double* out3 = out;
-    if (want_grad)
-        for (int k = 0; k < npar; ++k) grad[k] = NAN;
-    // device memory of the gradient: N + 1 unit / data rows of Npad doubles (the right-hand sides, mpad = Npad + 256 rows) and
-    // the lower triangle of G (packed block columns with their tails, as the Schur complement of ck_verify_model)
-    const int64_t mrows = want_grad ? Np : 0;
-    const int64_t mpad_need = roundup(mrows + 1 + p, CK_AUX_ALIGN);
-    if (want_grad) {
-        int64_t g_bytes = 0;
-        for (int J = 0; J < h->nK; ++J) g_bytes += ((Np - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;
-        const int64_t aux_bytes = mpad_need * Np * 8;
-        const int64_t need = (aux_bytes > aux_cap(h) * 8 ? aux_bytes : 0) + (h->sch.M == Np ? 0 : g_bytes);
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        int64_t avail = (int64_t)fr;
-        if (!h->arena) avail += aux_cap(h) * 8;   // the right-hand sides' buffer is released before a larger one is taken
-        if (h->sch.M != Np)
-            for (int J = 0; J < (int)h->sch.sig.size(); ++J)
-                avail += ((h->sch.M - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;   // schur_ensure releases these first
-        if (h->arena && aux_bytes > aux_cap(h) * 8 && aux_bytes > h->arena_size - h->arena_used)
-            return fail(std::string(name) + ": the gradient needs " + std::to_string(aux_bytes) + " bytes of the arena for its " +
-                        std::to_string(mrows + 1 + p) + " right-hand-side rows of " + std::to_string(Np) + " doubles; " +
-                        std::to_string(h->arena_size - h->arena_used) + " bytes are left");
-        if (need > avail)
-            return fail(std::string(name) + ": the gradient needs " + std::to_string(aux_bytes + g_bytes) + " bytes of device memory (" +
-                        std::to_string(aux_bytes) + " for " + std::to_string(mrows + 1 + p) + " rows of " + std::to_string(Np) + " doubles, " +
-                        std::to_string(g_bytes) + " for the lower triangle of G); " + std::to_string(avail) +
-                        " bytes are available");
-    }
-    CallGuard guard(h, AUX_LOGLIK, true);
-    for (int k = 24; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
-    h->t_ms[24] = h->t_ms[0];   // the assembly of this Sigma (ck_assemble_joint)
-    // ---- the factor: factor here, or the resident one of a preceding ck_factor
-    if (!h->factored) {
-        if (ck_factor(h, info)) return -1;
-        h->t_ms[25] = h->t_ms[1];
-    } else {
-        if (factor_info_raw(h, info)) return -1;
-    }
-    if (*info != 0) {   // not positive definite: the factor is unusable; assemble again before the next call
+    return 0;
+}
+
+// Device memory of the unit-row sweep and G, in front of the first allocation: Npad + 1 + p unit / data / trend rows of Npad
+// doubles (the right-hand sides) and the Schur buffers of order Npad, as far as they have to grow.  An arena without room for
+// the rows is refused here; the caller compares a->need with a->avail and words that refusal.
+static int lik_mem_admit(const ck_handle* h, const char* name, int p, CkMemAdmit* a) {
+    const int64_t Np = h->Npad, aux_bytes = rhs_bytes(roundup(Np + 1 + p, CK_AUX_ALIGN), Np);
+    if (mem_admit(h, {aux_bytes, Np, 0, 0}, a)) return -1;
+    if (a->arena_short)
+        return fail(std::string(name) + ": the gradient needs " + std::to_string(aux_bytes) + " bytes of the arena for its " +
+                    std::to_string(Np + 1 + p) + " right-hand-side rows of " + std::to_string(Np) + " doubles; " +
+                    std::to_string(h->arena_size - h->arena_used) + " bytes are left");
+    return 0;
+}
+
+// What the factor, the sweep and its reductions found.  info != 0: Sigma is not positive definite, the handle has to be
+// assembled again, and nothing else is set.
+struct LikSweep {
+    int64_t info = 0;
+    bool factored_here = false;   // ck_factor ran (its milliseconds: ck_timings [1])
+    double logdet = 0.0, logdetA = 0.0, quad = 0.0;   // log|Sigma|, log|A| (REML), z^T Sigma^-1 z (REML: z^T P z)
+    double sweep_ms = 0.0;                            // sweep and reductions on the device
+    std::vector<double> W;            // REML: the reduced rows (k_reduce_univ), 2 + p doubles each
+    std::vector<double> beta, R, A;   // REML: the GLS step (A = X^T Sigma^-1 X = R R^T)
+    std::vector<double> H;            // REML, on request: Sigma^-1 X (Npad x p)
+};
+
+// The factor (here, or the resident one of a preceding ck_factor), the right-hand sides -- row 0 = z, rows 1 .. p = X^T (REML),
+// with want_rows the unit vectors of every internal position behind them -- their sweep, the reductions and the GLS step.
+static int lik_sweep(ck_handle* h, DevTemps& tmp, const char* name, bool want_rows, int p, bool want_H, LikSweep* S) {
+    *S = LikSweep();
+    S->factored_here = !h->factored;
+    if (S->factored_here ? ck_factor(h, &S->info) : factor_info_raw(h, &S->info)) return -1;
+    if (S->info != 0) {   // not positive definite: the factor is unusable; assemble again before the next call
         h->factored = false;
         h->assembled = false;
-        h->t_ms[29] = ms_since(t_begin);
         return 0;
     }
+    const int64_t Np = h->Npad, mrows = want_rows ? Np : 0;
+    const int q = 1 + p;
     const CkLayout L = layout_of(h);
-    DevTemps tmp;
     if (p > 0 && ensure_trend(h)) return -1;
-    // ---- right-hand sides: row 0 = z, rows 1 .. p = X^T (REML), rows 1 + p .. p + mrows = the unit vectors of every internal
-    // position; the sweep
     if (aux_begin_impl(h, 0, nullptr, mrows + p, false)) return -1;
     h->aux_state = AUX_LOGLIK;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
@@ -3011,149 +3006,197 @@ static int loglik_impl(ck_handle* h, int want_grad, bool reml, double* out, doub
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     std::vector<double> ldp((size_t)h->nK);
-    double quad = 0.0;
     HIPCHK(hipMemcpyAsync(ldp.data(), d_ldp, (size_t)h->nK * 8, hipMemcpyDeviceToHost, h->stream));
-    std::vector<double> W;
     if (p == 0) {
-        HIPCHK(hipMemcpyAsync(&quad, h->d_pred, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(&S->quad, h->d_pred, 8, hipMemcpyDeviceToHost, h->stream));
     } else {
-        W.resize((size_t)(nrows * (q + 1)));
-        HIPCHK(hipMemcpyAsync(W.data(), h->d_univ, W.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        S->W.resize((size_t)(nrows * (q + 1)));
+        HIPCHK(hipMemcpyAsync(S->W.data(), h->d_univ, S->W.size() * 8, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->t_ms[26] = elapsed_ms(h->ev0, h->ev1);
+    S->sweep_ms = elapsed_ms(h->ev0, h->ev1);
     double half_logdet = 0.0;
     for (int K = 0; K < h->nK; ++K) half_logdet += ldp[(size_t)K];
-    const double logdet = 2.0 * half_logdet;
-    double logdetA = 0.0;
-    std::vector<double> R((size_t)p * p), bh((size_t)p);
-    if (p > 0) {   // the GLS step: A = U^T U, b = U^T y from rows 1 .. p
-        std::vector<double> A((size_t)p * p), b((size_t)p);
-        for (int j = 0; j < p; ++j) {
-            const double* wr = &W[(size_t)((1 + j) * (q + 1))];
-            b[(size_t)j] = wr[1];
-            for (int l = 0; l < p; ++l) A[(size_t)(j * p + l)] = wr[2 + l];
-        }
+    S->logdet = 2.0 * half_logdet;
+    if (p > 0) {
+        const std::vector<double>& W = S->W;
+        S->A.resize((size_t)p * p), S->R.resize((size_t)p * p), S->beta.resize((size_t)p);
         double bAb = 0.0;
-        const int bad = ck_host_gls(p, A.data(), b.data(), CK_TREND_TOL, R.data(), bh.data(), nullptr, &logdetA, &bAb);
-        if (bad)
-            return fail(std::string(name) + ": the trend design is rank deficient: " + trend_column_name(h, bad - 1) +
-                        " is, to rounding, a combination of the regressors in front of it (X^T Sigma^-1 X is singular)");
-        quad = W[1] - bAb;   // z^T P z = |y|^2 - b^T A^-1 b
-        if (fisher) {
-            h->fi_A = A;
-            h->fi_H.assign((size_t)(Np * p), 0.0);
-            for (int64_t r = 0; r < Np && want_grad; ++r)
-                for (int j = 0; j < p; ++j) h->fi_H[(size_t)(r * p + j)] = W[(size_t)((q + r) * (q + 1) + 2 + j)];
+        if (trend_gls(h, name, W, 1, p, S->A.data(), S->R.data(), S->beta.data(), nullptr, &S->logdetA, &bAb)) return -1;
+        S->quad = W[1] - bAb;   // z^T P z = |y|^2 - b^T A^-1 b
+        if (want_H) {
+            S->H.assign((size_t)(Np * p), 0.0);
+            for (int64_t r = 0; r < mrows; ++r)
+                for (int j = 0; j < p; ++j) S->H[(size_t)(r * p + j)] = W[(size_t)((q + r) * (q + 1) + 2 + j)];
         }
     }
-    out3[1] = logdet;
+    return 0;
+}
+
+// G <- start start^T - Sigma^-1 on the lower tiles of the first nend rows, in the Schur buffers (k_ginv_syrk_d over the swept
+// unit rows).  start (device): q_syrk rows of Npad doubles -- the data's alpha (q_syrk = q = 1), REML's [alpha_R; C], or zeros
+// (with trend rows in front of the unit rows the rank-q kernel, q_syrk = 2: it reads `dense`).  The launch lies between ev0
+// and ev1: lik_ginv_ms behind the caller's next synchronisation.
+static int lik_ginv(ck_handle* h, const double* start, int q_syrk, int q) {
+    if (schur_ensure(h, h->Npad)) return -1;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    ck_launch_ginv_syrk(h->stream, h->sch.d_ptr, h->aux, h->mpad, start, h->nK, h->nend, q_syrk, h->Npad, q);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    return 0;
+}
+static double lik_ginv_ms(const ck_handle* h) { return elapsed_ms(h->ev0, h->ev1); }
+
+// The five-point stencil in nu of the model's blocks -- 3 blocks x (the block, nu - 2 d, nu - d, nu + d, nu + 2 d), d = dnu3[b]
+// -- built in the handle's staging array and queued for d_lik_blk.  One process: its block in all three places.
+static int lik_blocks(ck_handle* h, double dnu3[3]) {
+    const int nblk = h->n_procs == 1 ? 1 : 3;
+    const double offs[4] = {-2.0, -1.0, 1.0, 2.0};
+    CkMatern* hb = h->lik_hb;
+    for (int b = 0; b < 3; ++b) {
+        const CkMatern& m = h->blk[b < nblk ? b : 0];
+        dnu3[b] = ck_matern_dnu_step(m.nu);
+        hb[5 * b] = m;
+        for (int k = 0; k < 4; ++k) ck_matern_prepare(m.nu + offs[k] * dnu3[b], m.len_scale, m.amp, m.nugget, &hb[5 * b + 1 + k]);
+    }
+    HIPCHK(h->d_lik_blk.reserve(sizeof(h->lik_hb) / sizeof(CkMatern)));
+    HIPCHK(hipMemcpyAsync(h->d_lik_blk, hb, sizeof(h->lik_hb), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+// The live parameter slots of a 13-slot score or information (bit k): the model's parameters, the noise scale of a process
+// that has variances, less what free13 (may be null) fixes.
+static unsigned live_slots(const ck_handle* h, const int32_t* free13) {
+    unsigned live = 0;
+    const int npar = h->n_procs == 1 ? 4 : CK_LIK_NPAR;
+    for (int k = 0; k < npar; ++k) live |= 1u << k;
+    if (!h->noise_var[0].empty()) live |= 1u << 11;
+    if (h->n_procs == 2 && !h->noise_var[1].empty()) live |= 1u << 12;
+    if (free13)
+        for (int k = 0; k < CK_FISHER_NPAR; ++k)
+            if (free13[k] == 0) live &= ~(1u << k);
+    return live;
+}
+
+// grad[0 .. npar) <- the contraction of G (in the Schur buffers, behind lik_ginv) with the derivatives of Sigma; *ms: its
+// device window (ev1 .. ev2).  Synchronises the stream.
+static int lik_contract(ck_handle* h, DevTemps& tmp, int npar, double* grad, double* ms) {
+    const CkLayout L = layout_of(h);
+    double dnu3[3] = {0.0, 0.0, 0.0};
+    if (lik_blocks(h, dnu3)) return -1;
+    const int64_t ngr = ck_lik_grad_groups(L);
+    double* d_part = nullptr;
+    HIPCHK(tmp.get(&d_part, (size_t)(ngr * CK_LIK_NPAR) * 8));
+    ck_launch_loglik_grad(h->stream, h->sch.d_ptr, L, h->n_procs, h->metric, h->s0, h->d_lik_blk, dnu3, h->par_sigma[0],
+                          h->par_sigma[1], h->par_rho, d_part);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev2, h->stream));
+    std::vector<double> part((size_t)(ngr * CK_LIK_NPAR));
+    HIPCHK(hipMemcpyAsync(part.data(), d_part, part.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *ms = elapsed_ms(h->ev1, h->ev2);
+    double g[CK_LIK_NPAR] = {};
+    for (int64_t w = 0; w < ngr; ++w)
+        for (int k = 0; k < CK_LIK_NPAR; ++k) g[k] += part[(size_t)(w * CK_LIK_NPAR + k)];
+    for (int k = 0; k < npar; ++k) grad[k] = g[k];
+    return 0;
+}
+
+// dl/ds_k = 1/2 sum_{a in k} G_aa d_a while G is in the Schur buffers: what ck_loglik_noise_grad hands out
+static int lik_noise_scores(ck_handle* h, DevTemps& tmp) {
+    h->lik_noise_grad[0] = h->lik_noise_grad[1] = 0.0;
+    if (ensure_noise(h)) return -1;
+    if (!h->noise_var[0].empty() || (h->n_procs == 2 && !h->noise_var[1].empty())) {
+        double* d_np = nullptr;
+        HIPCHK(tmp.get(&d_np, (size_t)(2 * h->nK) * 8));
+        ck_launch_lik_noise_grad(h->stream, h->sch.d_ptr, h->nK, layout_of(h), h->d_noise + h->Npad, d_np);
+        HIPCHK(hipGetLastError());
+        std::vector<double> np2((size_t)(2 * h->nK));
+        HIPCHK(hipMemcpyAsync(np2.data(), d_np, np2.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (int K = 0; K < h->nK; ++K)
+            for (int k = 0; k < 2; ++k) h->lik_noise_grad[k] += np2[(size_t)(2 * K + k)];
+        for (int k = 0; k < 2; ++k) h->lik_noise_grad[k] *= 0.5;
+    }
+    h->lik_noise_valid = true;
+    return 0;
+}
+
+// ck_loglik (p = 0, three outputs) and ck_loglik_reml (p = the trend columns, four)
+static int loglik_value_grad(ck_handle* h, const char* name, bool reml, int want_grad, double* out, double* grad, int64_t* info) {
+    if (lik_admit(h, name, !out || !info || (want_grad && !grad))) return -1;
+    const auto t_begin = std::chrono::steady_clock::now();
+    const int64_t Np = h->Npad;
+    const int npar = h->n_procs == 1 ? 4 : CK_LIK_NPAR;
+    const int p = reml ? trend_total(h) : 0;   // trend columns (0: the zero-mean likelihood)
+    const int q = 1 + p;
+    *info = 0;
+    for (int k = 0; k < (reml ? 4 : 3); ++k) out[k] = NAN;
+    if (want_grad) {
+        for (int k = 0; k < npar; ++k) grad[k] = NAN;
+        CkMemAdmit a;
+        if (lik_mem_admit(h, name, p, &a)) return -1;
+        if (a.need > a.avail) {
+            const int64_t aux_bytes = rhs_bytes(roundup(Np + 1 + p, CK_AUX_ALIGN), Np);
+            return fail(std::string(name) + ": the gradient needs " + std::to_string(aux_bytes + schur_bytes(Np)) +
+                        " bytes of device memory (" + std::to_string(aux_bytes) + " for " + std::to_string(Np + 1 + p) + " rows of " +
+                        std::to_string(Np) + " doubles, " + std::to_string(schur_bytes(Np)) + " for the lower triangle of G); " +
+                        std::to_string(a.avail) + " bytes are available");
+        }
+    }
+    CallGuard guard(h, AUX_LOGLIK, true);
+    double* t = h->t_ms;
+    for (int k = 24; k < CK_N_TIMINGS; ++k) t[k] = 0.0;
+    DevTemps tmp;
+    LikSweep S;
+    const int rc = lik_sweep(h, tmp, name, want_grad != 0, p, false, &S);
+    *info = S.info;
+    if (rc) return -1;
+    t[24] = t[0];   // the assembly of this Sigma (ck_assemble_joint)
+    if (S.factored_here) t[25] = t[1];
+    if (S.info != 0) {
+        t[29] = ms_since(t_begin);
+        return 0;
+    }
+    t[26] = S.sweep_ms;
+    out[1] = S.logdet;
     if (reml) {
-        out[2] = logdetA;
-        out[3] = quad;
-        out[0] = -0.5 * ((double)(h->N - p) * log(2.0 * M_PI) + logdet + logdetA + quad);
+        out[2] = S.logdetA;
+        out[3] = S.quad;
+        out[0] = -0.5 * ((double)(h->N - p) * log(2.0 * M_PI) + S.logdet + S.logdetA + S.quad);
     } else {
-        out3[2] = quad;
-        out3[0] = -0.5 * ((double)h->N * log(2.0 * M_PI) + logdet + quad);
+        out[2] = S.quad;
+        out[0] = -0.5 * ((double)h->N * log(2.0 * M_PI) + S.logdet + S.quad);
     }
     if (want_grad) {
-        // ---- G = alpha alpha^T - Sigma^-1 (REML: alpha_R alpha_R^T + C C^T - Sigma^-1), lower tiles of the first nend rows
-        const double* avec = h->d_pred + 1;
-        int q_syrk = q;
-        if (fisher) {   // zero start; with trend rows in front of the unit rows the rank-q kernel (it reads `dense`)
-            q_syrk = p > 0 ? 2 : 1;
-            double* d_zero = nullptr;
-            HIPCHK(tmp.get(&d_zero, (size_t)(q_syrk * Np) * 8));
-            HIPCHK(hipMemsetAsync(d_zero, 0, (size_t)(q_syrk * Np) * 8, h->stream));
-            avec = d_zero;
-        } else if (p > 0) {
-            std::vector<double> av((size_t)q * Np, 0.0);
-            for (int64_t r = 0; r < Np; ++r) {
-                const double* wr = &W[(size_t)((q + r) * (q + 1))];   // unit row of internal position r
-                double a = wr[1];
-                for (int j = 0; j < p; ++j) a -= wr[2 + j] * bh[(size_t)j];
-                av[(size_t)r] = a;
-                for (int j = 0; j < p; ++j) {   // C_r = R^-1 B_r (forward substitution)
-                    double c = wr[2 + j];
-                    for (int l = 0; l < j; ++l) c -= R[(size_t)(j * p + l)] * av[(size_t)(1 + l) * Np + r];
-                    av[(size_t)(1 + j) * Np + r] = c / R[(size_t)(j * p + j)];
-                }
-            }
+        // ---- G = alpha alpha^T - Sigma^-1 (REML: alpha_R alpha_R^T + C C^T - Sigma^-1), its contraction and the noise scores
+        const double* start = h->d_pred + 1;
+        std::vector<double> av;
+        if (p > 0) {
+            av.assign((size_t)q * Np, 0.0);
+            ck_host_reml_start(p, Np, S.W.data(), q, S.beta.data(), S.R.data(), av.data());
             double* d_av = nullptr;
             HIPCHK(tmp.get(&d_av, av.size() * 8));
             HIPCHK(hipMemcpyAsync(d_av, av.data(), av.size() * 8, hipMemcpyHostToDevice, h->stream));
-            avec = d_av;
+            start = d_av;
         }
-        if (schur_ensure(h, Np)) return -1;
-        HIPCHK(hipEventRecord(h->ev0, h->stream));
-        ck_launch_ginv_syrk(h->stream, h->sch.d_ptr, h->aux, h->mpad, avec, h->nK, h->nend, q_syrk, Np, q);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(h->ev1, h->stream));
-        if (fisher) {
-            HIPCHK(hipStreamSynchronize(h->stream));
-            h->t_ms[27] = elapsed_ms(h->ev0, h->ev1);
-            h->t_ms[29] = ms_since(t_begin);
-            return 0;
-        }
-        // ---- the contraction: the model's blocks and their nu +- dnu, nu +- 2 dnu neighbours
-        const int nblk = h->n_procs == 1 ? 1 : 3;
-        CkMatern hb[15];
-        double dnu3[3] = {0.0, 0.0, 0.0};
-        const double offs[4] = {-2.0, -1.0, 1.0, 2.0};
-        for (int b = 0; b < 3; ++b) {
-            const CkMatern& m = h->blk[b < nblk ? b : 0];
-            dnu3[b] = ck_matern_dnu_step(m.nu);
-            hb[5 * b] = m;
-            for (int k = 0; k < 4; ++k)
-                ck_matern_prepare(m.nu + offs[k] * dnu3[b], m.len_scale, m.amp, m.nugget, &hb[5 * b + 1 + k]);
-        }
-        HIPCHK(h->d_lik_blk.reserve(sizeof(hb) / sizeof(CkMatern)));
-        HIPCHK(hipMemcpyAsync(h->d_lik_blk, hb, sizeof(hb), hipMemcpyHostToDevice, h->stream));
-        const int64_t ngr = ck_lik_grad_groups(L);
-        double* d_part = nullptr;
-        HIPCHK(tmp.get(&d_part, (size_t)(ngr * CK_LIK_NPAR) * 8));
-        ck_launch_loglik_grad(h->stream, h->sch.d_ptr, L, h->n_procs, h->metric, h->s0, h->d_lik_blk, dnu3, h->par_sigma[0],
-                              h->par_sigma[1], h->par_rho, d_part);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(h->ev2, h->stream));
-        std::vector<double> part((size_t)(ngr * CK_LIK_NPAR));
-        HIPCHK(hipMemcpyAsync(part.data(), d_part, part.size() * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));   // (hb is stack memory)
-        h->t_ms[27] = elapsed_ms(h->ev0, h->ev1);
-        h->t_ms[28] = elapsed_ms(h->ev1, h->ev2);
-        double g[CK_LIK_NPAR] = {};
-        for (int64_t w = 0; w < ngr; ++w)
-            for (int k = 0; k < CK_LIK_NPAR; ++k) g[k] += part[(size_t)(w * CK_LIK_NPAR + k)];
-        for (int k = 0; k < npar; ++k) grad[k] = g[k];
-        // ---- dl/ds_k = 1/2 sum_{a in k} G_aa d_a while G is in the Schur buffers (ck_loglik_noise_grad)
-        h->lik_noise_grad[0] = h->lik_noise_grad[1] = 0.0;
-        if (ensure_noise(h)) return -1;
-        if (!h->noise_var[0].empty() || (h->n_procs == 2 && !h->noise_var[1].empty())) {
-            double* d_np = nullptr;
-            HIPCHK(tmp.get(&d_np, (size_t)(2 * h->nK) * 8));
-            ck_launch_lik_noise_grad(h->stream, h->sch.d_ptr, h->nK, L, h->d_noise + Np, d_np);
-            HIPCHK(hipGetLastError());
-            std::vector<double> np2((size_t)(2 * h->nK));
-            HIPCHK(hipMemcpyAsync(np2.data(), d_np, np2.size() * 8, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            for (int K = 0; K < h->nK; ++K)
-                for (int k = 0; k < 2; ++k) h->lik_noise_grad[k] += np2[(size_t)(2 * K + k)];
-            for (int k = 0; k < 2; ++k) h->lik_noise_grad[k] *= 0.5;
-        }
-        h->lik_noise_valid = true;
+        if (lik_ginv(h, start, q, q)) return -1;
+        if (lik_contract(h, tmp, npar, grad, &t[28])) return -1;
+        t[27] = lik_ginv_ms(h);
+        if (lik_noise_scores(h, tmp)) return -1;
     }
-    h->t_ms[29] = ms_since(t_begin);
+    t[29] = ms_since(t_begin);
     return 0;
 }
 
 extern "C" int ck_loglik(ck_handle* h, int want_grad, double* out3, double* grad, int64_t* info) {
     CHKH(h);
-    return loglik_impl(h, want_grad, false, out3, grad, info);
+    return loglik_value_grad(h, "ck_loglik", false, want_grad, out3, grad, info);
 }
 
 extern "C" int ck_loglik_reml(ck_handle* h, int want_grad, double* out4, double* grad, int64_t* info) {
     CHKH(h);
-    return loglik_impl(h, want_grad, true, out4, grad, info);
+    return loglik_value_grad(h, "ck_loglik_reml", true, want_grad, out4, grad, info);
 }
 
 extern "C" int ck_loglik_noise_grad(ck_handle* h, double* out2) {
@@ -3170,25 +3213,20 @@ extern "C" int ck_loglik_noise_grad(ck_handle* h, double* out2) {
 // ---------------------------------------------------------------------------------------
 // Fisher information of the likelihood fit (ck_fisher.hip)
 // ---------------------------------------------------------------------------------------
-// I_jk = 1/2 tr(Sigma^-1 D_j Sigma^-1 D_k) in the plain form.  loglik_impl's sweep leaves -Sigma^-1 in the Schur buffers (zero
+// I_jk = 1/2 tr(Sigma^-1 D_j Sigma^-1 D_k) in the plain form.  lik_sweep and lik_ginv leave -Sigma^-1 in the Schur buffers (zero
 // start); it is expanded to full K-panels, the derivative operands (ck_internal.h: CK_FOP_*) are assembled as the product
 // kernel's second operand, B_a = -Sigma^-1 D_a runs on the trailing updates' tile restricted to the operand's block (N^3 / 2
 // flop for an operand inside one process of a half-and-half model, N^3 for a cross operand), and one contraction kernel takes
 // all wanted pairs to per-workgroup partial sums.  The products of all operands are kept when they fit; otherwise the operands
 // are cut into groups of at most half the free memory, and the pairs across two groups are contracted with the later group's
 // products formed again (memory first: the need is computed in front of the first allocation).
-struct FisherUnit {
-    int op, r, kp;   // operand, process of its columns, process of its K-panels
-    int64_t d_doubles;
-};
+static_assert(CK_HOST_FOP_R11 == CK_FOP_R11 && CK_HOST_FOP_R01 == CK_FOP_R01 && CK_HOST_FOP_DIAG0 == CK_FOP_DIAG0 &&
+                  CK_HOST_FISHER_YROWS == CK_FISHER_YROWS && CK_HOST_FISHER_NOPS == CK_FISHER_NOPS,
+              "ck_host.h and ck_internal.h disagree about the Fisher operands");
 extern "C" int ck_loglik_fisher(ck_handle* h, int reml, const int32_t* free13, double* fisher, int64_t* info) {
     CHKH(h);
     const char* name = "ck_loglik_fisher";
-    if (!fisher || !info) return fail(std::string(name) + ": null argument");
-    if (h->world != 1)
-        return fail(std::string(name) + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) +
-                    "); the multi-GPU likelihood is not available");
-    if (!h->assembled) return fail(std::string(name) + ": ck_assemble_joint has not been called");
+    if (lik_admit(h, name, !fisher || !info)) return -1;
     const auto t_begin = std::chrono::steady_clock::now();
     const int NP = CK_FISHER_NPAR, NO = CK_FISHER_NOPS;
     *info = 0;
@@ -3198,101 +3236,60 @@ extern "C" int ck_loglik_fisher(ck_handle* h, int reml, const int32_t* free13, d
     const int p = reml ? trend_total(h) : 0;
     // ---- live slots and the operands they need
     unsigned char live[CK_FISHER_NPAR] = {};
-    const int npar = h->n_procs == 1 ? 4 : CK_LIK_NPAR;
-    for (int k = 0; k < npar; ++k) live[k] = 1;
-    if (!h->noise_var[0].empty()) live[11] = 1;
-    if (h->n_procs == 2 && !h->noise_var[1].empty()) live[12] = 1;
-    if (free13)
-        for (int k = 0; k < NP; ++k) live[k] = live[k] && free13[k] != 0;
+    const unsigned live_mask = live_slots(h, free13);
+    for (int k = 0; k < NP; ++k) live[k] = live_mask >> k & 1u;
     double coef[CK_FISHER_NPAR * CK_FISHER_NOPS];
     ck_host_fisher_coef(h->n_procs, h->par_sigma[0], h->par_sigma[1], h->par_rho, coef);
     bool op_live[CK_FISHER_NOPS] = {};
     for (int k = 0; k < NP; ++k)
         for (int a = 0; a < NO; ++a)
             if (live[k] && coef[k * NO + a] != 0.0) op_live[a] = true;
-    // ---- geometry of the units: columns (c0, wpad, nlo, nhi) and K-panels (pK0, npan) of process 0 / 1
-    int64_t c0[2] = {0, 0}, wpad[2] = {Np, 0}, nlo[2] = {0, 0}, nhi[2] = {Np, 0};
-    int pK0[2] = {0, 0}, npan[2] = {nK, 0};
-    if (h->n_procs == 2) {
-        wpad[0] = roundup(h->n0p, 128), nhi[0] = h->n0p, npan[0] = (int)((h->n0p + CK_NB - 1) / CK_NB);
-        c0[1] = h->n0p / 128 * 128, wpad[1] = Np - c0[1], nlo[1] = h->n0p, nhi[1] = Np;
-        pK0[1] = (int)(h->n0p / CK_NB), npan[1] = nK - pK0[1];
-    }
-    std::vector<FisherUnit> units;
-    int64_t b_doubles[CK_FISHER_NOPS] = {};
-    int64_t d_total = 0, b_total = 0, b_max = 0;
-    for (int a = 0; a < CK_FOP_DIAG0; ++a) {
-        if (!op_live[a]) continue;
-        if (a < CK_FOP_R01) {
-            const int r = a < CK_FOP_R11 ? 0 : 1;
-            units.push_back({a, r, r, (int64_t)npan[r] * wpad[r] * CK_NB});
-            b_doubles[a] = Np * wpad[r];
-        } else {
-            units.push_back({a, 0, 1, (int64_t)npan[1] * wpad[0] * CK_NB});
-            units.push_back({a, 1, 0, (int64_t)npan[0] * wpad[1] * CK_NB});
-            b_doubles[a] = Np * Np;
-        }
-        b_total += b_doubles[a];
-        b_max = std::max(b_max, b_doubles[a]);
-    }
-    for (const auto& u : units) d_total += u.d_doubles;
-    // ---- memory, in front of the first allocation: what loglik_impl's gradient path takes (as it computes it), Sigma^-1, the
-    // operands, the thin REML terms and the partial sums are needed whole; the products in as many groups as fit
+    // ---- memory, in front of the first allocation: the unit-row sweep and G as ck_loglik's gradient takes them; Sigma^-1, the
+    // operands, the thin REML terms and the partial sums whole; the products in as many groups as fit (ck_host_fisher_plan)
+    CkMemAdmit adm;
+    if (lik_mem_admit(h, name, p, &adm)) return -1;
+    CkFisherPlan P;
+    if (ck_host_fisher_plan(h->n_procs, Np, h->n0p, nK, op_live, adm.avail - adm.need, p, ck_fisher_contract_groups(Np),
+                            h->fisher_product_mb << 20, &P))
+        return fail(std::string(name) + ": needs " + std::to_string(adm.need + P.fixed_bytes + 2 * P.b_max * 8) +
+                    " bytes of device memory (" + std::to_string(adm.need) + " for the unit-row sweep and Sigma^-1's triangle, " +
+                    std::to_string(Np * Np * 8) + " for Sigma^-1 in full, " + std::to_string(P.d_total * 8) + " for " +
+                    std::to_string(P.units.size()) + " derivative operands, " + std::to_string(2 * P.b_max * 8) +
+                    " for two of their products); " + std::to_string(adm.avail) + " bytes are available");
+    const std::vector<CkFisherUnit0>& units = P.units;
+    const std::vector<std::vector<int>>& groups = P.groups;
+    const int64_t *c0 = P.c0, *wpad = P.wpad, *nlo = P.nlo, *nhi = P.nhi, *b_doubles = P.b_doubles, region = P.region;
+    const int *pK0 = P.pK0, *npan = P.npan;
     const int64_t ngr = ck_fisher_contract_groups(Np);
-    const int64_t thin = p > 0 ? ((int64_t)nK * CK_FISHER_YROWS * CK_NB + Np * CK_FISHER_YROWS + Np * p + CK_FISHER_YROWS * (CK_FISHER_YROWS + p)) : 0;
-    const int64_t fixed_bytes = (Np * Np + d_total + thin + ngr * CK_FISHER_NPAIR + 2 * Np) * 8 + (1 << 20);
-    int64_t lik_bytes = 0;
-    {
-        int64_t g_bytes = 0;
-        for (int J = 0; J < nK; ++J) g_bytes += ((Np - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;
-        const int64_t aux_bytes = roundup(Np + 1 + p, CK_AUX_ALIGN) * Np * 8;
-        lik_bytes = (aux_bytes > aux_cap(h) * 8 ? aux_bytes : 0) + (h->sch.M == Np ? 0 : g_bytes);
-    }
-    size_t fr = 0, tot = 0;
-    HIPCHK(hipMemGetInfo(&fr, &tot));
-    int64_t avail = (int64_t)fr;
-    if (!h->arena && roundup(Np + 1 + p, CK_AUX_ALIGN) * Np > aux_cap(h)) avail += aux_cap(h) * 8;
-    if (h->sch.M != Np)
-        for (int J = 0; J < (int)h->sch.sig.size(); ++J) avail += ((h->sch.M - (int64_t)J * CK_NB) * CK_NB + CK_PANEL_TAIL) * 8;
-    int64_t room = avail - lik_bytes - fixed_bytes;
-    if (h->fisher_product_mb > 0 && room > 0) room = std::min(room, h->fisher_product_mb << 20);
-    std::vector<std::vector<int>> groups(1);
-    int64_t region = b_total;
-    if (b_total * 8 > room) {
-        region = room / 16;   // two regions of products, doubles each
-        if (room < 0 || b_max > region)
-            return fail(std::string(name) + ": needs " + std::to_string(lik_bytes + fixed_bytes + 2 * b_max * 8) +
-                        " bytes of device memory (" + std::to_string(lik_bytes) + " for the unit-row sweep and Sigma^-1's triangle, " +
-                        std::to_string(Np * Np * 8) + " for Sigma^-1 in full, " + std::to_string(d_total * 8) + " for " +
-                        std::to_string(units.size()) + " derivative operands, " + std::to_string(2 * b_max * 8) +
-                        " for two of their products); " + std::to_string(avail) + " bytes are available");
-        int64_t used = 0, big = 0;
-        for (int a = 0; a < CK_FOP_DIAG0; ++a) {
-            if (!op_live[a]) continue;
-            if (used + b_doubles[a] > region && !groups.back().empty()) {
-                groups.emplace_back();
-                used = 0;
-            }
-            groups.back().push_back(a);
-            used += b_doubles[a];
-            big = std::max(big, used);
-        }
-        region = big;
-    } else {
-        for (int a = 0; a < CK_FOP_DIAG0; ++a)
-            if (op_live[a]) groups.back().push_back(a);
-    }
     // ---- the sweep: factor, unit rows, -Sigma^-1 in the Schur buffers (and A, H of REML)
-    double out4[4], gdummy[CK_LIK_NPAR];
-    if (loglik_impl(h, 1, reml != 0, out4, gdummy, info, true)) return -1;
-    for (int k = 64; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
-    if (*info != 0) {
-        h->t_ms[67] = ms_since(t_begin);
+    CallGuard guard(h, AUX_LOGLIK, true);
+    double* t = h->t_ms;
+    for (int k = 24; k < CK_N_TIMINGS; ++k) t[k] = 0.0;
+    DevTemps tmp;
+    LikSweep S;
+    {
+        const int rc = lik_sweep(h, tmp, name, true, p, true, &S);
+        *info = S.info;
+        if (rc) return -1;
+    }
+    t[24] = t[0];
+    if (S.factored_here) t[25] = t[1];
+    if (S.info != 0) {
+        t[29] = t[67] = ms_since(t_begin);
         return 0;
     }
-    CallGuard guard(h, AUX_LOGLIK, true);
+    t[26] = S.sweep_ms;
+    {
+        const int q_syrk = p > 0 ? 2 : 1;
+        double* d_zero = nullptr;
+        HIPCHK(tmp.get(&d_zero, (size_t)(q_syrk * Np) * 8));
+        HIPCHK(hipMemsetAsync(d_zero, 0, (size_t)(q_syrk * Np) * 8, h->stream));
+        if (lik_ginv(h, d_zero, q_syrk, 1 + p)) return -1;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        t[27] = lik_ginv_ms(h);
+        t[29] = ms_since(t_begin);
+    }
     const CkLayout L = layout_of(h);
-    DevTemps tmp;
     if (ensure_noise(h)) return -1;
     double *d_Sp = nullptr, *d_part = nullptr, *d_reg[2] = {nullptr, nullptr};
     HIPCHK(tmp.get(&d_Sp, (size_t)(Np * Np) * 8));
@@ -3312,25 +3309,15 @@ extern "C" int ck_loglik_fisher(ck_handle* h, int reml, const int32_t* free13, d
     for (int r = 0; r < 2; ++r) A.c0[r] = c0[r], A.wpad[r] = wpad[r], A.pK0[r] = pK0[r];
     for (size_t u = 0; u < units.size(); ++u) A.D[units[u].op][units[u].r] = d_D[u];
     if (!units.empty()) {
-        const int nblk = h->n_procs == 1 ? 1 : 3;
-        CkMatern hb[15];
         double dnu3[3] = {0.0, 0.0, 0.0};
-        const double offs[4] = {-2.0, -1.0, 1.0, 2.0};
-        for (int b = 0; b < 3; ++b) {   // the blocks and their nu +- dnu, nu +- 2 dnu neighbours, as loglik_impl prepares them
-            const CkMatern& m = h->blk[b < nblk ? b : 0];
-            dnu3[b] = ck_matern_dnu_step(m.nu);
-            hb[5 * b] = m;
-            for (int k = 0; k < 4; ++k) ck_matern_prepare(m.nu + offs[k] * dnu3[b], m.len_scale, m.amp, m.nugget, &hb[5 * b + 1 + k]);
-        }
-        HIPCHK(h->d_lik_blk.reserve(sizeof(hb) / sizeof(CkMatern)));
-        HIPCHK(hipMemcpyAsync(h->d_lik_blk, hb, sizeof(hb), hipMemcpyHostToDevice, h->stream));
+        if (lik_blocks(h, dnu3)) return -1;
         ck_launch_fisher_assemble(h->stream, A, L, h->n_procs, h->metric, h->s0, h->d_lik_blk, dnu3);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(h->stream));   // (hb is stack memory)
+        HIPCHK(hipStreamSynchronize(h->stream));
     }
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->t_ms[64] = elapsed_ms(h->ev0, h->ev1);
+    t[64] = elapsed_ms(h->ev0, h->ev1);
     // ---- products and contraction, group by group
     const CkFisherCtx X{d_Sp, h->d_noise ? h->d_noise + Np : nullptr, Np, h->n_procs == 2 ? h->n0p : Np, h->n_procs};
     double T[CK_FISHER_NOPS * CK_FISHER_NOPS] = {};
@@ -3416,7 +3403,7 @@ extern "C" int ck_loglik_fisher(ck_handle* h, int reml, const int32_t* free13, d
         HIPCHK(tmp.get(&d_V, (size_t)(Np * CK_FISHER_YROWS) * 8));
         HIPCHK(tmp.get(&d_K, (size_t)(CK_FISHER_YROWS * (CK_FISHER_YROWS + p)) * 8));
         HIPCHK(hipEventRecord(h->ev0, h->stream));
-        HIPCHK(hipMemcpyAsync(d_H, h->fi_H.data(), (size_t)(Np * p) * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_H, S.H.data(), (size_t)(Np * p) * 8, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemsetAsync(d_Yp, 0, (size_t)yp_doubles * 8, h->stream));
         HIPCHK(hipMemsetAsync(d_V, 0, (size_t)(Np * CK_FISHER_YROWS) * 8, h->stream));
         for (size_t u = 0; u < units.size(); ++u) {
@@ -3439,7 +3426,7 @@ extern "C" int ck_loglik_fisher(ck_handle* h, int reml, const int32_t* free13, d
         HIPCHK(hipStreamSynchronize(h->stream));
         h->t_ms[65] += elapsed_ms(h->ev0, h->ev1);
         for (size_t k = 0; k < (size_t)(CK_FISHER_YROWS * CK_FISHER_YROWS); ++k) Kh[k] = -Kh[k];   // V holds -Sigma^-1 Y
-        if (ck_host_fisher_reml(p, NO, h->fi_A.data(), Kh.data(), CK_FISHER_YROWS, Kh.data() + CK_FISHER_YROWS * CK_FISHER_YROWS, T))
+        if (ck_host_fisher_reml(p, NO, S.A.data(), Kh.data(), CK_FISHER_YROWS, Kh.data() + CK_FISHER_YROWS * CK_FISHER_YROWS, T))
             return fail(std::string(name) + ": X^T Sigma^-1 X did not factor");
     }
     ck_host_fisher_combine(coef, T, live, fisher);
@@ -4093,25 +4080,10 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
     // live slots (ck_loglik_fisher's rule) and the operands of the contraction (ck_loglik's)
     CkVecchiaGradArgs A{};
     CkVecchiaModel& V = A.V;
-    const int npar = h->n_procs == 1 ? 4 : CK_LIK_NPAR;
-    for (int k = 0; k < npar; ++k) V.live |= 1u << k;
-    if (!h->noise_var[0].empty()) V.live |= 1u << 11;
-    if (h->n_procs == 2 && !h->noise_var[1].empty()) V.live |= 1u << 12;
-    if (free13)
-        for (int k = 0; k < NP; ++k)
-            if (free13[k] == 0) V.live &= ~(1u << k);
-    const int nblk3 = h->n_procs == 1 ? 1 : 3;
-    CkMatern hb[15];
-    const double offs[4] = {-2.0, -1.0, 1.0, 2.0};
-    for (int b = 0; b < 3; ++b) {
-        const CkMatern& m = h->blk[b < nblk3 ? b : 0];
-        V.dnu[b] = ck_matern_dnu_step(m.nu);
-        hb[5 * b] = m;
-        for (int k = 0; k < 4; ++k) ck_matern_prepare(m.nu + offs[k] * V.dnu[b], m.len_scale, m.amp, m.nugget, &hb[5 * b + 1 + k]);
-        if (b < nblk3 && (V.live >> ck_vg_nu_slot(h->n_procs, b) & 1u)) V.nu_live |= 1u << b;
-    }
-    HIPCHK(h->d_lik_blk.reserve(sizeof(hb) / sizeof(CkMatern)));
-    HIPCHK(hipMemcpyAsync(h->d_lik_blk, hb, sizeof(hb), hipMemcpyHostToDevice, h->stream));
+    V.live = live_slots(h, free13);
+    for (int b = 0; b < (h->n_procs == 1 ? 1 : 3); ++b)
+        if (V.live >> ck_vg_nu_slot(h->n_procs, b) & 1u) V.nu_live |= 1u << b;
+    if (lik_blocks(h, V.dnu)) return -1;
     V.blk5 = h->d_lik_blk;
     V.sig1 = h->par_sigma[0];
     V.sig2 = h->par_sigma[1];
@@ -4648,7 +4620,7 @@ extern "C" int ck_debug_coop_profile(ck_handle* h, int64_t rows, double* out64) 
     DevTemps tmp;
     double *dP = nullptr;
     long long *dprof = nullptr, *dinfo = nullptr;
-    HIPCHK(tmp.get(&dP, (size_t)(rows * CK_NB + CK_PANEL_TAIL) * 8));
+    HIPCHK(tmp.get(&dP, (size_t)panel_payload(rows, 0)));
     HIPCHK(tmp.get(&dprof, 64 * 8));
     HIPCHK(tmp.get(&dinfo, 8));
     std::vector<double> A((size_t)rows * CK_NB);
@@ -4695,7 +4667,7 @@ extern "C" int ck_debug_stream_overlap(ck_handle* h, int mode, int64_t rows, int
     DevTemps tmp;
     double* dP = nullptr;
     long long* dinfo = nullptr;
-    HIPCHK(tmp.get(&dP, (size_t)(rows * CK_NB + CK_PANEL_TAIL) * 8));
+    HIPCHK(tmp.get(&dP, (size_t)panel_payload(rows, 0)));
     HIPCHK(tmp.get(&dinfo, 8));
     std::vector<double> A((size_t)rows * CK_NB);
     for (int64_t i = 0; i < rows; ++i)

@@ -538,6 +538,108 @@ int ck_host_fisher_reml(int p, int nops, const double* A, const double* K, int64
     return 0;
 }
 
+int ck_host_fisher_plan(int n_procs, int64_t Npad, int64_t n0p, int nK, const bool* op_live, int64_t room, int p, int64_t ngr,
+                        int64_t cap, CkFisherPlan* out) {
+    const int64_t NB = CK_HOST_NB, Np = Npad, YR = CK_HOST_FISHER_YROWS;
+    CkFisherPlan& P = *out;
+    P = CkFisherPlan();
+    for (int r = 0; r < 2; ++r) P.c0[r] = P.wpad[r] = P.nlo[r] = P.nhi[r] = 0, P.pK0[r] = P.npan[r] = 0;
+    P.wpad[0] = P.nhi[0] = Np, P.npan[0] = nK;
+    if (n_procs == 2) {
+        P.wpad[0] = (n0p + 127) / 128 * 128, P.nhi[0] = n0p, P.npan[0] = (int)((n0p + NB - 1) / NB);
+        P.c0[1] = n0p / 128 * 128, P.wpad[1] = Np - P.c0[1], P.nlo[1] = n0p, P.nhi[1] = Np;
+        P.pK0[1] = (int)(n0p / NB), P.npan[1] = nK - P.pK0[1];
+    }
+    for (int a = 0; a < CK_HOST_FISHER_NOPS; ++a) P.b_doubles[a] = 0;
+    for (int a = 0; a < CK_HOST_FOP_DIAG0; ++a) {
+        if (!op_live[a]) continue;
+        if (a < CK_HOST_FOP_R01) {
+            const int r = a < CK_HOST_FOP_R11 ? 0 : 1;
+            P.units.push_back({a, r, r, (int64_t)P.npan[r] * P.wpad[r] * NB});
+            P.b_doubles[a] = Np * P.wpad[r];
+        } else {
+            P.units.push_back({a, 0, 1, (int64_t)P.npan[1] * P.wpad[0] * NB});
+            P.units.push_back({a, 1, 0, (int64_t)P.npan[0] * P.wpad[1] * NB});
+            P.b_doubles[a] = Np * Np;
+        }
+        P.b_total += P.b_doubles[a];
+        P.b_max = std::max(P.b_max, P.b_doubles[a]);
+    }
+    for (const auto& u : P.units) P.d_total += u.d_doubles;
+    const int64_t thin = p > 0 ? (int64_t)nK * YR * NB + Np * YR + Np * p + YR * (YR + p) : 0;
+    const int64_t npair = CK_HOST_FISHER_NOPS * (CK_HOST_FISHER_NOPS + 1) / 2;
+    P.fixed_bytes = (Np * Np + P.d_total + thin + ngr * npair + 2 * Np) * 8 + (1 << 20);
+    room -= P.fixed_bytes;
+    if (cap > 0 && room > 0) room = std::min(room, cap);
+    P.region = P.b_total;
+    P.groups.assign(1, {});
+    if (P.b_total * 8 <= room) {
+        for (int a = 0; a < CK_HOST_FOP_DIAG0; ++a)
+            if (op_live[a]) P.groups.back().push_back(a);
+        return 0;
+    }
+    P.region = room / 16;   // two regions of products, doubles each
+    if (room < 0 || P.b_max > P.region) {
+        P.region = 0;
+        P.groups.clear();
+        return 1;
+    }
+    int64_t used = 0, big = 0;
+    for (int a = 0; a < CK_HOST_FOP_DIAG0; ++a) {
+        if (!op_live[a]) continue;
+        if (used + P.b_doubles[a] > P.region && !P.groups.back().empty()) {
+            P.groups.emplace_back();
+            used = 0;
+        }
+        P.groups.back().push_back(a);
+        used += P.b_doubles[a];
+        big = std::max(big, used);
+    }
+    P.region = big;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// REML: the rank-(1 + p) start of G from the reduced unit rows
+// ---------------------------------------------------------------------------------------
+void ck_host_reml_start(int p, int64_t Npad, const double* W, int q, const double* beta, const double* R, double* av) {
+    for (int64_t r = 0; r < Npad; ++r) {
+        const double* wr = &W[(size_t)((q + r) * (q + 1))];   // unit row of internal position r
+        double a = wr[1];
+        for (int j = 0; j < p; ++j) a -= wr[2 + j] * beta[j];
+        av[(size_t)r] = a;
+        for (int j = 0; j < p; ++j) {   // C_r = R^-1 B_r (forward substitution)
+            double c = wr[2 + j];
+            for (int l = 0; l < j; ++l) c -= R[(size_t)(j * p + l)] * av[(size_t)(1 + l) * Npad + r];
+            av[(size_t)(1 + j) * Npad + r] = c / R[(size_t)(j * p + j)];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// device memory admission: free memory plus what the call releases first, against what it must take
+// ---------------------------------------------------------------------------------------
+CkMemAdmit ck_host_mem_admit(const CkMemState& st, const CkMemAsk& ask) {
+    CkMemAdmit r = {ask.extra_bytes, st.free_bytes, false};
+    if (ask.rhs_bytes > st.rhs_bytes) {
+        if (st.arena) {
+            r.arena_short = ask.rhs_bytes > st.arena_size - st.arena_used;
+        } else {
+            r.need += ask.rhs_bytes;
+            r.avail += st.rhs_bytes;   // released before the larger one is taken
+        }
+    }
+    if (ask.schur_order > 0 && ask.schur_order != st.schur_order) {
+        r.need += ck_host_schur_bytes(ask.schur_order);
+        r.avail += ck_host_schur_bytes(st.schur_order);   // schur_ensure releases these first
+    }
+    if (ask.slab_bytes > st.slab_bytes) {
+        r.need += ask.slab_bytes;
+        r.avail += st.slab_bytes;
+    }
+    return r;
+}
+
 // ---------------------------------------------------------------------------------------
 // leave-group-out cross-validation: members, gather list, tile map and system offsets of the folds
 // ---------------------------------------------------------------------------------------

@@ -105,6 +105,75 @@ CK_HIDDEN void ck_host_fisher_combine(const double* C, const double* T, const un
 // triangle read).  Returns 0, or 1 + the column at which A failed to factor.
 CK_HIDDEN int ck_host_fisher_reml(int p, int nops, const double* A, const double* K, int64_t ldk, const double* Gm, double* T);
 
+// ck_loglik_fisher's plan, pure arithmetic: the geometry of the derivative operands, the doubles of their products B_a =
+// -Sigma^-1 D_a, and the products cut into groups that fit.  A unit is one launch's operand: the columns of process r
+// (c0 rounded DOWN to 128, wpad columns, the live ones in [nlo, nhi)) times the K-panels of process kp (pK0, npan); an operand
+// inside a process has one unit, a cross operand two.  op_live[CK_HOST_FISHER_NOPS]: the diagonal operands (11, 12) have no unit
+// and no product.  room: the bytes the call may take beside the unit-row sweep (may be negative); fixed_bytes -- Sigma^-1 in
+// full, the operands, the thin REML terms of p trend columns, `ngr` workgroups' partial sums, a margin -- comes off it first,
+// cap (bytes, 0: none) bounds what is left for the products.  All products fit: one group, region = their doubles.  Otherwise
+// two regions of room / 16 doubles each hold a group apiece: the operands in order, a new group where the next product does not
+// fit; region = the largest group.  Returns 0, or 1 when two of the largest product (b_max) do not fit: groups is empty, and
+// the caller words the refusal from fixed_bytes, d_total and b_max.
+#define CK_HOST_NB 512                    // == CK_NB (ck_internal.h)
+#define CK_HOST_PANEL_TAIL (8 * 64 * 64)  // == CK_PANEL_TAIL
+#define CK_HOST_FOP_R11 4                 // == CK_FOP_R11, CK_FOP_R01, CK_FOP_DIAG0
+#define CK_HOST_FOP_R01 8
+#define CK_HOST_FOP_DIAG0 11
+#define CK_HOST_FISHER_YROWS 256          // == CK_FISHER_YROWS
+struct CkFisherUnit0 {
+    int op, r, kp;   // operand, process of its columns, process of its K-panels
+    int64_t d_doubles;
+};
+struct CkFisherPlan {
+    int64_t c0[2], wpad[2], nlo[2], nhi[2];
+    int pK0[2], npan[2];
+    std::vector<CkFisherUnit0> units;
+    int64_t b_doubles[CK_HOST_FISHER_NOPS];
+    int64_t d_total = 0, b_total = 0, b_max = 0, fixed_bytes = 0, region = 0;
+    std::vector<std::vector<int>> groups;
+};
+CK_HIDDEN int ck_host_fisher_plan(int n_procs, int64_t Npad, int64_t n0p, int nK, const bool* op_live, int64_t room, int p,
+                                  int64_t ngr, int64_t cap, CkFisherPlan* out);
+
+// ---- the REML gradient's start vectors (ck_api.hip: ck_loglik_reml) ---------------------------------------------------
+// W: the reduced rows of the sweep, q + 1 = p + 2 doubles each (|row|^2, row . y, row . U_0 .. U_p-1); row q + r is the unit
+// row of internal position r < Npad, so W[q + r] = (., alpha_r, B_r).  av (q x Npad, row-major) <- row 0: alpha_R = alpha -
+// B beta; rows 1 .. p: C = R^-1 B^T by forward substitution (A = R R^T, R lower, p x p row-major).  A padding position's row
+// goes through the same arithmetic.
+CK_HIDDEN void ck_host_reml_start(int p, int64_t Npad, const double* W, int q, const double* beta, const double* R, double* av);
+
+// ---- device memory admission (ck_api.hip: mem_admit) -------------------------------------------------------------------
+// bytes of panel K of a packed lower triangle of order Np: its rows with the diagonal blocks' inverses behind them
+static inline int64_t ck_host_panel_payload(int64_t Np, int K) {
+    return ((Np - (int64_t)K * CK_HOST_NB) * CK_HOST_NB + CK_HOST_PANEL_TAIL) * 8;
+}
+// the packed triangle of order Mp (a multiple of CK_NB) | with the 8 Mp doubles of site arrays schur_ensure allocates beside it
+static inline int64_t ck_host_tri_bytes(int64_t Mp) {
+    int64_t b = 0;
+    for (int K = 0; (int64_t)K * CK_HOST_NB < Mp; ++K) b += ck_host_panel_payload(Mp, K);
+    return b;
+}
+static inline int64_t ck_host_schur_bytes(int64_t Mp) { return Mp > 0 ? ck_host_tri_bytes(Mp) + 8 * Mp * 8 : 0; }
+// One rule for every call that grows the handle's buffers: free memory plus what the call releases first, against what it must
+// take.  A buffer that does not grow (right-hand sides and slab: the ask is not above what is held; Schur buffers: the same
+// order, or order 0 = not wanted) adds nothing to either side.  Right-hand sides of an arena handle come out of the arena's
+// rest and never count against free memory: arena_short says they do not fit there.  extra_bytes: the call's temporaries.
+struct CkMemState {
+    int64_t free_bytes;
+    bool arena;
+    int64_t arena_size, arena_used;
+    int64_t rhs_bytes, schur_order, slab_bytes;   // held
+};
+struct CkMemAsk {
+    int64_t rhs_bytes, schur_order, slab_bytes, extra_bytes;
+};
+struct CkMemAdmit {
+    int64_t need, avail;
+    bool arena_short;
+};
+CK_HIDDEN CkMemAdmit ck_host_mem_admit(const CkMemState& st, const CkMemAsk& ask);
+
 // ---- tiled local systems: their geometry (ck_internal.h has the layout) and ck_predict_local's plan -----------------------
 struct CkLocalSys {
     long long off;      // doubles into the slab

@@ -474,3 +474,35 @@ def test_growing_sequence_and_handle_life_cycle(native):
     assert a.factor() == 0
     assert same([a.predict(0, sites[m]) for m in (700, 5, 700)], want)
     a.close()
+
+
+def test_arena_refusal_leaves_the_handle_usable(native):
+    """an arena of estimate_bytes(700) has no room for the gradient's Npad + 1 unit rows: the call is refused in front of its first
+    allocation, with the amounts, and the handle goes on giving the bits it gave before"""
+    import re
+    import torch
+    ds = dc.data_set(dc.REFIT)
+    p = ds.p
+    sites = dc.pred_sites(np.random.default_rng(66), ds.metric, 700)
+    a = native.Handle(0)
+    a.set_model(2, p.sigma, [p.nu[0, 0], p.nu[0, 1], p.nu[1, 1]], [p.len_scale[0, 0], p.len_scale[0, 1], p.len_scale[1, 1]],
+                p.nugget, p.rho)
+    a.set_metric(ds.metric)
+    for k in range(2):
+        a.set_data(k, ds.coords[k], ds.values[k])
+    nbytes = a.estimate_bytes(700)
+    arena = torch.empty(nbytes, dtype=torch.uint8, device="cuda:0")
+    a.set_arena(arena.data_ptr(), nbytes, keepalive=arena)
+    a.assemble_joint()
+    assert a.factor() == 0
+    pred = a.predict(0, sites)
+    value = a.loglik(False)
+    assert value[0] == 0 and same(a.predict(0, sites), pred)
+    with pytest.raises(native.NativeError, match="of the arena") as err:
+        a.loglik(True)
+    rows = int(re.search(r"for its (\d+) right-hand-side rows", str(err.value)).group(1))
+    N = sum(len(c) for c in ds.coords)
+    assert rows > N and (rows - 1) % 512 == 0       # Npad + 1: the data row and the unit row of every internal position
+    assert same(a.loglik(False), value)
+    assert same(a.predict(0, sites), pred)
+    a.close()

@@ -302,3 +302,44 @@ def test_fit_likelihood_std_errors(native):
     x = mod.params.get_values().astype(float)
     ref3 = reference(x, coords, HAV)[:3, :3]
     assert np.max(np.abs(r.std_error.values[:3] / np.sqrt(np.diag(np.linalg.inv(ref3))) - 1)) <= 1e-5
+
+
+def test_nothing_of_a_sweep_stays_on_the_handle(native):
+    """Fisher REML -> loglik_reml with gradient -> Fisher ML -> loglik with gradient -> Fisher REML on ONE handle: every result
+    (and loglik_noise_grad behind each gradient) has the bits of the same call on a fresh handle.  BIV-300-333 with a
+    two-column trend: Npad = 1024, two panels, the process boundary off every tile edge; noise on process 0, so that the noise
+    scores are not identically zero"""
+    coords, values, _ = case("BIV-300-333", 21, BIV, HAV, 300, 333)
+    F, X = _trend_rows("constant", coords)
+    assert X.shape[1] == 2
+    noise = np.random.default_rng(5).uniform(0.01, 0.1, len(coords[0]))
+
+    def fresh():
+        h = handle(native, BIV, coords, values, HAV)
+        for k in range(2):
+            h.set_trend(k, F[k])
+        h.set_noise(0, noise, 1.7)
+        h.assemble_joint()
+        return h
+
+    def grad_call(reml):
+        def call(h):
+            r = h.loglik_reml(True) if reml else h.loglik(True)
+            return r[0], tuple(r[1]), r[2], h.loglik_noise_grad()
+        return call
+
+    steps = [("fisher reml", lambda h: h.fisher(reml=True)), ("loglik_reml grad", grad_call(True)),
+             ("fisher ml", lambda h: h.fisher()), ("loglik grad", grad_call(False)), ("fisher reml again", lambda h: h.fisher(reml=True))]
+
+    def flat(r):
+        return np.concatenate([np.atleast_1d(np.asarray(x, dtype=float)).ravel() for x in r])
+
+    h = fresh()
+    for name, step in steps:
+        got = flat(step(h))
+        f = fresh()
+        want = flat(step(f))
+        f.close()
+        assert np.all(np.isfinite(got)), name
+        assert got.tobytes() == want.tobytes(), name
+    h.close()
