@@ -372,6 +372,38 @@ int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, double max_di
                            double* out3, double* grad13, double* score_host /* N x 13 or NULL */,
                            int64_t* stats3 /* n_empty, k_max, n_capped */, int64_t* info);
 
+/* The expected information of the Vecchia likelihood, for conditioning sets of at most 64 data: the uncertainty that goes with a
+ * Vecchia fit.  The Vecchia value is sum_t [log p(z_S) - log p(z_c)], c = c(t) the set of datum t and S = c + {t}; every term is a
+ * Gaussian marginal of the exact model, so the expected negative Hessian of the value under the model is
+ *     I^V = sum_t [I(S_t) - I(c_t)],   I(A)_jk = 1/2 tr(C_A^-1 D_j,A C_A^-1 D_k,A),   D_j = dC_t / dtheta_j,
+ * C_t the (k + 1) x (k + 1) covariance of the set and the OBSERVATION (ck_set_noise's s d on its diagonal, the datum's own
+ * included).  This is the expected information of the Vecchia OBJECTIVE under the exact model -- what GpGp reports with its
+ * fits -- and not a Godambe sandwich: that needs the covariances of the scores across data (score_host of
+ * ck_loglik_vecchia_grad serves an empirical version).  The datum is the last row of S_t, so the difference collapses onto the
+ * last row of L_t^-1 D_j L_t^-T: with Sigma_loc = L L^T, w = Sigma_loc^-1 c, b = (-w, 1) and s_t^2 of ck_loglik_vecchia,
+ *     g_j = (D_j b)[c],   q_j = b^T D_j b (= ds_t^2 / dtheta_j),   y_j = L^-1 g_j,
+ *     I_t[j, k] = (y_j . y_k) / s_t^2 + 1/2 q_j q_k / s_t^4;     an empty set: 1/2 q_j q_k / s_t^4, q_j the derivative of the
+ * prior observation variance.  Every I_t is a Gram matrix plus a rank-one term, so the sum is positive semi-definite; when every
+ * earlier datum is in every set it telescopes to ck_loglik_fisher's matrix, whatever the ordering.  D_j is, entry for entry,
+ * the matrix whose contraction gives ck_loglik_vecchia_grad's gradient (the same pair rule: evaluator, distance, h == 0 test).
+ * The result does not depend on the values of the data.
+ * fisher_host (13 x 13, row-major): the slots, free13 and the rule for slots that are not live are ck_loglik_fisher's: rows and
+ * columns of slots that are not live are exact 0, the matrix is symmetric to the bit, masking a slot changes no bit of the
+ * others, and when no nu slot of a block is live the four shifted evaluations of its nu difference are skipped.
+ * The sets are those of ck_loglik_vecchia for the same ranks, max_dist and caps; stats3 as there.  A datum whose local system is
+ * not positive definite or whose s_t^2 is not > 0 has no term: the live block of fisher_host is NaN, *info = 1 + the first such
+ * datum in the caller's stacked order, and the call returns 0.  *info = 0 otherwise.
+ * Sums: a workgroup adds the terms of 8 consecutive data of a process in their order (a constant of the layout, not of the
+ * device), the workgroups' 91 sums (the lower triangle) are added by the fixed tree of the scores; no atomics; repeated calls
+ * give the same bits.  No N x 91 array exists.
+ * State: as ck_loglik_vecchia -- no Sigma panels, nothing invalidated, ck_predict's bits unchanged.
+ * Refused through ck_last_error: what ck_loglik_vecchia_grad refuses (NULL rank_host or fisher_host here), and -- after the
+ * select passes of both processes, before any solve -- any conditioning set of more than 64 data, with that call's message.
+ * ck_timings [88 ..]: the select passes, k_vecchia_info (both processes), the reductions, host wall clock (ms), the data solved
+ * and the entries evaluated (sum over the data of (k + 1)^2); [72 ..] and [60 ..] as after ck_loglik_vecchia (no terms: [74] is 0). */
+int ck_loglik_vecchia_fisher(ck_handle* h, const int64_t* rank_host, double max_dist, const int32_t* free13 /* or NULL: all */,
+                             double* fisher_host /* 13 x 13 */, int64_t* stats3 /* n_empty, k_max, n_capped */, int64_t* info);
+
 /* Simulation draw z = L eps in the caller's stacked order (process 0 sites, then process 1):
  * sim.BivariateRandomField._simulate (src/sim.py:52-54: cholesky(cmat, lower=True) @ noise).
  * n = number of observations; needs ck_factor. */
@@ -658,7 +690,9 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * the LDS class (empty sets included) / beyond it.  [10], [14] and [60 ..] then hold the sums over its two passes.
  * ck_loglik_vecchia_grad (n up to 86): [80] the select passes of both processes; [81] solve, back substitution and contraction
  * (k_vecchia_grad, both processes); [82] the reductions (the terms' and the scores'); [83] host wall clock of the call; [84] data
- * solved; [85] pairs contracted (sum over the data of (k + 1)(k + 2) / 2).  [72 ..] and [60 ..] are filled as by ck_loglik_vecchia. */
+ * solved; [85] pairs contracted (sum over the data of (k + 1)(k + 2) / 2).  [72 ..] and [60 ..] are filled as by ck_loglik_vecchia.
+ * ck_loglik_vecchia_fisher (n up to 94): [88] the select passes of both processes; [89] k_vecchia_info, both processes; [90] the
+ * reductions; [91] host wall clock of the call; [92] data solved; [93] entries evaluated (sum over the data of (k + 1)^2). */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it

@@ -34,7 +34,7 @@
 #include "ck_vecchia.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 88
+#define CK_N_TIMINGS 96
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -4058,28 +4058,28 @@ extern "C" int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host, double 
     return 0;
 }
 
-// The gradient of the Vecchia likelihood (include/cokrige.h has the definition, ck_vecchia_grad.h the formula).  Its own two
-// phases instead of predict_local_impl's one: the select passes of BOTH processes first -- a set beyond the LDS limit is
-// refused before any solve -- then one launch of k_vecchia_grad per process on the cut distances those passes left on the
-// device, then the terms (vecchia_terms_tail: ck_loglik_vecchia's bits) and the column sums of the scores.
-extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, double max_dist, const int32_t* free13, double* out3,
-                                      double* grad13, double* score_host, int64_t* stats3, int64_t* info) {
-    CHKH(h);
-    if (vecchia_admit(h, "ck_loglik_vecchia_grad", rank_host && out3 && grad13 ? nullptr : "rank_host / out3 / grad13", max_dist))
-        return -1;
-    const auto t_begin = std::chrono::steady_clock::now();
-    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
-    const int NP = CK_FISHER_NPAR;
-    static_assert(CK_FISHER_NPAR == CK_VG_NPAR, "the score has the slots of ck_loglik_fisher");
-    for (int k = 0; k < NP; ++k) grad13[k] = NAN;
-    const int64_t N = h->N, n0 = h->n[0], Np = h->Npad;
-    DevTemps tmp;
+// What the two calls on the LDS class of the local solver (name: ck_loglik_vecchia_grad, ck_loglik_vecchia_fisher) do before
+// their own kernel, written once: the ordering, the live slots (ck_loglik_fisher's rule) and the operands of the pair rule
+// (ck_loglik's), every datum's own internal index on the device, then the select pass of BOTH processes -- a set beyond the LDS
+// limit is refused here, before any solve (refused_for: what the message says the call is for).
+struct VecchiaLdsStages {
     CkVecchiaOrder ord;   // with every datum's own internal index (gself)
     int* d_rs = nullptr;
-    if (vecchia_order(h, "ck_loglik_vecchia_grad", rank_host, tmp, &ord, &d_rs)) return -1;
-    // live slots (ck_loglik_fisher's rule) and the operands of the contraction (ck_loglik's)
-    CkVecchiaGradArgs A{};
-    CkVecchiaModel& V = A.V;
+    CkVecchiaModel V{};
+    const double* dvar = nullptr;   // the raw measurement-error variances, internal order; null: no noise slot is live
+    int* d_gself = nullptr;
+    LocalPass pass[2];              // a process's pass: the select here, the solve in the caller's kernel
+    std::vector<int32_t> cnt2;
+    VecchiaReport rep;
+    int64_t n_pairs = 0, n_square = 0;   // sum over the data of (k + 1)(k + 2) / 2 and of (k + 1)^2
+};
+static int vecchia_lds_stages(ck_handle* h, const std::string& name, const char* refused_for, const int64_t* rank_host,
+                              double max_dist, const int32_t* free13, DevTemps& tmp, VecchiaLdsStages* out) {
+    static_assert(CK_FISHER_NPAR == CK_VG_NPAR, "the score has the slots of ck_loglik_fisher");
+    VecchiaLdsStages& C = *out;
+    const int64_t N = h->N, n0 = h->n[0], Np = h->Npad;
+    if (vecchia_order(h, name, rank_host, tmp, &C.ord, &C.d_rs)) return -1;
+    CkVecchiaModel& V = C.V;
     V.live = live_slots(h, free13);
     for (int b = 0; b < (h->n_procs == 1 ? 1 : 3); ++b)
         if (V.live >> ck_vg_nu_slot(h->n_procs, b) & 1u) V.nu_live |= 1u << b;
@@ -4089,53 +4089,81 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
     V.sig2 = h->par_sigma[1];
     V.rho = h->par_rho;
     V.n_procs = h->n_procs;
-    A.dvar = (V.live >> 11 & 3u) ? h->d_noise + Np : nullptr;
-    int* d_gself = nullptr;
-    double* d_score = nullptr;
-    HIPCHK(tmp.get(&d_gself, (size_t)N * sizeof(int)));
-    HIPCHK(tmp.get(&d_score, (size_t)(N * NP) * 8));
-    HIPCHK(hipMemcpyAsync(d_gself, ord.gself.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    // ---- phase 1: the select pass of every process (its points: the process's data in the caller's order)
-    LocalPass pass[2];
-    double *d_out[2] = {nullptr, nullptr}, *d_vv[2] = {nullptr, nullptr};
+    C.dvar = (V.live >> 11 & 3u) ? h->d_noise + Np : nullptr;
+    HIPCHK(tmp.get(&C.d_gself, (size_t)N * sizeof(int)));
+    HIPCHK(hipMemcpyAsync(C.d_gself, C.ord.gself.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    // the select pass of every process (its points: the process's data in the caller's order)
     const int kl = ck_local_lds_limit();
-    std::vector<int32_t> cnt2((size_t)(2 * N), 0);
-    VecchiaReport rep;
-    int64_t n_over = 0, n_pairs = 0;
+    C.cnt2.assign((size_t)(2 * N), 0);
+    int64_t n_over = 0;
     for (int k = 0; k < h->n_procs; ++k) {
-        const int64_t m = h->n[k], mp = roundup(m, 64), soff = k == 0 ? 0 : n0;
+        const int64_t m = h->n[k], soff = k == 0 ? 0 : n0;
         if (m == 0) continue;
-        HIPCHK(tmp.get(&d_out[k], (size_t)(2 * mp * 8)));
-        HIPCHK(tmp.get(&d_vv[k], (size_t)(mp * 8)));
-        HIPCHK(hipMemsetAsync(d_vv[k], 0, (size_t)(mp * 8), h->stream));
-        LocalPass& S = pass[k];   // this process's pass: the select here, the solve in phase 2
-        if (local_pass(h, tmp, k, h->h_coords[k].data(), m, max_dist, 0, true, d_rs, ord.pos.data() + soff, nullptr, &S)) return -1;
-        rep.st.add(S.st);
+        LocalPass& S = C.pass[k];
+        if (local_pass(h, tmp, k, h->h_coords[k].data(), m, max_dist, 0, true, C.d_rs, C.ord.pos.data() + soff, nullptr, &S)) return -1;
+        C.rep.st.add(S.st);
         for (int64_t p = 0; p < m; ++p) {
             const int k0 = S.sel[(size_t)(4 * p)], k1 = S.sel[(size_t)(4 * p + 1)], kt = k0 + k1;
-            cnt2[(size_t)(2 * (soff + p))] = k0;
-            cnt2[(size_t)(2 * (soff + p) + 1)] = k1;
-            rep.n_empty += kt == 0;
+            C.cnt2[(size_t)(2 * (soff + p))] = k0;
+            C.cnt2[(size_t)(2 * (soff + p) + 1)] = k1;
+            C.rep.n_empty += kt == 0;
             n_over += kt > kl;
-            rep.k_max = std::max<int64_t>(rep.k_max, kt);
-            n_pairs += (int64_t)(kt + 1) * (kt + 2) / 2;
+            C.rep.k_max = std::max<int64_t>(C.rep.k_max, kt);
+            C.n_pairs += (int64_t)(kt + 1) * (kt + 2) / 2;
+            C.n_square += (int64_t)(kt + 1) * (kt + 1);
         }
     }
     if (n_over > 0) {
-        write_select_timings(h, rep.st);   // the refused call's passes did run
-        return fail("ck_loglik_vecchia_grad: " + std::to_string(n_over) + " data have a conditioning set of more than " +
-                    std::to_string(kl) + " data (the largest: " + std::to_string(rep.k_max) +
-                    "); the gradient is for sets the LDS solver takes: lower the caps or the radius, or difference ck_loglik_vecchia");
+        write_select_timings(h, C.rep.st);   // the refused call's passes did run
+        return fail(name + ": " + std::to_string(n_over) + " data have a conditioning set of more than " + std::to_string(kl) +
+                    " data (the largest: " + std::to_string(C.rep.k_max) + "); " + refused_for);
+    }
+    return 0;
+}
+
+// The gradient of the Vecchia likelihood (include/cokrige.h has the definition, ck_vecchia_grad.h the formula).  Its own two
+// phases instead of predict_local_impl's one: the stages above, then one launch of k_vecchia_grad per process on the cut
+// distances the select passes left on the device, then the terms (vecchia_terms_tail: ck_loglik_vecchia's bits) and the column
+// sums of the scores.
+extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, double max_dist, const int32_t* free13, double* out3,
+                                      double* grad13, double* score_host, int64_t* stats3, int64_t* info) {
+    CHKH(h);
+    if (vecchia_admit(h, "ck_loglik_vecchia_grad", rank_host && out3 && grad13 ? nullptr : "rank_host / out3 / grad13", max_dist))
+        return -1;
+    const auto t_begin = std::chrono::steady_clock::now();
+    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    const int NP = CK_FISHER_NPAR;
+    for (int k = 0; k < NP; ++k) grad13[k] = NAN;
+    const int64_t N = h->N, n0 = h->n[0];
+    DevTemps tmp;
+    VecchiaLdsStages C;
+    if (vecchia_lds_stages(h, "ck_loglik_vecchia_grad",
+                           "the gradient is for sets the LDS solver takes: lower the caps or the radius, or difference ck_loglik_vecchia",
+                           rank_host, max_dist, free13, tmp, &C))
+        return -1;
+    CkVecchiaGradArgs A{};
+    A.V = C.V;
+    A.dvar = C.dvar;
+    VecchiaReport& rep = C.rep;
+    double* d_score = nullptr;
+    HIPCHK(tmp.get(&d_score, (size_t)(N * NP) * 8));
+    double *d_out[2] = {nullptr, nullptr}, *d_vv[2] = {nullptr, nullptr};
+    for (int k = 0; k < h->n_procs; ++k) {
+        const int64_t mp = C.pass[k].mp;   // this process's pass: the select in the stages, the solve in phase 2
+        if (C.pass[k].m == 0) continue;
+        HIPCHK(tmp.get(&d_out[k], (size_t)(2 * mp * 8)));
+        HIPCHK(tmp.get(&d_vv[k], (size_t)(mp * 8)));
+        HIPCHK(hipMemsetAsync(d_vv[k], 0, (size_t)(mp * 8), h->stream));
     }
     // ---- phase 2: solve, back substitution and contraction, one workgroup per datum
     std::vector<double> mu((size_t)N), vv((size_t)N, 0.0);
     HIPCHK(hipEventRecord(h->ev2, h->stream));
     for (int k = 0; k < h->n_procs; ++k) {
-        const LocalPass& S = pass[k];
+        const LocalPass& S = C.pass[k];
         if (S.m == 0) continue;
         const int64_t soff = k == 0 ? 0 : n0;
         CkVecchiaGradArgs Ak = A;
-        Ak.gself = d_gself + soff;
+        Ak.gself = C.d_gself + soff;
         Ak.score = d_score + soff * NP;
         ck_launch_vecchia_grad(h->stream, S.prob, S.m, S.d_cnt, d_out[k], d_out[k] + S.mp, d_vv[k], Ak);
         HIPCHK(hipGetLastError());
@@ -4144,7 +4172,7 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
     VecchiaData D;
     vecchia_data(h, &D);   // on the host while the device solves: before the downloads, which wait for it
     for (int k = 0; k < h->n_procs; ++k) {
-        const int64_t m = pass[k].m, soff = k == 0 ? 0 : n0;
+        const int64_t m = C.pass[k].m, soff = k == 0 ? 0 : n0;
         if (m == 0) continue;
         HIPCHK(hipMemcpyAsync(mu.data() + soff, d_out[k], m * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(vv.data() + soff, d_vv[k], m * 8, hipMemcpyDeviceToHost, h->stream));
@@ -4152,7 +4180,7 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
     HIPCHK(hipStreamSynchronize(h->stream));   // (hb is stack memory)
     HIPCHK(elapsed_ms(h->ev2, h->ev3, &rep.solve_ms));
     int64_t first_bad = 0;
-    if (vecchia_terms_tail(h, tmp, D, mu, vv, cnt2, out3, nullptr, nullptr, nullptr, &first_bad, &rep.n_lds, &rep.terms_ms)) return -1;
+    if (vecchia_terms_tail(h, tmp, D, mu, vv, C.cnt2, out3, nullptr, nullptr, nullptr, &first_bad, &rep.n_lds, &rep.terms_ms)) return -1;
     // ---- the column sums of the scores, in the caller's stacked order
     const int64_t nblk = (N + 255) / 256;
     double *d_part = nullptr, *d_g = nullptr;
@@ -4177,7 +4205,85 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
     h->t_ms[82] = rep.terms_ms + ms_sum;
     h->t_ms[83] = rep.total_ms;
     h->t_ms[84] = (double)N;
-    h->t_ms[85] = (double)n_pairs;
+    h->t_ms[85] = (double)C.n_pairs;
+    return 0;
+}
+
+// The expected information of the Vecchia likelihood (include/cokrige.h has the definition, ck_vecchia_info.h the formula): the
+// stages of the gradient call, one launch of k_vecchia_info per process, the fixed tree over the workgroups' 91-vectors, and on
+// the host the mirror to 13 x 13.  No terms are formed: the result does not depend on the values.
+extern "C" int ck_loglik_vecchia_fisher(ck_handle* h, const int64_t* rank_host, double max_dist, const int32_t* free13,
+                                        double* fisher_host, int64_t* stats3, int64_t* info) {
+    CHKH(h);
+    if (vecchia_admit(h, "ck_loglik_vecchia_fisher", rank_host && fisher_host ? nullptr : "rank_host / fisher_host", max_dist))
+        return -1;
+    const auto t_begin = std::chrono::steady_clock::now();
+    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    const int NP = CK_FISHER_NPAR, NT = CK_VI_NTRI;
+    for (int k = 0; k < NP * NP; ++k) fisher_host[k] = NAN;
+    const int64_t N = h->N, n0 = h->n[0];
+    DevTemps tmp;
+    VecchiaLdsStages C;
+    if (vecchia_lds_stages(h, "ck_loglik_vecchia_fisher", "the information is for sets the LDS solver takes: lower the caps or the radius",
+                           rank_host, max_dist, free13, tmp, &C))
+        return -1;
+    // one row of 91 partial sums per workgroup: a fixed run of consecutive data of a process, whatever the device
+    const int64_t run = ck_vecchia_info_run();
+    const int64_t rows0 = (n0 + run - 1) / run, rows1 = h->n_procs == 2 ? (h->n[1] + run - 1) / run : 0, n_rows = rows0 + rows1;
+    const int64_t nblk = (n_rows + 255) / 256;
+    double *d_rows = nullptr, *d_part = nullptr, *d_tri = nullptr;
+    long long* d_bad = nullptr;
+    HIPCHK(tmp.get(&d_rows, (size_t)(std::max<int64_t>(n_rows, 1) * NT) * 8));
+    HIPCHK(tmp.get(&d_part, (size_t)(std::max<int64_t>(nblk, 1) * NT) * 8));
+    HIPCHK(tmp.get(&d_tri, (size_t)NT * 8));
+    HIPCHK(tmp.get(&d_bad, (size_t)std::max<int64_t>(n_rows, 1) * sizeof(long long)));
+    HIPCHK(hipEventRecord(h->ev2, h->stream));
+    for (int k = 0; k < h->n_procs; ++k) {
+        const LocalPass& S = C.pass[k];
+        if (S.m == 0) continue;
+        const int64_t soff = k == 0 ? 0 : n0;
+        CkVecchiaInfoArgs A{};
+        A.V = C.V;
+        A.dvar = C.dvar;
+        A.gself = C.d_gself + soff;
+        A.part = d_rows;
+        A.bad = d_bad;
+        A.row0 = k == 0 ? 0 : rows0;
+        A.stacked0 = soff;
+        ck_launch_vecchia_info(h->stream, S.prob, S.m, S.d_cnt, A);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(h->ev3, h->stream));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    ck_launch_vecchia_info_sum(h->stream, n_rows, d_rows, d_part, d_tri);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    double tri[CK_VI_NTRI] = {};
+    std::vector<long long> bad((size_t)n_rows, 0);
+    if (n_rows > 0) {
+        HIPCHK(hipMemcpyAsync(tri, d_tri, (size_t)NT * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(bad.data(), d_bad, (size_t)n_rows * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));   // (tri is stack memory)
+    int64_t first_bad = 0;   // the rows come in the stacked order of their data
+    for (int64_t r = 0; r < n_rows && first_bad == 0; ++r) first_bad = bad[(size_t)r];
+    ck_vecchia_info_mirror(tri, C.V.live, first_bad != 0, fisher_host);
+    if (info) *info = first_bad;
+    double ms_sum = 0.0;
+    VecchiaReport& rep = C.rep;
+    if (n_rows > 0) {
+        HIPCHK(elapsed_ms(h->ev2, h->ev3, &rep.solve_ms));
+        HIPCHK(elapsed_ms(h->ev0, h->ev1, &ms_sum));
+    }
+    rep.n_lds = N;
+    rep.total_ms = ms_since(t_begin);
+    vecchia_report(h, rep, stats3);   // (terms_ms, n_tiled, grow_ms: 0 -- no terms, every set is of the LDS class)
+    h->t_ms[88] = rep.st.ms;
+    h->t_ms[89] = rep.solve_ms;
+    h->t_ms[90] = ms_sum;
+    h->t_ms[91] = rep.total_ms;
+    h->t_ms[92] = (double)N;
+    h->t_ms[93] = (double)C.n_square;
     return 0;
 }
 

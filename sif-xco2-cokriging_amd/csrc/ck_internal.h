@@ -7,6 +7,7 @@
 #include "ck_host.h"
 #include "ck_math.h"
 #include "ck_vecchia_grad.h"
+#include "ck_vecchia_info.h"
 
 #define CK_NB 512   // outer block column width (panel width)
 #define CK_IB 64    // inner block (diagonal factor / row solves)
@@ -400,6 +401,22 @@ struct CkVecchiaGradArgs {
 void ck_launch_vecchia_grad(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, double* pred, double* err,
                             double* vv, CkVecchiaGradArgs A);
 void ck_launch_vecchia_grad_sum(hipStream_t s, int64_t n, const double* score, double* part, double* out13);
+// The expected information of the Vecchia likelihood (ck_loglik_vecchia_fisher; ck_vecchia_info.h): k_vecchia_info runs
+// k_vecchia_grad's steps up to the back substitution on the points [0, m), ck_vecchia_info_run() consecutive points per
+// workgroup, then the product D b, the forward substitution and the combination.  Workgroup w writes row row0 + w of part
+// (CK_VI_NTRI sums) and of bad (1 + stacked0 + the first of its points without a term; 0: none).  gself, dvar: as above.
+// ck_launch_vecchia_info_sum: column sums of n_rows rows by the fixed tree of the scores (part: CK_VI_NTRI x ceil(n_rows / 256)).
+struct CkVecchiaInfoArgs {
+    CkVecchiaModel V;
+    const int* gself;
+    const double* dvar;
+    double* part;
+    long long* bad;
+    long long row0, stacked0;
+};
+int ck_vecchia_info_run();
+void ck_launch_vecchia_info(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, CkVecchiaInfoArgs A);
+void ck_launch_vecchia_info_sum(hipStream_t s, int64_t n_rows, const double* rows, double* part, double* out91);
 
 // Large neighbourhoods (k > k_hi above): the "tiled" path.  The systems of a batch are factored TOGETHER,
 // 64 columns per step, by launches over all systems that still have columns left (diagonal block + its

@@ -34,6 +34,8 @@
 //   k_vecchia_terms / k_vecchia_sum            vt_tree
 //   k_vecchia_grad      k_local_solve's calls, then back substitution and the contraction (ck_vecchia_grad.h)
 //   k_vecchia_grad_part / k_vecchia_grad_sum   vg_tree
+//   k_vecchia_info      k_vecchia_grad's calls up to the back substitution, then the product D b, the forward substitution and
+//                       the combination (ck_vecchia_info.h);  k_vecchia_info_part / k_vecchia_info_sum: vg_tree, 7 x 13 columns
 // The Vecchia likelihood (ck_loglik_vecchia) runs the prediction kernels with the data as the points and one more predicate
 // in the search: only sites that come earlier in the caller's ordering (lp_later).
 #include "ck_internal.h"
@@ -1151,7 +1153,8 @@ void ck_launch_vecchia_terms(hipStream_t s, int64_t n, const double* z, const do
 // k_vecchia_grad: one workgroup per datum, sets of at most LP_KL data.  Steps 1 - 4 are k_local_solve's: the same
 // calls of the same device functions with the same arguments, so mu and v . v come out with the same bits (the one difference:
 // the neighbour list is written under the capacity guard of lp_compact, which never drops an entry here); then
-//   5. back substitution in place on rows k and k + 1: v -> w = L^-T v, y -> alpha = L^-T y.  ONE wave, lane a holding x_a of
+//   5. back substitution in place on rows k and k + 1: v -> w = L^-T v, y -> alpha = L^-T y (vg_back_substitute, shared with
+//      k_vecchia_info).  ONE wave, lane a holding x_a of
 //      both rows: step j broadcasts x_j / L_jj from lane j and every lane a < j subtracts L[j][a] x_j -- row j of L is
 //      contiguous in LDS, and with k <= 64 the whole vector lives in one wave, so the k dependent steps need no barrier
 //      (a barrier per step across four waves would cost more than the three waves add: a step has at most 64 updates);
@@ -1161,6 +1164,32 @@ void ck_launch_vecchia_terms(hipStream_t s, int64_t n, const double* z, const do
 // An empty set is the one-entry system (b = 1, a = 0): it runs step 6 alone.  A system that is not positive definite or a
 // variance that is not > 0: NaN in the live slots.  k_vecchia_grad_part / _sum: the column sums of the scores by vg_tree,
 // the 13-column form of the terms' tree and partial-sum order.  No atomics: repeated calls give the same bits.
+
+// step 5 of both kernels: rows k, k + 1 of S become b = -L^-T v and alpha = L^-T y; ends with a barrier
+__device__ __forceinline__ void vg_back_substitute(double* S, long ld, int k) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (wv == 0 && k > 0) {
+        double xv = lane < k ? S[(long)k * ld + lane] : 0.0, xy = lane < k ? S[(long)(k + 1) * ld + lane] : 0.0;
+        for (int j = k - 1; j >= 0; --j) {
+            const double dj = S[(long)j * ld + j];
+            const double lj = lane < j ? S[(long)j * ld + lane] : 0.0;
+            const double vj = __shfl(xv, j) / dj, yj = __shfl(xy, j) / dj;
+            if (lane == j) {
+                xv = vj;
+                xy = yj;
+            } else if (lane < j) {
+                xv -= lj * vj;
+                xy -= lj * yj;
+            }
+        }
+        if (lane < k) {
+            S[(long)k * ld + lane] = -xv;
+            S[(long)(k + 1) * ld + lane] = xy;
+        }
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(LP_TPB) void k_vecchia_grad(CkLocalProblem P, const int* __restrict__ counts,
                                                           double* __restrict__ pred, double* __restrict__ err,
                                                           double* __restrict__ vv, CkVecchiaGradArgs A) {
@@ -1202,27 +1231,7 @@ __global__ __launch_bounds__(LP_TPB) void k_vecchia_grad(CkLocalProblem P, const
         if (tid < CK_VG_NPAR) score[tid] = ck_vecchia_slot_out(V, tid, 0.0, 1);
         return;
     }
-    // ---- 5. back substitution: rows k, k + 1 become b = -w and a = alpha ----
-    if (wv == 0 && k > 0) {
-        double xv = lane < k ? S[(long)k * ld + lane] : 0.0, xy = lane < k ? S[(long)(k + 1) * ld + lane] : 0.0;
-        for (int j = k - 1; j >= 0; --j) {
-            const double dj = S[(long)j * ld + j];
-            const double lj = lane < j ? S[(long)j * ld + lane] : 0.0;
-            const double vj = __shfl(xv, j) / dj, yj = __shfl(xy, j) / dj;
-            if (lane == j) {
-                xv = vj;
-                xy = yj;
-            } else if (lane < j) {
-                xv -= lj * vj;
-                xy -= lj * yj;
-            }
-        }
-        if (lane < k) {
-            S[(long)k * ld + lane] = -xv;
-            S[(long)(k + 1) * ld + lane] = xy;
-        }
-    }
-    __syncthreads();
+    vg_back_substitute(S, ld, k);                  // 5. rows k, k + 1 become b = -w and a = alpha
     // ---- 6. the contraction over the lower triangle of the set plus the datum ----
     double acc[CK_VG_NPAR];
 #pragma unroll
@@ -1297,4 +1306,177 @@ void ck_launch_vecchia_grad_sum(hipStream_t s, int64_t n, const double* score, d
     const long nblk = (long)((n + LP_TPB - 1) / LP_TPB);
     k_vecchia_grad_part<<<dim3((unsigned)nblk), dim3(LP_TPB), 0, s>>>((long)n, score, part);
     k_vecchia_grad_sum<<<dim3(1), dim3(LP_TPB), 0, s>>>(nblk, part, out13);
+}
+
+// ---------------------------------------------------------------------------------------
+// the expected information of the Vecchia likelihood (ck_loglik_vecchia_fisher; ck_vecchia_info.h has the formula and the rules)
+// ---------------------------------------------------------------------------------------
+// k_vecchia_info: a workgroup takes VI_RUN consecutive data of a process, one after the other, sets of at most LP_KL data.  Per
+// datum, steps 1 - 5 are k_vecchia_grad's: the same calls of the same device functions with the same arguments (the z row rides
+// along unused), so L, v . v and b = -w are that kernel's.  Then
+//   5'. L is mirrored into the unused upper triangle of S, S[j][a] = L[a][j] for a > j, along diagonals (lane l moves entry
+//       (l + d, l): reads and writes both walk the banks), so that COLUMN j of L is the contiguous tail of row j;
+//   6'. the product U = D b over the full square of the set plus the datum: row a belongs to VI_T = 16 consecutive lanes, lane
+//       `sub` of them takes the entries q = sub, sub + 16, .. through ck_vecchia_info_entry (ck_vecchia_pair itself) into 13
+//       sums, xor-shuffles over the 16 lanes add them in a fixed order and lane 0 writes U[slot][a]: no two threads add to one
+//       element, 16 rows per pass;
+//   7'. q_slot = b . U[slot] (a wave reduction) and the forward substitution Y = L^-1 U[., 0 : k], wave w taking the slots w,
+//       w + 4, w + 8, w + 12: lane a holds entry a of its (up to four) right-hand sides, step j broadcasts x_j / L_jj from
+//       lane j and every lane a > j subtracts L[a][j] x_j, read from the mirrored copy -- the column form of step 5, no barrier
+//       and no reduction inside the k dependent steps, no bank conflict (a column walk on L itself puts all lanes on one bank);
+//   8'. thread e < 91 adds ck_vecchia_info_combine(y_j . y_k, q_j, q_k, s2) of its pair (j, k) to its running sum.
+// The workgroup writes its 91 sums to one row of `part` and 1 + the first of its data without a term (0: none) to `bad`: N / VI_RUN
+// rows, whatever the device.  k_vecchia_info_part / _sum: the column sums of the rows by vg_tree, 13 columns per workgroup
+// (blockIdx.y / blockIdx.x = the group of columns), in the partial-sum order of the scores.  No atomics: repeated calls give the
+// same bits.
+#define VI_RUN 8   // consecutive data per workgroup: a constant of the reduction's layout
+#define VI_T 16    // lanes per row of the product
+static_assert(CK_VI_NTRI % CK_VG_NPAR == 0 && CK_VI_NTRI <= LP_TPB, "91 = 7 groups of vg_tree's 13 columns, one thread per sum");
+static_assert(LP_KL <= 64, "the set's vector lives in one wave");
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_info(CkLocalProblem P, const int* __restrict__ counts, long m,
+                                                          CkVecchiaInfoArgs A) {
+    __shared__ double S[(LP_KL + 2) * LP_KL];
+    __shared__ int idx[LP_KL];
+    __shared__ double U[CK_VI_NPAR][LP_KL + 2];
+    __shared__ double qv[CK_VI_NPAR];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const CkVecchiaModel& V = A.V;
+    const long ld = LP_KL;
+    int je = 0, ke = 0;   // this thread's pair of slots (tid < 91)
+    if (tid < CK_VI_NTRI) ck_vg_pair_of(tid, &je, &ke);
+    double sum = 0.0;
+    long long first_bad = 0;
+    for (int r = 0; r < VI_RUN; ++r) {
+        const long p = (long)blockIdx.x * VI_RUN + r;
+        if (p >= m) break;     // uniform
+        __syncthreads();       // the previous datum's reads of S, U and qv are done
+        const int k = counts[p];
+        if (k > LP_KL) continue;   // refused by the host before any launch
+        const LpPoint X = lp_point(P, p);
+        bool ok = true;
+        if (k > 0) {
+            lp_compact<false, LP_KL>(P, X, idx);       // 1. neighbour list (the count is the select pass's: never beyond k)
+            lp_triangle(P, X, idx, S, ld, k);          // 2. local covariance, c row, z row, noise
+            lp_cz_rows(P, X, idx, S, ld, k);
+            lp_noise(P, idx, S, ld, k);
+            ok = lp_chol(S, ld, k, 2);                 // 3. Cholesky, the two extra rows ride along
+        }
+        double mu = 0.0, vvs = 0.0, s2 = 0.0;
+        if (ok && k > 0) lp_dots(S + (long)k * ld, S + (long)(k + 1) * ld, k, &mu, &vvs);   // 4. v . v
+        const long gs = A.gself[p];
+        if (!ok || ck_vecchia_info_var(P.z[gs], mu, vvs, P.c0var, P.nz ? P.nz[gs] : 0.0, k, &s2)) {   // uniform
+            if (first_bad == 0) first_bad = A.stacked0 + p + 1;
+            continue;
+        }
+        vg_back_substitute(S, ld, k);                  // 5. row k becomes b = -w
+        // ---- 5'. the mirror of L ----
+        for (int d = 1 + wv; d < k; d += LP_TPB / 64) {
+            const int a = lane + d;
+            if (a < k) S[(long)lane * ld + a] = S[(long)a * ld + lane];
+        }
+        // ---- 6'. U = D b ----
+        const int n1 = k + 1;
+        for (int a0 = 0; a0 < n1; a0 += LP_TPB / VI_T) {
+            const int a = a0 + tid / VI_T, sub = tid % VI_T;
+            double row[CK_VI_NPAR];
+#pragma unroll
+            for (int c = 0; c < CK_VI_NPAR; ++c) row[c] = 0.0;
+            if (a < n1) {
+                const long ga = a < k ? idx[a] : gs;
+                const int pa = a < k ? (V.n_procs == 2 && ga >= P.L.n0p ? 1 : 0) : P.i_pred;
+                const double a0c = a < k ? X.s0[ga] : X.p0, a1c = a < k ? X.s1[ga] : X.p1, a2c = a < k ? X.s2[ga] : X.p2;
+                const double d_a = A.dvar ? A.dvar[ga] : 0.0;
+                for (int q = sub; q < n1; q += VI_T) {
+                    const long gq = q < k ? idx[q] : gs;
+                    const int pq = q < k ? (V.n_procs == 2 && gq >= P.L.n0p ? 1 : 0) : P.i_pred;
+                    const double q0 = q < k ? X.s0[gq] : X.p0, q1 = q < k ? X.s1[gq] : X.p1, q2 = q < k ? X.s2[gq] : X.p2;
+                    const double bq = q < k ? S[(long)k * ld + q] : 1.0;
+                    const double h = a == q ? 0.0 : lp_dist(P.metric, a0c, a1c, a2c, q0, q1, q2);
+                    ck_vecchia_info_entry(row, V, pa, pq, a == q, h, bq, a == q ? d_a : 0.0);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < CK_VI_NPAR; ++c) {
+                double v = row[c];
+#pragma unroll
+                for (int off = VI_T / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+                if (a < n1 && sub == 0) U[c][a] = v;
+            }
+        }
+        __syncthreads();
+        // ---- 7'. q = b . U and Y = L^-1 U[., 0 : k], in place ----
+        {
+            const double bl = lane < k ? S[(long)k * ld + lane] : 0.0;
+            double x[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int s = wv + 4 * i;
+                x[i] = (s < CK_VI_NPAR && lane < k) ? U[s < CK_VI_NPAR ? s : 0][lane] : 0.0;
+                double v = x[i] * bl;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+                if (s < CK_VI_NPAR && lane == 0) qv[s] = v + U[s][k];
+            }
+            for (int j = 0; j < k; ++j) {
+                const double dj = S[(long)j * ld + j];
+                const double lj = (lane > j && lane < k) ? S[(long)j * ld + lane] : 0.0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const double xj = __shfl(x[i], j) / dj;
+                    if (lane == j)
+                        x[i] = xj;
+                    else if (lane > j)
+                        x[i] -= lj * xj;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int s = wv + 4 * i;
+                if (s < CK_VI_NPAR && lane < k) U[s][lane] = x[i];
+            }
+        }
+        __syncthreads();
+        // ---- 8'. the combination ----
+        if (tid < CK_VI_NTRI) {
+            double yy = 0.0;
+            for (int a = 0; a < k; ++a) yy += U[je][a] * U[ke][a];
+            sum += ck_vecchia_info_combine(V, je, ke, yy, qv[je], qv[ke], s2);
+        }
+    }
+    const long long row = A.row0 + blockIdx.x;
+    if (tid < CK_VI_NTRI) A.part[row * CK_VI_NTRI + tid] = sum;
+    if (tid == 0) A.bad[row] = first_bad;
+}
+
+// column sums of n rows of 91: workgroup (x, y) sums the rows 256 x .. of the columns 13 y ..
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_info_part(long n, const double* __restrict__ rows, double* __restrict__ part) {
+    const long t = (long)blockIdx.x * LP_TPB + threadIdx.x;
+    const int c0 = CK_VG_NPAR * blockIdx.y;
+    vg_tree([&](int c) { return t < n ? rows[t * CK_VI_NTRI + c0 + c] : 0.0; }, part + (long)blockIdx.x * CK_VI_NTRI + c0);
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_info_sum(long nblk, const double* __restrict__ part, double* __restrict__ out91) {
+    const int c0 = CK_VG_NPAR * blockIdx.x;
+    vg_tree(
+        [&](int c) {
+            double v = 0.0;
+            for (long e = threadIdx.x; e < nblk; e += LP_TPB) v += part[e * CK_VI_NTRI + c0 + c];
+            return v;
+        },
+        out91 + c0);
+}
+
+int ck_vecchia_info_run() { return VI_RUN; }
+
+void ck_launch_vecchia_info(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, CkVecchiaInfoArgs A) {
+    if (m <= 0) return;
+    k_vecchia_info<<<dim3((unsigned)((m + VI_RUN - 1) / VI_RUN)), dim3(LP_TPB), 0, s>>>(P, counts, (long)m, A);
+}
+
+void ck_launch_vecchia_info_sum(hipStream_t s, int64_t n_rows, const double* rows, double* part, double* out91) {
+    if (n_rows <= 0) return;
+    const long nblk = (long)((n_rows + LP_TPB - 1) / LP_TPB);
+    k_vecchia_info_part<<<dim3((unsigned)nblk, CK_VI_NTRI / CK_VG_NPAR), dim3(LP_TPB), 0, s>>>((long)n_rows, rows, part);
+    k_vecchia_info_sum<<<dim3(CK_VI_NTRI / CK_VG_NPAR), dim3(LP_TPB), 0, s>>>(nblk, part, out91);
 }

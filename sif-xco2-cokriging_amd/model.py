@@ -415,14 +415,28 @@ class MultivariateMatern:
         return h, var
 
     def information(self, mf, dist_units: str = "km", fast_dist: bool = True, trend=None, measurement_error=None,
-                    noise_scale=None, fixed=None, _at_bound=None):
+                    noise_scale=None, fixed=None, _at_bound=None, vecchia=None, _ranks=None):
         """Expected (Fisher) information of the likelihood at the current parameters and what follows from it
         (``ParameterInformation``): I_jk = 1/2 tr(Sigma^-1 D_j Sigma^-1 D_k) with D_k = dSigma/dtheta_k, computed on the
         device (``ck_loglik_fisher``); with ``trend`` the information of the restricted likelihood.  The arguments are those
         of ``log_likelihood``.  The noise scales of the processes that have ``measurement_error`` are parameters too
         (``noise_scale_0`` / ``noise_scale_1``).  ``fixed``: names (or flat indices of the model parameters) conditioned on:
-        they are left out, and the standard errors are those of the others given them."""
-        h, var = self._lik_assembled(mf, dist_units, fast_dist, trend, measurement_error, noise_scale)
+        they are left out, and the standard errors are those of the others given them.
+
+        ``vecchia`` (a ``vecchia.Vecchia``): the expected information of the Vecchia likelihood instead
+        (``ck_loglik_vecchia_fisher``), for data whose Sigma does not fit: I^V = sum_t [I(S_t) - I(c_t)] over the conditioning
+        sets c_t and S_t = c_t + {t} of ``log_likelihood(vecchia=...)`` -- the expected negative Hessian of the Vecchia
+        objective under the exact model, what GpGp reports with its fits; not a Godambe sandwich.  It equals the dense
+        information when every earlier datum is in every set.  Conditioning sets of at most 64 data (a larger one raises the
+        native error); ``trend`` is refused (no REML form).  The call works whatever ``vecchia.information`` says."""
+        if vecchia is not None:
+            from .vecchia import Vecchia
+            if trend is not None:
+                raise ValueError("information(vecchia=...) has no restricted (REML) form: trend must be None")
+            if not isinstance(vecchia, Vecchia):
+                raise ValueError(f"vecchia must be a vecchia.Vecchia, got {type(vecchia).__name__}")
+            caps = vecchia.caps(self.n_procs)
+        h, var = self._lik_assembled(mf, dist_units, fast_dist, trend, measurement_error, noise_scale, assemble=vecchia is None)
         names13 = information_slot_names(self.n_procs)
         model_names = list(self.params.get_names())
         live = np.zeros(13, dtype=bool)
@@ -441,9 +455,25 @@ class MultivariateMatern:
         bound = np.zeros(13, dtype=bool)
         for f in ([] if _at_bound is None else _at_bound):
             bound[names13.index(f)] = live[names13.index(f)]
-        info, fisher = h.fisher(reml=trend is not None, free=live & ~bound)
-        if info != 0:
-            raise LinAlgError(f"{info}-th leading minor of the array is not positive definite")
+        if vecchia is not None:
+            ranks = _ranks
+            if ranks is None:
+                ranks = vecchia.ranks([np.asarray(mf.fields[k].coords_main, dtype=np.float64)[:, :2] for k in range(self.n_procs)])
+            h.set_local_neighbours(*caps)
+            try:
+                fisher, info, _ = h.loglik_vecchia_fisher(ranks, vecchia.max_dist, free=live & ~bound)
+            except native.NativeError as exc:
+                if "conditioning set of more than" in str(exc):
+                    raise native.NativeError(f"{exc}.  The information of the Vecchia likelihood is for sets of at most 64 "
+                                             "data: use smaller max_neighbours") from None
+                raise
+            if info != 0:
+                raise LinAlgError(f"the local system of datum {info - 1} (stacked order) is not positive definite, or its "
+                                  "conditional variance is not positive")
+        else:
+            info, fisher = h.fisher(reml=trend is not None, free=live & ~bound)
+            if info != 0:
+                raise LinAlgError(f"{info}-th leading minor of the array is not positive definite")
         est = np.full(13, np.nan)
         est[:len(model_names)] = self.params.get_values().astype(float)
         if var is not None:
@@ -486,17 +516,21 @@ class MultivariateMatern:
         for k free parameters).  With ``Vecchia(..., gradient="analytic")`` value and gradient come from one native call per
         evaluation (``ck_loglik_vecchia_grad``, the slots held fixed masked out), under the dense path's optimiser options;
         ``fd_step`` is then validated and otherwise unused, and a conditioning set beyond 64 data raises the native error.
-        The ordering's ranks are computed once per fit.  ``fit_result.method`` is "Vecchia-ML";
-        ``trend`` and ``std_errors=True`` are refused (the Fisher information is the dense one)."""
+        The ordering's ranks are computed once per fit.  ``fit_result.method`` is "Vecchia-ML"; ``trend`` is refused.
+        ``std_errors=True`` is refused (the Fisher information is not configured) unless the configuration says
+        ``Vecchia(..., information="expected")``: then ``fit_result.information``, ``.std_error``, ``.conf_int()`` and
+        ``.at_bound`` are filled as after a dense fit, from ``information(vecchia=...)`` at the optimum on the fit's ranks --
+        the expected information of the Vecchia objective under the exact model, for conditioning sets of at most 64 data."""
         from .noise import resolve_measurement_error
         from .trend import check_trend
         check_trend(trend)
         if vecchia is not None:
             if trend is not None:
                 raise ValueError("fit_likelihood(vecchia=...) has no restricted (REML) form: trend must be None")
-            if std_errors:
-                raise NotImplementedError("std_errors=True needs the Fisher information, which is the dense likelihood's: fit "
-                                          "with vecchia, then call information() where Sigma fits")
+            if std_errors and getattr(vecchia, "information", "none") != "expected":
+                raise NotImplementedError("std_errors=True needs the Fisher information: configure the expected information of "
+                                          "the Vecchia likelihood with Vecchia(..., information=\"expected\"), or fit with "
+                                          "vecchia and call information() afterwards")
             if not (isinstance(fd_step, (float, np.floating)) and 0.0 < fd_step < 0.5):
                 raise ValueError(f"fd_step must be a float in (0, 0.5), got {fd_step!r}")
             v_ranks = vecchia.ranks([np.asarray(mf.fields[k].coords_main, dtype=np.float64)[:, :2]
@@ -641,7 +675,8 @@ class MultivariateMatern:
                 warnings.warn(f"fit_likelihood: {', '.join(at_bound)} ended on a bound; the standard errors are conditional on "
                               "them and their own are NaN")
             inf = self.information(mf, dist_units, fast_dist, trend=trend, measurement_error=measurement_error,
-                                   noise_scale=scales_of(res.x), fixed=held, _at_bound=at_bound)
+                                   noise_scale=scales_of(res.x), fixed=held, _at_bound=at_bound, vecchia=vecchia,
+                                   _ranks=v_ranks if vecchia is not None else None)
             self.fit_result.information = inf
             self.fit_result.at_bound = at_bound
             self.fit_result.std_error = inf.std_error

@@ -81,6 +81,7 @@ _PROTOS = {
                           POINTER(c_int64)],
     "ck_loglik_vecchia_grad": [c_void_p, POINTER(c_int64), c_double, POINTER(c_int32), _dp, _dp, _dp, POINTER(c_int64),
                                POINTER(c_int64)],
+    "ck_loglik_vecchia_fisher": [c_void_p, POINTER(c_int64), c_double, POINTER(c_int32), _dp, POINTER(c_int64), POINTER(c_int64)],
     "ck_predict_local_universal": [c_void_p, c_int, _dp, c_int64, _dp, c_double, c_int, _dp, _dp, _dp, POINTER(c_int64),
                                    POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
     "ck_vario_begin": [c_void_p, _dp, _dp, c_int64, _dp, _dp, c_int64, c_int],
@@ -735,6 +736,33 @@ class Handle:
         _chk(lib().ck_timings(self._h, _p(out), 86))
         keys = ["select_ms", "solve_ms", "reduce_ms", "total_ms", "n_data", "n_pairs"]
         return dict(zip(keys, out[80:86].tolist()))
+
+    def loglik_vecchia_fisher(self, rank, max_dist, free=None):
+        """Expected information of the Vecchia likelihood (include/cokrige.h: ck_loglik_vecchia_fisher), for conditioning sets
+        of at most 64 data, on the sets loglik_vecchia uses.  ``free``: 13 flags over the slots of fisher() (None: all).
+        Returns (fisher, info, stats): the 13 x 13 array, symmetric, exact zeros in the rows and columns of slots that are not
+        live; info = 1 + the first datum without a term (the live block is then NaN), else 0; stats: n_empty, k_max, n_capped."""
+        r = np.ascontiguousarray(rank, dtype=np.int64).reshape(-1)
+        n = int(sum(self._n_data.values()))
+        if r.size != n:
+            raise ValueError(f"rank has {r.size} entries, the handle {n} data")
+        fr = None
+        if free is not None:
+            fr = np.ascontiguousarray(np.asarray(free).astype(bool), dtype=np.int32)
+            if fr.shape != (13,):
+                raise ValueError("free: 13 flags, one per slot")
+        out, st, info = np.empty((13, 13)), np.zeros(3, dtype=np.int64), c_int64(0)
+        _chk(lib().ck_loglik_vecchia_fisher(self._h, r.ctypes.data_as(POINTER(c_int64)), float(max_dist),
+                                            fr.ctypes.data_as(POINTER(c_int32)) if fr is not None else None, _p(out),
+                                            st.ctypes.data_as(POINTER(c_int64)), byref(info)))
+        return out, info.value, dict(n_empty=int(st[0]), k_max=int(st[1]), n_capped=int(st[2]))
+
+    def vecchia_fisher_timings(self):
+        """ck_timings [88 ..] of the last loglik_vecchia_fisher() call (milliseconds; the last two are counts)."""
+        out = np.zeros(94)
+        _chk(lib().ck_timings(self._h, _p(out), 94))
+        keys = ["select_ms", "kernel_ms", "reduce_ms", "total_ms", "n_data", "n_entries"]
+        return dict(zip(keys, out[88:94].tolist()))
 
     def local_reserve(self, nbytes: int = 0):
         """Pre-size the scratch slab of predict_local (0: the automatic budget) -- include/cokrige.h: ck_local_reserve."""

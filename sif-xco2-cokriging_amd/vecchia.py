@@ -10,6 +10,7 @@ from .point_prediction import check_max_neighbours
 
 ORDERINGS = ("random", "hilbert")
 GRADIENTS = ("numeric", "analytic")
+INFORMATIONS = ("none", "expected")
 
 
 def check_ordering(ordering):
@@ -58,9 +59,12 @@ class Vecchia:
     an int for every process or one int per process; 0 = no cap), ``ordering`` ("random", "hilbert" or an array of ranks) and
     the ``seed`` of the random ordering.  ``gradient``: "numeric" (the default: ``fit_likelihood`` differences the value) or
     "analytic" (``ck_loglik_vecchia_grad``: value and gradient from one native call, for conditioning sets of at most 64 data --
-    ``log_likelihood(..., gradient=True)`` then works and the fit uses it).  Validated here, before any device work."""
+    ``log_likelihood(..., gradient=True)`` then works and the fit uses it).  ``information``: "none" (the default:
+    ``fit_likelihood(..., std_errors=True)`` is refused) or "expected" (``ck_loglik_vecchia_fisher``: the fit reports the expected
+    information of the Vecchia objective under the exact model and the standard errors that follow from it, for conditioning
+    sets of at most 64 data; it is what GpGp reports, not a Godambe sandwich).  Validated here, before any device work."""
 
-    def __init__(self, max_dist, max_neighbours=None, ordering="random", seed=0, gradient="numeric"):
+    def __init__(self, max_dist, max_neighbours=None, ordering="random", seed=0, gradient="numeric", information="none"):
         if isinstance(max_dist, (bool, np.bool_)) or not isinstance(max_dist, (int, float, np.integer, np.floating)):
             raise ValueError(f"max_dist must be a number, got {max_dist!r}")
         if not np.isfinite(max_dist) or max_dist < 0:
@@ -78,6 +82,9 @@ class Vecchia:
         if not isinstance(gradient, str) or gradient not in GRADIENTS:
             raise ValueError(f"gradient must be one of {GRADIENTS}, got {gradient!r}")
         self.gradient = gradient
+        if not isinstance(information, str) or information not in INFORMATIONS:
+            raise ValueError(f"information must be one of {INFORMATIONS}, got {information!r}")
+        self.information = information
 
     def caps(self, n_procs):
         """The pair of caps for a model of ``n_procs`` processes ((0, 0): none)."""

@@ -1,0 +1,135 @@
+"""The expected information of the Vecchia likelihood (include/cokrige.h: ck_loglik_vecchia_fisher) in numpy, on the sets of
+tests/vecchia_ref.py: vecchia_reference, in the set-difference form
+    I^V = sum_t [fisher_of(S_t) - fisher_of(c_t)],   fisher_of(A)_jk = 1/2 tr(C_A^-1 D_j,A C_A^-1 D_k,A),
+with dense_chains.fisher_of / derivative_matrices / dense_sigma on sub-matrices: a different formula from the device's last-row
+form, with differenced nu and length-scale derivatives instead of the analytic ones.  Also the fixtures the host and the GPU
+tests share, and the reference's own floor on each of them.  Used by tests/test_vecchia_info_host.py and
+tests/test_gpu_vecchia_info.py."""
+import numpy as np
+
+from tests import dense_chains as dc
+from tests import vecchia_ref as vr
+
+HAV, EUC = 0, 1
+
+
+def vecchia_info_reference(params, coords, metric, keep, noise_d=None, scales=(1.0, 1.0), scale=1.0, per_datum=False):
+    """the 13 x 13 information on the sets keep (N x N bool, keep[t, s]: datum s is in the set of datum t); noise_d: per
+    process the variances d_a or None; scale multiplies the step of the differenced derivatives (dense_chains._d4).
+    per_datum: the (N, 13, 13) array of the terms instead of their sum"""
+    S = dc.dense_sigma(params, coords, metric, noise_d, scales)
+    D = dc.derivative_matrices(params, coords, metric, noise_d, scale)
+    N = S.shape[0]
+    out = np.zeros((N, 13, 13))
+    for t in range(N):
+        c = np.flatnonzero(keep[t])
+        ix = np.r_[c, t]
+        out[t] = dc.fisher_of(S[np.ix_(ix, ix)], {k: Dk[np.ix_(ix, ix)] for k, Dk in D.items()})
+        if c.size:
+            out[t] -= dc.fisher_of(S[np.ix_(c, c)], {k: Dk[np.ix_(c, c)] for k, Dk in D.items()})
+    return out if per_datum else out.sum(axis=0)
+
+
+# ---- the fixtures of tests/test_gpu_vecchia_info.py (those of tests/test_gpu_vecchia_grad.py) -----------------------------------
+SCALES = (0.7, 1.3)
+_cache = {}
+
+
+def parameter_set(name):
+    from sif_xco2_cokriging_amd import synth
+    if name == "SET_B_UNIT":
+        return list(synth.SET_B_UNIT)
+    if name == "SET_A":
+        return list(synth.SET_A)
+    gen = list(synth.SET_A)
+    gen[5:8] = [0.2, 0.2, 0.2]                                     # GEN: generic nu on the unit square
+    return gen
+
+
+def _unit(name):
+    coords, values = vr.half_colocated_sites(150)
+    return dict(coords=coords, values=values, params=parameter_set(name), metric=EUC, max_dist=0.5, noise_d=None, scales=(1.0, 1.0),
+                ranks=np.random.default_rng(11).permutation(300).astype(np.int64))
+
+
+def _small(name, ordering):
+    """N = 65: 33 + 32 sites, one conditioning set of 64 under full conditioning"""
+    from sif_xco2_cokriging_amd import vecchia
+    coords, values = vr.half_colocated_sites(33)
+    coords, values = [coords[0], coords[1][:32]], [values[0], values[1][:32]]
+    return dict(coords=coords, values=values, params=parameter_set(name), metric=EUC, max_dist=2.0, caps=(0, 0), noise_d=None,
+                scales=(1.0, 1.0), ranks=vecchia.ordering_ranks(coords, ordering, 1))
+
+
+def _build(label):
+    kind, name = label.split("/")
+    if kind.startswith("caps"):
+        cap = int(kind[4:])
+        return dict(_unit(name), caps=(cap, cap))
+    if kind.startswith("full_"):
+        return _small(name, kind[5:])
+    if kind == "noise16":
+        rng = np.random.default_rng(21)
+        return dict(_unit(name), caps=(16, 16), noise_d=[rng.uniform(0.01, 0.05, 150) for _ in range(2)], scales=SCALES)
+    if kind == "uni8":
+        pb = _unit(name)
+        return dict(pb, coords=pb["coords"][:1], values=pb["values"][:1], params=[1.0, 1.2, 0.2, 0.02], caps=(8,),
+                    ranks=np.random.default_rng(12).permutation(150).astype(np.int64))
+    if kind == "hav12":
+        from sif_xco2_cokriging_amd import synth
+        rng = np.random.default_rng(4102)
+        c0, c1 = synth.split_sites(np.column_stack([rng.uniform(30.0, 38.0, 225), rng.uniform(-105.0, -95.0, 225)]), 150)
+        return dict(coords=[c0, c1], values=[rng.standard_normal(150), rng.standard_normal(150)], params=parameter_set(name),
+                    metric=HAV, max_dist=250.0, caps=(12, 12), noise_d=None, scales=(1.0, 1.0),
+                    ranks=np.random.default_rng(13).permutation(300).astype(np.int64))
+    raise KeyError(label)
+
+
+FIXTURES = ([f"caps{c}/{n}" for n in ("SET_B_UNIT", "GEN") for c in (4, 16, 32)] +
+            [f"full_{o}/{n}" for n in ("SET_B_UNIT", "GEN") for o in ("random", "hilbert")] +
+            ["noise16/GEN", "uni8/GEN", "hav12/SET_A"])
+
+
+def fixture(label):
+    if label not in _cache:
+        _cache[label] = _build(label)
+    return _cache[label]
+
+
+def sets_of(label):
+    """vecchia_reference of the fixture (its sets, counts and gaps) -- computed once and left unchanged"""
+    key = ("sets", label)
+    if key not in _cache:
+        f = fixture(label)
+        noise = None if f["noise_d"] is None else [f["scales"][q] * d for q, d in enumerate(f["noise_d"])]
+        _cache[key] = vr.vecchia_reference(f["params"], f["coords"], f["values"], f["metric"], f["ranks"], f["max_dist"], f["caps"],
+                                           noise=noise)
+    return _cache[key]
+
+
+def reference(label, scale=1.0):
+    """the reference information of the fixture -- computed once per (fixture, step scale) and left unchanged"""
+    key = ("ref", label, scale)
+    if key not in _cache:
+        f = fixture(label)
+        _cache[key] = vecchia_info_reference(f["params"], f["coords"], f["metric"], sets_of(label)["keep"], f["noise_d"], f["scales"],
+                                             scale)
+    return _cache[key]
+
+
+# The reference's own floor in the length-scale class on every fixture -- what halving _d4's step changes, in
+# dense_chains.normalised's measure (tests/test_vecchia_info_host.py: test_reference_floor measures and prints it, the procedure
+# of tests/test_dense_chains.py: test_fisher_reference_floor).  The bound of the length-scale class is max(1e-9, 10 x the
+# fixture's floor), dense_chains.fisher_tol's rule; a fixture is listed only when its floor exceeds 1e-10.
+# Measured (rounded up in the third digit): the unit-square fixtures have length scales of 0.2 under _d4's absolute step of 1e-3,
+# so their floors are of the order 1e-9; the haversine fixture (460 km) stays at 1.3e-11.
+INFO_LEN_FLOOR = {"caps4/SET_B_UNIT": 6.45e-9, "caps16/SET_B_UNIT": 6.79e-9, "caps32/SET_B_UNIT": 6.78e-9,
+                  "caps4/GEN": 4.27e-9, "caps16/GEN": 4.47e-9, "caps32/GEN": 4.46e-9,
+                  "full_random/SET_B_UNIT": 2.25e-9, "full_hilbert/SET_B_UNIT": 2.25e-9,
+                  "full_random/GEN": 1.57e-9, "full_hilbert/GEN": 1.57e-9,
+                  "noise16/GEN": 2.93e-9, "uni8/GEN": 6.69e-9}
+INFO_TOL = {"exact": 1e-9, "nu": 1e-6}
+
+
+def info_tol(label):
+    return dict(INFO_TOL, len=max(1e-9, 10.0 * INFO_LEN_FLOOR.get(label, 0.0)))
