@@ -335,7 +335,7 @@ int ck_loglik_fisher(ck_handle* h, int reml, const int32_t* free13, double* fish
  * invalidates nothing: a resident factor, the solved right-hand sides and ck_predict's bits are as before the call.  The ranks
  * are permuted to the internal site order inside the call and kept nowhere.  The data of process i are the points of one pass
  * of the local solver with i_pred = i (select pass, then both size classes as in ck_predict_local), one pass per process.
- * Refused through ck_last_error: a partitioned handle; a trend set on the handle (REML is not defined here); two equal ranks
+ * Refused through ck_last_error: a partitioned handle; a trend set on the handle (ck_loglik_vecchia_trend takes one); two equal ranks
  * (both data are named); a non-finite or negative max_dist; NULL rank_host or out3.
  * ck_timings [72 ..]: the select pass, the solves of both size classes, the term reduction, host wall clock (ms), the number of
  * data whose set fits the LDS class (<= 64, the empty ones among them) and the number beyond it; [60 ..] hold the select
@@ -403,6 +403,58 @@ int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, double max_di
  * and the entries evaluated (sum over the data of (k + 1)^2); [72 ..] and [60 ..] as after ck_loglik_vecchia (no terms: [74] is 0). */
 int ck_loglik_vecchia_fisher(ck_handle* h, const int64_t* rank_host, double max_dist, const int32_t* free13 /* or NULL: all */,
                              double* fisher_host /* 13 x 13 */, int64_t* stats3 /* n_empty, k_max, n_capped */, int64_t* info);
+
+/* The Vecchia likelihood with an unknown trend X beta estimated by GLS inside it: the profile likelihood and its restricted
+ * (REML) form, for conditioning sets of at most 64 data (the LDS class of the local solver).  X is ck_set_trend's block-diagonal
+ * N x p design, p = p_0 + p_1 <= 16, x_t its row at datum t.  For datum t with set c and Sigma_loc = L L^T as in
+ * ck_loglik_vecchia (ck_set_noise's s d on the diagonal):
+ *   v = L^-1 c,  y = L^-1 z_c,  U = L^-1 X_c,     s_t^2 = prior + own - v . v  (unchanged),
+ *   e_t = z_t - v . y,  f_t = x_t - U^T v,        r_t = (e_t, f_t) / s_t       (an empty set: r_t = (z_t, x_t) / s_t),
+ *   G = sum_t r_t r_t^T = [[yy, b^T], [b, A]],    beta = A^-1 b,  Cov(beta) = A^-1,  Q = yy - b^T beta,
+ *   profile ML:  l_P = -1/2 [N log 2 pi + sum_t log s_t^2 + Q],
+ *   REML:        l_R = -1/2 [(N - p) log 2 pi + sum_t log s_t^2 + log|A| + Q]      (ck_loglik_reml's convention: no log|X^T X|).
+ * This is the likelihood of the Vecchia model with mean X beta maximised over (profile) or integrated against (REML) beta --
+ * what GpGp profiles out of its fits.  When every earlier datum is in every set, A = X^T Sigma^-1 X, b = X^T Sigma^-1 z and
+ * sum_t log s_t^2 = log|Sigma| exactly, whatever the ordering: out5 and beta are ck_loglik_reml's and ck_predict_universal's.
+ * out5 = (l, sum_t log s_t^2, log|A|, Q, yy);  beta_host (p, or NULL), beta_cov_host (p x p, or NULL).
+ * mean_host (N or NULL): mu_t + f_t^T beta, the conditional mean of the observation under the fitted trend;  var_host, count_host,
+ * stats3: as ck_loglik_vecchia, var and count bit for bit those of that call on a handle without the trend -- the p trend rows
+ * ride along the factorisation behind c and z (k_vecchia_trend) and change no operation on them.
+ * Sums: every dot of the solve in a fixed order; G by a fixed tree (256 consecutive data per workgroup, each entry of the lower
+ * triangle summed over them in order, then the workgroups' triangles in the partial-sum order of the scores); no atomics;
+ * repeated calls give the same bits.  A is factored on the host with ck_predict_universal's relative pivot threshold of 1e-10:
+ * a rank-deficient design is refused with a message naming the process and the regressor.
+ * A datum whose local system is not positive definite or whose s_t^2 is not > 0 adds nothing to G: out5, beta and beta_cov are
+ * NaN and *info = 1 + that datum (the first such) in the caller's stacked order; the call still returns 0.
+ * With no trend set (p = 0) the call is ck_loglik_vecchia: its bits in out5[0], [1], [3] and [4], log|A| = 0, larger sets allowed.
+ * State: as ck_loglik_vecchia -- no Sigma panels, nothing invalidated.  Refused through ck_last_error: what ck_loglik_vecchia
+ * refuses except the trend, NULL rank_host or out5, and -- after the select passes of both processes, before any solve -- any
+ * conditioning set of more than 64 data.  ck_loglik_vecchia, ck_loglik_vecchia_grad and ck_loglik_vecchia_fisher keep refusing
+ * a handle with a trend.
+ * ck_timings [96 ..]: the select passes, k_vecchia_trend (both processes), the terms and the Gram matrix, residual + gradient
+ * (0 here), host wall clock (ms), the data solved and p; [72 ..] and [60 ..] as after ck_loglik_vecchia. */
+int ck_loglik_vecchia_trend(ck_handle* h, const int64_t* rank_host, double max_dist, int reml,
+                            double* out5 /* l, sum log s^2, log|A|, Q, yy */, double* beta_host /* p or NULL */,
+                            double* beta_cov_host /* p x p or NULL */, double* mean_host /* N or NULL */,
+                            double* var_host /* N or NULL */, int32_t* count_host /* N x 2 or NULL */,
+                            int64_t* stats3 /* n_empty, k_max, n_capped */, int64_t* info);
+/* The profile form with its analytic gradient: dl_P/dtheta = dl(theta, beta)/dtheta at beta = beta-hat (the envelope theorem:
+ * the derivative through beta-hat vanishes at the maximum), which is ck_loglik_vecchia_grad's formula on the residual
+ * z - X beta-hat.  The call runs the stages of ck_loglik_vecchia_trend, forms the residual over the sites (k_vecchia_residual)
+ * and launches that call's kernel on it: every value it reads, the datum's own included, is the residual.
+ * out5, beta_host, beta_cov_host: the bits of ck_loglik_vecchia_trend(reml = 0).  grad13, free13, score_host (the per-datum
+ * dl_t/dtheta at beta-hat), stats3, info: the slots, the masking and the rules of ck_loglik_vecchia_grad; with *info != 0 there
+ * is no beta-hat and every score is NaN.  The REML form has no analytic gradient (it needs d log|A| / dtheta): difference
+ * ck_loglik_vecchia_trend(reml = 1).  With no trend set the call is ck_loglik_vecchia_grad.
+ * ck_timings [96 ..] as ck_loglik_vecchia_trend, [99] the residual, k_vecchia_grad and the score sums. */
+int ck_loglik_vecchia_trend_grad(ck_handle* h, const int64_t* rank_host, double max_dist, const int32_t* free13 /* or NULL: all */,
+                                 double* out5, double* beta_host /* p or NULL */, double* beta_cov_host /* p x p or NULL */,
+                                 double* grad13, double* score_host /* N x 13 or NULL */,
+                                 int64_t* stats3 /* n_empty, k_max, n_capped */, int64_t* info);
+/* The per-datum solve of the two calls above, alone: mu_t = v . y, v . v and g_t = U^T v (N x p) in the caller's stacked order,
+ * zeros where the set is empty, NaN where the local system is not positive definite; the test surface of k_vecchia_trend. */
+int ck_debug_vecchia_trend(ck_handle* h, const int64_t* rank_host, double max_dist, double* mu_host, double* vv_host,
+                           double* g_host /* N x p */);
 
 /* Simulation draw z = L eps in the caller's stacked order (process 0 sites, then process 1):
  * sim.BivariateRandomField._simulate (src/sim.py:52-54: cholesky(cmat, lower=True) @ noise).
@@ -692,7 +744,11 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * (k_vecchia_grad, both processes); [82] the reductions (the terms' and the scores'); [83] host wall clock of the call; [84] data
  * solved; [85] pairs contracted (sum over the data of (k + 1)(k + 2) / 2).  [72 ..] and [60 ..] are filled as by ck_loglik_vecchia.
  * ck_loglik_vecchia_fisher (n up to 94): [88] the select passes of both processes; [89] k_vecchia_info, both processes; [90] the
- * reductions; [91] host wall clock of the call; [92] data solved; [93] entries evaluated (sum over the data of (k + 1)^2). */
+ * reductions; [91] host wall clock of the call; [92] data solved; [93] entries evaluated (sum over the data of (k + 1)^2).
+ * ck_loglik_vecchia_trend / _trend_grad (n up to 103): [96] the select passes of both processes; [97] k_vecchia_trend, both
+ * processes; [98] the terms with their rows and the Gram matrix (k_vecchia_trend_terms, k_vecchia_sum, k_vecchia_trend_gram and
+ * its tree); [99] the gradient call's residual, k_vecchia_grad and score sums (0 after the value call); [100] host wall clock of
+ * the call; [101] data solved; [102] trend columns p.  [72 ..] and [60 ..] are filled as by ck_loglik_vecchia. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it

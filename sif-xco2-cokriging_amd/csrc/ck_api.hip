@@ -34,7 +34,7 @@
 #include "ck_vecchia.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 96
+#define CK_N_TIMINGS 104
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -1833,8 +1833,18 @@ static std::string trend_column_name(const ck_handle* h, int c) {
     return "regressor " + std::to_string(k == 0 ? c : c - h->trend_p[0]) + " of process " + std::to_string(k);
 }
 
+// ck_host_gls on (A, b) in the caller's name: a rank-deficient design is refused, naming the process and the regressor
+static int trend_gls_solve(const ck_handle* h, const char* name, int p, const double* A, const double* b, double* R, double* beta,
+                           double* Ainv, double* logdet, double* bAb) {
+    const int bad = ck_host_gls(p, A, b, CK_TREND_TOL, R, beta, Ainv, logdet, bAb);
+    if (bad)
+        return fail(std::string(name) + ": the trend design is rank deficient: " + trend_column_name(h, bad - 1) +
+                    " is, to rounding, a combination of the regressors in front of it (X^T Sigma^-1 X is singular)");
+    return 0;
+}
+
 // The GLS step behind k_reduce_univ: A = U^T U and b = U^T y from the p trend rows of the reduced rows W (p + 2 doubles each,
-// the first trend row at row0), then ck_host_gls; a rank-deficient design is refused in the caller's name.  A: p x p, kept
+// the first trend row at row0), then trend_gls_solve.  A: p x p, kept
 // for the caller; the other outputs as ck_host_gls's (any may be null).
 static int trend_gls(const ck_handle* h, const char* name, const std::vector<double>& W, int64_t row0, int p, double* A, double* R,
                      double* beta, double* Ainv, double* logdet, double* bAb) {
@@ -1844,11 +1854,7 @@ static int trend_gls(const ck_handle* h, const char* name, const std::vector<dou
         b[(size_t)j] = wr[1];
         for (int l = 0; l < p; ++l) A[(size_t)(j * p + l)] = wr[2 + l];
     }
-    const int bad = ck_host_gls(p, A, b.data(), CK_TREND_TOL, R, beta, Ainv, logdet, bAb);
-    if (bad)
-        return fail(std::string(name) + ": the trend design is rank deficient: " + trend_column_name(h, bad - 1) +
-                    " is, to rounding, a combination of the regressors in front of it (X^T Sigma^-1 X is singular)");
-    return 0;
+    return trend_gls_solve(h, name, p, A, b.data(), R, beta, Ainv, logdet, bAb);
 }
 
 static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m, bool may_sort) {
@@ -3895,20 +3901,21 @@ extern "C" int ck_predict_local_universal(ck_handle* h, int i, const double* pco
 // ---------------------------------------------------------------------------------------
 // the Vecchia likelihood (include/cokrige.h has the definition)
 // ---------------------------------------------------------------------------------------
-// What both Vecchia entry points (name) refuse, in this order, before they touch the device; null_args: the arguments the
-// entry point cannot do without, named when one of them is null.  Then the layout: sites, tables, chunk bounds -- no Sigma
+// What the Vecchia entry points (name) refuse, in this order, before they touch the device; null_args: the arguments the
+// entry point cannot do without, named when one of them is null; trend_ok: the entry point takes a trend (ck_loglik_vecchia_trend).  Then the layout: sites, tables, chunk bounds -- no Sigma
 // panels, nothing invalidated.
-static int vecchia_admit(ck_handle* h, const std::string& name, const char* null_args, double max_dist) {
+static int vecchia_admit(ck_handle* h, const std::string& name, const char* null_args, double max_dist, bool trend_ok = false) {
     if (h->world != 1)
         return fail(name + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) + ")");
     if (null_args) return fail(name + ": null " + null_args);
     if (!(max_dist >= 0.0) || !std::isfinite(max_dist))
         return fail(name + ": max_dist must be finite and >= 0, got " + std::to_string(max_dist));
-    if (trend_total(h) > 0)
+    if (trend_total(h) > 0 && !trend_ok)
         return fail(name + ": a trend of " + std::to_string(trend_total(h)) +
                     " columns is set on the handle; the Vecchia likelihood has no REML form (clear it with ck_set_trend)");
     if (ensure_layout(h, false)) return -1;
     if (ensure_noise(h)) return -1;
+    if (trend_ok && ensure_trend(h)) return -1;
     if (h->N > INT32_MAX) return fail(name + ": more than 2^31 - 1 data");
     return 0;
 }
@@ -3970,11 +3977,12 @@ static void vecchia_report(ck_handle* h, const VecchiaReport& V, int64_t* stats3
 }
 
 // The terms and their sums in the caller's stacked order, from what the passes of the local solver left on the host: the tail of
-// both Vecchia entry points -- the same uploads and launches, so the same bits in out3.  *terms_ms: the two term kernels
-// ([ev0, ev1], read here).
+// the Vecchia entry points -- the same uploads and launches, so the same bits in out3.  *terms_ms: the two term kernels
+// ([ev0, ev1], read here).  rows (ck_loglik_vecchia_trend; null: none): the term kernel also writes every datum's row.
 static int vecchia_terms_tail(ck_handle* h, DevTemps& tmp, const VecchiaData& D, const std::vector<double>& mu, std::vector<double>& vv,
                               const std::vector<int32_t>& cnt2, double* out3, double* mean_host, double* var_host,
-                              int32_t* count_host, int64_t* info, int64_t* n_lds_out, double* terms_ms) {
+                              int32_t* count_host, int64_t* info, int64_t* n_lds_out, double* terms_ms,
+                              const CkVecchiaTrendRows* rows = nullptr) {
     const int64_t N = h->N;
     const int kl = ck_local_lds_limit();
     int64_t n_lds = 0;
@@ -3999,8 +4007,12 @@ static int vecchia_terms_tail(ck_handle* h, DevTemps& tmp, const VecchiaData& D,
     for (const auto& c : up) HIPCHK(hipMemcpyAsync(c.first, c.second, (size_t)(N * 8), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(d_cnt2, cnt2.data(), (size_t)(2 * N) * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    ck_launch_vecchia_terms(h->stream, N, d_z, d_mu, d_vv, d_prior, h->noise_on ? d_own : nullptr, d_cnt2, d_mean, d_var, d_part,
-                            d_bad, d_out, d_bad + nblk);
+    if (rows)
+        ck_launch_vecchia_trend_terms(h->stream, N, d_z, d_mu, d_vv, d_prior, h->noise_on ? d_own : nullptr, d_cnt2, *rows, d_mean,
+                                      d_var, d_part, d_bad, d_out, d_bad + nblk);
+    else
+        ck_launch_vecchia_terms(h->stream, N, d_z, d_mu, d_vv, d_prior, h->noise_on ? d_own : nullptr, d_cnt2, d_mean, d_var, d_part,
+                                d_bad, d_out, d_bad + nblk);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     double sums[2] = {0.0, 0.0};
@@ -4021,17 +4033,17 @@ static int vecchia_terms_tail(ck_handle* h, DevTemps& tmp, const VecchiaData& D,
     return 0;
 }
 
-extern "C" int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host, double max_dist, double* out3, double* mean_host,
-                                 double* var_host, int32_t* count_host, int64_t* stats3, int64_t* info) {
-    CHKH(h);
-    if (vecchia_admit(h, "ck_loglik_vecchia", rank_host && out3 ? nullptr : "rank_host / out3", max_dist)) return -1;
+// The zero-mean value in an entry point's name (ck_loglik_vecchia; ck_loglik_vecchia_trend on a handle without a trend), behind
+// vecchia_admit: both size classes of the local solver, then the terms.
+static int vecchia_value(ck_handle* h, const std::string& name, const int64_t* rank_host, double max_dist, double* out3,
+                         double* mean_host, double* var_host, int32_t* count_host, int64_t* stats3, int64_t* info) {
     const auto t_begin = std::chrono::steady_clock::now();
     for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
     const int64_t N = h->N;
     DevTemps tmp;
     CkVecchiaOrder ord;
     int* d_rs = nullptr;
-    if (vecchia_order(h, "ck_loglik_vecchia", rank_host, tmp, &ord, &d_rs)) return -1;
+    if (vecchia_order(h, name, rank_host, tmp, &ord, &d_rs)) return -1;
     // one pass of the local solver per process: its data are the points, i_pred = the process
     std::vector<double> mu((size_t)N), vv((size_t)N, 0.0), sd((size_t)N);
     std::vector<int32_t> cnt2((size_t)(2 * N), 0);
@@ -4056,6 +4068,13 @@ extern "C" int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host, double 
     V.total_ms = ms_since(t_begin);
     vecchia_report(h, V, stats3);
     return 0;
+}
+
+extern "C" int ck_loglik_vecchia(ck_handle* h, const int64_t* rank_host, double max_dist, double* out3, double* mean_host,
+                                 double* var_host, int32_t* count_host, int64_t* stats3, int64_t* info) {
+    CHKH(h);
+    if (vecchia_admit(h, "ck_loglik_vecchia", rank_host && out3 ? nullptr : "rank_host / out3", max_dist)) return -1;
+    return vecchia_value(h, "ck_loglik_vecchia", rank_host, max_dist, out3, mean_host, var_host, count_host, stats3, info);
 }
 
 // What the two calls on the LDS class of the local solver (name: ck_loglik_vecchia_grad, ck_loglik_vecchia_fisher) do before
@@ -4121,6 +4140,84 @@ static int vecchia_lds_stages(ck_handle* h, const std::string& name, const char*
     return 0;
 }
 
+// Phase 2 of a gradient call, behind the stages: solve, back substitution and contraction, one workgroup per datum and one
+// launch of k_vecchia_grad per process on the cut distances the select passes left on the device.  d_z (or null: the data):
+// the values in the internal site order every read of the kernel sees -- the residual of ck_loglik_vecchia_trend_grad.  d_score:
+// N x 13, the caller's stacked order.  D, mu, vv (all or none): what the terms need, the data gathered on the host while the
+// device solves.  *solve_ms: the launches' device window ([ev2, ev3], read here).
+static int vecchia_grad_solve(ck_handle* h, DevTemps& tmp, const VecchiaLdsStages& C, const double* d_z, double* d_score,
+                              VecchiaData* D, std::vector<double>* mu, std::vector<double>* vv, double* solve_ms) {
+    const int NP = CK_FISHER_NPAR;
+    const int64_t n0 = h->n[0];
+    CkVecchiaGradArgs A{};
+    A.V = C.V;
+    A.dvar = C.dvar;
+    double *d_out[2] = {nullptr, nullptr}, *d_vv[2] = {nullptr, nullptr};
+    for (int k = 0; k < h->n_procs; ++k) {
+        const int64_t mp = C.pass[k].mp;   // this process's pass: the select in the stages, the solve here
+        if (C.pass[k].m == 0) continue;
+        HIPCHK(tmp.get(&d_out[k], (size_t)(2 * mp * 8)));
+        HIPCHK(tmp.get(&d_vv[k], (size_t)(mp * 8)));
+        HIPCHK(hipMemsetAsync(d_vv[k], 0, (size_t)(mp * 8), h->stream));
+    }
+    HIPCHK(hipEventRecord(h->ev2, h->stream));
+    for (int k = 0; k < h->n_procs; ++k) {
+        const LocalPass& S = C.pass[k];
+        if (S.m == 0) continue;
+        const int64_t soff = k == 0 ? 0 : n0;
+        CkVecchiaGradArgs Ak = A;
+        Ak.gself = C.d_gself + soff;
+        Ak.score = d_score + soff * NP;
+        CkLocalProblem P = S.prob;
+        if (d_z) P.z = d_z;
+        ck_launch_vecchia_grad(h->stream, P, S.m, S.d_cnt, d_out[k], d_out[k] + S.mp, d_vv[k], Ak);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(h->ev3, h->stream));
+    if (D) {
+        vecchia_data(h, D);   // on the host while the device solves: before the downloads, which wait for it
+        for (int k = 0; k < h->n_procs; ++k) {
+            const int64_t m = C.pass[k].m, soff = k == 0 ? 0 : n0;
+            if (m == 0) continue;
+            HIPCHK(hipMemcpyAsync(mu->data() + soff, d_out[k], m * 8, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(vv->data() + soff, d_vv[k], m * 8, hipMemcpyDeviceToHost, h->stream));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(elapsed_ms(h->ev2, h->ev3, solve_ms));
+    return 0;
+}
+// The column sums of the scores, in the caller's stacked order, and the scores themselves where asked for; first_bad != 0:
+// grad13 is NaN.  *ms: the reduction's device window ([ev2, ev3], read here).
+static int vecchia_score_sums(ck_handle* h, DevTemps& tmp, const double* d_score, int64_t first_bad, double* grad13,
+                              double* score_host, double* ms) {
+    const int NP = CK_FISHER_NPAR;
+    const int64_t N = h->N, nblk = (N + 255) / 256;
+    double *d_part = nullptr, *d_g = nullptr;
+    HIPCHK(tmp.get(&d_part, (size_t)(nblk * NP) * 8));
+    HIPCHK(tmp.get(&d_g, (size_t)NP * 8));
+    HIPCHK(hipEventRecord(h->ev2, h->stream));
+    ck_launch_vecchia_grad_sum(h->stream, N, d_score, d_part, d_g);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev3, h->stream));
+    HIPCHK(hipMemcpyAsync(grad13, d_g, (size_t)NP * 8, hipMemcpyDeviceToHost, h->stream));
+    if (score_host) HIPCHK(hipMemcpyAsync(score_host, d_score, (size_t)(N * NP) * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (first_bad)
+        for (int k = 0; k < NP; ++k) grad13[k] = NAN;
+    HIPCHK(elapsed_ms(h->ev2, h->ev3, ms));
+    return 0;
+}
+// ck_timings [80 ..] of a gradient call (behind vecchia_report); reduce_ms: the terms' and the scores' reductions
+static void vecchia_grad_timings(ck_handle* h, const VecchiaLdsStages& C, double reduce_ms) {
+    h->t_ms[80] = C.rep.st.ms;
+    h->t_ms[81] = C.rep.solve_ms;
+    h->t_ms[82] = reduce_ms;
+    h->t_ms[83] = C.rep.total_ms;
+    h->t_ms[84] = (double)h->N;
+    h->t_ms[85] = (double)C.n_pairs;
+}
+
 // The gradient of the Vecchia likelihood (include/cokrige.h has the definition, ck_vecchia_grad.h the formula).  Its own two
 // phases instead of predict_local_impl's one: the stages above, then one launch of k_vecchia_grad per process on the cut
 // distances the select passes left on the device, then the terms (vecchia_terms_tail: ck_loglik_vecchia's bits) and the column
@@ -4141,71 +4238,246 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
                            "the gradient is for sets the LDS solver takes: lower the caps or the radius, or difference ck_loglik_vecchia",
                            rank_host, max_dist, free13, tmp, &C))
         return -1;
-    CkVecchiaGradArgs A{};
-    A.V = C.V;
-    A.dvar = C.dvar;
     VecchiaReport& rep = C.rep;
     double* d_score = nullptr;
     HIPCHK(tmp.get(&d_score, (size_t)(N * NP) * 8));
-    double *d_out[2] = {nullptr, nullptr}, *d_vv[2] = {nullptr, nullptr};
-    for (int k = 0; k < h->n_procs; ++k) {
-        const int64_t mp = C.pass[k].mp;   // this process's pass: the select in the stages, the solve in phase 2
-        if (C.pass[k].m == 0) continue;
-        HIPCHK(tmp.get(&d_out[k], (size_t)(2 * mp * 8)));
-        HIPCHK(tmp.get(&d_vv[k], (size_t)(mp * 8)));
-        HIPCHK(hipMemsetAsync(d_vv[k], 0, (size_t)(mp * 8), h->stream));
-    }
-    // ---- phase 2: solve, back substitution and contraction, one workgroup per datum
     std::vector<double> mu((size_t)N), vv((size_t)N, 0.0);
+    VecchiaData D;
+    if (vecchia_grad_solve(h, tmp, C, nullptr, d_score, &D, &mu, &vv, &rep.solve_ms)) return -1;
+    int64_t first_bad = 0;
+    if (vecchia_terms_tail(h, tmp, D, mu, vv, C.cnt2, out3, nullptr, nullptr, nullptr, &first_bad, &rep.n_lds, &rep.terms_ms)) return -1;
+    double ms_sum = 0;
+    if (vecchia_score_sums(h, tmp, d_score, first_bad, grad13, score_host, &ms_sum)) return -1;
+    if (info) *info = first_bad;
+    rep.total_ms = ms_since(t_begin);
+    vecchia_report(h, rep, stats3);   // (n_tiled, grow_ms: 0 -- every set is of the LDS class)
+    vecchia_grad_timings(h, C, rep.terms_ms + ms_sum);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// the Vecchia likelihood with a GLS trend: profile ML and REML (include/cokrige.h has the definition, ck_vecchia_trend.h a
+// datum's arithmetic)
+// ---------------------------------------------------------------------------------------
+// What the trend calls share behind vecchia_lds_stages.  vecchia_trend_solve: k_vecchia_trend on both processes, (mu, v . v,
+// g = v . U) per datum in the caller's stacked order, on the device and on the host.  vecchia_trend_fit: the terms with their
+// rows (vecchia_terms_tail), the Gram matrix G by its fixed tree, and on the host the GLS step on A = G[1:, 1:], b = G[1:, 0]
+// (ck_predict_universal's: trend_gls_solve), out5 and the per-datum outputs.
+#define CK_VT_REFUSED_FOR "the trend form is for sets the LDS solver takes: lower the caps or the radius"
+struct VecchiaTrendFit {
+    int p = 0;
+    std::vector<double> mu, vv, g;   // N, N, N x p
+    double* d_g = nullptr;
+    std::vector<double> beta, cov;   // p, p x p (NaN with first_bad)
+    double out5[5] = {NAN, NAN, NAN, NAN, NAN};
+    int64_t first_bad = 0;
+    double solve_ms = 0.0, gram_ms = 0.0;
+};
+static int vecchia_trend_solve(ck_handle* h, DevTemps& tmp, const VecchiaLdsStages& C, VecchiaTrendFit* F) {
+    const int p = F->p = trend_total(h);
+    const int64_t N = h->N, n0 = h->n[0];
+    const size_t ng = (size_t)std::max<int64_t>(N * p, 1);
+    double *d_mu = nullptr, *d_vv = nullptr;
+    HIPCHK(tmp.get(&d_mu, (size_t)N * 8));
+    HIPCHK(tmp.get(&d_vv, (size_t)N * 8));
+    HIPCHK(tmp.get(&F->d_g, ng * 8));
+    HIPCHK(hipMemsetAsync(d_mu, 0, (size_t)N * 8, h->stream));   // an empty set: no workgroup writes
+    HIPCHK(hipMemsetAsync(d_vv, 0, (size_t)N * 8, h->stream));
+    HIPCHK(hipMemsetAsync(F->d_g, 0, ng * 8, h->stream));
+    const CkLocalTrend Tr{h->d_trendX, nullptr, h->trend_p[0], h->n_procs == 2 ? h->trend_p[1] : 0, CK_TREND_TOL};
     HIPCHK(hipEventRecord(h->ev2, h->stream));
     for (int k = 0; k < h->n_procs; ++k) {
         const LocalPass& S = C.pass[k];
         if (S.m == 0) continue;
         const int64_t soff = k == 0 ? 0 : n0;
-        CkVecchiaGradArgs Ak = A;
-        Ak.gself = C.d_gself + soff;
-        Ak.score = d_score + soff * NP;
-        ck_launch_vecchia_grad(h->stream, S.prob, S.m, S.d_cnt, d_out[k], d_out[k] + S.mp, d_vv[k], Ak);
+        ck_launch_vecchia_trend(h->stream, S.prob, S.m, S.d_cnt, Tr, d_mu + soff, d_vv + soff, F->d_g + soff * p);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(h->ev3, h->stream));
-    VecchiaData D;
-    vecchia_data(h, &D);   // on the host while the device solves: before the downloads, which wait for it
-    for (int k = 0; k < h->n_procs; ++k) {
-        const int64_t m = C.pass[k].m, soff = k == 0 ? 0 : n0;
-        if (m == 0) continue;
-        HIPCHK(hipMemcpyAsync(mu.data() + soff, d_out[k], m * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipMemcpyAsync(vv.data() + soff, d_vv[k], m * 8, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));   // (hb is stack memory)
-    HIPCHK(elapsed_ms(h->ev2, h->ev3, &rep.solve_ms));
-    int64_t first_bad = 0;
-    if (vecchia_terms_tail(h, tmp, D, mu, vv, C.cnt2, out3, nullptr, nullptr, nullptr, &first_bad, &rep.n_lds, &rep.terms_ms)) return -1;
-    // ---- the column sums of the scores, in the caller's stacked order
-    const int64_t nblk = (N + 255) / 256;
-    double *d_part = nullptr, *d_g = nullptr;
-    HIPCHK(tmp.get(&d_part, (size_t)(nblk * NP) * 8));
-    HIPCHK(tmp.get(&d_g, (size_t)NP * 8));
-    HIPCHK(hipEventRecord(h->ev2, h->stream));
-    ck_launch_vecchia_grad_sum(h->stream, N, d_score, d_part, d_g);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev3, h->stream));
-    HIPCHK(hipMemcpyAsync(grad13, d_g, (size_t)NP * 8, hipMemcpyDeviceToHost, h->stream));
-    if (score_host) HIPCHK(hipMemcpyAsync(score_host, d_score, (size_t)(N * NP) * 8, hipMemcpyDeviceToHost, h->stream));
+    F->mu.resize((size_t)N);
+    F->vv.resize((size_t)N);
+    F->g.assign(ng, 0.0);
+    HIPCHK(hipMemcpyAsync(F->mu.data(), d_mu, (size_t)N * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(F->vv.data(), d_vv, (size_t)N * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(F->g.data(), F->d_g, ng * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (first_bad)
-        for (int k = 0; k < NP; ++k) grad13[k] = NAN;
-    if (info) *info = first_bad;
-    double ms_sum = 0;
-    HIPCHK(elapsed_ms(h->ev2, h->ev3, &ms_sum));
-    rep.total_ms = ms_since(t_begin);
-    vecchia_report(h, rep, stats3);   // (n_tiled, grow_ms: 0 -- every set is of the LDS class)
-    h->t_ms[80] = rep.st.ms;
-    h->t_ms[81] = rep.solve_ms;
-    h->t_ms[82] = rep.terms_ms + ms_sum;
-    h->t_ms[83] = rep.total_ms;
-    h->t_ms[84] = (double)N;
-    h->t_ms[85] = (double)C.n_pairs;
+    HIPCHK(elapsed_ms(h->ev2, h->ev3, &F->solve_ms));
+    return 0;
+}
+static int vecchia_trend_fit(ck_handle* h, const char* name, int reml, DevTemps& tmp, VecchiaLdsStages& C, VecchiaTrendFit* F,
+                             double* mean_host, double* var_host, int32_t* count_host) {
+    if (vecchia_trend_solve(h, tmp, C, F)) return -1;
+    const int p = F->p, NT = CK_VT_NTRI;
+    const int64_t N = h->N, nblk = (N + 255) / 256;
+    VecchiaData D;
+    vecchia_data(h, &D);
+    double *d_rows = nullptr, *d_part = nullptr, *d_tri = nullptr;
+    HIPCHK(tmp.get(&d_rows, (size_t)(N * (p + 1)) * 8));
+    HIPCHK(tmp.get(&d_part, (size_t)(nblk * NT) * 8));
+    HIPCHK(tmp.get(&d_tri, (size_t)NT * 8));
+    const CkVecchiaTrendRows T{p, h->Npad, h->d_trendX, C.d_gself, F->d_g, d_rows};
+    double out3[3];
+    if (vecchia_terms_tail(h, tmp, D, F->mu, F->vv, C.cnt2, out3, mean_host, var_host, count_host, &F->first_bad, &C.rep.n_lds,
+                           &C.rep.terms_ms, &T))
+        return -1;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    ck_launch_vecchia_trend_gram(h->stream, N, p, d_rows, d_part, d_tri);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    double tri[CK_VT_NTRI] = {};
+    HIPCHK(hipMemcpyAsync(tri, d_tri, (size_t)NT * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));   // (tri is stack memory)
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &F->gram_ms));
+    F->beta.assign((size_t)p, NAN);
+    F->cov.assign((size_t)(p * p), NAN);
+    if (F->first_bad == 0) {
+        std::vector<double> A((size_t)(p * p)), b((size_t)p);
+        for (int e = 0; e < (p + 1) * (p + 2) / 2; ++e) {
+            int r, c;
+            ck_vecchia_trend_pair(e, &r, &c);
+            if (r > 0 && c == 0) b[(size_t)(r - 1)] = tri[e];
+            if (c > 0) A[(size_t)((r - 1) * p + c - 1)] = A[(size_t)((c - 1) * p + r - 1)] = tri[e];
+        }
+        double logdet = 0.0;
+        if (trend_gls_solve(h, name, p, A.data(), b.data(), nullptr, F->beta.data(), F->cov.data(), &logdet, nullptr)) return -1;
+        const double q = ck_vecchia_trend_q(p, tri[0], b.data(), F->beta.data());
+        F->out5[0] = ck_vecchia_trend_total(N, p, reml, out3[1], logdet, q);
+        F->out5[1] = out3[1];
+        F->out5[2] = logdet;
+        F->out5[3] = q;
+        F->out5[4] = tri[0];
+    }
+    if (mean_host) {   // mu_t + f_t . beta: the regressors of datum t in the columns of its process
+        std::vector<double> x((size_t)p);
+        for (int k = 0, col = 0; k < h->n_procs; col += h->trend_p[k], ++k) {
+            const int pk = h->trend_p[k];
+            const int64_t soff = k == 0 ? 0 : h->n[0];
+            for (int64_t t = 0; t < h->n[k]; ++t) {
+                std::fill(x.begin(), x.end(), 0.0);
+                for (int c = 0; c < pk; ++c) x[(size_t)(col + c)] = h->trend_F[k][(size_t)(t * pk + c)];
+                const int64_t s = soff + t;
+                const int kt = C.cnt2[(size_t)(2 * s)] + C.cnt2[(size_t)(2 * s + 1)];
+                mean_host[s] = ck_vecchia_trend_mean(mean_host[s], kt, p, x.data(), 1, F->g.data() + s * p, F->beta.data());
+            }
+        }
+    }
+    return 0;
+}
+static void vecchia_trend_out(const VecchiaTrendFit& F, double* out5, double* beta_host, double* beta_cov_host) {
+    memcpy(out5, F.out5, sizeof(F.out5));
+    if (beta_host) memcpy(beta_host, F.beta.data(), F.beta.size() * 8);
+    if (beta_cov_host) memcpy(beta_cov_host, F.cov.data(), F.cov.size() * 8);
+}
+// ck_timings [96 ..] of a trend call (behind vecchia_report); grad_ms: the residual, k_vecchia_grad and the score sums
+static void vecchia_trend_timings(ck_handle* h, const VecchiaLdsStages& C, const VecchiaTrendFit& F, double grad_ms) {
+    h->t_ms[96] = C.rep.st.ms;
+    h->t_ms[97] = F.solve_ms;
+    h->t_ms[98] = C.rep.terms_ms + F.gram_ms;
+    h->t_ms[99] = grad_ms;
+    h->t_ms[100] = C.rep.total_ms;
+    h->t_ms[101] = (double)h->N;
+    h->t_ms[102] = (double)F.p;
+}
+
+extern "C" int ck_loglik_vecchia_trend(ck_handle* h, const int64_t* rank_host, double max_dist, int reml, double* out5,
+                                       double* beta_host, double* beta_cov_host, double* mean_host, double* var_host,
+                                       int32_t* count_host, int64_t* stats3, int64_t* info) {
+    CHKH(h);
+    const char* name = "ck_loglik_vecchia_trend";
+    if (vecchia_admit(h, name, rank_host && out5 ? nullptr : "rank_host / out5", max_dist, true)) return -1;
+    if (trend_total(h) == 0) {   // no trend: ck_loglik_vecchia, larger sets included
+        double out3[3];
+        if (vecchia_value(h, name, rank_host, max_dist, out3, mean_host, var_host, count_host, stats3, info)) return -1;
+        const double o5[5] = {out3[0], out3[1], out3[0] == out3[0] ? 0.0 : NAN, out3[2], out3[2]};
+        memcpy(out5, o5, sizeof(o5));
+        return 0;
+    }
+    const auto t_begin = std::chrono::steady_clock::now();
+    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    DevTemps tmp;
+    VecchiaLdsStages C;
+    if (vecchia_lds_stages(h, name, CK_VT_REFUSED_FOR, rank_host, max_dist, nullptr, tmp, &C)) return -1;
+    VecchiaTrendFit F;
+    if (vecchia_trend_fit(h, name, reml != 0, tmp, C, &F, mean_host, var_host, count_host)) return -1;
+    vecchia_trend_out(F, out5, beta_host, beta_cov_host);
+    if (info) *info = F.first_bad;
+    C.rep.solve_ms = F.solve_ms;
+    C.rep.total_ms = ms_since(t_begin);
+    vecchia_report(h, C.rep, stats3);   // (n_tiled, grow_ms: 0 -- every set is of the LDS class)
+    vecchia_trend_timings(h, C, F, 0.0);
+    return 0;
+}
+
+// The gradient of the profiled value at beta = beta-hat (the envelope theorem): the stages of the value call, then
+// k_vecchia_residual and ck_loglik_vecchia_grad's phase 2 and score sums on the residual.
+extern "C" int ck_loglik_vecchia_trend_grad(ck_handle* h, const int64_t* rank_host, double max_dist, const int32_t* free13,
+                                            double* out5, double* beta_host, double* beta_cov_host, double* grad13,
+                                            double* score_host, int64_t* stats3, int64_t* info) {
+    CHKH(h);
+    const char* name = "ck_loglik_vecchia_trend_grad";
+    if (vecchia_admit(h, name, rank_host && out5 && grad13 ? nullptr : "rank_host / out5 / grad13", max_dist, true)) return -1;
+    if (trend_total(h) == 0) {   // no trend: ck_loglik_vecchia_grad
+        double out3[3];
+        if (ck_loglik_vecchia_grad(h, rank_host, max_dist, free13, out3, grad13, score_host, stats3, info)) return -1;
+        const double o5[5] = {out3[0], out3[1], out3[0] == out3[0] ? 0.0 : NAN, out3[2], out3[2]};
+        memcpy(out5, o5, sizeof(o5));
+        return 0;
+    }
+    const auto t_begin = std::chrono::steady_clock::now();
+    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    const int NP = CK_FISHER_NPAR;
+    for (int k = 0; k < NP; ++k) grad13[k] = NAN;
+    const int64_t N = h->N;
+    DevTemps tmp;
+    VecchiaLdsStages C;
+    if (vecchia_lds_stages(h, name, CK_VT_REFUSED_FOR, rank_host, max_dist, free13, tmp, &C)) return -1;
+    VecchiaTrendFit F;
+    if (vecchia_trend_fit(h, name, 0, tmp, C, &F, nullptr, nullptr, nullptr)) return -1;
+    vecchia_trend_out(F, out5, beta_host, beta_cov_host);
+    if (info) *info = F.first_bad;
+    double grad_ms = 0.0;
+    if (F.first_bad) {   // no beta-hat, so no residual: every score is NaN
+        if (score_host)
+            for (int64_t e = 0; e < N * NP; ++e) score_host[e] = NAN;
+    } else {
+        double *d_res = nullptr, *d_score = nullptr;
+        HIPCHK(tmp.get(&d_res, (size_t)h->Npad * 8));
+        HIPCHK(tmp.get(&d_score, (size_t)(N * NP) * 8));
+        CkVecchiaTrendBeta B{};
+        for (int j = 0; j < F.p; ++j) B.b[j] = F.beta[(size_t)j];
+        ck_launch_vecchia_residual(h->stream, h->Npad, F.p, h->z, h->d_trendX, B, d_res);
+        HIPCHK(hipGetLastError());
+        double ms_solve = 0.0, ms_sum = 0.0;
+        if (vecchia_grad_solve(h, tmp, C, d_res, d_score, nullptr, nullptr, nullptr, &ms_solve)) return -1;
+        if (vecchia_score_sums(h, tmp, d_score, 0, grad13, score_host, &ms_sum)) return -1;
+        grad_ms = ms_solve + ms_sum;
+    }
+    C.rep.solve_ms = F.solve_ms;
+    C.rep.total_ms = ms_since(t_begin);
+    vecchia_report(h, C.rep, stats3);   // (n_tiled, grow_ms: 0 -- every set is of the LDS class)
+    vecchia_trend_timings(h, C, F, grad_ms);
+    return 0;
+}
+
+// the per-datum solve of the trend calls alone (the test surface of k_vecchia_trend): mu = v . y, v . v and g = v . U (N x p)
+// in the caller's stacked order, zeros where the set is empty
+extern "C" int ck_debug_vecchia_trend(ck_handle* h, const int64_t* rank_host, double max_dist, double* mu_host, double* vv_host,
+                                      double* g_host) {
+    CHKH(h);
+    const char* name = "ck_debug_vecchia_trend";
+    if (vecchia_admit(h, name, rank_host && mu_host && vv_host && g_host ? nullptr : "rank_host / mu_host / vv_host / g_host",
+                      max_dist, true))
+        return -1;
+    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    DevTemps tmp;
+    VecchiaLdsStages C;
+    if (vecchia_lds_stages(h, name, CK_VT_REFUSED_FOR, rank_host, max_dist, nullptr, tmp, &C)) return -1;
+    VecchiaTrendFit F;
+    if (vecchia_trend_solve(h, tmp, C, &F)) return -1;
+    memcpy(mu_host, F.mu.data(), (size_t)h->N * 8);
+    memcpy(vv_host, F.vv.data(), (size_t)h->N * 8);
+    memcpy(g_host, F.g.data(), (size_t)(h->N * F.p) * 8);
+    write_select_timings(h, C.rep.st);
     return 0;
 }
 

@@ -8,6 +8,7 @@
 #include "ck_math.h"
 #include "ck_vecchia_grad.h"
 #include "ck_vecchia_info.h"
+#include "ck_vecchia_trend.h"
 
 #define CK_NB 512   // outer block column width (panel width)
 #define CK_IB 64    // inner block (diagonal factor / row solves)
@@ -417,6 +418,33 @@ struct CkVecchiaInfoArgs {
 int ck_vecchia_info_run();
 void ck_launch_vecchia_info(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, CkVecchiaInfoArgs A);
 void ck_launch_vecchia_info_sum(hipStream_t s, int64_t n_rows, const double* rows, double* part, double* out91);
+// The Vecchia likelihood with a GLS trend (ck_loglik_vecchia_trend; ck_vecchia_trend.h).  ck_launch_vecchia_trend: k_local_solve's
+// steps on sets of at most ck_local_lds_limit() data, points [0, m), with the p = Tr.p0 + Tr.p1 trend rows riding along (Tr.f0
+// unused): mu = v . y, vv = v . v (ck_loglik_vecchia's bits) and g (m x p) = v . U_j per point; a point with an empty set is left
+// as it was, one whose system is not positive definite gets NaN.  ck_launch_vecchia_trend_terms: ck_launch_vecchia_terms plus
+// every datum's row (CkVecchiaTrendRows) in the caller's stacked order.  ck_launch_vecchia_trend_gram: out_tri (CK_VT_NTRI
+// doubles) = the lower triangle of sum_t r_t r_t^T by a fixed tree (part: CK_VT_NTRI x ceil(n / 256) doubles).
+// ck_launch_vecchia_residual: out = z - sum_j beta_j X[j] over npad sites of the internal order.
+struct CkVecchiaTrendRows {
+    int p;
+    int64_t npad;
+    const double* X;     // d_trendX: p rows of npad doubles, internal site order
+    const int* gself;    // every datum's own internal site index, stacked order
+    const double* g;     // n x p, stacked order
+    double* rows;        // n x (1 + p), stacked order
+};
+struct CkVecchiaTrendBeta {
+    double b[CK_VT_PMAX];
+};
+struct CkLocalTrend;   // below: the universal form of the local predictor
+void ck_launch_vecchia_trend(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, CkLocalTrend Tr, double* mu,
+                             double* vv, double* g);
+void ck_launch_vecchia_trend_terms(hipStream_t s, int64_t n, const double* z, const double* mu, const double* vv, const double* prior,
+                                   const double* noise, const int* cnt2, CkVecchiaTrendRows T, double* mean, double* var,
+                                   double* part, long long* bad, double* out2, long long* info);
+void ck_launch_vecchia_trend_gram(hipStream_t s, int64_t n, int p, const double* rows, double* part, double* out_tri);
+void ck_launch_vecchia_residual(hipStream_t s, int64_t npad, int p, const double* z, const double* X, CkVecchiaTrendBeta B,
+                                double* out);
 
 // Large neighbourhoods (k > k_hi above): the "tiled" path.  The systems of a batch are factored TOGETHER,
 // 64 columns per step, by launches over all systems that still have columns left (diagonal block + its

@@ -36,6 +36,10 @@
 //   k_vecchia_grad_part / k_vecchia_grad_sum   vg_tree
 //   k_vecchia_info      k_vecchia_grad's calls up to the back substitution, then the product D b, the forward substitution and
 //                       the combination (ck_vecchia_info.h);  k_vecchia_info_part / k_vecchia_info_sum: vg_tree, 7 x 13 columns
+//   k_vecchia_trend     k_local_solve's calls with the p trend rows of k_local_solve_u riding along, then mu, v . v and the first
+//                       column of the Gram matrix (ck_loglik_vecchia_trend);  k_vecchia_trend_terms: k_vecchia_terms plus a
+//                       datum's row (ck_vecchia_trend.h);  k_vecchia_trend_gram: G = R^T R, 256 rows per workgroup, then
+//                       k_vecchia_info_sum on 12 x 13 columns;  k_vecchia_residual: z - X beta for k_vecchia_grad
 // The Vecchia likelihood (ck_loglik_vecchia) runs the prediction kernels with the data as the points and one more predicate
 // in the search: only sites that come earlier in the caller's ordering (lp_later).
 #include "ck_internal.h"
@@ -1456,12 +1460,14 @@ __global__ __launch_bounds__(LP_TPB) void k_vecchia_info_part(long n, const doub
     vg_tree([&](int c) { return t < n ? rows[t * CK_VI_NTRI + c0 + c] : 0.0; }, part + (long)blockIdx.x * CK_VI_NTRI + c0);
 }
 
-__global__ __launch_bounds__(LP_TPB) void k_vecchia_info_sum(long nblk, const double* __restrict__ part, double* __restrict__ out91) {
+// (ld: the doubles of a row of part -- 91 here, the padded triangle of k_vecchia_trend_gram there)
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_info_sum(long nblk, int ld, const double* __restrict__ part,
+                                                              double* __restrict__ out91) {
     const int c0 = CK_VG_NPAR * blockIdx.x;
     vg_tree(
         [&](int c) {
             double v = 0.0;
-            for (long e = threadIdx.x; e < nblk; e += LP_TPB) v += part[e * CK_VI_NTRI + c0 + c];
+            for (long e = threadIdx.x; e < nblk; e += LP_TPB) v += part[e * ld + c0 + c];
             return v;
         },
         out91 + c0);
@@ -1478,5 +1484,145 @@ void ck_launch_vecchia_info_sum(hipStream_t s, int64_t n_rows, const double* row
     if (n_rows <= 0) return;
     const long nblk = (long)((n_rows + LP_TPB - 1) / LP_TPB);
     k_vecchia_info_part<<<dim3((unsigned)nblk, CK_VI_NTRI / CK_VG_NPAR), dim3(LP_TPB), 0, s>>>((long)n_rows, rows, part);
-    k_vecchia_info_sum<<<dim3(CK_VI_NTRI / CK_VG_NPAR), dim3(LP_TPB), 0, s>>>(nblk, part, out91);
+    k_vecchia_info_sum<<<dim3(CK_VI_NTRI / CK_VG_NPAR), dim3(LP_TPB), 0, s>>>(nblk, CK_VI_NTRI, part, out91);
+}
+
+// ---------------------------------------------------------------------------------------
+// the Vecchia likelihood with a GLS trend (ck_loglik_vecchia_trend; include/cokrige.h has the definition, ck_vecchia_trend.h a
+// datum's arithmetic)
+// ---------------------------------------------------------------------------------------
+// k_vecchia_trend: one workgroup per datum, sets of at most LP_KL data, the system and its 2 + p riding rows in dynamic LDS as
+// in k_local_solve_u.  Steps 1 - 4 are k_local_solve's: the same calls of the same device functions with the same arguments
+// (the neighbour list under lp_compact's capacity guard, as in k_vecchia_grad), and the p trend rows behind c and z change no
+// operation on the rows in front of them -- so mu and v . v come out with ck_loglik_vecchia's bits.  Of the Gram matrix of the
+// solved rows only the first column is formed: thread j adds g_j = v . U_j over the set in its order.  An empty set returns
+// at once (the outputs are cleared by the caller); a system that is not positive definite writes NaN.
+// k_vecchia_trend_terms: k_vecchia_terms with the row r_t = (e_t, f_t) / s_t behind it (ck_vecchia_trend_row), one thread per
+// datum in the caller's stacked order; the sums of log s^2 go through vt_tree, so they have ck_loglik_vecchia's bits.
+// k_vecchia_trend_gram: G = R^T R.  A workgroup stages the rows of LP_TPB consecutive data in LDS and thread e < (p + 1)(p + 2) / 2
+// adds its entry over them in order; the workgroups' triangles (padded to CK_VT_NTRI = 12 x 13) are added by
+// k_vecchia_info_sum: vg_tree in the partial-sum order of the scores.  No atomics: repeated calls give the same bits.
+// k_vecchia_residual: r_s = z_s - sum_j beta_j X[j][s] over the internal site order -- the values k_vecchia_grad then reads.
+#include "ck_vecchia_trend.h"
+
+static_assert(CK_VT_PMAX == CK_LU_PMAX && CK_VT_NTRI % CK_VG_NPAR == 0 && CK_VT_NTRI <= LP_TPB &&
+                  CK_VT_NTRI >= CK_VT_ROW * (CK_VT_ROW + 1) / 2,
+              "the triangle of G: one thread per entry, whole groups of vg_tree's 13 columns");
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_trend(CkLocalProblem P, const int* __restrict__ counts, CkLocalTrend Tr,
+                                                           double* __restrict__ mu, double* __restrict__ vv,
+                                                           double* __restrict__ g) {
+    extern __shared__ __attribute__((aligned(16))) double vt_lds[];   // (LP_KL + nx) x LP_KL matrix
+    __shared__ int idx[LP_KL];
+    const int tid = threadIdx.x;
+    const int np = Tr.p0 + Tr.p1, nx = np + 2;
+    const long p = blockIdx.x;
+    const int k = counts[p];
+    if (k == 0 || k > LP_KL) return;   // empty: nothing to solve; larger: refused by the host before any launch
+    double* S = vt_lds;
+    const long ld = LP_KL;
+    const LpPoint X = lp_point(P, p);
+    lp_compact<false, LP_KL>(P, X, idx);       // 1. neighbour list (the count is the select pass's: never beyond k)
+    lp_triangle(P, X, idx, S, ld, k);          // 2. local covariance, c row, z row, trend rows, noise
+    lp_cz_rows(P, X, idx, S, ld, k);
+    for (int e = tid; e < np * k; e += LP_TPB) {
+        const int j = e / k, a = e - j * k;
+        S[(long)(k + 2 + j) * ld + a] = Tr.X[(long)j * P.L.npad + idx[a]];
+    }
+    lp_noise(P, idx, S, ld, k);
+    if (!lp_chol(S, ld, k, nx)) {              // 3. Cholesky, the nx extra rows ride along
+        if (tid == 0) mu[p] = vv[p] = NAN;
+        if (tid < np) g[p * np + tid] = NAN;
+        return;
+    }
+    double vy, v2;                             // 4. mu = v . y, v . v, and the first column of the Gram matrix
+    lp_dots(S + (long)k * ld, S + (long)(k + 1) * ld, k, &vy, &v2);
+    if (tid == 0) {
+        mu[p] = vy;
+        vv[p] = v2;
+    }
+    if (tid < np) {
+        const double *v = S + (long)k * ld, *u = S + (long)(k + 2 + tid) * ld;
+        double acc = 0.0;
+        for (int a = 0; a < k; ++a) acc += v[a] * u[a];
+        g[p * np + tid] = acc;
+    }
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_trend_terms(long n, const double* __restrict__ z, const double* __restrict__ mu,
+                                                                 const double* __restrict__ vv, const double* __restrict__ prior,
+                                                                 const double* __restrict__ noise, const int* __restrict__ cnt2,
+                                                                 CkVecchiaTrendRows T, double* __restrict__ mean,
+                                                                 double* __restrict__ var, double* __restrict__ part,
+                                                                 long long* __restrict__ bad) {
+    const long t = (long)blockIdx.x * LP_TPB + threadIdx.x;
+    double lv = 0.0, qd = 0.0;
+    long long b = 0;
+    if (t < n) {
+        double m, s2;   // (the row goes straight to global memory: a local array indexed by j would live in scratch)
+        if (ck_vecchia_trend_row(z[t], mu[t], vv[t], prior[t], noise ? noise[t] : 0.0, cnt2[2 * t] + cnt2[2 * t + 1], T.p,
+                                 T.X + T.gself[t], (long)T.npad, T.g + t * T.p, &m, &s2, &lv, &qd, T.rows + t * (T.p + 1)))
+            b = t + 1;
+        mean[t] = m;
+        var[t] = s2;
+    }
+    vt_tree(lv, qd, b, part + 2 * blockIdx.x, bad + blockIdx.x);
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_trend_gram(long n, int p, const double* __restrict__ rows,
+                                                                double* __restrict__ part) {
+    __shared__ double R[LP_TPB * CK_VT_ROW];
+    const int tid = threadIdx.x, w = p + 1;
+    const long e0 = (long)blockIdx.x * LP_TPB * w, e1 = n * w;   // the workgroup's rows are contiguous in `rows`
+    for (int e = tid; e < LP_TPB * w; e += LP_TPB) R[e] = e0 + e < e1 ? rows[e0 + e] : 0.0;
+    __syncthreads();
+    if (tid < CK_VT_NTRI) {
+        double acc = 0.0;
+        if (tid < w * (w + 1) / 2) {
+            int r, c;
+            ck_vecchia_trend_pair(tid, &r, &c);
+            for (int t = 0; t < LP_TPB; ++t) acc += R[t * w + r] * R[t * w + c];
+        }
+        part[(long)blockIdx.x * CK_VT_NTRI + tid] = acc;
+    }
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_vecchia_residual(long npad, int p, const double* __restrict__ z,
+                                                              const double* __restrict__ X, CkVecchiaTrendBeta B,
+                                                              double* __restrict__ out) {
+    const long s = (long)blockIdx.x * LP_TPB + threadIdx.x;
+    if (s >= npad) return;
+    double acc = 0.0;
+    for (int j = 0; j < p; ++j) acc += B.b[j] * X[(long)j * npad + s];
+    out[s] = z[s] - acc;
+}
+
+void ck_launch_vecchia_trend(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, CkLocalTrend Tr, double* mu,
+                             double* vv, double* g) {
+    if (m <= 0) return;
+    const size_t lds = (size_t)((LP_KL + 2 + Tr.p0 + Tr.p1) * LP_KL) * sizeof(double);   // 34 KB (p = 2) .. 41 KB (p = 16)
+    k_vecchia_trend<<<dim3((unsigned)m), dim3(LP_TPB), lds, s>>>(P, counts, Tr, mu, vv, g);
+}
+
+void ck_launch_vecchia_trend_terms(hipStream_t s, int64_t n, const double* z, const double* mu, const double* vv, const double* prior,
+                                   const double* noise, const int* cnt2, CkVecchiaTrendRows T, double* mean, double* var,
+                                   double* part, long long* bad, double* out2, long long* info) {
+    if (n <= 0) return;
+    const long nblk = (long)((n + LP_TPB - 1) / LP_TPB);
+    k_vecchia_trend_terms<<<dim3((unsigned)nblk), dim3(LP_TPB), 0, s>>>((long)n, z, mu, vv, prior, noise, cnt2, T, mean, var, part,
+                                                                        bad);
+    k_vecchia_sum<<<dim3(1), dim3(LP_TPB), 0, s>>>(nblk, part, bad, out2, info);
+}
+
+void ck_launch_vecchia_trend_gram(hipStream_t s, int64_t n, int p, const double* rows, double* part, double* out_tri) {
+    if (n <= 0) return;
+    const long nblk = (long)((n + LP_TPB - 1) / LP_TPB);
+    k_vecchia_trend_gram<<<dim3((unsigned)nblk), dim3(LP_TPB), 0, s>>>((long)n, p, rows, part);
+    k_vecchia_info_sum<<<dim3(CK_VT_NTRI / CK_VG_NPAR), dim3(LP_TPB), 0, s>>>(nblk, CK_VT_NTRI, part, out_tri);
+}
+
+void ck_launch_vecchia_residual(hipStream_t s, int64_t npad, int p, const double* z, const double* X, CkVecchiaTrendBeta B,
+                                double* out) {
+    if (npad <= 0) return;
+    k_vecchia_residual<<<dim3((unsigned)((npad + LP_TPB - 1) / LP_TPB)), dim3(LP_TPB), 0, s>>>((long)npad, p, z, X, B, out);
 }

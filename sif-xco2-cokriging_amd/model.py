@@ -321,13 +321,21 @@ class MultivariateMatern:
         ``Vecchia(..., gradient="analytic")``: then the call returns (l, dl/dtheta) -- with ``measurement_error``
         (l, dl/dtheta, dl/ds) -- in the shapes of the dense call, from ``ck_loglik_vecchia_grad`` (conditioning sets of at most
         64 data; a larger one raises the native error).  A datum whose local system is not positive definite raises
-        LinAlgError naming it."""
+        LinAlgError naming it.  A trend belongs to the configuration: with ``Vecchia(trend=...)`` the value is the profile
+        likelihood l_P, beta estimated by GLS inside it (``ck_loglik_vecchia_trend``), or with ``trend_likelihood="reml"`` the
+        restricted l_R; ``gradient=True`` then needs the profile form (``ck_loglik_vecchia_trend_grad``) and is refused for
+        "reml", which the fit differences numerically."""
         if vecchia is not None:
             if trend is not None:
-                raise ValueError("log_likelihood(vecchia=...) has no restricted (REML) form: trend must be None")
+                raise ValueError("log_likelihood(vecchia=...) has no restricted (REML) form: trend must be None -- the trend of "
+                                 "a Vecchia likelihood is part of its configuration, Vecchia(trend=..., trend_likelihood=...)")
             if gradient and getattr(vecchia, "gradient", "numeric") != "analytic":
                 raise NotImplementedError("the Vecchia likelihood has no analytic gradient yet: call it with gradient=False "
                                           "(fit_likelihood(vecchia=...) differentiates it numerically)")
+            if gradient and getattr(vecchia, "reml", False):
+                raise NotImplementedError("the restricted (REML) Vecchia likelihood has no analytic gradient: call it with "
+                                          "gradient=False (fit_likelihood(vecchia=...) takes the numeric route and differences "
+                                          "the value), or use Vecchia(trend_likelihood=\"profile\")")
             if gradient:
                 out3, g13, info, var = self._vecchia_grad_eval(mf, vecchia, dist_units, fast_dist, measurement_error, noise_scale,
                                                                _ranks, _free13)
@@ -354,11 +362,28 @@ class MultivariateMatern:
         if not isinstance(vecchia, Vecchia):
             raise ValueError(f"vecchia must be a vecchia.Vecchia, got {type(vecchia).__name__}")
         caps = vecchia.caps(self.n_procs)
-        h, _ = self._lik_assembled(mf, dist_units, fast_dist, None, measurement_error, noise_scale, assemble=False)
+        h, _ = self._lik_assembled(mf, dist_units, fast_dist, vecchia.trend, measurement_error, noise_scale, assemble=False)
         if ranks is None:
             ranks = vecchia.ranks([np.asarray(mf.fields[k].coords_main, dtype=np.float64)[:, :2] for k in range(self.n_procs)])
         h.set_local_neighbours(*caps)
+        if vecchia.trend is not None:   # (out5, info, stats): beta and beta_cov ride in stats
+            out5, beta, cov, info, st = self._vecchia_native(lambda: h.loglik_vecchia_trend(ranks, vecchia.max_dist,
+                                                                                           reml=vecchia.reml, terms=terms),
+                                                             "trend form")
+            st.update(beta=beta, beta_cov=cov)
+            return out5, info, st
         return h.loglik_vecchia(ranks, vecchia.max_dist, terms=terms)
+
+    @staticmethod
+    def _vecchia_native(call, what):
+        """``call()``; a conditioning set beyond the LDS class is reported with the way out"""
+        try:
+            return call()
+        except native.NativeError as exc:
+            if "conditioning set of more than" in str(exc):
+                raise native.NativeError(f"{exc}.  The {what} of the Vecchia likelihood is for sets of at most 64 data: use "
+                                         "smaller max_neighbours") from None
+            raise
 
     def _vecchia_grad_eval(self, mf, vecchia, dist_units, fast_dist, measurement_error, noise_scale, ranks=None, free13=None):
         """(out3, grad13, info, variances) of ``ck_loglik_vecchia_grad`` on the likelihood's handle, set up as ``_vecchia_eval``."""
@@ -366,10 +391,14 @@ class MultivariateMatern:
         if not isinstance(vecchia, Vecchia):
             raise ValueError(f"vecchia must be a vecchia.Vecchia, got {type(vecchia).__name__}")
         caps = vecchia.caps(self.n_procs)
-        h, var = self._lik_assembled(mf, dist_units, fast_dist, None, measurement_error, noise_scale, assemble=False)
+        h, var = self._lik_assembled(mf, dist_units, fast_dist, vecchia.trend, measurement_error, noise_scale, assemble=False)
         if ranks is None:
             ranks = vecchia.ranks([np.asarray(mf.fields[k].coords_main, dtype=np.float64)[:, :2] for k in range(self.n_procs)])
         h.set_local_neighbours(*caps)
+        if vecchia.trend is not None:   # the profile form: the gradient at beta-hat
+            out5, _, _, g13, info, _ = self._vecchia_native(
+                lambda: h.loglik_vecchia_trend_grad(ranks, vecchia.max_dist, free=free13), "trend form")
+            return out5, g13, info, var
         try:
             out3, g13, info, _ = h.loglik_vecchia_grad(ranks, vecchia.max_dist, free=free13)
         except native.NativeError as exc:
@@ -428,13 +457,20 @@ class MultivariateMatern:
         sets c_t and S_t = c_t + {t} of ``log_likelihood(vecchia=...)`` -- the expected negative Hessian of the Vecchia
         objective under the exact model, what GpGp reports with its fits; not a Godambe sandwich.  It equals the dense
         information when every earlier datum is in every set.  Conditioning sets of at most 64 data (a larger one raises the
-        native error); ``trend`` is refused (no REML form).  The call works whatever ``vecchia.information`` says."""
+        native error); ``trend`` is refused (no REML form).  The call works whatever ``vecchia.information`` says.  With
+        ``Vecchia(trend=...)`` in its profile form the same matrix is returned -- under the Gaussian model it does not depend on
+        the mean and the theta and beta blocks are orthogonal, so it is computed without the trend -- together with
+        ``beta_cov`` = Cov(beta-hat) of the trend call; ``trend_likelihood="reml"`` raises NotImplementedError."""
         if vecchia is not None:
             from .vecchia import Vecchia
             if trend is not None:
-                raise ValueError("information(vecchia=...) has no restricted (REML) form: trend must be None")
+                raise ValueError("information(vecchia=...) has no restricted (REML) form: trend must be None -- see "
+                                 "Vecchia(trend=...)")
             if not isinstance(vecchia, Vecchia):
                 raise ValueError(f"vecchia must be a vecchia.Vecchia, got {type(vecchia).__name__}")
+            if vecchia.reml:
+                raise NotImplementedError("the restricted (REML) Vecchia likelihood has no expected information: use "
+                                          "Vecchia(trend_likelihood=\"profile\")")
             caps = vecchia.caps(self.n_procs)
         h, var = self._lik_assembled(mf, dist_units, fast_dist, trend, measurement_error, noise_scale, assemble=vecchia is None)
         names13 = information_slot_names(self.n_procs)
@@ -481,7 +517,13 @@ class MultivariateMatern:
             scales = resolve_measurement_error(measurement_error, noise_scale, mf.fields)[1]
             for k in range(self.n_procs):
                 est[11 + k] = scales[k]
-        return summarize_information(fisher, self.n_procs, live, est, at_bound=bound)
+        inf = summarize_information(fisher, self.n_procs, live, est, at_bound=bound)
+        if vecchia is not None and vecchia.trend is not None:
+            # the profile form: under the Gaussian model I^V does not depend on the mean and the theta and beta blocks are
+            # orthogonal, so the matrix above (computed without the trend) stands; Cov(beta-hat) comes from the trend call
+            st = self._vecchia_eval(mf, vecchia, dist_units, fast_dist, measurement_error, noise_scale, ranks)[2]
+            inf.beta_cov = st["beta_cov"]
+        return inf
 
     def fit_likelihood(self, mf, guess: MaternParams = None, fixed=None, dist_units: str = "km", fast_dist: bool = True,
                        trend=None, measurement_error=None, noise_scale=None, fit_noise_scale: bool = False,
@@ -520,13 +562,22 @@ class MultivariateMatern:
         ``std_errors=True`` is refused (the Fisher information is not configured) unless the configuration says
         ``Vecchia(..., information="expected")``: then ``fit_result.information``, ``.std_error``, ``.conf_int()`` and
         ``.at_bound`` are filled as after a dense fit, from ``information(vecchia=...)`` at the optimum on the fit's ranks --
-        the expected information of the Vecchia objective under the exact model, for conditioning sets of at most 64 data."""
+        the expected information of the Vecchia objective under the exact model, for conditioning sets of at most 64 data.
+        ``Vecchia(trend=...)``: beta is estimated by GLS at every evaluation (``ck_loglik_vecchia_trend``); the profile form with
+        the analytic gradient makes one native call per evaluation, ``trend_likelihood="reml"`` is differenced numerically.
+        ``fit_result.method`` is "Vecchia-ML" or "Vecchia-REML" and ``fit_result.beta`` / ``.beta_cov`` hold the trend at the
+        optimum (None for every other fit); ``std_errors=True`` works with the profile form (``information``) and is refused
+        for "reml"."""
         from .noise import resolve_measurement_error
         from .trend import check_trend
         check_trend(trend)
         if vecchia is not None:
             if trend is not None:
-                raise ValueError("fit_likelihood(vecchia=...) has no restricted (REML) form: trend must be None")
+                raise ValueError("fit_likelihood(vecchia=...) has no restricted (REML) form: trend must be None -- see "
+                                 "Vecchia(trend=..., trend_likelihood=...)")
+            if std_errors and getattr(vecchia, "reml", False):
+                raise NotImplementedError("std_errors=True needs the Fisher information, which the restricted (REML) Vecchia "
+                                          "likelihood does not have: use Vecchia(trend_likelihood=\"profile\")")
             if std_errors and getattr(vecchia, "information", "none") != "expected":
                 raise NotImplementedError("std_errors=True needs the Fisher information: configure the expected information of "
                                           "the Vecchia likelihood with Vecchia(..., information=\"expected\"), or fit with "
@@ -608,7 +659,9 @@ class MultivariateMatern:
                     gs[k] = gu[nf + j] / (sc[k] * s_width)
             return ll, g, gs
 
-        analytic_v = vecchia is not None and getattr(vecchia, "gradient", "numeric") == "analytic"
+        # (the restricted form of a trend is value-only: it takes the numeric route whatever the configuration says)
+        analytic_v = (vecchia is not None and getattr(vecchia, "gradient", "numeric") == "analytic"
+                      and not getattr(vecchia, "reml", False))
         free13 = np.zeros(13, dtype=bool)   # the live slots of ck_loglik_vecchia_grad: the free parameters, the fitted scales
         free13[free] = True
         for k in s_free:
@@ -662,9 +715,13 @@ class MultivariateMatern:
         self.params.set_values(theta)
         ll, g, gs = loglik(res.x)
         self.fit_result = FittedLikelihood(self, ll, g, free, state["n_eval"], state["n_not_pd"], res,
-                                           method="Vecchia-ML" if vecchia is not None else "ML" if trend is None else "REML",
+                                           method=("Vecchia-REML" if getattr(vecchia, "reml", False) else "Vecchia-ML")
+                                           if vecchia is not None else "ML" if trend is None else "REML",
                                            noise_scale=scales_of(res.x),
                                            noise_gradient=None if var is None else gs, noise_free=s_free)
+        if vecchia is not None and getattr(vecchia, "trend", None) is not None:   # the trend at the optimum
+            st = self._vecchia_eval(mf, vecchia, dist_units, fast_dist, measurement_error, scales_of(res.x), v_ranks)[2]
+            self.fit_result.beta, self.fit_result.beta_cov = st["beta"], st["beta_cov"]
         if std_errors:
             # a parameter within 1e-8 of its bound width from a bound: conditioned on (no normal approximation on a boundary)
             u = np.asarray(res.x, dtype=float)
@@ -712,6 +769,9 @@ class FittedLikelihood:
         self.information = None
         self.std_error = None
         self.at_bound = None
+        # fit_likelihood(vecchia=Vecchia(trend=...)): the GLS trend coefficients at the optimum and their covariance A^-1
+        self.beta = None
+        self.beta_cov = None
 
     def conf_int(self, level: float = 0.95):
         """``information.conf_int(level)``; None without ``std_errors=True``."""
@@ -798,6 +858,7 @@ class ParameterInformation:
         self.not_identified = list(not_identified)
         self.at_bound = list(at_bound)
         self.positive_definite = bool(positive_definite)
+        self.beta_cov = None   # information(vecchia=Vecchia(trend=...)): Cov(beta-hat) = A^-1 of the profiled trend
 
     def conf_int(self, level: float = 0.95):
         """estimate -+ z std_error with z the normal quantile of (1 + level) / 2: a DataFrame (lower, upper) by name."""

@@ -82,6 +82,11 @@ _PROTOS = {
     "ck_loglik_vecchia_grad": [c_void_p, POINTER(c_int64), c_double, POINTER(c_int32), _dp, _dp, _dp, POINTER(c_int64),
                                POINTER(c_int64)],
     "ck_loglik_vecchia_fisher": [c_void_p, POINTER(c_int64), c_double, POINTER(c_int32), _dp, POINTER(c_int64), POINTER(c_int64)],
+    "ck_loglik_vecchia_trend": [c_void_p, POINTER(c_int64), c_double, c_int, _dp, _dp, _dp, _dp, _dp, POINTER(c_int32),
+                                POINTER(c_int64), POINTER(c_int64)],
+    "ck_loglik_vecchia_trend_grad": [c_void_p, POINTER(c_int64), c_double, POINTER(c_int32), _dp, _dp, _dp, _dp, _dp,
+                                     POINTER(c_int64), POINTER(c_int64)],
+    "ck_debug_vecchia_trend": [c_void_p, POINTER(c_int64), c_double, _dp, _dp, _dp],
     "ck_predict_local_universal": [c_void_p, c_int, _dp, c_int64, _dp, c_double, c_int, _dp, _dp, _dp, POINTER(c_int64),
                                    POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
     "ck_vario_begin": [c_void_p, _dp, _dp, c_int64, _dp, _dp, c_int64, c_int],
@@ -763,6 +768,75 @@ class Handle:
         _chk(lib().ck_timings(self._h, _p(out), 94))
         keys = ["select_ms", "kernel_ms", "reduce_ms", "total_ms", "n_data", "n_entries"]
         return dict(zip(keys, out[88:94].tolist()))
+
+    def _ranks_arg(self, rank):
+        r = np.ascontiguousarray(rank, dtype=np.int64).reshape(-1)
+        n = int(sum(self._n_data.values()))
+        if r.size != n:
+            raise ValueError(f"rank has {r.size} entries, the handle {n} data")
+        return r, n
+
+    def loglik_vecchia_trend(self, rank, max_dist, reml=False, terms=False):
+        """Vecchia log-likelihood with the trend of set_trend estimated by GLS inside it (include/cokrige.h:
+        ck_loglik_vecchia_trend): the profile value, or with ``reml`` the restricted one, for conditioning sets of at most 64
+        data.  Returns (out5, beta, beta_cov, info, stats): out5 = (l, sum log s_t^2, log|A|, Q, yy); beta (p) and beta_cov
+        (p, p) over the trend columns of both processes; all NaN with info = 1 + the first datum without a term; stats as
+        loglik_vecchia (with ``terms`` the mean under the fitted trend, var and count).  Without a trend it is loglik_vecchia."""
+        r, n = self._ranks_arg(rank)
+        p = sum(self._trend_p.values())
+        out5, st, info = np.zeros(5), np.zeros(3, dtype=np.int64), c_int64(0)
+        beta, cov = np.zeros(p), np.zeros((p, p))
+        mean = np.empty(n) if terms else None
+        var = np.empty(n) if terms else None
+        count = np.zeros((n, 2), dtype=np.int32) if terms else None
+        _chk(lib().ck_loglik_vecchia_trend(self._h, r.ctypes.data_as(POINTER(c_int64)), float(max_dist), int(bool(reml)), _p(out5),
+                                           _p(beta) if p else None, _p(cov) if p else None,
+                                           _p(mean) if terms else None, _p(var) if terms else None,
+                                           count.ctypes.data_as(POINTER(c_int32)) if terms else None,
+                                           st.ctypes.data_as(POINTER(c_int64)), byref(info)))
+        stats = dict(n_empty=int(st[0]), k_max=int(st[1]), n_capped=int(st[2]))
+        if terms:
+            stats.update(mean=mean, var=var, count=count)
+        return out5, beta, cov, info.value, stats
+
+    def loglik_vecchia_trend_grad(self, rank, max_dist, free=None, scores=False):
+        """The profile value of loglik_vecchia_trend with its analytic gradient at beta-hat (include/cokrige.h:
+        ck_loglik_vecchia_trend_grad).  Returns (out5, beta, beta_cov, grad13, info, stats): out5 and beta have the value call's
+        bits; grad13, ``free`` and ``scores`` as loglik_vecchia_grad."""
+        r, n = self._ranks_arg(rank)
+        p = sum(self._trend_p.values())
+        fr = None
+        if free is not None:
+            fr = np.ascontiguousarray(np.asarray(free).astype(bool), dtype=np.int32)
+            if fr.shape != (13,):
+                raise ValueError("free: 13 flags, one per slot")
+        out5, grad, st, info = np.zeros(5), np.zeros(13), np.zeros(3, dtype=np.int64), c_int64(0)
+        beta, cov = np.zeros(p), np.zeros((p, p))
+        score = np.empty((n, 13)) if scores else None
+        _chk(lib().ck_loglik_vecchia_trend_grad(self._h, r.ctypes.data_as(POINTER(c_int64)), float(max_dist),
+                                                fr.ctypes.data_as(POINTER(c_int32)) if fr is not None else None, _p(out5),
+                                                _p(beta) if p else None, _p(cov) if p else None, _p(grad),
+                                                _p(score) if scores else None, st.ctypes.data_as(POINTER(c_int64)), byref(info)))
+        stats = dict(n_empty=int(st[0]), k_max=int(st[1]), n_capped=int(st[2]))
+        if scores:
+            stats["score"] = score
+        return out5, beta, cov, grad, info.value, stats
+
+    def debug_vecchia_trend(self, rank, max_dist):
+        """(mu, vv, g) of every datum's local solve with the trend rows riding along (include/cokrige.h: ck_debug_vecchia_trend):
+        v . y, v . v (N each) and U^T v (N, p) in the stacked order."""
+        r, n = self._ranks_arg(rank)
+        p = sum(self._trend_p.values())
+        mu, vv, g = np.empty(n), np.empty(n), np.zeros((n, max(p, 1)))
+        _chk(lib().ck_debug_vecchia_trend(self._h, r.ctypes.data_as(POINTER(c_int64)), float(max_dist), _p(mu), _p(vv), _p(g)))
+        return mu, vv, g[:, :p] if p else np.zeros((n, 0))
+
+    def vecchia_trend_timings(self):
+        """ck_timings [96 ..] of the last loglik_vecchia_trend() / _trend_grad() call (milliseconds; the last two are counts)."""
+        out = np.zeros(103)
+        _chk(lib().ck_timings(self._h, _p(out), 103))
+        keys = ["select_ms", "solve_ms", "terms_gram_ms", "grad_ms", "total_ms", "n_data", "p"]
+        return dict(zip(keys, out[96:103].tolist()))
 
     def local_reserve(self, nbytes: int = 0):
         """Pre-size the scratch slab of predict_local (0: the automatic budget) -- include/cokrige.h: ck_local_reserve."""

@@ -7,10 +7,12 @@ import pandas as pd
 
 from . import native
 from .point_prediction import check_max_neighbours
+from .trend import check_trend
 
 ORDERINGS = ("random", "hilbert")
 GRADIENTS = ("numeric", "analytic")
 INFORMATIONS = ("none", "expected")
+TREND_LIKELIHOODS = ("profile", "reml")
 
 
 def check_ordering(ordering):
@@ -62,9 +64,14 @@ class Vecchia:
     ``log_likelihood(..., gradient=True)`` then works and the fit uses it).  ``information``: "none" (the default:
     ``fit_likelihood(..., std_errors=True)`` is refused) or "expected" (``ck_loglik_vecchia_fisher``: the fit reports the expected
     information of the Vecchia objective under the exact model and the standard errors that follow from it, for conditioning
-    sets of at most 64 data; it is what GpGp reports, not a Godambe sandwich).  Validated here, before any device work."""
+    sets of at most 64 data; it is what GpGp reports, not a Godambe sandwich).  ``trend`` (None, the default: zero mean; or
+    "constant", "linear", a callable, as ``Predictor(trend=...)``): an unknown mean X beta estimated by GLS inside the likelihood
+    (``ck_loglik_vecchia_trend``, conditioning sets of at most 64 data); ``trend_likelihood``: "profile" (the default: beta
+    profiled out of the likelihood, analytic gradient available) or "reml" (the restricted form, value only: the fit differences
+    it).  Validated here, before any device work."""
 
-    def __init__(self, max_dist, max_neighbours=None, ordering="random", seed=0, gradient="numeric", information="none"):
+    def __init__(self, max_dist, max_neighbours=None, ordering="random", seed=0, gradient="numeric", information="none",
+                 trend=None, trend_likelihood="profile"):
         if isinstance(max_dist, (bool, np.bool_)) or not isinstance(max_dist, (int, float, np.integer, np.floating)):
             raise ValueError(f"max_dist must be a number, got {max_dist!r}")
         if not np.isfinite(max_dist) or max_dist < 0:
@@ -85,6 +92,15 @@ class Vecchia:
         if not isinstance(information, str) or information not in INFORMATIONS:
             raise ValueError(f"information must be one of {INFORMATIONS}, got {information!r}")
         self.information = information
+        self.trend = check_trend(trend)
+        if not isinstance(trend_likelihood, str) or trend_likelihood not in TREND_LIKELIHOODS:
+            raise ValueError(f"trend_likelihood must be one of {TREND_LIKELIHOODS}, got {trend_likelihood!r}")
+        self.trend_likelihood = trend_likelihood
+
+    @property
+    def reml(self):
+        """True when the configuration asks for the restricted likelihood of a trend."""
+        return self.trend is not None and self.trend_likelihood == "reml"
 
     def caps(self, n_procs):
         """The pair of caps for a model of ``n_procs`` processes ((0, 0): none)."""
@@ -102,7 +118,8 @@ def _coords(mf, n_procs):
 def vecchia_terms(model, mf, vecchia, dist_units="km", fast_dist=True, measurement_error=None, noise_scale=None, ranks=None):
     """One row per datum of the Vecchia likelihood of ``mf`` under ``model``: process, index (within the process), mean and
     variance of the conditional density of the observation, n0 / n1 = the conditioning data of either process.  The frame's
-    ``attrs`` hold out3, info and the counters of the call."""
+    ``attrs`` hold out3, info and the counters of the call.  With ``Vecchia(trend=...)`` the mean is the native call's
+    mu_t + f_t^T beta-hat, out3 is that call's out5 = (l, sum log s^2, log|A|, Q, yy) and ``attrs`` also hold beta and beta_cov."""
     out3, info, st = model._vecchia_eval(mf, vecchia, dist_units, fast_dist, measurement_error, noise_scale, ranks, terms=True)
     ns = [np.asarray(mf.fields[k].values_main).size for k in range(model.n_procs)]
     df = pd.DataFrame({"process": np.repeat(np.arange(model.n_procs), ns),
@@ -110,4 +127,6 @@ def vecchia_terms(model, mf, vecchia, dist_units="km", fast_dist=True, measureme
                        "mean": st["mean"], "variance": st["var"],
                        "n0": st["count"][:, 0].astype(np.int64), "n1": st["count"][:, 1].astype(np.int64)})
     df.attrs.update(out3=out3, info=info, n_empty=st["n_empty"], k_max=st["k_max"], n_capped=st["n_capped"])
+    if vecchia.trend is not None:
+        df.attrs.update(beta=st["beta"], beta_cov=st["beta_cov"])
     return df
