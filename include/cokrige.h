@@ -597,6 +597,40 @@ int ck_debug_local_neighbours(ck_handle* h, int i, const double* pcoords_host, i
 int ck_predict_local_universal(ck_handle* h, int i, const double* pcoords_host, int64_t m, const double* f0_host,
                                double max_dist, int cv, double* pred_host, double* pred_err_host, double* beta_host,
                                int64_t* n_empty, int64_t* n_not_pd, int64_t* n_rank_def, int64_t* k_max);
+/* Block cokriging in the moving neighbourhood (gstat's block= with nmax / maxdist): the weighted mean of process i over the
+ * member sites of each of r blocks, with the standard error of that mean, from the observations around the block -- no Sigma.
+ * Block b: members x_a with weights w_a (block[a] == b; pcoords m x 2, weight m; weights need not sum to 1 and may be
+ * negative) and a search centre c_b (centres r x 2).  The neighbourhood of the block is that of the POINT c_b, by the rules
+ * of ck_predict_local with cv = 0: the radius max_dist, the caps of ck_set_local_neighbours with ties kept, the internal site
+ * order of the neighbour list.  It is not the union of the members' neighbourhoods, and there is no cross-validation of
+ * blocks.  With the k neighbours s_g and Sigma_loc = L L^T exactly as in ck_predict_local (ck_set_noise on its diagonal):
+ *   cbar_g   = sum_a w_a C_{i, proc(g)}(x_a, s_g), every term the c entry of ck_predict_local for the point x_a (the nugget
+ *              of process i where h = 0), summed in the caller's member order;
+ *   sigma_BB = sum_{a, a'} w_a w_a' C_ii(x_a, x_a') with the nugget where h = 0 (the prior term of ck_predict_blocks);
+ *   no trend:  v = L^-1 cbar, y = L^-1 z, pred = v . y, pred_err = nan_to_num(sqrt(sigma_BB - v . v)), clamped at 0;
+ *   a trend (ck_set_trend): the formulas of ck_predict_local_universal with c -> cbar, sigma_i^2 + nugget_i -> sigma_BB and
+ *              x0 -> f0[b] = sum_a w_a f_i(x_a), supplied by the caller (r x p_i; NULL when p_i = 0); beta (r x p, or NULL)
+ *              as there.  The degenerate-case rules 1 to 5 of ck_predict_local_universal hold with "point" read as "block":
+ *              an empty neighbourhood of the centre (n_empty), a local Sigma that is not positive definite (n_not_pd), a
+ *              design that cannot be met (n_rank_def), a non-finite row of f0 (NaN, in no counter).
+ * No covariance BETWEEN blocks is offered: different blocks have different neighbourhoods, so such a matrix would be no
+ * posterior covariance of anything (ck_predict_blocks on a factored Sigma gives one).
+ * Identity: with r = m, block[a] = a, weight 1 and centres = pcoords the outputs are those of ck_predict_local_universal
+ * (cv = 0) bit for bit wherever both calls solve a neighbourhood in the same size class -- always with a trend set and, without
+ * one, under the default "local_tile_min" (64) or 0; the block call has no slab kernel.
+ * Every sum has a fixed order (the members of cbar in slices of consecutive members combined in ascending order, sigma_BB in
+ * pieces of 512 pairs; no atomics): repeated calls give the same bits, whatever the batching and the order in which the
+ * caller interleaves the members of different blocks.
+ * Needs ck_set_model / ck_set_data; optional ck_set_trend, ck_set_noise, ck_set_local_neighbours.  Refused through
+ * ck_last_error, with the offending index and value: a partitioned handle; r < 1 or m outside [1, 2^31); a label outside
+ * [0, r); a block without a member; a weight, centre or member coordinate that is not finite; f0 == NULL with p_i > 0.
+ * k_max: the largest neighbourhood.  ck_timings [104 ..] describe the call. */
+int ck_predict_local_blocks(ck_handle* h, int i, const double* centres_host /* r x 2 */, int32_t r,
+                            const double* pcoords_host /* m x 2 member sites */, int64_t m,
+                            const int32_t* block_host /* m, in [0, r) */, const double* weight_host /* m */,
+                            const double* f0_host /* r x p_i block regressors, NULL when p_i = 0 */, double max_dist,
+                            double* pred_host, double* pred_err_host, double* beta_host /* r x p or NULL */,
+                            int64_t* n_empty, int64_t* n_not_pd, int64_t* n_rank_def, int64_t* k_max);
 
 /* ---- empirical (cross-)semivariogram / covariogram: src/fields.py:192-232, 378-403 ----- */
 /* Fields i and j: coords (n x 2), residuals = values minus their mean (src/fields.py:380).
@@ -748,7 +782,11 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * ck_loglik_vecchia_trend / _trend_grad (n up to 103): [96] the select passes of both processes; [97] k_vecchia_trend, both
  * processes; [98] the terms with their rows and the Gram matrix (k_vecchia_trend_terms, k_vecchia_sum, k_vecchia_trend_gram and
  * its tree); [99] the gradient call's residual, k_vecchia_grad and score sums (0 after the value call); [100] host wall clock of
- * the call; [101] data solved; [102] trend columns p.  [72 ..] and [60 ..] are filled as by ck_loglik_vecchia. */
+ * the call; [101] data solved; [102] trend columns p.  [72 ..] and [60 ..] are filled as by ck_loglik_vecchia.
+ * ck_predict_local_blocks (n up to 110): [104] the counting or select pass of the centres; [105] the LDS class (search,
+ * assembly with cbar, factorisation, outputs); [106] the tiled class; [107] the sigma_BB pass (k_block_prior_part + _sum); [108]
+ * host wall clock of the call; [109] member-neighbour covariance evaluations, sum over the blocks of q_b k_b.  [10], [14] and
+ * [60 ..] are filled as by ck_predict_local. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it

@@ -34,7 +34,7 @@
 #include "ck_vecchia.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 104
+#define CK_N_TIMINGS 110
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -3658,6 +3658,12 @@ struct LocalVecchia {
     int32_t* cnt2;        // host, m x 2: conditioning data of process 0 / 1
 };
 
+// Block cokriging's extras (ck_predict_local_blocks); null: a point call.  The points of the call are the blocks' search
+// centres; the members (lay: ck_host_local_block_layout) enter the c row and the prior variance only.
+struct LocalBlocks {
+    const CkLocalBlockLayout* lay;
+};
+
 // What a call of predict_local_impl reports: to the caller, and to ck_timings through the exported entry points
 struct LocalResult {
     int64_t n_empty = 0, n_not_pd = 0, k_max = 0;
@@ -3666,7 +3672,10 @@ struct LocalResult {
     double solve_ms = 0.0;      // assembly / factorisations / reductions,
     double reduce_ms = 0.0;     // of which the tiled class's universal reductions (universal form)
     double grow_ms = 0.0;       // host: a growth of the scratch slab, between the two device windows
-    double total_ms = 0.0;      // host: the call (universal form)
+    double total_ms = 0.0;      // host: the call (universal form, block form)
+    double lds_ms = 0.0;        // block form: the LDS class's launch inside solve_ms,
+    double prior_ms = 0.0;      // the sigma_BB pass (its own device window, in front of the solve window),
+    double cbar_evals = 0.0;    // sum_b q_b k_b: the member-neighbour covariance evaluations
     LocalSelectStats st;
 };
 // ck_timings [10] device work, [14] slab growth, [60 .. 63] the select pass (zeros after an uncapped call)
@@ -3676,8 +3685,50 @@ static void write_local_timings(ck_handle* h, const LocalResult& R) {
     write_select_timings(h, R.st);
 }
 
+// Block cokriging: the members on the device in both forms the kernels read (the site transform that prepares the centres), their
+// weights and offsets, and the r prior variances sigma_BB through the joint block predictor's pair sum (ck_blocks.hip: pieces
+// of CK_PRIOR_PIECE pairs, a fixed-order sum).  Fills the member fields of *P.  One synchronisation; *prior_ms: the device
+// window of the pass ([ev0, ev1], free again behind the counting pass).
+static int local_block_members(ck_handle* h, DevTemps& tmp, int i, const CkLocalBlockLayout& lay, int64_t r, CkLocalProblem* P,
+                               double* prior_ms) {
+    const int64_t bm = lay.mpad;
+    double *d_xy = nullptr, *d_mc = nullptr, *d_mu = nullptr, *d_w = nullptr, *d_sbb = nullptr, *d_part = nullptr;
+    int* d_bo = nullptr;
+    long long* d_poff = nullptr;
+    HIPCHK(tmp.get(&d_xy, (size_t)(2 * bm * 8)));
+    HIPCHK(tmp.get(&d_mc, (size_t)(3 * bm * 8)));
+    HIPCHK(tmp.get(&d_mu, (size_t)(3 * bm * 8)));
+    HIPCHK(tmp.get(&d_w, (size_t)(bm * 8)));
+    HIPCHK(tmp.get(&d_bo, ((size_t)r + 1) * sizeof(int)));
+    HIPCHK(tmp.get(&d_sbb, (size_t)r * 8));
+    std::vector<long long> poff;
+    const int64_t n_pieces = prior_pieces(lay.off, (int32_t)r, 0, poff);
+    HIPCHK(tmp.get(&d_poff, poff.size() * sizeof(long long)));
+    HIPCHK(tmp.get(&d_part, (size_t)n_pieces * 8));
+    HIPCHK(hipMemcpyAsync(d_xy, lay.xy.data(), (size_t)(2 * bm * 8), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_w, lay.w.data(), (size_t)(bm * 8), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_bo, lay.off.data(), ((size_t)r + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_poff, poff.data(), poff.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    ck_launch_prep_sites(h->stream, d_xy, bm, h->metric, d_mc, d_mc + bm, d_mc + 2 * bm, d_mu);
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    ck_launch_block_prior(h->stream, h->d_blk + 2 * i, h->metric, d_mc, d_mc + bm, d_mc + 2 * bm, d_w, d_bo, r, 0, d_poff, n_pieces,
+                          d_part, d_sbb, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipEventSynchronize(h->ev1));   // poff is host memory
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, prior_ms));
+    P->bo = d_bo;
+    P->mc = d_mc;
+    P->mu = d_mu;
+    P->bw = d_w;
+    P->sbb = d_sbb;
+    P->bmpad = bm;
+    return 0;
+}
+
 static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_t m, double max_dist, int cv, double* pred,
-                              double* pred_err, LocalResult* res, const LocalUniv* u, const LocalVecchia* vc = nullptr) {
+                              double* pred_err, LocalResult* res, const LocalUniv* u, const LocalVecchia* vc = nullptr,
+                              const LocalBlocks* bk = nullptr) {
     LocalResult& R = *res = LocalResult();
     if (ensure_layout(h, false)) return -1;   // sites, tables, chunk bounds -- no Sigma panels
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
@@ -3725,6 +3776,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     const bool select = local_nmax_of(h, 0) > 0 || local_nmax_of(h, 1) > 0 || vc;
     LocalPass S;
     if (local_pass(h, tmp, i, pcoords, m, max_dist, cv, select, vc ? vc->d_rs : nullptr, vc ? vc->rp : nullptr, nullptr, &S)) return -1;
+    if (bk && local_block_members(h, tmp, i, *bk->lay, m, &S.prob, &R.prior_ms)) return -1;
     const CkLocalProblem& P = S.prob;   // what every launch below is told about the call
     const int* d_cnt = S.d_cnt;
     const std::vector<int>& cnt = S.cnt;
@@ -3741,21 +3793,23 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     const int kl = ck_local_lds_limit();
     // may lie below the LDS limit: then the LDS kernel only sees k <= k_hi.  The universal form has no slab kernel: every
     // neighbourhood beyond the LDS limit takes the tiled path
-    const int k_hi = u ? std::min(h->local_tile_min, kl) : h->local_tile_min;
+    const int k_hi = (u || bk) ? std::min(h->local_tile_min, kl) : h->local_tile_min;
     CkLocalNeeds nd;   // ck_host.cpp: the slab need of every point, the tiled class largest first
     ck_host_local_needs(cnt.data(), m, kl, k_hi, up, &nd);
     long long budget = 0;
     size_t mem_free = 0;
     if (local_budget_doubles(h, &budget, &mem_free)) return -1;
     if (budget < nd.need_max) budget = nd.need_max;
-    if ((size_t)nd.need_max * 8 > mem_free) return fail(std::string(u ? "ck_predict_local_universal" : "ck_predict_local") + ": a neighbourhood of " + std::to_string(nd.k_max) + " sites does not fit the device memory");
+    if ((size_t)nd.need_max * 8 > mem_free) return fail(std::string(bk ? "ck_predict_local_blocks" : u ? "ck_predict_local_universal" : "ck_predict_local") + ": a neighbourhood of " + std::to_string(nd.k_max) + " sites does not fit the device memory");
     CkLocalPlan plan;   // slab offsets, the batches of both classes under the budget, the tiled systems
     ck_host_local_plan(cnt.data(), nd, budget, up, &plan);
     if (local_slab_grow(h, plan.slab_doubles, budget, &R.grow_ms)) return -1;
     if (plan.slab_doubles > 0) d_slab = h->local_slab;
     HIPCHK(hipEventRecord(h->ev2, h->stream));
     HIPCHK(hipMemcpyAsync(d_off, plan.off.data(), m * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    if (u)
+    if (bk)   // the universal form's two classes, with or without a trend
+        ck_launch_local_solve_b(h->stream, P, m, d_cnt, k_hi, Tr, d_out, d_out + mp, d_beta, d_stat);
+    else if (u)
         ck_launch_local_solve_u(h->stream, P, m, d_cnt, k_hi, Tr, d_out, d_out + mp, d_beta, d_stat);
     else
         for (const auto& bt : plan.batches)
@@ -3769,6 +3823,14 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
             for (hipEvent_t e : v) (void)hipEventDestroy(e);
         }
     } ev_free{ev_red};
+    std::vector<hipEvent_t> ev_cls;   // block form: the end of the LDS class's launch (ck_timings [105] / [106])
+    EvFree ev_free_cls{ev_cls};
+    if (bk) {
+        hipEvent_t e = nullptr;
+        HIPCHK(hipEventCreate(&e));
+        ev_cls.push_back(e);
+        HIPCHK(hipEventRecord(e, h->stream));
+    }
     if (!nd.tiled.empty()) {
         HIPCHK(tmp.get(&d_sys, (size_t)(plan.sys.size() * sizeof(CkLocalSys))));
         HIPCHK(tmp.get(&d_linfo, (size_t)(plan.sys.size() * sizeof(long long))));
@@ -3793,10 +3855,10 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
                 ev_red.push_back(e1);
                 HIPCHK(hipEventRecord(e0, h->stream));
                 ck_launch_local_reduce_ut(h->stream, bsys, nb, d_slab, d_linfo + tb.first, d_k0 + tb.first, i, c0var, d_out,
-                                          d_out + mp, Tr, d_beta, d_stat);
+                                          d_out + mp, Tr, d_beta, d_stat, P.sbb);
                 HIPCHK(hipEventRecord(e1, h->stream));
             } else {
-                ck_launch_local_reduce_t(h->stream, bsys, nb, d_slab, d_linfo + tb.first, c0var, d_out, d_out + mp, d_vv);
+                ck_launch_local_reduce_t(h->stream, bsys, nb, d_slab, d_linfo + tb.first, c0var, d_out, d_out + mp, d_vv, P.sbb);
             }
             HIPCHK(hipGetLastError());
         }
@@ -3817,6 +3879,14 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     R.k_max = nd.k_max;
     R.n_tiled = (int64_t)nd.tiled.size();
     R.n_empty = nd.n_empty;
+    if (bk) {
+        double t = 0;
+        HIPCHK(elapsed_ms(h->ev2, ev_cls[0], &t));
+        R.lds_ms = t;
+        for (int64_t b = 0; b < m; ++b)
+            R.cbar_evals += (double)(bk->lay->off[(size_t)b + 1] - bk->lay->off[(size_t)b]) * (double)cnt[(size_t)b];
+        R.total_ms = ms_since(t_begin);
+    }
     if (u) {
         std::vector<int> stat((size_t)m);
         HIPCHK(hipMemcpy(stat.data(), d_stat, (size_t)m * sizeof(int), hipMemcpyDeviceToHost));
@@ -3895,6 +3965,41 @@ extern "C" int ck_predict_local_universal(ck_handle* h, int i, const double* pco
         h->t_ms[52] = (double)(m - R.n_tiled);        // points of the LDS class (the empty ones among them)
         h->t_ms[53] = (double)R.n_tiled;              // points of the tiled class
     }
+    return 0;
+}
+
+// Block cokriging in the moving neighbourhood: include/cokrige.h has the definition; ck_host.cpp the member layout, ck_local.hip
+// the kernels.  The stages are predict_local_impl's, run on the blocks' centres.
+extern "C" int ck_predict_local_blocks(ck_handle* h, int i, const double* centres, int32_t r, const double* pcoords, int64_t m,
+                                       const int32_t* block, const double* weight, const double* f0, double max_dist, double* pred,
+                                       double* pred_err, double* beta, int64_t* n_empty, int64_t* n_not_pd, int64_t* n_rank_def,
+                                       int64_t* k_max) {
+    CHKH(h);
+    if (h->world != 1)
+        return fail("ck_predict_local_blocks is the single-process form: this handle is partitioned (world = " +
+                    std::to_string(h->world) + ")");
+    if (n_rank_def) *n_rank_def = 0;
+    if (i < 0 || i >= h->n_procs) return fail("process index out of range");
+    if (!centres || !pcoords || !block || !weight || !pred || !pred_err) return fail("ck_predict_local_blocks: null argument");
+    const bool trend = trend_total(h) > 0;
+    if (trend && h->trend_p[i] > 0 && !f0)
+        return fail("ck_predict_local_blocks: null block regressors f0 with a trend of p_i = " + std::to_string(h->trend_p[i]) +
+                    " columns of process " + std::to_string(i));
+    CkLocalBlockLayout lay;
+    if (ck_host_local_block_layout(centres, r, pcoords, m, block, weight, 64, &lay)) return -1;
+    for (int k = 104; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots from zero
+    const LocalUniv u{f0, beta, n_rank_def};
+    const LocalBlocks bk{&lay};
+    LocalResult R;
+    if (predict_local_impl(h, i, centres, r, max_dist, 0, pred, pred_err, &R, trend ? &u : nullptr, nullptr, &bk)) return -1;
+    local_counts_out(R, n_empty, n_not_pd, k_max);
+    write_local_timings(h, R);
+    h->t_ms[104] = R.pass_ms;                    // the counting or select pass of the centres
+    h->t_ms[105] = R.n_tiled ? R.lds_ms : R.solve_ms;           // the LDS class: search, assembly with cbar, factorisation, outputs
+    h->t_ms[106] = R.n_tiled ? R.solve_ms - R.lds_ms : 0.0;     // the tiled class (0: no block took it)
+    h->t_ms[107] = R.prior_ms;                   // the sigma_BB pass
+    h->t_ms[108] = R.total_ms;                   // host wall clock of the call
+    h->t_ms[109] = R.cbar_evals;                 // sum_b q_b k_b
     return 0;
 }
 

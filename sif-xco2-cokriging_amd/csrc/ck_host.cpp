@@ -795,6 +795,52 @@ void ck_host_local_plan(const int* cnt, const CkLocalNeeds& nd, long long budget
         &out->tbatches, &out->slab_doubles);
 }
 
+// ---- ck_predict_local_blocks: the member layout (ck_host.h) ----------------------------------------------------------------
+int ck_host_local_block_layout(const double* centres, int32_t r, const double* pcoords, int64_t m, const int32_t* block,
+                               const double* weight, int pad, CkLocalBlockLayout* out) {
+    *out = CkLocalBlockLayout();
+    const std::string name = "ck_predict_local_blocks: ";
+    if (r < 1) return ck_fail(name + "r must be >= 1, got " + std::to_string(r));
+    if (m < 1 || m > INT32_MAX) return ck_fail(name + "m must be in [1, 2^31), got " + std::to_string(m));
+    if (pad < 1) pad = 1;
+    for (int64_t e = 0; e < 2 * (int64_t)r; ++e)
+        if (!std::isfinite(centres[e]))
+            return ck_fail(name + "coordinate " + std::to_string(e % 2) + " of centre " + std::to_string(e / 2) + " is not finite (" +
+                           std::to_string(centres[e]) + ")");
+    out->off.assign((size_t)r + 1, 0);
+    for (int64_t a = 0; a < m; ++a) {
+        if (block[a] < 0 || block[a] >= r)
+            return ck_fail(name + "block label " + std::to_string(block[a]) + " of site " + std::to_string(a) + " is outside [0, " +
+                           std::to_string(r) + ")");
+        if (!std::isfinite(weight[a]))
+            return ck_fail(name + "weight of site " + std::to_string(a) + " is not finite (" + std::to_string(weight[a]) + ")");
+        for (int c = 0; c < 2; ++c)
+            if (!std::isfinite(pcoords[2 * a + c]))
+                return ck_fail(name + "coordinate " + std::to_string(c) + " of site " + std::to_string(a) + " is not finite (" +
+                               std::to_string(pcoords[2 * a + c]) + ")");
+        ++out->off[(size_t)block[a] + 1];
+    }
+    for (int32_t b = 0; b < r; ++b) {
+        const int q = out->off[(size_t)b + 1];
+        if (q == 0) return ck_fail(name + "block " + std::to_string(b) + " has no site");
+        out->q_max = std::max<int64_t>(out->q_max, q);
+        out->off[(size_t)b + 1] += out->off[(size_t)b];
+    }
+    out->mpad = (m + pad - 1) / pad * pad;
+    out->perm.resize((size_t)m);
+    out->xy.assign((size_t)(2 * out->mpad), 0.0);
+    out->w.assign((size_t)out->mpad, 0.0);
+    std::vector<int> pos(out->off.begin(), out->off.end() - 1);
+    for (int64_t a = 0; a < m; ++a) {
+        const size_t k = (size_t)pos[(size_t)block[a]]++;
+        out->perm[k] = a;
+        out->xy[2 * k] = pcoords[2 * a];
+        out->xy[2 * k + 1] = pcoords[2 * a + 1];
+        out->w[k] = weight[a];
+    }
+    return 0;
+}
+
 // ---- the Vecchia likelihood: ranks -> positions, of the data and of the sites (ck_host.h) ---------------------------------
 // ranks (distinct integers) -> positions 0 .. N - 1; two equal ranks: -1 and both data in dup
 static int vecchia_positions(const int64_t* rank, int64_t N, std::vector<int>& pos, int64_t dup[2]) {

@@ -212,6 +212,28 @@ struct CkLocalPlan {
 };
 CK_HIDDEN void ck_host_local_plan(const int* cnt, const CkLocalNeeds& nd, long long budget, int trend, CkLocalPlan* out);
 
+// ---- block cokriging in the neighbourhood: the member layout (ck_api.hip: ck_predict_local_blocks) --------------------------
+// Pure index work, no device.  block[a] in [0, r) labels member site a (pcoords: m x 2, weight: m), centres: r x 2.
+//   off     r + 1 CSR offsets: the members of block b are the grouped positions off[b] .. off[b + 1]
+//   perm    m: the caller's index of the member at each grouped position -- a stable grouping, the caller's order kept inside
+//           a block
+//   xy, w   the members' coordinate rows (mpad x 2, as the caller gave them) and weights (mpad) in grouped order, zero beyond
+//           m; mpad = m rounded up to `pad`.  The device's site transform (the one that prepares the centres and every other
+//           point of a local call) turns xy into the two forms the kernels read, the exact-formula rows and the chord vectors:
+//           the same arithmetic as for a point, which is what makes a block of one site the point itself to the bit.
+//   q_max   the largest block
+// The batch plan of the call is ck_host_local_needs / ck_host_local_plan with the r centres as the points.
+struct CkLocalBlockLayout {
+    std::vector<int> off;
+    std::vector<int64_t> perm;
+    std::vector<double> xy, w;
+    int64_t mpad = 0, q_max = 0;
+};
+// 0, or -1 with the error text set, the offender named with its index and value: r < 1, m outside [1, 2^31), a label outside
+// [0, r), a block without a member, a weight, centre or member coordinate that is not finite
+CK_HIDDEN int ck_host_local_block_layout(const double* centres, int32_t r, const double* pcoords, int64_t m, const int32_t* block,
+                                         const double* weight, int pad, CkLocalBlockLayout* out);
+
 // ---- the Vecchia likelihood: the ordering's index work (ck_api.hip: ck_loglik_vecchia, ck_loglik_vecchia_grad) --------------
 // Pure index work, no device.  rank: N = n[0] + n[1] distinct integers in the caller's stacked order (process 0, then 1); only
 // their order counts.  perm_k as in the fold plan below (ck_handle::perm); internal position of the site at position j of

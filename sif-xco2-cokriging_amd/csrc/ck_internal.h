@@ -361,6 +361,13 @@ struct CkLocalProblem {
     double cmax = 0.0;
     const double *rq = nullptr, *cp = nullptr;
     const int *rs = nullptr, *rp = nullptr;
+    // Block cokriging (ck_predict_local_blocks): the points are the blocks' search centres.  bo = r + 1 offsets into the member
+    // rows, the members grouped by block in the caller's order; mc = 3 x bmpad member coordinates (exact-formula form), mu =
+    // their chord vectors, bw = their weights; sbb = the r prior variances of the block means (in place of c0var).  All null
+    // for the point calls.
+    const int* bo = nullptr;
+    const double *mc = nullptr, *mu = nullptr, *bw = nullptr, *sbb = nullptr;
+    int64_t bmpad = 0;
 };
 // neighbour count of the points [0, m) (an uncapped call's counting pass)
 void ck_launch_local_count(hipStream_t s, const CkLocalProblem& P, int64_t m, int* counts);
@@ -481,8 +488,10 @@ void ck_launch_local_tiled_trailing(hipStream_t s, const CkLocalSys* sys, double
 // all updates from the columns to their left in ONE pass (K = g0) before the group is factored; W <= 256
 void ck_launch_local_tiled_left(hipStream_t s, const CkLocalSys* sys, double* slab, int n_active, int g0, int W,
                                 const int* kq_host);
+// sbb (here and in ck_launch_local_reduce_ut): the prior variance per point in place of c0var (block cokriging), or null
 void ck_launch_local_reduce_t(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab,
-                              const long long* info, double c0var, double* pred, double* err, double* vv /* or null */);
+                              const long long* info, double c0var, double* pred, double* err, double* vv /* or null */,
+                              const double* sbb = nullptr);
 
 // Universal cokriging in the neighbourhood (ck_predict_local_universal): the p = p0 + p1 trend rows X_loc^T ride along each
 // local factorisation like c and z, and a GLS step per point (ck_local_gls.h) follows the reduction.
@@ -508,4 +517,10 @@ void ck_launch_local_trend_rows_t(hipStream_t s, const CkLocalSys* sys, int n_sy
 // k0buf: the process-0 neighbour counts ck_launch_local_assemble_t left
 void ck_launch_local_reduce_ut(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab, const long long* info,
                                const int* k0buf, int i_pred, double c0var, double* pred, double* err, CkLocalTrend Tr,
-                               double* beta, int* status);
+                               double* beta, int* status, const double* sbb = nullptr);
+// Block cokriging in the neighbourhood (ck_predict_local_blocks), LDS class: k_local_solve_u's steps with the c row replaced by
+// cbar_g = sum_a w_a C(x_a, s_g) over the block's members (P.bo .. P.sbb set), the neighbourhood that of the block's centre.
+// No trend (Tr.p0 + Tr.p1 == 0): k_local_solve's outputs (status and beta may be null).  The tiled class: ck_launch_local_assemble_t
+// writes cbar where P.bo is set; the reductions take P.sbb.
+void ck_launch_local_solve_b(hipStream_t s, const CkLocalProblem& P, int64_t r, const int* counts, int k_hi, CkLocalTrend Tr,
+                             double* pred, double* err, double* beta, int* status);

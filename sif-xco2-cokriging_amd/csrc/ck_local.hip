@@ -31,6 +31,8 @@
 //   k_local_solve_u     universal cokriging, k <= LP_KL: lp_point lp_compact (with k0) lp_triangle lp_cz_rows, trend rows,
 //                       lp_noise lp_chol(2 + p), Gram matrix, GLS step (ck_local_gls.h);  tiled: k_local_trend_rows_t /
 //                       k_local_reduce_ut behind the tiled path
+//   k_local_solve_b     block cokriging, k <= LP_KL: k_local_solve_u's calls around the block's centre with lp_cbar_z_rows for
+//                       lp_cz_rows (cbar = the members' weighted covariances, lp_cbar_part);  tiled: k_local_search_t<true>
 //   k_vecchia_terms / k_vecchia_sum            vt_tree
 //   k_vecchia_grad      k_local_solve's calls, then back substitution and the contraction (ck_vecchia_grad.h)
 //   k_vecchia_grad_part / k_vecchia_grad_sum   vg_tree
@@ -189,6 +191,45 @@ __device__ __forceinline__ double lp_c_entry(const CkLocalProblem& P, const LpPo
     const int pa = ga >= P.L.n0p;
     return lp_cov(P, P.i_pred + pa, pa == P.i_pred, X.p0, X.p1, X.p2, X.q0, X.q1, X.q2, X.s0[ga], X.s1[ga], X.s2[ga], X.u0[ga],
                   X.u1[ga], X.u2[ga]);
+}
+
+// Block cokriging: the members [a0, a1) of a block (P.mc / P.mu / P.bw) against site ga, summed in the members' order:
+// sum_a w_a C_{i, proc(ga)}(x_a, s_ga), every term lp_c_entry's evaluation with the member in the point's place.  The first
+// term starts the sum, so a single member of weight 1 gives lp_c_entry's value itself.
+__device__ __forceinline__ double lp_cbar_part(const CkLocalProblem& P, const LpPoint& X, long ga, int a0, int a1) {
+    const int pa = ga >= P.L.n0p;
+    const double b0 = X.s0[ga], b1 = X.s1[ga], b2 = X.s2[ga], bu0 = X.u0[ga], bu1 = X.u1[ga], bu2 = X.u2[ga];
+    const double *m0 = P.mc, *m1 = P.mc + P.bmpad, *m2 = P.mc + 2 * P.bmpad;
+    const double *v0 = P.mu, *v1 = P.mu + P.bmpad, *v2 = P.mu + 2 * P.bmpad;
+    double acc = 0.0;
+    for (int a = a0; a < a1; ++a) {
+        const double t = P.bw[a] * lp_cov(P, P.i_pred + pa, pa == P.i_pred, m0[a], m1[a], m2[a], v0[a], v1[a], v2[a], b0, b1, b2,
+                                          bu0, bu1, bu2);
+        acc = a == a0 ? t : acc + t;
+    }
+    return acc;
+}
+
+// rows k (cbar) and k + 1 (z) of S for block p, k <= LP_KL.  The q k covariance evaluations are spread as (neighbour, member
+// slice) pairs: the members are cut into nsl = LP_TPB / k slices of consecutive members, thread s k + g sums slice s against
+// neighbour g into part[s k + g], and thread g adds the slices that hold a member in ascending order -- one fixed order for
+// given (q, k), so repeated calls give the same bits.  part: LP_TPB doubles of LDS.
+__device__ __forceinline__ void lp_cbar_z_rows(const CkLocalProblem& P, const LpPoint& X, long p, const int* idx, double* S, long ld,
+                                               int k, double* part) {
+    const int tid = threadIdx.x;
+    const int a0 = P.bo[p], q = P.bo[p + 1] - a0;
+    const int nsl = LP_TPB / k;
+    const int qs = (q + nsl - 1) / nsl;   // members per slice
+    const int nus = (q + qs - 1) / qs;    // slices that hold a member (<= nsl)
+    const int g = tid % k, s = tid / k;
+    if (s < nus) part[s * k + g] = lp_cbar_part(P, X, idx[g], a0 + s * qs, a0 + min(q, (s + 1) * qs));
+    __syncthreads();
+    if (tid < k) {
+        double acc = part[tid];
+        for (int s2 = 1; s2 < nus; ++s2) acc += part[s2 * k + tid];
+        S[(long)k * ld + tid] = acc;
+        S[(long)(k + 1) * ld + tid] = P.z[idx[tid]];
+    }
 }
 
 // lower triangle of the k x k local covariance into S (leading dimension ld), one entry per thread and pass
@@ -694,6 +735,9 @@ __device__ __noinline__ double lp_exact_pair(const CkMatern* m, int metric, int 
 #define LT_WL 1024   // deferred exact pairs per system and block (LDS list; beyond that they are evaluated in place)
 #define LT_AC 256
 #define LT_TPB 512   // 8 waves: with two workgroups per CU (LDS) four waves per SIMD hide the table-read latency
+// BLK (block cokriging): the point is the block's centre and the c row holds cbar, every entry the sum over all the block's
+// members in their order (lp_cbar_part)
+template <bool BLK>
 __global__ __launch_bounds__(LP_TPB) void k_local_search_t(CkLocalProblem P, const CkLocalSys* __restrict__ sys,
                                                             double* __restrict__ slab, int* __restrict__ k0out) {
     const int tid = threadIdx.x;
@@ -717,7 +761,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_search_t(CkLocalProblem P, con
         double cv0 = 0.0, zv = 0.0;
         if (a < k) {
             const long ga = idx[a];
-            cv0 = lp_c_entry(P, X, ga);
+            cv0 = BLK ? lp_cbar_part(P, X, ga, P.bo[q.p], P.bo[q.p + 1]) : lp_c_entry(P, X, ga);
             zv = P.z[ga];
         }
         S[(long)(kq - 2) * ld + a] = a == kq - 2 ? CK_LT_BIG : cv0;
@@ -869,7 +913,7 @@ __global__ __launch_bounds__(LT_TPB, 4) void k_local_assemble_t(const CkMatern* 
 __global__ __launch_bounds__(LP_TPB) void k_local_reduce_t(const CkLocalSys* __restrict__ sys, const double* __restrict__ slab,
                                                             const long long* __restrict__ info, double c0var,
                                                             double* __restrict__ pred, double* __restrict__ err,
-                                                            double* __restrict__ vv) {
+                                                            double* __restrict__ vv, const double* __restrict__ sbb) {
     const int tid = threadIdx.x;
     const CkLocalSys q = sys[blockIdx.x];
     if (info[blockIdx.x] != 0) {
@@ -879,13 +923,16 @@ __global__ __launch_bounds__(LP_TPB) void k_local_reduce_t(const CkLocalSys* __r
     const double* v = slab + q.off + (long)(q.kq - 2) * q.ld;
     double vy, v2;
     lp_dots(v, v + q.ld, q.k, &vy, &v2);
-    if (tid == 0) lp_write(q.p, vy, v2, c0var, pred, err, vv);
+    if (tid == 0) lp_write(q.p, vy, v2, sbb ? sbb[q.p] : c0var, pred, err, vv);
 }
 
 void ck_launch_local_assemble_t(hipStream_t s, const CkLocalProblem& P, const CkLocalSys* sys, int n_sys, double* slab,
                                 int* k0buf) {
     if (n_sys <= 0) return;
-    k_local_search_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(P, sys, slab, k0buf);
+    if (P.bo)
+        k_local_search_t<true><<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(P, sys, slab, k0buf);
+    else
+        k_local_search_t<false><<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(P, sys, slab, k0buf);
     const LpTab T{P.tabs, P.coefs, P.use_tab};
     const int nreg = P.L.nend > P.L.n0p ? 3 : 1;           // a second process?
     const int grid = n_sys < 512 ? n_sys : 512;            // two workgroups per CU; they walk over the systems
@@ -895,9 +942,9 @@ void ck_launch_local_assemble_t(hipStream_t s, const CkLocalProblem& P, const Ck
 }
 
 void ck_launch_local_reduce_t(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab,
-                              const long long* info, double c0var, double* pred, double* err, double* vv) {
+                              const long long* info, double c0var, double* pred, double* err, double* vv, const double* sbb) {
     if (n_sys <= 0) return;
-    k_local_reduce_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(sys, slab, info, c0var, pred, err, vv);
+    k_local_reduce_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(sys, slab, info, c0var, pred, err, vv, sbb);
 }
 
 int ck_local_lds_limit() { return LP_KL; }
@@ -957,6 +1004,21 @@ __device__ __forceinline__ void lu_finish(double* E, CkLocalTrend Tr, int i_pred
         for (int j = 0; j < np; ++j) beta[p * np + j] = bl[j];
 }
 
+// the Gram matrix G of the nx solved rows behind a k x k factor in LDS (rows k .. k + nx - 1 of S) into E: one thread per entry of
+// the lower triangle, each a sequential sum over the neighbours; ends with a barrier
+__device__ __forceinline__ void lu_gram(const double* S, long ld, int k, int nx, double* E) {
+    const int tid = threadIdx.x;
+    if (tid < LU_NPAIR(nx)) {
+        int r, c;
+        lu_pair(tid, &r, &c);
+        const double *xr = S + (long)(k + r) * ld, *xc = S + (long)(k + c) * ld;
+        double acc = 0.0;
+        for (int a = 0; a < k; ++a) acc += xr[a] * xc[a];
+        E[r * nx + c] = acc;
+    }
+    __syncthreads();
+}
+
 // LDS class: k_local_solve with k + 2 + p rows (c, z, then the trend rows); dynamic LDS sized by p
 __global__ __launch_bounds__(LP_TPB) void k_local_solve_u(CkLocalProblem P, const int* __restrict__ counts, int k_hi,
                                                            CkLocalTrend Tr, double* __restrict__ pred, double* __restrict__ err,
@@ -989,16 +1051,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_solve_u(CkLocalProblem P, cons
         if (tid == 0) lu_fill_nan(p, np, pred, err, beta, status, CK_LU_NOT_PD);
         return;
     }
-    // ---- 4. Gram matrix of the solved rows, then the GLS step ----
-    if (tid < LU_NPAIR(nx)) {
-        int r, c;
-        lu_pair(tid, &r, &c);
-        const double *xr = S + (long)(k + r) * ld, *xc = S + (long)(k + c) * ld;
-        double acc = 0.0;
-        for (int a = 0; a < k; ++a) acc += xr[a] * xc[a];
-        E[r * nx + c] = acc;
-    }
-    __syncthreads();
+    lu_gram(S, ld, k, nx, E);                  // 4. Gram matrix of the solved rows, then the GLS step
     if (tid == 0) lu_finish(E, Tr, P.i_pred, k0, k - k0, p, P.c0var, pred, err, beta, status);
 }
 
@@ -1008,6 +1061,65 @@ void ck_launch_local_solve_u(hipStream_t s, const CkLocalProblem& P, int64_t m, 
     const int np = Tr.p0 + Tr.p1;
     const size_t lds = (size_t)((LP_KL + 2 + np) * LP_KL + LU_EXTRA(np)) * sizeof(double);   // 34.9 KB (p = 2) .. 47.2 KB (p = 16)
     k_local_solve_u<<<dim3((unsigned)m), dim3(LP_TPB), lds, s>>>(P, counts, k_hi, Tr, pred, err, beta, status);
+}
+
+// Block cokriging, LDS class (ck_predict_local_blocks): k_local_solve_u's steps for block p -- the neighbourhood of its centre,
+// then the same local system -- with row k holding cbar (lp_cbar_z_rows) and P.sbb[p] in place of c0var.  No trend (np == 0):
+// k_local_solve's step 4, its tree and its outputs (status may be null).
+__global__ __launch_bounds__(LP_TPB) void k_local_solve_b(CkLocalProblem P, const int* __restrict__ counts, int k_hi,
+                                                           CkLocalTrend Tr, double* __restrict__ pred, double* __restrict__ err,
+                                                           double* __restrict__ beta, int* __restrict__ status) {
+    extern __shared__ __attribute__((aligned(16))) double lu_lds[];   // (LP_KL + nx) x LP_KL matrix | LU_EXTRA(p)
+    __shared__ int idx[LP_KL];
+    __shared__ double part[LP_TPB];
+    const int tid = threadIdx.x;
+    const int np = Tr.p0 + Tr.p1, nx = np + 2;
+    const long p = blockIdx.x;
+    const int k = counts[p];
+    if (k == 0) {
+        if (tid == 0) {
+            if (np) lu_fill_nan(p, np, pred, err, beta, status, CK_LU_EMPTY);
+            else lp_write_nan(p, pred, err);
+        }
+        return;
+    }
+    if (k > LP_KL || k > k_hi) return;   // the tiled path
+    double* S = lu_lds;
+    double* E = lu_lds + (LP_KL + nx) * LP_KL;
+    const long ld = LP_KL;
+    const LpPoint X = lp_point(P, p);          // the block's centre
+    int k0;                                    // 1. neighbour list; k0 = neighbours of process 0
+    lp_compact<true, 0>(P, X, idx, &k0);
+    lp_triangle(P, X, idx, S, ld, k);          // 2. local covariance, cbar row, z row, trend rows, noise
+    lp_cbar_z_rows(P, X, p, idx, S, ld, k, part);
+    for (int e = tid; e < np * k; e += LP_TPB) {
+        const int j = e / k, a = e - j * k;
+        S[(long)(k + 2 + j) * ld + a] = Tr.X[(long)j * P.L.npad + idx[a]];
+    }
+    lp_noise(P, idx, S, ld, k);
+    if (!lp_chol(S, ld, k, nx)) {              // 3. Cholesky, the nx extra rows ride along
+        if (tid == 0) {
+            if (np) lu_fill_nan(p, np, pred, err, beta, status, CK_LU_NOT_PD);
+            else lp_write_nan(p, pred, err);
+        }
+        return;
+    }
+    if (np == 0) {                             // 4. simple cokriging: pred = v . y, var = sigma_BB - v . v
+        double vy, v2;
+        lp_dots(S + (long)k * ld, S + (long)(k + 1) * ld, k, &vy, &v2);
+        if (tid == 0) lp_write(p, vy, v2, P.sbb[p], pred, err, nullptr);
+        return;
+    }
+    lu_gram(S, ld, k, nx, E);                  // 4. Gram matrix of the solved rows, then the GLS step
+    if (tid == 0) lu_finish(E, Tr, P.i_pred, k0, k - k0, p, P.sbb[p], pred, err, beta, status);
+}
+
+void ck_launch_local_solve_b(hipStream_t s, const CkLocalProblem& P, int64_t r, const int* counts, int k_hi, CkLocalTrend Tr,
+                             double* pred, double* err, double* beta, int* status) {
+    if (r <= 0) return;
+    const int np = Tr.p0 + Tr.p1;
+    const size_t lds = (size_t)((LP_KL + 2 + np) * LP_KL + LU_EXTRA(np)) * sizeof(double);   // k_local_solve_u's, + 2 KB of partials
+    k_local_solve_b<<<dim3((unsigned)r), dim3(LP_TPB), lds, s>>>(P, counts, k_hi, Tr, pred, err, beta, status);
 }
 
 // Tiled class: behind k_local_search_t (which has written identity rows up to kq - 2) the p rows [kq - 2 - p, kq - 2)
@@ -1030,7 +1142,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_reduce_ut(const CkLocalSys* __
                                                              const long long* __restrict__ info, const int* __restrict__ k0in,
                                                              int i_pred, double c0var, double* __restrict__ pred,
                                                              double* __restrict__ err, CkLocalTrend Tr, double* __restrict__ beta,
-                                                             int* __restrict__ status) {
+                                                             int* __restrict__ status, const double* __restrict__ sbb) {
     __shared__ double tile[2 + CK_LU_PMAX][65];
     __shared__ double E[LU_EXTRA(CK_LU_PMAX)];
     const int tid = threadIdx.x;
@@ -1061,7 +1173,7 @@ __global__ __launch_bounds__(LP_TPB) void k_local_reduce_ut(const CkLocalSys* __
     __syncthreads();
     if (tid == 0) {
         const int k0 = k0in[blockIdx.x];
-        lu_finish(E, Tr, i_pred, k0, q.k - k0, q.p, c0var, pred, err, beta, status);
+        lu_finish(E, Tr, i_pred, k0, q.k - k0, q.p, sbb ? sbb[q.p] : c0var, pred, err, beta, status);
     }
 }
 
@@ -1072,10 +1184,10 @@ void ck_launch_local_trend_rows_t(hipStream_t s, const CkLocalSys* sys, int n_sy
 
 void ck_launch_local_reduce_ut(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab, const long long* info,
                                const int* k0buf, int i_pred, double c0var, double* pred, double* err, CkLocalTrend Tr, double* beta,
-                               int* status) {
+                               int* status, const double* sbb) {
     if (n_sys <= 0) return;
     k_local_reduce_ut<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(sys, slab, info, k0buf, i_pred, c0var, pred, err, Tr, beta,
-                                                                     status);
+                                                                     status, sbb);
 }
 
 // ---------------------------------------------------------------------------------------

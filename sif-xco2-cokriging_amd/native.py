@@ -89,6 +89,8 @@ _PROTOS = {
     "ck_debug_vecchia_trend": [c_void_p, POINTER(c_int64), c_double, _dp, _dp, _dp],
     "ck_predict_local_universal": [c_void_p, c_int, _dp, c_int64, _dp, c_double, c_int, _dp, _dp, _dp, POINTER(c_int64),
                                    POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
+    "ck_predict_local_blocks": [c_void_p, c_int, _dp, c_int32, _dp, c_int64, POINTER(c_int32), _dp, _dp, c_double, _dp, _dp, _dp,
+                                POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
     "ck_vario_begin": [c_void_p, _dp, _dp, c_int64, _dp, _dp, c_int64, c_int],
     "ck_vario_extent": [c_void_p, c_double, _dp, _dp, POINTER(c_int64)],
     "ck_vario_bin": [c_void_p, c_double, _dp, c_int, c_int, _dp, POINTER(c_int64)],
@@ -666,6 +668,43 @@ class Handle:
         _chk(lib().ck_timings(self._h, _p(out), 54))
         keys = ["count_ms", "factor_ms", "reduce_ms", "total_ms", "n_lds", "n_tiled"]
         return dict(zip(keys, out[48:54].tolist()))
+
+    def predict_local_blocks(self, i, centres, pcoords, block, weight, f0=None, max_dist=1e3, want_beta=False):
+        """Block cokriging of process i in the moving neighbourhood (include/cokrige.h: ck_predict_local_blocks): the weighted
+        means over the members of r = len(centres) blocks, each from the neighbourhood of its search centre.  block[a] in [0, r)
+        names the block of member site a, weight[a] its weight; f0: (r, p_i) block regressors sum_a w_a f_i(x_a) under a trend.
+        Returns (pred, err, info) like predict_local_universal, r values each.  No covariance between blocks exists here."""
+        cc = _f64(centres, 2)
+        pc = _f64(pcoords, 2)
+        r, m = cc.shape[0], pc.shape[0]
+        b = np.ascontiguousarray(block, dtype=np.int32).ravel()
+        w = _f64(weight).ravel()
+        if b.size != m or w.size != m:
+            raise ValueError("pcoords, block and weight disagree in length")
+        p = sum(self._trend_p.values())
+        pi = self._trend_p.get(int(i), 0)
+        F0 = None
+        if pi > 0 and f0 is not None:   # a missing f0 is the library's refusal
+            F0 = _f64(f0)
+            if F0.shape != (r, pi):
+                raise ValueError(f"f0 has shape {F0.shape}, expected {(r, pi)}")
+        pred, err = np.empty(r), np.empty(r)
+        beta = np.full((r, p), np.nan) if want_beta else None
+        ne, npd, nrd, km = c_int64(0), c_int64(0), c_int64(0), c_int64(0)
+        _chk(lib().ck_predict_local_blocks(self._h, int(i), _p(cc), r, _p(pc), m, b.ctypes.data_as(POINTER(c_int32)), _p(w),
+                                           _p(F0) if F0 is not None else None, float(max_dist), _p(pred), _p(err),
+                                           _p(beta) if want_beta and p else None, byref(ne), byref(npd), byref(nrd), byref(km)))
+        info = dict(n_empty=ne.value, n_not_pd=npd.value, n_rank_def=nrd.value, k_max=km.value)
+        if want_beta:
+            info["beta"] = beta
+        return pred, err, info
+
+    def local_blocks_timings(self):
+        """ck_timings [104 ..] of the last predict_local_blocks() call (milliseconds; the last is a count)."""
+        out = np.zeros(110)
+        _chk(lib().ck_timings(self._h, _p(out), 110))
+        keys = ["count_ms", "lds_ms", "tiled_ms", "prior_ms", "total_ms", "cbar_evals"]
+        return dict(zip(keys, out[104:110].tolist()))
 
     def set_local_neighbours(self, n0: int, n1: int = 0):
         """Nearest-neighbour cap per process of the local predictor (include/cokrige.h: ck_set_local_neighbours); 0 = none."""

@@ -15,7 +15,9 @@ Differences from the reference, none in the arithmetic:
   * ``trend=`` (not in the reference): ordinary / universal cokriging in the moving neighbourhood -- the unknown mean is
     estimated by GLS in every neighbourhood and its uncertainty is part of ``pred_err``;
   * ``max_neighbours=`` (not in the reference): a nearest-neighbour cap per process inside ``max_dist``, so that the radius
-    can be chosen for coverage of sparse regions instead of for cost.
+    can be chosen for coverage of sparse regions instead of for cost;
+  * ``predict_blocks`` (not in the reference): weighted means over blocks of sites with the standard error of the mean,
+    from the neighbourhood of each block's search centre; no covariance between blocks.
 """
 from __future__ import annotations
 
@@ -211,6 +213,106 @@ class Predictor:
             return ds
         except TypeError:
             return ds.assign_coords(coords={"time": np.datetime64(ts)})
+
+    # -- areal means in the moving neighbourhood ---------------------------------------------------
+    _spatial_trend = _JointPredictor._spatial_trend   # what _postprocess_blocks reads of the class it is borrowed from
+
+    def _block_centres(self, pc, codes, labels, centres):
+        """(r, 2) search centres in the order of ``labels``.  None: the unweighted mean position of every block's members --
+        on the sphere the normalised mean of their unit vectors, else the coordinate mean."""
+        r = len(labels)
+        if centres is None:
+            n_b = np.bincount(codes, minlength=r)
+            if metric_of(self.dist_units, self.fast_dist) != 0:   # Euclidean
+                return np.column_stack([np.bincount(codes, weights=pc[:, c], minlength=r) / n_b for c in range(2)])
+            la, lo = np.radians(pc[:, 0]), np.radians(pc[:, 1])
+            u = np.column_stack([np.cos(la) * np.cos(lo), np.cos(la) * np.sin(lo), np.sin(la)])
+            mu = np.column_stack([np.bincount(codes, weights=u[:, c], minlength=r) / n_b for c in range(3)])
+            nrm = np.linalg.norm(mu, axis=1)
+            if np.any(nrm < 1e-12):
+                bad = labels[int(np.flatnonzero(nrm < 1e-12)[0])]
+                raise ValueError(f"the members of block {bad!r} have no mean direction on the sphere (their unit vectors "
+                                 "cancel); pass its search centre through centres=")
+            mu /= nrm[:, None]
+            return np.column_stack([np.degrees(np.arcsin(np.clip(mu[:, 2], -1.0, 1.0))), np.degrees(np.arctan2(mu[:, 1], mu[:, 0]))])
+        if hasattr(centres, "keys"):
+            missing = [lab for lab in labels if lab not in centres]
+            if missing:
+                raise ValueError(f"centres has no entry for block {missing[0]!r}")
+            cc = np.array([np.asarray(centres[lab], dtype=np.float64).ravel()[:2] for lab in labels], dtype=np.float64)
+        else:
+            cc = np.atleast_2d(np.asarray(centres, dtype=np.float64))
+        if cc.shape != (r, 2):
+            raise ValueError(f"centres has shape {cc.shape}, expected {(r, 2)}: one (lat, lon) per block, sorted labels' order")
+        if not np.all(np.isfinite(cc)):
+            bad = labels[int(np.flatnonzero(~np.all(np.isfinite(cc), axis=1))[0])]
+            raise ValueError(f"the search centre of block {bad!r} is not finite")
+        return np.ascontiguousarray(cc)
+
+    def predict_blocks(self, i: int, pcoords, blocks, weights=None, max_dist: float = 1e3, centres=None,
+                       postprocess: bool = True):
+        """Weighted means of process ``i`` over blocks of sites, each with the standard error of the mean, from the data
+        around the block -- block cokriging in a moving neighbourhood (gstat's ``block=`` with ``nmax`` / ``maxdist``;
+        include/cokrige.h: ck_predict_local_blocks).  No Sigma is needed, so this is the areal product for data beyond the
+        size of the joint predictor.
+
+        ``blocks[a]`` names the block of site ``pcoords[a]`` (any hashable; NaN / None leaves the site out), ``weights[a]``
+        its weight (default 1 / n_b).  The neighbourhood of a block is that of its search centre, a POINT: the data within
+        ``max_dist`` of it, under ``max_neighbours`` -- not the union of the members' neighbourhoods.  ``centres``: None (the
+        unweighted mean position of the members; on the sphere the normalised mean of their unit vectors), an (r, 2) array
+        in the order of the sorted labels, or a mapping label -> (lat, lon).  ``max_dist`` should reach well beyond the
+        block's own extent.
+
+        The standard error accounts for the correlation between the members; the ``pred_err`` of a block's points cannot be
+        combined into it.  No covariance BETWEEN blocks is offered: different blocks have different neighbourhoods, so such a
+        matrix would be the posterior covariance of nothing (``joint_prediction.Predictor.predict_blocks`` has one).
+
+        Honours ``trend=`` (block regressors sum_a w_a f(i, x_a); ``trend_coef`` becomes (r, p)), ``measurement_error=`` /
+        ``noise_scale=`` and ``max_neighbours=``; ``info`` and the warnings are those of ``predict_arrays``.  Returns a
+        DataFrame indexed by the sorted labels with ``pred``, ``pred_err``, ``n_sites``, ``lat``, ``lon`` (the weighted
+        centroid), as the joint method; ``postprocess=True`` is its arithmetic too."""
+        if self.devices is not None and len(self.devices) > 1:
+            raise NotImplementedError(f"predict_blocks runs on one device; this predictor has devices={self.devices}")
+        if isinstance(i, bool) or not (isinstance(i, (int, np.integer)) and 0 <= int(i) < self.n_procs):
+            raise ValueError(f"process index {i!r} out of range for {self.n_procs} processes")
+        pc, codes, w, labels, _ = _JointPredictor._block_layout(pcoords, blocks, weights)
+        r = len(labels)
+        cc = self._block_centres(pc, codes, labels, centres)
+        h = self._capped_handle()
+        F0 = None
+        if self.trend is not None:
+            coords = [np.asarray(self.mf.fields[k].coords_main, dtype=np.float64)[:, :2] for k in range(self.n_procs)]
+            design = TrendDesign(self.trend, coords)
+            F = [design.data(k, coords[k]) for k in range(self.n_procs)]
+            Fm = design(i, pc)
+            F0 = np.column_stack([np.bincount(codes, weights=w * Fm[:, j], minlength=r) for j in range(Fm.shape[1])]) \
+                if Fm.shape[1] else np.zeros((r, 0))
+            for k in range(self.n_procs):
+                h.set_trend(k, F[k])
+        pred, err, info = h.predict_local_blocks(i, cc, pc, codes, w, f0=F0, max_dist=max_dist, want_beta=self.trend is not None)
+        self.trend_coef = info.pop("beta", None)
+        info["n_capped"] = int(h.timings()["local_n_capped"]) if self.max_neighbours is not None else 0
+        self.info = info
+        if info["n_empty"]:
+            warnings.warn(f"No data within maximum distance {max_dist} at {info['n_empty']} location(s).")
+        if info["n_not_pd"]:
+            warnings.warn(f"Local covariance matrix not positive definte at {info['n_not_pd']} location(s);"
+                          " returning NaN.")
+        if info.get("n_rank_def"):
+            warnings.warn(f"Trend not estimable from the data within maximum distance {max_dist} at {info['n_rank_def']}"
+                          " location(s); returning NaN. Use a larger max_dist or a smaller trend.")
+        n_sites = np.bincount(codes, minlength=r)
+        sw = np.bincount(codes, weights=w, minlength=r)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            lat = np.bincount(codes, weights=w * pc[:, 0], minlength=r) / sw
+            lon = np.bincount(codes, weights=w * pc[:, 1], minlength=r) / sw
+        if postprocess:
+            self.i = i
+            pred, err, _ = _JointPredictor._postprocess_blocks(self, pc, codes, w, r, pred, err, None)
+        index = labels.copy()
+        if index.nlevels == 1:
+            index.name = "block"
+        return pd.DataFrame({"pred": pred, "pred_err": err, "n_sites": n_sites, "lat": lat, "lon": lon}, index=index)
 
     def cross_validation(self, i: int, max_dist: float = 1e3, partitions: int = None,
                          postprocess: bool = True) -> pd.DataFrame:
