@@ -632,6 +632,57 @@ int ck_predict_local_blocks(ck_handle* h, int i, const double* centres_host /* r
                             double* pred_host, double* pred_err_host, double* beta_host /* r x p or NULL */,
                             int64_t* n_empty, int64_t* n_not_pd, int64_t* n_rank_def, int64_t* k_max);
 
+/* Conditional simulation in the moving neighbourhood (gstat's nsim with nmax / maxdist: sequential Gaussian simulation): draws of
+ * process i at m sites from the data around each site and the sites drawn before it -- no Sigma, no limit on m but memory.
+ * Definition.  The m sites carry distinct integer ranks (rank_host; only their order counts).  Stack the sites behind the data
+ * of process i as noise-free pseudo-data: every datum precedes every site, site t precedes site u iff rho_t < rho_u.  The
+ * conditioning set of site t is that of ck_loglik_vecchia on this augmented data set: per process q the candidates are the
+ * earlier members within max_dist -- for q = i data AND earlier sites together, for q != i data only -- cut by the cap nmax_q
+ * of ck_set_local_neighbours with ties kept (the cap counts data and already simulated sites alike, gstat's rule).  A site
+ * behaves exactly like a noise-free datum of process i: C(0) = sigma_i^2 + nugget_i.  The local system:
+ *   Sigma_loc = L L^T over the set (ck_set_noise's s d on the data's diagonal, nothing on the sites'), c = the covariances with
+ *   site t, w = Sigma_loc^-1 c, s_t^2 = sigma_i^2 + nugget_i - c . w (raw), mu_t^data = sum over the DATA of the set of w_a z_a;
+ *   Y[d, t] = mu_t^data + sum over the earlier SITES u of the set of w_u Y[d, u] + s_t eps[d, t].
+ * An empty set gives Y = sqrt(sigma_i^2 + nugget_i) eps; empty sets are counted (stats4[0]) and are not an error.
+ * eps: noise_host (n_draws x m, the caller's site order) when given, else ck_conditional_draws' normals: Philox4x32-10, key =
+ * seed, counter = (the caller's site index, d / 2, 0, 0), cos for even d and sin for odd d -- draw d depends on (seed, site, d)
+ * only, not on n_draws, on the draw chunking (option "draw_chunk") or on the internal order.
+ * When every datum and every earlier site is in every set, Y = pred + L_S eps with L_S the Cholesky factor of the dense posterior
+ * covariance taken in rank order: the joint predictor's law.  Otherwise the ensemble mean is not ck_predict_local's pred.
+ * draws_host: n_draws x m, the caller's order.  mean_host, var_host (m, or NULL): mu_t^data and s_t^2.  count_host (m x 3, or
+ * NULL): data of process 0, data of process 1, earlier sites of the set.  stats4: sites with an empty set, the largest set,
+ * sites where a cap bound, the number of levels of the recursion (level(t) = 1 + the largest level among the earlier sites of
+ * its set; one launch per level).
+ * A site whose local system is not positive definite, or whose s_t^2 is not > 0, makes its every draw NaN, and so those of the
+ * sites that condition on it; *info = 1 + the first such site in the caller's order (0: none).  The call still returns 0 and
+ * mean / var / count stay valid for the other sites: a singular local system is reported, not repaired (two sites at the same
+ * coordinates, or a site on a noise-free datum of process i, are the caller's to set aside).
+ * Every sum has a fixed order (the data's share of the mean and the recursion in the order of the set's list, no atomics):
+ * repeated calls give the same bits.  Nothing on the handle is invalidated: the search runs on an internal copy of the data
+ * with the sites appended, built and released inside the call; a resident factor, the solved right-hand sides and the bits of
+ * ck_predict / ck_predict_local are as before.  Needs ck_set_model / ck_set_data; optional ck_set_noise, ck_set_local_neighbours.
+ * Two consequences of the internal copy: its buffers (the N + m sites, their tables, the call's temporaries) come from the
+ * device allocator, not from an arena given with ck_set_arena; and its covariance tables are built over the bounding box of
+ * data AND sites, so for a site without earlier sites in its set mu_t^data and s_t^2 equal ck_predict_local's pred and
+ * pred_err^2 to the tables' tolerance (2e-13 relative), not bit for bit.
+ * Refused through ck_last_error: a partitioned handle; a trend set on the handle; m < 1 or n_draws < 1; two equal ranks (both
+ * sites are named); a non-finite or negative max_dist; NULL pcoords_host, rank_host, draws_host, stats4 or info; after the
+ * select pass and before any solve, any conditioning set of more than 64 members (the message names how many sites have one
+ * and the largest set); too little device memory, for the weights (1 556 bytes per site) or for a chunk of two draws (the
+ * message states the amount needed and the amount free; option "sim_free_bytes" sets the latter).
+ * ck_timings [110 ..] describe the call. */
+int ck_simulate_local(ck_handle* h, int i, const double* pcoords_host, int64_t m, const int64_t* rank_host /* m, distinct */,
+                      double max_dist, int64_t n_draws, uint64_t seed, const double* noise_host /* n_draws x m or NULL */,
+                      double* draws_host /* n_draws x m, caller's order */, double* mean_host /* m or NULL: mu_t^data */,
+                      double* var_host /* m or NULL: s_t^2 */,
+                      int32_t* count_host /* m x 3 or NULL: data of 0, data of 1, earlier sites */,
+                      int64_t* stats4 /* n_empty, k_max, n_capped, n_levels */, int64_t* info);
+/* The weight kernel of ck_simulate_local alone: per site the set's members as stacked caller indices (data 0 .. N - 1, process 0
+ * then 1; a site is N + its caller index), sorted ascending on the host and padded with -1, and the weights w in the same order
+ * (0 in the padding; NaN where the local system is not positive definite). */
+int ck_debug_simulate_local_weights(ck_handle* h, int i, const double* pcoords_host, int64_t m, const int64_t* rank_host,
+                                    double max_dist, int64_t* idx_host /* m x 64 */, double* w_host /* m x 64 */);
+
 /* ---- empirical (cross-)semivariogram / covariogram: src/fields.py:192-232, 378-403 ----- */
 /* Fields i and j: coords (n x 2), residuals = values minus their mean (src/fields.py:380).
  * same != 0: marginal variogram, strict upper triangle of the i-i pairs (:195-199; j args ignored);
@@ -786,7 +837,10 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * ck_predict_local_blocks (n up to 110): [104] the counting or select pass of the centres; [105] the LDS class (search,
  * assembly with cbar, factorisation, outputs); [106] the tiled class; [107] the sigma_BB pass (k_block_prior_part + _sum); [108]
  * host wall clock of the call; [109] member-neighbour covariance evaluations, sum over the blocks of q_b k_b.  [10], [14] and
- * [60 ..] are filled as by ck_predict_local. */
+ * [60 ..] are filled as by ck_predict_local.
+ * ck_simulate_local (n up to 118): [110] the select pass of the sites on the augmented set; [111] the weights (k_local_sim_weights);
+ * [112] the level planning on the host; [113] the recursion (one launch per level and chunk, and the scatter); [114] host wall
+ * clock of the call; [115] sites solved (a non-empty set); [116] levels; [117] sum over the sites of their site-neighbours. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it
@@ -843,6 +897,8 @@ int ck_table_fallbacks(ck_handle* h, int reset, int64_t* count);
  * on (N = 40 000: 0.62 -> 0.56 ms), Sigma (K1) never (faster on one box, slower on another);
  * "draw_chunk" (default 0 = automatic: half of the free device memory, 128 .. 8192 draws): draws per product launch of
  * ck_conditional_draws;
+ * "sim_free_bytes" (default 0 = automatic: what the device reports; tests): the device memory ck_simulate_local counts as free
+ * when it admits its weights and its first chunk of draws, and sizes an automatic draw chunk;
  * "fisher_product_mb" (default 0 = automatic: what is free beside everything else the call holds): MiB the stored products of
  * ck_loglik_fisher may take -- less than all of them and they are formed in groups (the same bits);
  * "block_chunk" (default 0 = automatic: what the arena has left, or half of the free device memory, beside the point rows

@@ -34,7 +34,7 @@
 #include "ck_vecchia.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 110
+#define CK_N_TIMINGS 118
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -177,6 +177,7 @@ struct ck_handle {
     // between calls like aux; option "block_chunk": prediction sites per K2 assembly (0: from the device memory the handle may use)
     DevBuf<double> baux;
     int64_t block_chunk = 0;
+    int64_t sim_free_bytes = 0;   // option "sim_free_bytes" (tests): the device memory ck_simulate_local counts as free (0: what is free)
     int64_t draw_chunk = 0;   // option "draw_chunk": draws per product launch of ck_conditional_draws (0: from the free device memory)
     // Schur complement of the prediction sites (ck_verify_model), kept between calls with the same padded order
     struct Schur {
@@ -4361,6 +4362,309 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
 }
 
 // ---------------------------------------------------------------------------------------
+// conditional simulation in the moving neighbourhood (include/cokrige.h has the definition)
+// ---------------------------------------------------------------------------------------
+// The search runs on an AUGMENTED data set: an internal handle on the caller's device and stream that holds the caller's model,
+// metric, caps, noise and data, with the m sites appended to process i as noise-free pseudo-data of value 0.  Its precedence
+// pointers put every datum in front of every site (rs = the datum's stacked index < N; a site: N + its position in the
+// ordering), so local_pass on it is ck_loglik_vecchia's search on the augmented set.  The caller's handle is only read: no
+// existing kernel changes and no call on it can lose its bits.  The internal handle lives as long as the call.
+// The device memory a simulation call may still take: what the device reports, or option "sim_free_bytes" less what the call
+// holds already (taken) -- the option stands for the whole device, the report shrinks by itself.
+static int local_sim_free(const ck_handle* h, int64_t taken, size_t* fr) {
+    size_t tot = 0;
+    if (h->sim_free_bytes > 0)
+        *fr = (size_t)std::max<int64_t>(0, h->sim_free_bytes - taken);
+    else
+        HIPCHK(hipMemGetInfo(fr, &tot));
+    return 0;
+}
+struct HandleDeleter {
+    void operator()(ck_handle* c) const { (void)ck_destroy(c); }
+};
+struct LocalSim {
+    std::unique_ptr<ck_handle, HandleDeleter> child;
+    int64_t N = 0, m = 0;
+    std::vector<int> pos;    // the caller's site index -> position in the ordering
+    std::vector<int> ext;    // internal index of the augmented set -> the caller's stacked index (a site: N + its index)
+    LocalPass pass;
+    CkLocalSimOut out{};
+    std::vector<int> ns, spos;
+    std::vector<double> mu, s2;
+    int64_t n_empty = 0, k_max = 0, w_bytes = 0;   // w_bytes: what the weight kernel's outputs hold on the device
+    double weights_ms = 0.0;
+};
+// What both entry points (name) do up to the weight kernel: the refusals, the ordering, the augmented set, the select pass (a
+// set beyond the LDS limit is refused here, before any solve), then k_local_sim_weights and the downloads the host plans with.
+static int local_sim_stages(ck_handle* h, const std::string& name, int i, const double* pcoords, int64_t m, const int64_t* rank_host,
+                            double max_dist, const char* null_args, int64_t n_draws, DevTemps& tmp, LocalSim* out) {
+    LocalSim& C = *out;
+    if (h->world != 1)
+        return fail(name + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) + ")");
+    if (null_args) return fail(name + ": null " + null_args);
+    if (m < 1) return fail(name + ": m = " + std::to_string(m) + " sites; at least 1");
+    if (n_draws < 1) return fail(name + ": n_draws = " + std::to_string(n_draws) + "; at least 1");
+    if (!(max_dist >= 0.0) || !std::isfinite(max_dist))
+        return fail(name + ": max_dist must be finite and >= 0, got " + std::to_string(max_dist));
+    if (trend_total(h) > 0)
+        return fail(name + ": a trend of " + std::to_string(trend_total(h)) +
+                    " columns is set on the handle; the local draws take none (clear it with ck_set_trend)");
+    if (!h->model_set) return fail("ck_set_model has not been called");
+    for (int k = 0; k < h->n_procs; ++k)
+        if (!h->data_set[k]) return fail("ck_set_data missing for process " + std::to_string(k));
+    if (i < 0 || i >= h->n_procs) return fail(name + ": process index out of range");
+    const int64_t n0 = h->n[0], ni = h->n[i];
+    const int64_t N = C.N = n0 + (h->n_procs == 2 ? h->n[1] : 0);
+    C.m = m;
+    if (N <= 0) return fail("no observations");
+    if (N + m > INT32_MAX) return fail(name + ": more than 2^31 - 1 data and sites");
+    {   // the ordering of the sites
+        std::vector<int64_t> ident((size_t)m);
+        for (int64_t t = 0; t < m; ++t) ident[(size_t)t] = t;
+        const int64_t n2[2] = {m, 0};
+        CkVecchiaOrder ord;
+        if (ck_host_vecchia_order(rank_host, 1, n2, m, m, ident.data(), nullptr, &ord))
+            return fail(name + ": sites " + std::to_string(ord.dup[0]) + " and " + std::to_string(ord.dup[1]) +
+                        " have the same rank " + std::to_string((long long)rank_host[ord.dup[0]]));
+        C.pos = std::move(ord.pos);
+    }
+    // ---- the augmented set
+    {
+        ck_handle* c = nullptr;
+        if (ck_create(h->device, &c)) return -1;
+        C.child.reset(c);
+    }
+    ck_handle* c = C.child.get();
+    c->stream = h->stream;
+    c->metric = h->metric;
+    c->exact_cov = h->exact_cov;
+    c->site_order = h->site_order;
+    c->local_select_cap = h->local_select_cap;
+    c->local_nmax[0] = h->local_nmax[0];
+    c->local_nmax[1] = h->local_nmax[1];
+    memcpy(c->blk, h->blk, sizeof(h->blk));
+    c->n_procs = h->n_procs;
+    c->par_sigma[0] = h->par_sigma[0];
+    c->par_sigma[1] = h->par_sigma[1];
+    c->par_rho = h->par_rho;
+    HIPCHK(hipMemcpyAsync(c->d_blk, c->blk, 3 * sizeof(CkMatern), hipMemcpyHostToDevice, c->stream));
+    c->model_set = true;
+    for (int k = 0; k < h->n_procs; ++k) {
+        std::vector<double> co(h->h_coords[k]), va(h->h_values[k]);
+        if (k == i) {
+            co.insert(co.end(), pcoords, pcoords + 2 * m);
+            va.insert(va.end(), (size_t)m, 0.0);
+        }
+        if (ck_set_data(c, k, co.data(), va.data(), (int64_t)va.size())) return -1;
+        if (!h->noise_var[k].empty()) {
+            std::vector<double> nv(h->noise_var[k]);
+            if (k == i) nv.insert(nv.end(), (size_t)m, 0.0);   // a site is a noise-free pseudo-datum
+            if (ck_set_noise(c, k, nv.data(), (int64_t)nv.size(), h->noise_scale[k])) return -1;
+        }
+    }
+    if (ensure_layout(c, false)) return -1;
+    if (ensure_noise(c)) return -1;
+    // ---- precedence: the data in front of every site, the sites by position
+    C.ext.assign((size_t)c->Npad, -1);
+    std::vector<int> rs((size_t)c->Npad, INT32_MAX), rp((size_t)m);
+    for (int k = 0; k < c->n_procs; ++k) {
+        const int64_t off = k == 0 ? 0 : c->n0p, soff = k == 0 ? 0 : n0;
+        for (int64_t j = 0; j < c->n[k]; ++j) {
+            const int64_t e = c->perm[k][(size_t)j];
+            if (k == i && e >= ni) {
+                C.ext[(size_t)(off + j)] = (int)(N + (e - ni));
+                rs[(size_t)(off + j)] = (int)(N + C.pos[(size_t)(e - ni)]);
+            } else {
+                C.ext[(size_t)(off + j)] = rs[(size_t)(off + j)] = (int)(soff + e);
+            }
+        }
+    }
+    for (int64_t t = 0; t < m; ++t) rp[(size_t)t] = (int)(N + C.pos[(size_t)t]);
+    int* d_rs = nullptr;
+    HIPCHK(tmp.get(&d_rs, (size_t)c->Npad * sizeof(int)));
+    HIPCHK(hipMemcpyAsync(d_rs, rs.data(), (size_t)c->Npad * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    // ---- the select pass; sets beyond the LDS limit are refused before any solve
+    LocalPass& S = C.pass;
+    if (local_pass(c, tmp, i, pcoords, m, max_dist, 0, true, d_rs, rp.data(), nullptr, &S)) return -1;
+    h->t_ms[110] = S.st.ms;
+    const int kl = ck_local_lds_limit();
+    int64_t n_over = 0;
+    for (int64_t t = 0; t < m; ++t) {
+        const int kt = S.cnt[(size_t)t];
+        C.n_empty += kt == 0;
+        n_over += kt > kl;
+        C.k_max = std::max<int64_t>(C.k_max, kt);
+    }
+    if (n_over > 0)
+        return fail(name + ": " + std::to_string(n_over) + " sites have a conditioning set of more than " + std::to_string(kl) +
+                    " data (the largest: " + std::to_string(C.k_max) +
+                    "); the draws are for sets the LDS solver takes: lower the caps or the radius");
+    // ---- the weights
+    const int64_t w_bytes = m * ((int64_t)kl * (2 * sizeof(int) + 2 * 8) + 2 * 8 + sizeof(int));
+    {
+        size_t fr = 0;
+        if (local_sim_free(h, 0, &fr)) return -1;
+        if ((size_t)w_bytes > fr)
+            return fail(name + ": needs " + std::to_string(w_bytes) + " bytes of device memory for the weights of " + std::to_string(m) +
+                        " sites; " + std::to_string(fr) + " bytes are available");
+    }
+    C.w_bytes = w_bytes;
+    CkLocalSimOut& O = C.out;
+    O.n_data = (int)N;
+    HIPCHK(tmp.get(&O.gidx, (size_t)(m * kl) * sizeof(int)));
+    HIPCHK(tmp.get(&O.spos, (size_t)(m * kl) * sizeof(int)));
+    HIPCHK(tmp.get(&O.ns, (size_t)m * sizeof(int)));
+    HIPCHK(tmp.get(&O.w, (size_t)(m * kl) * 8));
+    HIPCHK(tmp.get(&O.sw, (size_t)(m * kl) * 8));
+    HIPCHK(tmp.get(&O.mu, (size_t)m * 8));
+    HIPCHK(tmp.get(&O.s2, (size_t)m * 8));
+    HIPCHK(hipEventRecord(c->ev2, c->stream));
+    ck_launch_local_sim_weights(c->stream, S.prob, m, S.d_cnt, O);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev3, c->stream));
+    C.ns.resize((size_t)m);
+    C.spos.resize((size_t)(m * kl));
+    C.mu.resize((size_t)m);
+    C.s2.resize((size_t)m);
+    HIPCHK(hipMemcpyAsync(C.ns.data(), O.ns, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(C.spos.data(), O.spos, (size_t)(m * kl) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(C.mu.data(), O.mu, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(C.s2.data(), O.s2, (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(elapsed_ms(c->ev2, c->ev3, &C.weights_ms));
+    h->t_ms[111] = C.weights_ms;
+    return 0;
+}
+
+extern "C" int ck_debug_simulate_local_weights(ck_handle* h, int i, const double* pcoords, int64_t m, const int64_t* rank_host,
+                                               double max_dist, int64_t* idx_host, double* w_host) {
+    CHKH(h);
+    for (int k = 110; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    DevTemps tmp;
+    LocalSim C;
+    if (local_sim_stages(h, "ck_debug_simulate_local_weights", i, pcoords, m, rank_host, max_dist,
+                         pcoords && rank_host && idx_host && w_host ? nullptr : "pcoords_host / rank_host / idx_host / w_host", 1, tmp, &C))
+        return -1;
+    const int kl = ck_local_lds_limit();
+    std::vector<int> gi((size_t)(m * kl));
+    std::vector<double> w((size_t)(m * kl));
+    HIPCHK(hipMemcpyAsync(gi.data(), C.out.gidx, gi.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(w.data(), C.out.w, w.size() * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<std::pair<int64_t, double>> row;
+    for (int64_t t = 0; t < m; ++t) {   // members as stacked caller indices, ascending
+        row.clear();
+        for (int a = 0; a < kl && gi[(size_t)(t * kl + a)] >= 0; ++a)
+            row.push_back({(int64_t)C.ext[(size_t)gi[(size_t)(t * kl + a)]], w[(size_t)(t * kl + a)]});
+        std::sort(row.begin(), row.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        for (int a = 0; a < kl; ++a) {
+            idx_host[t * kl + a] = a < (int)row.size() ? row[(size_t)a].first : -1;
+            w_host[t * kl + a] = a < (int)row.size() ? row[(size_t)a].second : 0.0;
+        }
+    }
+    return 0;
+}
+
+extern "C" int ck_simulate_local(ck_handle* h, int i, const double* pcoords, int64_t m, const int64_t* rank_host, double max_dist,
+                                 int64_t n_draws, uint64_t seed, const double* noise_host, double* draws_host, double* mean_host,
+                                 double* var_host, int32_t* count_host, int64_t* stats4, int64_t* info) {
+    CHKH(h);
+    const auto t_begin = std::chrono::steady_clock::now();
+    for (int k = 110; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots from zero
+    DevTemps tmp;
+    LocalSim C;
+    if (local_sim_stages(h, "ck_simulate_local", i, pcoords, m, rank_host, max_dist,
+                         pcoords && rank_host && draws_host && stats4 && info ? nullptr
+                                                                              : "pcoords_host / rank_host / draws_host / stats4 / info",
+                         n_draws, tmp, &C))
+        return -1;
+    const int kl = ck_local_lds_limit();
+    // ---- the levels of the recursion
+    const auto t_plan = std::chrono::steady_clock::now();
+    CkSimLevels lv;
+    const int64_t n_levels = ck_host_sim_levels(m, kl, C.pos.data(), C.ns.data(), C.spos.data(), &lv);
+    if (n_levels < 0)
+        return fail("ck_simulate_local: site " + std::to_string(lv.off[0]) + " conditions on position " + std::to_string(lv.off[1]) +
+                    ", which is not earlier than its own");
+    h->t_ms[112] = ms_since(t_plan);
+    int64_t first_bad = 0, n_site_nbr = 0;
+    for (int64_t t = 0; t < m; ++t) {
+        if (!first_bad && !(C.s2[(size_t)t] > 0.0)) first_bad = 1 + t;
+        n_site_nbr += C.ns[(size_t)t];
+    }
+    // ---- the recursion, chunk by chunk
+    const int64_t per_draw = m * 8 * 2;   // Y and the draws in the caller's order (the caller's noise is staged in the latter)
+    int64_t chunk = h->draw_chunk;
+    {
+        size_t fr = 0;
+        if (local_sim_free(h, C.w_bytes, &fr)) return -1;
+        const int64_t need = 2 * per_draw + 2 * m * (int64_t)sizeof(int);
+        if ((size_t)need > fr)
+            return fail("ck_simulate_local: needs " + std::to_string(need) + " bytes of device memory for a chunk of 2 draws at " +
+                        std::to_string(m) + " sites; " + std::to_string(fr) + " bytes are available");
+        if (chunk <= 0) chunk = std::min<int64_t>((int64_t)(fr / 2) / per_draw, 8192);
+    }
+    chunk = std::max<int64_t>(2, chunk & ~(int64_t)1);   // even: a thread makes the Box-Muller pair (d, d + 1)
+    chunk = std::min<int64_t>(chunk, roundup(n_draws, 2));
+    int *d_order = nullptr, *d_pos = nullptr;
+    double *d_Y = nullptr, *d_X = nullptr;
+    HIPCHK(tmp.get(&d_order, (size_t)m * sizeof(int)));
+    HIPCHK(tmp.get(&d_pos, (size_t)m * sizeof(int)));
+    HIPCHK(tmp.get(&d_Y, (size_t)(chunk * m) * 8));
+    HIPCHK(tmp.get(&d_X, (size_t)(chunk * m) * 8));
+    HIPCHK(hipMemcpyAsync(d_order, lv.order.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_pos, C.pos.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    CkLocalSimLevel A{};
+    A.pos = d_pos;
+    A.ns = C.out.ns;
+    A.spos = C.out.spos;
+    A.sw = C.out.sw;
+    A.mu = C.out.mu;
+    A.s2 = C.out.s2;
+    A.Y = d_Y;
+    A.ldy = chunk;
+    A.eps_in_y = noise_host ? 1 : 0;
+    A.seed = seed;
+    ck_handle* c = C.child.get();
+    for (int64_t d0 = 0; d0 < n_draws; d0 += chunk) {
+        const int64_t nd = std::min<int64_t>(chunk, n_draws - d0);
+        A.d0 = d0;
+        if (noise_host)   // staged where the chunk's draws will stand; the last chunk's download has ended (synchronised below)
+            HIPCHK(hipMemcpyAsync(d_X, noise_host + d0 * m, (size_t)(nd * m) * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipEventRecord(c->ev0, h->stream));
+        if (noise_host) ck_launch_local_sim_gather(h->stream, d_X, m, nd, d_pos, d_Y, chunk);
+        for (int64_t l = 0; l < n_levels; ++l)   // one launch per level, in stream order: no waiting inside a kernel
+            ck_launch_local_sim_level(h->stream, A, d_order + lv.off[(size_t)l], lv.off[(size_t)(l + 1)] - lv.off[(size_t)l]);
+        ck_launch_local_sim_scatter(h->stream, d_Y, chunk, d_pos, m, nd, d_X);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->ev1, h->stream));
+        HIPCHK(hipMemcpyAsync(draws_host + d0 * m, d_X, (size_t)(nd * m) * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->t_ms[113] += elapsed_ms(c->ev0, c->ev1);
+    }
+    // ---- the per-site outputs
+    if (mean_host) memcpy(mean_host, C.mu.data(), (size_t)m * 8);
+    if (var_host) memcpy(var_host, C.s2.data(), (size_t)m * 8);
+    if (count_host)
+        for (int64_t t = 0; t < m; ++t) {
+            const int nst = C.ns[(size_t)t];
+            count_host[3 * t] = C.pass.sel[(size_t)(4 * t)] - (i == 0 ? nst : 0);
+            count_host[3 * t + 1] = C.pass.sel[(size_t)(4 * t + 1)] - (i == 1 ? nst : 0);
+            count_host[3 * t + 2] = nst;
+        }
+    stats4[0] = C.n_empty;
+    stats4[1] = C.k_max;
+    stats4[2] = C.pass.st.n_capped;
+    stats4[3] = n_levels;
+    *info = first_bad;
+    h->t_ms[114] = ms_since(t_begin);
+    h->t_ms[115] = (double)(m - C.n_empty);
+    h->t_ms[116] = (double)n_levels;
+    h->t_ms[117] = (double)n_site_nbr;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // the Vecchia likelihood with a GLS trend: profile ML and REML (include/cokrige.h has the definition, ck_vecchia_trend.h a
 // datum's arithmetic)
 // ---------------------------------------------------------------------------------------
@@ -5472,6 +5776,11 @@ extern "C" int ck_set_option(ck_handle* h, const char* name, int64_t value) {
     if (!strcmp(name, "fisher_product_mb")) {   // ck_loglik_fisher: MiB the stored products may take (0 = automatic)
         if (value < 0) return fail("fisher_product_mb must be >= 0 (0 = automatic)");
         h->fisher_product_mb = value;
+        return 0;
+    }
+    if (!strcmp(name, "sim_free_bytes")) {   // ck_simulate_local: the bytes that count as free (0 = what the device reports)
+        if (value < 0) return fail("sim_free_bytes must be >= 0 (0 = automatic)");
+        h->sim_free_bytes = value;
         return 0;
     }
     if (!strcmp(name, "draw_chunk")) {   // ck_conditional_draws: draws per product launch (0 = automatic)

@@ -888,3 +888,48 @@ int ck_host_vecchia_order(const int64_t* rank, int n_procs, const int64_t n[2], 
     }
     return 0;
 }
+
+// ---- conditional simulation in the moving neighbourhood: the levels of the recursion -------------------------------------
+int64_t ck_host_sim_levels(int64_t m, int ld, const int32_t* pos, const int32_t* ns, const int32_t* nbr, CkSimLevels* out) {
+    *out = CkSimLevels();
+    std::vector<int32_t> at((size_t)m, -1);   // the caller's index of the site at every position
+    for (int64_t t = 0; t < m; ++t) {
+        if (pos[t] < 0 || pos[t] >= m || at[(size_t)pos[t]] != -1) {
+            out->off = {t, (int64_t)pos[t]};
+            return -1;
+        }
+        at[(size_t)pos[t]] = (int32_t)t;
+    }
+    out->level.assign((size_t)m, 0);
+    std::vector<int32_t> lev_at((size_t)m, 0);   // by position
+    int32_t n_levels = 0;
+    for (int64_t q = 0; q < m; ++q) {
+        const int64_t t = at[(size_t)q];
+        int32_t lv = 0;
+        if (ns[t] < 0 || ns[t] > ld) {
+            out->off = {t, (int64_t)ns[t]};
+            return -1;
+        }
+        for (int32_t j = 0; j < ns[t]; ++j) {
+            const int32_t u = nbr[t * ld + j];
+            if (u < 0 || u >= q) {
+                out->off = {t, (int64_t)u};
+                return -1;
+            }
+            lv = std::max(lv, lev_at[(size_t)u]);
+        }
+        lev_at[(size_t)q] = out->level[(size_t)t] = lv + 1;
+        n_levels = std::max(n_levels, lv + 1);
+    }
+    // counting sort by level; the positions are walked upwards, so a level's sites come out in ascending position
+    out->off.assign((size_t)n_levels + 1, 0);
+    for (int64_t t = 0; t < m; ++t) ++out->off[(size_t)out->level[(size_t)t]];
+    for (int32_t l = 1; l <= n_levels; ++l) out->off[(size_t)l] += out->off[(size_t)(l - 1)];
+    out->order.resize((size_t)m);
+    std::vector<int64_t> fill(out->off.begin(), out->off.end() - 1);
+    for (int64_t q = 0; q < m; ++q) {
+        const int32_t t = at[(size_t)q];
+        out->order[(size_t)fill[(size_t)(out->level[(size_t)t] - 1)]++] = t;
+    }
+    return n_levels;
+}

@@ -295,3 +295,19 @@ struct CkFoldPlan {
 // fold_max members (the messages state the amounts and name the fold)
 CK_HIDDEN int ck_host_fold_plan(int i, int n_procs, const int64_t n[2], int64_t n0p, const int64_t* perm0, const int64_t* perm1,
                                 const int32_t* fold0, const int32_t* fold1, int32_t n_folds, int fold_max, CkFoldPlan* out);
+
+// ---- conditional simulation in the moving neighbourhood: the levels of the recursion (ck_api.hip: ck_simulate_local) --------
+// Pure index work, no device.  Site t (the caller's index) sits at position pos[t] of the ordering (a permutation of 0 .. m - 1)
+// and conditions on ns[t] earlier sites, whose POSITIONS are nbr[t ld .. t ld + ns[t]).  level[t] = 1 + the largest level among
+// them, 1 without any: walking the positions upwards meets every neighbour before the site.  A level's sites depend on lower
+// levels only, so one launch per level computes them all.
+//   level   m: the caller's order
+//   order   m: the caller's indices grouped by level, ascending position inside a level
+//   off     the level l (1-based) owns order[off[l - 1] .. off[l]); n_levels + 1 entries
+struct CkSimLevels {
+    std::vector<int32_t> level, order;
+    std::vector<int64_t> off;
+};
+// the number of levels, or -1 when pos is no permutation or a neighbour is not an earlier position (out->off[0], off[1]: the
+// caller's index of the site and the offending entry)
+CK_HIDDEN int64_t ck_host_sim_levels(int64_t m, int ld, const int32_t* pos, const int32_t* ns, const int32_t* nbr, CkSimLevels* out);

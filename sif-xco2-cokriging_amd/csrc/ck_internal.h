@@ -524,3 +524,38 @@ void ck_launch_local_reduce_ut(hipStream_t s, const CkLocalSys* sys, int n_sys, 
 // writes cbar where P.bo is set; the reductions take P.sbb.
 void ck_launch_local_solve_b(hipStream_t s, const CkLocalProblem& P, int64_t r, const int* counts, int k_hi, CkLocalTrend Tr,
                              double* pred, double* err, double* beta, int* status);
+
+// Conditional simulation in the moving neighbourhood (ck_simulate_local; include/cokrige.h has the definition).  The sites are
+// the points of a pass over the AUGMENTED data set (the data, then the sites as noise-free pseudo-data of process i_pred), with
+// the precedence pointers set: P.rs < n_data for a datum, n_data + position in the ordering for a site.
+// k_local_sim_weights (one workgroup per site, sets of at most ck_local_lds_limit() members): k_vecchia_grad's steps 1 - 5 on the
+// same device functions, then the weights w = Sigma_loc^-1 c kept instead of contracted.  Per site p, rows of LP_KL entries:
+//   gidx / w    the set's members in list order (internal index of the augmented set; -1 / 0 beyond the set) and their weights
+//   spos / sw   the members that are earlier sites, in list order: their positions and weights (-1 / 0 beyond ns[p])
+//   mu          sum of w_a z_a over the data of the set, in list order;  s2 = c0var - c . w, raw
+// A local system that is not positive definite: NaN weights, mu and s2.  An empty set: mu = 0, s2 = c0var, ns = 0.
+struct CkLocalSimOut {
+    int n_data;
+    int *gidx, *spos, *ns;
+    double *w, *sw, *mu, *s2;
+};
+void ck_launch_local_sim_weights(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, CkLocalSimOut O);
+// k_local_sim_level: the sites order[0 .. n) of one level (the caller's indices), draws d0 .. d0 + nd - 1 of the call:
+//   Y[pos[t]][d] = mu[t] + sum_j sw[t][j] Y[spos[t][j]][d] (list order) + s_t eps[d][t],   s_t = sqrt(s2[t]), NaN unless s2[t] > 0
+// Y: [position][draw], ldy doubles per position (even, >= nd; the draws beyond nd are scratch).  eps: with eps_in_y what the
+// site's own row of Y holds (the caller's noise, put there by ck_launch_local_sim_gather: the reads run along the draws like
+// every other), else the Philox normals of ck_rng.h keyed on seed, counter (t, (d0 + d) / 2); d0 is even, a thread makes the
+// pair (d, d + 1).  Every input row was written by an earlier launch on the same stream: no waiting inside the kernel.
+struct CkLocalSimLevel {
+    const int *pos, *ns, *spos;
+    const double *sw, *mu, *s2;
+    double* Y;
+    long ldy, d0;
+    int eps_in_y;
+    unsigned long long seed;
+};
+void ck_launch_local_sim_level(hipStream_t s, const CkLocalSimLevel& A, const int* order, int64_t n);
+// Y (positions x ldy) <- E (nd x m, the caller's order), zeros in the draws nd .. ldy - 1
+void ck_launch_local_sim_gather(hipStream_t s, const double* E, int64_t m, int64_t nd, const int* pos, double* Y, int64_t ldy);
+// X (nd x m, the caller's order) <- Y (positions x ldy)
+void ck_launch_local_sim_scatter(hipStream_t s, const double* Y, int64_t ldy, const int* pos, int64_t m, int64_t nd, double* X);

@@ -42,9 +42,14 @@
 //                       column of the Gram matrix (ck_loglik_vecchia_trend);  k_vecchia_trend_terms: k_vecchia_terms plus a
 //                       datum's row (ck_vecchia_trend.h);  k_vecchia_trend_gram: G = R^T R, 256 rows per workgroup, then
 //                       k_vecchia_info_sum on 12 x 13 columns;  k_vecchia_residual: z - X beta for k_vecchia_grad
+//   k_local_sim_weights k_vecchia_grad's calls up to the back substitution, then the weights kept: all of the set, the earlier
+//                       sites' once more as (position, weight) rows, the data's share of the mean (ck_simulate_local);
+//                       k_local_sim_level: one level of the draws' recursion;  k_local_sim_gather / _scatter: the caller's noise
+//                       into the recursion's layout, the draws back into the caller's order
 // The Vecchia likelihood (ck_loglik_vecchia) runs the prediction kernels with the data as the points and one more predicate
 // in the search: only sites that come earlier in the caller's ordering (lp_later).
 #include "ck_internal.h"
+#include "ck_rng.h"
 #include "ck_select.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
@@ -1737,4 +1742,173 @@ void ck_launch_vecchia_residual(hipStream_t s, int64_t npad, int p, const double
                                 double* out) {
     if (npad <= 0) return;
     k_vecchia_residual<<<dim3((unsigned)((npad + LP_TPB - 1) / LP_TPB)), dim3(LP_TPB), 0, s>>>((long)npad, p, z, X, B, out);
+}
+
+// ---------------------------------------------------------------------------------------
+// conditional simulation in the moving neighbourhood (ck_simulate_local; ck_internal.h: CkLocalSimOut, CkLocalSimLevel)
+// ---------------------------------------------------------------------------------------
+// k_local_sim_weights: one workgroup per site.  Steps 1 - 5 are k_vecchia_grad's, the same calls of the same device functions;
+// then ONE wave (the set has at most 64 members, lane a holds member a) splits the set by P.rs[g] >= n_data into data and earlier
+// sites: the weights of all members go out in list order, those of the sites once more compacted by a ballot, and the data's
+// share of the mean is summed in list order by broadcasting the lanes one after the other -- every lane runs the same 64 steps,
+// so the sum has one order.  Plain vector stores, no atomics: repeated calls give the same bits.
+__global__ __launch_bounds__(LP_TPB) void k_local_sim_weights(CkLocalProblem P, const int* __restrict__ counts, CkLocalSimOut O) {
+    __shared__ double S[(LP_KL + 2) * LP_KL];
+    __shared__ int idx[LP_KL];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const long p = blockIdx.x;
+    const int k = counts[p];
+    if (k > LP_KL) return;   // refused by the host before any launch
+    int *gi = O.gidx + p * LP_KL, *sp = O.spos + p * LP_KL;
+    double *wr = O.w + p * LP_KL, *sw = O.sw + p * LP_KL;
+    if (k == 0) {   // an empty set: the prior
+        if (tid < LP_KL) {
+            gi[tid] = sp[tid] = -1;
+            wr[tid] = sw[tid] = 0.0;
+        }
+        if (tid == 0) {
+            O.mu[p] = 0.0;
+            O.s2[p] = P.c0var;
+            O.ns[p] = 0;
+        }
+        return;
+    }
+    const long ld = LP_KL;
+    const LpPoint X = lp_point(P, p);
+    lp_compact<false, LP_KL>(P, X, idx);       // 1. neighbour list (the count is the select pass's: never beyond k)
+    lp_triangle(P, X, idx, S, ld, k);          // 2. local covariance, c row, z row, noise
+    lp_cz_rows(P, X, idx, S, ld, k);
+    lp_noise(P, idx, S, ld, k);
+    const bool ok = lp_chol(S, ld, k, 2);      // 3. Cholesky, the two extra rows ride along
+    double vy, vvs;                            // 4. c . w = v . v (uniform: the sums of a failed factor are not used)
+    lp_dots(S + (long)k * ld, S + (long)(k + 1) * ld, k, &vy, &vvs);
+    if (ok) vg_back_substitute(S, ld, k);      // 5. row k becomes -w
+    if (wv != 0) return;
+    const bool in = lane < k;
+    const int g = in ? idx[lane] : -1;
+    const int r = in ? P.rs[g] : 0;
+    const bool site = in && r >= O.n_data;
+    const double wa = in ? (ok ? -S[(long)k * ld + lane] : NAN) : 0.0;
+    const double za = in && !site ? P.z[g] : 0.0;
+    const unsigned long long bal = __ballot(site);
+    const int below = __popcll(bal & ((1ULL << lane) - 1ULL)), nsite = __popcll(bal);
+    double mu = 0.0;
+    for (int a = 0; a < k; ++a) {              // the data's share of the mean, list order
+        const double t = __shfl(wa, a) * __shfl(za, a);
+        if (!(bal >> a & 1ULL)) mu += t;
+    }
+    gi[lane] = g;
+    wr[lane] = wa;
+    if (lane >= nsite) {
+        sp[lane] = -1;
+        sw[lane] = 0.0;
+    }
+    if (site) {
+        sp[below] = r - O.n_data;
+        sw[below] = wa;
+    }
+    if (lane == 0) {
+        O.mu[p] = ok ? mu : NAN;
+        O.s2[p] = ok ? P.c0var - vvs : NAN;
+        O.ns[p] = nsite;
+    }
+}
+
+void ck_launch_local_sim_weights(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, CkLocalSimOut O) {
+    if (m <= 0) return;
+    k_local_sim_weights<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(P, counts, O);
+}
+
+// k_local_sim_level: workgroup (site of the level, tile of draw pairs).  The site's row of at most 64 (position, weight) entries
+// is staged in LDS; a thread owns the draw pair (d, d + 1) and reads the neighbours' rows of Y as 16-byte words, consecutive
+// threads consecutive words.  The sum starts from mu, adds the neighbours in list order and then s eps: its bits do not depend
+// on n_draws or on the chunk.
+__global__ __launch_bounds__(LP_TPB) void k_local_sim_level(CkLocalSimLevel A, const int* __restrict__ order) {
+    __shared__ int su[LP_KL];
+    __shared__ double sw[LP_KL];
+    const int tid = threadIdx.x;
+    const long t = order[blockIdx.x];
+    const int n = A.ns[t];
+    if (tid < n) {
+        su[tid] = A.spos[t * LP_KL + tid];
+        sw[tid] = A.sw[t * LP_KL + tid];
+    }
+    __syncthreads();
+    const long d = 2 * ((long)blockIdx.y * blockDim.x + tid);
+    if (d >= A.ldy) return;
+    double a0 = A.mu[t], a1 = a0;
+    for (int j = 0; j < n; ++j) {
+        const d2_t y = *reinterpret_cast<const d2_t*>(A.Y + (long)su[j] * A.ldy + d);
+        a0 += sw[j] * y[0];
+        a1 += sw[j] * y[1];
+    }
+    double* own = A.Y + (long)A.pos[t] * A.ldy + d;
+    double e[2];
+    if (A.eps_in_y) {   // the caller's noise, put there by k_local_sim_gather
+        const d2_t ev = *reinterpret_cast<const d2_t*>(own);
+        e[0] = ev[0];
+        e[1] = ev[1];
+    } else {
+        ck_rng_normal2((uint64_t)A.seed, (uint32_t)t, (uint32_t)((A.d0 + d) >> 1), e);
+    }
+    const double v = A.s2[t];
+    const double sd = v > 0.0 ? sqrt(v) : NAN;
+    d2_t out;
+    out[0] = a0 + sd * e[0];
+    out[1] = a1 + sd * e[1];
+    *reinterpret_cast<d2_t*>(own) = out;
+}
+
+void ck_launch_local_sim_level(hipStream_t s, const CkLocalSimLevel& A, const int* order, int64_t n) {
+    if (n <= 0 || A.ldy <= 0) return;
+    const long pairs = A.ldy / 2;
+    const int tpb = pairs <= 64 ? 64 : pairs <= 128 ? 128 : LP_TPB;
+    k_local_sim_level<<<dim3((unsigned)n, (unsigned)((pairs + tpb - 1) / tpb)), dim3(tpb), 0, s>>>(A, order);
+}
+
+// X[d][t] = Y[pos[t]][d]: 32 x 32 tiles through LDS, reads along the draws, writes along the sites
+__global__ __launch_bounds__(LP_TPB) void k_local_sim_scatter(const double* __restrict__ Y, long ldy, const int* __restrict__ pos,
+                                                               long m, long nd, double* __restrict__ X) {
+    __shared__ double T[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const long t0 = (long)blockIdx.x * 32, d0 = (long)blockIdx.y * 32;
+    for (int r = ty; r < 32; r += LP_TPB / 32) {
+        const long t = t0 + r, d = d0 + tx;
+        if (t < m && d < nd) T[r][tx] = Y[(long)pos[t] * ldy + d];
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += LP_TPB / 32) {
+        const long d = d0 + r, t = t0 + tx;
+        if (t < m && d < nd) X[d * m + t] = T[tx][r];
+    }
+}
+
+// Y[pos[t]][d] = E[d][t] for d < nd, 0 in the scratch draws up to ldy: the caller's noise (nd x m, the caller's order) laid out
+// as the recursion reads it, the scatter in reverse
+__global__ __launch_bounds__(LP_TPB) void k_local_sim_gather(const double* __restrict__ E, long m, long nd, const int* __restrict__ pos,
+                                                              double* __restrict__ Y, long ldy) {
+    __shared__ double T[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const long t0 = (long)blockIdx.x * 32, d0 = (long)blockIdx.y * 32;
+    for (int r = ty; r < 32; r += LP_TPB / 32) {
+        const long d = d0 + r, t = t0 + tx;
+        T[r][tx] = (t < m && d < nd) ? E[d * m + t] : 0.0;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += LP_TPB / 32) {
+        const long t = t0 + r, d = d0 + tx;
+        if (t < m && d < ldy) Y[(long)pos[t] * ldy + d] = T[tx][r];
+    }
+}
+
+void ck_launch_local_sim_gather(hipStream_t s, const double* E, int64_t m, int64_t nd, const int* pos, double* Y, int64_t ldy) {
+    if (m <= 0 || ldy <= 0) return;
+    k_local_sim_gather<<<dim3((unsigned)((m + 31) / 32), (unsigned)((ldy + 31) / 32)), dim3(LP_TPB), 0, s>>>(E, (long)m, (long)nd, pos, Y,
+                                                                                                         (long)ldy);
+}
+
+void ck_launch_local_sim_scatter(hipStream_t s, const double* Y, int64_t ldy, const int* pos, int64_t m, int64_t nd, double* X) {
+    if (m <= 0 || nd <= 0) return;
+    k_local_sim_scatter<<<dim3((unsigned)((m + 31) / 32), (unsigned)((nd + 31) / 32)), dim3(LP_TPB), 0, s>>>(Y, (long)ldy, pos, (long)m,
+                                                                                                          (long)nd, X);
 }

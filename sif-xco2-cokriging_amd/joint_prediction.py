@@ -561,8 +561,14 @@ class Predictor:
             pcoords = pd.DataFrame({"d1": a[:, 0], "d2": a[:, 1]})
         draws, pred, err, defl, seed = self.conditional_draws_arrays(i, pcoords.values[:, :2], n_draws, seed=seed,
                                                                      noise=noise, tol=tol, jitter=jitter)
+        return self._draws_output(i, pcoords, draws, pred, err, {"seed": seed, "n_deflated": int(defl.sum()), "jitter": float(jitter)},
+                                  postprocess)
+
+    def _draws_output(self, i: int, pcoords: pd.DataFrame, draws, pred, err, attrs: dict, postprocess: bool):
+        """What a conditional simulation returns, from its arrays (also borrowed by ``point_prediction.Predictor``): the frame of
+        ``__call__`` with ``attrs``, every draw transformed as ``pred`` is, the xarray Dataset with a leading ``draw`` dimension
+        (without xarray: ``(DataFrame, draws)``)."""
         self.i = i
-        attrs = {"seed": seed, "n_deflated": int(defl.sum()), "jitter": float(jitter)}
         df = pcoords.copy()
         df["pred"], df["pred_err"] = pred, err
         if postprocess:

@@ -91,6 +91,9 @@ _PROTOS = {
                                    POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
     "ck_predict_local_blocks": [c_void_p, c_int, _dp, c_int32, _dp, c_int64, POINTER(c_int32), _dp, _dp, c_double, _dp, _dp, _dp,
                                 POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
+    "ck_simulate_local": [c_void_p, c_int, _dp, c_int64, POINTER(c_int64), c_double, c_int64, c_uint64, _dp, _dp, _dp, _dp,
+                          POINTER(c_int32), POINTER(c_int64), POINTER(c_int64)],
+    "ck_debug_simulate_local_weights": [c_void_p, c_int, _dp, c_int64, POINTER(c_int64), c_double, POINTER(c_int64), _dp],
     "ck_vario_begin": [c_void_p, _dp, _dp, c_int64, _dp, _dp, c_int64, c_int],
     "ck_vario_extent": [c_void_p, c_double, _dp, _dp, POINTER(c_int64)],
     "ck_vario_bin": [c_void_p, c_double, _dp, c_int, c_int, _dp, POINTER(c_int64)],
@@ -705,6 +708,61 @@ class Handle:
         _chk(lib().ck_timings(self._h, _p(out), 110))
         keys = ["count_ms", "lds_ms", "tiled_ms", "prior_ms", "total_ms", "cbar_evals"]
         return dict(zip(keys, out[104:110].tolist()))
+
+    def simulate_local(self, i, pcoords, rank, max_dist, n_draws, seed=0, noise=None, terms=True):
+        """Draws of process i at pcoords by sequential simulation in the moving neighbourhood (include/cokrige.h:
+        ck_simulate_local): site t is conditioned on the data and on the sites of smaller ``rank`` (m distinct integers) within
+        ``max_dist``, under the caps of set_local_neighbours.  ``noise``: (n_draws, m) normals in the caller's order, else the
+        device's Philox stream keyed on ``seed``.  Returns (draws (n_draws, m), info, stats): info = 1 + the first site whose
+        local system is not positive definite or whose variance is not > 0 (its draws, and those of the sites that condition
+        on it, are NaN), 0 otherwise; stats: n_empty, k_max, n_capped, n_levels and, with ``terms``, mean (mu_t^data), var
+        (s_t^2) and count (m, 3: data of process 0, of process 1, earlier sites)."""
+        pc = _f64(pcoords, 2)
+        m = pc.shape[0]
+        r = np.ascontiguousarray(rank, dtype=np.int64).reshape(-1)
+        if r.size != m:
+            raise ValueError(f"rank has {r.size} entries, pcoords {m} sites")
+        n_draws = int(n_draws)
+        e = None
+        if noise is not None:
+            e = _f64(noise)
+            if e.shape != (n_draws, m):
+                raise ValueError(f"noise has shape {e.shape}, expected {(n_draws, m)}")
+        draws = np.zeros((max(n_draws, 0), m))
+        mean = np.empty(m) if terms else None
+        var = np.empty(m) if terms else None
+        count = np.zeros((m, 3), dtype=np.int32) if terms else None
+        st, info = np.zeros(4, dtype=np.int64), c_int64(0)
+        _chk(lib().ck_simulate_local(self._h, int(i), _p(pc), m, r.ctypes.data_as(POINTER(c_int64)), float(max_dist), n_draws,
+                                     c_uint64(int(seed) & (2 ** 64 - 1)), _p(e) if e is not None else None, _p(draws),
+                                     _p(mean) if terms else None, _p(var) if terms else None,
+                                     count.ctypes.data_as(POINTER(c_int32)) if terms else None,
+                                     st.ctypes.data_as(POINTER(c_int64)), byref(info)))
+        stats = dict(n_empty=int(st[0]), k_max=int(st[1]), n_capped=int(st[2]), n_levels=int(st[3]))
+        if terms:
+            stats.update(mean=mean, var=var, count=count)
+        return draws, info.value, stats
+
+    def simulate_local_weights(self, i, pcoords, rank, max_dist):
+        """(idx, w), both (m, 64): every site's conditioning set as stacked caller indices (data 0 .. N - 1, a site N + its
+        index), ascending and padded with -1, and the weights w = Sigma_loc^-1 c in the same order (include/cokrige.h:
+        ck_debug_simulate_local_weights)."""
+        pc = _f64(pcoords, 2)
+        m = pc.shape[0]
+        r = np.ascontiguousarray(rank, dtype=np.int64).reshape(-1)
+        if r.size != m:
+            raise ValueError(f"rank has {r.size} entries, pcoords {m} sites")
+        idx, w = np.full((m, 64), -1, dtype=np.int64), np.zeros((m, 64))
+        _chk(lib().ck_debug_simulate_local_weights(self._h, int(i), _p(pc), m, r.ctypes.data_as(POINTER(c_int64)), float(max_dist),
+                                                   idx.ctypes.data_as(POINTER(c_int64)), _p(w)))
+        return idx, w
+
+    def simulate_local_timings(self):
+        """ck_timings [110 ..] of the last simulate_local() call (milliseconds; the last three are counts)."""
+        out = np.zeros(118)
+        _chk(lib().ck_timings(self._h, _p(out), 118))
+        keys = ["select_ms", "weights_ms", "levels_ms", "recursion_ms", "total_ms", "n_solved", "n_levels", "n_site_neighbours"]
+        return dict(zip(keys, out[110:118].tolist()))
 
     def set_local_neighbours(self, n0: int, n1: int = 0):
         """Nearest-neighbour cap per process of the local predictor (include/cokrige.h: ck_set_local_neighbours); 0 = none."""

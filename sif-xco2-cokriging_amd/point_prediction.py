@@ -314,6 +314,129 @@ class Predictor:
             index.name = "block"
         return pd.DataFrame({"pred": pred, "pred_err": err, "n_sites": n_sites, "lat": lat, "lon": lon}, index=index)
 
+    # -- conditional simulation in the moving neighbourhood ----------------------------------------
+    def conditional_draws_arrays(self, i: int, pcoords, max_dist: float, n_draws: int, seed=None, ordering="random", noise=None):
+        """Draws of process ``i`` at ``pcoords`` by sequential simulation in the moving neighbourhood -- the numeric body of
+        ``conditional_simulation`` (include/cokrige.h: ck_simulate_local; gstat's ``nsim`` with ``nmax`` / ``maxdist``).
+
+        The sites are visited in ``ordering``: "random" (the default, ``np.random.default_rng(seed).permutation``), "hilbert"
+        (along the library's Hilbert curve; far more levels of the recursion, so slower) or an array of m distinct integer ranks.
+        Every site is conditioned on the data and on the sites visited before it, within ``max_dist`` and under the Predictor's
+        ``max_neighbours`` -- the cap counts data and already simulated sites of process ``i`` alike.  A conditioning set holds
+        at most 64 members: choose the caps or the radius accordingly.
+
+        Set aside before the native call, and counted in ``sim_info["n_pinned"]``: rows of ``pcoords`` that repeat an earlier
+        row (one random variable: they get the draws of the first occurrence) and sites on a datum of process ``i`` without
+        measurement-error variance (every draw is that datum's value).  ``noise`` (n_draws, m) in the caller's sites replaces
+        the device's Philox stream (a set-aside site's column is not used); that stream is keyed on ``seed`` and on the index
+        among the sites that remain.  ``seed=None`` takes 64 bits from ``numpy.random.SeedSequence()``.
+
+        ``pred`` / ``pred_err`` are ``predict_arrays``' values at the same sites under the same caps.  The mean of the ensemble
+        equals ``pred`` only in the full-conditioning limit (every datum and every earlier site in every set): a site's set
+        also holds earlier sites, which take places under the cap that data would have had.
+
+        Returns (draws (n_draws, m), pred, pred_err, pinned (bool, m), seed); ``sim_info`` holds seed, ordering, n_levels,
+        n_empty, n_pinned, k_max and n_capped, ``timings`` the native call's.  Raises ValueError on bad arguments before any
+        device work and numpy.linalg.LinAlgError when a site's local system is not positive definite."""
+        from numpy.linalg import LinAlgError
+
+        from .vecchia import check_ordering, ordering_ranks
+        if self.devices is not None and len(self.devices) > 1:
+            raise NotImplementedError(f"conditional simulation runs on one device; this predictor has devices={self.devices}")
+        if self.trend is not None:
+            raise NotImplementedError("conditional simulation in the moving neighbourhood is simple cokriging only (trend=None)")
+        if isinstance(i, bool) or not (isinstance(i, (int, np.integer)) and 0 <= int(i) < self.n_procs):
+            raise ValueError(f"process index {i!r} out of range for {self.n_procs} processes")
+        pc = np.atleast_2d(np.asarray(pcoords.values if isinstance(pcoords, pd.DataFrame) else pcoords, dtype=np.float64))
+        if pc.ndim != 2 or pc.shape[1] < 2 or len(pc) < 1:
+            raise ValueError("pcoords must be [[lat, lon], ...] with at least one site")
+        pc = np.ascontiguousarray(pc[:, :2])
+        m = len(pc)
+        if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or n_draws < 1:
+            raise ValueError(f"n_draws must be an integer >= 1, not {n_draws!r}")
+        n_draws = int(n_draws)
+        if isinstance(max_dist, bool) or not np.isfinite(max_dist) or max_dist < 0:
+            raise ValueError(f"max_dist must be finite and >= 0, got {max_dist!r}")
+        if noise is not None:
+            noise = np.asarray(noise, dtype=np.float64)
+            if noise.shape != (n_draws, m):
+                raise ValueError(f"noise has shape {noise.shape}, expected (n_draws, m) = {(n_draws, m)}")
+        ordering = check_ordering(ordering)
+        if isinstance(ordering, np.ndarray) and ordering.size != m:
+            raise ValueError(f"the ordering has {ordering.size} ranks, pcoords {m} sites")
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+        if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must be an integer in [0, 2^64)")
+        seed = int(seed)
+        # sites that repeat an earlier row: the draws of the first occurrence
+        pair = [("a", np.float64), ("b", np.float64)]
+        rows = pc.view(pair).ravel()
+        _, first, inv = np.unique(rows, return_index=True, return_inverse=True)
+        source = first[np.asarray(inv).ravel()]                 # caller's site -> the first row with its coordinates
+        # sites on a datum of process i that carries no measurement-error variance: the datum's value
+        f = self.mf.fields[i]
+        dc = np.ascontiguousarray(np.asarray(f.coords_main, dtype=np.float64)[:, :2])
+        dv = np.asarray(f.values_main, dtype=np.float64).ravel()
+        var, scales = resolve_measurement_error(self.measurement_error, self.noise_scale, self.mf.fields, self.devices)
+        exact = np.ones(len(dc), dtype=bool) if var is None or var[i] is None else ~(scales[i] * var[i] > 0.0)
+        drows = dc[exact].view(pair).ravel()
+        du, dfirst = np.unique(drows, return_index=True)
+        at = np.searchsorted(du, rows)
+        on_datum = (at < len(du)) & (du[np.minimum(at, max(len(du) - 1, 0))] == rows) if len(du) else np.zeros(m, dtype=bool)
+        datum_value = np.where(on_datum, dv[exact][dfirst[np.minimum(at, max(len(du) - 1, 0))]] if len(du) else 0.0, np.nan)
+        free = np.flatnonzero((source == np.arange(m)) & ~on_datum)   # what the native call simulates, the caller's order
+        pinned = np.ones(m, dtype=bool)
+        pinned[free] = False
+        was_cv, self.cv = self.cv, False   # the sites' ordinary prediction, whatever cross_validation left behind
+        try:
+            pred, err = self.predict_arrays(i, pc, max_dist=max_dist)
+        finally:
+            self.cv = was_cv
+        draws = np.empty((n_draws, m))
+        stats = dict(n_levels=0, n_empty=0, k_max=0, n_capped=0)
+        if len(free):
+            if isinstance(ordering, np.ndarray):
+                ranks = ordering[free]
+            else:
+                ranks = ordering_ranks([pc[free]], ordering, seed % (2 ** 63))
+            h = self._capped_handle()
+            e = None if noise is None else np.ascontiguousarray(noise[:, free])
+            sub, info, stats = h.simulate_local(int(i), pc[free], ranks, float(max_dist), n_draws, seed=seed, noise=e, terms=False)
+            self.timings = h.simulate_local_timings()
+            if info != 0:
+                site = int(free[info - 1])
+                raise LinAlgError(f"the local system of site {site} {tuple(pc[site])} is not positive definite or leaves no "
+                                  "variance: nearly coincident sites, or a site nearly on a noise-free datum")
+            draws[:, free] = sub
+        on = np.flatnonzero(on_datum)
+        draws[:, on] = datum_value[on]
+        rest = np.flatnonzero(pinned & ~on_datum)
+        draws[:, rest] = draws[:, source[rest]]
+        self.sim_info = dict(seed=seed, ordering=ordering if isinstance(ordering, str) else "ranks", n_levels=stats["n_levels"],
+                             n_empty=stats["n_empty"], n_pinned=int(pinned.sum()), k_max=stats["k_max"], n_capped=stats["n_capped"])
+        return draws, pred, err, pinned, seed
+
+    def conditional_simulation(self, i: int, pcoords, max_dist: float = 1e3, n_draws: int = 100, seed=None, ordering="random",
+                               postprocess: bool = True, noise=None):
+        """Ensembles of maps of process ``i`` at ``pcoords`` drawn in the moving neighbourhood: the draws that the joint
+        predictor's ``conditional_simulation`` gives from the dense factor, for data and grids beyond its size -- exceedance
+        probabilities, areas above a threshold, ensembles for downstream models.  Returns what the joint method returns: an
+        xarray Dataset with ``pred``, ``pred_err`` and ``draws`` (a leading ``draw`` dimension), ``attrs`` holding ``seed``,
+        ``ordering``, ``n_levels``, ``n_empty`` and ``n_pinned``; ``postprocess=True`` applies ``_postprocess_predictions``'
+        transform to every draw.  Without xarray: ``(DataFrame, draws)``.  See ``conditional_draws_arrays`` for the arguments
+        and for how the ensemble mean relates to ``pred``."""
+        if not isinstance(pcoords, pd.DataFrame):
+            a = np.atleast_2d(np.asarray(pcoords, dtype=np.float64))
+            if a.ndim != 2 or a.shape[1] < 2:
+                raise ValueError("pcoords must be [[lat, lon], ...]")
+            pcoords = pd.DataFrame({"d1": a[:, 0], "d2": a[:, 1]})
+        draws, pred, err, _, seed = self.conditional_draws_arrays(i, pcoords.values[:, :2], max_dist, n_draws, seed=seed,
+                                                                  ordering=ordering, noise=noise)
+        return _JointPredictor._draws_output(self, i, pcoords, draws, pred, err,
+                                             {k: self.sim_info[k] for k in ("seed", "ordering", "n_levels", "n_empty", "n_pinned")},
+                                             postprocess)
+
     def cross_validation(self, i: int, max_dist: float = 1e3, partitions: int = None,
                          postprocess: bool = True) -> pd.DataFrame:
         """Leave-one-out at every data location of process ``i`` (src/point_prediction.py:303-346):
