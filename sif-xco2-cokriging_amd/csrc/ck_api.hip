@@ -327,6 +327,8 @@ struct CallGuard {
         h->aux_state = exit_state;
     }
 };
+// an admitted call starts its ck_timings slots, and those behind them, from zero
+static void timings_from(ck_handle* h, int first) { std::fill(h->t_ms + first, h->t_ms + CK_N_TIMINGS, 0.0); }
 static int64_t aux_cap(const ck_handle* h) { return (int64_t)h->aux_own.cap(); }               // doubles
 static long long local_slab_doubles(const ck_handle* h) { return (long long)h->local_slab.cap(); }
 
@@ -343,6 +345,8 @@ static int64_t align256(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
 // What the handle allocates in the caller's arena if there is one (ck_estimate_bytes is the sum of exactly these sizes):
 // a panel's rows with the diagonal blocks' inverses behind them (ck_panel_buffer) ...
 static_assert(CK_HOST_NB == CK_NB && CK_HOST_PANEL_TAIL == CK_PANEL_TAIL, "ck_host.h and ck_internal.h disagree about a panel");
+static_assert(CK_HOST_AUX_ALIGN == CK_AUX_ALIGN && CK_HOST_PRIOR_PIECE == CK_PRIOR_PIECE && CK_HOST_TREND_QMAX == CK_UNIV_QMAX,
+              "ck_host.h and ck_internal.h disagree about the dense predictors' constants");
 static int64_t panel_payload(int64_t Np, int K) { return ck_host_panel_payload(Np, K); }
 static int64_t panel_bytes(int64_t Np, int K) { return align256(panel_payload(Np, K) + CK_PANEL_SLACK_BYTES); }   // in the slab
 static int64_t recv_bytes(int64_t Np) { return panel_payload(Np, 0) + CK_PANEL_SLACK_BYTES; }   // a receive slot: any panel
@@ -1781,7 +1785,6 @@ extern "C" int ck_factor(ck_handle* h, int64_t* info) {
     return 0;
 }
 
-// pcoords == nullptr: storage only (ck_loocv fills the right-hand-side rows itself)
 // ---------------------------------------------------------------------------------------
 // universal cokriging: the regressors in the internal order (ck_set_trend)
 // ---------------------------------------------------------------------------------------
@@ -1858,7 +1861,12 @@ static int trend_gls(const ck_handle* h, const char* name, const std::vector<dou
     return trend_gls_solve(h, name, p, A, b.data(), R, beta, Ainv, logdet, bAb);
 }
 
-static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m, bool may_sort) {
+// ---------------------------------------------------------------------------------------
+// the dense predictors' stages: each written once, each hands what it found to its caller -- only the entry points write ck_timings
+// ---------------------------------------------------------------------------------------
+// Storage of m + 1 + aux_trend right-hand-side rows and of the site arrays that go with them; no device work.  The rows are the
+// caller's to fill: aux_begin_impl's prediction sites, or unit_rows' unit vectors.
+static int aux_storage(ck_handle* h, int i, int64_t m) {
     if (ensure_layout(h)) return -1;
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
     if (m < 0) return fail("bad pcoords");
@@ -1883,15 +1891,21 @@ static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m,
     h->i_pred = i;
     h->m = m;
     h->mpad = mpad;
-    h->aux_state = pcoords ? AUX_ASSEMBLED : AUX_NONE;
+    h->aux_state = AUX_NONE;
+    h->p_sorted = false;
+    return 0;
+}
+
+// The assembly stage (K2): the right-hand sides [c0^T; z^T] of m prediction sites of process i, the trend rows X^T behind them
+// where aux_trend says so.  *k2_ms: the device milliseconds of the site transform, the table kernel and the exact pass.
+static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m, double* k2_ms) {
+    if (aux_storage(h, i, m)) return -1;
+    h->aux_state = AUX_ASSEMBLED;
+    const int64_t mpad = h->mpad;
     // large sets of prediction points are laid out along the Hilbert curve like the data sites
     // (site_order above); ck_aux_finish hands the results back in the caller's order
     std::vector<double> sorted;
-    if (!pcoords) {
-        h->p_sorted = false;
-        return 0;
-    }
-    h->p_sorted = may_sort && h->site_order && m >= 256;
+    h->p_sorted = h->site_order && m >= 256;
     if (h->p_sorted) {
         double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
         ck_host_bounding_box(pcoords, m, lo, hi);
@@ -1926,15 +1940,25 @@ static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m,
     if (fast_done < 0) return -1;
     if (!fast_done) HIPCHK(hipEventRecord(h->ev1, h->stream));
     HIPCHK(hipEventSynchronize(h->ev1));   // pcoords is caller memory: do not return before the copy is done
-    HIPCHK(elapsed_ms(h->ev0, h->ev1, &h->t_ms[2]));
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, k2_ms));
     if (h->aux_trend > 0 && put_trend_rows(h, m + 1)) return -1;   // universal cokriging: X^T behind the data row
+    return 0;
+}
+
+// The timed sweep stage: the forward sweep over the right-hand sides between ev2 and ev3, the handle's second event pair (ev0 /
+// ev1 belong to the stages around it).  The caller reads the window behind its next synchronisation.
+static int timed_solve_sweep(ck_handle* h) {
+    h->gemm_ev_used = 0;
+    HIPCHK(hipEventRecord(h->ev2, h->stream));
+    if (solve_sweep(h)) return -1;
+    HIPCHK(hipEventRecord(h->ev3, h->stream));
     return 0;
 }
 
 extern "C" int ck_aux_begin(ck_handle* h, int i, const double* pcoords, int64_t m) {
     CHKH(h);
     if (m > 0 && !pcoords) return fail("bad pcoords");
-    return aux_begin_impl(h, i, pcoords, m, true);
+    return aux_begin_impl(h, i, pcoords, m, &h->t_ms[2]);
 }
 
 extern "C" int ck_aux_finish(ck_handle* h, double* pred, double* pred_err) {
@@ -1972,10 +1996,7 @@ extern "C" int ck_predict(ck_handle* h, int i, const double* pcoords, int64_t m,
     if (h->world != 1) return fail("ck_predict is the single-process form");
     if (!h->factored) return fail("ck_factor has not been called");
     if (ck_aux_begin(h, i, pcoords, m)) return -1;
-    h->gemm_ev_used = 0;
-    HIPCHK(hipEventRecord(h->ev2, h->stream));   // the handle's second event pair: ev0 / ev1 are used inside
-    if (solve_sweep(h)) return -1;
-    HIPCHK(hipEventRecord(h->ev3, h->stream));
+    if (timed_solve_sweep(h)) return -1;
     if (ck_aux_finish(h, pred, pred_err)) return -1;
     HIPCHK(elapsed_ms(h->ev2, h->ev3, &h->t_ms[3]));
     gemm_timed_collect(h, 7);
@@ -2009,17 +2030,13 @@ extern "C" int ck_predict_universal(ck_handle* h, int i, const double* pcoords, 
             return fail("ck_predict_universal: regressor " + std::to_string(e % pi) + " is not finite at prediction site " +
                         std::to_string(e / pi));
     const auto t_begin = std::chrono::steady_clock::now();
-    for (int k = 40; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    timings_from(h, 40);
     if (ensure_trend(h)) return -1;
     CallGuard guard(h, AUX_UNIVERSAL, false);
     h->aux_trend = p;
     static const double no_site[2] = {0.0, 0.0};
-    if (aux_begin_impl(h, i, m > 0 ? pcoords : no_site, m, true)) return -1;
-    h->t_ms[40] = h->t_ms[2];
-    h->gemm_ev_used = 0;
-    HIPCHK(hipEventRecord(h->ev2, h->stream));
-    if (solve_sweep(h)) return -1;
-    HIPCHK(hipEventRecord(h->ev3, h->stream));
+    if (aux_begin_impl(h, i, m > 0 ? pcoords : no_site, m, &h->t_ms[40])) return -1;
+    if (timed_solve_sweep(h)) return -1;
     const int q = 1 + p;
     const int64_t nrows = m + 1 + p;
     if (ensure_univ(h, nrows * (q + 1))) return -1;
@@ -2040,25 +2057,8 @@ extern "C" int ck_predict_universal(ck_handle* h, int i, const double* pcoords, 
     const auto t1 = std::chrono::steady_clock::now();
     // ---- the epilogue, in the caller's order
     const double c0 = h->blk[2 * i].amp + h->blk[2 * i].nugget;   // sigma_i^2 + nugget_i, as ck_aux_finish
-    ck_host_parallel(m, [&](int, int64_t a, int64_t e) {
-        double r[CK_UNIV_QMAX];
-        for (int64_t s = a; s < e; ++s) {
-            const int64_t c = h->p_sorted ? h->pperm[(size_t)s] : s;
-            const double* wr = &W[(size_t)(s * (q + 1))];
-            for (int j = 0; j < p; ++j) r[j] = -wr[2 + j];
-            for (int j = 0; j < pi; ++j) r[offi + j] += f0[c * pi + j];
-            double pr = wr[1], var = c0 - wr[0];
-            for (int j = 0; j < p; ++j) {
-                pr += r[j] * bh[(size_t)j];
-                double t = 0.0;
-                for (int l = 0; l < p; ++l) t += Ai[(size_t)(j * p + l)] * r[l];
-                var += r[j] * t;
-            }
-            const double er = sqrt(var);   // negative variance -> NaN -> 0.0 (np.nan_to_num, as ck_aux_finish)
-            pred[c] = pr;
-            pred_err[c] = (er == er) ? er : 0.0;
-        }
-    });
+    ck_host_universal_finish(W.data(), bh.data(), Ai.data(), f0, h->p_sorted ? h->pperm.data() : nullptr, c0, m, p, pi, offi, pred,
+                             pred_err);
     if (beta) memcpy(beta, bh.data(), (size_t)p * 8);
     if (beta_cov) memcpy(beta_cov, Ai.data(), (size_t)p * p * 8);
     h->t_ms[44] = ms_since(t1);
@@ -2126,6 +2126,24 @@ struct SchurSwap {
         h->rank = rank;
     }
 };
+
+// The entries (R, C), C <= R < n, of a packed lower triangle panel by panel: one download and one synchronisation per panel
+// this process holds, visit(R, C, value) on the host
+template <class Visit>
+static int read_lower(ck_handle* h, const std::vector<double*>& sig, int nJ, int64_t n, Visit visit) {
+    std::vector<double> panel;
+    for (int J = 0; J < nJ; ++J) {
+        const int64_t R0 = (int64_t)J * CK_NB, rows = n - R0;
+        if (!sig[(size_t)J] || rows <= 0) continue;
+        panel.resize((size_t)(rows * CK_NB));
+        HIPCHK(hipMemcpyAsync(panel.data(), sig[(size_t)J], (size_t)(rows * CK_NB) * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (int64_t R = R0; R < n; ++R)
+            for (int64_t C = R0; C < std::min<int64_t>(R0 + CK_NB, R + 1); ++C)
+                visit(R, C, panel[(size_t)((R - R0) * CK_NB + (C - R0))]);
+    }
+    return 0;
+}
 
 // the Schur complement's packed panels (Mp = roundup(sites, CK_NB) rows, a Sigma-like block-column layout) and the
 // assembly state that goes with them; kept between calls with the same padded order
@@ -2287,25 +2305,11 @@ struct AuxSwap {
     }
 };
 
-// piece offsets of the prior's elements (ck_blocks.hip): poff[e] .. poff[e + 1] = the pieces of CK_PRIOR_PIECE pairs of
-// element e (full == 0: e = b, n_b^2 pairs; full != 0: e = R (R + 1) / 2 + C, n_R n_C pairs); returns the number of pieces
-static int64_t prior_pieces(const std::vector<int>& off, int32_t r, int full, std::vector<long long>& poff) {
-    auto n = [&](int64_t b) { return (int64_t)(off[(size_t)b + 1] - off[(size_t)b]); };
-    auto pieces = [](int64_t pairs) { return (pairs + CK_PRIOR_PIECE - 1) / CK_PRIOR_PIECE; };
-    poff.assign(1, 0);
-    poff.reserve((size_t)(full ? (int64_t)r * (r + 1) / 2 : r) + 1);
-    for (int64_t R = 0; R < r; ++R) {
-        if (!full) {
-            poff.push_back(poff.back() + pieces(n(R) * n(R)));
-            continue;
-        }
-        for (int64_t C = 0; C <= R; ++C) poff.push_back(poff.back() + pieces(n(R) * n(C)));
-    }
-    return poff.back();
-}
-
-static int predict_blocks_impl(ck_handle* h, int i, const double* pcoords, int64_t m, const int32_t* block, const double* weight,
-                               int32_t r, double* pred, double* pred_err, double* cov) {
+// Slots 0 .. 15 of ck_timings describe the last point-path calls: no stage below writes one, so every return leaves them as they
+// were (tests/test_gpu_call_states.py).
+extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int64_t m, const int32_t* block,
+                                 const double* weight, int32_t r, double* pred, double* pred_err, double* cov) {
+    CHKH(h);
     if (h->world != 1) return fail("ck_predict_blocks is the single-process form");
     if (!h->factored) return fail("ck_factor has not been called");
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
@@ -2313,34 +2317,30 @@ static int predict_blocks_impl(ck_handle* h, int i, const double* pcoords, int64
     if (m < 1 || m > INT32_MAX) return fail("ck_predict_blocks: m must be in [1, 2^31)");
     if (!pcoords || !block || !weight || !pred || !pred_err) return fail("ck_predict_blocks: null argument");
     if (cov && r > 65536) return fail("ck_predict_blocks: the covariance is limited to 65 536 blocks");
-    // member lists: off[b] .. off[b + 1], the caller's order inside each block
-    std::vector<int> off((size_t)r + 1, 0);
-    for (int64_t a = 0; a < m; ++a) {
-        if (block[a] < 0 || block[a] >= r)
-            return fail("ck_predict_blocks: block label " + std::to_string(block[a]) + " of site " + std::to_string(a) +
-                        " is outside [0, r)");
+    // member lists: off[b] .. off[b + 1], the caller's order inside each block.  The first site at fault is reported, its label
+    // before its weight.
+    std::vector<int> off;
+    std::vector<int64_t> member;
+    int64_t q_max = 0, at = 0;
+    const int fault = ck_host_block_members(block, m, r, off, member, &q_max, &at);
+    for (int64_t a = 0; a < (fault == CK_HOST_BLOCKS_LABEL ? at : m); ++a)
         if (!std::isfinite(weight[a])) return fail("ck_predict_blocks: weight of site " + std::to_string(a) + " is not finite");
-        ++off[(size_t)block[a] + 1];
-    }
-    for (int32_t b = 0; b < r; ++b) {
-        if (off[(size_t)b + 1] == 0) return fail("ck_predict_blocks: block " + std::to_string(b) + " has no site");
-        off[(size_t)b + 1] += off[(size_t)b];
-    }
+    if (fault == CK_HOST_BLOCKS_LABEL)
+        return fail("ck_predict_blocks: block label " + std::to_string(block[at]) + " of site " + std::to_string(at) +
+                    " is outside [0, r)");
+    if (fault == CK_HOST_BLOCKS_EMPTY) return fail("ck_predict_blocks: block " + std::to_string(at) + " has no site");
     const auto t_begin = std::chrono::steady_clock::now();
     // from here on the right-hand sides are block rows (or a chunk's unsolved point rows after a failure)
     CallGuard guard(h, AUX_BLOCKS, true);
-    for (int k = 16; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    timings_from(h, 16);
     DevTemps tmp;
     // ---- prior of the blocks (diagonal): members in block order, exact-formula coordinates
     std::vector<double> mc((size_t)(2 * m)), mw((size_t)m);
-    {
-        std::vector<int> pos(off.begin(), off.end() - 1);
-        for (int64_t a = 0; a < m; ++a) {
-            const int k = pos[(size_t)block[a]]++;
-            mc[2 * (size_t)k] = pcoords[2 * a];
-            mc[2 * (size_t)k + 1] = pcoords[2 * a + 1];
-            mw[(size_t)k] = weight[a];
-        }
+    for (int64_t k = 0; k < m; ++k) {
+        const int64_t a = member[(size_t)k];
+        mc[2 * (size_t)k] = pcoords[2 * a];
+        mc[2 * (size_t)k + 1] = pcoords[2 * a + 1];
+        mw[(size_t)k] = weight[a];
     }
     double *d_mc = nullptr, *d_mx = nullptr, *d_mw = nullptr, *d_diag = nullptr, *d_red = nullptr;
     int* d_off = nullptr;
@@ -2354,7 +2354,7 @@ static int predict_blocks_impl(ck_handle* h, int i, const double* pcoords, int64
     HIPCHK(hipMemcpyAsync(d_mw, mw.data(), (size_t)m * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(d_off, off.data(), ((size_t)r + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
     std::vector<long long> poff;
-    const int64_t n_pieces = prior_pieces(off, r, 0, poff);
+    const int64_t n_pieces = ck_host_prior_pieces(off.data(), r, 0, poff);
     long long* d_poff = nullptr;
     double* d_part = nullptr;
     HIPCHK(tmp.get(&d_poff, poff.size() * sizeof(long long)));
@@ -2371,47 +2371,30 @@ static int predict_blocks_impl(ck_handle* h, int i, const double* pcoords, int64
     // ---- block rows
     const int64_t bmpad = roundup((int64_t)r + 1, CK_AUX_ALIGN);
     if (bmpad * h->Npad > (int64_t)h->baux.cap() && dev_alloc(h, h->baux, rhs_bytes(bmpad, h->Npad))) return -1;
-    int64_t chunk = h->block_chunk;
-    if (chunk <= 0) {   // what the handle may still take (the arena's rest or half of the free memory) beside the point rows it holds
-        int64_t avail = 0;
-        if (h->arena) {
-            avail = h->arena_size - h->arena_used;
-        } else {
-            size_t fr = 0, tot = 0;
-            HIPCHK(hipMemGetInfo(&fr, &tot));
-            avail = (int64_t)(fr / 2);
-        }
-        // hipMalloc: aux_begin_impl frees the point rows' buffer before it allocates a larger one; an arena never takes
-        // memory back, so there the chunk fits either the buffer the handle holds or the arena's rest
-        avail = h->arena ? std::max<int64_t>(avail, aux_cap(h) * 8) : avail + aux_cap(h) * 8;
-        chunk = std::max<int64_t>(avail / (8 * h->Npad) - CK_AUX_ALIGN, CK_AUX_ALIGN);
-    }
-    chunk = std::min<int64_t>(chunk, m);
+    size_t fr = 0, tot = 0;
+    if (h->block_chunk <= 0 && !h->arena) HIPCHK(hipMemGetInfo(&fr, &tot));
+    const int64_t chunk = ck_host_block_chunk(h->block_chunk, (int64_t)fr, h->arena ? h->arena_size - h->arena_used : -1,
+                                              aux_cap(h) * 8, h->Npad, m);
     int *d_coff = nullptr, *d_crows = nullptr;
     double* d_cw = nullptr;
     HIPCHK(tmp.get(&d_coff, ((size_t)r + 1) * sizeof(int)));
     HIPCHK(tmp.get(&d_crows, (size_t)chunk * sizeof(int)));
     HIPCHK(tmp.get(&d_cw, (size_t)chunk * 8));
-    std::vector<int> coff((size_t)r + 1), crows((size_t)chunk), inv((size_t)chunk);
+    std::vector<int> coff, crows((size_t)chunk), inv((size_t)chunk);
     std::vector<double> cw((size_t)chunk);
     int n_chunks = 0;
     for (int64_t a0 = 0; a0 < m; a0 += chunk, ++n_chunks) {
         const int64_t mc_ = std::min<int64_t>(chunk, m - a0);
-        if (aux_begin_impl(h, i, pcoords + 2 * a0, mc_, true)) return -1;   // K2 on this chunk's sites (synchronised)
+        double k2_ms = 0.0;
+        if (aux_begin_impl(h, i, pcoords + 2 * a0, mc_, &k2_ms)) return -1;   // K2 on this chunk's sites (synchronised)
         h->aux_state = AUX_BLOCKS;
-        h->t_ms[16] += h->t_ms[2];
-        // this chunk's member lists, rows in the library's internal order (Hilbert order when p_sorted)
+        h->t_ms[16] += k2_ms;
+        // this chunk's member lists (a block may have none here), rows in the library's internal order (Hilbert order when p_sorted)
         for (int64_t j = 0; j < mc_; ++j) inv[(size_t)(h->p_sorted ? h->pperm[(size_t)j] : j)] = (int)j;
-        std::fill(coff.begin(), coff.end(), 0);
-        for (int64_t q = 0; q < mc_; ++q) ++coff[(size_t)block[a0 + q] + 1];
-        for (int32_t b = 0; b < r; ++b) coff[(size_t)b + 1] += coff[(size_t)b];
-        {
-            std::vector<int> pos(coff.begin(), coff.end() - 1);
-            for (int64_t q = 0; q < mc_; ++q) {
-                const int k = pos[(size_t)block[a0 + q]]++;
-                crows[(size_t)k] = inv[(size_t)q];
-                cw[(size_t)k] = weight[a0 + q];
-            }
+        (void)ck_host_block_members(block + a0, mc_, r, coff, member, &q_max, &at);
+        for (int64_t k = 0; k < mc_; ++k) {
+            crows[(size_t)k] = inv[(size_t)member[(size_t)k]];
+            cw[(size_t)k] = weight[a0 + member[(size_t)k]];
         }
         HIPCHK(hipMemcpyAsync(d_coff, coff.data(), ((size_t)r + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(d_crows, crows.data(), (size_t)mc_ * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -2427,10 +2410,7 @@ static int predict_blocks_impl(ck_handle* h, int i, const double* pcoords, int64
     // ---- the forward sweep over the r + 1 block rows on the resident factor, raw reductions V_b . y and |V_b|^2
     {
         AuxSwap swap(h, h->baux, r, bmpad);
-        h->gemm_ev_used = 0;
-        HIPCHK(hipEventRecord(h->ev2, h->stream));
-        if (solve_sweep(h)) return -1;
-        HIPCHK(hipEventRecord(h->ev3, h->stream));
+        if (timed_solve_sweep(h)) return -1;
         h->gemm_ev_used = 0;
     }
     HIPCHK(hipEventRecord(h->ev0, h->stream));
@@ -2446,15 +2426,14 @@ static int predict_blocks_impl(ck_handle* h, int i, const double* pcoords, int64
     h->t_ms[20] = elapsed_ms(h->ev0, h->ev1);
     for (int32_t b = 0; b < r; ++b) {
         pred[b] = s1[(size_t)b];
-        const double e = sqrt(cbar[(size_t)b] - s2[(size_t)b]);   // negative variance -> NaN -> 0.0 (np.nan_to_num)
-        pred_err[b] = (e == e) ? e : 0.0;
+        pred_err[b] = ck_host_err_of(cbar[(size_t)b] - s2[(size_t)b]);
     }
     // ---- the full A S A^T: Cbar's lower triangle in the Schur buffers' packed panels, minus V^T V (k_schur_syrk_d)
     if (cov) {
         const int64_t Mp = roundup(r, CK_NB);
         const int nJ = (int)(Mp / CK_NB);
         if (schur_ensure(h, Mp)) return -1;
-        const int64_t n_pieces_full = prior_pieces(off, r, 1, poff);
+        const int64_t n_pieces_full = ck_host_prior_pieces(off.data(), r, 1, poff);
         long long* d_poff_full = nullptr;
         double* d_part_full = nullptr;
         HIPCHK(tmp.get(&d_poff_full, poff.size() * sizeof(long long)));
@@ -2469,20 +2448,8 @@ static int predict_blocks_impl(ck_handle* h, int i, const double* pcoords, int64
         HIPCHK(hipEventRecord(h->ev1, h->stream));
         ck_launch_schur_syrk(h->stream, h->sch.d_ptr, h->baux, bmpad, h->nK, nJ, Mp);
         HIPCHK(hipGetLastError());
-        std::vector<double> panel;
-        for (int J = 0; J < nJ; ++J) {   // rows J NB .. r - 1 of block column J; only R >= C is meaningful
-            const int64_t R0 = (int64_t)J * CK_NB, rows = r - R0;
-            panel.resize((size_t)(rows * CK_NB));
-            HIPCHK(hipMemcpyAsync(panel.data(), h->sch.sig[(size_t)J], (size_t)(rows * CK_NB) * 8, hipMemcpyDeviceToHost,
-                                  h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            for (int64_t R = R0; R < r; ++R)
-                for (int64_t C = R0; C < std::min<int64_t>(R0 + CK_NB, R + 1); ++C) {
-                    const double v = panel[(size_t)((R - R0) * CK_NB + (C - R0))];
-                    cov[R * r + C] = v;
-                    cov[C * r + R] = v;
-                }
-        }
+        // rows J NB .. r - 1 of block column J; only R >= C is meaningful
+        if (read_lower(h, h->sch.sig, nJ, r, [&](int64_t R, int64_t C, double v) { cov[R * r + C] = cov[C * r + R] = v; })) return -1;
         HIPCHK(hipEventRecord(h->ev2, h->stream));
         HIPCHK(hipEventSynchronize(h->ev2));
         h->t_ms[18] += elapsed_ms(h->ev0, h->ev1);
@@ -2490,17 +2457,6 @@ static int predict_blocks_impl(ck_handle* h, int i, const double* pcoords, int64
     }
     h->t_ms[21] = ms_since(t_begin);
     return 0;
-}
-
-// slots 0 .. 15 of ck_timings describe the last point-path calls: every return leaves them as they were
-extern "C" int ck_predict_blocks(ck_handle* h, int i, const double* pcoords, int64_t m, const int32_t* block,
-                                 const double* weight, int32_t r, double* pred, double* pred_err, double* cov) {
-    CHKH(h);
-    double kept[16];
-    memcpy(kept, h->t_ms, sizeof(kept));
-    const int rc = predict_blocks_impl(h, i, pcoords, m, block, weight, r, pred, pred_err, cov);
-    memcpy(h->t_ms, kept, sizeof(kept));
-    return rc;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2569,7 +2525,7 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
                         std::to_string(s_bytes) + " for the posterior covariance of " + std::to_string(m) + " sites, " +
                         std::to_string(c_bytes) + " for a chunk of 128 draws); " + std::to_string(a.avail) + " bytes are available");
     }
-    for (int k = 30; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    timings_from(h, 30);
     *info = 0;
     // ---- 1. the point prediction (the same call, the same bits)
     {
@@ -2616,22 +2572,10 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
     h->t_ms[38] = (double)n_defl;
     // ---- 4. the factor of S.  Two sites at the same coordinates have identical rows of S: singular unless deflated.  The
     // exact factorisation stops at the later of them (internal order); report that without leaving it to rounding.
-    {
-        std::vector<std::pair<std::pair<double, double>, int64_t>> key;
-        key.reserve((size_t)m);
-        for (int64_t j = 0; j < m; ++j)
-            if (!mask[(size_t)j]) key.push_back({{pcoords[2 * cmap[(size_t)j]], pcoords[2 * cmap[(size_t)j] + 1]}, j});
-        std::sort(key.begin(), key.end());
-        int64_t stop = -1;
-        for (size_t q = 1; q < key.size(); ++q)
-            if (key[q].first.first == key[q - 1].first.first && key[q].first.second == key[q - 1].first.second &&
-                (stop < 0 || key[q].second < stop))
-                stop = key[q].second;   // the larger internal index of the pair (equal keys are sorted by index)
-        if (stop >= 0) {
-            *info = 1 + cmap[(size_t)stop];
-            h->t_ms[37] = ms_since(t_begin);
-            return 0;
-        }
+    if (const int64_t stop = ck_host_coincident_site(pcoords, cmap.data(), mask.data(), m); stop >= 0) {
+        *info = 1 + cmap[(size_t)stop];
+        h->t_ms[37] = ms_since(t_begin);
+        return 0;
     }
     {
         long long v = 0;
@@ -2649,14 +2593,9 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
     ck_launch_draw_upper(h->stream, h->sch.d_ptr, nJ);
     HIPCHK(hipGetLastError());
     // ---- 5 / 6. noise and the draw product, chunk by chunk
-    int64_t chunk = h->draw_chunk;
-    if (chunk <= 0) {
-        size_t fr = 0, tot = 0;
-        HIPCHK(hipMemGetInfo(&fr, &tot));
-        chunk = (int64_t)(fr / 2) / (8 * (Mp + (noise ? 2 : 1) * m)) / 128 * 128;
-        chunk = std::max<int64_t>(128, std::min<int64_t>(chunk, 8192));
-    }
-    chunk = std::min<int64_t>(chunk, n_draws);
+    size_t fr = 0, tot = 0;
+    if (h->draw_chunk <= 0) HIPCHK(hipMemGetInfo(&fr, &tot));
+    const int64_t chunk = ck_host_draw_chunk(h->draw_chunk, (int64_t)fr, Mp, m, noise != nullptr, n_draws);
     const int64_t ldp = roundup(chunk, 128);
     double *d_E = nullptr, *d_X = nullptr, *d_noise = nullptr;
     HIPCHK(tmp.get(&d_E, (size_t)(ldp * Mp) * 8));
@@ -2710,11 +2649,10 @@ static void factor_tiled_batch(hipStream_t st, const CkLocalSys* sys, double* sl
 // ---------------------------------------------------------------------------------------
 // unit rows as right-hand sides (ck_loocv, ck_cv_folds, ck_loglik / ck_loglik_reml)
 // ---------------------------------------------------------------------------------------
-// Behind aux_begin_impl(.., nullptr, ..): the right-hand sides become row 0 = z, rows 1 .. dense - 1 = the trend rows X^T (REML),
-// row dense + p = the unit vector of internal position g0 + p (p < m), and are swept through the factor on the growing prefix
-// of live rows (aux_rows: loo_g0 / loo_dense, idle again on every return).  before_sweep (may be null) is recorded between the
-// row fill and the sweep.
-static int unit_row_sweep(ck_handle* h, int64_t m, int64_t g0, int dense, hipEvent_t before_sweep = nullptr) {
+// The right-hand sides become row 0 = z, rows 1 .. dense - 1 = the trend rows X^T (REML), row dense + p = the unit vector of
+// internal position g0 + p (p < m), and are swept through the factor on the growing prefix of live rows (aux_rows: loo_g0 /
+// loo_dense, idle again on every return).  before_sweep (may be null) is recorded between the row fill and the sweep.
+static int unit_row_sweep(ck_handle* h, int64_t m, int64_t g0, int dense, hipEvent_t before_sweep) {
     HIPCHK(hipMemsetAsync(h->aux, 0, (size_t)h->mpad * h->Npad * 8, h->stream));
     h->loo_g0 = g0;
     h->loo_dense = dense;
@@ -2727,6 +2665,27 @@ static int unit_row_sweep(ck_handle* h, int64_t m, int64_t g0, int dense, hipEve
     h->loo_g0 = -1;
     h->loo_dense = 1;
     return rc;
+}
+
+// The unit-row stage: storage for the data row, p trend rows and m unit rows from internal position g0 (aux_state <- state),
+// their fill and sweep, and the raw reduction of every row -- against y into d_pred / d_err (k_reduce_pred), with trend rows
+// against [y; U] into d_univ, p + 2 doubles a row (k_reduce_univ).  The caller's window opens at ev0, in front of the fill
+// (from_fill) or between the fill and the sweep; swept (may be null) is recorded between the sweep and the reduction.
+static int unit_rows(ck_handle* h, int i, int64_t m, int64_t g0, int p, AuxState state, bool from_fill, hipEvent_t swept) {
+    if (aux_storage(h, i, m + p)) return -1;
+    h->aux_state = state;
+    if (from_fill) HIPCHK(hipEventRecord(h->ev0, h->stream));
+    if (unit_row_sweep(h, m, g0, 1 + p, from_fill ? nullptr : h->ev0)) return -1;
+    if (swept) HIPCHK(hipEventRecord(swept, h->stream));
+    if (p == 0) {
+        ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, m + 1, 0, -1.0, h->d_pred, h->d_err);
+    } else {
+        const int64_t nrows = m + 1 + p;
+        if (ensure_univ(h, nrows * (p + 2))) return -1;
+        ck_launch_reduce_univ(h->stream, h->aux, h->mpad, h->nK, nrows, 0, 1 + p, h->d_univ);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -2747,13 +2706,8 @@ extern "C" int ck_loocv(ck_handle* h, int i, double* pred, double* pred_err) {
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
     const int64_t m = h->n[i];
     if (m <= 0) return 0;
-    // reuse the aux machinery: storage as for m prediction points; m + 1 rows:
-    // row 0 = z, row 1 + q = unit vector of datum q
-    if (aux_begin_impl(h, i, nullptr, m, false)) return -1;
-    if (unit_row_sweep(h, m, i == 0 ? 0 : h->n0p, 1, h->ev0)) return -1;
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, m + 1, 0, -1.0, h->d_pred, h->d_err);
-    HIPCHK(hipGetLastError());
+    // storage as for m prediction points; m + 1 rows: row 0 = z, row 1 + q = unit vector of datum q; [ev0, ev1]: the sweep
+    if (unit_rows(h, i, m, i == 0 ? 0 : h->n0p, 0, AUX_NONE, false, h->ev1)) return -1;
     std::vector<double> s1(m), s2(m);
     HIPCHK(hipMemcpyAsync(s1.data(), h->d_pred + 1, m * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(s2.data(), h->d_err + 1, m * 8, hipMemcpyDeviceToHost, h->stream));
@@ -2763,8 +2717,7 @@ extern "C" int ck_loocv(ck_handle* h, int i, double* pred, double* pred_err) {
     for (int64_t q = 0; q < m; ++q) {   // q: internal position; results go to the caller's index
         const int64_t x = h->perm[i][(size_t)q];
         pred[x] = zi[x] - s1[q] / s2[q];
-        const double e = sqrt(1.0 / s2[q]);
-        pred_err[x] = (e == e) ? e : 0.0;
+        pred_err[x] = ck_host_err_of(1.0 / s2[q]);
     }
     return 0;
 }
@@ -2838,17 +2791,12 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
     }
     *info = 0;
     for (int64_t a = 0; a < ni; ++a) pred[a] = pred_err[a] = NAN;
-    for (int k = 56; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    timings_from(h, 56);
     CallGuard guard(h, AUX_FOLDS, false);
-    // ---- 1. rows and sweep
-    if (aux_begin_impl(h, i, nullptr, m, false)) return -1;
-    h->aux_state = AUX_FOLDS;
     // outside the timed stages: only the first call of a layout allocates
     if (slab_doubles > local_slab_doubles(h)) HIPCHK(h->local_slab.reserve((size_t)slab_doubles));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    if (unit_row_sweep(h, m, plan.pmin, 1)) return -1;
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    // ---- 2. alpha and the Gram matrices
+    // ---- 1. rows and sweep [ev0, ev1]; 2. alpha (the stage's reduction) and the Gram matrices
+    if (unit_rows(h, i, m, plan.pmin, 0, AUX_FOLDS, true, h->ev1)) return -1;
     std::vector<int> grow((size_t)ng);
     for (int64_t g = 0; g < ng; ++g) grow[(size_t)g] = (int)(1 + plan.gpos[(size_t)g] - plan.pmin);
     std::vector<CkLocalSys> sysv((size_t)nbig);
@@ -2876,7 +2824,6 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
         HIPCHK(hipMemcpyAsync(d_sys, sysv.data(), (size_t)nbig * sizeof(CkLocalSys), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemsetAsync(d_linfo, 0, (size_t)nbig * sizeof(long long), h->stream));
     }
-    ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, m + 1, 0, -1.0, h->d_pred, h->d_err);
     ck_launch_fold_gram(h->stream, h->aux, h->mpad, h->nK, d_tiles, (int64_t)plan.tiles.size(), d_grow, d_buf);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev2, h->stream));
@@ -2917,8 +2864,7 @@ extern "C" int ck_cv_folds(ck_handle* h, int i, const int32_t* fold0, const int3
             if (x < 0) continue;   // a datum of the other process: withheld, not predicted
             const int64_t g = plan.gbase[(size_t)f] + q;
             pred[x] = zi[x] - xs[(size_t)g];
-            const double e = sqrt(ds[(size_t)g]);
-            pred_err[x] = (e == e) ? e : 0.0;
+            pred_err[x] = ck_host_err_of(ds[(size_t)g]);
         }
     }
     h->t_ms[59] = ms_since(t_begin);
@@ -2995,18 +2941,9 @@ static int lik_sweep(ck_handle* h, DevTemps& tmp, const char* name, bool want_ro
     const int q = 1 + p;
     const CkLayout L = layout_of(h);
     if (p > 0 && ensure_trend(h)) return -1;
-    if (aux_begin_impl(h, 0, nullptr, mrows + p, false)) return -1;
-    h->aux_state = AUX_LOGLIK;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    if (unit_row_sweep(h, mrows, 0, q)) return -1;
     // alpha_p = W_p . y (d_pred[1 + p]) and |y|^2 (d_pred[0]); with a trend every row's dots with [y; U]; log L_qq per panel
+    if (unit_rows(h, 0, mrows, 0, p, AUX_LOGLIK, true, nullptr)) return -1;
     const int64_t nrows = mrows + 1 + p;
-    if (p == 0) {
-        ck_launch_reduce_pred(h->stream, h->aux, h->mpad, h->nK, mrows + 1, 0, -1.0, h->d_pred, h->d_err);
-    } else {
-        if (ensure_univ(h, nrows * (q + 1))) return -1;
-        ck_launch_reduce_univ(h->stream, h->aux, h->mpad, h->nK, nrows, 0, q, h->d_univ);
-    }
     double* d_ldp = nullptr;
     HIPCHK(tmp.get(&d_ldp, (size_t)h->nK * 8));
     ck_launch_lik_logdet(h->stream, h->d_sigptr, h->nK, L, d_ldp);
@@ -3153,7 +3090,7 @@ static int loglik_value_grad(ck_handle* h, const char* name, bool reml, int want
     }
     CallGuard guard(h, AUX_LOGLIK, true);
     double* t = h->t_ms;
-    for (int k = 24; k < CK_N_TIMINGS; ++k) t[k] = 0.0;
+    timings_from(h, 24);
     DevTemps tmp;
     LikSweep S;
     const int rc = lik_sweep(h, tmp, name, want_grad != 0, p, false, &S);
@@ -3271,7 +3208,7 @@ extern "C" int ck_loglik_fisher(ck_handle* h, int reml, const int32_t* free13, d
     // ---- the sweep: factor, unit rows, -Sigma^-1 in the Schur buffers (and A, H of REML)
     CallGuard guard(h, AUX_LOGLIK, true);
     double* t = h->t_ms;
-    for (int k = 24; k < CK_N_TIMINGS; ++k) t[k] = 0.0;
+    timings_from(h, 24);
     DevTemps tmp;
     LikSweep S;
     {
@@ -3630,7 +3567,7 @@ extern "C" int ck_debug_local_neighbours(ck_handle* h, int i, const double* pcoo
     if (ensure_layout(h, false)) return -1;
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
     if (m < 0 || (m > 0 && (!pcoords || !count || !rcut))) return fail("ck_debug_local_neighbours: bad arguments");
-    for (int k = 60; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    timings_from(h, 60);
     DevTemps tmp;
     LocalPass S;   // (the select pass reads neither the values nor the noise)
     if (m > 0 && local_pass(h, tmp, i, pcoords, m, max_dist, cv, true, nullptr, nullptr, rcut, &S)) return -1;
@@ -3703,7 +3640,7 @@ static int local_block_members(ck_handle* h, DevTemps& tmp, int i, const CkLocal
     HIPCHK(tmp.get(&d_bo, ((size_t)r + 1) * sizeof(int)));
     HIPCHK(tmp.get(&d_sbb, (size_t)r * 8));
     std::vector<long long> poff;
-    const int64_t n_pieces = prior_pieces(lay.off, (int32_t)r, 0, poff);
+    const int64_t n_pieces = ck_host_prior_pieces(lay.off.data(), (int32_t)r, 0, poff);
     HIPCHK(tmp.get(&d_poff, poff.size() * sizeof(long long)));
     HIPCHK(tmp.get(&d_part, (size_t)n_pieces * 8));
     HIPCHK(hipMemcpyAsync(d_xy, lay.xy.data(), (size_t)(2 * bm * 8), hipMemcpyHostToDevice, h->stream));
@@ -3950,7 +3887,7 @@ extern "C" int ck_predict_local_universal(ck_handle* h, int i, const double* pco
     if (n_rank_def) *n_rank_def = 0;
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
     if (m > 0 && (!pred || !pred_err)) return fail("ck_predict_local_universal: bad prediction arrays");
-    for (int k = 48; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    timings_from(h, 48);
     const bool trend = trend_total(h) > 0;
     if (trend && m > 0 && h->trend_p[i] > 0 && !f0) return fail("ck_predict_local_universal: null regressors of the prediction sites");
     const LocalUniv u{f0, beta, n_rank_def};
@@ -3988,7 +3925,7 @@ extern "C" int ck_predict_local_blocks(ck_handle* h, int i, const double* centre
                     " columns of process " + std::to_string(i));
     CkLocalBlockLayout lay;
     if (ck_host_local_block_layout(centres, r, pcoords, m, block, weight, 64, &lay)) return -1;
-    for (int k = 104; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots from zero
+    timings_from(h, 104);
     const LocalUniv u{f0, beta, n_rank_def};
     const LocalBlocks bk{&lay};
     LocalResult R;
@@ -4144,7 +4081,7 @@ static int vecchia_terms_tail(ck_handle* h, DevTemps& tmp, const VecchiaData& D,
 static int vecchia_value(ck_handle* h, const std::string& name, const int64_t* rank_host, double max_dist, double* out3,
                          double* mean_host, double* var_host, int32_t* count_host, int64_t* stats3, int64_t* info) {
     const auto t_begin = std::chrono::steady_clock::now();
-    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    timings_from(h, 72);
     const int64_t N = h->N;
     DevTemps tmp;
     CkVecchiaOrder ord;
@@ -4334,7 +4271,7 @@ extern "C" int ck_loglik_vecchia_grad(ck_handle* h, const int64_t* rank_host, do
     if (vecchia_admit(h, "ck_loglik_vecchia_grad", rank_host && out3 && grad13 ? nullptr : "rank_host / out3 / grad13", max_dist))
         return -1;
     const auto t_begin = std::chrono::steady_clock::now();
-    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    timings_from(h, 72);
     const int NP = CK_FISHER_NPAR;
     for (int k = 0; k < NP; ++k) grad13[k] = NAN;
     const int64_t N = h->N, n0 = h->n[0];
@@ -4539,7 +4476,7 @@ static int local_sim_stages(ck_handle* h, const std::string& name, int i, const 
 extern "C" int ck_debug_simulate_local_weights(ck_handle* h, int i, const double* pcoords, int64_t m, const int64_t* rank_host,
                                                double max_dist, int64_t* idx_host, double* w_host) {
     CHKH(h);
-    for (int k = 110; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;
+    timings_from(h, 110);
     DevTemps tmp;
     LocalSim C;
     if (local_sim_stages(h, "ck_debug_simulate_local_weights", i, pcoords, m, rank_host, max_dist,
@@ -4570,7 +4507,7 @@ extern "C" int ck_simulate_local(ck_handle* h, int i, const double* pcoords, int
                                  double* var_host, int32_t* count_host, int64_t* stats4, int64_t* info) {
     CHKH(h);
     const auto t_begin = std::chrono::steady_clock::now();
-    for (int k = 110; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots from zero
+    timings_from(h, 110);
     DevTemps tmp;
     LocalSim C;
     if (local_sim_stages(h, "ck_simulate_local", i, pcoords, m, rank_host, max_dist,
@@ -4802,7 +4739,7 @@ extern "C" int ck_loglik_vecchia_trend(ck_handle* h, const int64_t* rank_host, d
         return 0;
     }
     const auto t_begin = std::chrono::steady_clock::now();
-    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    timings_from(h, 72);
     DevTemps tmp;
     VecchiaLdsStages C;
     if (vecchia_lds_stages(h, name, CK_VT_REFUSED_FOR, rank_host, max_dist, nullptr, tmp, &C)) return -1;
@@ -4833,7 +4770,7 @@ extern "C" int ck_loglik_vecchia_trend_grad(ck_handle* h, const int64_t* rank_ho
         return 0;
     }
     const auto t_begin = std::chrono::steady_clock::now();
-    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    timings_from(h, 72);
     const int NP = CK_FISHER_NPAR;
     for (int k = 0; k < NP; ++k) grad13[k] = NAN;
     const int64_t N = h->N;
@@ -4877,7 +4814,7 @@ extern "C" int ck_debug_vecchia_trend(ck_handle* h, const int64_t* rank_host, do
     if (vecchia_admit(h, name, rank_host && mu_host && vv_host && g_host ? nullptr : "rank_host / mu_host / vv_host / g_host",
                       max_dist, true))
         return -1;
-    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    timings_from(h, 72);
     DevTemps tmp;
     VecchiaLdsStages C;
     if (vecchia_lds_stages(h, name, CK_VT_REFUSED_FOR, rank_host, max_dist, nullptr, tmp, &C)) return -1;
@@ -4899,7 +4836,7 @@ extern "C" int ck_loglik_vecchia_fisher(ck_handle* h, const int64_t* rank_host, 
     if (vecchia_admit(h, "ck_loglik_vecchia_fisher", rank_host && fisher_host ? nullptr : "rank_host / fisher_host", max_dist))
         return -1;
     const auto t_begin = std::chrono::steady_clock::now();
-    for (int k = 72; k < CK_N_TIMINGS; ++k) h->t_ms[k] = 0.0;   // an admitted call starts its slots, and those behind, from zero
+    timings_from(h, 72);
     const int NP = CK_FISHER_NPAR, NT = CK_VI_NTRI;
     for (int k = 0; k < NP * NP; ++k) fisher_host[k] = NAN;
     const int64_t N = h->N, n0 = h->n[0];
@@ -5267,7 +5204,6 @@ extern "C" int ck_debug_get_lower(ck_handle* h, double* out, int64_t n) {
     CHKH(h);
     if (!h->assembled) return fail("nothing assembled");
     if (n != h->N) return fail("n must equal the number of observations");
-    std::vector<double> buf;
     memset(out, 0, (size_t)n * n * 8);
     const int64_t gap = h->n0p - h->n[0];
     auto ext = [&](int64_t g) -> int64_t {   // internal 0-based -> external 0-based, -1 for padding
@@ -5275,25 +5211,10 @@ extern "C" int ck_debug_get_lower(ck_handle* h, double* out, int64_t n) {
         if (g >= h->n0p && g < h->nend) return g - gap;
         return -1;
     };
-    for (int K = 0; K < h->nK; ++K) {
-        if (!h->sig[K]) continue;
-        const int64_t rows = h->Npad - (int64_t)K * CK_NB;
-        buf.resize(rows * CK_NB);
-        HIPCHK(hipMemcpyAsync(buf.data(), h->sig[K], rows * CK_NB * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        for (int64_t r = 0; r < rows; ++r) {
-            const int64_t er = ext((int64_t)K * CK_NB + r);
-            if (er < 0) continue;
-            for (int64_t c = 0; c < CK_NB; ++c) {
-                const int64_t gc = (int64_t)K * CK_NB + c;
-                if (gc > (int64_t)K * CK_NB + r) break;
-                const int64_t ec = ext(gc);
-                if (ec < 0) continue;
-                out[er * n + ec] = buf[r * CK_NB + c];
-            }
-        }
-    }
-    return 0;
+    return read_lower(h, h->sig, h->nK, h->Npad, [&](int64_t R, int64_t C, double v) {
+        const int64_t er = ext(R), ec = ext(C);
+        if (er >= 0 && ec >= 0) out[er * n + ec] = v;
+    });
 }
 
 // out[e] = entry (rows[e], cols[e]) of the lower triangle held in the packed panels (internal, padded indices; r >= c)

@@ -795,6 +795,103 @@ void ck_host_local_plan(const int* cnt, const CkLocalNeeds& nd, long long budget
         &out->tbatches, &out->slab_doubles);
 }
 
+// ---- the dense predictors' host arithmetic (ck_host.h) ----------------------------------------------------------------------
+int ck_host_block_members(const int32_t* block, int64_t m, int32_t r, std::vector<int>& off, std::vector<int64_t>& member,
+                          int64_t* q_max, int64_t* at) {
+    off.assign((size_t)r + 1, 0);
+    for (int64_t a = 0; a < m; ++a) {
+        if (block[a] < 0 || block[a] >= r) {
+            *at = a;
+            return CK_HOST_BLOCKS_LABEL;
+        }
+        ++off[(size_t)block[a] + 1];
+    }
+    int rc = CK_HOST_BLOCKS_OK;
+    *q_max = 0;
+    for (int32_t b = 0; b < r; ++b) {
+        const int q = off[(size_t)b + 1];
+        if (q == 0 && rc == CK_HOST_BLOCKS_OK) {
+            *at = b;
+            rc = CK_HOST_BLOCKS_EMPTY;
+        }
+        *q_max = std::max<int64_t>(*q_max, q);
+        off[(size_t)b + 1] += off[(size_t)b];
+    }
+    member.resize((size_t)m);
+    std::vector<int> pos(off.begin(), off.end() - 1);
+    for (int64_t a = 0; a < m; ++a) member[(size_t)pos[(size_t)block[a]]++] = a;
+    return rc;
+}
+
+int64_t ck_host_prior_pieces(const int* off, int32_t r, int full, std::vector<long long>& poff) {
+    auto n = [&](int64_t b) { return (int64_t)(off[b + 1] - off[b]); };
+    auto pieces = [](int64_t pairs) { return (pairs + CK_HOST_PRIOR_PIECE - 1) / CK_HOST_PRIOR_PIECE; };
+    poff.assign(1, 0);
+    poff.reserve((size_t)(full ? (int64_t)r * (r + 1) / 2 : r) + 1);
+    for (int64_t R = 0; R < r; ++R) {
+        if (!full) {
+            poff.push_back(poff.back() + pieces(n(R) * n(R)));
+            continue;
+        }
+        for (int64_t C = 0; C <= R; ++C) poff.push_back(poff.back() + pieces(n(R) * n(C)));
+    }
+    return poff.back();
+}
+
+int64_t ck_host_block_chunk(int64_t option, int64_t free_bytes, int64_t arena_rest, int64_t held_bytes, int64_t Npad, int64_t m) {
+    int64_t chunk = option;
+    if (chunk <= 0) {
+        const int64_t avail = arena_rest >= 0 ? std::max(arena_rest, held_bytes) : free_bytes / 2 + held_bytes;
+        chunk = std::max<int64_t>(avail / (8 * Npad) - CK_HOST_AUX_ALIGN, CK_HOST_AUX_ALIGN);
+    }
+    return std::min(chunk, m);
+}
+
+int64_t ck_host_draw_chunk(int64_t option, int64_t free_bytes, int64_t Mp, int64_t m, bool caller_noise, int64_t n_draws) {
+    int64_t chunk = option;
+    if (chunk <= 0) {
+        chunk = free_bytes / 2 / (8 * (Mp + (caller_noise ? 2 : 1) * m)) / 128 * 128;
+        chunk = std::max<int64_t>(128, std::min<int64_t>(chunk, 8192));
+    }
+    return std::min(chunk, n_draws);
+}
+
+int64_t ck_host_coincident_site(const double* pcoords, const int* cmap, const unsigned char* mask, int64_t m) {
+    std::vector<std::pair<std::pair<double, double>, int64_t>> key;
+    key.reserve((size_t)m);
+    for (int64_t j = 0; j < m; ++j)
+        if (!mask[j]) key.push_back({{pcoords[2 * cmap[j]], pcoords[2 * cmap[j] + 1]}, j});
+    std::sort(key.begin(), key.end());
+    int64_t stop = -1;
+    for (size_t q = 1; q < key.size(); ++q)
+        if (key[q].first.first == key[q - 1].first.first && key[q].first.second == key[q - 1].first.second &&
+            (stop < 0 || key[q].second < stop))
+            stop = key[q].second;   // the larger internal index of the pair (equal keys are sorted by index)
+    return stop;
+}
+
+void ck_host_universal_finish(const double* W, const double* beta, const double* Ainv, const double* f0, const int64_t* pperm,
+                              double c0, int64_t m, int p, int pi, int offi, double* pred, double* pred_err) {
+    ck_host_parallel(m, [&](int, int64_t a, int64_t e) {
+        double r[CK_HOST_TREND_QMAX];
+        for (int64_t s = a; s < e; ++s) {
+            const int64_t c = pperm ? pperm[s] : s;
+            const double* wr = &W[s * (p + 2)];
+            for (int j = 0; j < p; ++j) r[j] = -wr[2 + j];
+            for (int j = 0; j < pi; ++j) r[offi + j] += f0[c * pi + j];
+            double pr = wr[1], var = c0 - wr[0];
+            for (int j = 0; j < p; ++j) {
+                pr += r[j] * beta[j];
+                double t = 0.0;
+                for (int l = 0; l < p; ++l) t += Ainv[j * p + l] * r[l];
+                var += r[j] * t;
+            }
+            pred[c] = pr;
+            pred_err[c] = ck_host_err_of(var);
+        }
+    });
+}
+
 // ---- ck_predict_local_blocks: the member layout (ck_host.h) ----------------------------------------------------------------
 int ck_host_local_block_layout(const double* centres, int32_t r, const double* pcoords, int64_t m, const int32_t* block,
                                const double* weight, int pad, CkLocalBlockLayout* out) {
@@ -807,36 +904,29 @@ int ck_host_local_block_layout(const double* centres, int32_t r, const double* p
         if (!std::isfinite(centres[e]))
             return ck_fail(name + "coordinate " + std::to_string(e % 2) + " of centre " + std::to_string(e / 2) + " is not finite (" +
                            std::to_string(centres[e]) + ")");
-    out->off.assign((size_t)r + 1, 0);
-    for (int64_t a = 0; a < m; ++a) {
-        if (block[a] < 0 || block[a] >= r)
-            return ck_fail(name + "block label " + std::to_string(block[a]) + " of site " + std::to_string(a) + " is outside [0, " +
-                           std::to_string(r) + ")");
+    int64_t at = 0;
+    const int fault = ck_host_block_members(block, m, r, out->off, out->perm, &out->q_max, &at);
+    // the first site at fault is reported, its label before its weight and coordinates
+    for (int64_t a = 0; a < (fault == CK_HOST_BLOCKS_LABEL ? at : m); ++a) {
         if (!std::isfinite(weight[a]))
             return ck_fail(name + "weight of site " + std::to_string(a) + " is not finite (" + std::to_string(weight[a]) + ")");
         for (int c = 0; c < 2; ++c)
             if (!std::isfinite(pcoords[2 * a + c]))
                 return ck_fail(name + "coordinate " + std::to_string(c) + " of site " + std::to_string(a) + " is not finite (" +
                                std::to_string(pcoords[2 * a + c]) + ")");
-        ++out->off[(size_t)block[a] + 1];
     }
-    for (int32_t b = 0; b < r; ++b) {
-        const int q = out->off[(size_t)b + 1];
-        if (q == 0) return ck_fail(name + "block " + std::to_string(b) + " has no site");
-        out->q_max = std::max<int64_t>(out->q_max, q);
-        out->off[(size_t)b + 1] += out->off[(size_t)b];
-    }
+    if (fault == CK_HOST_BLOCKS_LABEL)
+        return ck_fail(name + "block label " + std::to_string(block[at]) + " of site " + std::to_string(at) + " is outside [0, " +
+                       std::to_string(r) + ")");
+    if (fault == CK_HOST_BLOCKS_EMPTY) return ck_fail(name + "block " + std::to_string(at) + " has no site");
     out->mpad = (m + pad - 1) / pad * pad;
-    out->perm.resize((size_t)m);
     out->xy.assign((size_t)(2 * out->mpad), 0.0);
     out->w.assign((size_t)out->mpad, 0.0);
-    std::vector<int> pos(out->off.begin(), out->off.end() - 1);
-    for (int64_t a = 0; a < m; ++a) {
-        const size_t k = (size_t)pos[(size_t)block[a]]++;
-        out->perm[k] = a;
-        out->xy[2 * k] = pcoords[2 * a];
-        out->xy[2 * k + 1] = pcoords[2 * a + 1];
-        out->w[k] = weight[a];
+    for (int64_t k = 0; k < m; ++k) {
+        const int64_t a = out->perm[(size_t)k];
+        out->xy[2 * (size_t)k] = pcoords[2 * a];
+        out->xy[2 * (size_t)k + 1] = pcoords[2 * a + 1];
+        out->w[(size_t)k] = weight[a];
     }
     return 0;
 }

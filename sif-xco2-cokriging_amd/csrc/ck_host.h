@@ -4,6 +4,7 @@
 // product by hipcc as plain C++ and, for tests/test_host_sanitize.py, by g++ with -fsanitize=address,undefined and
 // -fsanitize=thread (CPU only).
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -211,6 +212,61 @@ struct CkLocalPlan {
     long long slab_doubles = 0;
 };
 CK_HIDDEN void ck_host_local_plan(const int* cnt, const CkLocalNeeds& nd, long long budget, int trend, CkLocalPlan* out);
+
+// ---- the dense predictors' host arithmetic (ck_api.hip: ck_predict_universal, ck_predict_blocks, ck_conditional_draws) --------
+// The standard error behind a variance: a negative variance gives NaN and then 0.0 (np.nan_to_num; the device's k_reduce_pred
+// has the same rule)
+static inline double ck_host_err_of(double var) {
+    const double e = sqrt(var);
+    return e == e ? e : 0.0;
+}
+
+// Members of r blocks by stable counting sort: block[a] in [0, r) labels site a < m.
+//   off      r + 1 CSR offsets: the members of block b are the grouped positions off[b] .. off[b + 1]
+//   member   m: the caller's index of the member at each grouped position, the caller's order kept inside a block
+//   q_max    the largest block
+// Returns CK_HOST_BLOCKS_OK; CK_HOST_BLOCKS_LABEL with *at = the first site whose label is outside [0, r) (the outputs are not
+// usable); or CK_HOST_BLOCKS_EMPTY with *at = the first block without a member -- the outputs are complete, and a caller that
+// groups one chunk of a call's sites takes them as they are.  The caller words the refusal.
+#define CK_HOST_BLOCKS_OK 0
+#define CK_HOST_BLOCKS_LABEL 1
+#define CK_HOST_BLOCKS_EMPTY 2
+CK_HIDDEN int ck_host_block_members(const int32_t* block, int64_t m, int32_t r, std::vector<int>& off, std::vector<int64_t>& member,
+                                    int64_t* q_max, int64_t* at);
+
+// Piece offsets of the blocks' prior (ck_blocks.hip): poff[e] .. poff[e + 1] = the pieces of CK_HOST_PRIOR_PIECE pairs of element
+// e (full == 0: e = b, n_b^2 pairs; full != 0: e = R (R + 1) / 2 + C, n_R n_C pairs), n_b = off[b + 1] - off[b].  Returns the
+// number of pieces, poff's last entry.
+#define CK_HOST_PRIOR_PIECE 512   // == CK_PRIOR_PIECE (ck_internal.h)
+CK_HIDDEN int64_t ck_host_prior_pieces(const int* off, int32_t r, int full, std::vector<long long>& poff);
+
+// ck_predict_blocks' sites per pass through the assembly.  option > 0 (block_chunk): that many.  Otherwise what the handle may
+// still take beside the held_bytes of point rows it holds: with an arena (arena_rest >= 0, the bytes it has left; it never takes
+// memory back) the larger of the two, without one (arena_rest < 0) half of free_bytes plus what is held (the buffer is freed
+// before a larger one is allocated); in rows of Npad doubles, less CK_HOST_AUX_ALIGN rows of padding, at least CK_HOST_AUX_ALIGN.
+// Never more than m.
+#define CK_HOST_AUX_ALIGN 256   // == CK_AUX_ALIGN (ck_internal.h)
+CK_HIDDEN int64_t ck_host_block_chunk(int64_t option, int64_t free_bytes, int64_t arena_rest, int64_t held_bytes, int64_t Npad,
+                                      int64_t m);
+// ck_conditional_draws' draws per pass.  option > 0 (draw_chunk): that many.  Otherwise the multiple of 128 whose noise (Mp
+// doubles a draw), draws and, with the caller's noise, its copy (m doubles each) fit half of free_bytes, within [128, 8192].
+// Never more than n_draws.
+CK_HIDDEN int64_t ck_host_draw_chunk(int64_t option, int64_t free_bytes, int64_t Mp, int64_t m, bool caller_noise, int64_t n_draws);
+
+// Two sites at the same coordinates have identical rows of the posterior covariance: the exact factorisation stops at the later
+// of them.  pcoords: m x 2 in the caller's order; cmap[j]: the caller's index of internal position j < m; mask[j] != 0: position
+// j is deflated and cannot stop anything.  Returns the smallest internal position that coincides with an earlier one, or -1.
+CK_HIDDEN int64_t ck_host_coincident_site(const double* pcoords, const int* cmap, const unsigned char* mask, int64_t m);
+
+// ck_predict_universal's epilogue over the reduced rows W (internal order, p + 2 doubles each: |V_s|^2, V_s . y, U^T V_s):
+//   r_s = x0_s - U^T V_s,  pred_s = V_s . y + r_s^T beta,  pred_err_s^2 = c0 - |V_s|^2 + r_s^T A^-1 r_s
+// with x0_s = f0[c pi .. c pi + pi) in the columns offi .. offi + pi of the predicted process and zero elsewhere (pi may be 0);
+// c = pperm[s], or s where pperm is null: the results land in the caller's order.  beta: p, Ainv: p x p row-major, p <=
+// CK_HOST_TREND_QMAX - 1.
+#define CK_HOST_TREND_QMAX 17   // == CK_UNIV_QMAX (ck_internal.h)
+CK_HIDDEN void ck_host_universal_finish(const double* W, const double* beta, const double* Ainv, const double* f0,
+                                        const int64_t* pperm, double c0, int64_t m, int p, int pi, int offi, double* pred,
+                                        double* pred_err);
 
 // ---- block cokriging in the neighbourhood: the member layout (ck_api.hip: ck_predict_local_blocks) --------------------------
 // Pure index work, no device.  block[a] in [0, r) labels member site a (pcoords: m x 2, weight: m), centres: r x 2.

@@ -92,7 +92,7 @@ void ck_launch_block_fold(hipStream_t s, const double* aux, int64_t mpad, int n_
 // (c0 / c1 / c2: exact-formula coordinates, off: r + 1 offsets).  full == 0: diag[b] = Cbar[b][b];
 // full != 0: the lower triangle into packed panels (panel J = C / NB: rows J NB .., ld = NB).
 // The pairs of element e (e = b | R (R + 1) / 2 + C) are cut into pieces of CK_PRIOR_PIECE pairs: poff[e] .. poff[e + 1]
-// (n_elem + 1 words, host-built: ck_block_prior_pieces), part: n_pieces doubles of scratch
+// (n_elem + 1 words, host-built: ck_host_prior_pieces), part: n_pieces doubles of scratch
 #define CK_PRIOR_PIECE 512
 void ck_launch_block_prior(hipStream_t s, const CkMatern* blk, int metric, const double* c0, const double* c1,
                            const double* c2, const double* w, const int* off, int64_t r, int full, const long long* poff,

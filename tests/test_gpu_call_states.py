@@ -49,3 +49,31 @@ def test_refusals_name_the_last_call(native):
     h.predict(0, pc)
     assert h.verify_model() == want
     h.close()
+
+
+def test_predict_blocks_leaves_the_point_path_timings(native):
+    """Slots 0 .. 15 of ck_timings describe the last point-path calls.  ck_predict_blocks -- in one pass, in three passes
+    through the assembly stage, and refused -- leaves every one of them as it was, and a ck_predict afterwards returns the first
+    one's bits."""
+    ds = dc.data_set(dc.SMALL)
+    pc = dc.pred_sites(np.random.default_rng(7), ds.metric, 5)
+    block, w = [0, 1, 0, 1, 1], np.ones(5)
+    h = handle(native, ds)
+    pred, err = h.predict(0, pc)
+    point = list(h.timings().items())[:16]
+    assert [k for k, _ in point][:5] == ["assemble_sigma_ms", "factor_ms", "assemble_aux_ms", "solve_ms", "reduce_ms"]
+    assert all(dict(point)[k] > 0.0 for k in ("assemble_sigma_ms", "factor_ms", "assemble_aux_ms", "solve_ms", "reduce_ms"))
+    h.set_option("block_chunk", 0)
+    h.predict_blocks(0, pc, block, w, 2, want_cov=True)
+    assert list(h.timings().items())[:16] == point and h.timings()["blocks_chunks"] == 1
+    h.set_option("block_chunk", 2)
+    h.predict_blocks(0, pc, block, w, 2, want_cov=True)
+    t = h.timings()
+    assert list(t.items())[:16] == point and t["blocks_chunks"] == 3 and t["blocks_assemble_ms"] > 0.0
+    with pytest.raises(native.NativeError) as e:
+        h.predict_blocks(0, pc, [0, 1, 2, 1, 1], w, 2)
+    assert str(e.value) == "ck_predict_blocks: block label 2 of site 2 is outside [0, r)"
+    assert list(h.timings().items())[:16] == point
+    again = h.predict(0, pc)
+    assert np.array_equal(again[0], pred) and np.array_equal(again[1], err)
+    h.close()
