@@ -632,6 +632,55 @@ int ck_predict_local_blocks(ck_handle* h, int i, const double* centres_host /* r
                             double* pred_host, double* pred_err_host, double* beta_host /* r x p or NULL */,
                             int64_t* n_empty, int64_t* n_not_pd, int64_t* n_rank_def, int64_t* k_max);
 
+/* Leave-group-out and buffer cross-validation in the moving neighbourhood: ck_cv_folds' question for data whose Sigma does not
+ * fit -- leave-track-out, spatial blocks, K-fold, a buffer around the withheld datum -- answered by the local predictor.  Every
+ * predicted datum of process i is the point of one local prediction from which some sites are WITHHELD; two conditions, both
+ * evaluated where the radius predicate d <= max_dist is, with d the distance the local kernels compute on the device:
+ *   fold    site g of either process is withheld from datum a when label(g) >= 0 and label(g) == label(a).  fold_k[b], in the
+ *           caller's order of ck_set_data of process k, is the label of datum b; -1: never withheld, a neighbour of everything;
+ *   buffer  a site of process q with d <= buffer2[q] is withheld (buffer2[q] < 0: off; buffer2 NULL: both off).  The cv flag
+ *           of ck_predict_local is the case buffer2[i] = 0, other process off.
+ * The cap of ck_set_local_neighbours applies AFTER withholding: per process the nmax_q nearest remaining candidates, ties at
+ * the cut kept.  Everything behind the neighbour list is ck_predict_local's and, with a trend set, ck_predict_local_universal's
+ * (f0: n_i x p_i regressors of process i at ITS DATA in the caller's order, NULL when p_i = 0): the local system, ck_set_noise
+ * on its diagonal, the size classes, the NaN rules and the counters.  A fold that empties a neighbourhood is counted in n_empty
+ * and is no error.  There is no limit on a fold's size.
+ * The predicted data are those of process i with a label >= 0.  The array of process i may be NULL: then every datum of the
+ * process is predicted, which is admitted only with buffer2[i] >= 0 so that no datum ever predicts itself.  The other process's
+ * array may be NULL (nothing of it is withheld by label); with one process it is ignored.  Every fold in [0, n_folds) must hold
+ * at least one datum of process i; n_folds = 0 is the buffer-only call (every label given must then be -1).
+ * Outputs, in the caller's order of process i, NaN for a datum that is never withheld: pred, pred_err (n_i), beta (n_i x p or
+ * NULL).  counters4: n_empty, n_not_pd, n_rank_def, k_max.
+ * Scores.  Per scored datum e = z - pred and v = pred_err^2 + s_i d_a: the predictive variance of the withheld OBSERVATION --
+ * the local predictor filters measurement error out of pred_err, so the datum's own ck_set_noise term is added back, as
+ * ck_cv_folds has it inside Q_SS^-1.  A datum whose pred is not finite or whose v is not > 0 is skipped and not counted.
+ * fold_stats (n_folds x 6 row-major, or NULL): [0] data withheld, both processes counted; [1] data of process i scored; [2] sum
+ * e; [3] sum e^2; [4] sum e^2 / v; [5] sum log v.  score5 (or NULL): columns [1 .. 5] over all predicted data, the folds' sums
+ * added in fold order.  The negative log predictive density these give, 1/2 (n log 2 pi + [5] + [4]), is the sum of MARGINAL
+ * densities: different data have different neighbourhoods, which define no joint law of a fold (ck_cv_folds reports the joint one).
+ * Device path: the labels of both processes are laid out in the internal site order (k_cv_labels); the counting pass, the select
+ * pass of a capped call and every solve kernel take the two conditions from the call's one descriptor; a fold's sums come from
+ * one workgroup (k_cv_fold_scores: a strided sum per thread, a fixed 256-wide tree).  No atomics in any floating-point sum:
+ * repeated calls give the same bits.  Identities: singleton folds on data without coincident sites, and buffer2 = (0, off)
+ * without labels on any data, give ck_predict_local(cv = 1) at the data, bit for bit.
+ * Nothing on the handle is invalidated: a resident factor and the bits of ck_predict / ck_predict_local before and after are
+ * unchanged.  Needs ck_set_model / ck_set_data; optional ck_set_trend, ck_set_noise, ck_set_local_neighbours.
+ * Refused through ck_last_error, naming the process, the datum and the value where there is one: a partitioned handle; a label
+ * outside [-1, n_folds); a fold without a datum of process i; n_folds < 0; a non-finite buffer; the array of process i NULL with
+ * buffer2[i] off; f0 == NULL with p_i > 0; a non-finite or negative max_dist.  ck_timings [118 ..] describe the call. */
+int ck_cv_local_folds(ck_handle* h, int i, const int32_t* fold0_host, const int32_t* fold1_host, int32_t n_folds,
+                      const double* buffer2 /* per process, < 0 = off; NULL = both off */,
+                      const double* f0_host /* n_i x p_i regressors at the data of process i, NULL when p_i = 0 */,
+                      double max_dist, double* pred_host, double* pred_err_host, double* beta_host /* n_i x p or NULL */,
+                      double* fold_stats_host /* n_folds x 6 or NULL */, double* score5 /* or NULL */,
+                      int64_t* counters4 /* n_empty, n_not_pd, n_rank_def, k_max; or NULL */);
+/* The select pass of ck_cv_local_folds alone, with the handle's caps: count (n_i x 2) the final number of neighbours of process
+ * 0 / 1 of every predicted datum, rcut (n_i x 2) its cut distances, in the caller's order; (0, NaN) rows for a datum that is
+ * never withheld.  The test surface of the withholding conditions.  Sets ck_timings [60 ..]. */
+int ck_debug_local_cv_neighbours(ck_handle* h, int i, const int32_t* fold0_host, const int32_t* fold1_host, int32_t n_folds,
+                                 const double* buffer2, double max_dist, int32_t* count_host /* n_i x 2 */,
+                                 double* rcut_host /* n_i x 2 */);
+
 /* Conditional simulation in the moving neighbourhood (gstat's nsim with nmax / maxdist: sequential Gaussian simulation): draws of
  * process i at m sites from the data around each site and the sites drawn before it -- no Sigma, no limit on m but memory.
  * Definition.  The m sites carry distinct integer ranks (rank_host; only their order counts).  Stack the sites behind the data
@@ -840,7 +889,10 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * [60 ..] are filled as by ck_predict_local.
  * ck_simulate_local (n up to 118): [110] the select pass of the sites on the augmented set; [111] the weights (k_local_sim_weights);
  * [112] the level planning on the host; [113] the recursion (one launch per level and chunk, and the scatter); [114] host wall
- * clock of the call; [115] sites solved (a non-empty set); [116] levels; [117] sum over the sites of their site-neighbours. */
+ * clock of the call; [115] sites solved (a non-empty set); [116] levels; [117] sum over the sites of their site-neighbours.
+ * ck_cv_local_folds (n up to 124): [118] the counting or select pass of the predicted data; [119] the solves of every size
+ * class; [120] the fold scores (k_cv_fold_scores); [121] host wall clock of the call; [122] data predicted; [123] folds.  [10],
+ * [14] and [60 ..] are filled as by ck_predict_local. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it

@@ -34,7 +34,7 @@
 #include "ck_vecchia.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 118
+#define CK_N_TIMINGS 124
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -3404,6 +3404,7 @@ static CkLocalProblem local_problem(const ck_handle* h, int i, int cv, double ma
     P.metric = h->metric;
     P.i_pred = i;
     P.cv = cv ? 1 : 0;
+    if (cv) P.lo[i] = 0.0;   // the co-located data of process i
     P.max_dist = max_dist;
     P.c0var = h->blk[2 * i].amp + h->blk[2 * i].nugget;   // covariance(i, 0)[0], point_prediction.py:66
     P.sc = h->s0;
@@ -3449,6 +3450,7 @@ struct LocalPass {
     int64_t m = 0, mp = 0;
     double *d_p3 = nullptr, *d_pu = nullptr, *d_rq = nullptr, *d_cp = nullptr;   // d_rq, d_cp: select pass only
     int *d_cnt = nullptr, *d_sel = nullptr, *d_rp = nullptr;                     // d_sel: select pass only; d_rp: with rp_host
+    int* d_fp = nullptr;                                                         // with the fold labels of a withholding call
     CkLocalProblem prob;
     std::vector<int> cnt, sel;
     double pass_ms = 0.0;   // the pass's device window, whichever pass it was
@@ -3458,8 +3460,14 @@ struct LocalPass {
 // sees a cap pointer.  d_rs / rp_host: the precedence condition of the Vecchia likelihood (device: every site's position in the
 // ordering; host: the m points'), both null without one.  rcut_host: m x 2, receives the cut distances of a select pass.  One
 // synchronisation, after the downloads; pass_ms is read here, so [ev0, ev1] are free again when the stage returns.
+// wh: the withholding conditions of ck_cv_local_folds (null: none, and no kernel sees a label or a radius).
+struct LocalWithhold {
+    const int* d_fs;   // device: every site's fold label in the internal site order (Npad ints), or null: no fold condition
+    const int* fp;     // host: the m points' labels (read with d_fs)
+    double wb[2];      // the buffer radius of process 0 / 1, negative: off
+};
 static int local_pass(ck_handle* h, DevTemps& tmp, int i, const double* pcoords, int64_t m, double max_dist, int cv, bool select,
-                      const int* d_rs, const int* rp_host, double* rcut_host, LocalPass* out) {
+                      const int* d_rs, const int* rp_host, double* rcut_host, LocalPass* out, const LocalWithhold* wh = nullptr) {
     LocalPass& S = *out;
     const int64_t mp = S.mp = roundup(S.m = m, 64);
     double* d_pc = nullptr;
@@ -3476,11 +3484,24 @@ static int local_pass(ck_handle* h, DevTemps& tmp, int i, const double* pcoords,
         HIPCHK(tmp.get(&S.d_rp, (size_t)(mp * sizeof(int))));
         HIPCHK(hipMemcpyAsync(S.d_rp, rp_host, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
     }
+    if (wh && wh->d_fs) {
+        HIPCHK(tmp.get(&S.d_fp, (size_t)(mp * sizeof(int))));
+        HIPCHK(hipMemcpyAsync(S.d_fp, wh->fp, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    }
     HIPCHK(hipMemsetAsync(d_pc, 0, 2 * mp * 8, h->stream));
     HIPCHK(hipMemcpyAsync(d_pc, pcoords, 2 * m * 8, hipMemcpyHostToDevice, h->stream));
     ck_launch_prep_sites(h->stream, d_pc, mp, h->metric, S.d_p3, S.d_p3 + mp, S.d_p3 + 2 * mp, S.d_pu);
     HIPCHK(hipEventRecord(h->ev0, h->stream));
     S.prob = local_problem(h, i, cv, max_dist);
+    if (wh) {
+        S.prob.fs = wh->d_fs;
+        S.prob.fp = S.d_fp;
+        for (int q = 0; q < 2; ++q)
+            if (wh->wb[q] >= 0.0) {
+                S.prob.cv = 1;
+                S.prob.lo[q] = std::max(S.prob.lo[q], wh->wb[q]);
+            }
+    }
     S.prob.pc = S.d_p3;
     S.prob.pu = S.d_pu;
     S.prob.mpad = mp;
@@ -3488,6 +3509,7 @@ static int local_pass(ck_handle* h, DevTemps& tmp, int i, const double* pcoords,
     S.prob.cp = S.d_cp;
     S.prob.rs = d_rs;
     S.prob.rp = S.d_rp;
+    S.prob.listed = (d_rs || S.prob.fs) ? 1 : 0;
     if (select)
         ck_launch_local_select(h->stream, S.prob, m, local_nmax_of(h, 0), local_nmax_of(h, 1), local_key_cap(h), S.d_cnt, S.d_sel,
                                S.d_rq, S.d_cp);
@@ -3666,7 +3688,7 @@ static int local_block_members(ck_handle* h, DevTemps& tmp, int i, const CkLocal
 
 static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_t m, double max_dist, int cv, double* pred,
                               double* pred_err, LocalResult* res, const LocalUniv* u, const LocalVecchia* vc = nullptr,
-                              const LocalBlocks* bk = nullptr) {
+                              const LocalBlocks* bk = nullptr, const LocalWithhold* wh = nullptr) {
     LocalResult& R = *res = LocalResult();
     if (ensure_layout(h, false)) return -1;   // sites, tables, chunk bounds -- no Sigma panels
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
@@ -3713,7 +3735,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     // host-side planning and a growth of the scratch slab (hipMalloc: up to seconds) lie between the pass and the solve window
     const bool select = local_nmax_of(h, 0) > 0 || local_nmax_of(h, 1) > 0 || vc;
     LocalPass S;
-    if (local_pass(h, tmp, i, pcoords, m, max_dist, cv, select, vc ? vc->d_rs : nullptr, vc ? vc->rp : nullptr, nullptr, &S)) return -1;
+    if (local_pass(h, tmp, i, pcoords, m, max_dist, cv, select, vc ? vc->d_rs : nullptr, vc ? vc->rp : nullptr, nullptr, &S, wh)) return -1;
     if (bk && local_block_members(h, tmp, i, *bk->lay, m, &S.prob, &R.prior_ms)) return -1;
     const CkLocalProblem& P = S.prob;   // what every launch below is told about the call
     const int* d_cnt = S.d_cnt;
@@ -3738,7 +3760,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     size_t mem_free = 0;
     if (local_budget_doubles(h, &budget, &mem_free)) return -1;
     if (budget < nd.need_max) budget = nd.need_max;
-    if ((size_t)nd.need_max * 8 > mem_free) return fail(std::string(bk ? "ck_predict_local_blocks" : u ? "ck_predict_local_universal" : "ck_predict_local") + ": a neighbourhood of " + std::to_string(nd.k_max) + " sites does not fit the device memory");
+    if ((size_t)nd.need_max * 8 > mem_free) return fail(std::string(wh ? "ck_cv_local_folds" : bk ? "ck_predict_local_blocks" : u ? "ck_predict_local_universal" : "ck_predict_local") + ": a neighbourhood of " + std::to_string(nd.k_max) + " sites does not fit the device memory");
     CkLocalPlan plan;   // slab offsets, the batches of both classes under the budget, the tiled systems
     ck_host_local_plan(cnt.data(), nd, budget, up, &plan);
     if (local_slab_grow(h, plan.slab_doubles, budget, &R.grow_ms)) return -1;
@@ -3938,6 +3960,184 @@ extern "C" int ck_predict_local_blocks(ck_handle* h, int i, const double* centre
     h->t_ms[107] = R.prior_ms;                   // the sigma_BB pass
     h->t_ms[108] = R.total_ms;                   // host wall clock of the call
     h->t_ms[109] = R.cbar_evals;                 // sum_b q_b k_b
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// leave-group-out and buffer cross-validation in the moving neighbourhood (include/cokrige.h has the rules)
+// ---------------------------------------------------------------------------------------
+// What ck_cv_local_folds and ck_debug_local_cv_neighbours (name) do before the first launch, written once: the refusals, the layout,
+// the plan (ck_host.cpp), the labels of both processes in the internal site order on the device (k_cv_labels; null without
+// labels) and the coordinates of the predicted data.
+struct LocalCvStages {
+    CkLocalCvPlan plan;
+    LocalWithhold wh{nullptr, nullptr, {-1.0, -1.0}};
+    std::vector<double> pts;   // m x 2: the predicted data's coordinates, plist order
+    int64_t m = 0;
+};
+static int local_cv_stages(ck_handle* h, const std::string& name, int i, const int32_t* fold0, const int32_t* fold1, int32_t n_folds,
+                           const double* buffer2, double max_dist, DevTemps& tmp, LocalCvStages* out) {
+    LocalCvStages& C = *out;
+    if (h->world != 1)
+        return fail(name + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) + ")");
+    if (i < 0 || i >= h->n_procs) return fail(name + ": process index " + std::to_string(i) + " out of range");
+    if (!(max_dist >= 0.0) || !std::isfinite(max_dist))
+        return fail(name + ": max_dist must be finite and >= 0, got " + std::to_string(max_dist));
+    for (int q = 0; q < 2 && buffer2; ++q) {
+        if (!std::isfinite(buffer2[q])) return fail(name + ": buffer2[" + std::to_string(q) + "] = " + std::to_string(buffer2[q]) + " is not finite (a negative value turns the buffer of a process off)");
+        C.wh.wb[q] = q < h->n_procs && buffer2[q] >= 0.0 ? buffer2[q] : -1.0;
+    }
+    if (ensure_layout(h, false)) return -1;   // sites, tables, chunk bounds, perm -- no Sigma panels
+    if (h->N > INT32_MAX) return fail(name + ": more than 2^31 - 1 data");
+    if (ck_host_local_cv_plan(name.c_str(), i, h->n_procs, h->n, h->n0p, h->perm[0].data(), h->n_procs == 2 ? h->perm[1].data() : nullptr,
+                              fold0, fold1, n_folds, C.wh.wb[i] >= 0.0, &C.plan))
+        return -1;
+    const int32_t* fold[2] = {fold0, h->n_procs == 2 ? fold1 : nullptr};
+    const int64_t n0 = h->n[0], n1 = h->n_procs == 2 ? h->n[1] : 0;
+    if (n_folds > 0 && (fold[0] || fold[1])) {
+        int *d_fs = nullptr, *d_lab = nullptr, *d_gself = nullptr;
+        HIPCHK(tmp.get(&d_fs, (size_t)h->Npad * sizeof(int)));
+        HIPCHK(tmp.get(&d_lab, (size_t)std::max<int64_t>(h->N, 1) * sizeof(int)));
+        HIPCHK(tmp.get(&d_gself, (size_t)std::max<int64_t>(h->N, 1) * sizeof(int)));
+        HIPCHK(hipMemsetAsync(d_fs, 0xFF, (size_t)h->Npad * sizeof(int), h->stream));   // -1 everywhere
+        if (fold[0] && n0 > 0) HIPCHK(hipMemcpyAsync(d_lab, fold[0], (size_t)n0 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (fold[1] && n1 > 0) HIPCHK(hipMemcpyAsync(d_lab + n0, fold[1], (size_t)n1 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_gself, C.plan.gself.data(), (size_t)h->N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        ck_launch_cv_labels(h->stream, n0, n1, fold[0] ? d_lab : nullptr, fold[1] ? d_lab + n0 : nullptr, d_gself, d_fs);
+        HIPCHK(hipGetLastError());
+        C.wh.d_fs = d_fs;
+        C.wh.fp = C.plan.fp.data();
+    }
+    C.m = (int64_t)C.plan.plist.size();
+    C.pts.resize((size_t)(2 * C.m));
+    for (int64_t t = 0; t < C.m; ++t) {
+        const int64_t a = C.plan.plist[(size_t)t];
+        C.pts[(size_t)(2 * t)] = h->h_coords[i][(size_t)(2 * a)];
+        C.pts[(size_t)(2 * t + 1)] = h->h_coords[i][(size_t)(2 * a + 1)];
+    }
+    return 0;
+}
+
+// The select pass of a cross-validation call alone, with the handle's caps: the test surface of the withholding conditions.
+extern "C" int ck_debug_local_cv_neighbours(ck_handle* h, int i, const int32_t* fold0, const int32_t* fold1, int32_t n_folds,
+                                            const double* buffer2, double max_dist, int32_t* count, double* rcut) {
+    CHKH(h);
+    const std::string name = "ck_debug_local_cv_neighbours";
+    if (i >= 0 && i < h->n_procs && h->n[i] > 0 && (!count || !rcut)) return fail(name + ": null count / rcut");
+    DevTemps tmp;
+    LocalCvStages C;
+    if (local_cv_stages(h, name, i, fold0, fold1, n_folds, buffer2, max_dist, tmp, &C)) return -1;
+    timings_from(h, 60);
+    LocalPass S;
+    std::vector<double> rc((size_t)(2 * C.m));
+    if (C.m > 0 && local_pass(h, tmp, i, C.pts.data(), C.m, max_dist, 0, true, nullptr, nullptr, rc.data(), &S, &C.wh)) return -1;
+    for (int64_t a = 0; a < 2 * h->n[i]; ++a) {
+        count[a] = 0;
+        rcut[a] = NAN;
+    }
+    for (int64_t t = 0; t < C.m; ++t) {
+        const int64_t a = C.plan.plist[(size_t)t];
+        for (int q = 0; q < 2; ++q) {
+            count[2 * a + q] = S.sel[(size_t)(4 * t + q)];
+            rcut[2 * a + q] = rc[(size_t)(2 * t + q)];
+        }
+    }
+    write_select_timings(h, S.st);
+    return 0;
+}
+
+extern "C" int ck_cv_local_folds(ck_handle* h, int i, const int32_t* fold0, const int32_t* fold1, int32_t n_folds, const double* buffer2,
+                                 const double* f0, double max_dist, double* pred, double* pred_err, double* beta, double* fold_stats,
+                                 double* score5, int64_t* counters4) {
+    CHKH(h);
+    const std::string name = "ck_cv_local_folds";
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (i >= 0 && i < h->n_procs && h->n[i] > 0 && (!pred || !pred_err)) return fail(name + ": null pred / pred_err");
+    const bool trend = trend_total(h) > 0;
+    if (trend && i >= 0 && i < h->n_procs && h->trend_p[i] > 0 && !f0)
+        return fail(name + ": null regressors f0 with a trend of p_i = " + std::to_string(h->trend_p[i]) + " columns of process " +
+                    std::to_string(i));
+    DevTemps tmp;
+    LocalCvStages C;
+    if (local_cv_stages(h, name, i, fold0, fold1, n_folds, buffer2, max_dist, tmp, &C)) return -1;
+    timings_from(h, 118);
+    const int64_t m = C.m, n_i = h->n[i];
+    const int up = trend ? trend_total(h) : 0, upi = trend ? h->trend_p[i] : 0;
+    // the predicted data are the points of one call of the local predictor; its outputs come back in plist order
+    std::vector<double> pl((size_t)m), el((size_t)m), f0l((size_t)(m * upi)), bl(beta ? (size_t)(m * up) : 0);
+    for (int64_t t = 0; t < m; ++t)
+        for (int j = 0; j < upi; ++j) f0l[(size_t)(t * upi + j)] = f0[(int64_t)C.plan.plist[(size_t)t] * upi + j];
+    int64_t n_rank_def = 0;
+    const LocalUniv u{f0l.data(), beta ? bl.data() : nullptr, &n_rank_def};
+    LocalResult R;
+    if (predict_local_impl(h, i, C.pts.data(), m, max_dist, 0, pl.data(), el.data(), &R, trend ? &u : nullptr, nullptr, nullptr, &C.wh))
+        return -1;
+    for (int64_t a = 0; a < n_i; ++a) pred[a] = pred_err[a] = NAN;
+    if (beta) std::fill(beta, beta + n_i * up, NAN);
+    for (int64_t t = 0; t < m; ++t) {
+        const int64_t a = C.plan.plist[(size_t)t];
+        pred[a] = pl[(size_t)t];
+        pred_err[a] = el[(size_t)t];
+        for (int j = 0; beta && j < up; ++j) beta[a * up + j] = bl[(size_t)(t * up + j)];
+    }
+    if (counters4) {
+        counters4[0] = R.n_empty;
+        counters4[1] = R.n_not_pd;
+        counters4[2] = n_rank_def;
+        counters4[3] = R.k_max;
+    }
+    // the scores: e = z - pred, v = pred_err^2 + the datum's own s d (the variance of the withheld OBSERVATION), one workgroup
+    // per group of the plan, then the totals over the groups in order on the host
+    const int64_t ng = C.plan.n_groups;
+    std::vector<double> sums((size_t)(ng * CK_CV_NSCORE), 0.0);
+    double scores_ms = 0.0;
+    if (m > 0 && ng > 0 && (fold_stats || score5)) {
+        const bool nz = h->noise_on && !h->noise_var[i].empty();
+        std::vector<double> zl((size_t)m), ol(nz ? (size_t)m : 0);
+        for (int64_t t = 0; t < m; ++t) {
+            const int64_t a = C.plan.plist[(size_t)t];
+            zl[(size_t)t] = h->h_values[i][(size_t)a];
+            if (nz) ol[(size_t)t] = h->noise_scale[i] * h->noise_var[i][(size_t)a];
+        }
+        double *d_in = nullptr, *d_sum = nullptr;
+        int* d_idx = nullptr;
+        long long* d_goff = nullptr;
+        HIPCHK(tmp.get(&d_in, (size_t)(4 * m * 8)));
+        HIPCHK(tmp.get(&d_sum, (size_t)(ng * CK_CV_NSCORE * 8)));
+        HIPCHK(tmp.get(&d_idx, (size_t)m * sizeof(int)));
+        HIPCHK(tmp.get(&d_goff, (size_t)(ng + 1) * sizeof(long long)));
+        HIPCHK(hipMemcpyAsync(d_in, zl.data(), (size_t)(m * 8), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_in + m, pl.data(), (size_t)(m * 8), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_in + 2 * m, el.data(), (size_t)(m * 8), hipMemcpyHostToDevice, h->stream));
+        if (nz) HIPCHK(hipMemcpyAsync(d_in + 3 * m, ol.data(), (size_t)(m * 8), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_idx, C.plan.idx.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_goff, C.plan.off.data(), (size_t)(ng + 1) * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        ck_launch_cv_fold_scores(h->stream, ng, CkCvScoreArgs{d_idx, d_goff, d_in, d_in + m, d_in + 2 * m, nz ? d_in + 3 * m : nullptr, d_sum});
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        HIPCHK(hipMemcpyAsync(sums.data(), d_sum, sums.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(elapsed_ms(h->ev0, h->ev1, &scores_ms));
+    }
+    if (fold_stats)
+        for (int32_t f = 0; f < n_folds; ++f) {
+            fold_stats[6 * f] = (double)C.plan.size[(size_t)f];
+            for (int c = 0; c < CK_CV_NSCORE; ++c) fold_stats[6 * f + 1 + c] = sums[(size_t)(f * CK_CV_NSCORE + c)];
+        }
+    if (score5)
+        for (int c = 0; c < CK_CV_NSCORE; ++c) {
+            double acc = 0.0;
+            for (int64_t g = 0; g < ng; ++g) acc += sums[(size_t)(g * CK_CV_NSCORE + c)];
+            score5[c] = acc;
+        }
+    if (m > 0) write_local_timings(h, R);
+    h->t_ms[118] = R.pass_ms;             // the counting or select pass of the predicted data
+    h->t_ms[119] = R.solve_ms;            // assembly, factorisations, reductions: every size class
+    h->t_ms[120] = scores_ms;             // k_cv_fold_scores
+    h->t_ms[121] = ms_since(t_begin);     // host wall clock of the call
+    h->t_ms[122] = (double)m;             // data predicted
+    h->t_ms[123] = (double)n_folds;
     return 0;
 }
 

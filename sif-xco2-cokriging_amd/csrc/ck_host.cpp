@@ -736,6 +736,71 @@ int ck_host_fold_plan(int i, int n_procs, const int64_t n[2], int64_t n0p, const
     return 0;
 }
 
+// ---- ck_cv_local_folds: the predicted data, their labels, the score groups (ck_host.h) ---------------------------------------
+int ck_host_local_cv_plan(const char* name_c, int i, int n_procs, const int64_t n[2], int64_t n0p, const int64_t* perm0,
+                          const int64_t* perm1, const int32_t* fold0, const int32_t* fold1, int32_t n_folds, bool buffer_i,
+                          CkLocalCvPlan* out) {
+    const std::string name = std::string(name_c) + ": ";
+    if (!out) return ck_fail(name + "null plan");
+    if (n_procs < 1 || n_procs > 2 || i < 0 || i >= n_procs) return ck_fail(name + "process index out of range");
+    if (n_folds < 0) return ck_fail(name + "n_folds = " + std::to_string(n_folds) + " is negative");
+    const int32_t* fold[2] = {fold0, n_procs == 2 ? fold1 : nullptr};
+    const int64_t* perm[2] = {perm0, perm1};
+    if (!fold[i] && !buffer_i)
+        return ck_fail(name + "the fold labels of the predicted process " + std::to_string(i) + " are null and its buffer is off: every datum "
+                       "would predict itself (give labels, or buffer2[" + std::to_string(i) + "] >= 0)");
+    *out = CkLocalCvPlan();
+    const int64_t n_i = n[i];
+    out->size.assign((size_t)n_folds, 0);
+    std::vector<int64_t> cnt_i((size_t)n_folds, 0);
+    for (int k = 0; k < n_procs; ++k) {
+        if (!fold[k]) continue;
+        for (int64_t a = 0; a < n[k]; ++a) {
+            const int32_t f = fold[k][a];
+            if (f < -1 || f >= n_folds)
+                return ck_fail(name + "label " + std::to_string(f) + " of datum " + std::to_string(a) + " of process " + std::to_string(k) +
+                               " is outside [-1, n_folds = " + std::to_string(n_folds) + ")");
+            if (f < 0) continue;
+            ++out->size[(size_t)f];
+            if (k == i) ++cnt_i[(size_t)f];
+        }
+    }
+    for (int32_t f = 0; f < n_folds; ++f)
+        if (cnt_i[(size_t)f] == 0)
+            return ck_fail(name + "fold " + std::to_string(f) + " is empty: it holds no datum of process " + std::to_string(i) + " (and " +
+                           std::to_string(out->size[(size_t)f]) + " of the other process)");
+    // the predicted data in the caller's order, then the groups by a counting sort (stable: ascending inside a group)
+    if (fold[i]) {
+        out->n_groups = n_folds;
+        out->off.assign((size_t)n_folds + 1, 0);
+        for (int32_t f = 0; f < n_folds; ++f) out->off[(size_t)f + 1] = out->off[(size_t)f] + cnt_i[(size_t)f];
+        out->plist.reserve((size_t)out->off[(size_t)n_folds]);
+        for (int64_t a = 0; a < n_i; ++a)
+            if (fold[i][a] >= 0) {
+                out->plist.push_back((int32_t)a);
+                out->fp.push_back(fold[i][a]);
+            }
+        out->idx.resize(out->plist.size());
+        std::vector<long long> fill(out->off.begin(), out->off.end() - 1);
+        for (size_t t = 0; t < out->plist.size(); ++t) out->idx[(size_t)fill[(size_t)out->fp[t]]++] = (int32_t)t;
+    } else {
+        out->n_groups = n_i > 0 ? 1 : 0;
+        out->off = {0, (long long)n_i};
+        if (n_i == 0) out->off.resize(1);
+        out->plist.resize((size_t)n_i);
+        out->idx.resize((size_t)n_i);
+        for (int64_t a = 0; a < n_i; ++a) out->plist[(size_t)a] = out->idx[(size_t)a] = (int32_t)a;
+        out->fp.assign((size_t)n_i, -1);
+    }
+    const int64_t N = n[0] + (n_procs == 2 ? n[1] : 0);
+    out->gself.resize((size_t)N);
+    for (int k = 0; k < n_procs; ++k) {
+        const int64_t off = k == 0 ? 0 : n0p, soff = k == 0 ? 0 : n[0];
+        for (int64_t j = 0; j < n[k]; ++j) out->gself[(size_t)(soff + (perm[k] ? perm[k][j] : j))] = (int32_t)(off + j);
+    }
+    return 0;
+}
+
 // ---- ck_predict_local: size classes, slab offsets and batches (ck_host.h) -----------------------------------------------
 void ck_host_local_needs(const int* cnt, int64_t m, int lds_limit, int k_hi, int trend, CkLocalNeeds* out) {
     *out = CkLocalNeeds();

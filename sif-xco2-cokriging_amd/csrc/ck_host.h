@@ -352,6 +352,28 @@ struct CkFoldPlan {
 CK_HIDDEN int ck_host_fold_plan(int i, int n_procs, const int64_t n[2], int64_t n0p, const int64_t* perm0, const int64_t* perm1,
                                 const int32_t* fold0, const int32_t* fold1, int32_t n_folds, int fold_max, CkFoldPlan* out);
 
+// ---- cross-validation in the moving neighbourhood: who is predicted, under which label (ck_api.hip: ck_cv_local_folds) -----
+// Pure index work, no device.  fold_k / perm_k / the internal positions as in the fold plan above; either label array may be
+// null.  The predicted data are those of process i with a label >= 0, all n_i of them when fold_i is null (admitted only with
+// buffer_i, a buffer around the datum of its own process: no datum may predict itself), in the caller's order.
+//   plist    m: the caller's index within process i of every predicted datum, ascending
+//   fp       m: their labels (-1 throughout when fold_i is null)
+//   off/idx  the groups the scores are summed over: group g owns idx[off[g] .. off[g + 1]), positions in plist, ascending.
+//            One group per fold; with fold_i null a single group of everything (n_groups = 1, or 0 when n_i = 0)
+//   size     n_folds: the data of BOTH processes that carry the label
+//   gself    n[0] + n[1]: every datum's own internal position, stacked order (what scatters the labels on the device)
+struct CkLocalCvPlan {
+    std::vector<int32_t> plist, fp, idx, gself;
+    std::vector<long long> off;
+    std::vector<int64_t> size;
+    int64_t n_groups = 0;
+};
+// 0, or -1 with the error text set (name: the entry point the text starts with): n_folds < 0, fold_i null without buffer_i, a
+// label outside [-1, n_folds) (the message names the process, the datum and the value), a fold without a datum of process i
+CK_HIDDEN int ck_host_local_cv_plan(const char* name, int i, int n_procs, const int64_t n[2], int64_t n0p, const int64_t* perm0,
+                                    const int64_t* perm1, const int32_t* fold0, const int32_t* fold1, int32_t n_folds, bool buffer_i,
+                                    CkLocalCvPlan* out);
+
 // ---- conditional simulation in the moving neighbourhood: the levels of the recursion (ck_api.hip: ck_simulate_local) --------
 // Pure index work, no device.  Site t (the caller's index) sits at position pos[t] of the ordering (a permutation of 0 .. m - 1)
 // and conditions on ns[t] earlier sites, whose POSITIONS are nbr[t ld .. t ld + ns[t]).  level[t] = 1 + the largest level among

@@ -341,7 +341,11 @@ struct CkLocalProblem {
     const CkTable* tabs = nullptr;          // [3]
     const double* const* coefs = nullptr;   // [3]
     int use_tab = 0;
-    int metric = 0, i_pred = 0, cv = 0;     // cv: sites of process i_pred at distance 0 are no neighbours
+    int metric = 0, i_pred = 0;
+    // cv: the search has a lower cut -- a site of process q at d <= lo[q] is no neighbour (lo[q] = -1: none for that process).
+    // The reference's cross-validation flag is lo[i_pred] = 0: sites of process i_pred at distance 0 are no neighbours
+    int cv = 0;
+    double lo[2] = {-1.0, -1.0};
     double max_dist = 0.0;
     double c0var = 0.0;                     // the prior variance of process i_pred
     // the sites, internal order: sc = 3 x npad coordinates (exact-formula form), su = their chord vectors, z = the values,
@@ -361,6 +365,12 @@ struct CkLocalProblem {
     double cmax = 0.0;
     const double *rq = nullptr, *cp = nullptr;
     const int *rs = nullptr, *rp = nullptr;
+    // Withholding (ck_cv_local_folds), evaluated where the radius predicate is, so in front of the cap.  Fold: fs = one label
+    // per site (npad ints, internal order; -1 in padding and for data never withheld), fp = one label per point (mpad ints); a
+    // site is no candidate of a point when fs[site] >= 0 && fs[site] == fp[point] (both null: no condition, no label is
+    // loaded).  Buffer: the radius of process q is the lower cut lo[q] above (cv set).  listed: rs or fs is set.
+    const int *fs = nullptr, *fp = nullptr;
+    int listed = 0;
     // Block cokriging (ck_predict_local_blocks): the points are the blocks' search centres.  bo = r + 1 offsets into the member
     // rows, the members grouped by block in the caller's order; mc = 3 x bmpad member coordinates (exact-formula form), mu =
     // their chord vectors, bw = their weights; sbb = the r prior variances of the block means (in place of c0var).  All null
@@ -559,3 +569,18 @@ void ck_launch_local_sim_level(hipStream_t s, const CkLocalSimLevel& A, const in
 void ck_launch_local_sim_gather(hipStream_t s, const double* E, int64_t m, int64_t nd, const int* pos, double* Y, int64_t ldy);
 // X (nd x m, the caller's order) <- Y (positions x ldy)
 void ck_launch_local_sim_scatter(hipStream_t s, const double* Y, int64_t ldy, const int* pos, int64_t m, int64_t nd, double* X);
+
+// Leave-group-out cross-validation in the moving neighbourhood (ck_cv_local_folds).  ck_launch_cv_labels: fs (npad ints, all -1
+// at launch) <- the labels of both processes (fold0: n0, fold1: n1, the caller's order; either may be null) at every datum's own
+// internal position (gself: n0 + n1 ints, stacked order, all < npad).  ck_launch_cv_fold_scores: one workgroup per group g of
+// predicted data, idx[off[g] .. off[g + 1]) positions in the call's point list; z / pred / err / own (null: no noise) are indexed
+// by those positions; out: n_groups x CK_CV_NSCORE -- data scored, sum e, sum e^2, sum e^2 / v, sum log v.
+#define CK_CV_NSCORE 5
+struct CkCvScoreArgs {
+    const int* idx;
+    const long long* off;
+    const double *z, *pred, *err, *own;
+    double* out;
+};
+void ck_launch_cv_labels(hipStream_t s, int64_t n0, int64_t n1, const int* fold0, const int* fold1, const int* gself, int* fs);
+void ck_launch_cv_fold_scores(hipStream_t s, int64_t n_groups, CkCvScoreArgs A);

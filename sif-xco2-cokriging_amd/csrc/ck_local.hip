@@ -48,6 +48,9 @@
 //                       into the recursion's layout, the draws back into the caller's order
 // The Vecchia likelihood (ck_loglik_vecchia) runs the prediction kernels with the data as the points and one more predicate
 // in the search: only sites that come earlier in the caller's ordering (lp_later).
+// Cross-validation by folds and buffers (ck_cv_local_folds) runs them with the data as the points and two more: a site that
+// carries the point's fold label, or lies within the buffer radius of its process, takes no part (lp_same_fold, lp_in_reach);
+//   k_cv_labels         the labels of both processes into the internal site order;  k_cv_fold_scores: a fold's five sums
 #include "ck_internal.h"
 #include "ck_rng.h"
 #include "ck_select.h"
@@ -73,6 +76,7 @@ struct LpPoint {
     double q0, q1, q2;                 // chord vector
     LpReach Q;
     int rp;                            // position in the ordering (precedence), 0 without one
+    int fp;                            // fold label (withholding), -1 without one
     const double *s0, *s1, *s2;        // the sites' coordinate rows
     const double *u0, *u1, *u2;        // and chord-vector rows (table path)
 };
@@ -84,6 +88,7 @@ __device__ __forceinline__ LpPoint lp_point(const CkLocalProblem& P, long p, boo
     X.q0 = P.pu[p], X.q1 = P.pu[P.mpad + p], X.q2 = P.pu[2 * P.mpad + p];
     X.Q = (own_reach && P.rq) ? LpReach{P.rq[2 * p], P.rq[2 * p + 1], P.cp[p]} : LpReach{P.max_dist, P.max_dist, P.cmax};
     X.rp = P.rs ? P.rp[p] : 0;
+    X.fp = P.fs ? P.fp[p] : -1;
     X.s0 = P.sc, X.s1 = P.sc + P.L.npad, X.s2 = P.sc + 2 * P.L.npad;
     X.u0 = P.su, X.u1 = P.su + P.L.npad, X.u2 = P.su + 2 * P.L.npad;
     return X;
@@ -93,27 +98,42 @@ __device__ __forceinline__ LpPoint lp_point(const CkLocalProblem& P, long p, boo
 // Precedence (ck_loglik_vecchia): a site takes part only if it comes earlier in the ordering than the point.
 __device__ __forceinline__ bool lp_later(const CkLocalProblem& P, const LpPoint& X, long g) { return P.rs && !(P.rs[g] < X.rp); }
 
+// Withholding by fold (ck_cv_local_folds): a site that carries the point's own label takes no part.  A label is loaded only
+// where the call has labels.
+__device__ __forceinline__ bool lp_same_fold(const CkLocalProblem& P, const LpPoint& X, long g) {
+    if (!P.fs) return false;
+    const int f = P.fs[g];
+    return f >= 0 && f == X.fp;
+}
+// the conditions that read a per-site list, behind one uniform gate: a call without either pays one scalar branch
+__device__ __forceinline__ bool lp_listed_out(const CkLocalProblem& P, const LpPoint& X, long g) {
+    return P.listed && (lp_later(P, X, g) || lp_same_fold(P, X, g));
+}
+// The distance conditions: d <= lim, and where the call has a lower cut (P.cv: the reference's cross-validation flag, lo = 0 for
+// process i_pred -- the compare is d > 0.0 -- or the buffer radii of ck_cv_local_folds; -1 for a process without one) also d > lo.
+__device__ __forceinline__ bool lp_in_reach(const CkLocalProblem& P, int proc, double d, double lim) {
+    if (P.cv) return d > (proc ? P.lo[1] : P.lo[0]) && d <= lim;
+    return d <= lim;
+}
+
 // the radius predicate within max_dist (the candidates of the neighbour cap): *d is the device distance, *proc the site's process
 __device__ __forceinline__ bool lp_candidate(const CkLocalProblem& P, const LpPoint& X, long g, double* d, int* proc) {
     const CkLayout& L = P.L;
     if (!(g < L.n0 || (g >= L.n0p && g < L.nend))) return false;
-    if (lp_later(P, X, g)) return false;
+    if (lp_listed_out(P, X, g)) return false;
     *d = lp_dist(P.metric, X.p0, X.p1, X.p2, X.s0[g], X.s1[g], X.s2[g]);
     *proc = g >= L.n0p;
-    if (P.cv && *proc == P.i_pred) return *d > 0.0 && *d <= P.max_dist;
-    return *d <= P.max_dist;
+    return lp_in_reach(P, *proc, *d, P.max_dist);
 }
 
 // the same within the point's reach
 __device__ __forceinline__ bool lp_is_neighbour(const CkLocalProblem& P, const LpPoint& X, long g) {
     const CkLayout& L = P.L;
     if (!(g < L.n0 || (g >= L.n0p && g < L.nend))) return false;
-    if (lp_later(P, X, g)) return false;
+    if (lp_listed_out(P, X, g)) return false;
     const double d = lp_dist(P.metric, X.p0, X.p1, X.p2, X.s0[g], X.s1[g], X.s2[g]);
     const int proc = g >= L.n0p;
-    const double lim = proc ? X.Q.r1 : X.Q.r0;
-    if (P.cv && proc == P.i_pred) return d > 0.0 && d <= lim;
-    return d <= lim;
+    return lp_in_reach(P, proc, d, proc ? X.Q.r1 : X.Q.r0);
 }
 
 // Radius search with chunk culling: the sites are laid out along a Hilbert curve (ck_api.hip: site_order), so
@@ -1911,4 +1931,63 @@ void ck_launch_local_sim_scatter(hipStream_t s, const double* Y, int64_t ldy, co
     if (m <= 0 || nd <= 0) return;
     k_local_sim_scatter<<<dim3((unsigned)((m + 31) / 32), (unsigned)((nd + 31) / 32)), dim3(LP_TPB), 0, s>>>(Y, (long)ldy, pos, (long)m,
                                                                                                           (long)nd, X);
+}
+
+// ---------------------------------------------------------------------------------------
+// leave-group-out cross-validation in the moving neighbourhood (ck_cv_local_folds; include/cokrige.h has the rules)
+// ---------------------------------------------------------------------------------------
+// The search is lp_candidate / lp_is_neighbour's with the withholding conditions (lp_same_fold, lp_in_reach); the solves are the
+// prediction kernels'.  Two kernels of its own.  k_cv_labels: the labels of both processes from the caller's stacked order into
+// the internal site order (fs starts as -1 everywhere; gself: every datum's own internal position, ck_host_local_cv_plan).
+// k_cv_fold_scores: one workgroup per fold over the fold's predicted data (idx[off[f] .. off[f + 1]): positions in the call's
+// point list, ascending): thread t sums entries t, t + 256, .. in order, then the 256-wide tree of lp_dots over the five columns
+// n, sum e, sum e^2, sum e^2 / v, sum log v with e = z - pred, v = err^2 + own (the datum's own s d, null: none).  A datum whose
+// pred is not finite or whose v is not > 0 is skipped and not counted.  No atomics: repeated calls give the same bits.
+__global__ __launch_bounds__(LP_TPB) void k_cv_labels(long n0, long n1, const int* __restrict__ fold0, const int* __restrict__ fold1,
+                                                       const int* __restrict__ gself, int* __restrict__ fs) {
+    const long t = (long)blockIdx.x * LP_TPB + threadIdx.x;
+    if (t < n0) {
+        if (fold0) fs[gself[t]] = fold0[t];
+    } else if (t < n0 + n1) {
+        if (fold1) fs[gself[t]] = fold1[t - n0];
+    }
+}
+
+__global__ __launch_bounds__(LP_TPB) void k_cv_fold_scores(CkCvScoreArgs A) {
+    __shared__ double red[CK_CV_NSCORE][LP_TPB];
+    const int tid = threadIdx.x;
+    const long long b = A.off[blockIdx.x], e = A.off[blockIdx.x + 1];
+    double acc[CK_CV_NSCORE] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long long q = b + tid; q < e; q += LP_TPB) {
+        const int t = A.idx[q];
+        const double p = A.pred[t], sd = A.err[t];
+        const double v = sd * sd + (A.own ? A.own[t] : 0.0);
+        if (!isfinite(p) || !(v > 0.0)) continue;
+        const double r = A.z[t] - p;
+        acc[0] += 1.0;
+        acc[1] += r;
+        acc[2] += r * r;
+        acc[3] += r * r / v;
+        acc[4] += log(v);
+    }
+#pragma unroll
+    for (int c = 0; c < CK_CV_NSCORE; ++c) red[c][tid] = acc[c];
+    __syncthreads();
+    for (int s = LP_TPB / 2; s > 0; s >>= 1) {
+        if (tid < s)
+#pragma unroll
+            for (int c = 0; c < CK_CV_NSCORE; ++c) red[c][tid] += red[c][tid + s];
+        __syncthreads();
+    }
+    if (tid < CK_CV_NSCORE) A.out[(long)blockIdx.x * CK_CV_NSCORE + tid] = red[tid][0];
+}
+
+void ck_launch_cv_labels(hipStream_t s, int64_t n0, int64_t n1, const int* fold0, const int* fold1, const int* gself, int* fs) {
+    if (n0 + n1 <= 0 || (!fold0 && !fold1)) return;
+    k_cv_labels<<<dim3((unsigned)((n0 + n1 + LP_TPB - 1) / LP_TPB)), dim3(LP_TPB), 0, s>>>((long)n0, (long)n1, fold0, fold1, gself, fs);
+}
+
+void ck_launch_cv_fold_scores(hipStream_t s, int64_t n_groups, CkCvScoreArgs A) {
+    if (n_groups <= 0) return;
+    k_cv_fold_scores<<<dim3((unsigned)n_groups), dim3(LP_TPB), 0, s>>>(A);
 }

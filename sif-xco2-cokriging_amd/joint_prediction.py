@@ -716,12 +716,12 @@ def _is_missing(x):
         return False
 
 
-def fold_codes(folds, also_withhold, n_i, n_other, seed=0):
+def fold_codes(folds, also_withhold, n_i, n_other, seed=0, fold_max=CK_FOLD_MAX):
     """(codes_i, codes_other or None, labels): the fold labels of ``cross_validation(folds=...)`` as the int32 codes of
     ``ck_cv_folds``.  Labels are numbered in order of first appearance in ``folds``; None / NaN / -1 -> -1 (never withheld).
     An int K draws a random K-fold from ``seed``: a permutation of the data cut into K nearly equal parts.  Raises
     ValueError for wrong lengths, ``also_withhold`` labels that are no label of ``folds``, an empty fold set and folds of
-    more than CK_FOLD_MAX data.  Host only."""
+    more than ``fold_max`` data (CK_FOLD_MAX, the dense call's cap; None: no cap -- the local predictor has none).  Host only."""
     if folds is None:
         raise ValueError("also_withhold needs folds")
     if isinstance(folds, (int, np.integer)) and not isinstance(folds, bool):
@@ -767,9 +767,9 @@ def fold_codes(folds, also_withhold, n_i, n_other, seed=0):
     sizes = np.bincount(codes[codes >= 0], minlength=len(labels))
     if codes_o is not None:
         sizes = sizes + np.bincount(codes_o[codes_o >= 0], minlength=len(labels))
-    big = np.flatnonzero(sizes > CK_FOLD_MAX)
+    big = np.flatnonzero(sizes > fold_max) if fold_max is not None else []
     if len(big):
-        raise ValueError(f"fold {labels[big[0]]!r} withholds {int(sizes[big[0]])} data; the cap is CK_FOLD_MAX = {CK_FOLD_MAX} per fold")
+        raise ValueError(f"fold {labels[big[0]]!r} withholds {int(sizes[big[0]])} data; the cap is CK_FOLD_MAX = {fold_max} per fold")
     return codes, codes_o, labels
 
 

@@ -77,6 +77,10 @@ _PROTOS = {
     "ck_local_reserve": [c_void_p, c_int64],
     "ck_set_local_neighbours": [c_void_p, c_int64, c_int64],
     "ck_debug_local_neighbours": [c_void_p, c_int, _dp, c_int64, c_double, c_int, POINTER(c_int32), _dp],
+    "ck_cv_local_folds": [c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), c_int32, _dp, _dp, c_double, _dp, _dp, _dp, _dp, _dp,
+                          POINTER(c_int64)],
+    "ck_debug_local_cv_neighbours": [c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), c_int32, _dp, c_double, POINTER(c_int32),
+                                     _dp],
     "ck_loglik_vecchia": [c_void_p, POINTER(c_int64), c_double, _dp, _dp, _dp, POINTER(c_int32), POINTER(c_int64),
                           POINTER(c_int64)],
     "ck_loglik_vecchia_grad": [c_void_p, POINTER(c_int64), c_double, POINTER(c_int32), _dp, _dp, _dp, POINTER(c_int64),
@@ -777,6 +781,74 @@ class Handle:
         _chk(lib().ck_debug_local_neighbours(self._h, int(i), _p(pc), m, float(max_dist), int(bool(cv)),
                                              count.ctypes.data_as(POINTER(c_int32)), _p(rcut)))
         return count, rcut
+
+    def _cv_local_args(self, i, folds_i, folds_other, n_folds, buffer):
+        """(n_i, fold0, fold1, n_folds, buffer2, keepalive) of the two cross-validation calls of the local predictor"""
+        i = int(i)
+        n_i = int(self._n_data.get(i, 0))
+        ip = POINTER(c_int32)
+        fi = None if folds_i is None else np.ascontiguousarray(folds_i, dtype=np.int32).ravel()
+        fo = None if folds_other is None else np.ascontiguousarray(folds_other, dtype=np.int32).ravel()
+        if fi is not None and fi.size != n_i:
+            raise ValueError(f"folds_i has {fi.size} labels, process {i} has {n_i} data")
+        n_o = int(self._n_data.get(1 - i, 0))
+        if fo is not None and fo.size != n_o:
+            raise ValueError(f"folds_other has {fo.size} labels, process {1 - i} has {n_o} data")
+        if n_folds is None:
+            n_folds = int(max(-1 if fi is None else fi.max(initial=-1), -1 if fo is None else fo.max(initial=-1))) + 1
+        pi = None if fi is None else fi.ctypes.data_as(ip)
+        po = None if fo is None else fo.ctypes.data_as(ip)
+        f0, f1 = (pi, po) if i == 0 else (po, pi)
+        b2 = None
+        if buffer is not None:
+            b = [buffer, buffer] if np.isscalar(buffer) else list(buffer)
+            if len(b) != 2:
+                raise ValueError("buffer is a number or one entry per process (None = off)")
+            b2 = np.array([-1.0 if x is None else float(x) for x in b], dtype=np.float64)
+        return n_i, f0, f1, int(n_folds), b2, (fi, fo)
+
+    def cv_local_folds(self, i, folds_i=None, folds_other=None, n_folds=None, buffer=None, f0=None, max_dist=1e3, want_beta=False):
+        """Leave-group-out / buffer cross-validation of process ``i`` in the moving neighbourhood (include/cokrige.h:
+        ck_cv_local_folds).  ``folds_i`` / ``folds_other``: int labels in [-1, n_folds) of the data of process i / of the other
+        process, the caller's order (-1 = never withheld; None: no labels).  ``buffer``: None, a radius for both processes, or a pair
+        (an entry of None or < 0: off).  ``f0``: (n_i, p_i) regressors at the data of process i when a trend is set.
+        Returns (pred, pred_err, info): n_empty, n_not_pd, n_rank_def, k_max, fold_stats (n_folds, 6), score5 and, with
+        ``want_beta``, beta (n_i, p)."""
+        n_i, p0, p1, n_folds, b2, keep = self._cv_local_args(i, folds_i, folds_other, n_folds, buffer)
+        p = sum(self._trend_p.values())
+        pi = self._trend_p.get(int(i), 0)
+        F0 = None
+        if pi > 0:
+            F0 = _f64(np.zeros((n_i, 0)) if f0 is None else f0)
+            if F0.shape != (n_i, pi):
+                raise ValueError(f"f0 has shape {F0.shape}, expected {(n_i, pi)}")
+        pred, err = np.empty(n_i), np.empty(n_i)
+        beta = np.full((n_i, p), np.nan) if want_beta else None
+        stats, score = np.zeros((max(n_folds, 0), 6)), np.zeros(5)
+        cnt = np.zeros(4, dtype=np.int64)
+        _chk(lib().ck_cv_local_folds(self._h, int(i), p0, p1, n_folds, None if b2 is None else _p(b2), _p(F0) if F0 is not None else None,
+                                     float(max_dist), _p(pred), _p(err), _p(beta) if want_beta and p else None, _p(stats), _p(score),
+                                     cnt.ctypes.data_as(POINTER(c_int64))))
+        info = dict(n_empty=int(cnt[0]), n_not_pd=int(cnt[1]), n_rank_def=int(cnt[2]), k_max=int(cnt[3]), fold_stats=stats, score5=score)
+        if want_beta:
+            info["beta"] = beta
+        return pred, err, info
+
+    def local_cv_neighbours(self, i, folds_i=None, folds_other=None, n_folds=None, buffer=None, max_dist=1e3):
+        """(count, rcut), both (n_i, 2): the select pass of cv_local_folds alone (include/cokrige.h: ck_debug_local_cv_neighbours);
+        (0, NaN) rows for data that are never withheld."""
+        n_i, p0, p1, n_folds, b2, keep = self._cv_local_args(i, folds_i, folds_other, n_folds, buffer)
+        count, rcut = np.zeros((n_i, 2), dtype=np.int32), np.zeros((n_i, 2))
+        _chk(lib().ck_debug_local_cv_neighbours(self._h, int(i), p0, p1, n_folds, None if b2 is None else _p(b2), float(max_dist),
+                                                count.ctypes.data_as(POINTER(c_int32)), _p(rcut)))
+        return count, rcut
+
+    def cv_local_timings(self):
+        """ck_timings [118 ..] of the last cv_local_folds() call (milliseconds; the last two are counts)."""
+        out = np.zeros(124)
+        _chk(lib().ck_timings(self._h, _p(out), 124))
+        keys = ["pass_ms", "solve_ms", "scores_ms", "total_ms", "n_predicted", "n_folds"]
+        return dict(zip(keys, out[118:124].tolist()))
 
     def loglik_vecchia(self, rank, max_dist, terms=False):
         """Vecchia log-likelihood of the data under the model (include/cokrige.h: ck_loglik_vecchia): every datum conditioned on

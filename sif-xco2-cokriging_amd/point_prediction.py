@@ -29,7 +29,7 @@ import pandas as pd
 from . import native
 from .fields import metric_of
 from .joint_prediction import Predictor as _JointPredictor
-from .joint_prediction import prediction_coords, xr  # noqa: F401  (same helper, same signature)
+from .joint_prediction import fold_codes, prediction_coords, xr  # noqa: F401  (same helpers, same signatures)
 from .model import configure_handle
 from .noise import apply_noise, resolve_measurement_error
 from .trend import TrendDesign, check_trend
@@ -216,6 +216,7 @@ class Predictor:
 
     # -- areal means in the moving neighbourhood ---------------------------------------------------
     _spatial_trend = _JointPredictor._spatial_trend   # what _postprocess_blocks reads of the class it is borrowed from
+    _postprocess_predictions = _JointPredictor._postprocess_predictions   # and what _cv_frame does (cross_validation(folds=...))
 
     def _block_centres(self, pc, codes, labels, centres):
         """(r, 2) search centres in the order of ``labels``.  None: the unweighted mean position of every block's members --
@@ -438,9 +439,26 @@ class Predictor:
                                              postprocess)
 
     def cross_validation(self, i: int, max_dist: float = 1e3, partitions: int = None,
-                         postprocess: bool = True) -> pd.DataFrame:
+                         postprocess: bool = True, folds=None, also_withhold=None, buffer=None, seed: int = 0) -> pd.DataFrame:
         """Leave-one-out at every data location of process ``i`` (src/point_prediction.py:303-346):
-        one local prediction per location with the co-located datum withheld."""
+        one local prediction per location with the co-located datum withheld.
+
+        ``folds`` / ``also_withhold`` / ``buffer`` (not in the reference): leave-GROUP-out and buffer cross-validation, one
+        native call (include/cokrige.h: ck_cv_local_folds) under this predictor's ``max_neighbours``, ``trend`` and
+        ``measurement_error``.  ``folds`` and ``also_withhold`` are the joint method's: an array of n_i labels (any hashable
+        values; None / NaN / -1 = never withheld) or an int K (a random K-fold drawn from ``seed``), and n_other labels of the
+        same label set for the other process's data that leave together with a fold (the co-located partner, the same track).
+        A fold may be of any size.  ``buffer``: a radius in the units of ``max_dist`` (both processes) or a pair, an entry of None
+        turning that process off: the sites of that process within the radius of the predicted datum are withheld as well.
+        ``buffer`` alone predicts every datum and needs a radius for process ``i``.
+
+        The frame is the joint method's, with a ``fold`` column, without the rows of never-withheld data.  ``cv_folds_`` holds one
+        row per fold: label, n_withheld (both processes), n_scored, me, rmse, msdr (mean of e^2 / v) and nlpd_marginal =
+        1/2 (n log 2 pi + sum log v + sum e^2 / v) with v = pred_err^2 + the datum's own measurement-error variance -- the SUM OF
+        MARGINAL densities, not the joint density of the fold that the joint predictor reports as ``nlpd`` (different data have
+        different neighbourhoods, which define no joint law).  ``cv_scores_`` holds the same over all predicted data."""
+        if folds is not None or also_withhold is not None or buffer is not None:
+            return self._cv_local(i, max_dist, postprocess, folds, also_withhold, buffer, seed)
         self.cv = True
         names = ["lat", "lon"] if postprocess else ["d1", "d2"]
         f = self.mf.fields[i]
@@ -450,3 +468,79 @@ class Predictor:
         df = df.dropna(subset=["pred"]).merge(data, on=names, how="outer")
         df["residual"] = df["data"] - df["pred"]
         return df[names + ["data", "pred", "residual", "pred_err"]]
+
+    @staticmethod
+    def _cv_scores(n, se, se2, sr, sl):
+        """me, rmse, msdr, nlpd_marginal from the five sums of ck_cv_local_folds (NaN where nothing was scored)"""
+        n = np.asarray(n, dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return se / n, np.sqrt(se2 / n), sr / n, np.where(n > 0, 0.5 * (n * np.log(2.0 * np.pi) + sl + sr), np.nan)
+
+    def _cv_local(self, i, max_dist, postprocess, folds, also_withhold, buffer, seed):
+        """The ``folds=`` / ``buffer=`` form of ``cross_validation``: everything is validated on the host before any device work."""
+        if self.devices is not None and len(self.devices) > 1:
+            raise ValueError(f"cross_validation(folds=... / buffer=...) runs on a single device; this predictor has devices={self.devices}")
+        if isinstance(i, bool) or not (isinstance(i, (int, np.integer)) and 0 <= int(i) < self.n_procs):
+            raise ValueError(f"process index {i!r} out of range for {self.n_procs} processes")
+        if isinstance(max_dist, bool) or not np.isfinite(max_dist) or max_dist < 0:
+            raise ValueError(f"max_dist must be finite and >= 0, got {max_dist!r}")
+        b2 = None
+        if buffer is not None:
+            b = [buffer] * 2 if np.isscalar(buffer) else list(buffer)
+            if len(b) != max(self.n_procs, 1) and len(b) != 2:
+                raise ValueError(f"buffer is a number or one entry per process ({self.n_procs}), got {len(b)} entries")
+            b = (b + [None, None])[:2]
+            for x in b:
+                if x is not None and (isinstance(x, (bool, np.bool_)) or not np.isfinite(x) or x < 0):
+                    raise ValueError(f"a buffer radius must be None (off) or finite and >= 0, got {x!r}")
+            b2 = [None if x is None else float(x) for x in b]
+        f = self.mf.fields[i]
+        n_i = len(np.asarray(f.values_main))
+        n_o = len(np.asarray(self.mf.fields[1 - i].values_main)) if self.n_procs == 2 else None
+        if folds is None and also_withhold is None:
+            if b2 is None or b2[i] is None:
+                raise ValueError(f"buffer alone predicts every datum of process {i} and needs a radius for that process (0 withholds "
+                                 "the co-located data), or every datum would predict itself")
+            codes, codes_o, labels = None, None, []
+        else:
+            codes, codes_o, labels = fold_codes(folds, also_withhold, n_i, n_o, seed, fold_max=None)
+        names = ["lat", "lon"] if postprocess else ["d1", "d2"]
+        data = pd.DataFrame(np.hstack((f.coords_main, np.atleast_2d(f.values_main).T)), columns=names + ["data"])
+        h = self._capped_handle()
+        F0 = None
+        if self.trend is not None:
+            coords = [np.asarray(self.mf.fields[k].coords_main, dtype=np.float64)[:, :2] for k in range(self.n_procs)]
+            design = TrendDesign(self.trend, coords)
+            for k in range(self.n_procs):
+                h.set_trend(k, design.data(k, coords[k]))
+            F0 = design(i, coords[i])
+        pred, err, info = h.cv_local_folds(i, codes, codes_o, n_folds=len(labels), buffer=b2, f0=F0, max_dist=max_dist,
+                                           want_beta=self.trend is not None)
+        self.trend_coef = info.pop("beta", None)
+        self.timings = h.cv_local_timings()
+        stats, score = info.pop("fold_stats"), info.pop("score5")
+        info["n_capped"] = int(h.timings()["local_n_capped"]) if self.max_neighbours is not None else 0
+        self.info = info
+        if info["n_empty"]:
+            warnings.warn(f"No data within maximum distance {max_dist} at {info['n_empty']} location(s).")
+        if info["n_not_pd"]:
+            warnings.warn(f"Local covariance matrix not positive definte at {info['n_not_pd']} location(s);"
+                          " returning NaN.")
+        if info.get("n_rank_def"):
+            warnings.warn(f"Trend not estimable from the data within maximum distance {max_dist} at {info['n_rank_def']}"
+                          " location(s); returning NaN. Use a larger max_dist or a smaller trend.")
+        me, rmse, msdr, nlpd = self._cv_scores(stats[:, 1], stats[:, 2], stats[:, 3], stats[:, 4], stats[:, 5])
+        self.cv_folds_ = pd.DataFrame({"label": pd.Series(labels, dtype=object), "n_withheld": stats[:, 0].astype(int),
+                                       "n_scored": stats[:, 1].astype(int), "me": me, "rmse": rmse, "msdr": msdr, "nlpd_marginal": nlpd})
+        t = self._cv_scores(*score)
+        self.cv_scores_ = dict(n_scored=int(score[0]), me=float(t[0]), rmse=float(t[1]), msdr=float(t[2]), nlpd_marginal=float(t[3]))
+        if codes is None:
+            data["fold"] = pd.Series([None] * n_i, dtype=object)
+            return _JointPredictor._cv_frame(self, i, postprocess, data, names, pred, err, fold=True)
+        data["fold"] = pd.Series([labels[c] if c >= 0 else None for c in codes], dtype=object)
+        if postprocess:
+            out = _JointPredictor._cv_frame(self, i, True, data, names, pred, err, fold=True)
+            return out[out["fold"].notna()].reset_index(drop=True)
+        keep = codes >= 0
+        data = data[keep].reset_index(drop=True)
+        return _JointPredictor._cv_frame(self, i, False, data, names, pred[keep], err[keep], fold=True)
