@@ -1,7 +1,7 @@
 """Whole-globe inputs for the haversine paths: sites uniform on the sphere with the places that are awkward there (poles,
 the antimeridian written both ways, lon and lon + 360, exact antipodes), two clusters a third of the globe apart, and the
 chord-space arithmetic of the covariance tables in numpy.  Plain numpy plus the oracle; tests/test_global_sites_host.py pins
-what the GPU tests (tests/test_gpu_global_sites.py) lean on.
+what the GPU tests (tests/test_gpu_global_sites.py, tests/test_gpu_global_sites_newer.py) lean on.
 
 Half of all pairs of GLOBE are more than a quarter of the way round (10 007.5 km, squared chord q = 2): beyond the upper end of
 every haversine covariance table, where the table kernels hand the entry to the exact evaluator.  Every cross pair of CLUSTERS
@@ -75,6 +75,88 @@ def globe_pred_sites(rng, m):
     pc[5] = (d[0], d[1] - 360.0 if d[1] > 0 else d[1] + 360.0)
     pc[6] = (89.99, 10.0)
     return pc
+
+
+def around(centre, dist_km, bearing):
+    """sites [lat, lon] at the great-circle distance dist_km from centre = [lat, lon] under the initial bearing (radians from
+    north, clockwise), through the centre's own east / north frame, so that a pole is a centre like any other: its longitude
+    says where bearing 0 points.  The longitude is the centre's plus the offset in (-180, 180], NOT brought back into
+    [-180, 180]: the device has to be periodic in it."""
+    lat, lon = np.radians(float(centre[0])), float(centre[1])
+    dl, th = np.asarray(dist_km, dtype=np.float64) / orc.EARTH_RADIUS, np.asarray(bearing, dtype=np.float64)
+    x = np.cos(dl) * np.cos(lat) - np.sin(dl) * np.cos(th) * np.sin(lat)         # in the frame turned by the centre's longitude
+    y = np.sin(dl) * np.sin(th)
+    z = np.cos(dl) * np.sin(lat) + np.sin(dl) * np.cos(th) * np.cos(lat)
+    return np.column_stack([np.degrees(np.arctan2(z, np.hypot(x, y))), lon + np.degrees(np.arctan2(y, x))])
+
+
+BLOCK_SIZES = (64, 300, 3, 17, 17, 1, 64, 33)
+BLOCK_REACH_KM = (9000.0, 800.0, 800.0, 800.0, 800.0, 0.0, 800.0, 15000.0)
+BLOCK_CANCELLING = 4                                   # its weights sum to zero
+BLOCK_HEMISPHERES = (0, 7)                             # member pairs on opposite sides of the globe
+
+
+def globe_blocks(rng):
+    """(centres (8, 2), pc, lab, w): eight blocks centred on the first eight rows of globe_pred_sites -- both poles, either side
+    of the antimeridian, a datum of process 0, its lon -+ 360 copy, the site near the pole, one free -- with BLOCK_SIZES members
+    uniform in distance and bearing within BLOCK_REACH_KM of the centre (gs.around: longitudes unnormalised), the members of
+    all blocks interleaved.  The weights are positive and sum to 1, except those of block 4, which have their mean taken off: a
+    contrast, whose sigma_BB is small against the variance.  No two members of a block are closer than 1e-6 km, so the nugget
+    rule h == 0 between members does not rest on the last bit of anybody's distance (block 5 is its centre alone)."""
+    centres = globe_pred_sites(rng, 8)
+    pc, lab, w = [], [], []
+    for b, (q, reach) in enumerate(zip(BLOCK_SIZES, BLOCK_REACH_KM)):
+        x = around(centres[b], reach * rng.random(q), rng.uniform(0.0, 2.0 * np.pi, q)) if reach > 0 else np.repeat(centres[b][None], q, 0)
+        d = orc.haversine_km(x, x)
+        assert q == 1 or d[np.triu_indices(q, k=1)].min() > 1e-6, b
+        wb = rng.uniform(0.2, 2.0, q)
+        wb = wb / wb.sum()
+        if b == BLOCK_CANCELLING:
+            wb = wb - wb.mean()
+        pc.append(x)
+        lab.append(np.full(q, b))
+        w.append(wb)
+    pc, lab, w = np.vstack(pc), np.concatenate(lab), np.concatenate(w)
+    perm = rng.permutation(len(lab))
+    return centres, pc[perm], lab[perm], w[perm]
+
+
+def lon_folds(coords):
+    """six folds by longitude, floor(((lon + 210) mod 360) / 60): fold 0 is [150, 180] and [-180, -150), across the antimeridian"""
+    lon = np.asarray(coords, dtype=np.float64)[:, 1]
+    return np.floor(np.mod(lon + 210.0, 360.0) / 60.0).astype(np.int32)
+
+
+def sim_sites(rng, m, i):
+    """globe_pred_sites(rng, m) without the rows within 1e-6 km of a datum of process i: a simulation site on a noise-free datum
+    is singular by the rule of ck_simulate_local.  The sites either side of the antimeridian and (89.99, 10) stay."""
+    pc = globe_pred_sites(rng, m)
+    return pc[orc.haversine_km(pc, GLOBE["coords"][i]).min(axis=1) > 1e-6]
+
+
+# ---- the cases of tests/test_gpu_global_sites_newer.py, pinned without a GPU in tests/test_global_sites_host.py ------------------
+BLOCK_SEED = 300
+BLOCK_REACHES = (3000.0, 12000.0)                      # every neighbourhood in the LDS class | in the tiled class
+SIM_SITE_SEED, SIM_RANK_SEED, SIM_M = 101, 102, 64
+SIM_CASES = ((12000.0, (12, 12)), (3000.0, (0, 0)))    # (max_dist, caps)
+SIM_DATA_NOISE = 0.01                                  # on every datum, where sites sit on data
+# (max_dist, caps, buffer per process or None, lon_folds labels or none): the first five are the fold cases, the last two the
+# buffer-only calls that show what the buffer alone does to the special sites
+CV_CASES = ((3000.0, (0, 0), (500.0, 500.0), True), (12000.0, (40, 25), (500.0, None), True), (12000.0, (40, 25), (0.0, 0.0), True),
+            (3000.0, (0, 0), None, True), (12000.0, (0, 0), (500.0, 500.0), True),
+            (3000.0, (0, 0), (0.0, 0.0), False), (3000.0, (0, 0), (500.0, 500.0), False))
+CV_CULL_REACHES = (1500.0, 12000.0, 19500.0)
+CV_CULL_BUFFER = (300.0, 300.0)
+VECCHIA_RANK_SEED, VECCHIA_REACH, VECCHIA_CAPS = 3, 12000.0, (16, 16)
+
+
+def culling_sites():
+    """the 3 000 + 2 600 sites of test_radius_search_culling_on_the_globe: 12 + 11 chunks of 256"""
+    rng = np.random.default_rng(4)
+    coords = [sphere_sites(rng, 3000), sphere_sites(rng, 2600)]
+    coords[0][:len(SPECIAL_0)] = SPECIAL_0
+    coords[1][:len(SPECIAL_1)] = SPECIAL_1
+    return coords
 
 
 def vario_sites(n, seed):

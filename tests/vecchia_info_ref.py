@@ -82,12 +82,23 @@ def _build(label):
         return dict(coords=[c0, c1], values=[rng.standard_normal(150), rng.standard_normal(150)], params=parameter_set(name),
                     metric=HAV, max_dist=250.0, caps=(12, 12), noise_d=None, scales=(1.0, 1.0),
                     ranks=np.random.default_rng(13).permutation(300).astype(np.int64))
+    if kind in ("globe16", "globe16noise"):
+        # tests/global_sites.py: GLOBE under GLOBE_PARAMS[name], the sets of test_vecchia_on_the_globe -- half of the candidate
+        # pairs inside 12 000 km lie beyond the covariance tables' upper end (10 007.5 km)
+        from tests import global_sites as gs
+        g = gs.GLOBE
+        rng = np.random.default_rng(23)
+        noisy = kind == "globe16noise"
+        return dict(coords=g["coords"], values=g["values"], params=list(gs.GLOBE_PARAMS[name]), metric=HAV, max_dist=12000.0,
+                    caps=(16, 16), noise_d=[rng.uniform(0.01, 0.05, len(c)) for c in g["coords"]] if noisy else None,
+                    scales=SCALES if noisy else (1.0, 1.0),
+                    ranks=np.random.default_rng(3).permutation(gs.N0 + gs.N1).astype(np.int64))
     raise KeyError(label)
 
 
 FIXTURES = ([f"caps{c}/{n}" for n in ("SET_B_UNIT", "GEN") for c in (4, 16, 32)] +
             [f"full_{o}/{n}" for n in ("SET_B_UNIT", "GEN") for o in ("random", "hilbert")] +
-            ["noise16/GEN", "uni8/GEN", "hav12/SET_A"])
+            ["noise16/GEN", "uni8/GEN", "hav12/SET_A", "globe16/long", "globe16noise/long"])
 
 
 def fixture(label):
