@@ -111,7 +111,9 @@ int ck_assemble_joint(ck_handle* h);
 /* K3: in-place blocked Cholesky Sigma = L L^T (cho_factor(lower=True), src/joint_prediction.py:69).
  * info = 0, or the 1-based order of the leading minor that is not positive definite
  * (scipy raises LinAlgError with that number).  Single-process form; for world > 1 drive
- * ck_panel_factor / ck_panel_apply from the host with a broadcast in between. */
+ * ck_panel_factor / ck_panel_apply from the host with a broadcast in between.
+ * The rows below a 64 x 64 diagonal block are solved as a product with that block's explicit inverse, so the backward error of
+ * L grows with the condition number of the diagonal blocks: DESIGN.md section 4b, "Stability of the inverse-based row solves". */
 int ck_factor(ck_handle* h, int64_t* info);
 /* K2 + K4: prediction and standard error of process i at pcoords (m x 2):
  * c0 (Predictor._pred_cross_cov, :104-122), forward substitution V = L^-1 [c0 | z],
