@@ -780,6 +780,11 @@ int ck_debug_get_lower(ck_handle* h, double* out_host, int64_t n);
  * (process 0 sites, then process 1), whatever the internal site order; any n (parity tests at sizes where the dense
  * matrix does not fit a host array: sampled entries of the table-path assembly, sampled rows of the factor). */
 int ck_debug_get_entries(ck_handle* h, const int64_t* rows_host, const int64_t* cols_host, int64_t n, double* out_host);
+/* The per-entry Matern derivatives the likelihood gradient, the Fisher information and the Vecchia gradient are made of,
+ * evaluated on the device at given lags: out3_host[3 r ..] = (M, dM/dnu, dM/dlen) of block `block` (0: (1,1), 1: (1,2),
+ * 2: (2,2); one process: 0) at |lags_host[r]|, M the Matern CORRELATION (no amplitude, no nugget).  The shifted orders and the
+ * step of the nu difference are prepared by the code ck_loglik's gradient uses.  After ck_set_model; no data needed. */
+int ck_debug_matern_grad(ck_handle* h, int block, const double* lags_host, int64_t n, double* out3_host);
 /* perm_out[j] = caller's index (within process k) of the site at internal position j.  Identity
  * with option site_order = 0; a Hilbert-curve order with site_order = 1 (the default). */
 int ck_debug_site_order(ck_handle* h, int k, int64_t* perm_out, int64_t n_k);

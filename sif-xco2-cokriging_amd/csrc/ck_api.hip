@@ -5391,6 +5391,27 @@ extern "C" int ck_vario_end(ck_handle* h) {
 // ---------------------------------------------------------------------------------------
 // diagnostics
 // ---------------------------------------------------------------------------------------
+// ck_matern_grad per lag on the device, with the stencil blocks and the step lik_blocks hands the likelihood kernels
+extern "C" int ck_debug_matern_grad(ck_handle* h, int block, const double* lags, int64_t n, double* out3) {
+    CHKH(h);
+    if (!h->model_set) return fail("ck_set_model has not been called");
+    if (block < 0 || block >= (h->n_procs == 1 ? 1 : 3)) return fail("ck_debug_matern_grad: block index out of range");
+    if (n <= 0) return 0;
+    if (!lags || !out3) return fail("ck_debug_matern_grad: null array");
+    double dnu3[3] = {0.0, 0.0, 0.0};
+    if (lik_blocks(h, dnu3)) return -1;
+    DevTemps tmp;
+    double *dl = nullptr, *dO = nullptr;
+    HIPCHK(tmp.get(&dl, (size_t)(n * 8)));
+    HIPCHK(tmp.get(&dO, (size_t)(3 * n * 8)));
+    HIPCHK(hipMemcpyAsync(dl, lags, n * 8, hipMemcpyHostToDevice, h->stream));
+    ck_launch_debug_matern_grad(h->stream, h->d_lik_blk + 5 * block, dnu3[block], dl, n, dO);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out3, dO, 3 * n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 extern "C" int ck_debug_site_order(ck_handle* h, int k, int64_t* perm_out, int64_t n_k) {
     CHKH(h);
     if (k < 0 || k >= h->n_procs) return fail("process index out of range");

@@ -188,6 +188,8 @@ void ck_launch_lik_logdet(hipStream_t s, double* const* sigptr_dev, int nK, CkLa
 int64_t ck_lik_grad_groups(CkLayout L);
 void ck_launch_loglik_grad(hipStream_t s, double* const* G_dev, CkLayout L, int n_procs, int metric, const double* c,
                            const CkMatern* blk5, const double* dnu3, double sig1, double sig2, double rho, double* part);
+// out3[3 r ..] = (M, dM/dnu, dM/dlen) of ck_matern_grad at lag |lags[r]|; blk5: ONE block's five entries, dnu its step
+void ck_launch_debug_matern_grad(hipStream_t s, const CkMatern* blk5, double dnu, const double* lags, int64_t n, double* out3);
 
 // part[2 K + k] = sum of G_aa d_a over the sites a of process k in block column K (d: npad variances in the internal order);
 // dl/ds_k = 1/2 sum_K part[2 K + k] (ck_loglik_noise_grad)

@@ -154,6 +154,22 @@ void ck_launch_lik_noise_grad(hipStream_t s, double* const* G_dev, int nK, CkLay
 
 int64_t ck_lik_grad_groups(CkLayout L) { return (L.npad / CK_NB) * CK_LIK_STRIPS(L.npad); }
 
+// ck_debug_matern_grad: one thread per lag, ck_matern_grad on the stencil of one block exactly as k_loglik_grad calls it
+__global__ void k_debug_matern_grad(const CkMatern* __restrict__ blk5, double dnu, const double* __restrict__ lags, long n,
+                                    double* __restrict__ out3) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const CkMaternGrad gr = ck_matern_grad(blk5[0], blk5 + 1, dnu, fabs(lags[i]));
+    out3[3 * i] = gr.M;
+    out3[3 * i + 1] = gr.dnu;
+    out3[3 * i + 2] = gr.dlen;
+}
+
+void ck_launch_debug_matern_grad(hipStream_t s, const CkMatern* blk5, double dnu, const double* lags, int64_t n, double* out3) {
+    if (n <= 0) return;
+    k_debug_matern_grad<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(blk5, dnu, lags, n, out3);
+}
+
 void ck_launch_loglik_grad(hipStream_t s, double* const* G_dev, CkLayout L, int n_procs, int metric, const double* c,
                            const CkMatern* blk5, const double* dnu3, double sig1, double sig2, double rho, double* part) {
     const int64_t n = ck_lik_grad_groups(L);

@@ -105,6 +105,7 @@ _PROTOS = {
     "ck_vario_stats": [c_void_p, POINTER(c_int64), c_int],
     "ck_ref_distance": [c_int, _dp, _dp, c_int64, _dp],
     "ck_hilbert_order": [_dp, c_int64, POINTER(c_int64)],
+    "ck_debug_matern_grad": [c_void_p, c_int, _dp, c_int64, _dp],
     "ck_debug_get_lower": [c_void_p, _dp, c_int64],
     "ck_debug_site_order": [c_void_p, c_int, POINTER(c_int64), c_int64],
     "ck_debug_get_entries": [c_void_p, POINTER(c_int64), POINTER(c_int64), c_int64, _dp],
@@ -1043,6 +1044,14 @@ class Handle:
         return dict(zip(["extent_host_pairs", "bin_host_pairs", "bin_visited_pairs", "extent_extra_rounds"], out.tolist()))
 
     # -- diagnostics -----------------------------------------------------------------------------
+    def debug_matern_grad(self, block, h):
+        """(n, 3): (M, dM/dnu, dM/dlen) of the Matern correlation of block `block` at the lags h, as the likelihood kernels
+        evaluate them per entry (include/cokrige.h: ck_debug_matern_grad)."""
+        h = _f64(h).ravel()
+        out = np.empty((h.size, 3))
+        _chk(lib().ck_debug_matern_grad(self._h, int(block), _p(h), h.size, _p(out)))
+        return out
+
     def debug_get_lower(self, n):
         out = np.empty((n, n))
         _chk(lib().ck_debug_get_lower(self._h, _p(out), int(n)))
