@@ -492,6 +492,53 @@ int ck_conditional_draws(ck_handle* h, int i, const double* pcoords_host, int64_
                          const double* noise_host, double tol, double jitter, double* draws_host, double* pred_host,
                          double* pred_err_host, uint8_t* deflated_host, int64_t* info);
 
+/* Joint prediction of BOTH processes on the resident factor (needs ck_factor and a model of two processes; single-process
+ * form; simple cokriging -- no trend, no blocks).  pcoords0 (m0 x 2): the sites of process 0; pcoords1 (m1 x 2): those of
+ * process 1; either count may be 0.
+ *   pred0 / pred_err0 (m0 values) are what ck_predict(h, 0, pcoords0, m0, ..) gives, pred1 / pred_err1 (m1 values) what
+ *   ck_predict(h, 1, pcoords1, m1, ..) gives -- from ONE forward sweep over the stacked right-hand sides
+ *   [c0(sites of 0)^T; c0(sites of 1)^T; z^T] (a row's result does not depend on its neighbours).
+ *   pair_cov[t] (q values, or NULL: none wanted) = S[a_t, m0 + b_t] for the pairs (a_t, b_t) = pairs[2 t], pairs[2 t + 1]
+ *   (a: index into pcoords0, b: index into pcoords1), S = C_pp - c0^T Sigma^-1 c0 the posterior covariance of the stacked
+ *   sites, C_pp = [[C00, C01], [C01^T, C11]]: the auto blocks carry the nugget where h == 0 (as in ck_predict and
+ *   ck_verify_model), the cross block cross_covariance(0, 1, h) carries none, and ck_set_noise's variances enter through
+ *   Sigma only.  One value is C01(d(a, b)) - V_a . V_b: an exact covariance evaluation and the dot product of two solved
+ *   rows in a fixed order.
+ * Internal order of the stacked sites (it fixes the Cholesky order of ck_conditional_draws_pair): the sites of process 0 first,
+ * then those of process 1; each set along its own Hilbert curve (ck_hilbert_order of that set) when option "site_order" is on
+ * and the set has at least 256 sites, else in the caller's order.  (On the device the process-1 rows start at roundup(m0, 64);
+ * the rows between are zeros and take no part in anything.)
+ * Refused (through ck_last_error, the message starts with the call's name): no factor, a partitioned handle, a model of
+ * one process, a pair index out of range, a null argument that is needed.
+ * Afterwards the factor of Sigma stays resident and ck_predict gives its usual bits; the right-hand sides hold the stacked
+ * rows, so ck_verify_model and ck_aux_finish fail ("the last call was ck_predict_pair") until the next ck_predict /
+ * ck_aux_begin.  ck_timings [134 ..] describe the call (slots 0 .. 15 are left as they were). */
+int ck_predict_pair(ck_handle* h, const double* pcoords0_host, int64_t m0, const double* pcoords1_host, int64_t m1,
+                    double* pred0_host, double* pred_err0_host, double* pred1_host, double* pred_err1_host,
+                    const int64_t* pairs_host /* q x 2 */, int64_t q, double* pair_cov_host /* q, or NULL */);
+
+/* Co-simulation: ck_conditional_draws on the stacked sites of both processes (needs what ck_predict_pair needs).  The
+ * caller's STACKED index of a site is k for site k of pcoords0 and m0 + k for site k of pcoords1: draws (n_draws x (m0 + m1)
+ * row-major) holds process 0 in its columns [0, m0) and process 1 in [m0, m0 + m1); pred, pred_err, deflated (m0 + m1 each)
+ * and noise (n_draws x (m0 + m1), or NULL) are stacked the same way.
+ *   1. pred / pred_err are ck_predict_pair's, bit for bit (the call runs its stages).
+ *   2. S = C_pp - V^T V of the stacked sites (ck_predict_pair has the definition) in the Schur buffers.
+ *   3. Deflation and jitter as in ck_conditional_draws with EACH ROW'S OWN process: a site of process i is deflated when
+ *      S_kk <= tol (sigma_i^2 + nugget_i), every other diagonal entry gets jitter (sigma_i^2 + nugget_i).  A site of process 0 on
+ *      a datum of process 1 only keeps a positive variance and is not deflated.
+ *   4. The factor of S in the internal order given at ck_predict_pair.  info = 0, or 1 + the stacked index of the site at
+ *      whose pivot the factorisation stopped.  Two sites OF THE SAME PROCESS with identical coordinates that are not deflated
+ *      stop it at the later of them (internal order) without factoring; the two processes at one location are two random
+ *      variables -- S is positive definite there for |rho12| < 1 -- and stop nothing.
+ *   5. / 6. as ck_conditional_draws; the Philox counter is (stacked index, d / 2, 0, 0).
+ * Refused: as ck_predict_pair, and m0 + m1 outside 1 .. 65 536, n_draws < 1, tol or jitter negative or NaN, too little
+ * device memory (the message states the bytes).  Afterwards the handle is as after ck_predict_pair.
+ * ck_timings [124 .. 133] describe the call, laid out as ck_conditional_draws' [30 .. 39]. */
+int ck_conditional_draws_pair(ck_handle* h, const double* pcoords0_host, int64_t m0, const double* pcoords1_host, int64_t m1,
+                              int64_t n_draws, uint64_t seed, const double* noise_host, double tol, double jitter,
+                              double* draws_host, double* pred_host, double* pred_err_host, uint8_t* deflated_host,
+                              int64_t* info);
+
 /* ---- step-wise form (multi-GPU, fused solve) ------------------------------ */
 int ck_num_panels(ck_handle* h, int* n_panels, int* panel_width, int64_t* n_padded);
 int ck_panel_owner(ck_handle* h, int K, int* owner_rank);
@@ -899,7 +946,13 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * clock of the call; [115] sites solved (a non-empty set); [116] levels; [117] sum over the sites of their site-neighbours.
  * ck_cv_local_folds (n up to 124): [118] the counting or select pass of the predicted data; [119] the solves of every size
  * class; [120] the fold scores (k_cv_fold_scores); [121] host wall clock of the call; [122] data predicted; [123] folds.  [10],
- * [14] and [60 ..] are filled as by ck_predict_local. */
+ * [14] and [60 ..] are filled as by ck_predict_local.
+ * ck_conditional_draws_pair (n up to 134): [124] the joint point prediction (host wall clock of ck_predict_pair's stages);
+ * [125] the assembly of C_pp; [126] V^T V; [127] deflation and jitter; [128] the factor of S; [129] noise generation, summed
+ * over the chunks; [130] the draw product, summed; [131] host wall clock of the call; [132] number of deflated sites; [133]
+ * number of chunks.
+ * ck_predict_pair (n up to 138; also set by ck_conditional_draws_pair): [134] K2 assembly of the stacked right-hand sides;
+ * [135] the forward sweep; [136] the reductions (k_reduce_pred per process, k_pair_cov); [137] host wall clock of the call. */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it

@@ -34,7 +34,7 @@
 #include "ck_vecchia.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 124
+#define CK_N_TIMINGS 140
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -81,6 +81,7 @@ enum AuxState {
     AUX_LOGLIK,      // y, the trend rows (REML) and the unit rows of every internal position
     AUX_UNIVERSAL,   // ck_predict's rows with the trend rows behind the data row
     AUX_FOLDS,       // y and the unit rows of the withheld positions
+    AUX_PAIR,        // ck_predict_pair's stacked rows of both processes, row m0p + m1 = y
     AUX_N_STATES
 };
 // per state: the entry point that left it (null: none to name) and the clause ck_verify_model adds to the name
@@ -94,6 +95,7 @@ static const struct {
     {"ck_loglik", "whose right-hand sides are the data sites' unit rows"},
     {"ck_predict_universal", "for which the simple-kriging verdict does not apply"},
     {"ck_cv_folds", "whose right-hand sides are the withheld data's unit rows"},
+    {"ck_predict_pair", "whose right-hand sides are the stacked sites of both processes"},
 };
 
 struct ck_handle {
@@ -1896,12 +1898,13 @@ static int aux_storage(ck_handle* h, int i, int64_t m) {
     return 0;
 }
 
+static int aux_assemble_rows(ck_handle* h, const double* xy, int64_t pair_m0, double* k2_ms);
+
 // The assembly stage (K2): the right-hand sides [c0^T; z^T] of m prediction sites of process i, the trend rows X^T behind them
 // where aux_trend says so.  *k2_ms: the device milliseconds of the site transform, the table kernel and the exact pass.
 static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m, double* k2_ms) {
     if (aux_storage(h, i, m)) return -1;
     h->aux_state = AUX_ASSEMBLED;
-    const int64_t mpad = h->mpad;
     // large sets of prediction points are laid out along the Hilbert curve like the data sites
     // (site_order above); ck_aux_finish hands the results back in the caller's order
     std::vector<double> sorted;
@@ -1915,8 +1918,17 @@ static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m,
             sorted[2 * j] = pcoords[2 * h->pperm[(size_t)j]];
             sorted[2 * j + 1] = pcoords[2 * h->pperm[(size_t)j] + 1];
         }
-        pcoords = sorted.data();   // alive until the event synchronisation at the end of this function
+        pcoords = sorted.data();   // alive until the event synchronisation at the end of aux_assemble_rows
     }
+    return aux_assemble_rows(h, pcoords, -1, k2_ms);
+}
+
+// K2's device work on the h->m rows aux_storage laid out, xy (h->m x 2) their coordinates in the internal order.  pair_m0 < 0:
+// sites of process h->i_pred.  pair_m0 >= 0 (ck_predict_pair): the stacked rows of both processes (ck_host.h: CkPairPlan; xy has
+// zeros in the gap).
+static int aux_assemble_rows(ck_handle* h, const double* pcoords, int64_t pair_m0, double* k2_ms) {
+    const int i = h->i_pred;
+    const int64_t m = h->m, mpad = h->mpad;
     HIPCHK(hipMemsetAsync(h->d_pcoords, 0, 2 * mpad * 8, h->stream));
     if (m > 0) HIPCHK(hipMemcpyAsync(h->d_pcoords, pcoords, 2 * m * 8, hipMemcpyHostToDevice, h->stream));
     // timed like ck_assemble_joint: the device work of K2 (site transform, table kernel, exact pass) -- not the upload of the
@@ -1931,10 +1943,11 @@ static int aux_begin_impl(ck_handle* h, int i, const double* pcoords, int64_t m,
     auto assemble = [&](bool fast) {
         ck_launch_assemble_aux(h->stream, fast, h->d_blk, h->d_tabs, h->d_coefptr, h->metric, i, h->p0, h->pu, m, mpad, h->s0, h->su,
                                h->z, layout_of(h), h->nK, h->aux, h->wl, fast && fold ? h->d_pcoords : nullptr,
-                               fast ? h->assemble_queue : 0);
+                               fast ? h->assemble_queue : 0, pair_m0);
     };
     auto fix = [&] {
-        ck_launch_assemble_fix(h->stream, true, h->d_blk, h->metric, i, h->p0, mpad, h->s0, layout_of(h), h->wl, h->d_sigptr, h->aux);
+        ck_launch_assemble_fix(h->stream, true, h->d_blk, h->metric, i, h->p0, mpad, h->s0, layout_of(h), h->wl, h->d_sigptr, h->aux,
+                               pair_m0);
     };
     const int fast_done = table_or_exact(h, assemble, fix, h->ev1);
     if (fast_done < 0) return -1;
@@ -2187,17 +2200,20 @@ static int factor_sweep(ck_handle* h);
 // auto-covariance of process i_pred at the sites (nugget where h == 0), assembled in the packed panel format of Sigma, minus
 // V^T V over the solved right-hand-side rows (k_schur_syrk_d).  Consumes the data row m of the right-hand sides.  ms_cpp /
 // ms_vtv (may be null): device milliseconds of the assembly and of V^T V.
-static int schur_build(ck_handle* h, double* ms_cpp = nullptr, double* ms_vtv = nullptr) {
+// pair_m0 >= 0 (ck_conditional_draws_pair): the m rows are ck_predict_pair's stacked sites of both processes -- a two-process
+// site set with the layout {pair_m0, roundup(pair_m0, 64), m, Mp} and the model's own three blocks (cross block without nugget);
+// the gap rows come out as identity rows, and V^T V leaves them so (their right-hand-side rows are zeros).
+static int schur_build(ck_handle* h, double* ms_cpp = nullptr, double* ms_vtv = nullptr, int64_t pair_m0 = -1) {
     const int64_t m = h->m, mpad = h->mpad;
     const int64_t Mp = roundup(m, CK_NB);
     const int nJ = (int)(Mp / CK_NB);
     const bool timed = ms_cpp || ms_vtv;
-    // the prediction sites as a one-process site set: every tile uses the auto-block (i, i), replicated into all
+    // the prediction sites of ONE process as a site set: every tile uses the auto-block (i, i), replicated into all
     // three slots of the block / table arrays
-    const int bi = 2 * h->i_pred;
-    CkMatern hb[3] = {h->blk[bi], h->blk[bi], h->blk[bi]};
-    CkTable ht[3] = {h->tab[bi], h->tab[bi], h->tab[bi]};
-    double* hc[3] = {h->d_coef[bi], h->d_coef[bi], h->d_coef[bi]};
+    const int b0 = pair_m0 >= 0 ? 0 : 2 * h->i_pred, b1 = pair_m0 >= 0 ? 1 : b0, b2 = pair_m0 >= 0 ? 2 : b0;
+    CkMatern hb[3] = {h->blk[b0], h->blk[b1], h->blk[b2]};
+    CkTable ht[3] = {h->tab[b0], h->tab[b1], h->tab[b2]};
+    double* hc[3] = {h->d_coef[b0], h->d_coef[b1], h->d_coef[b2]};
     HIPCHK(hipMemcpyAsync(h->sch.d_blk, hb, sizeof(hb), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->sch.d_tabs, ht, sizeof(ht), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->sch.d_coefptr, hc, sizeof(hc), hipMemcpyHostToDevice, h->stream));
@@ -2206,7 +2222,7 @@ static int schur_build(ck_handle* h, double* ms_cpp = nullptr, double* ms_vtv = 
     if (timed) HIPCHK(hipEventRecord(h->ev0, h->stream));
     ck_launch_prep_sites(h->stream, h->sch.pc, Mp, h->metric, h->sch.c, h->sch.c + Mp, h->sch.c + 2 * Mp, h->sch.u);
     HIPCHK(hipStreamSynchronize(h->stream));   // hb / ht / hc are stack memory
-    const CkLayout L{m, Mp, Mp, Mp};
+    const CkLayout L = pair_m0 >= 0 ? CkLayout{pair_m0, roundup(pair_m0, 64), m, Mp} : CkLayout{m, Mp, Mp, Mp};
     auto assemble = [&](bool fast) {
         CkPanelMap pm{h->sch.d_tile0, h->sch.d_panel_of, h->sch.d_ptr, nJ, nullptr, 0, nullptr};
         ck_launch_assemble_sigma(h->stream, fast, h->sch.d_blk, h->sch.d_tabs, h->sch.d_coefptr, h->metric, h->sch.c, h->sch.u, L, pm,
@@ -2496,6 +2512,117 @@ extern "C" int ck_sample(ck_handle* h, const double* noise, double* out, int64_t
 // and column e_k, so that its draw is pred; every other diagonal entry gets jitter (sigma_i^2 + nugget_i).  The noise comes
 // from the caller or from the Philox stream of ck_rng.h keyed on (seed, caller's site index, draw index), and the product
 // E L_S^T runs on the matrix cores over the lower tiles, in chunks of option "draw_chunk" draws.
+// Stages 3 .. 6 on the S that schur_build left in the Schur buffers, for the sites of one process (pair == null: rows == m,
+// pc0 their coordinates, c0[0] their prior variance) or for ck_predict_pair's stacked sites (pair: the plan; m = m0 + m1 caller
+// columns, rows = pair->rows internal rows with the gap among them, c0[k] the prior variance of process k).  cmap: Mp ints, the
+// caller's column of every internal row, -1 where there is none.  tb: the call's first ck_timings slot (the ten slots are laid
+// out as ck_conditional_draws').  name: the entry point, for the message of a timed-out cooperative step.
+struct DrawSites {
+    const CkPairPlan* pair;
+    const double *pc0, *pc1;
+    int64_t m, rows;
+    const std::vector<int>& cmap;
+    double c0[2];
+};
+static int draw_stages(ck_handle* h, const char* name, int tb, const DrawSites& D, int64_t n_draws, uint64_t seed, const double* noise,
+                       double tol, double jitter, double* draws, uint8_t* deflated, int64_t* info,
+                       std::chrono::steady_clock::time_point t_begin) {
+    const int64_t m = D.m, rows = D.rows;
+    const int64_t Mp = roundup(rows, CK_NB);
+    const int nJ = (int)(Mp / CK_NB);
+    const std::vector<int>& cmap = D.cmap;
+    // ---- 3. deflation and jitter
+    DevTemps tmp;
+    unsigned char* d_mask = nullptr;
+    int* d_cmap = nullptr;
+    double *d_pred = nullptr, *d_ones = nullptr;
+    HIPCHK(tmp.get(&d_mask, (size_t)rows));
+    HIPCHK(tmp.get(&d_cmap, (size_t)Mp * sizeof(int)));
+    HIPCHK(tmp.get(&d_pred, (size_t)Mp * 8));
+    HIPCHK(tmp.get(&d_ones, 128 * 8));
+    const std::vector<double> ones(128, 1.0);
+    HIPCHK(hipMemcpyAsync(d_cmap, cmap.data(), (size_t)Mp * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_ones, ones.data(), 128 * 8, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(d_pred, 0, (size_t)Mp * 8, h->stream));
+    HIPCHK(hipMemcpyAsync(d_pred, h->d_pred, (size_t)rows * 8, hipMemcpyDeviceToDevice, h->stream));   // internal order
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    if (D.pair) {
+        const double thr[2] = {tol * D.c0[0], tol * D.c0[1]}, jit[2] = {jitter * D.c0[0], jitter * D.c0[1]};
+        ck_launch_draw_deflate_pair(h->stream, h->sch.d_ptr, D.pair->m0, D.pair->m0p, rows, thr, jit, d_mask);
+    } else {
+        ck_launch_draw_deflate(h->stream, h->sch.d_ptr, nJ, rows, tol * D.c0[0], jitter * D.c0[0], d_mask);
+    }
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned char> mask((size_t)rows);
+    HIPCHK(hipMemcpyAsync(mask.data(), d_mask, (size_t)rows, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));   // (cmap / ones are host memory)
+    int64_t n_defl = 0;
+    for (int64_t j = 0; j < rows; ++j) {
+        if (cmap[(size_t)j] < 0) continue;   // a gap row of the stacked layout: no site
+        deflated[cmap[(size_t)j]] = mask[(size_t)j];
+        n_defl += mask[(size_t)j] != 0;
+    }
+    if (n_defl > 0) ck_launch_draw_zero(h->stream, h->sch.d_ptr, nJ, rows, d_mask);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(hipEventSynchronize(h->ev1));
+    h->t_ms[tb + 3] = elapsed_ms(h->ev0, h->ev1);
+    h->t_ms[tb + 8] = (double)n_defl;
+    // ---- 4. the factor of S.  Two sites at the same coordinates have identical rows of S: singular unless deflated.  The
+    // exact factorisation stops at the later of them (internal order); report that without leaving it to rounding.  (Two
+    // PROCESSES at one location are two random variables: S is positive definite there for |rho| < 1.)
+    const int64_t stop = D.pair ? ck_host_pair_coincident(*D.pair, D.pc0, D.pc1, mask.data())
+                                : ck_host_coincident_site(D.pc0, cmap.data(), mask.data(), m);
+    if (stop >= 0) {
+        *info = 1 + cmap[(size_t)stop];
+        h->t_ms[tb + 7] = ms_since(t_begin);
+        return 0;
+    }
+    {
+        long long v = 0;
+        HIPCHK(hipEventRecord(h->ev2, h->stream));
+        if (schur_factor(h, &v, (std::string("call ") + name + " again").c_str())) return -1;
+        HIPCHK(hipEventRecord(h->ev3, h->stream));
+        HIPCHK(hipEventSynchronize(h->ev3));
+        h->t_ms[tb + 4] = elapsed_ms(h->ev2, h->ev3);
+        if (v != 0) {
+            *info = 1 + (v - 1 < rows && cmap[(size_t)(v - 1)] >= 0 ? cmap[(size_t)(v - 1)] : (int64_t)(v - 1));
+            h->t_ms[tb + 7] = ms_since(t_begin);
+            return 0;
+        }
+    }
+    ck_launch_draw_upper(h->stream, h->sch.d_ptr, nJ);
+    HIPCHK(hipGetLastError());
+    // ---- 5 / 6. noise and the draw product, chunk by chunk
+    size_t fr = 0, tot = 0;
+    if (h->draw_chunk <= 0) HIPCHK(hipMemGetInfo(&fr, &tot));
+    const int64_t chunk = ck_host_draw_chunk(h->draw_chunk, (int64_t)fr, Mp, m, noise != nullptr, n_draws);
+    const int64_t ldp = roundup(chunk, 128);
+    double *d_E = nullptr, *d_X = nullptr, *d_noise = nullptr;
+    HIPCHK(tmp.get(&d_E, (size_t)(ldp * Mp) * 8));
+    HIPCHK(tmp.get(&d_X, (size_t)(chunk * m) * 8));
+    if (noise) HIPCHK(tmp.get(&d_noise, (size_t)(chunk * m) * 8));
+    int n_chunks = 0;
+    for (int64_t d0 = 0; d0 < n_draws; d0 += chunk, ++n_chunks) {
+        const int64_t nd = std::min<int64_t>(chunk, n_draws - d0);
+        if (noise) HIPCHK(hipMemcpyAsync(d_noise, noise + d0 * m, (size_t)(nd * m) * 8, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipEventRecord(h->ev0, h->stream));
+        ck_launch_draw_noise(h->stream, d_E, ldp, Mp, nd, rows, d0, d_cmap, d_mask, d_noise, seed, m);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev1, h->stream));
+        ck_launch_draw_trmm(h->stream, d_X, m, d_E, ldp, nd, h->sch.d_ptr, d_pred, d_ones, d_cmap, rows);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(h->ev2, h->stream));
+        HIPCHK(hipMemcpyAsync(draws + d0 * m, d_X, (size_t)(nd * m) * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->t_ms[tb + 5] += elapsed_ms(h->ev0, h->ev1);
+        h->t_ms[tb + 6] += elapsed_ms(h->ev1, h->ev2);
+    }
+    h->t_ms[tb + 9] = n_chunks;
+    h->t_ms[tb + 7] = ms_since(t_begin);
+    return 0;
+}
+
 extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, int64_t m, int64_t n_draws, uint64_t seed,
                                     const double* noise, double tol, double jitter, double* draws, double* pred,
                                     double* pred_err, uint8_t* deflated, int64_t* info) {
@@ -2513,7 +2640,6 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
     if (!(tol >= 0.0) || !(jitter >= 0.0)) return fail("ck_conditional_draws: tol and jitter must be >= 0");
     const auto t_begin = std::chrono::steady_clock::now();
     const int64_t Mp = roundup(m, CK_NB);
-    const int nJ = (int)(Mp / CK_NB);
     // device memory: the Schur buffers, the right-hand sides of the point prediction, one chunk of 128 draws
     {
         const int64_t s_bytes = h->sch.M == Mp ? 0 : schur_bytes(Mp);
@@ -2536,90 +2662,152 @@ extern "C" int ck_conditional_draws(ck_handle* h, int i, const double* pcoords, 
     // ---- 2. S = C_pp - V^T V in the Schur buffers
     if (schur_ensure(h, Mp)) return -1;
     if (schur_build(h, &h->t_ms[31], &h->t_ms[32])) return -1;
-    // ---- 3. deflation and jitter
-    const double c0 = h->blk[2 * i].amp + h->blk[2 * i].nugget;   // sigma_i^2 + nugget_i
-    DevTemps tmp;
-    unsigned char* d_mask = nullptr;
-    int* d_cmap = nullptr;
-    double *d_pred = nullptr, *d_ones = nullptr;
-    HIPCHK(tmp.get(&d_mask, (size_t)m));
-    HIPCHK(tmp.get(&d_cmap, (size_t)Mp * sizeof(int)));
-    HIPCHK(tmp.get(&d_pred, (size_t)Mp * 8));
-    HIPCHK(tmp.get(&d_ones, 128 * 8));
+    // ---- 3 .. 6. deflation, the factor of S, noise and the draw product
     std::vector<int> cmap((size_t)Mp, -1);
     for (int64_t j = 0; j < m; ++j) cmap[(size_t)j] = (int)(h->p_sorted ? h->pperm[(size_t)j] : j);
-    const std::vector<double> ones(128, 1.0);
-    HIPCHK(hipMemcpyAsync(d_cmap, cmap.data(), (size_t)Mp * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(d_ones, ones.data(), 128 * 8, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(d_pred, 0, (size_t)Mp * 8, h->stream));
-    HIPCHK(hipMemcpyAsync(d_pred, h->d_pred, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream));   // internal order
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    ck_launch_draw_deflate(h->stream, h->sch.d_ptr, nJ, m, tol * c0, jitter * c0, d_mask);
-    HIPCHK(hipGetLastError());
-    std::vector<unsigned char> mask((size_t)m);
-    HIPCHK(hipMemcpyAsync(mask.data(), d_mask, (size_t)m, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));   // (cmap / ones are host memory)
-    int64_t n_defl = 0;
-    for (int64_t j = 0; j < m; ++j) {
-        deflated[cmap[(size_t)j]] = mask[(size_t)j];
-        n_defl += mask[(size_t)j] != 0;
-    }
-    if (n_defl > 0) ck_launch_draw_zero(h->stream, h->sch.d_ptr, nJ, m, d_mask);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    HIPCHK(hipEventSynchronize(h->ev1));
-    h->t_ms[33] = elapsed_ms(h->ev0, h->ev1);
-    h->t_ms[38] = (double)n_defl;
-    // ---- 4. the factor of S.  Two sites at the same coordinates have identical rows of S: singular unless deflated.  The
-    // exact factorisation stops at the later of them (internal order); report that without leaving it to rounding.
-    if (const int64_t stop = ck_host_coincident_site(pcoords, cmap.data(), mask.data(), m); stop >= 0) {
-        *info = 1 + cmap[(size_t)stop];
-        h->t_ms[37] = ms_since(t_begin);
-        return 0;
-    }
-    {
-        long long v = 0;
-        HIPCHK(hipEventRecord(h->ev2, h->stream));
-        if (schur_factor(h, &v, "call ck_conditional_draws again")) return -1;
-        HIPCHK(hipEventRecord(h->ev3, h->stream));
-        HIPCHK(hipEventSynchronize(h->ev3));
-        h->t_ms[34] = elapsed_ms(h->ev2, h->ev3);
-        if (v != 0) {
-            *info = 1 + (v - 1 < m ? cmap[(size_t)(v - 1)] : (int64_t)(v - 1));
-            h->t_ms[37] = ms_since(t_begin);
-            return 0;
-        }
-    }
-    ck_launch_draw_upper(h->stream, h->sch.d_ptr, nJ);
-    HIPCHK(hipGetLastError());
-    // ---- 5 / 6. noise and the draw product, chunk by chunk
-    size_t fr = 0, tot = 0;
-    if (h->draw_chunk <= 0) HIPCHK(hipMemGetInfo(&fr, &tot));
-    const int64_t chunk = ck_host_draw_chunk(h->draw_chunk, (int64_t)fr, Mp, m, noise != nullptr, n_draws);
-    const int64_t ldp = roundup(chunk, 128);
-    double *d_E = nullptr, *d_X = nullptr, *d_noise = nullptr;
-    HIPCHK(tmp.get(&d_E, (size_t)(ldp * Mp) * 8));
-    HIPCHK(tmp.get(&d_X, (size_t)(chunk * m) * 8));
-    if (noise) HIPCHK(tmp.get(&d_noise, (size_t)(chunk * m) * 8));
-    int n_chunks = 0;
-    for (int64_t d0 = 0; d0 < n_draws; d0 += chunk, ++n_chunks) {
-        const int64_t nd = std::min<int64_t>(chunk, n_draws - d0);
-        if (noise) HIPCHK(hipMemcpyAsync(d_noise, noise + d0 * m, (size_t)(nd * m) * 8, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipEventRecord(h->ev0, h->stream));
-        ck_launch_draw_noise(h->stream, d_E, ldp, Mp, nd, m, d0, d_cmap, d_mask, d_noise, seed);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(h->ev1, h->stream));
-        ck_launch_draw_trmm(h->stream, d_X, m, d_E, ldp, nd, h->sch.d_ptr, d_pred, d_ones, d_cmap);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(h->ev2, h->stream));
-        HIPCHK(hipMemcpyAsync(draws + d0 * m, d_X, (size_t)(nd * m) * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->t_ms[35] += elapsed_ms(h->ev0, h->ev1);
-        h->t_ms[36] += elapsed_ms(h->ev1, h->ev2);
-    }
-    h->t_ms[39] = n_chunks;
-    h->t_ms[37] = ms_since(t_begin);
+    const double c0 = h->blk[2 * i].amp + h->blk[2 * i].nugget;   // sigma_i^2 + nugget_i
+    const DrawSites D{nullptr, pcoords, nullptr, m, m, cmap, {c0, c0}};
+    return draw_stages(h, "ck_conditional_draws", 30, D, n_draws, seed, noise, tol, jitter, draws, deflated, info, t_begin);
+}
+
+// ---------------------------------------------------------------------------------------
+// joint prediction and co-simulation of both processes (ck_predict_pair, ck_conditional_draws_pair)
+// ---------------------------------------------------------------------------------------
+// The sites of both processes ride ONE forward sweep as the stacked right-hand sides [c0(sites of 0)^T; 0; c0(sites of 1)^T; z^T]
+// (ck_host.h: CkPairPlan -- the layout of Sigma's own sites, so that a 64-row assembly tile has one process).  A row's result
+// does not depend on its neighbours: pred / pred_err are ck_predict's.  The posterior covariance of the stacked sites is S =
+// C_pp - V^T V with C_pp = [[C00, C01], [C01^T, C11]]: one entry of its cross block per requested pair (k_pair_cov), all of it
+// through schur_build for the draws.
+static int pair_admit(const ck_handle* h, const std::string& name, bool null_argument) {
+    if (null_argument) return fail(name + ": null argument");
+    if (h->world != 1)
+        return fail(name + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) + ")");
+    if (!h->model_set || h->n_procs != 2)
+        return fail(name + ": needs a model of two processes (n_procs = " + std::to_string(h->n_procs) + ")");
+    if (!h->factored) return fail(name + ": ck_factor has not been called");
     return 0;
+}
+
+// K2, the sweep and the reductions of the stacked sites; P: the plan (out).  pred0 / err0: m0 values, pred1 / err1: m1 values, the
+// caller's order.  Writes ck_timings [134 .. 137].
+static int predict_pair_impl(ck_handle* h, const std::string& name, const double* pc0, int64_t m0, const double* pc1, int64_t m1,
+                             double* pred0, double* err0, double* pred1, double* err1, const int64_t* pairs, int64_t q,
+                             double* pair_cov, CkPairPlan* P) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    for (int64_t t = 0; t < q; ++t)
+        if (pairs[2 * t] < 0 || pairs[2 * t] >= m0 || pairs[2 * t + 1] < 0 || pairs[2 * t + 1] >= m1)
+            return fail(name + ": pair " + std::to_string(t) + " = (" + std::to_string(pairs[2 * t]) + ", " +
+                        std::to_string(pairs[2 * t + 1]) + ") is out of range (m0 = " + std::to_string(m0) + ", m1 = " +
+                        std::to_string(m1) + ")");
+    ck_host_pair_plan(pc0, m0, pc1, m1, h->site_order != 0, P);
+    std::vector<int2> prow((size_t)q);
+    for (int64_t t = 0; t < q; ++t)
+        prow[(size_t)t] = make_int2((int)P->row_of[(size_t)pairs[2 * t]], (int)P->row_of[(size_t)(m0 + pairs[2 * t + 1])]);
+    CallGuard guard(h, AUX_PAIR, false);
+    const int64_t rows = P->rows;
+    if (aux_storage(h, 0, rows)) return -1;
+    std::fill(h->t_ms + 134, h->t_ms + 138, 0.0);
+    if (aux_assemble_rows(h, P->xy.data(), m0, &h->t_ms[134])) return -1;
+    if (timed_solve_sweep(h)) return -1;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_pred, 0, (size_t)pair_bytes(h->mpad), h->stream));   // (the gap rows have no reduction)
+    for (int k = 0; k < 2; ++k) {   // each process's rows with its own prior variance sigma_k^2 + nugget_k
+        const int64_t r0 = k == 0 ? 0 : P->m0p;
+        ck_launch_reduce_pred(h->stream, h->aux + r0 * CK_NB, h->mpad, h->nK, k == 0 ? m0 : m1, rows - r0,
+                              h->blk[2 * k].amp + h->blk[2 * k].nugget, h->d_pred + r0, h->d_err + r0);
+    }
+    HIPCHK(hipGetLastError());
+    DevTemps tmp;
+    std::vector<double> tp((size_t)rows), te((size_t)rows);
+    if (q > 0) {
+        int2* d_rows = nullptr;
+        double* d_cov = nullptr;
+        HIPCHK(tmp.get(&d_rows, (size_t)q * sizeof(int2)));
+        HIPCHK(tmp.get(&d_cov, (size_t)q * 8));
+        HIPCHK(hipMemcpyAsync(d_rows, prow.data(), (size_t)q * sizeof(int2), hipMemcpyHostToDevice, h->stream));
+        ck_launch_pair_cov(h->stream, h->aux, h->mpad, h->nK, d_rows, q, h->d_blk, h->metric, h->p0, d_cov);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(pair_cov, d_cov, (size_t)q * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    if (rows > 0) {
+        HIPCHK(hipMemcpyAsync(tp.data(), h->d_pred, (size_t)rows * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(te.data(), h->d_err, (size_t)rows * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int64_t j = 0; j < rows; ++j) {   // back to the caller's order
+        const int c = P->cmap[(size_t)j];
+        if (c < 0) continue;
+        (c < m0 ? pred0[c] : pred1[c - m0]) = tp[(size_t)j];
+        (c < m0 ? err0[c] : err1[c - m0]) = te[(size_t)j];
+    }
+    HIPCHK(elapsed_ms(h->ev2, h->ev3, &h->t_ms[135]));
+    HIPCHK(elapsed_ms(h->ev0, h->ev1, &h->t_ms[136]));
+    h->t_ms[137] = ms_since(t_begin);
+    return 0;
+}
+
+extern "C" int ck_predict_pair(ck_handle* h, const double* pcoords0, int64_t m0, const double* pcoords1, int64_t m1, double* pred0,
+                               double* pred_err0, double* pred1, double* pred_err1, const int64_t* pairs, int64_t q,
+                               double* pair_cov) {
+    CHKH(h);
+    if (m0 < 0 || m1 < 0 || q < 0) return fail("ck_predict_pair: m0, m1 and q must be >= 0");
+    if (pair_admit(h, "ck_predict_pair",
+                   (m0 > 0 && (!pcoords0 || !pred0 || !pred_err0)) || (m1 > 0 && (!pcoords1 || !pred1 || !pred_err1)) ||
+                       (q > 0 && pair_cov && !pairs)))
+        return -1;
+    CkPairPlan P;
+    return predict_pair_impl(h, "ck_predict_pair", pcoords0, m0, pcoords1, m1, pred0, pred_err0, pred1, pred_err1, pairs,
+                             pair_cov ? q : 0, pair_cov, &P);
+}
+
+extern "C" int ck_conditional_draws_pair(ck_handle* h, const double* pcoords0, int64_t m0, const double* pcoords1, int64_t m1,
+                                         int64_t n_draws, uint64_t seed, const double* noise, double tol, double jitter,
+                                         double* draws, double* pred, double* pred_err, uint8_t* deflated, int64_t* info) {
+    CHKH(h);
+    const std::string name = "ck_conditional_draws_pair";
+    if (m0 < 0 || m1 < 0) return fail(name + ": m0 and m1 must be >= 0");
+    if (pair_admit(h, name, (m0 > 0 && !pcoords0) || (m1 > 0 && !pcoords1) || !draws || !pred || !pred_err || !deflated || !info))
+        return -1;
+    const int64_t m = m0 + m1;
+    if (m < 1 || m > 65536)
+        return fail(name + ": m0 + m1 = " + std::to_string(m) + " prediction sites; the posterior covariance is limited to "
+                    "1 .. 65 536 sites");
+    if (n_draws < 1) return fail(name + ": n_draws must be >= 1");
+    if (!(tol >= 0.0) || !(jitter >= 0.0)) return fail(name + ": tol and jitter must be >= 0");
+    const auto t_begin = std::chrono::steady_clock::now();
+    const int64_t rows = roundup(m0, 64) + m1;
+    const int64_t Mp = roundup(rows, CK_NB);
+    // device memory: the Schur buffers, the right-hand sides of the point prediction, one chunk of 128 draws
+    {
+        const int64_t s_bytes = h->sch.M == Mp ? 0 : schur_bytes(Mp);
+        const int64_t c_bytes = 128 * (Mp + (noise ? 2 : 1) * m) * 8 + rows * 13 + Mp * 12 + 1024;
+        CkMemAdmit a;
+        if (mem_admit(h, {rhs_bytes(roundup(rows + 1, CK_AUX_ALIGN), h->Npad), Mp, 0, c_bytes}, &a)) return -1;
+        if (a.need > a.avail)
+            return fail(name + ": needs " + std::to_string(a.need) + " bytes of device memory (" + std::to_string(s_bytes) +
+                        " for the posterior covariance of " + std::to_string(m0) + " + " + std::to_string(m1) + " sites, " +
+                        std::to_string(c_bytes) + " for a chunk of 128 draws); " + std::to_string(a.avail) + " bytes are available");
+    }
+    timings_from(h, 124);
+    *info = 0;
+    // ---- 1. the joint point prediction (ck_predict_pair's stages, the same bits)
+    CkPairPlan P;
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (predict_pair_impl(h, name, pcoords0, m0, pcoords1, m1, pred, pred_err, pred + m0, pred_err + m0, nullptr, 0, nullptr, &P))
+            return -1;
+        h->t_ms[124] = ms_since(t0);
+    }
+    // ---- 2. S = C_pp - V^T V of the stacked sites in the Schur buffers
+    if (schur_ensure(h, Mp)) return -1;
+    if (schur_build(h, &h->t_ms[125], &h->t_ms[126], m0)) return -1;
+    // ---- 3 .. 6. deflation by each row's own process, the factor of S, noise and the draw product
+    std::vector<int> cmap((size_t)Mp, -1);
+    std::copy(P.cmap.begin(), P.cmap.end(), cmap.begin());
+    const DrawSites D{&P, pcoords0, pcoords1, m, rows, cmap,
+                      {h->blk[0].amp + h->blk[0].nugget, h->blk[2].amp + h->blk[2].nugget}};
+    return draw_stages(h, name.c_str(), 124, D, n_draws, seed, noise, tol, jitter, draws, deflated, info, t_begin);
 }
 
 // ---------------------------------------------------------------------------------------

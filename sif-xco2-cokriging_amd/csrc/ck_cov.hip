@@ -127,7 +127,9 @@ __device__ __noinline__ void worklist_append(const CkWorklist& wl, unsigned mask
 // like any other row (their coordinates are zero padding, finite) and replaced in front of the store, so that
 // this tile runs the same code as the interior ones instead of the entry-by-entry edge path (which made these
 // 79 tiles the tail of the launch).
-template <bool ZROWS>
+// ZROWS == 2 (right-hand sides of two processes, the row tile that ends the process-0 rows): the rows with 16 a >= zrel are
+// the gap up to the process boundary -- all of them zeros, no data row among them.
+template <int ZROWS>
 __device__ __forceinline__ unsigned assemble_subtile_interior(const double* lcoef, int tbase, unsigned tn,
                                                               const double (&ru0)[4], const double (&ru1)[4],
                                                               const double (&ru2)[4], const CkSiteRef& S, long ct,
@@ -178,11 +180,12 @@ __device__ __forceinline__ unsigned assemble_subtile_interior(const double* lcoe
                 d2_t v;
                 v[0] = p[2 * h2];
                 v[1] = p[2 * h2 + 1];
-                if (ZROWS && 16 * (2 * ap + h2) >= zrel) {
+                if (ZROWS == 1 && 16 * (2 * ap + h2) >= zrel) {
                     const d2_t zv = *reinterpret_cast<const d2_t*>(z + c);
                     const d2_t zero = {0.0, 0.0};
                     v = (16 * (2 * ap + h2) == zrel) ? zv : zero;
                 }
+                if (ZROWS == 2 && 16 * (2 * ap + h2) >= zrel) v = d2_t{0.0, 0.0};
                 // non-temporal: 6.4 GB of panels stream out and are next read by the factorisation, long after they
                 // have left every cache (measured -3 % on the kernel against plain stores)
                 __builtin_nontemporal_store(v, reinterpret_cast<d2_t*>(obase + (ty + 16 * (2 * ap + h2)) * CK_NB + 2 * tx + 32 * b));
@@ -194,8 +197,9 @@ __device__ __forceinline__ unsigned assemble_subtile_interior(const double* lcoe
 
 // Sub-tiles that touch padding rows or columns (identity / z row / zeros), and every sub-tile of
 // the exact path: entry by entry, loops kept rolled so that this rarely-run code stays small in
-// registers.  AUX: rows are prediction sites (row m = data values z, rows > m zero).
-template <bool FAST, bool AUX>
+// registers.  AUX: rows are prediction sites (row m = data values z, rows > m zero).  PAIR: the prediction sites of process 0 in
+// [0, m0), those of process 1 in [roundup(m0, 64), m), zeros between them.
+template <bool FAST, bool AUX, bool PAIR = false>
 __device__ __forceinline__ unsigned assemble_subtile_edge(const CkMatern& mb, int metric, const double* lcoef,
                                                           int tbase, unsigned tn, const CkSiteRef& R,
                                                           const CkSiteRef& S, const double* __restrict__ z,
@@ -203,14 +207,15 @@ __device__ __forceinline__ unsigned assemble_subtile_edge(const CkMatern& mb, in
                                                           double* __restrict__ obase, int ty, int tx,
                                                           const double* rowu = nullptr /* LDS: chord vectors of the strip's
                                                           64 rows when the launch transforms them itself (R.u* is then being
-                                                          WRITTEN by the strips of block column 0 of the same launch) */) {
+                                                          WRITTEN by the strips of block column 0 of the same launch) */,
+                                                          long m0 = 0) {
     unsigned slowmask = 0;
 #pragma unroll 1
     for (int ba = 0; ba < 8; ++ba) {
         const int b = ba >> 2, a = ba & 3;
         const long r = rt + ty + 16 * a;
         const long c = ct + 2 * tx + 32 * b;
-        const bool rv = AUX ? (r < m) : site_valid(L, r);
+        const bool rv = PAIR ? (r < m0 || (r >= ((m0 + 63) & ~63L) && r < m)) : AUX ? (r < m) : site_valid(L, r);
         d2_t v;
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
@@ -252,7 +257,10 @@ __device__ __forceinline__ bool range_has_padding(const CkLayout& L, long g0) { 
 
 // FAST: table path (every block's table enabled) | exact per-entry Bessel evaluation.
 // AUX:  rows are prediction sites (row m = data values z, rows > m zero) | rows are data sites.
-template <bool FAST, bool AUX>
+// PAIR (with AUX): the rows belong to both processes, laid out like Sigma's own sites -- process 0 in [0, m0), zeros up to m0p =
+// roundup(m0, 64), process 1 in [m0p, m), the data row m behind them -- so that a 64-row tile still has ONE process and the strip
+// keeps one table in LDS.  i_pred then carries m0.  The other instantiations compile to what they were without the flag.
+template <bool FAST, bool AUX, bool PAIR = false>
 __global__ __launch_bounds__(256, FAST ? 3 : 1) void k_assemble(const CkMatern* __restrict__ blk,
                                                                  const CkTable* __restrict__ tabs,
                                                                  const double* const* __restrict__ coefs, int metric,
@@ -312,9 +320,11 @@ __global__ __launch_bounds__(256, FAST ? 3 : 1) void k_assemble(const CkMatern* 
         out = pm.sigptr[K];
     }
     const long rt = row0 + tile * 64;
-    const int pr = AUX ? i_pred : (int)(rt >= L.n0p);
+    const long m0 = PAIR ? (long)i_pred : 0, m0p = (m0 + 63) & ~63L;
+    const int pr = PAIR ? (int)(rt >= m0p) : AUX ? i_pred : (int)(rt >= L.n0p);
     const bool row_pad = AUX ? (rt + 64 > m) : range_has_padding(L, rt);
-    const int zrel = AUX ? (int)(m - rt) - ty : 0;   // this thread's row a is r = m + (16 a - zrel)
+    const bool row_gap = PAIR && rt < m0 && rt + 64 > m0;   // the tile that ends process 0: its rows from m0 on are zeros
+    const int zrel = AUX ? (int)((row_gap ? m0 : m) - rt) - ty : 0;   // this thread's row a is r = m + (16 a - zrel)
     double ru0[4], ru1[4], ru2[4];   // table path: chord vectors of this thread's four rows
     if (FAST && AUX && raw) {
         // The prediction sites arrive untransformed (round 4): one wave transforms the strip's 64 rows -- the arithmetic of
@@ -372,12 +382,14 @@ __global__ __launch_bounds__(256, FAST ? 3 : 1) void k_assemble(const CkMatern* 
         // right-hand sides: the row tile that holds row m runs the interior code with its rows >= m replaced in front of the
         // store (ZROWS; thread row a is row m + (16 a - zrel))
         if (!FAST || (row_pad && !AUX) || range_has_padding(L, ct))
-            slowmask = assemble_subtile_edge<FAST, AUX>(mb, metric, lcoef, tbase, tn, R, S, z, L, rt, ct, m, nug, obase, ty, tx,
-                                                        (FAST && AUX && raw) ? srow : nullptr);
+            slowmask = assemble_subtile_edge<FAST, AUX, PAIR>(mb, metric, lcoef, tbase, tn, R, S, z, L, rt, ct, m, nug, obase, ty, tx,
+                                                              (FAST && AUX && raw) ? srow : nullptr, m0);
+        else if (PAIR && row_gap)
+            slowmask = assemble_subtile_interior<2>(lcoef, tbase, tn, ru0, ru1, ru2, S, ct, obase, ty, tx, zrel);
         else if (AUX && row_pad)
-            slowmask = assemble_subtile_interior<true>(lcoef, tbase, tn, ru0, ru1, ru2, S, ct, obase, ty, tx, zrel, z);
+            slowmask = assemble_subtile_interior<1>(lcoef, tbase, tn, ru0, ru1, ru2, S, ct, obase, ty, tx, zrel, z);
         else
-            slowmask = assemble_subtile_interior<false>(lcoef, tbase, tn, ru0, ru1, ru2, S, ct, obase, ty, tx);
+            slowmask = assemble_subtile_interior<0>(lcoef, tbase, tn, ru0, ru1, ru2, S, ct, obase, ty, tx);
         if (FAST && __builtin_amdgcn_ballot_w64(slowmask != 0u) != 0ULL)   // rare: hand the pairs to the exact pass
             worklist_append(wl, slowmask, (int)(rt + ty), 16, (int)(ct + 2 * tx));
     }
@@ -389,7 +401,8 @@ __global__ __launch_bounds__(256, FAST ? 3 : 1) void k_assemble(const CkMatern* 
 
 // Exact evaluation of the worklist entries (see assemble_subtile).  Sigma: entry (r, c) lives in panel
 // K = c / NB at sigptr[K] + (r - K NB) NB + (c - K NB); right-hand sides: aux + K mpad NB + r NB + ...
-template <bool AUX>
+// PAIR: as k_assemble's (i_pred carries m0)
+template <bool AUX, bool PAIR = false>
 __global__ __launch_bounds__(256) void k_assemble_fix(const CkMatern* __restrict__ blk, int metric, int i_pred,
                                                        CkSiteRef R, CkSiteRef S, CkLayout L, CkWorklist wl,
                                                        double* const* __restrict__ sigptr, double* __restrict__ aux,
@@ -403,7 +416,7 @@ __global__ __launch_bounds__(256) void k_assemble_fix(const CkMatern* __restrict
         const int2 it = wl.items[e];
         const long r = it.x, c = it.y;
         const int pc = c >= L.n0p;
-        const int pr = AUX ? i_pred : (int)(r >= L.n0p);
+        const int pr = PAIR ? (int)(r >= (((long)i_pred + 63) & ~63L)) : AUX ? i_pred : (int)(r >= L.n0p);
         const double val = ck_cov_entry(blk[pr + pc], pair_dist(metric, R.c0[r], R.c1[r], R.c2[r], S.c0[c], S.c1[c], S.c2[c]),
                                         pr == pc);
         const long K = c / CK_NB;
@@ -442,8 +455,10 @@ void ck_launch_assemble_sigma(hipStream_t s, bool fast, const CkMatern* blk, con
 void ck_launch_assemble_aux(hipStream_t s, bool fast, const CkMatern* blk, const CkTable* tabs,
                             const double* const* coefs, int metric, int i_pred, double* pc, double* pu,
                             int64_t m, int64_t mpad, const double* c, const double* u, const double* z, CkLayout L,
-                            int n_panels, double* aux, CkWorklist wl, const double* raw, int queue_slots) {
+                            int n_panels, double* aux, CkWorklist wl, const double* raw, int queue_slots, int64_t pair_m0) {
     if (mpad <= 0 || n_panels <= 0) return;
+    const bool pair = pair_m0 >= 0;
+    if (pair) i_pred = (int)pair_m0;   // k_assemble<.., PAIR>: the process of a row tile comes from the split
     const int64_t np = L.npad;
     CkSiteRef P{pc, pc + mpad, pc + 2 * mpad, pu, pu + mpad, pu + 2 * mpad};
     CkSiteRef S{c, c + np, c + 2 * np, u, u + np, u + 2 * np};
@@ -458,10 +473,19 @@ void ck_launch_assemble_aux(hipStream_t s, bool fast, const CkMatern* blk, const
         const long strips = (long)n_panels * (mpad / 64);
         const int csubs = strips >= 16 * queue_slots ? 8 : (strips >= 4 * queue_slots ? 4 : 2);
         const long chunks = strips * (8 / csubs);
-        k_assemble<true, true><<<dim3((unsigned)std::min<long>(chunks, queue_slots)), dim3(256), 0, s>>>(
-            blk, tabs, coefs, metric, i_pred, P, m, S, z, L, pm, wl, raw, (long)mpad, pc, pu, wl.count + 1, (int)strips, csubs);
-    } else if (fast)
+        const dim3 qgrid((unsigned)std::min<long>(chunks, queue_slots));
+        if (pair)
+            k_assemble<true, true, true><<<qgrid, dim3(256), 0, s>>>(blk, tabs, coefs, metric, i_pred, P, m, S, z, L, pm, wl, raw,
+                                                                     (long)mpad, pc, pu, wl.count + 1, (int)strips, csubs);
+        else
+            k_assemble<true, true><<<qgrid, dim3(256), 0, s>>>(blk, tabs, coefs, metric, i_pred, P, m, S, z, L, pm, wl, raw,
+                                                               (long)mpad, pc, pu, wl.count + 1, (int)strips, csubs);
+    } else if (fast && pair)
+        k_assemble<true, true, true><<<grid, dim3(256), 0, s>>>(blk, tabs, coefs, metric, i_pred, P, m, S, z, L, pm, wl, raw, (long)mpad, pc, pu);
+    else if (fast)
         k_assemble<true, true><<<grid, dim3(256), 0, s>>>(blk, tabs, coefs, metric, i_pred, P, m, S, z, L, pm, wl, raw, (long)mpad, pc, pu);
+    else if (pair)
+        k_assemble<false, true, true><<<grid, dim3(256), 0, s>>>(blk, tabs, coefs, metric, i_pred, P, m, S, z, L, pm, wl);
     else
         k_assemble<false, true><<<grid, dim3(256), 0, s>>>(blk, tabs, coefs, metric, i_pred, P, m, S, z, L, pm, wl);
 }
@@ -469,15 +493,56 @@ void ck_launch_assemble_aux(hipStream_t s, bool fast, const CkMatern* blk, const
 // after all table-path panels of one assembly: evaluate what they deferred
 void ck_launch_assemble_fix(hipStream_t s, bool aux_rows, const CkMatern* blk, int metric, int i_pred,
                             const double* pc, int64_t mpad, const double* c, CkLayout L, CkWorklist wl,
-                            double* const* sigptr, double* aux) {
+                            double* const* sigptr, double* aux, int64_t pair_m0) {
     const int64_t np = L.npad;
     CkSiteRef S{c, c + np, c + 2 * np, nullptr, nullptr, nullptr};
     if (aux_rows) {
         CkSiteRef P{pc, pc + mpad, pc + 2 * mpad, nullptr, nullptr, nullptr};
-        k_assemble_fix<true><<<dim3(256), dim3(256), 0, s>>>(blk, metric, i_pred, P, S, L, wl, sigptr, aux, mpad);
+        if (pair_m0 >= 0)
+            k_assemble_fix<true, true><<<dim3(256), dim3(256), 0, s>>>(blk, metric, (int)pair_m0, P, S, L, wl, sigptr, aux, mpad);
+        else
+            k_assemble_fix<true><<<dim3(256), dim3(256), 0, s>>>(blk, metric, i_pred, P, S, L, wl, sigptr, aux, mpad);
     } else {
         k_assemble_fix<false><<<dim3(256), dim3(256), 0, s>>>(blk, metric, i_pred, S, S, L, wl, sigptr, aux, mpad);
     }
+}
+
+// Posterior cross-covariances of pairs of prediction sites (ck_predict_pair): out[t] = C_01(d(a_t, b_t)) - V_a . V_b, the rows
+// rows[t] = (a, b) of the solved right-hand sides (a: a process-0 site, b: a process-1 site of the stacked layout).  One wave
+// per pair; the two rows are dotted over the panels in k_reduce_pred's order (panel by panel, 128 columns a step, the lanes'
+// sums folded by the same butterfly), so a pair's value does not depend on q or on the other pairs.  The prior term comes from
+// the exact evaluator of the cross block (no nugget); pc: the sites' exact-formula coordinates, 3 x mpad.
+__global__ __launch_bounds__(256) void k_pair_cov(const double* __restrict__ aux, long mpad, int n_panels,
+                                                   const int2* __restrict__ rows, long q, const CkMatern* __restrict__ blk,
+                                                   int metric, const double* __restrict__ pc, double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= q) return;
+    const long ra = rows[t].x, rb = rows[t].y;
+    double s = 0.0;
+    for (int K = 0; K < n_panels; ++K) {
+        const double* pb = aux + (long)K * mpad * CK_NB;
+        const double* xa = pb + ra * CK_NB;
+        const double* xb = pb + rb * CK_NB;
+#pragma unroll
+        for (int c = 0; c < CK_NB; c += 128) {
+            const d2_t a = *reinterpret_cast<const d2_t*>(xa + c + lane * 2);
+            const d2_t b = *reinterpret_cast<const d2_t*>(xb + c + lane * 2);
+            s += a[0] * b[0] + a[1] * b[1];
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) {
+        const double d = pair_dist(metric, pc[ra], pc[mpad + ra], pc[2 * mpad + ra], pc[rb], pc[mpad + rb], pc[2 * mpad + rb]);
+        out[t] = ck_cov_entry(blk[1], d, 0) - s;
+    }
+}
+
+void ck_launch_pair_cov(hipStream_t s, const double* aux, int64_t mpad, int n_panels, const int2* rows, int64_t q,
+                        const CkMatern* blk, int metric, const double* pc, double* out) {
+    if (q <= 0) return;
+    k_pair_cov<<<dim3((unsigned)((q + 3) / 4)), dim3(256), 0, s>>>(aux, (long)mpad, n_panels, rows, (long)q, blk, metric, pc, out);
 }
 
 // Measurement-error variances (ck_set_noise), behind the table pass and k_assemble_fix: Sigma_gg += nz[g] for every data site

@@ -935,6 +935,45 @@ int64_t ck_host_coincident_site(const double* pcoords, const int* cmap, const un
     return stop;
 }
 
+void ck_host_pair_plan(const double* pc0, int64_t m0, const double* pc1, int64_t m1, bool site_order, CkPairPlan* out) {
+    *out = CkPairPlan();
+    out->m0 = m0;
+    out->m1 = m1;
+    out->m0p = (m0 + 63) / 64 * 64;
+    out->rows = out->m0p + m1;
+    out->cmap.assign((size_t)out->rows, -1);
+    out->row_of.assign((size_t)(m0 + m1), 0);
+    out->xy.assign((size_t)(2 * out->rows), 0.0);
+    const double* pc[2] = {pc0, pc1};
+    const int64_t mk[2] = {m0, m1}, row0[2] = {0, out->m0p}, stacked0[2] = {0, m0};
+    std::vector<int64_t> perm;
+    for (int k = 0; k < 2; ++k) {
+        out->sorted[k] = site_order && mk[k] >= CK_HOST_PAIR_SORT_MIN;
+        if (out->sorted[k]) {
+            double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
+            ck_host_bounding_box(pc[k], mk[k], lo, hi);
+            ck_host_hilbert_order(pc[k], mk[k], lo, hi, perm);
+        }
+        for (int64_t j = 0; j < mk[k]; ++j) {
+            const int64_t c = out->sorted[k] ? perm[(size_t)j] : j, r = row0[k] + j;
+            out->cmap[(size_t)r] = (int)(stacked0[k] + c);
+            out->row_of[(size_t)(stacked0[k] + c)] = r;
+            out->xy[(size_t)(2 * r)] = pc[k][2 * c];
+            out->xy[(size_t)(2 * r + 1)] = pc[k][2 * c + 1];
+        }
+    }
+}
+
+int64_t ck_host_pair_coincident(const CkPairPlan& P, const double* pc0, const double* pc1, const unsigned char* mask) {
+    // the rows of a process as ck_host_coincident_site wants them: the caller's index within the process per internal position
+    const int64_t s0 = ck_host_coincident_site(pc0, P.cmap.data(), mask, P.m0);
+    if (s0 >= 0) return s0;
+    std::vector<int> own((size_t)P.m1);
+    for (int64_t j = 0; j < P.m1; ++j) own[(size_t)j] = P.cmap[(size_t)(P.m0p + j)] - (int)P.m0;
+    const int64_t s1 = ck_host_coincident_site(pc1, own.data(), mask + P.m0p, P.m1);
+    return s1 >= 0 ? P.m0p + s1 : -1;
+}
+
 void ck_host_universal_finish(const double* W, const double* beta, const double* Ainv, const double* f0, const int64_t* pperm,
                               double c0, int64_t m, int p, int pi, int offi, double* pred, double* pred_err) {
     ck_host_parallel(m, [&](int, int64_t a, int64_t e) {

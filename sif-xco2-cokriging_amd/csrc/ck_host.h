@@ -258,6 +258,29 @@ CK_HIDDEN int64_t ck_host_draw_chunk(int64_t option, int64_t free_bytes, int64_t
 // j is deflated and cannot stop anything.  Returns the smallest internal position that coincides with an earlier one, or -1.
 CK_HIDDEN int64_t ck_host_coincident_site(const double* pcoords, const int* cmap, const unsigned char* mask, int64_t m);
 
+// ---- joint prediction of both processes: the stacked layout (ck_api.hip: ck_predict_pair, ck_conditional_draws_pair) --------
+// Pure index work, no device.  The m0 sites of process 0 (pc0: m0 x 2) and the m1 sites of process 1 (pc1: m1 x 2) as ONE set of
+// right-hand-side rows laid out like Sigma's own sites: process 0 in the rows [0, m0), zero rows up to m0p = roundup(m0, 64),
+// process 1 in [m0p, rows), rows = m0p + m1 (the data row's index).  Inside its range each set lies along its own Hilbert curve
+// (ck_hilbert_order of that set) when site_order is on and the set has at least CK_HOST_PAIR_SORT_MIN sites, else in the
+// caller's order.  The caller's STACKED index of a site: k for site k of process 0, m0 + k for site k of process 1.
+//   cmap     rows ints: the stacked index of the site in internal row j, -1 in the gap
+//   row_of   m0 + m1: the internal row of every stacked index
+//   xy       rows x 2: the coordinates in the internal order, zeros in the gap
+#define CK_HOST_PAIR_SORT_MIN 256
+struct CkPairPlan {
+    int64_t m0 = 0, m1 = 0, m0p = 0, rows = 0;
+    bool sorted[2] = {false, false};
+    std::vector<int> cmap;
+    std::vector<int64_t> row_of;
+    std::vector<double> xy;
+};
+CK_HIDDEN void ck_host_pair_plan(const double* pc0, int64_t m0, const double* pc1, int64_t m1, bool site_order, CkPairPlan* out);
+// ck_host_coincident_site inside each process (two processes at one location are two random variables: no stop).  mask: rows
+// bytes, != 0 where the row is deflated (the gap rows among them).  Returns the smallest internal row that coincides with an
+// earlier row of its own process, or -1.
+CK_HIDDEN int64_t ck_host_pair_coincident(const CkPairPlan& P, const double* pc0, const double* pc1, const unsigned char* mask);
+
 // ck_predict_universal's epilogue over the reduced rows W (internal order, p + 2 doubles each: |V_s|^2, V_s . y, U^T V_s):
 //   r_s = x0_s - U^T V_s,  pred_s = V_s . y + r_s^T beta,  pred_err_s^2 = c0 - |V_s|^2 + r_s^T A^-1 r_s
 // with x0_s = f0[c pi .. c pi + pi) in the columns offi .. offi + pi of the predicted process and zero elsewhere (pi may be 0);

@@ -66,11 +66,17 @@ void ck_launch_assemble_sigma(hipStream_t s, bool fast, const CkMatern* blk, con
 void ck_launch_assemble_aux(hipStream_t s, bool fast, const CkMatern* blk, const CkTable* tabs,
                             const double* const* coefs, int metric, int i_pred, double* pc, double* pu,
                             int64_t m, int64_t mpad, const double* c, const double* u, const double* z, CkLayout L,
-                            int n_panels, double* aux, CkWorklist wl, const double* raw = nullptr, int queue_slots = 0);
+                            int n_panels, double* aux, CkWorklist wl, const double* raw = nullptr, int queue_slots = 0,
+                            int64_t pair_m0 = -1 /* >= 0: rows of BOTH processes (ck_predict_pair) -- process 0 in [0, pair_m0), zeros up
+                            to roundup(pair_m0, 64), process 1 from there to m; i_pred is not used */);
 // evaluate the deferred entries of the preceding table-path launches (no-op when the list is empty)
 void ck_launch_assemble_fix(hipStream_t s, bool aux_rows, const CkMatern* blk, int metric, int i_pred,
                             const double* pc, int64_t mpad, const double* c, CkLayout L, CkWorklist wl,
-                            double* const* sigptr, double* aux);
+                            double* const* sigptr, double* aux, int64_t pair_m0 = -1 /* as ck_launch_assemble_aux */);
+// out[t] = C_01(d(a, b)) - V_a . V_b for the q row pairs rows[t] = (a, b) of the solved right-hand sides: the posterior
+// covariance between a process-0 and a process-1 prediction site (ck_predict_pair); pc: 3 x mpad exact-formula coordinates
+void ck_launch_pair_cov(hipStream_t s, const double* aux, int64_t mpad, int n_panels, const int2* rows, int64_t q,
+                        const CkMatern* blk, int metric, const double* pc, double* out);
 // measurement-error variances (ck_set_noise): Sigma_gg += nz[g] at every data site g (nz: npad values in the internal order,
 // zero where there is none); behind ck_launch_assemble_fix, once per assembled Sigma.  nz == null: no launch.
 void ck_launch_assemble_noise(hipStream_t s, double* const* sigptr, const double* nz, CkLayout L);
@@ -142,8 +148,9 @@ void ck_launch_ginv_syrk(hipStream_t s, double* const* G_dev, const double* aux,
 // tiles of the factor L_S in the Schur buffers (L_dev[J]: packed block columns, upper triangles of the diagonal blocks zero).
 // E: -eps in block columns of ldp >= roundup(nd, 128) rows (ck_launch_draw_noise); pred, cmap: Mp entries in the internal order
 // (cmap[j]: the caller's index of internal site j, -1 beyond m); ones: 128 doubles equal to 1.
+// rows (0: m): the internal sites where they outnumber the caller's m columns (ck_conditional_draws_pair's gap rows, cmap -1)
 void ck_launch_draw_trmm(hipStream_t s, double* X, int64_t m, const double* E, int64_t ldp, int64_t nd, double* const* L_dev,
-                         const double* pred, const double* ones, const int* cmap);
+                         const double* pred, const double* ones, const int* cmap, int64_t rows = 0);
 // In-place Cholesky of the 64 x 64 diagonal block at A (ld); info_dev gets global_index0 + j + 1 of
 // the first non-positive pivot (only if still 0).
 void ck_launch_potrf64(hipStream_t s, double* A, int64_t ld, int64_t global_index0, long long* info_dev,
@@ -265,14 +272,19 @@ void ck_launch_fisher_ytv(hipStream_t s, const double* Yp, int64_t npad, const d
 // on the Schur buffers sch[J] (packed block columns of S, nJ of them), sites k < m:
 // mask[k] = S_kk <= thr; S_kk = 1 where deflated, else S_kk + jit
 void ck_launch_draw_deflate(hipStream_t s, double* const* sch, int nJ, int64_t m, double thr, double jit, unsigned char* mask);
+// the same on the stacked sites of both processes (ck_conditional_draws_pair): process 0 in [0, m0), process 1 in [m0p, m), each
+// with its own thr[k] / jit[k]; the gap rows [m0, m0p) get mask 2 -- deflated for good, no caller column -- and keep their 1
+void ck_launch_draw_deflate_pair(hipStream_t s, double* const* sch, int64_t m0, int64_t m0p, int64_t m, const double thr[2],
+                                 const double jit[2], unsigned char* mask);
 // the strictly lower entries of the deflated sites' rows and columns -> 0
 void ck_launch_draw_zero(hipStream_t s, double* const* sch, int nJ, int64_t m, const unsigned char* mask);
 // above the diagonal of the nJ diagonal blocks -> 0 (after the factorisation, in front of ck_launch_draw_trmm)
 void ck_launch_draw_upper(hipStream_t s, double* const* sch, int nJ);
 // E = -eps of draws d0 .. d0 + nd - 1 (ldp x Mp, block columns of ld NB; 0 beyond nd, beyond m and at deflated sites):
-// noise (nd x m, the caller's order) if given, else the Philox normals of ck_rng.h keyed on seed, counter (cmap[j], d / 2)
+// noise (nd x ldn, the caller's order) if given, else the Philox normals of ck_rng.h keyed on seed, counter (cmap[j], d / 2).
+// ldn (0: m): the caller's number of sites where it is not m
 void ck_launch_draw_noise(hipStream_t s, double* E, int64_t ldp, int64_t Mp, int64_t nd, int64_t m, int64_t d0, const int* cmap,
-                          const unsigned char* mask, const double* noise, uint64_t seed);
+                          const unsigned char* mask, const double* noise, uint64_t seed, int64_t ldn = 0);
 
 // ---- leave-group-out cross-validation (ck_la.hip: the Gram kernel; ck_folds.hip: the fold solves) ------------------
 // Q_SS = W_S W_S^T of every fold, one workgroup per tile of the host's tile map (ck_host.h: CkFoldPlan): rows grow[a0 ..] and

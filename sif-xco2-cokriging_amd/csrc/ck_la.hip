@@ -931,9 +931,9 @@ __global__ __launch_bounds__(512, 4) void k_draw_trmm(double* __restrict__ X, lo
 
 // X: nd x m (the caller's site order, ld m); E: ldp x Mp in block columns; pred / cmap: Mp entries (cmap -1 beyond m)
 void ck_launch_draw_trmm(hipStream_t s, double* X, int64_t m, const double* E, int64_t ldp, int64_t nd, double* const* L_dev,
-                         const double* pred, const double* ones, const int* cmap) {
+                         const double* pred, const double* ones, const int* cmap, int64_t rows) {
     if (nd <= 0 || m <= 0) return;
-    const int tiles_r = (int)((nd + 127) / 128), tiles_c = (int)((m + 127) / 128);
+    const int tiles_r = (int)((nd + 127) / 128), tiles_c = (int)(((rows > 0 ? rows : m) + 127) / 128);
     k_draw_trmm<<<dim3((unsigned)(tiles_r * tiles_c)), dim3(512), 0, s>>>(X, (long)m, E, (long)ldp, L_dev, pred, ones, cmap,
                                                                           tiles_r, tiles_c, (long)nd);
 }

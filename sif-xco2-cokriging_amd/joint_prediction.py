@@ -400,6 +400,118 @@ class Predictor:
         trend[keep] = at["spatial_model"].predict(cov)
         return trend
 
+    # -- both processes at once -------------------------------------------------------------------
+    @staticmethod
+    def _sites_frame(pcoords):
+        """prediction sites as the frame ``__call__`` works on (columns d1, d2 for an array)"""
+        if isinstance(pcoords, pd.DataFrame):
+            return pcoords
+        a = np.atleast_2d(np.asarray(pcoords, dtype=np.float64))
+        if a.ndim != 2 or a.shape[1] < 2:
+            raise ValueError("pcoords must be [[lat, lon], ...]")
+        return pd.DataFrame({"d1": a[:, 0], "d2": a[:, 1]})
+
+    def predict_pair_arrays(self, pcoords, pcoords1=None, pairs=None):
+        """Both processes from one forward sweep per chunk -- the numeric body of ``predict_pair`` (include/cokrige.h:
+        ck_predict_pair).  Returns (pred_0, pred_err_0, pred_1, pred_err_1, cov): process 0 at ``pcoords``, process 1 at
+        ``pcoords1`` (None: the same sites), cov[t] the posterior covariance between process 0 at site pairs[t, 0] and
+        process 1 at site pairs[t, 1] (``pairs=None``: the co-located pairs (k, k) with the same sites, else no covariances
+        and cov is None).  Grids beyond ``rhs_budget_bytes`` go through in chunks, both sets cut at the same indices, so every
+        default pair stays inside one sweep; explicit ``pairs`` need both sets in one sweep.  Raises ValueError on bad
+        arguments before any device work.  Runs on the resident factor of ``__call__``; with ``devices=[...]`` on
+        ``devices[0]``."""
+        pc0, pc1 = self._pair_sites("joint prediction of both processes", (0, 1), pcoords, pcoords1)
+        m0, m1 = len(pc0), len(pc1)
+        same = pcoords1 is None
+        pr = None
+        if pairs is not None:
+            pr = np.asarray(pairs)
+            if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
+                raise ValueError("pairs must be (q, 2) integers: (site of process 0, site of process 1)")
+            pr = pr.astype(np.int64)
+            if len(pr) and (pr.min() < 0 or pr[:, 0].max() >= m0 or pr[:, 1].max() >= m1):
+                raise ValueError(f"pairs index sites outside the {m0} sites of process 0 / the {m1} sites of process 1")
+        h = self._factored_handle()
+        # a sweep carries roundup(m0, 64) + m1 + 1 right-hand-side rows of n_pad doubles
+        n_pad = h.num_panels()[2]
+        rows = max(1024, int(self.rhs_budget_bytes // (8 * max(n_pad, 1))))
+        step = max(1, (rows - 65) // 2)
+        if max(m0, m1) <= step:
+            p0, e0, p1, e1, cov = h.predict_pair(pc0, pc1, pr if pr is not None else
+                                                 (np.column_stack([np.arange(m0)] * 2) if same else None))
+        else:
+            if pr is not None:
+                raise ValueError(f"explicit pairs need both site sets in one sweep: {m0} + {m1} sites exceed the {rows} "
+                                 f"right-hand-side rows of rhs_budget_bytes = {self.rhs_budget_bytes}")
+            parts = []
+            for a in range(0, max(m0, m1), step):
+                s0, s1 = pc0[a:a + step], pc1[a:a + step]
+                parts.append(h.predict_pair(s0, s1, np.column_stack([np.arange(len(s0))] * 2) if same else None))
+            p0, e0, p1, e1 = (np.concatenate([p[j] for p in parts]) for j in range(4))
+            cov = np.concatenate([p[4] for p in parts]) if same else None
+        self.timings = h.pair_timings()
+        return p0, e0, p1, e1, cov
+
+    def predict_pair(self, pcoords, pcoords1=None, pairs=None, postprocess: bool = True):
+        """Prediction and standard error of BOTH processes with the covariance of their prediction errors.
+
+        Two ``__call__``s give two marginal posteriors; whatever needs both fields at once (a SIF / XCO2 ratio or
+        regression, anomaly co-occurrence, a flux inversion fed with both maps) also needs how their errors are correlated.
+        ``pcoords1=None``: the same sites for both processes.  The result has the shape of ``__call__``'s (Dataset, or
+        DataFrame without xarray) with ``pred_0``, ``pred_err_0``, ``pred_1``, ``pred_err_1`` and, per site, ``pred_cov`` --
+        the posterior covariance between the two processes there -- and ``pred_corr = pred_cov / (pred_err_0 pred_err_1)``
+        (NaN where an error is 0).  With ``pcoords1`` the two processes have their own site sets: the result is a pair
+        ``(out_0, out_1)``, each as ``__call__`` returns it for its process.  ``pairs`` (q, 2): explicit (site of process 0,
+        site of process 1) pairs; their covariances come back as an array beside the result, ``(result, cov)``.
+        ``postprocess`` transforms each process as ``__call__`` does and scales the covariances by the product of the two
+        ``scale_fact``s (the correlation is scale-free).  Simple cokriging only (``trend=`` raises NotImplementedError)."""
+        f0 = self._sites_frame(pcoords)
+        f1 = f0 if pcoords1 is None else self._sites_frame(pcoords1)
+        p0, e0, p1, e1, cov = self.predict_pair_arrays(f0.values[:, :2], None if pcoords1 is None else f1.values[:, :2], pairs)
+        scale = [self.mf.fields[k].ds.attrs["scale_fact"] for k in range(2)] if postprocess else [1.0, 1.0]
+        if cov is not None:
+            cov = cov * (scale[0] * scale[1])
+
+        def one(k, f, pred, err):
+            """the frame of process k as __call__ builds it"""
+            self.i = k
+            df = f.copy()
+            df["pred"], df["pred_err"] = pred, err
+            if postprocess:
+                df = df.rename(columns={"d1": "lat", "d2": "lon"})
+                at = self.mf.fields[k].ds.attrs
+                out = df[["lon", "lat"]].copy()
+                out["pred"] = pred * at["scale_fact"] + at["spatial_mean"] + self._spatial_trend(df) + at["temporal_trend"]
+                out["pred_err"] = err * at["scale_fact"]
+                out = out.set_index(["lon", "lat"])
+            else:
+                out = df.set_index(f.columns.values.tolist())
+            return out
+
+        def finish(out, k):
+            if xr is None:
+                return out
+            ds = out.to_xarray()
+            ts = self.mf.fields[k].timestamp
+            try:
+                np.isnan(ts)
+                return ds
+            except TypeError:
+                return ds.assign_coords(coords={"time": np.datetime64(ts)})
+
+        if pcoords1 is None:
+            a, b = one(0, f0, p0, e0), one(1, f0, p1, e1)
+            out = a.rename(columns={"pred": "pred_0", "pred_err": "pred_err_0"})
+            out["pred_1"], out["pred_err_1"] = b["pred"].values, b["pred_err"].values
+            if pairs is None:
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    den = e0 * e1 * (scale[0] * scale[1])
+                    out["pred_cov"], out["pred_corr"] = cov, np.where(den > 0, cov / den, np.nan)
+            res = finish(out, 0)
+        else:
+            res = (finish(one(0, f0, p0, e0), 0), finish(one(1, f1, p1, e1), 1))
+        return (res, cov) if pairs is not None else res
+
     # -- regional means ---------------------------------------------------------------------------
     @staticmethod
     def _block_layout(pcoords, blocks, weights=None):
@@ -485,8 +597,87 @@ class Predictor:
     # -- conditional simulation -------------------------------------------------------------------
     MAX_DRAW_SITES = 65536   # include/cokrige.h: ck_conditional_draws
 
-    def conditional_draws_arrays(self, i: int, pcoords, n_draws: int, seed=None, noise=None, tol: float = 1e-10,
-                                 jitter: float = 0.0):
+    @staticmethod
+    def _draw_sites(pcoords, name="pcoords"):
+        pc = np.atleast_2d(np.asarray(pcoords.values if isinstance(pcoords, pd.DataFrame) else pcoords, dtype=np.float64))
+        if pc.ndim != 2 or pc.shape[1] < 2 or len(pc) < 1:
+            raise ValueError(f"{name} must be [[lat, lon], ...] with at least one site")
+        return np.ascontiguousarray(pc[:, :2])
+
+    @staticmethod
+    def _draw_args(n_draws, tol, jitter, noise, m):
+        if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or n_draws < 1:
+            raise ValueError(f"n_draws must be an integer >= 1, not {n_draws!r}")
+        n_draws = int(n_draws)
+        if not (np.isfinite(tol) and tol >= 0.0) or not (np.isfinite(jitter) and jitter >= 0.0):
+            raise ValueError(f"tol and jitter must be finite and >= 0 (tol={tol!r}, jitter={jitter!r})")
+        if noise is not None:
+            noise = np.asarray(noise, dtype=np.float64)
+            if noise.shape != (n_draws, m):
+                raise ValueError(f"noise has shape {noise.shape}, expected (n_draws, m) = {(n_draws, m)}")
+        return n_draws, noise
+
+    @staticmethod
+    def _first_occurrences(pc):
+        """(keep, where): the first occurrences of the rows of pc in the caller's order, and every row's index among them"""
+        rows = pc.view([("a", np.float64), ("b", np.float64)]).ravel()
+        _, first, inv = np.unique(rows, return_index=True, return_inverse=True)
+        order = np.argsort(first)
+        keep = first[order]
+        rank = np.empty_like(order)
+        rank[order] = np.arange(len(order))
+        return keep, rank[np.asarray(inv).ravel()]
+
+    @staticmethod
+    def _draw_seed(seed):
+        if seed is None:
+            seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be in [0, 2^64)")
+        return seed
+
+    def _pair_sites(self, what, i, pcoords, pcoords1):
+        """The argument checks the joint forms share: the two site sets (pcoords1=None: the same sites for both)."""
+        self._no_trend(what)
+        if tuple(i) != (0, 1) or any(isinstance(k, bool) for k in i):
+            raise ValueError(f"process index {i!r}: the joint form is i=(0, 1)")
+        if self.n_procs != 2:
+            raise ValueError(f"{what} needs a model of two processes, not {self.n_procs}")
+        pc0 = self._draw_sites(pcoords)
+        pc1 = pc0 if pcoords1 is None else self._draw_sites(pcoords1, "pcoords1")
+        return pc0, pc1
+
+    def _conditional_draws_pair(self, i, pcoords, pcoords1, n_draws, seed, noise, tol, jitter):
+        """``conditional_draws_arrays`` for i=(0, 1): joint draws of both processes (include/cokrige.h:
+        ck_conditional_draws_pair).  Everything is STACKED: columns [0, m0) are process 0 at ``pcoords``, [m0, m0 + m1)
+        process 1 at ``pcoords1`` (None: the same sites); ``noise`` is (n_draws, m0 + m1) in that order.  Repeated sites
+        are removed per process -- the two processes at one location are two random variables.  The Philox stream is
+        keyed on the stacked index among the de-duplicated sites."""
+        pc0, pc1 = self._pair_sites("joint conditional simulation", i, pcoords, pcoords1)
+        m0, m1 = len(pc0), len(pc1)
+        n_draws, noise = self._draw_args(n_draws, tol, jitter, noise, m0 + m1)
+        (keep0, where0), (keep1, where1) = self._first_occurrences(pc0), self._first_occurrences(pc1)
+        if len(keep0) + len(keep1) > self.MAX_DRAW_SITES:
+            raise ValueError(f"{len(keep0)} + {len(keep1)} distinct prediction sites; conditional draws are limited to "
+                             f"{self.MAX_DRAW_SITES}")
+        seed = self._draw_seed(seed)
+        e = None if noise is None else np.ascontiguousarray(np.hstack([noise[:, keep0], noise[:, m0 + keep1]]))
+        h = self._factored_handle()
+        draws, pred, err, defl, info = h.conditional_draws_pair(pc0[keep0], pc1[keep1], n_draws, seed=seed, noise=e, tol=tol,
+                                                                jitter=jitter)
+        if info != 0:
+            k = 0 if info - 1 < len(keep0) else 1
+            site = int((keep0, keep1)[k][info - 1 - k * len(keep0)])
+            raise LinAlgError(f"the posterior covariance of the prediction sites is not positive definite at site {site} "
+                              f"{tuple((pc0, pc1)[k][site])} of process {k}; a small jitter (e.g. jitter=1e-10) regularises "
+                              f"nearly coincident sites")
+        self.timings = h.pair_timings()
+        where = np.concatenate([where0, len(keep0) + where1])
+        return draws[:, where], pred[where], err[where], defl[where], seed
+
+    def conditional_draws_arrays(self, i, pcoords, n_draws: int, seed=None, noise=None, tol: float = 1e-10,
+                                 jitter: float = 0.0, pcoords1=None):
         """Draws from the posterior of process ``i`` at ``pcoords`` -- the numeric body of ``conditional_simulation``.
 
         draws[d] = pred + L_S eps_d, S = C_pp - c0^T Sigma^-1 c0 the posterior covariance of the point predictions
@@ -499,38 +690,24 @@ class Predictor:
         ``devices[0]``.
 
         Returns (draws (n_draws, m), pred, pred_err, deflated (bool, m), seed).  Raises ValueError on bad arguments
-        before any device work, and numpy.linalg.LinAlgError when S cannot be factored."""
+        before any device work, and numpy.linalg.LinAlgError when S cannot be factored.
+
+        ``i=(0, 1)``: joint draws of both processes, stacked (``_conditional_draws_pair`` has the layout); ``pcoords1``
+        then gives process 1 its own sites."""
         self._no_trend("conditional simulation")
+        if isinstance(i, tuple):
+            return self._conditional_draws_pair(i, pcoords, pcoords1, n_draws, seed, noise, tol, jitter)
+        if pcoords1 is not None:
+            raise ValueError("pcoords1 belongs to the joint form i=(0, 1)")
         if isinstance(i, bool) or not (isinstance(i, (int, np.integer)) and 0 <= int(i) < self.n_procs):
             raise ValueError(f"process index {i!r} out of range for {self.n_procs} processes")
-        pc = np.atleast_2d(np.asarray(pcoords.values if isinstance(pcoords, pd.DataFrame) else pcoords, dtype=np.float64))
-        if pc.ndim != 2 or pc.shape[1] < 2 or len(pc) < 1:
-            raise ValueError("pcoords must be [[lat, lon], ...] with at least one site")
-        pc = np.ascontiguousarray(pc[:, :2])
+        pc = self._draw_sites(pcoords)
         m = len(pc)
-        if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or n_draws < 1:
-            raise ValueError(f"n_draws must be an integer >= 1, not {n_draws!r}")
-        n_draws = int(n_draws)
-        if not (np.isfinite(tol) and tol >= 0.0) or not (np.isfinite(jitter) and jitter >= 0.0):
-            raise ValueError(f"tol and jitter must be finite and >= 0 (tol={tol!r}, jitter={jitter!r})")
-        if noise is not None:
-            noise = np.asarray(noise, dtype=np.float64)
-            if noise.shape != (n_draws, m):
-                raise ValueError(f"noise has shape {noise.shape}, expected (n_draws, m) = {(n_draws, m)}")
-        rows = pc.view([("a", np.float64), ("b", np.float64)]).ravel()
-        _, first, inv = np.unique(rows, return_index=True, return_inverse=True)
-        order = np.argsort(first)
-        keep = first[order]                       # the first occurrences, in the caller's order
-        rank = np.empty_like(order)
-        rank[order] = np.arange(len(order))
-        where = rank[np.asarray(inv).ravel()]     # caller's site -> its index among the kept sites
+        n_draws, noise = self._draw_args(n_draws, tol, jitter, noise, m)
+        keep, where = self._first_occurrences(pc)
         if len(keep) > self.MAX_DRAW_SITES:
             raise ValueError(f"{len(keep)} distinct prediction sites; conditional draws are limited to {self.MAX_DRAW_SITES}")
-        if seed is None:
-            seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
-        seed = int(seed)
-        if not 0 <= seed < 2 ** 64:
-            raise ValueError("seed must be in [0, 2^64)")
+        seed = self._draw_seed(seed)
         e = None if noise is None else np.ascontiguousarray(noise[:, keep])
         h = self._factored_handle()
         draws, pred, err, defl, info = h.conditional_draws(int(i), pc[keep], n_draws, seed=seed, noise=e, tol=tol,
@@ -542,8 +719,8 @@ class Predictor:
         self.timings = h.draws_timings()
         return draws[:, where], pred[where], err[where], defl[where], seed
 
-    def conditional_simulation(self, i: int, pcoords, n_draws: int = 100, seed=None, postprocess: bool = True, noise=None,
-                               tol: float = 1e-10, jitter: float = 0.0):
+    def conditional_simulation(self, i, pcoords, n_draws: int = 100, seed=None, postprocess: bool = True, noise=None,
+                               tol: float = 1e-10, jitter: float = 0.0, pcoords1=None):
         """Ensembles of maps drawn from the posterior of process ``i`` at ``pcoords`` (conditional simulation).
 
         Nonlinear quantities -- exceedance probabilities, areas above a threshold, maxima, ratios, inputs to downstream
@@ -553,14 +730,24 @@ class Predictor:
         ``jitter``.  ``postprocess=True`` applies ``_postprocess_predictions``' transform to every draw (scale, spatial
         mean, OLS trend, temporal trend).  Without xarray: ``(DataFrame, draws)`` -- the frame as ``__call__`` returns it
         (with the attrs in ``DataFrame.attrs``) and the (n_draws, m) array in its row order.  See
-        ``conditional_draws_arrays`` for the arguments."""
-        if not isinstance(pcoords, pd.DataFrame):
-            a = np.atleast_2d(np.asarray(pcoords, dtype=np.float64))
-            if a.ndim != 2 or a.shape[1] < 2:
-                raise ValueError("pcoords must be [[lat, lon], ...]")
-            pcoords = pd.DataFrame({"d1": a[:, 0], "d2": a[:, 1]})
+        ``conditional_draws_arrays`` for the arguments.
+
+        ``i=(0, 1)``: co-simulation -- draw d of both processes comes from ONE draw of their joint posterior (the SIF / XCO2
+        ratio of draw d is a draw of the ratio).  Returns a pair ``(out_0, out_1)``, each shaped as above for its process
+        (process 1 at ``pcoords1``, default the same sites), with the same ``seed`` and ``jitter`` and its own ``n_deflated``;
+        ``noise`` is (n_draws, m0 + m1), process 0's columns first."""
+        pcoords = self._sites_frame(pcoords)
+        if isinstance(i, tuple):
+            pcoords1 = pcoords if pcoords1 is None else self._sites_frame(pcoords1)
+            draws, pred, err, defl, seed = self.conditional_draws_arrays(i, pcoords.values[:, :2], n_draws, seed=seed, noise=noise,
+                                                                         tol=tol, jitter=jitter, pcoords1=pcoords1.values[:, :2])
+            m0 = len(pcoords)
+            cols = [slice(0, m0), slice(m0, None)]
+            return tuple(self._draws_output(k, (pcoords, pcoords1)[k], draws[:, cols[k]], pred[cols[k]], err[cols[k]],
+                                            {"seed": seed, "n_deflated": int(defl[cols[k]].sum()), "jitter": float(jitter)},
+                                            postprocess) for k in range(2))
         draws, pred, err, defl, seed = self.conditional_draws_arrays(i, pcoords.values[:, :2], n_draws, seed=seed,
-                                                                     noise=noise, tol=tol, jitter=jitter)
+                                                                     noise=noise, tol=tol, jitter=jitter, pcoords1=pcoords1)
         return self._draws_output(i, pcoords, draws, pred, err, {"seed": seed, "n_deflated": int(defl.sum()), "jitter": float(jitter)},
                                   postprocess)
 

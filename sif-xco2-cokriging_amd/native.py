@@ -61,6 +61,9 @@ _PROTOS = {
     "ck_sample": [c_void_p, _dp, _dp, c_int64],
     "ck_conditional_draws": [c_void_p, c_int, _dp, c_int64, c_int64, c_uint64, _dp, c_double, c_double, _dp, _dp, _dp,
                              POINTER(c_uint8), POINTER(c_int64)],
+    "ck_predict_pair": [c_void_p, _dp, c_int64, _dp, c_int64, _dp, _dp, _dp, _dp, POINTER(c_int64), c_int64, _dp],
+    "ck_conditional_draws_pair": [c_void_p, _dp, c_int64, _dp, c_int64, c_int64, c_uint64, _dp, c_double, c_double, _dp, _dp,
+                                  _dp, POINTER(c_uint8), POINTER(c_int64)],
     "ck_num_panels": [c_void_p, POINTER(c_int), POINTER(c_int), POINTER(c_int64)],
     "ck_panel_owner": [c_void_p, c_int, POINTER(c_int)],
     "ck_aux_begin": [c_void_p, c_int, _dp, c_int64],
@@ -551,6 +554,54 @@ class Handle:
         keys = ["predict_ms", "cpp_ms", "vtv_ms", "deflate_ms", "factor_ms", "noise_ms", "product_ms", "total_ms",
                 "n_deflated", "n_chunks"]
         return dict(zip(keys, out[30:40].tolist()))
+
+    def predict_pair(self, pcoords0, pcoords1, pairs=None):
+        """Both processes from one forward sweep on the resident factor (include/cokrige.h: ck_predict_pair).  ``pairs``:
+        (q, 2) integers (a, b) -- a indexes pcoords0, b indexes pcoords1.  Returns (pred0, err0, pred1, err1, pair_cov | None);
+        pair_cov[t] is the posterior covariance between process 0 at site a_t and process 1 at site b_t."""
+        pc0, pc1 = _f64(pcoords0, 2), _f64(pcoords1, 2)
+        m0, m1 = pc0.shape[0], pc1.shape[0]
+        pred0, err0, pred1, err1 = np.empty(m0), np.empty(m0), np.empty(m1), np.empty(m1)
+        pr = cov = None
+        q = 0
+        if pairs is not None:
+            pr = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+            q = pr.shape[0]
+            cov = np.empty(q)
+        _chk(lib().ck_predict_pair(self._h, _p(pc0), m0, _p(pc1), m1, _p(pred0), _p(err0), _p(pred1), _p(err1),
+                                   pr.ctypes.data_as(POINTER(c_int64)) if pr is not None else None, q,
+                                   _p(cov) if cov is not None else None))
+        return pred0, err0, pred1, err1, cov
+
+    def conditional_draws_pair(self, pcoords0, pcoords1, n_draws, seed=0, noise=None, tol=1e-10, jitter=0.0):
+        """Joint draws of both processes (include/cokrige.h: ck_conditional_draws_pair).  Everything is stacked: columns
+        [0, m0) are process 0 at pcoords0, [m0, m0 + m1) process 1 at pcoords1.  Returns (draws (n_draws, m0 + m1), pred,
+        pred_err, deflated (bool), info); info != 0: S could not be factored at the stacked site info - 1."""
+        pc0, pc1 = _f64(pcoords0, 2), _f64(pcoords1, 2)
+        m0, m1 = pc0.shape[0], pc1.shape[0]
+        m = m0 + m1
+        n_draws = int(n_draws)
+        e = None
+        if noise is not None:
+            e = _f64(noise)
+            if e.shape != (n_draws, m):
+                raise ValueError(f"noise has shape {e.shape}, expected {(n_draws, m)}")
+        draws = np.zeros((max(n_draws, 0), m))
+        pred, err = np.empty(m), np.empty(m)
+        defl = np.zeros(m, dtype=np.uint8)
+        info = c_int64(0)
+        _chk(lib().ck_conditional_draws_pair(self._h, _p(pc0), m0, _p(pc1), m1, n_draws, c_uint64(int(seed) & (2 ** 64 - 1)),
+                                             _p(e) if e is not None else None, float(tol), float(jitter), _p(draws),
+                                             _p(pred), _p(err), defl.ctypes.data_as(POINTER(c_uint8)), byref(info)))
+        return draws, pred, err, defl.astype(bool), info.value
+
+    def pair_timings(self):
+        """ck_timings [124 ..] of the last conditional_draws_pair() and [134 ..] of the last predict_pair() stages."""
+        out = np.zeros(138)
+        _chk(lib().ck_timings(self._h, _p(out), 138))
+        keys = ["predict_ms", "cpp_ms", "vtv_ms", "deflate_ms", "factor_ms", "noise_ms", "product_ms", "total_ms",
+                "n_deflated", "n_chunks", "pair_assemble_ms", "pair_sweep_ms", "pair_reduce_ms", "pair_total_ms"]
+        return dict(zip(keys, out[124:138].tolist()))
 
     def loocv(self, i, n_i):
         pred, err = np.empty(n_i), np.empty(n_i)
