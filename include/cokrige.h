@@ -680,6 +680,41 @@ int ck_predict_local_blocks(ck_handle* h, int i, const double* centres_host /* r
                             const double* f0_host /* r x p_i block regressors, NULL when p_i = 0 */, double max_dist,
                             double* pred_host, double* pred_err_host, double* beta_host /* r x p or NULL */,
                             int64_t* n_empty, int64_t* n_not_pd, int64_t* n_rank_def, int64_t* k_max);
+/* Both processes at every point from ONE local system: ck_predict_pair's question -- how are the two prediction errors at a
+ * site correlated -- for data whose Sigma does not fit.  With cv = 0 the neighbourhood of a point does not depend on the
+ * predicted process (neither the radius predicate nor the caps of ck_set_local_neighbours look at it; only the c row and the
+ * prior variance do), so both processes share one search, one Sigma_loc and one Cholesky; the second process is one more row
+ * riding along the factorisation and the cross-covariance one more dot product of two solved rows.  Per point:
+ *   the neighbour list is exactly that of ck_predict_local(cv = 0): the radius, the caps with ties kept, the internal site order;
+ *   Sigma_loc = L L^T with ck_set_noise's terms on its diagonal;
+ *   c^q = the point's covariances with the neighbours as process q, the c row of ck_predict_local(q) (the nugget where h = 0
+ *         and the neighbour's process is q);  v_q = L^-1 c^q,  y = L^-1 z;
+ *   pred_q = v_q . y,  pred_err_q = nanmax(sqrt(sigma_q^2 + nugget_q - v_q . v_q), 0);
+ *   pred_cov = C_01(0) - v_0 . v_1, C_01(0) the model's cross-covariance at h = 0 from the exact evaluator (no nugget, as in
+ *         ck_predict_pair).
+ * Because the neighbourhood is shared, (pred_0, pred_1) is the simple-cokriging predictor of both processes from ONE data
+ * subset, and [[pred_err_0^2, pred_cov], [pred_cov, pred_err_1^2]] is a genuine conditional covariance: that of the two
+ * processes at the point given the data of the neighbourhood (positive semi-definite, |pred_cov| <= pred_err_0 pred_err_1).
+ * No covariance between DIFFERENT points is offered: their neighbourhoods differ, so such a matrix would be no posterior
+ * covariance of anything -- the argument of ck_predict_local_blocks (ck_predict_pair on a factored Sigma gives one).
+ * An empty neighbourhood, or a local Sigma that is not positive definite, gives NaN in all five outputs; each is counted once
+ * per point (n_empty, n_not_pd).  pred_cov may be NULL.  There is no cv argument: cross-validation of pairs is not offered.
+ * pred_q / pred_err_q carry the bits of ck_predict_local(q, cv = 0) on the same handle: the same steps on the same system, the
+ * sums by the same tree.  One exception, in the tiled class only: at k = 62 (mod 64) neighbours the padded height
+ * roundup(k + 3, 64) is 64 more than the single call's roundup(k + 2, 64), the rows ride through one more 64-column block, and
+ * the last bits may differ (measured: at most 9e-16 absolute on values of order 1).  Every sum has a fixed order (no atomics):
+ * repeated calls give the same bits, whatever the batching.
+ * Device path: k <= 64 neighbours in LDS (k_local_solve_pair, a (k + 3) x k matrix, 34 304 B: four workgroups per CU as
+ * k_local_solve); larger ones on the tiled path with kq = roundup(k + 3, 64) rows -- kq - 3, kq - 2, kq - 1 hold c^0, c^1, z --
+ * whatever "local_tile_min" says (no slab kernel, as the block call); batches and the slab budget count the third row.
+ * Nothing on the handle is invalidated: a resident factor and the bits of ck_predict / ck_predict_local before and after are
+ * unchanged.  Needs ck_set_model / ck_set_data; optional ck_set_noise, ck_set_local_neighbours.  Refused through ck_last_error,
+ * with the call's name: a partitioned handle; a model of one process; a trend set on the handle (clear it with ck_set_trend:
+ * the GLS cross term is not part of this call); m < 1; a non-finite or negative max_dist; NULL for any pointer but pred_cov.
+ * ck_timings [138 ..] describe the call. */
+int ck_predict_local_pair(ck_handle* h, const double* pcoords_host, int64_t m, double max_dist, double* pred0, double* pred_err0,
+                          double* pred1, double* pred_err1, double* pred_cov /* m, or NULL */, int64_t* n_empty,
+                          int64_t* n_not_pd, int64_t* k_max);
 
 /* Leave-group-out and buffer cross-validation in the moving neighbourhood: ck_cv_folds' question for data whose Sigma does not
  * fit -- leave-track-out, spatial blocks, K-fold, a buffer around the withheld datum -- answered by the local predictor.  Every
@@ -780,6 +815,39 @@ int ck_simulate_local(ck_handle* h, int i, const double* pcoords_host, int64_t m
  * (0 in the padding; NaN where the local system is not positive definite). */
 int ck_debug_simulate_local_weights(ck_handle* h, int i, const double* pcoords_host, int64_t m, const int64_t* rank_host,
                                     double max_dist, int64_t* idx_host /* m x 64 */, double* w_host /* m x 64 */);
+/* Sequential Gaussian CO-simulation in the moving neighbourhood: ck_simulate_local with the sites of BOTH processes stacked
+ * behind the data, so that every draw is a jointly consistent pair of maps (two ck_simulate_local calls give two independent
+ * ensembles).  The stacked index is k for site k of pcoords0 and m0 + k for site k of pcoords1, as in
+ * ck_conditional_draws_pair; rank_host, noise_host, draws_host, mean_host, var_host, count_host and *info speak of stacked sites.
+ * Definition: ck_simulate_local's, on the augmented set in which the sites of process 0 are appended to process 0's data and
+ * those of process 1 to process 1's, as noise-free pseudo-data.  Every datum precedes every site; the sites are ordered by rank
+ * ACROSS both processes.  The conditioning set of a stacked site is, per process q, the earlier members within max_dist -- data
+ * and earlier sites of process q alike -- cut by the cap nmax_q with ties kept.  A site of process q has C(0) = sigma_q^2 +
+ * nugget_q; its covariance with a member is the c entry of ck_predict_local for the site's OWN process (a co-located site of
+ * the other process contributes C_01(0), no nugget).  The local system, the recursion, the level rule, the NaN and info rules
+ * and stats4 are ck_simulate_local's.  count_host has four columns: data of process 0, data of process 1, earlier sites of
+ * process 0, earlier sites of process 1.  Philox counter: (stacked index, d / 2, 0, 0).
+ * Two sites of the SAME process at one location are reported through info, as in ck_simulate_local; the two processes at one
+ * location are two random variables and stop nothing, provided |rho_12| < 1.
+ * Identities: with m1 = 0 the call is ck_simulate_local(0), bit for bit, and with m0 = 0 it is ck_simulate_local(1); when every
+ * datum and every earlier stacked site is in every set, Y = pred + L_S eps with L_S the factor of the dense posterior covariance
+ * of the stacked sites in rank order -- ck_conditional_draws_pair's law.
+ * Device path: one select pass over the stacked sites (with cv = 0 the search does not look at the process), the weights in one
+ * launch of k_local_sim_weights per process's sites, then ck_simulate_local's levels, recursion and chunking on the stacked
+ * set.  Every sum has a fixed order: repeated calls give the same bits.  Nothing on the handle is invalidated.
+ * Refused through ck_last_error, with the call's name: what ck_simulate_local refuses (m read as m0 + m1), and a model of one
+ * process; m0 < 0 or m1 < 0; NULL coordinates of a non-empty site set; N + m0 + m1 > 2^31 - 1; any conditioning set of more
+ * than 64 members, before any solve.  ck_timings [110 ..] describe the call as they do ck_simulate_local. */
+int ck_simulate_local_pair(ck_handle* h, const double* pcoords0_host, int64_t m0, const double* pcoords1_host, int64_t m1,
+                           const int64_t* rank_host /* m0 + m1, stacked, distinct */, double max_dist, int64_t n_draws,
+                           uint64_t seed, const double* noise_host /* n_draws x (m0 + m1) or NULL */,
+                           double* draws_host /* n_draws x (m0 + m1) */, double* mean_host /* m0 + m1 or NULL */,
+                           double* var_host /* m0 + m1 or NULL */, int32_t* count_host /* (m0 + m1) x 4 or NULL */,
+                           int64_t* stats4 /* n_empty, k_max, n_capped, n_levels */, int64_t* info);
+/* ck_debug_simulate_local_weights for the stacked sites of both processes: a site is N + its stacked index. */
+int ck_debug_simulate_local_pair_weights(ck_handle* h, const double* pcoords0_host, int64_t m0, const double* pcoords1_host,
+                                         int64_t m1, const int64_t* rank_host, double max_dist,
+                                         int64_t* idx_host /* (m0 + m1) x 64 */, double* w_host /* (m0 + m1) x 64 */);
 
 /* ---- empirical (cross-)semivariogram / covariogram: src/fields.py:192-232, 378-403 ----- */
 /* Fields i and j: coords (n x 2), residuals = values minus their mean (src/fields.py:380).
@@ -952,7 +1020,12 @@ int ck_debug_gemm_stamps(ck_handle* h, uint64_t* out_host, int64_t n_words, int6
  * over the chunks; [130] the draw product, summed; [131] host wall clock of the call; [132] number of deflated sites; [133]
  * number of chunks.
  * ck_predict_pair (n up to 138; also set by ck_conditional_draws_pair): [134] K2 assembly of the stacked right-hand sides;
- * [135] the forward sweep; [136] the reductions (k_reduce_pred per process, k_pair_cov); [137] host wall clock of the call. */
+ * [135] the forward sweep; [136] the reductions (k_reduce_pred per process, k_pair_cov); [137] host wall clock of the call.
+ * ck_predict_local_pair (n up to 143): [138] the counting pass (a capped call's select pass); [139] the solve window: assembly,
+ * factorisation and outputs of both size classes; [140] host: a growth of the scratch slab; [141] points of the tiled class;
+ * [142] the batches the tiled class was factored in under the slab budget.
+ * [60 ..] are filled as by ck_predict_local.  Like every block, [138 ..] hold until the next call that describes itself in a
+ * lower block: such a call zeroes the slots from its own first one upwards (ck_simulate_local and its pair form from [110]). */
 int ck_timings(ck_handle* h, double* out, int n);
 /* The assembly kernels evaluate the covariance through a per-block table of C = amp * rho over
  * the squared chord (built on the device from the exact K_nu evaluator and verified against it

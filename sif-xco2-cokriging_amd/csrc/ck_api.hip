@@ -34,7 +34,7 @@
 #include "ck_vecchia.h"
 
 static int64_t roundup(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-#define CK_N_TIMINGS 140
+#define CK_N_TIMINGS 144
 // ck_host_gls's relative pivot threshold: a trend column whose pivot is not above 1e-10 of its diagonal is refused
 #define CK_TREND_TOL 1e-10
 static_assert(CK_LU_PMAX == 2 * CK_TREND_PMAX, "the local kernels size their LDS by CK_LU_PMAX trend columns");
@@ -3816,6 +3816,7 @@ struct LocalBlocks {
 struct LocalResult {
     int64_t n_empty = 0, n_not_pd = 0, k_max = 0;
     int64_t n_tiled = 0;        // points of the tiled class
+    int64_t n_tbatches = 0;     // batches the tiled class was cut into under the slab budget
     double pass_ms = 0.0;       // device windows: the counting pass (a capped call's select pass),
     double solve_ms = 0.0;      // assembly / factorisations / reductions,
     double reduce_ms = 0.0;     // of which the tiled class's universal reductions (universal form)
@@ -3874,9 +3875,16 @@ static int local_block_members(ck_handle* h, DevTemps& tmp, int i, const CkLocal
     return 0;
 }
 
+// The pair form's extras (ck_predict_local_pair); null: one process.  The call runs as process 0 (with cv = 0 the search does
+// not look at the process); pred / pred_err are process 0's, these are process 1's and the covariance of the two errors.
+struct LocalPair {
+    double *pred1, *err1;
+    double* cov;   // m or null
+};
+
 static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_t m, double max_dist, int cv, double* pred,
                               double* pred_err, LocalResult* res, const LocalUniv* u, const LocalVecchia* vc = nullptr,
-                              const LocalBlocks* bk = nullptr, const LocalWithhold* wh = nullptr) {
+                              const LocalBlocks* bk = nullptr, const LocalWithhold* wh = nullptr, const LocalPair* pr = nullptr) {
     LocalResult& R = *res = LocalResult();
     if (ensure_layout(h, false)) return -1;   // sites, tables, chunk bounds -- no Sigma panels
     if (i < 0 || i >= h->n_procs) return fail("process index out of range");
@@ -3893,7 +3901,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     long long *d_off = nullptr, *d_linfo = nullptr;
     int* d_k0 = nullptr;
     CkLocalSys* d_sys = nullptr;
-    HIPCHK(tmp.get(&d_out, (size_t)(2 * mp * 8)));
+    HIPCHK(tmp.get(&d_out, (size_t)((pr ? 5 : 2) * mp * 8)));
     HIPCHK(tmp.get(&d_off, (size_t)(mp * sizeof(long long))));
     if (vc) {
         HIPCHK(tmp.get(&d_vv, (size_t)(mp * 8)));
@@ -3941,21 +3949,34 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     const int kl = ck_local_lds_limit();
     // may lie below the LDS limit: then the LDS kernel only sees k <= k_hi.  The universal form has no slab kernel: every
     // neighbourhood beyond the LDS limit takes the tiled path
-    const int k_hi = (u || bk) ? std::min(h->local_tile_min, kl) : h->local_tile_min;
+    const int k_hi = (u || bk || pr) ? std::min(h->local_tile_min, kl) : h->local_tile_min;
+    const int xr = pr ? CK_LOCAL_PAIR_ROWS - 2 : up;   // rows of every tiled system beyond c and z
     CkLocalNeeds nd;   // ck_host.cpp: the slab need of every point, the tiled class largest first
-    ck_host_local_needs(cnt.data(), m, kl, k_hi, up, &nd);
+    if (pr)
+        ck_host_local_pair_needs(cnt.data(), m, kl, h->local_tile_min, &nd);
+    else
+        ck_host_local_needs(cnt.data(), m, kl, k_hi, up, &nd);
     long long budget = 0;
     size_t mem_free = 0;
     if (local_budget_doubles(h, &budget, &mem_free)) return -1;
     if (budget < nd.need_max) budget = nd.need_max;
-    if ((size_t)nd.need_max * 8 > mem_free) return fail(std::string(wh ? "ck_cv_local_folds" : bk ? "ck_predict_local_blocks" : u ? "ck_predict_local_universal" : "ck_predict_local") + ": a neighbourhood of " + std::to_string(nd.k_max) + " sites does not fit the device memory");
+    if ((size_t)nd.need_max * 8 > mem_free) return fail(std::string(pr ? "ck_predict_local_pair" : wh ? "ck_cv_local_folds" : bk ? "ck_predict_local_blocks" : u ? "ck_predict_local_universal" : "ck_predict_local") + ": a neighbourhood of " + std::to_string(nd.k_max) + " sites does not fit the device memory");
     CkLocalPlan plan;   // slab offsets, the batches of both classes under the budget, the tiled systems
-    ck_host_local_plan(cnt.data(), nd, budget, up, &plan);
+    ck_host_local_plan(cnt.data(), nd, budget, xr, &plan);
     if (local_slab_grow(h, plan.slab_doubles, budget, &R.grow_ms)) return -1;
     if (plan.slab_doubles > 0) d_slab = h->local_slab;
     HIPCHK(hipEventRecord(h->ev2, h->stream));
     HIPCHK(hipMemcpyAsync(d_off, plan.off.data(), m * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-    if (bk)   // the universal form's two classes, with or without a trend
+    const CkLocalPairOut PO{d_out,
+                            d_out + mp,
+                            d_out + 2 * mp,
+                            d_out + 3 * mp,
+                            d_out + 4 * mp,
+                            {h->blk[0].amp + h->blk[0].nugget, h->blk[2].amp + h->blk[2].nugget},
+                            ck_cov_entry(h->blk[1], 0.0, 0)};
+    if (pr)   // the pair form: the LDS class here, everything larger on the tiled path below
+        ck_launch_local_solve_pair(h->stream, P, m, d_cnt, k_hi, PO);
+    else if (bk)   // the universal form's two classes, with or without a trend
         ck_launch_local_solve_b(h->stream, P, m, d_cnt, k_hi, Tr, d_out, d_out + mp, d_beta, d_stat);
     else if (u)
         ck_launch_local_solve_u(h->stream, P, m, d_cnt, k_hi, Tr, d_out, d_out + mp, d_beta, d_stat);
@@ -3988,14 +4009,16 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
         for (const auto& tb : plan.tbatches) {
             const CkLocalSys* bsys = d_sys + tb.first;
             const int nb = (int)(tb.second - tb.first);
-            ck_launch_local_assemble_t(h->stream, P, bsys, nb, d_slab, d_k0 + tb.first);
+            ck_launch_local_assemble_t(h->stream, P, bsys, nb, d_slab, d_k0 + tb.first, pr != nullptr);
             if (u) ck_launch_local_trend_rows_t(h->stream, bsys, nb, d_slab, layout_of(h), Tr);
             const int kq_max = plan.sys[tb.first].kq;
             std::vector<int> kqv(nb);
             for (int y = 0; y < nb; ++y) kqv[y] = plan.sys[tb.first + y].kq;
             factor_tiled_batch(h->stream, bsys, d_slab, nb, kqv.data(), kq_max, kq_max, h->local_group,
                                h->local_left != 0 && 64 * h->local_group <= 256, d_linfo + tb.first);
-            if (u) {
+            if (pr) {
+                ck_launch_local_reduce_pair_t(h->stream, bsys, nb, d_slab, d_linfo + tb.first, PO);
+            } else if (u) {
                 hipEvent_t e0 = nullptr, e1 = nullptr;
                 HIPCHK(hipEventCreate(&e0));
                 ev_red.push_back(e0);
@@ -4015,6 +4038,11 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     HIPCHK(hipEventRecord(h->ev3, h->stream));
     HIPCHK(hipMemcpyAsync(pred, d_out, m * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipMemcpyAsync(pred_err, d_out + mp, m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (pr) {
+        HIPCHK(hipMemcpyAsync(pr->pred1, PO.pred1, m * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(pr->err1, PO.err1, m * 8, hipMemcpyDeviceToHost, h->stream));
+        if (pr->cov) HIPCHK(hipMemcpyAsync(pr->cov, PO.cov, m * 8, hipMemcpyDeviceToHost, h->stream));
+    }
     if (vc) {
         HIPCHK(hipMemcpyAsync(vc->vv, d_vv, m * 8, hipMemcpyDeviceToHost, h->stream));
         for (int64_t p = 0; p < m; ++p) {
@@ -4026,6 +4054,7 @@ static int predict_local_impl(ck_handle* h, int i, const double* pcoords, int64_
     HIPCHK(elapsed_ms(h->ev2, h->ev3, &R.solve_ms));
     R.k_max = nd.k_max;
     R.n_tiled = (int64_t)nd.tiled.size();
+    R.n_tbatches = nd.tiled.empty() ? 0 : (int64_t)plan.tbatches.size();
     R.n_empty = nd.n_empty;
     if (bk) {
         double t = 0;
@@ -4148,6 +4177,39 @@ extern "C" int ck_predict_local_blocks(ck_handle* h, int i, const double* centre
     h->t_ms[107] = R.prior_ms;                   // the sigma_BB pass
     h->t_ms[108] = R.total_ms;                   // host wall clock of the call
     h->t_ms[109] = R.cbar_evals;                 // sum_b q_b k_b
+    return 0;
+}
+
+// Both processes at every point from one local system: include/cokrige.h has the definition; ck_host.cpp the size classes with
+// three extra rows, ck_local.hip the kernels.  The stages are predict_local_impl's, run as process 0.
+extern "C" int ck_predict_local_pair(ck_handle* h, const double* pcoords, int64_t m, double max_dist, double* pred0, double* pred_err0,
+                                     double* pred1, double* pred_err1, double* pred_cov, int64_t* n_empty, int64_t* n_not_pd,
+                                     int64_t* k_max) {
+    CHKH(h);
+    const std::string name = "ck_predict_local_pair";
+    if (h->world != 1)
+        return fail(name + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) + ")");
+    if (!h->model_set || h->n_procs != 2)
+        return fail(name + ": needs a model of two processes (n_procs = " + std::to_string(h->n_procs) + ")");
+    if (trend_total(h) > 0)
+        return fail(name + ": a trend of " + std::to_string(trend_total(h)) +
+                    " columns is set on the handle; the pair form takes none (clear it with ck_set_trend)");
+    if (m < 1) return fail(name + ": m = " + std::to_string(m) + " points; at least 1");
+    if (!(max_dist >= 0.0) || !std::isfinite(max_dist))
+        return fail(name + ": max_dist must be finite and >= 0, got " + std::to_string(max_dist));
+    if (!pcoords || !pred0 || !pred_err0 || !pred1 || !pred_err1 || !n_empty || !n_not_pd || !k_max)
+        return fail(name + ": null pcoords_host / pred0 / pred_err0 / pred1 / pred_err1 / n_empty / n_not_pd / k_max");
+    timings_from(h, 138);
+    const LocalPair pr{pred1, pred_err1, pred_cov};
+    LocalResult R;
+    if (predict_local_impl(h, 0, pcoords, m, max_dist, 0, pred0, pred_err0, &R, nullptr, nullptr, nullptr, nullptr, &pr)) return -1;
+    local_counts_out(R, n_empty, n_not_pd, k_max);
+    write_select_timings(h, R.st);        // [60 .. 63], as after every local call
+    h->t_ms[138] = R.pass_ms;             // the counting pass (a capped call's select pass)
+    h->t_ms[139] = R.solve_ms;            // the solve window: both classes' assembly, factorisation and outputs
+    h->t_ms[140] = R.grow_ms;             // host: a growth of the scratch slab
+    h->t_ms[141] = (double)R.n_tiled;     // points of the tiled class
+    h->t_ms[142] = (double)R.n_tbatches;  // batches they were factored in (the slab budget)
     return 0;
 }
 
@@ -4709,8 +4771,9 @@ struct HandleDeleter {
 };
 struct LocalSim {
     std::unique_ptr<ck_handle, HandleDeleter> child;
-    int64_t N = 0, m = 0;
-    std::vector<int> pos;    // the caller's site index -> position in the ordering
+    int64_t N = 0, m = 0;    // m: the stacked sites of both processes
+    int64_t mq[2] = {0, 0};
+    std::vector<int> pos;    // the caller's stacked site index -> position in the ordering
     std::vector<int> ext;    // internal index of the augmented set -> the caller's stacked index (a site: N + its index)
     LocalPass pass;
     CkLocalSimOut out{};
@@ -4719,11 +4782,27 @@ struct LocalSim {
     int64_t n_empty = 0, k_max = 0, w_bytes = 0;   // w_bytes: what the weight kernel's outputs hold on the device
     double weights_ms = 0.0;
 };
-// What both entry points (name) do up to the weight kernel: the refusals, the ordering, the augmented set, the select pass (a
+// A launch's view of points [base, ..) of a pass as process i: the per-point arrays shifted, so that a kernel's point 0 is the
+// pass's point `base`
+static CkLocalProblem local_problem_from(const ck_handle* h, CkLocalProblem P, int64_t base, int i) {
+    P.pc += base;   // (the three rows keep their stride mpad)
+    P.pu += base;
+    if (P.rq) P.rq += 2 * base;
+    if (P.cp) P.cp += base;
+    if (P.rp) P.rp += base;
+    P.i_pred = i;
+    P.c0var = h->blk[2 * i].amp + h->blk[2 * i].nugget;
+    return P;
+}
+// What the entry points (name) do up to the weight kernel: the refusals, the ordering, the augmented set, the select pass (a
 // set beyond the LDS limit is refused here, before any solve), then k_local_sim_weights and the downloads the host plans with.
-static int local_sim_stages(ck_handle* h, const std::string& name, int i, const double* pcoords, int64_t m, const int64_t* rank_host,
-                            double max_dist, const char* null_args, int64_t n_draws, DevTemps& tmp, LocalSim* out) {
+// The sites: mq[q] of process q at pcs[q], stacked (ck_host.h: CkSimSites).  i: the process of ck_simulate_local, whose sites
+// are the only ones; pair: the pair form, which needs a model of two processes (i is not read).
+static int local_sim_stages(ck_handle* h, const std::string& name, int i, bool pair, const double* const pcs[2], const int64_t mq[2],
+                            const int64_t* rank_host, double max_dist, const char* null_args, int64_t n_draws, DevTemps& tmp,
+                            LocalSim* out) {
     LocalSim& C = *out;
+    const int64_t m = mq[0] + mq[1];
     if (h->world != 1)
         return fail(name + " is the single-process form: this handle is partitioned (world = " + std::to_string(h->world) + ")");
     if (null_args) return fail(name + ": null " + null_args);
@@ -4737,22 +4816,19 @@ static int local_sim_stages(ck_handle* h, const std::string& name, int i, const 
     if (!h->model_set) return fail("ck_set_model has not been called");
     for (int k = 0; k < h->n_procs; ++k)
         if (!h->data_set[k]) return fail("ck_set_data missing for process " + std::to_string(k));
-    if (i < 0 || i >= h->n_procs) return fail(name + ": process index out of range");
-    const int64_t n0 = h->n[0], ni = h->n[i];
+    if (!pair && (i < 0 || i >= h->n_procs)) return fail(name + ": process index out of range");
+    if (pair && h->n_procs != 2) return fail(name + ": needs a model of two processes (n_procs = " + std::to_string(h->n_procs) + ")");
+    const int64_t n0 = h->n[0];
     const int64_t N = C.N = n0 + (h->n_procs == 2 ? h->n[1] : 0);
     C.m = m;
+    C.mq[0] = mq[0];
+    C.mq[1] = mq[1];
     if (N <= 0) return fail("no observations");
     if (N + m > INT32_MAX) return fail(name + ": more than 2^31 - 1 data and sites");
-    {   // the ordering of the sites
-        std::vector<int64_t> ident((size_t)m);
-        for (int64_t t = 0; t < m; ++t) ident[(size_t)t] = t;
-        const int64_t n2[2] = {m, 0};
-        CkVecchiaOrder ord;
-        if (ck_host_vecchia_order(rank_host, 1, n2, m, m, ident.data(), nullptr, &ord))
-            return fail(name + ": sites " + std::to_string(ord.dup[0]) + " and " + std::to_string(ord.dup[1]) +
-                        " have the same rank " + std::to_string((long long)rank_host[ord.dup[0]]));
-        C.pos = std::move(ord.pos);
-    }
+    CkSimSites ST;   // ck_host.cpp: the ordering of the stacked sites, then their places in the augmented set
+    if (ck_host_sim_order(rank_host, mq, &ST))
+        return fail(name + ": sites " + std::to_string(ST.dup[0]) + " and " + std::to_string(ST.dup[1]) + " have the same rank " +
+                    std::to_string((long long)rank_host[ST.dup[0]]));
     // ---- the augmented set
     {
         ck_handle* c = nullptr;
@@ -4776,41 +4852,37 @@ static int local_sim_stages(ck_handle* h, const std::string& name, int i, const 
     c->model_set = true;
     for (int k = 0; k < h->n_procs; ++k) {
         std::vector<double> co(h->h_coords[k]), va(h->h_values[k]);
-        if (k == i) {
-            co.insert(co.end(), pcoords, pcoords + 2 * m);
-            va.insert(va.end(), (size_t)m, 0.0);
+        if (mq[k] > 0) {
+            co.insert(co.end(), pcs[k], pcs[k] + 2 * mq[k]);
+            va.insert(va.end(), (size_t)mq[k], 0.0);
         }
         if (ck_set_data(c, k, co.data(), va.data(), (int64_t)va.size())) return -1;
         if (!h->noise_var[k].empty()) {
             std::vector<double> nv(h->noise_var[k]);
-            if (k == i) nv.insert(nv.end(), (size_t)m, 0.0);   // a site is a noise-free pseudo-datum
+            nv.insert(nv.end(), (size_t)mq[k], 0.0);   // a site is a noise-free pseudo-datum
             if (ck_set_noise(c, k, nv.data(), (int64_t)nv.size(), h->noise_scale[k])) return -1;
         }
     }
     if (ensure_layout(c, false)) return -1;
     if (ensure_noise(c)) return -1;
     // ---- precedence: the data in front of every site, the sites by position
-    C.ext.assign((size_t)c->Npad, -1);
-    std::vector<int> rs((size_t)c->Npad, INT32_MAX), rp((size_t)m);
-    for (int k = 0; k < c->n_procs; ++k) {
-        const int64_t off = k == 0 ? 0 : c->n0p, soff = k == 0 ? 0 : n0;
-        for (int64_t j = 0; j < c->n[k]; ++j) {
-            const int64_t e = c->perm[k][(size_t)j];
-            if (k == i && e >= ni) {
-                C.ext[(size_t)(off + j)] = (int)(N + (e - ni));
-                rs[(size_t)(off + j)] = (int)(N + C.pos[(size_t)(e - ni)]);
-            } else {
-                C.ext[(size_t)(off + j)] = rs[(size_t)(off + j)] = (int)(soff + e);
-            }
-        }
-    }
-    for (int64_t t = 0; t < m; ++t) rp[(size_t)t] = (int)(N + C.pos[(size_t)t]);
+    ck_host_sim_ext(c->n_procs, h->n, mq, c->n0p, c->Npad, c->perm[0].data(), c->n_procs == 2 ? c->perm[1].data() : nullptr, &ST);
+    C.pos = std::move(ST.pos);
+    C.ext = std::move(ST.ext);
     int* d_rs = nullptr;
     HIPCHK(tmp.get(&d_rs, (size_t)c->Npad * sizeof(int)));
-    HIPCHK(hipMemcpyAsync(d_rs, rs.data(), (size_t)c->Npad * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    // ---- the select pass; sets beyond the LDS limit are refused before any solve
+    HIPCHK(hipMemcpyAsync(d_rs, ST.rs.data(), (size_t)c->Npad * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    // ---- the select pass, once over the stacked sites (with cv = 0 the search does not look at the process); sets beyond the
+    // LDS limit are refused before any solve
+    std::vector<double> stacked;   // the pair form: both site sets behind each other
+    const double* pts = mq[1] == 0 ? pcs[0] : pcs[1];
+    if (mq[0] > 0 && mq[1] > 0) {
+        stacked.assign(pcs[0], pcs[0] + 2 * mq[0]);
+        stacked.insert(stacked.end(), pcs[1], pcs[1] + 2 * mq[1]);
+        pts = stacked.data();
+    }
     LocalPass& S = C.pass;
-    if (local_pass(c, tmp, i, pcoords, m, max_dist, 0, true, d_rs, rp.data(), nullptr, &S)) return -1;
+    if (local_pass(c, tmp, mq[0] > 0 ? 0 : 1, pts, m, max_dist, 0, true, d_rs, ST.rp.data(), nullptr, &S)) return -1;
     h->t_ms[110] = S.st.ms;
     const int kl = ck_local_lds_limit();
     int64_t n_over = 0;
@@ -4844,7 +4916,12 @@ static int local_sim_stages(ck_handle* h, const std::string& name, int i, const 
     HIPCHK(tmp.get(&O.mu, (size_t)m * 8));
     HIPCHK(tmp.get(&O.s2, (size_t)m * 8));
     HIPCHK(hipEventRecord(c->ev2, c->stream));
-    ck_launch_local_sim_weights(c->stream, S.prob, m, S.d_cnt, O);
+    for (int q = 0; q < 2; ++q) {   // one launch per process's sites: the kernel carries the process and its prior as uniforms
+        if (mq[q] == 0) continue;
+        const int64_t b = q == 0 ? 0 : mq[0];
+        const CkLocalSimOut Oq{O.n_data, O.gidx + b * kl, O.spos + b * kl, O.ns + b, O.w + b * kl, O.sw + b * kl, O.mu + b, O.s2 + b};
+        ck_launch_local_sim_weights(c->stream, local_problem_from(c, S.prob, b, q), mq[q], S.d_cnt + b, Oq);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->ev3, c->stream));
     C.ns.resize((size_t)m);
@@ -4861,15 +4938,9 @@ static int local_sim_stages(ck_handle* h, const std::string& name, int i, const 
     return 0;
 }
 
-extern "C" int ck_debug_simulate_local_weights(ck_handle* h, int i, const double* pcoords, int64_t m, const int64_t* rank_host,
-                                               double max_dist, int64_t* idx_host, double* w_host) {
-    CHKH(h);
-    timings_from(h, 110);
-    DevTemps tmp;
-    LocalSim C;
-    if (local_sim_stages(h, "ck_debug_simulate_local_weights", i, pcoords, m, rank_host, max_dist,
-                         pcoords && rank_host && idx_host && w_host ? nullptr : "pcoords_host / rank_host / idx_host / w_host", 1, tmp, &C))
-        return -1;
+// the weights of every stacked site behind local_sim_stages: members as stacked caller indices, ascending
+static int local_sim_weights_out(ck_handle* h, const LocalSim& C, int64_t* idx_host, double* w_host) {
+    const int64_t m = C.m;
     const int kl = ck_local_lds_limit();
     std::vector<int> gi((size_t)(m * kl));
     std::vector<double> w((size_t)(m * kl));
@@ -4889,27 +4960,75 @@ extern "C" int ck_debug_simulate_local_weights(ck_handle* h, int i, const double
     }
     return 0;
 }
+// the sites of one process as the stacked sites of both
+struct SimSites {
+    const double* pcs[2] = {nullptr, nullptr};
+    int64_t mq[2] = {0, 0};
+    SimSites(int i, const double* pcoords, int64_t m) {
+        pcs[i == 1 ? 1 : 0] = pcoords;
+        mq[i == 1 ? 1 : 0] = m;
+    }
+    SimSites(const double* pc0, int64_t m0, const double* pc1, int64_t m1) {
+        pcs[0] = pc0, pcs[1] = pc1;
+        mq[0] = m0, mq[1] = m1;
+    }
+};
+// the pair forms' own refusals, in front of local_sim_stages'
+static int local_sim_pair_admit(const std::string& name, const SimSites& X) {
+    if (X.mq[0] < 0 || X.mq[1] < 0)
+        return fail(name + ": m0 = " + std::to_string(X.mq[0]) + ", m1 = " + std::to_string(X.mq[1]) + "; both must be >= 0");
+    if ((X.mq[0] > 0 && !X.pcs[0]) || (X.mq[1] > 0 && !X.pcs[1])) return fail(name + ": null pcoords0_host / pcoords1_host");
+    return 0;
+}
 
-extern "C" int ck_simulate_local(ck_handle* h, int i, const double* pcoords, int64_t m, const int64_t* rank_host, double max_dist,
-                                 int64_t n_draws, uint64_t seed, const double* noise_host, double* draws_host, double* mean_host,
-                                 double* var_host, int32_t* count_host, int64_t* stats4, int64_t* info) {
+extern "C" int ck_debug_simulate_local_weights(ck_handle* h, int i, const double* pcoords, int64_t m, const int64_t* rank_host,
+                                               double max_dist, int64_t* idx_host, double* w_host) {
     CHKH(h);
+    timings_from(h, 110);
+    DevTemps tmp;
+    LocalSim C;
+    const SimSites X(i, pcoords, m);
+    if (local_sim_stages(h, "ck_debug_simulate_local_weights", i, false, X.pcs, X.mq, rank_host, max_dist,
+                         pcoords && rank_host && idx_host && w_host ? nullptr : "pcoords_host / rank_host / idx_host / w_host", 1, tmp, &C))
+        return -1;
+    return local_sim_weights_out(h, C, idx_host, w_host);
+}
+
+extern "C" int ck_debug_simulate_local_pair_weights(ck_handle* h, const double* pcoords0, int64_t m0, const double* pcoords1,
+                                                    int64_t m1, const int64_t* rank_host, double max_dist, int64_t* idx_host,
+                                                    double* w_host) {
+    CHKH(h);
+    const std::string name = "ck_debug_simulate_local_pair_weights";
+    const SimSites X(pcoords0, m0, pcoords1, m1);
+    if (local_sim_pair_admit(name, X)) return -1;
+    timings_from(h, 110);
+    DevTemps tmp;
+    LocalSim C;
+    if (local_sim_stages(h, name, 0, true, X.pcs, X.mq, rank_host, max_dist,
+                         rank_host && idx_host && w_host ? nullptr : "rank_host / idx_host / w_host", 1, tmp, &C))
+        return -1;
+    return local_sim_weights_out(h, C, idx_host, w_host);
+}
+
+// Both simulation calls (name) behind their refusals: the stages above, the levels, the recursion chunk by chunk, the per-site
+// outputs.  pair: count_host has four columns (the earlier sites split by process), else three.
+static int simulate_local_impl(ck_handle* h, const std::string& name, int i, bool pair, const SimSites& X, const char* null_args,
+                               const int64_t* rank_host, double max_dist, int64_t n_draws, uint64_t seed, const double* noise_host,
+                               double* draws_host, double* mean_host, double* var_host, int32_t* count_host, int64_t* stats4,
+                               int64_t* info) {
     const auto t_begin = std::chrono::steady_clock::now();
     timings_from(h, 110);
     DevTemps tmp;
     LocalSim C;
-    if (local_sim_stages(h, "ck_simulate_local", i, pcoords, m, rank_host, max_dist,
-                         pcoords && rank_host && draws_host && stats4 && info ? nullptr
-                                                                              : "pcoords_host / rank_host / draws_host / stats4 / info",
-                         n_draws, tmp, &C))
-        return -1;
+    if (local_sim_stages(h, name, i, pair, X.pcs, X.mq, rank_host, max_dist, null_args, n_draws, tmp, &C)) return -1;
+    const int64_t m = C.m;
     const int kl = ck_local_lds_limit();
     // ---- the levels of the recursion
     const auto t_plan = std::chrono::steady_clock::now();
     CkSimLevels lv;
     const int64_t n_levels = ck_host_sim_levels(m, kl, C.pos.data(), C.ns.data(), C.spos.data(), &lv);
     if (n_levels < 0)
-        return fail("ck_simulate_local: site " + std::to_string(lv.off[0]) + " conditions on position " + std::to_string(lv.off[1]) +
+        return fail(name + ": site " + std::to_string(lv.off[0]) + " conditions on position " + std::to_string(lv.off[1]) +
                     ", which is not earlier than its own");
     h->t_ms[112] = ms_since(t_plan);
     int64_t first_bad = 0, n_site_nbr = 0;
@@ -4925,7 +5044,7 @@ extern "C" int ck_simulate_local(ck_handle* h, int i, const double* pcoords, int
         if (local_sim_free(h, C.w_bytes, &fr)) return -1;
         const int64_t need = 2 * per_draw + 2 * m * (int64_t)sizeof(int);
         if ((size_t)need > fr)
-            return fail("ck_simulate_local: needs " + std::to_string(need) + " bytes of device memory for a chunk of 2 draws at " +
+            return fail(name + ": needs " + std::to_string(need) + " bytes of device memory for a chunk of 2 draws at " +
                         std::to_string(m) + " sites; " + std::to_string(fr) + " bytes are available");
         if (chunk <= 0) chunk = std::min<int64_t>((int64_t)(fr / 2) / per_draw, 8192);
     }
@@ -4970,13 +5089,25 @@ extern "C" int ck_simulate_local(ck_handle* h, int i, const double* pcoords, int
     // ---- the per-site outputs
     if (mean_host) memcpy(mean_host, C.mu.data(), (size_t)m * 8);
     if (var_host) memcpy(var_host, C.s2.data(), (size_t)m * 8);
-    if (count_host)
+    if (count_host) {
+        std::vector<char> proc_at((size_t)m);   // by position: the process of the site there
+        for (int64_t t = 0; t < m; ++t) proc_at[(size_t)C.pos[(size_t)t]] = t >= C.mq[0];
         for (int64_t t = 0; t < m; ++t) {
-            const int nst = C.ns[(size_t)t];
-            count_host[3 * t] = C.pass.sel[(size_t)(4 * t)] - (i == 0 ? nst : 0);
-            count_host[3 * t + 1] = C.pass.sel[(size_t)(4 * t + 1)] - (i == 1 ? nst : 0);
-            count_host[3 * t + 2] = nst;
+            int nsq[2] = {0, 0};   // the earlier sites of the set by process
+            for (int a = 0; a < C.ns[(size_t)t]; ++a) ++nsq[(int)proc_at[(size_t)C.spos[(size_t)(t * kl + a)]]];
+            const int d0n = C.pass.sel[(size_t)(4 * t)] - nsq[0], d1n = C.pass.sel[(size_t)(4 * t + 1)] - nsq[1];
+            if (pair) {
+                count_host[4 * t] = d0n;
+                count_host[4 * t + 1] = d1n;
+                count_host[4 * t + 2] = nsq[0];
+                count_host[4 * t + 3] = nsq[1];
+            } else {
+                count_host[3 * t] = d0n;
+                count_host[3 * t + 1] = d1n;
+                count_host[3 * t + 2] = nsq[0] + nsq[1];
+            }
         }
+    }
     stats4[0] = C.n_empty;
     stats4[1] = C.k_max;
     stats4[2] = C.pass.st.n_capped;
@@ -4987,6 +5118,29 @@ extern "C" int ck_simulate_local(ck_handle* h, int i, const double* pcoords, int
     h->t_ms[116] = (double)n_levels;
     h->t_ms[117] = (double)n_site_nbr;
     return 0;
+}
+
+extern "C" int ck_simulate_local(ck_handle* h, int i, const double* pcoords, int64_t m, const int64_t* rank_host, double max_dist,
+                                 int64_t n_draws, uint64_t seed, const double* noise_host, double* draws_host, double* mean_host,
+                                 double* var_host, int32_t* count_host, int64_t* stats4, int64_t* info) {
+    CHKH(h);
+    return simulate_local_impl(h, "ck_simulate_local", i, false, SimSites(i, pcoords, m),
+                               pcoords && rank_host && draws_host && stats4 && info ? nullptr
+                                                                                    : "pcoords_host / rank_host / draws_host / stats4 / info",
+                               rank_host, max_dist, n_draws, seed, noise_host, draws_host, mean_host, var_host, count_host, stats4, info);
+}
+
+// Sequential Gaussian co-simulation: ck_simulate_local with the sites of both processes stacked behind the data (include/cokrige.h)
+extern "C" int ck_simulate_local_pair(ck_handle* h, const double* pcoords0, int64_t m0, const double* pcoords1, int64_t m1,
+                                      const int64_t* rank_host, double max_dist, int64_t n_draws, uint64_t seed,
+                                      const double* noise_host, double* draws_host, double* mean_host, double* var_host,
+                                      int32_t* count_host, int64_t* stats4, int64_t* info) {
+    CHKH(h);
+    const std::string name = "ck_simulate_local_pair";
+    const SimSites X(pcoords0, m0, pcoords1, m1);
+    if (local_sim_pair_admit(name, X)) return -1;
+    return simulate_local_impl(h, name, 0, true, X, rank_host && draws_host && stats4 && info ? nullptr : "rank_host / draws_host / stats4 / info",
+                               rank_host, max_dist, n_draws, seed, noise_host, draws_host, mean_host, var_host, count_host, stats4, info);
 }
 
 // ---------------------------------------------------------------------------------------

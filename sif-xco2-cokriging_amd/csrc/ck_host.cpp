@@ -821,6 +821,10 @@ void ck_host_local_needs(const int* cnt, int64_t m, int lds_limit, int k_hi, int
     std::sort(out->tiled.begin(), out->tiled.end(), [&](int64_t a, int64_t b) { return cnt[a] != cnt[b] ? cnt[a] > cnt[b] : a < b; });
 }
 
+void ck_host_local_pair_needs(const int* cnt, int64_t m, int lds_limit, int tile_min, CkLocalNeeds* out) {
+    ck_host_local_needs(cnt, m, lds_limit, std::min(tile_min, lds_limit), CK_LOCAL_PAIR_ROWS - 2, out);
+}
+
 // elements 0 .. n - 1 in order into batches under the budget: place(e, offset inside its batch); *largest is raised to the
 // largest batch sum
 template <class Need, class Place>
@@ -1081,6 +1085,45 @@ int ck_host_vecchia_order(const int64_t* rank, int n_procs, const int64_t n[2], 
         }
     }
     return 0;
+}
+
+// ---- conditional simulation in the moving neighbourhood: the stacked sites on the augmented set (ck_host.h) ---------------
+int ck_host_sim_order(const int64_t* rank, const int64_t m[2], CkSimSites* out) {
+    *out = CkSimSites();
+    const int64_t mt = m[0] + m[1];
+    std::vector<int64_t> ident((size_t)std::max(m[0], m[1]));
+    for (size_t t = 0; t < ident.size(); ++t) ident[t] = (int64_t)t;
+    CkVecchiaOrder ord;   // the sites as the "data" of an ordering: process 0's, then process 1's
+    if (ck_host_vecchia_order(rank, 2, m, m[0], mt, ident.data(), ident.data(), &ord)) {
+        out->dup[0] = ord.dup[0];
+        out->dup[1] = ord.dup[1];
+        return -1;
+    }
+    out->pos = std::move(ord.pos);
+    return 0;
+}
+
+void ck_host_sim_ext(int n_procs, const int64_t n[2], const int64_t m[2], int64_t n0p, int64_t npad, const int64_t* perm0,
+                     const int64_t* perm1, CkSimSites* out) {
+    const int64_t N = n[0] + (n_procs == 2 ? n[1] : 0), mt = m[0] + m[1];
+    out->ext.assign((size_t)npad, -1);
+    out->rs.assign((size_t)npad, INT32_MAX);
+    out->rp.resize((size_t)mt);
+    for (int k = 0; k < n_procs; ++k) {
+        const int64_t off = k == 0 ? 0 : n0p, soff = k == 0 ? 0 : n[0], moff = k == 0 ? 0 : m[0];
+        const int64_t* perm = k == 0 ? perm0 : perm1;
+        for (int64_t j = 0; j < n[k] + m[k]; ++j) {
+            const int64_t e = perm[j];
+            if (e >= n[k]) {
+                const int64_t s = moff + (e - n[k]);
+                out->ext[(size_t)(off + j)] = (int)(N + s);
+                out->rs[(size_t)(off + j)] = (int)(N + out->pos[(size_t)s]);
+            } else {
+                out->ext[(size_t)(off + j)] = out->rs[(size_t)(off + j)] = (int)(soff + e);
+            }
+        }
+    }
+    for (int64_t t = 0; t < mt; ++t) out->rp[(size_t)t] = (int)(N + out->pos[(size_t)t]);
 }
 
 // ---- conditional simulation in the moving neighbourhood: the levels of the recursion -------------------------------------

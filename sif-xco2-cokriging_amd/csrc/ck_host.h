@@ -212,6 +212,12 @@ struct CkLocalPlan {
     long long slab_doubles = 0;
 };
 CK_HIDDEN void ck_host_local_plan(const int* cnt, const CkLocalNeeds& nd, long long budget, int trend, CkLocalPlan* out);
+// ck_predict_local_pair: the c rows of both processes and z ride along every system, three extra rows.  Step (a) for them: two
+// classes only -- k <= lds_limit in LDS ((k + 3) x k doubles), everything larger tiled with kq = roundup(k + 3, 64) rows, whatever
+// tile_min says (the pair form has no slab kernel; tile_min below lds_limit lowers the LDS class's bound as in the universal
+// form).  Step (b) is ck_host_local_plan with trend = CK_LOCAL_PAIR_ROWS - 2: batches and the slab budget count the third row.
+#define CK_LOCAL_PAIR_ROWS 3
+CK_HIDDEN void ck_host_local_pair_needs(const int* cnt, int64_t m, int lds_limit, int tile_min, CkLocalNeeds* out);
 
 // ---- the dense predictors' host arithmetic (ck_api.hip: ck_predict_universal, ck_predict_blocks, ck_conditional_draws) --------
 // The standard error behind a variance: a negative variance gives NaN and then 0.0 (np.nan_to_num; the device's k_reduce_pred
@@ -396,6 +402,26 @@ struct CkLocalCvPlan {
 CK_HIDDEN int ck_host_local_cv_plan(const char* name, int i, int n_procs, const int64_t n[2], int64_t n0p, const int64_t* perm0,
                                     const int64_t* perm1, const int32_t* fold0, const int32_t* fold1, int32_t n_folds, bool buffer_i,
                                     CkLocalCvPlan* out);
+
+// ---- conditional simulation in the moving neighbourhood: the stacked sites of both processes on the augmented set ----------
+// Pure index work, no device (ck_api.hip: ck_simulate_local, ck_simulate_local_pair).  The augmented set holds, per process q,
+// its n[q] data and behind them its m[q] sites; the STACKED index of site k of process 0 is k, of site k of process 1 m[0] + k
+// (ck_conditional_draws_pair's).  rank: m[0] + m[1] distinct integers in stacked order; the sites are ordered by rank across
+// both processes, every datum precedes every site.  perm_q / n0p / npad: the augmented set's layout as in ck_host_vecchia_order
+// (perm_q[j] = the augmented caller index, within process q, of the site at internal position j).
+//   pos   m[0] + m[1]: every stacked site's position in the ordering
+//   ext   npad: internal index -> the caller's stacked index, a datum its stacked datum index < N, a site N + its stacked
+//         index; -1 in the padding
+//   rs    npad: internal index -> precedence, a datum its stacked index, a site N + its position; INT32_MAX in the padding
+//   rp    m[0] + m[1]: N + pos, the points' own precedence
+// 0, or -1 with two stacked sites of equal rank in out->dup (the earlier first; the caller words the refusal).
+struct CkSimSites {
+    std::vector<int> pos, ext, rs, rp;
+    int64_t dup[2] = {0, 0};
+};
+CK_HIDDEN int ck_host_sim_order(const int64_t* rank, const int64_t m[2], CkSimSites* out);
+CK_HIDDEN void ck_host_sim_ext(int n_procs, const int64_t n[2], const int64_t m[2], int64_t n0p, int64_t npad, const int64_t* perm0,
+                               const int64_t* perm1, CkSimSites* out /* pos set */);
 
 // ---- conditional simulation in the moving neighbourhood: the levels of the recursion (ck_api.hip: ck_simulate_local) --------
 // Pure index work, no device.  Site t (the caller's index) sits at position pos[t] of the ordering (a permutation of 0 .. m - 1)

@@ -492,8 +492,9 @@ void ck_launch_vecchia_residual(hipStream_t s, int64_t npad, int p, const double
 //   idx   k ints (neighbour list)
 // CkLocalSys, CK_LT_ROWS, CK_LT_NINV and the sizes ck_local_tiled_kq / ck_local_tiled_doubles: ck_host.h (the host plans with them)
 #define CK_LT_BIG 1e200
+// pair: the three rows of ck_predict_local_pair behind the padding (kq = roundup(k + 3, 64)) in place of c and z
 void ck_launch_local_assemble_t(hipStream_t s, const CkLocalProblem& P, const CkLocalSys* sys, int n_sys, double* slab,
-                                int* k0buf /* n_sys ints: the process-0 neighbour counts */);
+                                int* k0buf /* n_sys ints: the process-0 neighbour counts */, bool pair = false);
 // Columns are processed in groups of g 64-column blocks [g0, g0 + 64 g): block i of a group first receives the
 // updates of the group's earlier blocks (one pass, K = 64 i), then its diagonal block is factored and inverted and
 // the rows below are solved; the trailing matrix behind the group is updated once with K = 64 g (a g-th of the
@@ -548,6 +549,20 @@ void ck_launch_local_reduce_ut(hipStream_t s, const CkLocalSys* sys, int n_sys, 
 // writes cbar where P.bo is set; the reductions take P.sbb.
 void ck_launch_local_solve_b(hipStream_t s, const CkLocalProblem& P, int64_t r, const int* counts, int k_hi, CkLocalTrend Tr,
                              double* pred, double* err, double* beta, int* status);
+
+// Both processes at every point from one local system (ck_predict_local_pair; include/cokrige.h has the definition).  The c rows of
+// process 0 and 1 and z ride along one factorisation: LDS class k_local_solve_pair, a (k + 3) x k matrix; tiled class kq =
+// roundup(k + 3, 64) with the rows kq - 3, kq - 2, kq - 1 (ck_launch_local_assemble_t with pair, the factorisation steps
+// unchanged, ck_launch_local_reduce_pair_t).  Outputs per point: lp_write's of either process and cov = c01 - v0 . v1.
+struct CkLocalPairOut {
+    double *pred0, *err0, *pred1, *err1, *cov;   // m doubles each
+    double c0var[2];                              // sigma_q^2 + nugget_q
+    double c01;                                   // C_01(0), no nugget
+};
+void ck_launch_local_solve_pair(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, int k_hi,
+                                const CkLocalPairOut& O);
+void ck_launch_local_reduce_pair_t(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab, const long long* info,
+                                   const CkLocalPairOut& O);
 
 // Conditional simulation in the moving neighbourhood (ck_simulate_local; include/cokrige.h has the definition).  The sites are
 // the points of a pass over the AUGMENTED data set (the data, then the sites as noise-free pseudo-data of process i_pred), with

@@ -33,6 +33,9 @@
 //                       k_local_reduce_ut behind the tiled path
 //   k_local_solve_b     block cokriging, k <= LP_KL: k_local_solve_u's calls around the block's centre with lp_cbar_z_rows for
 //                       lp_cz_rows (cbar = the members' weighted covariances, lp_cbar_part);  tiled: k_local_search_t<true>
+//   k_local_solve_pair  both processes at a point (ck_predict_local_pair), k <= LP_KL: k_local_solve's calls with lp_cz_rows_pair
+//                       for lp_cz_rows, lp_chol(3), lp_write_pair (three lp_dots);  tiled: k_local_search_t<false, true> /
+//                       k_local_reduce_pair_t
 //   k_vecchia_terms / k_vecchia_sum            vt_tree
 //   k_vecchia_grad      k_local_solve's calls, then back substitution and the contraction (ck_vecchia_grad.h)
 //   k_vecchia_grad_part / k_vecchia_grad_sum   vg_tree
@@ -211,11 +214,15 @@ __device__ __forceinline__ double lp_cov(const CkLocalProblem& P, int bidx, int 
     return lp_exact_xyz(&P.blk[bidx], P.metric, nug, a0, a1, a2, b0, b1, b2);
 }
 
-// the point's covariance with site ga (point_prediction.py:115-125)
-__device__ __forceinline__ double lp_c_entry(const CkLocalProblem& P, const LpPoint& X, long ga) {
+// the point's covariance, as process ip, with site ga (point_prediction.py:115-125)
+__device__ __forceinline__ double lp_c_entry_of(const CkLocalProblem& P, const LpPoint& X, long ga, int ip) {
     const int pa = ga >= P.L.n0p;
-    return lp_cov(P, P.i_pred + pa, pa == P.i_pred, X.p0, X.p1, X.p2, X.q0, X.q1, X.q2, X.s0[ga], X.s1[ga], X.s2[ga], X.u0[ga],
-                  X.u1[ga], X.u2[ga]);
+    return lp_cov(P, ip + pa, pa == ip, X.p0, X.p1, X.p2, X.q0, X.q1, X.q2, X.s0[ga], X.s1[ga], X.s2[ga], X.u0[ga], X.u1[ga],
+                  X.u2[ga]);
+}
+// as the call's predicted process
+__device__ __forceinline__ double lp_c_entry(const CkLocalProblem& P, const LpPoint& X, long ga) {
+    return lp_c_entry_of(P, X, ga, P.i_pred);
 }
 
 // Block cokriging: the members [a0, a1) of a block (P.mc / P.mu / P.bw) against site ga, summed in the members' order:
@@ -279,6 +286,16 @@ __device__ __forceinline__ void lp_cz_rows(const CkLocalProblem& P, const LpPoin
         const long ga = idx[a];
         S[(long)k * ld + a] = lp_c_entry(P, X, ga);
         S[(long)(k + 1) * ld + a] = P.z[ga];
+    }
+}
+
+// the pair form (ck_predict_local_pair): rows k (c as process 0), k + 1 (c as process 1) and k + 2 (z) of S
+__device__ __forceinline__ void lp_cz_rows_pair(const CkLocalProblem& P, const LpPoint& X, const int* idx, double* S, long ld, int k) {
+    for (int a = threadIdx.x; a < k; a += LP_TPB) {
+        const long ga = idx[a];
+        S[(long)k * ld + a] = lp_c_entry_of(P, X, ga, 0);
+        S[(long)(k + 1) * ld + a] = lp_c_entry_of(P, X, ga, 1);
+        S[(long)(k + 2) * ld + a] = P.z[ga];
     }
 }
 
@@ -360,6 +377,30 @@ __device__ __forceinline__ void lp_write(long p, double vy, double vv, double c0
 __device__ __forceinline__ void lp_write_nan(long p, double* pred, double* err) {
     pred[p] = NAN;
     err[p] = NAN;
+}
+
+// The pair form's outputs (ck_predict_local_pair) from the solved rows v0, v1, y: three calls of lp_dots -- (v0, y), (v1, y),
+// (v0, v1) -- on its one tree, a barrier between them (a thread may still be reading the last call's root), so pred_q and
+// v_q . v_q are the single calls' bits; then one thread writes lp_write's outputs of both processes and C_01(0) - v0 . v1.
+// An empty neighbourhood or a system that is not positive definite: lp_write_pair_nan.
+__device__ __forceinline__ void lp_write_pair(const CkLocalPairOut& O, long p, const double* v0, const double* v1, const double* y,
+                                              int k) {
+    double vy0, vv0, vy1, vv1, v01, unused;
+    lp_dots(v0, y, k, &vy0, &vv0);
+    __syncthreads();
+    lp_dots(v1, y, k, &vy1, &vv1);
+    __syncthreads();
+    lp_dots(v0, v1, k, &v01, &unused);
+    if (threadIdx.x == 0) {
+        lp_write(p, vy0, vv0, O.c0var[0], O.pred0, O.err0, nullptr);
+        lp_write(p, vy1, vv1, O.c0var[1], O.pred1, O.err1, nullptr);
+        O.cov[p] = O.c01 - v01;
+    }
+}
+__device__ __forceinline__ void lp_write_pair_nan(const CkLocalPairOut& O, long p) {
+    lp_write_nan(p, O.pred0, O.err0);
+    lp_write_nan(p, O.pred1, O.err1);
+    O.cov[p] = NAN;
 }
 
 __global__ __launch_bounds__(LP_TPB) void k_local_chunk_bounds(const double* __restrict__ su, CkLayout L, long nchunk,
@@ -736,6 +777,40 @@ void ck_launch_local_solve(hipStream_t s, const CkLocalProblem& P, int64_t p_bas
         k_local_solve_big<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(P, counts, slab_off, slab, p_base, k_hi, pred, err, vv);
 }
 
+// Both processes at a point from one local system (ck_predict_local_pair), k <= LP_KL: k_local_solve's steps with the c rows of
+// both processes riding along -- a (k + 3) x k matrix, 34 304 B of LDS, still four workgroups per CU.  With cv = 0 nothing in
+// the search, the triangle or the noise looks at the predicted process, so one list, one Sigma_loc and one Cholesky serve both.
+__global__ __launch_bounds__(LP_TPB) void k_local_solve_pair(CkLocalProblem P, const int* __restrict__ counts, int k_hi,
+                                                              CkLocalPairOut O) {
+    __shared__ double S[(LP_KL + 3) * LP_KL];
+    __shared__ int idx[LP_KL];
+    const int tid = threadIdx.x;
+    const long p = blockIdx.x;
+    const int k = counts[p];
+    if (k == 0) {
+        if (tid == 0) lp_write_pair_nan(O, p);
+        return;
+    }
+    if (k > LP_KL || k > k_hi) return;   // the tiled path
+    const long ld = LP_KL;
+    const LpPoint X = lp_point(P, p);
+    lp_compact<false, 0>(P, X, idx);           // 1. neighbour list
+    lp_triangle(P, X, idx, S, ld, k);          // 2. local covariance, both c rows, z row, noise
+    lp_cz_rows_pair(P, X, idx, S, ld, k);
+    lp_noise(P, idx, S, ld, k);
+    if (!lp_chol(S, ld, k, 3)) {               // 3. Cholesky, the three extra rows ride along
+        if (tid == 0) lp_write_pair_nan(O, p);
+        return;
+    }
+    lp_write_pair(O, p, S + (long)k * ld, S + (long)(k + 1) * ld, S + (long)(k + 2) * ld, k);   // 4. the five outputs
+}
+
+void ck_launch_local_solve_pair(hipStream_t s, const CkLocalProblem& P, int64_t m, const int* counts, int k_hi,
+                                const CkLocalPairOut& O) {
+    if (m <= 0) return;
+    k_local_solve_pair<<<dim3((unsigned)m), dim3(LP_TPB), 0, s>>>(P, counts, k_hi, O);
+}
+
 // ---------------------------------------------------------------------------------------
 // tiled path (ck_internal.h: CkLocalSys; the factorisation steps are in ck_la.hip)
 // ---------------------------------------------------------------------------------------
@@ -762,9 +837,12 @@ __device__ __noinline__ double lp_exact_pair(const CkMatern* m, int metric, int 
 #define LT_TPB 512   // 8 waves: with two workgroups per CU (LDS) four waves per SIMD hide the table-read latency
 // BLK (block cokriging): the point is the block's centre and the c row holds cbar, every entry the sum over all the block's
 // members in their order (lp_cbar_part)
-template <bool BLK>
+// PAIR (ck_predict_local_pair): three rows behind the identity padding -- kq - 3 (c as process 0), kq - 2 (c as process 1) and
+// kq - 1 (z), their corner diag(BIG, BIG, BIG); kq = roundup(k + 3, 64)
+template <bool BLK, bool PAIR>
 __global__ __launch_bounds__(LP_TPB) void k_local_search_t(CkLocalProblem P, const CkLocalSys* __restrict__ sys,
                                                             double* __restrict__ slab, int* __restrict__ k0out) {
+    constexpr int NX = PAIR ? 3 : 2;
     const int tid = threadIdx.x;
     const CkLocalSys q = sys[blockIdx.x];
     const int k = q.k, kq = q.kq;
@@ -776,20 +854,31 @@ __global__ __launch_bounds__(LP_TPB) void k_local_search_t(CkLocalProblem P, con
     lp_compact<true, 0>(P, X, idx, &k0);
     if (tid == 0) k0out[blockIdx.x] = k0;
     // zeros up to the end of each row's 4-column diagonal block (the 64 x 64 factorisation loads whole 4 x 4
-    // register blocks); rows [k, kq - 2): identity padding
+    // register blocks); rows [k, kq - NX): identity padding
     for (int a = tid; a < k; a += LP_TPB)
         for (int b = a + 1; b <= (a | 3); ++b) S[(long)a * ld + b] = 0.0;
-    for (int a = k; a < kq - 2; ++a)
+    for (int a = k; a < kq - NX; ++a)
         for (int b = tid; b <= (a | 3); b += LP_TPB) S[(long)a * ld + b] = (b == a) ? 1.0 : 0.0;
-    // rows kq - 2 (c) and kq - 1 (z): two more rows of the matrix, their own 2 x 2 corner diag(BIG, BIG)
+    // rows kq - 2 (c) and kq - 1 (z): two more rows of the matrix, their own 2 x 2 corner diag(BIG, BIG); PAIR: kq - 3 (c as
+    // process 0), kq - 2 (c as process 1), kq - 1 (z), a 3 x 3 corner
     for (int a = tid; a < kq; a += LP_TPB) {
-        double cv0 = 0.0, zv = 0.0;
+        double cv0 = 0.0, cv1 = 0.0, zv = 0.0;
         if (a < k) {
             const long ga = idx[a];
-            cv0 = BLK ? lp_cbar_part(P, X, ga, P.bo[q.p], P.bo[q.p + 1]) : lp_c_entry(P, X, ga);
+            if (PAIR) {
+                cv0 = lp_c_entry_of(P, X, ga, 0);
+                cv1 = lp_c_entry_of(P, X, ga, 1);
+            } else {
+                cv0 = BLK ? lp_cbar_part(P, X, ga, P.bo[q.p], P.bo[q.p + 1]) : lp_c_entry(P, X, ga);
+            }
             zv = P.z[ga];
         }
-        S[(long)(kq - 2) * ld + a] = a == kq - 2 ? CK_LT_BIG : cv0;
+        if (PAIR) {
+            S[(long)(kq - 3) * ld + a] = a == kq - 3 ? CK_LT_BIG : cv0;
+            S[(long)(kq - 2) * ld + a] = a == kq - 2 ? CK_LT_BIG : cv1;
+        } else {
+            S[(long)(kq - 2) * ld + a] = a == kq - 2 ? CK_LT_BIG : cv0;
+        }
         S[(long)(kq - 1) * ld + a] = a == kq - 1 ? CK_LT_BIG : zv;
     }
 }
@@ -951,13 +1040,27 @@ __global__ __launch_bounds__(LP_TPB) void k_local_reduce_t(const CkLocalSys* __r
     if (tid == 0) lp_write(q.p, vy, v2, sbb ? sbb[q.p] : c0var, pred, err, vv);
 }
 
+// the pair form: the five outputs from the three solved rows kq - 3 (v0), kq - 2 (v1), kq - 1 (y)
+__global__ __launch_bounds__(LP_TPB) void k_local_reduce_pair_t(const CkLocalSys* __restrict__ sys, const double* __restrict__ slab,
+                                                                 const long long* __restrict__ info, CkLocalPairOut O) {
+    const CkLocalSys q = sys[blockIdx.x];
+    if (info[blockIdx.x] != 0) {
+        if (threadIdx.x == 0) lp_write_pair_nan(O, q.p);
+        return;
+    }
+    const double* v0 = slab + q.off + (long)(q.kq - 3) * q.ld;
+    lp_write_pair(O, q.p, v0, v0 + q.ld, v0 + 2 * (long)q.ld, q.k);
+}
+
 void ck_launch_local_assemble_t(hipStream_t s, const CkLocalProblem& P, const CkLocalSys* sys, int n_sys, double* slab,
-                                int* k0buf) {
+                                int* k0buf, bool pair) {
     if (n_sys <= 0) return;
-    if (P.bo)
-        k_local_search_t<true><<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(P, sys, slab, k0buf);
+    if (pair)
+        k_local_search_t<false, true><<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(P, sys, slab, k0buf);
+    else if (P.bo)
+        k_local_search_t<true, false><<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(P, sys, slab, k0buf);
     else
-        k_local_search_t<false><<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(P, sys, slab, k0buf);
+        k_local_search_t<false, false><<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(P, sys, slab, k0buf);
     const LpTab T{P.tabs, P.coefs, P.use_tab};
     const int nreg = P.L.nend > P.L.n0p ? 3 : 1;           // a second process?
     const int grid = n_sys < 512 ? n_sys : 512;            // two workgroups per CU; they walk over the systems
@@ -970,6 +1073,12 @@ void ck_launch_local_reduce_t(hipStream_t s, const CkLocalSys* sys, int n_sys, c
                               const long long* info, double c0var, double* pred, double* err, double* vv, const double* sbb) {
     if (n_sys <= 0) return;
     k_local_reduce_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(sys, slab, info, c0var, pred, err, vv, sbb);
+}
+
+void ck_launch_local_reduce_pair_t(hipStream_t s, const CkLocalSys* sys, int n_sys, const double* slab, const long long* info,
+                                   const CkLocalPairOut& O) {
+    if (n_sys <= 0) return;
+    k_local_reduce_pair_t<<<dim3((unsigned)n_sys), dim3(LP_TPB), 0, s>>>(sys, slab, info, O);
 }
 
 int ck_local_lds_limit() { return LP_KL; }

@@ -468,6 +468,12 @@ class Predictor:
         f0 = self._sites_frame(pcoords)
         f1 = f0 if pcoords1 is None else self._sites_frame(pcoords1)
         p0, e0, p1, e1, cov = self.predict_pair_arrays(f0.values[:, :2], None if pcoords1 is None else f1.values[:, :2], pairs)
+        return self._pair_output(f0, None if pcoords1 is None else f1, p0, e0, p1, e1, cov, pairs, postprocess)
+
+    def _pair_output(self, f0, f1, p0, e0, p1, e1, cov, pairs, postprocess):
+        """What ``predict_pair`` returns from the arrays of both processes at the site frames f0 / f1 (f1 None: the same
+        sites); shared with the local predictor's ``predict_pair``."""
+        pcoords1 = f1
         scale = [self.mf.fields[k].ds.attrs["scale_fact"] for k in range(2)] if postprocess else [1.0, 1.0]
         if cov is not None:
             cov = cov * (scale[0] * scale[1])

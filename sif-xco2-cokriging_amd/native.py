@@ -96,11 +96,17 @@ _PROTOS = {
     "ck_debug_vecchia_trend": [c_void_p, POINTER(c_int64), c_double, _dp, _dp, _dp],
     "ck_predict_local_universal": [c_void_p, c_int, _dp, c_int64, _dp, c_double, c_int, _dp, _dp, _dp, POINTER(c_int64),
                                    POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
+    "ck_predict_local_pair": [c_void_p, _dp, c_int64, c_double, _dp, _dp, _dp, _dp, _dp, POINTER(c_int64), POINTER(c_int64),
+                              POINTER(c_int64)],
     "ck_predict_local_blocks": [c_void_p, c_int, _dp, c_int32, _dp, c_int64, POINTER(c_int32), _dp, _dp, c_double, _dp, _dp, _dp,
                                 POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)],
     "ck_simulate_local": [c_void_p, c_int, _dp, c_int64, POINTER(c_int64), c_double, c_int64, c_uint64, _dp, _dp, _dp, _dp,
                           POINTER(c_int32), POINTER(c_int64), POINTER(c_int64)],
     "ck_debug_simulate_local_weights": [c_void_p, c_int, _dp, c_int64, POINTER(c_int64), c_double, POINTER(c_int64), _dp],
+    "ck_simulate_local_pair": [c_void_p, _dp, c_int64, _dp, c_int64, POINTER(c_int64), c_double, c_int64, c_uint64, _dp, _dp, _dp,
+                               _dp, POINTER(c_int32), POINTER(c_int64), POINTER(c_int64)],
+    "ck_debug_simulate_local_pair_weights": [c_void_p, _dp, c_int64, _dp, c_int64, POINTER(c_int64), c_double, POINTER(c_int64),
+                                             _dp],
     "ck_vario_begin": [c_void_p, _dp, _dp, c_int64, _dp, _dp, c_int64, c_int],
     "ck_vario_extent": [c_void_p, c_double, _dp, _dp, POINTER(c_int64)],
     "ck_vario_bin": [c_void_p, c_double, _dp, c_int, c_int, _dp, POINTER(c_int64)],
@@ -765,6 +771,26 @@ class Handle:
         keys = ["count_ms", "lds_ms", "tiled_ms", "prior_ms", "total_ms", "cbar_evals"]
         return dict(zip(keys, out[104:110].tolist()))
 
+    def predict_local_pair(self, pcoords, max_dist=1e3):
+        """Both processes at every site from one local system (include/cokrige.h: ck_predict_local_pair): the neighbourhood,
+        the local Sigma and its Cholesky are predict_local's (cv off) and serve both processes.  Returns (pred0, err0, pred1,
+        err1, cov, info): cov the covariance of the two prediction errors at each site, info with n_empty, n_not_pd, k_max.
+        pred / err carry the bits of predict_local(0) and predict_local(1).  No covariance between sites exists here."""
+        pc = _f64(pcoords, 2)
+        m = pc.shape[0]
+        out = [np.empty(m) for _ in range(5)]
+        ne, npd, km = c_int64(0), c_int64(0), c_int64(0)
+        _chk(lib().ck_predict_local_pair(self._h, _p(pc), m, float(max_dist), *[_p(o) for o in out], byref(ne), byref(npd),
+                                         byref(km)))
+        return (*out, dict(n_empty=ne.value, n_not_pd=npd.value, k_max=km.value))
+
+    def local_pair_timings(self):
+        """ck_timings [138 ..] of the last predict_local_pair() call (milliseconds; the last two are counts)."""
+        out = np.zeros(143)
+        _chk(lib().ck_timings(self._h, _p(out), 143))
+        keys = ["pass_ms", "solve_ms", "grow_ms", "n_tiled", "n_tiled_batches"]
+        return dict(zip(keys, out[138:143].tolist()))
+
     def simulate_local(self, i, pcoords, rank, max_dist, n_draws, seed=0, noise=None, terms=True):
         """Draws of process i at pcoords by sequential simulation in the moving neighbourhood (include/cokrige.h:
         ck_simulate_local): site t is conditioned on the data and on the sites of smaller ``rank`` (m distinct integers) within
@@ -811,6 +837,55 @@ class Handle:
         idx, w = np.full((m, 64), -1, dtype=np.int64), np.zeros((m, 64))
         _chk(lib().ck_debug_simulate_local_weights(self._h, int(i), _p(pc), m, r.ctypes.data_as(POINTER(c_int64)), float(max_dist),
                                                    idx.ctypes.data_as(POINTER(c_int64)), _p(w)))
+        return idx, w
+
+    def simulate_local_pair(self, pcoords0, pcoords1, rank, max_dist, n_draws, seed=0, noise=None, terms=True):
+        """Sequential co-simulation of both processes in the moving neighbourhood (include/cokrige.h: ck_simulate_local_pair):
+        process 0 at pcoords0 (m0 sites), process 1 at pcoords1 (m1), stacked -- index k for site k of process 0, m0 + k for
+        site k of process 1.  ``rank``: m0 + m1 distinct integers over the stacked sites; a stacked site is conditioned on the
+        data and on the stacked sites of smaller rank, of either process, within ``max_dist`` and under the caps.  ``noise``:
+        (n_draws, m0 + m1), process 0's columns first.  Returns (draws (n_draws, m0 + m1), info, stats) as simulate_local;
+        count has four columns (data of process 0, of process 1, earlier sites of process 0, of process 1)."""
+        pc0, pc1 = _f64(np.zeros((0, 2)) if pcoords0 is None else pcoords0, 2), _f64(np.zeros((0, 2)) if pcoords1 is None else pcoords1, 2)
+        m0, m1 = pc0.shape[0], pc1.shape[0]
+        m = m0 + m1
+        r = np.ascontiguousarray(rank, dtype=np.int64).reshape(-1)
+        if r.size != m:
+            raise ValueError(f"rank has {r.size} entries, the two site sets {m} sites")
+        n_draws = int(n_draws)
+        e = None
+        if noise is not None:
+            e = _f64(noise)
+            if e.shape != (n_draws, m):
+                raise ValueError(f"noise has shape {e.shape}, expected {(n_draws, m)}")
+        draws = np.zeros((max(n_draws, 0), m))
+        mean = np.empty(m) if terms else None
+        var = np.empty(m) if terms else None
+        count = np.zeros((m, 4), dtype=np.int32) if terms else None
+        st, info = np.zeros(4, dtype=np.int64), c_int64(0)
+        _chk(lib().ck_simulate_local_pair(self._h, _p(pc0) if m0 else None, m0, _p(pc1) if m1 else None, m1,
+                                          r.ctypes.data_as(POINTER(c_int64)), float(max_dist), n_draws,
+                                          c_uint64(int(seed) & (2 ** 64 - 1)), _p(e) if e is not None else None, _p(draws),
+                                          _p(mean) if terms else None, _p(var) if terms else None,
+                                          count.ctypes.data_as(POINTER(c_int32)) if terms else None,
+                                          st.ctypes.data_as(POINTER(c_int64)), byref(info)))
+        stats = dict(n_empty=int(st[0]), k_max=int(st[1]), n_capped=int(st[2]), n_levels=int(st[3]))
+        if terms:
+            stats.update(mean=mean, var=var, count=count)
+        return draws, info.value, stats
+
+    def simulate_local_pair_weights(self, pcoords0, pcoords1, rank, max_dist):
+        """(idx, w), both (m0 + m1, 64): simulate_local_weights for the stacked sites of both processes -- a site is N + its
+        stacked index (include/cokrige.h: ck_debug_simulate_local_pair_weights)."""
+        pc0, pc1 = _f64(np.zeros((0, 2)) if pcoords0 is None else pcoords0, 2), _f64(np.zeros((0, 2)) if pcoords1 is None else pcoords1, 2)
+        m0, m1 = pc0.shape[0], pc1.shape[0]
+        r = np.ascontiguousarray(rank, dtype=np.int64).reshape(-1)
+        if r.size != m0 + m1:
+            raise ValueError(f"rank has {r.size} entries, the two site sets {m0 + m1} sites")
+        idx, w = np.full((m0 + m1, 64), -1, dtype=np.int64), np.zeros((m0 + m1, 64))
+        _chk(lib().ck_debug_simulate_local_pair_weights(self._h, _p(pc0) if m0 else None, m0, _p(pc1) if m1 else None, m1,
+                                                        r.ctypes.data_as(POINTER(c_int64)), float(max_dist),
+                                                        idx.ctypes.data_as(POINTER(c_int64)), _p(w)))
         return idx, w
 
     def simulate_local_timings(self):

@@ -17,7 +17,9 @@ Differences from the reference, none in the arithmetic:
   * ``max_neighbours=`` (not in the reference): a nearest-neighbour cap per process inside ``max_dist``, so that the radius
     can be chosen for coverage of sparse regions instead of for cost;
   * ``predict_blocks`` (not in the reference): weighted means over blocks of sites with the standard error of the mean,
-    from the neighbourhood of each block's search centre; no covariance between blocks.
+    from the neighbourhood of each block's search centre; no covariance between blocks;
+  * ``predict_pair`` (not in the reference): both processes at every site from one local system, with the covariance of
+    their two prediction errors there; no covariance between sites.
 """
 from __future__ import annotations
 
@@ -214,6 +216,60 @@ class Predictor:
         except TypeError:
             return ds.assign_coords(coords={"time": np.datetime64(ts)})
 
+    # -- both processes at once ----------------------------------------------------------------------
+    def predict_pair_arrays(self, pcoords, max_dist: float = 1e3):
+        """Both processes at every site from ONE neighbourhood, local Sigma and Cholesky per site -- the numeric body of
+        ``predict_pair`` (include/cokrige.h: ck_predict_local_pair).  Returns (pred_0, pred_err_0, pred_1, pred_err_1, cov):
+        cov[t] the covariance of the two prediction errors at site t.  pred / pred_err carry the bits of ``predict_arrays``
+        (cross-validation off) for either process; ``info`` and the warnings are its.  Runs on one device: with several
+        ``devices=[...]`` it raises NotImplementedError, as ``predict_blocks`` does."""
+        if self.devices is not None and len(self.devices) > 1:
+            raise NotImplementedError(f"predict_pair runs on one device; this predictor has devices={self.devices}")
+        if self.trend is not None:
+            raise NotImplementedError("the joint prediction of both processes in the moving neighbourhood is simple cokriging "
+                                      "only (trend=None)")
+        if self.n_procs != 2:
+            raise ValueError(f"the joint prediction of both processes needs a model of two processes, not {self.n_procs}")
+        if isinstance(max_dist, bool) or not np.isfinite(max_dist) or max_dist < 0:
+            raise ValueError(f"max_dist must be finite and >= 0, got {max_dist!r}")
+        pc = np.atleast_2d(np.asarray(pcoords, dtype=np.float64))
+        if pc.ndim != 2 or pc.shape[1] < 2 or len(pc) < 1:
+            raise ValueError("pcoords must be [[lat, lon], ...] with at least one site")
+        h = self._capped_handle()
+        p0, e0, p1, e1, cov, info = h.predict_local_pair(np.ascontiguousarray(pc[:, :2]), max_dist=max_dist)
+        self.timings = h.local_pair_timings()
+        info["n_capped"] = int(h.timings()["local_n_capped"]) if self.max_neighbours is not None else 0
+        self.info = info
+        if info["n_empty"]:
+            warnings.warn(f"No data within maximum distance {max_dist} at {info['n_empty']} location(s).")
+        if info["n_not_pd"]:
+            warnings.warn(f"Local covariance matrix not positive definte at {info['n_not_pd']} location(s);"
+                          " returning NaN.")
+        return p0, e0, p1, e1, cov
+
+    def predict_pair(self, pcoords, max_dist: float = 1e3, postprocess: bool = True, pcoords1=None):
+        """Prediction and standard error of BOTH processes at ``pcoords`` with the covariance of their prediction errors, for
+        data beyond the size of the joint predictor.  Both processes at a site share one neighbourhood (with cross-validation
+        off it does not depend on the predicted process), so (pred_0, pred_1) is the simple-cokriging predictor from one data
+        subset and [[pred_err_0^2, pred_cov], [pred_cov, pred_err_1^2]] a genuine conditional covariance.  Returns what
+        ``joint_prediction.Predictor.predict_pair`` returns for one site set: ``pred_0``, ``pred_err_0``, ``pred_1``,
+        ``pred_err_1``, ``pred_cov`` and ``pred_corr`` (NaN where an error is 0); ``postprocess`` transforms each process as
+        ``__call__`` does and scales the covariance by the product of the two ``scale_fact``s.
+
+        A second site set (``pcoords1``) is refused: sites apart have different neighbourhoods, and a covariance between
+        predictions from different data subsets is the posterior covariance of nothing (the joint predictor has one).
+        Honours ``measurement_error=`` and ``max_neighbours=``; ``trend=`` raises NotImplementedError."""
+        if pcoords1 is not None:
+            raise ValueError("predict_pair in the moving neighbourhood takes one site set: two sites apart have different "
+                             "neighbourhoods, which give no posterior covariance between them (joint_prediction.Predictor."
+                             "predict_pair on a factored Sigma has one); call it once per site set")
+        if self.trend is not None:
+            raise NotImplementedError("the joint prediction of both processes in the moving neighbourhood is simple cokriging "
+                                      "only (trend=None)")
+        f0 = _JointPredictor._sites_frame(pcoords)
+        p0, e0, p1, e1, cov = self.predict_pair_arrays(f0.values[:, :2], max_dist=max_dist)
+        return _JointPredictor._pair_output(self, f0, None, p0, e0, p1, e1, cov, None, postprocess)
+
     # -- areal means in the moving neighbourhood ---------------------------------------------------
     _spatial_trend = _JointPredictor._spatial_trend   # what _postprocess_blocks reads of the class it is borrowed from
     _postprocess_predictions = _JointPredictor._postprocess_predictions   # and what _cv_frame does (cross_validation(folds=...))
@@ -316,18 +372,52 @@ class Predictor:
         return pd.DataFrame({"pred": pred, "pred_err": err, "n_sites": n_sites, "lat": lat, "lon": lon}, index=index)
 
     # -- conditional simulation in the moving neighbourhood ----------------------------------------
-    def conditional_draws_arrays(self, i: int, pcoords, max_dist: float, n_draws: int, seed=None, ordering="random", noise=None):
+    def _sim_sites(self, pcoords, what="pcoords"):
+        pc = np.atleast_2d(np.asarray(pcoords.values if isinstance(pcoords, pd.DataFrame) else pcoords, dtype=np.float64))
+        if pc.ndim != 2 or pc.shape[1] < 2 or len(pc) < 1:
+            raise ValueError(f"{what} must be [[lat, lon], ...] with at least one site")
+        return np.ascontiguousarray(pc[:, :2])
+
+    def _sim_pins(self, q, pc):
+        """The sites of process q that the native call does not simulate: (source, on_datum, datum_value) -- for every row the
+        first row with its coordinates, whether it lies on a datum of process q without measurement-error variance, and that
+        datum's value (NaN elsewhere)."""
+        m = len(pc)
+        pair = [("a", np.float64), ("b", np.float64)]
+        rows = pc.view(pair).ravel()
+        _, first, inv = np.unique(rows, return_index=True, return_inverse=True)
+        source = first[np.asarray(inv).ravel()]                 # caller's site -> the first row with its coordinates
+        f = self.mf.fields[q]
+        dc = np.ascontiguousarray(np.asarray(f.coords_main, dtype=np.float64)[:, :2])
+        dv = np.asarray(f.values_main, dtype=np.float64).ravel()
+        var, scales = resolve_measurement_error(self.measurement_error, self.noise_scale, self.mf.fields, self.devices)
+        exact = np.ones(len(dc), dtype=bool) if var is None or var[q] is None else ~(scales[q] * var[q] > 0.0)
+        drows = dc[exact].view(pair).ravel()
+        du, dfirst = np.unique(drows, return_index=True)
+        at = np.searchsorted(du, rows)
+        on_datum = (at < len(du)) & (du[np.minimum(at, max(len(du) - 1, 0))] == rows) if len(du) else np.zeros(m, dtype=bool)
+        datum_value = np.where(on_datum, dv[exact][dfirst[np.minimum(at, max(len(du) - 1, 0))]] if len(du) else 0.0, np.nan)
+        return source, on_datum, datum_value
+
+    def conditional_draws_arrays(self, i, pcoords, max_dist: float, n_draws: int, seed=None, ordering="random", noise=None,
+                                 pcoords1=None):
         """Draws of process ``i`` at ``pcoords`` by sequential simulation in the moving neighbourhood -- the numeric body of
         ``conditional_simulation`` (include/cokrige.h: ck_simulate_local; gstat's ``nsim`` with ``nmax`` / ``maxdist``).
+
+        ``i=(0, 1)``: the co-simulation of BOTH processes (ck_simulate_local_pair) -- process 0 at ``pcoords``, process 1 at
+        ``pcoords1`` (None: the same sites), stacked: column k is site k of process 0, column m0 + k site k of process 1.  A
+        stacked site is conditioned on the data and on the earlier stacked sites of either process, so every draw is a jointly
+        consistent pair of maps; two single calls give two independent ensembles.  ``noise`` is then (n_draws, m0 + m1) with
+        process 0's columns first, an array ``ordering`` holds m0 + m1 ranks, and "random" permutes the stacked sites.
 
         The sites are visited in ``ordering``: "random" (the default, ``np.random.default_rng(seed).permutation``), "hilbert"
         (along the library's Hilbert curve; far more levels of the recursion, so slower) or an array of m distinct integer ranks.
         Every site is conditioned on the data and on the sites visited before it, within ``max_dist`` and under the Predictor's
-        ``max_neighbours`` -- the cap counts data and already simulated sites of process ``i`` alike.  A conditioning set holds
+        ``max_neighbours`` -- the cap counts data and already simulated sites of a process alike.  A conditioning set holds
         at most 64 members: choose the caps or the radius accordingly.
 
-        Set aside before the native call, and counted in ``sim_info["n_pinned"]``: rows of ``pcoords`` that repeat an earlier
-        row (one random variable: they get the draws of the first occurrence) and sites on a datum of process ``i`` without
+        Set aside before the native call, and counted in ``sim_info["n_pinned"]``: rows of a process's sites that repeat an
+        earlier row (one random variable: they get the draws of the first occurrence) and sites on a datum of their process without
         measurement-error variance (every draw is that datum's value).  ``noise`` (n_draws, m) in the caller's sites replaces
         the device's Philox stream (a set-aside site's column is not used); that stream is keyed on ``seed`` and on the index
         among the sites that remain.  ``seed=None`` takes 64 bits from ``numpy.random.SeedSequence()``.
@@ -346,13 +436,23 @@ class Predictor:
             raise NotImplementedError(f"conditional simulation runs on one device; this predictor has devices={self.devices}")
         if self.trend is not None:
             raise NotImplementedError("conditional simulation in the moving neighbourhood is simple cokriging only (trend=None)")
-        if isinstance(i, bool) or not (isinstance(i, (int, np.integer)) and 0 <= int(i) < self.n_procs):
-            raise ValueError(f"process index {i!r} out of range for {self.n_procs} processes")
-        pc = np.atleast_2d(np.asarray(pcoords.values if isinstance(pcoords, pd.DataFrame) else pcoords, dtype=np.float64))
-        if pc.ndim != 2 or pc.shape[1] < 2 or len(pc) < 1:
-            raise ValueError("pcoords must be [[lat, lon], ...] with at least one site")
-        pc = np.ascontiguousarray(pc[:, :2])
-        m = len(pc)
+        joint = isinstance(i, (tuple, list))
+        if joint:
+            if tuple(i) != (0, 1) or any(isinstance(k, bool) for k in i):
+                raise ValueError(f"process index {i!r}: the joint form is i=(0, 1)")
+            if self.n_procs != 2:
+                raise ValueError(f"the co-simulation of both processes needs a model of two processes, not {self.n_procs}")
+            procs = [0, 1]
+            pcs = [self._sim_sites(pcoords)]
+            pcs.append(pcs[0] if pcoords1 is None else self._sim_sites(pcoords1, "pcoords1"))
+        else:
+            if isinstance(i, bool) or not (isinstance(i, (int, np.integer)) and 0 <= int(i) < self.n_procs):
+                raise ValueError(f"process index {i!r} out of range for {self.n_procs} processes")
+            if pcoords1 is not None:
+                raise ValueError("pcoords1 belongs to the joint form i=(0, 1)")
+            procs, pcs = [int(i)], [self._sim_sites(pcoords)]
+        offs = np.concatenate([[0], np.cumsum([len(pc) for pc in pcs])])
+        m = int(offs[-1])
         if isinstance(n_draws, bool) or not isinstance(n_draws, (int, np.integer)) or n_draws < 1:
             raise ValueError(f"n_draws must be an integer >= 1, not {n_draws!r}")
         n_draws = int(n_draws)
@@ -370,44 +470,43 @@ class Predictor:
         if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
             raise ValueError("seed must be an integer in [0, 2^64)")
         seed = int(seed)
-        # sites that repeat an earlier row: the draws of the first occurrence
-        pair = [("a", np.float64), ("b", np.float64)]
-        rows = pc.view(pair).ravel()
-        _, first, inv = np.unique(rows, return_index=True, return_inverse=True)
-        source = first[np.asarray(inv).ravel()]                 # caller's site -> the first row with its coordinates
-        # sites on a datum of process i that carries no measurement-error variance: the datum's value
-        f = self.mf.fields[i]
-        dc = np.ascontiguousarray(np.asarray(f.coords_main, dtype=np.float64)[:, :2])
-        dv = np.asarray(f.values_main, dtype=np.float64).ravel()
-        var, scales = resolve_measurement_error(self.measurement_error, self.noise_scale, self.mf.fields, self.devices)
-        exact = np.ones(len(dc), dtype=bool) if var is None or var[i] is None else ~(scales[i] * var[i] > 0.0)
-        drows = dc[exact].view(pair).ravel()
-        du, dfirst = np.unique(drows, return_index=True)
-        at = np.searchsorted(du, rows)
-        on_datum = (at < len(du)) & (du[np.minimum(at, max(len(du) - 1, 0))] == rows) if len(du) else np.zeros(m, dtype=bool)
-        datum_value = np.where(on_datum, dv[exact][dfirst[np.minimum(at, max(len(du) - 1, 0))]] if len(du) else 0.0, np.nan)
+        # per process: sites that repeat an earlier row, sites on a noise-free datum; everything below in stacked indices
+        pins = [self._sim_pins(q, pc) for q, pc in zip(procs, pcs)]
+        source = np.concatenate([offs[j] + pins[j][0] for j in range(len(procs))])
+        on_datum = np.concatenate([p[1] for p in pins])
+        datum_value = np.concatenate([p[2] for p in pins])
         free = np.flatnonzero((source == np.arange(m)) & ~on_datum)   # what the native call simulates, the caller's order
         pinned = np.ones(m, dtype=bool)
         pinned[free] = False
         was_cv, self.cv = self.cv, False   # the sites' ordinary prediction, whatever cross_validation left behind
         try:
-            pred, err = self.predict_arrays(i, pc, max_dist=max_dist)
+            parts = [self.predict_arrays(q, pc, max_dist=max_dist) for q, pc in zip(procs, pcs)]
         finally:
             self.cv = was_cv
+        pred, err = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
         draws = np.empty((n_draws, m))
         stats = dict(n_levels=0, n_empty=0, k_max=0, n_capped=0)
         if len(free):
+            allpc = np.vstack(pcs)
+            fq = [free[(free >= offs[j]) & (free < offs[j + 1])] for j in range(len(procs))]   # the free sites by process
             if isinstance(ordering, np.ndarray):
                 ranks = ordering[free]
             else:
-                ranks = ordering_ranks([pc[free]], ordering, seed % (2 ** 63))
+                ranks = ordering_ranks([allpc[f] for f in fq], ordering, seed % (2 ** 63))
             h = self._capped_handle()
             e = None if noise is None else np.ascontiguousarray(noise[:, free])
-            sub, info, stats = h.simulate_local(int(i), pc[free], ranks, float(max_dist), n_draws, seed=seed, noise=e, terms=False)
+            if joint:
+                sub, info, stats = h.simulate_local_pair(allpc[fq[0]], allpc[fq[1]], ranks, float(max_dist), n_draws, seed=seed, noise=e,
+                                                         terms=False)
+            else:
+                sub, info, stats = h.simulate_local(procs[0], allpc[free], ranks, float(max_dist), n_draws, seed=seed, noise=e,
+                                                    terms=False)
             self.timings = h.simulate_local_timings()
             if info != 0:
                 site = int(free[info - 1])
-                raise LinAlgError(f"the local system of site {site} {tuple(pc[site])} is not positive definite or leaves no "
+                j = int(np.searchsorted(offs, site, side="right") - 1)
+                raise LinAlgError(f"the local system of site {site - int(offs[j])} {tuple(allpc[site])}"
+                                  + (f" of process {procs[j]}" if joint else "") + " is not positive definite or leaves no "
                                   "variance: nearly coincident sites, or a site nearly on a noise-free datum")
             draws[:, free] = sub
         on = np.flatnonzero(on_datum)
@@ -418,25 +517,31 @@ class Predictor:
                              n_empty=stats["n_empty"], n_pinned=int(pinned.sum()), k_max=stats["k_max"], n_capped=stats["n_capped"])
         return draws, pred, err, pinned, seed
 
-    def conditional_simulation(self, i: int, pcoords, max_dist: float = 1e3, n_draws: int = 100, seed=None, ordering="random",
-                               postprocess: bool = True, noise=None):
+    def conditional_simulation(self, i, pcoords, max_dist: float = 1e3, n_draws: int = 100, seed=None, ordering="random",
+                               postprocess: bool = True, noise=None, pcoords1=None):
         """Ensembles of maps of process ``i`` at ``pcoords`` drawn in the moving neighbourhood: the draws that the joint
         predictor's ``conditional_simulation`` gives from the dense factor, for data and grids beyond its size -- exceedance
         probabilities, areas above a threshold, ensembles for downstream models.  Returns what the joint method returns: an
         xarray Dataset with ``pred``, ``pred_err`` and ``draws`` (a leading ``draw`` dimension), ``attrs`` holding ``seed``,
         ``ordering``, ``n_levels``, ``n_empty`` and ``n_pinned``; ``postprocess=True`` applies ``_postprocess_predictions``'
-        transform to every draw.  Without xarray: ``(DataFrame, draws)``.  See ``conditional_draws_arrays`` for the arguments
-        and for how the ensemble mean relates to ``pred``."""
-        if not isinstance(pcoords, pd.DataFrame):
-            a = np.atleast_2d(np.asarray(pcoords, dtype=np.float64))
-            if a.ndim != 2 or a.shape[1] < 2:
-                raise ValueError("pcoords must be [[lat, lon], ...]")
-            pcoords = pd.DataFrame({"d1": a[:, 0], "d2": a[:, 1]})
-        draws, pred, err, _, seed = self.conditional_draws_arrays(i, pcoords.values[:, :2], max_dist, n_draws, seed=seed,
-                                                                  ordering=ordering, noise=noise)
-        return _JointPredictor._draws_output(self, i, pcoords, draws, pred, err,
-                                             {k: self.sim_info[k] for k in ("seed", "ordering", "n_levels", "n_empty", "n_pinned")},
-                                             postprocess)
+        transform to every draw.  Without xarray: ``(DataFrame, draws)``.  ``i=(0, 1)``: the co-simulation of both processes,
+        process 1 at ``pcoords1`` (None: the same sites); the result is the pair ``(out_0, out_1)``, each as for one process,
+        draw d of both being one jointly consistent pair of maps.  See ``conditional_draws_arrays`` for the arguments and for
+        how the ensemble mean relates to ``pred``."""
+        frames = [_JointPredictor._sites_frame(pcoords)]
+        joint = isinstance(i, (tuple, list))
+        if joint:
+            frames.append(frames[0] if pcoords1 is None else _JointPredictor._sites_frame(pcoords1))
+        draws, pred, err, _, seed = self.conditional_draws_arrays(i, frames[0].values[:, :2], max_dist, n_draws, seed=seed,
+                                                                  ordering=ordering, noise=noise,
+                                                                  pcoords1=None if pcoords1 is None else frames[1].values[:, :2])
+        attrs = {k: self.sim_info[k] for k in ("seed", "ordering", "n_levels", "n_empty", "n_pinned")}
+        if not joint:
+            return _JointPredictor._draws_output(self, i, frames[0], draws, pred, err, attrs, postprocess)
+        m0 = len(frames[0])
+        cut = [slice(0, m0), slice(m0, None)]
+        return tuple(_JointPredictor._draws_output(self, q, frames[q], draws[:, cut[q]], pred[cut[q]], err[cut[q]], attrs, postprocess)
+                     for q in range(2))
 
     def cross_validation(self, i: int, max_dist: float = 1e3, partitions: int = None,
                          postprocess: bool = True, folds=None, also_withhold=None, buffer=None, seed: int = 0) -> pd.DataFrame:
